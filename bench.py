@@ -12,7 +12,12 @@ The data matrix is generated in HBM on rank 0 and handed to that rank's chain, w
 it into bit planes; the planes (160 MB, not the 4 GB int32 matrix) are broadcast once over
 RCCL -- the only collective on this path; chains are independent, so scaling is weak.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps sweeps and prints the
+headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`, and `multi_gpu`
+for N > 1).  Everything else below is measured only with --full:
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+--dump-outputs DIR writes what the timed chain holds after its last sweep (see dump_outputs).
+
   roofline       the dominant kernel, k_resample, timed with HIP events on the chain's own stream
                  inside the timed region.  `achieved` / `peak` / `frac` are SURVEY.md section 8d's figure:
                  algorithmic bytes of the layout actually streamed (bit planes: 4*ceil(P/32) + 8 bytes per
@@ -95,6 +100,40 @@ def socket_cores():
     return cores or avail, avail
 
 
+DUMP_LABEL_BYTES = 48 << 20   # labels of all chains; the statistics beside them stay well inside 64 MB in all
+
+
+def dump_outputs(out_dir, chains, first=0, total=None, write_index=True):
+    """--dump-outputs: what a caller of the timed path receives from a resident chain after its last sweep, one
+    DIR/<name>.npy per array -- `labels` (1-based, as bmm_chain_get_labels returns them) in float32 (exact: at
+    most maxK), `cluster_sizes` (K), `feature_counts` (K x P), `alpha`, and `pi` / `theta` for the samplers that
+    carry them, in float64.  Chains are numbered from `first` of `total`; with more than one chain in the job
+    every name is prefixed `chain<c>_`.  The labels are kept whole while those of all chains fit in 48 MB;
+    beyond that every chain keeps the same seeded sample of observations, whose (0-based) indices are written
+    as `labels_index`."""
+    import numpy as np
+    total = len(chains) if total is None else total
+    os.makedirs(out_dir, exist_ok=True)
+    N = chains[0].N
+    keep = max(1, DUMP_LABEL_BYTES // (4 * total))
+    idx = None
+    if N > keep:
+        idx = np.sort(np.random.default_rng(20240601).choice(N, keep, replace=False))
+        if write_index:
+            np.save(os.path.join(out_dir, "labels_index.npy"), idx.astype(np.float64))
+    for c, ch in enumerate(chains):
+        pre = "chain%d_" % (first + c) if total > 1 else ""
+        z = ch.labels()
+        Nk, S = ch.counts()
+        arrays = {"labels": (z if idx is None else z[idx]).astype(np.float32),
+                  "cluster_sizes": Nk.astype(np.float64), "feature_counts": S.astype(np.float64),
+                  "alpha": np.array([ch.alpha()], dtype=np.float64)}
+        if ch.sampler in ("stickbreaking", "full"):
+            arrays["pi"], arrays["theta"] = ch.params()
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, pre + name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -123,6 +162,11 @@ def main():
                          "only; strong scaling, one all-reduce of the statistics per sweep)")
     ap.add_argument("--cpu-rows", type=int, default=1_000_000)
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU time of a baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: roofline (HIP events around the resample "
+                         "launches), copy-kernel rate, from_random_start, cpu_baseline, other_workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed sweeps, write what the timed chain(s) hold as DIR/<name>.npy")
     args = ap.parse_args()
 
     import numpy as np
@@ -224,8 +268,9 @@ def main():
         for c in chains:
             c.sync()
         # HIP events around the resample launches of every 4th timed sweep: the per-launch average
-        # is what the roofline needs, and 16 event records per sweep would cost ~7 % of the sweep
-        ch.profile(0 if args.no_events else args.event_stride)
+        # is what the roofline needs, and 16 event records per sweep would cost ~7 % of the sweep.
+        # Only --full reports a roofline; a plain run times the sweeps alone
+        ch.profile(args.event_stride if (args.full and not args.no_events) else 0)
         barrier()
         t0 = time.perf_counter()
         run(steps)
@@ -410,11 +455,14 @@ def main():
 
     if args.shard:
         return bench_sharded(args, world, rank, local, dev, barrier)
-    rs = 3 if (args.workload in ("c5", "ns", "c2") and args.chains_per_gpu == 1 and args.x_layout == "bits") else 0
+    rs = 3 if (args.full and args.workload in ("c5", "ns", "c2") and args.chains_per_gpu == 1
+               and args.x_layout == "bits") else 0
     m = measure(args.workload, args.steps, args.warmup, args.burn, args.batch, args.rows, args.k, args.x_layout,
                 nchains=args.chains_per_gpu, random_start=rs)
     sampler, K, N, P, batch = m["sampler"], m["K"], m["N"], m["P"], m["batch"]
     dt, nch = m["dt"], m["nchains"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["chains"], first=rank * nch, total=world * nch, write_index=rank == 0)
 
     result = None
     if rank == 0:
@@ -440,8 +488,9 @@ def main():
                        "x_layout": ("bit planes, ceil(P/32) words per observation, packed once at hand-over"
                                     if layout == "bits" else "int32 column-major (as R hands it over)"),
                        "allocations_per_s": world * nch * args.steps * N / dt},
-            "roofline": roofline_of(m, args.steps, key),
         }
+        if args.full:
+            result["roofline"] = roofline_of(m, args.steps, key)
         if world > 1:
             seen = m["ranks_seen"]
             result["multi_gpu"] = {
@@ -459,24 +508,25 @@ def main():
                 "sweeps_per_s": m["first"],
                 "note": "the first 3 sweeps of the chain from a uniformly random allocation (every observation "
                         "moves, every statistic cell is flushed); `value` is the steady state after %d sweeps" % args.burn}
-        copy_gbps = copy_rate() if world == 1 else None
+        copy_gbps = copy_rate() if (args.full and world == 1) else None
         if copy_gbps and result["roofline"]:
             result["roofline"]["copy_kernel_GBps"] = copy_gbps
-        if not args.no_cpu and world == 1 and m["X"] is not None:
+        if args.full and not args.no_cpu and world == 1 and m["X"] is not None:
             result["cpu_baseline"] = cpu_leg(sampler, m["X"], K, N, batch, args.workload)
             result["config"]["gpu_over_cpu"] = result["value"] / result["cpu_baseline"]["value"]
+    # the other BASELINE points, the int32 kernel and the drop-in call, measured in the same run (--full, single
+    # GPU only).  Reported beside the headline, never instead of it.
+    extras = (args.full and world == 1 and not args.no_extra and args.workload == "c5" and not (args.rows or args.k)
+              and args.chains_per_gpu == 1)
     c5_e2e = None
-    if (world == 1 and not args.no_extra and args.workload == "c5" and not (args.rows or args.k) and args.chains_per_gpu == 1
-            and m["X"] is not None and sampler == "collapsed"):
+    if extras and m["X"] is not None and sampler == "collapsed":
         # C5 through the drop-in call: the same matrix, copied to the host (N x P column-major as R holds it)
         Xh = m["X"].t().cpu().numpy()
         c5_e2e = end_to_end(Xh, K, 30, 3, "gibbs_collapsed(host X 4 GB in, 30 sweeps, 27 kept: S x N trace 1.08 GB out) at C5, PCIe included")
         del Xh
     close(m)
     del m
-    # the other BASELINE points, measured in the same run (single GPU only).  Reported beside the
-    # headline, never instead of it.
-    if world == 1 and not args.no_extra and args.workload == "c5" and not (args.rows or args.k) and args.chains_per_gpu == 1:
+    if extras:
         extra = {}
         if args.x_layout == "bits":
             # the kernel that streams the int32 matrix in place: the HBM-roofline measurement proper
@@ -580,6 +630,8 @@ def bench_native(args):
     for ch in chains:
         ch.sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, chains)
     print(json.dumps({
         "metric": "gibbs_sweeps_per_s", "value": n * args.steps / dt, "unit": "sweeps/s", "n_gpus": n,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
@@ -604,6 +656,8 @@ def bench_sharded(args, world, rank, local, dev, barrier):
     sampler, K, K_true, N, P, dseed = synth.WORKLOADS[args.workload]
     if sampler not in ("stickbreaking", "full"):
         raise SystemExit("--shard needs a stick-breaking or full workload (e.g. --workload c4)")
+    if args.dump_outputs:
+        raise SystemExit("--dump-outputs is not available with --shard (every rank holds only its rows' labels)")
     if args.rows:
         N = args.rows
     X, _ = synth.device_matrix(N, P, K_true, dseed, dev)      # same seed => same matrix on every rank

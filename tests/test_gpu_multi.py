@@ -234,7 +234,8 @@ def test_multi_device_bookkeeping_on_fake_devices(oracle, dbg_lib):
 
 @pytest.mark.timeout(600)
 def test_bench_line_contract_on_one_gpu():
-    """the ONE JSON line `python bench.py` prints: the keys the driver reads, the roofline and cpu_baseline objects"""
+    """the ONE JSON line `python bench.py --full` prints: the keys the driver reads, the roofline and cpu_baseline
+    objects"""
     import json
     import os
     import subprocess
@@ -242,7 +243,7 @@ def test_bench_line_contract_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c2", "--steps", "8", "--warmup", "2", "--burn", "4",
-                        "--no-extra", "--cpu-seconds", "1", "--cpu-rows", "20000"], capture_output=True, text=True, timeout=500,
+                        "--full", "--no-extra", "--cpu-seconds", "1", "--cpu-rows", "20000"], capture_output=True, text=True, timeout=500,
                        env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -263,3 +264,39 @@ def test_bench_line_contract_on_one_gpu():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in cb, k
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0
+
+
+@pytest.mark.timeout(600)
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """a plain `python bench.py` run prints the headline alone (the side measurements are --full's), and
+    --dump-outputs writes the timed chain's state after its last sweep: the same arrays from run to run"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    got = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", "7",
+                            "--warmup", "2", "--burn", "4", "--dump-outputs", str(out)], capture_output=True, text=True,
+                           timeout=500, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"], d["steps"], d["warmup"]) == (
+            "gibbs_sweeps_per_s", "sweeps/s", True, "f64", 7, 2)
+        assert abs(d["value"] - 7 / (d["ms_per_step"] * 7e-3)) < 1e-6 * d["value"]
+        for k in ("roofline", "cpu_baseline", "other_workloads", "from_random_start"):
+            assert k not in d, k
+        arrays = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert set(arrays) == {"labels", "cluster_sizes", "feature_counts", "alpha"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        z, nk, s = arrays["labels"], arrays["cluster_sizes"], arrays["feature_counts"]
+        assert z.shape == (100_000,) and s.shape == (3, 20) and z.min() >= 1 and z.max() <= 3
+        assert np.array_equal(nk, np.bincount(z.astype(np.int64) - 1, minlength=3))
+        got.append(arrays)
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k

@@ -3,10 +3,11 @@
 * r-shim/bmmmcmc_shim.c passes `gcc -fsyntax-only -Wall -Wextra -Werror` against test-only declarations of
   the R API symbols it uses (tests/r_api_stub: declarations, nothing linked or run);
 * its registration table carries the reference's seven .Call entries name for name and arity for
-  arity.  REFERENCE_TABLE is /root/reference/src/RcppExports.cpp:137-146 committed as constants (the
-  reference is not on the GPU box; where it is present the constants are re-read from it);
+  arity.  REFERENCE_TABLE is src/RcppExports.cpp:137-146 of the reference committed as constants, checked
+  against the names and arities stored in tests/golden/reference_registration.json;
 * the R wrappers pass the *_ex entry points exactly as many arguments as the shim registers.
 """
+import json
 import os
 import re
 import shutil
@@ -17,6 +18,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "bmm-mcmc_amd", "r-shim", "bmmmcmc_shim.c")
 WRAPPERS = os.path.join(ROOT, "bmm-mcmc_amd", "R", "gibbs.R")
+REGISTRATION = os.path.join(ROOT, "tests", "golden", "reference_registration.json")
 
 # src/RcppExports.cpp:137-146 of stulacy/bmm-mcmc
 REFERENCE_TABLE = {
@@ -105,12 +107,15 @@ def test_registered_arity_is_the_defined_arity():
         assert defs[fn] == arity, (name, defs[fn], arity)
 
 
+def _registration():
+    with open(REGISTRATION) as f:
+        return json.load(f)
+
+
 def test_constants_are_the_reference_registration_table():
-    ref = "/root/reference/src/RcppExports.cpp"
-    if not os.path.exists(ref):
-        pytest.skip("the reference is not on this machine; REFERENCE_TABLE is its committed copy")
-    got = {k: v[1] for k, v in _table(ref).items()}
-    assert got == REFERENCE_TABLE
+    entries = _registration()["call_entries"]
+    assert [(e["name"], e["arity"]) for e in entries] == list(REFERENCE_TABLE.items())
+    assert all(e["function"] == e["name"] for e in entries)
 
 
 def test_r_wrappers_pass_what_the_shim_registers():
@@ -121,9 +126,4 @@ def test_r_wrappers_pass_what_the_shim_registers():
         args = [a for a in re.sub(r"\([^()]*\)", "", m.group(1)).split(",") if a.strip()]
         assert len(args) == arity, (name, len(args), arity)
     # and the unchanged R/RcppExports.R of the reference calls the *_cpp names with the reference arities
-    ref = "/root/reference/R/RcppExports.R"
-    if os.path.exists(ref):
-        rsrc = open(ref).read()
-        for name, arity in REFERENCE_TABLE.items():
-            m = re.search(r"\.Call\('%s', PACKAGE = 'bmmmcmc'(.*?)\)\n" % name, rsrc)
-            assert m and len([a for a in m.group(1).split(",") if a.strip()]) == arity
+    assert _registration()["r_call_arguments"] == REFERENCE_TABLE

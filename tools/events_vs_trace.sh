@@ -6,7 +6,7 @@ REPO=$(dirname $(dirname $(readlink -f $0)))
 OUT=$REPO/gpurun_out/evt_$$
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o trace -- python3 $REPO/bench.py --no-cpu --no-extra "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o trace -- python3 $REPO/bench.py --full --no-cpu --no-extra "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python3 - "$OUT" <<'PY'
 import csv, glob, json, sys
 out = sys.argv[1]

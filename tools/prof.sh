@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run() { # name, rocprof args...
   local name=$1; shift
-  timeout -k 10 240 rocprofv3 "$@" --output-format csv -d $OUT/$name -o $name -- python3 $REPO/bench.py --no-cpu $BENCH_ARGS > $OUT/$name.log 2>&1 || { echo "pass $name failed"; tail -5 $OUT/$name.log; return 1; }
+  timeout -k 10 240 rocprofv3 "$@" --output-format csv -d $OUT/$name -o $name -- python3 $REPO/bench.py --full --no-cpu $BENCH_ARGS > $OUT/$name.log 2>&1 || { echo "pass $name failed"; tail -5 $OUT/$name.log; return 1; }
 }
 BENCH_ARGS="$*"
 run trace --kernel-trace --stats &&
