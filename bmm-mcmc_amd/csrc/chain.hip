@@ -1234,6 +1234,13 @@ int bmm_chain_create(bmm_chain** out, int sampler, int64_t N, int P, int K, doub
         c->grid_max = (int)(threads / 256);
     } else {
         c->num_cus = cus;
+        // test variant (BMM_DEBUG_CUS=n, n >= 1): the kernel choice sees n compute units -- the grid limits, the
+        // short-launch and step-down rules -- so that test-sized batches reach the default-sized kernels and give
+        // a wave several chunks (tests/test_gpu_chunks.py).  The device itself is not asked again.
+        if (const char* v = dbg_env("BMM_DEBUG_CUS")) {
+            const int n = atoi(v);
+            if (n >= 1) c->num_cus = n;
+        }
         rc = pick_kernel(c);
         if (rc) { delete c; return rc; }
     }
@@ -2049,6 +2056,25 @@ extern "C" int bmm_dbg_host_labels(const void* src, int narrow, int32_t* dst, in
         }
         return BMM_OK;
     });
+}
+// Test variant only: which k_resample instantiation the chain's launches run -- accumulators, workgroup size, lanes
+// per observation, own-cluster tier (0 none, 1 LDS, 2 global memory), X layout (1 bit planes), group width, whether
+// it builds its own tables, the weight-emitting twin's workgroup size (as set up by the first hand-off; before that
+// the size it will get, 0 where there is none and the hand-off runs the generic kernel), whether the chain is on the generic kernel altogether, and the emitting twin's grid limit (0 until a
+// hand-off has set the twin up) (tests/test_gpu_chunks.py)
+extern "C" int bmm_dbg_kernel_key(const bmm_chain* c, int* key) {
+    if (!c || !key) return set_err(BMM_E_ARG, "null argument");
+    key[0] = c->p.KT;
+    key[1] = c->NT;
+    key[2] = c->generic || c->OT <= 0 ? 1 : c->NT / c->OT;
+    key[3] = explicit_params(c->p.mode) ? 0 : (c->minus_in_lds ? 1 : 2);
+    key[4] = c->bits ? 1 : 0;
+    key[5] = c->p.W;
+    key[6] = c->self_tables ? 1 : 0;
+    key[7] = c->fn_emit ? c->NT_emit : (c->bits && !c->generic ? threads_for(c->p.KT, true) : 0);
+    key[8] = c->generic ? 1 : 0;
+    key[9] = c->fn_emit ? c->grid_max_emit : 0;
+    return BMM_OK;
 }
 #endif
 

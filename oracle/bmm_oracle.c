@@ -26,7 +26,7 @@ int oracle_group_width_own(void) { return GWM; }
  * cluster sizes, the 256-entry exponential table, for the counting samplers the own-cluster tables (groups
  * of 3, padded to a multiple of 6 groups) -- and the integer histogram fit in 160 KiB; 4 otherwise. */
 int oracle_group_width_for(int sampler, int K, int P) {
-    static const int kts[] = {4, 8, 12, 16, 20, 24, 28, 32, 40, 48, 56, 64};
+    static const int kts[] = {4, 8, 12, 16, 20, 24, 28, 32, 40, 48, 52, 56, 64};  /* the library's kKT */
     const int cats = sampler == 1 ? K + 1 : K;
     int KT = -1;
     for (unsigned q = 0; q < sizeof kts / sizeof kts[0]; ++q) if (kts[q] >= cats) { KT = kts[q]; break; }

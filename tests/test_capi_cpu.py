@@ -112,7 +112,7 @@ def test_group_width_rule_is_the_oracles(oracle):
     seen = set()
     for sampler in range(4):
         for K in (1, 2, 3, 4, 5, 12, 19, 20, 21, 24, 29, 30, 31, 32, 33, 40, 47, 48, 50, 56, 63, 64, 65, 100):
-            for P in (1, 5, 20, 31, 32, 33, 50, 64, 65, 96, 100, 101, 110, 127, 128, 129, 513):
+            for P in (1, 5, 20, 31, 32, 33, 36, 50, 52, 53, 64, 65, 96, 100, 101, 110, 127, 128, 129, 513):
                 w = L.bmm_spec_group_width_for(sampler, K, P)
                 assert w == O.oracle_group_width_for(sampler, K, P), (sampler, K, P)
                 seen.add(w)
@@ -121,6 +121,9 @@ def test_group_width_rule_is_the_oracles(oracle):
     assert L.bmm_spec_group_width_for(2, 50, 50) == 5 and L.bmm_spec_group_width_for(0, 3, 20) == 5    # C4, C2
     assert L.bmm_spec_group_width_for(0, 20, 128) == 4 and L.bmm_spec_group_width_for(2, 64, 64) == 4
     assert L.bmm_spec_group_width_for(7, 3, 3) == -1
+    # 49-52 categories: tables of 52 accumulators, where 56 would need the narrower groups
+    for sampler, K, P, w in ((0, 50, 36, 5), (2, 50, 52, 5), (3, 52, 55, 5), (1, 50, 36, 5)):
+        assert L.bmm_spec_group_width_for(sampler, K, P) == O.oracle_group_width_for(sampler, K, P) == w, (sampler, K, P)
 
 
 def test_multi_run_placement_is_pure_bookkeeping():

@@ -67,12 +67,18 @@ def test_run_entry_points_under_both_layouts(oracle, dbg_lib, env):
 def test_the_product_library_ignores_the_steering_environment(oracle, monkeypatch):
     """The product build reads no environment: with every switch set, a *_run call still runs the
     bit-plane resident kernel (same chain either way, so this is seen in the layout it reports)."""
-    for k in ("BMM_X_LAYOUT_INT32", "BMM_DEBUG_GENERIC", "BMM_DEBUG_NOSPLIT"):
+    for k in ("BMM_X_LAYOUT_INT32", "BMM_DEBUG_GENERIC", "BMM_DEBUG_NOSPLIT", "BMM_DEBUG_CUS"):
         monkeypatch.setenv(k, "1")
     monkeypatch.setenv("BMM_DEBUG_THREADS", "512")
     with bm.Chain("collapsed", 500, 8, 2, seed=1) as c:
         assert c.x_layout() == "bits"
         assert c.kernel_shape()["lds_bytes"] > 0   # resident kernel, not the generic path
+    # nor the CU count the kernel choice sees (BMM_DEBUG_CUS): the grid limit is the real device's
+    with bm.Chain("collapsed", 500_000, 50, 20, seed=1) as c:
+        with_env = c.kernel_shape()["grid_max"]
+    monkeypatch.delenv("BMM_DEBUG_CUS", raising=False)
+    with bm.Chain("collapsed", 500_000, 50, 20, seed=1) as c:
+        assert c.kernel_shape()["grid_max"] == with_env
 
 
 def test_layout_is_fixed_once_the_data_are_set():
