@@ -19,7 +19,8 @@ from ._capi import BmmError, NA_INTEGER
 from .rdata import read_rdata_matrix  # the package's bundled data sets (data/*.RData) without R
 
 __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "Chain", "BmmError", "NA_INTEGER", "set_progress",
-           "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA"]
+           "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
+           "stephens_batch", "stephens_online", "DeviceStephens", "STEPHENS_MAX_K"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -70,9 +71,9 @@ class _Relabel:
     def __init__(self, stephens, N, K, nsamples, burnin, burnrelabel):
         if stephens is None:
             raise NotImplementedError(
-                "relabel=TRUE runs Stephens' relabelling (src/stephens.cpp, src/my_lpsolve.cpp) on the host, and "
-                "that code stays in the reference package: pass stephens=<object with batch(p) and "
-                "online(Q, p, j)> bound to it; this build supplies the probability matrices it consumes")
+                "relabel=TRUE needs Stephens' relabelling (src/stephens.cpp, src/my_lpsolve.cpp): pass "
+                "stephens=\"device\" to run it on the device, or stephens=<object with batch(p) and "
+                "online(Q, p, j)> to run host code of your own on the probability matrices this build supplies")
         self.st, self.N, self.K, self.burnin = stephens, N, K, burnin
         self.S = nsamples - burnin
         self.W = max(0, int(burnrelabel))
@@ -118,6 +119,95 @@ class _Relabel:
             thr[pm, :, s] = theta[:, :, s]    # thetas_relab(perm(k), d, j) = theta(k, d, j)     (:216)
         out.update(permutations=self.perms, z=zr, theta=thr, z_original=z, theta_original=theta)
         return out
+
+
+# ---------------------------------------------------------------- relabel = TRUE, Stephens on the device
+STEPHENS_MAX_K = 128  # include/bmm_mcmc.h BMM_STEPHENS_MAX_K
+
+
+class _RelabelOut(_C.Structure):  # bmm_relabel_out
+    _fields_ = [("burnrelabel", _C.c_int), ("permutations", _C.c_void_p), ("z_original", _C.c_void_p),
+                ("theta_original", _C.c_void_p)]
+
+
+def _device_relabel(stephens, relabel, burnin, burnrelabel):
+    """stephens="device" with relabel=True: checked before any device is touched.  The reference has no Q
+    unless the batch step runs at sweep burnin - 1 over at least one sweep (collapsed_gibbs.cpp:187-190)."""
+    if isinstance(stephens, str):
+        if stephens != "device":
+            raise ValueError('stephens must be "device", None or an object with batch() and online()')
+        if not relabel:
+            return False
+        if burnin < 2 or burnrelabel < 1:
+            raise ValueError("relabel on the device needs the batch step: burnin >= 2 and burnrelabel >= 1 "
+                             "(burnin = %d, burnrelabel = %d)" % (burnin, burnrelabel))
+        return True
+    return False
+
+
+class _DeviceRelabelRun:
+    """Outputs of a bmm_*_run_relabel call, laid out as the reference's list (collapsed_gibbs.cpp:232-243)."""
+
+    def __init__(self, N, K, P, S, W):
+        self.perms = _np.empty((S, K), dtype=_np.int32, order="F")
+        self.z_orig = _np.empty((S, N), dtype=_np.int32, order="F")
+        self.th_orig = _np.zeros((K, P, S), order="F")
+        self.s = _RelabelOut(int(W), self.perms.ctypes.data, self.z_orig.ctypes.data, self.th_orig.ctypes.data)
+
+    def ref(self):
+        return _C.byref(self.s)
+
+    def finish(self, rc, out):
+        _capi.check(rc)
+        out.update(permutations=self.perms, z=out["z"], theta=out["theta"], z_original=self.z_orig,
+                   theta_original=self.th_orig)
+        return out
+
+
+def stephens_batch(p, device=0):
+    """my_stephens_batch (src/stephens.cpp:6-66) on the device: p is an N x K x M cube of allocation
+    probabilities; returns (Q, perm) -- Q (N x K) the one computed at the start of the last of the 100
+    iterations, perm (M x K, 0-based) that iteration's permutations."""
+    p = _np.asfortranarray(p, dtype=_np.float64)
+    if p.ndim != 3:
+        raise ValueError("p must be an N x K x M cube")
+    N, K, M = p.shape
+    Q = _np.zeros((N, K), order="F")
+    perm = _np.zeros((M, K), dtype=_np.int32, order="F")
+    _capi.check(_capi.lib().bmm_device_stephens_batch(_C.c_int(device), _capi.vp(p), _C.c_int64(N), _C.c_int(K),
+                                                      _C.c_int(M), _capi.vp(Q), _capi.vp(perm)))
+    return Q, perm
+
+
+def stephens_online(Q, p, j, device=0, with_cost=False):
+    """my_stephens_online (src/stephens.cpp:68-94) on the device for sweep j: returns (perm, Q_new), and the
+    K x K cost matrix the assignment was solved on with with_cost=True."""
+    Q = _np.asfortranarray(Q, dtype=_np.float64)
+    p = _np.asfortranarray(p, dtype=_np.float64)
+    if p.ndim != 2 or Q.shape != p.shape:
+        raise ValueError("Q and p must both be N x K")
+    N, K = p.shape
+    perm = _np.zeros(K, dtype=_np.int32)
+    Qn = _np.zeros((N, K), order="F")
+    C = _np.zeros((K, K), order="F")
+    _capi.check(_capi.lib().bmm_device_stephens_online(_C.c_int(device), _capi.vp(Q), _capi.vp(p), _C.c_int64(N),
+                                                       _C.c_int(K), _C.c_int(int(j)), _capi.vp(perm), _capi.vp(Qn),
+                                                       _capi.vp(C)))
+    return (perm, Qn, C) if with_cost else (perm, Qn)
+
+
+class DeviceStephens:
+    """The two functions of src/stephens.h on a device, for the hook path (stephens=DeviceStephens(0)): each call
+    moves its inputs over PCIe.  stephens="device" keeps the whole relabelling resident instead."""
+
+    def __init__(self, device=0):
+        self.device = int(device)
+
+    def batch(self, p):
+        return stephens_batch(p, self.device)[0]
+
+    def online(self, Q, p, j):
+        return stephens_online(Q, p, j, self.device)
 
 
 # ---------------------------------------------------------------- progress ("Sample j", as the reference prints it)
@@ -210,8 +300,9 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     RNG), `batch` (observations resampled per frozen-statistics batch; 1 = the reference's
     sequential scan; None = library default), `device`, `initial_K` (1-based labels; default
     sampled uniformly as R/utils.R:42 does), `chains` / `devices` (several independent chains,
-    seed + c, in one call: returns a list of chain objects), `stephens` (the host relabelling
-    code for relabel=True, see _Relabel).
+    seed + c, in one call: returns a list of chain objects), `stephens` (relabel=True: "device" runs
+    Stephens' relabelling on the device; an object with batch / online runs host code on the hook
+    path, see _Relabel).
     """
     X = _capi.as_x(data)
     N, P = X.shape
@@ -232,7 +323,20 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     if z0.shape != (N,):
         raise ValueError("initial_K must have one label per observation")
     S = nsamples - burnin
-    rl = _Relabel(stephens, N, K, nsamples, burnin, _clamp_burnrelabel(burnrelabel, burnin)) if relabel else None
+    W = _clamp_burnrelabel(burnrelabel, burnin)
+    if _device_relabel(stephens, relabel, burnin, W):
+        dr = _DeviceRelabelRun(N, K, P, S, W)
+        z = _np.empty((S, N), dtype=_np.int32, order="F")
+        theta = _np.zeros((K, P, S), order="F")
+        al = _np.zeros((S, 1), order="F")
+        with _progress(debug):
+            rc = _capi.lib().bmm_collapsed_run_relabel(
+                _capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(K),
+                _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
+                _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
+                _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al), dr.ref())
+        return dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta})
+    rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((K, P, S), order="F")
     al = _np.zeros((S, 1), order="F")
@@ -266,7 +370,21 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
         return _multi("dp", X, int(chains), devices, None, None, None, nsamples, maxK, alpha, beta, gamma, a, b,
                       burnin, batch, seed, False)
     S = nsamples - burnin
-    rl = _Relabel(stephens, N, maxK, nsamples, burnin, _clamp_burnrelabel(burnrelabel, burnin)) if relabel else None
+    W = _clamp_burnrelabel(burnrelabel, burnin)
+    if _device_relabel(stephens, relabel, burnin, W):
+        dr = _DeviceRelabelRun(N, maxK, P, S, W)
+        z = _np.empty((S, N), dtype=_np.int32, order="F")
+        theta = _np.zeros((maxK, P, S), order="F")
+        al = _np.zeros((S, 1), order="F")
+        with _progress(debug):
+            rc = _capi.lib().bmm_dp_run_relabel(
+                _capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(nsamples),
+                _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
+                _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int(maxK),
+                _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
+                _capi.vp(theta), _capi.vp(al), dr.ref())
+        return dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta})
+    rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((maxK, P, S), order="F")
     al = _np.zeros((S, 1), order="F")
@@ -306,6 +424,8 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             raise ValueError("initial_pi must have K entries and initial_theta be K x P")
         return pi, th
 
+    S = nsamples - burnin
+    W = _clamp_burnrelabel(burnrelabel, burnin) if clamp else int(burnrelabel)  # R/utils.R:97-101 has no clamp
     if chains > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
@@ -313,9 +433,21 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
                     initial_theta[c] if initial_theta is not None else None) for c in range(chains)]
         return _multi(sampler, X, chains, devices, None, [p for p, _ in st], [t for _, t in st], nsamples, K,
                       alpha, beta, gamma, a, b, burnin, None, seed, True)
+    on_device = _device_relabel(stephens, relabel, burnin, W)
     pi0, th0 = start(seed, initial_pi, initial_theta)
-    S = nsamples - burnin
-    W = _clamp_burnrelabel(burnrelabel, burnin) if clamp else int(burnrelabel)  # R/utils.R:97-101 has no clamp
+    if on_device:
+        dr = _DeviceRelabelRun(N, K, P, S, W)
+        z = _np.empty((S, N), dtype=_np.int32, order="F")
+        theta = _np.zeros((K, P, S), order="F")
+        al = _np.zeros((S, 1), order="F")
+        pi = _np.zeros((S, K), order="F")
+        with _progress(debug):
+            rc = getattr(_capi.lib(), fn.replace("_probs", "_relabel"))(
+                _capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(pi0), _capi.vp(th0), _C.c_int(nsamples),
+                _C.c_int(K), _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta),
+                _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
+                _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al), dr.ref())
+        return dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta})
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((K, P, S), order="F")

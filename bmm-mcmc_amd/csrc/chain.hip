@@ -1747,6 +1747,178 @@ int run_prepare(bmm_chain* c, int nsamples, int burnin) {
     return BMM_OK;
 }
 
+// ---- Stephens' relabelling on the device (src/stephens.cpp as it executes) ----
+// Workspace of one relabelling: the per-workgroup partial cost matrices, the K x K costs, Q (and log Q for the
+// batch), the batch's M x K permutation table.  Everything is stream-ordered: no host round trip.
+constexpr size_t kStPartialBudget = (size_t)64 << 20;  // bytes of partial cost matrices at most
+constexpr int kStBatchIters = 100;  // stephens.cpp:25; its threshold (10^(-6) = -16, :24) never stops the loop
+
+// workgroups of the cost pass over N rows for `slices` slices: a function of (N, K, slices) only, so that a
+// shape always sums in the same order
+int st_groups(int64_t N, int K, int slices) {
+    int64_t G = (N + 511) / 512;
+    const int64_t cap_wg = slices > 1 ? (1024 + slices - 1) / slices : 1024;
+    int64_t cap_mem = (int64_t)(kStPartialBudget / ((size_t)slices * K * K * sizeof(double)));
+    if (G > cap_wg) G = cap_wg;
+    if (G > cap_mem) G = cap_mem;
+    return (int)(G < 1 ? 1 : G);
+}
+
+struct StWork {
+    int64_t N = 0;
+    int K = 0, M = 0, G1 = 0, GM = 0;
+    DevBuf partial, cost, Q, LQ, permb;
+    size_t bytes() const {  // what alloc() takes
+        const size_t nk = (size_t)N * K * sizeof(double), kk = (size_t)K * K * sizeof(double);
+        const size_t g = (size_t)(GM * (M > 0 ? M : 1) > G1 ? GM * (M > 0 ? M : 1) : G1);
+        return g * kk + (size_t)(M > 1 ? M : 1) * kk + nk * (M > 0 ? 2 : 1) + (size_t)M * K * sizeof(int32_t);
+    }
+    void shape(int64_t n, int k, int m) {
+        N = n; K = k; M = m;
+        G1 = st_groups(N, K, 1);
+        GM = m > 0 ? st_groups(N, K, m) : 0;
+    }
+    int alloc() {
+        const size_t nk = (size_t)N * K * sizeof(double), kk = (size_t)K * K * sizeof(double);
+        const size_t g = (size_t)(GM * (M > 0 ? M : 1) > G1 ? GM * (M > 0 ? M : 1) : G1);
+        HIP_TRY(partial.alloc(g * kk));
+        HIP_TRY(cost.alloc((size_t)(M > 1 ? M : 1) * kk));
+        HIP_TRY(Q.alloc(nk));
+        if (M > 0) {
+            HIP_TRY(LQ.alloc(nk));
+            HIP_TRY(permb.alloc((size_t)M * K * sizeof(int32_t)));
+        }
+        return BMM_OK;
+    }
+};
+
+int st_check_k(int K) {
+    if (K < 1 || K > kStephensMaxK)
+        return set_err(BMM_E_ARG, "Stephens relabelling on the device supports 1 <= K <= %d categories (K = %d)",
+                       kStephensMaxK, K);
+    return BMM_OK;
+}
+
+// cost matrices of `slices` slices of p (slice_stride apart) against q (or log q) into w.cost
+int st_cost(hipStream_t st, StWork& w, const double* p, int64_t slice_stride, int slices, const double* q,
+            bool q_is_log, bool batch_form) {
+    const int K = w.K, G = slices > 1 ? w.GM : w.G1;
+    const int64_t rows = (w.N + G - 1) / G;
+    const int nb = ((K + 3) / 4) * ((K + 3) / 4);
+    const int B = nb <= 256 ? 1 : (nb + 255) / 256;
+    const dim3 grid((unsigned)G, (unsigned)slices);
+    const size_t lds = st_cost_lds(K);
+    double* part = w.partial.as<double>();
+    switch (B) {
+        case 1: hipLaunchKernelGGL(k_st_cost_partial<1>, grid, dim3(256), lds, st, p, w.N, K, slice_stride, q, (int)q_is_log, (int)batch_form, rows, part); break;
+        case 2: hipLaunchKernelGGL(k_st_cost_partial<2>, grid, dim3(256), lds, st, p, w.N, K, slice_stride, q, (int)q_is_log, (int)batch_form, rows, part); break;
+        case 3: hipLaunchKernelGGL(k_st_cost_partial<3>, grid, dim3(256), lds, st, p, w.N, K, slice_stride, q, (int)q_is_log, (int)batch_form, rows, part); break;
+        default: hipLaunchKernelGGL(k_st_cost_partial<4>, grid, dim3(256), lds, st, p, w.N, K, slice_stride, q, (int)q_is_log, (int)batch_form, rows, part); break;
+    }
+    HIP_TRY(hipGetLastError());
+    const int KK = K * K;
+    hipLaunchKernelGGL(k_st_cost_reduce, dim3((unsigned)((KK + 63) / 64), (unsigned)slices), dim3(256), 0, st, part, G, KK,
+                       w.cost.as<double>());
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+
+int st_assign(hipStream_t st, const double* cost, int K, int slices, int32_t* perm, int64_t ld) {
+    const size_t lds = st_assign_lds(K);
+    const int in_lds = (size_t)K * K * sizeof(double) + (size_t)(K + 1) * (3 * sizeof(double) + 3 * sizeof(int)) <= 65536;
+    hipLaunchKernelGGL(k_st_assign, dim3((unsigned)slices), dim3(64), lds, st, cost, K, perm, ld, in_lds);
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+
+unsigned st_grid(int64_t n) { return (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
+
+// my_stephens_batch (stephens.cpp:6-66) over the window p (N x K x M, modified in place: zeros -> 1e-6), enqueued:
+// w.Q receives the Q of the last iteration's start, w.LQ its log, w.permb the last iteration's permutations
+int st_batch(hipStream_t st, StWork& w, double* p) {
+    const int64_t N = w.N, NK = N * w.K;
+    const int K = w.K, M = w.M;
+    hipLaunchKernelGGL(k_st_replace_zeros, dim3(st_grid(NK * M)), dim3(256), 0, st, p, NK * M);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_st_perm_identity, dim3((unsigned)((M * K + 255) / 256)), dim3(256), 0, st, w.permb.as<int32_t>(), M, K);
+    HIP_TRY(hipGetLastError());
+    for (int t = 0; t < kStBatchIters; ++t) {
+        hipLaunchKernelGGL(k_st_q_batch, dim3(st_grid(NK)), dim3(256), 0, st, p, N, K, M, w.permb.as<int32_t>(),
+                           w.Q.as<double>(), w.LQ.as<double>());
+        HIP_TRY(hipGetLastError());
+        int rc = st_cost(st, w, p, NK, M, w.LQ.as<double>(), true, true);
+        if (rc == BMM_OK) rc = st_assign(st, w.cost.as<double>(), K, M, w.permb.as<int32_t>(), M);
+        if (rc) return rc;
+    }
+    return BMM_OK;
+}
+
+// my_stephens_online (stephens.cpp:68-94) for sweep j, enqueued: perm -> perm[0], perm[ld], ..; w.Q updated in place
+int st_online(hipStream_t st, StWork& w, const double* p, int j, int32_t* perm, int64_t ld) {
+    int rc = st_cost(st, w, p, 0, 1, w.Q.as<double>(), false, false);
+    if (rc == BMM_OK) rc = st_assign(st, w.cost.as<double>(), w.K, 1, perm, ld);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_st_q_online, dim3(st_grid(w.N * w.K)), dim3(256), 0, st, w.Q.as<double>(), p, w.N, w.K, perm, ld,
+                       (double)j, (double)(j + 1));
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+
+// The sweeps of a relabel = TRUE run with Stephens on the device (collapsed_gibbs.cpp:160-201): the window's
+// matrices go into a device ring, the batch runs after sweep burnin - 1, every kept sweep's matrix feeds the online
+// step, whose permutation lands in row j - burnin of the S x K device table dPerm.  All of it is enqueued ahead
+// of the device as the plain sweeps are.
+struct StRun {
+    StWork w;
+    DevBuf ring, dbuf, perm;  // one matrix buffer: the online step of sweep j is stream-ordered before sweep j + 1
+    int W = 0;
+};
+
+int st_run_prepare(bmm_chain* c, StRun& r, int W) {
+    const int64_t N = c->p.N;
+    const int K = c->p.K;
+    if (c->burnin < 2 || W < 1)
+        return set_err(BMM_E_ARG, "relabel on the device needs the batch step, which the reference runs only with "
+                       "burnin >= 2 and burnrelabel >= 1 (burnin = %d, burnrelabel = %d)", c->burnin, W);
+    int rc = st_check_k(K);
+    if (rc) return rc;
+    r.W = W;
+    r.w.shape(N, K, W);
+    const size_t mat = (size_t)N * K * sizeof(double);
+    const size_t need = mat * (size_t)W + mat + r.w.bytes() + (size_t)c->S * K * sizeof(int32_t);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b)
+        return set_err(BMM_E_ARG, "relabel on the device: the batch window (%d sweeps of N x K = %lld x %d doubles) and "
+                       "its workspace need %zu bytes of device memory, %zu are free", W, (long long)N, K, need, free_b);
+    rc = probs_alloc(c, false);
+    if (rc) return rc;
+    if (r.ring.alloc(mat * (size_t)W) != hipSuccess || r.dbuf.alloc(mat) != hipSuccess || r.perm.alloc((size_t)c->S * K * sizeof(int32_t)) != hipSuccess)
+        return set_err(BMM_E_ARG, "relabel on the device: allocating %zu bytes of device memory failed", need);
+    rc = r.w.alloc();
+    if (rc) return rc;
+    // slices of sweeps j < 1 (a window longer than the burn-in) stay zero, as arma::fill::zeros leaves them
+    HIP_TRY(hipMemsetAsync(r.ring.p, 0, mat * (size_t)W, c->stream));
+    return BMM_OK;
+}
+
+// one sweep j of a relabelling run, with its share of Stephens
+int st_run_sweep(bmm_chain* c, StRun& r, int j) {
+    const int64_t N = c->p.N;
+    const int burnin = c->burnin, first_window = burnin - r.W;
+    const size_t mat = (size_t)N * c->p.K;
+    const bool window = j >= first_window && j < burnin;
+    if (window) c->probs_dst = r.ring.as<double>() + (size_t)(j - first_window) * mat;
+    else if (j >= burnin) c->probs_dst = r.dbuf.as<double>();
+    else c->probs_dst = nullptr;
+    int rc = bmm_chain_sweeps(c, 1);
+    c->probs_dst = nullptr;
+    if (rc) return rc;
+    if (j == burnin - 1) return st_batch(c->stream, r.w, r.ring.as<double>());
+    if (j >= burnin) return st_online(c->stream, r.w, r.dbuf.as<double>(), j, r.perm.as<int32_t>() + (j - burnin), c->S);
+    return BMM_OK;
+}
+
 // The sweeps of a run whose allocation probabilities go to the host's relabelling code
 // (collapsed_gibbs.cpp:162-172, 187-201): sweeps burnin - burnrelabel .. burnin - 1 fill the batch
 // cube (through a device ring when it fits, so that those sweeps need no host round trip), then
@@ -1867,7 +2039,8 @@ void copy_labels(const int32_t* src, int32_t* dst, int64_t n) {  // the same for
 // and the host's memory.  Up to 254 labels travel as one byte each and are widened by that host copy (a
 // quarter of the PCIe bytes).  Nothing of it can start before the last sweep has finished: each
 // observation's run is complete only then.
-int trace_out(bmm_chain* c, int32_t* z_out, PhaseClock* clock) {
+// perm: the S x K device permutation table of a relabelling run -- the trace then leaves relabelled
+int trace_out(bmm_chain* c, int32_t* z_out, PhaseClock* clock, const int32_t* perm = nullptr) {
     const int64_t N = c->p.N;
     const int S = c->S;
     const bool narrow = c->p.K <= 254;
@@ -1920,8 +2093,8 @@ int trace_out(bmm_chain* c, int32_t* z_out, PhaseClock* clock) {
         const dim3 grid((unsigned)((rows + 31) / 32), (unsigned)((S + 31) / 32));
         char* const dblk = c->dOutBlk[blk & 1];
         // block blk - 2 has been consumed (below) before this iteration started: its staging is free
-        if (narrow) hipLaunchKernelGGL(k_trace_block<uint8_t>, grid, dim3(256), 0, c->stream, c->dTrace, N, S, i0, rows, reinterpret_cast<uint8_t*>(dblk));
-        else hipLaunchKernelGGL(k_trace_block<int32_t>, grid, dim3(256), 0, c->stream, c->dTrace, N, S, i0, rows, reinterpret_cast<int32_t*>(dblk));
+        if (narrow) hipLaunchKernelGGL(k_trace_block<uint8_t>, grid, dim3(256), 0, c->stream, c->dTrace, N, S, i0, rows, reinterpret_cast<uint8_t*>(dblk), perm);
+        else hipLaunchKernelGGL(k_trace_block<int32_t>, grid, dim3(256), 0, c->stream, c->dTrace, N, S, i0, rows, reinterpret_cast<int32_t*>(dblk), perm);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(hblk[blk & 1], dblk, (size_t)rows * S * el, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipEventRecord(ev.e[blk & 1], c->stream));
@@ -1942,8 +2115,9 @@ int trace_out(bmm_chain* c, int32_t* z_out, PhaseClock* clock) {
 // the device, an event after every `every`-th sweep; the calling thread then follows the events and calls
 // the hook as each one is reached.  For the DP sampler the cluster sizes at those sweeps ride along (K
 // int32 into pinned memory) so that the hook gets the number of clusters in use, as the reference prints
-// it (collapsed_gibbs_dp.cpp:99).
-int run_sweeps_reported(bmm_chain* c, int nsamples) {
+// it (collapsed_gibbs_dp.cpp:99).  step (a relabelling run): enqueues sweep j with its share of the relabelling,
+// in place of the plain sweeps.
+int run_sweeps_reported(bmm_chain* c, int nsamples, const std::function<int(int)>& step = nullptr) {
     const int every = g_progress.every, K = c->p.K;
     const int total = nsamples - 1, marks = (total + every - 1) / every;
     if (marks < 1) return BMM_OK;
@@ -1954,7 +2128,9 @@ int run_sweeps_reported(bmm_chain* c, int nsamples) {
     if (dp) HIP_TRY(sizes.alloc((size_t)marks * K * sizeof(int32_t)));
     for (int m = 0; m < marks; ++m) {
         const int n = total - m * every < every ? total - m * every : every;
-        int rc = bmm_chain_sweeps(c, n);
+        int rc = BMM_OK;
+        if (step) { for (int t = 0; t < n && rc == BMM_OK; ++t) rc = step(c->sweep + 1); }
+        else rc = bmm_chain_sweeps(c, n);
         if (rc) return rc;
         if (dp) HIP_TRY(hipMemcpyAsync(sizes.as<int32_t>() + (size_t)m * K, c->dNk, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipEventCreateWithFlags(&evs[(size_t)m], hipEventDisableTiming));
@@ -1996,13 +2172,33 @@ int run_start_state(bmm_chain* c, const RunIO& io) {
     return BMM_OK;
 }
 
+// the relabelled theta trace: theta_relab(perm(s, k), d, s) = theta(k, d, s) (collapsed_gibbs.cpp:215-217)
+void permute_theta(const double* th, const int32_t* perm, int K, int P, int S, double* out) {
+    for (int s = 0; s < S; ++s)
+        for (int k = 0; k < K; ++k) {
+            const int to = perm[s + (size_t)k * S];
+            for (int d = 0; d < P; ++d) out[to + (size_t)K * d + (size_t)K * P * s] = th[k + (size_t)K * d + (size_t)K * P * s];
+        }
+}
+
 // the sweeps, then the traces out (data and starting state are in place)
-int run_body(bmm_chain* c, int nsamples, const RunIO& io, const bmm_relabel_hooks* hooks) {
+int run_body(bmm_chain* c, int nsamples, const RunIO& io, const bmm_relabel_hooks* hooks,
+             const bmm_relabel_out* rel = nullptr) {
     const int sampler = c->p.mode, K = c->p.K, P = c->p.P, S = c->S;
     HIP_TRY(hipSetDevice(c->device));
     PhaseClock clock;
-    int rc = hooks ? run_sweeps_hooked(c, nsamples, hooks)
+    StRun st;
+    int rc = BMM_OK;
+    if (rel) {
+        rc = st_run_prepare(c, st, rel->burnrelabel);
+        if (rc) return rc;
+        auto step = [&](int j) { return st_run_sweep(c, st, j); };
+        if (g_progress.fn && g_progress.every > 0) rc = run_sweeps_reported(c, nsamples, step);
+        else for (int j = 1; j < nsamples && rc == BMM_OK; ++j) rc = step(j);
+    } else {
+        rc = hooks ? run_sweeps_hooked(c, nsamples, hooks)
                    : (g_progress.fn && g_progress.every > 0 ? run_sweeps_reported(c, nsamples) : bmm_chain_sweeps(c, nsamples - 1));
+    }
     if (rc) return rc;
     clock.lap(2);
     // theta, alpha, pi: small, queued behind the sweeps
@@ -2010,8 +2206,17 @@ int run_body(bmm_chain* c, int nsamples, const RunIO& io, const bmm_relabel_hook
     HIP_TRY(hipMemcpyAsync(io.alpha_out, c->dAlphaTrace, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (explicit_params(sampler))
         HIP_TRY(hipMemcpyAsync(io.pi_out, c->dPiTrace, (size_t)S * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    rc = trace_out(c, io.z_out, &clock);
-    if (rc) return rc;
+    if (rel) {
+        HIP_TRY(hipMemcpyAsync(rel->permutations, st.perm.p, (size_t)S * K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        rc = trace_out(c, rel->z_original, &clock);
+        if (rc == BMM_OK) rc = trace_out(c, io.z_out, nullptr, st.perm.as<int32_t>());
+        if (rc) return rc;
+        std::memcpy(rel->theta_original, io.theta_out, (size_t)S * K * P * sizeof(double));
+        permute_theta(rel->theta_original, rel->permutations, K, P, S, io.theta_out);
+    } else {
+        rc = trace_out(c, io.z_out, &clock);
+        if (rc) return rc;
+    }
     clock.lap(4);
     return dbg_labels_ok(c);
 }
@@ -2089,10 +2294,18 @@ int check_run_args(const int32_t* X, int nsamples, int burnin, const RunIO& io, 
 
 int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int K, double alpha, double beta,
               double gamma, double a, double b, int burnin, int64_t batch, uint64_t seed, int device,
-              const RunIO& io, const bmm_relabel_hooks* hooks) {
+              const RunIO& io, const bmm_relabel_hooks* hooks, const bmm_relabel_out* rel = nullptr) {
     return guarded([&]() -> int {
         int rc = check_run_args(X, nsamples, burnin, io, sampler);
         if (rc) return rc;
+        if (rel) {  // refused before any device is touched
+            if (!rel->permutations || !rel->z_original || !rel->theta_original) return set_err(BMM_E_ARG, "null buffer");
+            if (burnin < 2 || rel->burnrelabel < 1)
+                return set_err(BMM_E_ARG, "relabel on the device needs the batch step, which the reference runs only with "
+                               "burnin >= 2 and burnrelabel >= 1 (burnin = %d, burnrelabel = %d)", burnin, rel->burnrelabel);
+            rc = st_check_k(K);
+            if (rc) return rc;
+        }
         for (double& v : g_phase_ms) v = 0.0;
         PhaseClock clock;
         // The host's cores start validating and packing X at once (bit planes, the default layout) while this
@@ -2124,7 +2337,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             }
             if (rc) return rc;
             clock.lap(0);
-            rc = run_body(c, nsamples, io, hooks);
+            rc = run_body(c, nsamples, io, hooks, rel);
             clock.t = std::chrono::steady_clock::now();
         }
         clock.lap(5);  // releasing the chain
@@ -2270,6 +2483,101 @@ int bmm_full_run_probs(const int32_t* X, int64_t N, int P, const double* initial
     io.theta_out = theta_out; io.alpha_out = alpha_out;
     return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
                      hooks);
+}
+
+// ---- relabel = TRUE with Stephens' relabelling on the device ---------------------------------
+int bmm_collapsed_run_relabel(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int K,
+                              double alpha, double beta, double gamma, double a, double b, int burnin,
+                              int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
+                              double* alpha_out, const bmm_relabel_out* rel) {
+    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
+    RunIO io; io.z0 = initialK; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
+    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
+                     device, io, nullptr, rel);
+}
+int bmm_dp_run_relabel(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
+                       double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
+                       int32_t* z_out, double* theta_out, double* alpha_out, const bmm_relabel_out* rel) {
+    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
+    RunIO io; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
+    return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
+                     io, nullptr, rel);
+}
+int bmm_sb_run_relabel(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                       int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b,
+                       int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
+                       double* alpha_out, const bmm_relabel_out* rel) {
+    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
+    RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
+    io.theta_out = theta_out; io.alpha_out = alpha_out;
+    return run_chain(BMM_SAMPLER_SB, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
+                     nullptr, rel);
+}
+int bmm_full_run_relabel(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                         int nsamples, int K, double alpha, double beta, double gamma, double a, double b,
+                         int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out,
+                         double* theta_out, double* alpha_out, const bmm_relabel_out* rel) {
+    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
+    RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
+    io.theta_out = theta_out; io.alpha_out = alpha_out;
+    return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
+                     nullptr, rel);
+}
+
+int bmm_device_stephens_batch(int device, const double* p, int64_t N, int K, int M, double* Q_out, int32_t* perm_out) {
+    return guarded([&]() -> int {
+        if (!p || !Q_out || !perm_out) return set_err(BMM_E_ARG, "null argument");
+        if (N < 1 || M < 1) return set_err(BMM_E_ARG, "N and M must be >= 1");
+        int rc = st_check_k(K);
+        if (rc) return rc;
+        const size_t n = (size_t)N * K * M;
+        for (size_t i = 0; i < n; ++i)
+            if (!(p[i] >= 0.0) || std::isinf(p[i])) return set_err(BMM_E_ARG, "p must hold finite values >= 0 (element %zu)", i);
+        HIP_TRY(hipSetDevice(device));
+        StWork w;
+        w.shape(N, K, M);
+        DevBuf dp;
+        HIP_TRY(dp.alloc(n * sizeof(double)));
+        rc = w.alloc();
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(dp.p, p, n * sizeof(double), hipMemcpyHostToDevice));
+        rc = st_batch(nullptr, w, dp.as<double>());
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(Q_out, w.Q.p, (size_t)N * K * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(perm_out, w.permb.p, (size_t)M * K * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return BMM_OK;
+    });
+}
+
+int bmm_device_stephens_online(int device, const double* Q, const double* p, int64_t N, int K, int j, int32_t* perm_out,
+                               double* Q_out, double* cost_out) {
+    return guarded([&]() -> int {
+        if (!Q || !p || !perm_out || !Q_out) return set_err(BMM_E_ARG, "null argument");
+        if (N < 1) return set_err(BMM_E_ARG, "N must be >= 1");
+        int rc = st_check_k(K);
+        if (rc) return rc;
+        const size_t nk = (size_t)N * K;
+        for (size_t i = 0; i < nk; ++i) {
+            if (!(p[i] >= 0.0) || std::isinf(p[i])) return set_err(BMM_E_ARG, "p must hold finite values >= 0 (element %zu)", i);
+            if (!(Q[i] > 0.0) || std::isinf(Q[i])) return set_err(BMM_E_ARG, "Q must hold finite values > 0 (element %zu)", i);
+        }
+        HIP_TRY(hipSetDevice(device));
+        StWork w;
+        w.shape(N, K, 0);
+        DevBuf dp, dperm;
+        HIP_TRY(dp.alloc(nk * sizeof(double)));
+        HIP_TRY(dperm.alloc((size_t)K * sizeof(int32_t)));
+        rc = w.alloc();
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(dp.p, p, nk * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(w.Q.p, Q, nk * sizeof(double), hipMemcpyHostToDevice));
+        rc = st_online(nullptr, w, dp.as<double>(), j, dperm.as<int32_t>(), 1);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(perm_out, dperm.p, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(Q_out, w.Q.p, nk * sizeof(double), hipMemcpyDeviceToHost));
+        if (cost_out) HIP_TRY(hipMemcpy(cost_out, w.cost.p, (size_t)K * K * sizeof(double), hipMemcpyDeviceToHost));
+        return BMM_OK;
+    });
 }
 
 // ---- several independent chains in one call (SURVEY.md section 8 rows b, e) ----------------

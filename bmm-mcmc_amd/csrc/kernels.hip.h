@@ -1397,9 +1397,12 @@ __global__ __launch_bounds__(256) void k_probs_finish(ChainParams p, const doubl
 // rows x S block of R's S x N column-major matrix they occupy (out[(i - i0) * S + s]: that block is
 // contiguous in the caller's buffer), labels 1-based.  T = int32_t: unassigned -> NA_integer_;
 // T = uint8_t (at most 254 labels): unassigned -> 0, widened on the host, a quarter of the bytes over PCIe.
+// perm (relabel = TRUE, Stephens on the device): label v of kept sweep s leaves as perm(s, v) + 1, perm the
+// S x K column-major permutation table (collapsed_gibbs.cpp:197-199); nullptr: as sampled.
 template <typename T>
 __global__ __launch_bounds__(256) void k_trace_block(const int32_t* __restrict__ trace, int64_t N, int S,
-                                                     int64_t i0, int64_t rows, T* __restrict__ out) {
+                                                     int64_t i0, int64_t rows, T* __restrict__ out,
+                                                     const int32_t* __restrict__ perm = nullptr) {
     __shared__ int32_t tile[32][33];
     const int64_t b0 = (int64_t)blockIdx.x * 32;  // within the block of observations
     const int s0 = blockIdx.y * 32;
@@ -1414,7 +1417,8 @@ __global__ __launch_bounds__(256) void k_trace_block(const int32_t* __restrict__
         const int64_t li = b0 + r;
         const int s = s0 + tx;
         if (s < S && li < rows) {
-            const int32_t v = tile[tx][r];
+            int32_t v = tile[tx][r];
+            if (perm && v >= 0) v = perm[s + (int64_t)v * S];
             if (sizeof(T) == 1) out[(size_t)li * S + s] = (T)(v < 0 ? 0 : v + 1);
             else out[(size_t)li * S + s] = (T)(v < 0 ? (int32_t)0x80000000 : v + 1);
         }
@@ -1430,6 +1434,261 @@ __global__ __launch_bounds__(256) void k_labels_from_r(const int32_t* __restrict
         if (v < 1 || v > K) atomicMin(bad, (unsigned long long)i);
         z0[i] = v - 1;
     }
+}
+
+// ---- Stephens' relabelling (src/stephens.cpp as it executes) --------------------
+// Matrices are N x K column-major (p[n + k*N]); a cost matrix is K x K column-major (C[k + l*K]); a
+// permutation table is rows x K column-major (perm(r, k) at perm[r + k*ld]), 0-based.
+constexpr int kStephensMaxK = 128;  // = BMM_STEPHENS_MAX_K
+// rows of p / log q staged in LDS per step of the cost kernel: 64 up to 32 categories (48 KiB), 16 above
+__host__ __device__ inline int st_tile_rows(int K) { return (K + 3) / 4 * 4 <= 32 ? 64 : 16; }
+
+// LDS bytes of k_st_cost_partial for K categories: three T x K4 tiles, or the cross-group reduction (ng x nb x 16)
+__host__ __device__ inline size_t st_cost_lds(int K) {
+    const int K4 = (K + 3) / 4 * 4, nb = (K4 / 4) * (K4 / 4);
+    const int ng = nb >= 256 ? 1 : 256 / nb;
+    const size_t tiles = (size_t)3 * st_tile_rows(K) * K4 * sizeof(double);
+    const size_t red = ng > 1 ? (size_t)ng * nb * 16 * sizeof(double) : 0;
+    return tiles > red ? tiles : red;
+}
+
+// Per-workgroup partial cost matrices over rows [wg*rows, (wg+1)*rows) of slice blockIdx.y:
+//   C[k,l] = sum_n p(n,l) * (a(n,l) - log q(n,k)),  a = log p (batch, stephens.cpp:50) or p (online, :79),
+// a term with p(n,l) == 0 counting exactly 0 (an all-zero column costs 0 against every row).  q is read as
+// log q (lq_is_log) or as q; rows are staged st_tile_rows(K) at a time.  Each thread owns 4 x 4 blocks of C (B of them when there are more than 256
+// blocks); with fewer blocks, ng groups of threads take every ng-th row of a tile and are summed in group
+// order at the end.  partial[(slice * G + wg) * K*K + k + l*K]; no atomics: a fixed shape sums in a fixed order.
+template <int B>
+__global__ __launch_bounds__(256) void k_st_cost_partial(const double* __restrict__ p, int64_t N, int K,
+                                                         int64_t slice_stride, const double* __restrict__ q,
+                                                         int lq_is_log, int batch_form, int64_t rows,
+                                                         double* __restrict__ partial) {
+    extern __shared__ double st_lds[];
+    const int K4 = (K + 3) / 4 * 4, nbk = K4 / 4, nb = nbk * nbk;
+    const int ng = nb >= 256 ? 1 : 256 / nb;
+    const int tid = threadIdx.x;
+    const int g = nb >= 256 ? 0 : tid / nb;
+    const bool active = g < ng;
+    const int T = st_tile_rows(K);
+    double* sP = st_lds;
+    double* sA = st_lds + T * K4;
+    double* sL = st_lds + 2 * T * K4;
+    const double* ps = p + (int64_t)blockIdx.y * slice_stride;
+    const int64_t n0 = (int64_t)blockIdx.x * rows;
+    const int64_t n1 = n0 + rows < N ? n0 + rows : N;
+    double acc[B][16];
+#pragma unroll
+    for (int b = 0; b < B; ++b)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[b][e] = 0.0;
+    for (int64_t r0 = n0; r0 < n1; r0 += T) {
+        for (int idx = tid; idx < T * K4; idx += 256) {
+            const int t = idx % T, col = idx / T;
+            const int64_t n = r0 + t;
+            const bool ok = n < n1 && col < K;
+            const double pv = ok ? ps[n + (int64_t)col * N] : 0.0;
+            const double qv = ok ? q[n + (int64_t)col * N] : 1.0;
+            sP[t * K4 + col] = pv;
+            sA[t * K4 + col] = batch_form ? (pv > 0.0 ? log(pv) : 0.0) : pv;
+            sL[t * K4 + col] = lq_is_log ? qv : log(qv);
+        }
+        __syncthreads();
+        if (active) {
+            for (int t = g; t < T; t += ng) {
+#pragma unroll
+                for (int b = 0; b < B; ++b) {
+                    const int blk = nb >= 256 ? tid + 256 * b : tid % nb;
+                    if (blk >= nb) continue;
+                    const int kb = blk % nbk, lb = blk / nbk;
+                    double lq[4], pp[4], aa[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        lq[u] = sL[t * K4 + 4 * kb + u];
+                        pp[u] = sP[t * K4 + 4 * lb + u];
+                        aa[u] = sA[t * K4 + 4 * lb + u];
+                    }
+#pragma unroll
+                    for (int l = 0; l < 4; ++l)
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const double term = pp[l] * (aa[l] - lq[k]);
+                            acc[b][k + 4 * l] += pp[l] != 0.0 ? term : 0.0;
+                        }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    const int KK = K * K;
+    double* out = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * KK;
+    if (ng == 1) {
+#pragma unroll
+        for (int b = 0; b < B; ++b) {
+            const int blk = tid + 256 * b;
+            if (blk >= nb) continue;
+            const int kb = blk % nbk, lb = blk / nbk;
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int kk = 4 * kb + k, ll = 4 * lb + l;
+                    if (kk < K && ll < K) out[kk + ll * K] = acc[b][k + 4 * l];
+                }
+        }
+        return;
+    }
+    // ng > 1: one block per thread (B == 1); sum the groups in order
+    double* red = st_lds;  // [ng][nb][16]
+    if (active)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) red[((size_t)g * nb + (tid % nb)) * 16 + e] = acc[0][e];
+    __syncthreads();
+    for (int e = tid; e < KK; e += 256) {
+        const int kk = e % K, ll = e / K;
+        const int blk = kk / 4 + (ll / 4) * nbk, sub = (kk % 4) + 4 * (ll % 4);
+        double s = 0.0;
+        for (int gg = 0; gg < ng; ++gg) s += red[((size_t)gg * nb + blk) * 16 + sub];
+        out[e] = s;
+    }
+}
+
+// cost[slice][e] = sum over the G partials of that slice, in a fixed order (four quarters, then the quarters
+// in order).  Grid (ceil(KK / 64), slices), 256 threads.
+__global__ __launch_bounds__(256) void k_st_cost_reduce(const double* __restrict__ partial, int G, int KK,
+                                                        double* __restrict__ cost) {
+    __shared__ double part[4][64];
+    const int lane = threadIdx.x & 63, quarter = threadIdx.x >> 6;
+    const int e = blockIdx.x * 64 + lane;
+    const int per = (G + 3) / 4, g0 = quarter * per, g1 = g0 + per < G ? g0 + per : G;
+    const double* base = partial + (int64_t)blockIdx.y * G * KK;
+    double s = 0.0;
+    if (e < KK)
+        for (int g = g0; g < g1; ++g) s += base[(int64_t)g * KK + e];
+    part[quarter][lane] = s;
+    __syncthreads();
+    if (quarter == 0 && e < KK)
+        cost[(int64_t)blockIdx.y * KK + e] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+}
+
+// The assignment (lp_solve's integer program in my_lpsolve): min sum_k C[k, sigma(k)] over permutations, by the
+// O(K^3) shortest-augmenting-path Hungarian method with potentials u (rows), v (columns), rows added in index
+// order.  In each scan the free column with the smallest slack wins under strict <, i.e. the lowest index wins a
+// tie; potentials are updated elementwise.  tests/stephens_ref.py restates exactly these steps.  One wave per
+// cost matrix (blockIdx.x = slice), lane j handling columns j, j + 64, j + 128 (index 0 is the virtual column).
+// perm(slice, l) = the row assigned to column l (stephens.cpp:54-55, 83-84; not inverted: :56, :85).
+constexpr int kStAssignCols = 3;  // columns per lane: 1 + kStephensMaxK <= 64 * 3
+inline size_t st_assign_lds(int K) {
+    const size_t cm = (size_t)K * K * sizeof(double);
+    const size_t rest = (size_t)(K + 1) * (3 * sizeof(double) + 3 * sizeof(int));
+    return (cm + rest <= 65536 ? cm : 0) + rest;
+}
+__global__ __launch_bounds__(64) void k_st_assign(const double* __restrict__ cost, int K, int32_t* __restrict__ perm,
+                                                  int64_t ld, int cost_in_lds) {
+    extern __shared__ double st_lds[];
+    const int lane = threadIdx.x;
+    const int KK = K * K;
+    const double* Cg = cost + (int64_t)blockIdx.x * KK;
+    double* sC = st_lds;
+    double* u = st_lds + (cost_in_lds ? KK : 0);
+    double* v = u + (K + 1);
+    double* minv = v + (K + 1);
+    int* pr = reinterpret_cast<int*>(minv + (K + 1));
+    int* way = pr + (K + 1);
+    int* used = way + (K + 1);
+    if (cost_in_lds)
+        for (int e = lane; e < KK; e += 64) sC[e] = Cg[e];
+    const double* C = cost_in_lds ? sC : Cg;
+    for (int j = lane; j <= K; j += 64) { u[j] = 0.0; v[j] = 0.0; pr[j] = 0; way[j] = 0; }
+    __syncthreads();
+    const double INF = __builtin_huge_val();
+    for (int i = 1; i <= K; ++i) {
+        for (int j = lane; j <= K; j += 64) { minv[j] = INF; used[j] = 0; }
+        if (lane == 0) pr[0] = i;
+        __syncthreads();
+        int j0 = 0;
+        for (;;) {
+            if (lane == 0) used[j0] = 1;
+            __syncthreads();
+            const int i0 = pr[j0];
+            const double ui0 = u[i0];
+            double best = INF;
+            int bj = 0x7fffffff;
+#pragma unroll
+            for (int r = 0; r < kStAssignCols; ++r) {
+                const int j = lane + 64 * r;
+                if (j < 1 || j > K || used[j]) continue;
+                const double cur = (C[(i0 - 1) + (int64_t)(j - 1) * K] - ui0) - v[j];
+                if (cur < minv[j]) { minv[j] = cur; way[j] = j0; }
+                if (minv[j] < best) { best = minv[j]; bj = j; }
+            }
+            for (int off = 32; off >= 1; off >>= 1) {  // (value, index) minimum: the lowest index wins a tie
+                const double ob = __shfl_xor(best, off);
+                const int oj = __shfl_xor(bj, off);
+                if (ob < best || (ob == best && oj < bj)) { best = ob; bj = oj; }
+            }
+            const double delta = best;
+            const int j1 = bj;
+            __syncthreads();
+            for (int j = lane; j <= K; j += 64) {
+                if (used[j]) { u[pr[j]] += delta; v[j] -= delta; }
+                else minv[j] -= delta;
+            }
+            __syncthreads();
+            j0 = j1;
+            if (j0 > K || pr[j0] == 0) break;  // j0 > K: no finite slack left (non-finite costs)
+        }
+        if (lane == 0 && j0 <= K) {
+            do { const int j1 = way[j0]; pr[j0] = pr[j1]; j0 = j1; } while (j0);
+        }
+        __syncthreads();
+    }
+    for (int l = lane; l < K; l += 64) perm[blockIdx.x + (int64_t)l * ld] = pr[l + 1] - 1;
+}
+
+// p.replace(0, 1e-6) over the whole batch window (stephens.cpp:30-31)
+__global__ __launch_bounds__(256) void k_st_replace_zeros(double* __restrict__ p, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        if (p[i] == 0.0) p[i] = 0.000001;
+}
+
+// Q of one batch iteration (stephens.cpp:36-43): q(n,k) = (sum over slices m, in order, of p_m(n, perm(m,k))) / M,
+// and log q for that iteration's costs
+__global__ __launch_bounds__(256) void k_st_q_batch(const double* __restrict__ p, int64_t N, int K, int M,
+                                                    const int32_t* __restrict__ perm, double* __restrict__ Q,
+                                                    double* __restrict__ LQ) {
+    const int64_t NK = N * K;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < NK; i += (int64_t)gridDim.x * 256) {
+        const int64_t n = i % N;
+        const int k = (int)(i / N);
+        double s = 0.0;
+        for (int m = 0; m < M; ++m) {
+            const int pk = min(max(perm[m + (int64_t)k * M], 0), K - 1);  // in range whatever the costs were
+            s += p[(int64_t)m * NK + n + (int64_t)pk * N];
+        }
+        const double qv = s / (double)M;
+        Q[i] = qv;
+        LQ[i] = log(qv);
+    }
+}
+
+// The online update (stephens.cpp:86-92): Q = (j * (Q + p[:, perm])) / (j + 1) -- add, multiply, correctly rounded
+// divide, no contraction (the library is built with -ffp-contract=off)
+__global__ __launch_bounds__(256) void k_st_q_online(double* __restrict__ Q, const double* __restrict__ p, int64_t N,
+                                                     int K, const int32_t* __restrict__ perm, int64_t ld, double j,
+                                                     double j1) {
+    const int64_t NK = N * K;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < NK; i += (int64_t)gridDim.x * 256) {
+        const int64_t n = i % N;
+        const int k = (int)(i / N);
+        const int pk = min(max(perm[(int64_t)k * ld], 0), K - 1);
+        const double sum = Q[i] + p[n + (int64_t)pk * N];
+        Q[i] = (j * sum) / j1;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_st_perm_identity(int32_t* __restrict__ perm, int M, int K) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < M * K) perm[i] = i / M;
 }
 
 // ---- self-check kernels ----------------------------------------------------------

@@ -190,6 +190,56 @@ int bmm_full_run_probs(const int32_t* X, int64_t N, int P, const double* initial
                        double* pi_out, int32_t* z_out, double* theta_out, double* alpha_out,
                        const bmm_relabel_hooks* hooks);
 
+/* ---- relabel = TRUE with Stephens' relabelling on the device ----------------
+ * The reference's online relabelling (src/stephens.cpp, lp_solve underneath) as it executes, resident on the
+ * device: the batch window's matrices stay in HBM, my_stephens_batch runs once after sweep burnin - 1
+ * (collapsed_gibbs.cpp:187-190; always maxiter = 100 iterations: its threshold 10^(-6) is an integer XOR,
+ * stephens.cpp:24), my_stephens_online after every kept sweep (:191-199), all stream-ordered behind the sweeps
+ * with no host round trip.  The assignment lp_solve solves is solved exactly by the Hungarian method with a fixed
+ * tie rule (lowest column index wins; DESIGN.md lists the choice among equal-cost optima as a deviation).
+ * Arguments are those of the *_run_probs entry points with the hooks replaced by `rel`; z_out / theta_out
+ * receive the relabelled traces (z = perm[z - 1] + 1, theta_relab(perm(k), d, s) = theta(k, d, s):
+ * collapsed_gibbs.cpp:197-199, 215-217), rel the rest of the reference's list.  BMM_E_ARG when the reference
+ * would have no Q (burnin < 2 or burnrelabel < 1), for K (maxK) above BMM_STEPHENS_MAX_K, and -- before the first
+ * sweep, naming the bytes -- when the window (burnrelabel x N x K doubles) and its workspace do not fit in device
+ * memory.  Progress hooks and bmm_last_run_phases behave as in a plain run. */
+#define BMM_STEPHENS_MAX_K 128
+typedef struct bmm_relabel_out {
+    int burnrelabel;          /* sweeps of the batch window (>= 1; clamped as the R wrappers do) */
+    int32_t* permutations;    /* S x K int32 column-major, 0-based (arma::Mat<int>, collapsed_gibbs.cpp:194) */
+    int32_t* z_original;      /* S x N as z_out: the labels as sampled */
+    double* theta_original;   /* K x P x S as theta_out: theta as sampled */
+} bmm_relabel_out;
+int bmm_collapsed_run_relabel(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples,
+                              int K, double alpha, double beta, double gamma, double a, double b,
+                              int burnin, int64_t batch, uint64_t seed, int device, int32_t* z_out,
+                              double* theta_out, double* alpha_out, const bmm_relabel_out* rel);
+int bmm_dp_run_relabel(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta,
+                       double gamma, double a, double b, int burnin, int maxK, int64_t batch,
+                       uint64_t seed, int device, int32_t* z_out, double* theta_out, double* alpha_out,
+                       const bmm_relabel_out* rel);
+int bmm_sb_run_relabel(const int32_t* X, int64_t N, int P, const double* initialPi,
+                       const double* initialTheta, int nsamples, int maxK, double alpha, double beta,
+                       double gamma, double a, double b, int burnin, uint64_t seed, int device,
+                       double* pi_out, int32_t* z_out, double* theta_out, double* alpha_out,
+                       const bmm_relabel_out* rel);
+int bmm_full_run_relabel(const int32_t* X, int64_t N, int P, const double* initialPi,
+                         const double* initialTheta, int nsamples, int K, double alpha, double beta,
+                         double gamma, double a, double b, int burnin, uint64_t seed, int device,
+                         double* pi_out, int32_t* z_out, double* theta_out, double* alpha_out,
+                         const bmm_relabel_out* rel);
+/* The two functions of src/stephens.h on the device, for arbitrary host inputs (what the runs above execute):
+ *   batch:  p N x K x M (column-major cube, finite, >= 0) -> Q_out N x K (the Q computed at the start of the last
+ *           of the 100 iterations, stephens.cpp:36-43, 64) and perm_out M x K int32 (that iteration's
+ *           permutations, 0-based, not inverted: :54-56)
+ *   online: Q, p N x K and the sweep index j -> perm_out K (0-based), Q_out = (j * (Q + p[:, perm])) / (j + 1)
+ *           (:77-92), and, unless NULL, cost_out K x K column-major: the cost matrix the assignment was solved on,
+ *           C[k,l] = sum_n p(n,l) * (p(n,l) - log Q(n,k)) with terms of p(n,l) == 0 counting 0 (:79). */
+int bmm_device_stephens_batch(int device, const double* p, int64_t N, int K, int M, double* Q_out,
+                              int32_t* perm_out);
+int bmm_device_stephens_online(int device, const double* Q, const double* p, int64_t N, int K, int j,
+                               int32_t* perm_out, double* Q_out, double* cost_out);
+
 /* ---- several independent chains in one call (SURVEY.md section 8 rows b and e) ---------------
  * n_chains chains of one sampler over the same data, chain c keyed seed + c and resident on
  * devices[c] (all on device 0 when devices is NULL; a device may appear several times: its chains
