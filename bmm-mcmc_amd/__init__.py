@@ -164,6 +164,57 @@ class _DeviceRelabelRun:
         return out
 
 
+# ---------------------------------------------------------------- newdata=: the posterior predictive
+class _PredictOut(_C.Structure):  # bmm_predict_out
+    _fields_ = [("lppd", _C.c_void_p), ("logdens", _C.c_void_p), ("resp", _C.c_void_p), ("relabel", _C.c_void_p),
+                ("hooks", _C.c_void_p)]
+
+
+class _Predict:
+    """Inputs and outputs of a bmm_*_run_predict call: the new rows, lppd (M,), optionally the (S, M) trace of
+    log p(x_m | state s) and the (M, Kc) mean responsibilities (include/bmm_mcmc.h)."""
+
+    def __init__(self, newdata, P, S, Kc, trace, responsibilities, chains):
+        if int(chains) > 1:
+            raise NotImplementedError("newdata= is offered per chain (chains=1)")
+        self.X = _capi.as_x(newdata)
+        if self.X.shape[1] != P:
+            raise ValueError("newdata must have the %d columns of data" % P)
+        self.M = self.X.shape[0]
+        self.lppd = _np.full(self.M, _np.nan)
+        self.logdens = _np.full((S, self.M), _np.nan, order="F") if trace else None
+        self.resp = _np.full((self.M, Kc), _np.nan, order="F") if responsibilities else None
+        self.s = _PredictOut(self.lppd.ctypes.data, self.logdens.ctypes.data if trace else None,
+                             self.resp.ctypes.data if responsibilities else None, None, None)
+
+    def result(self):
+        out = {"lppd": self.lppd}
+        if self.logdens is not None:
+            out["logdens"] = self.logdens
+        if self.resp is not None:
+            out["resp"] = self.resp
+        return out
+
+
+def _with_predictive(out, pr):
+    if pr is not None:
+        out["predictive"] = pr.result()
+    return out
+
+
+def _run(base, args, pr, hooks=None, rel=None):
+    """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
+    them with the predictive of new rows (_run_predict)."""
+    L = _capi.lib()
+    if pr is None:
+        if rel is not None:
+            return getattr(L, "bmm_%s_run_relabel" % base)(*args, rel.ref())
+        return getattr(L, "bmm_%s_run_probs" % base)(*args, hooks.ref() if hooks else None)
+    pr.s.relabel = _C.addressof(rel.s) if rel is not None else None
+    pr.s.hooks = _C.addressof(hooks.hooks) if hooks is not None else None
+    return getattr(L, "bmm_%s_run_predict" % base)(*args, _capi.vp(pr.X), _C.c_int64(pr.M), _C.byref(pr.s))
+
+
 def stephens_batch(p, device=0):
     """my_stephens_batch (src/stephens.cpp:6-66) on the device: p is an N x K x M cube of allocation
     probabilities; returns (Q, perm) -- Q (N x K) the one computed at the start of the last of the 100
@@ -293,7 +344,8 @@ def _multi(sampler, X, chains, devices, z0s, pi0s, th0s, nsamples, K, alpha, bet
 
 def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
                     relabel=False, burnrelabel=50, debug=False, *, seed=None, batch=None, device=0,
-                    initial_K=None, chains=1, devices=None, stephens=None):
+                    initial_K=None, chains=1, devices=None, stephens=None, newdata=None, predictive_trace=False,
+                    responsibilities=False):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -302,7 +354,13 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     sampled uniformly as R/utils.R:42 does), `chains` / `devices` (several independent chains,
     seed + c, in one call: returns a list of chain objects), `stephens` (relabel=True: "device" runs
     Stephens' relabelling on the device; an object with batch / online runs host code on the hook
-    path, see _Relabel).
+    path, see _Relabel).  `newdata` (M x P binary rows the chain has not seen): the result gains
+    `predictive = {"lppd": (M,)}`, the log pointwise predictive density over the kept sweeps, computed on the
+    device; `predictive_trace=True` adds "logdens", the (S, M) trace of log p(x_m | state of sweep s) (without
+    burn-in its first row, the starting state, is NaN), `responsibilities=True` adds "resp", the (M, K) mean
+    normalised category weights -- in the sampler's label order of each sweep, so they mean something only for a
+    chain that does not switch labels (relabel=True does not reorder them).  The predictive itself does not
+    depend on the labels.
     """
     X = _capi.as_x(data)
     N, P = X.shape
@@ -310,6 +368,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
     chains = int(chains)
+    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
     if chains > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
@@ -329,41 +388,42 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
         z = _np.empty((S, N), dtype=_np.int32, order="F")
         theta = _np.zeros((K, P, S), order="F")
         al = _np.zeros((S, 1), order="F")
-        with _progress(debug):
-            rc = _capi.lib().bmm_collapsed_run_relabel(
-                _capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(K),
+        args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(K),
                 _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
-                _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al), dr.ref())
-        return dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta})
+                _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
+        with _progress(debug):
+            rc = _run("collapsed", args, pr, rel=dr)
+        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr)
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((K, P, S), order="F")
     al = _np.zeros((S, 1), order="F")
-    with _progress(debug):
-        rc = _capi.lib().bmm_collapsed_run_probs(
-            _capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(K),
+    args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(K),
             _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
-            _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al),
-            rl.ref() if rl else None)
+            _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
+    with _progress(debug):
+        rc = _run("collapsed", args, pr, hooks=rl)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
-        return rl.finish(rc, out)
+        return _with_predictive(rl.finish(rc, out), pr)
     _capi.check(rc)
-    return out
+    return _with_predictive(out, pr)
 
 
 def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=None, relabel=False,
              burnrelabel=50, maxK=30, debug=False, *, seed=None, batch=None, device=0, chains=1, devices=None,
-             stephens=None):
+             stephens=None, newdata=None, predictive_trace=False, responsibilities=False):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
-    (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27)."""
+    (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`: as
+    gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column."""
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, maxK = int(nsamples), int(maxK)
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
+    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, maxK + 1, predictive_trace, responsibilities, chains)
     if int(chains) > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
@@ -376,40 +436,43 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
         z = _np.empty((S, N), dtype=_np.int32, order="F")
         theta = _np.zeros((maxK, P, S), order="F")
         al = _np.zeros((S, 1), order="F")
-        with _progress(debug):
-            rc = _capi.lib().bmm_dp_run_relabel(
-                _capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(nsamples),
+        args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(nsamples),
                 _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int(maxK),
                 _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
-                _capi.vp(theta), _capi.vp(al), dr.ref())
-        return dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta})
+                _capi.vp(theta), _capi.vp(al))
+        with _progress(debug):
+            rc = _run("dp", args, pr, rel=dr)
+        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr)
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((maxK, P, S), order="F")
     al = _np.zeros((S, 1), order="F")
-    with _progress(debug):
-        rc = _capi.lib().bmm_dp_run_probs(
-            _capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(nsamples),
+    args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(nsamples),
             _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int(maxK),
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
-            _capi.vp(theta), _capi.vp(al), rl.ref() if rl else None)
+            _capi.vp(theta), _capi.vp(al))
+    with _progress(debug):
+        rc = _run("dp", args, pr, hooks=rl)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
-        return rl.finish(rc, out)
+        return _with_predictive(rl.finish(rc, out), pr)
     _capi.check(rc)
-    return out
+    return _with_predictive(out, pr)
 
 
 def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, burnin, relabel, burnrelabel, seed,
-              device, initial_pi, initial_theta, chains, devices, stephens, debug=False):
+              device, initial_pi, initial_theta, chains, devices, stephens, debug=False, newdata=None,
+              predictive_trace=False, responsibilities=False):
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, K = int(nsamples), int(K)
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
     chains = int(chains)
+    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
+    base = fn[len("bmm_"):-len("_run_probs")]
 
     def start(sd, pi, th):
         rng = _np.random.default_rng(sd)
@@ -441,46 +504,51 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
         theta = _np.zeros((K, P, S), order="F")
         al = _np.zeros((S, 1), order="F")
         pi = _np.zeros((S, K), order="F")
-        with _progress(debug):
-            rc = getattr(_capi.lib(), fn.replace("_probs", "_relabel"))(
-                _capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(pi0), _capi.vp(th0), _C.c_int(nsamples),
+        args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(pi0), _capi.vp(th0), _C.c_int(nsamples),
                 _C.c_int(K), _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta),
                 _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
-                _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al), dr.ref())
-        return dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta})
+                _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
+        with _progress(debug):
+            rc = _run(base, args, pr, rel=dr)
+        return _with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr)
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((K, P, S), order="F")
     al = _np.zeros((S, 1), order="F")
     pi = _np.zeros((S, K), order="F")
-    with _progress(debug):
-        rc = getattr(_capi.lib(), fn)(
-            _capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(pi0), _capi.vp(th0), _C.c_int(nsamples),
+    args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(pi0), _capi.vp(th0), _C.c_int(nsamples),
             _C.c_int(K), _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta),
             _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
-            _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al), rl.ref() if rl else None)
+            _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
+    with _progress(debug):
+        rc = _run(base, args, pr, hooks=rl)
     out = {"pi": pi, "alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
-        return rl.finish(rc, out)
+        return _with_predictive(rl.finish(rc, out), pr)
     _capi.check(rc)
-    return out
+    return _with_predictive(out, pr)
 
 
 def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
                         relabel=False, burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None,
-                        initial_theta=None, chains=1, devices=None, stephens=None):
+                        initial_theta=None, chains=1, devices=None, stephens=None, newdata=None,
+                        predictive_trace=False, responsibilities=False):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
-    src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch."""
+    src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
+    `predictive_trace`, `responsibilities`: as gibbs_collapsed."""
     return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
-                     burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug)
+                     burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
+                     newdata, predictive_trace, responsibilities)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
                burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None, initial_theta=None, chains=1,
-               devices=None, stephens=None):
-    """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32)."""
+               devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False):
+    """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
+    `predictive_trace`, `responsibilities`: as gibbs_collapsed."""
     return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
-                     relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug)
+                     relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
+                     newdata, predictive_trace, responsibilities)
 
 
 class Chain:
@@ -496,6 +564,7 @@ class Chain:
         self._h = _C.c_void_p()
         self.sampler, self.N, self.P, self.K = sampler, int(N), int(P), int(K)
         self._keep = None
+        self._M = 0
         rc = _capi.lib().bmm_chain_create(
             _C.byref(self._h), _C.c_int(self._CODE[sampler]), _C.c_int64(N), _C.c_int(P), _C.c_int(K),
             _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
@@ -637,6 +706,56 @@ class Chain:
         theta = _np.zeros((self.K, self.P), order="F")
         _capi.check(_capi.lib().bmm_chain_get_params(self._h, _capi.vp(pi), _capi.vp(theta)))
         return pi, theta
+
+    # -- posterior predictive density of new rows (include/bmm_mcmc.h)
+    def set_newdata(self, Xnew, responsibilities=False):
+        """M x P binary rows the chain has not seen, validated and packed on the device; replaces any earlier set and
+        empties the accumulators (None or zero rows: drops it).  `responsibilities`: sweeps_predict also accumulates
+        the mean normalised category weights (Kc more doubles per row and sweep)."""
+        if Xnew is None:
+            Xnew = _np.zeros((0, self.P), dtype=_np.int32)
+        Xn = _capi.as_x(Xnew)
+        if Xn.shape[1] != self.P:
+            raise ValueError("newdata must have the %d columns of data" % self.P)
+        _capi.check(_capi.lib().bmm_chain_predict_responsibilities(self._h, _C.c_int(1 if responsibilities else 0)))
+        _capi.check(_capi.lib().bmm_chain_set_newdata_host(self._h, _capi.vp(Xn), _C.c_int64(Xn.shape[0])))
+        self._M = Xn.shape[0]
+
+    def _kc(self):
+        return self.K + 1 if self.sampler == "dp" else self.K
+
+    def predict_state(self, responsibilities=False):
+        """log p(x_m | current state) for every new row, (M,); no sweep is run and the accumulators are untouched.
+        With responsibilities=True returns (logdens, resp): resp (M, Kc) are the normalised category weights (DP:
+        the maxK labels, then the new-cluster column), in the sampler's label order."""
+        ld = _np.zeros(self._M)
+        rp = _np.zeros((self._M, self._kc()), order="F") if responsibilities else None
+        _capi.check(_capi.lib().bmm_chain_predict_state(self._h, _capi.vp(ld), _capi.vp(rp) if responsibilities else None))
+        return (ld, rp) if responsibilities else ld
+
+    def sweeps_predict(self, n, trace=False):
+        """n more sweeps, each state folded into the running predictive.  trace=True returns the (n, M) matrix of
+        log p(x_m | state after sweep s) (and waits); otherwise returns None without waiting, as sweeps()."""
+        out = _np.zeros((n, self._M), order="F") if trace else None
+        _capi.check(_capi.lib().bmm_chain_sweeps_predict(self._h, _C.c_int(n), _capi.vp(out) if trace else None))
+        return out
+
+    def predictive(self, responsibilities=False):
+        """{"lppd": (M,), "n": states folded, "resp": (M, Kc) with responsibilities=True} over the sweeps folded so
+        far.  resp is in the sampler's label order of each sweep: it means something only for a chain that does not
+        switch labels."""
+        lp = _np.zeros(self._M)
+        rp = _np.zeros((self._M, self._kc()), order="F") if responsibilities else None
+        n = _C.c_int(0)
+        _capi.check(_capi.lib().bmm_chain_get_predictive(self._h, _capi.vp(lp), _capi.vp(rp) if responsibilities else None,
+                                                         _C.byref(n)))
+        out = {"lppd": lp, "n": n.value}
+        if responsibilities:
+            out["resp"] = rp
+        return out
+
+    def predict_reset(self):
+        _capi.check(_capi.lib().bmm_chain_predict_reset(self._h))
 
     def profile(self, every=1):
         """Time the resample launches of every `every`-th sweep with HIP events (0/False: off)."""

@@ -492,6 +492,32 @@ resample_fn resample_kernel_small_of(int kt, int minus, bool bits) {
     return minus == 0 ? resample_kernel_small<0, false>(kt) : resample_kernel_small<1, false>(kt);
 }
 
+
+// The predictive kernel (k_predict) by accumulator count and group width: one workgroup size, one lane per row.
+typedef void (*predict_fn)(ChainParams, PredictArgs);
+template <int GW>
+predict_fn predict_kernel_w(int kt) {
+    switch (kt) {
+        case 4: return k_predict<4, kPredictThreads, GW>;
+        case 8: return k_predict<8, kPredictThreads, GW>;
+        case 12: return k_predict<12, kPredictThreads, GW>;
+        case 16: return k_predict<16, kPredictThreads, GW>;
+        case 20: return k_predict<20, kPredictThreads, GW>;
+        case 24: return k_predict<24, kPredictThreads, GW>;
+        case 28: return k_predict<28, kPredictThreads, GW>;
+        case 32: return k_predict<32, kPredictThreads, GW>;
+        case 40: return k_predict<40, kPredictThreads, GW>;
+        case 48: return k_predict<48, kPredictThreads, GW>;
+        case 52: return k_predict<52, kPredictThreads, GW>;
+        case 56: return k_predict<56, kPredictThreads, GW>;
+        case 64: return k_predict<64, kPredictThreads, GW>;
+        default: return nullptr;
+    }
+}
+predict_fn predict_kernel(int kt, int gw) {
+    return gw == kGroupW ? predict_kernel_w<kGroupW>(kt) : predict_kernel_w<kGroupWAlt>(kt);
+}
+
 }  // namespace
 
 struct bmm_chain {
@@ -557,6 +583,21 @@ struct bmm_chain {
     int* dSelfDone = nullptr;     // SELF kernels: workgroups of the running launch that have read the statistics
     int32_t *dDNkAlt = nullptr, *dDSAlt = nullptr;  // ... and the second set of delta accumulators (self_fold_prev)
     int* dDbgFlag = nullptr;      // -DBMM_DEBUG_HOOKS: raised by a kernel that meets a label out of range
+    // posterior predictive of new rows: their bit planes [ceil(P/32)][predM], the predictive
+    // table image of the counting samplers (the explicit samplers' own image dTab is the predictive image), the
+    // accumulators that live across sweeps, and what a sweep folds while pred_fold is set
+    int64_t predM = 0;
+    uint32_t* dXnb = nullptr;
+    double *dPredTab = nullptr, *dPredMax = nullptr, *dPredSum = nullptr, *dRespAcc = nullptr;
+    bool pred_resp = false;       // the responsibilities are accumulated too
+    int pred_folded = 0;          // states folded so far
+    predict_fn pfn = nullptr;
+    int pred_grid_max = 0;
+    size_t pred_lds = 0;
+    bool pred_fold = false;       // sweeps j >= pred_from are folded as they are enqueued
+    int pred_from = 0;
+    double* pred_trace = nullptr; // or [..][predM] on the device: row j - pred_trace_base receives sweep j's logdens
+    int pred_trace_base = 0;
     int prof = 0;             // > 0: HIP events around the resample launches of every prof-th sweep
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
@@ -931,6 +972,42 @@ int launch_count_tables(bmm_chain* c) {
     return BMM_OK;
 }
 
+// ---- posterior predictive of new rows ----
+// Score the chain's new rows against its current state, stream-ordered behind whatever produced that state:
+// logdens / resp receive this state's values (device, may be null); fold adds it to the accumulators.
+int enqueue_predict(bmm_chain* c, double* logdens, double* resp, bool fold) {
+    const ChainParams& p = c->p;
+    if (c->predM <= 0) return BMM_OK;
+    const double* tab = c->dTab;  // stick-breaking / full: group tables of (pi, theta), log pi in group 0
+    if (!explicit_params(p.mode)) {
+        hipLaunchKernelGGL(k_predict_tables, dim3(p.KT), dim3(256), 0, c->stream, p, c->dNk, c->dS, c->dDNk, c->dDS,
+                           c->dAlpha, c->dPredTab);
+        HIP_TRY(hipGetLastError());
+        tab = c->dPredTab;
+    }
+    PredictArgs a{};
+    a.Xb = c->dXnb; a.M = c->predM; a.tab = tab; a.logdens = logdens; a.resp = resp;
+    if (fold) { a.run_max = c->dPredMax; a.run_sum = c->dPredSum; a.resp_acc = c->pred_resp ? c->dRespAcc : nullptr; }
+    if (c->generic) {
+        const int64_t nb = (c->predM + 255) / 256, maxb = c->scratch_stride / 256;
+        hipLaunchKernelGGL(k_predict_generic, dim3((unsigned)(nb < maxb ? nb : maxb)), dim3(256), 0, c->stream, p, a,
+                           c->dScratch, c->scratch_stride);
+    } else {
+        const int64_t ntiles = (c->predM + kPredictThreads - 1) / kPredictThreads;
+        const int grid = (int)(ntiles < c->pred_grid_max ? ntiles : c->pred_grid_max);
+        hipLaunchKernelGGL(c->pfn, dim3(grid), dim3(kPredictThreads), c->pred_lds, c->stream, p, a);
+    }
+    HIP_TRY(hipGetLastError());
+    if (fold) c->pred_folded++;
+    return BMM_OK;
+}
+// the end of sweep j: its state is folded when a predictive run or bmm_chain_sweeps_predict asked for it
+int sweep_end_predict(bmm_chain* c, int j) {
+    if (!c->pred_fold || c->predM <= 0 || j < c->pred_from) return BMM_OK;
+    double* row = c->pred_trace ? c->pred_trace + (size_t)(j - c->pred_trace_base) * (size_t)c->predM : nullptr;
+    return enqueue_predict(c, row, nullptr, true);
+}
+
 // one sweep (index j >= 1) enqueued on the stream
 // phase 0: whole sweep; 1: z-resample only; 2: parameter draws and tables only (sharded chains)
 int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
@@ -956,7 +1033,7 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
         hipLaunchKernelGGL(k_sb_theta_tables, dim3(p.KT + 1), dim3(256), 0, c->stream, p, c->dNk, c->dS,
                            c->dPi, c->dTheta, 1, (uint32_t)j, th_tr, c->dTab, c->dAlpha, al_tr, c->dViable);
         HIP_TRY(hipGetLastError());
-        return BMM_OK;
+        return sweep_end_predict(c, j);
     }
     int64_t lo = 0;
     while (lo < p.N) {
@@ -977,7 +1054,7 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
     hipLaunchKernelGGL(k_count_sweep_end, dim3(1), dim3(1024), 0, c->stream, p, c->dNk, c->dS, c->dDNk,
                        c->dDS, c->dAlpha, (uint32_t)j, th_tr, al_tr, nk_tr);
     HIP_TRY(hipGetLastError());
-    return BMM_OK;
+    return sweep_end_predict(c, j);
 }
 
 // The resident kernel for this chain's shape, workgroup size and X layout (c->bits).
@@ -1275,7 +1352,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     }
     dev_pool().put(c->device, c->arena, c->arena_bytes);  // the stream is idle (synchronised above)
     dev_pool().put(c->device, c->run_arena, c->run_arena_bytes);
-    void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot};
+    void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     chain_stream_release(c->device, c->stream, c->stream_kind);  // synchronised above
@@ -1697,6 +1774,226 @@ int bmm_chain_kernel_form(const bmm_chain* c, int* lanes_per_observation, int* b
     if (lanes_per_observation) *lanes_per_observation = c->generic || c->OT <= 0 ? 1 : c->NT / c->OT;
     if (builds_own_tables) *builds_own_tables = c->self_tables ? 1 : 0;
     return BMM_OK;
+}
+
+// ---- posterior predictive of new rows ----
+static int pred_refused(const bmm_chain* c) {
+    if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the predictive density is not offered on a sharded chain");
+    return BMM_OK;
+}
+static int pred_reset(bmm_chain* c) {
+    c->pred_folded = 0;
+    if (c->predM <= 0) return BMM_OK;
+    const int64_t nb = (c->predM + 255) / 256;
+    hipLaunchKernelGGL(k_predict_reset, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, c->stream, c->predM,
+                       c->dPredMax, c->dPredSum);
+    HIP_TRY(hipGetLastError());
+    if (c->dRespAcc) HIP_TRY(hipMemsetAsync(c->dRespAcc, 0, (size_t)c->predM * c->p.Kc * sizeof(double), c->stream));
+    return BMM_OK;
+}
+// the predictive kernel of the chain's shape, set up on first use
+static int pred_setup(bmm_chain* c) {
+    if (c->generic || c->pfn) return BMM_OK;
+    predict_fn f = predict_kernel(c->p.KT, c->p.W);
+    if (!f) return set_err(BMM_E_STATE, "no predictive kernel for %d accumulators", c->p.KT);
+    const size_t lds = (size_t)layout_of(c->p, false).head() * sizeof(double);
+    if (lds > kLdsMax) return set_err(BMM_E_STATE, "the predictive table image (%zu bytes) does not fit in LDS", lds);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    int per_cu = 0;
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(f), kPredictThreads, lds);
+    if (e != hipSuccess) return set_err(BMM_E_HIP, "kernel set-up failed: %s", hipGetErrorString(e));
+    c->pfn = f;
+    c->pred_lds = lds;
+    c->pred_grid_max = (per_cu < 1 ? 1 : per_cu) * c->num_cus;
+    return BMM_OK;
+}
+// device memory for `bytes` more, refused with a message when it is not there
+static int pred_room(size_t bytes, const char* what) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (bytes > free_b)
+        return set_err(BMM_E_ARG, "predictive: %s needs %zu bytes of device memory, %zu are free", what, bytes, free_b);
+    return BMM_OK;
+}
+// rows x M log densities on the device (row-major) into the caller's rows x M column-major matrix
+static int pred_trace_out(bmm_chain* c, const double* dtrace, int rows, double* out, int ld, int row0) {
+    const int64_t M = c->predM;
+    std::vector<double> line((size_t)M);
+    for (int s = 0; s < rows; ++s) {
+        HIP_TRY(hipMemcpy(line.data(), dtrace + (size_t)s * (size_t)M, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
+        for (int64_t m = 0; m < M; ++m) out[(size_t)(row0 + s) + (size_t)m * (size_t)ld] = line[(size_t)m];
+    }
+    return BMM_OK;
+}
+
+int bmm_chain_predict_responsibilities(bmm_chain* c, int on) {
+    if (!c) return set_err(BMM_E_ARG, "null chain");
+    int rc = pred_refused(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->pred_resp = on != 0;
+    if (c->dRespAcc && !c->pred_resp) { (void)hipFree(c->dRespAcc); c->dRespAcc = nullptr; }
+    if (c->pred_resp && !c->dRespAcc && c->predM > 0) {
+        const size_t bytes = (size_t)c->predM * c->p.Kc * sizeof(double);
+        rc = pred_room(bytes, "the responsibilities (M x Kc doubles)");
+        if (rc) { c->pred_resp = false; return rc; }
+        HIP_TRY(hipMalloc(&c->dRespAcc, bytes));
+    }
+    return pred_reset(c);
+}
+
+int bmm_chain_set_newdata_host(bmm_chain* c, const int32_t* Xnew, int64_t M) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (M < 0) return set_err(BMM_E_ARG, "M must be >= 0");
+        if (M > 0 && !Xnew) return set_err(BMM_E_ARG, "Xnew is null");
+        int rc = pred_refused(c);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // nothing still reads the set that goes
+        auto drop = [&]() {
+            void** bufs[] = {reinterpret_cast<void**>(&c->dXnb), reinterpret_cast<void**>(&c->dPredMax),
+                             reinterpret_cast<void**>(&c->dPredSum), reinterpret_cast<void**>(&c->dRespAcc)};
+            for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+            c->predM = 0;
+            c->pred_folded = 0;
+        };
+        if (M == 0) { drop(); return BMM_OK; }
+        rc = pred_setup(c);
+        if (rc) return rc;
+        const int P = c->p.P, W = (P + 31) / 32, Kc = c->p.Kc;
+        int64_t slab = ((int64_t)64 << 20) / ((int64_t)P * 4);  // rows per staged piece of the int32 matrix
+        slab = slab / 4096 * 4096;
+        if (slab < 4096) slab = 4096;
+        if (slab > M) slab = M;
+        const size_t resp_bytes = c->pred_resp ? (size_t)M * Kc * sizeof(double) : 0;
+        rc = pred_room((size_t)W * M * 4 + (size_t)2 * M * 8 + resp_bytes + (size_t)slab * P * 4, "the new rows and their accumulators");
+        if (rc) return rc;
+        DevBuf planes, mx, sm, ra, stage;
+        HIP_TRY(planes.alloc((size_t)W * M * sizeof(uint32_t)));
+        HIP_TRY(mx.alloc((size_t)M * sizeof(double)));
+        HIP_TRY(sm.alloc((size_t)M * sizeof(double)));
+        if (resp_bytes) HIP_TRY(ra.alloc(resp_bytes));
+        HIP_TRY(stage.alloc((size_t)slab * P * sizeof(int32_t)));
+        if (!explicit_params(c->p.mode) && !c->dPredTab)
+            HIP_TRY(hipMalloc(&c->dPredTab, (size_t)layout_of(c->p, false).head() * sizeof(double)));
+        // validated and packed on the device, a slab of rows at a time (k_validate_binary, k_pack_bits)
+        for (int64_t i0 = 0; i0 < M; i0 += slab) {
+            const int64_t rows = M - i0 < slab ? M - i0 : slab;
+            HIP_TRY(hipMemcpy2DAsync(stage.p, (size_t)rows * 4, Xnew + i0, (size_t)M * 4, (size_t)rows * 4, (size_t)P,
+                                     hipMemcpyHostToDevice, c->stream));
+            rc = validate_binary(c, stage.as<int32_t>(), rows * P);  // waits
+            if (rc == BMM_E_ARG) return set_err(BMM_E_ARG, "newdata must be binary: Xnew holds a value other than 0 and 1");
+            if (rc) return rc;
+            const int64_t nb = (rows + 255) / 256;
+            hipLaunchKernelGGL(k_pack_bits, dim3((unsigned)(nb < 16384 ? nb : 16384)), dim3(256), 0, c->stream,
+                               stage.as<int32_t>(), rows, rows, P, planes.as<uint32_t>() + i0, M);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        drop();
+        c->dXnb = planes.as<uint32_t>(); planes.p = nullptr;
+        c->dPredMax = mx.as<double>(); mx.p = nullptr;
+        c->dPredSum = sm.as<double>(); sm.p = nullptr;
+        c->dRespAcc = ra.as<double>(); ra.p = nullptr;
+        c->predM = M;
+        return pred_reset(c);
+    });
+}
+
+int bmm_chain_predict_state(bmm_chain* c, double* logdens_out, double* resp_out) {
+    return guarded([&]() -> int {
+        if (!c || !logdens_out) return set_err(BMM_E_ARG, "null argument");
+        int rc = pred_refused(c);
+        if (rc) return rc;
+        if (c->predM <= 0) return set_err(BMM_E_STATE, "no new data set (bmm_chain_set_newdata_host)");
+        HIP_TRY(hipSetDevice(c->device));
+        if (!c->started) { rc = chain_start(c); if (rc) return rc; }
+        const size_t M = (size_t)c->predM, Kc = (size_t)c->p.Kc;
+        DevBuf ld, rp;
+        HIP_TRY(ld.alloc(M * sizeof(double)));
+        if (resp_out) {
+            rc = pred_room(M * Kc * sizeof(double), "the responsibilities (M x Kc doubles)");
+            if (rc) return rc;
+            HIP_TRY(rp.alloc(M * Kc * sizeof(double)));
+        }
+        rc = enqueue_predict(c, ld.as<double>(), resp_out ? rp.as<double>() : nullptr, false);
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+        hipError_t e = hipMemcpyAsync(logdens_out, ld.p, M * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && resp_out) e = hipMemcpyAsync(resp_out, rp.p, M * Kc * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);  // the scratch goes out of scope
+        if (e != hipSuccess || e2 != hipSuccess) return set_err(BMM_E_HIP, "copying the predictive failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_sweeps_predict(bmm_chain* c, int n, double* logdens_trace) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (n < 0) return set_err(BMM_E_ARG, "n must be >= 0");
+        int rc = pred_refused(c);
+        if (rc) return rc;
+        if (c->predM <= 0) return set_err(BMM_E_STATE, "no new data set (bmm_chain_set_newdata_host)");
+        if (n == 0) return BMM_OK;
+        HIP_TRY(hipSetDevice(c->device));
+        DevBuf tr;
+        if (logdens_trace) {
+            const size_t bytes = (size_t)n * (size_t)c->predM * sizeof(double);
+            rc = pred_room(bytes, "the log-density trace (n x M doubles)");
+            if (rc) return rc;
+            HIP_TRY(tr.alloc(bytes));
+        }
+        c->pred_fold = true;
+        c->pred_from = c->sweep + 1;
+        c->pred_trace = tr.as<double>();
+        c->pred_trace_base = c->sweep + 1;
+        rc = bmm_chain_sweeps(c, n);
+        c->pred_fold = false;
+        c->pred_trace = nullptr;
+        if (!logdens_trace) return rc;  // as bmm_chain_sweeps: enqueued, not waited for
+        const hipError_t e = hipStreamSynchronize(c->stream);  // the trace buffer goes out of scope
+        if (rc) return rc;
+        if (e != hipSuccess) return set_err(BMM_E_HIP, "the sweeps failed: %s", hipGetErrorString(e));
+        return pred_trace_out(c, tr.as<double>(), n, logdens_trace, n, 0);
+    });
+}
+
+int bmm_chain_get_predictive(bmm_chain* c, double* lppd, double* resp, int* n_folded) {
+    return guarded([&]() -> int {
+        if (!c || !lppd) return set_err(BMM_E_ARG, "null argument");
+        int rc = pred_refused(c);
+        if (rc) return rc;
+        if (c->predM <= 0) return set_err(BMM_E_STATE, "no new data set (bmm_chain_set_newdata_host)");
+        if (resp && !c->pred_resp) return set_err(BMM_E_STATE, "the responsibilities were not accumulated (bmm_chain_predict_responsibilities)");
+        if (n_folded) *n_folded = c->pred_folded;
+        if (c->pred_folded < 1) return set_err(BMM_E_STATE, "no state has been folded yet (bmm_chain_sweeps_predict)");
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t M = (size_t)c->predM, Kc = (size_t)c->p.Kc;
+        DevBuf lp, rp;
+        HIP_TRY(lp.alloc(M * sizeof(double)));
+        if (resp) {
+            rc = pred_room(M * Kc * sizeof(double), "the responsibilities (M x Kc doubles)");
+            if (rc) return rc;
+            HIP_TRY(rp.alloc(M * Kc * sizeof(double)));
+        }
+        const int64_t nb = ((int64_t)M + 255) / 256;
+        hipLaunchKernelGGL(k_predict_finish, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, c->stream, c->predM,
+                           c->p.Kc, c->pred_folded, c->dPredMax, c->dPredSum, c->dRespAcc, lp.as<double>(),
+                           resp ? rp.as<double>() : nullptr);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(lppd, lp.p, M * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && resp) e = hipMemcpyAsync(resp, rp.p, M * Kc * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess || e2 != hipSuccess) return set_err(BMM_E_HIP, "reading the predictive failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_predict_reset(bmm_chain* c) {
+    if (!c) return set_err(BMM_E_ARG, "null chain");
+    HIP_TRY(hipSetDevice(c->device));
+    return pred_reset(c);
 }
 
 }  // extern "C"
@@ -2294,10 +2591,16 @@ int check_run_args(const int32_t* X, int nsamples, int burnin, const RunIO& io, 
 
 int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int K, double alpha, double beta,
               double gamma, double a, double b, int burnin, int64_t batch, uint64_t seed, int device,
-              const RunIO& io, const bmm_relabel_hooks* hooks, const bmm_relabel_out* rel = nullptr) {
+              const RunIO& io, const bmm_relabel_hooks* hooks, const bmm_relabel_out* rel = nullptr,
+              const int32_t* Xnew = nullptr, int64_t M = 0, const bmm_predict_out* pred = nullptr) {
     return guarded([&]() -> int {
         int rc = check_run_args(X, nsamples, burnin, io, sampler);
         if (rc) return rc;
+        if (pred) {  // refused before any device is touched
+            if (M < 0) return set_err(BMM_E_ARG, "M must be >= 0");
+            if (M > 0 && !Xnew) return set_err(BMM_E_ARG, "Xnew is null");
+            if (M > 0 && !pred->lppd) return set_err(BMM_E_ARG, "null buffer: lppd");
+        }
         if (rel) {  // refused before any device is touched
             if (!rel->permutations || !rel->z_original || !rel->theta_original) return set_err(BMM_E_ARG, "null buffer");
             if (burnin < 2 || rel->burnrelabel < 1)
@@ -2337,7 +2640,48 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             }
             if (rc) return rc;
             clock.lap(0);
+            // the predictive of new rows: every kept sweep is folded as it is enqueued (sweep_end_predict)
+            const bool predict = pred && M > 0;
+            const int S = nsamples - burnin;
+            DevBuf ptrace;
+            if (predict) {
+                c->pred_resp = pred->resp != nullptr;
+                rc = bmm_chain_set_newdata_host(c, Xnew, M);
+                if (rc) return rc;
+                if (pred->logdens) {
+                    const size_t bytes = (size_t)S * (size_t)M * sizeof(double);
+                    rc = pred_room(bytes, "the log-density trace (S x M doubles)");
+                    if (rc) return rc;
+                    HIP_TRY(ptrace.alloc(bytes));
+                }
+                c->pred_fold = true;
+                c->pred_from = burnin > 0 ? burnin : 1;  // (trace row 0 of a run without burn-in is the start, not a sweep)
+                c->pred_trace = ptrace.as<double>();
+                c->pred_trace_base = burnin;
+            }
             rc = run_body(c, nsamples, io, hooks, rel);
+            c->pred_fold = false;
+            c->pred_trace = nullptr;
+            if (predict) {
+                const hipError_t es = hipStreamSynchronize(c->stream);  // before ptrace may go
+                if (rc == BMM_OK && es != hipSuccess) rc = set_err(BMM_E_HIP, "the run failed: %s", hipGetErrorString(es));
+            }
+            if (rc == BMM_OK && predict) {
+                const double nan = std::nan("");
+                if (c->pred_folded < 1) {
+                    for (int64_t m = 0; m < M; ++m) pred->lppd[m] = nan;
+                    if (pred->resp) for (int64_t q = 0; q < M * c->p.Kc; ++q) pred->resp[q] = nan;
+                } else {
+                    rc = bmm_chain_get_predictive(c, pred->lppd, pred->resp, nullptr);
+                }
+                if (rc == BMM_OK && pred->logdens) {
+                    const int first = c->pred_from - burnin;  // 1 without burn-in: that row stays NaN
+                    for (int s = 0; s < first && s < S; ++s)
+                        for (int64_t m = 0; m < M; ++m) pred->logdens[(size_t)s + (size_t)m * (size_t)S] = nan;
+                    if (S > first)
+                        rc = pred_trace_out(c, ptrace.as<double>() + (size_t)first * (size_t)M, S - first, pred->logdens, S, first);
+                }
+            }
             clock.t = std::chrono::steady_clock::now();
         }
         clock.lap(5);  // releasing the chain
@@ -2483,6 +2827,47 @@ int bmm_full_run_probs(const int32_t* X, int64_t N, int P, const double* initial
     io.theta_out = theta_out; io.alpha_out = alpha_out;
     return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
                      hooks);
+}
+
+// ---- the runs above with the posterior predictive of new rows ---------
+int bmm_collapsed_run_predict(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int K,
+                              double alpha, double beta, double gamma, double a, double b, int burnin,
+                              int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
+                              double* alpha_out, const int32_t* Xnew, int64_t M, const bmm_predict_out* pred) {
+    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
+    RunIO io; io.z0 = initialK; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
+    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
+                     device, io, pred->hooks, pred->relabel, Xnew, M, pred);
+}
+int bmm_dp_run_predict(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
+                       double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
+                       int32_t* z_out, double* theta_out, double* alpha_out, const int32_t* Xnew, int64_t M,
+                       const bmm_predict_out* pred) {
+    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
+    RunIO io; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
+    return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
+                     io, pred->hooks, pred->relabel, Xnew, M, pred);
+}
+int bmm_sb_run_predict(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                       int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b,
+                       int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
+                       double* alpha_out, const int32_t* Xnew, int64_t M, const bmm_predict_out* pred) {
+    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
+    RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
+    io.theta_out = theta_out; io.alpha_out = alpha_out;
+    return run_chain(BMM_SAMPLER_SB, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
+                     pred->hooks, pred->relabel, Xnew, M, pred);
+}
+int bmm_full_run_predict(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                         int nsamples, int K, double alpha, double beta, double gamma, double a, double b,
+                         int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out,
+                         double* theta_out, double* alpha_out, const int32_t* Xnew, int64_t M,
+                         const bmm_predict_out* pred) {
+    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
+    RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
+    io.theta_out = theta_out; io.alpha_out = alpha_out;
+    return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
+                     pred->hooks, pred->relabel, Xnew, M, pred);
 }
 
 // ---- relabel = TRUE with Stephens' relabelling on the device ---------------------------------

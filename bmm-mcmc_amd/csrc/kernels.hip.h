@@ -1691,6 +1691,269 @@ __global__ __launch_bounds__(256) void k_st_perm_identity(int32_t* __restrict__ 
     if (i < M * K) perm[i] = i / M;
 }
 
+// ---- posterior predictive density of new observations -------------------------
+// The z-step for an (N+1)-th observation that is not in the data: no own-cluster pass, no uniform, no draw,
+// no histogram -- the Kc category scores from the group tables, max-shift, expw, total, and then
+//   logdens = max + log(total) = log p(x | state).
+// New rows are always held as bit planes (k_pack_bits: word w of row m at Xb[w * M + m]).  A row is owned by one
+// lane, so the accumulators that live in global memory across sweeps are updated without atomics and in a
+// fixed order: the streaming log-sum-exp pair (run_max, run_sum) with
+//   sum_s p(x | s) = exp(run_max) * run_sum,
+// and, when asked for, the Kc running sums of the normalised category weights.
+struct PredictArgs {
+    const uint32_t* Xb;  // bit planes of the new rows
+    int64_t M;           // new rows
+    const double* tab;   // predictive table image: TableLayout without own-cluster tables (head() doubles)
+    double* logdens;     // or null: [M], log p(x_m | this state)
+    double* resp;        // or null: [Kc][M], this state's normalised category weights
+    double* run_max;     // or null (nothing is folded): [M] running maximum of logdens over the folded states
+    double* run_sum;     //   [M] sum over the folded states of exp(logdens - run_max)
+    double* resp_acc;    // or null: [Kc][M] running sums of the normalised category weights
+};
+
+// The predictive image of the counting samplers from the statistics as they stand (the pending deltas are added,
+// nothing is folded or cleared: this kernel changes no state of the chain).  One workgroup per category, laid out
+// as k_count_tables lays the image out, with the predictive constants in group 0:
+//   finite sampler  label k: log(n_k + alpha/K) - log(N + alpha), an empty label included (its prior weight and the
+//                   prior Bernoulli terms log(beta) - log(beta + gamma), log(gamma) - log(beta + gamma))
+//   DP              used label: log(n_k) - log(N + alpha); unused label: -inf; category K, the new cluster:
+//                   log(alpha) - log(N + alpha) with the prior Bernoulli terms as a per-feature table like any other
+// (N, not N - 1: the new row is not among the N fitted observations).  Same functions as k_count_tables: log_, div_,
+// term_x1 / term_x0, group_entry.
+__global__ __launch_bounds__(256) void k_predict_tables(ChainParams p, const int32_t* __restrict__ Nk,
+                                                        const int32_t* __restrict__ S,
+                                                        const int32_t* __restrict__ dNk,
+                                                        const int32_t* __restrict__ dS,
+                                                        const double* __restrict__ alpha_ptr,
+                                                        double* __restrict__ tab) {
+    __shared__ double e1[kMaxP], e0[kMaxP], cst[2];  // cst: the constant term, log(beta + gamma + n)
+    const int k = blockIdx.x;
+    const TableLayout L = layout_of(p, false);
+    const int P = p.P, K = p.K;
+    const bool is_label = k < K;
+    const bool dp_new = p.mode == MODE_DP && k == K;
+    const size_t KP = (size_t)K * P;
+    const int64_t n = is_label ? (int64_t)Nk[k] + delta_take(const_cast<int32_t*>(dNk), k, K) : 0;
+    const int half = threadIdx.x >> 7, dl = threadIdx.x & 127;
+    if (threadIdx.x == 0) {
+        const double alpha = *alpha_ptr;
+        const double ldN = log_((double)p.Ntot + alpha);
+        double c = neg_inf();
+        if (is_label && p.mode == MODE_COLLAPSED) c = log_((double)n + div_(alpha, (double)K)) - ldN;
+        else if (is_label && n > 0) c = log_((double)n) - ldN;
+        else if (dp_new) c = log_(alpha) - ldN;
+        cst[0] = c;
+        cst[1] = log_((p.beta + p.gamma) + (double)n);
+        tab[L.cp() + k] = c;
+        tab[L.cm() + k] = neg_inf();
+        reinterpret_cast<int32_t*>(tab + L.nk())[k] = (int32_t)n;
+    }
+    __syncthreads();
+    const bool scored = is_label || dp_new;  // accumulators past Kc keep all-zero tables under a -inf constant
+    for (int c0 = 0; c0 < P; c0 += kChunkP) {
+        const int pc = P - c0 < kChunkP ? P - c0 : kChunkP;
+        if (dl < pc) {
+            double t = 0.0;
+            if (scored) {
+                const int d = c0 + dl;
+                const int64_t s = is_label ? (int64_t)S[(size_t)k * P + d] + delta_take(const_cast<int32_t*>(dS), (size_t)k * P + d, KP) : 0;
+                t = half == 0 ? term_x1(p.beta, s, cst[1]) : term_x0(p.gamma, n, s, cst[1]);
+            }
+            if (half == 0) e1[dl] = t; else e0[dl] = t;
+        }
+        __syncthreads();
+        write_group_tables(p.W, e1, e0, pc, c0, p.KT, k, cst[0], tab + L.tp());
+        __syncthreads();
+    }
+    if (k == 0) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];  // 256 threads
+}
+
+// one new row's share of the accumulators; ld = log p(x | state), ET the exp256 table
+template <class Tab>
+__device__ __forceinline__ void predict_fold(const PredictArgs& a, int64_t m, double ld, Tab ET) {
+    const double rm = a.run_max[m], rs = a.run_sum[m];
+    const bool up = ld > rm;
+    const double e = expw_tab(up ? rm - ld : ld - rm, ET);  // (-inf and NaN arguments give exactly 0)
+    a.run_max[m] = up ? ld : rm;
+    a.run_sum[m] = up ? rs * e + 1.0 : rs + e;
+}
+
+// One lane per new row, KT accumulators, NT threads; the LDS image is the head of the table image and the exp256
+// table (no own-cluster tables, no histogram), read as k_resample reads it: one ds_read_b64 per category and
+// group, conflict-free.  The next tile's words are loaded before this tile is scored.
+constexpr int kPredictThreads = 512;
+template <int KT, int NT, int GW>
+__global__ __launch_bounds__(NT) void k_predict(ChainParams p, PredictArgs a) {
+    constexpr int GM = 1 << GW;
+    constexpr int CH = KT <= 24 ? KT : (KT <= 48 ? KT / 2 : KT / 4);  // lookups issued together
+    static_assert(KT % CH == 0, "chunking");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const TableLayout L{p.G, KT, 0, GM};
+    double* const lds = reinterpret_cast<double*>(smem);
+    const volatile lds_f64* const Tp = (const volatile lds_f64*)(lds + L.tp());
+    const lds_f64* const ET = (const lds_f64*)(lds + L.et());
+    const int P = p.P, G = p.G, Kc = p.Kc;
+    const int tid = threadIdx.x;
+    const int W = (P + 31) / 32;
+    const int64_t ntiles = (a.M + NT - 1) / NT;
+    int64_t tile = blockIdx.x;
+    uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+    if (tile < ntiles) {  // the first tile's words go out before the image is staged
+        const int64_t m0 = tile * NT + tid;
+        load_words(a.Xb, a.M, W, m0 < a.M ? m0 : a.M - 1, b0, b1, b2, b3);
+    }
+    {
+        const double2* src = reinterpret_cast<const double2*>(a.tab);
+        double2* dst = reinterpret_cast<double2*>(smem);
+        const int n2 = L.head() / 2;  // head() is even: every piece of the layout is
+        for (int i0 = tid; i0 < n2; i0 += NT * 8) {
+            double2 t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + u * NT;
+                t[u] = src[i < n2 ? i : n2 - 1];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + u * NT;
+                if (i < n2) dst[i] = t[u];
+            }
+        }
+    }
+    __syncthreads();
+    for (; tile < ntiles; tile += gridDim.x) {
+        const int64_t m = tile * NT + tid;
+        const bool valid = m < a.M;
+        const int64_t tnext = tile + gridDim.x;
+        uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
+        if (tnext < ntiles) {
+            const int64_t mn = tnext * NT + tid;
+            load_words(a.Xb, a.M, W, mn < a.M ? mn : a.M - 1, n0, n1, n2, n3);
+        }
+        double acc[KT];
+#pragma unroll
+        for (int k = 0; k < KT; ++k) acc[k] = 0.0;
+#pragma unroll 1
+        for (int h = 0; h < W; ++h) {
+            const uint32_t cur = word_of(h, b0, b1, b2, b3), nxt = word_of(h + 1, b0, b1, b2, b3);
+            const int g_lo = (32 * h + GW - 1) / GW;
+            int g_hi = (32 * (h + 1) + GW - 1) / GW;
+            g_hi = g_hi < G ? g_hi : G;
+#pragma unroll 1
+            for (int g = g_lo; g < g_hi; ++g) {
+                const unsigned nib = __builtin_amdgcn_alignbit(nxt, cur, (unsigned)(g * GW - 32 * h)) & (unsigned)(GM - 1);
+                const volatile lds_f64* row = Tp + ((size_t)g * KT * GM + nib);
+#pragma unroll
+                for (int c0 = 0; c0 < KT; c0 += CH) {
+                    double tv[CH];
+#pragma unroll
+                    for (int j = 0; j < CH; ++j) tv[j] = row[(c0 + j) * GM];
+#pragma unroll
+                    for (int j = 0; j < CH; ++j) acc[c0 + j] = acc[c0 + j] + tv[j];
+                    if (CH < KT) __builtin_amdgcn_sched_barrier(0);  // keep the chunks apart
+                }
+            }
+        }
+        double mx = neg_inf();
+#pragma unroll
+        for (int k = 0; k < KT; ++k) mx = __builtin_fmax(mx, acc[k]);
+        double tot = 0.0;
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            const double w = expw_tab(acc[k] - mx, ET);
+            tot = tot + w;
+            acc[k] = w;
+            if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);  // two at a time: bounds the temporaries
+        }
+        const double ld = mx + log_(tot);
+        if (valid) {
+            if (a.logdens) a.logdens[m] = ld;
+            if (a.run_max) predict_fold(a, m, ld, ET);
+            if (a.resp || a.resp_acc) {  // uniform
+#pragma unroll
+                for (int k = 0; k < KT; ++k) {
+                    if (k < Kc) {
+                        const double r = div_(acc[k], tot);
+                        if (a.resp) a.resp[(int64_t)k * a.M + m] = r;
+                        if (a.resp_acc) a.resp_acc[(int64_t)k * a.M + m] += r;
+                    }
+                }
+            }
+        }
+        b0 = n0; b1 = n1; b2 = n2; b3 = n3;
+    }
+}
+
+// Any shape (more than kMaxCats categories or P > kMaxP: the shapes k_resample_generic takes): tables gathered from
+// global memory, the scores in a per-thread scratch column scr[k * stride + thread], as there.  Same arithmetic and
+// the same order of sums as k_predict.
+__global__ __launch_bounds__(256) void k_predict_generic(ChainParams p, PredictArgs a, double* scr, int64_t stride) {
+    const TableLayout L = layout_of(p, false);
+    const int GM = L.M;
+    const double* const Tp = a.tab + L.tp();
+    const double* const ET = a.tab + L.et();
+    const int P = p.P, G = p.G, Kc = p.Kc, KT = p.KT;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // < stride: the host sizes the grid
+    double* const my = scr + gid;
+    for (int64_t m = gid; m < a.M; m += (int64_t)gridDim.x * blockDim.x) {
+        double mx = neg_inf();
+        for (int k0 = 0; k0 < Kc; k0 += 16) {
+            double acc[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[j] = 0.0;
+            for (int g = 0; g < G; ++g) {
+                const double* row = Tp + ((size_t)g * KT + k0) * GM + field_from_x(nullptr, a.Xb, a.M, P, m, g, p.W);
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if (k0 + j < Kc) acc[j] = acc[j] + row[j * GM];
+            }
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (k0 + j < Kc) {
+                    my[(int64_t)(k0 + j) * stride] = acc[j];
+                    mx = __builtin_fmax(mx, acc[j]);
+                }
+        }
+        double tot = 0.0;
+        for (int k = 0; k < Kc; ++k) {
+            const double w = expw_tab(my[(int64_t)k * stride] - mx, ET);
+            tot = tot + w;
+            my[(int64_t)k * stride] = w;
+        }
+        const double ld = mx + log_(tot);
+        if (a.logdens) a.logdens[m] = ld;
+        if (a.run_max) predict_fold(a, m, ld, ET);
+        if (a.resp || a.resp_acc)
+            for (int k = 0; k < Kc; ++k) {
+                const double r = div_(my[(int64_t)k * stride], tot);
+                if (a.resp) a.resp[(int64_t)k * a.M + m] = r;
+                if (a.resp_acc) a.resp_acc[(int64_t)k * a.M + m] += r;
+            }
+    }
+}
+
+// empty accumulators: no state folded
+__global__ __launch_bounds__(256) void k_predict_reset(int64_t M, double* __restrict__ run_max, double* __restrict__ run_sum) {
+    for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < M; m += (int64_t)gridDim.x * 256) {
+        run_max[m] = neg_inf();
+        run_sum[m] = 0.0;
+    }
+}
+
+// The accumulators after n folded states: lppd = run_max + log(run_sum) - log(n), resp = resp_acc / n.  The
+// accumulators themselves are left as they are, so more sweeps may be folded afterwards.
+__global__ __launch_bounds__(256) void k_predict_finish(int64_t M, int Kc, int n, const double* __restrict__ run_max,
+                                                        const double* __restrict__ run_sum,
+                                                        const double* __restrict__ resp_acc,
+                                                        double* __restrict__ lppd, double* __restrict__ resp) {
+    const double ln = log_((double)n), dn = (double)n;
+    for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < M; m += (int64_t)gridDim.x * 256) {
+        lppd[m] = (run_max[m] + log_(run_sum[m])) - ln;
+        if (resp)
+            for (int k = 0; k < Kc; ++k) resp[(int64_t)k * M + m] = div_(resp_acc[(int64_t)k * M + m], dn);
+    }
+}
+
 // ---- self-check kernels ----------------------------------------------------------
 __global__ void k_test_math(int op, const double* in, const double* in2, double* out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

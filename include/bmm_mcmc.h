@@ -373,6 +373,75 @@ int bmm_chain_kernel_shape(const bmm_chain* c, int* lds_bytes, int* threads, int
  * batches).  Which form runs never changes a chain's values. */
 int bmm_chain_kernel_form(const bmm_chain* c, int* lanes_per_observation, int* builds_own_tables);
 
+/* ---- posterior predictive density of new observations ------------------------------
+ * For a state s of the chain (the state after a sweep) and a new binary row x of P features, the per-state
+ * predictive density p(x | s) is the model's posterior predictive given that state:
+ *   collapsed  (counts Nk, S; concentration alpha_s; N fitted observations), over all K labels:
+ *              sum_k (Nk + alpha/K)/(N + alpha) * prod_d (beta + S_kd)^x_d (gamma + Nk - S_kd)^(1-x_d) / (beta + gamma + Nk)
+ *              -- an empty label keeps its prior weight (alpha/K)/(N + alpha) and the prior Bernoulli terms;
+ *   dp         sum over used labels of Nk/(N + alpha) * (the same product), plus the new-cluster term
+ *              alpha/(N + alpha) * prod_d beta^x_d gamma^(1-x_d) / (beta + gamma);
+ *   sb, full   (pi_s, theta_s as returned for that sweep): sum_k pi_k prod_d theta_kd^x_d (1 - theta_kd)^(1-x_d).
+ * alpha_s is the value the next sweep's conditional would use.  These are proper densities (over all 2^P rows they
+ * sum to 1) and the samplers' own allocation conditionals for an (N+1)-th observation in all but two places, where
+ * the predictive uses the model's terms: the finite collapsed sampler gives an emptied label probability 0 for ever,
+ * and the DP sampler's new-cluster term is P * (log beta - log(beta + gamma)) whatever x is (equal to the term above
+ * only when beta == gamma).  The quantity does not depend on how the labels are numbered: it needs no relabelling.
+ *
+ * For M new rows and the S folded states:
+ *   lppd[m]       log((1/S) sum_s p(x_m | s)), the log pointwise predictive density;
+ *   logdens[s, m] log p(x_m | s), S x M column-major like the label trace;
+ *   resp[m, k]    the mean over the folded states of the normalised category weights, M x Kc column-major, Kc = K,
+ *                 for the DP sampler maxK labels and then the new-cluster column.  It is in the sampler's label
+ *                 order of each sweep, so it means something only for a chain that does not switch labels.
+ * Xnew is M x P int32 column-major (element (m, d) at Xnew[m + d*M]); it is validated (0/1) and packed into bit
+ * planes on the device.  Everything is enqueued on the chain's stream behind the sweep's last kernel: a folded
+ * sweep adds no synchronisation and no host-device copy.  Not offered on a sharded chain (bmm_chain_set_shard). */
+/* resident chains: the new rows; replaces any earlier set and empties the accumulators; M = 0 drops it */
+int bmm_chain_set_newdata_host(bmm_chain* c, const int32_t* Xnew, int64_t M);
+/* whether the folds also accumulate resp (off by default: Kc more doubles per row and fold); empties the accumulators */
+int bmm_chain_predict_responsibilities(bmm_chain* c, int on);
+/* the new rows against the current state, once: no sweep, accumulators untouched.  logdens_out M doubles, resp_out
+ * M x Kc or NULL.  Waits. */
+int bmm_chain_predict_state(bmm_chain* c, double* logdens_out, double* resp_out);
+/* n more sweeps, each folded into the accumulators; logdens_trace n x M column-major (then the call waits) or NULL
+ * (then it returns without waiting, as bmm_chain_sweeps).  BMM_E_ARG, naming the bytes, when the trace does not fit
+ * in device memory. */
+int bmm_chain_sweeps_predict(bmm_chain* c, int n, double* logdens_trace);
+/* lppd (M doubles) and resp (M x Kc, or NULL) over the states folded so far, and their number; the accumulators
+ * stay, so more sweeps may follow */
+int bmm_chain_get_predictive(bmm_chain* c, double* lppd, double* resp, int* n_folded);
+int bmm_chain_predict_reset(bmm_chain* c);
+
+/* One call: the *_run entry points plus Xnew, M and the outputs; only kept sweeps (j >= burnin) are folded.  Without
+ * burn-in the first kept row of the traces is the starting state, not a sweep: that row of logdens is NaN and
+ * lppd averages over the S - 1 sweeps.  relabel / hooks: NULL, or what the *_run_relabel / *_run_probs entry points
+ * take in their last argument -- the predictive does not depend on the labels, so it combines with either. */
+typedef struct bmm_predict_out {
+    double* lppd;                     /* M doubles */
+    double* logdens;                  /* S x M doubles column-major, or NULL */
+    double* resp;                     /* M x Kc doubles column-major, or NULL */
+    const bmm_relabel_out* relabel;   /* or NULL */
+    const bmm_relabel_hooks* hooks;   /* or NULL (ignored when relabel is set) */
+} bmm_predict_out;
+int bmm_collapsed_run_predict(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int K,
+                              double alpha, double beta, double gamma, double a, double b, int burnin,
+                              int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
+                              double* alpha_out, const int32_t* Xnew, int64_t M, const bmm_predict_out* pred);
+int bmm_dp_run_predict(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
+                       double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
+                       int32_t* z_out, double* theta_out, double* alpha_out, const int32_t* Xnew, int64_t M,
+                       const bmm_predict_out* pred);
+int bmm_sb_run_predict(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                       int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b,
+                       int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
+                       double* alpha_out, const int32_t* Xnew, int64_t M, const bmm_predict_out* pred);
+int bmm_full_run_predict(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                         int nsamples, int K, double alpha, double beta, double gamma, double a, double b,
+                         int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out,
+                         double* theta_out, double* alpha_out, const int32_t* Xnew, int64_t M,
+                         const bmm_predict_out* pred);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
