@@ -20,7 +20,7 @@ from .rdata import read_rdata_matrix  # the package's bundled data sets (data/*.
 
 __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "Chain", "BmmError", "NA_INTEGER", "set_progress",
            "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
-           "stephens_batch", "stephens_online", "DeviceStephens", "STEPHENS_MAX_K"]
+           "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -245,6 +245,21 @@ def stephens_online(Q, p, j, device=0, with_cost=False):
                                                        _C.c_int(K), _C.c_int(int(j)), _capi.vp(perm), _capi.vp(Qn),
                                                        _capi.vp(C)))
     return (perm, Qn, C) if with_cost else (perm, Qn)
+
+
+_PLAN_FIELDS = ("groups_online", "groups_batch", "rows_online", "rows_batch", "blocks_per_thread", "tile_rows",
+                "blocks", "thread_groups", "cost_in_lds", "cols_per_lane")
+
+
+def stephens_plan(N, K, M=0):
+    """Which form of the relabelling kernels the shape (N rows, K categories, M batch slices; M = 0: the online
+    step only) runs, read from the library's own launch arithmetic without touching a device (include/bmm_mcmc.h,
+    bmm_device_stephens_plan): a dict of workgroups and rows per workgroup of the cost pass (online, and per slice
+    of the batch), 4 x 4 blocks per thread, rows per LDS tile, blocks, thread groups, cost-in-LDS (0/1) and columns
+    per lane of the assignment."""
+    out = (_C.c_int64 * 12)()
+    _capi.check(_capi.lib().bmm_device_stephens_plan(_C.c_int64(int(N)), _C.c_int(int(K)), _C.c_int(int(M)), out))
+    return dict(zip(_PLAN_FIELDS, (int(v) for v in out)))
 
 
 class DeviceStephens:

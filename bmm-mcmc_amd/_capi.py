@@ -27,7 +27,7 @@ SYMBOLS = [
     "bmm_chain_planes_filled", "bmm_chain_shard_resample_async", "bmm_chain_stream",
     "bmm_chains_broadcast_planes", "bmm_set_progress", "bmm_last_run_phases", "bmm_host_threads", "bmm_multi_plan", "bmm_release_pools",
     "bmm_collapsed_run_relabel", "bmm_dp_run_relabel", "bmm_sb_run_relabel", "bmm_full_run_relabel",
-    "bmm_device_stephens_batch", "bmm_device_stephens_online",
+    "bmm_device_stephens_batch", "bmm_device_stephens_online", "bmm_device_stephens_plan",
     "bmm_chain_set_newdata_host", "bmm_chain_predict_responsibilities", "bmm_chain_predict_state",
     "bmm_chain_sweeps_predict", "bmm_chain_get_predictive", "bmm_chain_predict_reset",
     "bmm_collapsed_run_predict", "bmm_dp_run_predict", "bmm_sb_run_predict", "bmm_full_run_predict",

@@ -2044,7 +2044,7 @@ int run_prepare(bmm_chain* c, int nsamples, int burnin) {
     return BMM_OK;
 }
 
-// ---- Stephens' relabelling on the device (src/stephens.cpp as it executes; DESIGN.md section 9) ----
+// ---- Stephens' relabelling on the device (src/stephens.cpp as it executes; DESIGN.md section 11) ----
 // Workspace of one relabelling: the per-workgroup partial cost matrices, the K x K costs, Q (and log Q for the
 // batch), the batch's M x K permutation table.  Everything is stream-ordered: no host round trip.
 constexpr size_t kStPartialBudget = (size_t)64 << 20;  // bytes of partial cost matrices at most
@@ -2060,6 +2060,8 @@ int st_groups(int64_t N, int K, int slices) {
     if (G > cap_mem) G = cap_mem;
     return (int)(G < 1 ? 1 : G);
 }
+// rows of p per workgroup of the cost pass
+int64_t st_rows(int64_t N, int G) { return (N + G - 1) / G; }
 
 struct StWork {
     int64_t N = 0;
@@ -2100,9 +2102,8 @@ int st_check_k(int K) {
 int st_cost(hipStream_t st, StWork& w, const double* p, int64_t slice_stride, int slices, const double* q,
             bool q_is_log, bool batch_form) {
     const int K = w.K, G = slices > 1 ? w.GM : w.G1;
-    const int64_t rows = (w.N + G - 1) / G;
-    const int nb = ((K + 3) / 4) * ((K + 3) / 4);
-    const int B = nb <= 256 ? 1 : (nb + 255) / 256;
+    const int64_t rows = st_rows(w.N, G);
+    const int B = st_cost_b(K);
     const dim3 grid((unsigned)G, (unsigned)slices);
     const size_t lds = st_cost_lds(K);
     double* part = w.partial.as<double>();
@@ -2122,7 +2123,7 @@ int st_cost(hipStream_t st, StWork& w, const double* p, int64_t slice_stride, in
 
 int st_assign(hipStream_t st, const double* cost, int K, int slices, int32_t* perm, int64_t ld) {
     const size_t lds = st_assign_lds(K);
-    const int in_lds = (size_t)K * K * sizeof(double) + (size_t)(K + 1) * (3 * sizeof(double) + 3 * sizeof(int)) <= 65536;
+    const int in_lds = st_assign_in_lds(K);
     hipLaunchKernelGGL(k_st_assign, dim3((unsigned)slices), dim3(64), lds, st, cost, K, perm, ld, in_lds);
     HIP_TRY(hipGetLastError());
     return BMM_OK;
@@ -2963,6 +2964,29 @@ int bmm_device_stephens_online(int device, const double* Q, const double* p, int
         if (cost_out) HIP_TRY(hipMemcpy(cost_out, w.cost.p, (size_t)K * K * sizeof(double), hipMemcpyDeviceToHost));
         return BMM_OK;
     });
+}
+
+// Which form of every k_st_* kernel a shape runs, from the functions the launches above call (no device is
+// touched; tests/test_stephens_cpu.py, and tests/test_gpu_stephens_forms.py proves its reach with it)
+int bmm_device_stephens_plan(int64_t N, int K, int M, int64_t out[12]) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    if (N < 1 || M < 0) return set_err(BMM_E_ARG, "N must be >= 1 and M >= 0");
+    int rc = st_check_k(K);
+    if (rc) return rc;
+    StWork w;
+    w.shape(N, K, M);
+    for (int i = 0; i < 12; ++i) out[i] = 0;
+    out[0] = w.G1;
+    out[1] = w.GM;
+    out[2] = st_rows(N, w.G1);
+    out[3] = M > 0 ? st_rows(N, w.GM) : 0;
+    out[4] = st_cost_b(K);
+    out[5] = st_tile_rows(K);
+    out[6] = st_cost_nb(K);
+    out[7] = st_cost_ng(K);
+    out[8] = st_assign_in_lds(K) ? 1 : 0;
+    out[9] = st_assign_cols(K);
+    return BMM_OK;
 }
 
 // ---- several independent chains in one call (SURVEY.md section 8 rows b, e) ----------------

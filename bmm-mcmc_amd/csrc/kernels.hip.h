@@ -1436,17 +1436,24 @@ __global__ __launch_bounds__(256) void k_labels_from_r(const int32_t* __restrict
     }
 }
 
-// ---- Stephens' relabelling (src/stephens.cpp as it executes) --------------------
+// ---- Stephens' relabelling (src/stephens.cpp as it executes) -------------------
 // Matrices are N x K column-major (p[n + k*N]); a cost matrix is K x K column-major (C[k + l*K]); a
 // permutation table is rows x K column-major (perm(r, k) at perm[r + k*ld]), 0-based.
 constexpr int kStephensMaxK = 128;  // = BMM_STEPHENS_MAX_K
 // rows of p / log q staged in LDS per step of the cost kernel: 64 up to 32 categories (48 KiB), 16 above
 __host__ __device__ inline int st_tile_rows(int K) { return (K + 3) / 4 * 4 <= 32 ? 64 : 16; }
 
+// The shape of the cost pass for K categories -- the kernel, its launch and bmm_device_stephens_plan all read it
+// here: nb 4 x 4 blocks of C; below 256 blocks, ng groups of nb threads share a tile's rows (256 - ng * nb threads
+// idle); above, every thread owns B blocks (the template argument of k_st_cost_partial)
+__host__ __device__ inline int st_cost_nb(int K) { return ((K + 3) / 4) * ((K + 3) / 4); }
+__host__ __device__ inline int st_cost_ng(int K) { return st_cost_nb(K) >= 256 ? 1 : 256 / st_cost_nb(K); }
+__host__ __device__ inline int st_cost_b(int K) { return st_cost_nb(K) <= 256 ? 1 : (st_cost_nb(K) + 255) / 256; }
+
 // LDS bytes of k_st_cost_partial for K categories: three T x K4 tiles, or the cross-group reduction (ng x nb x 16)
 __host__ __device__ inline size_t st_cost_lds(int K) {
-    const int K4 = (K + 3) / 4 * 4, nb = (K4 / 4) * (K4 / 4);
-    const int ng = nb >= 256 ? 1 : 256 / nb;
+    const int K4 = (K + 3) / 4 * 4, nb = st_cost_nb(K);
+    const int ng = st_cost_ng(K);
     const size_t tiles = (size_t)3 * st_tile_rows(K) * K4 * sizeof(double);
     const size_t red = ng > 1 ? (size_t)ng * nb * 16 * sizeof(double) : 0;
     return tiles > red ? tiles : red;
@@ -1464,8 +1471,8 @@ __global__ __launch_bounds__(256) void k_st_cost_partial(const double* __restric
                                                          int lq_is_log, int batch_form, int64_t rows,
                                                          double* __restrict__ partial) {
     extern __shared__ double st_lds[];
-    const int K4 = (K + 3) / 4 * 4, nbk = K4 / 4, nb = nbk * nbk;
-    const int ng = nb >= 256 ? 1 : 256 / nb;
+    const int K4 = (K + 3) / 4 * 4, nbk = K4 / 4, nb = st_cost_nb(K);
+    const int ng = st_cost_ng(K);
     const int tid = threadIdx.x;
     const int g = nb >= 256 ? 0 : tid / nb;
     const bool active = g < ng;
@@ -1577,10 +1584,15 @@ __global__ __launch_bounds__(256) void k_st_cost_reduce(const double* __restrict
 // cost matrix (blockIdx.x = slice), lane j handling columns j, j + 64, j + 128 (index 0 is the virtual column).
 // perm(slice, l) = the row assigned to column l (stephens.cpp:54-55, 83-84; not inverted: :56, :85).
 constexpr int kStAssignCols = 3;  // columns per lane: 1 + kStephensMaxK <= 64 * 3
+inline int st_assign_cols(int K) { return (K + 1 + 63) / 64; }  // columns 0 .. K over 64 lanes: registers in use
+// the cost matrix is staged in LDS when it fits beside u, v, minv, pr, way, used (K <= 88)
+inline bool st_assign_in_lds(int K) {
+    return (size_t)K * K * sizeof(double) + (size_t)(K + 1) * (3 * sizeof(double) + 3 * sizeof(int)) <= 65536;
+}
 inline size_t st_assign_lds(int K) {
     const size_t cm = (size_t)K * K * sizeof(double);
     const size_t rest = (size_t)(K + 1) * (3 * sizeof(double) + 3 * sizeof(int));
-    return (cm + rest <= 65536 ? cm : 0) + rest;
+    return (st_assign_in_lds(K) ? cm : 0) + rest;
 }
 __global__ __launch_bounds__(64) void k_st_assign(const double* __restrict__ cost, int K, int32_t* __restrict__ perm,
                                                   int64_t ld, int cost_in_lds) {

@@ -239,6 +239,17 @@ int bmm_device_stephens_batch(int device, const double* p, int64_t N, int K, int
                               int32_t* perm_out);
 int bmm_device_stephens_online(int device, const double* Q, const double* p, int64_t N, int K, int j,
                                int32_t* perm_out, double* Q_out, double* cost_out);
+/* Which form of the relabelling kernels a shape runs, as pure bookkeeping -- no device is touched, and the values
+ * come from the functions the launches themselves call.  N rows, K categories, M slices of a batch window (M = 0:
+ * the online step only).  out:
+ *   [0] workgroups of the cost pass over one slice (the online step)   [1] the same per slice of an M-slice batch
+ *   [2] rows of p per workgroup for [0]                                [3] for [1]       ([1], [3]: 0 when M = 0)
+ *   [4] 4 x 4 blocks of the cost matrix per thread (1..4)              [5] rows staged in LDS per tile (64 or 16)
+ *   [6] 4 x 4 blocks in all, ceil(K/4)^2                               [7] thread groups sharing a tile's rows
+ *   [8] 1 when the assignment holds the cost matrix in LDS, else 0     [9] columns per lane of the assignment (1..3)
+ *   [10], [11] unused, 0.
+ * BMM_E_ARG unless N >= 1, M >= 0 and 1 <= K <= BMM_STEPHENS_MAX_K. */
+int bmm_device_stephens_plan(int64_t N, int K, int M, int64_t out[12]);
 
 /* ---- several independent chains in one call (SURVEY.md section 8 rows b and e) ---------------
  * n_chains chains of one sampler over the same data, chain c keyed seed + c and resident on

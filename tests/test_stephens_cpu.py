@@ -9,7 +9,7 @@ import bmm_mcmc_amd as bm
 from bmm_mcmc_amd import _capi
 
 NEW = ["bmm_collapsed_run_relabel", "bmm_dp_run_relabel", "bmm_sb_run_relabel", "bmm_full_run_relabel",
-       "bmm_device_stephens_batch", "bmm_device_stephens_online"]
+       "bmm_device_stephens_batch", "bmm_device_stephens_online", "bmm_device_stephens_plan"]
 
 
 def test_stephens_entry_points_are_exported():
@@ -18,7 +18,7 @@ def test_stephens_entry_points_are_exported():
         assert s in _capi.SYMBOLS
         getattr(L, s)
     assert bm.STEPHENS_MAX_K == 128
-    for name in ("stephens_batch", "stephens_online", "DeviceStephens"):
+    for name in ("stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens"):
         assert name in bm.__all__
 
 
@@ -82,3 +82,53 @@ def test_relabel_entry_points_refuse_before_touching_a_device():
     assert L.bmm_device_stephens_batch(C.c_int(0), _capi.vp(p), C.c_int64(4), C.c_int(2), C.c_int(1), _capi.vp(Q),
                                        _capi.vp(perm)) == 1
     assert b"finite" in L.bmm_last_error()
+
+
+def _plan(N, K, M=0):
+    p = bm.stephens_plan(N, K, M)
+    return [p[k] for k in ("groups_online", "groups_batch", "rows_online", "rows_batch", "blocks_per_thread",
+                           "tile_rows", "blocks", "thread_groups", "cost_in_lds", "cols_per_lane")]
+
+
+def test_stephens_plan_at_shapes_computed_by_hand():
+    # G = ceil(N / 512), at most 1024 (ceil(1024 / M) per slice of a batch) and at most 64 MiB / (M K^2 8) partials;
+    # rows = ceil(N / G); nb = ceil(K / 4)^2 blocks, ng = 256 // nb groups below 256 blocks, B = ceil(nb / 256)
+    # blocks per thread above; 64-row tiles up to K4 = 32, 16 above; cost in LDS while 8 K^2 + 36 (K + 1) <= 65536
+    # (K <= 88); columns 0..K over 64 lanes.
+    #                                  G1    GM   rows1 rowsM  B   T   nb   ng  lds cols
+    assert _plan(1, 1) == [1, 0, 1, 0, 1, 64, 1, 256, 1, 1]
+    assert _plan(5003, 20, 4) == [10, 10, 501, 501, 1, 64, 25, 10, 1, 1]
+    assert _plan(1000, 10) == [2, 0, 500, 0, 1, 64, 9, 28, 1, 1]              # 28 * 9 = 252: four threads idle
+    assert _plan(512, 32) == [1, 0, 512, 0, 1, 64, 64, 4, 1, 1]
+    assert _plan(513, 33) == [2, 0, 257, 0, 1, 16, 81, 3, 1, 1]
+    assert _plan(700, 50, 2) == [2, 2, 350, 350, 1, 16, 169, 1, 1, 1]
+    assert _plan(100, 63) == [1, 0, 100, 0, 1, 16, 256, 1, 1, 1]
+    assert _plan(100, 64) == [1, 0, 100, 0, 1, 16, 256, 1, 1, 2]              # column 64 is lane 0's second
+    assert _plan(100, 65) == [1, 0, 100, 0, 2, 16, 289, 1, 1, 2]
+    assert _plan(100, 88) == [1, 0, 100, 0, 2, 16, 484, 1, 1, 2]              # 8 * 88^2 + 36 * 89 = 65156
+    assert _plan(100, 89) == [1, 0, 100, 0, 3, 16, 529, 1, 0, 2]              # 8 * 89^2 + 36 * 90 = 66608
+    assert _plan(100, 108) == [1, 0, 100, 0, 3, 16, 729, 1, 0, 2]
+    assert _plan(100, 109) == [1, 0, 100, 0, 4, 16, 784, 1, 0, 2]
+    assert _plan(100, 127) == [1, 0, 100, 0, 4, 16, 1024, 1, 0, 2]
+    assert _plan(100, 128) == [1, 0, 100, 0, 4, 16, 1024, 1, 0, 3]
+    # the caps: 1024 workgroups; ceil(1024 / 3) = 342 per slice; 64 MiB / (128^2 * 8) = 512 partials
+    assert _plan(524_288, 3) == [1024, 0, 512, 0, 1, 64, 1, 256, 1, 1]
+    assert _plan(600_001, 3) == [1024, 0, 586, 0, 1, 64, 1, 256, 1, 1]
+    assert _plan(200_003, 3, 3) == [391, 342, 512, 585, 1, 64, 1, 256, 1, 1]
+    assert _plan(262_144, 128) == [512, 0, 512, 0, 4, 16, 1024, 1, 0, 3]
+    assert _plan(263_001, 128) == [512, 0, 514, 0, 4, 16, 1024, 1, 0, 3]
+    assert _plan(1_000_000, 128, 4) == [512, 128, 1954, 7813, 4, 16, 1024, 1, 0, 3]
+
+
+def test_stephens_plan_refuses_bad_shapes_and_clears_unused_slots():
+    L = _capi.lib()
+    out = (C.c_int64 * 12)(*([-1] * 12))
+    assert L.bmm_device_stephens_plan(C.c_int64(1000), C.c_int(10), C.c_int(0), out) == 0
+    assert list(out)[10:] == [0, 0] and out[1] == 0 and out[3] == 0
+    for K in (0, 129):
+        with pytest.raises(bm.BmmError, match="128"):
+            bm.stephens_plan(100, K)
+    for N, M in ((0, 0), (100, -1)):
+        with pytest.raises(bm.BmmError, match="N must be"):
+            bm.stephens_plan(N, 3, M)
+    assert L.bmm_device_stephens_plan(C.c_int64(10), C.c_int(3), C.c_int(0), None) == 1

@@ -124,3 +124,107 @@ def test_online_cost_uses_p_not_log_p():
             assert np.isclose(C[k, l], np.sum(p[:, l] * (p[:, l] - np.log(Q[:, k]))), rtol=1e-14, atol=0)
     Cb = sr.cost(p, np.log(Q), True)
     assert np.isclose(Cb[1, 2], np.sum(p[:, 2] * (np.log(p[:, 2]) - np.log(Q[:, 1]))), rtol=1e-14, atol=0)
+
+
+# ---- the restatement at the sizes the device tests trust it at (tests/test_gpu_stephens_forms.py) -----------
+
+def _total(C, perm):
+    return sum(C[perm[l], l] for l in range(C.shape[0]))
+
+
+@pytest.mark.parametrize("K", [8, 33, 64, 65, 89, 128])
+def test_hungarian_reaches_the_optimum_at_the_sizes_of_the_device_tests(K):
+    lsa = pytest.importorskip("scipy.optimize").linear_sum_assignment
+    rng = np.random.default_rng(500 + K)
+    mats = [rng.normal(size=(K, K)), rng.random((K, K)) * 50, rng.integers(0, 3, size=(K, K)).astype(float),
+            rng.integers(0, 4, size=(K, K)).astype(float), rng.choice([0.0, 3.0, 5.0], size=(K, K))]
+    for C in mats:
+        perm = sr.hungarian(C)
+        assert sorted(perm) == list(range(K))
+        rows, cols = lsa(C)
+        # rounding of a K-term sum only
+        assert abs(_total(C, perm) - C[rows, cols].sum()) <= 1e-12 * K * np.abs(C).max()
+
+
+def test_hungarian_equals_brute_force_at_8():
+    rng = np.random.default_rng(108)
+    for C in (rng.normal(size=(8, 8)), rng.integers(0, 3, size=(8, 8)).astype(float)):
+        perm = sr.hungarian(C)
+        best, arg = sr.brute_force(C)
+        assert abs(_total(C, perm) - best) <= 1e-12 * 8 * np.abs(C).max()
+        assert tuple(perm) in arg
+
+
+@pytest.mark.parametrize("K", [2, 7, 63, 64, 65, 88, 89, 127, 128])
+def test_tie_inputs_lay_the_chosen_ties_under_the_assignment(K):
+    rng = np.random.default_rng(300 + K)
+    D = rng.choice([0, 1, 2, 3], size=(K, K)).astype(np.float64)
+    Q, p = sr.tie_inputs(D)
+    lq = np.log(Q)
+    t = sr.terms(p, lq, False)                                    # t[k, n, l]
+    off = ~np.eye(K, dtype=bool)
+    assert (t[:, off] == 0).all() and not np.signbit(t[:, off]).any()   # terms of n != l: exact +0.0
+    C = sr.cost(p, lq, False)
+    assert np.array_equal(C, 1.0 - np.log(np.exp2(D)))
+    vals = np.unique(D)
+    assert len(np.unique(C)) == len(vals)
+    for d in vals:
+        assert len(np.unique(C[D == d])) == 1                     # equal entries of D: bit-equal costs
+    assert all(C[D == a][0] > C[D == b][0] for a, b in zip(vals, vals[1:]))   # a larger D is cheaper
+    if K >= 63:
+        lsa = pytest.importorskip("scipy.optimize").linear_sum_assignment
+        perm = sr.hungarian(C)
+        rows, cols = lsa(C)
+        assert abs(_total(C, perm) - C[rows, cols].sum()) <= 1e-12 * K * np.abs(C).max()
+
+
+@pytest.mark.parametrize("K", [2, 7, 63, 64, 65, 88, 89, 127, 128])
+def test_the_tie_rule_on_crafted_costs(K):
+    """the literal permutations of crafted_ties, written out here once more where they are short to state"""
+    cases = {name: (D, want) for name, D, want in sr.crafted_ties(K)}
+    for name, (D, want) in cases.items():
+        Q, p = sr.tie_inputs(D)
+        C = sr.cost(p, np.log(Q), False)
+        assert list(sr.hungarian(C)) == list(want), name
+    assert list(cases["constant"][1]) == list(range(K))
+    assert list(cases["cyclic"][1]) == [K - 1] + list(range(K - 1))
+    assert list(cases["antidiagonal"][1]) == list(range(K - 1, -1, -1))
+    assert ("registers" in cases) == (K >= 88) == ("lanes" in cases)
+    if K >= 88:
+        # the last row is equally cheap in columns 3 and 67 / 70 and 9: the lower column takes it, that
+        # column's row moves to the free column K - 1
+        swap = lambda a, b: [b if l == a else a if l == b else l for l in range(K)]
+        D, want = cases["registers"]
+        assert D[K - 1, 3] == D[K - 1, 67] == 1 and D.sum() == 2 and list(want) == swap(3, K - 1)
+        D, want = cases["lanes"]
+        assert D[K - 1, 9] == D[K - 1, 70] == 1 and D.sum() == 2 and list(want) == swap(9, K - 1)
+        if K == 128:
+            D, want = cases["registers3"]
+            assert D[126, 63] == D[126, 127] == 1 and D.sum() == 2 and list(want) == swap(63, 126)
+
+
+def test_margin_warm_equals_margin():
+    rng = np.random.default_rng(77)
+    for K in (1, 2, 3, 5, 8, 20, 33):
+        for C in (rng.normal(size=(K, K)), rng.random((K, K)), rng.integers(0, 4, size=(K, K)).astype(float)):
+            perm = sr.hungarian(C)
+            a, b = sr.margin(C, perm), sr.margin_warm(C, perm)
+            assert (np.isinf(a) and np.isinf(b)) or abs(a - b) <= 1e-12 * K * max(np.abs(C).max(), 1.0)
+    C = np.zeros((4, 4))
+    C[0, 1] = 1.0
+    with pytest.raises(ValueError):
+        sr.margin_warm(C, np.array([1, 0, 2, 3], dtype=np.int32))     # not the restatement's assignment
+
+
+def test_blocked_cost_equals_cost():
+    rng = np.random.default_rng(13)
+    N, K = 5000, 3
+    p = rng.dirichlet(np.ones(K), size=N)
+    p[:, 1] = 0.0
+    lq = np.log(rng.random((N, K)) * 3 + 0.01)
+    for batch_form in (False, True):
+        C = sr.cost(p, lq, batch_form)
+        scale = sr.cost_scale(p, lq, batch_form)
+        for got in (sr.cost_blocked(p, lq, batch_form, block=1024), sr.cost_blocked(p, lq, batch_form, wide=True)):
+            assert np.all(np.abs(got - C) <= N * 2.0 ** -53 * scale) and (got[:, 1] == 0).all()
+        assert np.allclose(sr.cost_scale_blocked(p, lq, batch_form, block=1024), scale, rtol=1e-13, atol=0)
