@@ -20,7 +20,8 @@ from .rdata import read_rdata_matrix  # the package's bundled data sets (data/*.
 
 __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "Chain", "BmmError", "NA_INTEGER", "set_progress",
            "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
-           "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K"]
+           "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
+           "partition_distances", "posterior_similarity", "partition_plan", "PARTITION_MAX_K"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -196,16 +197,181 @@ class _Predict:
         return out
 
 
-def _with_predictive(out, pr):
+def _with_predictive(out, pr, pt=None):
     if pr is not None:
         out["predictive"] = pr.result()
+    if pt is not None:
+        out["partition"] = pt.result()
     return out
 
 
-def _run(base, args, pr, hooks=None, rel=None):
+# ---------------------------------------------------------------- partition=: point estimate and similarity
+PARTITION_MAX_K = 1024  # include/bmm_mcmc.h BMM_PARTITION_MAX_K
+_CRITERION = {"binder": 0, "vi": 1}
+
+
+class _PartitionOut(_C.Structure):  # bmm_partition_out
+    _fields_ = [("criterion", _C.c_int), ("stride", _C.c_int), ("loss", _C.c_void_p), ("binder2", _C.c_void_p),
+                ("best", _C.c_void_p), ("z_best", _C.c_void_p), ("n_used", _C.c_void_p), ("dist", _C.c_void_p),
+                ("psm_idx", _C.c_void_p), ("psm_M", _C.c_int64), ("psm_cnt", _C.c_void_p)]
+
+
+def _criterion(criterion):
+    if criterion not in _CRITERION:
+        raise ValueError('partition criterion must be "binder" or "vi"')
+    return _CRITERION[criterion]
+
+
+def _stride(stride):
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("partition stride must be >= 1")
+    return stride
+
+
+def _indices(idx, N):
+    idx = _np.ascontiguousarray(idx, dtype=_np.int64).ravel()
+    if idx.size < 1 or idx.min() < 0 or idx.max() >= N:
+        raise ValueError("similarity indices must be observations 0 .. N-1, at least one")
+    return idx
+
+
+class _Partition:
+    """Outputs of an armed bmm_set_partition_summary: the run fills them after its last sweep (include/bmm_mcmc.h,
+    DESIGN.md section 13).  With several chains nothing is armed: the traces are pooled afterwards."""
+
+    def __init__(self, criterion, stride, similarity_of, N, S):
+        self.criterion, self.stride = criterion, _stride(stride)
+        code = _criterion(criterion)
+        C = -(-S // self.stride)
+        self.loss = _np.full(C, _np.nan)
+        self.binder2 = _np.zeros(C, dtype=_np.uint64)
+        self.best = _C.c_int(-1)
+        self.n_used = _C.c_int(0)
+        self.z = _np.zeros(N, dtype=_np.int32)
+        self.idx = None if similarity_of is None else _indices(similarity_of, N)
+        self.cnt = None if self.idx is None else _np.zeros((self.idx.size, self.idx.size), dtype=_np.uint32)
+        self.s = _PartitionOut(code, self.stride, self.loss.ctypes.data, self.binder2.ctypes.data,
+                               _C.addressof(self.best), self.z.ctypes.data, _C.addressof(self.n_used),
+                               None,
+                               None if self.idx is None else self.idx.ctypes.data,
+                               0 if self.idx is None else self.idx.size,
+                               None if self.cnt is None else self.cnt.ctypes.data)
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_partition_summary(_C.byref(self.s)))
+
+    def result(self):
+        nu = self.n_used.value
+        C = -(-nu // self.stride)
+        out = {"criterion": self.criterion, "loss": self.loss[:C], "binder2": self.binder2[:C],
+               "best": self.best.value, "z": self.z, "n_used": nu}
+        if self.cnt is not None:
+            out["similarity"] = self.cnt
+        return out
+
+
+def _make_partition(partition, stride, similarity_of, N, S, chains):
+    """partition=, partition_stride=, similarity_of= of a wrapper, checked before any device is touched.  One chain:
+    the outputs to arm for the run; several: None (the traces are pooled afterwards, _pooled)."""
+    if partition is None:
+        if similarity_of is not None:
+            raise ValueError('similarity_of= needs partition="binder" or "vi"')
+        return None
+    if int(chains) > 1:
+        _criterion(partition), _stride(stride)
+        if similarity_of is not None:
+            _indices(similarity_of, N)
+        return None
+    return _Partition(partition, stride, similarity_of, N, S)
+
+
+def _pooled(chains_out, partition, stride, similarity_of, device):
+    """chains > 1: the chains' traces stacked (rows that are no partition -- the unassigned starting state of a run
+    without burn-in -- left out), one stand-alone call, the pooled summary attached to every chain object."""
+    if partition is None:
+        return chains_out
+    rows, src = [], []
+    for ci, o in enumerate(chains_out):
+        z = o["z"]
+        keep = [s for s in range(z.shape[0]) if z[s].min() >= 1]
+        rows.append(z[keep])
+        src += [(ci, s) for s in keep]
+    zz = _np.asfortranarray(_np.concatenate(rows, axis=0))
+    res = partition_distances(zz, partition, stride, device=device)
+    res["chain"], res["best"] = src[res["best"]]
+    if similarity_of is not None:
+        res["similarity"] = posterior_similarity(zz, similarity_of, device=device)
+    for o in chains_out:
+        o["partition"] = res
+    return chains_out
+
+
+def _as_trace(z):
+    z = _np.asfortranarray(z, dtype=_np.int32)
+    if z.ndim != 2 or z.shape[0] < 1 or z.shape[1] < 1:
+        raise ValueError("z must be an S x N matrix of labels (rows: kept sweeps), S, N >= 1")
+    return z
+
+
+def partition_distances(z, criterion="binder", stride=1, distances=False, device=0, Kc=None):
+    """Point estimate of the clustering from a label trace, on the device (include/bmm_mcmc.h).
+    z: S x N labels, 1-based, as a run returns them -- or the traces of several chains stacked.  Candidates are rows
+    0, stride, ...; the draws are all rows.  Returns {"criterion", "loss" (C,), "binder2" (C,) uint64 exact totals
+    sum_t 2 B(c, z_t), "best" (row of z, 0-based, smallest expected loss, lowest index on ties), "z" (that row),
+    "n_used" (S)} and, with distances=True, "distances" (C, S): Binder (exact integers held in doubles) or VI in nats.
+    Kc: number of categories (default: the largest label)."""
+    z = _as_trace(z)
+    S, N = z.shape
+    code, stride = _criterion(criterion), _stride(stride)
+    Kc = max(1, int(z.max())) if Kc is None else int(Kc)
+    C = -(-S // stride)
+    loss = _np.zeros(C)
+    b2 = _np.zeros(C, dtype=_np.uint64)
+    best = _C.c_int(-1)
+    dist = _np.zeros((C, S), order="F") if distances else None
+    _capi.check(_capi.lib().bmm_device_partition_distances(
+        _C.c_int(device), _capi.vp(z), _C.c_int(S), _C.c_int64(N), _C.c_int(Kc), _C.c_int(code), _C.c_int(stride),
+        _capi.vp(loss), _capi.vp(b2), _C.byref(best), _capi.vp(dist) if distances else None))
+    out = {"criterion": criterion, "loss": loss, "binder2": b2, "best": best.value, "z": z[best.value].copy(), "n_used": S}
+    if distances:
+        out["distances"] = dist
+    return out
+
+
+def posterior_similarity(z, idx, device=0):
+    """cnt[u, v] = number of rows of z (S x N, labels >= 1) in which observations idx[u] and idx[v] (0-based, any
+    order, repeats allowed) share a cluster: (M, M) uint32, symmetric, diagonal S.  Computed on the device."""
+    z = _as_trace(z)
+    S, N = z.shape
+    idx = _indices(idx, N)
+    cnt = _np.zeros((idx.size, idx.size), dtype=_np.uint32)
+    _capi.check(_capi.lib().bmm_device_psm(_C.c_int(device), _capi.vp(z), _C.c_int(S), _C.c_int64(N), _capi.vp(idx),
+                                           _C.c_int64(idx.size), _capi.vp(cnt)))
+    return cnt
+
+
+_PT_PLAN_FIELDS = ("label_bytes", "lds", "draws_per_workgroup", "replicas", "draw_blocks", "workgroups", "threads",
+                   "lds_bytes", "triangular", "vi", "generic_bytes", "pitch")
+
+
+def partition_plan(S, N, Kc, candidates=None, criterion="binder"):
+    """Which form of the partition kernels a shape runs (S rows, N observations, Kc categories, `candidates` of the
+    rows -- default all), read from the library's launch arithmetic without touching a device
+    (bmm_device_partition_plan): a dict of the fields include/bmm_mcmc.h lists."""
+    out = (_C.c_int64 * 12)()
+    C = int(S) if candidates is None else int(candidates)
+    _capi.check(_capi.lib().bmm_device_partition_plan(_C.c_int(int(S)), _C.c_int64(int(N)), _C.c_int(int(Kc)),
+                                                      _C.c_int(C), _C.c_int(_criterion(criterion)), out))
+    return dict(zip(_PT_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def _run(base, args, pr, hooks=None, rel=None, part=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
-    them with the predictive of new rows (_run_predict)."""
+    them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
+    if part is not None:
+        part.arm()
     if pr is None:
         if rel is not None:
             return getattr(L, "bmm_%s_run_relabel" % base)(*args, rel.ref())
@@ -360,7 +526,7 @@ def _multi(sampler, X, chains, devices, z0s, pi0s, th0s, nsamples, K, alpha, bet
 def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
                     relabel=False, burnrelabel=50, debug=False, *, seed=None, batch=None, device=0,
                     initial_K=None, chains=1, devices=None, stephens=None, newdata=None, predictive_trace=False,
-                    responsibilities=False):
+                    responsibilities=False, partition=None, partition_stride=1, similarity_of=None):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -375,7 +541,14 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     burn-in its first row, the starting state, is NaN), `responsibilities=True` adds "resp", the (M, K) mean
     normalised category weights -- in the sampler's label order of each sweep, so they mean something only for a
     chain that does not switch labels (relabel=True does not reorder them).  The predictive itself does not
-    depend on the labels.
+    depend on the labels.  `partition="binder"` or `"vi"`: the result gains `partition = {"criterion", "loss", "binder2",
+    "best", "z", "n_used"}` -- the kept sweep that minimises the posterior expected Binder or variation-of-information
+    loss over the kept sweeps (candidates every `partition_stride`-th), computed on the device from the resident trace;
+    `best` is its row of `z` (of `z_original` under stephens="device": the summary is on the labels as sampled and does
+    not depend on their numbering), "z" that row, `n_used` the rows used (the unassigned starting row of a run without
+    burn-in is left out).  `similarity_of=` indices (0-based) adds "similarity", how often each pair of those
+    observations shared a cluster.  With `chains > 1` the chains' traces are pooled into one estimate, attached to
+    every chain object with "chain" naming the chain `best` indexes.
     """
     X = _capi.as_x(data)
     N, P = X.shape
@@ -384,13 +557,14 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     seed = _seed(seed)
     chains = int(chains)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
+    pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     if chains > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
         z0s = [_np.ascontiguousarray(_np.random.default_rng(seed + c).integers(1, K + 1, N), dtype=_np.int32)
                for c in range(chains)] if initial_K is None else [_np.ascontiguousarray(z, dtype=_np.int32) for z in initial_K]
-        return _multi("collapsed", X, chains, devices, z0s, None, None, nsamples, K, alpha, beta, gamma, a, b,
-                      burnin, batch, seed, False)
+        return _pooled(_multi("collapsed", X, chains, devices, z0s, None, None, nsamples, K, alpha, beta, gamma, a, b,
+                      burnin, batch, seed, False), partition, partition_stride, similarity_of, device if devices is None else int(devices[0]))
     if initial_K is None:
         initial_K = _np.random.default_rng(seed).integers(1, K + 1, N)
     z0 = _np.ascontiguousarray(initial_K, dtype=_np.int32)
@@ -408,8 +582,8 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
                 _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("collapsed", args, pr, rel=dr)
-        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr)
+            rc = _run("collapsed", args, pr, rel=dr, part=pt)
+        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt)
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((K, P, S), order="F")
@@ -419,17 +593,18 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
             _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
-        return _with_predictive(rl.finish(rc, out), pr)
+        return _with_predictive(rl.finish(rc, out), pr, pt)
     _capi.check(rc)
-    return _with_predictive(out, pr)
+    return _with_predictive(out, pr, pt)
 
 
 def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=None, relabel=False,
              burnrelabel=50, maxK=30, debug=False, *, seed=None, batch=None, device=0, chains=1, devices=None,
-             stephens=None, newdata=None, predictive_trace=False, responsibilities=False):
+             stephens=None, newdata=None, predictive_trace=False, responsibilities=False, partition=None,
+             partition_stride=1, similarity_of=None):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column."""
@@ -439,11 +614,12 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, maxK + 1, predictive_trace, responsibilities, chains)
+    pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     if int(chains) > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
-        return _multi("dp", X, int(chains), devices, None, None, None, nsamples, maxK, alpha, beta, gamma, a, b,
-                      burnin, batch, seed, False)
+        return _pooled(_multi("dp", X, int(chains), devices, None, None, None, nsamples, maxK, alpha, beta, gamma, a, b,
+                      burnin, batch, seed, False), partition, partition_stride, similarity_of, device if devices is None else int(devices[0]))
     S = nsamples - burnin
     W = _clamp_burnrelabel(burnrelabel, burnin)
     if _device_relabel(stephens, relabel, burnin, W):
@@ -457,8 +633,8 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                 _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
                 _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("dp", args, pr, rel=dr)
-        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr)
+            rc = _run("dp", args, pr, rel=dr, part=pt)
+        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt)
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((maxK, P, S), order="F")
@@ -469,17 +645,17 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl)
+        rc = _run("dp", args, pr, hooks=rl, part=pt)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
-        return _with_predictive(rl.finish(rc, out), pr)
+        return _with_predictive(rl.finish(rc, out), pr, pt)
     _capi.check(rc)
-    return _with_predictive(out, pr)
+    return _with_predictive(out, pr, pt)
 
 
 def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, burnin, relabel, burnrelabel, seed,
               device, initial_pi, initial_theta, chains, devices, stephens, debug=False, newdata=None,
-              predictive_trace=False, responsibilities=False):
+              predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None):
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, K = int(nsamples), int(K)
@@ -487,6 +663,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
     seed = _seed(seed)
     chains = int(chains)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
+    pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     base = fn[len("bmm_"):-len("_run_probs")]
 
     def start(sd, pi, th):
@@ -509,8 +686,8 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
         st = [start(seed + c, initial_pi[c] if initial_pi is not None else None,
                     initial_theta[c] if initial_theta is not None else None) for c in range(chains)]
-        return _multi(sampler, X, chains, devices, None, [p for p, _ in st], [t for _, t in st], nsamples, K,
-                      alpha, beta, gamma, a, b, burnin, None, seed, True)
+        return _pooled(_multi(sampler, X, chains, devices, None, [p for p, _ in st], [t for _, t in st], nsamples, K,
+                      alpha, beta, gamma, a, b, burnin, None, seed, True), partition, partition_stride, similarity_of, device if devices is None else int(devices[0]))
     on_device = _device_relabel(stephens, relabel, burnin, W)
     pi0, th0 = start(seed, initial_pi, initial_theta)
     if on_device:
@@ -524,8 +701,8 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
                 _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
                 _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run(base, args, pr, rel=dr)
-        return _with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr)
+            rc = _run(base, args, pr, rel=dr, part=pt)
+        return _with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt)
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((K, P, S), order="F")
@@ -536,34 +713,36 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
             _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run(base, args, pr, hooks=rl)
+        rc = _run(base, args, pr, hooks=rl, part=pt)
     out = {"pi": pi, "alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
-        return _with_predictive(rl.finish(rc, out), pr)
+        return _with_predictive(rl.finish(rc, out), pr, pt)
     _capi.check(rc)
-    return _with_predictive(out, pr)
+    return _with_predictive(out, pr, pt)
 
 
 def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
                         relabel=False, burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None,
                         initial_theta=None, chains=1, devices=None, stephens=None, newdata=None,
-                        predictive_trace=False, responsibilities=False):
+                        predictive_trace=False, responsibilities=False, partition=None, partition_stride=1,
+                        similarity_of=None):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
     src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
     `predictive_trace`, `responsibilities`: as gibbs_collapsed."""
     return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
                      burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
-                     newdata, predictive_trace, responsibilities)
+                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
                burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None, initial_theta=None, chains=1,
-               devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False):
+               devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False,
+               partition=None, partition_stride=1, similarity_of=None):
     """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
     `predictive_trace`, `responsibilities`: as gibbs_collapsed."""
     return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
                      relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
-                     newdata, predictive_trace, responsibilities)
+                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of)
 
 
 class Chain:

@@ -2479,6 +2479,262 @@ void permute_theta(const double* th, const int32_t* perm, int K, int P, int S, d
         }
 }
 
+// ---- clustering point estimate and posterior similarity (include/bmm_mcmc.h) ----
+// Which form of the k_pt_* kernels a shape runs: a pure function of (S, N, Kc, candidates, criterion) -- the
+// launches below and bmm_device_partition_plan both read it from here.
+constexpr size_t kPtLdsBudget = (size_t)48 << 10;       // bytes of contingency tables per workgroup
+constexpr size_t kPtGenericBudget = (size_t)256 << 20;  // bytes of global-memory tables of the generic form
+struct PtPlan {
+    int el = 1, lds = 1, T = 1, R = 1, blocks = 1, threads = kPtThreads, tri = 0, vi = 0;
+    int64_t wgs = 0, pitch = 0;
+    size_t lds_bytes = 0, generic_bytes = 0;
+};
+PtPlan pt_plan(int S, int64_t N, int Kc, int C, int criterion) {
+    PtPlan p;
+    const size_t tb = (size_t)Kc * Kc * sizeof(uint32_t);
+    p.el = Kc <= 256 ? 1 : 4;
+    p.lds = Kc <= kPtMaxLdsK ? 1 : 0;
+    p.tri = C == S ? 1 : 0;  // stride 1 (or a single row): rc == c
+    p.vi = criterion == BMM_PARTITION_VI ? 1 : 0;
+    p.pitch = (N + 15) / 16 * 16;
+    if (p.lds) {
+        p.R = tb <= 1024 ? 4 : 1;
+        int64_t T = (int64_t)(kPtLdsBudget / (tb * p.R));
+        if (T > 8) T = 8;
+        if (T > S) T = S;
+        p.T = (int)(T < 1 ? 1 : T);
+        p.blocks = (S + p.T - 1) / p.T;
+        p.wgs = (int64_t)C * p.blocks;
+        p.lds_bytes = (size_t)p.T * p.R * tb;
+    } else {
+        p.blocks = S;
+        int64_t g = (int64_t)(kPtGenericBudget / tb);
+        if (g > 1024) g = 1024;
+        if (g > (int64_t)C * S) g = (int64_t)C * S;
+        p.wgs = g < 1 ? 1 : g;
+        p.generic_bytes = (size_t)p.wgs * tb;
+    }
+    return p;
+}
+// refused before any device is touched
+int pt_check_shape(int S, int64_t N, int Kc, int criterion, int stride) {
+    if (S < 1) return set_err(BMM_E_ARG, "partition: S must be >= 1");
+    if (N < 1) return set_err(BMM_E_ARG, "partition: N must be >= 1");
+    if (S > BMM_PARTITION_MAX_ROWS) return set_err(BMM_E_ARG, "partition: S = %d rows is more than the %d one call takes", S, BMM_PARTITION_MAX_ROWS);
+    if (stride < 1) return set_err(BMM_E_ARG, "partition: stride must be >= 1");
+    if (Kc < 1 || Kc > BMM_PARTITION_MAX_K) return set_err(BMM_E_ARG, "partition: Kc must be in 1 .. %d (got %d)", BMM_PARTITION_MAX_K, Kc);
+    if (criterion != BMM_PARTITION_BINDER && criterion != BMM_PARTITION_VI) return set_err(BMM_E_ARG, "partition: unknown criterion %d", criterion);
+    if ((unsigned __int128)S * (unsigned __int128)N * (unsigned __int128)N >= ((unsigned __int128)1 << 63))
+        return set_err(BMM_E_ARG, "partition: S * N^2 = %d * %lld^2 does not fit the exact integer totals (must be < 2^63)", S, (long long)N);
+    return BMM_OK;
+}
+// every label of the caller's S x N matrix in lo .. hi (1-based); the first offender is named
+int pt_check_labels(const int32_t* z, int S, int64_t N, int lo, int64_t hi, int32_t* max_out) {
+    const int64_t total = (int64_t)S * N;
+    std::atomic<int64_t> bad{INT64_MAX};
+    std::atomic<int32_t> top{0};
+    HostCrew crew;
+    crew.run(total, 1 << 16, 64, [&](int64_t a, int64_t b) {
+        int32_t mx = 0;
+        for (int64_t q = a; q < b; ++q) {
+            const int32_t v = z[q];
+            if (v < lo || v > hi) {
+                int64_t cur = bad.load(std::memory_order_relaxed);
+                while (q < cur && !bad.compare_exchange_weak(cur, q, std::memory_order_relaxed)) {}
+                return;
+            }
+            if (v > mx) mx = v;
+        }
+        int32_t cur = top.load(std::memory_order_relaxed);
+        while (mx > cur && !top.compare_exchange_weak(cur, mx, std::memory_order_relaxed)) {}
+    });
+    const int64_t q = bad.load();
+    if (q != INT64_MAX)
+        return set_err(BMM_E_ARG, "partition: label %d at row %lld, observation %lld (0-based) is outside %d .. %lld: not a partition",
+                       z[q], (long long)(q % S), (long long)(q / S), lo, (long long)hi);
+    if (max_out) *max_out = top.load();
+    return BMM_OK;
+}
+
+struct PtWork {
+    int S = 0, Kc = 0, C = 0, stride = 1;
+    int64_t N = 0;
+    PtPlan plan;
+    DevBuf lab, flag, A, F, Q, G, sum2, loss, best, tabs, dist;
+    void shape(int S_, int64_t N_, int Kc_, int criterion, int stride_) {
+        S = S_; N = N_; Kc = Kc_; stride = stride_;
+        C = (S + stride - 1) / stride;
+        plan = pt_plan(S, N, Kc, C, criterion);
+    }
+    int alloc_labels() {
+        HIP_TRY(lab.alloc((size_t)S * plan.pitch * plan.el));
+        HIP_TRY(flag.alloc(sizeof(int)));
+        HIP_TRY(hipMemset(flag.p, 0, sizeof(int)));
+        return BMM_OK;
+    }
+    int alloc_pairs(bool want_dist) {
+        const size_t cs = (size_t)C * S;
+        HIP_TRY(A.alloc((size_t)S * sizeof(uint64_t)));
+        HIP_TRY(F.alloc((size_t)S * sizeof(double)));
+        HIP_TRY(Q.alloc(cs * sizeof(uint64_t)));
+        HIP_TRY(G.alloc(cs * sizeof(double)));
+        HIP_TRY(sum2.alloc((size_t)C * sizeof(uint64_t)));
+        HIP_TRY(loss.alloc((size_t)C * sizeof(double)));
+        HIP_TRY(best.alloc(sizeof(int)));
+        if (!plan.lds) HIP_TRY(tabs.alloc(plan.generic_bytes));
+        if (want_dist) HIP_TRY(dist.alloc(cs * sizeof(double)));
+        return BMM_OK;
+    }
+};
+
+// labels (s, li) at src[s * ss + li * si] - base for observations [i0, i0 + rows) into the label block
+int pt_narrow(hipStream_t st, PtWork& w, const int32_t* src, int64_t ss, int64_t si, int base, int64_t i0, int64_t rows) {
+    const dim3 grid((unsigned)((rows + 31) / 32), (unsigned)((w.S + 31) / 32));
+    if (w.plan.el == 1)
+        hipLaunchKernelGGL(k_pt_narrow<uint8_t>, grid, dim3(256), 0, st, src, ss, si, base, w.S, i0, rows, w.Kc, w.lab.as<uint8_t>(), w.plan.pitch, w.flag.as<int>());
+    else
+        hipLaunchKernelGGL(k_pt_narrow<int32_t>, grid, dim3(256), 0, st, src, ss, si, base, w.S, i0, rows, w.Kc, w.lab.as<int32_t>(), w.plan.pitch, w.flag.as<int>());
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+// the caller's S x N column-major matrix (observation i's S labels are contiguous) in blocks of observations
+int pt_upload(PtWork& w, const int32_t* z) {
+    const int S = w.S;
+    int64_t B = (int64_t)(((size_t)32 << 20) / ((size_t)S * sizeof(int32_t))) / 32 * 32;
+    if (B < 32) B = 32;
+    if (B > w.N) B = w.N;
+    DevBuf stage;
+    HIP_TRY(stage.alloc((size_t)B * S * sizeof(int32_t)));
+    for (int64_t i0 = 0; i0 < w.N; i0 += B) {
+        const int64_t rows = w.N - i0 < B ? w.N - i0 : B;
+        HIP_TRY(hipMemcpy(stage.p, z + (size_t)i0 * S, (size_t)rows * S * sizeof(int32_t), hipMemcpyHostToDevice));
+        const int rc = pt_narrow(nullptr, w, stage.as<int32_t>(), 1, S, 1, i0, rows);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipDeviceSynchronize());  // before the staging block goes
+    return BMM_OK;
+}
+// sizes, pairs, losses, argmin: everything enqueued on st
+int pt_compute(hipStream_t st, PtWork& w) {
+    const PtPlan& p = w.plan;
+    const int S = w.S, C = w.C, Kc = w.Kc;
+    const size_t hist = (size_t)4 * Kc * sizeof(uint32_t);
+    if (p.el == 1) hipLaunchKernelGGL(k_pt_sizes<uint8_t>, dim3(S), dim3(256), hist, st, w.lab.as<uint8_t>(), p.pitch, w.N, Kc, w.A.as<uint64_t>(), w.F.as<double>());
+    else hipLaunchKernelGGL(k_pt_sizes<int32_t>, dim3(S), dim3(256), hist, st, w.lab.as<int32_t>(), p.pitch, w.N, Kc, w.A.as<uint64_t>(), w.F.as<double>());
+    HIP_TRY(hipGetLastError());
+    uint64_t* const Q = w.Q.as<uint64_t>();
+    double* const G = w.G.as<double>();
+    if (S > 1) {
+        if (p.lds) {
+            const dim3 grid((unsigned)p.blocks, (unsigned)C);
+            if (p.vi) hipLaunchKernelGGL(k_pt_pairs<true>, grid, dim3(256), p.lds_bytes, st, w.lab.as<uint8_t>(), p.pitch, w.N, S, Kc, w.stride, p.T, p.R, p.tri, Q, G);
+            else hipLaunchKernelGGL(k_pt_pairs<false>, grid, dim3(256), p.lds_bytes, st, w.lab.as<uint8_t>(), p.pitch, w.N, S, Kc, w.stride, p.T, p.R, p.tri, Q, G);
+        } else {
+            const dim3 grid((unsigned)p.wgs);
+            uint32_t* const tabs = w.tabs.as<uint32_t>();
+            if (p.el == 1) {
+                if (p.vi) hipLaunchKernelGGL((k_pt_pairs_generic<uint8_t, true>), grid, dim3(256), 0, st, w.lab.as<uint8_t>(), p.pitch, w.N, S, Kc, w.stride, C, p.tri, tabs, Q, G);
+                else hipLaunchKernelGGL((k_pt_pairs_generic<uint8_t, false>), grid, dim3(256), 0, st, w.lab.as<uint8_t>(), p.pitch, w.N, S, Kc, w.stride, C, p.tri, tabs, Q, G);
+            } else {
+                if (p.vi) hipLaunchKernelGGL((k_pt_pairs_generic<int32_t, true>), grid, dim3(256), 0, st, w.lab.as<int32_t>(), p.pitch, w.N, S, Kc, w.stride, C, p.tri, tabs, Q, G);
+                else hipLaunchKernelGGL((k_pt_pairs_generic<int32_t, false>), grid, dim3(256), 0, st, w.lab.as<int32_t>(), p.pitch, w.N, S, Kc, w.stride, C, p.tri, tabs, Q, G);
+            }
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_pt_loss, dim3(C), dim3(256), 0, st, w.A.as<uint64_t>(), w.F.as<double>(), Q, G, S, C, w.stride, w.N, p.vi, w.sum2.as<uint64_t>(), w.loss.as<double>(), w.dist.as<double>());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_pt_argmin, dim3(1), dim3(256), 0, st, w.sum2.as<uint64_t>(), w.loss.as<double>(), C, p.vi, w.best.as<int>());
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+// after the stream has been waited for: the results out; best_out is the candidate's row, c * stride
+int pt_fetch(PtWork& w, double* loss_out, uint64_t* binder2_out, int* best_out, double* dist_out) {
+    int flag = 0, best = -1;
+    HIP_TRY(hipMemcpy(&flag, w.flag.p, sizeof flag, hipMemcpyDeviceToHost));
+    if (flag) return set_err(BMM_E_STATE, "partition: a label outside 0 .. %d reached the device", w.Kc - 1);
+    HIP_TRY(hipMemcpy(loss_out, w.loss.p, (size_t)w.C * sizeof(double), hipMemcpyDeviceToHost));
+    if (binder2_out) HIP_TRY(hipMemcpy(binder2_out, w.sum2.p, (size_t)w.C * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&best, w.best.p, sizeof best, hipMemcpyDeviceToHost));
+    if (best_out) *best_out = best * w.stride;
+    if (dist_out) HIP_TRY(hipMemcpy(dist_out, w.dist.p, (size_t)w.C * w.S * sizeof(double), hipMemcpyDeviceToHost));
+    return BMM_OK;
+}
+// similarity counts of idx[0 .. M) over the label block's S rows
+int pt_psm(hipStream_t st, PtWork& w, const int64_t* idx, int64_t M, uint32_t* cnt_out) {
+    const size_t need = (size_t)M * M * sizeof(uint32_t) + (size_t)w.S * M * w.plan.el + (size_t)M * sizeof(int64_t);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b)
+        return set_err(BMM_E_ARG, "similarity: %lld x %lld counts and the %d x %lld block of labels need %zu bytes of device memory, %zu are free",
+                       (long long)M, (long long)M, w.S, (long long)M, need, free_b);
+    DevBuf didx, g, cnt;
+    HIP_TRY(didx.alloc((size_t)M * sizeof(int64_t)));
+    HIP_TRY(g.alloc((size_t)w.S * M * w.plan.el));
+    HIP_TRY(cnt.alloc((size_t)M * M * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpyAsync(didx.p, idx, (size_t)M * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    const dim3 gg((unsigned)((M + 255) / 256), (unsigned)w.S);
+    const unsigned nt = (unsigned)((M + 63) / 64);
+    if (w.plan.el == 1) {
+        hipLaunchKernelGGL(k_pt_gather<uint8_t>, gg, dim3(256), 0, st, w.lab.as<uint8_t>(), w.plan.pitch, didx.as<int64_t>(), M, g.as<uint8_t>());
+        hipLaunchKernelGGL(k_pt_psm<uint8_t>, dim3(nt, nt), dim3(256), 0, st, g.as<uint8_t>(), w.S, M, cnt.as<uint32_t>());
+    } else {
+        hipLaunchKernelGGL(k_pt_gather<int32_t>, gg, dim3(256), 0, st, w.lab.as<int32_t>(), w.plan.pitch, didx.as<int64_t>(), M, g.as<int32_t>());
+        hipLaunchKernelGGL(k_pt_psm<int32_t>, dim3(nt, nt), dim3(256), 0, st, g.as<int32_t>(), w.S, M, cnt.as<uint32_t>());
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(cnt_out, cnt.p, (size_t)M * M * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return BMM_OK;
+}
+int pt_check_idx(const int64_t* idx, int64_t M, int64_t N) {
+    for (int64_t u = 0; u < M; ++u)
+        if (idx[u] < 0 || idx[u] >= N) return set_err(BMM_E_ARG, "similarity: idx[%lld] = %lld is outside 0 .. %lld", (long long)u, (long long)idx[u], (long long)(N - 1));
+    return BMM_OK;
+}
+
+// The summary of a run (bmm_set_partition_summary), per calling thread: armed for the next single-chain run.
+struct PtArmed { bool on = false; bmm_partition_out o{}; };
+thread_local PtArmed g_partition;
+// first line of every public *_run* entry point, bmm_multi_run included: whatever the call returns, and wherever it
+// returns from, the summary is no longer armed afterwards
+struct PtDisarm { ~PtDisarm() { g_partition.on = false; } };
+// what a run checks of it before any device is touched
+int pt_check_armed(const bmm_partition_out& o, int S, int64_t N, int K) {
+    if (!o.loss || !o.best || !o.n_used) return set_err(BMM_E_ARG, "partition: null buffer (loss, best, n_used)");
+    int rc = pt_check_shape(S, N, K, o.criterion, o.stride);
+    if (rc) return rc;
+    if (o.psm_M < 0 || (o.psm_M > 0 && (!o.psm_idx || !o.psm_cnt))) return set_err(BMM_E_ARG, "similarity: null buffer or negative count");
+    return pt_check_idx(o.psm_idx, o.psm_M, N);
+}
+// after the last sweep, before the trace leaves: everything on the chain's stream, then one wait
+int pt_run_summary(bmm_chain* c, const bmm_partition_out& o) {
+    const int64_t N = c->p.N;
+    const int first = (c->burnin == 0 && c->p.mode != MODE_COLLAPSED) ? 1 : 0;  // row 0: the unassigned starting state
+    const int Su = c->S - first;
+    *o.n_used = Su;
+    *o.best = -1;
+    if (Su < 1) return BMM_OK;
+    PtWork w;
+    w.shape(Su, N, c->p.K, o.criterion, o.stride);
+    int rc = w.alloc_labels();
+    if (rc == BMM_OK) rc = w.alloc_pairs(o.dist != nullptr);
+    if (rc == BMM_OK) rc = pt_narrow(c->stream, w, c->dTrace + (size_t)first * N, N, 1, 0, 0, N);
+    if (rc == BMM_OK) rc = pt_compute(c->stream, w);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int best = -1;
+    rc = pt_fetch(w, o.loss, o.binder2, &best, o.dist);
+    if (rc) return rc;
+    *o.best = first + best;
+    if (o.z_best) {
+        HIP_TRY(hipMemcpy(o.z_best, c->dTrace + (size_t)(first + best) * N, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < N; ++i) o.z_best[i] += 1;
+    }
+    if (o.psm_M > 0) rc = pt_psm(c->stream, w, o.psm_idx, o.psm_M, o.psm_cnt);
+    return rc;
+}
+
 // the sweeps, then the traces out (data and starting state are in place)
 int run_body(bmm_chain* c, int nsamples, const RunIO& io, const bmm_relabel_hooks* hooks,
              const bmm_relabel_out* rel = nullptr) {
@@ -2504,6 +2760,10 @@ int run_body(bmm_chain* c, int nsamples, const RunIO& io, const bmm_relabel_hook
     HIP_TRY(hipMemcpyAsync(io.alpha_out, c->dAlphaTrace, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (explicit_params(sampler))
         HIP_TRY(hipMemcpyAsync(io.pi_out, c->dPiTrace, (size_t)S * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (g_partition.on) {  // the clustering summary, from the resident trace (labels as sampled)
+        rc = pt_run_summary(c, g_partition.o);
+        if (rc) return rc;
+    }
     if (rel) {
         HIP_TRY(hipMemcpyAsync(rel->permutations, st.perm.p, (size_t)S * K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         rc = trace_out(c, rel->z_original, &clock);
@@ -2597,6 +2857,10 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
     return guarded([&]() -> int {
         int rc = check_run_args(X, nsamples, burnin, io, sampler);
         if (rc) return rc;
+        if (g_partition.on) {  // refused before any device is touched
+            rc = pt_check_armed(g_partition.o, nsamples - burnin, N, K);
+            if (rc) return rc;
+        }
         if (pred) {  // refused before any device is touched
             if (M < 0) return set_err(BMM_E_ARG, "M must be >= 0");
             if (M > 0 && !Xnew) return set_err(BMM_E_ARG, "Xnew is null");
@@ -2777,6 +3041,7 @@ int bmm_collapsed_run_probs(const int32_t* X, int64_t N, int P, const int32_t* i
                             double alpha, double beta, double gamma, double a, double b, int burnin,
                             int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
                             double* alpha_out, const bmm_relabel_hooks* hooks) {
+    PtDisarm disarm;
     RunIO io; io.z0 = initialK; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
     return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
                      device, io, hooks);
@@ -2791,6 +3056,7 @@ int bmm_dp_run(const int32_t* X, int64_t N, int P, int nsamples, double alpha, d
 int bmm_dp_run_probs(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
                      double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
                      int32_t* z_out, double* theta_out, double* alpha_out, const bmm_relabel_hooks* hooks) {
+    PtDisarm disarm;
     RunIO io; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
     return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
                      io, hooks);
@@ -2807,6 +3073,7 @@ int bmm_sb_run_probs(const int32_t* X, int64_t N, int P, const double* initialPi
                      int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b,
                      int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
                      double* alpha_out, const bmm_relabel_hooks* hooks) {
+    PtDisarm disarm;
     RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
     io.theta_out = theta_out; io.alpha_out = alpha_out;
     return run_chain(BMM_SAMPLER_SB, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
@@ -2824,6 +3091,7 @@ int bmm_full_run_probs(const int32_t* X, int64_t N, int P, const double* initial
                        int nsamples, int K, double alpha, double beta, double gamma, double a, double b,
                        int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out,
                        double* theta_out, double* alpha_out, const bmm_relabel_hooks* hooks) {
+    PtDisarm disarm;
     RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
     io.theta_out = theta_out; io.alpha_out = alpha_out;
     return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
@@ -2835,6 +3103,7 @@ int bmm_collapsed_run_predict(const int32_t* X, int64_t N, int P, const int32_t*
                               double alpha, double beta, double gamma, double a, double b, int burnin,
                               int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
                               double* alpha_out, const int32_t* Xnew, int64_t M, const bmm_predict_out* pred) {
+    PtDisarm disarm;
     if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
     RunIO io; io.z0 = initialK; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
     return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
@@ -2844,6 +3113,7 @@ int bmm_dp_run_predict(const int32_t* X, int64_t N, int P, int nsamples, double 
                        double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
                        int32_t* z_out, double* theta_out, double* alpha_out, const int32_t* Xnew, int64_t M,
                        const bmm_predict_out* pred) {
+    PtDisarm disarm;
     if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
     RunIO io; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
     return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
@@ -2853,6 +3123,7 @@ int bmm_sb_run_predict(const int32_t* X, int64_t N, int P, const double* initial
                        int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b,
                        int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
                        double* alpha_out, const int32_t* Xnew, int64_t M, const bmm_predict_out* pred) {
+    PtDisarm disarm;
     if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
     RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
     io.theta_out = theta_out; io.alpha_out = alpha_out;
@@ -2864,6 +3135,7 @@ int bmm_full_run_predict(const int32_t* X, int64_t N, int P, const double* initi
                          int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out,
                          double* theta_out, double* alpha_out, const int32_t* Xnew, int64_t M,
                          const bmm_predict_out* pred) {
+    PtDisarm disarm;
     if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
     RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
     io.theta_out = theta_out; io.alpha_out = alpha_out;
@@ -2876,6 +3148,7 @@ int bmm_collapsed_run_relabel(const int32_t* X, int64_t N, int P, const int32_t*
                               double alpha, double beta, double gamma, double a, double b, int burnin,
                               int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
                               double* alpha_out, const bmm_relabel_out* rel) {
+    PtDisarm disarm;
     if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
     RunIO io; io.z0 = initialK; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
     return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
@@ -2884,6 +3157,7 @@ int bmm_collapsed_run_relabel(const int32_t* X, int64_t N, int P, const int32_t*
 int bmm_dp_run_relabel(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
                        double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
                        int32_t* z_out, double* theta_out, double* alpha_out, const bmm_relabel_out* rel) {
+    PtDisarm disarm;
     if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
     RunIO io; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
     return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
@@ -2893,6 +3167,7 @@ int bmm_sb_run_relabel(const int32_t* X, int64_t N, int P, const double* initial
                        int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b,
                        int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
                        double* alpha_out, const bmm_relabel_out* rel) {
+    PtDisarm disarm;
     if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
     RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
     io.theta_out = theta_out; io.alpha_out = alpha_out;
@@ -2903,6 +3178,7 @@ int bmm_full_run_relabel(const int32_t* X, int64_t N, int P, const double* initi
                          int nsamples, int K, double alpha, double beta, double gamma, double a, double b,
                          int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out,
                          double* theta_out, double* alpha_out, const bmm_relabel_out* rel) {
+    PtDisarm disarm;
     if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
     RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
     io.theta_out = theta_out; io.alpha_out = alpha_out;
@@ -2989,6 +3265,72 @@ int bmm_device_stephens_plan(int64_t N, int K, int M, int64_t out[12]) {
     return BMM_OK;
 }
 
+// ---- clustering point estimate and posterior similarity: the stand-alone entry points ----
+int bmm_set_partition_summary(const bmm_partition_out* out) {
+    g_partition.on = out != nullptr;
+    if (out) g_partition.o = *out;
+    return BMM_OK;
+}
+
+int bmm_device_partition_distances(int device, const int32_t* z, int S, int64_t N, int Kc, int criterion, int stride,
+                                   double* loss_out, uint64_t* binder2_out, int* best_out, double* dist_out) {
+    return guarded([&]() -> int {
+        if (!z || !loss_out || !best_out) return set_err(BMM_E_ARG, "null argument");
+        int rc = pt_check_shape(S, N, Kc, criterion, stride);
+        if (rc == BMM_OK) rc = pt_check_labels(z, S, N, 1, Kc, nullptr);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(device));
+        PtWork w;
+        w.shape(S, N, Kc, criterion, stride);
+        rc = w.alloc_labels();
+        if (rc == BMM_OK) rc = w.alloc_pairs(dist_out != nullptr);
+        if (rc == BMM_OK) rc = pt_upload(w, z);
+        if (rc == BMM_OK) rc = pt_compute(nullptr, w);
+        if (rc) { (void)hipDeviceSynchronize(); return rc; }
+        HIP_TRY(hipDeviceSynchronize());
+        return pt_fetch(w, loss_out, binder2_out, best_out, dist_out);
+    });
+}
+
+int bmm_device_psm(int device, const int32_t* z, int S, int64_t N, const int64_t* idx, int64_t M, uint32_t* cnt_out) {
+    return guarded([&]() -> int {
+        if (!z || !idx || !cnt_out) return set_err(BMM_E_ARG, "null argument");
+        if (S < 1 || N < 1 || M < 1) return set_err(BMM_E_ARG, "similarity: S, N and M must be >= 1");
+        if (S > BMM_PARTITION_MAX_ROWS) return set_err(BMM_E_ARG, "similarity: S = %d rows is more than the %d one call takes", S, BMM_PARTITION_MAX_ROWS);
+        int rc = pt_check_idx(idx, M, N);
+        int32_t top = 1;
+        if (rc == BMM_OK) rc = pt_check_labels(z, S, N, 1, INT32_MAX, &top);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(device));
+        PtWork w;
+        w.shape(S, N, 1, BMM_PARTITION_BINDER, 1);
+        w.Kc = top;  // only the width of a label and the range check depend on it here
+        w.plan.el = top <= 256 ? 1 : 4;
+        rc = w.alloc_labels();
+        if (rc == BMM_OK) rc = pt_upload(w, z);
+        if (rc) return rc;
+        return pt_psm(nullptr, w, idx, M, cnt_out);
+    });
+}
+
+// Which form of every k_pt_* kernel a shape runs, from the function the launches call (no device is touched)
+int bmm_device_partition_plan(int S, int64_t N, int Kc, int n_candidates, int criterion, int64_t out[12]) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    int rc = pt_check_shape(S, N, Kc, criterion, 1);
+    if (rc) return rc;
+    bool ok = false;  // C = ceil(S / stride) for some stride
+    if (n_candidates >= 1 && n_candidates <= S) {
+        const int st = (S + n_candidates - 1) / n_candidates;
+        for (int q = st; q >= 1 && q >= st - 1; --q) ok = ok || (S + q - 1) / q == n_candidates;
+    }
+    if (!ok) return set_err(BMM_E_ARG, "partition: %d candidates is not ceil(%d / stride) for any stride", n_candidates, S);
+    const PtPlan p = pt_plan(S, N, Kc, n_candidates, criterion);
+    out[0] = p.el; out[1] = p.lds; out[2] = p.T; out[3] = p.R; out[4] = p.blocks; out[5] = p.wgs;
+    out[6] = p.threads; out[7] = (int64_t)p.lds_bytes; out[8] = p.tri; out[9] = p.vi; out[10] = (int64_t)p.generic_bytes;
+    out[11] = p.pitch;
+    return BMM_OK;
+}
+
 // ---- several independent chains in one call (SURVEY.md section 8 rows b, e) ----------------
 // Where bmm_multi_run puts things, as pure bookkeeping (no device is touched; tests/test_capi_cpu.py): the
 // distinct devices in first-use order -- the RCCL broadcast list, root first -- and for every chain the chain
@@ -3015,6 +3357,7 @@ int bmm_multi_run(int sampler, int n_chains, const int* devices, const int32_t* 
                   double gamma, double a, double b, int burnin, int64_t batch, uint64_t seed,
                   double* const* pi_out, int32_t* const* z_out, double* const* theta_out,
                   double* const* alpha_out) {
+    PtDisarm disarm;
     return guarded([&]() -> int {
         if (sampler < 0 || sampler > 3) return set_err(BMM_E_ARG, "unknown sampler %d", sampler);
         if (n_chains < 1) return set_err(BMM_E_ARG, "n_chains must be >= 1");

@@ -1997,4 +1997,289 @@ __global__ void k_test_variates(int kind, double pp, double qq, uint64_t seed, u
     out[i] = y;
 }
 
+// ---- partition summaries over a label trace (include/bmm_mcmc.h "clustering point estimate")
+// Labels are 0-based, one row of `pitch` labels per kept sweep (pitch a multiple of 16, so that every row starts on
+// a 16-byte boundary; the cells past N are never read), one byte each up to 256 categories, int32 above.  Every
+// count is an integer and every floating-point sum runs in an order that depends on the shape alone: each of the
+// 256 threads adds its cells in ascending order (cell k belongs to thread k mod 256), then a binary tree over the
+// threads.  No float atomics anywhere: results do not depend on scheduling.
+constexpr int kPtThreads = 256;
+constexpr int kPtMaxLdsK = 64;  // tables of Kc^2 uint32 bins in LDS up to here (16 KB each at 64)
+
+template <class T>
+__device__ inline T pt_block_sum(T v, T* slot) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    slot[tid] = v;
+    __syncthreads();
+    for (int h = kPtThreads / 2; h > 0; h >>= 1) {
+        if (tid < h) slot[tid] += slot[tid + h];
+        __syncthreads();
+    }
+    return slot[0];
+}
+__device__ inline double pt_f(uint32_t n) { return n ? (double)n * log_((double)n) : 0.0; }  // f(n) = n log n, f(0) = 0
+
+// Label (s, i) of the source, at src[s * ss + li * si] for li = i - i0 in [0, rows), minus `base`, into row s of the
+// label block: a 32 x 32 tile through LDS, read along whichever of the two source strides is 1 (the resident trace
+// has si = 1; a block of the caller's S x N column-major matrix has ss = 1) and written along i.  A label outside
+// 0 .. Kc-1 raises the flag and is stored as 0: nothing downstream indexes out of its tables.
+template <class L>
+__global__ __launch_bounds__(256) void k_pt_narrow(const int32_t* __restrict__ src, int64_t ss, int64_t si, int base,
+                                                   int S, int64_t i0, int64_t rows, int Kc, L* __restrict__ out,
+                                                   int64_t pitch, int* __restrict__ flag) {
+    __shared__ int32_t tile[32][33];
+    const int64_t b0 = (int64_t)blockIdx.x * 32;
+    const int s0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+    for (int r = ty; r < 32; r += 8) {
+        if (si == 1) {
+            const int s = s0 + r;
+            const int64_t li = b0 + tx;
+            tile[r][tx] = (s < S && li < rows) ? src[(size_t)s * ss + li] : base;
+        } else {
+            const int s = s0 + tx;
+            const int64_t li = b0 + r;
+            tile[tx][r] = (s < S && li < rows) ? src[(size_t)s * ss + (size_t)li * si] : base;
+        }
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {
+        const int s = s0 + r;
+        const int64_t li = b0 + tx;
+        if (s < S && li < rows) {
+            int v = tile[r][tx] - base;
+            if ((uint32_t)v >= (uint32_t)Kc) { *flag = 1; v = 0; }
+            out[(size_t)s * pitch + i0 + li] = (L)v;
+        }
+    }
+}
+
+// Row s: the cluster sizes n_a (one histogram per wave in LDS), A[s] = sum_a n_a^2 and F[s] = sum_a f(n_a).
+// Dynamic LDS: 4 * Kc uint32.
+template <class L>
+__global__ __launch_bounds__(256) void k_pt_sizes(const L* __restrict__ lab, int64_t pitch, int64_t N, int Kc,
+                                                  uint64_t* __restrict__ A, double* __restrict__ F) {
+    extern __shared__ uint32_t pt_lds[];
+    __shared__ uint64_t su[kPtThreads];
+    __shared__ double sd[kPtThreads];
+    const int tid = threadIdx.x;
+    for (int k = tid; k < 4 * Kc; k += kPtThreads) pt_lds[k] = 0;
+    __syncthreads();
+    const L* __restrict__ row = lab + (size_t)blockIdx.x * pitch;
+    uint32_t* const h = pt_lds + (tid >> 6) * Kc;
+    for (int64_t i = tid; i < N; i += kPtThreads) atomicAdd(&h[(uint32_t)row[i]], 1u);
+    __syncthreads();
+    uint64_t a = 0;
+    double f = 0.0;
+    for (int k = tid; k < Kc; k += kPtThreads) {
+        const uint32_t n = pt_lds[k] + pt_lds[Kc + k] + pt_lds[2 * Kc + k] + pt_lds[3 * Kc + k];
+        a += (uint64_t)n * n;
+        f += pt_f(n);
+    }
+    a = pt_block_sum(a, su);
+    f = pt_block_sum(f, sd);
+    if (tid == 0) { A[blockIdx.x] = a; F[blockIdx.x] = f; }
+}
+
+// The hot path.  Workgroup (x, y): candidate row rc = y * stride against the draws t of block x, [x * T, x * T + T),
+// one pass over all N (a contingency table must be complete before it is squared: the split is over pairs, never
+// over N).  Per draw a table of Kc^2 uint32 bins in LDS, key a * Kc + b, filled with LDS integer adds that return
+// nothing; R copies of each table, the waves of the workgroup spread over them (the few big clusters put most lanes
+// of a wave on a handful of bins).  Byte labels, four per dword.  At the end each table becomes one cell of
+// Q[y][t] = sum_ab n_ab^2 and, for VI, G[y][t] = sum_ab f(n_ab).  tri (every row a candidate, stride 1): only
+// t > rc is counted and the cell is mirrored.  Dynamic LDS: T * R * Kc^2 uint32.
+template <bool VI>
+__global__ __launch_bounds__(256) void k_pt_pairs(const uint8_t* __restrict__ lab, int64_t pitch, int64_t N, int S,
+                                                  int Kc, int stride, int T, int R, int tri,
+                                                  uint64_t* __restrict__ Q, double* __restrict__ G) {
+    extern __shared__ uint32_t pt_lds[];
+    __shared__ uint64_t su[kPtThreads];
+    __shared__ double sd[kPtThreads];
+    const int tid = threadIdx.x;
+    const int c = blockIdx.y, rc = c * stride;
+    int t0 = blockIdx.x * T;
+    const int t1 = t0 + T < S ? t0 + T : S;
+    if (tri && t0 <= rc) t0 = rc + 1;
+    if (t0 >= t1) return;  // the whole workgroup
+    const int nT = t1 - t0, KK = Kc * Kc, TS = R * KK;
+    for (int k = tid; k < nT * TS; k += kPtThreads) pt_lds[k] = 0;
+    __syncthreads();
+    uint32_t* const mine = pt_lds + ((tid >> 6) % R) * KK;  // table tt, copy r at (tt * R + r) * KK
+    const uint8_t* __restrict__ ca = lab + (size_t)rc * pitch;
+    const uint8_t* __restrict__ da = lab + (size_t)t0 * pitch;
+    const int64_t W = N >> 2;
+    for (int64_t w = tid; w < W; w += kPtThreads) {
+        const uint32_t a4 = reinterpret_cast<const uint32_t*>(ca)[w];
+        const uint32_t k0 = (a4 & 255u) * Kc, k1 = ((a4 >> 8) & 255u) * Kc, k2 = ((a4 >> 16) & 255u) * Kc, k3 = (a4 >> 24) * Kc;
+#pragma unroll 4
+        for (int tt = 0; tt < nT; ++tt) {
+            if (t0 + tt == rc) continue;  // a row against itself is never used (k_pt_loss): no pass over it
+            const uint32_t b4 = reinterpret_cast<const uint32_t*>(da + (size_t)tt * pitch)[w];
+            uint32_t* const tb = mine + tt * TS;
+            atomicAdd(tb + k0 + (b4 & 255u), 1u);
+            atomicAdd(tb + k1 + ((b4 >> 8) & 255u), 1u);
+            atomicAdd(tb + k2 + ((b4 >> 16) & 255u), 1u);
+            atomicAdd(tb + k3 + (b4 >> 24), 1u);
+        }
+    }
+    for (int64_t i = (W << 2) + tid; i < N; i += kPtThreads) {
+        const uint32_t k0 = (uint32_t)ca[i] * Kc;
+        for (int tt = 0; tt < nT; ++tt)
+            if (t0 + tt != rc) atomicAdd(mine + tt * TS + k0 + da[(size_t)tt * pitch + i], 1u);
+    }
+    __syncthreads();
+    for (int tt = 0; tt < nT; ++tt) {
+        uint64_t q = 0;
+        double g = 0.0;
+        for (int k = tid; k < KK; k += kPtThreads) {
+            uint32_t n = 0;
+            for (int r = 0; r < R; ++r) n += pt_lds[(tt * R + r) * KK + k];
+            q += (uint64_t)n * n;
+            if (VI) g += pt_f(n);
+        }
+        q = pt_block_sum(q, su);
+        if (VI) g = pt_block_sum(g, sd);
+        if (tid == 0) {
+            const int t = t0 + tt;
+            Q[(size_t)c * S + t] = q;
+            if (VI) G[(size_t)c * S + t] = g;
+            if (tri) {
+                Q[(size_t)t * S + c] = q;
+                if (VI) G[(size_t)t * S + c] = g;
+            }
+        }
+    }
+}
+
+// The same for more than kPtMaxLdsK categories (up to the 1024 the generic resample path takes): one table of
+// Kc^2 uint32 per workgroup in global memory, zeroed per pair, filled with global integer adds and read back past
+// the L1, the workgroups striding over the C x S pairs.  A correctness fallback, as k_resample_generic is.
+template <class L, bool VI>
+__global__ __launch_bounds__(256) void k_pt_pairs_generic(const L* __restrict__ lab, int64_t pitch, int64_t N, int S,
+                                                          int Kc, int stride, int C, int tri, uint32_t* tabs,
+                                                          uint64_t* __restrict__ Q, double* __restrict__ G) {
+    __shared__ uint64_t su[kPtThreads];
+    __shared__ double sd[kPtThreads];
+    const int tid = threadIdx.x;
+    const size_t KK = (size_t)Kc * Kc;
+    uint32_t* const tab = tabs + (size_t)blockIdx.x * KK;
+    for (int64_t p = blockIdx.x; p < (int64_t)C * S; p += gridDim.x) {
+        const int c = (int)(p / S), t = (int)(p % S), rc = c * stride;
+        if (tri ? t <= rc : t == rc) continue;  // the whole workgroup
+        for (size_t k = tid; k < KK; k += kPtThreads) __hip_atomic_store(tab + k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        __syncthreads();
+        const L* __restrict__ ca = lab + (size_t)rc * pitch;
+        const L* __restrict__ da = lab + (size_t)t * pitch;
+        for (int64_t i = tid; i < N; i += kPtThreads) atomicAdd(tab + (size_t)(uint32_t)ca[i] * Kc + (uint32_t)da[i], 1u);
+        __threadfence();
+        __syncthreads();
+        uint64_t q = 0;
+        double g = 0.0;
+        for (size_t k = tid; k < KK; k += kPtThreads) {
+            const uint32_t n = __hip_atomic_load(tab + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            q += (uint64_t)n * n;
+            if (VI) g += pt_f(n);
+        }
+        q = pt_block_sum(q, su);
+        if (VI) g = pt_block_sum(g, sd);
+        if (tid == 0) {
+            Q[(size_t)c * S + t] = q;
+            if (VI) G[(size_t)c * S + t] = g;
+            if (tri) {
+                Q[(size_t)t * S + c] = q;
+                if (VI) G[(size_t)t * S + c] = g;
+            }
+        }
+    }
+}
+
+// Candidate c (row rc = c * stride) against every draw: 2 B(rc, t) = A[rc] + A[t] - 2 Q[c][t], exact in uint64, and
+// VI(rc, t) = (F[rc] + F[t] - 2 G[c][t]) / N -- exactly 0 on the diagonal (not computed) and wherever the Binder
+// distance is 0 (the two rows are one partition).  sum2[c] = sum_t 2 B, loss[c] = sum2 / (2 S) or the mean VI;
+// dist, unless null, is C x S column-major: B as a double (exact below 2^53) or VI.
+__global__ __launch_bounds__(256) void k_pt_loss(const uint64_t* __restrict__ A, const double* __restrict__ F,
+                                                 const uint64_t* __restrict__ Q, const double* __restrict__ G, int S,
+                                                 int C, int stride, int64_t N, int vi, uint64_t* __restrict__ sum2,
+                                                 double* __restrict__ loss, double* __restrict__ dist) {
+    __shared__ uint64_t su[kPtThreads];
+    __shared__ double sd[kPtThreads];
+    const int tid = threadIdx.x, c = blockIdx.x, rc = c * stride;
+    uint64_t b = 0;
+    double v = 0.0;
+    for (int t = tid; t < S; t += kPtThreads) {
+        uint64_t d2 = 0;
+        double dv = 0.0;
+        if (t != rc) {
+            d2 = A[rc] + A[t] - 2 * Q[(size_t)c * S + t];
+            if (vi && d2 != 0) dv = (F[rc] + F[t] - 2.0 * G[(size_t)c * S + t]) / (double)N;
+        }
+        b += d2;
+        v += dv;
+        if (dist) dist[(size_t)c + (size_t)C * t] = vi ? dv : (double)(d2 >> 1);
+    }
+    b = pt_block_sum(b, su);
+    v = pt_block_sum(v, sd);
+    if (tid == 0) {
+        sum2[c] = b;
+        loss[c] = vi ? v / (double)S : (double)b / (2.0 * (double)S);
+    }
+}
+
+// the candidate with the smallest loss (Binder: the exact integer total; VI: the double), lowest index on ties
+__global__ __launch_bounds__(256) void k_pt_argmin(const uint64_t* __restrict__ sum2, const double* __restrict__ loss,
+                                                   int C, int vi, int* __restrict__ best) {
+    __shared__ int idx[kPtThreads];
+    const int tid = threadIdx.x;
+    auto less = [&](int i, int j) {  // i beats j
+        if (j < 0) return i >= 0;
+        if (i < 0) return false;
+        if (vi) return loss[i] < loss[j] || (loss[i] == loss[j] && i < j);
+        return sum2[i] < sum2[j] || (sum2[i] == sum2[j] && i < j);
+    };
+    int m = -1;
+    for (int c = tid; c < C; c += kPtThreads) if (less(c, m)) m = c;
+    idx[tid] = m;
+    __syncthreads();
+    for (int h = kPtThreads / 2; h > 0; h >>= 1) {
+        if (tid < h && less(idx[tid + h], idx[tid])) idx[tid] = idx[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) *best = idx[0];
+}
+
+// the labels of the chosen observations, gathered once: g[s][u] = lab[s][idx[u]]
+template <class L>
+__global__ __launch_bounds__(256) void k_pt_gather(const L* __restrict__ lab, int64_t pitch, const int64_t* __restrict__ idx,
+                                                   int64_t M, L* __restrict__ g) {
+    const int64_t u = (int64_t)blockIdx.x * kPtThreads + threadIdx.x;
+    if (u < M) g[(size_t)blockIdx.y * M + u] = lab[(size_t)blockIdx.y * pitch + idx[u]];
+}
+// Posterior similarity counts cnt[u][v] = #{s : g[s][u] == g[s][v]}: a 64 x 64 tile per workgroup, 4 x 4 cells per
+// thread, the counts in registers over all S rows and stored once; tiles on or above the diagonal, mirrored on store.
+template <class L>
+__global__ __launch_bounds__(256) void k_pt_psm(const L* __restrict__ g, int S, int64_t M, uint32_t* __restrict__ cnt) {
+    if (blockIdx.x < blockIdx.y) return;
+    const int64_t u0 = (int64_t)blockIdx.y * 64 + (threadIdx.x >> 4) * 4;
+    const int64_t v0 = (int64_t)blockIdx.x * 64 + (threadIdx.x & 15) * 4;
+    uint32_t n[4][4] = {};
+    for (int s = 0; s < S; ++s) {
+        const L* __restrict__ row = g + (size_t)s * M;
+        L lu[4], lv[4];
+        for (int a = 0; a < 4; ++a) {
+            lu[a] = u0 + a < M ? row[u0 + a] : (L)0;
+            lv[a] = v0 + a < M ? row[v0 + a] : (L)0;
+        }
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) n[a][b] += lu[a] == lv[b] ? 1u : 0u;
+    }
+    for (int a = 0; a < 4; ++a)
+        for (int b = 0; b < 4; ++b)
+            if (u0 + a < M && v0 + b < M) {
+                cnt[(size_t)(u0 + a) * M + (v0 + b)] = n[a][b];
+                cnt[(size_t)(v0 + b) * M + (u0 + a)] = n[a][b];
+            }
+}
+
 }  // namespace bmm

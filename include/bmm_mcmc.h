@@ -453,6 +453,80 @@ int bmm_full_run_predict(const int32_t* X, int64_t N, int P, const double* initi
                          double* theta_out, double* alpha_out, const int32_t* Xnew, int64_t M,
                          const bmm_predict_out* pred);
 
+/* ---- clustering point estimate and posterior similarity ------------------------------
+ * Label-invariant summaries of a label trace, computed where the trace is.  A row z of N labels in 0 .. Kc-1 is a
+ * partition.  For two rows c, z let n_ab = #{i : c_i = a, z_i = b}, n_a. = sum_b n_ab, n_.b = sum_a n_ab.
+ *   Binder distance   B(c, z) = (sum_a n_a.^2 + sum_b n_.b^2 - 2 sum_ab n_ab^2) / 2: the pairs i < j on which the two
+ *                     partitions disagree, an exact integer;
+ *   VI distance       VI(c, z) = (sum_a f(n_a.) + sum_b f(n_.b) - 2 sum_ab f(n_ab)) / N in nats, f(n) = n log n, f(0) = 0,
+ *                     with the spec's log_ (DESIGN.md "Numerics").  Every sum runs in an order fixed by the shape (256
+ *                     partial sums, cell k in partial k mod 256, ascending; then a binary tree), d(z, z) = 0 by
+ *                     construction (the diagonal is not computed), and VI is exactly 0 wherever B is 0;
+ *   expected loss     of candidate row c over the S draws: L(c) = (1/S) sum_t d(c, z_t); binder2 = sum_t 2 B(c, z_t) is
+ *                     the exact integer behind it (for Binder L = binder2 / (2 S));
+ *   point estimate    the candidate with the smallest L (Binder: the smallest binder2), lowest index on ties.
+ *                     Candidates are rows 0, stride, 2 stride, ... (C = ceil(S / stride) of them; stride = 1: every row);
+ *                     the draws are always all S rows;
+ *   similarity        of chosen observations idx[0 .. M): cnt[u, v] = #{t : z_t[idx_u] = z_t[idx_v]}, uint32, M x M,
+ *                     symmetric, diagonal S.
+ * With delta_ij = [c_i = c_j]: sum_{i<j} (S delta_ij - cnt_ij)^2 = S sum_t B(c, z_t) + sum_{i<j} cnt_ij^2 - S sum_{i<j} cnt_ij,
+ * so Dahl's least-squares criterion against the full N x N similarity matrix orders the candidates as the expected
+ * Binder loss does, and that matrix is never needed.
+ * A row with a label below 1 (1-based, as z_out) or above Kc is not a partition: the stand-alone entry points refuse
+ * it, naming the row and the observation, before a device is touched. */
+#define BMM_PARTITION_BINDER 0
+#define BMM_PARTITION_VI 1
+#define BMM_PARTITION_MAX_K 1024
+#define BMM_PARTITION_MAX_ROWS 65535 /* rows of one call (a grid dimension of the launches) */
+/* z: S x N int32 column-major, 1-based, as z_out -- any stack of rows over the same observations, so traces of several
+ * chains can be pooled by the caller.  loss_out C doubles; binder2_out C uint64 or NULL (filled under either
+ * criterion); best_out the row of z (0-based, a multiple of stride) of the point estimate; dist_out C x S doubles
+ * column-major or NULL: B (exact below 2^53) or VI of candidate c against row t.  BMM_E_ARG unless 1 <= S <=
+ * BMM_PARTITION_MAX_ROWS, N >= 1,
+ * stride >= 1, 1 <= Kc <= BMM_PARTITION_MAX_K and S * N^2 < 2^63 (the integer totals would overflow). */
+int bmm_device_partition_distances(int device, const int32_t* z, int S, int64_t N, int Kc, int criterion, int stride,
+                                   double* loss_out, uint64_t* binder2_out, int* best_out, double* dist_out);
+/* idx: M observations, 0-based, in any order, repeats allowed; cnt_out M x M uint32.  Labels may be any values >= 1.
+ * S at most BMM_PARTITION_MAX_ROWS.  BMM_E_ARG, naming the bytes, when the M^2 counts and the S x M block of gathered labels do not fit in device memory. */
+int bmm_device_psm(int device, const int32_t* z, int S, int64_t N, const int64_t* idx, int64_t M, uint32_t* cnt_out);
+/* Which form of the kernels a shape runs, as pure bookkeeping -- no device is touched, and the values come from the
+ * functions the launches themselves call.  out:
+ *   [0] bytes per label on the device (1 up to 256 categories, else 4)
+ *   [1] 1: contingency tables in LDS (Kc <= 64); 0: the generic form, tables in global memory
+ *   [2] draws per workgroup, T                    [3] copies of each table, R (4 while a table is at most 1 KiB)
+ *   [4] blocks of draws, ceil(S / T)              [5] workgroups launched ([4] x candidates; generic: its grid)
+ *   [6] threads per workgroup                     [7] bytes of dynamic LDS (0: generic)
+ *   [8] 1 when only t > c is counted and mirrored (every row a candidate)
+ *   [9] 1 when the VI sums are computed           [10] bytes of tables in global memory (0: LDS form)
+ *   [11] labels per row of the device block (N rounded up to 16).
+ * BMM_E_ARG as bmm_device_partition_distances, and unless n_candidates = ceil(S / stride) for some stride >= 1. */
+int bmm_device_partition_plan(int S, int64_t N, int Kc, int n_candidates, int criterion, int64_t out[12]);
+/* For a run: armed per calling thread, like bmm_set_progress, for the NEXT single-chain *_run* call of that thread
+ * (plain, _probs, _relabel, _predict) and disarmed when that call returns, whatever it returns; NULL disarms.  The
+ * struct is copied; its buffers must stay valid through that call.  With it armed the run computes the summary from
+ * the resident trace after the last sweep and before the trace leaves, on the labels as sampled (the quantities do
+ * not depend on the numbering, so a relabelling run gives the same).  Trace row 0 of a run without burn-in is the
+ * starting state; where that is no partition (every sampler but the finite collapsed one leaves it unassigned) the
+ * row is left out of candidates and draws alike: n_used = S - 1, candidates are rows first, first + stride, ...
+ * with first = S - n_used, and loss, binder2 and dist have ceil(n_used / stride) rows and n_used columns.  Not armed:
+ * nothing changes, no allocation, no launch.  bmm_multi_run does not take it (pool chains through the stand-alone
+ * call): a bmm_multi_run call of the arming thread disarms it like any other run and computes no summary.  The summary's time is counted in phases [3] and [4] of bmm_last_run_phases (it sits between the last sweep
+ * and the trace on its way out). */
+typedef struct bmm_partition_out {
+    int criterion;           /* BMM_PARTITION_BINDER or BMM_PARTITION_VI */
+    int stride;              /* >= 1 */
+    double* loss;            /* room for ceil(S / stride) doubles */
+    uint64_t* binder2;       /* the same count, or NULL */
+    int* best;               /* row of the trace (0-based) of the point estimate; -1 when no row was usable */
+    int32_t* z_best;         /* N int32, 1-based: that row, the labels as sampled; or NULL */
+    int* n_used;             /* rows used */
+    double* dist;            /* room for ceil(S / stride) x S doubles, or NULL */
+    const int64_t* psm_idx;  /* psm_M observations, 0-based, or NULL */
+    int64_t psm_M;
+    uint32_t* psm_cnt;       /* psm_M x psm_M, counts over the rows used */
+} bmm_partition_out;
+int bmm_set_partition_summary(const bmm_partition_out* out);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
