@@ -3,8 +3,8 @@
 Two variants of the same sources:
   lib/libbmmmcmc_hip.so      the product: reads no environment, no debug hooks
   lib/libbmmmcmc_hip_dbg.so  -DBMM_DEBUG_HOOKS: the kernel-steering environment switches the parity
-                             tests use to reach every kernel variant (BMM_DEBUG_GENERIC,
-                             BMM_DEBUG_THREADS, BMM_DEBUG_NOSPLIT, BMM_DEBUG_CUS, BMM_X_LAYOUT_INT32)
+                             tests use to reach every kernel variant (listed at struct DebugSwitches
+                             in csrc/chain.hip)
 `BMM_LIB_PATH` makes _capi.py load another build (tools/exp_lib.sh, tools/diag.sh) -- nothing ever
 overwrites the product library in place.
 """

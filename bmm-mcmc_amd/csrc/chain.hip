@@ -30,6 +30,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -306,12 +307,27 @@ struct PhaseClock {
     }
 };
 
-// accumulator counts the resample kernel is instantiated for
-const int kKT[] = {4, 8, 12, 16, 20, 24, 28, 32, 40, 48, 52, 56, 64};  // (52: maxK = 50, BASELINE config 4)
+// A list of integers known at compile time, and the one lift from run-time values to template arguments: for
+// each (list, value) pair the element equal to the value is handed to f as a std::integral_constant, all of
+// them in one call.  False, and f not called, when some value is in none of its list's elements.
+template <int... V> struct IntList {};
+template <class F> bool lift(F&& f) { f(); return true; }
+template <class F, int... V, class... Rest>
+bool lift(F&& f, IntList<V...>, int v, Rest... rest) {
+    return ((v == V && lift([&](auto... c) { f(std::integral_constant<int, V>{}, c...); }, rest...)) || ...);
+}
+
+// accumulator counts the resample and predictive kernels are instantiated for
+constexpr IntList<4, 8, 12, 16, 20, 24, 28, 32, 40, 48, 52, 56, 64> kKT{};  // (52: maxK = 50, BASELINE config 4)
+template <int... V>
+int pick_kt(IntList<V...>, int cats) { for (int kt : {V...}) if (kt >= cats) return kt; return -1; }
+int pick_kt(int cats) { return pick_kt(kKT, cats); }
+
 // workgroup size by accumulator count: the VGPR budget per lane is 512 / (waves per SIMD)
 constexpr int kThreadsSmall = 1024;  // KT <= 12: 128 VGPRs
 constexpr int kThreadsMid = 768;     // KT 16, 20: 168 VGPRs
 constexpr int kThreadsLarge = 512;   // 256 VGPRs
+constexpr int kThreadsSplit = 1024;  // two lanes per observation (SPLIT = 2 in kernels.hip.h)
 #ifndef BMM_STREAM_MODE
 #define BMM_STREAM_MODE 2  // chains that share a device: a hardware queue of its own each (chain_stream_create)
 #endif
@@ -319,203 +335,115 @@ constexpr int kThreadsLarge = 512;   // 256 VGPRs
 #define BMM_STAGE_WIDE 32
 #endif
 #ifndef BMM_SMALL_SPLIT
-#define BMM_SMALL_SPLIT 1  // short launches of 16-32 accumulators run two lanes per observation (pick_kernel)
+#define BMM_SMALL_SPLIT 1  // short launches of 16-32 accumulators run two lanes per observation (plan_kernel)
 #endif
 #ifndef BMM_SELF_TABLES
-#define BMM_SELF_TABLES 1  // small finite-sampler shapes: resample workgroups build their own tables (pick_kernel)
+#define BMM_SELF_TABLES 1  // small finite-sampler shapes: resample workgroups build their own tables (plan_kernel)
 #endif
 constexpr int kStageWide = BMM_STAGE_WIDE;  // features in flight per wave where registers allow
 
-int pick_kt(int cats) {
-    for (int kt : kKT)
-        if (kt >= cats) return kt;
-    return -1;
-}
-// the bit-plane kernel holds no feature loads in flight, which frees 20-odd VGPRs: one size up
-int threads_for(int kt, bool bits) {
+// The default workgroup size of the one-lane kernels.  The bit-plane kernel holds no feature loads in flight,
+// which frees 20-odd VGPRs: one size up.
+constexpr int threads_for(int kt, bool bits) {
     if (bits) return kt <= 20 ? kThreadsSmall : (kt <= 32 ? kThreadsMid : kThreadsLarge);
     return kt <= 12 ? kThreadsSmall : (kt <= 20 ? kThreadsMid : kThreadsLarge);
 }
 
+// One instantiation of k_resample, named by what bmm_dbg_kernel_key reports of it.
+struct KernelForm {
+    int kt = 0;         // accumulators
+    int nt = 0;         // threads per workgroup
+    int minus = 0;      // own-cluster tables: 0 none (stick-breaking / full), 1 in LDS, 2 in global memory
+    bool bits = false;  // X streamed as bit planes (k_pack_bits) instead of the int32 matrix as handed over
+    int lanes = 1;      // lanes per observation (SPLIT)
+    bool emit = false;  // the weight-emitting twin: what a sweep runs on while its probabilities go to the host
+    int gw = kGroupW;   // the shape's group width (bmm_spec.h)
+    bool self = false;  // workgroups that build their own table image (SELF)
+};
+constexpr int tile_of(const KernelForm& f) { return f.nt / f.lanes; }  // observations per tile
+constexpr KernelForm resized(KernelForm f, int nt, int lanes = 1) { f.nt = nt; f.lanes = lanes; return f; }
+// The emitting twin of a bit-plane chain's kernel: default-sized and one lane per observation whatever the
+// chain itself runs (any workgroup size serves any batch), same tables.
+constexpr KernelForm emit_twin(const KernelForm& f) {
+    return KernelForm{f.kt, threads_for(f.kt, true), f.minus, true, 1, true, f.gw, false};
+}
+
+// STG, the one template argument that is not part of the form: features in flight per wave.  16 wherever
+// registers are short -- bit planes, more than 20 accumulators, the 256-thread kernels -- and kStageWide
+// otherwise, with one exception in either direction at 1024 threads (128 VGPRs): a size that was named
+// (BMM_DEBUG_THREADS, the experiment knob of tools/try_threads.sh) gets 16 by that register rule, while the
+// default kernel of 4-12 accumulators, which has that size by threads_for, keeps the measured kStageWide.  So
+// the int32 kernel of 4-12 accumulators at 1024 threads exists twice, and named_size tells the two apart.
+constexpr int stage_width(const KernelForm& f, bool named_size) {
+    if (f.bits || f.kt > 20 || f.nt == 256) return 16;
+    if (f.nt == kThreadsSmall) return f.nt == threads_for(f.kt, false) && !named_size ? kStageWide : 16;
+    return kStageWide;
+}
+
+// Which forms are instantiated: the whole kernel set of the library.  (accumulator counts: those of kKT)
+constexpr bool instantiated(const KernelForm& f, bool named_size) {
+    const bool preferred = f.gw == kGroupW;
+    // SELF: 256-thread workgroups that build their own table image (finite sampler, small shapes: kernels.hip.h)
+    if (f.self) return f.kt <= 12 && f.nt == 256 && f.minus == 1 && f.bits && f.lanes == 1 && !f.emit && preferred;
+    // EMIT: the twins of the default-sized bit-plane kernels, every tier and width
+    if (f.emit) return f.bits && f.lanes == 1 && f.nt == threads_for(f.kt, true);
+    // two lanes per observation, bit planes: more than 32 accumulators at either width, 16 to 32 (for launches too
+    // short to give a wave more than a chunk or two) at the preferred one; own-cluster tables from LDS only
+    if (f.lanes == 2) return f.bits && f.nt == kThreadsSplit && f.minus != 2 && (f.kt > 32 || (f.kt >= 16 && preferred));
+    if (f.lanes != 1) return false;
+    // the default-sized kernels: every tier, both layouts, both widths
+    if (f.nt == threads_for(f.kt, f.bits) && !named_size) return true;
+    // other workgroup sizes for the preferred width only (shapes that fall back to the narrower groups are the
+    // ones with big tables), and not with the own-cluster tables in global memory:
+    if (!preferred || f.minus == 2) return false;
+    // 256 threads: used when a batch is too small to give every CU a workgroup otherwise
+    if (f.nt == 256) return true;
+    // a chosen size up to 32 accumulators: the stepped-down workgroups of a batch too small to give every CU a
+    // default-sized one (bit planes), and BMM_DEBUG_THREADS (the int32 layout with own-cluster tables in LDS only)
+    return (f.nt == 1024 || f.nt == 768 || f.nt == 512) && f.kt <= 32 && (f.bits || f.minus == 1);
+}
+
 typedef void (*resample_fn)(ChainParams, ResampleArgs);
-// BITS: X streamed as bit planes (k_pack_bits) instead of the int32 matrix as handed over
-// GW: the shape's group width (bmm_spec.h).  The default-sized kernels, their two-lane forms and their
-// emitting twins exist for both widths; the stepped-down workgroup sizes for the preferred width only
-// (shapes that fall back to the narrower groups are the ones with big tables).
-template <int MINUS, bool BITS, int GW>
-resample_fn resample_kernel_m(int kt) {
-    constexpr int SW = BITS ? 16 : kStageWide;
-    switch (kt) {
-        case 4: return k_resample<4, kThreadsSmall, MINUS, SW, BITS, 1, false, GW>;
-        case 8: return k_resample<8, kThreadsSmall, MINUS, SW, BITS, 1, false, GW>;
-        case 12: return k_resample<12, kThreadsSmall, MINUS, SW, BITS, 1, false, GW>;
-        case 16: return k_resample<16, BITS ? kThreadsSmall : kThreadsMid, MINUS, SW, BITS, 1, false, GW>;
-        case 20: return k_resample<20, BITS ? kThreadsSmall : kThreadsMid, MINUS, SW, BITS, 1, false, GW>;
-        case 24: return k_resample<24, BITS ? kThreadsMid : kThreadsLarge, MINUS, 16, BITS, 1, false, GW>;
-        case 28: return k_resample<28, BITS ? kThreadsMid : kThreadsLarge, MINUS, 16, BITS, 1, false, GW>;
-        case 32: return k_resample<32, BITS ? kThreadsMid : kThreadsLarge, MINUS, 16, BITS, 1, false, GW>;
-        case 40: return k_resample<40, kThreadsLarge, MINUS, 16, BITS, 1, false, GW>;
-        case 48: return k_resample<48, kThreadsLarge, MINUS, 16, BITS, 1, false, GW>;
-        case 52: return k_resample<52, kThreadsLarge, MINUS, 16, BITS, 1, false, GW>;
-        case 56: return k_resample<56, kThreadsLarge, MINUS, 16, BITS, 1, false, GW>;
-        case 64: return k_resample<64, kThreadsLarge, MINUS, 16, BITS, 1, false, GW>;
-    }
-    return nullptr;
+// The instantiation a form names, nullptr when there is none.  Nothing outside `instantiated` is instantiated.
+template <int KT, int NT, int MINUS, bool BITS, int GW, int LANES, bool EMIT, bool SELF, bool NAMED>
+resample_fn instance() {
+    constexpr KernelForm F{KT, NT, MINUS, BITS, LANES, EMIT, GW, SELF};
+    if constexpr (instantiated(F, NAMED)) return k_resample<KT, NT, MINUS, stage_width(F, NAMED), BITS, LANES, EMIT, GW, SELF>;
+    else return nullptr;
 }
-// 256-thread variants: used when a batch is too small to give every CU a workgroup otherwise
-template <int MINUS, bool BITS>
-resample_fn resample_kernel_small(int kt) {
-    switch (kt) {
-        case 4: return k_resample<4, 256, MINUS, 16, BITS>;
-        case 8: return k_resample<8, 256, MINUS, 16, BITS>;
-        case 12: return k_resample<12, 256, MINUS, 16, BITS>;
-        case 16: return k_resample<16, 256, MINUS, 16, BITS>;
-        case 20: return k_resample<20, 256, MINUS, 16, BITS>;
-        case 24: return k_resample<24, 256, MINUS, 16, BITS>;
-        case 28: return k_resample<28, 256, MINUS, 16, BITS>;
-        case 32: return k_resample<32, 256, MINUS, 16, BITS>;
-        case 40: return k_resample<40, 256, MINUS, 16, BITS>;
-        case 48: return k_resample<48, 256, MINUS, 16, BITS>;
-        case 52: return k_resample<52, 256, MINUS, 16, BITS>;
-        case 56: return k_resample<56, 256, MINUS, 16, BITS>;
-        case 64: return k_resample<64, 256, MINUS, 16, BITS>;
-    }
-    return nullptr;
+resample_fn lookup(const KernelForm& f, bool named_size = false) {
+    resample_fn fn = nullptr;
+    lift([&](auto kt, auto nt, auto minus, auto bits, auto gw) {
+        // two lanes, EMIT, SELF and a named size come one at a time (lifting them as well would cost the compiler
+        // sixteen times the combinations for the same five)
+        if (f.lanes == 2) fn = f.emit || f.self ? nullptr : instance<kt, nt, minus, bits != 0, gw, 2, false, false, false>();
+        else if (f.lanes != 1 || (f.emit && f.self)) fn = nullptr;
+        else if (f.emit) fn = instance<kt, nt, minus, bits != 0, gw, 1, true, false, false>();
+        else if (f.self) fn = instance<kt, nt, minus, bits != 0, gw, 1, false, true, false>();
+        else if (named_size) fn = instance<kt, nt, minus, bits != 0, gw, 1, false, false, true>();
+        else fn = instance<kt, nt, minus, bits != 0, gw, 1, false, false, false>();
+    }, kKT, f.kt, IntList<1024, 768, 512, 256>{}, f.nt, IntList<0, 1, 2>{}, f.minus, IntList<0, 1>{}, (int)f.bits,
+       IntList<kGroupW, kGroupWAlt>{}, f.gw);
+    return fn;
 }
-// the same kernels at a chosen workgroup size (up to 32 categories): used when a batch is too
-// small to give every CU one of the default-sized workgroups, and by BMM_DEBUG_THREADS
-template <int NT, int MINUS, bool BITS>
-resample_fn resample_kernel_nt(int kt) {
-    constexpr int SW = BITS || NT == 1024 ? 16 : kStageWide;  // 1024 threads: 128 VGPRs, 16 loads in flight per wave
-    switch (kt) {
-        case 4: return k_resample<4, NT, MINUS, SW, BITS>;
-        case 8: return k_resample<8, NT, MINUS, SW, BITS>;
-        case 12: return k_resample<12, NT, MINUS, SW, BITS>;
-        case 16: return k_resample<16, NT, MINUS, SW, BITS>;
-        case 20: return k_resample<20, NT, MINUS, SW, BITS>;
-        case 24: return k_resample<24, NT, MINUS, 16, BITS>;
-        case 28: return k_resample<28, NT, MINUS, 16, BITS>;
-        case 32: return k_resample<32, NT, MINUS, 16, BITS>;
-    }
-    return nullptr;
-}
-resample_fn resample_kernel_at(int kt, int nt, int minus, bool bits) {
-    if (minus == 2) return nullptr;
-    if (bits) {
-        if (nt == 768) return minus ? resample_kernel_nt<768, 1, true>(kt) : resample_kernel_nt<768, 0, true>(kt);
-        if (nt == 512) return minus ? resample_kernel_nt<512, 1, true>(kt) : resample_kernel_nt<512, 0, true>(kt);
-        if (nt == 1024 && kt <= 20) return minus ? resample_kernel_nt<1024, 1, true>(kt) : resample_kernel_nt<1024, 0, true>(kt);
-        return nullptr;
-    }
-    if (kt > 20 || minus != 1) return nullptr;
-    if (nt == 1024) return resample_kernel_nt<1024, 1, false>(kt);
-    if (nt == 768) return resample_kernel_nt<768, 1, false>(kt);
-    if (nt == 512) return resample_kernel_nt<512, 1, false>(kt);
-    return nullptr;
-}
-// more than 32 accumulators on bit planes: two lanes per observation (SPLIT = 2 in kernels.hip.h)
-constexpr int kThreadsSplit = 1024;
-template <int MINUS, int GW>
-resample_fn resample_kernel_split_w(int kt) {
-    switch (kt) {
-        // 16 to 32 accumulators: for launches too short to give a wave more than a chunk or two (pick_kernel)
-        case 16: return GW == kGroupW ? k_resample<16, kThreadsSplit, MINUS, 16, true, 2, false, kGroupW> : nullptr;
-        case 20: return GW == kGroupW ? k_resample<20, kThreadsSplit, MINUS, 16, true, 2, false, kGroupW> : nullptr;
-        case 24: return GW == kGroupW ? k_resample<24, kThreadsSplit, MINUS, 16, true, 2, false, kGroupW> : nullptr;
-        case 28: return GW == kGroupW ? k_resample<28, kThreadsSplit, MINUS, 16, true, 2, false, kGroupW> : nullptr;
-        case 32: return GW == kGroupW ? k_resample<32, kThreadsSplit, MINUS, 16, true, 2, false, kGroupW> : nullptr;
-        case 40: return k_resample<40, kThreadsSplit, MINUS, 16, true, 2, false, GW>;
-        case 48: return k_resample<48, kThreadsSplit, MINUS, 16, true, 2, false, GW>;
-        case 52: return k_resample<52, kThreadsSplit, MINUS, 16, true, 2, false, GW>;
-        case 56: return k_resample<56, kThreadsSplit, MINUS, 16, true, 2, false, GW>;
-        case 64: return k_resample<64, kThreadsSplit, MINUS, 16, true, 2, false, GW>;
-    }
-    return nullptr;
-}
-template <int MINUS>
-resample_fn resample_kernel_split(int kt, int gw) {
-    return gw == kGroupW ? resample_kernel_split_w<MINUS, kGroupW>(kt) : resample_kernel_split_w<MINUS, kGroupWAlt>(kt);
-}
-// The weight-emitting twins (EMIT) of the default-sized bit-plane kernels: what a sweep runs on
-// while its allocation probabilities go to the host (any workgroup size serves any batch).
-template <int MINUS, int GW>
-resample_fn resample_kernel_emit_m(int kt) {
-    switch (kt) {
-        case 4: return k_resample<4, kThreadsSmall, MINUS, 16, true, 1, true, GW>;
-        case 8: return k_resample<8, kThreadsSmall, MINUS, 16, true, 1, true, GW>;
-        case 12: return k_resample<12, kThreadsSmall, MINUS, 16, true, 1, true, GW>;
-        case 16: return k_resample<16, kThreadsSmall, MINUS, 16, true, 1, true, GW>;
-        case 20: return k_resample<20, kThreadsSmall, MINUS, 16, true, 1, true, GW>;
-        case 24: return k_resample<24, kThreadsMid, MINUS, 16, true, 1, true, GW>;
-        case 28: return k_resample<28, kThreadsMid, MINUS, 16, true, 1, true, GW>;
-        case 32: return k_resample<32, kThreadsMid, MINUS, 16, true, 1, true, GW>;
-        case 40: return k_resample<40, kThreadsLarge, MINUS, 16, true, 1, true, GW>;
-        case 48: return k_resample<48, kThreadsLarge, MINUS, 16, true, 1, true, GW>;
-        case 52: return k_resample<52, kThreadsLarge, MINUS, 16, true, 1, true, GW>;
-        case 56: return k_resample<56, kThreadsLarge, MINUS, 16, true, 1, true, GW>;
-        case 64: return k_resample<64, kThreadsLarge, MINUS, 16, true, 1, true, GW>;
-    }
-    return nullptr;
-}
-template <int GW>
-resample_fn resample_kernel_emit_w(int kt, int minus) {
-    return minus == 0 ? resample_kernel_emit_m<0, GW>(kt)
-                      : (minus == 1 ? resample_kernel_emit_m<1, GW>(kt) : resample_kernel_emit_m<2, GW>(kt));
-}
-resample_fn resample_kernel_emit(int kt, int minus, int gw) {
-    return gw == kGroupW ? resample_kernel_emit_w<kGroupW>(kt, minus) : resample_kernel_emit_w<kGroupWAlt>(kt, minus);
-}
-
-// minus: 0 no own-cluster tables (stick-breaking), 1 in LDS, 2 in global memory
-template <int GW>
-resample_fn resample_kernel_w(int kt, int minus, bool bits) {
-    if (bits)
-        return minus == 0 ? resample_kernel_m<0, true, GW>(kt)
-                          : (minus == 1 ? resample_kernel_m<1, true, GW>(kt) : resample_kernel_m<2, true, GW>(kt));
-    return minus == 0 ? resample_kernel_m<0, false, GW>(kt)
-                      : (minus == 1 ? resample_kernel_m<1, false, GW>(kt) : resample_kernel_m<2, false, GW>(kt));
-}
-resample_fn resample_kernel(int kt, int minus, bool bits, int gw) {
-    return gw == kGroupW ? resample_kernel_w<kGroupW>(kt, minus, bits) : resample_kernel_w<kGroupWAlt>(kt, minus, bits);
-}
-// SELF: 256-thread workgroups that build their own table image (finite sampler, small shapes: kernels.hip.h)
-resample_fn resample_kernel_self(int kt) {
-    switch (kt) {
-        case 4: return k_resample<4, 256, 1, 16, true, 1, false, kGroupW, true>;
-        case 8: return k_resample<8, 256, 1, 16, true, 1, false, kGroupW, true>;
-        case 12: return k_resample<12, 256, 1, 16, true, 1, false, kGroupW, true>;
-    }
-    return nullptr;
-}
-resample_fn resample_kernel_small_of(int kt, int minus, bool bits) {
-    if (bits) return minus == 0 ? resample_kernel_small<0, true>(kt) : resample_kernel_small<1, true>(kt);
-    return minus == 0 ? resample_kernel_small<0, false>(kt) : resample_kernel_small<1, false>(kt);
-}
-
 
 // The predictive kernel (k_predict) by accumulator count and group width: one workgroup size, one lane per row.
 typedef void (*predict_fn)(ChainParams, PredictArgs);
-template <int GW>
-predict_fn predict_kernel_w(int kt) {
-    switch (kt) {
-        case 4: return k_predict<4, kPredictThreads, GW>;
-        case 8: return k_predict<8, kPredictThreads, GW>;
-        case 12: return k_predict<12, kPredictThreads, GW>;
-        case 16: return k_predict<16, kPredictThreads, GW>;
-        case 20: return k_predict<20, kPredictThreads, GW>;
-        case 24: return k_predict<24, kPredictThreads, GW>;
-        case 28: return k_predict<28, kPredictThreads, GW>;
-        case 32: return k_predict<32, kPredictThreads, GW>;
-        case 40: return k_predict<40, kPredictThreads, GW>;
-        case 48: return k_predict<48, kPredictThreads, GW>;
-        case 52: return k_predict<52, kPredictThreads, GW>;
-        case 56: return k_predict<56, kPredictThreads, GW>;
-        case 64: return k_predict<64, kPredictThreads, GW>;
-        default: return nullptr;
-    }
+predict_fn lookup_predict(int kt, int gw) {
+    predict_fn fn = nullptr;
+    lift([&](auto KT, auto GW) { fn = k_predict<KT, kPredictThreads, GW>; }, kKT, kt, IntList<kGroupW, kGroupWAlt>{}, gw);
+    return fn;
 }
-predict_fn predict_kernel(int kt, int gw) {
-    return gw == kGroupW ? predict_kernel_w<kGroupW>(kt) : predict_kernel_w<kGroupWAlt>(kt);
+
+constexpr size_t kLdsMax = 163840;  // gfx950: 160 KiB per workgroup
+// The one place a kernel is set up for launching with `lds` bytes of dynamic LDS: the attribute that allows
+// them, and how many of its workgroups of nt threads the runtime then fits on a CU.
+template <class Fn>
+hipError_t kernel_fits(Fn fn, int nt, size_t lds, int* blocks_per_cu) {
+    *blocks_per_cu = 0;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void*>(fn), nt, lds);
+    return e;
 }
 
 }  // namespace
@@ -529,12 +457,10 @@ struct bmm_chain {
     bool dedicated_queue = false;  // the stream has a hardware queue of its own (chains sharing a device)
     int stream_kind = 0;           // what the stream pool takes back: 1 an ordinary non-blocking stream, 2 one with its own queue, 0 neither
     bool shares_device = false;    // another chain runs beside this one on the device (bmm_chain_share_data)
-    bool self_tables = false;      // the resample workgroups build their own table image: no k_count_tables per batch
     size_t lds_bytes_base = 0;     // lds_bytes without the SELF kernels' scratch
     int64_t batch = 1;
     double alpha0 = 1.0;
-    int NT = 0, grid_max = 0, minus_in_lds = 1;
-    int OT = 0;  // observations per tile (= NT, or NT / 2 for the two-lanes-per-observation kernels)
+    int grid_max = 0, minus_in_lds = 1;
     bool sharded = false, shard_open = false;  // one chain over several ranks (explicit-parameter samplers)
     bool generic = false;         // shape beyond the resident kernel: tables from global memory
     double* dScratch = nullptr;   // generic path: per-thread score columns
@@ -545,9 +471,12 @@ struct bmm_chain {
     double* probs_dst = nullptr;
     int64_t scratch_stride = 0;
     size_t lds_bytes = 0;
-    resample_fn fn = nullptr;
-    resample_fn fn_emit = nullptr;  // weight-emitting twin (bit planes), its workgroup size and grid limit
-    int NT_emit = 0, grid_max_emit = 0;
+    // what the chain's launches run (pick_kernel; on the generic path `form` carries the key of k_resample_generic
+    // and fn stays null), and the weight-emitting twin of a bit-plane chain: its form from the start, fn_emit and
+    // its grid limit once the first hand-off has set it up (probs_alloc)
+    KernelForm form, form_emit{};
+    resample_fn fn = nullptr, fn_emit = nullptr;
+    int grid_max_emit = 0;
 
     const int32_t* dX = nullptr;
     int32_t* dX_owned = nullptr;
@@ -661,21 +590,87 @@ int64_t default_batch(int sampler, int64_t N) {
 
 TableLayout layout_of(const bmm_chain* c) { return layout_of(c->p, !explicit_params(c->p.mode)); }
 
-constexpr size_t kLdsMax = 163840;  // gfx950: 160 KiB per workgroup
-size_t hist_bytes_of(int K, int P) { return ((size_t)K * P + K + 4) * sizeof(int32_t); }  // histogram + chunk counter
+// The test variant's switches (-DBMM_DEBUG_HOOKS: environment variables, read through dbg_env, so the product
+// library has none of them set).  These steer the shape and the kernel choice and are read when one of these is
+// made, once per choice; the others are read where they act: BMM_DEBUG_STREAM (chain_stream_create),
+// BMM_DEBUG_FAKE_DEVICES (fake_devices), BMM_DEBUG_BADLABEL and BMM_DEBUG_STRAGGLER (launch_resample).
+int dbg_env_int(const char* name, int unset) { const char* v = dbg_env(name); return v ? (atoi(v) > 0 ? atoi(v) : 0) : unset; }
+struct DebugSwitches {
+    bool generic = dbg_env("BMM_DEBUG_GENERIC");        // every shape on the generic path
+    bool int32_layout = dbg_env("BMM_X_LAYOUT_INT32");  // chains start on the int32 layout (the *_run calls have no layout argument)
+    // n >= 1: the kernel choice sees n compute units -- the grid limits, the short-launch and step-down rules -- so that
+    // test-sized batches reach the default-sized kernels and give a wave several chunks (tests/test_gpu_chunks.py)
+    int cus = dbg_env_int("BMM_DEBUG_CUS", 0);
+    int threads = dbg_env_int("BMM_DEBUG_THREADS", -1); // the one-lane kernel at that many threads where it exists (-1: unset)
+    bool split = dbg_env("BMM_DEBUG_SPLIT");            // every launch counts as short (two lanes from 16 accumulators)
+    bool nosplit = dbg_env("BMM_DEBUG_NOSPLIT");        // never two lanes per observation
+    bool small = dbg_env("BMM_DEBUG_SMALL");            // the 256-thread form whatever the size of the tables
+    bool noself = dbg_env("BMM_DEBUG_NOSELF");          // no table-building workgroups
+};
+
+// What follows from (sampler, N, P, K, batch) alone -- no device state enters.
+struct ChainShape {
+    ChainParams p{};            // mode, N, P, K and the geometry: W, G, Gm, Kc, KT (priors and seed are the caller's)
+    int64_t batch = 1;
+    bool generic = false;       // shape beyond the resident kernel
+    int minus_in_lds = 1;
+    size_t lds_bytes_base = 0;  // resident: what a workgroup keeps in LDS (table image + histogram)
+};
+ChainParams geometry(int sampler, int P, int K, int kt, int W) {
+    ChainParams q{};
+    q.mode = sampler; q.P = P; q.K = K; q.KT = kt; q.W = W;
+    q.G = (P + W - 1) / W; q.Gm = (P + kGroupWm - 1) / kGroupWm;
+    q.Kc = sampler == BMM_SAMPLER_DP ? K + 1 : K;
+    return q;
+}
+// LDS of a resident workgroup: the table image (with the own-cluster tables, or its head only), the histogram
+// and the chunk counter
+size_t image_bytes(const ChainParams& q, bool own_tables) {
+    const TableLayout l = layout_of(q, own_tables && !explicit_params(q.mode));
+    return (size_t)(own_tables ? l.doubles() : l.head()) * sizeof(double) + ((size_t)q.K * q.P + q.K + 4) * sizeof(int32_t);
+}
 
 // The spec's rule for the group width of a shape (bmm_spec.h; the oracle restates it): groups of kGroupW
 // features when the whole table image of the shape and the histogram fit in LDS that way, kGroupWAlt
 // otherwise.  A pure function of (sampler, K, P).
 int group_width_rule(int sampler, int K, int P) {
-    const int cats = sampler == BMM_SAMPLER_DP ? K + 1 : K;
-    const int kt = pick_kt(cats);
+    const int kt = pick_kt(sampler == BMM_SAMPLER_DP ? K + 1 : K);
     if (kt < 0 || P > kMaxP) return kGroupWAlt;
-    ChainParams q{};
-    q.mode = sampler; q.P = P; q.K = K; q.KT = kt; q.W = kGroupW;
-    q.G = (P + kGroupW - 1) / kGroupW; q.Gm = (P + kGroupWm - 1) / kGroupWm;
-    const size_t bytes = (size_t)layout_of(q, !explicit_params(sampler)).doubles() * sizeof(double) + hist_bytes_of(K, P);
-    return bytes <= kLdsMax ? kGroupW : kGroupWAlt;
+    return image_bytes(geometry(sampler, P, K, kt, kGroupW), true) <= kLdsMax ? kGroupW : kGroupWAlt;
+}
+
+// threads of the generic path (k_resample_generic, k_predict_generic): a scratch column of Kc scores each
+int64_t generic_threads(int Kc) {
+    int64_t threads = (int64_t)256 * 1024;
+    const int64_t cap = ((int64_t)256 << 20) / ((int64_t)Kc * 8);  // <= 256 MiB of scratch
+    if (threads > cap) threads = cap / 256 * 256;
+    return threads < 256 ? 256 : threads;
+}
+
+ChainShape chain_shape(int sampler, int64_t N, int P, int K, int64_t batch, const DebugSwitches& d) {
+    ChainShape s;
+    const int kt = pick_kt(sampler == BMM_SAMPLER_DP ? K + 1 : K);
+    ChainParams& p = s.p;
+    p = geometry(sampler, P, K, kt, group_width_rule(sampler, K, P));
+    p.N = N; p.Ntot = N; p.obs0 = 0;
+    s.batch = batch <= 0 ? default_batch(sampler, N) : (batch > N ? N : batch);
+    if (explicit_params(sampler)) s.batch = N;
+    s.generic = p.KT < 0 || P > kMaxP || d.generic;
+    if (!s.generic) {
+        s.lds_bytes_base = image_bytes(p, true);
+        if (s.lds_bytes_base > kLdsMax && !explicit_params(sampler)) {  // second tier: own-cluster tables stay in L2
+            s.minus_in_lds = 0;
+            s.lds_bytes_base = image_bytes(p, false);
+        }
+        if (s.lds_bytes_base > kLdsMax) s.generic = true;  // third tier: nothing resident
+    }
+    if (s.generic) {
+        // any shape: tables gathered from global memory, scores in a scratch column per thread
+        p.KT = (p.Kc + 3) / 4 * 4;
+        s.minus_in_lds = 0;
+        s.lds_bytes_base = 0;
+    }
+    return s;
 }
 
 int32_t* label_row(bmm_chain* c, int j) {
@@ -880,10 +875,11 @@ int launch_resample(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t l
     const bool use_generic = c->generic || (emit && !c->fn_emit);  // the int32 layout has no emitting twin
     // a kernel that builds its own tables reads the pending deltas and flushes into the other (empty) set, which
     // is the pending one from then on (self_fold_prev, kernels.hip.h)
-    const bool self_launch = c->self_tables && !emit && !use_generic;
+    const bool self_launch = c->form.self && !emit && !use_generic;
     if (self_launch) { a.dNk_prev = c->dDNk; a.dS_prev = c->dDS; a.dNk = c->dDNkAlt; a.dS = c->dDSAlt; }
-    const int OT = emit ? c->NT_emit : c->OT, gmax = emit ? c->grid_max_emit : c->grid_max;
-    const int64_t ntiles = use_generic ? 1 : (hi - lo + OT - 1) / OT;
+    const KernelForm& form = emit ? c->form_emit : c->form;
+    const int gmax = emit ? c->grid_max_emit : c->grid_max;
+    const int64_t ntiles = use_generic ? 1 : (hi - lo + tile_of(form) - 1) / tile_of(form);
     int grid = (int)(ntiles < gmax ? ntiles : gmax);
     if (use_generic) {
         const int64_t nt256 = (hi - lo + 255) / 256;
@@ -912,7 +908,7 @@ int launch_resample(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t l
                                 c->scratch_stride);
     } else {
         const resample_fn fn = emit ? c->fn_emit : c->fn;
-        const int nt = emit ? c->NT_emit : c->NT;
+        const int nt = form.nt;
         const size_t lds = emit ? c->lds_bytes_base : c->lds_bytes;  // the SELF kernels carry scratch behind the image
         if (e0) hipExtLaunchKernelGGL(fn, dim3(grid), dim3(nt), (uint32_t)lds, c->stream, e0, e1, 0, c->p, a);
         else hipLaunchKernelGGL(fn, dim3(grid), dim3(nt), lds, c->stream, c->p, a);
@@ -932,26 +928,19 @@ int launch_resample(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t l
 int probs_alloc(bmm_chain* c, bool with_matrix) {
     const size_t n = (size_t)c->p.N;
     if (c->bits && !c->generic && !c->fn_emit) {
-        const int minus = explicit_params(c->p.mode) ? 0 : (c->minus_in_lds ? 1 : 2);
-        c->fn_emit = resample_kernel_emit(c->p.KT, minus, c->p.W);
-        c->NT_emit = threads_for(c->p.KT, true);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(c->fn_emit), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes_base);
+        const resample_fn fn = lookup(c->form_emit);
         int pe = 0;
-        if (e == hipSuccess)
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pe, reinterpret_cast<const void*>(c->fn_emit), c->NT_emit, c->lds_bytes_base);
-        if (e != hipSuccess) { c->fn_emit = nullptr; return set_err(BMM_E_HIP, "kernel set-up failed: %s", hipGetErrorString(e)); }
+        const hipError_t e = kernel_fits(fn, c->form_emit.nt, c->lds_bytes_base, &pe);
+        if (e != hipSuccess) return set_err(BMM_E_HIP, "kernel set-up failed: %s", hipGetErrorString(e));
+        c->fn_emit = fn;
         c->grid_max_emit = (pe < 1 ? 1 : pe) * c->num_cus;
     }
     if (!c->dWts) HIP_TRY(hipMalloc(&c->dWts, n * c->p.Kc * sizeof(double)));
     if (!c->dWtot) HIP_TRY(hipMalloc(&c->dWtot, n * sizeof(double)));
     if (with_matrix && !c->dProbs) HIP_TRY(hipMalloc(&c->dProbs, n * c->p.K * sizeof(double)));
     if (!c->fn_emit && !c->dScratch) {  // int32 layout: the hand-off sweeps run on the generic kernel
-        int64_t threads = (int64_t)256 * 1024;
-        const int64_t cap = ((int64_t)256 << 20) / ((int64_t)c->p.Kc * 8);
-        if (threads > cap) threads = cap / 256 * 256;
-        if (threads < 256) threads = 256;
-        c->scratch_stride = threads;
-        HIP_TRY(hipMalloc(&c->dScratch, (size_t)threads * c->p.Kc * sizeof(double)));
+        c->scratch_stride = generic_threads(c->p.Kc);
+        HIP_TRY(hipMalloc(&c->dScratch, (size_t)c->scratch_stride * c->p.Kc * sizeof(double)));
     }
     return BMM_OK;
 }
@@ -1045,7 +1034,7 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
         const int64_t hi = lo + len > p.N ? p.N : lo + len;
         // (SELF kernels build their own image from Nk, S and the previous launch's deltas; a sweep that hands its
         // probabilities to the host runs the emitting twin, which reads the image k_count_tables writes)
-        int rc = c->self_tables && !c->probs_dst ? BMM_OK : launch_count_tables(c);
+        int rc = c->form.self && !c->probs_dst ? BMM_OK : launch_count_tables(c);
         if (rc) return rc;
         rc = launch_resample(c, zin, zout, lo, hi, (uint32_t)j);
         if (rc) return rc;
@@ -1057,17 +1046,22 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
     return sweep_end_predict(c, j);
 }
 
-// The resident kernel for this chain's shape, workgroup size and X layout (c->bits).
-int pick_kernel(bmm_chain* c) {
-    const ChainParams& p = c->p;
-    const size_t lds_max = kLdsMax;
-    const int minus = explicit_params(p.mode) ? 0 : (c->minus_in_lds ? 1 : 2);
-    c->NT = threads_for(p.KT, c->bits);
-    c->lds_bytes = c->lds_bytes_base;  // (a previous choice may have been a SELF kernel, which carries scratch)
-    c->self_tables = false;
+// The resident kernel for a shape, batch and X layout: the forms to try, in order, each with its dynamic LDS.
+// The first is always there and is what runs unless a later one is taken; a later one is tried only when the one
+// before it was taken and is taken when the runtime fits at least one of its workgroups on a CU (pick_kernel).
+// `minus` is the own-cluster tier of KernelForm.  A pure function: no device and no chain enter.
+struct KernelPlan {
+    int n = 0;
+    KernelForm form[3];
+    size_t lds[3] = {0, 0, 0};
+    bool named_size = false;  // form[0] has its workgroup size from BMM_DEBUG_THREADS (stage_width)
+};
+KernelPlan plan_kernel(const ChainParams& p, bool bits, int minus, int64_t batch, int num_cus, bool shares_device,
+                       size_t lds_bytes_base, const DebugSwitches& d) {
     const bool alt = p.W != kGroupW;  // the narrower groups: default-sized kernels only
-    c->fn = resample_kernel(p.KT, minus, c->bits, p.W);
-    int split = 1;
+    KernelForm f{p.KT, threads_for(p.KT, bits), minus, bits, 1, false, p.W, false};
+    KernelPlan plan;
+    auto offer = [&plan](const KernelForm& g, size_t lds) { plan.form[plan.n] = g; plan.lds[plan.n++] = lds; };
     // Two lanes per observation: always above 32 accumulators (registers), and from 16 up when a launch is so
     // short that the default form would give a wave at most a chunk or two -- then a launch is all latency
     // (the north-star shape: 15 us per launch of which 4 are arithmetic, VALU busy 27 %), and the two-lane
@@ -1078,62 +1072,70 @@ int pick_kernel(bmm_chain* c) {
     // shape by batch: 125 000 two-lane +11 %, 162 500 +11 %, 200 000 -2.5 %, 250 000 -8 % (profiles/r03/ab_smallsplit.log).
     // (not for chains that share their device: several chains' launches fill the chip between them, and then
     // the one-lane form's lower total work wins -- four north-star chains: 14.8 k against 12.1 k sweeps/s)
-    const bool short_launch = BMM_SMALL_SPLIT && !c->shares_device && p.KT >= 16 && !alt && (c->batch < (int64_t)c->num_cus * kThreadsMid || dbg_env("BMM_DEBUG_SPLIT"));
-    if (c->bits && (p.KT > 32 || short_launch) && minus != 2 && !dbg_env("BMM_DEBUG_NOSPLIT")) {
-        if (resample_fn f = minus ? resample_kernel_split<1>(p.KT, p.W) : resample_kernel_split<0>(p.KT, p.W)) {
-            c->fn = f;
-            c->NT = kThreadsSplit;
-            split = 2;
-        }
+    const bool short_launch = BMM_SMALL_SPLIT && !shares_device && p.KT >= 16 && !alt && (batch < (int64_t)num_cus * kThreadsMid || d.split);
+    if (bits && (p.KT > 32 || short_launch) && minus != 2 && !d.nosplit) {
+        const KernelForm g = resized(f, kThreadsSplit, 2);
+        if (instantiated(g, false)) f = g;
     }
-    if (const char* dbg = alt ? nullptr : dbg_env("BMM_DEBUG_THREADS")) {
-        const int nt = atoi(dbg);
-        if (resample_fn f = resample_kernel_at(p.KT, nt, minus, c->bits)) { c->fn = f; c->NT = nt; }
-    } else if (c->bits && split == 1 && !alt) {
+    if (d.threads >= 0 && !alt) {
+        // the experiment knob: honoured up to 20 accumulators, and up to 32 on bit planes below 1024 threads (the
+        // other kernels of a chosen size are in the library but nothing runs them)
+        const KernelForm g = resized(f, d.threads);
+        if (instantiated(g, true) && (p.KT <= 20 || (bits && g.nt != 1024))) { f = g; plan.named_size = true; }
+    } else if (bits && f.lanes == 1 && !alt) {
         // a batch that cannot give every CU a workgroup of the default size gets smaller ones -- as long as they
         // still hold the whole batch in one round (250 000 observations: 245 workgroups of 1024 threads, one chunk
         // per wave, beat 256 of 768 where a quarter of the waves takes a second chunk: north-star kernel -6 %)
         for (int nt : {768, 512}) {
-            if ((c->batch + c->NT - 1) / c->NT >= c->num_cus || nt >= c->NT || (c->batch + nt - 1) / nt > c->num_cus) continue;
-            if (resample_fn f = resample_kernel_at(p.KT, nt, minus, true)) { c->fn = f; c->NT = nt; }
+            if ((batch + f.nt - 1) / f.nt >= num_cus || nt >= f.nt || (batch + nt - 1) / nt > num_cus) continue;
+            if (instantiated(resized(f, nt), false)) f = resized(f, nt);
         }
     }
-    hipError_t e = hipSetDevice(c->device);
-    c->fn_emit = nullptr;  // the weight-emitting twin is set up when a hand-off first asks for it (probs_alloc)
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(c->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-    int per_cu = 0;
-    if (e == hipSuccess)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(c->fn), c->NT, c->lds_bytes);
-    if (e != hipSuccess) return set_err(BMM_E_HIP, "kernel set-up failed: %s", hipGetErrorString(e));
-    if (per_cu < 1) per_cu = 1;
-    c->grid_max = per_cu * c->num_cus;
+    offer(f, lds_bytes_base);
     // a batch that cannot give every CU a workgroup runs on 256-thread workgroups instead, when the
     // tables are small enough for several of them per CU (otherwise fewer waves per CU just hurts)
-    c->OT = c->NT / split;
-    const int64_t tiles = (c->batch + c->NT - 1) / c->NT;
-    if (split == 1 && !alt && tiles < c->num_cus && c->NT > 256 && (c->lds_bytes * 4 <= lds_max || dbg_env("BMM_DEBUG_SMALL")) &&
-        minus != 2 && !dbg_env("BMM_DEBUG_THREADS")) {
-        resample_fn f = resample_kernel_small_of(p.KT, minus, c->bits);
-        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-        int pc2 = 0;
-        if (e2 == hipSuccess) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc2, reinterpret_cast<const void*>(f), 256, c->lds_bytes);
-        if (e2 == hipSuccess && pc2 >= 1) { c->fn = f; c->NT = 256; c->OT = 256; c->grid_max = pc2 * c->num_cus; }
-    }
+    const int64_t tiles = (batch + f.nt - 1) / f.nt;
+    if (!(f.lanes == 1 && !alt && tiles < num_cus && f.nt > 256 && (lds_bytes_base * 4 <= kLdsMax || d.small) && minus != 2 && d.threads < 0))
+        return plan;
+    f.nt = 256;
+    offer(f, lds_bytes_base);
     // ... and such workgroups build the table image themselves when that is at most two logs per thread: the
     // shape is bound by launches then, and this drops k_count_tables from every batch (BASELINE config 2)
-    if (BMM_SELF_TABLES && c->NT == 256 && split == 1 && c->bits && !alt && minus == 1 && !c->shares_device &&
-        self_tables_fit(p.mode, p.K, p.P, 256) && !dbg_env("BMM_DEBUG_NOSELF")) {
-        if (resample_fn f = resample_kernel_self(p.KT)) {
-            const size_t lds = (c->lds_bytes_base + 7) / 8 * 8 + self_scratch_doubles(p.K, p.KT, p.P) * sizeof(double);
-            hipError_t e3 = lds <= lds_max ? hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                                           : hipErrorInvalidValue;
-            int pc3 = 0;
-            if (e3 == hipSuccess) e3 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc3, reinterpret_cast<const void*>(f), 256, lds);
-            if (e3 == hipSuccess && pc3 >= 1) { c->fn = f; c->lds_bytes = lds; c->grid_max = pc3 * c->num_cus; c->self_tables = true; }
-            else (void)hipGetLastError();
+    f.self = true;
+    const size_t lds = (lds_bytes_base + 7) / 8 * 8 + self_scratch_doubles(p.K, p.KT, p.P) * sizeof(double);  // scratch behind the image
+    if (BMM_SELF_TABLES && bits && minus == 1 && !shares_device && self_tables_fit(p.mode, p.K, p.P, 256) && !d.noself &&
+        instantiated(f, false) && lds <= kLdsMax)
+        offer(f, lds);
+    return plan;
+}
+
+int tier_of(const bmm_chain* c) { return explicit_params(c->p.mode) ? 0 : (c->minus_in_lds ? 1 : 2); }
+
+// The chain's resident kernel, set up for launching: the last form of the plan that the runtime takes.
+int pick_kernel(bmm_chain* c) {
+    const KernelPlan plan = plan_kernel(c->p, c->bits, tier_of(c), c->batch, c->num_cus, c->shares_device, c->lds_bytes_base,
+                                        DebugSwitches{});
+    hipError_t e = hipSetDevice(c->device);
+    for (int i = 0; i < plan.n; ++i) {
+        const KernelForm& f = plan.form[i];
+        const resample_fn fn = lookup(f, plan.named_size);
+        int per_cu = 0;
+        if (e == hipSuccess) e = kernel_fits(fn, f.nt, plan.lds[i], &per_cu);
+        if (i == 0) {
+            if (e != hipSuccess) return set_err(BMM_E_HIP, "kernel set-up failed: %s", hipGetErrorString(e));
+            if (per_cu < 1) per_cu = 1;
+        } else if (e != hipSuccess || per_cu < 1) {
+            (void)hipGetLastError();
+            break;
         }
+        c->form = f;
+        c->fn = fn;
+        c->lds_bytes = plan.lds[i];
+        c->grid_max = per_cu * c->num_cus;
     }
+    // the weight-emitting twin is set up when a hand-off first asks for it (probs_alloc)
+    c->form_emit = c->bits ? emit_twin(c->form) : KernelForm{};
+    c->fn_emit = nullptr;
     return BMM_OK;
 }
 
@@ -1261,63 +1263,32 @@ int bmm_chain_create(bmm_chain** out, int sampler, int64_t N, int P, int K, doub
 
     bmm_chain* c = new (std::nothrow) bmm_chain();
     if (!c) return set_err(BMM_E_ARG, "out of host memory");
+    const DebugSwitches dbg;
+    const ChainShape shape = chain_shape(sampler, N, P, K, batch, dbg);
     ChainParams& p = c->p;
-    p.mode = sampler; p.N = N; p.Ntot = N; p.obs0 = 0; p.P = P; p.K = K;
-    p.W = group_width_rule(sampler, K, P);
-    p.G = (P + p.W - 1) / p.W;
-    p.Gm = (P + kGroupWm - 1) / kGroupWm;
-    p.Kc = sampler == BMM_SAMPLER_DP ? K + 1 : K;
-    p.KT = pick_kt(p.Kc);
+    p = shape.p;
     p.beta = beta; p.gamma = gamma; p.a = a; p.b = b; p.seed = seed;
     p.sample_alpha = alpha == 0.0;  // collapsed_gibbs.cpp:50-54
     c->alpha0 = p.sample_alpha ? 1.0 : alpha;
     c->device = device;
     c->slot = slot;
-    c->batch = batch <= 0 ? default_batch(sampler, N) : (batch > N ? N : batch);
-    if (explicit_params(sampler)) c->batch = N;
+    c->batch = shape.batch;
     if (p.Kc > kMaxCatsAny) {
         delete c;
         return set_err(BMM_E_UNSUPPORTED, "%d categories exceed the %d this build supports", p.Kc, kMaxCatsAny);
     }
     const int cus = device_cus(device);
     if (cus <= 0) { delete c; return set_err(BMM_E_HIP, "hipGetDeviceProperties failed"); }
-    const size_t lds_max = kLdsMax;
-    const size_t hist_bytes = hist_bytes_of(K, P);
-    c->bits = dbg_env("BMM_X_LAYOUT_INT32") == nullptr;
-    c->generic = p.KT < 0 || P > kMaxP || dbg_env("BMM_DEBUG_GENERIC") != nullptr;
-    if (!c->generic) {
-        c->NT = threads_for(p.KT, false);
-        c->OT = c->NT;
-        c->lds_bytes = (size_t)layout_of(c).doubles() * sizeof(double) + hist_bytes;
-        if (c->lds_bytes > lds_max && !explicit_params(p.mode)) {  // second tier: own-cluster tables stay in L2
-            c->minus_in_lds = 0;
-            c->lds_bytes = (size_t)layout_of(c).head() * sizeof(double) + hist_bytes;
-        }
-        if (c->lds_bytes > lds_max) c->generic = true;  // third tier: nothing resident
-        c->lds_bytes_base = c->lds_bytes;
-    }
+    c->bits = !dbg.int32_layout;
+    c->generic = shape.generic;
+    c->minus_in_lds = shape.minus_in_lds;
+    c->lds_bytes_base = c->lds_bytes = shape.lds_bytes_base;
     if (c->generic) {
-        // any shape: tables gathered from global memory, scores in a scratch column per thread
-        p.KT = (p.Kc + 3) / 4 * 4;
-        c->NT = 256;
-        c->OT = 256;
-        c->lds_bytes = 0;
-        c->minus_in_lds = 0;
-        int64_t threads = (int64_t)256 * 1024;
-        const int64_t cap = ((int64_t)256 << 20) / ((int64_t)p.Kc * 8);  // <= 256 MiB of scratch
-        if (threads > cap) threads = cap / 256 * 256;
-        if (threads < 256) threads = 256;
-        c->scratch_stride = threads;
-        c->grid_max = (int)(threads / 256);
+        c->form = KernelForm{p.KT, 256, tier_of(c), c->bits, 1, false, p.W, false};
+        c->scratch_stride = generic_threads(p.Kc);
+        c->grid_max = (int)(c->scratch_stride / 256);
     } else {
-        c->num_cus = cus;
-        // test variant (BMM_DEBUG_CUS=n, n >= 1): the kernel choice sees n compute units -- the grid limits, the
-        // short-launch and step-down rules -- so that test-sized batches reach the default-sized kernels and give
-        // a wave several chunks (tests/test_gpu_chunks.py).  The device itself is not asked again.
-        if (const char* v = dbg_env("BMM_DEBUG_CUS")) {
-            const int n = atoi(v);
-            if (n >= 1) c->num_cus = n;
-        }
+        c->num_cus = dbg.cus >= 1 ? dbg.cus : cus;
         rc = pick_kernel(c);
         if (rc) { delete c; return rc; }
     }
@@ -1373,7 +1344,7 @@ int bmm_chain_set_x_layout(bmm_chain* c, int layout) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (layout != BMM_X_BITPLANES && layout != BMM_X_INT32) return set_err(BMM_E_ARG, "unknown X layout %d", layout);
     if (c->have_data || c->started) return set_err(BMM_E_STATE, "the X layout is chosen before the data are set");
-    c->bits = layout == BMM_X_BITPLANES;
+    c->bits = c->form.bits = layout == BMM_X_BITPLANES;
     if (c->generic) return BMM_OK;  // one kernel for both layouts there
     return pick_kernel(c);
 }
@@ -1764,15 +1735,15 @@ int64_t bmm_chain_batch(const bmm_chain* c) { return c ? c->batch : -1; }
 int bmm_chain_kernel_shape(const bmm_chain* c, int* lds_bytes, int* threads, int* grid_max) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (lds_bytes) *lds_bytes = (int)c->lds_bytes;
-    if (threads) *threads = c->NT;
+    if (threads) *threads = c->form.nt;
     if (grid_max) *grid_max = c->grid_max;
     return BMM_OK;
 }
 
 int bmm_chain_kernel_form(const bmm_chain* c, int* lanes_per_observation, int* builds_own_tables) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
-    if (lanes_per_observation) *lanes_per_observation = c->generic || c->OT <= 0 ? 1 : c->NT / c->OT;
-    if (builds_own_tables) *builds_own_tables = c->self_tables ? 1 : 0;
+    if (lanes_per_observation) *lanes_per_observation = c->form.lanes;
+    if (builds_own_tables) *builds_own_tables = c->form.self ? 1 : 0;
     return BMM_OK;
 }
 
@@ -1794,13 +1765,12 @@ static int pred_reset(bmm_chain* c) {
 // the predictive kernel of the chain's shape, set up on first use
 static int pred_setup(bmm_chain* c) {
     if (c->generic || c->pfn) return BMM_OK;
-    predict_fn f = predict_kernel(c->p.KT, c->p.W);
+    predict_fn f = lookup_predict(c->p.KT, c->p.W);
     if (!f) return set_err(BMM_E_STATE, "no predictive kernel for %d accumulators", c->p.KT);
     const size_t lds = (size_t)layout_of(c->p, false).head() * sizeof(double);
     if (lds > kLdsMax) return set_err(BMM_E_STATE, "the predictive table image (%zu bytes) does not fit in LDS", lds);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     int per_cu = 0;
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(f), kPredictThreads, lds);
+    const hipError_t e = kernel_fits(f, kPredictThreads, lds, &per_cu);
     if (e != hipSuccess) return set_err(BMM_E_HIP, "kernel set-up failed: %s", hipGetErrorString(e));
     c->pfn = f;
     c->pred_lds = lds;
@@ -2822,21 +2792,37 @@ extern "C" int bmm_dbg_host_labels(const void* src, int narrow, int32_t* dst, in
 }
 // Test variant only: which k_resample instantiation the chain's launches run -- accumulators, workgroup size, lanes
 // per observation, own-cluster tier (0 none, 1 LDS, 2 global memory), X layout (1 bit planes), group width, whether
-// it builds its own tables, the weight-emitting twin's workgroup size (as set up by the first hand-off; before that
-// the size it will get, 0 where there is none and the hand-off runs the generic kernel), whether the chain is on the generic kernel altogether, and the emitting twin's grid limit (0 until a
-// hand-off has set the twin up) (tests/test_gpu_chunks.py)
+// it builds its own tables, the weight-emitting twin's workgroup size (0 where there is none and the hand-off runs
+// the generic kernel), whether the chain is on the generic kernel altogether, and the emitting twin's grid limit
+// (0 until a hand-off has set the twin up) (tests/test_gpu_chunks.py)
+static void kernel_key(const KernelForm& f, const KernelForm& twin, bool generic, int grid_max_emit, int* key) {
+    const int k[10] = {f.kt, f.nt, f.lanes, f.minus, f.bits ? 1 : 0, f.gw, f.self ? 1 : 0, generic ? 0 : twin.nt, generic ? 1 : 0, grid_max_emit};
+    std::memcpy(key, k, sizeof k);
+}
 extern "C" int bmm_dbg_kernel_key(const bmm_chain* c, int* key) {
     if (!c || !key) return set_err(BMM_E_ARG, "null argument");
-    key[0] = c->p.KT;
-    key[1] = c->NT;
-    key[2] = c->generic || c->OT <= 0 ? 1 : c->NT / c->OT;
-    key[3] = explicit_params(c->p.mode) ? 0 : (c->minus_in_lds ? 1 : 2);
-    key[4] = c->bits ? 1 : 0;
-    key[5] = c->p.W;
-    key[6] = c->self_tables ? 1 : 0;
-    key[7] = c->fn_emit ? c->NT_emit : (c->bits && !c->generic ? threads_for(c->p.KT, true) : 0);
-    key[8] = c->generic ? 1 : 0;
-    key[9] = c->fn_emit ? c->grid_max_emit : 0;
+    kernel_key(c->form, c->form_emit, c->generic, c->fn_emit ? c->grid_max_emit : 0, key);
+    return BMM_OK;
+}
+// ... and the same key for a chain that is not created: what chain_shape and plan_kernel make of the arguments, of
+// num_cus compute units and of the switches a chain would read, every form the plan offers taken.  No device is
+// touched (tests/test_capi_cpu.py holds the measured rules this way; tests/test_gpu_chunks.py holds plan and chain
+// to each other).
+extern "C" int bmm_dbg_kernel_plan(int sampler, int64_t N, int P, int K, int64_t batch, int num_cus, int shares_device,
+                                   int int32_layout, int* key) {
+    if (!key || sampler < 0 || sampler > 3 || N < 1 || P < 1 || K < 1 || num_cus < 1) return set_err(BMM_E_ARG, "bad argument");
+    const DebugSwitches dbg;
+    const ChainShape s = chain_shape(sampler, N, P, K, batch, dbg);
+    const bool bits = !int32_layout && !dbg.int32_layout;
+    const int minus = explicit_params(sampler) ? 0 : (s.minus_in_lds ? 1 : 2);
+    if (s.generic) {
+        kernel_key(KernelForm{s.p.KT, 256, minus, bits, 1, false, s.p.W, false}, KernelForm{}, true, 0, key);
+        return BMM_OK;
+    }
+    const KernelPlan plan = plan_kernel(s.p, bits, minus, s.batch, dbg.cus >= 1 ? dbg.cus : num_cus, shares_device != 0,
+                                        s.lds_bytes_base, dbg);
+    const KernelForm& f = plan.form[plan.n - 1];
+    kernel_key(f, bits ? emit_twin(f) : KernelForm{}, false, 0, key);
     return BMM_OK;
 }
 #endif

@@ -208,3 +208,35 @@ def test_host_label_copies_widen_and_mark_unassigned(n, offset):
     assert lib.bmm_dbg_host_labels(src32.ctypes.data_as(ctypes.c_void_p), 0, dst.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(n), 2) == 0
     np.testing.assert_array_equal(dst, src32)
     assert (buf[:offset] == 12345).all() and (buf[offset + n:] == 12345).all()
+
+
+def test_kernel_forms_at_the_benchmark_shapes_without_a_device(monkeypatch):
+    """tests/test_gpu_layouts.py::test_kernel_forms_at_the_benchmark_shapes, through bmm_dbg_kernel_plan: the shape
+    arithmetic and the kernel choice are pure functions, so the measured rules of profiles/r03/ab_smallsplit.log and
+    ab_self_tables.log are held without a device too, at the CU count they were measured on (an MI355X: 256)"""
+    import ctypes
+    for name in [k for k in os.environ if k.startswith("BMM_DEBUG_") or k == "BMM_X_LAYOUT_INT32"]:
+        monkeypatch.delenv(name)
+    lib = _dbg_cdll()
+
+    def form(sampler, N, P, K, batch=0, cus=256, shares=0, int32=0):
+        key = (ctypes.c_int * 10)()
+        rc = lib.bmm_dbg_kernel_plan(_capi.SAMPLER_CODE[sampler], ctypes.c_int64(N), P, K, ctypes.c_int64(batch), cus,
+                                     shares, int32, key)
+        assert rc == 0 and key[8] == 0 and key[9] == 0
+        return batch or bm.default_batch(sampler, N), key[1], key[2], bool(key[6])
+    assert form("collapsed", 1_000_000, 50, 20) == (250_000, 1024, 1, False)
+    assert form("collapsed", 1_000_000, 50, 20, batch=125_000) == (125_000, 1024, 2, False)
+    assert form("collapsed", 1_000_000, 50, 20, batch=200_000)[2] == 1          # from 196 608 on: one lane
+    assert form("dp", 1_000_000, 50, 30) == (250_000, 768, 1, False)
+    assert form("dp", 1_000_000, 50, 30, batch=125_000)[2] == 2
+    assert form("collapsed", 100_000, 20, 3) == (25_000, 256, 1, True)
+    assert form("collapsed", 10_000_000, 100, 20)[:3] == (2_500_000, 1024, 1)
+    assert form("stickbreaking", 1_000_000, 50, 50)[1:3] == (1024, 2)           # 52 accumulators: always two lanes
+    # chains that share their device keep one lane per observation and the table kernel (plan_kernel)
+    assert form("collapsed", 1_000_000, 50, 20, batch=125_000, shares=1)[2] == 1
+    assert form("collapsed", 100_000, 20, 3, shares=1) == (25_000, 256, 1, False)
+    # a shape beyond the resident kernel reports the generic path
+    key = (ctypes.c_int * 10)()
+    assert lib.bmm_dbg_kernel_plan(0, ctypes.c_int64(300_000), 200, 5, ctypes.c_int64(0), 256, 0, 0, key) == 0
+    assert (key[1], key[7], key[8]) == (256, 0, 1)

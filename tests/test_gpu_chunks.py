@@ -4,10 +4,10 @@ against the oracle, bit for bit.
 
 Test-sized batches fill one round of the real chip, so the tests below make the kernel choice see fewer compute
 units (BMM_DEBUG_CUS, test variant): a batch of a few thousand observations then runs the default-sized kernels
-of pick_kernel's own rules with several chunks per wave.  Every case states which kernel it gets and how many
-chunks per wave that gives (kernel_shape), so that a later change to pick_kernel cannot quietly turn a looping case
+of plan_kernel's own rules with several chunks per wave.  Every case states which kernel it gets and how many
+chunks per wave that gives (kernel_shape), so that a later change to plan_kernel cannot quietly turn a looping case
 back into a one-round one, and test_the_cases_reach_every_selectable_kernel holds the set of k_resample
-instantiations the cases reach against the dispatch tables of chain.hip.  The last tests run the benchmark
+instantiations the cases reach against the kernel set of chain.hip (instantiated).  The last tests run the benchmark
 shapes on the product library at the real CU count."""
 import ctypes
 from collections import namedtuple
@@ -122,6 +122,16 @@ def kernel_key(ch):
     threads, generic, emitting twin's grid limit) of the chain's kernel: bmm_dbg_kernel_key, test variant"""
     k = (ctypes.c_int * 10)()
     _capi.check(_capi.lib().bmm_dbg_kernel_key(ch._h, k))
+    return tuple(k)
+
+
+def kernel_plan(case, num_cus, shares_device=False):
+    """the same key, slot 9 zero, as the shape arithmetic and the kernel choice give it for the case's arguments
+    without a chain or a device: bmm_dbg_kernel_plan, test variant"""
+    k = (ctypes.c_int * 10)()
+    _capi.check(_capi.lib().bmm_dbg_kernel_plan(_capi.SAMPLER_CODE[case.sampler], ctypes.c_int64(case.N), case.P, case.K,
+                                                ctypes.c_int64(case.batch), num_cus, int(shares_device),
+                                                int(case.layout == "int32"), k))
     return tuple(k)
 
 
@@ -297,17 +307,17 @@ def test_every_kernel_form_draws_the_oracle_chain(oracle, dbg_lib, case):
 
 
 # --------------------------------------------------------------------------- which kernels the cases reach
-# Every k_resample instantiation in the dispatch tables of chain.hip that pick_kernel (and the hand-off's probs_alloc)
-# can select, written out per table: {(own-cluster tier, group width): accumulator counts}.  Tier 1 = own-cluster
+# Every k_resample instantiation of chain.hip (the forms `instantiated` admits) that plan_kernel (and the hand-off's
+# probs_alloc) can select, written out per family: {(own-cluster tier, group width): accumulator counts}.  Tier 1 = own-cluster
 # tables in LDS, 2 = in global memory, 0 = none.  Left out, because no rule selects them:
-#   - tier 2 at group width 5 (resample_kernel_m, _emit_m): the width rule picks 5 only when the whole table image
+#   - tier 2 at group width 5 (default-sized kernels and emitting twins): the width rule picks 5 only when the whole table image
 #     fits in LDS, own-cluster tables included, so a width-5 shape never needs the second tier;
 #   - width 4 at 4-12 accumulators (any tier) and at 16-20 without own-cluster tables, and tier 2 below 24: those
 #     tables fit at P <= 128 (beyond that the generic kernel runs);
-#   - the two-lane forms of 16-32 accumulators at width 4 (null entries of resample_kernel_split_w) and in tier 2
+#   - the two-lane forms of 16-32 accumulators at width 4 (not instantiated) and in tier 2
 #     (the split form reads its own-cluster tables from LDS only);
-#   - resample_kernel_small<1, *> at 64 accumulators: the tables never fit four times into LDS;
-#   - resample_kernel_nt for the int32 layout (1024 / 768 / 512 threads): only BMM_DEBUG_THREADS reaches them, no
+#   - the 256-thread kernels with own-cluster tables at 64 accumulators: the tables never fit four times into LDS;
+#   - the kernels of a chosen size for the int32 layout (1024 / 768 / 512 threads): only BMM_DEBUG_THREADS reaches them, no
 #     rule; for bit planes at 1024 threads it is the default instantiation itself;
 #   - the stepped-down forms of 16-32 accumulators are reached only where the short-launch rule, which would run
 #     them two lanes per observation, is off (a chain that shares its device; BMM_DEBUG_NOSPLIT here).
@@ -315,25 +325,25 @@ KT_ALL = (4, 8, 12, 16, 20, 24, 28, 32, 40, 48, 52, 56, 64)
 KT_W4_OWN = (16, 20, 24, 28, 32, 40, 48, 52, 56, 64)
 KT_W4 = (24, 28, 32, 40, 48, 52, 56, 64)
 SELECTABLE = {
-    # resample_kernel_m<MINUS, BITS, GW>: one lane, default size, for both layouts (2 x 52)
+    # one lane, default size, for both layouts (2 x 52)
     "default": {(1, 5): KT_ALL, (0, 5): KT_ALL, (1, 4): KT_W4_OWN, (0, 4): KT_W4, (2, 4): KT_W4},
-    # resample_kernel_emit_m<MINUS, GW>: the emitting twins, bit planes only (52)
+    # the emitting twins, bit planes only (52)
     "emit": {(1, 5): KT_ALL, (0, 5): KT_ALL, (1, 4): KT_W4_OWN, (0, 4): KT_W4, (2, 4): KT_W4},
-    # resample_kernel_split_w<MINUS, GW>: 1024 threads, two lanes per observation (30)
+    # 1024 threads, two lanes per observation (30)
     "two-lane": {(1, 5): KT_ALL[3:], (0, 5): KT_ALL[3:], (1, 4): KT_ALL[8:], (0, 4): KT_ALL[8:]},
-    # resample_kernel_nt<768 / 512, MINUS, true>: the stepped-down workgroups, width 5 (26)
+    # 768 / 512 threads: the stepped-down workgroups, width 5 (26)
     "step-down-768": {(1, 5): KT_ALL[:5], (0, 5): KT_ALL[:5]},
     "step-down-512": {(1, 5): KT_ALL[:8], (0, 5): KT_ALL[:8]},
-    # resample_kernel_small<MINUS, BITS>: 256 threads, width 5, for both layouts (2 x 25)
+    # 256 threads, width 5, for both layouts (2 x 25)
     "256": {(1, 5): KT_ALL[:12], (0, 5): KT_ALL},
-    # resample_kernel_self: 256 threads that build their own tables (3)
+    # SELF: 256 threads that build their own tables (3)
     "self": {(1, 5): (4, 8, 12)},
 }
 SELECTABLE_COUNTS = {"default": 104, "emit": 52, "two-lane": 30, "step-down-768": 10, "step-down-512": 16, "256": 50, "self": 3}
 
 
 def _table_of(key):
-    """which dispatch table a (kind, accumulators, threads, lanes, tier, bits, width, own tables) key comes from"""
+    """which family of SELECTABLE a (kind, accumulators, threads, lanes, tier, bits, width, own tables) key comes from"""
     kind, kt, nt, lanes, _, bits, _, own = key
     if kind == "emit":
         return "emit"
@@ -373,6 +383,9 @@ def test_the_cases_reach_every_selectable_kernel(dbg_lib):
         with bm.Chain(case.sampler, case.N, case.P, case.K, batch=case.batch, seed=1, x_layout=case.layout) as ch:
             k = kernel_key(ch)
             assert k[8] == 0, case.id
+            # the plan and what the chain set up cannot drift apart (every case names its CU count, so the real
+            # device's does not enter)
+            assert kernel_plan(case, 256)[:9] == k[:9], (case.id, kernel_plan(case, 256), k)
             key = ("resample", k[0], k[1], k[2], k[3], k[4], k[5], k[6])
             got.setdefault(_table_of(key), set()).add(key)
             if case.probs:

@@ -129,7 +129,7 @@ def test_wide_category_counts_two_lanes_per_observation(oracle, dbg_lib, nosplit
 
 @pytest.mark.parametrize("nosplit", [False, True])
 def test_both_forms_of_16_to_32_accumulators_on_short_launches(oracle, dbg_lib, nosplit):
-    """Launches of at most 24 chunks per CU run 16-32 accumulators two lanes per observation (pick_kernel); the
+    """Launches of at most 24 chunks per CU run 16-32 accumulators two lanes per observation (plan_kernel); the
     one-lane form of the same kernels is what long launches (C5) run.  Test-sized inputs are all short launches,
     so the one-lane form is reached here through BMM_DEBUG_NOSPLIT: both must be the oracle's chain, bit for bit."""
     if nosplit:
@@ -224,7 +224,7 @@ def test_self_built_tables_with_a_workgroup_that_starts_late(oracle, dbg_lib):
 
 
 def test_kernel_forms_at_the_benchmark_shapes():
-    """Which form of the resample kernel a shape and batch get (pick_kernel) -- never visible in a chain's values, so
+    """Which form of the resample kernel a shape and batch get (plan_kernel) -- never visible in a chain's values, so
     held here: the measured rules of profiles/r03/ab_smallsplit.log and ab_self_tables.log at the shapes they were
     measured on (an MI355X: 256 CUs)."""
     def form(sampler, N, P, K, batch=0):
