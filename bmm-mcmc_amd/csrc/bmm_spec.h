@@ -284,6 +284,86 @@ BMM_HD double expw_tab(double x, Tab T) {
 }
 BMM_HD double expw_(double x) { return expw_tab(x, exp256_table()); }
 
+// ---------------------------------------------------------------- the draw, decided in binary32 where that is safe
+// The draw of z_n is ONE integer: cnt = #{k : u * tot >= cdf_k}, cdf_k the binary64 running sum of
+// expw_(score_k - m) in label order, tot = cdf_K (the definition; draw_spec below).  draw_tier1 computes the same
+// count from binary32 weights and says whether that count is PROVEN equal to the definition's: it is whenever
+// u~ * tot~ stays further than kTier1Eps * tot~ from every binary32 CDF entry.  A caller that gets `false` runs the
+// definition; so the two tiers together are exact, not approximate.
+//
+// Why kTier1Eps = 2^-16 suffices, for up to kTier1MaxCats = 64 categories.  Both tiers start from the same binary64
+// d_k = score_k - m <= 0 (0 for the maximum, so the exact total T = sum_k e^(d_k) is >= 1).  Write h = 2^-24 (half an
+// ulp of binary32).  Against the exact e^(d_k), partial sums C_k and u * T, tier 1 is off by at most, in units of T:
+//   narrowing d_k to binary32, the binary32 constant log2(e) and their rounded product: the argument of exp2 is
+//     d_k log2(e) (1 + delta), |delta| <= 3.01 h, which moves the weight w_k by w_k ln(1/w_k) |delta|; summed,
+//     sum_k w_k ln(1/w_k) = T (H(w / T) - ln T) <= T ln K (H the entropy, <= ln K)      <= 3.01 ln(64) h = 12.6 h
+//   the hardware exp2 (v_exp_f32: 1 ulp = 2 h of each weight, the ISA's documented bound; results below 2^-126
+//     are flushed to 0, an absolute 2^-126 each)                                          <=  2.0 h
+//   the binary32 running sum: K - 1 additions, each within h of a partial sum <= T          <= 63.0 h
+//   u narrowed to binary32 (h) and the rounded product u~ * tot~ (h)                        <=  2.0 h
+//   second-order terms of all of the above ((1 + 63 h)^2 and the like)                      <   0.1 h
+// and the definition itself by its own rounding: expw_ < 1 ulp of binary64, 63 binary64 additions and one product,
+// < 2^-45.  The difference t - cdf_k that either tier takes the sign of therefore differs between the tiers by
+// less than E * T with E = 79.7 h + 2^-45 < 2^-17.6 = 4.8e-6, and tot~ >= T (1 - E).  The test is
+// |t~ - c~_k| > 2^-16 tot~ >= 2^-16 (1 - E) T > 3.2 E T: the sign cannot differ, with a factor three to spare.  Equal
+// consecutive CDF entries (categories of weight zero) and u = 0 need no case of their own: a tie t~ = c~_k is
+// never "further than", and a non-tie is decided by the same bound.  A lane whose scores hold a NaN or whose
+// maximum is not finite gets NaN into tot~ (the running sum carries it to the end) or fails the test on m: never
+// certain.  exp2 is a parameter so that the host test can run the function with the exponential pushed to either
+// end of its documented error.
+constexpr float kTier1Eps = 0x1p-16f;
+constexpr int kTier1MaxCats = 64;
+struct Exp2Fast {
+    BMM_HD float operator()(float x) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_amdgcn_exp2f(x);  // v_exp_f32
+#else
+        return __builtin_exp2f(x);
+#endif
+    }
+};
+// sc[0..KT): the scores (the own-cluster substitution done), m their maximum, u the draw's uniform.  Returns
+// whether cnt is proven to be the definition's count.
+template <int KT, class Exp2 = Exp2Fast>
+BMM_HD bool draw_tier1(const double (&sc)[KT], double m, double u, float eps, int& cnt, Exp2 ex2 = Exp2()) {
+    static_assert(KT <= kTier1MaxCats, "kTier1Eps is derived for at most kTier1MaxCats categories");
+    float c[KT];
+    float run = 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < KT; ++k) {
+        const float d = (float)(sc[k] - m);
+        run = run + ex2(d * 0x1.715476p+0f);  // log2(e)
+        c[k] = run;
+    }
+    const float t = (float)u * run;
+    float nearest = __builtin_inff();
+    int n = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < KT; ++k) {
+        const float diff = t - c[k];
+        n += diff >= 0.0f ? 1 : 0;
+        nearest = __builtin_fminf(nearest, __builtin_fabsf(diff));  // (a NaN here is a NaN in `run` too)
+    }
+    cnt = n;
+    return nearest > eps * run && m > neg_inf() && m < pos_inf();  // false when `run` is NaN
+}
+// The definition, for the host: the count the draw is.  (The kernels carry it inline, around their emitting
+// and lane-sharing forms.)
+template <int KT>
+BMM_HD int draw_spec(const double (&sc)[KT], double m, double u) {
+    double cdf[KT];
+    double run = 0.0;
+    for (int k = 0; k < KT; ++k) { run = run + expw_(sc[k] - m); cdf[k] = run; }
+    const double t = u * run;
+    int n = 0;
+    for (int k = 0; k < KT; ++k) n += t >= cdf[k] ? 1 : 0;
+    return n;
+}
+
 // ---------------------------------------------------------------- variates
 // Standard normal by the Marsaglia polar method (log and sqrt only).
 BMM_HD double rnorm_(Stream& st) {

@@ -593,7 +593,8 @@ TableLayout layout_of(const bmm_chain* c) { return layout_of(c->p, !explicit_par
 // The test variant's switches (-DBMM_DEBUG_HOOKS: environment variables, read through dbg_env, so the product
 // library has none of them set).  These steer the shape and the kernel choice and are read when one of these is
 // made, once per choice; the others are read where they act: BMM_DEBUG_STREAM (chain_stream_create),
-// BMM_DEBUG_FAKE_DEVICES (fake_devices), BMM_DEBUG_BADLABEL and BMM_DEBUG_STRAGGLER (launch_resample).
+// BMM_DEBUG_FAKE_DEVICES (fake_devices), BMM_DEBUG_BADLABEL, BMM_DEBUG_STRAGGLER, BMM_DEBUG_DRAW_FALLBACK and
+// BMM_DEBUG_DRAW_NOEPS (launch_resample).
 int dbg_env_int(const char* name, int unset) { const char* v = dbg_env(name); return v ? (atoi(v) > 0 ? atoi(v) : 0) : unset; }
 struct DebugSwitches {
     bool generic = dbg_env("BMM_DEBUG_GENERIC");        // every shape on the generic path
@@ -869,7 +870,8 @@ int launch_resample(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t l
     ResampleArgs a{};
     a.X = c->dX; a.Xb = c->dXb; a.z_in = z_in; a.z_out = z_out; a.tab = c->dTab; a.dNk = c->dDNk; a.dS = c->dDS;
     a.lo = lo; a.hi = hi; a.sweep = sweep; a.minus_in_lds = c->minus_in_lds; a.diag = c->dDiag;
-    a.dbg_flag = c->dDbgFlag; a.dbg_inject = (dbg_env("BMM_DEBUG_BADLABEL") ? 1 : 0) | (dbg_env("BMM_DEBUG_STRAGGLER") ? 2 : 0);
+    a.dbg_flag = c->dDbgFlag; a.dbg_inject = (dbg_env("BMM_DEBUG_BADLABEL") ? 1 : 0) | (dbg_env("BMM_DEBUG_STRAGGLER") ? 2 : 0) |
+                                             (dbg_env("BMM_DEBUG_DRAW_FALLBACK") ? 4 : 0) | (dbg_env("BMM_DEBUG_DRAW_NOEPS") ? 8 : 0);
     a.Nk = c->dNk; a.S = c->dS; a.alpha_ptr = c->dAlpha; a.self_done = c->dSelfDone;
     const bool emit = c->probs_dst != nullptr;
     const bool use_generic = c->generic || (emit && !c->fn_emit);  // the int32 layout has no emitting twin
@@ -1314,6 +1316,9 @@ void bmm_chain_destroy(bmm_chain* c) {
         if (hipMemcpy(d, c->dDiag, sizeof d, hipMemcpyDeviceToHost) == hipSuccess && d[5])
             fprintf(stderr, "[bmm diag launch] ticks per wave and launch: table staging %.0f, tile loop %.0f, waiting for the workgroup %.0f, flush %.0f\n",
                     d[8] / (double)d[5], d[9] / (double)d[5], d[10] / (double)d[5], d[11] / (double)d[5]);
+        if (d[5] && d[12])
+            fprintf(stderr, "[bmm diag draw] draws of a wave (64 observations) %llu, of them by the binary64 definition %llu (%.4f%%)\n",
+                    d[12], d[13], 100.0 * (double)d[13] / (double)d[12]);
     }
 #endif
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);

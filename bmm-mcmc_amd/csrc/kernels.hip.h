@@ -505,9 +505,25 @@ __device__ __forceinline__ void dbg_check_labels(const ResampleArgs& a, bool val
     }
 }
 #define BMM_DBG_LABELS(a, valid, first, K, zn, zo) dbg_check_labels(a, valid, first, K, zn, zo)
+// The two-tier draw of k_resample under test: BMM_DEBUG_DRAW_FALLBACK (bit 4) sends every wave to the binary64
+// definition; BMM_DEBUG_DRAW_NOEPS (bit 8) gives the binary32 tier a band of width zero around the CDF entries, so
+// that it answers for draws it cannot prove -- a test then sees that the band is what keeps the labels right.
+#define DBG_TIER1_FORCE(a, certain) if ((a).dbg_inject & 4) certain = false
+#define DBG_TIER1_EPS(a, eps) if ((a).dbg_inject & 8) eps = 0.0f
 #else
 #define BMM_DBG_LABELS(a, valid, first, K, zn, zo)
+#define DBG_TIER1_FORCE(a, certain)
+#define DBG_TIER1_EPS(a, eps)
 #endif
+
+// The running maximum of the scores in one v_max_f64 per score.  __builtin_fmax first quiets a signalling NaN in
+// either operand (a v_max_f64 x, x apiece: twenty spare binary64 instructions per observation at K = 20), which a
+// score, being a sum, never is; on every other operand, quiet NaNs included, the instruction alone is fmax.
+__device__ __forceinline__ double max_score(double m, double sc) {
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(m), "v"(sc));
+    return r;
+}
 
 // Where a lane sits in a tile of NT consecutive observations.  Lanes past the end of the
 // batch re-read its last observation (and never write back).
@@ -915,6 +931,8 @@ __global__ __launch_bounds__(NT) void k_resample(ChainParams p, ResampleArgs a) 
     // C5 +3.5 %, c3 +2.6 % over raising the priority for the issue of the reads only (which was +2 % over
     // none); the int32 pipeline and the two-lane form lose 1-3 % with it (profiles/r02/README.md).
     constexpr bool kPrioKernel = BITS && SPLIT == 1;
+    // the draw tries binary32 first (below): the plain kernels with an observation's categories all in one lane
+    constexpr bool kTier1 = SPLIT == 1 && !EMIT;
     static_assert(SPLIT == 1 || (SPLIT == 2 && BITS && MINUS != 2 && KT % 2 == 0), "split form");
     constexpr int SB = BITS ? 32 : STG;  // start bits of the lookup groups one stage scores
     constexpr int KH = KT / SPLIT;      // accumulators per lane
@@ -1022,6 +1040,7 @@ __global__ __launch_bounds__(NT) void k_resample(ChainParams p, ResampleArgs a) 
         }
     }
 
+    DIAG(unsigned long long d_ndraw = 0, d_nfall = 0;)
     DIAG(unsigned long long d_nmov = 0, d_ntile = 0; unsigned long long d_score = 0, d_pack = 0, d_draw = 0, d_mov = 0, d_pro = 0; unsigned long long d_t = diag_stamp(); const unsigned long long d_staged = d_t;)
     if (has_tile) {
         // prologue: the rest of the first tile's features, nothing to overlap with yet
@@ -1150,38 +1169,57 @@ __global__ __launch_bounds__(NT) void k_resample(ChainParams p, ResampleArgs a) 
                 double sc = acc[k];
                 if (has_minus && kb + k == zo) sc = acc_own;
                 acc[k] = sc;
-                m = __builtin_fmax(m, sc);  // v_max_f64; scores are never NaN
+                m = max_score(m, sc);
             }
             if (SPLIT == 2) m = __builtin_fmax(m, __shfl_xor(m, 32));
-            // weights exp(score - max) and their running sum in label order; acc[k] becomes the CDF
-            double run = 0.0;
-#pragma unroll
-            for (int k = 0; k < KH; ++k) {
-                const double w = expw_tab(acc[k] - m, ET);
-                if (EMIT && kb + k < p.Kc && pos.valid) a.wts[(int64_t)(kb + k) * p.N + pos.i] = w;
-                if (SPLIT == 1) { run = run + w; acc[k] = run; }
-                else acc[k] = w;
-                if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);  // two at a time: bounds the temporaries
-            }
-            if (SPLIT == 2) {
-                // the running sum goes through the categories in label order: the upper half continues
-                // from the lower half's total
-#pragma unroll
-                for (int k = 0; k < KH; ++k) run = run + acc[k];
-                const double lower = __shfl(run, lane & 31);
-                run = half ? lower : 0.0;
-#pragma unroll
-                for (int k = 0; k < KH; ++k) { run = run + acc[k]; acc[k] = run; }
-                run = __shfl(run, (lane & 31) + 32);
-            }
-            const double tot = run;
-            if (EMIT && half == 0 && pos.valid) a.wtot[pos.i] = tot;
             // u <= 1 - 2^-52, so u * tot < tot: the walk always ends on a category with weight
-            const double t = z_uniform(p.seed, (uint64_t)(p.obs0 + pos.ic), a.sweep) * tot;
+            const double u = z_uniform(p.seed, (uint64_t)(p.obs0 + pos.ic), a.sweep);
+            // The draw is one integer, the count of CDF entries at or below u * tot.  The plain one-lane kernels
+            // first take it from binary32 weights (draw_tier1, bmm_spec.h: hardware exp2, no table read), which also
+            // says per lane whether that count is proven to be the definition's; when it is for every lane of the
+            // wave the twenty binary64 exponentials below are not run at all.  Otherwise -- some lane's u * tot
+            // within 2^-16 tot of a CDF entry, an impossible observation, a NaN -- the whole wave runs the
+            // definition as before and every lane takes its result: a uniform branch, nothing per lane.
+            bool tier1 = false;
             int cnt = 0;
+            if constexpr (kTier1) {
+                float eps = kTier1Eps;
+                DBG_TIER1_EPS(a, eps);
+                bool certain = draw_tier1<KH>(acc, m, u, eps, cnt);
+                DBG_TIER1_FORCE(a, certain);
+                tier1 = __ballot(!certain) == 0;
+                DIAG(++d_ndraw; d_nfall += tier1 ? 0 : 1;)
+            }
+            if (!tier1) {
+                // weights exp(score - max) and their running sum in label order; acc[k] becomes the CDF
+                double run = 0.0;
 #pragma unroll
-            for (int k = 0; k < KH; ++k) cnt += t >= acc[k] ? 1 : 0;
-            if (SPLIT == 2) cnt += __shfl_xor(cnt, 32);
+                for (int k = 0; k < KH; ++k) {
+                    const double w = expw_tab(acc[k] - m, ET);
+                    if (EMIT && kb + k < p.Kc && pos.valid) a.wts[(int64_t)(kb + k) * p.N + pos.i] = w;
+                    if (SPLIT == 1) { run = run + w; acc[k] = run; }
+                    else acc[k] = w;
+                    if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);  // two at a time: bounds the temporaries
+                }
+                if (SPLIT == 2) {
+                    // the running sum goes through the categories in label order: the upper half continues
+                    // from the lower half's total
+#pragma unroll
+                    for (int k = 0; k < KH; ++k) run = run + acc[k];
+                    const double lower = __shfl(run, lane & 31);
+                    run = half ? lower : 0.0;
+#pragma unroll
+                    for (int k = 0; k < KH; ++k) { run = run + acc[k]; acc[k] = run; }
+                    run = __shfl(run, (lane & 31) + 32);
+                }
+                const double tot = run;
+                if (EMIT && half == 0 && pos.valid) a.wtot[pos.i] = tot;
+                const double t = u * tot;
+                cnt = 0;
+#pragma unroll
+                for (int k = 0; k < KH; ++k) cnt += t >= acc[k] ? 1 : 0;
+                if (SPLIT == 2) cnt += __shfl_xor(cnt, 32);
+            }
             int zn = cnt;
             if (!(m > neg_inf())) zn = zoc;  // every category impossible: keep (or 0)
             if (p.mode == MODE_DP && zn == K) {
@@ -1228,6 +1266,8 @@ __global__ __launch_bounds__(NT) void k_resample(ChainParams p, ResampleArgs a) 
         // per-launch phases of a wave: table staging, tile loop, wait for the workgroup, flush
         atomicAdd(&a.diag[8], d_staged - d_entry); atomicAdd(&a.diag[9], d_loop - d_staged);
         atomicAdd(&a.diag[10], d_sync - d_loop); atomicAdd(&a.diag[11], d_flush - d_sync);
+        // the two-tier draw: draws of 64 observations a wave made, and how many of them ran the binary64 definition
+        atomicAdd(&a.diag[12], d_ndraw); atomicAdd(&a.diag[13], d_nfall);
     })
 }
 
