@@ -197,12 +197,60 @@ class _Predict:
         return out
 
 
-def _with_predictive(out, pr, pt=None):
+def _with_predictive(out, pr, pt=None, lo=None):
     if pr is not None:
         out["predictive"] = pr.result()
     if pt is not None:
         out["partition"] = pt.result()
+    if lo is not None:
+        out["loo"] = lo.result()
     return out
+
+
+# ---------------------------------------------------------------- loo=: leave-one-out predictive, LPML, WAIC
+class _LooOut(_C.Structure):  # bmm_loo_out
+    _fields_ = [("log_cpo", _C.c_void_p), ("ess", _C.c_void_p), ("lppd", _C.c_void_p), ("mean", _C.c_void_p),
+                ("var", _C.c_void_p), ("lpml", _C.c_void_p), ("min_ess", _C.c_void_p), ("p_waic", _C.c_void_p),
+                ("elpd_waic", _C.c_void_p), ("n_folded", _C.c_void_p), ("ell", _C.c_void_p)]
+
+
+class _Loo:
+    """Outputs of the leave-one-out summary (include/bmm_mcmc.h): per fitted row log_cpo, ess,
+    lppd, mean and var of ell over the folded states; lpml, min_ess, n_folded; p_waic and elpd_waic for the samplers
+    that carry explicit parameters; optionally the (S, N) trace ell."""
+
+    def __init__(self, N, S=0, trace=False, waic=False):
+        self.waic = waic
+        self.rows = {k: _np.full(N, _np.nan) for k in ("log_cpo", "ess", "lppd", "mean", "var")}
+        self.scal = (_C.c_double * 4)(*([float("nan")] * 4))
+        self.n = _C.c_int(0)
+        self.ell = _np.full((S, N), _np.nan, order="F") if trace else None
+        a = _C.addressof(self.scal)
+        self.s = _LooOut(*[self.rows[k].ctypes.data for k in ("log_cpo", "ess", "lppd", "mean", "var")],
+                         a, a + 8, a + 16, a + 24, _C.addressof(self.n), self.ell.ctypes.data if trace else None)
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_loo_summary(_C.byref(self.s)))
+
+    def result(self):
+        out = dict(self.rows)
+        out.update(lpml=self.scal[0], min_ess=self.scal[1], n_folded=self.n.value)
+        if self.waic:
+            out.update(p_waic=self.scal[2], elpd_waic=self.scal[3])
+        if self.ell is not None:
+            out["ell"] = self.ell
+        return out
+
+
+def _make_loo(loo, N, S, chains, waic):
+    """loo= of a wrapper, checked before any device is touched"""
+    if loo is None or loo is False:
+        return None
+    if loo is not True and loo != "trace":
+        raise ValueError('loo must be True, "trace" or False')
+    if int(chains) > 1:
+        raise ValueError("loo= is offered per chain (chains=1): pooling the leave-one-out summary over chains is not offered")
+    return _Loo(N, S, loo == "trace", waic)
 
 
 # ---------------------------------------------------------------- partition=: point estimate and similarity
@@ -366,12 +414,14 @@ def partition_plan(S, N, Kc, candidates=None, criterion="binder"):
     return dict(zip(_PT_PLAN_FIELDS, (int(v) for v in out)))
 
 
-def _run(base, args, pr, hooks=None, rel=None, part=None):
+def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
     if part is not None:
         part.arm()
+    if loo is not None:
+        loo.arm()
     if pr is None:
         if rel is not None:
             return getattr(L, "bmm_%s_run_relabel" % base)(*args, rel.ref())
@@ -526,7 +576,7 @@ def _multi(sampler, X, chains, devices, z0s, pi0s, th0s, nsamples, K, alpha, bet
 def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
                     relabel=False, burnrelabel=50, debug=False, *, seed=None, batch=None, device=0,
                     initial_K=None, chains=1, devices=None, stephens=None, newdata=None, predictive_trace=False,
-                    responsibilities=False, partition=None, partition_stride=1, similarity_of=None):
+                    responsibilities=False, partition=None, partition_stride=1, similarity_of=None, loo=False):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -548,7 +598,13 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     not depend on their numbering), "z" that row, `n_used` the rows used (the unassigned starting row of a run without
     burn-in is left out).  `similarity_of=` indices (0-based) adds "similarity", how often each pair of those
     observations shared a cluster.  With `chains > 1` the chains' traces are pooled into one estimate, attached to
-    every chain object with "chain" naming the chain `best` indexes.
+    every chain object with "chain" naming the chain `best` indexes.  `loo=True`: the result gains `loo = {"log_cpo",
+    "ess", "lppd", "mean", "var" (N,), "lpml", "min_ess", "n_folded"}`, the leave-one-out predictive of every fitted
+    row over the kept sweeps, computed on the device (include/bmm_mcmc.h): log_cpo[i] estimates
+    log p(x_i | X_-i), lpml is their sum (the log pseudo-marginal likelihood: compare K, priors or samplers with it),
+    ess the effective sample size of each row's harmonic mean (between 1 and n_folded; small values flag an
+    unreliable log_cpo).  gibbs_stickbreaking and gibbs_full add "p_waic" and "elpd_waic".  `loo="trace"` adds "ell",
+    the (S, N) trace of the per-state values (without burn-in its first row is NaN).  Not offered with chains > 1.
     """
     X = _capi.as_x(data)
     N, P = X.shape
@@ -558,6 +614,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     chains = int(chains)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
+    lo = _make_loo(loo, N, nsamples - burnin, chains, False)
     if chains > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
@@ -582,8 +639,8 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
                 _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("collapsed", args, pr, rel=dr, part=pt)
-        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt)
+            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo)
+        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo)
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((K, P, S), order="F")
@@ -593,20 +650,20 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
             _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
-        return _with_predictive(rl.finish(rc, out), pr, pt)
+        return _with_predictive(rl.finish(rc, out), pr, pt, lo)
     _capi.check(rc)
-    return _with_predictive(out, pr, pt)
+    return _with_predictive(out, pr, pt, lo)
 
 
 def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=None, relabel=False,
              burnrelabel=50, maxK=30, debug=False, *, seed=None, batch=None, device=0, chains=1, devices=None,
              stephens=None, newdata=None, predictive_trace=False, responsibilities=False, partition=None,
-             partition_stride=1, similarity_of=None):
+             partition_stride=1, similarity_of=None, loo=False):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
-    (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`: as
+    (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column."""
     X = _capi.as_x(data)
     N, P = X.shape
@@ -615,6 +672,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     seed = _seed(seed)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, maxK + 1, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
+    lo = _make_loo(loo, N, nsamples - burnin, chains, False)
     if int(chains) > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
@@ -633,8 +691,8 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                 _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
                 _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("dp", args, pr, rel=dr, part=pt)
-        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt)
+            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo)
+        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo)
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((maxK, P, S), order="F")
@@ -645,17 +703,18 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt)
+        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
-        return _with_predictive(rl.finish(rc, out), pr, pt)
+        return _with_predictive(rl.finish(rc, out), pr, pt, lo)
     _capi.check(rc)
-    return _with_predictive(out, pr, pt)
+    return _with_predictive(out, pr, pt, lo)
 
 
 def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, burnin, relabel, burnrelabel, seed,
               device, initial_pi, initial_theta, chains, devices, stephens, debug=False, newdata=None,
-              predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None):
+              predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None,
+              loo=False):
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, K = int(nsamples), int(K)
@@ -664,6 +723,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
     chains = int(chains)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
+    lo = _make_loo(loo, N, nsamples - burnin, chains, True)
     base = fn[len("bmm_"):-len("_run_probs")]
 
     def start(sd, pi, th):
@@ -701,8 +761,8 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
                 _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
                 _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run(base, args, pr, rel=dr, part=pt)
-        return _with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt)
+            rc = _run(base, args, pr, rel=dr, part=pt, loo=lo)
+        return _with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo)
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((K, P, S), order="F")
@@ -713,36 +773,36 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
             _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run(base, args, pr, hooks=rl, part=pt)
+        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo)
     out = {"pi": pi, "alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
-        return _with_predictive(rl.finish(rc, out), pr, pt)
+        return _with_predictive(rl.finish(rc, out), pr, pt, lo)
     _capi.check(rc)
-    return _with_predictive(out, pr, pt)
+    return _with_predictive(out, pr, pt, lo)
 
 
 def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
                         relabel=False, burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None,
                         initial_theta=None, chains=1, devices=None, stephens=None, newdata=None,
                         predictive_trace=False, responsibilities=False, partition=None, partition_stride=1,
-                        similarity_of=None):
+                        similarity_of=None, loo=False):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
     src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
-    `predictive_trace`, `responsibilities`: as gibbs_collapsed."""
+    `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic"."""
     return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
                      burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
-                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of)
+                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
                burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None, initial_theta=None, chains=1,
                devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False,
-               partition=None, partition_stride=1, similarity_of=None):
+               partition=None, partition_stride=1, similarity_of=None, loo=False):
     """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
-    `predictive_trace`, `responsibilities`: as gibbs_collapsed."""
+    `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic"."""
     return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
                      relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
-                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of)
+                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo)
 
 
 class Chain:
@@ -950,6 +1010,37 @@ class Chain:
 
     def predict_reset(self):
         _capi.check(_capi.lib().bmm_chain_predict_reset(self._h))
+
+    # -- leave-one-out predictive of the fitted rows (include/bmm_mcmc.h)
+    def set_loo(self, on=True):
+        """Arm (or disarm) the leave-one-out summary: 12 doubles per fitted row on the device.  Arming an armed chain
+        empties the accumulators.  An armed chain that is not folding sweeps exactly as an unarmed one."""
+        _capi.check(_capi.lib().bmm_chain_set_loo(self._h, _C.c_int(1 if on else 0)))
+
+    def loo_state(self):
+        """ell[i] = log p(x_i | everything else in the current state), (N,); no sweep is run and the accumulators
+        are untouched.  Refused for a state with unseated rows (every sampler but the finite collapsed one before
+        its first sweep)."""
+        out = _np.zeros(self.N)
+        _capi.check(_capi.lib().bmm_chain_loo_state(self._h, _capi.vp(out)))
+        return out
+
+    def sweeps_loo(self, n, trace=False):
+        """n more sweeps, each state folded into the leave-one-out accumulators.  trace=True returns the (n, N)
+        matrix of ell (and waits); otherwise returns None without waiting, as sweeps()."""
+        out = _np.zeros((n, self.N), order="F") if trace else None
+        _capi.check(_capi.lib().bmm_chain_sweeps_loo(self._h, _C.c_int(n), _capi.vp(out) if trace else None))
+        return out
+
+    def loo(self):
+        """The summary over the sweeps folded so far: {"log_cpo", "ess", "lppd", "mean", "var" (N,), "lpml", "min_ess",
+        "n_folded"} and, for stick-breaking and full, "p_waic" and "elpd_waic"."""
+        lo = _Loo(self.N, waic=self.sampler in ("stickbreaking", "full"))
+        _capi.check(_capi.lib().bmm_chain_get_loo(self._h, _C.byref(lo.s)))
+        return lo.result()
+
+    def loo_reset(self):
+        _capi.check(_capi.lib().bmm_chain_loo_reset(self._h))
 
     def profile(self, every=1):
         """Time the resample launches of every `every`-th sweep with HIP events (0/False: off)."""

@@ -435,6 +435,21 @@ predict_fn lookup_predict(int kt, int gw) {
     return fn;
 }
 
+// The leave-one-out kernel (k_loo) by accumulator count, group width and own-label tier (0 none: the explicit samplers,
+// 1 the minus-self tables in LDS, 2 in global memory): one workgroup size, one lane per row.  With an own-label pass
+// the kernel needs about 7.5 VGPRs per accumulator (code-object metadata: 118 at 12 accumulators, 256 at 32) and from 40
+// accumulators on would use scratch, so those forms are not instantiated: nullptr, and the chain's rows are scored by
+// k_loo_generic (loo_setup).  Without one (the explicit samplers) 64 accumulators take 191 VGPRs.
+constexpr int kLooMaxOwnKT = 32;
+typedef void (*loo_fn)(ChainParams, LooArgs);
+loo_fn lookup_loo(int kt, int gw, int minus) {
+    loo_fn fn = nullptr;
+    lift([&](auto KT, auto GW, auto MINUS) {
+        if constexpr (MINUS == 0 || KT <= kLooMaxOwnKT) fn = k_loo<KT, kLooThreads, GW, MINUS>;
+    }, kKT, kt, IntList<kGroupW, kGroupWAlt>{}, gw, IntList<0, 1, 2>{}, minus);
+    return fn;
+}
+
 constexpr size_t kLdsMax = 163840;  // gfx950: 160 KiB per workgroup
 // The one place a kernel is set up for launching with `lds` bytes of dynamic LDS: the attribute that allows
 // them, and how many of its workgroups of nt threads the runtime then fits on a CU.
@@ -527,6 +542,22 @@ struct bmm_chain {
     int pred_from = 0;
     double* pred_trace = nullptr; // or [..][predM] on the device: row j - pred_trace_base receives sweep j's logdens
     int pred_trace_base = 0;
+    // leave-one-out predictive of the fitted rows: the two table sets of the counting samplers
+    // (the explicit samplers score their own image dTab), the accumulators [kLooAcc][N] that live across sweeps, the
+    // outputs of k_loo_finish ([kLooOut][N], then the scalars), and what a sweep folds while loo_fold is set
+    bool loo_on = false;
+    double *dLooTab = nullptr, *dLooAcc = nullptr, *dLooOut = nullptr;
+    bool loo_generic = false;    // a resident shape whose rows k_loo_generic scores (lookup_loo), on scratch columns of its own
+    double* dLooScratch = nullptr;
+    int64_t loo_scratch_stride = 0;
+    int loo_folded = 0;          // states folded so far
+    loo_fn lfn = nullptr;
+    int loo_minus = 0, loo_grid_max = 0;
+    size_t loo_lds = 0;
+    bool loo_fold = false;       // sweeps j >= loo_from are folded as they are enqueued
+    int loo_from = 0;
+    double* loo_trace = nullptr; // or [..][N] on the device: row j - loo_trace_base receives sweep j's ell
+    int loo_trace_base = 0;
     int prof = 0;             // > 0: HIP events around the resample launches of every prof-th sweep
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
@@ -999,6 +1030,43 @@ int sweep_end_predict(bmm_chain* c, int j) {
     return enqueue_predict(c, row, nullptr, true);
 }
 
+// ---- leave-one-out predictive of the fitted rows ----
+// Score every fitted row against state j with its own contribution removed, stream-ordered behind whatever produced
+// that state: ell receives this state's values (device, may be null); fold adds them to the accumulators.
+int enqueue_loo(bmm_chain* c, int j, double* ell, bool fold) {
+    const ChainParams& p = c->p;
+    const double* tab = c->dTab;  // stick-breaking / full: group tables of (pi, theta), log pi in group 0
+    if (!explicit_params(p.mode)) {
+        hipLaunchKernelGGL(k_loo_tables, dim3(p.KT), dim3(512), 0, c->stream, p, c->dNk, c->dS, c->dDNk, c->dDS,
+                           c->dAlpha, c->dLooTab);
+        HIP_TRY(hipGetLastError());
+        tab = c->dLooTab;
+    }
+    LooArgs a{};
+    a.X = c->dX; a.Xb = c->dXb; a.N = p.N; a.z = explicit_params(p.mode) ? nullptr : label_row(c, j); a.tab = tab;
+    a.ell = ell; a.acc = fold ? c->dLooAcc : nullptr; a.n = c->loo_folded;
+    if (c->generic || c->loo_generic) {
+        double* const scr = c->generic ? c->dScratch : c->dLooScratch;
+        const int64_t stride = c->generic ? c->scratch_stride : c->loo_scratch_stride;
+        const int64_t nb = (p.N + 255) / 256, maxb = stride / 256;
+        hipLaunchKernelGGL(k_loo_generic, dim3((unsigned)(nb < maxb ? nb : maxb)), dim3(256), 0, c->stream, p, a, scr, stride);
+    } else {
+        const int64_t ntiles = (p.N + kLooThreads - 1) / kLooThreads;
+        const int grid = (int)(ntiles < c->loo_grid_max ? ntiles : c->loo_grid_max);
+        hipLaunchKernelGGL(c->lfn, dim3(grid), dim3(kLooThreads), c->loo_lds, c->stream, p, a);
+    }
+    HIP_TRY(hipGetLastError());
+    if (fold) c->loo_folded++;
+    return BMM_OK;
+}
+// the end of sweep j: what a predictive run, a leave-one-out run or the resident calls asked to fold
+int sweep_end_folds(bmm_chain* c, int j) {
+    const int rc = sweep_end_predict(c, j);
+    if (rc || !c->loo_fold || !c->loo_on || j < c->loo_from) return rc;
+    double* row = c->loo_trace ? c->loo_trace + (size_t)(j - c->loo_trace_base) * (size_t)c->p.N : nullptr;
+    return enqueue_loo(c, j, row, true);
+}
+
 // one sweep (index j >= 1) enqueued on the stream
 // phase 0: whole sweep; 1: z-resample only; 2: parameter draws and tables only (sharded chains)
 int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
@@ -1024,7 +1092,7 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
         hipLaunchKernelGGL(k_sb_theta_tables, dim3(p.KT + 1), dim3(256), 0, c->stream, p, c->dNk, c->dS,
                            c->dPi, c->dTheta, 1, (uint32_t)j, th_tr, c->dTab, c->dAlpha, al_tr, c->dViable);
         HIP_TRY(hipGetLastError());
-        return sweep_end_predict(c, j);
+        return sweep_end_folds(c, j);
     }
     int64_t lo = 0;
     while (lo < p.N) {
@@ -1045,7 +1113,7 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
     hipLaunchKernelGGL(k_count_sweep_end, dim3(1), dim3(1024), 0, c->stream, p, c->dNk, c->dS, c->dDNk,
                        c->dDS, c->dAlpha, (uint32_t)j, th_tr, al_tr, nk_tr);
     HIP_TRY(hipGetLastError());
-    return sweep_end_predict(c, j);
+    return sweep_end_folds(c, j);
 }
 
 // The resident kernel for a shape, batch and X layout: the forms to try, in order, each with its dynamic LDS.
@@ -1328,7 +1396,8 @@ void bmm_chain_destroy(bmm_chain* c) {
     }
     dev_pool().put(c->device, c->arena, c->arena_bytes);  // the stream is idle (synchronised above)
     dev_pool().put(c->device, c->run_arena, c->run_arena_bytes);
-    void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc};
+    void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
+                    c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     chain_stream_release(c->device, c->stream, c->stream_kind);  // synchronised above
@@ -1969,6 +2038,230 @@ int bmm_chain_predict_reset(bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     HIP_TRY(hipSetDevice(c->device));
     return pred_reset(c);
+}
+
+// ---- leave-one-out predictive of the fitted rows ----
+static int loo_refused(const bmm_chain* c) {
+    if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the leave-one-out predictive is not offered on a sharded chain");
+    return BMM_OK;
+}
+static int loo_armed(const bmm_chain* c) {
+    if (!c->loo_on) return set_err(BMM_E_STATE, "the leave-one-out summary is not armed (bmm_chain_set_loo)");
+    return BMM_OK;
+}
+static int loo_reset(bmm_chain* c) {
+    c->loo_folded = 0;
+    const int64_t nb = (c->p.N + 255) / 256;
+    hipLaunchKernelGGL(k_loo_reset, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, c->stream, c->p.N, c->dLooAcc);
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+// the kernel of the chain's shape
+static int loo_setup(bmm_chain* c) {
+    if (c->generic || c->lfn || c->loo_generic) return BMM_OK;
+    if (!c->bits)
+        return set_err(BMM_E_UNSUPPORTED, "the leave-one-out predictive reads the bit planes: not offered on the int32 layout of a resident shape");
+    const int minus = explicit_params(c->p.mode) ? 0 : (c->minus_in_lds ? 1 : 2);
+    loo_fn f = lookup_loo(c->p.KT, c->p.W, minus);
+    if (!f && minus != 0 && c->p.KT > kLooMaxOwnKT) {  // more accumulators than the own-label form has registers for
+        int64_t stride = (c->p.N + 255) / 256 * 256;
+        if (stride > generic_threads(c->p.Kc)) stride = generic_threads(c->p.Kc);
+        const size_t bytes = (size_t)stride * c->p.Kc * sizeof(double);
+        int rc = pred_room(bytes, "the leave-one-out score columns");
+        if (rc) return rc;
+        HIP_TRY(hipMalloc(&c->dLooScratch, bytes));
+        c->loo_scratch_stride = stride;
+        c->loo_generic = true;
+        return BMM_OK;
+    }
+    if (!f) return set_err(BMM_E_STATE, "no leave-one-out kernel for %d accumulators", c->p.KT);
+    const TableLayout l = layout_of(c->p, minus != 0);
+    const size_t lds = (size_t)(minus == 1 ? l.doubles() : l.head()) * sizeof(double);
+    if (lds > kLdsMax) return set_err(BMM_E_STATE, "the leave-one-out table image (%zu bytes) does not fit in LDS", lds);
+    int per_cu = 0;
+    const hipError_t e = kernel_fits(f, kLooThreads, lds, &per_cu);
+    if (e != hipSuccess) return set_err(BMM_E_HIP, "kernel set-up failed: %s", hipGetErrorString(e));
+    c->lfn = f;
+    c->loo_minus = minus;
+    c->loo_lds = lds;
+    c->loo_grid_max = (per_cu < 1 ? 1 : per_cu) * c->num_cus;
+    return BMM_OK;
+}
+// a state every row of which is seated: the finite collapsed sampler from its initial labels on, the others after
+// their first sweep
+static int loo_seated(const bmm_chain* c) {
+    if (c->p.mode != MODE_COLLAPSED && c->sweep < 1)
+        return set_err(BMM_E_STATE, "no row has a label before the first sweep: there is no leave-one-out predictive of this state");
+    return BMM_OK;
+}
+// rows x N values on the device (row-major) into the caller's ld x N column-major matrix, from row row0 on
+static int loo_trace_out(bmm_chain* c, const double* dtrace, int rows, double* out, int ld, int row0) {
+    const int64_t N = c->p.N;
+    std::vector<double> line((size_t)N);
+    for (int s = 0; s < rows; ++s) {
+        HIP_TRY(hipMemcpy(line.data(), dtrace + (size_t)s * (size_t)N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < N; ++i) out[(size_t)(row0 + s) + (size_t)i * (size_t)ld] = line[(size_t)i];
+    }
+    return BMM_OK;
+}
+
+int bmm_chain_set_loo(bmm_chain* c, int on) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        int rc = loo_refused(c);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // nothing still reads what goes
+        if (!on) {
+            void** bufs[] = {reinterpret_cast<void**>(&c->dLooTab), reinterpret_cast<void**>(&c->dLooAcc),
+                             reinterpret_cast<void**>(&c->dLooOut), reinterpret_cast<void**>(&c->dLooScratch)};
+            for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+            c->loo_generic = false;
+            c->loo_on = false;
+            c->loo_folded = 0;
+            return BMM_OK;
+        }
+        if (c->loo_on) return loo_reset(c);
+        if (!c->have_data) return set_err(BMM_E_STATE, "data matrix not set");
+        rc = loo_setup(c);
+        if (rc) return rc;
+        const size_t N = (size_t)c->p.N;
+        const bool counting = !explicit_params(c->p.mode);
+        const size_t tab_bytes = counting ? (size_t)layout_of(c->p, true).doubles() * sizeof(double) : 0;
+        const size_t acc_bytes = N * kLooAcc * sizeof(double), out_bytes = (N * kLooOut + 8) * sizeof(double);
+        rc = pred_room(tab_bytes + acc_bytes + out_bytes, "the leave-one-out accumulators (12 doubles per fitted row)");
+        if (rc) return rc;
+        DevBuf tab, acc, out;
+        if (counting) {
+            HIP_TRY(tab.alloc(tab_bytes));
+            HIP_TRY(hipMemsetAsync(tab.p, 0, tab_bytes, c->stream));  // (the padding groups of the minus-self tables)
+        }
+        HIP_TRY(acc.alloc(acc_bytes));
+        HIP_TRY(out.alloc(out_bytes));
+        c->dLooTab = tab.as<double>(); tab.p = nullptr;
+        c->dLooAcc = acc.as<double>(); acc.p = nullptr;
+        c->dLooOut = out.as<double>(); out.p = nullptr;
+        c->loo_on = true;
+        return loo_reset(c);
+    });
+}
+
+int bmm_chain_loo_state(bmm_chain* c, double* ell_out) {
+    return guarded([&]() -> int {
+        if (!c || !ell_out) return set_err(BMM_E_ARG, "null argument");
+        int rc = loo_refused(c);
+        if (rc == BMM_OK) rc = loo_armed(c);
+        if (rc == BMM_OK) rc = loo_seated(c);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        if (!c->started) { rc = chain_start(c); if (rc) return rc; }
+        const size_t N = (size_t)c->p.N;
+        DevBuf el;
+        HIP_TRY(el.alloc(N * sizeof(double)));
+        rc = enqueue_loo(c, c->sweep, el.as<double>(), false);
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+        const hipError_t e = hipMemcpyAsync(ell_out, el.p, N * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);  // the scratch goes out of scope
+        if (e != hipSuccess || e2 != hipSuccess) return set_err(BMM_E_HIP, "copying the leave-one-out predictive failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_sweeps_loo(bmm_chain* c, int n, double* ell_trace) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (n < 0) return set_err(BMM_E_ARG, "n must be >= 0");
+        int rc = loo_refused(c);
+        if (rc == BMM_OK) rc = loo_armed(c);
+        if (rc) return rc;
+        if (n == 0) return BMM_OK;
+        HIP_TRY(hipSetDevice(c->device));
+        DevBuf tr;
+        if (ell_trace) {
+            const size_t bytes = (size_t)n * (size_t)c->p.N * sizeof(double);
+            rc = pred_room(bytes, "the leave-one-out trace (n x N doubles)");
+            if (rc) return rc;
+            HIP_TRY(tr.alloc(bytes));
+        }
+        c->loo_fold = true;
+        c->loo_from = c->sweep + 1;
+        c->loo_trace = tr.as<double>();
+        c->loo_trace_base = c->sweep + 1;
+        rc = bmm_chain_sweeps(c, n);
+        c->loo_fold = false;
+        c->loo_trace = nullptr;
+        if (!ell_trace) return rc;  // as bmm_chain_sweeps: enqueued, not waited for
+        const hipError_t e = hipStreamSynchronize(c->stream);  // the trace buffer goes out of scope
+        if (rc) return rc;
+        if (e != hipSuccess) return set_err(BMM_E_HIP, "the sweeps failed: %s", hipGetErrorString(e));
+        return loo_trace_out(c, tr.as<double>(), n, ell_trace, n, 0);
+    });
+}
+
+int bmm_chain_get_loo(bmm_chain* c, const bmm_loo_out* o) {
+    return guarded([&]() -> int {
+        if (!c || !o) return set_err(BMM_E_ARG, "null argument");
+        int rc = loo_refused(c);
+        if (rc == BMM_OK) rc = loo_armed(c);
+        if (rc) return rc;
+        if (o->n_folded) *o->n_folded = c->loo_folded;
+        if (c->loo_folded < 1) return set_err(BMM_E_STATE, "no state has been folded yet (bmm_chain_sweeps_loo)");
+        HIP_TRY(hipSetDevice(c->device));
+        const int64_t N = c->p.N;
+        const int64_t nb = (N + 255) / 256;
+        double* const scal = c->dLooOut + (size_t)N * kLooOut;
+        hipLaunchKernelGGL(k_loo_finish, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, c->stream, N, c->loo_folded,
+                           c->dLooAcc, c->dLooOut);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_loo_reduce, dim3(1), dim3(1024), 0, c->stream, N, c->dLooOut, scal);
+            e = hipGetLastError();
+        }
+        double* const rows[kLooOut] = {o->log_cpo, o->ess, o->lppd, o->mean, o->var};
+        for (int q = 0; q < kLooOut && e == hipSuccess; ++q)
+            if (rows[q]) e = hipMemcpyAsync(rows[q], c->dLooOut + (size_t)q * N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        double sc[5] = {0, 0, 0, 0, 0};
+        if (e == hipSuccess) e = hipMemcpyAsync(sc, scal, sizeof sc, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess || e2 != hipSuccess) return set_err(BMM_E_HIP, "reading the leave-one-out summary failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        const bool waic = explicit_params(c->p.mode);  // ell is a log likelihood for the explicit samplers only
+        if (o->lpml) *o->lpml = sc[0];
+        if (o->min_ess) *o->min_ess = sc[1];
+        if (o->p_waic) *o->p_waic = waic ? sc[3] : std::nan("");
+        if (o->elpd_waic) *o->elpd_waic = waic ? sc[4] : std::nan("");
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_loo_reset(bmm_chain* c) {
+    if (!c) return set_err(BMM_E_ARG, "null chain");
+    int rc = loo_armed(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return loo_reset(c);
+}
+
+// the outputs of a run that had the summary armed: S kept rows, the first `burnin ? 0 : 1` of them not folded
+static int loo_run_out(bmm_chain* c, const bmm_loo_out& o, const double* dtrace, int S, int burnin) {
+    const int64_t N = c->p.N;
+    const double nan = std::nan("");
+    int rc = BMM_OK;
+    if (c->loo_folded < 1) {
+        double* const rows[kLooOut] = {o.log_cpo, o.ess, o.lppd, o.mean, o.var};
+        for (double* r : rows) if (r) for (int64_t i = 0; i < N; ++i) r[i] = nan;
+        double* const sc[4] = {o.lpml, o.min_ess, o.p_waic, o.elpd_waic};
+        for (double* v : sc) if (v) *v = nan;
+        if (o.n_folded) *o.n_folded = 0;
+    } else {
+        rc = bmm_chain_get_loo(c, &o);
+    }
+    if (rc == BMM_OK && o.ell) {
+        const int first = c->loo_from - burnin;  // 1 without burn-in: that row stays NaN
+        for (int s = 0; s < first && s < S; ++s)
+            for (int64_t i = 0; i < N; ++i) o.ell[(size_t)s + (size_t)i * (size_t)S] = nan;
+        if (S > first) rc = loo_trace_out(c, dtrace + (size_t)first * (size_t)N, S - first, o.ell, S, first);
+    }
+    return rc;
 }
 
 }  // extern "C"
@@ -2673,7 +2966,10 @@ struct PtArmed { bool on = false; bmm_partition_out o{}; };
 thread_local PtArmed g_partition;
 // first line of every public *_run* entry point, bmm_multi_run included: whatever the call returns, and wherever it
 // returns from, the summary is no longer armed afterwards
-struct PtDisarm { ~PtDisarm() { g_partition.on = false; } };
+// ... and the leave-one-out summary (bmm_set_loo_summary), armed and disarmed the same way
+struct LooArmed { bool on = false; bmm_loo_out o{}; };
+thread_local LooArmed g_loo;
+struct PtDisarm { ~PtDisarm() { g_partition.on = false; g_loo.on = false; } };
 // what a run checks of it before any device is touched
 int pt_check_armed(const bmm_partition_out& o, int S, int64_t N, int K) {
     if (!o.loss || !o.best || !o.n_used) return set_err(BMM_E_ARG, "partition: null buffer (loss, best, n_used)");
@@ -2915,7 +3211,31 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
                 c->pred_trace = ptrace.as<double>();
                 c->pred_trace_base = burnin;
             }
+            // the leave-one-out summary: armed for this run, every kept sweep folded the same way (sweep_end_folds)
+            const bool loo = g_loo.on;
+            DevBuf ltrace;
+            if (loo) {
+                rc = bmm_chain_set_loo(c, 1);
+                if (rc) return rc;
+                if (g_loo.o.ell) {
+                    const size_t bytes = (size_t)S * (size_t)N * sizeof(double);
+                    rc = pred_room(bytes, "the leave-one-out trace (S x N doubles)");
+                    if (rc) return rc;
+                    HIP_TRY(ltrace.alloc(bytes));
+                }
+                c->loo_fold = true;
+                c->loo_from = burnin > 0 ? burnin : 1;  // (trace row 0 of a run without burn-in is the start, not a sweep)
+                c->loo_trace = ltrace.as<double>();
+                c->loo_trace_base = burnin;
+            }
             rc = run_body(c, nsamples, io, hooks, rel);
+            c->loo_fold = false;
+            c->loo_trace = nullptr;
+            if (loo) {
+                const hipError_t es = hipStreamSynchronize(c->stream);  // before ltrace may go
+                if (rc == BMM_OK && es != hipSuccess) rc = set_err(BMM_E_HIP, "the run failed: %s", hipGetErrorString(es));
+                if (rc == BMM_OK) rc = loo_run_out(c, g_loo.o, ltrace.as<double>(), S, burnin);
+            }
             c->pred_fold = false;
             c->pred_trace = nullptr;
             if (predict) {
@@ -3257,6 +3577,12 @@ int bmm_device_stephens_plan(int64_t N, int K, int M, int64_t out[12]) {
 }
 
 // ---- clustering point estimate and posterior similarity: the stand-alone entry points ----
+int bmm_set_loo_summary(const bmm_loo_out* out) {
+    g_loo.on = out != nullptr;
+    if (out) g_loo.o = *out;
+    return BMM_OK;
+}
+
 int bmm_set_partition_summary(const bmm_partition_out* out) {
     g_partition.on = out != nullptr;
     if (out) g_partition.o = *out;

@@ -2006,6 +2006,369 @@ __global__ __launch_bounds__(256) void k_predict_finish(int64_t M, int Kc, int n
     }
 }
 
+// ---- leave-one-out predictive of the fitted rows ------------------------------
+// ell_i = log p(x_i | everything else in the state), include/bmm_mcmc.h.  For the counting samplers that is the
+// z-step of row i with its own contribution removed, normalised as the predictive is: every label scored from the
+// plain tables (constants over N - 1 fitted rows), the row's own label from the minus-self tables (n_k - 1, S_k - x_i),
+// max-shift, expw, total, ell = max + log(total).  No uniform, no draw, no histogram, no statistics.  For the explicit
+// samplers the labels do not enter and the chain's own image (log pi in group 0) is scored as k_predict scores it.
+// A fitted row is owned by one lane, so the seven accumulators a row keeps across sweeps are updated without atomics
+// and in a fixed order.
+constexpr int kLooAcc = 7;
+enum : int { LOO_MAX = 0, LOO_SUM, LOO_MIN, LOO_S1, LOO_S2, LOO_MEAN, LOO_M2 };
+//   LOO_MAX, LOO_SUM   streaming pair of logsumexp(ell): sum_s exp(ell_s) = exp(MAX) * SUM
+//   LOO_MIN, S1, S2    one running minimum for both harmonic sums: sum_s exp(-ell_s) = exp(-MIN) * S1,
+//                      sum_s exp(-2 ell_s) = exp(-2 MIN) * S2
+//   LOO_MEAN, LOO_M2   Welford's mean and sum of squared deviations of ell
+constexpr int kLooOut = 5;  // per-row outputs of k_loo_finish: log_cpo, ess, lppd, mean, var
+struct LooArgs {
+    const int32_t* X;    // generic path on the int32 layout: the matrix as handed over (else null)
+    const uint32_t* Xb;  // bit planes of the fitted rows (null on the int32 layout)
+    int64_t N;           // fitted rows
+    const int32_t* z;    // the state's labels, 0-based (null for the explicit samplers)
+    const double* tab;   // counting samplers: the image k_loo_tables wrote; explicit samplers: the chain's own image
+    double* ell;         // or null: [N], this state's ell
+    double* acc;         // or null (nothing is folded): [kLooAcc][N]
+    int n;               // states folded before this one
+};
+
+// The two table sets of the counting samplers from the statistics as they stand (the pending deltas are added,
+// nothing is folded or cleared: this kernel changes no state of the chain), in the TableLayout with own-cluster
+// tables at the shape's group width.  One workgroup per category; roles by thread / 128: the term of feature d for
+// x = 1 and x = 0 of the plain set (0, 1) and of the minus-self set (2, 3).
+//   plain       label k: log(n_k + alpha/K) - log(N - 1 + alpha) (finite; an empty label included, with the prior
+//               Bernoulli terms), log(n_k) - log(N - 1 + alpha) (DP; -inf when unused); the DP's new cluster, category
+//               K: log(alpha) - log(N - 1 + alpha) with the prior Bernoulli terms as a per-feature table
+//   minus-self  label k with n_k >= 1, groups of kGroupWm: the same with n_k - 1 and S_kd - x_d.  n_k = 1 gives the
+//               prior term (finite) and -inf (DP: a row that sat alone has its own label unused).  An entry whose bit
+//               pattern no member of the label can have (x_d = 1 where S_kd = 0, x_d = 0 where S_kd = n_k) is never read.
+// Same functions as k_count_tables and k_predict_tables: log_, div_, term_x1 / term_x0, group_entry.
+__global__ __launch_bounds__(512) void k_loo_tables(ChainParams p, const int32_t* __restrict__ Nk,
+                                                    const int32_t* __restrict__ S, const int32_t* __restrict__ dNk,
+                                                    const int32_t* __restrict__ dS, const double* __restrict__ alpha_ptr,
+                                                    double* __restrict__ tab) {
+    __shared__ double e1[kMaxP], e0[kMaxP], m1[kMaxP], m0[kMaxP], cst[4];  // cst: Cp, log(bg + n), Cm, log(bg + n - 1)
+    const int k = blockIdx.x;
+    const TableLayout L = layout_of(p, true);
+    const int P = p.P, K = p.K;
+    const bool is_label = k < K;
+    const bool dp_new = p.mode == MODE_DP && k == K;
+    const size_t KP = (size_t)K * P;
+    const int64_t n = is_label ? (int64_t)Nk[k] + delta_take(const_cast<int32_t*>(dNk), k, K) : 0;
+    const int role = threadIdx.x >> 7, dl = threadIdx.x & 127;
+    if (threadIdx.x == 0) {
+        const double alpha = *alpha_ptr;
+        const double ldN = log_((double)(p.Ntot - 1) + alpha);
+        const double bg = p.beta + p.gamma;
+        double cp = neg_inf(), cm = neg_inf();
+        if (is_label && p.mode == MODE_COLLAPSED) {
+            const double ak = div_(alpha, (double)K);
+            cp = log_((double)n + ak) - ldN;
+            if (n >= 1) cm = log_((double)(n - 1) + ak) - ldN;
+        } else if (is_label) {
+            if (n > 0) cp = log_((double)n) - ldN;
+            if (n > 1) cm = log_((double)(n - 1)) - ldN;
+        } else if (dp_new) {
+            cp = log_(alpha) - ldN;
+        }
+        cst[0] = cp;
+        cst[1] = log_(bg + (double)n);
+        cst[2] = cm;
+        cst[3] = n >= 1 ? log_(bg + (double)(n - 1)) : 0.0;
+        tab[L.cp() + k] = cp;
+        tab[L.cm() + k] = cm;
+        reinterpret_cast<int32_t*>(tab + L.nk())[k] = (int32_t)n;
+    }
+    __syncthreads();
+    const bool scored = is_label || dp_new;  // accumulators past Kc keep all-zero tables under a -inf constant
+    for (int c0 = 0; c0 < P; c0 += kChunkP) {
+        const int pc = P - c0 < kChunkP ? P - c0 : kChunkP;
+        if (dl < pc) {
+            const int d = c0 + dl;
+            const int64_t s = is_label ? (int64_t)S[(size_t)k * P + d] + delta_take(const_cast<int32_t*>(dS), (size_t)k * P + d, KP) : 0;
+            double t = 0.0;
+            if (role == 0) { if (scored) t = term_x1(p.beta, s, cst[1]); }
+            else if (role == 1) { if (scored) t = term_x0(p.gamma, n, s, cst[1]); }
+            else if (role == 2) { if (is_label && n >= 1 && s >= 1) t = term_x1(p.beta, s - 1, cst[3]); }
+            else { if (is_label && n >= 1 && s <= n - 1) t = term_x0(p.gamma, n - 1, s, cst[3]); }
+            (role == 0 ? e1 : role == 1 ? e0 : role == 2 ? m1 : m0)[dl] = t;
+        }
+        __syncthreads();
+        write_group_tables(p.W, e1, e0, pc, c0, p.KT, k, cst[0], tab + L.tp());
+        write_group_tables(kGroupWm, m1, m0, pc, c0, p.KT, k, cst[2], tab + L.tm());
+        __syncthreads();
+    }
+    if (k == 0 && threadIdx.x < 256) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];
+}
+
+// one fitted row's share of the accumulators; ell = this state's value, ET the exp256 table
+template <class Tab>
+__device__ __forceinline__ void loo_fold(const LooArgs& a, int64_t i, double ell, Tab ET) {
+    double* const A = a.acc + i;
+    const int64_t N = a.N;
+    {
+        const double rm = A[LOO_MAX * N], rs = A[LOO_SUM * N];
+        const bool up = ell > rm;
+        const double e = expw_tab(up ? rm - ell : ell - rm, ET);  // (-inf gives exactly 0: the first fold)
+        A[LOO_MAX * N] = up ? ell : rm;
+        A[LOO_SUM * N] = up ? rs * e + 1.0 : rs + e;
+    }
+    {
+        const double mn = A[LOO_MIN * N], s1 = A[LOO_S1 * N], s2 = A[LOO_S2 * N];
+        const bool dn = ell < mn;
+        const double e = expw_tab(dn ? ell - mn : mn - ell, ET);
+        const double e2 = e * e;
+        A[LOO_MIN * N] = dn ? ell : mn;
+        A[LOO_S1 * N] = dn ? s1 * e + 1.0 : s1 + e;
+        A[LOO_S2 * N] = dn ? s2 * e2 + 1.0 : s2 + e2;
+    }
+    {
+        const double mean = A[LOO_MEAN * N], m2 = A[LOO_M2 * N];
+        const double delta = ell - mean;
+        const double mean1 = mean + div_(delta, (double)(a.n + 1));
+        A[LOO_MEAN * N] = mean1;
+        A[LOO_M2 * N] = m2 + delta * (ell - mean1);
+    }
+}
+
+// One lane per fitted row, KT accumulators, NT threads.  MINUS: 0 the explicit samplers (no labels, no own pass),
+// 1 the minus-self tables in LDS behind the plain ones (the LDS image is Tp + Tm + the exponential's table: no
+// histogram, no chunk counter), 2 the minus-self tables gathered from global memory (the shapes whose resample
+// kernel does the same).  The own-label score is gathered before the accumulators are live, as k_resample's own
+// pass does; the others are read with the conflict-free per-group pattern of k_predict.  The next tile's words and
+// label are loaded before this tile is scored.
+constexpr int kLooThreads = 512;
+template <int KT, int NT, int GW, int MINUS>
+__global__ __launch_bounds__(NT) void k_loo(ChainParams p, LooArgs a) {
+    constexpr int GM = 1 << GW;
+    constexpr int CH = KT <= 24 ? KT : (KT <= 48 ? KT / 2 : KT / 4);  // lookups issued together
+    static_assert(KT % CH == 0, "chunking");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const TableLayout L{p.G, KT, MINUS ? p.Gm : 0, GM};
+    double* const lds = reinterpret_cast<double*>(smem);
+    const volatile lds_f64* const Tp = (const volatile lds_f64*)(lds + L.tp());
+    const volatile lds_f64* const TmL = (const volatile lds_f64*)(lds + L.tm());
+    const double* const TmG = a.tab + L.tm();
+    const lds_f64* const ET = (const lds_f64*)(lds + L.et());
+    const int P = p.P, G = p.G, Gm = p.Gm, K = p.K;
+    const int tid = threadIdx.x;
+    const int W = (P + 31) / 32;
+    const int64_t ntiles = (a.N + NT - 1) / NT;
+    int64_t tile = blockIdx.x;
+    uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+    int z = -1;
+    if (tile < ntiles) {  // the first tile's words go out before the image is staged
+        const int64_t i0 = tile * NT + tid;
+        const int64_t ic = i0 < a.N ? i0 : a.N - 1;
+        load_words(a.Xb, a.N, W, ic, b0, b1, b2, b3);
+        if (MINUS) z = a.z[ic];
+    }
+    {
+        const double2* src = reinterpret_cast<const double2*>(a.tab);
+        double2* dst = reinterpret_cast<double2*>(smem);
+        const int n2 = (MINUS == 1 ? L.doubles() : L.head()) / 2;  // even: every piece of the layout is
+        for (int i0 = tid; i0 < n2; i0 += NT * 8) {
+            double2 t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + u * NT;
+                t[u] = src[i < n2 ? i : n2 - 1];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + u * NT;
+                if (i < n2) dst[i] = t[u];
+            }
+        }
+    }
+    __syncthreads();
+    for (; tile < ntiles; tile += gridDim.x) {
+        const int64_t i = tile * NT + tid;
+        const bool valid = i < a.N;
+        const int64_t tnext = tile + gridDim.x;
+        uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
+        int zn = -1;
+        if (tnext < ntiles) {
+            const int64_t in = tnext * NT + tid;
+            const int64_t ic = in < a.N ? in : a.N - 1;
+            load_words(a.Xb, a.N, W, ic, n0, n1, n2, n3);
+            if (MINUS) zn = a.z[ic];
+        }
+        const bool seated = !MINUS || (unsigned)z < (unsigned)K;
+        double own = 0.0;
+        if (MINUS) {  // the row's own label from the minus-self tables, before the accumulators are live
+            const int zc = seated ? z : 0;
+#pragma unroll 1
+            for (int h = 0; h < W; ++h) {
+                const uint32_t cur = word_of(h, b0, b1, b2, b3), nxt = word_of(h + 1, b0, b1, b2, b3);
+                const int g_lo = (32 * h + kGroupWm - 1) / kGroupWm;
+                int g_hi = (32 * (h + 1) + kGroupWm - 1) / kGroupWm;
+                g_hi = g_hi < Gm ? g_hi : Gm;
+#pragma unroll 1
+                for (int g = g_lo; g < g_hi; ++g) {
+                    const unsigned nib = __builtin_amdgcn_alignbit(nxt, cur, (unsigned)(g * kGroupWm - 32 * h)) & (unsigned)(kGroupMm - 1);
+                    const size_t at = ((size_t)g * KT + zc) * kGroupMm + nib;
+                    own = own + (MINUS == 1 ? TmL[at] : TmG[at]);
+                }
+            }
+        }
+        // The own label's accumulator starts at -inf and stays there whatever is added (the tables hold no +inf), so
+        // its plain score counts exactly 0 below; the minus-self score is one more category, summed last.  (Replacing
+        // acc[z] after the scoring instead costs a second set of live accumulators: 254 VGPRs at KT = 32 and scratch
+        // from KT = 40 on, against 127 and none this way.)
+        double acc[KT];
+#pragma unroll
+        for (int k = 0; k < KT; ++k) acc[k] = MINUS && k == z ? neg_inf() : 0.0;
+#pragma unroll 1
+        for (int h = 0; h < W; ++h) {
+            const uint32_t cur = word_of(h, b0, b1, b2, b3), nxt = word_of(h + 1, b0, b1, b2, b3);
+            const int g_lo = (32 * h + GW - 1) / GW;
+            int g_hi = (32 * (h + 1) + GW - 1) / GW;
+            g_hi = g_hi < G ? g_hi : G;
+#pragma unroll 1
+            for (int g = g_lo; g < g_hi; ++g) {
+                const unsigned nib = __builtin_amdgcn_alignbit(nxt, cur, (unsigned)(g * GW - 32 * h)) & (unsigned)(GM - 1);
+                const volatile lds_f64* row = Tp + ((size_t)g * KT * GM + nib);
+#pragma unroll
+                for (int c0 = 0; c0 < KT; c0 += CH) {
+                    double tv[CH];
+#pragma unroll
+                    for (int j = 0; j < CH; ++j) tv[j] = row[(c0 + j) * GM];
+#pragma unroll
+                    for (int j = 0; j < CH; ++j) acc[c0 + j] = acc[c0 + j] + tv[j];
+                    if (CH < KT) __builtin_amdgcn_sched_barrier(0);  // keep the chunks apart
+                }
+            }
+        }
+        const double ownv = MINUS && seated ? own : neg_inf();
+        double mx = ownv;
+#pragma unroll
+        for (int k = 0; k < KT; ++k) mx = __builtin_fmax(mx, acc[k]);
+        double tot = 0.0;
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            tot = tot + expw_tab(acc[k] - mx, ET);
+            if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);  // two at a time: bounds the temporaries
+        }
+        if (MINUS) tot = tot + expw_tab(ownv - mx, ET);
+        const double ell = seated ? mx + log_(tot) : qnan();  // (the host refuses a state with an unseated row)
+        if (valid) {
+            if (a.ell) a.ell[i] = ell;
+            if (a.acc) loo_fold(a, i, ell, ET);
+        }
+        b0 = n0; b1 = n1; b2 = n2; b3 = n3;
+        z = zn;
+    }
+}
+
+// Any shape (the shapes k_resample_generic takes): tables gathered from global memory, the scores in a per-thread
+// scratch column scr[k * stride + thread], as there.  Same arithmetic and the same order of sums as k_loo.
+__global__ __launch_bounds__(256) void k_loo_generic(ChainParams p, LooArgs a, double* scr, int64_t stride) {
+    const bool has_minus = !explicit_params(p.mode);
+    const TableLayout L = layout_of(p, has_minus);
+    const int GM = L.M;
+    const double* const Tp = a.tab + L.tp();
+    const double* const Tm = a.tab + L.tm();
+    const double* const ET = a.tab + L.et();
+    const int P = p.P, G = p.G, K = p.K, Kc = p.Kc, KT = p.KT;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // < stride: the host sizes the grid
+    double* const my = scr + gid;
+    for (int64_t i = gid; i < a.N; i += (int64_t)gridDim.x * blockDim.x) {
+        const int z = has_minus ? a.z[i] : -1;
+        const bool seated = !has_minus || (unsigned)z < (unsigned)K;
+        const int zc = has_minus && seated ? z : 0;
+        double own = 0.0;
+        if (has_minus)
+            for (int g = 0; g < p.Gm; ++g)
+                own = own + Tm[((size_t)g * KT + zc) * kGroupMm + field_from_x(a.X, a.Xb, a.N, P, i, g, kGroupWm)];
+        const double ownv = has_minus && seated ? own : neg_inf();  // one more category, summed last, as in k_loo
+        double mx = ownv;
+        for (int k0 = 0; k0 < Kc; k0 += 16) {
+            double acc[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[j] = has_minus && k0 + j == z ? neg_inf() : 0.0;
+            for (int g = 0; g < G; ++g) {
+                const double* row = Tp + ((size_t)g * KT + k0) * GM + field_from_x(a.X, a.Xb, a.N, P, i, g, p.W);
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if (k0 + j < Kc) acc[j] = acc[j] + row[j * GM];
+            }
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (k0 + j < Kc) {
+                    my[(int64_t)(k0 + j) * stride] = acc[j];
+                    mx = __builtin_fmax(mx, acc[j]);
+                }
+        }
+        double tot = 0.0;
+        for (int k = 0; k < Kc; ++k) tot = tot + expw_tab(my[(int64_t)k * stride] - mx, ET);
+        if (has_minus) tot = tot + expw_tab(ownv - mx, ET);
+        const double ell = seated ? mx + log_(tot) : qnan();
+        if (a.ell) a.ell[i] = ell;
+        if (a.acc) loo_fold(a, i, ell, ET);
+    }
+}
+
+// empty accumulators: no state folded
+__global__ __launch_bounds__(256) void k_loo_reset(int64_t N, double* __restrict__ acc) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
+        acc[LOO_MAX * N + i] = neg_inf();
+        acc[LOO_SUM * N + i] = 0.0;
+        acc[LOO_MIN * N + i] = pos_inf();
+        acc[LOO_S1 * N + i] = 0.0;
+        acc[LOO_S2 * N + i] = 0.0;
+        acc[LOO_MEAN * N + i] = 0.0;
+        acc[LOO_M2 * N + i] = 0.0;
+    }
+}
+
+// The per-row outputs after n folded states, into a buffer of their own ([kLooOut][N]: log_cpo, ess, lppd, mean,
+// var); the accumulators are left as they are, so more sweeps may be folded afterwards.
+//   log_cpo = log n - logsumexp(-ell) = log n + MIN - log S1        ess = S1^2 / S2
+//   lppd    = MAX + log SUM - log n                                 var = M2 / (n - 1), NaN when n = 1
+__global__ __launch_bounds__(256) void k_loo_finish(int64_t N, int n, const double* __restrict__ acc,
+                                                    double* __restrict__ out) {
+    const double ln = log_((double)n);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
+        const double s1 = acc[LOO_S1 * N + i];
+        out[0 * N + i] = (ln + acc[LOO_MIN * N + i]) - log_(s1);
+        out[1 * N + i] = div_(s1 * s1, acc[LOO_S2 * N + i]);
+        out[2 * N + i] = (acc[LOO_MAX * N + i] + log_(acc[LOO_SUM * N + i])) - ln;
+        out[3 * N + i] = acc[LOO_MEAN * N + i];
+        out[4 * N + i] = n > 1 ? div_(acc[LOO_M2 * N + i], (double)(n - 1)) : qnan();
+    }
+}
+
+// The scalars, in an order fixed by N alone: 1024 partial sums (row i in partial i mod 1024, ascending), then a
+// binary tree.  One workgroup.  scal: lpml = sum log_cpo, min ess, sum lppd, p_waic = sum var,
+// elpd_waic = sum lppd - p_waic.
+__global__ __launch_bounds__(1024) void k_loo_reduce(int64_t N, const double* __restrict__ out, double* __restrict__ scal) {
+    __shared__ double sh[4][1024];
+    const int t = threadIdx.x;
+    double cpo = 0.0, lp = 0.0, vr = 0.0, es = pos_inf();
+    for (int64_t i = t; i < N; i += 1024) {
+        cpo = cpo + out[0 * N + i];
+        es = __builtin_fmin(es, out[1 * N + i]);
+        lp = lp + out[2 * N + i];
+        vr = vr + out[4 * N + i];
+    }
+    sh[0][t] = cpo; sh[1][t] = es; sh[2][t] = lp; sh[3][t] = vr;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if (t < s) {
+            sh[0][t] = sh[0][t] + sh[0][t + s];
+            sh[1][t] = __builtin_fmin(sh[1][t], sh[1][t + s]);
+            sh[2][t] = sh[2][t] + sh[2][t + s];
+            sh[3][t] = sh[3][t] + sh[3][t + s];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        scal[0] = sh[0][0]; scal[1] = sh[1][0]; scal[2] = sh[2][0]; scal[3] = sh[3][0];
+        scal[4] = sh[2][0] - sh[3][0];
+    }
+}
+
 // ---- self-check kernels ----------------------------------------------------------
 __global__ void k_test_math(int op, const double* in, const double* in2, double* out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -527,6 +527,71 @@ typedef struct bmm_partition_out {
 } bmm_partition_out;
 int bmm_set_partition_summary(const bmm_partition_out* out);
 
+/* ---- leave-one-out predictive of the fitted rows: LPML, WAIC ---------------------------
+ * For the state s after a kept sweep and a fitted row i with label z_i, ell[s, i] is the log density of x_i given
+ * everything else in the state:
+ *   collapsed, dp  row i is taken out of the statistics, Nk' = Nk - [k = z_i], S'_kd = S_kd - x_id [k = z_i], N - 1 fitted
+ *                  rows remain, and ell is the per-state predictive above of x_i for a chain fitted to those N - 1 rows:
+ *                    collapsed  log sum_k (Nk' + alpha/K)/(N - 1 + alpha) prod_d (beta + S'_kd)^x (gamma + Nk' - S'_kd)^(1-x) / (beta + gamma + Nk')
+ *                    dp         the same over the labels with Nk' > 0, weight Nk'/(N - 1 + alpha), plus the new cluster
+ *                               alpha/(N - 1 + alpha) prod_d beta^x gamma^(1-x) / (beta + gamma)
+ *                  with alpha_s the value the next sweep's conditional would use.  So a finite label that removing i has
+ *                  emptied, or that was empty, keeps its prior weight (alpha/K)/(N - 1 + alpha) and the prior Bernoulli
+ *                  terms (the model's term, not the sampler's "probability 0 for ever"); a DP row that sat alone has its
+ *                  own label unused and is scored by the other used labels and the new cluster; away from those cases
+ *                  ell is the log normaliser of the allocation conditional the sampler computes for row i at batch 1.
+ *   sb, full       ell = log sum_k pi_k prod_d theta_kd^x (1 - theta_kd)^(1-x): the predictive above with the fitted rows
+ *                  as the new rows.  The labels do not enter.
+ * Only the states of the other rows enter ell for the collapsed model, and
+ *   CPO_i^-1 = 1 / p(x_i | X_-i) = E[ 1 / p(x_i | X_-i, z_-i) | X ]      exactly:
+ *     p(z_-i | X) = p(z_-i | X_-i) p(x_i | X_-i, z_-i) / p(x_i | X_-i)                           (Bayes, x_i as the datum)
+ *     so sum_{z_-i} p(z_-i | X) / p(x_i | X_-i, z_-i) = sum_{z_-i} p(z_-i | X_-i) / p(x_i | X_-i)  (the factor cancels)
+ *     = 1 / p(x_i | X_-i)                                                                          (p(z_-i | X_-i) sums to 1),
+ * and z_-i of a draw of z | X is a draw of z_-i | X: the harmonic mean of exp(ell[s, i]) over the chain estimates CPO_i.
+ * (For the explicit samplers the same identity holds with (pi, theta) in the place of z_-i.)
+ * A state in which some row has no label -- a DP, stick-breaking or full chain before its first sweep -- is refused with
+ * BMM_E_STATE and the chain stays usable.  Per row, over the S' folded states:
+ *   log_cpo[i]  log S' - logsumexp_s(-ell)          ess[i]   exp(2 logsumexp(-ell) - logsumexp(-2 ell)), the effective
+ *   lppd[i]     logsumexp_s(ell) - log S'                    sample size of the harmonic-mean weights, in [1, S']
+ *   mean[i], var[i]  mean and sample variance (denominator S' - 1; NaN when S' = 1) of ell
+ * and the scalars lpml = sum_i log_cpo, min_ess, n_folded, and -- for the two explicit samplers only, where ell is a log
+ * likelihood -- p_waic = sum_i var, elpd_waic = sum_i lppd - p_waic (NaN for the counting samplers).  The sums over rows
+ * run in an order fixed by N: 1024 partial sums, row i in partial i mod 1024, ascending; then a binary tree.  A row is
+ * owned by one lane and nothing is atomic, so one seed gives the same bits twice.  Everything is enqueued on the chain's
+ * stream behind the sweep's last kernel: a folded sweep adds no synchronisation and no host-device copy, an armed chain
+ * that is not folding enqueues what an unarmed one does.  Not offered on a sharded chain, nor on the int32 layout of a
+ * shape the resident kernels take (it reads the bit planes). */
+typedef struct bmm_loo_out {
+    double* log_cpo;    /* N doubles each; any may be NULL */
+    double* ess;
+    double* lppd;
+    double* mean;
+    double* var;
+    double* lpml;       /* scalars; any may be NULL */
+    double* min_ess;
+    double* p_waic;
+    double* elpd_waic;
+    int* n_folded;
+    double* ell;        /* whole runs only: S x N doubles column-major like logdens, or NULL */
+} bmm_loo_out;
+/* resident chains: arm (allocates 12 doubles per fitted row and, for the counting samplers, the two table sets; arming an
+ * armed chain empties the accumulators) or disarm; needs the data */
+int bmm_chain_set_loo(bmm_chain* c, int on);
+/* ell of the current state, once: no sweep, accumulators untouched.  ell_out N doubles.  Waits. */
+int bmm_chain_loo_state(bmm_chain* c, double* ell_out);
+/* n more sweeps, each folded; ell_trace n x N column-major (then the call waits) or NULL (then it returns without
+ * waiting, as bmm_chain_sweeps).  BMM_E_ARG, naming the bytes, when the trace does not fit in device memory. */
+int bmm_chain_sweeps_loo(bmm_chain* c, int n, double* ell_trace);
+/* the summary over the states folded so far (out->ell is ignored); the accumulators stay, so more sweeps may follow */
+int bmm_chain_get_loo(bmm_chain* c, const bmm_loo_out* out);
+int bmm_chain_loo_reset(bmm_chain* c);
+/* For a run: armed per calling thread for the NEXT single-chain *_run* call of that thread (plain, _probs, _relabel,
+ * _predict) and disarmed when that call returns, whatever it returns, exactly as bmm_set_partition_summary; NULL
+ * disarms.  The struct is copied; its buffers must stay valid through that call.  Only kept sweeps (j >= burnin) are
+ * folded; without burn-in the first kept row of the traces is the starting state, not a sweep: that row of ell is NaN
+ * and is not folded.  bmm_multi_run does not take it and disarms it. */
+int bmm_set_loo_summary(const bmm_loo_out* out);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
