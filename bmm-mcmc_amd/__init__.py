@@ -414,10 +414,52 @@ def partition_plan(S, N, Kc, candidates=None, criterion="binder"):
     return dict(zip(_PT_PLAN_FIELDS, (int(v) for v in out)))
 
 
-def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None):
+# ---------------------------------------------------------------- split_merge=: Jain & Neal's move for the DP chain
+SPLIT_MERGE_SCANS = 5  # the default of split_merge_scans (DESIGN.md section 15 says where it comes from)
+_SM_FIELDS = ("split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped")
+
+
+class _SplitMergeStep(_C.Structure):  # bmm_split_merge_step
+    _fields_ = [("row_i", _C.c_int64), ("row_j", _C.c_int64), ("label_a", _C.c_int32), ("label_b", _C.c_int32),
+                ("kind", _C.c_int32), ("accepted", _C.c_int32), ("members", _C.c_int64), ("n_before", _C.c_int64 * 2),
+                ("n_after", _C.c_int64 * 2), ("log_prior", _C.c_double), ("log_lik", _C.c_double),
+                ("log_q", _C.c_double), ("log_u", _C.c_double), ("log_r", _C.c_double), ("sweep", _C.c_uint32),
+                ("move", _C.c_uint32), ("launch_side", _C.c_void_p), ("proposal_side", _C.c_void_p)]
+
+
+class _SplitMerge:
+    """split_merge= of gibbs_dp, checked before any device is touched and armed for exactly one run"""
+
+    def __init__(self, moves, scans):
+        self.moves, self.scans = int(moves), int(scans)
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_split_merge(_C.c_int(self.moves), _C.c_int(self.scans)))
+
+    def result(self):
+        out = (_C.c_int64 * 5)()
+        _capi.check(_capi.lib().bmm_last_split_merge_stats(out))
+        return dict(zip(_SM_FIELDS, (int(v) for v in out)))
+
+
+def _make_split_merge(split_merge, scans, chains):
+    moves = int(split_merge or 0)
+    scans = SPLIT_MERGE_SCANS if scans is None else int(scans)
+    if moves < 0 or scans < 0:
+        raise ValueError("split_merge and split_merge_scans must be >= 0")
+    if moves == 0:
+        return None
+    if int(chains) > 1:
+        raise ValueError("split_merge= is offered per chain (chains=1)")
+    return _SplitMerge(moves, scans)
+
+
+def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
+    if sm is not None:
+        sm.arm()
     if part is not None:
         part.arm()
     if loo is not None:
@@ -661,10 +703,13 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
 def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=None, relabel=False,
              burnrelabel=50, maxK=30, debug=False, *, seed=None, batch=None, device=0, chains=1, devices=None,
              stephens=None, newdata=None, predictive_trace=False, responsibilities=False, partition=None,
-             partition_stride=1, similarity_of=None, loo=False):
+             partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
-    gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column."""
+    gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
+    split-merge Metropolis-Hastings moves (Jain & Neal 2004, include/bmm_mcmc.h) at the start of every sweep from the
+    second, each with `split_merge_scans` intermediate restricted scans (default SPLIT_MERGE_SCANS); the result gains
+    `split_merge = {"split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped"}`.  Per chain."""
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, maxK = int(nsamples), int(maxK)
@@ -673,6 +718,12 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, maxK + 1, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     lo = _make_loo(loo, N, nsamples - burnin, chains, False)
+    sm = _make_split_merge(split_merge, split_merge_scans, chains)
+
+    def done(out):
+        if sm is not None:
+            out["split_merge"] = sm.result()
+        return out
     if int(chains) > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
@@ -691,8 +742,8 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                 _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
                 _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo)
-        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo)
+            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm)
+        return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((maxK, P, S), order="F")
@@ -703,12 +754,12 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo)
+        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
-        return _with_predictive(rl.finish(rc, out), pr, pt, lo)
+        return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
     _capi.check(rc)
-    return _with_predictive(out, pr, pt, lo)
+    return done(_with_predictive(out, pr, pt, lo))
 
 
 def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, burnin, relabel, burnrelabel, seed,
@@ -1041,6 +1092,45 @@ class Chain:
 
     def loo_reset(self):
         _capi.check(_capi.lib().bmm_chain_loo_reset(self._h))
+
+    # -- split-merge moves of a DP chain (include/bmm_mcmc.h)
+    def set_split_merge(self, moves_per_sweep, scans=SPLIT_MERGE_SCANS):
+        """`moves_per_sweep` moves at the start of every sweep from the second (0: off), `scans` intermediate scans each."""
+        _capi.check(_capi.lib().bmm_chain_set_split_merge(self._h, _C.c_int(int(moves_per_sweep)), _C.c_int(int(scans))))
+
+    def split_merge(self, n):
+        """n moves now, enqueued behind whatever the chain is doing."""
+        _capi.check(_capi.lib().bmm_chain_split_merge(self._h, _C.c_int(int(n))))
+
+    def split_merge_step(self, sides=False):
+        """One move, waited for; its diagnostics as a dict (labels 1-based, rows 0-based).  `sides=True` adds
+        "launch_side" and "proposal_side": one byte per row (0 / 1 a member's side, 2 / 3 the anchors, 255 outside)."""
+        s = _SplitMergeStep()
+        la = pr = None
+        if sides:
+            la, pr = _np.zeros(self.N, dtype=_np.uint8), _np.zeros(self.N, dtype=_np.uint8)
+            s.launch_side, s.proposal_side = la.ctypes.data, pr.ctypes.data
+        _capi.check(_capi.lib().bmm_chain_split_merge_step(self._h, _C.byref(s)))
+        out = {"rows": (int(s.row_i), int(s.row_j)), "labels": (int(s.label_a), int(s.label_b)),
+               "kind": ("split", "merge", "skipped")[s.kind], "accepted": bool(s.accepted), "members": int(s.members),
+               "n_before": (int(s.n_before[0]), int(s.n_before[1])), "n_after": (int(s.n_after[0]), int(s.n_after[1])),
+               "log_prior": s.log_prior, "log_lik": s.log_lik, "log_q": s.log_q, "log_u": s.log_u, "log_r": s.log_r,
+               "sweep": int(s.sweep), "move": int(s.move)}
+        if sides:
+            out["launch_side"], out["proposal_side"] = la, pr
+        return out
+
+    def split_merge_stats(self):
+        out = (_C.c_int64 * 5)()
+        _capi.check(_capi.lib().bmm_chain_split_merge_stats(self._h, out))
+        return dict(zip(_SM_FIELDS, (int(v) for v in out)))
+
+    def set_labels(self, z1):
+        """Replace the allocation of a seated DP chain between sweeps (1-based labels); Nk and S are recounted."""
+        z1 = _np.ascontiguousarray(z1, dtype=_np.int32)
+        if z1.shape != (self.N,):
+            raise ValueError("one label per observation")
+        _capi.check(_capi.lib().bmm_chain_set_labels(self._h, _capi.vp(z1)))
 
     def profile(self, every=1):
         """Time the resample launches of every `every`-th sweep with HIP events (0/False: off)."""

@@ -34,6 +34,8 @@ SYMBOLS = [
     "bmm_device_partition_distances", "bmm_device_psm", "bmm_device_partition_plan", "bmm_set_partition_summary",
     "bmm_chain_set_loo", "bmm_chain_loo_state", "bmm_chain_sweeps_loo", "bmm_chain_get_loo", "bmm_chain_loo_reset",
     "bmm_set_loo_summary",
+    "bmm_chain_set_split_merge", "bmm_chain_split_merge", "bmm_chain_split_merge_step", "bmm_chain_split_merge_stats",
+    "bmm_chain_set_labels", "bmm_set_split_merge", "bmm_last_split_merge_stats",
 ]
 
 

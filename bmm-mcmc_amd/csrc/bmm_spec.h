@@ -54,6 +54,7 @@ enum : uint32_t {
     kStreamAlphaEta = 5, // eta ~ Beta(alpha+1, N): first gamma (c0 = 0), second gamma (c0 = 1)
     kStreamAlphaG1 = 6,  // Gamma(a+K)
     kStreamAlphaG2 = 7,  // Gamma(a+K-1)
+    kStreamSplitMerge = 8,  // a split-merge move: c0 = move index, c1 = block counter, c2 = sweep (sm_move_draws)
 };
 
 // ---------------------------------------------------------------- bit helpers
@@ -145,6 +146,33 @@ BMM_HD uint32_t z_key(uint64_t seed, uint64_t i) {
 BMM_HD double z_uniform(uint64_t seed, uint64_t i, uint32_t sweep) {
     uint32_t a, b;
     philox2x32_10((uint32_t)i, sweep, z_key(seed, i), a, b);
+    return u52(a, b);
+}
+
+// The draws of split-merge move number `move` ahead of sweep `sweep` (include/bmm_mcmc.h "split-merge"), a pure
+// function of (seed, sweep, move): two Philox4x32 blocks of a stream of their own.  Block 0: the anchors, row i
+// uniform over N and row j uniform over the other N - 1; block 1: the uniform of the accept step and a 32-bit salt.
+// The members' uniforms are Philox2x32 at counter (row mod 2^32, 2^31 + scan) under the salt (with the high word of
+// the row folded in as z_key does): the sweeps' own uniforms have a counter word 1 below 2^31 (the sweep index), so
+// no (key, counter) pair of theirs is ever reused, whatever the salt.  Scan 0 is the launch state.
+struct SmDraws { int64_t i, j; double u; uint32_t salt; };
+BMM_HD SmDraws sm_move_draws(uint64_t seed, uint32_t sweep, uint32_t move, int64_t N) {
+    Stream st = make_stream(seed, move, sweep, kStreamSplitMerge);
+    const U4 r0 = st.next(), r1 = st.next();
+    SmDraws d;
+    d.i = (int64_t)(u01(r0.x, r0.y) * (double)N);
+    d.i = d.i > N - 1 ? N - 1 : d.i;
+    int64_t j = (int64_t)(u01(r0.z, r0.w) * (double)(N - 1));
+    j = j > N - 2 ? N - 2 : j;
+    d.j = j >= d.i ? j + 1 : j;
+    d.u = u01_open0(r1.x, r1.y);
+    d.salt = r1.z;
+    return d;
+}
+BMM_HD double sm_member_uniform(uint32_t salt, uint64_t i, uint32_t scan) {
+    const uint32_t h = (uint32_t)(i >> 32);
+    uint32_t a, b;
+    philox2x32_10((uint32_t)i, 0x80000000u | scan, salt ^ ((h << 16) | (h >> 16)), a, b);
     return u52(a, b);
 }
 
@@ -283,6 +311,28 @@ BMM_HD double expw_tab(double x, Tab T) {
     return ldexp_(fma_(t, q, t), k);
 }
 BMM_HD double expw_(double x) { return expw_tab(x, exp256_table()); }
+
+// ---------------------------------------------------------------- lgamma
+// log Gamma(x) for x > 0 (the split-merge move's arguments: a prior plus an integer, up to about 1e7).  The
+// argument is shifted up to y >= 8 by the recurrence, Gamma(x) = Gamma(y) / (x (x+1) ... (y-1)) with the product
+// (at most eight factors, below 4e5) in binary64, then Stirling's series in 1/y with eight Bernoulli terms (the
+// first one left out is 43867/(244188 y^17) < 8e-17 at y = 8) on log_.  Absolute error a few 1e-16 * max(1, |result|);
+// near the zeros at x = 1 and x = 2 the result is small and the error is not (tests/test_split_merge_ref.py
+// records the largest error found, in ulps of max(1, |result|)).
+BMM_HD double lgamma_(double x) {
+    double prod = 1.0, y = x;
+    while (y < 8.0) { prod = prod * y; y = y + 1.0; }
+    const double r = div_(1.0, y), r2 = r * r;
+    double s = fma_(r2, -2.9550653594771241e-02, 6.4102564102564100e-03);   // -3617/122400, 1/156
+    s = fma_(r2, s, -1.9175269175269176e-03);                                // -691/360360
+    s = fma_(r2, s, 8.4175084175084171e-04);                                 // 1/1188
+    s = fma_(r2, s, -5.9523809523809529e-04);                                // -1/1680
+    s = fma_(r2, s, 7.9365079365079365e-04);                                 // 1/1260
+    s = fma_(r2, s, -2.7777777777777779e-03);                                // -1/360
+    s = fma_(r2, s, 8.3333333333333329e-02);                                 // 1/12
+    const double stirling = (((y - 0.5) * log_(y) - y) + 9.1893853320467278e-01) + r * s;  // log(2 pi)/2
+    return stirling - log_(prod);
+}
 
 // ---------------------------------------------------------------- the draw, decided in binary32 where that is safe
 // The draw of z_n is ONE integer: cnt = #{k : u * tot >= cdf_k}, cdf_k the binary64 running sum of

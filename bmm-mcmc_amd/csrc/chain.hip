@@ -558,6 +558,17 @@ struct bmm_chain {
     int loo_from = 0;
     double* loo_trace = nullptr; // or [..][N] on the device: row j - loo_trace_base receives sweep j's ell
     int loo_trace_base = 0;
+    // split-merge moves: sm_moves > 0: that many moves at the start of every sweep from the
+    // second; the side bytes, the final scan's log probabilities, the statistic sets of one move ([sm_sets]), the
+    // move's cell and the five counters.  Moves are numbered within the sweep they precede (sm_tag, sm_ctr).
+    int sm_moves = 0, sm_scans = 0, sm_sets = 0;
+    uint8_t *dSmSide = nullptr, *dSmSideLaunch = nullptr;
+    double* dSmLq = nullptr;
+    int32_t* dSmStat = nullptr;
+    SmCell* dSmCell = nullptr;
+    long long* dSmCounters = nullptr;
+    int sm_tag = -1;
+    uint32_t sm_ctr = 0;
     int prof = 0;             // > 0: HIP events around the resample launches of every prof-th sweep
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
@@ -1067,6 +1078,70 @@ int sweep_end_folds(bmm_chain* c, int j) {
     return enqueue_loo(c, j, row, true);
 }
 
+// ---- split-merge moves ----
+int sm_refused(const bmm_chain* c) {
+    if (c->sharded) return set_err(BMM_E_STATE, "split-merge moves are not offered on a sharded chain");
+    if (c->p.mode != MODE_DP)
+        return set_err(BMM_E_UNSUPPORTED, "split-merge moves are offered for the DP sampler only (the finite sampler gives an "
+                       "emptied label probability 0 for ever: a different model from the one the move's ratio targets)");
+    if (!c->bits) return set_err(BMM_E_UNSUPPORTED, "split-merge moves read the bit planes: not offered on the int32 layout");
+    if (c->p.P > kSmMaxP) return set_err(BMM_E_UNSUPPORTED, "split-merge moves are offered up to %d features", kSmMaxP);
+    if (c->p.N < 2) return set_err(BMM_E_ARG, "a split-merge move needs two rows");
+    return BMM_OK;
+}
+int sm_seated(const bmm_chain* c) {
+    if (!c->started || c->sweep < 1) return set_err(BMM_E_STATE, "the chain has rows without a label: run a sweep first");
+    return BMM_OK;
+}
+// the buffers of the moves, for `scans` intermediate scans
+int sm_setup(bmm_chain* c, int scans) {
+    const size_t n = (size_t)c->p.N;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->dSmSide) {
+        HIP_TRY(hipMalloc(&c->dSmSide, n));
+        HIP_TRY(hipMalloc(&c->dSmSideLaunch, n));
+        HIP_TRY(hipMalloc(&c->dSmLq, n * sizeof(double)));
+        HIP_TRY(hipMalloc(&c->dSmCell, sizeof(SmCell)));
+        HIP_TRY(hipMalloc(&c->dSmCounters, 5 * sizeof(long long)));
+        HIP_TRY(hipMemsetAsync(c->dSmCounters, 0, 5 * sizeof(long long), c->stream));
+        HIP_TRY(hipMemsetAsync(c->dSmCell, 0, sizeof(SmCell), c->stream));
+    }
+    if (scans + 2 > c->sm_sets) {
+        HIP_TRY(hipStreamSynchronize(c->stream));  // moves enqueued earlier may still use the old sets
+        if (c->dSmStat) HIP_TRY(hipFree(c->dSmStat));
+        c->dSmStat = nullptr;
+        HIP_TRY(hipMalloc(&c->dSmStat, (size_t)(scans + 2) * 2 * (c->p.P + 1) * sizeof(int32_t)));
+        c->sm_sets = scans + 2;
+    }
+    c->sm_scans = scans;
+    return BMM_OK;
+}
+// one move on label row `z`, ahead of sweep `tag`, enqueued on the stream
+int enqueue_move(bmm_chain* c, int32_t* z, int tag, bool keep_launch) {
+    const ChainParams& p = c->p;
+    if (c->sm_tag != tag) { c->sm_tag = tag; c->sm_ctr = 0; }
+    SmArgs a{};
+    a.Xb = c->dXb; a.z = z; a.Nk = c->dNk; a.S = c->dS; a.alpha_ptr = c->dAlpha;
+    a.side = c->dSmSide; a.side_launch = keep_launch ? c->dSmSideLaunch : nullptr; a.lq = c->dSmLq;
+    a.stat = c->dSmStat; a.cell = c->dSmCell; a.counters = c->dSmCounters;
+    a.sweep = (uint32_t)tag; a.move = c->sm_ctr++; a.scans = c->sm_scans;
+    const size_t set_bytes = (size_t)2 * (p.P + 1) * sizeof(int32_t);
+    HIP_TRY(hipMemsetAsync(c->dSmStat, 0, (size_t)(c->sm_scans + 2) * set_bytes, c->stream));
+    const unsigned grid = (unsigned)((p.N + kSmThreads - 1) / kSmThreads);
+    hipLaunchKernelGGL(k_sm_launch, dim3(grid), dim3(kSmThreads), set_bytes, c->stream, p, a);
+    HIP_TRY(hipGetLastError());
+    const size_t scan_lds = (size_t)4 * p.P * sizeof(double) + set_bytes;
+    for (int t = 1; t <= c->sm_scans + 1; ++t) {
+        hipLaunchKernelGGL(k_sm_scan, dim3(grid), dim3(kSmThreads), scan_lds, c->stream, p, a, t, t == c->sm_scans + 1 ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_sm_decide, dim3(1), dim3(1024), 0, c->stream, p, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sm_commit, dim3(grid), dim3(kSmThreads), 0, c->stream, p, a);
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+
 // one sweep (index j >= 1) enqueued on the stream
 // phase 0: whole sweep; 1: z-resample only; 2: parameter draws and tables only (sharded chains)
 int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
@@ -1093,6 +1168,21 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
                            c->dPi, c->dTheta, 1, (uint32_t)j, th_tr, c->dTab, c->dAlpha, al_tr, c->dViable);
         HIP_TRY(hipGetLastError());
         return sweep_end_folds(c, j);
+    }
+    if (c->sm_moves > 0 && j >= 2 && phase == 0) {
+        // the armed split-merge moves, ahead of the sweep's first table build; a row of the trace stays as it was
+        // recorded (with the theta-hat of its sweep): the moves then work on a copy, which the sweep reads
+        int32_t* row = label_row(c, j - 1);
+        if (c->dTrace && j - 1 >= c->burnin) {
+            int32_t* const copy = c->dZ[(j - 1) & 1];
+            HIP_TRY(hipMemcpyAsync(copy, row, (size_t)p.N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+            row = copy;
+        }
+        zin = row;
+        for (int m = 0; m < c->sm_moves; ++m) {
+            const int rc = enqueue_move(c, row, j, false);
+            if (rc) return rc;
+        }
     }
     int64_t lo = 0;
     while (lo < p.N) {
@@ -1397,7 +1487,8 @@ void bmm_chain_destroy(bmm_chain* c) {
     dev_pool().put(c->device, c->arena, c->arena_bytes);  // the stream is idle (synchronised above)
     dev_pool().put(c->device, c->run_arena, c->run_arena_bytes);
     void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
-                    c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch};
+                    c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch, c->dSmSide, c->dSmSideLaunch, c->dSmLq, c->dSmStat, c->dSmCell,
+                    c->dSmCounters};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     chain_stream_release(c->device, c->stream, c->stream_kind);  // synchronised above
@@ -2242,6 +2333,127 @@ int bmm_chain_loo_reset(bmm_chain* c) {
 }
 
 // the outputs of a run that had the summary armed: S kept rows, the first `burnin ? 0 : 1` of them not folded
+// ---- split-merge moves ----
+int bmm_chain_set_split_merge(bmm_chain* c, int moves_per_sweep, int scans) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (moves_per_sweep < 0 || scans < 0 || scans > 4096) return set_err(BMM_E_ARG, "moves_per_sweep and scans must be >= 0 (scans at most 4096)");
+        if (moves_per_sweep == 0) { c->sm_moves = 0; return BMM_OK; }
+        int rc = sm_refused(c);
+        if (rc == BMM_OK) rc = sm_setup(c, scans);
+        if (rc) return rc;
+        c->sm_moves = moves_per_sweep;
+        return BMM_OK;
+    });
+}
+
+static int sm_ready(bmm_chain* c) {
+    if (!c) return set_err(BMM_E_ARG, "null chain");
+    int rc = sm_refused(c);
+    if (rc == BMM_OK) rc = sm_seated(c);
+    if (rc == BMM_OK && c->dTrace) rc = set_err(BMM_E_STATE, "not offered inside a run");
+    if (rc == BMM_OK && !c->dSmStat) rc = sm_setup(c, c->sm_scans);
+    return rc;
+}
+
+int bmm_chain_split_merge(bmm_chain* c, int n) {
+    return guarded([&]() -> int {
+        if (n < 0) return set_err(BMM_E_ARG, "n must be >= 0");
+        int rc = sm_ready(c);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        for (int t = 0; t < n; ++t) {
+            rc = enqueue_move(c, label_row(c, c->sweep), c->sweep + 1, false);
+            if (rc) return rc;
+        }
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_split_merge_step(bmm_chain* c, bmm_split_merge_step* out) {
+    return guarded([&]() -> int {
+        if (!out) return set_err(BMM_E_ARG, "null argument");
+        int rc = sm_ready(c);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        rc = enqueue_move(c, label_row(c, c->sweep), c->sweep + 1, true);
+        if (rc) return rc;
+        rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        SmCell h;
+        HIP_TRY(hipMemcpy(&h, c->dSmCell, sizeof h, hipMemcpyDeviceToHost));
+        out->row_i = h.row_i; out->row_j = h.row_j; out->label_a = h.label_a + 1; out->label_b = h.label_b + 1;
+        out->kind = h.kind; out->accepted = h.accepted; out->members = h.members;
+        for (int q = 0; q < 2; ++q) { out->n_before[q] = h.n_before[q]; out->n_after[q] = h.n_after[q]; }
+        out->log_prior = h.log_prior; out->log_lik = h.log_lik; out->log_q = h.log_q; out->log_u = h.log_u; out->log_r = h.log_r;
+        out->sweep = (uint32_t)(c->sweep + 1); out->move = c->sm_ctr - 1;
+        const size_t n = (size_t)c->p.N;
+        if (h.kind == SM_SKIPPED) {  // no launch state: every row outside
+            if (out->launch_side) std::memset(out->launch_side, 255, n);
+            if (out->proposal_side) std::memset(out->proposal_side, 255, n);
+            return BMM_OK;
+        }
+        if (out->launch_side) HIP_TRY(hipMemcpy(out->launch_side, c->dSmSideLaunch, n, hipMemcpyDeviceToHost));
+        if (out->proposal_side) HIP_TRY(hipMemcpy(out->proposal_side, c->dSmSide, n, hipMemcpyDeviceToHost));
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_split_merge_stats(bmm_chain* c, int64_t out[5]) {
+    if (!c || !out) return set_err(BMM_E_ARG, "null argument");
+    for (int q = 0; q < 5; ++q) out[q] = 0;
+    if (!c->dSmCounters) return BMM_OK;
+    int rc = bmm_chain_sync(c);
+    if (rc) return rc;
+    long long h[5];
+    HIP_TRY(hipMemcpy(h, c->dSmCounters, sizeof h, hipMemcpyDeviceToHost));
+    for (int q = 0; q < 5; ++q) out[q] = h[q];
+    return BMM_OK;
+}
+
+int bmm_chain_set_labels(bmm_chain* c, const int32_t* z1) {
+    return guarded([&]() -> int {
+        if (!c || !z1) return set_err(BMM_E_ARG, "null argument");
+        if (c->p.mode != MODE_DP) return set_err(BMM_E_UNSUPPORTED, "only a DP chain takes labels between sweeps");
+        if (c->sharded) return set_err(BMM_E_STATE, "not offered on a sharded chain");
+        int rc = sm_seated(c);
+        if (rc) return rc;
+        if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+        HIP_TRY(hipSetDevice(c->device));
+        const int64_t N = c->p.N;
+        const size_t K = (size_t)c->p.K, KP = K * c->p.P;
+        // uploaded as R holds them (1-based), checked and shifted on the device into the row the next sweep will
+        // overwrite; the chain changes only once they have passed
+        int32_t* const cur = label_row(c, c->sweep);
+        int32_t* const other = c->dZ[(c->sweep + 1) & 1];
+        DevBuf tmp, badbuf;
+        HIP_TRY(tmp.alloc((size_t)N * sizeof(int32_t)));
+        HIP_TRY(badbuf.alloc(sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(badbuf.p, 0xff, sizeof(unsigned long long), c->stream));
+        HIP_TRY(hipMemcpyAsync(tmp.p, z1, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        const int64_t nb = (N + 255) / 256;
+        const unsigned grid = (unsigned)(nb < 4096 ? nb : 4096);
+        hipLaunchKernelGGL(k_labels_from_r, dim3(grid), dim3(256), 0, c->stream, tmp.as<int32_t>(), N, c->p.K, other,
+                           badbuf.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        unsigned long long bad = 0;
+        HIP_TRY(hipMemcpyAsync(&bad, badbuf.p, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (bad != ~0ull) return set_err(BMM_E_ARG, "z[%lld] = %d outside 1..%d", (long long)bad, z1[bad], c->p.K);
+        HIP_TRY(hipMemcpyAsync(cur, other, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+        // the recount: nothing is pending between sweeps (k_count_sweep_end folded the last batch), so the statistics
+        // are rebuilt in place
+        HIP_TRY(hipMemsetAsync(c->dNk, 0, K * sizeof(int32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(c->dS, 0, KP * sizeof(int32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(c->dDNk, 0, K * kDeltaReps * sizeof(int32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(c->dDS, 0, KP * kDeltaReps * sizeof(int32_t), c->stream));
+        hipLaunchKernelGGL(k_count_labels_generic, dim3(grid), dim3(256), 0, c->stream, c->p, c->dX, c->dXb, cur, c->dNk, c->dS);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return BMM_OK;
+    });
+}
+
 static int loo_run_out(bmm_chain* c, const bmm_loo_out& o, const double* dtrace, int S, int burnin) {
     const int64_t N = c->p.N;
     const double nan = std::nan("");
@@ -2969,7 +3181,10 @@ thread_local PtArmed g_partition;
 // ... and the leave-one-out summary (bmm_set_loo_summary), armed and disarmed the same way
 struct LooArmed { bool on = false; bmm_loo_out o{}; };
 thread_local LooArmed g_loo;
-struct PtDisarm { ~PtDisarm() { g_partition.on = false; g_loo.on = false; } };
+struct SmArmed { int moves = 0, scans = 0; };
+thread_local SmArmed g_sm;
+thread_local int64_t g_sm_stats[5] = {0, 0, 0, 0, 0};
+struct PtDisarm { ~PtDisarm() { g_partition.on = false; g_loo.on = false; g_sm.moves = 0; } };
 // what a run checks of it before any device is touched
 int pt_check_armed(const bmm_partition_out& o, int S, int64_t N, int K) {
     if (!o.loss || !o.best || !o.n_used) return set_err(BMM_E_ARG, "partition: null buffer (loss, best, n_used)");
@@ -3228,7 +3443,13 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
                 c->loo_trace = ltrace.as<double>();
                 c->loo_trace_base = burnin;
             }
+            for (int64_t& v : g_sm_stats) v = 0;
+            if (g_sm.moves > 0) {  // the split-merge moves armed for this run (bmm_set_split_merge)
+                rc = bmm_chain_set_split_merge(c, g_sm.moves, g_sm.scans);
+                if (rc) return rc;
+            }
             rc = run_body(c, nsamples, io, hooks, rel);
+            if (rc == BMM_OK && g_sm.moves > 0) rc = bmm_chain_split_merge_stats(c, g_sm_stats);
             c->loo_fold = false;
             c->loo_trace = nullptr;
             if (loo) {
@@ -3577,6 +3798,18 @@ int bmm_device_stephens_plan(int64_t N, int K, int M, int64_t out[12]) {
 }
 
 // ---- clustering point estimate and posterior similarity: the stand-alone entry points ----
+int bmm_set_split_merge(int moves_per_sweep, int scans) {
+    if (moves_per_sweep < 0 || scans < 0 || scans > 4096) return set_err(BMM_E_ARG, "moves_per_sweep and scans must be >= 0 (scans at most 4096)");
+    g_sm.moves = moves_per_sweep;
+    g_sm.scans = scans;
+    return BMM_OK;
+}
+int bmm_last_split_merge_stats(int64_t out[5]) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    for (int q = 0; q < 5; ++q) out[q] = g_sm_stats[q];
+    return BMM_OK;
+}
+
 int bmm_set_loo_summary(const bmm_loo_out* out) {
     g_loo.on = out != nullptr;
     if (out) g_loo.o = *out;
@@ -3865,7 +4098,7 @@ int bmm_multi_selfcheck(int n_devices, const int* devices, int64_t words) {
 }
 
 int bmm_device_math(int device, int op, const double* in, const double* in2, double* out, int64_t n) {
-    if (!in || !out || n < 0 || op < 0 || op > 4) return set_err(BMM_E_ARG, "bad argument");
+    if (!in || !out || n < 0 || op < 0 || op > 5) return set_err(BMM_E_ARG, "bad argument");
     if (op == 2 && !in2) return set_err(BMM_E_ARG, "division needs in2");
     HIP_TRY(hipSetDevice(device));
     DevBuf bi, bi2, bo;
@@ -3876,8 +4109,11 @@ int bmm_device_math(int device, int op, const double* in, const double* in2, dou
         HIP_TRY(bi2.alloc(n * sizeof(double)));
         HIP_TRY(hipMemcpy(bi2.p, in2, n * sizeof(double), hipMemcpyHostToDevice));
     }
-    hipLaunchKernelGGL(k_test_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, bi.as<double>(),
-                       bi2.as<double>(), bo.as<double>(), n);
+    if (op == 5)
+        hipLaunchKernelGGL(k_test_lgamma, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, bi.as<double>(), bo.as<double>(), n);
+    else
+        hipLaunchKernelGGL(k_test_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, bi.as<double>(),
+                           bi2.as<double>(), bo.as<double>(), n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, bo.p, n * sizeof(double), hipMemcpyDeviceToHost));
     return BMM_OK;

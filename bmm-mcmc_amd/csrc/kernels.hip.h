@@ -2685,4 +2685,296 @@ __global__ __launch_bounds__(256) void k_pt_psm(const L* __restrict__ g, int S, 
             }
 }
 
+// ---- split-merge moves of the DP chain (include/bmm_mcmc.h "split-merge moves") ----------
+// One move = k_sm_launch, `scans` + 1 launches of k_sm_scan, k_sm_decide, k_sm_commit, stream-ordered; the host
+// never reads anything back.  The two labels of the move are its sides 0 and 1.  One byte per row: its side (0 / 1)
+// for a member, 2 + side for the two anchors, kSmOut for every other row.  The statistics of the two sides after
+// the launch state (set 0) and after scan t (set t) live in `stat`, a set being {n_0, S_0[P], n_1, S_1[P]} int32:
+// scan t reads set t - 1, frozen, and adds into set t, which the host zeroed when it enqueued the move.  The last
+// set (scans + 1) is the proposal of a split.  A workgroup holds 256 consecutive rows, one per lane.
+constexpr int kSmThreads = 256;
+constexpr int kSmMaxP = 1024;  // the per-feature terms (32 bytes a feature) and the histogram stay below 64 KiB of LDS
+constexpr uint8_t kSmOut = 255;
+enum : int { SM_SPLIT = 0, SM_MERGE = 1, SM_SKIPPED = 2 };
+struct SmCell {
+    long long row_i, row_j, members, n_before[2], n_after[2];
+    int32_t label_a, label_b, kind, accepted;
+    uint32_t salt, pad;
+    double log_prior, log_lik, log_q, log_u, log_r;
+};
+struct SmArgs {
+    const uint32_t* Xb;
+    int32_t* z;              // the label row the move works on, in place
+    int32_t *Nk, *S;         // the chain's statistics, nothing pending
+    const double* alpha_ptr;
+    uint8_t *side, *side_launch;  // side_launch: a copy of the launch state for the caller, or null
+    double* lq;              // [N]: the final scan's log probability per row, 0 outside the members
+    int32_t* stat;           // [scans + 2] sets
+    SmCell* cell;
+    long long* counters;     // proposed / accepted splits, proposed / accepted merges, skipped
+    uint32_t sweep, move;
+    int scans;
+};
+__device__ __forceinline__ size_t sm_set(int P) { return (size_t)2 * (P + 1); }
+
+// The rows of one wave into the histogram {n_0, S_0[P], n_1, S_1[P]} of a workgroup: a ballot per feature, one
+// LDS atomic per feature, side and wave.  Uniform over the wave.
+__device__ __forceinline__ void sm_count_wave(bool counted, int sd, const uint32_t* __restrict__ Xb, int64_t N, int P,
+                                              int64_t r, int32_t* hist, int lane) {
+    const unsigned long long any = __ballot(counted);
+    if (!any) return;
+    const unsigned long long m1 = __ballot(counted && sd == 1), m0 = any & ~m1;
+    if (lane == 0) {
+        if (m0) atomicAdd(&hist[0], (int)__popcll(m0));
+        if (m1) atomicAdd(&hist[P + 1], (int)__popcll(m1));
+    }
+    const int W = (P + 31) >> 5;
+    for (int w = 0; w < W; ++w) {
+        const uint32_t bits = counted ? Xb[(int64_t)w * N + r] : 0u;
+        const int nd = P - w * 32 < 32 ? P - w * 32 : 32;
+        for (int t = 0; t < nd; ++t) {
+            const unsigned long long b = __ballot(((bits >> t) & 1u) != 0);
+            if (lane == t) {
+                const int c0 = (int)__popcll(b & m0), c1 = (int)__popcll(b & m1);
+                if (c0) atomicAdd(&hist[1 + w * 32 + t], c0);
+                if (c1) atomicAdd(&hist[P + 2 + w * 32 + t], c1);
+            }
+        }
+    }
+}
+__device__ __forceinline__ void sm_flush(const int32_t* hist, int P, int32_t* set, int tid) {
+    for (int i = tid; i < 2 * (P + 1); i += kSmThreads) {
+        const int32_t v = hist[i];
+        if (v != 0) atomicAdd(&set[i], v);
+    }
+}
+
+// The pair, the two labels and the kind of the move (every workgroup derives them; workgroup 0 records them), then
+// the launch state: anchor i on side 0, anchor j on side 1, every other row of the two labels on either side with
+// probability 1/2 from its own uniform, whatever its current label.
+__global__ __launch_bounds__(kSmThreads) void k_sm_launch(ChainParams p, SmArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int32_t* const hist = reinterpret_cast<int32_t*>(smem);
+    __shared__ int sh_free, sh_la, sh_lb, sh_kind;
+    __shared__ long long sh_i, sh_j;
+    __shared__ uint32_t sh_salt;
+    const int P = p.P, K = p.K, tid = threadIdx.x, lane = tid & 63;
+    const int64_t N = p.N;
+    for (int i = tid; i < 2 * (P + 1); i += kSmThreads) hist[i] = 0;
+    if (tid == 0) sh_free = K;
+    __syncthreads();
+    for (int k = tid; k < K; k += kSmThreads)
+        if (a.Nk[k] == 0) atomicMin(&sh_free, k);
+    __syncthreads();
+    if (tid == 0) {
+        const SmDraws dr = sm_move_draws(p.seed, a.sweep, a.move, N);
+        const int la = a.z[dr.i], zj = a.z[dr.j];
+        const int kind = la != zj ? SM_MERGE : (sh_free < K ? SM_SPLIT : SM_SKIPPED);
+        const int lb = kind == SM_MERGE ? zj : sh_free;
+        sh_i = dr.i; sh_j = dr.j; sh_la = la; sh_lb = lb; sh_kind = kind; sh_salt = dr.salt;
+        if (blockIdx.x == 0) {
+            SmCell* c = a.cell;
+            c->row_i = dr.i; c->row_j = dr.j; c->label_a = la; c->label_b = lb; c->kind = kind; c->salt = dr.salt;
+            c->accepted = 0; c->members = 0;
+            c->n_before[0] = a.Nk[la]; c->n_before[1] = kind == SM_MERGE ? a.Nk[lb] : 0;
+            c->n_after[0] = c->n_after[1] = 0;
+            c->log_u = log_(dr.u);
+            c->log_prior = c->log_lik = c->log_q = c->log_r = 0.0;
+        }
+    }
+    __syncthreads();
+    const int kind = sh_kind, la = sh_la, lb = sh_lb;
+    if (kind == SM_SKIPPED) return;
+    const int64_t r = (int64_t)blockIdx.x * kSmThreads + tid;
+    int sd = kSmOut;
+    if (r < N) {
+        const int zr = a.z[r];
+        if (zr == la || (kind == SM_MERGE && zr == lb)) {
+            if (r == sh_i) sd = 2;
+            else if (r == sh_j) sd = 3;
+            else sd = sm_member_uniform(sh_salt, (uint64_t)(p.obs0 + r), 0u) < 0.5 ? 0 : 1;
+        }
+        a.side[r] = (uint8_t)sd;
+        if (a.side_launch) a.side_launch[r] = (uint8_t)sd;
+    }
+    sm_count_wave(sd != kSmOut, sd & 1, a.Xb, N, P, r, hist, lane);
+    __syncthreads();
+    sm_flush(hist, P, a.stat, tid);
+}
+
+// log probabilities of the two sides from diff = log w_0 - log w_1
+__device__ __forceinline__ void sm_side_logp(double diff, double& lp0, double& lp1) {
+    const bool pos = diff > 0.0;
+    const double l = -log_(1.0 + exp_(pos ? -diff : diff));  // the likelier side
+    lp0 = pos ? l : l + diff;
+    lp1 = pos ? l - diff : l;
+}
+
+// Restricted scan t (1 .. scans + 1; the last one is `final`): every member is redrawn between the two sides at
+// once against set t - 1 with its own contribution removed exactly, w_c = (n_c - [own]) prod_d (the Beta-Bernoulli
+// predictive of side c without the row).  The per-feature terms are differences D[d][own][x] = log term of side 0
+// - log term of side 1 (own side "minus self", other side plain), built once per workgroup; a member adds them in
+// feature order onto base[own] = log(n_0 - [own = 0]) - log(n_1 - [own = 1]).  The final scan of a split is drawn
+// like the others and records the log probability of the side drawn; the final scan of a merge draws nothing and
+// records the log probability of the side that is the row's current label.
+__global__ __launch_bounds__(kSmThreads) void k_sm_scan(ChainParams p, SmArgs a, int t, int final) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    const int P = p.P, tid = threadIdx.x, lane = tid & 63;
+    const int64_t N = p.N;
+    double* const D = reinterpret_cast<double*>(smem);                // [P][2][2]
+    int32_t* const hist = reinterpret_cast<int32_t*>(D + 4 * (size_t)P);
+    __shared__ double base[2];
+    const int kind = a.cell->kind;
+    if (kind == SM_SKIPPED) return;
+    const bool score_only = final && kind == SM_MERGE;
+    const int64_t r = (int64_t)blockIdx.x * kSmThreads + tid;
+    const int sd = r < N ? a.side[r] : kSmOut;
+    const bool member = sd < 2, counted = sd != kSmOut;
+    if (final && r < N && !member) a.lq[r] = 0.0;
+    if (!__syncthreads_or(counted)) return;
+    const int32_t* const in = a.stat + (size_t)(t - 1) * sm_set(P);
+    const int32_t n0 = in[0], n1 = in[P + 1];
+    const double bg = p.beta + p.gamma;
+    for (int idx = tid; idx < 4 * P; idx += kSmThreads) {
+        const int d = idx >> 2, own = (idx >> 1) & 1, x = idx & 1;
+        const int32_t s0 = in[1 + d], s1 = in[P + 2 + d];
+        const int64_t nm = (own ? n1 : n0) - 1, sm = own ? s1 : s0, np = own ? n0 : n1, sp = own ? s0 : s1;
+        const double denm = log_(bg + (double)nm), denp = log_(bg + (double)np);
+        // (a member with x = 1 is one of the sm rows, one with x = 0 one of the nm + 1 - sm: the other entries are never read)
+        double m = 0.0;
+        if (x) { if (sm >= 1) m = term_x1(p.beta, sm - 1, denm); }
+        else if (sm <= nm) m = term_x0(p.gamma, nm, sm, denm);
+        const double pl = x ? term_x1(p.beta, sp, denp) : term_x0(p.gamma, np, sp, denp);
+        D[idx] = own ? pl - m : m - pl;
+    }
+    for (int i = tid; i < 2 * (P + 1); i += kSmThreads) hist[i] = 0;
+    if (tid < 2) base[tid] = log_((double)(n0 - (tid == 0))) - log_((double)(n1 - (tid == 1)));
+    __syncthreads();
+    int ns = sd & 1;
+    if (member) {
+        const int own = sd;
+        double acc = base[own];
+        const int W = (P + 31) >> 5;
+        for (int w = 0; w < W; ++w) {
+            const uint32_t bits = a.Xb[(int64_t)w * N + r];
+            const int nd = P - w * 32 < 32 ? P - w * 32 : 32;
+            for (int q = 0; q < nd; ++q) {
+                const double4 e = *reinterpret_cast<const double4*>(D + 4 * (size_t)(w * 32 + q));  // one address for the wave
+                const bool x = (bits >> q) & 1u;
+                acc = acc + (own ? (x ? e.w : e.z) : (x ? e.y : e.x));
+            }
+        }
+        double lp0, lp1;
+        sm_side_logp(acc, lp0, lp1);
+        if (score_only) {
+            a.lq[r] = a.z[r] == a.cell->label_a ? lp0 : lp1;
+        } else {
+            const double u = sm_member_uniform(a.cell->salt, (uint64_t)(p.obs0 + r), (uint32_t)t);
+            ns = u < exp_(lp0) ? 0 : 1;
+            a.side[r] = (uint8_t)ns;
+            if (final) a.lq[r] = ns ? lp1 : lp0;
+        }
+    }
+    if (score_only) return;
+    sm_count_wave(counted, ns, a.Xb, N, P, r, hist, lane);
+    __syncthreads();
+    sm_flush(hist, P, a.stat + (size_t)t * sm_set(P), tid);
+}
+
+// One workgroup: log q in an order fixed by N (1024 partial sums, row i in partial i mod 1024, ascending, then a
+// binary tree, as k_loo_reduce), the marginal-likelihood ratio the same way over the features, the prior ratio, the
+// decision and the counters.
+__device__ __forceinline__ double sm_pair(double beta, double gamma, int64_t n, int64_t s) {
+    return lgamma_(beta + (double)s) + lgamma_((gamma + (double)n) - (double)s);
+}
+__global__ __launch_bounds__(1024) void k_sm_decide(ChainParams p, SmArgs a) {
+    __shared__ double sh[2][1024];
+    const int t = threadIdx.x, P = p.P;
+    SmCell* const c = a.cell;
+    const int kind = c->kind;
+    if (kind == SM_SKIPPED) {
+        if (t == 0) a.counters[4] += 1;
+        return;
+    }
+    const int la = c->label_a, lb = c->label_b;
+    const int32_t* const fin = a.stat + (size_t)(a.scans + 1) * sm_set(P);
+    const bool split = kind == SM_SPLIT;
+    const int64_t no0 = a.Nk[la], no1 = split ? 0 : a.Nk[lb];
+    const int64_t nn0 = split ? fin[0] : no0 + no1, nn1 = split ? fin[P + 1] : 0;
+    double lq = 0.0, ll = 0.0;
+    for (int64_t i = t; i < p.N; i += 1024) lq = lq + a.lq[i];
+    for (int d = t; d < P; d += 1024) {
+        const int64_t so0 = a.S[(size_t)la * P + d], so1 = split ? 0 : a.S[(size_t)lb * P + d];
+        const int64_t sn0 = split ? fin[1 + d] : so0 + so1, sn1 = split ? fin[P + 2 + d] : 0;
+        double term;
+        if (split) term = (sm_pair(p.beta, p.gamma, nn0, sn0) + sm_pair(p.beta, p.gamma, nn1, sn1)) - sm_pair(p.beta, p.gamma, no0, so0);
+        else term = sm_pair(p.beta, p.gamma, nn0, sn0) - (sm_pair(p.beta, p.gamma, no0, so0) + sm_pair(p.beta, p.gamma, no1, so1));
+        ll = ll + term;
+    }
+    sh[0][t] = lq; sh[1][t] = ll;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if (t < s) { sh[0][t] = sh[0][t] + sh[0][t + s]; sh[1][t] = sh[1][t] + sh[1][t + s]; }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    const double bg = p.beta + p.gamma, la_ = log_(*a.alpha_ptr);
+    const double c0 = (lgamma_(bg) - lgamma_(p.beta)) - lgamma_(p.gamma);
+    const double log_q = sh[0][0];
+    double cst, log_prior;
+    if (split) {
+        cst = ((c0 - lgamma_(bg + (double)nn0)) - lgamma_(bg + (double)nn1)) + lgamma_(bg + (double)no0);
+        log_prior = ((la_ + lgamma_((double)nn0)) + lgamma_((double)nn1)) - lgamma_((double)no0);
+    } else {
+        cst = ((lgamma_(bg + (double)no0) + lgamma_(bg + (double)no1)) - lgamma_(bg + (double)nn0)) - c0;
+        log_prior = ((lgamma_((double)nn0) - lgamma_((double)no0)) - lgamma_((double)no1)) - la_;
+    }
+    const double log_lik = sh[1][0] + (double)P * cst;
+    const double log_r = split ? (log_prior + log_lik) - log_q : (log_prior + log_lik) + log_q;
+    const int acc = c->log_u < log_r ? 1 : 0;
+    c->log_prior = log_prior; c->log_lik = log_lik; c->log_q = log_q; c->log_r = log_r; c->accepted = acc;
+    c->n_after[0] = nn0; c->n_after[1] = nn1;
+    const int32_t* const first = a.stat;
+    c->members = (long long)first[0] + first[P + 1] - 2;
+    a.counters[split ? 0 : 2] += 1;
+    if (acc) a.counters[split ? 1 : 3] += 1;
+}
+
+// An accepted move: the labels and the exact integer statistics of the two labels.  A rejected or skipped one:
+// nothing, so the host never waits inside a move.
+__global__ __launch_bounds__(kSmThreads) void k_sm_commit(ChainParams p, SmArgs a) {
+    const SmCell* const c = a.cell;
+    if (!c->accepted) return;
+    const int P = p.P, tid = threadIdx.x, la = c->label_a, lb = c->label_b;
+    const bool split = c->kind == SM_SPLIT;
+    const int lo = la < lb ? la : lb, hi = la < lb ? lb : la;
+    const int64_t r = (int64_t)blockIdx.x * kSmThreads + tid;
+    if (r < p.N) {
+        if (split) {
+            const int sd = a.side[r];
+            if (sd == 1 || sd == 3) a.z[r] = lb;
+        } else if (a.z[r] == hi) {
+            a.z[r] = lo;
+        }
+    }
+    if (blockIdx.x != 0) return;
+    const int32_t* const fin = a.stat + (size_t)(a.scans + 1) * sm_set(P);
+    for (int idx = tid; idx <= P; idx += kSmThreads) {
+        int32_t* const A = idx == 0 ? a.Nk + la : a.S + (size_t)la * P + (idx - 1);
+        int32_t* const B = idx == 0 ? a.Nk + lb : a.S + (size_t)lb * P + (idx - 1);
+        if (split) {
+            *A = fin[idx]; *B = fin[P + 1 + idx];
+        } else {
+            const int32_t s = *A + *B;
+            *(la < lb ? A : B) = s;
+            *(la < lb ? B : A) = 0;
+        }
+    }
+}
+
+__global__ void k_test_lgamma(const double* in, double* out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = lgamma_(in[i]);
+}
+
 }  // namespace bmm

@@ -592,8 +592,85 @@ int bmm_chain_loo_reset(bmm_chain* c);
  * and is not folded.  bmm_multi_run does not take it and disarms it. */
 int bmm_set_loo_summary(const bmm_loo_out* out);
 
+/* ---- split-merge moves of the DP chain --------------------------------------------------
+ * One-row-at-a-time Gibbs cannot move a block of rows between clusters; the split-merge Metropolis-Hastings move of
+ * Jain & Neal (2004) can, and its accept step makes it exact whatever the parallelism of the proposal.  The model is
+ * the DP Beta-Bernoulli mixture of the predictive section above, alpha the value the next sweep would use.  The move
+ * applies to a DP chain whose rows are all seated, between sweeps (then no statistic deltas are pending: the end of a
+ * sweep folds them).  THE MOVE, number m ahead of sweep j (tests/split_merge_ref.py restates it in NumPy):
+ *   1. two distinct rows i, j uniformly; a = z_i, b = z_j.
+ *   2. a == b: a split candidate; the second label is f, the smallest label with Nk = 0 below maxK; with none the
+ *      move is SKIPPED (and counted).           3. a != b: a merge candidate; the two labels are a and b.
+ *   4. members: the rows carrying either label, minus the two anchors.
+ *   5. launch state: i on side 0 (the first label), j on side 1 (the second); every member on either side with
+ *      probability 1/2 from its own uniform (side 0 iff u < 1/2), whatever its current label.
+ *   6. `scans` >= 0 intermediate restricted scans: every member is redrawn between the two sides AT ONCE, scored
+ *      against the two sides' statistics frozen at the start of that scan with its own contribution removed exactly,
+ *      w_c = (n_c - [own]) prod_d (Beta-Bernoulli predictive of side c without the row) -- the terms k_resample uses
+ *      for a used label; n_c - [own] >= 1 because of the anchors.  Side 0 iff u < w_0 / (w_0 + w_1).
+ *   7. final scan: for a split of the same form, and drawn; log q = the sum over members of the log probability of
+ *      the side drawn.  For a merge nothing is drawn; log q = the sum over members of the log probability, from the
+ *      launch state (after the intermediate scans), of the side that is the member's current label.
+ *   8. L(c) = sum_d [lgamma(beta + S_cd) + lgamma(gamma + n_c - S_cd) - lgamma(beta + gamma + n_c)]
+ *             + P [lgamma(beta + gamma) - lgamma(beta) - lgamma(gamma)];
+ *      split: log_prior = log alpha + lgamma(n_a') + lgamma(n_f') - lgamma(n_a), log_lik = L(a') + L(f') - L(a),
+ *             log r = log_prior + log_lik - log q;
+ *      merge: log_prior = -log alpha + lgamma(n_a + n_b) - lgamma(n_a) - lgamma(n_b), log_lik = L(a u b) - L(a) - L(b),
+ *             log r = log_prior + log_lik + log q.
+ *   9. accept iff log u < log r.
+ *  10. commit: a split writes the proposed labels; a merge gives every row of the larger label the smaller one; Nk
+ *      and S of the two labels are replaced by their exact integer values.  (The DP bookkeeping keeps nothing else
+ *      derived from Nk on the device: the sweep finds its free label in the table image it builds per batch.)
+ * Random streams, a pure function of (seed, sweep j, move m, row): the pair, u and a 32-bit salt from two
+ * Philox4x32 blocks of stream 8 (c0 = m, c2 = j); a member's uniform of scan t (0 = launch) is Philox2x32 at counter
+ * (row, 2^31 + t) keyed by the salt.  The sweeps' own row uniforms have a second counter word below 2^31, so none of
+ * their (key, counter) pairs is reused.  Moves enqueued between sweeps j - 1 and j count on from the armed ones.
+ * Determinism: log q is summed in an order fixed by N (1024 partial sums, row i in partial i mod 1024, ascending,
+ * then a binary tree); the integer statistics use atomics; one seed gives the same bits twice.  lgamma is the
+ * spec's lgamma_ (bmm_spec.h), the same bits on host and device.
+ * The reference's DP sweep uses, for beta != gamma, a new-cluster term that is not the model's (see the predictive
+ * section); the move targets the model.  A DP chain is created with beta == gamma only, where the two agree.
+ * Refused: a sampler other than DP with BMM_E_UNSUPPORTED (the finite collapsed sampler gives an emptied label
+ * probability 0 for ever, so its chain targets a different model from the one this ratio is for; the explicit
+ * samplers carry pi and theta, which the move does not update), the int32 layout and P above 1024 with
+ * BMM_E_UNSUPPORTED, an unseated or sharded chain with BMM_E_STATE. */
+#define BMM_SM_SPLIT 0
+#define BMM_SM_MERGE 1
+#define BMM_SM_SKIPPED 2
+#define BMM_SM_OUTSIDE 255 /* side byte of a row outside the two labels; 0 / 1 a member's side, 2 / 3 anchors i / j */
+typedef struct bmm_split_merge_step {
+    int64_t row_i, row_j;      /* 0-based */
+    int32_t label_a, label_b;  /* 1-based: the first and the second label */
+    int32_t kind;              /* BMM_SM_* */
+    int32_t accepted;
+    int64_t members;
+    int64_t n_before[2];       /* sizes of the two labels before the move (split: n_a, 0) */
+    int64_t n_after[2];        /* ... as proposed (split: n_a', n_f'; merge: n_a + n_b, 0) */
+    double log_prior, log_lik, log_q, log_u, log_r;
+    uint32_t sweep, move;      /* what keyed the move's streams */
+    uint8_t* launch_side;      /* in: room for N side bytes, or NULL; the launch state */
+    uint8_t* proposal_side;    /* in: the same; the state the final scan drew (split) or scored from (merge) */
+} bmm_split_merge_step;
+/* moves_per_sweep moves at the start of every sweep from the second, before its first table build (so the theta-hat
+ * and the label row a sweep records belong together); 0 turns them off.  An unarmed chain enqueues what it always did. */
+int bmm_chain_set_split_merge(bmm_chain* c, int moves_per_sweep, int scans);
+/* n moves now, with the scans last set (returns without waiting) */
+int bmm_chain_split_merge(bmm_chain* c, int n);
+/* one move, then waits; fills *out (set launch_side / proposal_side first) */
+int bmm_chain_split_merge_step(bmm_chain* c, bmm_split_merge_step* out);
+/* proposed splits, accepted splits, proposed merges, accepted merges, skipped.  Waits. */
+int bmm_chain_split_merge_stats(bmm_chain* c, int64_t out[5]);
+/* Replaces the allocation of a seated DP chain between sweeps (1-based labels, validated on the device, BMM_E_ARG
+ * naming the first bad row and the chain unchanged) and recounts Nk and S: warm starts.  Waits. */
+int bmm_chain_set_labels(bmm_chain* c, const int32_t* z1);
+/* For a run: armed per calling thread for the NEXT single-chain *_run* call of that thread and disarmed when it
+ * returns, as bmm_set_loo_summary; moves_per_sweep = 0 disarms.  The run's five counts are read afterwards with
+ * bmm_last_split_merge_stats.  bmm_multi_run does not take it and disarms it. */
+int bmm_set_split_merge(int moves_per_sweep, int scans);
+int bmm_last_split_merge_stats(int64_t out[5]);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
- * 4 the draw's weight exponential expw; elementwise over n doubles, evaluated on the GPU with the
+ * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
 int bmm_device_math(int device, int op, const double* in, const double* in2, double* out, int64_t n);
 /* out[i] = the spec's variate number `kind` (0 gamma(shape p), 1 beta(p,q), 2 update_alpha
