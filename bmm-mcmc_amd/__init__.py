@@ -454,12 +454,61 @@ def _make_split_merge(split_merge, scans, chains):
     return _SplitMerge(moves, scans)
 
 
-def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None):
+# ---------------------------------------------------------------- select_features=: noise features (White, Wyse & Murphy 2016)
+class _FeatureStep(_C.Structure):  # bmm_feature_step
+    _fields_ = [("lambda_", _C.c_void_p), ("p", _C.c_void_p), ("u", _C.c_void_p), ("gamma", _C.c_void_p),
+                ("sweep", _C.c_uint32)]
+
+
+class _FeatureOut(_C.Structure):  # bmm_feature_out
+    _fields_ = [("rho", _C.c_double), ("gamma", _C.c_void_p), ("inclusion", _C.c_void_p), ("inclusion_rb", _C.c_void_p),
+                ("n_selected", _C.c_void_p), ("n_folded", _C.POINTER(_C.c_int))]
+
+
+class _Features:
+    """select_features= of gibbs_collapsed / gibbs_dp, checked before any device is touched and armed for one run"""
+
+    def __init__(self, rho, P, S):
+        self.rho = float(rho)
+        self.gamma = _np.zeros((S, P), dtype=_np.uint8)
+        self.inclusion, self.inclusion_rb = _np.zeros(P), _np.zeros(P)
+        self.n_selected = _np.zeros(S, dtype=_np.int32)
+        self.n = _C.c_int(0)
+        self.s = _FeatureOut(self.rho, _capi.vp(self.gamma), _capi.vp(self.inclusion), _capi.vp(self.inclusion_rb),
+                             _capi.vp(self.n_selected), _C.pointer(self.n))
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_feature_select(_C.byref(self.s)))
+
+    def result(self):
+        return {"gamma": self.gamma, "inclusion": self.inclusion, "inclusion_rb": self.inclusion_rb,
+                "n_selected": self.n_selected, "rho": self.rho, "n_folded": self.n.value}
+
+
+def _make_features(select_features, rho, P, S, chains, beta, gamma, dp, newdata, loo, split_merge=0):
+    if not select_features:
+        return None
+    rho = float(rho)
+    if not 0.0 < rho < 1.0:
+        raise ValueError("rho must lie strictly inside (0, 1): it is the prior probability that a feature clusters")
+    if int(chains) > 1:
+        raise ValueError("select_features= is offered per chain (chains=1)")
+    if dp and float(beta) != float(gamma):
+        raise ValueError("select_features= on the DP sampler needs beta == gamma: its new-cluster term is the model's only then")
+    if newdata is not None or (loo is not None and loo is not False) or int(split_merge or 0) > 0:
+        raise ValueError("select_features= is not offered together with newdata=, loo= or split_merge=: their tables and "
+                         "ratios are written for the all-features model")
+    return _Features(rho, P, S)
+
+
+def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
     if sm is not None:
         sm.arm()
+    if fs is not None:
+        fs.arm()
     if part is not None:
         part.arm()
     if loo is not None:
@@ -618,7 +667,8 @@ def _multi(sampler, X, chains, devices, z0s, pi0s, th0s, nsamples, K, alpha, bet
 def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
                     relabel=False, burnrelabel=50, debug=False, *, seed=None, batch=None, device=0,
                     initial_K=None, chains=1, devices=None, stephens=None, newdata=None, predictive_trace=False,
-                    responsibilities=False, partition=None, partition_stride=1, similarity_of=None, loo=False):
+                    responsibilities=False, partition=None, partition_stride=1, similarity_of=None, loo=False,
+                    select_features=False, rho=0.5):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -647,6 +697,13 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     ess the effective sample size of each row's harmonic mean (between 1 and n_folded; small values flag an
     unreliable log_cpo).  gibbs_stickbreaking and gibbs_full add "p_waic" and "elpd_waic".  `loo="trace"` adds "ell",
     the (S, N) trace of the per-state values (without burn-in its first row is NaN).  Not offered with chains > 1.
+    `select_features=True`: every feature gets an inclusion indicator with prior Bernoulli(`rho`), redrawn on the device
+    behind every sweep (White, Wyse & Murphy 2016; include/bmm_mcmc.h "feature selection"): an
+    excluded feature is noise, one rate shared by every row, and drops out of the allocation.  The result gains
+    `features = {"gamma": (S, P) uint8, "inclusion": (P,), "inclusion_rb": (P,), "n_selected": (S,), "rho", "n_folded"}`:
+    the indicators per kept sweep, their mean, the mean of their conditional probabilities (less noisy) and the number
+    of included features per sweep; "n_folded" is the number of kept sweeps behind the two means (the starting row of a
+    run without burn-in is not one).  Per chain; not with newdata=, loo= (or split_merge= on gibbs_dp).
     """
     X = _capi.as_x(data)
     N, P = X.shape
@@ -656,7 +713,13 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     chains = int(chains)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
+    fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, False, newdata, loo)
     lo = _make_loo(loo, N, nsamples - burnin, chains, False)
+
+    def done(out):
+        if fs is not None:
+            out["features"] = fs.result()
+        return out
     if chains > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
@@ -681,8 +744,8 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
                 _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo)
-        return _with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo)
+            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs)
+        return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((K, P, S), order="F")
@@ -692,24 +755,26 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
             _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
-        return _with_predictive(rl.finish(rc, out), pr, pt, lo)
+        return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
     _capi.check(rc)
-    return _with_predictive(out, pr, pt, lo)
+    return done(_with_predictive(out, pr, pt, lo))
 
 
 def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=None, relabel=False,
              burnrelabel=50, maxK=30, debug=False, *, seed=None, batch=None, device=0, chains=1, devices=None,
              stephens=None, newdata=None, predictive_trace=False, responsibilities=False, partition=None,
-             partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None):
+             partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None,
+             select_features=False, rho=0.5):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
     split-merge Metropolis-Hastings moves (Jain & Neal 2004, include/bmm_mcmc.h) at the start of every sweep from the
     second, each with `split_merge_scans` intermediate restricted scans (default SPLIT_MERGE_SCANS); the result gains
-    `split_merge = {"split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped"}`.  Per chain."""
+    `split_merge = {"split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped"}`.  Per chain.
+    `select_features`, `rho`: as gibbs_collapsed (needs beta == gamma; not with split_merge=)."""
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, maxK = int(nsamples), int(maxK)
@@ -718,11 +783,14 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, maxK + 1, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     lo = _make_loo(loo, N, nsamples - burnin, chains, False)
+    fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, True, newdata, loo, split_merge)
     sm = _make_split_merge(split_merge, split_merge_scans, chains)
 
     def done(out):
         if sm is not None:
             out["split_merge"] = sm.result()
+        if fs is not None:
+            out["features"] = fs.result()
         return out
     if int(chains) > 1:
         if relabel:
@@ -742,7 +810,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                 _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
                 _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm)
+            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
@@ -754,7 +822,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm)
+        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1131,6 +1199,48 @@ class Chain:
         if z1.shape != (self.N,):
             raise ValueError("one label per observation")
         _capi.check(_capi.lib().bmm_chain_set_labels(self._h, _capi.vp(z1)))
+
+    # -- feature selection (include/bmm_mcmc.h "feature selection")
+    def set_feature_select(self, on=True, rho=0.5):
+        """a gamma-step behind every sweep from now on (on=False: no more steps, the mask stays)"""
+        _capi.check(_capi.lib().bmm_chain_set_feature_select(self._h, _C.c_int(1 if on else 0), _C.c_double(float(rho))))
+
+    def set_features(self, gamma):
+        """the inclusion mask, between sweeps: P values in {0, 1}"""
+        g = _np.ascontiguousarray(gamma)
+        if g.shape != (self.P,):
+            raise ValueError("one indicator per feature")
+        if not _np.all((g == 0) | (g == 1)):
+            raise ValueError("indicators are 0 or 1")
+        g = g.astype(_np.uint8)
+        _capi.check(_capi.lib().bmm_chain_set_features(self._h, _capi.vp(g)))
+
+    def features(self):
+        g = _np.zeros(self.P, dtype=_np.uint8)
+        _capi.check(_capi.lib().bmm_chain_get_features(self._h, _capi.vp(g)))
+        return g
+
+    def feature_step(self):
+        """the last gamma-step: {"lambda", "p", "u", "gamma", "sweep"}"""
+        lam, pr, u = _np.zeros(self.P), _np.zeros(self.P), _np.zeros(self.P)
+        g = _np.zeros(self.P, dtype=_np.uint8)
+        s = _FeatureStep(_capi.vp(lam), _capi.vp(pr), _capi.vp(u), _capi.vp(g), 0)
+        _capi.check(_capi.lib().bmm_chain_feature_step(self._h, _C.byref(s)))
+        return {"lambda": lam, "p": pr, "u": u, "gamma": g, "sweep": int(s.sweep)}
+
+    def sweeps_features(self, n):
+        """n more sweeps of an armed chain; returns the (n, P) indicators after each"""
+        out = _np.zeros((int(n), self.P), dtype=_np.uint8)
+        _capi.check(_capi.lib().bmm_chain_sweeps_features(self._h, _C.c_int(int(n)), _capi.vp(out)))
+        return out
+
+    def feature_summary(self):
+        inc, rb, n = _np.zeros(self.P), _np.zeros(self.P), _C.c_int(0)
+        _capi.check(_capi.lib().bmm_chain_get_feature_summary(self._h, _capi.vp(inc), _capi.vp(rb), _C.byref(n)))
+        return {"inclusion": inc, "inclusion_rb": rb, "n_folded": n.value}
+
+    def feature_reset(self):
+        _capi.check(_capi.lib().bmm_chain_feature_reset(self._h))
 
     def profile(self, every=1):
         """Time the resample launches of every `every`-th sweep with HIP events (0/False: off)."""

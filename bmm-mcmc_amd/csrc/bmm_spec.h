@@ -55,6 +55,7 @@ enum : uint32_t {
     kStreamAlphaG1 = 6,  // Gamma(a+K)
     kStreamAlphaG2 = 7,  // Gamma(a+K-1)
     kStreamSplitMerge = 8,  // a split-merge move: c0 = move index, c1 = block counter, c2 = sweep (sm_move_draws)
+    kStreamFeatureSelect = 9,  // the inclusion indicator of feature d after sweep j: c0 = d, c1 = block counter, c2 = j (fs_uniform)
 };
 
 // ---------------------------------------------------------------- bit helpers
@@ -174,6 +175,14 @@ BMM_HD double sm_member_uniform(uint32_t salt, uint64_t i, uint32_t scan) {
     uint32_t a, b;
     philox2x32_10((uint32_t)i, 0x80000000u | scan, salt ^ ((h << 16) | (h >> 16)), a, b);
     return u52(a, b);
+}
+
+// The uniform that decides the inclusion indicator of feature d behind sweep `sweep` (include/bmm_mcmc.h "feature
+// selection"): the first block of a stream of its own, so it shares no (key, counter) pair with any other draw.
+BMM_HD double fs_uniform(uint64_t seed, uint32_t d, uint32_t sweep) {
+    Stream st = make_stream(seed, d, sweep, kStreamFeatureSelect);
+    const U4 r = st.next();
+    return u01(r.x, r.y);
 }
 
 // ---------------------------------------------------------------- log / exp

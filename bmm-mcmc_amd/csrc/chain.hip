@@ -569,6 +569,19 @@ struct bmm_chain {
     long long* dSmCounters = nullptr;
     int sm_tag = -1;
     uint32_t sm_ctr = 0;
+    // feature selection: fs_mask: the table builds read the inclusion mask (set once a mask
+    // was given or the step armed, and for good: the kernel choice then leaves out the forms that build their own
+    // tables); fs_on: a gamma-step behind every sweep end.  One block holds the mask words, the indicator bytes, the
+    // step record [3][P] and the two accumulators; steps of sweeps j >= fs_from are folded.
+    bool fs_mask = false, fs_on = false;
+    double fs_rho = 0.5, fs_logit = 0.0;
+    char* dFsBlock = nullptr;
+    uint32_t *dFsMask = nullptr, *dFsCount = nullptr;
+    uint8_t* dFsGamma = nullptr;
+    double *dFsRec = nullptr, *dFsProb = nullptr;
+    int fs_folded = 0, fs_from = 0, fs_last = -1;  // fs_last: the sweep of the last step, -1 none yet
+    uint8_t* fs_trace = nullptr;  // or [..][P] on the device: row j - fs_trace_base receives sweep j's indicators
+    int fs_trace_base = 0;
     int prof = 0;             // > 0: HIP events around the resample launches of every prof-th sweep
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
@@ -999,8 +1012,12 @@ int launch_reduce_deltas(bmm_chain* c) {
 }
 
 int launch_count_tables(bmm_chain* c) {
-    hipLaunchKernelGGL(k_count_tables, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
-                       c->dDNk, c->dDS, c->dAlpha, c->dTab);
+    if (c->fs_mask)  // feature selection: excluded features are written as zeros
+        hipLaunchKernelGGL(k_count_tables<true>, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
+                           c->dDNk, c->dDS, c->dAlpha, c->dTab, (const uint32_t*)c->dFsMask);
+    else
+        hipLaunchKernelGGL(k_count_tables<false>, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
+                           c->dDNk, c->dDS, c->dAlpha, c->dTab, (const uint32_t*)nullptr);
     HIP_TRY(hipGetLastError());
     return BMM_OK;
 }
@@ -1078,12 +1095,20 @@ int sweep_end_folds(bmm_chain* c, int j) {
     return enqueue_loo(c, j, row, true);
 }
 
+// what the predictive, the leave-one-out summary and the split-merge moves answer a chain with a feature mask
+// (DESIGN.md section 16): their tables and ratios are those of the model in which every feature clusters
+int fs_mask_refuses(const char* what) {
+    return set_err(BMM_E_UNSUPPORTED, "%s is written for the model in which every feature clusters: not offered on a chain "
+                   "with a feature mask (feature selection)", what);
+}
+
 // ---- split-merge moves ----
 int sm_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_STATE, "split-merge moves are not offered on a sharded chain");
     if (c->p.mode != MODE_DP)
         return set_err(BMM_E_UNSUPPORTED, "split-merge moves are offered for the DP sampler only (the finite sampler gives an "
                        "emptied label probability 0 for ever: a different model from the one the move's ratio targets)");
+    if (c->fs_mask) return fs_mask_refuses("the split-merge ratio");
     if (!c->bits) return set_err(BMM_E_UNSUPPORTED, "split-merge moves read the bit planes: not offered on the int32 layout");
     if (c->p.P > kSmMaxP) return set_err(BMM_E_UNSUPPORTED, "split-merge moves are offered up to %d features", kSmMaxP);
     if (c->p.N < 2) return set_err(BMM_E_ARG, "a split-merge move needs two rows");
@@ -1139,6 +1164,22 @@ int enqueue_move(bmm_chain* c, int32_t* z, int tag, bool keep_launch) {
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_sm_commit, dim3(grid), dim3(kSmThreads), 0, c->stream, p, a);
     HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+
+// ---- feature selection ----
+// the gamma-step behind the end of sweep j, stream-ordered: no host wait
+int enqueue_fs_gamma(bmm_chain* c, int j) {
+    const ChainParams& p = c->p;
+    FsArgs a{};
+    a.Nk = c->dNk; a.S = c->dS; a.mask = c->dFsMask; a.gamma = c->dFsGamma; a.rec = c->dFsRec;
+    a.gamma_row = c->fs_trace && j >= c->fs_trace_base ? c->fs_trace + (size_t)(j - c->fs_trace_base) * (size_t)p.P : nullptr;
+    a.incl_count = c->dFsCount; a.incl_prob = c->dFsProb; a.logit_rho = c->fs_logit; a.sweep = (uint32_t)j;
+    a.fold = j >= c->fs_from ? 1 : 0;
+    hipLaunchKernelGGL(k_fs_gamma, dim3((unsigned)((p.P + 31) / 32)), dim3(kFsThreads), 0, c->stream, p, a);
+    HIP_TRY(hipGetLastError());
+    if (a.fold) c->fs_folded++;
+    c->fs_last = j;
     return BMM_OK;
 }
 
@@ -1203,6 +1244,10 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
     hipLaunchKernelGGL(k_count_sweep_end, dim3(1), dim3(1024), 0, c->stream, p, c->dNk, c->dS, c->dDNk,
                        c->dDS, c->dAlpha, (uint32_t)j, th_tr, al_tr, nk_tr);
     HIP_TRY(hipGetLastError());
+    if (c->fs_on) {  // the gamma-step, from the counts the sweep end has just folded; sweep j + 1 reads its mask
+        const int rc = enqueue_fs_gamma(c, j);
+        if (rc) return rc;
+    }
     return sweep_end_folds(c, j);
 }
 
@@ -1217,7 +1262,7 @@ struct KernelPlan {
     bool named_size = false;  // form[0] has its workgroup size from BMM_DEBUG_THREADS (stage_width)
 };
 KernelPlan plan_kernel(const ChainParams& p, bool bits, int minus, int64_t batch, int num_cus, bool shares_device,
-                       size_t lds_bytes_base, const DebugSwitches& d) {
+                       size_t lds_bytes_base, const DebugSwitches& d, bool masked = false) {
     const bool alt = p.W != kGroupW;  // the narrower groups: default-sized kernels only
     KernelForm f{p.KT, threads_for(p.KT, bits), minus, bits, 1, false, p.W, false};
     KernelPlan plan;
@@ -1263,8 +1308,9 @@ KernelPlan plan_kernel(const ChainParams& p, bool bits, int minus, int64_t batch
     // shape is bound by launches then, and this drops k_count_tables from every batch (BASELINE config 2)
     f.self = true;
     const size_t lds = (lds_bytes_base + 7) / 8 * 8 + self_scratch_doubles(p.K, p.KT, p.P) * sizeof(double);  // scratch behind the image
+    // (not for a chain with a feature mask: build_tables_self knows no mask, k_count_tables<true> does)
     if (BMM_SELF_TABLES && bits && minus == 1 && !shares_device && self_tables_fit(p.mode, p.K, p.P, 256) && !d.noself &&
-        instantiated(f, false) && lds <= kLdsMax)
+        !masked && instantiated(f, false) && lds <= kLdsMax)
         offer(f, lds);
     return plan;
 }
@@ -1274,7 +1320,7 @@ int tier_of(const bmm_chain* c) { return explicit_params(c->p.mode) ? 0 : (c->mi
 // The chain's resident kernel, set up for launching: the last form of the plan that the runtime takes.
 int pick_kernel(bmm_chain* c) {
     const KernelPlan plan = plan_kernel(c->p, c->bits, tier_of(c), c->batch, c->num_cus, c->shares_device, c->lds_bytes_base,
-                                        DebugSwitches{});
+                                        DebugSwitches{}, c->fs_mask);
     hipError_t e = hipSetDevice(c->device);
     for (int i = 0; i < plan.n; ++i) {
         const KernelForm& f = plan.form[i];
@@ -1488,7 +1534,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     dev_pool().put(c->device, c->run_arena, c->run_arena_bytes);
     void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
                     c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch, c->dSmSide, c->dSmSideLaunch, c->dSmLq, c->dSmStat, c->dSmCell,
-                    c->dSmCounters};
+                    c->dSmCounters, c->dFsBlock};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     chain_stream_release(c->device, c->stream, c->stream_kind);  // synchronised above
@@ -1915,6 +1961,7 @@ int bmm_chain_kernel_form(const bmm_chain* c, int* lanes_per_observation, int* b
 // ---- posterior predictive of new rows ----
 static int pred_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the predictive density is not offered on a sharded chain");
+    if (c->fs_mask) return fs_mask_refuses("the predictive density");
     return BMM_OK;
 }
 static int pred_reset(bmm_chain* c) {
@@ -2134,6 +2181,7 @@ int bmm_chain_predict_reset(bmm_chain* c) {
 // ---- leave-one-out predictive of the fitted rows ----
 static int loo_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the leave-one-out predictive is not offered on a sharded chain");
+    if (c->fs_mask) return fs_mask_refuses("the leave-one-out predictive");
     return BMM_OK;
 }
 static int loo_armed(const bmm_chain* c) {
@@ -2451,6 +2499,181 @@ int bmm_chain_set_labels(bmm_chain* c, const int32_t* z1) {
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(c->stream));
         return BMM_OK;
+    });
+}
+
+// ---- feature selection ----
+// who may carry a mask: the two counting samplers, whole (not sharded), with rows that have or will get seats
+static int fs_refused(const bmm_chain* c) {
+    if (!c) return set_err(BMM_E_ARG, "null chain");
+    if (c->sharded) return set_err(BMM_E_STATE, "feature selection is not offered on a sharded chain");
+    if (explicit_params(c->p.mode))
+        return set_err(BMM_E_UNSUPPORTED, "feature selection is offered for the collapsed and DP samplers only: the stick-breaking and "
+                       "full samplers carry theta, which the collapsed indicator step integrates out");
+    // (a DP chain has beta == gamma: bmm_chain_create makes no other; a run armed for one that has not is refused in run_chain)
+    if (c->predM > 0) return set_err(BMM_E_UNSUPPORTED, "feature selection is not offered together with newdata: the predictive tables are written for the all-features model");
+    if (c->loo_on) return set_err(BMM_E_UNSUPPORTED, "feature selection is not offered together with the leave-one-out summary: its tables are written for the all-features model");
+    if (c->sm_moves > 0) return set_err(BMM_E_UNSUPPORTED, "feature selection is not offered together with split-merge moves: their ratio is written for the all-features model");
+    if (!c->have_data) return set_err(BMM_E_STATE, "the chain has no rows to seat: set the data first");
+    if (c->p.mode == MODE_COLLAPSED && !c->have_init) return set_err(BMM_E_STATE, "the chain's rows have no labels: set the initial labels first");
+    return BMM_OK;
+}
+// the block behind a mask, the mask all ones; the kernel choice is made again without the table-building forms
+static int fs_setup(bmm_chain* c) {
+    if (c->fs_mask) return BMM_OK;
+    const size_t P = (size_t)c->p.P, W = (P + 31) / 32;
+    HIP_TRY(hipSetDevice(c->device));
+    Carver a{nullptr};
+    auto carve = [&](Carver& v) {
+        c->dFsRec = v.take<double>(3 * P);
+        c->dFsProb = v.take<double>(P);
+        c->dFsMask = v.take<uint32_t>(W);
+        c->dFsCount = v.take<uint32_t>(P);
+        c->dFsGamma = v.take<uint8_t>(P);
+    };
+    carve(a);
+    const size_t bytes = a.used;
+    if (!c->dFsBlock) HIP_TRY(hipMalloc(&c->dFsBlock, bytes));  // (kept by a call that failed further down: not allocated twice)
+    Carver real{c->dFsBlock};
+    carve(real);
+    std::vector<uint32_t> ones(W, 0xffffffffu);
+    if (P % 32) ones[W - 1] = (1u << (P % 32)) - 1u;
+    HIP_TRY(hipMemsetAsync(c->dFsBlock, 0, bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(c->dFsGamma, 1, P, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->dFsMask, ones.data(), W * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // `ones` goes out of scope
+    c->fs_mask = true;
+    c->fs_folded = 0;
+    c->fs_last = -1;
+    return c->generic ? BMM_OK : pick_kernel(c);
+}
+static int fs_reset(bmm_chain* c) {
+    c->fs_folded = 0;
+    HIP_TRY(hipMemsetAsync(c->dFsCount, 0, (size_t)c->p.P * sizeof(uint32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(c->dFsProb, 0, (size_t)c->p.P * sizeof(double), c->stream));
+    return BMM_OK;
+}
+
+int bmm_chain_set_feature_select(bmm_chain* c, int on, double rho) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (!on) { c->fs_on = false; return BMM_OK; }  // the mask stays as it is
+        if (!(rho > 0.0 && rho < 1.0)) return set_err(BMM_E_ARG, "rho must lie strictly inside (0, 1): it is the prior probability that a feature clusters");
+        int rc = fs_refused(c);
+        if (rc == BMM_OK) rc = fs_setup(c);
+        if (rc == BMM_OK) rc = fs_reset(c);
+        if (rc) return rc;
+        c->fs_rho = rho;
+        c->fs_logit = log_(rho) - log_(1.0 - rho);
+        c->fs_from = 0;
+        c->fs_on = true;
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_set_features(bmm_chain* c, const uint8_t* gamma) {
+    return guarded([&]() -> int {
+        if (!c || !gamma) return set_err(BMM_E_ARG, "null argument");
+        int rc = fs_refused(c);
+        if (rc) return rc;
+        if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+        const int P = c->p.P, W = (P + 31) / 32;
+        std::vector<uint32_t> words((size_t)W, 0u);
+        std::vector<uint8_t> bytes((size_t)P);
+        for (int d = 0; d < P; ++d) {
+            if (gamma[d] > 1) return set_err(BMM_E_ARG, "gamma[%d] = %d is neither 0 nor 1", d, (int)gamma[d]);
+            bytes[d] = gamma[d];
+            words[d >> 5] |= (uint32_t)gamma[d] << (d & 31);
+        }
+        rc = fs_setup(c);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(c->dFsMask, words.data(), (size_t)W * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dFsGamma, bytes.data(), (size_t)P, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_get_features(bmm_chain* c, uint8_t* gamma) {
+    return guarded([&]() -> int {
+        if (!c || !gamma) return set_err(BMM_E_ARG, "null argument");
+        if (!c->fs_mask) { std::memset(gamma, 1, (size_t)c->p.P); return BMM_OK; }  // every feature clusters
+        int rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(gamma, c->dFsGamma, (size_t)c->p.P, hipMemcpyDeviceToHost));
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_feature_step(bmm_chain* c, bmm_feature_step* out) {
+    return guarded([&]() -> int {
+        if (!c || !out) return set_err(BMM_E_ARG, "null argument");
+        if (!c->fs_mask || c->fs_last < 0) return set_err(BMM_E_STATE, "no indicator step has run yet (bmm_chain_set_feature_select, then a sweep)");
+        int rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        const size_t P = (size_t)c->p.P;
+        if (out->lambda) HIP_TRY(hipMemcpy(out->lambda, c->dFsRec, P * sizeof(double), hipMemcpyDeviceToHost));
+        if (out->p) HIP_TRY(hipMemcpy(out->p, c->dFsRec + P, P * sizeof(double), hipMemcpyDeviceToHost));
+        if (out->u) HIP_TRY(hipMemcpy(out->u, c->dFsRec + 2 * P, P * sizeof(double), hipMemcpyDeviceToHost));
+        if (out->gamma) HIP_TRY(hipMemcpy(out->gamma, c->dFsGamma, P, hipMemcpyDeviceToHost));
+        out->sweep = (uint32_t)c->fs_last;
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_sweeps_features(bmm_chain* c, int n, uint8_t* gamma_trace) {
+    return guarded([&]() -> int {
+        if (!c || !gamma_trace) return set_err(BMM_E_ARG, "null argument");
+        if (n < 0) return set_err(BMM_E_ARG, "n must be >= 0");
+        if (!c->fs_on) return set_err(BMM_E_STATE, "feature selection is not armed (bmm_chain_set_feature_select)");
+        if (n == 0) return BMM_OK;
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t bytes = (size_t)n * (size_t)c->p.P;
+        DevBuf tr;
+        HIP_TRY(tr.alloc(bytes));
+        c->fs_trace = tr.as<uint8_t>();
+        c->fs_trace_base = c->sweep + 1;
+        int rc = bmm_chain_sweeps(c, n);
+        c->fs_trace = nullptr;
+        if (rc == BMM_OK) {
+            hipError_t e = hipMemcpyAsync(gamma_trace, tr.p, bytes, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) rc = set_err(BMM_E_HIP, "copying the indicator trace failed: %s", hipGetErrorString(e));
+        } else {
+            (void)hipStreamSynchronize(c->stream);  // before the trace may go
+        }
+        return rc;
+    });
+}
+
+int bmm_chain_get_feature_summary(bmm_chain* c, double* inclusion, double* inclusion_rb, int* n_folded) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (!c->fs_mask) return set_err(BMM_E_STATE, "feature selection was never armed on this chain (bmm_chain_set_feature_select)");
+        int rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        const size_t P = (size_t)c->p.P;
+        const double n = (double)c->fs_folded;  // 0: NaN
+        if (inclusion) {
+            std::vector<uint32_t> cnt(P);
+            HIP_TRY(hipMemcpy(cnt.data(), c->dFsCount, P * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (size_t d = 0; d < P; ++d) inclusion[d] = (double)cnt[d] / n;
+        }
+        if (inclusion_rb) {
+            HIP_TRY(hipMemcpy(inclusion_rb, c->dFsProb, P * sizeof(double), hipMemcpyDeviceToHost));
+            for (size_t d = 0; d < P; ++d) inclusion_rb[d] = inclusion_rb[d] / n;
+        }
+        if (n_folded) *n_folded = c->fs_folded;
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_feature_reset(bmm_chain* c) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (!c->fs_mask) return BMM_OK;
+        HIP_TRY(hipSetDevice(c->device));
+        return fs_reset(c);
     });
 }
 
@@ -3184,7 +3407,10 @@ thread_local LooArmed g_loo;
 struct SmArmed { int moves = 0, scans = 0; };
 thread_local SmArmed g_sm;
 thread_local int64_t g_sm_stats[5] = {0, 0, 0, 0, 0};
-struct PtDisarm { ~PtDisarm() { g_partition.on = false; g_loo.on = false; g_sm.moves = 0; } };
+// ... and feature selection (bmm_set_feature_select)
+struct FsArmed { bool on = false; bmm_feature_out o{}; };
+thread_local FsArmed g_fs;
+struct PtDisarm { ~PtDisarm() { g_partition.on = false; g_loo.on = false; g_sm.moves = 0; g_fs.on = false; } };
 // what a run checks of it before any device is touched
 int pt_check_armed(const bmm_partition_out& o, int S, int64_t N, int K) {
     if (!o.loss || !o.best || !o.n_used) return set_err(BMM_E_ARG, "partition: null buffer (loss, best, n_used)");
@@ -3368,6 +3594,19 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             if (M > 0 && !Xnew) return set_err(BMM_E_ARG, "Xnew is null");
             if (M > 0 && !pred->lppd) return set_err(BMM_E_ARG, "null buffer: lppd");
         }
+        if (g_fs.on) {  // refused before any device is touched
+            const bmm_feature_out& o = g_fs.o;
+            if (explicit_params(sampler))
+                return set_err(BMM_E_UNSUPPORTED, "feature selection is offered for the collapsed and DP samplers only: the stick-breaking and "
+                               "full samplers carry theta, which the collapsed indicator step integrates out");
+            if (sampler == BMM_SAMPLER_DP && beta != gamma)
+                return set_err(BMM_E_UNSUPPORTED, "feature selection on the DP sampler needs beta == gamma: its new-cluster term is the model's only then");
+            if ((pred && M > 0) || g_loo.on || g_sm.moves > 0)
+                return set_err(BMM_E_UNSUPPORTED, "feature selection is not offered together with newdata, the leave-one-out summary or split-merge "
+                               "moves: their tables and ratios are written for the all-features model");
+            if (!(o.rho > 0.0 && o.rho < 1.0)) return set_err(BMM_E_ARG, "rho must lie strictly inside (0, 1): it is the prior probability that a feature clusters");
+            if (!o.gamma || !o.inclusion || !o.inclusion_rb || !o.n_selected) return set_err(BMM_E_ARG, "feature selection: null buffer");
+        }
         if (rel) {  // refused before any device is touched
             if (!rel->permutations || !rel->z_original || !rel->theta_original) return set_err(BMM_E_ARG, "null buffer");
             if (burnin < 2 || rel->burnrelabel < 1)
@@ -3448,8 +3687,39 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
                 rc = bmm_chain_set_split_merge(c, g_sm.moves, g_sm.scans);
                 if (rc) return rc;
             }
+            // feature selection armed for this run: a gamma-step behind every sweep, kept sweeps folded and recorded
+            const bool fs = g_fs.on;
+            DevBuf gtrace;
+            if (fs) {
+                rc = bmm_chain_set_feature_select(c, 1, g_fs.o.rho);
+                if (rc) return rc;
+                const size_t bytes = (size_t)S * (size_t)P;
+                HIP_TRY(gtrace.alloc(bytes));
+                HIP_TRY(hipMemsetAsync(gtrace.p, 1, bytes, c->stream));  // (trace row 0 of a run without burn-in: the initial mask)
+                c->fs_from = burnin > 0 ? burnin : 1;
+                c->fs_trace = gtrace.as<uint8_t>();
+                c->fs_trace_base = burnin;
+            }
             rc = run_body(c, nsamples, io, hooks, rel);
             if (rc == BMM_OK && g_sm.moves > 0) rc = bmm_chain_split_merge_stats(c, g_sm_stats);
+            c->fs_trace = nullptr;
+            if (fs) {
+                const hipError_t es = hipStreamSynchronize(c->stream);  // before gtrace may go
+                if (rc == BMM_OK && es != hipSuccess) rc = set_err(BMM_E_HIP, "the run failed: %s", hipGetErrorString(es));
+                const bmm_feature_out& o = g_fs.o;
+                if (rc == BMM_OK) {
+                    const hipError_t ec = hipMemcpy(o.gamma, gtrace.p, (size_t)S * (size_t)P, hipMemcpyDeviceToHost);
+                    if (ec != hipSuccess) rc = set_err(BMM_E_HIP, "copying the indicator trace failed: %s", hipGetErrorString(ec));
+                }
+                if (rc == BMM_OK) {
+                    for (int t = 0; t < S; ++t) {
+                        int32_t n = 0;
+                        for (int d = 0; d < P; ++d) n += o.gamma[(size_t)t * P + d];
+                        o.n_selected[t] = n;
+                    }
+                    rc = bmm_chain_get_feature_summary(c, o.inclusion, o.inclusion_rb, o.n_folded);
+                }
+            }
             c->loo_fold = false;
             c->loo_trace = nullptr;
             if (loo) {
@@ -3807,6 +4077,12 @@ int bmm_set_split_merge(int moves_per_sweep, int scans) {
 int bmm_last_split_merge_stats(int64_t out[5]) {
     if (!out) return set_err(BMM_E_ARG, "null argument");
     for (int q = 0; q < 5; ++q) out[q] = g_sm_stats[q];
+    return BMM_OK;
+}
+
+int bmm_set_feature_select(const bmm_feature_out* out) {
+    g_fs.on = out != nullptr;
+    if (out) g_fs.o = *out;
     return BMM_OK;
 }
 

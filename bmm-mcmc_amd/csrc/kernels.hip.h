@@ -163,12 +163,18 @@ __device__ __forceinline__ void write_group_tables(int W, const double* e1, cons
 }
 
 constexpr int kCountTablesThreads = 576;
+// MASK (feature selection): `mask` holds one inclusion bit per feature (word d / 32, bit d % 32,
+// the bits from P on zero).  An excluded feature's terms are written as 0 in all four roles -- it scores the same for
+// every category, so it drops out of the conditional -- and the DP's new-cluster term counts the included features
+// only.  The statistics are folded for every feature alike.  MASK = false is the code as it always was.
+template <bool MASK>
 __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParams p, int32_t* __restrict__ Nk,
                                                                      int32_t* __restrict__ S,
                                                                      int32_t* __restrict__ dNk,
                                                                      int32_t* __restrict__ dS,
                                                                      const double* __restrict__ alpha_ptr,
-                                                                     double* __restrict__ tab) {
+                                                                     double* __restrict__ tab,
+                                                                     const uint32_t* __restrict__ mask) {
     __shared__ double e1[kMaxP], e0[kMaxP], m1[kMaxP], m0[kMaxP], cst[4];  // cst: Cp, Cm, the two denominators
     const int k = blockIdx.x;
     const TableLayout L = layout_of(p, true);
@@ -208,6 +214,12 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
             default: break;
         }
         const double v = need ? log_(arg) : 0.0;
+        int p_in = P;  // features that enter the conditional
+        if (MASK) {
+            p_in = 0;
+            for (int w = lane; w < (P + 31) >> 5; w += 64) p_in += __popc(mask[w]);
+            for (int o = 32; o > 0; o >>= 1) p_in += __shfl_xor(p_in, o);
+        }
         const double den_p = __shfl(v, 0), den_m = __shfl(v, 1), ln = __shfl(v, 2), lm = __shfl(v, 3);
         const double ldN = __shfl(v, 4), la = __shfl(v, 5), lb = __shfl(v, 6), lbg = __shfl(v, 7);
         if (lane == 0) {
@@ -216,7 +228,7 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
                 if (n > 0) cp = ln - ldN;
                 if (n > 1) cm = lm - ldN;
             } else if (dp_new) {
-                cp = (la - ldN) + (double)P * (lb - lbg);
+                cp = (la - ldN) + (double)p_in * (lb - lbg);
             }
             tab[L.cp() + k] = cp;
             tab[L.cm() + k] = cm;
@@ -240,7 +252,8 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
         }
         __syncthreads();  // the constants are in place; every role has read S + dS before either is rewritten
         if (dl < pc) {
-            const double t = have ? raw - cst[role < 2 ? 2 : 3] : 0.0;
+            double t = have ? raw - cst[role < 2 ? 2 : 3] : 0.0;
+            if (MASK && !((mask[(c0 + dl) >> 5] >> ((c0 + dl) & 31)) & 1u)) t = 0.0;
             (role == 0 ? e1 : role == 1 ? e0 : role == 2 ? m1 : m0)[dl] = t;
             if (role == 0 && is_label) {
                 const int d = c0 + dl;
@@ -2970,6 +2983,83 @@ __global__ __launch_bounds__(kSmThreads) void k_sm_commit(ChainParams p, SmArgs 
             *(la < lb ? B : A) = 0;
         }
     }
+}
+
+// ---- feature selection for the counting samplers (include/bmm_mcmc.h "feature selection") ----
+// The gamma-step behind a sweep end: every inclusion indicator redrawn from its exact conditional given the folded
+// counts.  A workgroup owns the 32 features of one mask word, one wave per feature (16 waves, two rounds); lanes
+// stride over the clusters in ascending order, an empty cluster is skipped, and the 64 partial sums are added by a
+// butterfly, so the order of the sum is fixed by K alone.  lgamma_(beta + gamma + N_k) is the same for every
+// feature: once per workgroup, in LDS.  Lane 0 of a wave decides, records and folds; the word is put together in LDS
+// and written once with a plain store.  Nothing is atomic in global memory: one seed gives the same bits twice.
+// lgamma_ and the logistic are called, not inlined, in k_fs_gamma: inlined at their five places their binary64
+// constants crowd the scalar registers (28 of them spilled to vector lanes); called, the kernel spills nothing and
+// still needs no stack.  Same arithmetic, same bits.
+__device__ __attribute__((noinline)) double fs_lgamma(double x) { return lgamma_(x); }
+__device__ __attribute__((noinline)) double fs_prob(double lam) { return div_(1.0, 1.0 + exp_(-lam)); }
+__device__ __forceinline__ double fs_pair(double beta, double gamma, int64_t n, int64_t s) {  // sm_pair, called
+    return fs_lgamma(beta + (double)s) + fs_lgamma((gamma + (double)n) - (double)s);
+}
+constexpr int kFsThreads = 1024;
+struct FsArgs {
+    const int32_t *Nk, *S;   // the chain's statistics, nothing pending (k_count_sweep_end folded them)
+    uint32_t* mask;          // [ceil(P / 32)] words: the indicators the next sweep's tables read
+    uint8_t* gamma;          // [P] the same, a byte each
+    uint8_t* gamma_row;      // or null: [P], this sweep's row of a trace
+    double* rec;             // [3][P]: Lambda, p, u of this step
+    uint32_t* incl_count;    // [P] accumulators over the folded steps: the draws ...
+    double* incl_prob;       // ... and their probabilities (one add per step: a fixed order)
+    double logit_rho;        // log rho - log(1 - rho)
+    uint32_t sweep;
+    int fold;
+};
+__global__ __launch_bounds__(kFsThreads) void k_fs_gamma(ChainParams p, FsArgs a) {
+    // lgamma_ of: beta + gamma + N_k (k < K; 0 for an empty cluster), beta + gamma + N, beta, gamma, beta + gamma
+    __shared__ double lg[kMaxCatsAny + 4];
+    __shared__ unsigned sh_word;
+    const int P = p.P, K = p.K, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double bg = p.beta + p.gamma;
+    for (int i = tid; i < K + 4; i += kFsThreads) {
+        const int32_t n = i < K ? a.Nk[i] : 1;
+        const double arg = i < K ? bg + (double)n : (i == K ? bg + (double)p.N : (i == K + 1 ? p.beta : (i == K + 2 ? p.gamma : bg)));
+        lg[i] = n > 0 ? fs_lgamma(arg) : 0.0;
+    }
+    if (tid == 0) sh_word = 0u;
+    __syncthreads();
+    const double lb0 = (lg[K + 1] + lg[K + 2]) - lg[K + 3];  // lB(beta, gamma)
+    for (int r = 0; r < 2; ++r) {
+        const int bit = r * 16 + wave, d = blockIdx.x * 32 + bit;
+        if (d >= P) break;  // uniform over the wave
+        int64_t T = 0;  // (an empty cluster's count is 0)
+        for (int k = lane; k < K; k += 64) T += a.S[(size_t)k * P + d];
+        for (int o = 32; o > 0; o >>= 1) T += __shfl_xor(T, o);
+        // lane l walks the clusters l, l + 64, ... in ascending order, an empty one skipped (not added as a zero); the
+        // all-rows term of the noise model is entry K of the same walk, subtracted
+        double acc = 0.0;
+        for (int k = lane; k <= K; k += 64) {
+            const int64_t n = k < K ? (int64_t)a.Nk[k] : p.N;
+            if (n <= 0) continue;
+            const int64_t s = k < K ? (int64_t)a.S[(size_t)k * P + d] : T;
+            const double t = (fs_pair(p.beta, p.gamma, n, s) - lg[k]) - lb0;
+            acc = k < K ? acc + t : acc - t;
+        }
+        for (int o = 32; o > 0; o >>= 1) acc = acc + __shfl_xor(acc, o);
+        if (lane != 0) continue;
+        const double lam = a.logit_rho + acc;
+        const double pr = fs_prob(lam);
+        const double u = fs_uniform(p.seed, (uint32_t)d, a.sweep);
+        const unsigned g = u < pr ? 1u : 0u;
+        if (g) atomicOr(&sh_word, 1u << bit);
+        a.gamma[d] = (uint8_t)g;
+        if (a.gamma_row) a.gamma_row[d] = (uint8_t)g;
+        a.rec[d] = lam; a.rec[(size_t)P + d] = pr; a.rec[(size_t)2 * P + d] = u;
+        if (a.fold) {
+            a.incl_count[d] += g;
+            a.incl_prob[d] = a.incl_prob[d] + pr;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) a.mask[blockIdx.x] = sh_word;
 }
 
 __global__ void k_test_lgamma(const double* in, double* out, int64_t n) {

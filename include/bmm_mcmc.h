@@ -669,6 +669,84 @@ int bmm_chain_set_labels(bmm_chain* c, const int32_t* z1);
 int bmm_set_split_merge(int moves_per_sweep, int scans);
 int bmm_last_split_merge_stats(int64_t out[5]);
 
+/* ---- feature selection for the counting samplers ------------------------------------------
+ * In questionnaire or clinical data many of the P binary features say nothing about the clusters.  The variable-selection
+ * collapsed Gibbs sampler of White, Wyse & Murphy (2016) gives every feature an inclusion indicator and samples it with
+ * the allocation.  THE MODEL: gamma_d ~ Bernoulli(rho), independently, for every feature d;
+ *   gamma_d = 1  feature d clusters: theta_kd ~ Beta(beta, gamma) per cluster -- the model of the rest of this header;
+ *   gamma_d = 0  feature d is noise: one rate theta_0d ~ Beta(beta, gamma) shared by every row.
+ * theta is integrated out throughout.  Offered for BMM_SAMPLER_COLLAPSED and BMM_SAMPLER_DP.
+ *   z-step      the sampler's own conditional with the product over d running over gamma_d = 1 only: a noise
+ *               feature's predictive term is the same for every category and cancels.  The tables the resample
+ *               kernels read hold 0 for an excluded feature -- both terms, full and own-cluster tables -- and the DP's
+ *               new-cluster term counts the included features, P_in (log beta - log(beta + gamma)); the resample kernels
+ *               themselves are the ones every chain runs.
+ *   gamma-step  with lB(x, y) = lgamma(x) + lgamma(y) - lgamma(x + y), T_d = sum_k S_kd and the counts as the end of
+ *               the sweep folded them,
+ *                 Lambda_d = log rho - log(1 - rho)
+ *                            + sum_{k : N_k > 0} [ lB(beta + S_kd, gamma + N_k - S_kd) - lB(beta, gamma) ]
+ *                            - [ lB(beta + T_d, gamma + N - T_d) - lB(beta, gamma) ],
+ *                 p_d = 1 / (1 + exp(-Lambda_d)),   gamma_d = [u_d < p_d].
+ *               Given the labels the P indicators are independent, so one launch redraws them all exactly.  An empty
+ *               cluster is skipped, not added as a zero; the sum runs in an order fixed by K (lane l of a wave adds
+ *               the terms of clusters l, l + 64, ... in ascending order, the all-rows term counting as entry K of
+ *               that walk, subtracted; the 64 partial sums are added by a butterfly; log rho - log(1 - rho) last).
+ *               u_d is the 53-bit uniform of the first Philox4x32 block of stream 9 at counter (c0 = d, block 0,
+ *               c2 = sweep j) under the chain's key: no (key, counter) pair of any other stream.  lgamma, log and exp
+ *               are the spec's (bmm_spec.h), the same bits on host and device.
+ *   order       inside sweep j: z is resampled against the mask of sweep j - 1, the sweep end folds the counts (theta-hat
+ *               and alpha as ever), then gamma is drawn from those counts; trace row j records that gamma.  The initial
+ *               mask is all ones.  The step is stream-ordered behind the sweep end: no host wait.
+ * inclusion[d] is the mean of the draws over the folded steps, inclusion_rb[d] the mean of p_d (the Rao-Blackwellised
+ * estimate of the same probability; one binary64 add per step, so one seed gives the same bits twice).
+ * A chain that was never given a mask enqueues exactly what it always did.  A chain with a mask builds its tables with
+ * the masked twin of the table kernel and never takes the form whose workgroups build their own tables
+ * (bmm_chain_kernel_form reports what runs); its values with the all-ones mask are those of a chain without one.
+ * Refused: the stick-breaking and full samplers (they carry theta) and a run of the DP sampler with beta != gamma (its
+ * new-cluster term is the model's only when they are equal; a resident DP chain is created with beta == gamma only)
+ * with BMM_E_UNSUPPORTED; a chain with a mask combined with newdata,
+ * the leave-one-out summary or split-merge moves, in either order, with BMM_E_UNSUPPORTED -- their tables and ratios
+ * are written for the all-features model; the selection model's versions are a follow-up; a sharded chain, a chain
+ * without data and a finite chain without initial labels (rows that cannot be seated yet) with BMM_E_STATE; rho
+ * outside (0, 1) with BMM_E_ARG. */
+typedef struct bmm_feature_step {
+    double* lambda;   /* in: room for P doubles each, or NULL: Lambda_d, p_d, u_d of the last step */
+    double* p;
+    double* u;
+    uint8_t* gamma;   /* in: room for P bytes, or NULL: the indicators it drew */
+    uint32_t sweep;   /* out: the sweep it followed (what keyed its uniforms) */
+} bmm_feature_step;
+/* on != 0: a gamma-step behind every sweep from now on, every step folded; arming empties the accumulators.  on = 0:
+ * no more steps; the mask stays as it is. */
+int bmm_chain_set_feature_select(bmm_chain* c, int on, double rho);
+/* the mask, between sweeps: gamma[d] in {0, 1}, P bytes.  set waits; get waits and gives all ones for a chain that
+ * never had a mask. */
+int bmm_chain_set_features(bmm_chain* c, const uint8_t* gamma);
+int bmm_chain_get_features(bmm_chain* c, uint8_t* gamma);
+/* the last step's record.  Waits. */
+int bmm_chain_feature_step(bmm_chain* c, bmm_feature_step* out);
+/* n more sweeps of an armed chain, returning the indicators after each: gamma_trace is n x P bytes, row-major (sweep,
+ * feature).  Waits. */
+int bmm_chain_sweeps_features(bmm_chain* c, int n, uint8_t* gamma_trace);
+/* inclusion, inclusion_rb (P doubles each, either may be NULL; NaN while nothing is folded) and the number of folded
+ * steps; the accumulators stay, so more sweeps may follow */
+int bmm_chain_get_feature_summary(bmm_chain* c, double* inclusion, double* inclusion_rb, int* n_folded);
+int bmm_chain_feature_reset(bmm_chain* c);
+/* For a run: armed per calling thread for the NEXT single-chain collapsed or DP *_run* call of that thread and
+ * disarmed when that call returns, whatever it returns, as bmm_set_split_merge and bmm_set_loo_summary; NULL disarms.
+ * The struct is copied; its buffers must stay valid through that call.  Only kept sweeps (j >= burnin) are recorded
+ * and folded; without burn-in the first kept row is the starting state: its indicators are the initial mask (all
+ * ones) and it is not folded.  bmm_multi_run does not take it and disarms it. */
+typedef struct bmm_feature_out {
+    double rho;
+    uint8_t* gamma;        /* S x P bytes, row-major (kept sweep, feature) */
+    double* inclusion;     /* P doubles */
+    double* inclusion_rb;  /* P doubles */
+    int32_t* n_selected;   /* S ints: the included features per kept sweep */
+    int* n_folded;         /* or NULL */
+} bmm_feature_out;
+int bmm_set_feature_select(const bmm_feature_out* out);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
