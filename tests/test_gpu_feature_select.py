@@ -41,12 +41,14 @@ def _masks(P, W):
             "zeros": np.zeros(P, dtype=np.uint8)}
 
 
-def _chain(bmm, sampler, X, K, batch, seed, layout=None, labels=None):
+def _chain(bmm, sampler, X, K, batch, seed, layout=None, labels=None, initial=None):
     N, P = X.shape
     c = bmm.Chain(sampler, N, P, K, alpha=ALPHA, beta=BETA, gamma=GAMMA, batch=batch, seed=seed, x_layout=layout)
     c.set_data(X)
     if sampler == "collapsed":
-        c.set_initial_labels(np.random.default_rng(seed).integers(1, (labels or K) + 1, N).astype(np.int32))
+        if initial is None:
+            initial = np.random.default_rng(seed).integers(1, (labels or K) + 1, N).astype(np.int32)
+        c.set_initial_labels(initial)
     return c
 
 
@@ -151,16 +153,43 @@ def test_theta_of_a_run_with_the_all_ones_mask_never_drawn_is_the_unarmed_run(bm
 
 
 # ---------------------------------------------------------------- 2. the gamma-step
-@pytest.mark.parametrize("sampler,P,K", [("dp", 37, 8), ("dp", 130, 8), ("collapsed", 37, 40)])
+def _spread_labels(comp, K):
+    """labels over all of 3 .. K: the rows of generating component 2 under label K, a cluster that lasts, every other
+    row dealt out over 3 .. K - 1; labels 1 and 2 stay empty"""
+    z = 3 + np.arange(len(comp)) % (K - 3)
+    return np.where(comp == 2, K, z).astype(np.int32)
+
+
+# K = 8 and 40: one trip of the lane walk `for k = lane; k <= K; k += 64` and of the integer butterfly's.  K = 63: the
+# all-rows entry K on lane 63; 64: on lane 0 of the second trip; 65: one cluster and the entry in the second trip; 130:
+# a third trip; 1024 (collapsed) and 1023 (dp): the most categories a chain takes, 17 trips.  P = 1, 32, 33, 64: one
+# feature; a full mask word; a second workgroup that owns one feature (its other 15 waves leave the loop); two full
+# words.  P = 2000: 63 workgroups, half a word in the last.
+STEP_SHAPES = [("dp", 37, 8), ("dp", 130, 8), ("collapsed", 37, 40),
+               ("collapsed", 37, 63), ("collapsed", 37, 64), ("collapsed", 37, 65), ("collapsed", 37, 130), ("collapsed", 37, 1024),
+               ("dp", 37, 130), ("dp", 37, 1023),
+               ("dp", 1, 8), ("dp", 32, 8), ("dp", 33, 8), ("dp", 64, 8), ("dp", 2000, 8)]
+
+
+@pytest.mark.parametrize("sampler,P,K", STEP_SHAPES)
 def test_thirty_steps_replayed_from_the_counts(bmm, sampler, P, K):
-    N, seed, rho = 300, 17, 0.3
-    X, _ = _mixture(N, P, [0.2, 0.5, 0.8], 4)
-    X[:, 3] = X[:, 0]                       # (a feature that clusters as well as another)
-    X[:, 5] = np.arange(N) % 2              # (and one that does not)
-    with _chain(bmm, sampler, X, K, 16, seed, labels=K - 2) as c:  # (collapsed: the last two labels stay empty)
-        c.sweeps(2)
+    wide = K >= 63                          # (the shapes of the lane walk: N = 2000 and labels spread over all of them)
+    N, seed, rho = 2000 if wide else 300, 17, 0.3
+    X, comp = _mixture(N, P, [0.2, 0.5, 0.8], 4)
+    if P >= 6:
+        X[:, 3] = X[:, 0]                   # (a feature that clusters as well as another)
+        X[:, 5] = np.arange(N) % 2          # (and one that does not)
+    initial = _spread_labels(comp, K) if wide else None
+    batch = 250 if wide else 16             # (eight launches a sweep at N = 2000: a sweep over 1024 categories is slow)
+    with _chain(bmm, sampler, X, K, batch, seed, labels=K - 2, initial=initial) as c:  # (collapsed: the last two labels stay empty)
+        if wide and sampler == "dp":
+            c.sweeps(1)                     # (seated: a DP chain takes labels from here on)
+            c.set_labels(initial)
+            c.sweeps(1)
+        else:
+            c.sweeps(2)
         c.set_feature_select(True, rho)
-        acc, draws, empties = np.zeros(P), np.zeros(P), 0
+        acc, draws, empties, high, worst = np.zeros(P), np.zeros(P), 0, 0, 0.0
         for step in range(30):
             if step % 2:
                 row = c.sweeps_features(1)[0]
@@ -169,6 +198,8 @@ def test_thirty_steps_replayed_from_the_counts(bmm, sampler, P, K):
                 row = None
             Nk, S = c.counts()
             empties += int(np.sum(Nk == 0) > 0)
+            if K > 64 and high == step:     # a cluster in the second trip of the walk or later, in every step so far
+                high += int(Nk[64:].sum() > 0)
             d = c.feature_step()
             assert d["sweep"] == 3 + step == c.sweep_index
             lam, mag, n = fsr.gamma_logit(Nk, S, BETA, GAMMA, rho, with_terms=True)
@@ -180,6 +211,7 @@ def test_thirty_steps_replayed_from_the_counts(bmm, sampler, P, K):
             err = np.abs(d["lambda"] - lam)
             print("step %d: Lambda worst %.3e (bound there %.3e)" % (step, err.max(), bound[np.argmax(err)]))
             assert np.all(err <= bound)
+            worst = max(worst, float(np.max(err / bound)))
             # p and the draw, on the device's own numbers
             with np.errstate(over="ignore"):
                 p_host = 1.0 / (1.0 + np.exp(-d["lambda"]))
@@ -190,17 +222,55 @@ def test_thirty_steps_replayed_from_the_counts(bmm, sampler, P, K):
                 np.testing.assert_array_equal(row, d["gamma"])
             acc = acc + d["p"]
             draws = draws + d["gamma"]
+        print("%s P=%d K=%d: worst Lambda error as a share of its bound %.3g" % (sampler, P, K, worst))
         sm = c.feature_summary()
         assert sm["n_folded"] == 30
         np.testing.assert_array_equal(sm["inclusion_rb"].view(np.uint64), (acc / 30.0).view(np.uint64))
         np.testing.assert_array_equal(sm["inclusion"], draws / 30.0)
         assert empties == 30                 # every state: unused labels (dp), empty clusters (collapsed)
+        if K > 64:                           # (K = 64: index 64 of the walk is the all-rows entry itself)
+            print("%s K=%d: a non-empty cluster at index >= 64 in the first %d of 30 steps" % (sampler, K, high))
+            assert high == 30
         c.feature_reset()
         assert c.feature_summary()["n_folded"] == 0
         c.set_feature_select(False)
         before = c.features()
         c.sweeps(2)
         np.testing.assert_array_equal(c.features(), before)   # no step any more, the mask stays
+
+
+def word_data():
+    """N = 300, P = 64: every third feature is noise of one rate, so that both mask words come out mixed"""
+    X, _ = _mixture(300, 64, [0.2, 0.5, 0.8], 4)
+    X[:, ::3] = np.random.default_rng(0).random((300, 22)) < 0.4
+    return X
+
+
+def test_the_packed_word_the_next_sweep_reads_agrees_with_the_indicator_bytes(bmm):
+    """The step stores the indicators twice: a byte each (what features() and feature_step() return) and packed, 32 to
+    a word, with one plain store per workgroup (what the next sweep's tables read).  batch = N: the probabilities of
+    the sweep behind a step are a pure function of the labels and of the word, as in section 1."""
+    N, P, K, seed, rho = 300, 64, 8, 17, 0.3
+    X = word_data()
+    with _chain(bmm, "dp", X, K, N, seed) as c:
+        c.sweeps(2)
+        c.set_feature_select(True, rho)
+        for step in range(3):
+            c.sweeps(1)
+            g = c.feature_step()["gamma"]
+            np.testing.assert_array_equal(c.features(), g)
+            assert 0 < g[:32].sum() < 32 and 0 < g[32:].sum() < 32, g   # both words mixed: a lost or misplaced bit shows
+            z = c.labels() - 1
+            got = c.sweep_probs()                                        # (one more sweep, and its own step behind it)
+            want = fsr.z_conditional(X, z, K, ALPHA, BETA, GAMMA, g, "dp")
+            big = want > 1e-300
+            rel = np.abs(got[big] - want[big]) / want[big]
+            print("step %d: %d of 64 features in, worst relative %.2e" % (step, g.sum(), rel.max()))
+            assert rel.max() <= 1e-12
+            assert np.all(got[~big] <= 1e-300)
+            # and the check can tell: under the mask with the two words exchanged the conditional is another one
+            other = fsr.z_conditional(X, z, K, ALPHA, BETA, GAMMA, np.concatenate([g[32:], g[:32]]), "dp")
+            assert np.array_equal(g[32:], g[:32]) or np.abs(other - want).max() > 1e-6
 
 
 # ---------------------------------------------------------------- 3. the joint chain against the exact posterior

@@ -172,18 +172,9 @@ def test_partly_used_last_groups(K, P):
 
 
 # ---------------------------------------------------------------- the fold
-@pytest.mark.parametrize("sampler,K,n", [("collapsed", 5, 6), ("dp", 9, 8), ("stickbreaking", 6, 10), ("full", 4, 7)])
-def test_the_fold(sampler, K, n):
-    X, _, _, _ = synth(2500, 30, 3, seed=8)
-    N = X.shape[0]
-
-    def run():
-        with _chain(sampler, X, K, alpha=None) as c:
-            c.sweeps(2)
-            trace = c.sweeps_loo(n, trace=True)
-            return trace, c.loo()
-
-    trace, got = run()
+def _check_fold(sampler, trace, got, n, N):
+    """the summary `got` of a fold over the n kept sweeps whose ell is `trace` (n x N), against the restatement's
+    (tests/test_gpu_split_merge_routes.py holds a run with split-merge moves to the same)"""
     assert trace.shape == (n, N) and got["n_folded"] == n
     want = lref.summary(trace, waic=sampler in ("stickbreaking", "full"))
     R = np.max(np.abs(trace))
@@ -209,6 +200,21 @@ def test_the_fold(sampler, K, n):
         assert abs(got["elpd_waic"] - (lp - got["p_waic"])) <= depth * EPS * math.fsum(np.abs(got["lppd"])) + EPS * abs(lp)
     else:
         assert "p_waic" not in got and "elpd_waic" not in got
+
+
+@pytest.mark.parametrize("sampler,K,n", [("collapsed", 5, 6), ("dp", 9, 8), ("stickbreaking", 6, 10), ("full", 4, 7)])
+def test_the_fold(sampler, K, n):
+    X, _, _, _ = synth(2500, 30, 3, seed=8)
+    N = X.shape[0]
+
+    def run():
+        with _chain(sampler, X, K, alpha=None) as c:
+            c.sweeps(2)
+            trace = c.sweeps_loo(n, trace=True)
+            return trace, c.loo()
+
+    trace, got = run()
+    _check_fold(sampler, trace, got, n, N)
     with _chain(sampler, X, K, alpha=None) as c:  # the same chain stepped by hand
         c.sweeps(2)
         for s in range(n):

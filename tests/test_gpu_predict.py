@@ -152,6 +152,15 @@ def test_the_dp_predictive_is_a_density_on_the_device():
         assert abs(np.exp(c.predict_state()).sum() - 1.0) < 1e-12  # over all 2^P rows
 
 
+def _check_fold_lppd(sampler, trace, lppd, n, M):
+    """lppd of a fold over the n kept sweeps whose log densities are `trace` (n x M)
+    (tests/test_gpu_split_merge_routes.py holds a run with split-merge moves to the same)"""
+    assert trace.shape == (n, M) and lppd.shape == (M,)
+    want = logsumexp(trace, axis=0) - np.log(n)
+    print(sampler, "largest |lppd - logsumexp(trace) + log n|", np.max(np.abs(lppd - want)))
+    assert np.max(np.abs(lppd - want)) < 1e-12
+
+
 @pytest.mark.parametrize("sampler,K", [("collapsed", 5), ("dp", 9), ("stickbreaking", 6), ("full", 4)])
 def test_the_fold(sampler, K):
     X, _, _, _ = synth(4000, 30, 3, seed=8)
@@ -166,10 +175,8 @@ def test_the_fold(sampler, K):
             return trace, c.predictive(responsibilities=True)
 
     trace, pr = run()
-    assert trace.shape == (n, 700) and pr["n"] == n
-    want = logsumexp(trace, axis=0) - np.log(n)
-    print(sampler, "largest |lppd - logsumexp(trace) + log n|", np.max(np.abs(pr["lppd"] - want)))
-    assert np.max(np.abs(pr["lppd"] - want)) < 1e-12
+    assert pr["n"] == n
+    _check_fold_lppd(sampler, trace, pr["lppd"], n, 700)
     assert np.max(np.abs(pr["resp"].sum(axis=1) - 1.0)) < 1e-13  # a mean of n rows that each sum to 1 within 1e-14
     with _chain(sampler, X, K, alpha=None) as c:  # the same chain stepped by hand
         c.set_newdata(Xnew)

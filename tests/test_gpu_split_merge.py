@@ -8,27 +8,22 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import split_merge_cases as cases  # noqa: E402
 import split_merge_checks as chk  # noqa: E402
 import split_merge_ref as ref  # noqa: E402
 from test_split_merge_ref import seven_observations  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-BETA = GAMMA = 0.5
-ALPHA = 1.3
+# the one source of the replayed chains' constants and data, shared with the CPU pre-check of the cases
+ALPHA, BETA, GAMMA = cases.ALPHA, cases.BETA, cases.GAMMA
+_mixture = cases.mixture
 
 
 @pytest.fixture(scope="module")
 def bmm():
     import importlib
     return importlib.import_module("bmm-mcmc_amd")
-
-
-def _mixture(N, P, thetas, seed):
-    rng = np.random.default_rng(seed)
-    comp = rng.integers(len(thetas), size=N)
-    X = (rng.random((N, P)) < np.asarray(thetas)[comp][:, None]).astype(np.int32)
-    return np.asfortranarray(X), comp
 
 
 def _recount(X, z1, K):
@@ -39,67 +34,118 @@ def _recount(X, z1, K):
     return Nk, S
 
 
+def _integer_parts(c, d, r, z_before):
+    """the parts of a device step that are pure functions of seed, counters and labels, against the restatement's,
+    exactly; False for a skipped move (which must have changed nothing)"""
+    assert d["rows"] == r["rows"] and d["kind"] == r["kind"]
+    assert d["log_u"] == pytest.approx(r["log_u"], abs=4 * chk.EPS * max(1.0, abs(r["log_u"])))
+    if d["kind"] == "skipped":
+        np.testing.assert_array_equal(c.labels(), z_before)
+        return False
+    assert d["labels"] == (r["labels"][0] + 1, r["labels"][1] + 1)
+    assert d["members"] == r["members"] and d["n_before"] == r["n_before"] and d["n_after"] == r["n_after"]
+    np.testing.assert_array_equal(d["launch_side"], r["launch_side"])
+    np.testing.assert_array_equal(d["proposal_side"], r["proposal_side"])
+    return True
+
+
+def _replay(bmm, N, P, K, scans, X, seed, prepare=None):
+    """cases.SWEEPS sweeps at batch cases.BATCH, `prepare(chain)` if given, then 40 manual moves (or, `scans` a tuple
+    of (scans, steps) phases, the steps of every phase on the one chain), each against the restatement fed with the
+    labels before it.  Returns what split_merge_cases.check_reached wants to see of every move."""
+    phases = ((scans, 40),) if isinstance(scans, int) else tuple(scans)
+    total = sum(n for _, n in phases)
+    worst = {"log_prior": 0.0, "log_lik": 0.0, "log_q": 0.0}
+    seen = []
+    with bmm.Chain("dp", N, P, K, alpha=ALPHA, beta=BETA, gamma=GAMMA, batch=cases.BATCH, seed=seed) as c:
+        c.set_data(X)
+        c.sweeps(cases.SWEEPS)
+        if prepare is not None:
+            prepare(c)
+        kinds = set()
+        done = 0  # moves made so far, over all phases: the move counter of the next one
+        for phase_scans, n_steps in phases:
+            c.set_split_merge(1, phase_scans)  # the scans of the manual moves ...
+            c.set_split_merge(0, phase_scans)  # ... and nothing armed
+            for _ in range(n_steps):
+                step, done = done, done + 1
+                z_before = c.labels()
+                d = c.split_merge_step(sides=True)
+                assert (d["sweep"], d["move"]) == (cases.SWEEPS + 1, step)
+                r = ref.move(X, z_before - 1, K, ALPHA, BETA, GAMMA, phase_scans, ref.PhiloxDraws(seed, d["sweep"], d["move"]))
+                kinds.add(d["kind"])
+                seen.append((d["kind"], d["labels"], d["members"], d["launch_side"]))
+                # the integer parts, exactly
+                if not _integer_parts(c, d, r, z_before):
+                    continue
+                # the three sums.  Bound: every lgamma_ term is within LGAMMA_ULPS ulps of max(1, |term|), the log within
+                # LOG_ULPS, and adding n terms in binary64 loses at most n ulps of the sum of their magnitudes; scipy's own
+                # error is taken as no larger than lgamma_'s.  So |difference| <= 2 (LGAMMA_ULPS + n) eps (sum |terms| + n).
+                tot, n = r["abs_terms"]
+                bound = 2.0 * (chk.LGAMMA_ULPS + n) * chk.EPS * (tot + n)
+                print("step %d %s: log_prior %.3e log_lik %.3e (bound %.3e)" % (step, d["kind"], abs(d["log_prior"] - r["log_prior"]),
+                                                                               abs(d["log_lik"] - r["log_lik"]), bound))
+                assert abs(d["log_prior"] - r["log_prior"]) <= bound
+                assert abs(d["log_lik"] - r["log_lik"]) <= bound
+                # log q: per member 4 P + 2 logs of magnitude below log(bg + N) + |log prior| each, a difference and a sum per
+                # feature, then exp and log of the draw (1 ulp each on a value below 1 + |diff|)
+                m = d["members"]
+                per_member = (4 * P + 8) * (chk.LOG_ULPS + 2.0) * chk.EPS * (math.log(BETA + GAMMA + N) + abs(math.log(BETA)) + 1.0) * 2.0
+                bound_q = m * per_member + m * chk.EPS * max(1.0, abs(r["log_q"]))
+                print("         log_q %.3e (bound %.3e)" % (abs(d["log_q"] - r["log_q"]), bound_q))
+                assert abs(d["log_q"] - r["log_q"]) <= bound_q
+                for key, b in (("log_prior", bound), ("log_lik", bound), ("log_q", bound_q)):
+                    if b > 0.0:
+                        worst[key] = max(worst[key], abs(d[key] - r[key]) / b)
+                # the decision, on the device's own numbers
+                sign = -1.0 if d["kind"] == "split" else 1.0
+                assert d["log_r"] == (d["log_prior"] + d["log_lik"]) + sign * d["log_q"]
+                assert d["accepted"] == (d["log_u"] < d["log_r"])
+                # the state afterwards
+                z_after = c.labels()
+                Nk, S = c.counts()
+                Nk_ref, S_ref = _recount(X, z_after, K)
+                np.testing.assert_array_equal(Nk, Nk_ref)
+                np.testing.assert_array_equal(S, S_ref)
+                outside = d["launch_side"] == 255
+                np.testing.assert_array_equal(z_after[outside], z_before[outside])
+                if d["accepted"] == r["accepted"]:
+                    np.testing.assert_array_equal(z_after - 1, r["z"])
+                if not d["accepted"]:
+                    np.testing.assert_array_equal(z_after, z_before)
+        assert done == total and {"split", "merge"} <= kinds
+        st = c.split_merge_stats()
+        assert st["split_proposed"] + st["merge_proposed"] + st["skipped"] == total
+    print("N=%d P=%d K=%d scans=%s: worst error as a share of its bound: log_prior %.3g, log_lik %.3g, log_q %.3g"
+          % (N, P, K, [s for s, _ in phases], worst["log_prior"], worst["log_lik"], worst["log_q"]))
+    return seen
+
+
+def _replay_case(bmm, case):
+    prepare = None
+    if case.plant is not None:
+        def prepare(c):
+            z0 = case.plant(case.N)
+            c.set_labels(z0)
+            np.testing.assert_array_equal(c.labels(), z0)
+    seen = _replay(bmm, case.N, case.P, case.K, cases.scans_of(case), cases.data(case), case.seed, prepare)
+    assert len(seen) == cases.steps_of(case)
+    cases.check_reached(case, seen)
+
+
 @pytest.mark.parametrize("P", [37, 130])
 def test_step_diagnostics_against_the_restatement(bmm, P):
-    N, K, scans, seed = 300, 8, 2, 17
-    X, _ = _mixture(N, P, [0.2, 0.5, 0.8], 4)
-    with bmm.Chain("dp", N, P, K, alpha=ALPHA, beta=BETA, gamma=GAMMA, batch=16, seed=seed) as c:
-        c.set_data(X)
-        c.sweeps(3)
-        c.set_split_merge(1, scans)  # the scans of the manual moves ...
-        c.set_split_merge(0, scans)  # ... and nothing armed
-        kinds = set()
-        for step in range(40):
-            z_before = c.labels()
-            d = c.split_merge_step(sides=True)
-            assert (d["sweep"], d["move"]) == (4, step)
-            r = ref.move(X, z_before - 1, K, ALPHA, BETA, GAMMA, scans, ref.PhiloxDraws(seed, d["sweep"], d["move"]))
-            kinds.add(d["kind"])
-            # the integer parts, exactly
-            assert d["rows"] == r["rows"] and d["kind"] == r["kind"]
-            assert d["log_u"] == pytest.approx(r["log_u"], abs=4 * chk.EPS * max(1.0, abs(r["log_u"])))
-            if d["kind"] == "skipped":
-                np.testing.assert_array_equal(c.labels(), z_before)
-                continue
-            assert d["labels"] == (r["labels"][0] + 1, r["labels"][1] + 1)
-            assert d["members"] == r["members"] and d["n_before"] == r["n_before"] and d["n_after"] == r["n_after"]
-            np.testing.assert_array_equal(d["launch_side"], r["launch_side"])
-            np.testing.assert_array_equal(d["proposal_side"], r["proposal_side"])
-            # the three sums.  Bound: every lgamma_ term is within LGAMMA_ULPS ulps of max(1, |term|), the log within
-            # LOG_ULPS, and adding n terms in binary64 loses at most n ulps of the sum of their magnitudes; scipy's own
-            # error is taken as no larger than lgamma_'s.  So |difference| <= 2 (LGAMMA_ULPS + n) eps (sum |terms| + n).
-            tot, n = r["abs_terms"]
-            bound = 2.0 * (chk.LGAMMA_ULPS + n) * chk.EPS * (tot + n)
-            print("step %d %s: log_prior %.3e log_lik %.3e (bound %.3e)" % (step, d["kind"], abs(d["log_prior"] - r["log_prior"]),
-                                                                           abs(d["log_lik"] - r["log_lik"]), bound))
-            assert abs(d["log_prior"] - r["log_prior"]) <= bound
-            assert abs(d["log_lik"] - r["log_lik"]) <= bound
-            # log q: per member 4 P + 2 logs of magnitude below log(bg + N) + |log prior| each, a difference and a sum per
-            # feature, then exp and log of the draw (1 ulp each on a value below 1 + |diff|)
-            m = d["members"]
-            per_member = (4 * P + 8) * (chk.LOG_ULPS + 2.0) * chk.EPS * (math.log(BETA + GAMMA + N) + abs(math.log(BETA)) + 1.0) * 2.0
-            bound_q = m * per_member + m * chk.EPS * max(1.0, abs(r["log_q"]))
-            print("         log_q %.3e (bound %.3e)" % (abs(d["log_q"] - r["log_q"]), bound_q))
-            assert abs(d["log_q"] - r["log_q"]) <= bound_q
-            # the decision, on the device's own numbers
-            sign = -1.0 if d["kind"] == "split" else 1.0
-            assert d["log_r"] == (d["log_prior"] + d["log_lik"]) + sign * d["log_q"]
-            assert d["accepted"] == (d["log_u"] < d["log_r"])
-            # the state afterwards
-            z_after = c.labels()
-            Nk, S = c.counts()
-            Nk_ref, S_ref = _recount(X, z_after, K)
-            np.testing.assert_array_equal(Nk, Nk_ref)
-            np.testing.assert_array_equal(S, S_ref)
-            outside = d["launch_side"] == 255
-            np.testing.assert_array_equal(z_after[outside], z_before[outside])
-            if d["accepted"] == r["accepted"]:
-                np.testing.assert_array_equal(z_after - 1, r["z"])
-            if not d["accepted"]:
-                np.testing.assert_array_equal(z_after, z_before)
-        assert {"split", "merge"} <= kinds
-        st = c.split_merge_stats()
-        assert st["split_proposed"] + st["merge_proposed"] + st["skipped"] == 40
+    case = cases.BY_NAME["original-P%d" % P]
+    assert (case.N, case.K, case.phases, case.seed, case.data_seed) == (300, 8, ((2, 40),), 17, 4)
+    _replay_case(bmm, case)
+
+
+# the shapes past one trip of the kernels' loops (tests/split_merge_cases.py says what each one reaches, and
+# tests/test_split_merge_cases.py that the restatement alone gets there with the case's seed).  The side bytes of every
+# member are compared exactly: no member of any case has so far drawn a uniform within rounding of exp(lp0).
+@pytest.mark.parametrize("name", [c.name for c in cases.CASES if not c.name.startswith("original")])
+def test_step_diagnostics_past_one_trip_of_the_loops(bmm, name):
+    _replay_case(bmm, cases.BY_NAME[name])
 
 
 def test_lgamma_on_the_device_is_bit_equal_to_the_host_build(bmm, tmp_path):
@@ -286,6 +332,20 @@ def test_refusals(bmm):
             c.set_labels(bad)
         assert e.value.code == 1 and "z[10]" in str(e.value)
         np.testing.assert_array_equal(c.labels(), z0)
+    Xw, _ = _mixture(64, 1025, [0.3, 0.7], 1)
+    with bmm.Chain("dp", 64, 1025, 5, alpha=1.0, seed=1) as c:  # one feature past the 1024 the moves are offered for
+        c.set_data(Xw)
+        c.sweeps(1)
+        for call in (lambda: c.set_split_merge(1, 2), lambda: c.split_merge(1), lambda: c.split_merge_step()):
+            with pytest.raises(_capi.BmmError) as e:
+                call()
+            assert e.value.code == 2 and "1024" in str(e.value)
+        c.sweeps(1)                            # and the chain still sweeps
+        assert c.sweep_index == 2
+        Nk, S = c.counts()
+        Nk_ref, S_ref = _recount(Xw, c.labels(), 5)
+        np.testing.assert_array_equal(Nk, Nk_ref)
+        np.testing.assert_array_equal(S, S_ref)
     with bmm.Chain("stickbreaking", 64, 8, 5, alpha=1.0, seed=1) as c:
         with pytest.raises(_capi.BmmError) as e:
             c.set_split_merge(1, 2)
