@@ -282,6 +282,29 @@ static int scores_to_weights(const double* score, int n, double* w) {
     return 1;
 }
 
+/* ------------------------------------------------------------------ the probability matrix of a sweep */
+/* The optional output of the *_probs entry points: probs_out holds one N x K column-major matrix per requested
+ * sweep, in the order of probs_sweeps; this returns the matrix of sweep j, or NULL when j was not asked for. */
+static double* probs_slice(int nprobs, const int32_t* probs_sweeps, double* probs_out, int j, size_t nk) {
+    if (!probs_out) return NULL;
+    for (int q = 0; q < nprobs; ++q) if (probs_sweeps[q] == j) return probs_out + (size_t)q * nk;
+    return NULL;
+}
+/* One row of that matrix from the weights the draw used: w[0..ncat) over their total, summed in label order as
+ * draw_index sums it, filed by label -- what the reference stores for Stephens' relabelling
+ * (collapsed_gibbs.cpp:162-172, stickbreaking.cpp:129-139, collapsed_gibbs_dp.cpp:190-200).  The first K
+ * categories are the labels themselves.  The DP has one more, the new cluster, stored through choices(K)
+ * (collapsed_gibbs_dp.cpp:193,197) under new_label, the label the caller worked out for this observation; a
+ * label without members has weight exactly 0, so the mass overwrites a zero.  new_label < 0 (no label left
+ * without a member): the reference would file it beyond column maxK; here it is in no column and the row sums
+ * to less than 1.  row points at element (i, 0); stride = N. */
+static void file_weights(const double* w, int ncat, int K, int new_label, double* row, int64_t stride) {
+    double tot = 0.0;
+    for (int k = 0; k < ncat; ++k) tot = tot + w[k];
+    for (int k = 0; k < K; ++k) row[(size_t)k * stride] = w[k] / tot;
+    if (ncat > K && new_label >= 0) row[(size_t)new_label * stride] = w[K] / tot;
+}
+
 /* ------------------------------------------------------------------ spec tables */
 /* Group table of one cluster from counts (n observations, s[d] ones), optionally
  * with the scored observation's own contribution removed (minus = 1: n-1, and s-1
@@ -773,7 +796,8 @@ thetas:
 static int sb_common(int literal, int full, const int32_t* X, int64_t N, int P, const double* pi0,
                      const double* theta0, int nsamples, int maxK, double alpha, double beta,
                      double gamma, double a, double b, int burnin, uint64_t seed, double* pi_out,
-                     int32_t* z_out, double* theta_out, double* alpha_out) {
+                     int32_t* z_out, double* theta_out, double* alpha_out, int nprobs, const int32_t* probs_sweeps,
+                     double* probs_out) {
     if (nsamples < 1 || burnin < 0 || burnin > nsamples) return fail("bad nsamples/burnin");
     const int gw = oracle_group_width_for(full ? 3 : 2, maxK, P), GM = 1 << gw;
     int S = nsamples - burnin, G = (P + gw - 1) / gw;
@@ -803,6 +827,7 @@ static int sb_common(int literal, int full, const int32_t* X, int64_t N, int P, 
                 theta_group_table(P, gw, maxK, k, theta, T + (size_t)k * G * GM);
                 C[k] = oracle_log(pi[k]);
             }
+        double* pm = probs_slice(nprobs, probs_sweeps, probs_out, j, (size_t)N * maxK);
         for (int64_t i = 0; i < N; ++i) { /* :70-125 */
             int pick;
             double u = oracle_z_uniform(seed, (uint64_t)i, (uint32_t)j);
@@ -823,10 +848,13 @@ static int sb_common(int literal, int full, const int32_t* X, int64_t N, int P, 
                 }
                 for (int p = 0; p < maxK; ++p) s[p] /= cum_probs; /* :103-105 */
                 pick = draw_index(s, maxK, u);
+                if (pm) for (int k = 0; k < maxK; ++k) pm[i + (size_t)k * N] = s[k]; /* :129-139 */
             } else {
                 for (int k = 0; k < maxK; ++k)
                     s[k] = table_sum(C[k], T + (size_t)k * G * GM, nib + (size_t)i * G, G, GM);
-                pick = scores_to_weights(s, maxK, w) ? draw_index(w, maxK, u) : -1;
+                const int ok = scores_to_weights(s, maxK, w);
+                pick = ok ? draw_index(w, maxK, u) : -1;
+                if (pm && ok) file_weights(w, maxK, maxK, -1, pm + i, N);
             }
             if (pick < 0) pick = (j > 1) ? zcur[i] : 0;
             zcur[i] = pick;
@@ -860,14 +888,14 @@ int oracle_sb_literal(const int32_t* X, int64_t N, int P, const double* pi0, con
                       double b, int burnin, uint64_t seed, double* pi_out, int32_t* z_out,
                       double* theta_out, double* alpha_out) {
     return sb_common(1, 0, X, N, P, pi0, theta0, nsamples, maxK, alpha, beta, gamma, a, b, burnin, seed,
-                     pi_out, z_out, theta_out, alpha_out);
+                     pi_out, z_out, theta_out, alpha_out, 0, NULL, NULL);
 }
 int oracle_sb_run(const int32_t* X, int64_t N, int P, const double* pi0, const double* theta0,
                   int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b,
                   int burnin, uint64_t seed, double* pi_out, int32_t* z_out, double* theta_out,
                   double* alpha_out) {
     return sb_common(0, 0, X, N, P, pi0, theta0, nsamples, maxK, alpha, beta, gamma, a, b, burnin, seed,
-                     pi_out, z_out, theta_out, alpha_out);
+                     pi_out, z_out, theta_out, alpha_out, 0, NULL, NULL);
 }
 
 /* full_gibbs.cpp:32-249 (gibbs_cpp): the z-step is stickbreaking.cpp's with K for maxK */
@@ -876,14 +904,14 @@ int oracle_full_literal(const int32_t* X, int64_t N, int P, const double* pi0, c
                         int burnin, uint64_t seed, double* pi_out, int32_t* z_out, double* theta_out,
                         double* alpha_out) {
     return sb_common(1, 1, X, N, P, pi0, theta0, nsamples, K, alpha, beta, gamma, a, b, burnin, seed,
-                     pi_out, z_out, theta_out, alpha_out);
+                     pi_out, z_out, theta_out, alpha_out, 0, NULL, NULL);
 }
 int oracle_full_run(const int32_t* X, int64_t N, int P, const double* pi0, const double* theta0,
                     int nsamples, int K, double alpha, double beta, double gamma, double a, double b,
                     int burnin, uint64_t seed, double* pi_out, int32_t* z_out, double* theta_out,
                     double* alpha_out) {
     return sb_common(0, 1, X, N, P, pi0, theta0, nsamples, K, alpha, beta, gamma, a, b, burnin, seed,
-                     pi_out, z_out, theta_out, alpha_out);
+                     pi_out, z_out, theta_out, alpha_out, 0, NULL, NULL);
 }
 
 /* ------------------------------------------------------------------ sufficient-statistics chains */
@@ -904,6 +932,7 @@ typedef struct {
     int sample_alpha;
     uint64_t seed;
     int64_t batch;
+    int nprobs; const int32_t* probs_sweeps; double* probs_out; /* optional: N x K matrices of chosen sweeps */
 } ochain;
 
 static void chain_free(ochain* c) {
@@ -994,6 +1023,7 @@ static void chain_batch(ochain* c, int64_t lo, int64_t hi, uint32_t j) {
     const int ncat = c->sampler == 1 ? K + 1 : K;
     if (c->sampler == 1 && all) c->Cp[K] = dp_new_score(alpha, c->beta, c->gamma, P, ldN);
     c->alpha_consts = alpha;
+    double* pm = probs_slice(c->nprobs, c->probs_sweeps, c->probs_out, (int)j, (size_t)c->N * K);
     for (int64_t i = lo; i < hi; ++i) {
         const uint8_t* nb = c->nib + (size_t)i * G;
         const uint8_t* nbm = c->nibm + (size_t)i * Gm;
@@ -1003,8 +1033,19 @@ static void chain_batch(ochain* c, int64_t lo, int64_t hi, uint32_t j) {
             else c->score[k] = table_sum(c->Cp[k], c->Tp + k * tk, nb, G, GM);
         }
         if (c->sampler == 1) c->score[K] = c->Cp[K] + 0.0;
-        int pick = scores_to_weights(c->score, ncat, c->w)
-                       ? draw_index(c->w, ncat, oracle_z_uniform(c->seed, (uint64_t)i, j)) : -1;
+        const int ok = scores_to_weights(c->score, ncat, c->w);
+        int pick = ok ? draw_index(c->w, ncat, oracle_z_uniform(c->seed, (uint64_t)i, j)) : -1;
+        if (pm && ok) {
+            /* The DP's new-cluster mass is filed under choices(K) = unused_clusters.top()
+             * (collapsed_gibbs_dp.cpp:169-170): the smallest label on the heap of labels without a member.
+             * Against statistics frozen at batch start that heap holds the labels free at batch start --
+             * and the observation's own label when it had its cluster to itself, because taking it out
+             * (:113-128) pushes that label before the top is read.  So: the smallest free label of the
+             * batch, or the own label of an observation that sat alone when that one is smaller. */
+            int file_under = new_label;
+            if (c->sampler == 1 && zo >= 0 && c->Nk[zo] == 1 && (file_under < 0 || zo < file_under)) file_under = zo;
+            file_weights(c->w, ncat, K, file_under, pm + i, c->N);
+        }
         if (pick < 0) pick = zo >= 0 ? zo : 0;
         if (c->sampler == 1 && pick == K) {
             const int own_single = (zo >= 0 && c->Nk[zo] == 1);
@@ -1059,12 +1100,14 @@ static void chain_emit(const ochain* c, int s, int S, int32_t* z_out, double* th
 static int run_counts_chain(int sampler, const int32_t* X, int64_t N, int P, const int32_t* z0,
                             int nsamples, int K, double alpha, double beta, double gamma, double a,
                             double b, int burnin, int64_t batch, uint64_t seed, int32_t* z_out,
-                            double* theta_out, double* alpha_out, int32_t* nk_out, int32_t* z_last) {
+                            double* theta_out, double* alpha_out, int32_t* nk_out, int32_t* z_last,
+                            int nprobs, const int32_t* probs_sweeps, double* probs_out) {
     if (nsamples < 1 || burnin < 0 || burnin > nsamples) return fail("bad nsamples/burnin");
     if (sampler == 1 && beta != gamma)
         return fail("Error: sampler currently not implemented for non-symmetric priors on beta and gamma");
     ochain c;
     if (chain_init(&c, sampler, X, N, P, K, z0, alpha, beta, gamma, a, b, batch, seed)) { chain_free(&c); return 1; }
+    c.nprobs = nprobs; c.probs_sweeps = probs_sweeps; c.probs_out = probs_out;
     int S = nsamples - burnin;
     if (burnin == 0) {
         if (z_out) for (int64_t i = 0; i < N; ++i) z_out[0 + (size_t)i * S] = z0 ? z0[i] : ORACLE_NA_INT;
@@ -1094,13 +1137,13 @@ int oracle_collapsed_run(const int32_t* X, int64_t N, int P, const int32_t* z0, 
                          double* alpha_out) {
     if (!z0) return fail("initialK required");
     return run_counts_chain(0, X, N, P, z0, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
-                            z_out, theta_out, alpha_out, NULL, NULL);
+                            z_out, theta_out, alpha_out, NULL, NULL, 0, NULL, NULL);
 }
 int oracle_dp_run(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta,
                   double gamma, double a, double b, int burnin, int maxK, int64_t batch,
                   uint64_t seed, int32_t* z_out, double* theta_out, double* alpha_out) {
     return run_counts_chain(1, X, N, P, NULL, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch,
-                            seed, z_out, theta_out, alpha_out, NULL, NULL);
+                            seed, z_out, theta_out, alpha_out, NULL, NULL, 0, NULL, NULL);
 }
 /* The same chains without the S x N label trace (which does not fit at N = 10^6 and hundreds of kept
  * sweeps): cluster sizes per kept sweep, theta-hat, alpha, and the labels after the last sweep.
@@ -1112,7 +1155,36 @@ int oracle_counts_summary(int sampler, const int32_t* X, int64_t N, int P, const
     if (sampler != 0 && sampler != 1) return fail("sampler must be 0 (collapsed) or 1 (dp)");
     if (sampler == 0 && !z0) return fail("initialK required");
     return run_counts_chain(sampler, X, N, P, sampler == 0 ? z0 : NULL, nsamples, K, alpha, beta, gamma, a, b,
-                            burnin, batch, seed, NULL, theta_out, alpha_out, nk_out, z_last);
+                            burnin, batch, seed, NULL, theta_out, alpha_out, nk_out, z_last, 0, NULL, NULL);
+}
+
+/* The *_run chains with the probability matrix of chosen sweeps beside the trace: probs_out receives nprobs
+ * N x K column-major matrices (zero-filled by the caller), the q-th that of sweep probs_sweeps[q] (1-based sweep
+ * number j of the chain, whether kept or burnt in).  Every row is computed under the state its batch saw, with
+ * the weights its draw used.  A row whose scores are all -inf is left as it was. */
+int oracle_collapsed_run_probs(const int32_t* X, int64_t N, int P, const int32_t* z0, int nsamples, int K,
+                               double alpha, double beta, double gamma, double a, double b, int burnin,
+                               int64_t batch, uint64_t seed, int32_t* z_out, double* theta_out,
+                               double* alpha_out, int nprobs, const int32_t* probs_sweeps, double* probs_out) {
+    if (!z0) return fail("initialK required");
+    return run_counts_chain(0, X, N, P, z0, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
+                            z_out, theta_out, alpha_out, NULL, NULL, nprobs, probs_sweeps, probs_out);
+}
+int oracle_dp_run_probs(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta,
+                        double gamma, double a, double b, int burnin, int maxK, int64_t batch,
+                        uint64_t seed, int32_t* z_out, double* theta_out, double* alpha_out, int nprobs,
+                        const int32_t* probs_sweeps, double* probs_out) {
+    return run_counts_chain(1, X, N, P, NULL, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch,
+                            seed, z_out, theta_out, alpha_out, NULL, NULL, nprobs, probs_sweeps, probs_out);
+}
+/* variant: 0 stick-breaking, 1 full; literal as in the entry points without the matrix */
+int oracle_explicit_probs(int variant, int literal, const int32_t* X, int64_t N, int P, const double* pi0,
+                          const double* theta0, int nsamples, int maxK, double alpha, double beta, double gamma,
+                          double a, double b, int burnin, uint64_t seed, double* pi_out, int32_t* z_out,
+                          double* theta_out, double* alpha_out, int nprobs, const int32_t* probs_sweeps,
+                          double* probs_out) {
+    return sb_common(literal != 0, variant != 0, X, N, P, pi0, theta0, nsamples, maxK, alpha, beta, gamma, a, b,
+                     burnin, seed, pi_out, z_out, theta_out, alpha_out, nprobs, probs_sweeps, probs_out);
 }
 
 /* ------------------------------------------------------------------ CPU baseline timing */

@@ -95,6 +95,24 @@ int oracle_dp_literal(const int32_t* X, int64_t N, int P, int nsamples, double a
 int oracle_dp_run(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta,
                   double gamma, double a, double b, int burnin, int maxK, int64_t batch,
                   uint64_t seed, int32_t* z_out, double* theta_out, double* alpha_out);
+/* The same chains with the probability matrix of chosen sweeps beside the trace -- the N x K column-major
+ * matrix the reference stores for Stephens' relabelling, filed by label, every row under the state its batch
+ * saw (for the DP's first sweep that includes the doubling batch schedule).  probs_out: nprobs such matrices,
+ * zero-filled by the caller; the q-th is that of sweep probs_sweeps[q] (the chain's sweep number j >= 1). */
+int oracle_collapsed_run_probs(const int32_t* X, int64_t N, int P, const int32_t* z0, int nsamples, int K,
+                               double alpha, double beta, double gamma, double a, double b, int burnin,
+                               int64_t batch, uint64_t seed, int32_t* z_out, double* theta_out,
+                               double* alpha_out, int nprobs, const int32_t* probs_sweeps, double* probs_out);
+int oracle_dp_run_probs(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta,
+                        double gamma, double a, double b, int burnin, int maxK, int64_t batch,
+                        uint64_t seed, int32_t* z_out, double* theta_out, double* alpha_out, int nprobs,
+                        const int32_t* probs_sweeps, double* probs_out);
+/* the explicit samplers (variant 0 stick-breaking, 1 full; literal 0 = the *_run form, 1 = *_literal) */
+int oracle_explicit_probs(int variant, int literal, const int32_t* X, int64_t N, int P, const double* pi0,
+                          const double* theta0, int nsamples, int maxK, double alpha, double beta, double gamma,
+                          double a, double b, int burnin, uint64_t seed, double* pi_out, int32_t* z_out,
+                          double* theta_out, double* alpha_out, int nprobs, const int32_t* probs_sweeps,
+                          double* probs_out);
 /* the *_run chains of the two counting samplers without the S x N label trace: cluster sizes per kept
  * sweep (S x K, row-major by sweep), theta-hat, alpha, labels after the last sweep (1-based) */
 int oracle_counts_summary(int sampler, const int32_t* X, int64_t N, int P, const int32_t* z0, int nsamples,

@@ -184,13 +184,39 @@ def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def collapsed(X, z0, nsamples, K, alpha, beta, gamma, a, b, burnin, seed, batch=1, literal=False):
+def _probs_arg(probs_sweep, N, K, nsamples, literal=False):
+    """the optional matrix output of a chain: (sweeps as int32 array, zeroed N x K [x len] output, scalar?)"""
+    if literal:
+        raise ValueError("probs_sweep needs the *_run form (literal=False)")
+    scalar = np.ndim(probs_sweep) == 0
+    sweeps = np.atleast_1d(np.asarray(probs_sweep, dtype=np.int32))
+    if sweeps.size == 0 or sweeps.min() < 1 or sweeps.max() >= nsamples or len(set(sweeps.tolist())) != sweeps.size:
+        raise ValueError("probs_sweep: distinct sweep numbers in 1..nsamples-1")
+    return np.ascontiguousarray(sweeps), np.zeros((N, K, sweeps.size), order="F"), scalar
+
+
+def _probs_out(out, pm, scalar):
+    out["probs"] = pm[:, :, 0] if scalar else pm
+    return out
+
+
+def collapsed(X, z0, nsamples, K, alpha, beta, gamma, a, b, burnin, seed, batch=1, literal=False, probs_sweep=None):
+    """probs_sweep=j (or a sequence of sweeps): the result also carries "probs", the N x K matrix of allocation
+    probabilities of sweep j (N x K x len for a sequence) as the reference stores it for relabelling, every row
+    under the state its batch saw.  The same for dp, stickbreaking and full."""
     X = _x(X)
     N, P = X.shape
     z0 = np.ascontiguousarray(z0, dtype=np.int32)
     S = nsamples - burnin
     z, th, al = _outs(S, N, K, P)
     L = lib()
+    if probs_sweep is not None:
+        sw, pm, scalar = _probs_arg(probs_sweep, N, K, nsamples, literal)
+        _check(L.oracle_collapsed_run_probs(_vp(X), C.c_int64(N), C.c_int(P), _vp(z0), C.c_int(nsamples), C.c_int(K),
+                                            C.c_double(alpha), C.c_double(beta), C.c_double(gamma), C.c_double(a),
+                                            C.c_double(b), C.c_int(burnin), C.c_int64(batch), C.c_uint64(seed),
+                                            _vp(z), _vp(th), _vp(al), C.c_int(sw.size), _vp(sw), _vp(pm)))
+        return _probs_out({"alpha": al, "z": z, "theta": th}, pm, scalar)
     if literal:
         rc = L.oracle_collapsed_literal(_vp(X), C.c_int64(N), C.c_int(P), _vp(z0), C.c_int(nsamples), C.c_int(K),
                                         C.c_double(alpha), C.c_double(beta), C.c_double(gamma), C.c_double(a),
@@ -204,12 +230,19 @@ def collapsed(X, z0, nsamples, K, alpha, beta, gamma, a, b, burnin, seed, batch=
     return {"alpha": al, "z": z, "theta": th}
 
 
-def dp(X, nsamples, alpha, beta, gamma, a, b, burnin, maxK, seed, batch=1, literal=False):
+def dp(X, nsamples, alpha, beta, gamma, a, b, burnin, maxK, seed, batch=1, literal=False, probs_sweep=None):
     X = _x(X)
     N, P = X.shape
     S = nsamples - burnin
     z, th, al = _outs(S, N, maxK, P)
     L = lib()
+    if probs_sweep is not None:
+        sw, pm, scalar = _probs_arg(probs_sweep, N, maxK, nsamples, literal)
+        _check(L.oracle_dp_run_probs(_vp(X), C.c_int64(N), C.c_int(P), C.c_int(nsamples), C.c_double(alpha),
+                                     C.c_double(beta), C.c_double(gamma), C.c_double(a), C.c_double(b),
+                                     C.c_int(burnin), C.c_int(maxK), C.c_int64(batch), C.c_uint64(seed), _vp(z),
+                                     _vp(th), _vp(al), C.c_int(sw.size), _vp(sw), _vp(pm)))
+        return _probs_out({"alpha": al, "z": z, "theta": th}, pm, scalar)
     if literal:
         rc = L.oracle_dp_literal(_vp(X), C.c_int64(N), C.c_int(P), C.c_int(nsamples), C.c_double(alpha),
                                  C.c_double(beta), C.c_double(gamma), C.c_double(a), C.c_double(b),
@@ -242,13 +275,14 @@ def counts_summary(sampler, X, z0, nsamples, K, alpha, beta, gamma, a, b, burnin
     return {"nk": nk, "theta": th, "alpha": al, "z_last": zl}
 
 
-def full(X, pi0, theta0, nsamples, K, alpha, beta, gamma, a, b, burnin, seed, literal=False):
+def full(X, pi0, theta0, nsamples, K, alpha, beta, gamma, a, b, burnin, seed, literal=False, probs_sweep=None):
     """gibbs_cpp (full_gibbs.cpp): the stick-breaking z-step with a Dirichlet pi draw."""
     return stickbreaking(X, pi0, theta0, nsamples, K, alpha, beta, gamma, a, b, burnin, seed, literal=literal,
-                         _fn=("oracle_full_literal" if literal else "oracle_full_run"))
+                         _fn=("oracle_full_literal" if literal else "oracle_full_run"), probs_sweep=probs_sweep)
 
 
-def stickbreaking(X, pi0, theta0, nsamples, maxK, alpha, beta, gamma, a, b, burnin, seed, literal=False, _fn=None):
+def stickbreaking(X, pi0, theta0, nsamples, maxK, alpha, beta, gamma, a, b, burnin, seed, literal=False, _fn=None,
+                  probs_sweep=None):
     X = _x(X)
     N, P = X.shape
     S = nsamples - burnin
@@ -257,6 +291,14 @@ def stickbreaking(X, pi0, theta0, nsamples, maxK, alpha, beta, gamma, a, b, burn
     assert pi0.shape == (maxK,) and theta0.shape == (maxK, P)
     z, th, al = _outs(S, N, maxK, P)
     pi = np.zeros((S, maxK), order="F")
+    if probs_sweep is not None:
+        sw, pm, scalar = _probs_arg(probs_sweep, N, maxK, nsamples)
+        _check(lib().oracle_explicit_probs(C.c_int(int(bool(_fn and "full" in _fn))), C.c_int(int(literal)), _vp(X),
+                                           C.c_int64(N), C.c_int(P), _vp(pi0), _vp(theta0), C.c_int(nsamples),
+                                           C.c_int(maxK), C.c_double(alpha), C.c_double(beta), C.c_double(gamma),
+                                           C.c_double(a), C.c_double(b), C.c_int(burnin), C.c_uint64(seed), _vp(pi),
+                                           _vp(z), _vp(th), _vp(al), C.c_int(sw.size), _vp(sw), _vp(pm)))
+        return _probs_out({"pi": pi, "alpha": al, "z": z, "theta": th}, pm, scalar)
     fn = getattr(lib(), _fn) if _fn else (lib().oracle_sb_literal if literal else lib().oracle_sb_run)
     rc = fn(_vp(X), C.c_int64(N), C.c_int(P), _vp(pi0), _vp(theta0), C.c_int(nsamples), C.c_int(maxK),
             C.c_double(alpha), C.c_double(beta), C.c_double(gamma), C.c_double(a), C.c_double(b),

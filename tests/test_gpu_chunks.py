@@ -17,7 +17,7 @@ import pytest
 
 import bmm_mcmc_amd as bm
 from bmm_mcmc_amd import _capi
-from util import synth
+from util import assert_matrix_equal, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -162,13 +162,15 @@ def _init(case, seed):
     return pi0, th0
 
 
-def _oracle(oracle, case, X, init, S, seed):
+def _oracle(oracle, case, X, init, S, seed, probs_sweep=None):
+    """the oracle chain of a case; probs_sweep=j: with the whole probability matrix of sweep j (its "probs")"""
     if case.sampler == "collapsed":
-        return oracle.collapsed(X, init, S, case.K, 0.0, 0.5, 0.5, 1, 1, 0, seed=seed, batch=case.batch)
+        return oracle.collapsed(X, init, S, case.K, 0.0, 0.5, 0.5, 1, 1, 0, seed=seed, batch=case.batch,
+                                probs_sweep=probs_sweep)
     if case.sampler == "dp":
-        return oracle.dp(X, S, 0.0, 0.5, 0.5, 1, 1, 0, case.K, seed=seed, batch=case.batch)
+        return oracle.dp(X, S, 0.0, 0.5, 0.5, 1, 1, 0, case.K, seed=seed, batch=case.batch, probs_sweep=probs_sweep)
     fn = oracle.stickbreaking if case.sampler == "stickbreaking" else oracle.full
-    return fn(X, init[0], init[1], S, case.K, 0.0, 0.5, 0.5, 1, 1, 0, seed=seed)
+    return fn(X, init[0], init[1], S, case.K, 0.0, 0.5, 0.5, 1, 1, 0, seed=seed, probs_sweep=probs_sweep)
 
 
 def _run(case, X, init, S, seed):
@@ -204,12 +206,16 @@ def probe_rows(lo, hi, threads, grid_max, lanes=1):
     return sorted(r for r in rows if lo <= r < hi)
 
 
-def check_probs(oracle, case, X, probs, z_before, z_after, alpha_before, params_before, threads, grid_max, limit=24):
-    """rows of a hand-off sweep's probabilities against the oracle's conditionals, each under the state its batch
-    saw: the labels already redrawn by the earlier batches of the sweep, the previous sweep's for the rest"""
+def check_probs(oracle, case, X, probs, want_matrix, z_before, z_after, alpha_before, params_before, threads, grid_max,
+                limit=24):
+    """a hand-off sweep's probabilities against the oracle chain's matrix of the same sweep, every row and column bit
+    for bit (the DP's too: the oracle files the new-cluster mass by the reference's rule, tests/test_oracle_probs.py);
+    then rows at the chunk and workgroup edges against the oracle's per-row conditionals, each under the state its
+    batch saw: the labels already redrawn by the earlier batches of the sweep, the previous sweep's for the rest"""
     np.testing.assert_allclose(probs.sum(axis=1), 1.0, rtol=0, atol=1e-13)
+    assert_matrix_equal(probs, want_matrix, case.id)
     if case.sampler == "dp":
-        return   # (the new-cluster mass is filed under a label chosen per batch: tests/test_gpu_parity.py)
+        return   # (no per-row probes: the whole matrix above covers them)
     rows = []
     for lo, hi in batches(case.N, case.batch if case.sampler == "collapsed" else case.N):
         rows += [(lo, r) for r in probe_rows(lo, hi, threads, grid_max)]
@@ -232,12 +238,15 @@ def test_hand_off_probabilities_at_52_accumulators(oracle):
     N, P, K = 6000, 36, 50
     X, _, _, _ = synth(N, P, 5, N + P)
     z0 = np.random.default_rng(5).integers(1, K + 1, N).astype(np.int32)
+    want = oracle.collapsed(X, z0, 3, K, 0.0, 0.5, 0.5, 1, 1, 0, seed=9, batch=N, probs_sweep=2)
     with bm.Chain("collapsed", N, P, K, batch=N, seed=9) as ch:
         ch.set_data(X)
         ch.set_initial_labels(z0)
         ch.sweeps(1)
         zb, alpha = ch.labels(), ch.alpha()
         probs = ch.sweep_probs()
+        assert np.array_equal(ch.labels(), want["z"][2])
+    assert_matrix_equal(probs, want["probs"], "52 accumulators")
     for i in (0, 1, 63, 64, N - 1):
         _, norm = oracle.collapsed_cond(X, zb, i, K, alpha, 0.5, 0.5, spec=True)
         assert np.array_equal(probs[i], norm), i
@@ -265,7 +274,8 @@ def test_every_kernel_form_draws_the_oracle_chain(oracle, dbg_lib, case):
     S, seed = SWEEPS, 11 + case.K + case.P
     X, _, _, _ = synth(case.N, case.P, min(case.K, 5), case.N + case.P)
     init = _init(case, seed)
-    want = _oracle(oracle, case, X, init, S + 1, seed)      # (sample 0 of the oracle's trace: the initial state)
+    # (sample 0 of the oracle's trace: the initial state; with the whole matrix of the hand-off sweep)
+    want = _oracle(oracle, case, X, init, S + 1, seed, probs_sweep=2 if case.probs else None)
     explicit = case.sampler in ("stickbreaking", "full")
     with bm.Chain(case.sampler, case.N, case.P, case.K, batch=case.batch, seed=seed, x_layout=case.layout) as ch:
         key = kernel_key(ch)
@@ -290,7 +300,7 @@ def test_every_kernel_form_draws_the_oracle_chain(oracle, dbg_lib, case):
             z = ch.labels()
             assert np.array_equal(z, want["z"][j]), (case.id, j, int((z != want["z"][j]).sum()))
             if case.probs and j == 2:
-                check_probs(oracle, case, X, probs, z_prev, z, alpha_before, params_before, kp[7], kp[9])
+                check_probs(oracle, case, X, probs, want["probs"], z_prev, z, alpha_before, params_before, kp[7], kp[9])
             z_prev = z
         nk, s = ch.counts()
         assert np.array_equal(nk, np.bincount(z - 1, minlength=case.K)[:case.K]), case.id
@@ -402,6 +412,16 @@ def test_the_cases_reach_every_selectable_kernel(dbg_lib):
         assert got.get(table, set()) == want[table], (table, sorted(want[table] - got.get(table, set())),
                                                       sorted(got.get(table, set()) - want[table]))
     assert set(got) == set(SELECTABLE), sorted(got)
+
+
+def test_every_family_the_dp_can_select_hands_a_matrix_over():
+    """The DP has own-cluster tables, so it selects tier 1 at both group widths and tier 2 (at width 4): each of those
+    families must keep a DP case whose hand-off matrix is compared (check_probs), or a wrong weight of a DP
+    category that was not drawn goes unseen in that family's emitting twins."""
+    families = {(c.tier, c.W) for c in CASES if c.sampler == "dp" and c.probs}
+    assert families == {(1, 5), (1, 4), (2, 4)}, sorted(families)
+    for fam in families:      # and at more than one accumulator count each
+        assert len({kt_of("dp", c.K) for c in CASES if c.sampler == "dp" and c.probs and (c.tier, c.W) == fam}) >= 4, fam
 
 
 def test_a_launch_with_workgroups_that_get_no_chunk(oracle, dbg_lib):
@@ -554,11 +574,12 @@ def test_benchmark_shape_generic_kernel_past_its_grid(oracle):
 
 @pytest.mark.timeout(900)
 def test_benchmark_shape_north_star_hand_off_in_one_launch(oracle):
-    """sweep_probs() at the north-star shape, batch N: rows at chunk and workgroup edges against the oracle"""
+    """sweep_probs() at the north-star shape, batch N: the whole matrix against the oracle chain's, then rows at chunk
+    and workgroup edges against the per-row conditionals"""
     N, P, K = 1_000_000, 50, 20
     X = block_matrix(N, P, 5, 2)
     z0 = np.random.default_rng(12).integers(1, K + 1, N).astype(np.int32)
-    want = oracle.collapsed(X, z0, 3, K, 0.0, 0.5, 0.5, 1, 1, 0, seed=13, batch=N)
+    want = oracle.collapsed(X, z0, 3, K, 0.0, 0.5, 0.5, 1, 1, 0, seed=13, batch=N, probs_sweep=2)
     with bm.Chain("collapsed", N, P, K, batch=N, seed=13) as ch:
         shape = ch.kernel_shape()
         ch.set_data(X)
@@ -569,6 +590,7 @@ def test_benchmark_shape_north_star_hand_off_in_one_launch(oracle):
         probs = ch.sweep_probs()
         assert np.array_equal(ch.labels(), want["z"][2])
     np.testing.assert_allclose(probs.sum(axis=1), 1.0, rtol=0, atol=1e-13)
+    assert_matrix_equal(probs, want["probs"], "north-star hand-off")
     # the emitting twin has the plain kernel's workgroup size and tables, hence its grid limit
     rows = probe_rows(0, N, 1024, shape["grid_max"])
     rows = [rows[i] for i in sorted(set(np.linspace(0, len(rows) - 1, 16).round().astype(int)))]

@@ -176,3 +176,34 @@ def test_posterior_recovers_the_generating_mixture_at_the_default_batch():
         post = torch.softmax(logp, dim=0)
         expected = post[truth, torch.arange(N, device=dev)].mean().item()
         assert agree / N >= expected - 0.01, (agree / N, expected)
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("sampler,K", [("collapsed", 3), ("dp", 4)])
+def test_hand_off_of_a_batch_past_one_trip_of_the_finishing_loop(oracle, sampler, K):
+    """k_probs_finish runs at most 4096 workgroups of 256: a batch above 1 048 576 rows sends its first workgroups
+    round the loop a second time.  N = 2^20 + 300 in one batch, the third sweep's matrix whole against the oracle
+    chain's (the DP's new-cluster mass filed per row)."""
+    import bmm_mcmc_amd as bm
+    from util import assert_matrix_equal
+    N, P = 1_048_576 + 300, 5
+    assert (N + 255) // 256 > 4096                 # past the grid clamp: the shape must not drift below it
+    rng = np.random.default_rng(17)
+    theta = 0.1 + 0.8 * rng.random((3, P))
+    X = np.asfortranarray((rng.random((N, P)) < theta[rng.integers(0, 3, N)]).astype(np.int32))
+    if sampler == "collapsed":
+        z0 = rng.integers(1, K + 1, N).astype(np.int32)
+        want = oracle.collapsed(X, z0, 4, K, 0.0, 0.5, 0.5, 1, 1, 0, seed=23, batch=N, probs_sweep=3)
+    else:
+        want = oracle.dp(X, 4, 0.0, 0.5, 0.5, 1, 1, 0, K, seed=23, batch=N, probs_sweep=3)
+    with bm.Chain(sampler, N, P, K, batch=N, seed=23) as ch:
+        assert ch.batch == N
+        ch.set_data(X)
+        if sampler == "collapsed":
+            ch.set_initial_labels(z0)
+        ch.sweeps(2)                               # two plain sweeps
+        assert np.array_equal(ch.labels(), want["z"][2])
+        probs = ch.sweep_probs()
+        assert np.array_equal(ch.labels(), want["z"][3])
+    np.testing.assert_allclose(probs.sum(axis=1), 1.0, rtol=0, atol=1e-13)
+    assert_matrix_equal(probs, want["probs"], sampler)

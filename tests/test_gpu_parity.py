@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import bmm_mcmc_amd as bm
-from util import load_dataset, proportions, synth
+from util import assert_matrix_equal, load_dataset, proportions, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -357,6 +357,56 @@ def test_collapsed_beyond_the_resident_kernel(oracle, N, P, K, batch):
     got = bm.gibbs_collapsed(X, 5, K, burnin=0, seed=13, batch=batch, initial_K=z0)
     want = oracle.collapsed(X, z0, 5, K, 0.0, 0.5, 0.5, 1, 1, 0, seed=13, batch=batch)
     _same(got, want, ["z", "theta", "alpha"])
+
+
+def _kernel_key(ch):
+    """bmm_dbg_kernel_key (test variant): slot 4 bit planes, 8 generic, 9 the emitting twin's grid limit (0: none)"""
+    import ctypes
+    from bmm_mcmc_amd import _capi
+    k = (ctypes.c_int * 10)()
+    _capi.check(_capi.lib().bmm_dbg_kernel_key(ch._h, k))
+    return tuple(k)
+
+
+@pytest.mark.parametrize("sampler,N,P,K,batch,layout", [
+    ("collapsed", 1200, 200, 5, 300, None),        # P > 128: 40 lookup groups
+    ("collapsed", 900, 40, 100, 900, None),        # 100 categories: seven trips of the 16-wide k0 loop, the last ragged
+    ("stickbreaking", 1500, 10, 70, None, None),   # 70 categories without own-cluster tables
+    ("dp", 1500, 10, 70, 500, None),               # 71 categories, the new-cluster mass filed by k_probs_finish
+    ("collapsed", 3000, 36, 50, 1000, "int32")])   # a resident int32 chain: no emitting twin, the hand-off is generic
+def test_generic_kernel_hands_over_the_oracle_matrix(oracle, dbg_lib, sampler, N, P, K, batch, layout):
+    """sweep_probs() where k_resample_generic is the only emitter, the whole matrix against the oracle chain's: the
+    labels alone cannot see a wrong weight of a category that was not drawn"""
+    for name in ("BMM_DEBUG_CUS", "BMM_DEBUG_NOSPLIT", "BMM_DEBUG_SPLIT", "BMM_DEBUG_NOSELF", "BMM_DEBUG_GENERIC",
+                 "BMM_X_LAYOUT_INT32"):
+        dbg_lib.delenv(name, raising=False)
+    X, _, _, _ = synth(N, P, 4, 31)
+    sweeps = [2, 3]
+    if sampler == "collapsed":
+        z0 = _z0(N, K, 2)
+        want = oracle.collapsed(X, z0, 4, K, 0.0, 0.5, 0.5, 1, 1, 0, seed=13, batch=batch, probs_sweep=sweeps)
+    elif sampler == "dp":
+        want = oracle.dp(X, 4, 0.0, 0.5, 0.5, 1, 1, 0, K, seed=13, batch=batch, probs_sweep=sweeps)
+    else:
+        pi0, th0 = _sb_init(K, P, 9)
+        want = oracle.stickbreaking(X, pi0, th0, 4, K, 0.0, 0.5, 0.5, 1, 1, 0, seed=13, probs_sweep=sweeps)
+    with bm.Chain(sampler, N, P, K, batch=batch, seed=13, x_layout=layout) as ch:
+        key = _kernel_key(ch)
+        # the chain's own kernel is the generic one -- or, for the int32 layout, a resident kernel without bit planes
+        assert (key[8] == 1) if layout is None else (key[8] == 0 and key[4] == 0), key
+        ch.set_data(X)
+        if sampler == "collapsed":
+            ch.set_initial_labels(z0)
+        elif sampler != "dp":
+            ch.set_initial_params(pi0, th0)
+        ch.sweeps(1)
+        assert np.array_equal(ch.labels(), want["z"][1])
+        for q, j in enumerate(sweeps):
+            probs = ch.sweep_probs()
+            assert _kernel_key(ch)[9] == 0                  # no emitting twin was set up: the generic kernel emitted
+            assert np.array_equal(ch.labels(), want["z"][j]), j
+            np.testing.assert_allclose(probs.sum(axis=1), 1.0, rtol=0, atol=1e-13)
+            assert_matrix_equal(probs, want["probs"][:, :, q], "%s sweep %d" % (sampler, j))
 
 
 def test_dp_and_explicit_samplers_beyond_the_resident_kernel(oracle):

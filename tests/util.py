@@ -40,3 +40,16 @@ def synth(N, P, K_true, seed, shuffle=True):
         perm = rng.permutation(N)
         X, labels = X[perm], labels[perm]
     return np.asfortranarray(X), labels, theta, w
+
+
+def assert_matrix_equal(got, want, what=""):
+    """np.array_equal over a whole matrix; on a mismatch the message names the first differing (row, column) -- the
+    first row that differs, and its first column -- both values there, and how many entries differ"""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    if np.array_equal(got, want):
+        return
+    bad = np.argwhere(~((got == want) | (np.isnan(got) & np.isnan(want))))
+    idx = tuple(int(v) for v in bad[0])
+    raise AssertionError("%s: %d of %d entries differ, the first at (row, column%s) = %s: got %r, want %r"
+                         % (what, len(bad), got.size, ", slice" if got.ndim == 3 else "", idx, got[idx], want[idx]))
