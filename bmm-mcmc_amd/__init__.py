@@ -501,7 +501,51 @@ def _make_features(select_features, rho, P, S, chains, beta, gamma, dp, newdata,
     return _Features(rho, P, S)
 
 
-def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None):
+# ---------------------------------------------------------------- init=: the k-modes++ start on the device
+INIT_KINDS = {"kmodes": 1}
+INIT_ITERS = 10  # a cap, not a tuned value: the refinement stops at the first round that changes no label
+
+
+class _InitInfo(_C.Structure):  # bmm_init_info
+    _fields_ = [("k_eff", _C.c_int32), ("rounds_run", _C.c_int32), ("changed_last", _C.c_int64), ("cost", _C.c_int64),
+                ("device_ms", _C.c_double)]
+
+    def as_dict(self):
+        return {"k_eff": int(self.k_eff), "rounds_run": int(self.rounds_run), "changed_last": int(self.changed_last),
+                "cost": int(self.cost), "device_ms": float(self.device_ms)}
+
+
+def _init_kind(init, init_iters, allowed=True):
+    """None for the random start, else (kind, iters); `allowed`: whether the sampler offers a data-driven start"""
+    if init is None or init == "random":
+        return None
+    if not allowed:
+        raise ValueError("init=%r: a data-driven start is offered by gibbs_collapsed only (Chain.init_labels seats a "
+                         "resident DP chain)" % (init,))
+    if init not in INIT_KINDS:
+        raise ValueError('init must be "random" or "kmodes"')
+    iters = int(init_iters)
+    if iters < 0:
+        raise ValueError("init_iters must be >= 0")
+    return INIT_KINDS[init], iters
+
+
+class _Init:
+    """init= of gibbs_collapsed, armed for exactly one run"""
+
+    def __init__(self, kind, iters):
+        self.kind, self.iters = kind, iters
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_init(_C.c_int(self.kind), _C.c_int(self.iters)))
+
+    def result(self):
+        info = _InitInfo()
+        _capi.check(_capi.lib().bmm_last_init_info(_C.byref(info)))
+        return info.as_dict()
+
+
+def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
@@ -513,6 +557,8 @@ def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=
         part.arm()
     if loo is not None:
         loo.arm()
+    if init is not None:  # last, just ahead of the call: a run of another sampler refuses an armed start
+        init.arm()
     if pr is None:
         if rel is not None:
             return getattr(L, "bmm_%s_run_relabel" % base)(*args, rel.ref())
@@ -668,7 +714,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                     relabel=False, burnrelabel=50, debug=False, *, seed=None, batch=None, device=0,
                     initial_K=None, chains=1, devices=None, stephens=None, newdata=None, predictive_trace=False,
                     responsibilities=False, partition=None, partition_stride=1, similarity_of=None, loo=False,
-                    select_features=False, rho=0.5):
+                    select_features=False, rho=0.5, init="random", init_iters=INIT_ITERS):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -704,10 +750,21 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     the indicators per kept sweep, their mean, the mean of their conditional probabilities (less noisy) and the number
     of included features per sweep; "n_folded" is the number of kept sweeps behind the two means (the starting row of a
     run without burn-in is not one).  Per chain; not with newdata=, loo= (or split_merge= on gibbs_dp).
+    `init="kmodes"`: the chain starts from a k-modes++ allocation computed on the device from the resident bit planes
+    (k-means++ seeding under Hamming distance with K centres, then at most `init_iters` k-modes rounds, stopping at the
+    first that changes no label; include/bmm_mcmc.h "initial allocation") instead of the uniform
+    random one; no label crosses PCIe, and the result gains `init = {"k_eff", "rounds_run", "changed_last", "cost",
+    "device_ms"}`.  Not together with `initial_K`.  With `chains > 1` chain c is initialised with seed + c by a resident
+    chain on device 0 and its labels are handed to the multi-chain call as `initial_K`: that one round trip of N labels
+    per chain over PCIe is accepted there.  `init="random"`, the default, is the code path it always was.
     """
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, K = int(nsamples), int(K)
+    ik = _init_kind(init, init_iters)
+    if ik is not None and initial_K is not None:
+        raise ValueError('init="kmodes" computes the starting labels: not together with initial_K')
+    ini = None if ik is None else _Init(*ik)
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
     chains = int(chains)
@@ -719,14 +776,28 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     def done(out):
         if fs is not None:
             out["features"] = fs.result()
+        if ini is not None:
+            out["init"] = ini.result()
         return out
     if chains > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
+        if ini is not None:
+            initial_K, infos = [], []
+            for c in range(chains):
+                with Chain("collapsed", N, P, K, alpha=alpha, beta=beta, gamma=gamma, a=a, b=b, seed=seed + c, device=0) as ch:
+                    ch.set_data(X)
+                    info = ch.init_labels("kmodes", iters=ik[1])
+                    infos.append({k: info[k] for k in ("k_eff", "rounds_run", "changed_last", "cost", "device_ms")})
+                    initial_K.append(ch.labels())
         z0s = [_np.ascontiguousarray(_np.random.default_rng(seed + c).integers(1, K + 1, N), dtype=_np.int32)
                for c in range(chains)] if initial_K is None else [_np.ascontiguousarray(z, dtype=_np.int32) for z in initial_K]
-        return _pooled(_multi("collapsed", X, chains, devices, z0s, None, None, nsamples, K, alpha, beta, gamma, a, b,
+        outs = _pooled(_multi("collapsed", X, chains, devices, z0s, None, None, nsamples, K, alpha, beta, gamma, a, b,
                       burnin, batch, seed, False), partition, partition_stride, similarity_of, device if devices is None else int(devices[0]))
+        if ini is not None:
+            for o, info in zip(outs, infos):
+                o["init"] = info
+        return outs
     if initial_K is None:
         initial_K = _np.random.default_rng(seed).integers(1, K + 1, N)
     z0 = _np.ascontiguousarray(initial_K, dtype=_np.int32)
@@ -744,7 +815,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
                 _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs)
+            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
@@ -755,7 +826,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
             _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -767,14 +838,16 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
              burnrelabel=50, maxK=30, debug=False, *, seed=None, batch=None, device=0, chains=1, devices=None,
              stephens=None, newdata=None, predictive_trace=False, responsibilities=False, partition=None,
              partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None,
-             select_features=False, rho=0.5):
+             select_features=False, rho=0.5, init="random"):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
     split-merge Metropolis-Hastings moves (Jain & Neal 2004, include/bmm_mcmc.h) at the start of every sweep from the
     second, each with `split_merge_scans` intermediate restricted scans (default SPLIT_MERGE_SCANS); the result gains
     `split_merge = {"split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped"}`.  Per chain.
-    `select_features`, `rho`: as gibbs_collapsed (needs beta == gamma; not with split_merge=)."""
+    `select_features`, `rho`: as gibbs_collapsed (needs beta == gamma; not with split_merge=).  `init`: "random" only (a
+    DP run seats its rows in its first sweep; Chain.init_labels re-seats a resident DP chain)."""
+    _init_kind(init, 0, allowed=False)
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, maxK = int(nsamples), int(maxK)
@@ -904,10 +977,12 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
                         relabel=False, burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None,
                         initial_theta=None, chains=1, devices=None, stephens=None, newdata=None,
                         predictive_trace=False, responsibilities=False, partition=None, partition_stride=1,
-                        similarity_of=None, loo=False):
+                        similarity_of=None, loo=False, init="random"):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
     src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
-    `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic"."""
+    `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
+    "random" only (the sampler starts from pi and theta)."""
+    _init_kind(init, 0, allowed=False)
     return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
                      burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo)
@@ -916,9 +991,11 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
                burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None, initial_theta=None, chains=1,
                devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False,
-               partition=None, partition_stride=1, similarity_of=None, loo=False):
+               partition=None, partition_stride=1, similarity_of=None, loo=False, init="random"):
     """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
-    `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic"."""
+    `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
+    "random" only (the sampler starts from pi and theta)."""
+    _init_kind(init, 0, allowed=False)
     return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
                      relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo)
@@ -1201,6 +1278,28 @@ class Chain:
         _capi.check(_capi.lib().bmm_chain_set_labels(self._h, _capi.vp(z1)))
 
     # -- feature selection (include/bmm_mcmc.h "feature selection")
+    def init_labels(self, kind="kmodes", centres=None, iters=INIT_ITERS):
+        """The k-modes++ start on the device (include/bmm_mcmc.h "initial allocation"): the initial labels of a collapsed
+        chain that has its data and has not started, or a new allocation of a seated DP chain between sweeps (`centres`
+        must be given there; default K for the collapsed sampler).  Returns the record {"k_eff", "rounds_run",
+        "changed_last", "cost", "device_ms"} with "rows" (the picked rows, 0-based), "centres" (k_eff x P, 0/1) and "Nk"
+        (k_eff)."""
+        if kind not in INIT_KINDS:
+            raise ValueError('kind must be "kmodes"')
+        info = _InitInfo()
+        L = _capi.lib()
+        _capi.check(L.bmm_chain_init_labels(self._h, _C.c_int(INIT_KINDS[kind]), _C.c_int(0 if centres is None else int(centres)),
+                                            _C.c_int(int(iters)), _C.byref(info)))
+        out = info.as_dict()
+        ke, W = out["k_eff"], (self.P + 31) // 32
+        words = _np.zeros((ke, W), dtype=_np.uint32)
+        rows, nk = _np.zeros(ke, dtype=_np.int64), _np.zeros(ke, dtype=_np.int32)
+        _capi.check(L.bmm_chain_get_init_centres(self._h, _capi.vp(words)))
+        _capi.check(L.bmm_chain_get_init_rows(self._h, _capi.vp(rows), _capi.vp(nk)))
+        bits = (words[:, :, None] >> _np.arange(32, dtype=_np.uint32)[None, None, :]) & _np.uint32(1)
+        out.update(rows=rows, Nk=nk, centres=bits.reshape(ke, W * 32)[:, :self.P].astype(_np.uint8))
+        return out
+
     def set_feature_select(self, on=True, rho=0.5):
         """a gamma-step behind every sweep from now on (on=False: no more steps, the mask stays)"""
         _capi.check(_capi.lib().bmm_chain_set_feature_select(self._h, _C.c_int(1 if on else 0), _C.c_double(float(rho))))

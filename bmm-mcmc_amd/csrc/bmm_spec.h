@@ -56,6 +56,7 @@ enum : uint32_t {
     kStreamAlphaG2 = 7,  // Gamma(a+K-1)
     kStreamSplitMerge = 8,  // a split-merge move: c0 = move index, c1 = block counter, c2 = sweep (sm_move_draws)
     kStreamFeatureSelect = 9,  // the inclusion indicator of feature d after sweep j: c0 = d, c1 = block counter, c2 = j (fs_uniform)
+    kStreamInit = 10,    // the pick of centre j of the k-modes++ start: c0 = j, c1 = block counter, c2 = 0 (init_uniform)
 };
 
 // ---------------------------------------------------------------- bit helpers
@@ -183,6 +184,19 @@ BMM_HD double fs_uniform(uint64_t seed, uint32_t d, uint32_t sweep) {
     Stream st = make_stream(seed, d, sweep, kStreamFeatureSelect);
     const U4 r = st.next();
     return u01(r.x, r.y);
+}
+
+// The uniform that picks centre j of the k-modes++ initial allocation (include/bmm_mcmc.h "initial allocation"): the
+// first block of a stream of its own, so it shares no (key, counter) pair with any other draw.
+BMM_HD double init_uniform(uint64_t seed, uint32_t j) {
+    Stream st = make_stream(seed, j, 0, kStreamInit);
+    const U4 r = st.next();
+    return u01(r.x, r.y);
+}
+// the valid bits of word w of a row of P features (every word but the last one is full)
+BMM_HD uint32_t init_word_mask(int P, int w) {
+    const int rest = P - 32 * w;
+    return rest >= 32 ? 0xffffffffu : ((1u << rest) - 1u);
 }
 
 // ---------------------------------------------------------------- log / exp

@@ -582,6 +582,12 @@ struct bmm_chain {
     int fs_folded = 0, fs_from = 0, fs_last = -1;  // fs_last: the sweep of the last step, -1 none yet
     uint8_t* fs_trace = nullptr;  // or [..][P] on the device: row j - fs_trace_base receives sweep j's indicators
     int fs_trace_base = 0;
+    // the last k-modes++ initialisation, kept on the host: the k_eff centres [k_eff][W], the
+    // picked rows and the final cluster sizes
+    int init_keff = 0;
+    std::vector<uint32_t> init_centres;
+    std::vector<long long> init_rows;
+    std::vector<int32_t> init_nk;
     int prof = 0;             // > 0: HIP events around the resample launches of every prof-th sweep
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
@@ -1180,6 +1186,140 @@ int enqueue_fs_gamma(bmm_chain* c, int j) {
     HIP_TRY(hipGetLastError());
     if (a.fold) c->fs_folded++;
     c->fs_last = j;
+    return BMM_OK;
+}
+
+// ---- k-modes++ initial allocation ----
+// who may be initialised on the device, whatever the moment
+int init_refused(const bmm_chain* c) {
+    if (c->sharded) return set_err(BMM_E_STATE, "the initialisation is not offered on a sharded chain");
+    if (explicit_params(c->p.mode))
+        return set_err(BMM_E_UNSUPPORTED, "a data-driven start is offered for the collapsed and DP samplers only: the stick-breaking and "
+                       "full samplers start from pi and theta");
+    if (!c->bits) return set_err(BMM_E_UNSUPPORTED, "the initialisation reads the bit planes: not offered on the int32 layout");
+    return BMM_OK;
+}
+// whether k_init_assign counts its labels in LDS (centres and histogram within kInitLdsBudget: at K = 20 up to P = 1587) or
+// leaves the counting to k_count_labels_generic: a pure function of (Kc, P)
+bool init_counts_in_lds(int Kc, int P) {
+    const size_t W = ((size_t)P + 31) / 32;
+    return (size_t)Kc * W * 4 + (size_t)Kc * ((size_t)P + 1) * 4 <= kInitLdsBudget;
+}
+// One initialisation into `lab` (N labels, 0-based) on the chain's stream: every launch enqueued at once, one wait at
+// the end.  The chain itself is not touched.
+int init_run(bmm_chain* c, int kind, int Kc, int iters, int32_t* lab, bmm_init_info* info) {
+    const ChainParams& p = c->p;
+    if (kind != BMM_INIT_KMODES) return set_err(BMM_E_ARG, "unknown kind of initialisation %d", kind);
+    if (Kc < 1 || Kc > p.K) return set_err(BMM_E_ARG, "n_centres = %d outside 1..%d", Kc, p.K);
+    if (iters < 0) return set_err(BMM_E_ARG, "iters must be >= 0");
+    const size_t W = ((size_t)p.P + 31) / 32, N = (size_t)p.N;
+    if ((size_t)Kc * W * 4 > (size_t)kInitMaxCentreBytes)
+        return set_err(BMM_E_UNSUPPORTED, "%d centres of %zu words need %zu bytes, above the %d the initialisation keeps in LDS", Kc, W,
+                       (size_t)Kc * W * 4, kInitMaxCentreBytes);
+    if (!c->have_data || !c->dXb) return set_err(BMM_E_STATE, "data matrix not set");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t nb = (N + kInitThreads - 1) / kInitThreads;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    // one block: the cell, the rows, the counts and the centres (cleared together), then dist and the block sums
+    const size_t o_rows = up(sizeof(InitCell)), o_nk = o_rows + up((size_t)Kc * 8), o_s = o_nk + up((size_t)Kc * 4),
+                 o_cen = o_s + up((size_t)Kc * p.P * 4), o_dist = o_cen + up((size_t)Kc * W * 4), o_bs = o_dist + up(N * 4),
+                 bytes = o_bs + up(nb * 4);
+    DevBuf blk;
+    HIP_TRY(blk.alloc(bytes));
+    char* const b0 = blk.as<char>();
+    HIP_TRY(hipMemsetAsync(b0, 0, o_dist, c->stream));
+    InitArgs a{};
+    a.Xb = c->dXb; a.lab = lab; a.cell = reinterpret_cast<InitCell*>(b0); a.rows = reinterpret_cast<long long*>(b0 + o_rows);
+    a.Nk = reinterpret_cast<int32_t*>(b0 + o_nk); a.S = reinterpret_cast<int32_t*>(b0 + o_s);
+    a.centres = reinterpret_cast<uint32_t*>(b0 + o_cen); a.dist = reinterpret_cast<int32_t*>(b0 + o_dist);
+    a.blocksum = reinterpret_cast<int32_t*>(b0 + o_bs); a.Kc = Kc;
+    struct Timed {  // (EventPair's events carry no time)
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~Timed() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    HIP_TRY(hipEventCreate(&ev.e[0]));
+    HIP_TRY(hipEventCreate(&ev.e[1]));
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    const dim3 grid((unsigned)nb), wg(kInitThreads);
+    for (int m = 0; m < Kc; ++m) {
+        if (m > 0) hipLaunchKernelGGL(k_init_pick, dim3(1), dim3(1024), 0, c->stream, p, a, m, (int)nb);
+        hipLaunchKernelGGL(k_init_dist, grid, wg, 0, c->stream, p, a, m);
+        HIP_TRY(hipGetLastError());
+    }
+    const bool in_lds = init_counts_in_lds(Kc, p.P);
+    const size_t cen_bytes = (size_t)Kc * W * 4, lds = cen_bytes + (in_lds ? (size_t)Kc * (p.P + 1) * 4 : 0);
+    // up to kInitLdsBudget (or kInitMaxCentreBytes) of dynamic LDS on top of the kernel's static bytes: past 64 KiB in all
+    HIP_TRY(hipFuncSetAttribute(in_lds ? reinterpret_cast<const void*>(k_init_assign<true>) : reinterpret_cast<const void*>(k_init_assign<false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (int r = 0; r <= iters; ++r) {
+        if (r > 0) hipLaunchKernelGGL(k_init_modes, dim3((unsigned)Kc), wg, 0, c->stream, p, a, r);
+        if (in_lds) {
+            hipLaunchKernelGGL(k_init_assign<true>, grid, wg, lds, c->stream, p, a, r);
+        } else {
+            // (after `done` the labels no longer change, and the recount of unchanged labels gives the same counts)
+            hipLaunchKernelGGL(k_init_assign<false>, grid, wg, lds, c->stream, p, a, r);
+            HIP_TRY(hipMemsetAsync(b0 + o_nk, 0, o_cen - o_nk, c->stream));
+            hipLaunchKernelGGL(k_count_labels_generic, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, c->stream, p,
+                               (const int32_t*)nullptr, c->dXb, lab, a.Nk, a.S);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    InitCell h{};
+    c->init_centres.assign((size_t)Kc * W, 0u);
+    c->init_rows.assign((size_t)Kc, 0);
+    c->init_nk.assign((size_t)Kc, 0);
+    HIP_TRY(hipMemcpyAsync(&h, a.cell, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->init_rows.data(), a.rows, (size_t)Kc * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->init_nk.data(), a.Nk, (size_t)Kc * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->init_centres.data(), a.centres, cen_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    c->init_keff = h.k_eff;
+    c->init_centres.resize((size_t)h.k_eff * W);
+    c->init_rows.resize((size_t)h.k_eff);
+    c->init_nk.resize((size_t)h.k_eff);
+    if (info) {
+        info->k_eff = h.k_eff;
+        info->rounds_run = h.rounds_run;
+        info->changed_last = h.rounds_run > 0 ? h.changed[h.rounds_run & 1] : 0;
+        info->cost = h.cost[h.rounds_run & 1];
+        info->device_ms = (double)ms;
+    }
+    return BMM_OK;
+}
+// ... and into the chain: a collapsed chain that has not started gets its initial labels, a seated DP chain between
+// sweeps a new allocation and the recount (the tail of bmm_chain_set_labels)
+int init_labels(bmm_chain* c, int kind, int n_centres, int iters, bmm_init_info* info) {
+    int rc = init_refused(c);
+    if (rc) return rc;
+    const ChainParams& p = c->p;
+    if (p.mode == MODE_COLLAPSED) {
+        if (c->started) return set_err(BMM_E_STATE, "chain already started");
+        rc = init_run(c, kind, n_centres == 0 ? p.K : n_centres, iters, c->dZ[0], info);
+        if (rc) return rc;
+        c->have_init = true;
+        return BMM_OK;
+    }
+    rc = sm_seated(c);
+    if (rc) return rc;
+    if (n_centres == 0) return set_err(BMM_E_ARG, "n_centres must be given for the DP sampler (1..%d)", p.K);
+    int32_t* const cur = label_row(c, c->sweep);
+    int32_t* const other = c->dZ[(c->sweep + 1) & 1];  // the row the next sweep will overwrite
+    rc = init_run(c, kind, n_centres, iters, other, info);
+    if (rc) return rc;
+    const size_t K = (size_t)p.K, KP = K * p.P;
+    const int64_t nb = (p.N + 255) / 256;
+    HIP_TRY(hipMemcpyAsync(cur, other, (size_t)p.N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->dNk, 0, K * sizeof(int32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(c->dS, 0, KP * sizeof(int32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(c->dDNk, 0, K * kDeltaReps * sizeof(int32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(c->dDS, 0, KP * kDeltaReps * sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(k_count_labels_generic, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, c->stream, c->p, c->dX, c->dXb, cur,
+                       c->dNk, c->dS);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return BMM_OK;
 }
 
@@ -2502,6 +2642,30 @@ int bmm_chain_set_labels(bmm_chain* c, const int32_t* z1) {
     });
 }
 
+// ---- k-modes++ initial allocation ----
+int bmm_chain_init_labels(bmm_chain* c, int kind, int n_centres, int iters, bmm_init_info* info) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+        return init_labels(c, kind, n_centres, iters, info);
+    });
+}
+
+int bmm_chain_get_init_centres(bmm_chain* c, uint32_t* words) {
+    if (!c || !words) return set_err(BMM_E_ARG, "null argument");
+    if (c->init_keff < 1) return set_err(BMM_E_STATE, "the chain has not been initialised on the device");
+    std::memcpy(words, c->init_centres.data(), c->init_centres.size() * sizeof(uint32_t));
+    return BMM_OK;
+}
+
+int bmm_chain_get_init_rows(bmm_chain* c, int64_t* rows, int32_t* Nk) {
+    if (!c || !rows) return set_err(BMM_E_ARG, "null argument");
+    if (c->init_keff < 1) return set_err(BMM_E_STATE, "the chain has not been initialised on the device");
+    for (int k = 0; k < c->init_keff; ++k) rows[k] = c->init_rows[(size_t)k];
+    if (Nk) std::memcpy(Nk, c->init_nk.data(), c->init_nk.size() * sizeof(int32_t));
+    return BMM_OK;
+}
+
 // ---- feature selection ----
 // who may carry a mask: the two counting samplers, whole (not sharded), with rows that have or will get seats
 static int fs_refused(const bmm_chain* c) {
@@ -3151,12 +3315,13 @@ int run_sweeps_reported(bmm_chain* c, int nsamples, const std::function<int(int)
 }
 
 // the starting state of a run: initial labels or parameters, and trace row 0 when burnin = 0
-int run_start_state(bmm_chain* c, const RunIO& io) {
+int run_start_state(bmm_chain* c, const RunIO& io, bool device_init = false) {
     const int sampler = c->p.mode, K = c->p.K, P = c->p.P, S = c->S, burnin = c->burnin;
     const int64_t N = c->p.N;
     HIP_TRY(hipSetDevice(c->device));
     int rc = BMM_OK;
-    if (sampler == BMM_SAMPLER_COLLAPSED) rc = bmm_chain_set_initial_labels(c, io.z0);
+    // (device_init: the labels are computed on the device once the planes are there, bmm_set_init)
+    if (sampler == BMM_SAMPLER_COLLAPSED && !device_init) rc = bmm_chain_set_initial_labels(c, io.z0);
     if (explicit_params(sampler)) rc = bmm_chain_set_initial_params(c, io.pi0, io.theta0);
     if (rc) return rc;
     if (burnin == 0) {
@@ -3410,7 +3575,11 @@ thread_local int64_t g_sm_stats[5] = {0, 0, 0, 0, 0};
 // ... and feature selection (bmm_set_feature_select)
 struct FsArmed { bool on = false; bmm_feature_out o{}; };
 thread_local FsArmed g_fs;
-struct PtDisarm { ~PtDisarm() { g_partition.on = false; g_loo.on = false; g_sm.moves = 0; g_fs.on = false; } };
+// ... and the device start of a collapsed run (bmm_set_init)
+struct InitArmed { int kind = 0, iters = 0; };
+thread_local InitArmed g_init;
+thread_local bmm_init_info g_init_info{};
+struct PtDisarm { ~PtDisarm() { g_partition.on = false; g_loo.on = false; g_sm.moves = 0; g_fs.on = false; g_init.kind = 0; } };
 // what a run checks of it before any device is touched
 int pt_check_armed(const bmm_partition_out& o, int S, int64_t N, int K) {
     if (!o.loss || !o.best || !o.n_used) return set_err(BMM_E_ARG, "partition: null buffer (loss, best, n_used)");
@@ -3589,6 +3758,9 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             rc = pt_check_armed(g_partition.o, nsamples - burnin, N, K);
             if (rc) return rc;
         }
+        g_init_info = bmm_init_info{};
+        if (g_init.kind != 0 && sampler != BMM_SAMPLER_COLLAPSED)  // refused before any device is touched
+            return set_err(BMM_E_UNSUPPORTED, "a device start is armed (bmm_set_init): offered for runs of the finite collapsed sampler only");
         if (pred) {  // refused before any device is touched
             if (M < 0) return set_err(BMM_E_ARG, "M must be >= 0");
             if (M > 0 && !Xnew) return set_err(BMM_E_ARG, "Xnew is null");
@@ -3632,7 +3804,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
         {
             struct Guard { bmm_chain* c; ~Guard() { bmm_chain_destroy(c); } } guard{c};
             rc = run_prepare(c, nsamples, burnin);
-            if (rc == BMM_OK) rc = run_start_state(c, io);
+            if (rc == BMM_OK) rc = run_start_state(c, io, g_init.kind != 0);
             if (rc) return rc;
             clock.lap(1);
             pack.join();
@@ -3645,6 +3817,10 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
                 rc = bmm_chain_set_data_host(c, X);
             }
             if (rc) return rc;
+            if (g_init.kind != 0) {  // the start armed for this run, from the planes that have just arrived
+                rc = init_labels(c, g_init.kind, 0, g_init.iters, &g_init_info);
+                if (rc) return rc;
+            }
             clock.lap(0);
             // the predictive of new rows: every kept sweep is folded as it is enqueued (sweep_end_predict)
             const bool predict = pred && M > 0;
@@ -4072,6 +4248,18 @@ int bmm_set_split_merge(int moves_per_sweep, int scans) {
     if (moves_per_sweep < 0 || scans < 0 || scans > 4096) return set_err(BMM_E_ARG, "moves_per_sweep and scans must be >= 0 (scans at most 4096)");
     g_sm.moves = moves_per_sweep;
     g_sm.scans = scans;
+    return BMM_OK;
+}
+int bmm_set_init(int kind, int iters) {
+    if (kind != 0 && kind != BMM_INIT_KMODES) return set_err(BMM_E_ARG, "unknown kind of initialisation %d", kind);
+    if (iters < 0) return set_err(BMM_E_ARG, "iters must be >= 0");
+    g_init.kind = kind;
+    g_init.iters = iters;
+    return BMM_OK;
+}
+int bmm_last_init_info(bmm_init_info* info) {
+    if (!info) return set_err(BMM_E_ARG, "null argument");
+    *info = g_init_info;
     return BMM_OK;
 }
 int bmm_last_split_merge_stats(int64_t out[5]) {

@@ -3062,6 +3062,269 @@ __global__ __launch_bounds__(kFsThreads) void k_fs_gamma(ChainParams p, FsArgs a
     if (tid == 0) a.mask[blockIdx.x] = sh_word;
 }
 
+// ---- k-modes++ initial allocation (include/bmm_mcmc.h "initial allocation") ---------------
+// Seeding: k_init_dist(0), then k_init_pick(j), k_init_dist(j) for j = 1 .. Kc - 1; seating: k_init_assign(0), which
+// gives every row its nearest seeded centre (the strict minimum of the seeding, so the labels it writes are `near`)
+// and counts them; refinement round r = 1 .. iters: k_init_modes(r), k_init_assign(r).  All stream-ordered, nothing is
+// read back in between: the cell's `stop` (fewer distinct rows than centres) and `done` (a round changed no label)
+// make the launches that are left over return at once.  Integers throughout; the one product per centre is
+// init_uniform * (double)T.  A workgroup holds 256 consecutive rows, one per lane.
+constexpr int kInitThreads = 256;
+constexpr int kInitMaxCentreBytes = 65536;  // Kc * W * 4 above this is refused (the centres live in LDS)
+// centres and the count histogram of k_init_assign in dynamic LDS up to here (of the 160 KiB of a gfx950 workgroup; the
+// kernel has a few bytes of static LDS besides, and its launches set the attribute that allows the size); above it
+// the labels are counted by k_count_labels_generic behind the launch
+constexpr size_t kInitLdsBudget = 131072;
+struct InitCell {
+    int32_t k_eff, stop, done, rounds_run;
+    long long changed[2], cost[2];  // of the assign launch of round r in slot r & 1 (the seating counts as round 0)
+};
+struct InitArgs {
+    const uint32_t* Xb;
+    int32_t *dist, *lab;   // [N]: distance to the nearest centre so far; the labels (0-based)
+    int32_t* blocksum;     // [ceil(N / 256)]: sum of dist over a workgroup's rows (at most 256 * (P + 1) < 2^31)
+    uint32_t* centres;     // [Kc][W], the last word masked to its valid bits
+    long long* rows;       // [Kc]: the picked rows
+    int32_t *Nk, *S;       // [Kc], [Kc][P]: counts of the labels of the last assign launch
+    InitCell* cell;
+    int Kc;
+};
+
+// inclusive prefix sum over the workgroup (wave scan, then the wave totals through LDS); shw: one slot per wave
+__device__ __forceinline__ long long init_block_scan(long long v, long long* shw, long long& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    long long x = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    __syncthreads();  // shw may still be read from an earlier call
+    if (lane == 63) shw[wave] = x;
+    __syncthreads();
+    long long before = 0, tot = 0;
+    for (int w = 0; w < nw; ++w) {
+        const long long s = shw[w];
+        tot += s;
+        if (w < wave) before += s;
+    }
+    total = tot;
+    return x + before;
+}
+
+// Centre m against every row: Hamming distance by XOR and popcount, strict minimum into dist / lab (ties keep the
+// lower label), and the workgroup's sum of dist.  Centre 0 is row r_0, which every workgroup derives from the draw
+// itself; later centres were written by k_init_pick.  The centre's words are read through one address per wave.
+__global__ __launch_bounds__(kInitThreads) void k_init_dist(ChainParams p, InitArgs a, int m) {
+    __shared__ int sh_sum;
+    InitCell* const cell = a.cell;
+    if (m > 0 && cell->stop) return;
+    const int tid = threadIdx.x, P = p.P, W = (P + 31) >> 5;
+    const int64_t N = p.N;
+    const uint32_t* src = a.centres + (size_t)m * W;
+    int64_t stride = 1;
+    if (m == 0) {
+        int64_t r0 = (int64_t)(init_uniform(p.seed, 0u) * (double)N);
+        r0 = r0 > N - 1 ? N - 1 : r0;
+        src = a.Xb + r0;
+        stride = N;
+        if (blockIdx.x == 0) {
+            for (int w = tid; w < W; w += kInitThreads) a.centres[w] = src[(int64_t)w * N] & init_word_mask(P, w);
+            if (tid == 0) { a.rows[0] = r0; cell->k_eff = a.Kc; }
+        }
+    }
+    if (tid == 0) sh_sum = 0;
+    __syncthreads();
+    const int64_t r = (int64_t)blockIdx.x * kInitThreads + tid;
+    int d = 0;
+    if (r < N) {
+        int h = 0;
+        for (int w = 0; w < W; ++w) h += __popc((a.Xb[(int64_t)w * N + r] ^ src[(int64_t)w * stride]) & init_word_mask(P, w));
+        d = m == 0 ? P + 1 : a.dist[r];
+        if (h < d) { d = h; a.dist[r] = h; a.lab[r] = m; }
+    }
+    for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o);
+    if ((tid & 63) == 0) atomicAdd(&sh_sum, d);
+    __syncthreads();
+    if (tid == 0) a.blocksum[blockIdx.x] = sh_sum;
+}
+
+// One workgroup: T = sum of dist, t = min(T - 1, (int64)(u_j * (double)T)), the smallest row whose inclusive prefix
+// sum of dist exceeds t -- first the workgroup of k_init_dist that holds it (1024 block sums a trip, the running total
+// carried), then the row among that workgroup's 256 -- and that row's words as centre j.  T == 0: every row coincides
+// with a centre; k_eff = j and the seeding stops.
+__global__ __launch_bounds__(1024) void k_init_pick(ChainParams p, InitArgs a, int j, int nblocks) {
+    __shared__ long long shw[16];
+    __shared__ long long sh_off, sh_row;
+    __shared__ int sh_blk;
+    InitCell* const cell = a.cell;
+    if (cell->stop) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, P = p.P, W = (P + 31) >> 5;
+    const int64_t N = p.N;
+    long long part = 0;
+    for (int b = tid; b < nblocks; b += 1024) part += a.blocksum[b];
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+    if (lane == 0) shw[wave] = part;
+    if (tid == 0) { sh_blk = -1; sh_row = -1; }
+    __syncthreads();
+    long long T = 0;
+    for (int w = 0; w < 16; ++w) T += shw[w];
+    if (T == 0) {
+        if (tid == 0) { cell->k_eff = j; cell->stop = 1; }
+        return;
+    }
+    long long t = (long long)(init_uniform(p.seed, (uint32_t)j) * (double)T);
+    t = t > T - 1 ? T - 1 : t;
+    long long carry = 0;
+    for (int base = 0; base < nblocks; base += 1024) {
+        const int b = base + tid;
+        const long long v = b < nblocks ? a.blocksum[b] : 0;
+        long long total;
+        const long long incl = carry + init_block_scan(v, shw, total);
+        if (incl > t && incl - v <= t) { sh_blk = b; sh_off = t - (incl - v); }
+        carry += total;
+        __syncthreads();
+        if (sh_blk >= 0) break;
+    }
+    const int blk = sh_blk;
+    if (blk < 0) return;  // (t < T: never)
+    const long long off = sh_off;
+    const int64_t r = (int64_t)blk * kInitThreads + tid;
+    const long long v = tid < kInitThreads && r < N ? a.dist[r] : 0;
+    long long total;
+    const long long incl = init_block_scan(v, shw, total);
+    if (incl > off && incl - v <= off) sh_row = r;
+    __syncthreads();
+    const int64_t row = sh_row;
+    if (row < 0) return;
+    for (int w = tid; w < W; w += 1024) a.centres[(size_t)j * W + w] = a.Xb[(int64_t)w * N + row] & init_word_mask(P, w);
+    if (tid == 0) a.rows[j] = row;
+}
+
+// The labelled rows of one wave into the histogram {Nk, S[P]} per label of a workgroup, as sm_count_wave counts its
+// two sides: one ballot per feature, kept by the lane of that feature; then, per label present in the wave, one
+// ballot for its rows and one LDS atomic per feature with a count.  Uniform over the wave.
+__device__ __forceinline__ void init_count_wave(bool valid, int label, const uint32_t* __restrict__ Xb, int64_t N, int P,
+                                                int64_t r, int32_t* hist, int lane) {
+    const unsigned long long any = __ballot(valid);
+    if (!any) return;
+    const int W = (P + 31) >> 5;
+    for (int w = 0; w < W; ++w) {
+        const uint32_t bits = valid ? Xb[(int64_t)w * N + r] : 0u;
+        const int nd = P - w * 32 < 32 ? P - w * 32 : 32;
+        unsigned long long mine = 0;  // lane t: the rows of the wave with feature w * 32 + t set
+        for (int t = 0; t < nd; ++t) {
+            const unsigned long long b = __ballot(((bits >> t) & 1u) != 0);
+            if (lane == t) mine = b;
+        }
+        unsigned long long left = any;
+        while (left) {
+            const int k = __shfl(label, __builtin_ctzll(left));
+            const unsigned long long mk = __ballot(valid && label == k);
+            left &= ~mk;
+            int32_t* const h = hist + (size_t)k * (P + 1);
+            if (w == 0 && lane == 0) atomicAdd(&h[0], (int)__popcll(mk));
+            if (lane < nd) {
+                const int cnt = (int)__popcll(mine & mk);
+                if (cnt) atomicAdd(&h[1 + w * 32 + lane], cnt);
+            }
+        }
+    }
+}
+
+// Every row takes the nearest of the k_eff centres (LDS), ties to the lowest label; `changed` against the label it had
+// (not counted by the seating, round 0), the cost (the sum of the distances to the centres taken), and with COUNT the
+// new labels' Nk and S, flushed once per workgroup.  Rows of up to four words keep them in registers.
+template <bool COUNT>
+__global__ __launch_bounds__(kInitThreads) void k_init_assign(ChainParams p, InitArgs a, int round) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int sh_changed, sh_cost;
+    InitCell* const cell = a.cell;
+    if (cell->done) return;
+    const int tid = threadIdx.x, lane = tid & 63, P = p.P, W = (P + 31) >> 5, ke = cell->k_eff;
+    const int64_t N = p.N;
+    uint32_t* const cen = reinterpret_cast<uint32_t*>(smem);
+    int32_t* const hist = reinterpret_cast<int32_t*>(cen + (size_t)ke * W);
+    for (int i = tid; i < ke * W; i += kInitThreads) cen[i] = a.centres[i];
+    if (COUNT) for (int i = tid; i < ke * (P + 1); i += kInitThreads) hist[i] = 0;
+    if (tid == 0) { sh_changed = 0; sh_cost = 0; }
+    __syncthreads();
+    const int64_t r = (int64_t)blockIdx.x * kInitThreads + tid;
+    const bool valid = r < N;
+    int best = 0, bd = 0;
+    if (valid) {
+        bd = 0x7fffffff;
+        if (W <= 4) {
+            uint32_t x[4];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) x[w] = w < W ? a.Xb[(int64_t)w * N + r] & init_word_mask(P, w) : 0u;
+            for (int k = 0; k < ke; ++k) {
+                int h = 0;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) h += w < W ? __popc(x[w] ^ cen[k * W + w]) : 0;
+                if (h < bd) { bd = h; best = k; }
+            }
+        } else {
+            for (int k = 0; k < ke; ++k) {
+                int h = 0;
+                for (int w = 0; w < W; ++w) h += __popc((a.Xb[(int64_t)w * N + r] & init_word_mask(P, w)) ^ cen[(size_t)k * W + w]);
+                if (h < bd) { bd = h; best = k; }
+            }
+        }
+    }
+    const bool moved = valid && round > 0 && a.lab[r] != best;
+    if (valid) a.lab[r] = best;
+    const unsigned long long mv = __ballot(moved);
+    int cs = bd;
+    for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o);
+    if (lane == 0) {
+        if (mv) atomicAdd(&sh_changed, (int)__popcll(mv));
+        if (cs) atomicAdd(&sh_cost, cs);
+    }
+    if (COUNT) init_count_wave(valid, best, a.Xb, N, P, r, hist, lane);
+    __syncthreads();
+    if (COUNT)
+        for (int i = tid; i < ke * (P + 1); i += kInitThreads) {
+            const int32_t v = hist[i];
+            if (v == 0) continue;
+            const int k = i / (P + 1), d = i - k * (P + 1);
+            atomicAdd(d == 0 ? &a.Nk[k] : &a.S[(size_t)k * P + d - 1], v);
+        }
+    if (tid == 0) {
+        if (sh_changed) atomicAdd(reinterpret_cast<unsigned long long*>(&cell->changed[round & 1]), (unsigned long long)sh_changed);
+        if (sh_cost) atomicAdd(reinterpret_cast<unsigned long long*>(&cell->cost[round & 1]), (unsigned long long)sh_cost);
+    }
+}
+
+// Round `round` >= 1, one workgroup per centre: a round after one that changed no label ends the refinement (`done`).
+// Otherwise bit d of centre k becomes 1 if 2 S > Nk, 0 if 2 S < Nk and keeps its value on a tie or when Nk == 0; the
+// counts it has read are cleared for the assign launch that follows, and so are that launch's two totals.
+__global__ __launch_bounds__(kInitThreads) void k_init_modes(ChainParams p, InitArgs a, int round) {
+    InitCell* const cell = a.cell;
+    if (cell->done) return;
+    const int tid = threadIdx.x, P = p.P, W = (P + 31) >> 5, k = blockIdx.x;
+    if (round > 1 && cell->changed[(round - 1) & 1] == 0) {
+        if (k == 0 && tid == 0) cell->done = 1;
+        return;
+    }
+    if (k == 0 && tid == 0) { cell->rounds_run = round; cell->changed[round & 1] = 0; cell->cost[round & 1] = 0; }
+    if (k >= cell->k_eff) return;
+    const int32_t nk = a.Nk[k];
+    __syncthreads();
+    for (int w = tid; w < W; w += kInitThreads) {
+        uint32_t c = a.centres[(size_t)k * W + w];
+        const int nd = P - w * 32 < 32 ? P - w * 32 : 32;
+        for (int t = 0; t < nd; ++t) {
+            int32_t* const sp = a.S + (size_t)k * P + w * 32 + t;
+            const int64_t s2 = 2 * (int64_t)*sp;
+            if (s2 > nk) c |= 1u << t;
+            else if (s2 < nk) c &= ~(1u << t);
+            *sp = 0;
+        }
+        a.centres[(size_t)k * W + w] = c;
+    }
+    if (tid == 0) a.Nk[k] = 0;
+}
+
 __global__ void k_test_lgamma(const double* in, double* out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = lgamma_(in[i]);

@@ -747,6 +747,60 @@ typedef struct bmm_feature_out {
 } bmm_feature_out;
 int bmm_set_feature_select(const bmm_feature_out* out);
 
+/* ---- k-modes++ initial allocation of the counting samplers ------------------------------------
+ * A data-driven start computed on the device from the resident bit planes: k-means++ seeding under Hamming distance
+ * (for 0/1 data the squared Euclidean distance, so D^2 sampling is Hamming-weighted sampling), then a few k-modes
+ * rounds.  Integer arithmetic throughout but for one product per centre, so the result does not depend on the launch
+ * geometry and is the same on host and device (tests/init_ref.py restates it in NumPy).  THE DEFINITION.  Inputs: the
+ * planes Xb[w][N], W = ceil(P/32) words per row, the last word masked to its P valid bits on both sides of every
+ * comparison; Kc centres, 1 <= Kc <= K; seed; iters >= 0.
+ *   draws       init_uniform(seed, j) = u01(x, y) of the first Philox4x32 block of stream 10 (bmm_spec.h kStreamInit) at
+ *               counter (c0 = j, block 0, c2 = 0), j = 0 .. Kc - 1: no (key, counter) pair of any other draw.
+ *   seeding     r_0 = min(N - 1, (int64)(u_0 * (double)N)); centre 0 is row r_0.  Per row dist[i] (int32, initially
+ *               P + 1) and near[i].  After centre m is fixed, h = sum over words of popcount(x_i[w] ^ c_m[w]); if
+ *               h < dist[i] (strict: ties go to the lowest label) then dist[i] = h, near[i] = m.  For j = 1 .. Kc - 1:
+ *               T = sum_i dist[i] (int64; N P < 2^53, so (double)T is exact); T == 0: every row coincides with a centre,
+ *               stop with k_eff = j; otherwise t = min(T - 1, (int64)(u_j * (double)T)), r_j = the smallest i whose
+ *               inclusive prefix sum of dist exceeds t, centre j is row r_j.  Without a stop k_eff = Kc.
+ *   refinement  at most `iters` rounds of k-modes from the labels `near`.  (a) Nk and S of the current labels; bit d of
+ *               centre k becomes 1 if 2 S_kd > Nk, 0 if 2 S_kd < Nk, and keeps its value on a tie or when Nk == 0.
+ *               (b) every row takes the nearest centre among 0 .. k_eff - 1, ties to the lowest label; `changed` = the
+ *               rows whose label differs from before.  A round with changed == 0 ends the refinement.
+ *   result      0-based labels in [0, k_eff); the centres (k_eff x W words); the picked rows; the final Nk; and
+ *               {k_eff, rounds_run, changed_last, cost}: rounds_run counts the rounds executed (the one that found
+ *               changed == 0 included), changed_last is the last of them's `changed` (0 when iters = 0), cost the sum
+ *               over rows of the Hamming distance to the row's own centre (after seeding: the sum of dist).  With this
+ *               tie rule the cost never increases from one round to the next.
+ * One initialisation is 2 Kc - 1 seeding launches, one seating launch (nearest seeded centre per row, which is `near`,
+ * and the counts of those labels) and two launches per round, all enqueued at once on the chain's stream; flags on the
+ * device make the launches left over after a stop or after convergence return at once, and the record is read after one
+ * final wait.  Kc * W * 4 above BMM_INIT_MAX_CENTRE_BYTES is refused with BMM_E_UNSUPPORTED, the chain stays usable. */
+#define BMM_INIT_KMODES 1
+#define BMM_INIT_MAX_CENTRE_BYTES 65536
+typedef struct bmm_init_info {
+    int32_t k_eff, rounds_run;
+    int64_t changed_last, cost;
+    double device_ms;  /* HIP-event time of the launches of this initialisation */
+} bmm_init_info;
+/* n_centres = 0: K for the collapsed sampler; must be given for the DP sampler.  A collapsed chain that has its data
+ * and has not started gets its initial labels on the device and is left exactly as bmm_chain_set_initial_labels leaves
+ * it: no label crosses PCIe.  A seated DP chain between sweeps and outside a run gets a new allocation and the recount
+ * of Nk and S, as bmm_chain_set_labels.  Waits.  Refused: a sharded chain, a collapsed chain already started, an
+ * unseated DP chain, a chain inside a run with BMM_E_STATE; the stick-breaking and full samplers (they start from pi
+ * and theta) and the int32 layout with BMM_E_UNSUPPORTED; n_centres outside 1..K and iters < 0 with BMM_E_ARG. */
+int bmm_chain_init_labels(bmm_chain* c, int kind, int n_centres, int iters, bmm_init_info* info);
+/* of the last initialisation of this chain: the centres, k_eff x ceil(P/32) words; the picked rows (k_eff, 0-based)
+ * and, unless NULL, the final cluster sizes (k_eff) */
+int bmm_chain_get_init_centres(bmm_chain* c, uint32_t* words);
+int bmm_chain_get_init_rows(bmm_chain* c, int64_t* rows, int32_t* Nk);
+/* For a run: armed per calling thread for the NEXT single-chain bmm_collapsed_run* call of that thread and disarmed
+ * when it returns, as bmm_set_split_merge; kind = 0 disarms.  The run initialises on the device once the planes have
+ * arrived and ignores the initialK it is handed (which must still be there); its record is read afterwards with
+ * bmm_last_init_info.  A run of another sampler made while armed returns BMM_E_UNSUPPORTED (and disarms);
+ * bmm_multi_run does not take it and disarms it. */
+int bmm_set_init(int kind, int iters);
+int bmm_last_init_info(bmm_init_info* info);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
