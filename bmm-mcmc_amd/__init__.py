@@ -21,7 +21,7 @@ from .rdata import read_rdata_matrix  # the package's bundled data sets (data/*.
 __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "Chain", "BmmError", "NA_INTEGER", "set_progress",
            "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
            "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
-           "partition_distances", "posterior_similarity", "partition_plan", "PARTITION_MAX_K"]
+           "partition_distances", "posterior_similarity", "partition_plan", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -452,6 +452,83 @@ def _make_split_merge(split_merge, scans, chains):
     if int(chains) > 1:
         raise ValueError("split_merge= is offered per chain (chains=1)")
     return _SplitMerge(moves, scans)
+
+
+# ---------------------------------------------------------------- gibbs_allocation: unknown K for the finite chain
+_EA_FIELDS = ("eject_proposed", "eject_accepted", "absorb_proposed", "absorb_accepted")
+
+
+class _AllocStep(_C.Structure):  # bmm_alloc_step
+    _fields_ = [("kind", _C.c_int32), ("accepted", _C.c_int32), ("j1", _C.c_int32), ("j2", _C.c_int32),
+                ("k_before", _C.c_int32), ("k_after", _C.c_int32), ("pe_bits", _C.c_uint64), ("members", _C.c_int64),
+                ("n_before", _C.c_int64 * 2), ("n_after", _C.c_int64 * 2), ("log_prior", _C.c_double),
+                ("log_lik", _C.c_double), ("log_q", _C.c_double), ("log_move", _C.c_double), ("log_u", _C.c_double),
+                ("log_r", _C.c_double), ("sweep", _C.c_uint32), ("move", _C.c_uint32), ("side", _C.c_void_p)]
+
+
+def log_prior_k(prior_k, maxK):
+    """log p(K), K = 1..maxK: "poisson" (Poisson(1) truncated to 1..maxK, the default of Nobile & Fearnside 2007),
+    "uniform", or maxK positive weights (normalised here)"""
+    maxK = int(maxK)
+    if isinstance(prior_k, str):
+        if prior_k == "poisson":
+            lw = -_np.cumsum(_np.log(_np.arange(1.0, maxK + 1.0)))  # -log K!
+        elif prior_k == "uniform":
+            lw = _np.zeros(maxK)
+        else:
+            raise ValueError('prior_k is "poisson", "uniform" or an array of maxK weights')
+    else:
+        w = _np.asarray(prior_k, dtype=_np.float64)
+        if w.shape != (maxK,) or not _np.all(_np.isfinite(w)) or not _np.all(w > 0.0):
+            raise ValueError("prior_k needs maxK finite positive weights: the moves must be able to reach every K")
+        lw = _np.log(w)
+    return _np.ascontiguousarray(lw - _np.log(_np.sum(_np.exp(lw - lw.max()))) - lw.max())
+
+
+def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, moves=1, eject_a=1.0, beta=0.5, gamma=0.5,
+                     burnin=None, *, seed=None, batch=None, device=0, initial_K=None, partition=None, partition_stride=1,
+                     similarity_of=None):
+    """The allocation sampler of Nobile & Fearnside (2007): the finite collapsed Beta-Bernoulli mixture with the number of
+    components K unknown, 1 <= K <= maxK <= 64 (include/bmm_mcmc.h "allocation sampler").  The
+    weights are Dirichlet(a, ..., a) with `a` fixed per component; `prior_k`: see log_prior_k.  A sweep is the finite
+    sampler's with empty labels below K kept open at their prior weight; `moves` eject / absorb moves (p_E ~
+    Beta(eject_a, eject_a)) at the start of every sweep from the second change K.  The chain starts from `K0` components
+    (default min(maxK, 2)) and `initial_K` (1-based labels in 1..K0; default uniform).  Returns z (S, N), theta (maxK, P,
+    S) with NaN where a label is empty, K (S,), k_posterior (maxK,): the kept-sweep frequencies of K = 1..maxK, k_used
+    (S,): the non-empty labels per sweep, moves: the four counts, and with `partition=` the summary of gibbs_collapsed."""
+    X = _capi.as_x(data)
+    N, P = X.shape
+    nsamples, maxK = int(nsamples), int(maxK)
+    burnin = _burnin(burnin, nsamples)
+    seed = _seed(seed)
+    K0 = min(maxK, 2) if K0 is None else int(K0)
+    if not 1 <= K0 <= maxK:
+        raise ValueError("K0 must lie in 1..maxK")
+    lp = log_prior_k(prior_k, maxK)
+    if initial_K is None:
+        initial_K = _np.random.default_rng(seed).integers(1, K0 + 1, N)
+    z0 = _np.ascontiguousarray(initial_K, dtype=_np.int32)
+    if z0.shape != (N,):
+        raise ValueError("initial_K must have one label per observation")
+    S = nsamples - burnin
+    pt = _make_partition(partition, partition_stride, similarity_of, N, S, 1)
+    z = _np.empty((S, N), dtype=_np.int32, order="F")
+    theta = _np.zeros((maxK, P, S), order="F")
+    Ks = _np.zeros(S, dtype=_np.int32)
+    counts = (_C.c_int64 * 4)()
+    if pt is not None:
+        pt.arm()
+    _capi.check(_capi.lib().bmm_alloc_run(
+        _capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(maxK), _C.c_double(a),
+        _C.c_double(beta), _C.c_double(gamma), _capi.vp(lp), _C.c_int(K0), _C.c_int(int(moves)), _C.c_double(eject_a),
+        _C.c_int(burnin), _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
+        _capi.vp(theta), _capi.vp(Ks), counts))
+    used = _np.array([len(_np.unique(row)) for row in z], dtype=_np.int32)
+    out = {"z": z, "theta": theta, "K": Ks, "k_posterior": _np.bincount(Ks, minlength=maxK + 1)[1:] / float(S), "k_used": used,
+           "moves": dict(zip(_EA_FIELDS, (int(v) for v in counts)))}
+    if pt is not None:
+        out["partition"] = pt.result()
+    return out
 
 
 # ---------------------------------------------------------------- select_features=: noise features (White, Wyse & Murphy 2016)
@@ -1269,6 +1346,48 @@ class Chain:
         out = (_C.c_int64 * 5)()
         _capi.check(_capi.lib().bmm_chain_split_merge_stats(self._h, out))
         return dict(zip(_SM_FIELDS, (int(v) for v in out)))
+
+    # -- the allocation sampler: a finite collapsed chain with K unknown (include/bmm_mcmc.h)
+    def set_alloc(self, prior_k="poisson", moves_per_sweep=1, eject_a=1.0):
+        """Arms the chain, for good: K = maxK components open (set_k changes it), the chain's alpha the Dirichlet
+        parameter a per component, `moves_per_sweep` eject / absorb moves at the start of every sweep from the second."""
+        lp = log_prior_k(prior_k, self.K)
+        _capi.check(_capi.lib().bmm_chain_set_alloc(self._h, _capi.vp(lp), _C.c_int(int(moves_per_sweep)), _C.c_double(eject_a)))
+
+    def set_k(self, K):
+        _capi.check(_capi.lib().bmm_chain_set_k(self._h, _C.c_int(int(K))))
+
+    def k(self):
+        v = _C.c_int(0)
+        _capi.check(_capi.lib().bmm_chain_get_k(self._h, _C.byref(v)))
+        return v.value
+
+    def alloc(self, n):
+        """n eject / absorb moves now, enqueued behind whatever the chain is doing."""
+        _capi.check(_capi.lib().bmm_chain_alloc(self._h, _C.c_int(int(n))))
+
+    def alloc_step(self, sides=False):
+        """One move, waited for; its diagnostics as a dict (labels 1-based).  `sides=True` adds "side": one byte per row
+        (BMM_EA_OUTSIDE = 255 for a row the move does not touch)."""
+        s = _AllocStep()
+        sd = None
+        if sides:
+            sd = _np.zeros(self.N, dtype=_np.uint8)
+            s.side = sd.ctypes.data
+        _capi.check(_capi.lib().bmm_chain_alloc_step(self._h, _C.byref(s)))
+        out = {"kind": ("eject", "absorb")[s.kind], "labels": (int(s.j1), int(s.j2)), "accepted": bool(s.accepted),
+               "k_before": int(s.k_before), "k_after": int(s.k_after), "pe_bits": int(s.pe_bits), "members": int(s.members),
+               "n_before": (int(s.n_before[0]), int(s.n_before[1])), "n_after": (int(s.n_after[0]), int(s.n_after[1])),
+               "log_prior": s.log_prior, "log_lik": s.log_lik, "log_q": s.log_q, "log_move": s.log_move, "log_u": s.log_u,
+               "log_r": s.log_r, "sweep": int(s.sweep), "move": int(s.move)}
+        if sides:
+            out["side"] = sd
+        return out
+
+    def alloc_stats(self):
+        out = (_C.c_int64 * 4)()
+        _capi.check(_capi.lib().bmm_chain_alloc_stats(self._h, out))
+        return dict(zip(_EA_FIELDS, (int(v) for v in out)))
 
     def set_labels(self, z1):
         """Replace the allocation of a seated DP chain between sweeps (1-based labels); Nk and S are recounted."""

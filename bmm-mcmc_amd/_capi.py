@@ -39,6 +39,8 @@ SYMBOLS = [
     "bmm_chain_set_feature_select", "bmm_chain_set_features", "bmm_chain_get_features", "bmm_chain_feature_step",
     "bmm_chain_sweeps_features", "bmm_chain_get_feature_summary", "bmm_chain_feature_reset", "bmm_set_feature_select",
     "bmm_chain_init_labels", "bmm_chain_get_init_centres", "bmm_chain_get_init_rows", "bmm_set_init", "bmm_last_init_info",
+    "bmm_chain_set_alloc", "bmm_chain_set_k", "bmm_chain_get_k", "bmm_chain_alloc", "bmm_chain_alloc_step",
+    "bmm_chain_alloc_stats", "bmm_alloc_run",
 ]
 
 

@@ -57,6 +57,9 @@ enum : uint32_t {
     kStreamSplitMerge = 8,  // a split-merge move: c0 = move index, c1 = block counter, c2 = sweep (sm_move_draws)
     kStreamFeatureSelect = 9,  // the inclusion indicator of feature d after sweep j: c0 = d, c1 = block counter, c2 = j (fs_uniform)
     kStreamInit = 10,    // the pick of centre j of the k-modes++ start: c0 = j, c1 = block counter, c2 = 0 (init_uniform)
+    kStreamAlloc = 11,     // an eject / absorb move: c0 = move index, c1 = block counter, c2 = sweep (ea_move_draws)
+    kStreamAllocPeA = 12,  // its p_E ~ Beta(e, e): first gamma; c0 = move index, c2 = sweep
+    kStreamAllocPeB = 13,  // ... second gamma
 };
 
 // ---------------------------------------------------------------- bit helpers
@@ -475,6 +478,43 @@ BMM_HD double rgamma_(double shape, Stream& st) {
 BMM_HD double rbeta_(double p, double q, Stream& sa, Stream& sb) {
     const double x = rgamma_(p, sa), y = rgamma_(q, sb);
     return div_(x, x + y);
+}
+
+// The draws of eject / absorb move number `move` ahead of sweep `sweep` (include/bmm_mcmc.h "allocation sampler"), a
+// pure function of (seed, sweep, move) and of the chain's K and maxK: three Philox4x32 blocks of a stream of their own.
+// Block 0: the kind (eject iff u < pe_K; pe_1 = 1, pe_maxK = 0, 1/2 otherwise) and j1 uniform over the K labels;
+// block 1: the uniform of the accept step and the 32-bit salt of the members' uniforms (sm_member_uniform at scan 0:
+// a second counter word of 2^31); block 2: an absorb's j2, uniform over the other K - 1 labels.  An eject's j2 is K,
+// the appended label, and its p_E ~ Beta(e, e) comes from two more streams (rbeta_); an absorb draws no p_E (NaN).
+enum : int { kEaEject = 0, kEaAbsorb = 1 };
+struct EaDraws { int kind, j1, j2; double u, pe; uint32_t salt; };
+BMM_HD EaDraws ea_move_draws(uint64_t seed, uint32_t sweep, uint32_t move, int K, int maxK, double e) {
+    Stream st = make_stream(seed, move, sweep, kStreamAlloc);
+    const U4 r0 = st.next(), r1 = st.next(), r2 = st.next();
+    EaDraws d;
+    d.kind = K <= 1 ? kEaEject : (K >= maxK ? kEaAbsorb : (u01(r0.x, r0.y) < 0.5 ? kEaEject : kEaAbsorb));
+    int j1 = (int)(u01(r0.z, r0.w) * (double)K);
+    d.j1 = j1 > K - 1 ? K - 1 : j1;
+    d.u = u01_open0(r1.x, r1.y);
+    d.salt = r1.z;
+    if (d.kind == kEaEject) {
+        d.j2 = K;
+        Stream sa = make_stream(seed, move, sweep, kStreamAllocPeA);
+        Stream sb = make_stream(seed, move, sweep, kStreamAllocPeB);
+        d.pe = rbeta_(e, e, sa, sb);
+    } else {
+        int t = (int)(u01(r2.x, r2.y) * (double)(K - 1));
+        t = t > K - 2 ? K - 2 : t;
+        d.j2 = t >= d.j1 ? t + 1 : t;
+        d.pe = qnan();
+    }
+    return d;
+}
+// lbeta(x, y) and the closed-form log proposal density of an eject that leaves n1 rows and moves n2, p_E ~ Beta(e, e)
+// integrated out: log q = lbeta(e + n1, e + n2) - lbeta(e, e).
+BMM_HD double lbeta_(double x, double y) { return (lgamma_(x) + lgamma_(y)) - lgamma_(x + y); }
+BMM_HD double ea_log_q(double e, int64_t n1, int64_t n2) {
+    return lbeta_(e + (double)n1, e + (double)n2) - lbeta_(e, e);
 }
 
 // Escobar & West auxiliary-variable update of the concentration (utils.cpp:6-14).

@@ -588,6 +588,22 @@ struct bmm_chain {
     std::vector<uint32_t> init_centres;
     std::vector<long long> init_rows;
     std::vector<int32_t> init_nk;
+    // the allocation sampler: alloc_on: the table builds are k_alloc_tables, reading the open
+    // label count dEaK, and (for good) the kernel choice leaves out the forms that build their own tables; alloc_moves
+    // > 0: that many eject / absorb moves at the start of every sweep from the second.  One block holds K, log p(K),
+    // the moved rows' statistics, the move's cell and the four counters; the side bytes are a block of their own.
+    bool alloc_on = false;
+    int alloc_moves = 0;
+    double alloc_a = 0.0, alloc_e = 1.0;
+    char* dEaBlock = nullptr;
+    int32_t *dEaK = nullptr, *dEaStat = nullptr;
+    double* dEaLogPrior = nullptr;
+    EaCell* dEaCell = nullptr;
+    long long* dEaCounters = nullptr;
+    uint8_t* dEaSide = nullptr;
+    int ea_tag = -1;
+    uint32_t ea_ctr = 0;
+    int32_t* k_trace = nullptr;  // or [S] on the device: row j - burnin receives K after sweep j (a run)
     int prof = 0;             // > 0: HIP events around the resample launches of every prof-th sweep
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
@@ -1018,7 +1034,10 @@ int launch_reduce_deltas(bmm_chain* c) {
 }
 
 int launch_count_tables(bmm_chain* c) {
-    if (c->fs_mask)  // feature selection: excluded features are written as zeros
+    if (c->alloc_on)  // the allocation sampler: open empty labels keep their prior weight
+        hipLaunchKernelGGL(k_alloc_tables, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
+                           c->dDNk, c->dDS, (const int32_t*)c->dEaK, c->alloc_a, c->dTab);
+    else if (c->fs_mask)  // feature selection: excluded features are written as zeros
         hipLaunchKernelGGL(k_count_tables<true>, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
                            c->dDNk, c->dDS, c->dAlpha, c->dTab, (const uint32_t*)c->dFsMask);
     else
@@ -1173,6 +1192,30 @@ int enqueue_move(bmm_chain* c, int32_t* z, int tag, bool keep_launch) {
     return BMM_OK;
 }
 
+// ---- the allocation sampler ----
+int alloc_refuses(const char* what) {
+    return set_err(BMM_E_UNSUPPORTED, "%s assumes a fixed number of components: not offered on a chain of the allocation sampler", what);
+}
+// one eject / absorb move on label row `z`, ahead of sweep `tag`, enqueued on the stream
+int enqueue_ea(bmm_chain* c, int32_t* z, int tag) {
+    const ChainParams& p = c->p;
+    if (c->ea_tag != tag) { c->ea_tag = tag; c->ea_ctr = 0; }
+    EaArgs a{};
+    a.Xb = c->dXb; a.z = z; a.Nk = c->dNk; a.S = c->dS; a.K = c->dEaK; a.log_prior_k = c->dEaLogPrior;
+    a.side = c->dEaSide; a.stat = c->dEaStat; a.cell = c->dEaCell; a.counters = c->dEaCounters;
+    a.a = c->alloc_a; a.eject_a = c->alloc_e; a.sweep = (uint32_t)tag; a.move = c->ea_ctr++;
+    const size_t set_bytes = (size_t)(p.P + 1) * sizeof(int32_t);
+    HIP_TRY(hipMemsetAsync(c->dEaStat, 0, set_bytes, c->stream));
+    const unsigned grid = (unsigned)((p.N + kEaThreads - 1) / kEaThreads);
+    hipLaunchKernelGGL(k_ea_launch, dim3(grid), dim3(kEaThreads), set_bytes, c->stream, p, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_ea_decide, dim3(1), dim3(1024), 0, c->stream, p, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_ea_commit, dim3(grid), dim3(kEaThreads), 0, c->stream, p, a);
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+
 // ---- feature selection ----
 // the gamma-step behind the end of sweep j, stream-ordered: no host wait
 int enqueue_fs_gamma(bmm_chain* c, int j) {
@@ -1197,6 +1240,7 @@ int init_refused(const bmm_chain* c) {
         return set_err(BMM_E_UNSUPPORTED, "a data-driven start is offered for the collapsed and DP samplers only: the stick-breaking and "
                        "full samplers start from pi and theta");
     if (!c->bits) return set_err(BMM_E_UNSUPPORTED, "the initialisation reads the bit planes: not offered on the int32 layout");
+    if (c->alloc_on) return alloc_refuses("a device start");
     return BMM_OK;
 }
 // whether k_init_assign counts its labels in LDS (centres and histogram within kInitLdsBudget: at K = 20 up to P = 1587) or
@@ -1365,6 +1409,20 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
             if (rc) return rc;
         }
     }
+    if (c->alloc_on && c->alloc_moves > 0 && j >= 2 && phase == 0) {
+        // the armed eject / absorb moves, where the split-merge moves of a DP chain sit and on a copy for the same reason
+        int32_t* row = label_row(c, j - 1);
+        if (c->dTrace && j - 1 >= c->burnin) {
+            int32_t* const copy = c->dZ[(j - 1) & 1];
+            HIP_TRY(hipMemcpyAsync(copy, row, (size_t)p.N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+            row = copy;
+        }
+        zin = row;
+        for (int m = 0; m < c->alloc_moves; ++m) {
+            const int rc = enqueue_ea(c, row, j);
+            if (rc) return rc;
+        }
+    }
     int64_t lo = 0;
     while (lo < p.N) {
         int64_t len = c->batch;
@@ -1384,6 +1442,8 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
     hipLaunchKernelGGL(k_count_sweep_end, dim3(1), dim3(1024), 0, c->stream, p, c->dNk, c->dS, c->dDNk,
                        c->dDS, c->dAlpha, (uint32_t)j, th_tr, al_tr, nk_tr);
     HIP_TRY(hipGetLastError());
+    if (c->k_trace && rec)  // the allocation sampler's K after this sweep, device to device
+        HIP_TRY(hipMemcpyAsync(c->k_trace + s, c->dEaK, sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
     if (c->fs_on) {  // the gamma-step, from the counts the sweep end has just folded; sweep j + 1 reads its mask
         const int rc = enqueue_fs_gamma(c, j);
         if (rc) return rc;
@@ -1460,7 +1520,7 @@ int tier_of(const bmm_chain* c) { return explicit_params(c->p.mode) ? 0 : (c->mi
 // The chain's resident kernel, set up for launching: the last form of the plan that the runtime takes.
 int pick_kernel(bmm_chain* c) {
     const KernelPlan plan = plan_kernel(c->p, c->bits, tier_of(c), c->batch, c->num_cus, c->shares_device, c->lds_bytes_base,
-                                        DebugSwitches{}, c->fs_mask);
+                                        DebugSwitches{}, c->fs_mask || c->alloc_on);
     hipError_t e = hipSetDevice(c->device);
     for (int i = 0; i < plan.n; ++i) {
         const KernelForm& f = plan.form[i];
@@ -1674,7 +1734,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     dev_pool().put(c->device, c->run_arena, c->run_arena_bytes);
     void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
                     c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch, c->dSmSide, c->dSmSideLaunch, c->dSmLq, c->dSmStat, c->dSmCell,
-                    c->dSmCounters, c->dFsBlock};
+                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     chain_stream_release(c->device, c->stream, c->stream_kind);  // synchronised above
@@ -1965,6 +2025,7 @@ int bmm_chain_shard_finish(bmm_chain* c) {
 int bmm_chain_sweep_probs(bmm_chain* c, double* probs_out) {
     if (!c || !probs_out) return set_err(BMM_E_ARG, "null argument");
     if (c->sharded) return set_err(BMM_E_STATE, "not available on a sharded chain");
+    if (c->alloc_on) return alloc_refuses("the probability hand-off of the relabelling");
     HIP_TRY(hipSetDevice(c->device));
     int rc = probs_alloc(c, true);
     if (rc) return rc;
@@ -2102,6 +2163,7 @@ int bmm_chain_kernel_form(const bmm_chain* c, int* lanes_per_observation, int* b
 static int pred_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the predictive density is not offered on a sharded chain");
     if (c->fs_mask) return fs_mask_refuses("the predictive density");
+    if (c->alloc_on) return alloc_refuses("the predictive density");
     return BMM_OK;
 }
 static int pred_reset(bmm_chain* c) {
@@ -2322,6 +2384,7 @@ int bmm_chain_predict_reset(bmm_chain* c) {
 static int loo_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the leave-one-out predictive is not offered on a sharded chain");
     if (c->fs_mask) return fs_mask_refuses("the leave-one-out predictive");
+    if (c->alloc_on) return alloc_refuses("the leave-one-out predictive");
     return BMM_OK;
 }
 static int loo_armed(const bmm_chain* c) {
@@ -2642,6 +2705,173 @@ int bmm_chain_set_labels(bmm_chain* c, const int32_t* z1) {
     });
 }
 
+// ---- the allocation sampler ----
+// who may run it: a whole finite collapsed chain on the bit planes, fixed concentration, rows with labels
+static int alloc_refused(const bmm_chain* c) {
+    if (!c) return set_err(BMM_E_ARG, "null chain");
+    if (c->sharded) return set_err(BMM_E_STATE, "the allocation sampler is not offered on a sharded chain");
+    if (c->p.mode != MODE_COLLAPSED)
+        return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is the finite collapsed sampler with K unknown: create the chain with that sampler, K = maxK");
+    if (c->p.sample_alpha)
+        return set_err(BMM_E_UNSUPPORTED, "the allocation sampler keeps the Dirichlet parameter a fixed (the chain's alpha is a): alpha = 0, "
+                       "which asks for the concentration's update, is not offered");
+    if (c->p.K > kMaxCats) return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is offered up to maxK = %d", kMaxCats);
+    if (c->p.P > kEaMaxP) return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is offered up to %d features", kEaMaxP);
+    if (!c->bits) return set_err(BMM_E_UNSUPPORTED, "the eject / absorb moves read the bit planes: not offered on the int32 layout");
+    if (c->fs_mask) return fs_mask_refuses("the allocation sampler");
+    if (c->predM > 0) return alloc_refuses("the predictive density");
+    if (c->loo_on) return alloc_refuses("the leave-one-out predictive");
+    if (c->p.K < 2) return set_err(BMM_E_ARG, "maxK must be >= 2");
+    if (!c->have_data) return set_err(BMM_E_STATE, "the chain has no rows to seat: set the data first");
+    if (!c->have_init) return set_err(BMM_E_STATE, "the chain's rows have no labels: set the initial labels first");
+    return BMM_OK;
+}
+// the chain started and nothing pending: the initial allocation's counts wait in the deltas until a table build folds them
+static int alloc_prepare(bmm_chain* c) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->started) {
+        const int rc = chain_start(c);
+        if (rc) return rc;
+    }
+    return c->sweep == 0 ? launch_count_tables(c) : BMM_OK;
+}
+static int alloc_ready(bmm_chain* c) {
+    int rc = alloc_refused(c);
+    if (rc) return rc;
+    if (!c->alloc_on) return set_err(BMM_E_STATE, "the allocation sampler is not armed (bmm_chain_set_alloc)");
+    if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+    return alloc_prepare(c);
+}
+static int alloc_set_k(bmm_chain* c, int K) {
+    if (K < 1 || K > c->p.K) return set_err(BMM_E_ARG, "K must lie in 1..maxK = %d", c->p.K);
+    int rc = alloc_prepare(c);
+    if (rc) return rc;
+    std::vector<int32_t> nk((size_t)c->p.K);
+    HIP_TRY(hipMemcpyAsync(nk.data(), c->dNk, nk.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int k = K; k < c->p.K; ++k)
+        if (nk[(size_t)k] != 0) return set_err(BMM_E_ARG, "K = %d, but label %d holds %d rows: every label above K must be empty", K, k + 1, nk[(size_t)k]);
+    const int32_t k32 = K;
+    HIP_TRY(hipMemcpy(c->dEaK, &k32, sizeof k32, hipMemcpyHostToDevice));
+    return BMM_OK;
+}
+
+int bmm_chain_set_alloc(bmm_chain* c, const double* log_prior_k, int moves_per_sweep, double eject_a) {
+    return guarded([&]() -> int {
+        int rc = alloc_refused(c);
+        if (rc) return rc;
+        if (!log_prior_k) return set_err(BMM_E_ARG, "null argument");
+        if (moves_per_sweep < 0) return set_err(BMM_E_ARG, "moves_per_sweep must be >= 0");
+        if (!(eject_a > 0.0) || !(eject_a < 1e300)) return set_err(BMM_E_ARG, "eject_a must be > 0");
+        const int maxK = c->p.K;
+        for (int k = 0; k < maxK; ++k)
+            if (!(log_prior_k[k] > -1e300 && log_prior_k[k] < 1e300)) return set_err(BMM_E_ARG, "log_prior_k[%d] is not finite: every K in 1..maxK needs positive prior mass", k);
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t P = (size_t)c->p.P;
+        auto carve = [&](Carver& v) {
+            c->dEaLogPrior = v.take<double>((size_t)maxK);
+            c->dEaCell = v.take<EaCell>(1);
+            c->dEaCounters = v.take<long long>(4);
+            c->dEaStat = v.take<int32_t>(P + 1);
+            c->dEaK = v.take<int32_t>(1);
+        };
+        const bool first = !c->dEaBlock;
+        Carver measure{nullptr};
+        carve(measure);
+        if (first) {
+            HIP_TRY(hipMalloc(&c->dEaBlock, measure.used));
+            HIP_TRY(hipMalloc(&c->dEaSide, (size_t)c->p.N));
+        }
+        Carver real{c->dEaBlock};
+        carve(real);
+        if (first) {
+            HIP_TRY(hipMemsetAsync(c->dEaBlock, 0, measure.used, c->stream));
+            const int32_t k32 = maxK;
+            HIP_TRY(hipMemcpyAsync(c->dEaK, &k32, sizeof k32, hipMemcpyHostToDevice, c->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(c->dEaLogPrior, log_prior_k, (size_t)maxK * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's vector may go
+        c->alloc_a = c->alpha0;
+        c->alloc_e = eject_a;
+        c->alloc_moves = moves_per_sweep;
+        if (!c->alloc_on) {
+            c->alloc_on = true;
+            if (!c->generic) return pick_kernel(c);  // again, without the forms that build their own tables
+        }
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_set_k(bmm_chain* c, int K) {
+    return guarded([&]() -> int {
+        int rc = alloc_ready(c);
+        if (rc) return rc;
+        return alloc_set_k(c, K);
+    });
+}
+
+int bmm_chain_get_k(bmm_chain* c, int* K) {
+    return guarded([&]() -> int {
+        if (!c || !K) return set_err(BMM_E_ARG, "null argument");
+        if (!c->alloc_on) return set_err(BMM_E_STATE, "the allocation sampler is not armed (bmm_chain_set_alloc)");
+        int rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        int32_t k32 = 0;
+        HIP_TRY(hipMemcpy(&k32, c->dEaK, sizeof k32, hipMemcpyDeviceToHost));
+        *K = k32;
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_alloc(bmm_chain* c, int n) {
+    return guarded([&]() -> int {
+        if (n < 0) return set_err(BMM_E_ARG, "n must be >= 0");
+        int rc = alloc_ready(c);
+        if (rc) return rc;
+        for (int t = 0; t < n; ++t) {
+            rc = enqueue_ea(c, label_row(c, c->sweep), c->sweep + 1);
+            if (rc) return rc;
+        }
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_alloc_step(bmm_chain* c, bmm_alloc_step* out) {
+    return guarded([&]() -> int {
+        if (!out) return set_err(BMM_E_ARG, "null argument");
+        int rc = alloc_ready(c);
+        if (rc) return rc;
+        rc = enqueue_ea(c, label_row(c, c->sweep), c->sweep + 1);
+        if (rc) return rc;
+        rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        EaCell h;
+        HIP_TRY(hipMemcpy(&h, c->dEaCell, sizeof h, hipMemcpyDeviceToHost));
+        out->kind = h.kind; out->accepted = h.accepted; out->j1 = h.j1 + 1; out->j2 = h.j2 + 1;
+        out->k_before = h.k_before; out->k_after = h.k_after; out->pe_bits = h.pe_bits; out->members = h.members;
+        for (int q = 0; q < 2; ++q) { out->n_before[q] = h.n_before[q]; out->n_after[q] = h.n_after[q]; }
+        out->log_prior = h.log_prior; out->log_lik = h.log_lik; out->log_q = h.log_q; out->log_move = h.log_move;
+        out->log_u = h.log_u; out->log_r = h.log_r;
+        out->sweep = (uint32_t)(c->sweep + 1); out->move = c->ea_ctr - 1;
+        if (out->side) HIP_TRY(hipMemcpy(out->side, c->dEaSide, (size_t)c->p.N, hipMemcpyDeviceToHost));
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_alloc_stats(bmm_chain* c, int64_t out[4]) {
+    return guarded([&]() -> int {
+        if (!c || !out) return set_err(BMM_E_ARG, "null argument");
+        for (int q = 0; q < 4; ++q) out[q] = 0;
+        if (!c->dEaCounters) return BMM_OK;
+        int rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        long long h[4];
+        HIP_TRY(hipMemcpy(h, c->dEaCounters, sizeof h, hipMemcpyDeviceToHost));
+        for (int q = 0; q < 4; ++q) out[q] = h[q];
+        return BMM_OK;
+    });
+}
+
 // ---- k-modes++ initial allocation ----
 int bmm_chain_init_labels(bmm_chain* c, int kind, int n_centres, int iters, bmm_init_info* info) {
     return guarded([&]() -> int {
@@ -2678,6 +2908,7 @@ static int fs_refused(const bmm_chain* c) {
     if (c->predM > 0) return set_err(BMM_E_UNSUPPORTED, "feature selection is not offered together with newdata: the predictive tables are written for the all-features model");
     if (c->loo_on) return set_err(BMM_E_UNSUPPORTED, "feature selection is not offered together with the leave-one-out summary: its tables are written for the all-features model");
     if (c->sm_moves > 0) return set_err(BMM_E_UNSUPPORTED, "feature selection is not offered together with split-merge moves: their ratio is written for the all-features model");
+    if (c->alloc_on) return alloc_refuses("feature selection");
     if (!c->have_data) return set_err(BMM_E_STATE, "the chain has no rows to seat: set the data first");
     if (c->p.mode == MODE_COLLAPSED && !c->have_init) return set_err(BMM_E_STATE, "the chain's rows have no labels: set the initial labels first");
     return BMM_OK;
@@ -3579,6 +3810,9 @@ thread_local FsArmed g_fs;
 struct InitArmed { int kind = 0, iters = 0; };
 thread_local InitArmed g_init;
 thread_local bmm_init_info g_init_info{};
+// ... and the allocation sampler's run (bmm_alloc_run arms it for its own call of run_chain)
+struct AllocArmed { bool on = false; const double* log_prior_k = nullptr; int K0 = 0, moves = 0; double eject_a = 1.0; int32_t* k_out = nullptr; int64_t* moves_out = nullptr; };
+thread_local AllocArmed g_alloc;
 struct PtDisarm { ~PtDisarm() { g_partition.on = false; g_loo.on = false; g_sm.moves = 0; g_fs.on = false; g_init.kind = 0; } };
 // what a run checks of it before any device is touched
 int pt_check_armed(const bmm_partition_out& o, int S, int64_t N, int K) {
@@ -3779,6 +4013,11 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             if (!(o.rho > 0.0 && o.rho < 1.0)) return set_err(BMM_E_ARG, "rho must lie strictly inside (0, 1): it is the prior probability that a feature clusters");
             if (!o.gamma || !o.inclusion || !o.inclusion_rb || !o.n_selected) return set_err(BMM_E_ARG, "feature selection: null buffer");
         }
+        if (g_alloc.on) {  // refused before any device is touched
+            if ((pred && M > 0) || g_loo.on || g_sm.moves > 0 || g_fs.on || g_init.kind != 0 || rel || hooks)
+                return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is not offered together with relabelling, feature selection, split-merge moves, "
+                               "the leave-one-out summary, newdata or a device start: they assume a fixed number of components");
+        }
         if (rel) {  // refused before any device is touched
             if (!rel->permutations || !rel->z_original || !rel->theta_original) return set_err(BMM_E_ARG, "null buffer");
             if (burnin < 2 || rel->burnrelabel < 1)
@@ -3876,8 +4115,29 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
                 c->fs_trace = gtrace.as<uint8_t>();
                 c->fs_trace_base = burnin;
             }
+            // the allocation sampler: armed, K set (the labels above it empty), K recorded behind every kept sweep
+            DevBuf ktrace;
+            if (g_alloc.on) {
+                rc = bmm_chain_set_alloc(c, g_alloc.log_prior_k, g_alloc.moves, g_alloc.eject_a);
+                if (rc == BMM_OK) rc = alloc_set_k(c, g_alloc.K0);
+                if (rc) return rc;
+                HIP_TRY(ktrace.alloc((size_t)S * sizeof(int32_t)));
+                const int32_t k0 = g_alloc.K0;
+                if (burnin == 0) HIP_TRY(hipMemcpy(ktrace.p, &k0, sizeof k0, hipMemcpyHostToDevice));  // trace row 0: the starting state
+                c->k_trace = ktrace.as<int32_t>();
+            }
             rc = run_body(c, nsamples, io, hooks, rel);
             if (rc == BMM_OK && g_sm.moves > 0) rc = bmm_chain_split_merge_stats(c, g_sm_stats);
+            c->k_trace = nullptr;
+            if (g_alloc.on) {
+                const hipError_t es = hipStreamSynchronize(c->stream);  // before ktrace may go
+                if (rc == BMM_OK && es != hipSuccess) rc = set_err(BMM_E_HIP, "the run failed: %s", hipGetErrorString(es));
+                if (rc == BMM_OK) {
+                    const hipError_t ec = hipMemcpy(g_alloc.k_out, ktrace.p, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToHost);
+                    if (ec != hipSuccess) rc = set_err(BMM_E_HIP, "copying the K trace failed: %s", hipGetErrorString(ec));
+                }
+                if (rc == BMM_OK && g_alloc.moves_out) rc = bmm_chain_alloc_stats(c, g_alloc.moves_out);
+            }
             c->fs_trace = nullptr;
             if (fs) {
                 const hipError_t es = hipStreamSynchronize(c->stream);  // before gtrace may go
@@ -4023,6 +4283,27 @@ int bmm_collapsed_run_probs(const int32_t* X, int64_t N, int P, const int32_t* i
     RunIO io; io.z0 = initialK; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
     return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
                      device, io, hooks);
+}
+
+// The allocation sampler: the finite collapsed run with K in the state.
+int bmm_alloc_run(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int maxK, double a,
+                  double beta, double gamma, const double* log_prior_k, int K0, int moves_per_sweep, double eject_a,
+                  int burnin, int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
+                  int32_t* k_out, int64_t moves_out[4]) {
+    PtDisarm disarm;
+    struct Off { ~Off() { g_alloc = AllocArmed{}; } } off;
+    if (!log_prior_k || !k_out) return set_err(BMM_E_ARG, "null buffer");
+    if (!(a > 0.0)) return set_err(BMM_E_ARG, "a must be > 0");
+    if (maxK > kMaxCats) return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is offered up to maxK = %d", kMaxCats);
+    if (P > kEaMaxP) return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is offered up to %d features", kEaMaxP);
+    if (maxK < 2) return set_err(BMM_E_ARG, "maxK must be >= 2");
+    if (K0 < 1 || K0 > maxK) return set_err(BMM_E_ARG, "the initial K must lie in 1..maxK");
+    if (nsamples < 1 || burnin < 0 || burnin >= nsamples) return set_err(BMM_E_ARG, "burnin must be in [0, nsamples)");
+    std::vector<double> alpha_out((size_t)(nsamples - burnin));
+    g_alloc.on = true; g_alloc.log_prior_k = log_prior_k; g_alloc.K0 = K0; g_alloc.moves = moves_per_sweep;
+    g_alloc.eject_a = eject_a; g_alloc.k_out = k_out; g_alloc.moves_out = moves_out;
+    RunIO io; io.z0 = initialK; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out.data();
+    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, maxK, a, beta, gamma, 1.0, 1.0, burnin, batch, seed, device, io, nullptr);
 }
 
 int bmm_dp_run(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,

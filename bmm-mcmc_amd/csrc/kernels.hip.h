@@ -3325,6 +3325,259 @@ __global__ __launch_bounds__(kInitThreads) void k_init_modes(ChainParams p, Init
     if (tid == 0) a.Nk[k] = 0;
 }
 
+// ---- the allocation sampler: unknown K for the finite chain (include/bmm_mcmc.h "allocation sampler")
+// The table build of a chain whose number of components K is part of the state: k_count_tables for maxK = p.K
+// labels of which the first *Kact are open.  It folds and clears the deltas as k_count_tables does and writes the same
+// image, so the resample kernels are the ones every chain runs.  A label below *Kact scores with its prior weight and
+// the prior Bernoulli terms when it is empty (the Dirichlet-multinomial model; k_count_tables gives it -inf for ever),
+// and a row that sits alone keeps its own label at that weight; a label from *Kact on is closed: -inf, tables zero.
+// `a` is the Dirichlet parameter per component, the denominator log(N - 1 + K a).  Roles and order of operations are
+// those of k_count_tables; with no label empty or single and K a = alpha the two write the same bits.
+__global__ __launch_bounds__(kCountTablesThreads) void k_alloc_tables(ChainParams p, int32_t* __restrict__ Nk,
+                                                                     int32_t* __restrict__ S,
+                                                                     int32_t* __restrict__ dNk,
+                                                                     int32_t* __restrict__ dS,
+                                                                     const int32_t* __restrict__ Kact, double a,
+                                                                     double* __restrict__ tab) {
+    __shared__ double e1[kMaxP], e0[kMaxP], m1[kMaxP], m0[kMaxP], cst[4];  // cst: Cp, Cm, the two denominators
+    const int k = blockIdx.x;
+    const TableLayout L = layout_of(p, true);
+    const int P = p.P;
+    const bool is_label = k < p.K;
+    const int Ka = *Kact;
+    const bool open = k < Ka;
+    const int role = threadIdx.x >> 7;
+    const int dl = role < 4 ? (threadIdx.x & 127) : kMaxP;
+    int32_t n_old = 0, n_dl = 0, s_old = 0, s_dl = 0;
+    const size_t KP = (size_t)p.K * P;
+    if (is_label) { n_old = Nk[k]; n_dl = delta_take(dNk, k, p.K); }
+    if (is_label && dl < P) { s_old = S[(size_t)k * P + dl]; s_dl = delta_take(dS, (size_t)k * P + dl, KP); }
+    const int64_t n = (int64_t)n_old + n_dl;
+    const double bg = p.beta + p.gamma;
+    if (role == 4) {
+        const int lane = threadIdx.x & 63;
+        double arg = 1.0;
+        bool need = false;
+        switch (lane) {
+            case 0: arg = bg + (double)n; need = open; break;                       // log(beta+gamma+n)
+            case 1: arg = bg + (double)(n - 1); need = open && n > 0; break;         // ... with one removed
+            case 2: arg = (double)n + a; need = open; break;                        // log(n + a)
+            case 3: arg = (double)(n - 1) + a; need = open && n > 0; break;
+            case 4: arg = (double)(p.Ntot - 1) + (double)Ka * a; need = true; break;  // log(N - 1 + K a)
+            default: break;
+        }
+        const double v = need ? log_(arg) : 0.0;
+        const double den_p = __shfl(v, 0), den_m = __shfl(v, 1), ln = __shfl(v, 2), lm = __shfl(v, 3);
+        const double ldN = __shfl(v, 4);
+        if (lane == 0) {
+            double cp = neg_inf(), cm = neg_inf();
+            if (open) {
+                cp = ln - ldN;
+                if (n > 0) cm = lm - ldN;
+            }
+            tab[L.cp() + k] = cp;
+            tab[L.cm() + k] = cm;
+            cst[0] = cp; cst[1] = cm; cst[2] = den_p; cst[3] = den_m;  // read after the first barrier below
+            reinterpret_cast<int32_t*>(tab + L.nk())[k] = (int32_t)n;
+        }
+    }
+    for (int c0 = 0; c0 < P; c0 += kChunkP) {  // kChunkP features (whole groups) at a time
+        const int pc = P - c0 < kChunkP ? P - c0 : kChunkP;
+        int32_t s = 0;
+        double raw = 0.0;
+        bool have = false;
+        if (dl < pc && is_label) {
+            const int d = c0 + dl;
+            s = c0 == 0 ? s_old + s_dl : S[(size_t)k * P + d] + delta_take(dS, (size_t)k * P + d, KP);
+            // term_x1 / term_x0 of bmm_spec.h, the denominator subtracted below
+            if (role == 0) { have = open; raw = have ? log_(p.beta + (double)s) : 0.0; }
+            else if (role == 1) { have = open; raw = have ? log_((p.gamma + (double)n) - (double)s) : 0.0; }
+            else if (role == 2) { have = open && n > 0 && s >= 1; raw = have ? log_(p.beta + (double)((int64_t)s - 1)) : 0.0; }
+            else { have = open && n > 0 && s <= n - 1; raw = have ? log_((p.gamma + (double)(n - 1)) - (double)s) : 0.0; }
+        }
+        __syncthreads();  // the constants are in place; every role has read S + dS before either is rewritten
+        if (dl < pc) {
+            const double t = have ? raw - cst[role < 2 ? 2 : 3] : 0.0;
+            (role == 0 ? e1 : role == 1 ? e0 : role == 2 ? m1 : m0)[dl] = t;
+            if (role == 0 && is_label) {
+                const int d = c0 + dl;
+                S[(size_t)k * P + d] = s;
+                delta_clear(dS, (size_t)k * P + d, KP);
+            }
+        }
+        __syncthreads();
+        write_group_tables(p.W, e1, e0, pc, c0, p.KT, k, cst[0], tab + L.tp());
+        write_group_tables(kGroupWm, m1, m0, pc, c0, p.KT, k, cst[1], tab + L.tm());
+        __syncthreads();
+    }
+    if (is_label && threadIdx.x == 0) {  // every thread read the old pair before the barriers above
+        Nk[k] = (int32_t)n;
+        delta_clear(dNk, k, p.K);
+    }
+    if (k == 0 && threadIdx.x < 256) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];
+}
+
+// The eject / absorb move of Nobile & Fearnside (2007), p_E integrated out of the proposal density: k_ea_launch,
+// k_ea_decide, k_ea_commit, stream-ordered; the host never reads anything back.  One byte per row.  An eject of label
+// j1 into the appended label j2 = K: 0 a row of j1 that stays, 1 one that moves.  An absorb of j2 into j1: 0 a row of
+// j1, 1 a row of j2 (it takes j1), 2 a row of label K - 1 when j2 != K - 1 (it takes the freed label j2, after the
+// rows of j2 have moved: with j1 == K - 1 the rows of j1 carry 2 and the merged component ends up under j2).  kEaOut
+// every other row.  `stat` = {n2', S2'[P]}, the statistics of the rows an eject moves, zeroed by the host.
+constexpr int kEaThreads = 256;
+constexpr int kEaMaxP = 1024;
+constexpr uint8_t kEaOut = 255;
+struct EaCell {
+    long long members, n_before[2], n_after[2];
+    int32_t kind, j1, j2, accepted, k_before, k_after;
+    uint32_t salt, pad;
+    unsigned long long pe_bits;
+    double log_prior, log_lik, log_q, log_move, log_u, log_r;
+};
+struct EaArgs {
+    const uint32_t* Xb;
+    int32_t* z;               // the label row the move works on, in place
+    int32_t *Nk, *S;          // the chain's statistics, nothing pending
+    int32_t* K;               // the number of open labels
+    const double* log_prior_k;  // [maxK]: log p(K = k + 1)
+    uint8_t* side;
+    int32_t* stat;
+    EaCell* cell;
+    long long* counters;      // proposed / accepted ejects, proposed / accepted absorbs
+    double a, eject_a;
+    uint32_t sweep, move;
+};
+
+// Every workgroup derives the move; workgroup 0 records it.  Then the side bytes and, for an eject, the statistics of
+// the rows that move: a ballot per feature, one LDS atomic per feature and wave, one flush per workgroup.
+__global__ __launch_bounds__(kEaThreads) void k_ea_launch(ChainParams p, EaArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int32_t* const hist = reinterpret_cast<int32_t*>(smem);  // [P + 1]
+    __shared__ int sh_kind, sh_j1, sh_j2, sh_K;
+    __shared__ uint32_t sh_salt;
+    __shared__ double sh_pe;
+    const int P = p.P, tid = threadIdx.x, lane = tid & 63;
+    const int64_t N = p.N;
+    for (int i = tid; i <= P; i += kEaThreads) hist[i] = 0;
+    if (tid == 0) {
+        const int K = *a.K;
+        const EaDraws dr = ea_move_draws(p.seed, a.sweep, a.move, K, p.K, a.eject_a);
+        sh_kind = dr.kind; sh_j1 = dr.j1; sh_j2 = dr.j2; sh_K = K; sh_salt = dr.salt; sh_pe = dr.pe;
+        if (blockIdx.x == 0) {
+            EaCell* c = a.cell;
+            c->kind = dr.kind; c->j1 = dr.j1; c->j2 = dr.j2; c->salt = dr.salt; c->pe_bits = dbits(dr.pe);
+            c->accepted = 0; c->members = 0; c->k_before = K; c->k_after = K;
+            c->n_before[0] = a.Nk[dr.j1]; c->n_before[1] = dr.kind == kEaAbsorb ? a.Nk[dr.j2] : 0;
+            c->n_after[0] = c->n_after[1] = 0;
+            c->log_u = log_(dr.u);
+            c->log_prior = c->log_lik = c->log_q = c->log_move = c->log_r = 0.0;
+        }
+    }
+    __syncthreads();
+    const int kind = sh_kind, j1 = sh_j1, j2 = sh_j2, last = sh_K - 1;
+    const int64_t r = (int64_t)blockIdx.x * kEaThreads + tid;
+    int sd = kEaOut;
+    if (r < N) {
+        const int zr = a.z[r];
+        if (kind == kEaEject) {
+            if (zr == j1) sd = sm_member_uniform(sh_salt, (uint64_t)(p.obs0 + r), 0u) < sh_pe ? 1 : 0;
+        } else {
+            if (zr == last && j2 != last) sd = 2;
+            else if (zr == j2) sd = 1;
+            else if (zr == j1) sd = 0;
+        }
+        a.side[r] = (uint8_t)sd;
+    }
+    if (kind != kEaEject) return;
+    // the split-merge counting with every counted row on its side 0: the histogram's first set {n, S[P]} is all it
+    // writes, and all this workgroup holds
+    sm_count_wave(sd == 1, 0, a.Xb, N, P, r, hist, lane);
+    __syncthreads();
+    for (int i = tid; i <= P; i += kEaThreads) {
+        const int32_t v = hist[i];
+        if (v != 0) atomicAdd(&a.stat[i], v);
+    }
+}
+
+// One workgroup: the marginal-likelihood ratio over the features in a fixed order (feature d in partial d mod 1024,
+// ascending, then a binary tree), the prior ratio, log q in closed form, the decision and the counters.  Everything is
+// computed in the eject's direction, from the smaller K; an absorb negates it.
+__global__ __launch_bounds__(1024) void k_ea_decide(ChainParams p, EaArgs a) {
+    __shared__ double sh[1024];
+    const int t = threadIdx.x, P = p.P;
+    EaCell* const c = a.cell;
+    const bool eject = c->kind == kEaEject;
+    const int j1 = c->j1, j2 = c->j2, K = c->k_before;
+    const int64_t n1 = eject ? (int64_t)a.Nk[j1] - a.stat[0] : a.Nk[j1];
+    const int64_t n2 = eject ? a.stat[0] : a.Nk[j2];
+    const int64_t n = n1 + n2;
+    double ll = 0.0;
+    for (int d = t; d < P; d += 1024) {
+        const int64_t sa = a.S[(size_t)j1 * P + d];
+        const int64_t s2 = eject ? a.stat[1 + d] : a.S[(size_t)j2 * P + d];
+        const int64_t s1 = eject ? sa - s2 : sa, s = s1 + s2;
+        ll = ll + ((sm_pair(p.beta, p.gamma, n1, s1) + sm_pair(p.beta, p.gamma, n2, s2)) - sm_pair(p.beta, p.gamma, n, s));
+    }
+    sh[t] = ll;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if (t < s) sh[t] = sh[t] + sh[t + s];
+        __syncthreads();
+    }
+    if (t != 0) return;
+    const double bg = p.beta + p.gamma, A = a.a, e = a.eject_a, Nd = (double)p.Ntot;
+    const double c0 = (lgamma_(bg) - lgamma_(p.beta)) - lgamma_(p.gamma);
+    const double cst = ((c0 - lgamma_(bg + (double)n1)) - lgamma_(bg + (double)n2)) + lgamma_(bg + (double)n);
+    const double lik = sh[0] + (double)P * cst;
+    const int Kl = eject ? K : K - 1;  // the smaller K: the eject goes from Kl to Kl + 1
+    const double ka = (double)Kl * A, kb = (double)(Kl + 1) * A;
+    const double prior = (((a.log_prior_k[Kl] - a.log_prior_k[Kl - 1]) + ((lgamma_(kb) - lgamma_(kb + Nd)) - (lgamma_(ka) - lgamma_(ka + Nd)))) +
+                          ((lgamma_(A + (double)n1) + lgamma_(A + (double)n2)) - lgamma_(A + (double)n))) - lgamma_(A);
+    const double log_q = ea_log_q(e, n1, n2);
+    // log(1 - pe_{Kl + 1}) - log pe_{Kl}: pe_1 = 1, pe_maxK = 0, 1/2 otherwise
+    const double log_move = log_(Kl + 1 == p.K ? 1.0 : 0.5) - log_(Kl == 1 ? 1.0 : 0.5);
+    const double log_prior = eject ? prior : -prior, log_lik = eject ? lik : -lik;
+    const double log_r = eject ? ((log_prior + log_lik) + log_move) - log_q : ((log_prior + log_lik) - log_move) + log_q;
+    const int acc = c->log_u < log_r ? 1 : 0;
+    c->log_prior = log_prior; c->log_lik = log_lik; c->log_q = log_q; c->log_move = log_move; c->log_r = log_r;
+    c->accepted = acc;
+    c->n_after[0] = eject ? n1 : n; c->n_after[1] = eject ? n2 : 0;
+    c->members = n2;
+    c->k_after = acc ? (eject ? K + 1 : K - 1) : K;
+    a.counters[eject ? 0 : 2] += 1;
+    if (acc) a.counters[eject ? 1 : 3] += 1;
+}
+
+// An accepted move: the labels, the exact integer statistics of the labels touched (the swapped label included) and K.
+// A rejected one: nothing.
+__global__ __launch_bounds__(kEaThreads) void k_ea_commit(ChainParams p, EaArgs a) {
+    const EaCell* const c = a.cell;
+    if (!c->accepted) return;
+    const int P = p.P, tid = threadIdx.x, j1 = c->j1, j2 = c->j2, last = c->k_before - 1;
+    const bool eject = c->kind == kEaEject;
+    const int64_t r = (int64_t)blockIdx.x * kEaThreads + tid;
+    if (r < p.N) {
+        const int sd = a.side[r];
+        if (eject) { if (sd == 1) a.z[r] = j2; }
+        else if (sd == 1) a.z[r] = (j1 == last && j2 != last) ? j2 : j1;
+        else if (sd == 2) a.z[r] = j2;
+    }
+    if (blockIdx.x != 0) return;
+    for (int idx = tid; idx <= P; idx += kEaThreads) {
+        int32_t* const A = idx == 0 ? a.Nk + j1 : a.S + (size_t)j1 * P + (idx - 1);
+        int32_t* const B = idx == 0 ? a.Nk + j2 : a.S + (size_t)j2 * P + (idx - 1);
+        int32_t* const Z = idx == 0 ? a.Nk + last : a.S + (size_t)last * P + (idx - 1);
+        if (eject) {
+            const int32_t v = a.stat[idx];
+            *B = v; *A = *A - v;
+        } else {  // in this order: j1 may be the last label
+            const int32_t s = *A + *B;
+            *A = s; *B = 0;
+            if (j2 != last) { *B = *Z; *Z = 0; }
+        }
+    }
+    if (tid == 0) *a.K = c->k_after;
+}
+
 __global__ void k_test_lgamma(const double* in, double* out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = lgamma_(in[i]);

@@ -801,6 +801,86 @@ int bmm_chain_get_init_rows(bmm_chain* c, int64_t* rows, int32_t* Nk);
 int bmm_set_init(int kind, int iters);
 int bmm_last_init_info(bmm_init_info* info);
 
+/* ---- the allocation sampler: unknown K for the finite chain ----------------------------------
+ * The finite collapsed sampler fixes K; the DP sampler frees it but puts no prior on it.  The allocation sampler of Nobile
+ * & Fearnside (2007) runs the finite model with K in the state and a prior on it, and gives a posterior p(K | x).
+ * THE MODEL AND THE CHAIN (tests/alloc_ref.py restates them in NumPy).  State (K, z), 1 <= K <= maxK, z in {0..K-1}^N.
+ * K ~ p(K), a caller-supplied vector of maxK log probabilities; weights ~ Dirichlet(a, ..., a) with a fixed a > 0 PER
+ * COMPONENT (not alpha / K); theta_kd ~ Beta(beta, gamma).  With the weights and theta integrated out,
+ *   log pi(K, z) = log p(K) + lgamma(K a) - lgamma(K a + N) + sum_k [lgamma(a + n_k) - lgamma(a)] + sum_k L(k),
+ * L the L(c) of the split-merge section, 0 for an empty label.
+ *   sweep   the finite sampler's sweep with the table build k_alloc_tables: label k < K scores log(n + a) - log(N - 1
+ *           + K a) plus the Beta-Bernoulli terms of its statistics -- the prior terms when it is empty, so an emptied
+ *           label can be taken again; the row's own label with the row removed, log(n - 1 + a) - ..., so a row that
+ *           sits alone keeps its label at prior weight; labels from K on are closed.  K is read from the device: no
+ *           host wait.  The resample kernels are the ones every chain runs (they draw from the table image alone);
+ *           the form whose workgroups build their own tables is never chosen, and above 128 features the sweeps run on
+ *           the generic kernel, which reads the same image.
+ *   move    eject / absorb (section 3.2 of the paper, p_E integrated out of the proposal density), number m ahead of
+ *           sweep j.  Eject with probability pe_K (pe_1 = 1, pe_maxK = 0, else 1/2), otherwise absorb.
+ *           eject   j1 uniform over the K labels, j2 = K the appended label, p_E ~ Beta(e, e); every row of j1 moves to
+ *                   j2 iff its own uniform is < p_E; n1', n2' the proposed sizes (either may be 0);
+ *                   log q = lbeta(e + n1', e + n2') - lbeta(e, e);
+ *                   log_prior = log p(K+1) - log p(K) + [lgamma((K+1)a) - lgamma((K+1)a + N)] - [lgamma(K a) - lgamma(K a + N)]
+ *                               + lgamma(a + n1') + lgamma(a + n2') - lgamma(a + n) - lgamma(a),
+ *                   log_lik = L(j1') + L(j2') - L(j1), log_move = log(1 - pe_{K+1}) - log pe_K,
+ *                   log r = log_prior + log_lik + log_move - log q.
+ *           absorb  an ordered pair (j1, j2), j1 != j2, uniform over the K (K - 1) pairs; every row of j2 takes j1, then
+ *                   the rows of label K - 1 take j2 (when j2 != K - 1), K falls by one.  log r is the negative of the
+ *                   eject's with n1' = n_j1, n2' = n_j2 and K - 1 in the eject's role; log_prior and log_lik are
+ *                   reported negated, log_q and log_move as the eject's: log r = log_prior + log_lik - log_move + log q.
+ *           accept iff log u < log r; the commit writes the labels, the exact integer Nk and S of the labels touched
+ *           (the swapped label included) and K.
+ * The labelled chain is valid on the lumped state (K, partition): tests/test_alloc_ref.py builds the exact transition
+ * matrices of the move and of a batch-1 sweep on a small data set and holds them to detailed balance.
+ * Random streams, a pure function of (seed, sweep j, move m, row): kind, j1, u, the salt and an absorb's j2 from three
+ * Philox4x32 blocks of stream 11 (c0 = m, c2 = j), p_E from streams 12 and 13 (the spec's rbeta_); a row's uniform is
+ * Philox2x32 at counter (row, 2^31) under the salt, as a split-merge member's.  The sums over features run in an order
+ * fixed by P (feature d in partial d mod 1024, ascending, then a binary tree); lgamma is the spec's lgamma_.
+ * A chain is the finite collapsed one created with K = maxK and alpha = a (the per-component parameter); arming it is
+ * for good.  K starts at maxK; bmm_chain_set_k changes it between sweeps.
+ * Refused with BMM_E_UNSUPPORTED: a sampler other than the finite collapsed one, alpha = 0 (the concentration's update
+ * does not apply: a is fixed), a chain with a feature mask, newdata or the leave-one-out summary, and those on an armed
+ * chain, as the probability hand-off of the relabelling (their tables assume a fixed K), the int32 layout, P above 1024,
+ * maxK above 64; a sharded chain or one without data or initial labels with BMM_E_STATE.  bmm_multi_run does not take it. */
+#define BMM_EA_EJECT 0
+#define BMM_EA_ABSORB 1
+#define BMM_EA_OUTSIDE 255 /* side byte of a row the move does not touch.  Eject: 0 a row of j1 that stays, 1 one that
+                            * moves to j2.  Absorb: 0 a row of j1, 1 a row of j2, 2 a row of label K - 1 that takes j2
+                            * (j2 != K - 1; with j1 == K - 1 the rows of j1 carry 2) */
+typedef struct bmm_alloc_step {
+    int32_t kind, accepted;    /* BMM_EA_* */
+    int32_t j1, j2;            /* 1-based */
+    int32_t k_before, k_after;
+    uint64_t pe_bits;          /* the bits of p_E (a NaN for an absorb, which draws none) */
+    int64_t members;           /* rows moved: n2' */
+    int64_t n_before[2];       /* sizes of j1 and j2 before the move (eject: n_j1, 0) */
+    int64_t n_after[2];        /* ... as proposed (eject: n1', n2'; absorb: n_j1 + n_j2, 0) */
+    double log_prior, log_lik, log_q, log_move, log_u, log_r;
+    uint32_t sweep, move;      /* what keyed the move's streams */
+    uint8_t* side;             /* in: room for N side bytes, or NULL */
+} bmm_alloc_step;
+/* arms the chain (for good) and sets log p(K), K = 1..maxK, every one finite, the moves at the start of every sweep from
+ * the second, before its first table build (0: sweeps with open empty labels only), and e of p_E ~ Beta(e, e) */
+int bmm_chain_set_alloc(bmm_chain* c, const double* log_prior_k, int moves_per_sweep, double eject_a);
+/* K between sweeps: every label above it must be empty (BMM_E_ARG otherwise).  Waits. */
+int bmm_chain_set_k(bmm_chain* c, int K);
+int bmm_chain_get_k(bmm_chain* c, int* K);
+/* n moves now (returns without waiting) */
+int bmm_chain_alloc(bmm_chain* c, int n);
+/* one move, then waits; fills *out (set side first) */
+int bmm_chain_alloc_step(bmm_chain* c, bmm_alloc_step* out);
+/* proposed ejects, accepted ejects, proposed absorbs, accepted absorbs.  Waits. */
+int bmm_chain_alloc_stats(bmm_chain* c, int64_t out[4]);
+/* One call, shaped like bmm_collapsed_run: initialK holds 1-based labels in 1..K0, theta_out is maxK x P x S with NaN
+ * where a label is empty, k_out S int32: K after every kept sweep (row 0 of a run without burn-in: K0), moves_out the four
+ * counts or NULL.  bmm_set_partition_summary combines with it; relabelling, feature selection, split-merge moves, the
+ * leave-one-out summary, newdata and a device start armed for the call make it return BMM_E_UNSUPPORTED. */
+int bmm_alloc_run(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int maxK, double a,
+                  double beta, double gamma, const double* log_prior_k, int K0, int moves_per_sweep, double eject_a,
+                  int burnin, int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
+                  int32_t* k_out, int64_t moves_out[4]);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
