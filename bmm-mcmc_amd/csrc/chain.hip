@@ -461,6 +461,18 @@ hipError_t kernel_fits(Fn fn, int nt, size_t lds, int* blocks_per_cu) {
     return e;
 }
 
+// What a chain records per sweep for one consumer (the predictive, the leave-one-out summary, the indicator step,
+// the allocation sampler's K): while `fold` is set, sweeps j >= from are folded into the consumer's accumulators;
+// p: or rows of row_bytes on the device, row j - base receiving sweep j's values.  Installed by a Recording.
+struct SweepTrace {
+    char* p = nullptr;
+    size_t row_bytes = 0;
+    int base = 0, from = 0;  // sweep indices
+    bool fold = false;
+    bool folds(int j) const { return fold && j >= from; }
+    template <class T> T* row(int j) const { return p && j >= base ? reinterpret_cast<T*>(p + (size_t)(j - base) * row_bytes) : nullptr; }
+};
+
 }  // namespace
 
 struct bmm_chain {
@@ -529,7 +541,7 @@ struct bmm_chain {
     int* dDbgFlag = nullptr;      // -DBMM_DEBUG_HOOKS: raised by a kernel that meets a label out of range
     // posterior predictive of new rows: their bit planes [ceil(P/32)][predM], the predictive
     // table image of the counting samplers (the explicit samplers' own image dTab is the predictive image), the
-    // accumulators that live across sweeps, and what a sweep folds while pred_fold is set
+    // accumulators that live across sweeps, and what a sweep folds and records (pred_rec: rows of predM doubles)
     int64_t predM = 0;
     uint32_t* dXnb = nullptr;
     double *dPredTab = nullptr, *dPredMax = nullptr, *dPredSum = nullptr, *dRespAcc = nullptr;
@@ -538,13 +550,10 @@ struct bmm_chain {
     predict_fn pfn = nullptr;
     int pred_grid_max = 0;
     size_t pred_lds = 0;
-    bool pred_fold = false;       // sweeps j >= pred_from are folded as they are enqueued
-    int pred_from = 0;
-    double* pred_trace = nullptr; // or [..][predM] on the device: row j - pred_trace_base receives sweep j's logdens
-    int pred_trace_base = 0;
+    SweepTrace pred_rec;
     // leave-one-out predictive of the fitted rows: the two table sets of the counting samplers
     // (the explicit samplers score their own image dTab), the accumulators [kLooAcc][N] that live across sweeps, the
-    // outputs of k_loo_finish ([kLooOut][N], then the scalars), and what a sweep folds while loo_fold is set
+    // outputs of k_loo_finish ([kLooOut][N], then the scalars), and what a sweep folds and records (loo_rec: rows of N doubles)
     bool loo_on = false;
     double *dLooTab = nullptr, *dLooAcc = nullptr, *dLooOut = nullptr;
     bool loo_generic = false;    // a resident shape whose rows k_loo_generic scores (lookup_loo), on scratch columns of its own
@@ -554,10 +563,7 @@ struct bmm_chain {
     loo_fn lfn = nullptr;
     int loo_minus = 0, loo_grid_max = 0;
     size_t loo_lds = 0;
-    bool loo_fold = false;       // sweeps j >= loo_from are folded as they are enqueued
-    int loo_from = 0;
-    double* loo_trace = nullptr; // or [..][N] on the device: row j - loo_trace_base receives sweep j's ell
-    int loo_trace_base = 0;
+    SweepTrace loo_rec;
     // split-merge moves: sm_moves > 0: that many moves at the start of every sweep from the
     // second; the side bytes, the final scan's log probabilities, the statistic sets of one move ([sm_sets]), the
     // move's cell and the five counters.  Moves are numbered within the sweep they precede (sm_tag, sm_ctr).
@@ -572,16 +578,16 @@ struct bmm_chain {
     // feature selection: fs_mask: the table builds read the inclusion mask (set once a mask
     // was given or the step armed, and for good: the kernel choice then leaves out the forms that build their own
     // tables); fs_on: a gamma-step behind every sweep end.  One block holds the mask words, the indicator bytes, the
-    // step record [3][P] and the two accumulators; steps of sweeps j >= fs_from are folded.
+    // step record [3][P] and the two accumulators; fs_rec: the steps that are folded (every one of an armed chain, the
+    // kept ones of a run) and the rows of P indicator bytes they are recorded in.
     bool fs_mask = false, fs_on = false;
     double fs_rho = 0.5, fs_logit = 0.0;
     char* dFsBlock = nullptr;
     uint32_t *dFsMask = nullptr, *dFsCount = nullptr;
     uint8_t* dFsGamma = nullptr;
     double *dFsRec = nullptr, *dFsProb = nullptr;
-    int fs_folded = 0, fs_from = 0, fs_last = -1;  // fs_last: the sweep of the last step, -1 none yet
-    uint8_t* fs_trace = nullptr;  // or [..][P] on the device: row j - fs_trace_base receives sweep j's indicators
-    int fs_trace_base = 0;
+    int fs_folded = 0, fs_last = -1;  // fs_last: the sweep of the last step, -1 none yet
+    SweepTrace fs_rec;
     // the last k-modes++ initialisation, kept on the host: the k_eff centres [k_eff][W], the
     // picked rows and the final cluster sizes
     int init_keff = 0;
@@ -603,7 +609,7 @@ struct bmm_chain {
     uint8_t* dEaSide = nullptr;
     int ea_tag = -1;
     uint32_t ea_ctr = 0;
-    int32_t* k_trace = nullptr;  // or [S] on the device: row j - burnin receives K after sweep j (a run)
+    SweepTrace k_rec;  // a run: one int32 per kept sweep, K after it
     int prof = 0;             // > 0: HIP events around the resample launches of every prof-th sweep
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
@@ -612,6 +618,88 @@ struct bmm_chain {
 };
 
 namespace {
+
+// device memory for `bytes` more, refused with a message when it is not there
+int pred_room(size_t bytes, const char* what) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (bytes > free_b)
+        return set_err(BMM_E_ARG, "predictive: %s needs %zu bytes of device memory, %zu are free", what, bytes, free_b);
+    return BMM_OK;
+}
+// One recording into a SweepTrace of a chain.  It owns the device rows (none: the sweeps are folded, not recorded),
+// installs the window and, when it ends, puts back what was there and waits for the chain's stream before the rows
+// may go: on every return path.  Without rows nothing is waited for.
+struct Recording {
+    bmm_chain* c = nullptr;
+    SweepTrace* slot = nullptr;  // where it is installed ...
+    SweepTrace before;           // ... and what was there
+    hipError_t status = hipSuccess;  // of the wait in end()
+    DevBuf rows;
+    int alloc(size_t bytes, const char* what) {  // rows that are refused with a message when the room is not there
+        const int rc = pred_room(bytes, what);
+        if (rc) return rc;
+        HIP_TRY(rows.alloc(bytes));
+        return BMM_OK;
+    }
+    void begin(bmm_chain* chain, SweepTrace& s, size_t row_bytes, int base, int from, bool fold) {
+        c = chain; slot = &s; before = s;
+        s.p = rows.as<char>(); s.row_bytes = row_bytes; s.base = base; s.from = from; s.fold = fold;
+    }
+    hipError_t end() {
+        if (!slot) return status;
+        *std::exchange(slot, nullptr) = before;
+        return status = rows.p ? hipStreamSynchronize(c->stream) : hipSuccess;
+    }
+    int end_run(int rc) {  // ... at the end of a run: its status, or that the wait failed
+        const hipError_t es = end();
+        return rc == BMM_OK && es != hipSuccess ? set_err(BMM_E_HIP, "the run failed: %s", hipGetErrorString(es)) : rc;
+    }
+    ~Recording() { (void)end(); }
+};
+
+// rows x width doubles on the device (row-major) into the caller's column-major ld x width matrix, from row row0 on
+int rows_out(const double* dtrace, int rows, int64_t width, double* out, int ld, int row0) {
+    std::vector<double> line((size_t)width);
+    for (int s = 0; s < rows; ++s) {
+        HIP_TRY(hipMemcpy(line.data(), dtrace + (size_t)s * (size_t)width, (size_t)width * sizeof(double), hipMemcpyDeviceToHost));
+        for (int64_t m = 0; m < width; ++m) out[(size_t)(row0 + s) + (size_t)m * (size_t)ld] = line[(size_t)m];
+    }
+    return BMM_OK;
+}
+// the first sweep a run folds (trace row 0 of a run without burn-in is the start, not a sweep)
+int run_first_fold(const bmm_chain* c) { return c->burnin > 0 ? c->burnin : 1; }
+// ... and the trace of a run, S kept rows recorded from sweep `burnin` on, into the caller's S x width matrix: the rows
+// before the first fold (1 without burn-in) stay NaN
+int run_rows_out(const bmm_chain* c, const double* dtrace, int64_t width, double* out) {
+    const int S = c->S, first = run_first_fold(c) - c->burnin;
+    for (int s = 0; s < first && s < S; ++s)
+        for (int64_t m = 0; m < width; ++m) out[(size_t)s + (size_t)m * (size_t)S] = std::nan("");
+    return S > first ? rows_out(dtrace + (size_t)first * (size_t)width, S - first, width, out, S, first) : BMM_OK;
+}
+
+// What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_loo_summary,
+// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init; bmm_alloc_run fills `alloc` for its own run), and what a
+// *_run_predict / *_run_relabel / *_run_probs entry point was handed.
+struct RunOptions {
+    struct { bool on = false; bmm_partition_out o{}; } partition;
+    struct { bool on = false; bmm_loo_out o{}; } loo;
+    struct { int moves = 0, scans = 0; } sm;
+    struct { bool on = false; bmm_feature_out o{}; } fs;
+    struct { int kind = 0, iters = 0; } init;
+    struct { bool on = false; const double* log_prior_k = nullptr; int K0 = 0, moves = 0; double eject_a = 1.0; int32_t* k_out = nullptr; int64_t* moves_out = nullptr; } alloc;
+    const bmm_relabel_hooks* hooks = nullptr;  // *_run_probs
+    const bmm_relabel_out* rel = nullptr;      // *_run_relabel
+    const int32_t* Xnew = nullptr; int64_t M = 0; const bmm_predict_out* pred = nullptr;  // *_run_predict
+    bool predict() const { return pred && M > 0; }
+};
+thread_local RunOptions g_armed;
+// First statement of every public *_run* entry point, bmm_multi_run included: the armed state moves into the call,
+// so whatever the call returns, and wherever it returns from, nothing is armed afterwards.
+RunOptions take_run_options() { return std::exchange(g_armed, RunOptions{}); }
+// ... and what the bmm_last_* getters read of the thread's last run
+thread_local int64_t g_sm_stats[5] = {0, 0, 0, 0, 0};
+thread_local bmm_init_info g_init_info{};
 
 int planes_alloc(bmm_chain* c, size_t words) {
     size_t got = 0;
@@ -1078,9 +1166,8 @@ int enqueue_predict(bmm_chain* c, double* logdens, double* resp, bool fold) {
 }
 // the end of sweep j: its state is folded when a predictive run or bmm_chain_sweeps_predict asked for it
 int sweep_end_predict(bmm_chain* c, int j) {
-    if (!c->pred_fold || c->predM <= 0 || j < c->pred_from) return BMM_OK;
-    double* row = c->pred_trace ? c->pred_trace + (size_t)(j - c->pred_trace_base) * (size_t)c->predM : nullptr;
-    return enqueue_predict(c, row, nullptr, true);
+    if (!c->pred_rec.folds(j) || c->predM <= 0) return BMM_OK;
+    return enqueue_predict(c, c->pred_rec.row<double>(j), nullptr, true);
 }
 
 // ---- leave-one-out predictive of the fitted rows ----
@@ -1115,9 +1202,8 @@ int enqueue_loo(bmm_chain* c, int j, double* ell, bool fold) {
 // the end of sweep j: what a predictive run, a leave-one-out run or the resident calls asked to fold
 int sweep_end_folds(bmm_chain* c, int j) {
     const int rc = sweep_end_predict(c, j);
-    if (rc || !c->loo_fold || !c->loo_on || j < c->loo_from) return rc;
-    double* row = c->loo_trace ? c->loo_trace + (size_t)(j - c->loo_trace_base) * (size_t)c->p.N : nullptr;
-    return enqueue_loo(c, j, row, true);
+    if (rc || !c->loo_rec.folds(j) || !c->loo_on) return rc;
+    return enqueue_loo(c, j, c->loo_rec.row<double>(j), true);
 }
 
 // what the predictive, the leave-one-out summary and the split-merge moves answer a chain with a feature mask
@@ -1222,9 +1308,9 @@ int enqueue_fs_gamma(bmm_chain* c, int j) {
     const ChainParams& p = c->p;
     FsArgs a{};
     a.Nk = c->dNk; a.S = c->dS; a.mask = c->dFsMask; a.gamma = c->dFsGamma; a.rec = c->dFsRec;
-    a.gamma_row = c->fs_trace && j >= c->fs_trace_base ? c->fs_trace + (size_t)(j - c->fs_trace_base) * (size_t)p.P : nullptr;
+    a.gamma_row = c->fs_rec.row<uint8_t>(j);
     a.incl_count = c->dFsCount; a.incl_prob = c->dFsProb; a.logit_rho = c->fs_logit; a.sweep = (uint32_t)j;
-    a.fold = j >= c->fs_from ? 1 : 0;
+    a.fold = c->fs_rec.folds(j) ? 1 : 0;
     hipLaunchKernelGGL(k_fs_gamma, dim3((unsigned)((p.P + 31) / 32)), dim3(kFsThreads), 0, c->stream, p, a);
     HIP_TRY(hipGetLastError());
     if (a.fold) c->fs_folded++;
@@ -1367,6 +1453,18 @@ int init_labels(bmm_chain* c, int kind, int n_centres, int iters, bmm_init_info*
     return BMM_OK;
 }
 
+// The label row that the moves ahead of sweep j work on and the sweep then reads: row j - 1, or a copy of it when the
+// trace holds the original (a row of the trace stays as it was recorded, with the theta-hat of its sweep).
+int moves_row(bmm_chain* c, int j, int32_t** row) {
+    *row = label_row(c, j - 1);
+    if (c->dTrace && j - 1 >= c->burnin) {
+        int32_t* const copy = c->dZ[(j - 1) & 1];
+        HIP_TRY(hipMemcpyAsync(copy, *row, (size_t)c->p.N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+        *row = copy;
+    }
+    return BMM_OK;
+}
+
 // one sweep (index j >= 1) enqueued on the stream
 // phase 0: whole sweep; 1: z-resample only; 2: parameter draws and tables only (sharded chains)
 int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
@@ -1394,34 +1492,16 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
         HIP_TRY(hipGetLastError());
         return sweep_end_folds(c, j);
     }
-    if (c->sm_moves > 0 && j >= 2 && phase == 0) {
-        // the armed split-merge moves, ahead of the sweep's first table build; a row of the trace stays as it was
-        // recorded (with the theta-hat of its sweep): the moves then work on a copy, which the sweep reads
-        int32_t* row = label_row(c, j - 1);
-        if (c->dTrace && j - 1 >= c->burnin) {
-            int32_t* const copy = c->dZ[(j - 1) & 1];
-            HIP_TRY(hipMemcpyAsync(copy, row, (size_t)p.N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-            row = copy;
-        }
+    // the armed moves, ahead of the sweep's first table build: split-merge (a DP chain) or eject / absorb (a finite one)
+    const int n_sm = c->sm_moves, n_ea = c->alloc_on ? c->alloc_moves : 0;
+    if ((n_sm > 0 || n_ea > 0) && j >= 2 && phase == 0) {
+        int32_t* row = nullptr;
+        int rc = moves_row(c, j, &row);
+        if (rc) return rc;
         zin = row;
-        for (int m = 0; m < c->sm_moves; ++m) {
-            const int rc = enqueue_move(c, row, j, false);
-            if (rc) return rc;
-        }
-    }
-    if (c->alloc_on && c->alloc_moves > 0 && j >= 2 && phase == 0) {
-        // the armed eject / absorb moves, where the split-merge moves of a DP chain sit and on a copy for the same reason
-        int32_t* row = label_row(c, j - 1);
-        if (c->dTrace && j - 1 >= c->burnin) {
-            int32_t* const copy = c->dZ[(j - 1) & 1];
-            HIP_TRY(hipMemcpyAsync(copy, row, (size_t)p.N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-            row = copy;
-        }
-        zin = row;
-        for (int m = 0; m < c->alloc_moves; ++m) {
-            const int rc = enqueue_ea(c, row, j);
-            if (rc) return rc;
-        }
+        for (int m = 0; m < n_sm && rc == BMM_OK; ++m) rc = enqueue_move(c, row, j, false);
+        for (int m = 0; m < n_ea && rc == BMM_OK; ++m) rc = enqueue_ea(c, row, j);
+        if (rc) return rc;
     }
     int64_t lo = 0;
     while (lo < p.N) {
@@ -1442,8 +1522,8 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
     hipLaunchKernelGGL(k_count_sweep_end, dim3(1), dim3(1024), 0, c->stream, p, c->dNk, c->dS, c->dDNk,
                        c->dDS, c->dAlpha, (uint32_t)j, th_tr, al_tr, nk_tr);
     HIP_TRY(hipGetLastError());
-    if (c->k_trace && rec)  // the allocation sampler's K after this sweep, device to device
-        HIP_TRY(hipMemcpyAsync(c->k_trace + s, c->dEaK, sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    if (int32_t* const k_row = c->k_rec.row<int32_t>(j))  // the allocation sampler's K after this sweep, device to device
+        HIP_TRY(hipMemcpyAsync(k_row, c->dEaK, sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
     if (c->fs_on) {  // the gamma-step, from the counts the sweep end has just folded; sweep j + 1 reads its mask
         const int rc = enqueue_fs_gamma(c, j);
         if (rc) return rc;
@@ -2176,6 +2256,20 @@ static int pred_reset(bmm_chain* c) {
     if (c->dRespAcc) HIP_TRY(hipMemsetAsync(c->dRespAcc, 0, (size_t)c->predM * c->p.Kc * sizeof(double), c->stream));
     return BMM_OK;
 }
+// n more sweeps folded through `slot` and, with `trace` (n x width, the caller's), recorded; without: enqueued, not waited for
+static int sweeps_folded(bmm_chain* c, int n, SweepTrace& slot, int64_t width, double* trace, const char* what) {
+    if (n == 0) return BMM_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    Recording rec;
+    int rc = trace ? rec.alloc((size_t)n * (size_t)width * sizeof(double), what) : BMM_OK;
+    if (rc) return rc;
+    rec.begin(c, slot, (size_t)width * sizeof(double), c->sweep + 1, c->sweep + 1, true);
+    rc = bmm_chain_sweeps(c, n);
+    const hipError_t e = rec.end();
+    if (rc || !trace) return rc;
+    if (e != hipSuccess) return set_err(BMM_E_HIP, "the sweeps failed: %s", hipGetErrorString(e));
+    return rows_out(rec.rows.as<double>(), n, width, trace, n, 0);
+}
 // the predictive kernel of the chain's shape, set up on first use
 static int pred_setup(bmm_chain* c) {
     if (c->generic || c->pfn) return BMM_OK;
@@ -2189,24 +2283,6 @@ static int pred_setup(bmm_chain* c) {
     c->pfn = f;
     c->pred_lds = lds;
     c->pred_grid_max = (per_cu < 1 ? 1 : per_cu) * c->num_cus;
-    return BMM_OK;
-}
-// device memory for `bytes` more, refused with a message when it is not there
-static int pred_room(size_t bytes, const char* what) {
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (bytes > free_b)
-        return set_err(BMM_E_ARG, "predictive: %s needs %zu bytes of device memory, %zu are free", what, bytes, free_b);
-    return BMM_OK;
-}
-// rows x M log densities on the device (row-major) into the caller's rows x M column-major matrix
-static int pred_trace_out(bmm_chain* c, const double* dtrace, int rows, double* out, int ld, int row0) {
-    const int64_t M = c->predM;
-    std::vector<double> line((size_t)M);
-    for (int s = 0; s < rows; ++s) {
-        HIP_TRY(hipMemcpy(line.data(), dtrace + (size_t)s * (size_t)M, (size_t)M * sizeof(double), hipMemcpyDeviceToHost));
-        for (int64_t m = 0; m < M; ++m) out[(size_t)(row0 + s) + (size_t)m * (size_t)ld] = line[(size_t)m];
-    }
     return BMM_OK;
 }
 
@@ -2319,27 +2395,7 @@ int bmm_chain_sweeps_predict(bmm_chain* c, int n, double* logdens_trace) {
         int rc = pred_refused(c);
         if (rc) return rc;
         if (c->predM <= 0) return set_err(BMM_E_STATE, "no new data set (bmm_chain_set_newdata_host)");
-        if (n == 0) return BMM_OK;
-        HIP_TRY(hipSetDevice(c->device));
-        DevBuf tr;
-        if (logdens_trace) {
-            const size_t bytes = (size_t)n * (size_t)c->predM * sizeof(double);
-            rc = pred_room(bytes, "the log-density trace (n x M doubles)");
-            if (rc) return rc;
-            HIP_TRY(tr.alloc(bytes));
-        }
-        c->pred_fold = true;
-        c->pred_from = c->sweep + 1;
-        c->pred_trace = tr.as<double>();
-        c->pred_trace_base = c->sweep + 1;
-        rc = bmm_chain_sweeps(c, n);
-        c->pred_fold = false;
-        c->pred_trace = nullptr;
-        if (!logdens_trace) return rc;  // as bmm_chain_sweeps: enqueued, not waited for
-        const hipError_t e = hipStreamSynchronize(c->stream);  // the trace buffer goes out of scope
-        if (rc) return rc;
-        if (e != hipSuccess) return set_err(BMM_E_HIP, "the sweeps failed: %s", hipGetErrorString(e));
-        return pred_trace_out(c, tr.as<double>(), n, logdens_trace, n, 0);
+        return sweeps_folded(c, n, c->pred_rec, c->predM, logdens_trace, "the log-density trace (n x M doubles)");
     });
 }
 
@@ -2378,6 +2434,37 @@ int bmm_chain_predict_reset(bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     HIP_TRY(hipSetDevice(c->device));
     return pred_reset(c);
+}
+
+// ... of a run: every kept sweep is folded as it is enqueued (sweep_end_predict)
+static int pred_run_check(const RunOptions& o) {
+    if (!o.pred) return BMM_OK;
+    if (o.M < 0) return set_err(BMM_E_ARG, "M must be >= 0");
+    if (o.M > 0 && !o.Xnew) return set_err(BMM_E_ARG, "Xnew is null");
+    if (o.M > 0 && !o.pred->lppd) return set_err(BMM_E_ARG, "null buffer: lppd");
+    return BMM_OK;
+}
+static int pred_run_attach(bmm_chain* c, const RunOptions& o, Recording& rec) {
+    if (!o.predict()) return BMM_OK;
+    c->pred_resp = o.pred->resp != nullptr;
+    int rc = bmm_chain_set_newdata_host(c, o.Xnew, o.M);
+    if (rc == BMM_OK && o.pred->logdens) rc = rec.alloc((size_t)c->S * (size_t)o.M * sizeof(double), "the log-density trace (S x M doubles)");
+    if (rc) return rc;
+    rec.begin(c, c->pred_rec, (size_t)o.M * sizeof(double), c->burnin, run_first_fold(c), true);
+    return BMM_OK;
+}
+static int pred_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, int rc) {
+    if (!o.predict()) return rc;
+    rc = rec.end_run(rc);
+    if (rc) return rc;
+    if (c->pred_folded < 1) {
+        for (int64_t m = 0; m < o.M; ++m) o.pred->lppd[m] = std::nan("");
+        if (o.pred->resp) for (int64_t q = 0; q < o.M * c->p.Kc; ++q) o.pred->resp[q] = std::nan("");
+    } else {
+        rc = bmm_chain_get_predictive(c, o.pred->lppd, o.pred->resp, nullptr);
+    }
+    if (rc == BMM_OK && o.pred->logdens) rc = run_rows_out(c, rec.rows.as<double>(), o.M, o.pred->logdens);
+    return rc;
 }
 
 // ---- leave-one-out predictive of the fitted rows ----
@@ -2434,16 +2521,6 @@ static int loo_setup(bmm_chain* c) {
 static int loo_seated(const bmm_chain* c) {
     if (c->p.mode != MODE_COLLAPSED && c->sweep < 1)
         return set_err(BMM_E_STATE, "no row has a label before the first sweep: there is no leave-one-out predictive of this state");
-    return BMM_OK;
-}
-// rows x N values on the device (row-major) into the caller's ld x N column-major matrix, from row row0 on
-static int loo_trace_out(bmm_chain* c, const double* dtrace, int rows, double* out, int ld, int row0) {
-    const int64_t N = c->p.N;
-    std::vector<double> line((size_t)N);
-    for (int s = 0; s < rows; ++s) {
-        HIP_TRY(hipMemcpy(line.data(), dtrace + (size_t)s * (size_t)N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < N; ++i) out[(size_t)(row0 + s) + (size_t)i * (size_t)ld] = line[(size_t)i];
-    }
     return BMM_OK;
 }
 
@@ -2516,27 +2593,7 @@ int bmm_chain_sweeps_loo(bmm_chain* c, int n, double* ell_trace) {
         int rc = loo_refused(c);
         if (rc == BMM_OK) rc = loo_armed(c);
         if (rc) return rc;
-        if (n == 0) return BMM_OK;
-        HIP_TRY(hipSetDevice(c->device));
-        DevBuf tr;
-        if (ell_trace) {
-            const size_t bytes = (size_t)n * (size_t)c->p.N * sizeof(double);
-            rc = pred_room(bytes, "the leave-one-out trace (n x N doubles)");
-            if (rc) return rc;
-            HIP_TRY(tr.alloc(bytes));
-        }
-        c->loo_fold = true;
-        c->loo_from = c->sweep + 1;
-        c->loo_trace = tr.as<double>();
-        c->loo_trace_base = c->sweep + 1;
-        rc = bmm_chain_sweeps(c, n);
-        c->loo_fold = false;
-        c->loo_trace = nullptr;
-        if (!ell_trace) return rc;  // as bmm_chain_sweeps: enqueued, not waited for
-        const hipError_t e = hipStreamSynchronize(c->stream);  // the trace buffer goes out of scope
-        if (rc) return rc;
-        if (e != hipSuccess) return set_err(BMM_E_HIP, "the sweeps failed: %s", hipGetErrorString(e));
-        return loo_trace_out(c, tr.as<double>(), n, ell_trace, n, 0);
+        return sweeps_folded(c, n, c->loo_rec, c->p.N, ell_trace, "the leave-one-out trace (n x N doubles)");
     });
 }
 
@@ -2583,7 +2640,38 @@ int bmm_chain_loo_reset(bmm_chain* c) {
     return loo_reset(c);
 }
 
+// ... of a run: armed for it, every kept sweep folded as it is enqueued (sweep_end_folds)
+static int loo_run_attach(bmm_chain* c, const RunOptions& o, Recording& rec) {
+    if (!o.loo.on) return BMM_OK;
+    int rc = bmm_chain_set_loo(c, 1);
+    if (rc == BMM_OK && o.loo.o.ell) rc = rec.alloc((size_t)c->S * (size_t)c->p.N * sizeof(double), "the leave-one-out trace (S x N doubles)");
+    if (rc) return rc;
+    rec.begin(c, c->loo_rec, (size_t)c->p.N * sizeof(double), c->burnin, run_first_fold(c), true);
+    return BMM_OK;
+}
 // the outputs of a run that had the summary armed: S kept rows, the first `burnin ? 0 : 1` of them not folded
+static int loo_run_out(bmm_chain* c, const bmm_loo_out& o, const double* dtrace) {
+    const int64_t N = c->p.N;
+    const double nan = std::nan("");
+    int rc = BMM_OK;
+    if (c->loo_folded < 1) {
+        double* const rows[kLooOut] = {o.log_cpo, o.ess, o.lppd, o.mean, o.var};
+        for (double* r : rows) if (r) for (int64_t i = 0; i < N; ++i) r[i] = nan;
+        double* const sc[4] = {o.lpml, o.min_ess, o.p_waic, o.elpd_waic};
+        for (double* v : sc) if (v) *v = nan;
+        if (o.n_folded) *o.n_folded = 0;
+    } else {
+        rc = bmm_chain_get_loo(c, &o);
+    }
+    if (rc == BMM_OK && o.ell) rc = run_rows_out(c, dtrace, N, o.ell);
+    return rc;
+}
+static int loo_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, int rc) {
+    if (!o.loo.on) return rc;
+    rc = rec.end_run(rc);
+    return rc == BMM_OK ? loo_run_out(c, o.loo.o, rec.rows.as<double>()) : rc;
+}
+
 // ---- split-merge moves ----
 int bmm_chain_set_split_merge(bmm_chain* c, int moves_per_sweep, int scans) {
     return guarded([&]() -> int {
@@ -2660,6 +2748,15 @@ int bmm_chain_split_merge_stats(bmm_chain* c, int64_t out[5]) {
     HIP_TRY(hipMemcpy(h, c->dSmCounters, sizeof h, hipMemcpyDeviceToHost));
     for (int q = 0; q < 5; ++q) out[q] = h[q];
     return BMM_OK;
+}
+
+// ... of a run: the moves armed for it (bmm_set_split_merge), and their counters for bmm_last_split_merge_stats
+static int sm_run_attach(bmm_chain* c, const RunOptions& o) {
+    for (int64_t& v : g_sm_stats) v = 0;
+    return o.sm.moves > 0 ? bmm_chain_set_split_merge(c, o.sm.moves, o.sm.scans) : BMM_OK;
+}
+static int sm_run_collect(bmm_chain* c, const RunOptions& o, int rc) {
+    return rc == BMM_OK && o.sm.moves > 0 ? bmm_chain_split_merge_stats(c, g_sm_stats) : rc;
 }
 
 int bmm_chain_set_labels(bmm_chain* c, const int32_t* z1) {
@@ -2872,7 +2969,44 @@ int bmm_chain_alloc_stats(bmm_chain* c, int64_t out[4]) {
     });
 }
 
+// ... of a run (bmm_alloc_run): armed, K set (the labels above it empty), K recorded behind every kept sweep
+static int alloc_run_check(const RunOptions& o) {
+    if (o.alloc.on && (o.predict() || o.loo.on || o.sm.moves > 0 || o.fs.on || o.init.kind != 0 || o.rel || o.hooks))
+        return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is not offered together with relabelling, feature selection, split-merge moves, "
+                       "the leave-one-out summary, newdata or a device start: they assume a fixed number of components");
+    return BMM_OK;
+}
+static int alloc_run_attach(bmm_chain* c, const RunOptions& o, Recording& rec) {
+    if (!o.alloc.on) return BMM_OK;
+    int rc = bmm_chain_set_alloc(c, o.alloc.log_prior_k, o.alloc.moves, o.alloc.eject_a);
+    if (rc == BMM_OK) rc = alloc_set_k(c, o.alloc.K0);
+    if (rc) return rc;
+    HIP_TRY(rec.rows.alloc((size_t)c->S * sizeof(int32_t)));
+    const int32_t k0 = o.alloc.K0;
+    if (c->burnin == 0) HIP_TRY(hipMemcpy(rec.rows.p, &k0, sizeof k0, hipMemcpyHostToDevice));  // trace row 0: the starting state
+    rec.begin(c, c->k_rec, sizeof(int32_t), c->burnin, c->burnin, false);
+    return BMM_OK;
+}
+static int alloc_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, int rc) {
+    if (!o.alloc.on) return rc;
+    rc = rec.end_run(rc);
+    if (rc) return rc;
+    const hipError_t ec = hipMemcpy(o.alloc.k_out, rec.rows.p, (size_t)c->S * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (ec != hipSuccess) return set_err(BMM_E_HIP, "copying the K trace failed: %s", hipGetErrorString(ec));
+    return o.alloc.moves_out ? bmm_chain_alloc_stats(c, o.alloc.moves_out) : BMM_OK;
+}
+
 // ---- k-modes++ initial allocation ----
+// ... of a run: the start armed for it (bmm_set_init), from the planes that have just arrived
+static int init_run_check(const RunOptions& o, int sampler) {
+    if (o.init.kind != 0 && sampler != BMM_SAMPLER_COLLAPSED)
+        return set_err(BMM_E_UNSUPPORTED, "a device start is armed (bmm_set_init): offered for runs of the finite collapsed sampler only");
+    return BMM_OK;
+}
+static int init_run_attach(bmm_chain* c, const RunOptions& o) {
+    return o.init.kind != 0 ? init_labels(c, o.init.kind, 0, o.init.iters, &g_init_info) : BMM_OK;
+}
+
 int bmm_chain_init_labels(bmm_chain* c, int kind, int n_centres, int iters, bmm_init_info* info) {
     return guarded([&]() -> int {
         if (!c) return set_err(BMM_E_ARG, "null chain");
@@ -2960,7 +3094,8 @@ int bmm_chain_set_feature_select(bmm_chain* c, int on, double rho) {
         if (rc) return rc;
         c->fs_rho = rho;
         c->fs_logit = log_(rho) - log_(1.0 - rho);
-        c->fs_from = 0;
+        c->fs_rec.fold = true;  // every step from now on
+        c->fs_rec.from = 0;
         c->fs_on = true;
         return BMM_OK;
     });
@@ -3024,18 +3159,14 @@ int bmm_chain_sweeps_features(bmm_chain* c, int n, uint8_t* gamma_trace) {
         if (n == 0) return BMM_OK;
         HIP_TRY(hipSetDevice(c->device));
         const size_t bytes = (size_t)n * (size_t)c->p.P;
-        DevBuf tr;
-        HIP_TRY(tr.alloc(bytes));
-        c->fs_trace = tr.as<uint8_t>();
-        c->fs_trace_base = c->sweep + 1;
+        Recording rec;
+        HIP_TRY(rec.rows.alloc(bytes));
+        rec.begin(c, c->fs_rec, (size_t)c->p.P, c->sweep + 1, c->fs_rec.from, c->fs_rec.fold);
         int rc = bmm_chain_sweeps(c, n);
-        c->fs_trace = nullptr;
         if (rc == BMM_OK) {
-            hipError_t e = hipMemcpyAsync(gamma_trace, tr.p, bytes, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            hipError_t e = hipMemcpyAsync(gamma_trace, rec.rows.p, bytes, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = rec.end();
             if (e != hipSuccess) rc = set_err(BMM_E_HIP, "copying the indicator trace failed: %s", hipGetErrorString(e));
-        } else {
-            (void)hipStreamSynchronize(c->stream);  // before the trace may go
         }
         return rc;
     });
@@ -3072,26 +3203,46 @@ int bmm_chain_feature_reset(bmm_chain* c) {
     });
 }
 
-static int loo_run_out(bmm_chain* c, const bmm_loo_out& o, const double* dtrace, int S, int burnin) {
-    const int64_t N = c->p.N;
-    const double nan = std::nan("");
-    int rc = BMM_OK;
-    if (c->loo_folded < 1) {
-        double* const rows[kLooOut] = {o.log_cpo, o.ess, o.lppd, o.mean, o.var};
-        for (double* r : rows) if (r) for (int64_t i = 0; i < N; ++i) r[i] = nan;
-        double* const sc[4] = {o.lpml, o.min_ess, o.p_waic, o.elpd_waic};
-        for (double* v : sc) if (v) *v = nan;
-        if (o.n_folded) *o.n_folded = 0;
-    } else {
-        rc = bmm_chain_get_loo(c, &o);
+// ... of a run: armed for it (bmm_set_feature_select), a gamma-step behind every sweep, kept sweeps folded and recorded
+static int fs_run_check(const RunOptions& o, int sampler, double beta, double gamma) {
+    if (!o.fs.on) return BMM_OK;
+    if (explicit_params(sampler))
+        return set_err(BMM_E_UNSUPPORTED, "feature selection is offered for the collapsed and DP samplers only: the stick-breaking and "
+                       "full samplers carry theta, which the collapsed indicator step integrates out");
+    if (sampler == BMM_SAMPLER_DP && beta != gamma)
+        return set_err(BMM_E_UNSUPPORTED, "feature selection on the DP sampler needs beta == gamma: its new-cluster term is the model's only then");
+    if (o.predict() || o.loo.on || o.sm.moves > 0)
+        return set_err(BMM_E_UNSUPPORTED, "feature selection is not offered together with newdata, the leave-one-out summary or split-merge "
+                       "moves: their tables and ratios are written for the all-features model");
+    const bmm_feature_out& f = o.fs.o;
+    if (!(f.rho > 0.0 && f.rho < 1.0)) return set_err(BMM_E_ARG, "rho must lie strictly inside (0, 1): it is the prior probability that a feature clusters");
+    if (!f.gamma || !f.inclusion || !f.inclusion_rb || !f.n_selected) return set_err(BMM_E_ARG, "feature selection: null buffer");
+    return BMM_OK;
+}
+static int fs_run_attach(bmm_chain* c, const RunOptions& o, Recording& rec) {
+    if (!o.fs.on) return BMM_OK;
+    const int rc = bmm_chain_set_feature_select(c, 1, o.fs.o.rho);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->S * (size_t)c->p.P;
+    HIP_TRY(rec.rows.alloc(bytes));
+    HIP_TRY(hipMemsetAsync(rec.rows.p, 1, bytes, c->stream));  // (trace row 0 of a run without burn-in: the initial mask)
+    rec.begin(c, c->fs_rec, (size_t)c->p.P, c->burnin, run_first_fold(c), true);
+    return BMM_OK;
+}
+static int fs_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, int rc) {
+    if (!o.fs.on) return rc;
+    rc = rec.end_run(rc);
+    if (rc) return rc;
+    const bmm_feature_out& f = o.fs.o;
+    const int S = c->S, P = c->p.P;
+    const hipError_t ec = hipMemcpy(f.gamma, rec.rows.p, (size_t)S * (size_t)P, hipMemcpyDeviceToHost);
+    if (ec != hipSuccess) return set_err(BMM_E_HIP, "copying the indicator trace failed: %s", hipGetErrorString(ec));
+    for (int t = 0; t < S; ++t) {
+        int32_t n = 0;
+        for (int d = 0; d < P; ++d) n += f.gamma[(size_t)t * P + d];
+        f.n_selected[t] = n;
     }
-    if (rc == BMM_OK && o.ell) {
-        const int first = c->loo_from - burnin;  // 1 without burn-in: that row stays NaN
-        for (int s = 0; s < first && s < S; ++s)
-            for (int64_t i = 0; i < N; ++i) o.ell[(size_t)s + (size_t)i * (size_t)S] = nan;
-        if (S > first) rc = loo_trace_out(c, dtrace + (size_t)first * (size_t)N, S - first, o.ell, S, first);
-    }
-    return rc;
+    return bmm_chain_get_feature_summary(c, f.inclusion, f.inclusion_rb, f.n_folded);
 }
 
 }  // extern "C"
@@ -3106,6 +3257,20 @@ struct RunIO {
     int32_t* z_out = nullptr;
     double *theta_out = nullptr, *alpha_out = nullptr;
 };
+// ... of a counting sampler (z0: the finite one's initial labels, null for the DP sampler) and of one that carries pi and theta
+RunIO counting_io(const int32_t* z0, int32_t* z_out, double* theta_out, double* alpha_out) {
+    return RunIO{z0, nullptr, nullptr, nullptr, z_out, theta_out, alpha_out};
+}
+RunIO explicit_io(const double* pi0, const double* theta0, double* pi_out, int32_t* z_out, double* theta_out, double* alpha_out) {
+    return RunIO{nullptr, pi0, theta0, pi_out, z_out, theta_out, alpha_out};
+}
+// the options of a call with hooks, with relabelling on the device, with the predictive of new rows
+RunOptions with_hooks(RunOptions o, const bmm_relabel_hooks* hooks) { o.hooks = hooks; return o; }
+RunOptions with_relabel(RunOptions o, const bmm_relabel_out* rel) { o.rel = rel; return o; }
+RunOptions with_predict(RunOptions o, const int32_t* Xnew, int64_t M, const bmm_predict_out* pred) {
+    o.hooks = pred->hooks; o.rel = pred->relabel; o.Xnew = Xnew; o.M = M; o.pred = pred;
+    return o;
+}
 
 // Blocks of the outgoing label trace (trace_out): a whole number of observations, at most a staging piece
 size_t out_block_rows(int S, size_t el, int64_t N) {
@@ -3792,30 +3957,10 @@ int pt_check_idx(const int64_t* idx, int64_t M, int64_t N) {
     return BMM_OK;
 }
 
-// The summary of a run (bmm_set_partition_summary), per calling thread: armed for the next single-chain run.
-struct PtArmed { bool on = false; bmm_partition_out o{}; };
-thread_local PtArmed g_partition;
-// first line of every public *_run* entry point, bmm_multi_run included: whatever the call returns, and wherever it
-// returns from, the summary is no longer armed afterwards
-// ... and the leave-one-out summary (bmm_set_loo_summary), armed and disarmed the same way
-struct LooArmed { bool on = false; bmm_loo_out o{}; };
-thread_local LooArmed g_loo;
-struct SmArmed { int moves = 0, scans = 0; };
-thread_local SmArmed g_sm;
-thread_local int64_t g_sm_stats[5] = {0, 0, 0, 0, 0};
-// ... and feature selection (bmm_set_feature_select)
-struct FsArmed { bool on = false; bmm_feature_out o{}; };
-thread_local FsArmed g_fs;
-// ... and the device start of a collapsed run (bmm_set_init)
-struct InitArmed { int kind = 0, iters = 0; };
-thread_local InitArmed g_init;
-thread_local bmm_init_info g_init_info{};
-// ... and the allocation sampler's run (bmm_alloc_run arms it for its own call of run_chain)
-struct AllocArmed { bool on = false; const double* log_prior_k = nullptr; int K0 = 0, moves = 0; double eject_a = 1.0; int32_t* k_out = nullptr; int64_t* moves_out = nullptr; };
-thread_local AllocArmed g_alloc;
-struct PtDisarm { ~PtDisarm() { g_partition.on = false; g_loo.on = false; g_sm.moves = 0; g_fs.on = false; g_init.kind = 0; } };
-// what a run checks of it before any device is touched
-int pt_check_armed(const bmm_partition_out& o, int S, int64_t N, int K) {
+// The summary of a run (bmm_set_partition_summary): what the run checks of it before any device is touched
+int pt_run_check(const RunOptions& opts, int S, int64_t N, int K) {
+    if (!opts.partition.on) return BMM_OK;
+    const bmm_partition_out& o = opts.partition.o;
     if (!o.loss || !o.best || !o.n_used) return set_err(BMM_E_ARG, "partition: null buffer (loss, best, n_used)");
     int rc = pt_check_shape(S, N, K, o.criterion, o.stride);
     if (rc) return rc;
@@ -3851,8 +3996,8 @@ int pt_run_summary(bmm_chain* c, const bmm_partition_out& o) {
 }
 
 // the sweeps, then the traces out (data and starting state are in place)
-int run_body(bmm_chain* c, int nsamples, const RunIO& io, const bmm_relabel_hooks* hooks,
-             const bmm_relabel_out* rel = nullptr) {
+int run_body(bmm_chain* c, int nsamples, const RunIO& io, const RunOptions& opts) {
+    const bmm_relabel_out* const rel = opts.rel;
     const int sampler = c->p.mode, K = c->p.K, P = c->p.P, S = c->S;
     HIP_TRY(hipSetDevice(c->device));
     PhaseClock clock;
@@ -3865,7 +4010,7 @@ int run_body(bmm_chain* c, int nsamples, const RunIO& io, const bmm_relabel_hook
         if (g_progress.fn && g_progress.every > 0) rc = run_sweeps_reported(c, nsamples, step);
         else for (int j = 1; j < nsamples && rc == BMM_OK; ++j) rc = step(j);
     } else {
-        rc = hooks ? run_sweeps_hooked(c, nsamples, hooks)
+        rc = opts.hooks ? run_sweeps_hooked(c, nsamples, opts.hooks)
                    : (g_progress.fn && g_progress.every > 0 ? run_sweeps_reported(c, nsamples) : bmm_chain_sweeps(c, nsamples - 1));
     }
     if (rc) return rc;
@@ -3875,8 +4020,8 @@ int run_body(bmm_chain* c, int nsamples, const RunIO& io, const bmm_relabel_hook
     HIP_TRY(hipMemcpyAsync(io.alpha_out, c->dAlphaTrace, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (explicit_params(sampler))
         HIP_TRY(hipMemcpyAsync(io.pi_out, c->dPiTrace, (size_t)S * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (g_partition.on) {  // the clustering summary, from the resident trace (labels as sampled)
-        rc = pt_run_summary(c, g_partition.o);
+    if (opts.partition.on) {  // the clustering summary, from the resident trace (labels as sampled)
+        rc = pt_run_summary(c, opts.partition.o);
         if (rc) return rc;
     }
     if (rel) {
@@ -3972,6 +4117,17 @@ extern "C" int bmm_dbg_kernel_plan(int sampler, int64_t N, int P, int K, int64_t
 }
 #endif
 
+// relabelling on the device in a run (*_run_relabel): what is refused before any device is touched
+int st_run_check(const RunOptions& opts, int burnin, int K) {
+    const bmm_relabel_out* const rel = opts.rel;
+    if (!rel) return BMM_OK;
+    if (!rel->permutations || !rel->z_original || !rel->theta_original) return set_err(BMM_E_ARG, "null buffer");
+    if (burnin < 2 || rel->burnrelabel < 1)
+        return set_err(BMM_E_ARG, "relabel on the device needs the batch step, which the reference runs only with "
+                       "burnin >= 2 and burnrelabel >= 1 (burnin = %d, burnrelabel = %d)", burnin, rel->burnrelabel);
+    return st_check_k(K);
+}
+
 int check_run_args(const int32_t* X, int nsamples, int burnin, const RunIO& io, int sampler) {
     if (!X || !io.z_out || !io.theta_out || !io.alpha_out) return set_err(BMM_E_ARG, "null buffer");
     if (sampler == BMM_SAMPLER_COLLAPSED && !io.z0) return set_err(BMM_E_ARG, "initialK is null");
@@ -3983,49 +4139,19 @@ int check_run_args(const int32_t* X, int nsamples, int burnin, const RunIO& io, 
 
 int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int K, double alpha, double beta,
               double gamma, double a, double b, int burnin, int64_t batch, uint64_t seed, int device,
-              const RunIO& io, const bmm_relabel_hooks* hooks, const bmm_relabel_out* rel = nullptr,
-              const int32_t* Xnew = nullptr, int64_t M = 0, const bmm_predict_out* pred = nullptr) {
+              const RunIO& io, const RunOptions& opts) {
     return guarded([&]() -> int {
+        // refused before any device is touched
         int rc = check_run_args(X, nsamples, burnin, io, sampler);
+        if (rc == BMM_OK) rc = pt_run_check(opts, nsamples - burnin, N, K);
         if (rc) return rc;
-        if (g_partition.on) {  // refused before any device is touched
-            rc = pt_check_armed(g_partition.o, nsamples - burnin, N, K);
-            if (rc) return rc;
-        }
         g_init_info = bmm_init_info{};
-        if (g_init.kind != 0 && sampler != BMM_SAMPLER_COLLAPSED)  // refused before any device is touched
-            return set_err(BMM_E_UNSUPPORTED, "a device start is armed (bmm_set_init): offered for runs of the finite collapsed sampler only");
-        if (pred) {  // refused before any device is touched
-            if (M < 0) return set_err(BMM_E_ARG, "M must be >= 0");
-            if (M > 0 && !Xnew) return set_err(BMM_E_ARG, "Xnew is null");
-            if (M > 0 && !pred->lppd) return set_err(BMM_E_ARG, "null buffer: lppd");
-        }
-        if (g_fs.on) {  // refused before any device is touched
-            const bmm_feature_out& o = g_fs.o;
-            if (explicit_params(sampler))
-                return set_err(BMM_E_UNSUPPORTED, "feature selection is offered for the collapsed and DP samplers only: the stick-breaking and "
-                               "full samplers carry theta, which the collapsed indicator step integrates out");
-            if (sampler == BMM_SAMPLER_DP && beta != gamma)
-                return set_err(BMM_E_UNSUPPORTED, "feature selection on the DP sampler needs beta == gamma: its new-cluster term is the model's only then");
-            if ((pred && M > 0) || g_loo.on || g_sm.moves > 0)
-                return set_err(BMM_E_UNSUPPORTED, "feature selection is not offered together with newdata, the leave-one-out summary or split-merge "
-                               "moves: their tables and ratios are written for the all-features model");
-            if (!(o.rho > 0.0 && o.rho < 1.0)) return set_err(BMM_E_ARG, "rho must lie strictly inside (0, 1): it is the prior probability that a feature clusters");
-            if (!o.gamma || !o.inclusion || !o.inclusion_rb || !o.n_selected) return set_err(BMM_E_ARG, "feature selection: null buffer");
-        }
-        if (g_alloc.on) {  // refused before any device is touched
-            if ((pred && M > 0) || g_loo.on || g_sm.moves > 0 || g_fs.on || g_init.kind != 0 || rel || hooks)
-                return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is not offered together with relabelling, feature selection, split-merge moves, "
-                               "the leave-one-out summary, newdata or a device start: they assume a fixed number of components");
-        }
-        if (rel) {  // refused before any device is touched
-            if (!rel->permutations || !rel->z_original || !rel->theta_original) return set_err(BMM_E_ARG, "null buffer");
-            if (burnin < 2 || rel->burnrelabel < 1)
-                return set_err(BMM_E_ARG, "relabel on the device needs the batch step, which the reference runs only with "
-                               "burnin >= 2 and burnrelabel >= 1 (burnin = %d, burnrelabel = %d)", burnin, rel->burnrelabel);
-            rc = st_check_k(K);
-            if (rc) return rc;
-        }
+        rc = init_run_check(opts, sampler);
+        if (rc == BMM_OK) rc = pred_run_check(opts);
+        if (rc == BMM_OK) rc = fs_run_check(opts, sampler, beta, gamma);
+        if (rc == BMM_OK) rc = alloc_run_check(opts);
+        if (rc == BMM_OK) rc = st_run_check(opts, burnin, K);
+        if (rc) return rc;
         for (double& v : g_phase_ms) v = 0.0;
         PhaseClock clock;
         // The host's cores start validating and packing X at once (bit planes, the default layout) while this
@@ -4043,7 +4169,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
         {
             struct Guard { bmm_chain* c; ~Guard() { bmm_chain_destroy(c); } } guard{c};
             rc = run_prepare(c, nsamples, burnin);
-            if (rc == BMM_OK) rc = run_start_state(c, io, g_init.kind != 0);
+            if (rc == BMM_OK) rc = run_start_state(c, io, opts.init.kind != 0);
             if (rc) return rc;
             clock.lap(1);
             pack.join();
@@ -4055,136 +4181,23 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
                 pack.release();
                 rc = bmm_chain_set_data_host(c, X);
             }
+            if (rc == BMM_OK) rc = init_run_attach(c, opts);
             if (rc) return rc;
-            if (g_init.kind != 0) {  // the start armed for this run, from the planes that have just arrived
-                rc = init_labels(c, g_init.kind, 0, g_init.iters, &g_init_info);
-                if (rc) return rc;
-            }
             clock.lap(0);
-            // the predictive of new rows: every kept sweep is folded as it is enqueued (sweep_end_predict)
-            const bool predict = pred && M > 0;
-            const int S = nsamples - burnin;
-            DevBuf ptrace;
-            if (predict) {
-                c->pred_resp = pred->resp != nullptr;
-                rc = bmm_chain_set_newdata_host(c, Xnew, M);
-                if (rc) return rc;
-                if (pred->logdens) {
-                    const size_t bytes = (size_t)S * (size_t)M * sizeof(double);
-                    rc = pred_room(bytes, "the log-density trace (S x M doubles)");
-                    if (rc) return rc;
-                    HIP_TRY(ptrace.alloc(bytes));
-                }
-                c->pred_fold = true;
-                c->pred_from = burnin > 0 ? burnin : 1;  // (trace row 0 of a run without burn-in is the start, not a sweep)
-                c->pred_trace = ptrace.as<double>();
-                c->pred_trace_base = burnin;
-            }
-            // the leave-one-out summary: armed for this run, every kept sweep folded the same way (sweep_end_folds)
-            const bool loo = g_loo.on;
-            DevBuf ltrace;
-            if (loo) {
-                rc = bmm_chain_set_loo(c, 1);
-                if (rc) return rc;
-                if (g_loo.o.ell) {
-                    const size_t bytes = (size_t)S * (size_t)N * sizeof(double);
-                    rc = pred_room(bytes, "the leave-one-out trace (S x N doubles)");
-                    if (rc) return rc;
-                    HIP_TRY(ltrace.alloc(bytes));
-                }
-                c->loo_fold = true;
-                c->loo_from = burnin > 0 ? burnin : 1;  // (trace row 0 of a run without burn-in is the start, not a sweep)
-                c->loo_trace = ltrace.as<double>();
-                c->loo_trace_base = burnin;
-            }
-            for (int64_t& v : g_sm_stats) v = 0;
-            if (g_sm.moves > 0) {  // the split-merge moves armed for this run (bmm_set_split_merge)
-                rc = bmm_chain_set_split_merge(c, g_sm.moves, g_sm.scans);
-                if (rc) return rc;
-            }
-            // feature selection armed for this run: a gamma-step behind every sweep, kept sweeps folded and recorded
-            const bool fs = g_fs.on;
-            DevBuf gtrace;
-            if (fs) {
-                rc = bmm_chain_set_feature_select(c, 1, g_fs.o.rho);
-                if (rc) return rc;
-                const size_t bytes = (size_t)S * (size_t)P;
-                HIP_TRY(gtrace.alloc(bytes));
-                HIP_TRY(hipMemsetAsync(gtrace.p, 1, bytes, c->stream));  // (trace row 0 of a run without burn-in: the initial mask)
-                c->fs_from = burnin > 0 ? burnin : 1;
-                c->fs_trace = gtrace.as<uint8_t>();
-                c->fs_trace_base = burnin;
-            }
-            // the allocation sampler: armed, K set (the labels above it empty), K recorded behind every kept sweep
-            DevBuf ktrace;
-            if (g_alloc.on) {
-                rc = bmm_chain_set_alloc(c, g_alloc.log_prior_k, g_alloc.moves, g_alloc.eject_a);
-                if (rc == BMM_OK) rc = alloc_set_k(c, g_alloc.K0);
-                if (rc) return rc;
-                HIP_TRY(ktrace.alloc((size_t)S * sizeof(int32_t)));
-                const int32_t k0 = g_alloc.K0;
-                if (burnin == 0) HIP_TRY(hipMemcpy(ktrace.p, &k0, sizeof k0, hipMemcpyHostToDevice));  // trace row 0: the starting state
-                c->k_trace = ktrace.as<int32_t>();
-            }
-            rc = run_body(c, nsamples, io, hooks, rel);
-            if (rc == BMM_OK && g_sm.moves > 0) rc = bmm_chain_split_merge_stats(c, g_sm_stats);
-            c->k_trace = nullptr;
-            if (g_alloc.on) {
-                const hipError_t es = hipStreamSynchronize(c->stream);  // before ktrace may go
-                if (rc == BMM_OK && es != hipSuccess) rc = set_err(BMM_E_HIP, "the run failed: %s", hipGetErrorString(es));
-                if (rc == BMM_OK) {
-                    const hipError_t ec = hipMemcpy(g_alloc.k_out, ktrace.p, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToHost);
-                    if (ec != hipSuccess) rc = set_err(BMM_E_HIP, "copying the K trace failed: %s", hipGetErrorString(ec));
-                }
-                if (rc == BMM_OK && g_alloc.moves_out) rc = bmm_chain_alloc_stats(c, g_alloc.moves_out);
-            }
-            c->fs_trace = nullptr;
-            if (fs) {
-                const hipError_t es = hipStreamSynchronize(c->stream);  // before gtrace may go
-                if (rc == BMM_OK && es != hipSuccess) rc = set_err(BMM_E_HIP, "the run failed: %s", hipGetErrorString(es));
-                const bmm_feature_out& o = g_fs.o;
-                if (rc == BMM_OK) {
-                    const hipError_t ec = hipMemcpy(o.gamma, gtrace.p, (size_t)S * (size_t)P, hipMemcpyDeviceToHost);
-                    if (ec != hipSuccess) rc = set_err(BMM_E_HIP, "copying the indicator trace failed: %s", hipGetErrorString(ec));
-                }
-                if (rc == BMM_OK) {
-                    for (int t = 0; t < S; ++t) {
-                        int32_t n = 0;
-                        for (int d = 0; d < P; ++d) n += o.gamma[(size_t)t * P + d];
-                        o.n_selected[t] = n;
-                    }
-                    rc = bmm_chain_get_feature_summary(c, o.inclusion, o.inclusion_rb, o.n_folded);
-                }
-            }
-            c->loo_fold = false;
-            c->loo_trace = nullptr;
-            if (loo) {
-                const hipError_t es = hipStreamSynchronize(c->stream);  // before ltrace may go
-                if (rc == BMM_OK && es != hipSuccess) rc = set_err(BMM_E_HIP, "the run failed: %s", hipGetErrorString(es));
-                if (rc == BMM_OK) rc = loo_run_out(c, g_loo.o, ltrace.as<double>(), S, burnin);
-            }
-            c->pred_fold = false;
-            c->pred_trace = nullptr;
-            if (predict) {
-                const hipError_t es = hipStreamSynchronize(c->stream);  // before ptrace may go
-                if (rc == BMM_OK && es != hipSuccess) rc = set_err(BMM_E_HIP, "the run failed: %s", hipGetErrorString(es));
-            }
-            if (rc == BMM_OK && predict) {
-                const double nan = std::nan("");
-                if (c->pred_folded < 1) {
-                    for (int64_t m = 0; m < M; ++m) pred->lppd[m] = nan;
-                    if (pred->resp) for (int64_t q = 0; q < M * c->p.Kc; ++q) pred->resp[q] = nan;
-                } else {
-                    rc = bmm_chain_get_predictive(c, pred->lppd, pred->resp, nullptr);
-                }
-                if (rc == BMM_OK && pred->logdens) {
-                    const int first = c->pred_from - burnin;  // 1 without burn-in: that row stays NaN
-                    for (int s = 0; s < first && s < S; ++s)
-                        for (int64_t m = 0; m < M; ++m) pred->logdens[(size_t)s + (size_t)m * (size_t)S] = nan;
-                    if (S > first)
-                        rc = pred_trace_out(c, ptrace.as<double>() + (size_t)first * (size_t)M, S - first, pred->logdens, S, first);
-                }
-            }
+            // what the options record per kept sweep: each ends, and waits for the stream before its rows go, on every way out
+            Recording pred_rec, loo_rec, fs_rec, k_rec;
+            rc = pred_run_attach(c, opts, pred_rec);
+            if (rc == BMM_OK) rc = loo_run_attach(c, opts, loo_rec);
+            if (rc == BMM_OK) rc = sm_run_attach(c, opts);
+            if (rc == BMM_OK) rc = fs_run_attach(c, opts, fs_rec);
+            if (rc == BMM_OK) rc = alloc_run_attach(c, opts, k_rec);
+            if (rc) return rc;
+            rc = run_body(c, nsamples, io, opts);
+            rc = sm_run_collect(c, opts, rc);
+            rc = alloc_run_collect(c, opts, k_rec, rc);
+            rc = fs_run_collect(c, opts, fs_rec, rc);
+            rc = loo_run_collect(c, opts, loo_rec, rc);
+            rc = pred_run_collect(c, opts, pred_rec, rc);
             clock.t = std::chrono::steady_clock::now();
         }
         clock.lap(5);  // releasing the chain
@@ -4268,21 +4281,144 @@ int rccl_broadcast_words(const std::vector<int>& devs, const std::vector<void*>&
 
 extern "C" {
 
-int bmm_collapsed_run(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int K,
-                      double alpha, double beta, double gamma, double a, double b, int burnin,
-                      int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
-                      double* alpha_out) {
-    return bmm_collapsed_run_probs(X, N, P, initialK, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
-                                   device, z_out, theta_out, alpha_out, nullptr);
+// ---- one chain, one call: the four samplers ------------------------------------------------
+int bmm_collapsed_run(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int K, double alpha,
+                      double beta, double gamma, double a, double b, int burnin, int64_t batch, uint64_t seed,
+                      int device, int32_t* z_out, double* theta_out, double* alpha_out) {
+    const RunOptions opts = take_run_options();
+    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, device,
+                     counting_io(initialK, z_out, theta_out, alpha_out), opts);
 }
+int bmm_dp_run(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma, double a,
+               double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device, int32_t* z_out,
+               double* theta_out, double* alpha_out) {
+    const RunOptions opts = take_run_options();
+    return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
+                     counting_io(nullptr, z_out, theta_out, alpha_out), opts);
+}
+int bmm_sb_run(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta, int nsamples,
+               int maxK, double alpha, double beta, double gamma, double a, double b, int burnin, uint64_t seed,
+               int device, double* pi_out, int32_t* z_out, double* theta_out, double* alpha_out) {
+    const RunOptions opts = take_run_options();
+    return run_chain(BMM_SAMPLER_SB, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, 0, seed, device,
+                     explicit_io(initialPi, initialTheta, pi_out, z_out, theta_out, alpha_out), opts);
+}
+int bmm_full_run(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta, int nsamples,
+                 int K, double alpha, double beta, double gamma, double a, double b, int burnin, uint64_t seed,
+                 int device, double* pi_out, int32_t* z_out, double* theta_out, double* alpha_out) {
+    const RunOptions opts = take_run_options();
+    return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device,
+                     explicit_io(initialPi, initialTheta, pi_out, z_out, theta_out, alpha_out), opts);
+}
+
+// ---- ... with the hooks that hand every sweep's allocation probabilities to the host ----------
 int bmm_collapsed_run_probs(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int K,
-                            double alpha, double beta, double gamma, double a, double b, int burnin,
-                            int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
-                            double* alpha_out, const bmm_relabel_hooks* hooks) {
-    PtDisarm disarm;
-    RunIO io; io.z0 = initialK; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
-                     device, io, hooks);
+                            double alpha, double beta, double gamma, double a, double b, int burnin, int64_t batch,
+                            uint64_t seed, int device, int32_t* z_out, double* theta_out, double* alpha_out,
+                            const bmm_relabel_hooks* hooks) {
+    const RunOptions opts = take_run_options();
+    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, device,
+                     counting_io(initialK, z_out, theta_out, alpha_out), with_hooks(opts, hooks));
+}
+int bmm_dp_run_probs(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
+                     double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device, int32_t* z_out,
+                     double* theta_out, double* alpha_out, const bmm_relabel_hooks* hooks) {
+    const RunOptions opts = take_run_options();
+    return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
+                     counting_io(nullptr, z_out, theta_out, alpha_out), with_hooks(opts, hooks));
+}
+int bmm_sb_run_probs(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                     int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b, int burnin,
+                     uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out, double* alpha_out,
+                     const bmm_relabel_hooks* hooks) {
+    const RunOptions opts = take_run_options();
+    return run_chain(BMM_SAMPLER_SB, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, 0, seed, device,
+                     explicit_io(initialPi, initialTheta, pi_out, z_out, theta_out, alpha_out), with_hooks(opts, hooks));
+}
+int bmm_full_run_probs(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                       int nsamples, int K, double alpha, double beta, double gamma, double a, double b, int burnin,
+                       uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out, double* alpha_out,
+                       const bmm_relabel_hooks* hooks) {
+    const RunOptions opts = take_run_options();
+    return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device,
+                     explicit_io(initialPi, initialTheta, pi_out, z_out, theta_out, alpha_out), with_hooks(opts, hooks));
+}
+
+// ---- ... with the posterior predictive of new rows ---------------------
+int bmm_collapsed_run_predict(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int K,
+                              double alpha, double beta, double gamma, double a, double b, int burnin, int64_t batch,
+                              uint64_t seed, int device, int32_t* z_out, double* theta_out, double* alpha_out,
+                              const int32_t* Xnew, int64_t M, const bmm_predict_out* pred) {
+    const RunOptions opts = take_run_options();
+    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
+    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, device,
+                     counting_io(initialK, z_out, theta_out, alpha_out), with_predict(opts, Xnew, M, pred));
+}
+int bmm_dp_run_predict(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
+                       double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
+                       int32_t* z_out, double* theta_out, double* alpha_out, const int32_t* Xnew, int64_t M,
+                       const bmm_predict_out* pred) {
+    const RunOptions opts = take_run_options();
+    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
+    return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
+                     counting_io(nullptr, z_out, theta_out, alpha_out), with_predict(opts, Xnew, M, pred));
+}
+int bmm_sb_run_predict(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                       int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b, int burnin,
+                       uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out, double* alpha_out,
+                       const int32_t* Xnew, int64_t M, const bmm_predict_out* pred) {
+    const RunOptions opts = take_run_options();
+    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
+    return run_chain(BMM_SAMPLER_SB, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, 0, seed, device,
+                     explicit_io(initialPi, initialTheta, pi_out, z_out, theta_out, alpha_out),
+                     with_predict(opts, Xnew, M, pred));
+}
+int bmm_full_run_predict(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                         int nsamples, int K, double alpha, double beta, double gamma, double a, double b, int burnin,
+                         uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
+                         double* alpha_out, const int32_t* Xnew, int64_t M, const bmm_predict_out* pred) {
+    const RunOptions opts = take_run_options();
+    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
+    return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device,
+                     explicit_io(initialPi, initialTheta, pi_out, z_out, theta_out, alpha_out),
+                     with_predict(opts, Xnew, M, pred));
+}
+
+// ---- ... with relabel = TRUE, Stephens' relabelling on the device ---------------------------
+int bmm_collapsed_run_relabel(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int K,
+                              double alpha, double beta, double gamma, double a, double b, int burnin, int64_t batch,
+                              uint64_t seed, int device, int32_t* z_out, double* theta_out, double* alpha_out,
+                              const bmm_relabel_out* rel) {
+    const RunOptions opts = take_run_options();
+    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
+    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, device,
+                     counting_io(initialK, z_out, theta_out, alpha_out), with_relabel(opts, rel));
+}
+int bmm_dp_run_relabel(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
+                       double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
+                       int32_t* z_out, double* theta_out, double* alpha_out, const bmm_relabel_out* rel) {
+    const RunOptions opts = take_run_options();
+    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
+    return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
+                     counting_io(nullptr, z_out, theta_out, alpha_out), with_relabel(opts, rel));
+}
+int bmm_sb_run_relabel(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                       int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b, int burnin,
+                       uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out, double* alpha_out,
+                       const bmm_relabel_out* rel) {
+    const RunOptions opts = take_run_options();
+    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
+    return run_chain(BMM_SAMPLER_SB, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, 0, seed, device,
+                     explicit_io(initialPi, initialTheta, pi_out, z_out, theta_out, alpha_out), with_relabel(opts, rel));
+}
+int bmm_full_run_relabel(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
+                         int nsamples, int K, double alpha, double beta, double gamma, double a, double b, int burnin,
+                         uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
+                         double* alpha_out, const bmm_relabel_out* rel) {
+    const RunOptions opts = take_run_options();
+    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
+    return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device,
+                     explicit_io(initialPi, initialTheta, pi_out, z_out, theta_out, alpha_out), with_relabel(opts, rel));
 }
 
 // The allocation sampler: the finite collapsed run with K in the state.
@@ -4290,8 +4426,7 @@ int bmm_alloc_run(const int32_t* X, int64_t N, int P, const int32_t* initialK, i
                   double beta, double gamma, const double* log_prior_k, int K0, int moves_per_sweep, double eject_a,
                   int burnin, int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
                   int32_t* k_out, int64_t moves_out[4]) {
-    PtDisarm disarm;
-    struct Off { ~Off() { g_alloc = AllocArmed{}; } } off;
+    RunOptions opts = take_run_options();
     if (!log_prior_k || !k_out) return set_err(BMM_E_ARG, "null buffer");
     if (!(a > 0.0)) return set_err(BMM_E_ARG, "a must be > 0");
     if (maxK > kMaxCats) return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is offered up to maxK = %d", kMaxCats);
@@ -4300,149 +4435,10 @@ int bmm_alloc_run(const int32_t* X, int64_t N, int P, const int32_t* initialK, i
     if (K0 < 1 || K0 > maxK) return set_err(BMM_E_ARG, "the initial K must lie in 1..maxK");
     if (nsamples < 1 || burnin < 0 || burnin >= nsamples) return set_err(BMM_E_ARG, "burnin must be in [0, nsamples)");
     std::vector<double> alpha_out((size_t)(nsamples - burnin));
-    g_alloc.on = true; g_alloc.log_prior_k = log_prior_k; g_alloc.K0 = K0; g_alloc.moves = moves_per_sweep;
-    g_alloc.eject_a = eject_a; g_alloc.k_out = k_out; g_alloc.moves_out = moves_out;
-    RunIO io; io.z0 = initialK; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out.data();
-    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, maxK, a, beta, gamma, 1.0, 1.0, burnin, batch, seed, device, io, nullptr);
-}
-
-int bmm_dp_run(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
-               double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
-               int32_t* z_out, double* theta_out, double* alpha_out) {
-    return bmm_dp_run_probs(X, N, P, nsamples, alpha, beta, gamma, a, b, burnin, maxK, batch, seed, device, z_out,
-                            theta_out, alpha_out, nullptr);
-}
-int bmm_dp_run_probs(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
-                     double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
-                     int32_t* z_out, double* theta_out, double* alpha_out, const bmm_relabel_hooks* hooks) {
-    PtDisarm disarm;
-    RunIO io; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
-                     io, hooks);
-}
-
-int bmm_sb_run(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
-               int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b,
-               int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
-               double* alpha_out) {
-    return bmm_sb_run_probs(X, N, P, initialPi, initialTheta, nsamples, maxK, alpha, beta, gamma, a, b, burnin,
-                            seed, device, pi_out, z_out, theta_out, alpha_out, nullptr);
-}
-int bmm_sb_run_probs(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
-                     int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b,
-                     int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
-                     double* alpha_out, const bmm_relabel_hooks* hooks) {
-    PtDisarm disarm;
-    RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
-    io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_SB, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
-                     hooks);
-}
-
-int bmm_full_run(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
-                 int nsamples, int K, double alpha, double beta, double gamma, double a, double b, int burnin,
-                 uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
-                 double* alpha_out) {
-    return bmm_full_run_probs(X, N, P, initialPi, initialTheta, nsamples, K, alpha, beta, gamma, a, b, burnin, seed,
-                              device, pi_out, z_out, theta_out, alpha_out, nullptr);
-}
-int bmm_full_run_probs(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
-                       int nsamples, int K, double alpha, double beta, double gamma, double a, double b,
-                       int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out,
-                       double* theta_out, double* alpha_out, const bmm_relabel_hooks* hooks) {
-    PtDisarm disarm;
-    RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
-    io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
-                     hooks);
-}
-
-// ---- the runs above with the posterior predictive of new rows ---------
-int bmm_collapsed_run_predict(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int K,
-                              double alpha, double beta, double gamma, double a, double b, int burnin,
-                              int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
-                              double* alpha_out, const int32_t* Xnew, int64_t M, const bmm_predict_out* pred) {
-    PtDisarm disarm;
-    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
-    RunIO io; io.z0 = initialK; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
-                     device, io, pred->hooks, pred->relabel, Xnew, M, pred);
-}
-int bmm_dp_run_predict(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
-                       double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
-                       int32_t* z_out, double* theta_out, double* alpha_out, const int32_t* Xnew, int64_t M,
-                       const bmm_predict_out* pred) {
-    PtDisarm disarm;
-    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
-    RunIO io; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
-                     io, pred->hooks, pred->relabel, Xnew, M, pred);
-}
-int bmm_sb_run_predict(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
-                       int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b,
-                       int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
-                       double* alpha_out, const int32_t* Xnew, int64_t M, const bmm_predict_out* pred) {
-    PtDisarm disarm;
-    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
-    RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
-    io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_SB, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
-                     pred->hooks, pred->relabel, Xnew, M, pred);
-}
-int bmm_full_run_predict(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
-                         int nsamples, int K, double alpha, double beta, double gamma, double a, double b,
-                         int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out,
-                         double* theta_out, double* alpha_out, const int32_t* Xnew, int64_t M,
-                         const bmm_predict_out* pred) {
-    PtDisarm disarm;
-    if (!pred) return set_err(BMM_E_ARG, "null predictive outputs");
-    RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
-    io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
-                     pred->hooks, pred->relabel, Xnew, M, pred);
-}
-
-// ---- relabel = TRUE with Stephens' relabelling on the device ---------------------------------
-int bmm_collapsed_run_relabel(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples, int K,
-                              double alpha, double beta, double gamma, double a, double b, int burnin,
-                              int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
-                              double* alpha_out, const bmm_relabel_out* rel) {
-    PtDisarm disarm;
-    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
-    RunIO io; io.z0 = initialK; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed,
-                     device, io, nullptr, rel);
-}
-int bmm_dp_run_relabel(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta, double gamma,
-                       double a, double b, int burnin, int maxK, int64_t batch, uint64_t seed, int device,
-                       int32_t* z_out, double* theta_out, double* alpha_out, const bmm_relabel_out* rel) {
-    PtDisarm disarm;
-    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
-    RunIO io; io.z_out = z_out; io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_DP, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, device,
-                     io, nullptr, rel);
-}
-int bmm_sb_run_relabel(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
-                       int nsamples, int maxK, double alpha, double beta, double gamma, double a, double b,
-                       int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out, double* theta_out,
-                       double* alpha_out, const bmm_relabel_out* rel) {
-    PtDisarm disarm;
-    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
-    RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
-    io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_SB, X, N, P, nsamples, maxK, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
-                     nullptr, rel);
-}
-int bmm_full_run_relabel(const int32_t* X, int64_t N, int P, const double* initialPi, const double* initialTheta,
-                         int nsamples, int K, double alpha, double beta, double gamma, double a, double b,
-                         int burnin, uint64_t seed, int device, double* pi_out, int32_t* z_out,
-                         double* theta_out, double* alpha_out, const bmm_relabel_out* rel) {
-    PtDisarm disarm;
-    if (!rel) return set_err(BMM_E_ARG, "null relabel outputs");
-    RunIO io; io.pi0 = initialPi; io.theta0 = initialTheta; io.pi_out = pi_out; io.z_out = z_out;
-    io.theta_out = theta_out; io.alpha_out = alpha_out;
-    return run_chain(BMM_SAMPLER_FULL, X, N, P, nsamples, K, alpha, beta, gamma, a, b, burnin, 0, seed, device, io,
-                     nullptr, rel);
+    opts.alloc.on = true; opts.alloc.log_prior_k = log_prior_k; opts.alloc.K0 = K0; opts.alloc.moves = moves_per_sweep;
+    opts.alloc.eject_a = eject_a; opts.alloc.k_out = k_out; opts.alloc.moves_out = moves_out;
+    return run_chain(BMM_SAMPLER_COLLAPSED, X, N, P, nsamples, maxK, a, beta, gamma, 1.0, 1.0, burnin, batch, seed, device,
+                     counting_io(initialK, z_out, theta_out, alpha_out.data()), opts);
 }
 
 int bmm_device_stephens_batch(int device, const double* p, int64_t N, int K, int M, double* Q_out, int32_t* perm_out) {
@@ -4527,15 +4523,15 @@ int bmm_device_stephens_plan(int64_t N, int K, int M, int64_t out[12]) {
 // ---- clustering point estimate and posterior similarity: the stand-alone entry points ----
 int bmm_set_split_merge(int moves_per_sweep, int scans) {
     if (moves_per_sweep < 0 || scans < 0 || scans > 4096) return set_err(BMM_E_ARG, "moves_per_sweep and scans must be >= 0 (scans at most 4096)");
-    g_sm.moves = moves_per_sweep;
-    g_sm.scans = scans;
+    g_armed.sm.moves = moves_per_sweep;
+    g_armed.sm.scans = scans;
     return BMM_OK;
 }
 int bmm_set_init(int kind, int iters) {
     if (kind != 0 && kind != BMM_INIT_KMODES) return set_err(BMM_E_ARG, "unknown kind of initialisation %d", kind);
     if (iters < 0) return set_err(BMM_E_ARG, "iters must be >= 0");
-    g_init.kind = kind;
-    g_init.iters = iters;
+    g_armed.init.kind = kind;
+    g_armed.init.iters = iters;
     return BMM_OK;
 }
 int bmm_last_init_info(bmm_init_info* info) {
@@ -4550,20 +4546,20 @@ int bmm_last_split_merge_stats(int64_t out[5]) {
 }
 
 int bmm_set_feature_select(const bmm_feature_out* out) {
-    g_fs.on = out != nullptr;
-    if (out) g_fs.o = *out;
+    g_armed.fs.on = out != nullptr;
+    if (out) g_armed.fs.o = *out;
     return BMM_OK;
 }
 
 int bmm_set_loo_summary(const bmm_loo_out* out) {
-    g_loo.on = out != nullptr;
-    if (out) g_loo.o = *out;
+    g_armed.loo.on = out != nullptr;
+    if (out) g_armed.loo.o = *out;
     return BMM_OK;
 }
 
 int bmm_set_partition_summary(const bmm_partition_out* out) {
-    g_partition.on = out != nullptr;
-    if (out) g_partition.o = *out;
+    g_armed.partition.on = out != nullptr;
+    if (out) g_armed.partition.o = *out;
     return BMM_OK;
 }
 
@@ -4652,7 +4648,8 @@ int bmm_multi_run(int sampler, int n_chains, const int* devices, const int32_t* 
                   double gamma, double a, double b, int burnin, int64_t batch, uint64_t seed,
                   double* const* pi_out, int32_t* const* z_out, double* const* theta_out,
                   double* const* alpha_out) {
-    PtDisarm disarm;
+    (void)take_run_options();  // a run of several chains disarms whatever was armed ...
+    const RunOptions opts;     // ... and runs every chain without it
     return guarded([&]() -> int {
         if (sampler < 0 || sampler > 3) return set_err(BMM_E_ARG, "unknown sampler %d", sampler);
         if (n_chains < 1) return set_err(BMM_E_ARG, "n_chains must be >= 1");
@@ -4662,9 +4659,8 @@ int bmm_multi_run(int sampler, int n_chains, const int* devices, const int32_t* 
         std::vector<RunIO> io((size_t)n_chains);
         for (int c = 0; c < n_chains; ++c) {
             RunIO& q = io[(size_t)c];
-            if (sampler == BMM_SAMPLER_COLLAPSED) q.z0 = initialK[c];
-            if (explicit_params(sampler)) { q.pi0 = initialPi[c]; q.theta0 = initialTheta[c]; q.pi_out = pi_out[c]; }
-            q.z_out = z_out[c]; q.theta_out = theta_out[c]; q.alpha_out = alpha_out[c];
+            q = explicit_params(sampler) ? explicit_io(initialPi[c], initialTheta[c], pi_out[c], z_out[c], theta_out[c], alpha_out[c])
+                                         : counting_io(sampler == BMM_SAMPLER_COLLAPSED ? initialK[c] : nullptr, z_out[c], theta_out[c], alpha_out[c]);
             int rc = check_run_args(X, nsamples, burnin, q, sampler);
             if (rc) return rc;
         }
@@ -4722,7 +4718,7 @@ int bmm_multi_run(int sampler, int n_chains, const int* devices, const int32_t* 
                     // no exception may leave a thread: the trace's way out starts helper threads of its own
                     status[(size_t)c] = guarded([&]() -> int {
                         int rcw = run_start_state(chains[(size_t)c], io[(size_t)c]);
-                        if (rcw == BMM_OK) rcw = run_body(chains[(size_t)c], nsamples, io[(size_t)c], nullptr);
+                        if (rcw == BMM_OK) rcw = run_body(chains[(size_t)c], nsamples, io[(size_t)c], opts);
                         return rcw;
                     });
                     try {
