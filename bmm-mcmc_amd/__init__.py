@@ -21,7 +21,8 @@ from .rdata import read_rdata_matrix  # the package's bundled data sets (data/*.
 __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "Chain", "BmmError", "NA_INTEGER", "set_progress",
            "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
            "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
-           "partition_distances", "posterior_similarity", "partition_plan", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k"]
+           "partition_distances", "posterior_similarity", "partition_plan", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
+           "ecr_relabel", "ecr_plan", "ECR_MAX_K"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -414,6 +415,155 @@ def partition_plan(S, N, Kc, candidates=None, criterion="binder"):
     return dict(zip(_PT_PLAN_FIELDS, (int(v) for v in out)))
 
 
+# ---------------------------------------------------------------- relabel="ecr": relabelling from the label trace alone
+ECR_MAX_K = 128  # include/bmm_mcmc.h BMM_ECR_MAX_K
+_ECR_GIVEN, _ECR_PARTITION, _ECR_ITERATIVE = 0, 1, 2
+
+
+class _EcrOut(_C.Structure):  # bmm_ecr_out
+    _fields_ = [("pivot_kind", _C.c_int), ("pivot", _C.c_void_p), ("max_iter", _C.c_int), ("permutations", _C.c_void_p),
+                ("z_original", _C.c_void_p), ("theta_original", _C.c_void_p), ("agree", _C.c_void_p),
+                ("pivot_out", _C.c_void_p), ("iterations", _C.c_void_p), ("converged", _C.c_void_p),
+                ("n_used", _C.c_void_p)]
+
+
+def _permute_theta(theta, perms):
+    """theta_relab[perm[s, k], :, s] = theta[k, :, s]"""
+    out = _np.empty_like(theta)
+    for s in range(perms.shape[0]):
+        out[perms[s], :, s] = theta[:, :, s]
+    return out
+
+
+def _ecr_pivot(ecr_pivot, N, partition):
+    """ecr_pivot= of a wrapper, checked before any device is touched: (kind, labels or None)."""
+    if isinstance(ecr_pivot, str):
+        if ecr_pivot == "iterative":
+            return _ECR_ITERATIVE, None
+        if ecr_pivot == "partition":
+            if partition is None:
+                raise ValueError('ecr_pivot="partition" needs partition="binder" or "vi"')
+            return _ECR_PARTITION, None
+        raise ValueError('ecr_pivot must be "iterative", "partition" or N labels')
+    pv = _np.ascontiguousarray(ecr_pivot, dtype=_np.int32).ravel()
+    if pv.shape != (N,):
+        raise ValueError("ecr_pivot must have one label per observation")
+    return _ECR_GIVEN, pv
+
+
+def _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition):
+    """relabel= of a wrapper: (relabel as the rest of the wrapper reads it, None or the checked ECR request)."""
+    if not (isinstance(relabel, str) and relabel == "ecr"):
+        return relabel, None
+    if stephens is not None:
+        raise ValueError('relabel="ecr" relabels from the label trace alone: not together with stephens= (two relabellings)')
+    kind, pv = _ecr_pivot(ecr_pivot, N, partition)
+    return False, (kind, pv, int(ecr_max_iter))
+
+
+class _Ecr:
+    """Outputs of an armed bmm_set_ecr_relabel: the run fills them after its last sweep (include/bmm_mcmc.h "ECR",
+    DESIGN.md section 19).  With several chains nothing is armed: the traces are stacked afterwards (_ecr_chains)."""
+
+    def __init__(self, req, N, K, P, S):
+        kind, self.given, max_iter = req
+        self.perms = _np.empty((S, K), dtype=_np.int32, order="F")
+        self.z_orig = _np.empty((S, N), dtype=_np.int32, order="F")
+        self.th_orig = _np.zeros((K, P, S), order="F")
+        self.agree = _np.zeros(S, dtype=_np.int64)
+        self.pivot = _np.zeros(N, dtype=_np.int32)
+        self.iterations, self.converged, self.n_used = _C.c_int(0), _C.c_int(0), _C.c_int(0)
+        self.s = _EcrOut(kind, None if self.given is None else self.given.ctypes.data, max_iter, self.perms.ctypes.data,
+                         self.z_orig.ctypes.data, self.th_orig.ctypes.data, self.agree.ctypes.data,
+                         self.pivot.ctypes.data, _C.addressof(self.iterations), _C.addressof(self.converged),
+                         _C.addressof(self.n_used))
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_ecr_relabel(_C.byref(self.s)))
+
+    def finish(self, out):
+        out.update(permutations=self.perms, z_original=self.z_orig, theta_original=self.th_orig,
+                   ecr={"agree": self.agree, "pivot": self.pivot, "iterations": self.iterations.value,
+                        "converged": bool(self.converged.value), "n_used": self.n_used.value})
+        return out
+
+
+def ecr_relabel(z, K, pivot=None, max_iter=50, theta=None, device=0, tables=False):
+    """ECR relabelling of a label trace on the device (include/bmm_mcmc.h "ECR").  z: S x N
+    labels in 1..K, as a run returns them -- or the traces of several chains stacked.  pivot: N labels in 1..K, every
+    row is then permuted to agree with it on as many observations as possible; None: the iterative form, the pivot
+    is the majority vote of the rows as relabelled so far, until the total agreement stops growing (at most max_iter
+    iterations).  Returns {"permutations" (S, K) int32, 0-based: label l of row t becomes permutations[t, l]; "z" the
+    relabelled trace; "agree" (S,) int64: observations on which a relabelled row agrees with the pivot; "pivot" (N,);
+    "iterations"; "converged"} and, given theta (K, P, S), "theta" permuted alike; with tables=True "tables" (S, K, K)
+    uint32: tables[t, a, b] = #{i : z[t, i] = a + 1, pivot[i] = b + 1} of the last iteration."""
+    z = _as_trace(z)
+    S, N = z.shape
+    K = int(K)
+    pv = None if pivot is None else _ecr_pivot(pivot, N, None)[1]
+    perms = _np.zeros((S, max(K, 1)), dtype=_np.int32, order="F")
+    agree = _np.zeros(S, dtype=_np.int64)
+    pivot_out = _np.zeros(N, dtype=_np.int32)
+    zr = _np.empty((S, N), dtype=_np.int32, order="F")
+    tabs = _np.zeros((S, max(K, 1), max(K, 1)), dtype=_np.uint32) if tables else None
+    it, conv = _C.c_int(0), _C.c_int(0)
+    _capi.check(_capi.lib().bmm_device_ecr(
+        _C.c_int(device), _capi.vp(z), _C.c_int(S), _C.c_int64(N), _C.c_int(K), None if pv is None else _capi.vp(pv),
+        _C.c_int(int(max_iter)), _capi.vp(perms), _capi.vp(agree), _capi.vp(pivot_out), _capi.vp(zr),
+        _capi.vp(tabs) if tables else None, _C.byref(it), _C.byref(conv)))
+    out = {"permutations": perms, "z": zr, "agree": agree, "pivot": pivot_out, "iterations": it.value,
+           "converged": bool(conv.value)}
+    if theta is not None:
+        theta = _np.asarray(theta)
+        if theta.ndim != 3 or theta.shape[0] != K or theta.shape[2] != S:
+            raise ValueError("theta must be K x P x S")
+        out["theta"] = _permute_theta(theta, perms)
+    if tables:
+        out["tables"] = tabs
+    return out
+
+
+_ECR_PLAN_FIELDS = ("label_bytes", "tables_lds", "rows_per_workgroup", "copies", "row_blocks", "slices", "span",
+                    "tables_lds_bytes", "votes_lds", "votes_workgroups", "votes_bytes", "pitch")
+
+
+def ecr_plan(S, N, K):
+    """Which form of the ECR kernels a shape runs (S rows, N observations, K categories), read from the library's launch
+    arithmetic without touching a device (bmm_device_ecr_plan): a dict of the fields include/bmm_mcmc.h lists."""
+    out = (_C.c_int64 * 12)()
+    _capi.check(_capi.lib().bmm_device_ecr_plan(_C.c_int(int(S)), _C.c_int64(int(N)), _C.c_int(int(K)), out))
+    return dict(zip(_ECR_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def _ecr_chains(chains_out, req, K, device):
+    """chains > 1: the chains' traces stacked (rows that are no partition left out, as _pooled leaves them out), one
+    stand-alone call against one pivot -- for "partition" the pooled estimate -- and every chain object receives its
+    rows of the result, theta permuted on the host."""
+    if req is None:
+        return chains_out
+    kind, pv, max_iter = req
+    if kind == _ECR_PARTITION:
+        pv = _np.ascontiguousarray(chains_out[0]["partition"]["z"], dtype=_np.int32)
+    src = [[s for s in range(o["z"].shape[0]) if o["z"][s].min() >= 1] for o in chains_out]
+    res = ecr_relabel(_np.concatenate([o["z"][keep] for o, keep in zip(chains_out, src)], axis=0), K, pv, max_iter,
+                      device=device)
+    at = 0
+    for o, keep in zip(chains_out, src):
+        S = o["z"].shape[0]
+        perms = _np.asfortranarray(_np.tile(_np.arange(K, dtype=_np.int32), (S, 1)))
+        agree = _np.zeros(S, dtype=_np.int64)
+        zr = o["z"].copy(order="F")
+        perms[keep] = res["permutations"][at:at + len(keep)]
+        agree[keep] = res["agree"][at:at + len(keep)]
+        zr[keep] = res["z"][at:at + len(keep)]
+        at += len(keep)
+        o.update(permutations=perms, z_original=o["z"], theta_original=o["theta"], z=zr,
+                 theta=_permute_theta(o["theta"], perms),
+                 ecr={"agree": agree, "pivot": res["pivot"], "iterations": res["iterations"],
+                      "converged": res["converged"], "n_used": sum(len(k) for k in src)})  # rows of all chains
+    return chains_out
+
+
 # ---------------------------------------------------------------- split_merge=: Jain & Neal's move for the DP chain
 SPLIT_MERGE_SCANS = 5  # the default of split_merge_scans (DESIGN.md section 15 says where it comes from)
 _SM_FIELDS = ("split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped")
@@ -487,7 +637,7 @@ def log_prior_k(prior_k, maxK):
 
 def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, moves=1, eject_a=1.0, beta=0.5, gamma=0.5,
                      burnin=None, *, seed=None, batch=None, device=0, initial_K=None, partition=None, partition_stride=1,
-                     similarity_of=None):
+                     similarity_of=None, relabel=False, ecr_pivot="iterative", ecr_max_iter=50):
     """The allocation sampler of Nobile & Fearnside (2007): the finite collapsed Beta-Bernoulli mixture with the number of
     components K unknown, 1 <= K <= maxK <= 64 (include/bmm_mcmc.h "allocation sampler").  The
     weights are Dirichlet(a, ..., a) with `a` fixed per component; `prior_k`: see log_prior_k.  A sweep is the finite
@@ -495,7 +645,8 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
     Beta(eject_a, eject_a)) at the start of every sweep from the second change K.  The chain starts from `K0` components
     (default min(maxK, 2)) and `initial_K` (1-based labels in 1..K0; default uniform).  Returns z (S, N), theta (maxK, P,
     S) with NaN where a label is empty, K (S,), k_posterior (maxK,): the kept-sweep frequencies of K = 1..maxK, k_used
-    (S,): the non-empty labels per sweep, moves: the four counts, and with `partition=` the summary of gibbs_collapsed."""
+    (S,): the non-empty labels per sweep, moves: the four counts, and with `partition=` the summary of gibbs_collapsed.
+    `relabel="ecr"` is refused by the library (BMM_E_UNSUPPORTED): the relabelling assumes a fixed number of components."""
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, maxK = int(nsamples), int(maxK)
@@ -516,6 +667,12 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
     theta = _np.zeros((maxK, P, S), order="F")
     Ks = _np.zeros(S, dtype=_np.int32)
     counts = (_C.c_int64 * 4)()
+    if relabel:
+        ecr_req = _ecr_request(relabel, None, ecr_pivot, ecr_max_iter, N, partition)[1]
+        if ecr_req is None:
+            raise ValueError('gibbs_allocation offers no relabelling (relabel must be False)')
+        ec = _Ecr(ecr_req, N, maxK, P, S)  # alive through the call
+        ec.arm()  # the library refuses the run
     if pt is not None:
         pt.arm()
     _capi.check(_capi.lib().bmm_alloc_run(
@@ -622,7 +779,7 @@ class _Init:
         return info.as_dict()
 
 
-def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None):
+def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
@@ -634,6 +791,8 @@ def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=
         part.arm()
     if loo is not None:
         loo.arm()
+    if ecr is not None:
+        ecr.arm()
     if init is not None:  # last, just ahead of the call: a run of another sampler refuses an armed start
         init.arm()
     if pr is None:
@@ -791,7 +950,8 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                     relabel=False, burnrelabel=50, debug=False, *, seed=None, batch=None, device=0,
                     initial_K=None, chains=1, devices=None, stephens=None, newdata=None, predictive_trace=False,
                     responsibilities=False, partition=None, partition_stride=1, similarity_of=None, loo=False,
-                    select_features=False, rho=0.5, init="random", init_iters=INIT_ITERS):
+                    select_features=False, rho=0.5, init="random", init_iters=INIT_ITERS, ecr_pivot="iterative",
+                    ecr_max_iter=50):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -834,6 +994,14 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     "device_ms"}`.  Not together with `initial_K`.  With `chains > 1` chain c is initialised with seed + c by a resident
     chain on device 0 and its labels are handed to the multi-chain call as `initial_K`: that one round trip of N labels
     per chain over PCIe is accepted there.  `init="random"`, the default, is the code path it always was.
+    `relabel="ecr"`: the kept sweeps are relabelled from the label trace alone, on the device, after the last sweep
+    (ECR, include/bmm_mcmc.h): every row gets the permutation that agrees with a pivot allocation
+    on as many observations as possible.  `ecr_pivot="iterative"` (the default) votes the pivot from the rows themselves
+    until the agreement stops growing (at most `ecr_max_iter` iterations), `"partition"` takes the point estimate of
+    `partition=`, an array of N labels is used as given.  No probability matrix, any burnin, and the result has the keys of
+    a stephens="device" run (`permutations`, `z`, `theta` relabelled, `z_original`, `theta_original`) plus `ecr = {"agree",
+    "pivot", "iterations", "converged", "n_used"}`.  With `chains > 1` the chains' traces are stacked and relabelled to one
+    common pivot (for "partition" the pooled estimate), so their `theta` can be averaged across chains.
     """
     X = _capi.as_x(data)
     N, P = X.shape
@@ -845,6 +1013,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
     chains = int(chains)
+    relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, False, newdata, loo)
@@ -869,8 +1038,9 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                     initial_K.append(ch.labels())
         z0s = [_np.ascontiguousarray(_np.random.default_rng(seed + c).integers(1, K + 1, N), dtype=_np.int32)
                for c in range(chains)] if initial_K is None else [_np.ascontiguousarray(z, dtype=_np.int32) for z in initial_K]
-        outs = _pooled(_multi("collapsed", X, chains, devices, z0s, None, None, nsamples, K, alpha, beta, gamma, a, b,
-                      burnin, batch, seed, False), partition, partition_stride, similarity_of, device if devices is None else int(devices[0]))
+        dev0 = device if devices is None else int(devices[0])
+        outs = _ecr_chains(_pooled(_multi("collapsed", X, chains, devices, z0s, None, None, nsamples, K, alpha, beta, gamma, a, b,
+                           burnin, batch, seed, False), partition, partition_stride, similarity_of, dev0), ecr_req, K, dev0)
         if ini is not None:
             for o, info in zip(outs, infos):
                 o["init"] = info
@@ -895,6 +1065,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
+    ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((K, P, S), order="F")
     al = _np.zeros((S, 1), order="F")
@@ -903,19 +1074,19 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
             _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
     _capi.check(rc)
-    return done(_with_predictive(out, pr, pt, lo))
+    return done(_with_predictive(out if ec is None else ec.finish(out), pr, pt, lo))
 
 
 def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=None, relabel=False,
              burnrelabel=50, maxK=30, debug=False, *, seed=None, batch=None, device=0, chains=1, devices=None,
              stephens=None, newdata=None, predictive_trace=False, responsibilities=False, partition=None,
              partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None,
-             select_features=False, rho=0.5, init="random"):
+             select_features=False, rho=0.5, init="random", ecr_pivot="iterative", ecr_max_iter=50):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
@@ -930,6 +1101,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     nsamples, maxK = int(nsamples), int(maxK)
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
+    relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, maxK + 1, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     lo = _make_loo(loo, N, nsamples - burnin, chains, False)
@@ -945,8 +1117,9 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     if int(chains) > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
-        return _pooled(_multi("dp", X, int(chains), devices, None, None, None, nsamples, maxK, alpha, beta, gamma, a, b,
-                      burnin, batch, seed, False), partition, partition_stride, similarity_of, device if devices is None else int(devices[0]))
+        dev0 = device if devices is None else int(devices[0])
+        return _ecr_chains(_pooled(_multi("dp", X, int(chains), devices, None, None, None, nsamples, maxK, alpha, beta, gamma, a, b,
+                           burnin, batch, seed, False), partition, partition_stride, similarity_of, dev0), ecr_req, maxK, dev0)
     S = nsamples - burnin
     W = _clamp_burnrelabel(burnrelabel, burnin)
     if _device_relabel(stephens, relabel, burnin, W):
@@ -963,6 +1136,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
+    ec = None if ecr_req is None else _Ecr(ecr_req, N, maxK, P, S)
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((maxK, P, S), order="F")
     al = _np.zeros((S, 1), order="F")
@@ -972,24 +1146,25 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs)
+        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
     _capi.check(rc)
-    return done(_with_predictive(out, pr, pt, lo))
+    return done(_with_predictive(out if ec is None else ec.finish(out), pr, pt, lo))
 
 
 def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, burnin, relabel, burnrelabel, seed,
               device, initial_pi, initial_theta, chains, devices, stephens, debug=False, newdata=None,
               predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None,
-              loo=False):
+              loo=False, ecr_pivot="iterative", ecr_max_iter=50):
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, K = int(nsamples), int(K)
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
     chains = int(chains)
+    relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     lo = _make_loo(loo, N, nsamples - burnin, chains, True)
@@ -1015,8 +1190,10 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
         st = [start(seed + c, initial_pi[c] if initial_pi is not None else None,
                     initial_theta[c] if initial_theta is not None else None) for c in range(chains)]
-        return _pooled(_multi(sampler, X, chains, devices, None, [p for p, _ in st], [t for _, t in st], nsamples, K,
-                      alpha, beta, gamma, a, b, burnin, None, seed, True), partition, partition_stride, similarity_of, device if devices is None else int(devices[0]))
+        dev0 = device if devices is None else int(devices[0])
+        return _ecr_chains(_pooled(_multi(sampler, X, chains, devices, None, [p for p, _ in st], [t for _, t in st], nsamples, K,
+                           alpha, beta, gamma, a, b, burnin, None, seed, True), partition, partition_stride, similarity_of, dev0),
+                           ecr_req, K, dev0)
     on_device = _device_relabel(stephens, relabel, burnin, W)
     pi0, th0 = start(seed, initial_pi, initial_theta)
     if on_device:
@@ -1033,6 +1210,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             rc = _run(base, args, pr, rel=dr, part=pt, loo=lo)
         return _with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo)
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
+    ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
     theta = _np.zeros((K, P, S), order="F")
     al = _np.zeros((S, 1), order="F")
@@ -1042,19 +1220,19 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
             _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo)
+        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec)
     out = {"pi": pi, "alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return _with_predictive(rl.finish(rc, out), pr, pt, lo)
     _capi.check(rc)
-    return _with_predictive(out, pr, pt, lo)
+    return _with_predictive(out if ec is None else ec.finish(out), pr, pt, lo)
 
 
 def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
                         relabel=False, burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None,
                         initial_theta=None, chains=1, devices=None, stephens=None, newdata=None,
                         predictive_trace=False, responsibilities=False, partition=None, partition_stride=1,
-                        similarity_of=None, loo=False, init="random"):
+                        similarity_of=None, loo=False, init="random", ecr_pivot="iterative", ecr_max_iter=50):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
     src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
@@ -1062,20 +1240,23 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
     _init_kind(init, 0, allowed=False)
     return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
                      burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
-                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo)
+                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
+                     ecr_max_iter)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
                burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None, initial_theta=None, chains=1,
                devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False,
-               partition=None, partition_stride=1, similarity_of=None, loo=False, init="random"):
+               partition=None, partition_stride=1, similarity_of=None, loo=False, init="random", ecr_pivot="iterative",
+               ecr_max_iter=50):
     """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
     "random" only (the sampler starts from pi and theta)."""
     _init_kind(init, 0, allowed=False)
     return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
                      relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
-                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo)
+                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
+                     ecr_max_iter)
 
 
 class Chain:

@@ -679,7 +679,7 @@ int run_rows_out(const bmm_chain* c, const double* dtrace, int64_t width, double
 }
 
 // What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_loo_summary,
-// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init; bmm_alloc_run fills `alloc` for its own run), and what a
+// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel; bmm_alloc_run fills `alloc` for its own run), and what a
 // *_run_predict / *_run_relabel / *_run_probs entry point was handed.
 struct RunOptions {
     struct { bool on = false; bmm_partition_out o{}; } partition;
@@ -687,6 +687,7 @@ struct RunOptions {
     struct { int moves = 0, scans = 0; } sm;
     struct { bool on = false; bmm_feature_out o{}; } fs;
     struct { int kind = 0, iters = 0; } init;
+    struct { bool on = false; bmm_ecr_out o{}; } ecr;
     struct { bool on = false; const double* log_prior_k = nullptr; int K0 = 0, moves = 0; double eject_a = 1.0; int32_t* k_out = nullptr; int64_t* moves_out = nullptr; } alloc;
     const bmm_relabel_hooks* hooks = nullptr;  // *_run_probs
     const bmm_relabel_out* rel = nullptr;      // *_run_relabel
@@ -3793,7 +3794,7 @@ int pt_check_shape(int S, int64_t N, int Kc, int criterion, int stride) {
     return BMM_OK;
 }
 // every label of the caller's S x N matrix in lo .. hi (1-based); the first offender is named
-int pt_check_labels(const int32_t* z, int S, int64_t N, int lo, int64_t hi, int32_t* max_out) {
+int pt_check_labels(const int32_t* z, int S, int64_t N, int lo, int64_t hi, int32_t* max_out, const char* what = "partition") {
     const int64_t total = (int64_t)S * N;
     std::atomic<int64_t> bad{INT64_MAX};
     std::atomic<int32_t> top{0};
@@ -3814,8 +3815,8 @@ int pt_check_labels(const int32_t* z, int S, int64_t N, int lo, int64_t hi, int3
     });
     const int64_t q = bad.load();
     if (q != INT64_MAX)
-        return set_err(BMM_E_ARG, "partition: label %d at row %lld, observation %lld (0-based) is outside %d .. %lld: not a partition",
-                       z[q], (long long)(q % S), (long long)(q / S), lo, (long long)hi);
+        return set_err(BMM_E_ARG, "%s: label %d at row %lld, observation %lld (0-based) is outside %d .. %lld: not a partition",
+                       what, z[q], (long long)(q % S), (long long)(q / S), lo, (long long)hi);
     if (max_out) *max_out = top.load();
     return BMM_OK;
 }
@@ -3995,6 +3996,194 @@ int pt_run_summary(bmm_chain* c, const bmm_partition_out& o) {
     return rc;
 }
 
+// ---- ECR relabelling from the label trace (include/bmm_mcmc.h) ----
+// Which form of the k_ecr_* kernels a shape runs: a pure function of (S, N, K) -- the launches below and
+// bmm_device_ecr_plan both read it from here.
+constexpr size_t kEcrLdsBudget = (size_t)48 << 10;  // bytes of tables, or of vote counters, per workgroup
+struct EcrPlan {
+    int tab_lds = 1, T = 1, R = 1, row_blocks = 1, slices = 1, votes_lds = 1, votes_wgs = 1;
+    int64_t span = 0, pitch = 0;
+    size_t tab_lds_bytes = 0, votes_bytes = 0;
+};
+EcrPlan ecr_plan(int S, int64_t N, int K) {
+    EcrPlan p;
+    const size_t copy = ((size_t)K * K | 1) * sizeof(uint32_t);
+    p.pitch = (N + 15) / 16 * 16;
+    p.tab_lds = copy <= kEcrLdsBudget ? 1 : 0;
+    p.T = S < kEcrMaxRows ? S : kEcrMaxRows;
+    if (p.tab_lds) {
+        if ((size_t)p.T * copy > kEcrLdsBudget) p.T = (int)(kEcrLdsBudget / copy);
+        while (p.R < kEcrMaxCopies && (size_t)p.T * (2 * p.R) * copy <= kEcrLdsBudget) p.R *= 2;
+        p.tab_lds_bytes = (size_t)p.T * p.R * copy;
+    }
+    p.row_blocks = (S + p.T - 1) / p.T;
+    // along N: slices of at least 1024 observations, as many as bring the grid to some 2048 workgroups
+    int64_t sl = (N + 1023) / 1024, cap = 2048 / p.row_blocks;
+    if (cap < 1) cap = 1;
+    if (sl > cap) sl = cap;
+    p.span = ((N + sl - 1) / sl + kEcrThreads - 1) / kEcrThreads * kEcrThreads;
+    p.slices = (int)((N + p.span - 1) / p.span);
+    const size_t words = (size_t)(K + 1) / 2;
+    p.votes_lds = words * kEcrThreads * sizeof(uint32_t) <= kEcrLdsBudget ? 1 : 0;
+    int64_t wg = (N + kEcrThreads - 1) / kEcrThreads;
+    const int64_t wg_cap = p.votes_lds ? 4096 : 1024;
+    p.votes_wgs = (int)(wg < wg_cap ? wg : wg_cap);
+    p.votes_bytes = words * kEcrThreads * sizeof(uint32_t) * (p.votes_lds ? 1 : (size_t)p.votes_wgs);
+    return p;
+}
+int ecr_check_shape(int S, int64_t N, int K) {
+    if (S < 1) return set_err(BMM_E_ARG, "ecr: S must be >= 1");
+    if (N < 1) return set_err(BMM_E_ARG, "ecr: N must be >= 1");
+    if (N >= ((int64_t)1 << 32)) return set_err(BMM_E_ARG, "ecr: N must be below 2^32 (the tables are uint32)");
+    if (S > BMM_PARTITION_MAX_ROWS) return set_err(BMM_E_ARG, "ecr: S = %d rows is more than the %d one call takes", S, BMM_PARTITION_MAX_ROWS);
+    if (K < 1 || K > BMM_ECR_MAX_K) return set_err(BMM_E_ARG, "ecr: K must be in 1 .. %d (got %d)", BMM_ECR_MAX_K, K);
+    return BMM_OK;
+}
+
+struct EcrWork {
+    int S = 0, K = 0;
+    int64_t N = 0;
+    EcrPlan plan;
+    DevBuf tables, cost, agree, total, pivot, scratch;
+    PinnedBuf htotal;
+    int alloc(int S_, int64_t N_, int K_, bool own_pivot) {
+        S = S_; N = N_; K = K_;
+        plan = ecr_plan(S, N, K);
+        const size_t kk = (size_t)K * K;
+        HIP_TRY(tables.alloc((size_t)S * kk * sizeof(uint32_t)));
+        HIP_TRY(cost.alloc((size_t)S * kk * sizeof(double)));
+        HIP_TRY(agree.alloc((size_t)S * sizeof(int64_t)));
+        HIP_TRY(total.alloc(sizeof(unsigned long long)));
+        HIP_TRY(htotal.alloc(sizeof(unsigned long long)));
+        if (own_pivot) HIP_TRY(pivot.alloc((size_t)N * sizeof(int32_t)));
+        if (!plan.votes_lds) HIP_TRY(scratch.alloc(plan.votes_bytes));
+        return BMM_OK;
+    }
+};
+// The permutations of S rows (row t at lab + t * pitch) against the pivot: given (iterative = false: one pass) or voted
+// per iteration.  perm: the rows' part of a device table with leading dimension ld, holding the identity on entry.
+// Everything is enqueued on st; the iterative form waits once per iteration for the 8 bytes of total_it.
+template <class L>
+int ecr_compute(hipStream_t st, EcrWork& w, const L* lab, int64_t pitch, int32_t* pivot, int32_t* perm, int64_t ld,
+                bool iterative, int max_iter, int* iterations, int* converged) {
+    const EcrPlan& p = w.plan;
+    const int S = w.S, K = w.K, KK = K * K;
+    uint32_t* const tabs = w.tables.as<uint32_t>();
+    long long prev = -1;
+    *iterations = 0;
+    *converged = iterative ? 0 : 1;
+    for (int it = 1; it <= (iterative ? max_iter : 1); ++it) {
+        if (iterative) {
+            if (p.votes_lds) hipLaunchKernelGGL((k_ecr_votes<L, true>), dim3((unsigned)p.votes_wgs), dim3(kEcrThreads), p.votes_bytes, st, lab, pitch, perm, ld, w.N, S, K, (uint32_t*)nullptr, pivot);
+            else hipLaunchKernelGGL((k_ecr_votes<L, false>), dim3((unsigned)p.votes_wgs), dim3(kEcrThreads), 0, st, lab, pitch, perm, ld, w.N, S, K, w.scratch.as<uint32_t>(), pivot);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemsetAsync(tabs, 0, (size_t)S * KK * sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(w.total.p, 0, sizeof(unsigned long long), st));
+        const dim3 grid((unsigned)p.slices, (unsigned)p.row_blocks);
+        if (p.tab_lds) hipLaunchKernelGGL((k_ecr_tables<L, true>), grid, dim3(kEcrThreads), p.tab_lds_bytes, st, lab, pitch, pivot, w.N, S, K, p.T, p.R, p.span, tabs);
+        else hipLaunchKernelGGL((k_ecr_tables<L, false>), grid, dim3(kEcrThreads), 0, st, lab, pitch, pivot, w.N, S, K, p.T, p.R, p.span, tabs);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_ecr_cost, dim3((unsigned)((KK + kEcrThreads - 1) / kEcrThreads), (unsigned)S), dim3(kEcrThreads), 0, st, tabs, KK, w.cost.as<double>());
+        HIP_TRY(hipGetLastError());
+        const int rc = st_assign(st, w.cost.as<double>(), K, S, perm, ld);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_ecr_agree, dim3((unsigned)S), dim3(64), 0, st, tabs, K, perm, ld, w.agree.as<int64_t>(), w.total.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        *iterations = it;
+        if (!iterative) break;
+        HIP_TRY(hipMemcpyAsync(w.htotal.p, w.total.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));  // the one round trip of an iteration
+        const long long total = (long long)*w.htotal.as<unsigned long long>();
+        if (total == prev) { *converged = 1; break; }
+        prev = total;
+    }
+    return BMM_OK;
+}
+int ecr_perm_identity(hipStream_t st, int32_t* perm, int S, int K) {
+    hipLaunchKernelGGL(k_st_perm_identity, dim3((unsigned)((S * K + 255) / 256)), dim3(256), 0, st, perm, S, K);
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+// N labels, 1-based, every one in 1 .. K
+int ecr_check_pivot(const int32_t* pivot, int64_t N, int K) {
+    for (int64_t i = 0; i < N; ++i)
+        if (pivot[i] < 1 || pivot[i] > K)
+            return set_err(BMM_E_ARG, "ecr: pivot label %d at observation %lld (0-based) is outside 1 .. %d", pivot[i], (long long)i, K);
+    return BMM_OK;
+}
+int ecr_upload_pivot(int32_t* dpivot, const int32_t* pivot, int64_t N, hipStream_t st) {
+    std::vector<int32_t> h((size_t)N);
+    for (int64_t i = 0; i < N; ++i) h[(size_t)i] = pivot[i] - 1;
+    HIP_TRY(hipMemcpyAsync(dpivot, h.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));  // before the host copy goes
+    return BMM_OK;
+}
+
+// ECR armed for a run (bmm_set_ecr_relabel): what the run checks of it before any device is touched
+int ecr_run_check(const RunOptions& opts, int S, int64_t N, int K) {
+    if (!opts.ecr.on) return BMM_OK;
+    const bmm_ecr_out& o = opts.ecr.o;
+    if (opts.alloc.on)
+        return set_err(BMM_E_UNSUPPORTED, "ecr: the allocation sampler is not offered together with relabelling: it assumes no fixed number of components");
+    if (opts.rel || opts.hooks)
+        return set_err(BMM_E_ARG, "ecr: armed together with Stephens' relabelling (a *_run_relabel call or *_run_probs hooks): two relabellings of one run");
+    if (!o.permutations || !o.z_original || !o.theta_original || !o.agree || !o.iterations || !o.converged || !o.n_used)
+        return set_err(BMM_E_ARG, "ecr: null buffer");
+    int rc = ecr_check_shape(S, N, K);
+    if (rc) return rc;
+    switch (o.pivot_kind) {
+        case BMM_ECR_PIVOT_GIVEN:
+            if (!o.pivot) return set_err(BMM_E_ARG, "ecr: the pivot is null");
+            return ecr_check_pivot(o.pivot, N, K);
+        case BMM_ECR_PIVOT_PARTITION:
+            if (!opts.partition.on) return set_err(BMM_E_ARG, "ecr: the partition pivot needs an armed partition summary (bmm_set_partition_summary)");
+            return BMM_OK;
+        case BMM_ECR_PIVOT_ITERATIVE:
+            if (o.max_iter < 1) return set_err(BMM_E_ARG, "ecr: max_iter must be >= 1 (got %d)", o.max_iter);
+            return BMM_OK;
+        default: return set_err(BMM_E_ARG, "ecr: unknown kind of pivot %d", o.pivot_kind);
+    }
+}
+// after the last sweep and the partition summary, before the trace leaves: the S x K table of permutations into perm
+int ecr_run(bmm_chain* c, const RunOptions& opts, DevBuf& perm) {
+    const bmm_ecr_out& o = opts.ecr.o;
+    const int64_t N = c->p.N;
+    const int S = c->S, K = c->p.K;
+    const int first = (c->burnin == 0 && c->p.mode != MODE_COLLAPSED) ? 1 : 0;  // row 0: the unassigned starting state
+    const int Su = S - first;
+    *o.n_used = Su;
+    *o.iterations = 0;
+    *o.converged = 1;
+    for (int s = 0; s < S; ++s) o.agree[s] = 0;
+    HIP_TRY(perm.alloc((size_t)S * K * sizeof(int32_t)));
+    int rc = ecr_perm_identity(c->stream, perm.as<int32_t>(), S, K);
+    if (rc) return rc;
+    int32_t* pivot = nullptr;  // 0-based, on the device
+    if (o.pivot_kind == BMM_ECR_PIVOT_PARTITION) {
+        const int best = *opts.partition.o.best;
+        if (best >= 0) pivot = c->dTrace + (size_t)best * N;
+    }
+    if (Su < 1 || (o.pivot_kind == BMM_ECR_PIVOT_PARTITION && !pivot)) {
+        if (o.pivot_out) for (int64_t i = 0; i < N; ++i) o.pivot_out[i] = 0;
+        return BMM_OK;
+    }
+    EcrWork w;
+    rc = w.alloc(Su, N, K, pivot == nullptr);
+    if (rc) return rc;
+    if (!pivot) pivot = w.pivot.as<int32_t>();
+    if (o.pivot_kind == BMM_ECR_PIVOT_GIVEN) rc = ecr_upload_pivot(pivot, o.pivot, N, c->stream);
+    if (rc == BMM_OK)
+        rc = ecr_compute<int32_t>(c->stream, w, c->dTrace + (size_t)first * N, N, pivot, perm.as<int32_t>() + first, S,
+                                  o.pivot_kind == BMM_ECR_PIVOT_ITERATIVE, o.max_iter, o.iterations, o.converged);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(hipMemcpyAsync(o.agree + first, w.agree.p, (size_t)Su * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (o.pivot_out) HIP_TRY(hipMemcpyAsync(o.pivot_out, pivot, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // before the work buffers go
+    if (o.pivot_out) for (int64_t i = 0; i < N; ++i) o.pivot_out[i] += 1;
+    return BMM_OK;
+}
+
 // the sweeps, then the traces out (data and starting state are in place)
 int run_body(bmm_chain* c, int nsamples, const RunIO& io, const RunOptions& opts) {
     const bmm_relabel_out* const rel = opts.rel;
@@ -4024,13 +4213,22 @@ int run_body(bmm_chain* c, int nsamples, const RunIO& io, const RunOptions& opts
         rc = pt_run_summary(c, opts.partition.o);
         if (rc) return rc;
     }
-    if (rel) {
-        HIP_TRY(hipMemcpyAsync(rel->permutations, st.perm.p, (size_t)S * K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        rc = trace_out(c, rel->z_original, &clock);
-        if (rc == BMM_OK) rc = trace_out(c, io.z_out, nullptr, st.perm.as<int32_t>());
+    DevBuf ecr_perm;
+    if (opts.ecr.on) {  // ECR: the permutations from the resident trace, then the trace leaves as a relabelling run's does
+        rc = ecr_run(c, opts, ecr_perm);
         if (rc) return rc;
-        std::memcpy(rel->theta_original, io.theta_out, (size_t)S * K * P * sizeof(double));
-        permute_theta(rel->theta_original, rel->permutations, K, P, S, io.theta_out);
+    }
+    if (rel || opts.ecr.on) {
+        const int32_t* const dperm = rel ? st.perm.as<int32_t>() : ecr_perm.as<int32_t>();
+        int32_t* const hperm = rel ? rel->permutations : opts.ecr.o.permutations;
+        int32_t* const z_original = rel ? rel->z_original : opts.ecr.o.z_original;
+        double* const theta_original = rel ? rel->theta_original : opts.ecr.o.theta_original;
+        HIP_TRY(hipMemcpyAsync(hperm, dperm, (size_t)S * K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        rc = trace_out(c, z_original, &clock);
+        if (rc == BMM_OK) rc = trace_out(c, io.z_out, nullptr, dperm);
+        if (rc) return rc;
+        std::memcpy(theta_original, io.theta_out, (size_t)S * K * P * sizeof(double));
+        permute_theta(theta_original, hperm, K, P, S, io.theta_out);
     } else {
         rc = trace_out(c, io.z_out, &clock);
         if (rc) return rc;
@@ -4151,6 +4349,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
         if (rc == BMM_OK) rc = fs_run_check(opts, sampler, beta, gamma);
         if (rc == BMM_OK) rc = alloc_run_check(opts);
         if (rc == BMM_OK) rc = st_run_check(opts, burnin, K);
+        if (rc == BMM_OK) rc = ecr_run_check(opts, nsamples - burnin, N, K);
         if (rc) return rc;
         for (double& v : g_phase_ms) v = 0.0;
         PhaseClock clock;
@@ -4557,6 +4756,12 @@ int bmm_set_loo_summary(const bmm_loo_out* out) {
     return BMM_OK;
 }
 
+int bmm_set_ecr_relabel(const bmm_ecr_out* out) {
+    g_armed.ecr.on = out != nullptr;
+    if (out) g_armed.ecr.o = *out;
+    return BMM_OK;
+}
+
 int bmm_set_partition_summary(const bmm_partition_out* out) {
     g_armed.partition.on = out != nullptr;
     if (out) g_armed.partition.o = *out;
@@ -4619,6 +4824,68 @@ int bmm_device_partition_plan(int S, int64_t N, int Kc, int n_candidates, int cr
     out[0] = p.el; out[1] = p.lds; out[2] = p.T; out[3] = p.R; out[4] = p.blocks; out[5] = p.wgs;
     out[6] = p.threads; out[7] = (int64_t)p.lds_bytes; out[8] = p.tri; out[9] = p.vi; out[10] = (int64_t)p.generic_bytes;
     out[11] = p.pitch;
+    return BMM_OK;
+}
+
+// ---- ECR relabelling of any stack of label rows: the stand-alone entry points ----
+int bmm_device_ecr(int device, const int32_t* z, int S, int64_t N, int K, const int32_t* pivot, int max_iter,
+                   int32_t* perm_out, int64_t* agree_out, int32_t* pivot_out, int32_t* z_out, uint32_t* tables_out,
+                   int* iterations, int* converged) {
+    return guarded([&]() -> int {
+        if (!z || !perm_out || !agree_out || !iterations || !converged) return set_err(BMM_E_ARG, "ecr: null argument");
+        int rc = ecr_check_shape(S, N, K);
+        if (rc) return rc;
+        if (!pivot && max_iter < 1) return set_err(BMM_E_ARG, "ecr: max_iter must be >= 1 without a pivot (got %d)", max_iter);
+        rc = pt_check_labels(z, S, N, 1, K, nullptr, "ecr");
+        if (rc == BMM_OK && pivot) rc = ecr_check_pivot(pivot, N, K);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(device));
+        PtWork lw;  // the label block: one byte per label (K <= 128), narrowed as the partition calls narrow it
+        lw.shape(S, N, K, BMM_PARTITION_BINDER, 1);
+        EcrWork w;
+        DevBuf perm;
+        rc = lw.alloc_labels();
+        if (rc == BMM_OK) rc = w.alloc(S, N, K, true);
+        if (rc) return rc;
+        HIP_TRY(perm.alloc((size_t)S * K * sizeof(int32_t)));
+        rc = pt_upload(lw, z);
+        if (rc == BMM_OK) rc = ecr_perm_identity(nullptr, perm.as<int32_t>(), S, K);
+        if (rc == BMM_OK && pivot) rc = ecr_upload_pivot(w.pivot.as<int32_t>(), pivot, N, nullptr);
+        if (rc == BMM_OK)
+            rc = ecr_compute<uint8_t>(nullptr, w, lw.lab.as<uint8_t>(), lw.plan.pitch, w.pivot.as<int32_t>(), perm.as<int32_t>(), S,
+                                      pivot == nullptr, max_iter, iterations, converged);
+        if (rc) { (void)hipDeviceSynchronize(); return rc; }
+        HIP_TRY(hipDeviceSynchronize());
+        int flag = 0;
+        HIP_TRY(hipMemcpy(&flag, lw.flag.p, sizeof flag, hipMemcpyDeviceToHost));
+        if (flag) return set_err(BMM_E_STATE, "ecr: a label outside 0 .. %d reached the device", K - 1);
+        HIP_TRY(hipMemcpy(perm_out, perm.p, (size_t)S * K * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(agree_out, w.agree.p, (size_t)S * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (tables_out) HIP_TRY(hipMemcpy(tables_out, w.tables.p, (size_t)S * K * K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (pivot_out) {
+            HIP_TRY(hipMemcpy(pivot_out, w.pivot.p, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < N; ++i) pivot_out[i] += 1;
+        }
+        if (z_out) {  // z_out = perm[z - 1] + 1: observation i's S labels are contiguous
+            HostCrew crew;
+            crew.run(N, 1024, 64, [&](int64_t lo, int64_t hi) {
+                for (int64_t i = lo; i < hi; ++i)
+                    for (int s = 0; s < S; ++s)
+                        z_out[(size_t)i * S + s] = perm_out[(size_t)s + (size_t)(z[(size_t)i * S + s] - 1) * S] + 1;
+            });
+        }
+        return BMM_OK;
+    });
+}
+
+int bmm_device_ecr_plan(int S, int64_t N, int K, int64_t out[12]) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    int rc = ecr_check_shape(S, N, K);
+    if (rc) return rc;
+    const EcrPlan p = ecr_plan(S, N, K);
+    out[0] = 1; out[1] = p.tab_lds; out[2] = p.T; out[3] = p.R; out[4] = p.row_blocks; out[5] = p.slices;
+    out[6] = p.span; out[7] = (int64_t)p.tab_lds_bytes; out[8] = p.votes_lds; out[9] = p.votes_wgs;
+    out[10] = (int64_t)p.votes_bytes; out[11] = p.pitch;
     return BMM_OK;
 }
 

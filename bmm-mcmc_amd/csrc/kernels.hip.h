@@ -3578,6 +3578,127 @@ __global__ __launch_bounds__(kEaThreads) void k_ea_commit(ChainParams p, EaArgs 
     if (tid == 0) *a.K = c->k_after;
 }
 
+// ---- ECR relabelling from the label trace alone (include/bmm_mcmc.h "ECR") -----------------
+// Label rows as the partition kernels hold them: 0-based, row t at lab + t * pitch, either the resident int32 trace
+// (pitch = N; -1 = unassigned, skipped everywhere) or the one-byte block k_pt_narrow makes of host input.  The pivot
+// is N int32 labels.  A table is K^2 uint32, cell a * K + b = #{i : z_t[i] = a, pivot[i] = b}: read as a K x K
+// column-major matrix its rows are pivot labels and its columns draw labels, which is the cost matrix k_st_assign
+// takes once negated.  Every count is an integer add, so the results do not depend on scheduling.
+constexpr int kEcrThreads = 256;
+constexpr int kEcrMaxRows = 8;     // label rows per workgroup of k_ecr_tables
+constexpr int kEcrMaxCopies = 16;  // copies of a row's table in LDS
+
+// Workgroup (x, y): rows [y * T, y * T + T) against observations [x * span, x * span + span).  LDS form: R copies of
+// each row's table, a lane adding to copy lane mod R -- section 13 found k_pt_pairs bound by the lanes of one wave
+// adding to one bin (a few big clusters own most cells), so the copies go across the lanes of a wave here, not across
+// the waves -- and a copy is K^2 | 1 words long, so that the same cell of neighbouring copies lies in neighbouring
+// banks.  The copies are summed and flushed with one global integer add per non-empty cell.  Generic form (a table
+// does not fit): the adds go to the global table directly.  Dynamic LDS: T * R * (K^2 | 1) uint32, or none.
+template <class L, bool LDS>
+__global__ __launch_bounds__(256) void k_ecr_tables(const L* __restrict__ lab, int64_t pitch,
+                                                    const int32_t* __restrict__ pivot, int64_t N, int S, int K, int T,
+                                                    int R, int64_t span, uint32_t* __restrict__ tables) {
+    extern __shared__ uint32_t ecr_lds[];
+    const int tid = threadIdx.x;
+    const int t0 = blockIdx.y * T;
+    const int nT = t0 + T < S ? T : S - t0;
+    const int64_t i0 = (int64_t)blockIdx.x * span;
+    const int64_t i1 = i0 + span < N ? i0 + span : N;
+    const int KK = K * K, CS = KK | 1, TS = R * CS;
+    if (LDS) {
+        for (int k = tid; k < nT * TS; k += kEcrThreads) ecr_lds[k] = 0;
+        __syncthreads();
+    }
+    uint32_t* const mine = ecr_lds + (tid % R) * CS;
+    const L* __restrict__ rows = lab + (size_t)t0 * pitch;
+    uint32_t* const out = tables + (size_t)t0 * KK;
+    for (int64_t i = i0 + tid; i < i1; i += kEcrThreads) {
+        const int b = pivot[i];
+        if ((uint32_t)b >= (uint32_t)K) continue;
+#pragma unroll 4
+        for (int tt = 0; tt < nT; ++tt) {
+            const int a = (int)rows[(size_t)tt * pitch + i];
+            if ((uint32_t)a >= (uint32_t)K) continue;  // unassigned
+            if (LDS) atomicAdd(mine + tt * TS + a * K + b, 1u);
+            else atomicAdd(out + (size_t)tt * KK + a * K + b, 1u);
+        }
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int e = tid; e < nT * KK; e += kEcrThreads) {
+            const int tt = e / KK, k = e - tt * KK;
+            uint32_t n = 0;
+            for (int r = 0; r < R; ++r) n += ecr_lds[tt * TS + r * CS + k];
+            if (n) atomicAdd(out + e, n);
+        }
+    }
+}
+
+// cost(t) = -(double) table(t), cell for cell: exact, and already in the layout of k_st_assign.  Grid (ceil(K^2 / 256), S).
+__global__ __launch_bounds__(256) void k_ecr_cost(const uint32_t* __restrict__ tables, int KK, double* __restrict__ cost) {
+    const int e = blockIdx.x * kEcrThreads + threadIdx.x;
+    if (e < KK) cost[(size_t)blockIdx.y * KK + e] = -(double)tables[(size_t)blockIdx.y * KK + e];
+}
+
+// agree[t] = sum_a table(t)[a, perm(t, a)] and total += agree[t] (an integer add: exact in any order).  One wave per row.
+__global__ __launch_bounds__(64) void k_ecr_agree(const uint32_t* __restrict__ tables, int K,
+                                                  const int32_t* __restrict__ perm, int64_t ld,
+                                                  int64_t* __restrict__ agree, unsigned long long* __restrict__ total) {
+    __shared__ unsigned long long part[64];
+    const int lane = threadIdx.x, t = blockIdx.x;
+    const uint32_t* __restrict__ tab = tables + (size_t)t * K * K;
+    unsigned long long s = 0;
+    for (int a = lane; a < K; a += 64) {
+        const int b = min(max(perm[t + (int64_t)a * ld], 0), K - 1);
+        s += tab[a * K + b];
+    }
+    part[lane] = s;
+    __syncthreads();
+    for (int h = 32; h > 0; h >>= 1) {
+        if (lane < h) part[lane] += part[lane + h];
+        __syncthreads();
+    }
+    if (lane == 0) {
+        agree[t] = (int64_t)part[0];
+        atomicAdd(total, part[0]);
+    }
+}
+
+// The pivot of the iterative form: observation i gets the label with the most votes among perm(t, z_t[i]) over the S
+// rows, the lowest label on a tie.  One thread per observation down the rows (a wave reads 64 neighbouring labels of
+// a row), K 16-bit counters per thread (S <= 65535), two to a word, word w of thread j at [w * stride + j]: in LDS
+// stride = 256, so the lanes of a wave are in 64 neighbouring words whatever labels they count; in the generic form
+// (the counters of 256 threads do not fit) the same layout in global memory, stride = the threads of the grid.
+// Dynamic LDS: ceil(K / 2) * 256 uint32, or none.
+template <class L, bool LDS>
+__global__ __launch_bounds__(256) void k_ecr_votes(const L* __restrict__ lab, int64_t pitch,
+                                                   const int32_t* __restrict__ perm, int64_t ld, int64_t N, int S, int K,
+                                                   uint32_t* __restrict__ scratch, int32_t* __restrict__ pivot) {
+    extern __shared__ uint32_t ecr_lds[];
+    const int tid = threadIdx.x;
+    const int W = (K + 1) / 2;
+    const int64_t nth = (int64_t)gridDim.x * kEcrThreads;
+    const int64_t j = (int64_t)blockIdx.x * kEcrThreads + tid;
+    uint32_t* const cnt = LDS ? ecr_lds + tid : scratch + j;
+    const int64_t stride = LDS ? kEcrThreads : nth;
+    for (int64_t i = j; i < N; i += nth) {
+        for (int w = 0; w < W; ++w) cnt[w * stride] = 0;
+        for (int t = 0; t < S; ++t) {
+            const int a = (int)lab[(size_t)t * pitch + i];
+            if ((uint32_t)a >= (uint32_t)K) continue;  // unassigned
+            const int v = min(max(perm[t + (int64_t)a * ld], 0), K - 1);
+            cnt[(v >> 1) * stride] += 1u << (16 * (v & 1));
+        }
+        uint32_t best = 0;
+        int bk = 0;
+        for (int k = 0; k < K; ++k) {
+            const uint32_t n = (cnt[(k >> 1) * stride] >> (16 * (k & 1))) & 0xffffu;
+            if (n > best) { best = n; bk = k; }
+        }
+        pivot[i] = bk;
+    }
+}
+
 __global__ void k_test_lgamma(const double* in, double* out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = lgamma_(in[i]);

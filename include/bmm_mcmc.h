@@ -881,6 +881,81 @@ int bmm_alloc_run(const int32_t* X, int64_t N, int P, const int32_t* initialK, i
                   int burnin, int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
                   int32_t* k_out, int64_t moves_out[4]);
 
+/* ---- label-switching correction from the label trace alone: ECR ------------------------------
+ * Equivalence Classes Representatives (Papastamoulis & Iliopoulos 2010) and its pivot-free iterative form
+ * ECR-ITERATIVE-1 (Rodriguez & Walker 2014; Papastamoulis 2016): every kept sweep gets the permutation of its labels
+ * that agrees with a pivot allocation on as many observations as possible.  No probability matrix is needed, any
+ * burn-in will do.  Labels are 0-based in these definitions (1-based at the interfaces, as z_out); z_t is row t of an
+ * S x N trace with labels in 0 .. K-1, c a pivot of N labels in 0 .. K-1.
+ *   table        n_t[a, b] = #{i : z_t[i] = a, c[i] = b}, an exact integer (uint32; N < 2^32);
+ *   permutation  perm_t maximises agree_t = sum_a n_t[a, perm_t[a]]: the min-cost assignment on the K x K column-major
+ *                matrix C[b + a K] = -(double) n_t[a, b] (rows: pivot labels, columns: draw labels) by the Hungarian
+ *                method of the Stephens path, unchanged (rows enter in index order, the lowest column index wins a
+ *                tie).  Its "perm[l] = the row assigned to column l" reads "draw label l leaves as pivot label
+ *                perm[l]": the convention of bmm_relabel_out.permutations, z = perm[z], theta_relab[perm[k]] =
+ *                theta[k].  The costs are integers below 2^53, so the potentials stay exact;
+ *   iterative    (no pivot given) perm_t = identity; iteration it = 1, 2, ...: c[i] = the label with the most votes
+ *                among perm_t[z_t[i]] over the rows used, the lowest label on a tie; tables and permutations as above;
+ *                total_it = sum_t agree_t, an exact int64, which never decreases.  The loop stops after the first
+ *                iteration with total_it == total_(it-1) (converged = 1) or after max_iter iterations (converged = 0),
+ *                and returns the permutations, agreements and pivot of the last iteration run.  With a pivot given:
+ *                one pass, iterations = 1, converged = 1;
+ *   unused rows  trace row 0 of a run without burn-in is unassigned for every sampler but the finite collapsed one:
+ *                it is left out of votes and totals, its permutation is the identity, its agree 0, and n_used = S - 1.
+ * Nothing is floating point but the cost handed to the assignment; all counting is integer adds, so two calls give
+ * the same bits.  One synchronising copy of 8 bytes (total_it) per iteration is the loop's only host round trip. */
+#define BMM_ECR_MAX_K BMM_STEPHENS_MAX_K
+#define BMM_ECR_PIVOT_GIVEN 0
+#define BMM_ECR_PIVOT_PARTITION 1
+#define BMM_ECR_PIVOT_ITERATIVE 2
+/* Any stack of rows over the same observations (traces of several chains can be stacked by the caller).  z: S x N int32
+ * column-major, 1-based; pivot: N labels, 1-based, or NULL for the iterative form (max_iter >= 1 then).  perm_out S x K
+ * int32 column-major, 0-based; agree_out S int64; pivot_out N int32, 1-based, or NULL: the pivot of the last iteration;
+ * z_out S x N as z, relabelled (z_out = perm[z - 1] + 1, applied by the host's cores), or NULL; tables_out S x K x K
+ * uint32 or NULL, n_t[a, b] at [(t K + a) K + b]; iterations, converged as above.  BMM_E_ARG, before a device is
+ * touched, unless 1 <= S <= BMM_PARTITION_MAX_ROWS, N >= 1, 1 <= K <= BMM_ECR_MAX_K, and for a label of z or of the
+ * pivot outside 1 .. K (the row and the observation are named). */
+int bmm_device_ecr(int device, const int32_t* z, int S, int64_t N, int K, const int32_t* pivot, int max_iter,
+                   int32_t* perm_out, int64_t* agree_out, int32_t* pivot_out, int32_t* z_out, uint32_t* tables_out,
+                   int* iterations, int* converged);
+/* Which form of the k_ecr_* kernels a shape runs, as pure bookkeeping -- no device is touched, and the values come from
+ * the function the launches themselves read.  out:
+ *   [0] bytes per label of the stand-alone call's device block (1; a run reads its resident int32 trace: 4)
+ *   [1] 1: tables in LDS; 0: the generic form, adds straight to the global tables (a table above 48 KiB, K > 110)
+ *   [2] label rows per workgroup, T               [3] copies of each table in LDS, R (across the lanes of a wave)
+ *   [4] blocks of rows, ceil(S / T)               [5] slices of observations (the grid is [5] x [4] workgroups)
+ *   [6] observations per slice                    [7] bytes of dynamic LDS of the tables pass (0: generic)
+ *   [8] 1: vote counters in LDS; 0: the generic form, counters in global memory (K > 96)
+ *   [9] workgroups of the votes pass              [10] its bytes of dynamic LDS, or of global counters (generic)
+ *   [11] labels per row of the stand-alone call's device block (N rounded up to 16).
+ * BMM_E_ARG unless 1 <= S <= BMM_PARTITION_MAX_ROWS, N >= 1 and 1 <= K <= BMM_ECR_MAX_K. */
+int bmm_device_ecr_plan(int S, int64_t N, int K, int64_t out[12]);
+/* For a run: armed per calling thread for the NEXT single-chain *_run* call of that thread and disarmed when that call
+ * returns, whatever it returns, like bmm_set_partition_summary; NULL disarms.  The struct is copied; its buffers must
+ * stay valid through that call.  After the last sweep (and after the partition summary, when one is armed) the run
+ * computes the permutations from the resident trace, and then z_out / theta_out receive the relabelled traces (z =
+ * perm[z - 1] + 1, theta_relab(perm(k), d, s) = theta(k, d, s)) and z_original / theta_original the traces as sampled,
+ * as a *_run_relabel call leaves them.  Any burnin >= 0; combines with the partition and leave-one-out summaries,
+ * newdata, feature selection, split-merge moves and a device start.  BMM_ECR_PIVOT_PARTITION takes the row the armed
+ * partition summary chose, straight from the device: BMM_E_ARG, before a device is touched, when none is armed.
+ * BMM_E_ARG together with a *_run_relabel call or *_run_probs hooks (two relabellings), BMM_E_UNSUPPORTED for
+ * bmm_alloc_run; bmm_multi_run disarms it like any other run.  Its time is counted in phases [3] and [4] of
+ * bmm_last_run_phases. */
+typedef struct bmm_ecr_out {
+    int pivot_kind;          /* BMM_ECR_PIVOT_GIVEN, _PARTITION or _ITERATIVE */
+    const int32_t* pivot;    /* _GIVEN: N labels, 1-based; else ignored */
+    int max_iter;            /* _ITERATIVE: >= 1; else ignored */
+    int32_t* permutations;   /* S x K int32 column-major, 0-based */
+    int32_t* z_original;     /* S x N as z_out: the labels as sampled */
+    double* theta_original;  /* K x P x S as theta_out: theta as sampled */
+    int64_t* agree;          /* S */
+    int32_t* pivot_out;      /* N int32, 1-based (0 when no row was usable), or NULL */
+    int* iterations;
+    int* converged;
+    int* n_used;             /* rows used */
+} bmm_ecr_out;
+int bmm_set_ecr_relabel(const bmm_ecr_out* out);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
