@@ -310,12 +310,15 @@ static void file_weights(const double* w, int ncat, int K, int new_label, double
  * with the scored observation's own contribution removed (minus = 1: n-1, and s-1
  * on the x=1 side).  Groups of W features: T has G * 2^W entries, G = ceil(P / W) (the callers use GW for
  * the full tables and GWM for the minus-self ones).  Combinations no member can exhibit get 0. */
-static void counts_group_table(double beta, double gamma, int P, int W, int64_t n, const int32_t* s,
-                               int minus, double* e1, double* e0, double* T) {
+/* prior_at_zero (the allocation sampler's open labels): a label left with no member keeps the prior terms
+ * log(beta) - log(beta + gamma), log(gamma) - log(beta + gamma) instead of an all-zero table; the "no member can
+ * exhibit it" zeros stay, and only a label that does not hold the row it should give up (ne < 0) is all zero */
+static void counts_group_table_ex(double beta, double gamma, int P, int W, int64_t n, const int32_t* s,
+                                  int minus, int prior_at_zero, double* e1, double* e0, double* T) {
     const int G = (P + W - 1) / W;
     const unsigned M = 1u << W;
     int64_t ne = n - minus;
-    if (ne <= 0) { memset(T, 0, sizeof(double) * (size_t)G * M); return; }
+    if (prior_at_zero ? ne < 0 : ne <= 0) { memset(T, 0, sizeof(double) * (size_t)G * M); return; }
     double den = oracle_log((beta + gamma) + (double)ne);
     for (int d = 0; d < P; ++d) {
         int64_t s1 = (int64_t)s[d] - minus;
@@ -331,6 +334,10 @@ static void counts_group_table(double beta, double gamma, int P, int W, int64_t 
             }
             T[g * M + m] = t;
         }
+}
+static void counts_group_table(double beta, double gamma, int P, int W, int64_t n, const int32_t* s,
+                               int minus, double* e1, double* e0, double* T) {
+    counts_group_table_ex(beta, gamma, P, W, n, s, minus, 0, e1, e0, T);
 }
 static void theta_group_table(int P, int W, int K, int k, const double* theta /*K x P colmajor*/,
                               double* T) {
@@ -435,6 +442,41 @@ void oracle_collapsed_cond_spec(const int32_t* X, int64_t N, int P, const int32_
         int64_t ne = Nk[k] - minus;
         counts_group_table(beta, gamma, P, minus ? GWM : gw, Nk[k], S + (size_t)k * P, minus, e1, e1 + P, T);
         double C = ne > 0 ? oracle_log((double)ne + alpha / (double)K) - ldN : O_NEG_INF;
+        score[k] = minus ? table_sum(C, T, nibm + (size_t)i * Gm, Gm, GMM) : table_sum(C, T, nib + (size_t)i * G, G, GM);
+    }
+    if (scores_to_weights(score, K, w)) {
+        double tot = 0.0;
+        for (int k = 0; k < K; ++k) tot = tot + w[k];
+        for (int k = 0; k < K; ++k) norm[k] = w[k] / tot;
+    }
+    free(Nk); free(S); free(e1); free(T); free(w); free(nib); free(nibm);
+}
+
+/* The allocation sampler's sweep for one observation (include/bmm_mcmc.h "allocation sampler": sweep): maxK labels of
+ * which the first K_open are open, a the Dirichlet parameter per component.  An open label scores log(n + a) -
+ * log(N - 1 + K_open a) plus the Bernoulli terms of its statistics, the prior terms when it is empty; the row's own label
+ * with the row taken out, so a row that sits alone keeps its label at prior weight; a closed label scores -inf and
+ * gets probability exactly 0.  Groups as the finite sampler's for maxK labels. */
+void oracle_alloc_cond_spec(const int32_t* X, int64_t N, int P, const int32_t* z, int64_t i, int maxK,
+                            int K_open, double a, double beta, double gamma, double* score, double* norm) {
+    const int K = maxK, gw = oracle_group_width_for(0, maxK, P), GM = 1 << gw;
+    int G = (P + gw - 1) / gw, Gm = (P + GWM - 1) / GWM;
+    int32_t* Nk = (int32_t*)malloc(sizeof(int32_t) * K);
+    int32_t* S = (int32_t*)malloc(sizeof(int32_t) * (size_t)K * P);
+    double* e1 = (double*)malloc(sizeof(double) * P * 2);
+    double* T = (double*)malloc(sizeof(double) * ((size_t)G * GM + (size_t)Gm * GMM));
+    double* w = (double*)malloc(sizeof(double) * K);
+    uint8_t* nib = pack_nibbles(X, N, P, gw);
+    uint8_t* nibm = pack_nibbles(X, N, P, GWM);
+    count_stats(X, N, P, z, K, Nk, S);
+    int zo = z[i] - 1;
+    double ldN = oracle_log((double)(N - 1) + (double)K_open * a);
+    for (int k = 0; k < K; ++k) {
+        if (k >= K_open) { score[k] = O_NEG_INF; continue; }
+        int minus = (k == zo);
+        int64_t ne = Nk[k] - minus;
+        counts_group_table_ex(beta, gamma, P, minus ? GWM : gw, Nk[k], S + (size_t)k * P, minus, 1, e1, e1 + P, T);
+        double C = oracle_log((double)ne + a) - ldN;
         score[k] = minus ? table_sum(C, T, nibm + (size_t)i * Gm, Gm, GMM) : table_sum(C, T, nib + (size_t)i * G, G, GM);
     }
     if (scores_to_weights(score, K, w)) {
@@ -916,7 +958,8 @@ int oracle_full_run(const int32_t* X, int64_t N, int P, const double* pi0, const
 
 /* ------------------------------------------------------------------ sufficient-statistics chains */
 typedef struct {
-    int sampler; /* 0 collapsed, 1 dp */
+    int sampler; /* 0 collapsed, 1 dp, 2 the allocation sampler's sweep: K labels of which K_open are open */
+    int K_open;
     int64_t N; int P, K, gw, G, Gm;  /* K = number of labels (K or maxK); groups of gw / of GWM features */
     const int32_t* X;
     uint8_t* nib; uint8_t* nibm;
@@ -943,7 +986,8 @@ static int chain_init(ochain* c, int sampler, const int32_t* X, int64_t N, int P
                       const int32_t* z0_1based, double alpha, double beta, double gamma, double a,
                       double b, int64_t batch, uint64_t seed) {
     memset(c, 0, sizeof *c);
-    c->sampler = sampler; c->N = N; c->P = P; c->K = K; c->gw = oracle_group_width_for(sampler, K, P);
+    c->sampler = sampler; c->N = N; c->P = P; c->K = K; c->K_open = K;
+    c->gw = oracle_group_width_for(sampler == 2 ? 0 : sampler, K, P); /* the allocation sampler: the finite chain's image for maxK */
     c->G = (P + c->gw - 1) / c->gw; c->Gm = (P + GWM - 1) / GWM; c->X = X;
     c->beta = beta; c->gamma = gamma; c->a = a; c->b = b; c->seed = seed;
     c->batch = batch < 1 ? 1 : (batch > N ? N : batch);
@@ -996,7 +1040,9 @@ static void chain_batch(ochain* c, int64_t lo, int64_t hi, uint32_t j) {
     const int GM = 1 << c->gw;
     const size_t tk = (size_t)G * GM, tkm = (size_t)Gm * GMM;
     const double alpha = c->alpha_cur;
-    const double ldN = oracle_log((double)(c->N - 1) + alpha);
+    /* the allocation sampler: alpha is a, per component, and K_open components share the denominator */
+    const double ldN = c->sampler == 2 ? oracle_log((double)(c->N - 1) + (double)c->K_open * alpha)
+                                       : oracle_log((double)(c->N - 1) + alpha);
     int Kused = 0, new_label = -1;
     /* tables and constants are functions of (Nk, S, alpha) only: a cluster no observation entered or
      * left since they were last computed, under the same alpha, keeps them (same values, computed once
@@ -1008,14 +1054,24 @@ static void chain_batch(ochain* c, int64_t lo, int64_t hi, uint32_t j) {
             if (c->sampler == 0) {
                 c->Cp[k] = n > 0 ? oracle_log((double)n + alpha / (double)K) - ldN : O_NEG_INF;
                 c->Cm[k] = n > 1 ? oracle_log((double)(n - 1) + alpha / (double)K) - ldN : O_NEG_INF;
+            } else if (c->sampler == 2) {
+                const int open = k < c->K_open;
+                c->Cp[k] = open ? oracle_log((double)n + alpha) - ldN : O_NEG_INF;
+                c->Cm[k] = open && n >= 1 ? oracle_log((double)(n - 1) + alpha) - ldN : O_NEG_INF;
             } else {
                 c->Cp[k] = n > 0 ? oracle_log((double)n) - ldN : O_NEG_INF;
                 c->Cm[k] = n > 1 ? oracle_log((double)(n - 1)) - ldN : O_NEG_INF;
             }
         }
         if (c->dirty[k]) {
-            counts_group_table(c->beta, c->gamma, P, c->gw, c->Nk[k], c->S + (size_t)k * P, 0, c->e, c->e + P, c->Tp + k * tk);
-            counts_group_table(c->beta, c->gamma, P, GWM, c->Nk[k], c->S + (size_t)k * P, 1, c->e, c->e + P, c->Tm + k * tkm);
+            if (c->sampler == 2 && k >= c->K_open) { /* closed: -inf above, tables zero */
+                memset(c->Tp + k * tk, 0, sizeof(double) * tk);
+                memset(c->Tm + k * tkm, 0, sizeof(double) * tkm);
+            } else {
+                const int pz = c->sampler == 2;
+                counts_group_table_ex(c->beta, c->gamma, P, c->gw, c->Nk[k], c->S + (size_t)k * P, 0, pz, c->e, c->e + P, c->Tp + k * tk);
+                counts_group_table_ex(c->beta, c->gamma, P, GWM, c->Nk[k], c->S + (size_t)k * P, 1, pz, c->e, c->e + P, c->Tm + k * tkm);
+            }
             c->dirty[k] = 0;
         }
         if (n > 0) Kused++; else if (new_label < 0) new_label = k;
@@ -1145,6 +1201,40 @@ int oracle_dp_run(const int32_t* X, int64_t N, int P, int nsamples, double alpha
     return run_counts_chain(1, X, N, P, NULL, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch,
                             seed, z_out, theta_out, alpha_out, NULL, NULL, 0, NULL, NULL);
 }
+/* The allocation sampler's sweeps with the moves off (include/bmm_mcmc.h "allocation sampler": sweep): maxK labels,
+ * K_open of them open, a fixed, no concentration update; z0 holds 1-based labels in 1..K_open.  Shaped like
+ * oracle_collapsed_run -- row 0 of a run without burn-in is z0 with theta NaN -- except that the sweeps are numbered
+ * first_sweep, first_sweep + 1, ..., so that a chain can be continued from the labels of any sweep.  theta_out is
+ * S / Nk, NaN where a label is empty. */
+int oracle_alloc_run(const int32_t* X, int64_t N, int P, const int32_t* z0, int nsamples, int maxK, int K_open,
+                     double a, double beta, double gamma, int burnin, int64_t batch, uint64_t seed,
+                     uint32_t first_sweep, int32_t* z_out, double* theta_out) {
+    if (!z0) return fail("initialK required");
+    if (nsamples < 1 || burnin < 0 || burnin > nsamples) return fail("bad nsamples/burnin");
+    if (maxK < 1 || K_open < 1 || K_open > maxK) return fail("K_open must lie in 1..maxK");
+    if (!(a > 0.0)) return fail("a must be > 0");
+    if (first_sweep < 1) return fail("first_sweep must be >= 1");
+    for (int64_t i = 0; i < N; ++i)
+        if (z0[i] < 1 || z0[i] > K_open) return fail("initialK must lie in 1..K_open: a closed label holds no row");
+    ochain c;
+    if (chain_init(&c, 2, X, N, P, maxK, z0, a, beta, gamma, 0.0, 0.0, batch, seed)) { chain_free(&c); return 1; }
+    c.K_open = K_open;
+    const int S = nsamples - burnin;
+    double* alpha_scratch = (double*)malloc(sizeof(double) * (S > 0 ? S : 1));
+    if (!alpha_scratch) { chain_free(&c); return fail("out of memory"); }
+    if (burnin == 0) {
+        for (int64_t i = 0; i < N; ++i) z_out[0 + (size_t)i * S] = z0[i];
+        for (int q = 0; q < maxK * P; ++q) theta_out[q] = NAN;
+    }
+    for (int j = 1; j < nsamples; ++j) {
+        chain_sweep(&c, first_sweep + (uint32_t)(j - 1));
+        if (j >= burnin) chain_emit(&c, j - burnin, S, z_out, theta_out, alpha_scratch);
+    }
+    free(alpha_scratch);
+    chain_free(&c);
+    return 0;
+}
+
 /* The same chains without the S x N label trace (which does not fit at N = 10^6 and hundreds of kept
  * sweeps): cluster sizes per kept sweep, theta-hat, alpha, and the labels after the last sweep.
  * sampler 0: collapsed (z0 required), 1: dp (z0 ignored, K = maxK).  For tests/golden/make_tolerance_fixtures.py. */

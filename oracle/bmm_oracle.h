@@ -69,6 +69,11 @@ void oracle_collapsed_cond_literal(const int32_t* X, int64_t N, int P, const int
 void oracle_collapsed_cond_spec(const int32_t* X, int64_t N, int P, const int32_t* z, int64_t i,
                                 int K, double alpha, double beta, double gamma,
                                 double* score /*K*/, double* norm /*K*/);
+/* The allocation sampler's sweep (include/bmm_mcmc.h "allocation sampler"): maxK labels, the first K_open open at
+ * weight log(n + a) - log(N - 1 + K_open a) with the prior terms where empty, the rest closed (-inf, norm exactly 0). */
+void oracle_alloc_cond_spec(const int32_t* X, int64_t N, int P, const int32_t* z, int64_t i, int maxK,
+                            int K_open, double a, double beta, double gamma, double* score /*maxK*/,
+                            double* norm /*maxK*/);
 /* DP: existing clusters in label order 1..K then the new-cluster option (K+1 values). */
 void oracle_dp_cond_literal(const int32_t* X, int64_t N, int P, const int32_t* z, int64_t i, int K,
                             double alpha, double beta, double gamma, double* logw /*K+1*/,
@@ -89,6 +94,12 @@ int oracle_collapsed_run(const int32_t* X, int64_t N, int P, const int32_t* z0, 
                          double alpha, double beta, double gamma, double a, double b, int burnin,
                          int64_t batch, uint64_t seed, int32_t* z_out, double* theta_out,
                          double* alpha_out);
+/* The allocation sampler's sweeps, moves off, as a third mode of the counts chain: rows as oracle_collapsed_run's
+ * (row 0 of a run without burn-in: z0, theta NaN), the sweeps numbered first_sweep, first_sweep + 1, ...; theta_out
+ * is S / Nk with NaN where a label is empty. */
+int oracle_alloc_run(const int32_t* X, int64_t N, int P, const int32_t* z0, int nsamples, int maxK, int K_open,
+                     double a, double beta, double gamma, int burnin, int64_t batch, uint64_t seed,
+                     uint32_t first_sweep, int32_t* z_out, double* theta_out);
 int oracle_dp_literal(const int32_t* X, int64_t N, int P, int nsamples, double alpha, double beta,
                       double gamma, double a, double b, int burnin, int maxK, uint64_t seed,
                       int32_t* z_out, double* theta_out, double* alpha_out);

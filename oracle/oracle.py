@@ -158,6 +158,20 @@ def dp_cond(X, z, i, K, alpha, beta, gamma, spec=False):
                  X, z, i, K, alpha, beta, gamma, K + 1)
 
 
+def alloc_cond(X, z, i, maxK, K_open, a, beta, gamma):
+    """(score, normalised) conditional of observation i (0-based) under the allocation sampler's sweep: maxK labels,
+    the first K_open open; z 1-based.  A closed label has score -inf and probability exactly 0."""
+    X = _x(X)
+    N, P = X.shape
+    z = np.ascontiguousarray(z, dtype=np.int32)
+    score = np.zeros(maxK)
+    norm = np.zeros(maxK)
+    lib().oracle_alloc_cond_spec(X.ctypes.data_as(C.c_void_p), C.c_int64(N), C.c_int(P), z.ctypes.data_as(C.c_void_p),
+                                 C.c_int64(i), C.c_int(maxK), C.c_int(K_open), C.c_double(a), C.c_double(beta),
+                                 C.c_double(gamma), score.ctypes.data_as(C.c_void_p), norm.ctypes.data_as(C.c_void_p))
+    return score, norm
+
+
 def sb_cond(X, i, pi, theta, spec=False):
     X = _x(X)
     N, P = X.shape
@@ -228,6 +242,22 @@ def collapsed(X, z0, nsamples, K, alpha, beta, gamma, a, b, burnin, seed, batch=
                                     _vp(z), _vp(th), _vp(al))
     _check(rc)
     return {"alpha": al, "z": z, "theta": th}
+
+
+def alloc(X, z0, nsamples, maxK, K_open, a, beta, gamma, burnin, seed, batch=1, first_sweep=1):
+    """The allocation sampler's sweeps with the moves off: maxK labels of which the first K_open are open, `a` per
+    component.  Rows as collapsed()'s -- row 0 of a run without burn-in is z0 -- with the sweeps numbered first_sweep,
+    first_sweep + 1, ..., so a chain can be continued from the labels read at any sweep.  theta is S / Nk, NaN where a
+    label is empty."""
+    X = _x(X)
+    N, P = X.shape
+    z0 = np.ascontiguousarray(z0, dtype=np.int32)
+    S = nsamples - burnin
+    z, th, _ = _outs(S, N, maxK, P)
+    _check(lib().oracle_alloc_run(_vp(X), C.c_int64(N), C.c_int(P), _vp(z0), C.c_int(nsamples), C.c_int(maxK),
+                                  C.c_int(K_open), C.c_double(a), C.c_double(beta), C.c_double(gamma), C.c_int(burnin),
+                                  C.c_int64(batch), C.c_uint64(seed), C.c_uint32(first_sweep), _vp(z), _vp(th)))
+    return {"z": z, "theta": th}
 
 
 def dp(X, nsamples, alpha, beta, gamma, a, b, burnin, maxK, seed, batch=1, literal=False, probs_sweep=None):
