@@ -440,6 +440,69 @@ BMM_HD int draw_spec(const double (&sc)[KT], double m, double u) {
     return n;
 }
 
+// ---------------------------------------------------------------- the draw from scores summed in binary32
+// The packed tier (k_resample_pk): the scores themselves come from binary32 copies of the table entries, two categories
+// to a 64-bit lookup, summed in binary32 in group order; the own-cluster score is the binary64 sum narrowed once.
+// draw_pk takes those scores s~_k and their maximum m~ and is draw_tier1 from there on, with a band that also covers
+// what the scores lost.  As there, `true` means the count is PROVEN to be the definition's.
+//
+// The band, per lane: kPkEpsUnit * (80 + (G + 2) (|m~| + ln 64 + 1)) * tot~, G the number of lookup groups.  With
+// h = 2^-24 and s_k, m, d_k = s_k - m <= 0, w_k = e^(d_k), T = sum w_k >= 1 the exact quantities of the definition:
+//   every table entry is <= 0 (a log of a probability; the constant term log(n_k + alpha/K) - log(N - 1 + alpha) of a
+//     category that is not the observation's own has n_k <= N - 1), so the partial sums of a score only grow in
+//     magnitude and every one of them is <= |s_k|.  An entry narrowed to binary32 is within h of itself, each of the
+//     G - 1 binary32 additions within h of a partial sum: |s~_k - s_k| <= G h |s_k| (1 + G h).  (The host test pushes
+//     every narrowed entry a further ulp = 2 h: (G + 2) h |s_k|, which is why the band says G + 2.)  The own score is
+//     one narrowing of a binary64 sum: h |s_k|.
+//   a shift common to all categories cancels in the sign of t - cdf_k, so m~ need not be m: tier and definition are
+//     compared on the weights e^(s_k - m~), which are the w_k times one common factor.  The argument of exp2 is
+//     (s~_k - m~) log2(e) (1 + delta), |delta| <= 3.01 h as in draw_tier1 (the subtraction's rounding in place of the
+//     narrowing there), so the weight of category k is off by the factor e^x, |x| <= (G + 2) h |s_k| + 3.01 h |d_k|,
+//     |x| < 6e-3 for G <= 26 and scores down to -3000 -- deeper than the resident kernels' shapes reach: P <= 128
+//     feature terms of at least log(beta / (beta + gamma + N)) each, about -22 at N = 1e9 with the default priors --
+//     so e^x - 1 <= 1.003 |x|.  With |s_k| = |m| + |d_k| and sum_k w_k |d_k| = T (H(w / T) - ln T) <= T ln K, the
+//     weights together are off by at most 1.003 h ((G + 2)(|m| + ln K) + 3.01 ln K) T
+//   exp2 itself (2 h), the binary32 running sum ((K - 1) h), u narrowed and the product (2 h), second order (0.1 h)
+//     and the definition's own rounding (2^-45): as in draw_tier1, 67.1 h + 2^-45 for K <= 64.
+// In all E <= h (79.7 + 1.003 (G + 2)(|m| + ln 64)) + 2^-45 in units of T (E < 6e-3 over that range), and
+// |m~| >= |m| (1 - G h); the band is 3.2 h (80 + (G + 2)(|m~| + ln 64 + 1)) tot~ with tot~ >= T (1 - E), more than
+// three times E T.  (Beyond -3000 the factor 1.003 grows with |s|, and the margin of three still covers it to 1e5.)  Ties, u = 0, NaN
+// and a maximum that is not finite: as in draw_tier1 (never certain).  Impossible categories (-inf, the padding
+// included) weigh exactly 0 on both sides.
+constexpr float kPkEpsUnit = 3.2f * 0x1p-24f;
+constexpr float kPkLnCats = 4.1588831f;  // ln kTier1MaxCats
+BMM_HD float pk_band(float m, int G, float unit) {
+    return unit * (80.0f + (float)(G + 2) * (__builtin_fabsf(m) + kPkLnCats + 1.0f));
+}
+// sc[0..KT): the binary32 scores (own-cluster substitution done), m their maximum, u the draw's uniform, G the lookup
+// groups each score is the sum of, unit = kPkEpsUnit (0: no band, for the tests that show what the band is for).
+template <int KT, class Exp2 = Exp2Fast>
+BMM_HD bool draw_pk(const float (&sc)[KT], float m, double u, int G, float unit, int& cnt, Exp2 ex2 = Exp2()) {
+    static_assert(KT <= kTier1MaxCats, "the band is derived for at most kTier1MaxCats categories");
+    float c[KT];
+    float run = 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < KT; ++k) {
+        run = run + ex2((sc[k] - m) * 0x1.715476p+0f);  // log2(e); -inf - -inf = NaN stays in `run`
+        c[k] = run;
+    }
+    const float t = (float)u * run;
+    float nearest = __builtin_inff();
+    int n = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 0; k < KT; ++k) {
+        const float diff = t - c[k];
+        n += diff >= 0.0f ? 1 : 0;
+        nearest = __builtin_fminf(nearest, __builtin_fabsf(diff));
+    }
+    cnt = n;
+    return nearest > pk_band(m, G, unit) * run && m > -__builtin_inff() && m < __builtin_inff();  // false when `run` is NaN
+}
+
 // ---------------------------------------------------------------- variates
 // Standard normal by the Marsaglia polar method (log and sqrt only).
 BMM_HD double rnorm_(Stream& st) {

@@ -359,6 +359,7 @@ struct KernelForm {
     bool emit = false;  // the weight-emitting twin: what a sweep runs on while its probabilities go to the host
     int gw = kGroupW;   // the shape's group width (bmm_spec.h)
     bool self = false;  // workgroups that build their own table image (SELF)
+    bool pk = false;    // k_resample_pk: scores from the packed binary32 image, the definition for the queued few
 };
 constexpr int tile_of(const KernelForm& f) { return f.nt / f.lanes; }  // observations per tile
 constexpr KernelForm resized(KernelForm f, int nt, int lanes = 1) { f.nt = nt; f.lanes = lanes; return f; }
@@ -383,6 +384,10 @@ constexpr int stage_width(const KernelForm& f, bool named_size) {
 // Which forms are instantiated: the whole kernel set of the library.  (accumulator counts: those of kKT)
 constexpr bool instantiated(const KernelForm& f, bool named_size) {
     const bool preferred = f.gw == kGroupW;
+    // the packed kernel: the plain bit-plane form (one lane, own-cluster tables in LDS) up to 32 accumulators, at
+    // every workgroup size for the preferred width and at the default size for the narrower one
+    if (f.pk) return f.bits && f.lanes == 1 && f.minus == 1 && !f.emit && !f.self && f.kt <= 32 &&
+                     (preferred || (f.gw == kGroupWAlt && f.nt == threads_for(f.kt, true)));
     // SELF: 256-thread workgroups that build their own table image (finite sampler, small shapes: kernels.hip.h)
     if (f.self) return f.kt <= 12 && f.nt == 256 && f.minus == 1 && f.bits && f.lanes == 1 && !f.emit && preferred;
     // EMIT: the twins of the default-sized bit-plane kernels, every tier and width
@@ -413,6 +418,13 @@ resample_fn instance() {
 }
 resample_fn lookup(const KernelForm& f, bool named_size = false) {
     resample_fn fn = nullptr;
+    if (f.pk) {
+        if (!instantiated(f, named_size)) return nullptr;
+        lift([&](auto kt, auto nt, auto gw) {
+            if constexpr (instantiated(KernelForm{kt, nt, 1, true, 1, false, gw, false, true}, false)) fn = k_resample_pk<kt, nt, gw>;
+        }, kKT, f.kt, IntList<1024, 768, 512, 256>{}, f.nt, IntList<kGroupW, kGroupWAlt>{}, f.gw);
+        return fn;
+    }
     lift([&](auto kt, auto nt, auto minus, auto bits, auto gw) {
         // two lanes, EMIT, SELF and a named size come one at a time (lifting them as well would cost the compiler
         // sixteen times the combinations for the same five)
@@ -538,6 +550,7 @@ struct bmm_chain {
     int* dViable = nullptr;       // stick-breaking / full: the cluster count the concentration's update uses (k_sb_params -> k_sb_theta_tables)
     int* dSelfDone = nullptr;     // SELF kernels: workgroups of the running launch that have read the statistics
     int32_t *dDNkAlt = nullptr, *dDSAlt = nullptr;  // ... and the second set of delta accumulators (self_fold_prev)
+    unsigned long long* dPkStat = nullptr;  // -DBMM_DEBUG_HOOKS: k_resample_pk's draws and deferred observations
     int* dDbgFlag = nullptr;      // -DBMM_DEBUG_HOOKS: raised by a kernel that meets a label out of range
     // posterior predictive of new rows: their bit planes [ceil(P/32)][predM], the predictive
     // table image of the counting samplers (the explicit samplers' own image dTab is the predictive image), the
@@ -773,6 +786,8 @@ struct DebugSwitches {
     bool nosplit = dbg_env("BMM_DEBUG_NOSPLIT");        // never two lanes per observation
     bool small = dbg_env("BMM_DEBUG_SMALL");            // the 256-thread form whatever the size of the tables
     bool noself = dbg_env("BMM_DEBUG_NOSELF");          // no table-building workgroups
+    bool nopk = dbg_env("BMM_DEBUG_NOPK");              // k_resample where k_resample_pk would run (A/B in one library)
+    bool pk = dbg_env("BMM_DEBUG_PK");                  // k_resample_pk whatever the length of a launch
 };
 
 // What follows from (sampler, N, P, K, batch) alone -- no device state enters.
@@ -795,6 +810,13 @@ ChainParams geometry(int sampler, int P, int K, int kt, int W) {
 size_t image_bytes(const ChainParams& q, bool own_tables) {
     const TableLayout l = layout_of(q, own_tables && !explicit_params(q.mode));
     return (size_t)(own_tables ? l.doubles() : l.head()) * sizeof(double) + ((size_t)q.K * q.P + q.K + 4) * sizeof(int32_t);
+}
+
+// LDS of a k_resample_pk workgroup: the packed image, the tail of the table image (Nk, E, Tm), the histogram with
+// its counters, the queue
+size_t pk_image_bytes(const ChainParams& q) {
+    const TableLayout l = layout_of(q, true);
+    return (size_t)(pk_tq_doubles(l) + l.doubles() - l.nk()) * sizeof(double) + ((size_t)q.K * q.P + q.K + 4 + kPkQueue) * sizeof(int32_t);
 }
 
 // The spec's rule for the group width of a shape (bmm_spec.h; the oracle restates it): groups of kGroupW
@@ -979,7 +1001,8 @@ int chain_alloc(bmm_chain* c) {
     }
     const size_t nz = (size_t)p.N;
     const size_t ns = (size_t)p.K * p.P, nn = (size_t)p.K;
-    const size_t ntab = (size_t)layout_of(c).doubles();
+    // (behind the image of a counting sampler: the packed image k_resample_pk reads)
+    const size_t ntab = (size_t)layout_of(c).doubles() + (explicit_params(p.mode) ? 0 : (size_t)pk_tq_doubles(layout_of(c)));
     auto carve = [&](Carver& a) {
         // the statistics, their delta replicas, the table image and the flags first: zeroed in one go
         c->dNk = a.take<int32_t>(nn);
@@ -996,6 +1019,7 @@ int chain_alloc(bmm_chain* c) {
         c->dDSAlt = a.take<int32_t>(ns * kDeltaReps);
 #ifdef BMM_DEBUG_HOOKS
         c->dDbgFlag = a.take<int>(1);
+        c->dPkStat = a.take<unsigned long long>(2);
 #endif
         const size_t zeroed = a.used;
         c->dAlpha = a.take<double>(1);
@@ -1039,6 +1063,11 @@ int launch_resample(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t l
     a.dbg_flag = c->dDbgFlag; a.dbg_inject = (dbg_env("BMM_DEBUG_BADLABEL") ? 1 : 0) | (dbg_env("BMM_DEBUG_STRAGGLER") ? 2 : 0) |
                                              (dbg_env("BMM_DEBUG_DRAW_FALLBACK") ? 4 : 0) | (dbg_env("BMM_DEBUG_DRAW_NOEPS") ? 8 : 0);
     a.Nk = c->dNk; a.S = c->dS; a.alpha_ptr = c->dAlpha; a.self_done = c->dSelfDone;
+    a.pk_qcap = kPkQueue;
+#ifdef BMM_DEBUG_HOOKS
+    if (const int cap = dbg_env_int("BMM_DEBUG_PK_QUEUE", 0)) a.pk_qcap = cap < kPkQueue ? cap : kPkQueue;
+    a.pk_stat = c->dPkStat;
+#endif
     const bool emit = c->probs_dst != nullptr;
     const bool use_generic = c->generic || (emit && !c->fn_emit);  // the int32 layout has no emitting twin
     // a kernel that builds its own tables reads the pending deltas and flushes into the other (empty) set, which
@@ -1128,10 +1157,10 @@ int launch_count_tables(bmm_chain* c) {
                            c->dDNk, c->dDS, (const int32_t*)c->dEaK, c->alloc_a, c->dTab);
     else if (c->fs_mask)  // feature selection: excluded features are written as zeros
         hipLaunchKernelGGL(k_count_tables<true>, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
-                           c->dDNk, c->dDS, c->dAlpha, c->dTab, (const uint32_t*)c->dFsMask);
+                           c->dDNk, c->dDS, c->dAlpha, c->dTab, (const uint32_t*)c->dFsMask, 0);
     else
         hipLaunchKernelGGL(k_count_tables<false>, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
-                           c->dDNk, c->dDS, c->dAlpha, c->dTab, (const uint32_t*)nullptr);
+                           c->dDNk, c->dDS, c->dAlpha, c->dTab, (const uint32_t*)nullptr, c->form.pk && !c->generic ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return BMM_OK;
 }
@@ -1547,7 +1576,22 @@ KernelPlan plan_kernel(const ChainParams& p, bool bits, int minus, int64_t batch
     const bool alt = p.W != kGroupW;  // the narrower groups: default-sized kernels only
     KernelForm f{p.KT, threads_for(p.KT, bits), minus, bits, 1, false, p.W, false};
     KernelPlan plan;
-    auto offer = [&plan](const KernelForm& g, size_t lds) { plan.form[plan.n] = g; plan.lds[plan.n++] = lds; };
+    // The packed kernel takes the place of every form it exists for (not with a feature mask or the allocation
+    // sampler's tables: the band of draw_pk rests on k_count_tables' entries, all of them <= 0); its LDS is its own
+    // image.  The choice of the form itself -- size, lanes, step-down -- is made as before, from the binary64 image.
+    // Only for launches that give a wave at least four chunks: the exact pass is a tail of a few microseconds behind
+    // the workgroup's barrier (dependent L2 round trips for as little as one queued observation), the packed scoring
+    // saves about 2 us per chunk and wave.  Same-box: C5 (9.5 chunks per wave) +19 %; the north-star shape and c3
+    // (one chunk per wave) lost 11 % and 6 % with the packed kernel (profiles/r05/README.md).
+    const size_t pk_lds = explicit_params(p.mode) ? 0 : pk_image_bytes(p);
+    auto offer = [&](KernelForm g, size_t lds) {
+        KernelForm h = g;
+        h.pk = true;
+        const bool long_launch = batch >= (int64_t)4 * num_cus * g.nt;
+        if (!masked && !d.nopk && (long_launch || d.pk) && !g.self && !explicit_params(p.mode) && instantiated(h, false) &&
+            pk_lds <= kLdsMax && batch < ((int64_t)1 << 31)) { g = h; lds = pk_lds; }
+        plan.form[plan.n] = g; plan.lds[plan.n++] = lds;
+    };
     // Two lanes per observation: always above 32 accumulators (registers), and from 16 up when a launch is so
     // short that the default form would give a wave at most a chunk or two -- then a launch is all latency
     // (the north-star shape: 15 us per launch of which 4 are arithmetic, VALU busy 27 %), and the two-lane
@@ -4286,6 +4330,20 @@ extern "C" int bmm_dbg_host_labels(const void* src, int narrow, int32_t* dst, in
 static void kernel_key(const KernelForm& f, const KernelForm& twin, bool generic, int grid_max_emit, int* key) {
     const int k[10] = {f.kt, f.nt, f.lanes, f.minus, f.bits ? 1 : 0, f.gw, f.self ? 1 : 0, generic ? 0 : twin.nt, generic ? 1 : 0, grid_max_emit};
     std::memcpy(key, k, sizeof k);
+}
+// ... whether that kernel is the packed one (k_resample_pk; the key's ten slots describe the form it stands in for),
+// and what its launches have counted so far: observations drawn, observations deferred to the binary64 definition
+extern "C" int bmm_dbg_kernel_packed(const bmm_chain* c) { return c && !c->generic && c->form.pk ? 1 : 0; }
+extern "C" int bmm_dbg_pk_counts(bmm_chain* c, unsigned long long* draws, unsigned long long* deferred) {
+    if (!c || !draws || !deferred) return set_err(BMM_E_ARG, "null argument");
+    return guarded([&]() -> int {
+        unsigned long long v[2] = {0, 0};
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(v, c->dPkStat, sizeof v, hipMemcpyDeviceToHost));
+        *draws = v[0]; *deferred = v[1];
+        return BMM_OK;
+    });
 }
 extern "C" int bmm_dbg_kernel_key(const bmm_chain* c, int* key) {
     if (!c || !key) return set_err(BMM_E_ARG, "null argument");

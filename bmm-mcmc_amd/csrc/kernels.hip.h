@@ -141,24 +141,28 @@ __device__ __forceinline__ double update_alpha_wave(double alpha_old, double a, 
 // ---------------------------------------------------------------------------------
 // e1/e0 hold the `pc` features of one chunk; its `gc` groups start at global group g0
 // `c` is the category's constant term: it goes into the entries of global group 0
+// Tq (or null): the packed image behind the table image, Tq[G][KT/2][M] pairs of binary32 -- the very entries
+// written to T, narrowed, categories 2j and 2j+1 side by side (k_resample_pk reads a pair in one ds_read_b64)
 template <int W>
 __device__ __forceinline__ void write_group_tables_w(const double* e1, const double* e0, int pc, int g0, int gc,
-                                                   int KT, int k, double c, double* T) {
+                                                   int KT, int k, double c, double* T, float* Tq = nullptr) {
     constexpr int M = 1 << W;
     for (int idx = threadIdx.x; idx < gc * M; idx += blockDim.x) {
         const int g = idx / M;
         const unsigned m = idx % M;
         const double t = group_entry(e1, e0, g, pc, m, W);
-        T[((size_t)(g0 + g) * KT + k) * M + m] = g0 + g == 0 ? c + t : t;
+        const double v = g0 + g == 0 ? c + t : t;
+        T[((size_t)(g0 + g) * KT + k) * M + m] = v;
+        if (Tq) Tq[(((size_t)(g0 + g) * (KT / 2) + (k >> 1)) * M + m) * 2 + (k & 1)] = (float)v;
     }
 }
 
 // W = the shape's width (kGroupW or kGroupWAlt) or the own-cluster tables' kGroupWm; uniform
 __device__ __forceinline__ void write_group_tables(int W, const double* e1, const double* e0, int pc, int c0,
-                                                   int KT, int k, double c, double* T) {
+                                                   int KT, int k, double c, double* T, float* Tq = nullptr) {
     const int g0 = c0 / W, gc = (pc + W - 1) / W;
-    if (W == kGroupW) write_group_tables_w<kGroupW>(e1, e0, pc, g0, gc, KT, k, c, T);
-    else if (W == kGroupWAlt) write_group_tables_w<kGroupWAlt>(e1, e0, pc, g0, gc, KT, k, c, T);
+    if (W == kGroupW) write_group_tables_w<kGroupW>(e1, e0, pc, g0, gc, KT, k, c, T, Tq);
+    else if (W == kGroupWAlt) write_group_tables_w<kGroupWAlt>(e1, e0, pc, g0, gc, KT, k, c, T, Tq);
     else write_group_tables_w<kGroupWm>(e1, e0, pc, g0, gc, KT, k, c, T);
 }
 
@@ -174,10 +178,13 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
                                                                      int32_t* __restrict__ dS,
                                                                      const double* __restrict__ alpha_ptr,
                                                                      double* __restrict__ tab,
-                                                                     const uint32_t* __restrict__ mask) {
+                                                                     const uint32_t* __restrict__ mask,
+                                                                     int packed) {
     __shared__ double e1[kMaxP], e0[kMaxP], m1[kMaxP], m0[kMaxP], cst[4];  // cst: Cp, Cm, the two denominators
     const int k = blockIdx.x;
     const TableLayout L = layout_of(p, true);
+    // the chain runs k_resample_pk: the packed image goes behind this one (uniform; never with a mask, plan_kernel)
+    float* const Tq = !MASK && packed ? reinterpret_cast<float*>(tab + L.doubles()) : nullptr;
     const int P = p.P;
     const bool is_label = k < p.K;
     // 576 threads, ONE log_ each on the critical path (a log_ is about 150 dependent instructions).  Waves
@@ -262,7 +269,7 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
             }
         }
         __syncthreads();
-        write_group_tables(p.W, e1, e0, pc, c0, p.KT, k, cst[0], tab + L.tp());
+        write_group_tables(p.W, e1, e0, pc, c0, p.KT, k, cst[0], tab + L.tp(), Tq);
         write_group_tables(kGroupWm, m1, m0, pc, c0, p.KT, k, cst[1], tab + L.tm());
         __syncthreads();
     }
@@ -502,6 +509,9 @@ struct ResampleArgs {
     int32_t* dS_prev;
     const double* alpha_ptr;
     int* self_done;
+    // k_resample_pk: entries its LDS queue holds, and (test variant) its counters [draws, deferred]
+    int pk_qcap;
+    unsigned long long* pk_stat;
 };
 
 // The test variant of the library (-DBMM_DEBUG_HOOKS) checks every label a resample kernel is about to count
@@ -1282,6 +1292,312 @@ __global__ __launch_bounds__(NT) void k_resample(ChainParams p, ResampleArgs a) 
         // the two-tier draw: draws of 64 observations a wave made, and how many of them ran the binary64 definition
         atomicAdd(&a.diag[12], d_ndraw); atomicAdd(&a.diag[13], d_nfall);
     })
+}
+
+// ---------------------------------------------------------------------------------
+// k_resample_pk: the plain bit-plane kernel (one lane per observation, own-cluster tables in LDS) with the scores
+// of the other categories summed in binary32 from the packed image Tq -- one ds_read_b64 and one v_pk_add_f32 per
+// PAIR of categories and lookup group, half of k_resample's LDS and scoring VALU instructions.  The draw is
+// draw_pk (bmm_spec.h), which says per lane whether its count is proven to be the definition's.  A lane that is
+// not certain writes its observation's index into a queue in LDS and neither stores nor counts it; after the
+// tile loop the workgroup runs the binary64 definition on the queue (pk_exact_one: one wave per observation, one
+// lane per category, Tp read from the global image), so the labels are k_resample's bit for bit.  An
+// observation that finds the queue full is scored by its wave on the spot.
+// LDS, in doubles: Tq [G][KT/2][M] pairs | the image's tail as it lies in global memory (Nk, E, Tm) | histogram,
+// chunk counter, queue counter | queue.
+// ---------------------------------------------------------------------------------
+constexpr int kPkQueue = 4096;  // queue entries (pk_image_bytes, chain.hip)
+typedef float pk_f2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) pk_f2 lds_pk_f2;
+__host__ __device__ inline int pk_tq_doubles(const TableLayout& L) { return L.G * (L.KT / 2) * L.M; }
+
+// the DP's bookkeeping for a draw of the new-cluster option (collapsed_gibbs_dp.cpp:212-231).  A second copy of the
+// block under `if (p.mode == MODE_DP && zn == K)` in k_resample, which stays inline there so that its 370
+// instantiations compile as they did: a fix to either belongs in both.
+__device__ __forceinline__ int pk_dp_label(const int32_t* NkT, int K, int Kused, int new_label, int zo, int zoc) {
+    const int own_single = (zo >= 0 && NkT[zoc] == 1) ? 1 : 0;
+    if (Kused - own_single < K - 1) {
+        int zn = new_label;
+        if (own_single && (zn < 0 || zo < zn)) zn = zo;
+        return zn;
+    }
+    int best = -1, bs = 0;
+    for (int k = 0; k < K; ++k) {
+        const int sz = NkT[k] - (k == zo ? 1 : 0);
+        if (sz > 0 && (best < 0 || sz < bs)) { best = k; bs = sz; }
+    }
+    return best >= 0 ? best : zoc;
+}
+// bits [bit, bit + width) of the observation's 128-bit pattern (bit uniform)
+__device__ __forceinline__ unsigned pk_field(int bit, unsigned mask, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3) {
+    const int wd = bit >> 5;
+    return __builtin_amdgcn_alignbit(word_of(wd + 1, b0, b1, b2, b3), word_of(wd, b0, b1, b2, b3), (unsigned)(bit & 31)) & mask;
+}
+
+// The definition for observation i (wave-uniform), by the whole wave: lane k scores category k -- the G entries of
+// Tp from the global image (L2), four loads in flight, added in group order; the own cluster from Tm in LDS, in
+// group order, padding groups included -- then the maximum, expw_ and the binary64 running sum walk the lanes in
+// label order.  Every operation and its order are k_resample's.
+template <int KT, int GW>
+__device__ __forceinline__ void pk_exact_one(const ChainParams& p, const ResampleArgs& a, const TableLayout& L, int64_t i,
+                                             const lds_f64* TmL, const lds_f64* ET, const int32_t* NkT, int32_t* hist,
+                                             int Kused, int new_label, int lane) {
+    constexpr int GM = 1 << GW;
+    const int P = p.P, G = p.G, K = p.K;
+    uint32_t b0, b1, b2, b3;
+    load_words(a.Xb, p.N, (P + 31) / 32, i, b0, b1, b2, b3);
+    int zo = a.z_in ? a.z_in[i] : -1;
+    const int zoc = zo < 0 ? 0 : zo;
+    const int k = lane < KT ? lane : KT - 1;
+    const double* const tp = a.tab + L.tp();
+    double sc = 0.0;
+#pragma unroll 1
+    for (int g0 = 0; g0 < G; g0 += 4) {
+        double tv[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int g = g0 + v < G ? g0 + v : G - 1;
+            tv[v] = tp[((size_t)g * KT + k) * GM + pk_field(g * GW, GM - 1, b0, b1, b2, b3)];
+        }
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            if (g0 + v < G) sc = sc + tv[v];
+    }
+    double own = 0.0;
+    const int gmp = L.gm_pad();
+#pragma unroll 1
+    for (int g = 0; g < gmp; ++g)
+        own = own + TmL[((size_t)g * KT + zoc) * kGroupMm + pk_field(g * kGroupWm, kGroupMm - 1, b0, b1, b2, b3)];
+    if (k == zo) sc = own;
+    double m = neg_inf();
+#pragma unroll
+    for (int j = 0; j < KT; ++j) m = max_score(m, __shfl(sc, j));
+    const double u = z_uniform(p.seed, (uint64_t)(p.obs0 + i), a.sweep);
+    const double w = expw_tab(sc - m, ET);
+    double run = 0.0, cdf = 0.0;
+#pragma unroll
+    for (int j = 0; j < KT; ++j) {
+        run = run + __shfl(w, j);
+        cdf = lane == j ? run : cdf;
+    }
+    const double t = u * run;
+    int zn = (int)__popcll(__ballot(lane < KT && t >= cdf));
+    if (!(m > neg_inf())) zn = zoc;  // every category impossible: keep (or 0)
+    if (p.mode == MODE_DP && zn == K) zn = pk_dp_label(NkT, K, Kused, new_label, zo, zoc);
+    BMM_DBG_LABELS(a, true, i == a.lo, K, zn, zo);
+    count_movers(lane == 0 && zn >= 0 && zn != zo, zo, zn, b0, b1, b2, b3, hist, K, P, lane);
+    if (lane == 0) a.z_out[i] = zn;
+}
+
+template <int KT, int NT, int GW>
+__global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs a) {
+    static_assert(KT % 2 == 0 && KT <= 32, "pairs of categories, one lane per category in the exact pass");
+    constexpr int GM = 1 << GW;
+    constexpr int KP = KT / 2;                      // pairs = accumulators (two binary32 each)
+    constexpr int CH = KP <= 12 ? KP : KP / 2;      // lookups issued together
+    static_assert(KP % CH == 0, "chunking");
+    constexpr int NW = NT / 64;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const TableLayout L{p.G, KT, p.Gm, GM};
+    double* const lds = reinterpret_cast<double*>(smem);
+    const int nq_d = pk_tq_doubles(L), tail_d = L.doubles() - L.nk();
+    const volatile lds_pk_f2* const Tq = (const volatile lds_pk_f2*)lds;
+    double* const tail = lds + nq_d;
+    const int32_t* const NkT = reinterpret_cast<const int32_t*>(tail);
+    const lds_f64* const ET = (const lds_f64*)(tail + (L.et() - L.nk()));
+    const lds_f64* const TmL = (const lds_f64*)(tail + (L.tm() - L.nk()));
+    int32_t* const hist = reinterpret_cast<int32_t*>(tail + tail_d);  // [K*P] then [K]
+    const int P = p.P, G = p.G, K = p.K;
+    const int tid = threadIdx.x, lane = tid & 63;
+    int* const next_chunk = hist + K * P + K;  // LDS counters behind the histogram
+    int* const qcount = next_chunk + 1;
+    int* const queue = next_chunk + 4;
+    const int qcap = a.pk_qcap;
+    // work per wave in chunks of 64 observations, as in k_resample
+    const int64_t nchunks = (a.hi - a.lo + 63) / 64;
+    const int64_t cpw = (nchunks + gridDim.x - 1) / gridDim.x;
+    const int64_t wg_c0 = (int64_t)blockIdx.x * cpw;
+    const int64_t wg_cn = nchunks - wg_c0 < cpw ? nchunks - wg_c0 : cpw;  // chunks of this workgroup (may be <= 0)
+    const int W = (P + 31) / 32;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int64_t tile = wg_c0 + wave;
+    const bool has_tile = wave < wg_cn;
+    TilePos pos = tile_pos(a, has_tile ? tile : 0, 64, lane, lane);
+    uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+    if (has_tile) load_words(a.Xb, p.N, W, pos.ic, b0, b1, b2, b3);  // before the tables are staged
+    {
+        // stage the packed image and the tail of the table image: eight 16-byte loads in flight per lane
+        auto stage = [&](const double* from, double* to, int n2) {
+            const double2* src = reinterpret_cast<const double2*>(from);
+            double2* dst = reinterpret_cast<double2*>(to);
+            for (int i0 = tid; i0 < n2; i0 += NT * 8) {
+                double2 t[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int i = i0 + u * NT;
+                    t[u] = src[i < n2 ? i : n2 - 1];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int i = i0 + u * NT;
+                    if (i < n2) dst[i] = t[u];
+                }
+            }
+        };
+        stage(a.tab + L.doubles(), lds, nq_d / 2);
+        stage(a.tab + L.nk(), tail, tail_d / 2);
+    }
+    for (int i = tid; i < K * P + K; i += NT) hist[i] = 0;
+    if (tid == 0) { *next_chunk = NW; *qcount = 0; }
+    __syncthreads();
+
+    int Kused = 0, new_label = -1;
+    if (p.mode == MODE_DP) {
+        for (int k = 0; k < K; ++k) {
+            if (NkT[k] > 0) ++Kused;
+            else if (new_label < 0) new_label = k;
+        }
+    }
+    float unit = kPkEpsUnit;
+#ifdef BMM_DEBUG_HOOKS
+    if (a.dbg_inject & 8) unit = 0.0f;
+#endif
+
+    if (has_tile) {
+        int zo = a.z_in ? a.z_in[pos.ic] : -1;
+        asm volatile("" : "+v"(zo));  // landed before the pipeline starts (k_resample)
+        int zn_prev = 0;
+        int64_t i_prev = -1;  // < 0: nothing to store
+        for (;;) {
+            const int zoc = zo < 0 ? 0 : zo;
+            double acc_own = 0.0;
+            {
+                // the own cluster from the "minus self" tables in binary64, as in k_resample
+                uint32_t r0 = b0, r1 = b1, r2 = b2, r3 = b3;
+                constexpr int RB = kOwnSub * kGroupWm;
+                const int rounds = (p.Gm + kOwnSub - 1) / kOwnSub;
+                size_t at0 = (size_t)zoc * kGroupMm;
+#pragma unroll 1
+                for (int it = 0; it < rounds; ++it) {
+                    double ow[kOwnSub];
+#pragma unroll
+                    for (int v = 0; v < kOwnSub; ++v) {
+                        unsigned f;
+                        asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(f) : "v"(r0), "n"(v * kGroupWm), "n"(kGroupWm));
+                        ow[v] = TmL[at0 + (size_t)v * KT * kGroupMm + f];
+                    }
+                    r0 = __builtin_amdgcn_alignbit(r1, r0, RB);
+                    r1 = __builtin_amdgcn_alignbit(r2, r1, RB);
+                    r2 = __builtin_amdgcn_alignbit(r3, r2, RB);
+                    r3 >>= RB;
+                    at0 += (size_t)kOwnSub * KT * kGroupMm;
+#pragma unroll
+                    for (int v = 0; v < kOwnSub; ++v) acc_own = acc_own + ow[v];
+                }
+            }
+            if (i_prev >= 0) a.z_out[i_prev] = zn_prev;
+            int nc = 0;
+            if (lane == 0) nc = atomicAdd(next_chunk, 1);
+            nc = __builtin_amdgcn_readfirstlane(nc);
+            const int64_t next = wg_c0 + nc;
+            const bool has_next = nc < wg_cn;  // uniform
+            const TilePos npos = tile_pos(a, has_next ? next : tile, 64, lane, lane);
+            uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
+            int zo_next = -1;
+
+            // ---- scoring: (K / 2) * G conflict-free 64-bit LDS lookups, one packed add each
+            pk_f2 acc[KP];
+#pragma unroll
+            for (int j = 0; j < KP; ++j) acc[j] = pk_f2{0.0f, 0.0f};
+            __builtin_amdgcn_s_setprio(BMM_LOOKUP_PRIO);
+#pragma unroll 1
+            for (int h = 0; h < W; ++h) {
+                if (has_next && h == 0) {
+                    load_words(a.Xb, p.N, W, npos.ic, n0, n1, n2, n3);
+                    if (a.z_in) zo_next = a.z_in[npos.ic];
+                }
+                const uint32_t cur = word_of(h, b0, b1, b2, b3), nxt = word_of(h + 1, b0, b1, b2, b3);
+                const int g_lo = (32 * h + GW - 1) / GW;
+                int g_hi = (32 * (h + 1) + GW - 1) / GW;
+                g_hi = g_hi < G ? g_hi : G;
+#pragma unroll 1
+                for (int g = g_lo; g < g_hi; ++g) {
+                    const unsigned nib = __builtin_amdgcn_alignbit(nxt, cur, (unsigned)(g * GW - 32 * h)) & (unsigned)(GM - 1);
+                    const volatile lds_pk_f2* row = Tq + ((size_t)g * KP * GM + nib);
+#pragma unroll
+                    for (int c0 = 0; c0 < KP; c0 += CH) {
+                        pk_f2 tv[CH];
+#pragma unroll
+                        for (int j = 0; j < CH; ++j) tv[j] = row[(c0 + j) * GM];
+#pragma unroll
+                        for (int j = 0; j < CH; ++j) acc[c0 + j] = acc[c0 + j] + tv[j];
+                        if (CH < KP) __builtin_amdgcn_sched_barrier(0);  // keep the chunks apart
+                    }
+                }
+            }
+            __builtin_amdgcn_s_setprio(0);
+            // the binary32 scores, the observation's own cluster narrowed from its binary64 sum
+            float sc[KT];
+            const float own32 = (float)acc_own;
+            float m = -__builtin_inff();
+#pragma unroll
+            for (int k = 0; k < KT; ++k) {
+                float v = (k & 1) ? acc[k >> 1].y : acc[k >> 1].x;
+                if (k == zo) v = own32;
+                sc[k] = v;
+                m = __builtin_fmaxf(m, v);
+            }
+            const double u = z_uniform(p.seed, (uint64_t)(p.obs0 + pos.ic), a.sweep);
+            int cnt = 0;
+            bool certain = draw_pk<KT>(sc, m, u, G, unit, cnt);
+            DBG_TIER1_FORCE(a, certain);
+            const bool defer = pos.valid && !certain;
+            int zn = cnt;
+            if (p.mode == MODE_DP && zn == K) zn = pk_dp_label(NkT, K, Kused, new_label, zo, zoc);
+            // (a certain lane has a finite maximum: the "every category impossible" case is always deferred)
+            const bool keep = pos.valid && certain;
+            BMM_DBG_LABELS(a, keep, pos.i == a.lo, K, zn, zo);
+            count_movers(keep && zn >= 0 && zn != zo, zo, zn, b0, b1, b2, b3, hist, K, P, lane);
+            if (__ballot(defer)) {  // uniform, rare: into the queue, or by this wave here and now when it is full
+                const int off = (int)(pos.i - a.lo);
+                int slot = 0;
+                if (defer) slot = atomicAdd(qcount, 1);
+                const bool full = defer && slot >= qcap;
+                if (defer && !full) queue[slot] = off;
+                unsigned long long o = __ballot(full);
+                while (o) {
+                    const int src = __ffsll((long long)o) - 1;
+                    o &= o - 1;
+                    pk_exact_one<KT, GW>(p, a, L, a.lo + __builtin_amdgcn_readlane(off, src), TmL, ET, NkT, hist, Kused,
+                                         new_label, lane);
+                }
+            }
+            zn_prev = zn;
+            i_prev = keep ? pos.i : -1;
+            if (!has_next) break;
+            b0 = n0; b1 = n1; b2 = n2; b3 = n3;
+            zo = zo_next;
+            pos = npos;
+            tile = next;
+        }
+        if (i_prev >= 0) a.z_out[i_prev] = zn_prev;
+    }
+
+    __syncthreads();
+    // ---- the exact pass: the queued observations, one wave each
+    const int nqueued = *qcount < qcap ? *qcount : qcap;
+    for (int q = wave; q < nqueued; q += NW)
+        pk_exact_one<KT, GW>(p, a, L, a.lo + queue[q], TmL, ET, NkT, hist, Kused, new_label, lane);
+    __syncthreads();
+    flush_hist(hist, K, P, a.dS + (size_t)(blockIdx.x % kDeltaReps) * K * P, a.dNk + (blockIdx.x % kDeltaReps) * K, tid, NT);
+#ifdef BMM_DEBUG_HOOKS
+    if (tid == 0 && a.pk_stat) {  // test variant: draws made and observations deferred (bmm_dbg_pk_counts)
+        int64_t first = a.lo + wg_c0 * 64, last = a.lo + (wg_c0 + (wg_cn > 0 ? wg_cn : 0)) * 64;
+        last = last < a.hi ? last : a.hi;
+        if (last > first) atomicAdd(&a.pk_stat[0], (unsigned long long)(last - first));
+        atomicAdd(&a.pk_stat[1], (unsigned long long)*qcount);
+    }
+#endif
 }
 
 // ---------------------------------------------------------------------------------
