@@ -618,4 +618,85 @@ BMM_HD double group_entry(const double* e1, const double* e0, int g, int P, unsi
     return t;
 }
 
+// ---------------------------------------------------------------- count-table rules
+// The log terms of a counting chain's table image -- which category scores, the argument of each log_ and when it is
+// needed -- for the three builds that call these functions: build_tables_self (BUILD_SELF) and
+// k_state_tables (BUILD_PREDICT, BUILD_LOO).  A builder takes the raw log_ of every argument that is needed and
+// subtracts the denominators afterwards (term_of, cat_consts).  The sweep's own launches, k_count_tables and
+// k_alloc_tables, are NOT among the callers: they keep bodies of their own (kernels.hip.h says why), and whoever
+// changes a rule of the finite sweep changes it there and here.
+//   BUILD_SELF     the finite sampler's z-step image as k_count_tables writes it: a label scores when it holds a row,
+//                  the scored row's own label from the minus-self set when it holds another; denominator log(N - 1 + alpha)
+//   BUILD_PREDICT  a new row against a stored state: no minus-self set, denominator log(N + alpha); the finite sampler's
+//                  empty labels score at prior weight, the DP's are -inf (their terms are written all the same), the
+//                  DP's new cluster, category K, is log(alpha) - log(N + alpha) with the prior terms as a per-feature table
+//   BUILD_LOO      a fitted row against a stored state: BUILD_PREDICT over N - 1 rows plus the minus-self set of every
+//                  label that holds a row (a row that sat alone: prior weight, finite; -inf, DP)
+enum : int { BUILD_SELF = 0, BUILD_PREDICT = 1, BUILD_LOO = 2 };
+struct CountRule {
+    int build;     // BUILD_*
+    bool dp;       // the CRP chain (stored-state builds only): a label weighs n, category K is the new cluster
+    int K;         // labels
+    int64_t N;     // fitted rows of the whole chain
+    double beta, gamma, alpha;
+};
+BMM_HD bool rule_dp_new(const CountRule& r, int k) { return r.dp && k == r.K; }
+BMM_HD int64_t rule_rows(const CountRule& r) { return r.build == BUILD_PREDICT ? r.N : r.N - 1; }
+// category k of n rows has plain terms / a finite plain constant by its weight / minus-self terms / a minus-self constant
+BMM_HD bool rule_scores(const CountRule& r, int k, int64_t n) {
+    return r.build == BUILD_SELF ? k < r.K && n > 0 : k < r.K || rule_dp_new(r, k);
+}
+BMM_HD bool rule_weighs(const CountRule& r, int k, int64_t n) {
+    return r.build == BUILD_SELF ? rule_scores(r, k, n) : k < r.K && (!r.dp || n > 0);
+}
+BMM_HD bool rule_minus(const CountRule& r, int k, int64_t n) {
+    return r.build == BUILD_SELF ? k < r.K && n > 1 : r.build == BUILD_LOO && k < r.K && n >= 1;
+}
+BMM_HD bool rule_minus_weighs(const CountRule& r, int k, int64_t n) {
+    return r.build == BUILD_LOO && r.dp ? k < r.K && n > 1 : rule_minus(r, k, n);
+}
+
+// The constants of category k holding n rows need up to kRuleLogs logs; log j has argument `arg` and is needed when
+// this returns true (a log that is not needed counts 0).  ak: what a label's weight adds to its size, rule_ak, passed
+// in so that a caller divides once.
+//   0, 1  log(beta + gamma + n), ... with the scored row removed: the two denominators of the terms
+//   2, 3  the label's weight log(n + ak), ... with the scored row removed
+//   4     the denominator of the weights      5  log(alpha), the DP's new cluster
+constexpr int kRuleLogs = 6;
+BMM_HD double rule_ak(const CountRule& r) { return r.dp ? 0.0 : div_(r.alpha, (double)r.K); }
+BMM_HD bool const_arg(const CountRule& r, double ak, int k, int64_t n, int j, double& arg) {
+    const double bg = r.beta + r.gamma;
+    switch (j) {
+        case 0: arg = bg + (double)n; return rule_scores(r, k, n);
+        case 1: arg = bg + (double)(n - 1); return rule_minus(r, k, n);
+        case 2: arg = (double)n + ak; return rule_weighs(r, k, n);
+        case 3: arg = (double)(n - 1) + ak; return rule_minus_weighs(r, k, n);
+        case 4: arg = (double)rule_rows(r) + r.alpha; return true;
+        case 5: arg = r.alpha; return rule_dp_new(r, k);
+        default: arg = 1.0; return false;
+    }
+}
+struct CatConsts { double cp, cm, den_p, den_m; };  // the constants of the plain and the minus-self set, the denominators
+BMM_HD CatConsts cat_consts(const CountRule& r, int k, int64_t n, const double* v) {
+    CatConsts c{neg_inf(), neg_inf(), v[0], v[1]};
+    if (rule_weighs(r, k, n)) c.cp = v[2] - v[4];
+    else if (rule_dp_new(r, k)) c.cp = v[5] - v[4];
+    if (rule_minus_weighs(r, k, n)) c.cm = v[3] - v[4];
+    return c;
+}
+// The term of a feature with s ones among the category's n rows, in role 0, 1 (x = 1, x = 0 against the full
+// statistics: term_x1 / term_x0) or 2, 3 (the same with the scored row removed: it had x = 1, so s >= 1; x = 0, so
+// s <= n - 1): the argument of its one log_, and whether the term exists.  term_den: which of the two denominators
+// (logs 0 and 1 of const_arg) it is taken against.  term_of: the term from that raw log, 0 for one that does not exist.
+BMM_HD bool term_arg(const CountRule& r, int k, int role, int64_t n, int64_t s, double& arg) {
+    switch (role) {
+        case 0: arg = r.beta + (double)s; return rule_scores(r, k, n);
+        case 1: arg = (r.gamma + (double)n) - (double)s; return rule_scores(r, k, n);
+        case 2: arg = r.beta + (double)(s - 1); return rule_minus(r, k, n) && s >= 1;
+        default: arg = (r.gamma + (double)(n - 1)) - (double)s; return rule_minus(r, k, n) && s <= n - 1;
+    }
+}
+BMM_HD int term_den(int role) { return role < 2 ? 0 : 1; }
+BMM_HD double term_of(bool have, double raw, double den) { return have ? raw - den : 0.0; }
+
 }  // namespace bmm

@@ -439,25 +439,19 @@ resample_fn lookup(const KernelForm& f, bool named_size = false) {
     return fn;
 }
 
-// The predictive kernel (k_predict) by accumulator count and group width: one workgroup size, one lane per row.
-typedef void (*predict_fn)(ChainParams, PredictArgs);
-predict_fn lookup_predict(int kt, int gw) {
-    predict_fn fn = nullptr;
-    lift([&](auto KT, auto GW) { fn = k_predict<KT, kPredictThreads, GW>; }, kKT, kt, IntList<kGroupW, kGroupWAlt>{}, gw);
-    return fn;
-}
-
-// The leave-one-out kernel (k_loo) by accumulator count, group width and own-label tier (0 none: the explicit samplers,
-// 1 the minus-self tables in LDS, 2 in global memory): one workgroup size, one lane per row.  With an own-label pass
-// the kernel needs about 7.5 VGPRs per accumulator (code-object metadata: 118 at 12 accumulators, 256 at 32) and from 40
-// accumulators on would use scratch, so those forms are not instantiated: nullptr, and the chain's rows are scored by
-// k_loo_generic (loo_setup).  Without one (the explicit samplers) 64 accumulators take 191 VGPRs.
+// The scorer of stored states (k_score) by accumulator count, group width, own-label tier (0 none: the predictive, and
+// the leave-one-out of the explicit samplers; 1 the minus-self tables in LDS, 2 in global memory) and tail (the
+// predictive's or the leave-one-out's): one workgroup size, one lane per row.  With an own-label pass the kernel needs
+// about 7.5 VGPRs per accumulator (code-object metadata: 118 at 12 accumulators, 256 at 32) and from 40 accumulators on
+// would use scratch, so those forms are not instantiated: nullptr, and the chain's rows are scored by k_score_generic
+// (loo_setup).  Without one 64 accumulators take 191 VGPRs.
 constexpr int kLooMaxOwnKT = 32;
-typedef void (*loo_fn)(ChainParams, LooArgs);
-loo_fn lookup_loo(int kt, int gw, int minus) {
-    loo_fn fn = nullptr;
+typedef void (*score_fn)(ChainParams, ScoreArgs);
+score_fn lookup_score(int kt, int gw, int minus, bool loo) {
+    score_fn fn = nullptr;
     lift([&](auto KT, auto GW, auto MINUS) {
-        if constexpr (MINUS == 0 || KT <= kLooMaxOwnKT) fn = k_loo<KT, kLooThreads, GW, MINUS>;
+        if constexpr (MINUS == 0) fn = loo ? k_score<KT, kScoreThreads, GW, 0, true> : k_score<KT, kScoreThreads, GW, 0, false>;
+        else if constexpr (KT <= kLooMaxOwnKT) fn = loo ? k_score<KT, kScoreThreads, GW, MINUS, true> : nullptr;
     }, kKT, kt, IntList<kGroupW, kGroupWAlt>{}, gw, IntList<0, 1, 2>{}, minus);
     return fn;
 }
@@ -560,7 +554,7 @@ struct bmm_chain {
     double *dPredTab = nullptr, *dPredMax = nullptr, *dPredSum = nullptr, *dRespAcc = nullptr;
     bool pred_resp = false;       // the responsibilities are accumulated too
     int pred_folded = 0;          // states folded so far
-    predict_fn pfn = nullptr;
+    score_fn pfn = nullptr;
     int pred_grid_max = 0;
     size_t pred_lds = 0;
     SweepTrace pred_rec;
@@ -569,11 +563,11 @@ struct bmm_chain {
     // outputs of k_loo_finish ([kLooOut][N], then the scalars), and what a sweep folds and records (loo_rec: rows of N doubles)
     bool loo_on = false;
     double *dLooTab = nullptr, *dLooAcc = nullptr, *dLooOut = nullptr;
-    bool loo_generic = false;    // a resident shape whose rows k_loo_generic scores (lookup_loo), on scratch columns of its own
+    bool loo_generic = false;    // a resident shape whose rows k_score_generic scores (lookup_score), on scratch columns of its own
     double* dLooScratch = nullptr;
     int64_t loo_scratch_stride = 0;
     int loo_folded = 0;          // states folded so far
-    loo_fn lfn = nullptr;
+    score_fn lfn = nullptr;
     int loo_minus = 0, loo_grid_max = 0;
     size_t loo_lds = 0;
     SweepTrace loo_rec;
@@ -828,7 +822,7 @@ int group_width_rule(int sampler, int K, int P) {
     return image_bytes(geometry(sampler, P, K, kt, kGroupW), true) <= kLdsMax ? kGroupW : kGroupWAlt;
 }
 
-// threads of the generic path (k_resample_generic, k_predict_generic): a scratch column of Kc scores each
+// threads of the generic path (k_resample_generic, k_score_generic): a scratch column of Kc scores each
 int64_t generic_threads(int Kc) {
     int64_t threads = (int64_t)256 * 1024;
     const int64_t cap = ((int64_t)256 << 20) / ((int64_t)Kc * 8);  // <= 256 MiB of scratch
@@ -1168,29 +1162,41 @@ int launch_count_tables(bmm_chain* c) {
 // ---- posterior predictive of new rows ----
 // Score the chain's new rows against its current state, stream-ordered behind whatever produced that state:
 // logdens / resp receive this state's values (device, may be null); fold adds it to the accumulators.
-int enqueue_predict(bmm_chain* c, double* logdens, double* resp, bool fold) {
+// The two launches behind both: the table image of a counting chain's state (explicit samplers: the chain's own image,
+// group tables of (pi, theta) with log pi in group 0), then the scorer over a.rows rows
+int launch_score(bmm_chain* c, ScoreArgs a, bool loo) {
     const ChainParams& p = c->p;
-    if (c->predM <= 0) return BMM_OK;
-    const double* tab = c->dTab;  // stick-breaking / full: group tables of (pi, theta), log pi in group 0
+    a.tab = c->dTab;
     if (!explicit_params(p.mode)) {
-        hipLaunchKernelGGL(k_predict_tables, dim3(p.KT), dim3(256), 0, c->stream, p, c->dNk, c->dS, c->dDNk, c->dDS,
-                           c->dAlpha, c->dPredTab);
+        double* const tab = loo ? c->dLooTab : c->dPredTab;
+        if (loo) hipLaunchKernelGGL(k_state_tables<true>, dim3(p.KT), dim3(512), 0, c->stream, p, c->dNk, c->dS, c->dDNk, c->dDS, c->dAlpha, tab);
+        else hipLaunchKernelGGL(k_state_tables<false>, dim3(p.KT), dim3(256), 0, c->stream, p, c->dNk, c->dS, c->dDNk, c->dDS, c->dAlpha, tab);
         HIP_TRY(hipGetLastError());
-        tab = c->dPredTab;
+        a.tab = tab;
     }
-    PredictArgs a{};
-    a.Xb = c->dXnb; a.M = c->predM; a.tab = tab; a.logdens = logdens; a.resp = resp;
-    if (fold) { a.run_max = c->dPredMax; a.run_sum = c->dPredSum; a.resp_acc = c->pred_resp ? c->dRespAcc : nullptr; }
-    if (c->generic) {
-        const int64_t nb = (c->predM + 255) / 256, maxb = c->scratch_stride / 256;
-        hipLaunchKernelGGL(k_predict_generic, dim3((unsigned)(nb < maxb ? nb : maxb)), dim3(256), 0, c->stream, p, a,
-                           c->dScratch, c->scratch_stride);
+    if (c->generic || (loo && c->loo_generic)) {
+        double* const scr = c->generic ? c->dScratch : c->dLooScratch;
+        const int64_t stride = c->generic ? c->scratch_stride : c->loo_scratch_stride;
+        const int64_t nb = (a.rows + 255) / 256, maxb = stride / 256;
+        const dim3 grid((unsigned)(nb < maxb ? nb : maxb));
+        if (loo) hipLaunchKernelGGL(k_score_generic<true>, grid, dim3(256), 0, c->stream, p, a, scr, stride);
+        else hipLaunchKernelGGL(k_score_generic<false>, grid, dim3(256), 0, c->stream, p, a, scr, stride);
     } else {
-        const int64_t ntiles = (c->predM + kPredictThreads - 1) / kPredictThreads;
-        const int grid = (int)(ntiles < c->pred_grid_max ? ntiles : c->pred_grid_max);
-        hipLaunchKernelGGL(c->pfn, dim3(grid), dim3(kPredictThreads), c->pred_lds, c->stream, p, a);
+        const int64_t ntiles = (a.rows + kScoreThreads - 1) / kScoreThreads;
+        const int grid_max = loo ? c->loo_grid_max : c->pred_grid_max;
+        hipLaunchKernelGGL(loo ? c->lfn : c->pfn, dim3((int)(ntiles < grid_max ? ntiles : grid_max)), dim3(kScoreThreads),
+                           loo ? c->loo_lds : c->pred_lds, c->stream, p, a);
     }
     HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+int enqueue_predict(bmm_chain* c, double* logdens, double* resp, bool fold) {
+    if (c->predM <= 0) return BMM_OK;
+    ScoreArgs a{};
+    a.Xb = c->dXnb; a.rows = c->predM; a.out = logdens; a.resp = resp;
+    if (fold) { a.run_max = c->dPredMax; a.run_sum = c->dPredSum; a.resp_acc = c->pred_resp ? c->dRespAcc : nullptr; }
+    const int rc = launch_score(c, a, false);
+    if (rc) return rc;
     if (fold) c->pred_folded++;
     return BMM_OK;
 }
@@ -1204,28 +1210,11 @@ int sweep_end_predict(bmm_chain* c, int j) {
 // Score every fitted row against state j with its own contribution removed, stream-ordered behind whatever produced
 // that state: ell receives this state's values (device, may be null); fold adds them to the accumulators.
 int enqueue_loo(bmm_chain* c, int j, double* ell, bool fold) {
-    const ChainParams& p = c->p;
-    const double* tab = c->dTab;  // stick-breaking / full: group tables of (pi, theta), log pi in group 0
-    if (!explicit_params(p.mode)) {
-        hipLaunchKernelGGL(k_loo_tables, dim3(p.KT), dim3(512), 0, c->stream, p, c->dNk, c->dS, c->dDNk, c->dDS,
-                           c->dAlpha, c->dLooTab);
-        HIP_TRY(hipGetLastError());
-        tab = c->dLooTab;
-    }
-    LooArgs a{};
-    a.X = c->dX; a.Xb = c->dXb; a.N = p.N; a.z = explicit_params(p.mode) ? nullptr : label_row(c, j); a.tab = tab;
-    a.ell = ell; a.acc = fold ? c->dLooAcc : nullptr; a.n = c->loo_folded;
-    if (c->generic || c->loo_generic) {
-        double* const scr = c->generic ? c->dScratch : c->dLooScratch;
-        const int64_t stride = c->generic ? c->scratch_stride : c->loo_scratch_stride;
-        const int64_t nb = (p.N + 255) / 256, maxb = stride / 256;
-        hipLaunchKernelGGL(k_loo_generic, dim3((unsigned)(nb < maxb ? nb : maxb)), dim3(256), 0, c->stream, p, a, scr, stride);
-    } else {
-        const int64_t ntiles = (p.N + kLooThreads - 1) / kLooThreads;
-        const int grid = (int)(ntiles < c->loo_grid_max ? ntiles : c->loo_grid_max);
-        hipLaunchKernelGGL(c->lfn, dim3(grid), dim3(kLooThreads), c->loo_lds, c->stream, p, a);
-    }
-    HIP_TRY(hipGetLastError());
+    ScoreArgs a{};
+    a.X = c->dX; a.Xb = c->dXb; a.rows = c->p.N; a.z = explicit_params(c->p.mode) ? nullptr : label_row(c, j);
+    a.out = ell; a.acc = fold ? c->dLooAcc : nullptr; a.n = c->loo_folded;
+    const int rc = launch_score(c, a, true);
+    if (rc) return rc;
     if (fold) c->loo_folded++;
     return BMM_OK;
 }
@@ -2318,12 +2307,12 @@ static int sweeps_folded(bmm_chain* c, int n, SweepTrace& slot, int64_t width, d
 // the predictive kernel of the chain's shape, set up on first use
 static int pred_setup(bmm_chain* c) {
     if (c->generic || c->pfn) return BMM_OK;
-    predict_fn f = lookup_predict(c->p.KT, c->p.W);
+    score_fn f = lookup_score(c->p.KT, c->p.W, 0, false);
     if (!f) return set_err(BMM_E_STATE, "no predictive kernel for %d accumulators", c->p.KT);
     const size_t lds = (size_t)layout_of(c->p, false).head() * sizeof(double);
     if (lds > kLdsMax) return set_err(BMM_E_STATE, "the predictive table image (%zu bytes) does not fit in LDS", lds);
     int per_cu = 0;
-    const hipError_t e = kernel_fits(f, kPredictThreads, lds, &per_cu);
+    const hipError_t e = kernel_fits(f, kScoreThreads, lds, &per_cu);
     if (e != hipSuccess) return set_err(BMM_E_HIP, "kernel set-up failed: %s", hipGetErrorString(e));
     c->pfn = f;
     c->pred_lds = lds;
@@ -2536,7 +2525,7 @@ static int loo_setup(bmm_chain* c) {
     if (!c->bits)
         return set_err(BMM_E_UNSUPPORTED, "the leave-one-out predictive reads the bit planes: not offered on the int32 layout of a resident shape");
     const int minus = explicit_params(c->p.mode) ? 0 : (c->minus_in_lds ? 1 : 2);
-    loo_fn f = lookup_loo(c->p.KT, c->p.W, minus);
+    score_fn f = lookup_score(c->p.KT, c->p.W, minus, true);
     if (!f && minus != 0 && c->p.KT > kLooMaxOwnKT) {  // more accumulators than the own-label form has registers for
         int64_t stride = (c->p.N + 255) / 256 * 256;
         if (stride > generic_threads(c->p.Kc)) stride = generic_threads(c->p.Kc);
@@ -2553,7 +2542,7 @@ static int loo_setup(bmm_chain* c) {
     const size_t lds = (size_t)(minus == 1 ? l.doubles() : l.head()) * sizeof(double);
     if (lds > kLdsMax) return set_err(BMM_E_STATE, "the leave-one-out table image (%zu bytes) does not fit in LDS", lds);
     int per_cu = 0;
-    const hipError_t e = kernel_fits(f, kLooThreads, lds, &per_cu);
+    const hipError_t e = kernel_fits(f, kScoreThreads, lds, &per_cu);
     if (e != hipSuccess) return set_err(BMM_E_HIP, "kernel set-up failed: %s", hipGetErrorString(e));
     c->lfn = f;
     c->loo_minus = minus;

@@ -167,6 +167,10 @@ __device__ __forceinline__ void write_group_tables(int W, const double* e1, cons
 }
 
 constexpr int kCountTablesThreads = 576;
+// This kernel and its twin k_alloc_tables write their log terms out themselves; they do not call the count-table
+// rules of bmm_spec.h that build_tables_self and k_state_tables share.  One kernel template over those functions
+// wrote the same bits but averaged 0.2 us (4 %) more per launch (profiles/r06/README.md), and this launch sits on every
+// batch of every counting chain, so the two bodies are left as they were: separate copies of the sweep's rules.
 // MASK (feature selection): `mask` holds one inclusion bit per feature (word d / 32, bit d % 32,
 // the bits from P on zero).  An excluded feature's terms are written as 0 in all four roles -- it scores the same for
 // every category, so it drops out of the conditional -- and the DP's new-cluster term counts the included features
@@ -807,8 +811,8 @@ __device__ __forceinline__ unsigned long long diag_stamp() {
 // is 8 table launches + 8 resample launches + 1, each a few microseconds, and this form drops the 8 table launches
 // (every workgroup of a launch building the image of a bigger shape itself was measured in round 2: 8 000 logs per
 // workgroup cost six times what the launch did).  The statistics are then folded by one of the launch's own
-// workgroups (self_fold_prev, below).  Same functions, same operands, same order as k_count_tables and write_group_tables: the
-// image is bit-identical.
+// workgroups (self_fold_prev, below).  The terms and constants are those of the count-table rules (bmm_spec.h) that
+// k_count_tables evaluates, the entries those of write_group_tables: the image is bit-identical.
 // scratch (LDS, doubles): terms [K][4][P] (x=1 / x=0 against the full statistics, then with the scored
 // observation removed), logs [K][8], consts [KT][2] (Cp, Cm).
 __host__ __device__ inline size_t self_scratch_doubles(int K, int KT, int P) { return (size_t)K * 4 * P + (size_t)K * 8 + (size_t)KT * 2; }
@@ -851,10 +855,10 @@ __device__ __forceinline__ void build_tables_self(const ChainParams& p, const Re
     double* const terms = scratch;
     double* const logs = scratch + (size_t)K * 4 * P;
     double* const consts = logs + (size_t)K * 8;
-    const double alpha = *a.alpha_ptr;
-    const double bg = p.beta + p.gamma;
-    const double ak = div_(alpha, (double)K);
-    const int nterm = K * 4 * P, nitem = nterm + K * 5;
+    const CountRule r{BUILD_SELF, false, K, p.Ntot, p.beta, p.gamma, *a.alpha_ptr};  // the finite sampler's sweep
+    const double ak = rule_ak(r);
+    constexpr int kLogs = 5;  // the logs of const_arg a finite label needs (log 5 belongs to the DP's new cluster)
+    const int nterm = K * 4 * P, nitem = nterm + K * kLogs;
     // phase A: every raw log, at most two per thread, held in registers across the barrier
     constexpr int R = 2;
     double raw[R];
@@ -863,29 +867,17 @@ __device__ __forceinline__ void build_tables_self(const ChainParams& p, const Re
     for (int q = 0; q < R; ++q) {
         const int t = tid + q * NT;
         raw[q] = 0.0; have[q] = false;
+        double arg;
         if (t < nterm) {
             const int k = t / (4 * P), role = (t / P) & 3, d = t % P;
             const int64_t n = (int64_t)a.Nk[k] + delta_take(a.dNk_prev, k, K);
             const int32_t sd = a.S[(size_t)k * P + d] + delta_take(a.dS_prev, (size_t)k * P + d, KP);
-            // term_x1 / term_x0 of bmm_spec.h as k_count_tables evaluates them, the denominator subtracted below
-            if (role == 0) { have[q] = n > 0; raw[q] = have[q] ? log_(p.beta + (double)sd) : 0.0; }
-            else if (role == 1) { have[q] = n > 0; raw[q] = have[q] ? log_((p.gamma + (double)n) - (double)sd) : 0.0; }
-            else if (role == 2) { have[q] = n > 1 && sd >= 1; raw[q] = have[q] ? log_(p.beta + (double)((int64_t)sd - 1)) : 0.0; }
-            else { have[q] = n > 1 && sd <= n - 1; raw[q] = have[q] ? log_((p.gamma + (double)(n - 1)) - (double)sd) : 0.0; }
+            have[q] = term_arg(r, k, role, n, sd, arg);
+            raw[q] = have[q] ? log_(arg) : 0.0;  // the denominator is subtracted below
         } else if (t < nitem) {
-            const int k = (t - nterm) / 5, lane = (t - nterm) % 5;
+            const int k = (t - nterm) / kLogs, lane = (t - nterm) % kLogs;
             const int64_t n = (int64_t)a.Nk[k] + delta_take(a.dNk_prev, k, K);
-            double arg = 1.0;
-            bool need = false;
-            switch (lane) {  // the logs of k_count_tables' ninth wave, lanes 0-4 (5-7 belong to the DP's new cluster)
-                case 0: arg = bg + (double)n; need = n > 0; break;
-                case 1: arg = bg + (double)(n - 1); need = n > 1; break;
-                case 2: arg = (double)n + ak; need = n > 0; break;
-                case 3: arg = (double)(n - 1) + ak; need = n > 1; break;
-                case 4: arg = (double)(p.Ntot - 1) + alpha; need = true; break;
-                default: break;
-            }
-            logs[(size_t)k * 8 + lane] = need ? log_(arg) : 0.0;
+            logs[(size_t)k * 8 + lane] = const_arg(r, ak, k, n, lane, arg) ? log_(arg) : 0.0;
         }
     }
     __syncthreads();
@@ -895,7 +887,7 @@ __device__ __forceinline__ void build_tables_self(const ChainParams& p, const Re
         const int t = tid + q * NT;
         if (t < nterm) {
             const int k = t / (4 * P), role = (t / P) & 3;
-            terms[t] = have[q] ? raw[q] - logs[(size_t)k * 8 + (role < 2 ? 0 : 1)] : 0.0;
+            terms[t] = term_of(have[q], raw[q], logs[(size_t)k * 8 + term_den(role)]);
         }
     }
     for (int k = tid; k < KT; k += NT) {
@@ -903,9 +895,8 @@ __device__ __forceinline__ void build_tables_self(const ChainParams& p, const Re
         int32_t n32 = 0;
         if (k < K) {
             const int64_t n = (int64_t)a.Nk[k] + delta_take(a.dNk_prev, k, K);
-            const double* v = logs + (size_t)k * 8;
-            if (n > 0) cp = v[2] - v[4];
-            if (n > 1) cm = v[3] - v[4];
+            const CatConsts c = cat_consts(r, k, n, logs + (size_t)k * 8);
+            cp = c.cp; cm = c.cm;
             n32 = (int32_t)n;
         }
         consts[2 * k] = cp; consts[2 * k + 1] = cm;
@@ -2081,236 +2072,95 @@ __global__ __launch_bounds__(256) void k_st_perm_identity(int32_t* __restrict__ 
 // fixed order: the streaming log-sum-exp pair (run_max, run_sum) with
 //   sum_s p(x | s) = exp(run_max) * run_sum,
 // and, when asked for, the Kc running sums of the normalised category weights.
-struct PredictArgs {
-    const uint32_t* Xb;  // bit planes of the new rows
-    int64_t M;           // new rows
-    const double* tab;   // predictive table image: TableLayout without own-cluster tables (head() doubles)
-    double* logdens;     // or null: [M], log p(x_m | this state)
-    double* resp;        // or null: [Kc][M], this state's normalised category weights
-    double* run_max;     // or null (nothing is folded): [M] running maximum of logdens over the folded states
-    double* run_sum;     //   [M] sum over the folded states of exp(logdens - run_max)
-    double* resp_acc;    // or null: [Kc][M] running sums of the normalised category weights
+// Leave-one-out scores the fitted rows the same way, the row's own label from the minus-self
+// tables; its arguments ride in the same struct.
+struct ScoreArgs {
+    const uint32_t* Xb;  // bit planes of the scored rows: the new rows, or the fitted rows (null on the int32 layout)
+    int64_t rows;        // scored rows
+    const double* tab;   // counting samplers: the image k_state_tables wrote; explicit samplers: the chain's own image
+    double* out;         // or null: [rows], this state's log p(x | state) (predictive) or ell (leave-one-out)
+    // predictive
+    double* resp;        // or null: [Kc][rows], this state's normalised category weights
+    double* run_max;     // or null (nothing is folded): [rows] running maximum of logdens over the folded states
+    double* run_sum;     //   [rows] sum over the folded states of exp(logdens - run_max)
+    double* resp_acc;    // or null: [Kc][rows] running sums of the normalised category weights
+    // leave-one-out
+    const int32_t* X;    // generic path on the int32 layout: the matrix as handed over (else null)
+    const int32_t* z;    // a counting sampler: the state's labels, 0-based (else null)
+    double* acc;         // or null (nothing is folded): [kLooAcc][rows]
+    int n;               // states folded before this one
 };
 
-// The predictive image of the counting samplers from the statistics as they stand (the pending deltas are added,
-// nothing is folded or cleared: this kernel changes no state of the chain).  One workgroup per category, laid out
-// as k_count_tables lays the image out, with the predictive constants in group 0:
-//   finite sampler  label k: log(n_k + alpha/K) - log(N + alpha), an empty label included (its prior weight and the
+// The table image of the counting samplers for a stored state, from the statistics as they stand (the pending deltas
+// are added, nothing is folded or cleared: this kernel changes no state of the chain).  One workgroup per category,
+// laid out as k_count_tables lays the image out; terms and constants are the count-table rules' (bmm_spec.h):
+//   MINUS = false  BUILD_PREDICT, the predictive image of a new row (N, not N - 1: the new row is not among the N
+//                  fitted observations), the plain set only, 256 threads: roles 0, 1
+//   MINUS = true   BUILD_LOO, the leave-one-out image of the fitted rows: the plain set over N - 1 rows and the
+//                  minus-self set in groups of kGroupWm (n_k - 1 and S_kd - x_d; an entry whose bit pattern no member
+//                  of the label can have is never read), 512 threads: roles 0 to 3
+//   finite sampler  label k: log(n_k + alpha/K) - log(rows + alpha), an empty label included (its prior weight and the
 //                   prior Bernoulli terms log(beta) - log(beta + gamma), log(gamma) - log(beta + gamma))
-//   DP              used label: log(n_k) - log(N + alpha); unused label: -inf; category K, the new cluster:
-//                   log(alpha) - log(N + alpha) with the prior Bernoulli terms as a per-feature table like any other
-// (N, not N - 1: the new row is not among the N fitted observations).  Same functions as k_count_tables: log_, div_,
-// term_x1 / term_x0, group_entry.
-__global__ __launch_bounds__(256) void k_predict_tables(ChainParams p, const int32_t* __restrict__ Nk,
-                                                        const int32_t* __restrict__ S,
-                                                        const int32_t* __restrict__ dNk,
-                                                        const int32_t* __restrict__ dS,
-                                                        const double* __restrict__ alpha_ptr,
-                                                        double* __restrict__ tab) {
-    __shared__ double e1[kMaxP], e0[kMaxP], cst[2];  // cst: the constant term, log(beta + gamma + n)
+//   DP              used label: log(n_k) - log(rows + alpha); unused label: -inf; category K, the new cluster:
+//                   log(alpha) - log(rows + alpha) with the prior Bernoulli terms as a per-feature table like any other
+template <bool MINUS>
+__global__ __launch_bounds__(MINUS ? 512 : 256) void k_state_tables(ChainParams p, const int32_t* __restrict__ Nk,
+                                                                    const int32_t* __restrict__ S,
+                                                                    const int32_t* __restrict__ dNk,
+                                                                    const int32_t* __restrict__ dS,
+                                                                    const double* __restrict__ alpha_ptr,
+                                                                    double* __restrict__ tab) {
+    __shared__ double e1[kMaxP], e0[kMaxP], m1[MINUS ? kMaxP : 1], m0[MINUS ? kMaxP : 1], cst[4];  // cst: Cp, Cm, the two denominators
     const int k = blockIdx.x;
-    const TableLayout L = layout_of(p, false);
+    const TableLayout L = layout_of(p, MINUS);
     const int P = p.P, K = p.K;
     const bool is_label = k < K;
-    const bool dp_new = p.mode == MODE_DP && k == K;
     const size_t KP = (size_t)K * P;
     const int64_t n = is_label ? (int64_t)Nk[k] + delta_take(const_cast<int32_t*>(dNk), k, K) : 0;
-    const int half = threadIdx.x >> 7, dl = threadIdx.x & 127;
+    const CountRule r{MINUS ? BUILD_LOO : BUILD_PREDICT, p.mode == MODE_DP, K, p.Ntot, p.beta, p.gamma, *alpha_ptr};
+    const int role = threadIdx.x >> 7, dl = threadIdx.x & 127;
     if (threadIdx.x == 0) {
-        const double alpha = *alpha_ptr;
-        const double ldN = log_((double)p.Ntot + alpha);
-        double c = neg_inf();
-        if (is_label && p.mode == MODE_COLLAPSED) c = log_((double)n + div_(alpha, (double)K)) - ldN;
-        else if (is_label && n > 0) c = log_((double)n) - ldN;
-        else if (dp_new) c = log_(alpha) - ldN;
-        cst[0] = c;
-        cst[1] = log_((p.beta + p.gamma) + (double)n);
-        tab[L.cp() + k] = c;
-        tab[L.cm() + k] = neg_inf();
+        const double ak = rule_ak(r);  // one division; unrolled, each j is a constant and only the logs needed are taken
+        double v[kRuleLogs];
+#pragma unroll
+        for (int j = 0; j < kRuleLogs; ++j) {
+            double arg;
+            v[j] = const_arg(r, ak, k, n, j, arg) ? log_(arg) : 0.0;
+        }
+        const CatConsts c = cat_consts(r, k, n, v);
+        cst[0] = c.cp; cst[1] = c.cm; cst[2] = c.den_p; cst[3] = c.den_m;
+        tab[L.cp() + k] = c.cp;
+        tab[L.cm() + k] = c.cm;
         reinterpret_cast<int32_t*>(tab + L.nk())[k] = (int32_t)n;
     }
     __syncthreads();
-    const bool scored = is_label || dp_new;  // accumulators past Kc keep all-zero tables under a -inf constant
     for (int c0 = 0; c0 < P; c0 += kChunkP) {
         const int pc = P - c0 < kChunkP ? P - c0 : kChunkP;
-        if (dl < pc) {
-            double t = 0.0;
-            if (scored) {
-                const int d = c0 + dl;
-                const int64_t s = is_label ? (int64_t)S[(size_t)k * P + d] + delta_take(const_cast<int32_t*>(dS), (size_t)k * P + d, KP) : 0;
-                t = half == 0 ? term_x1(p.beta, s, cst[1]) : term_x0(p.gamma, n, s, cst[1]);
-            }
-            if (half == 0) e1[dl] = t; else e0[dl] = t;
+        if (dl < pc) {  // (accumulators past Kc keep all-zero tables under a -inf constant)
+            const int d = c0 + dl;
+            const int64_t s = is_label ? (int64_t)S[(size_t)k * P + d] + delta_take(const_cast<int32_t*>(dS), (size_t)k * P + d, KP) : 0;
+            double arg;
+            const bool have = term_arg(r, k, role, n, s, arg);
+            const double t = term_of(have, have ? log_(arg) : 0.0, cst[2 + term_den(role)]);
+            if (MINUS) (role == 0 ? e1 : role == 1 ? e0 : role == 2 ? m1 : m0)[dl] = t;
+            else (role == 0 ? e1 : e0)[dl] = t;
         }
         __syncthreads();
         write_group_tables(p.W, e1, e0, pc, c0, p.KT, k, cst[0], tab + L.tp());
+        if (MINUS) write_group_tables(kGroupWm, m1, m0, pc, c0, p.KT, k, cst[1], tab + L.tm());
         __syncthreads();
     }
-    if (k == 0) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];  // 256 threads
+    if (k == 0 && threadIdx.x < 256) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];
 }
 
 // one new row's share of the accumulators; ld = log p(x | state), ET the exp256 table
 template <class Tab>
-__device__ __forceinline__ void predict_fold(const PredictArgs& a, int64_t m, double ld, Tab ET) {
+__device__ __forceinline__ void predict_fold(const ScoreArgs& a, int64_t m, double ld, Tab ET) {
     const double rm = a.run_max[m], rs = a.run_sum[m];
     const bool up = ld > rm;
     const double e = expw_tab(up ? rm - ld : ld - rm, ET);  // (-inf and NaN arguments give exactly 0)
     a.run_max[m] = up ? ld : rm;
     a.run_sum[m] = up ? rs * e + 1.0 : rs + e;
-}
-
-// One lane per new row, KT accumulators, NT threads; the LDS image is the head of the table image and the exp256
-// table (no own-cluster tables, no histogram), read as k_resample reads it: one ds_read_b64 per category and
-// group, conflict-free.  The next tile's words are loaded before this tile is scored.
-constexpr int kPredictThreads = 512;
-template <int KT, int NT, int GW>
-__global__ __launch_bounds__(NT) void k_predict(ChainParams p, PredictArgs a) {
-    constexpr int GM = 1 << GW;
-    constexpr int CH = KT <= 24 ? KT : (KT <= 48 ? KT / 2 : KT / 4);  // lookups issued together
-    static_assert(KT % CH == 0, "chunking");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const TableLayout L{p.G, KT, 0, GM};
-    double* const lds = reinterpret_cast<double*>(smem);
-    const volatile lds_f64* const Tp = (const volatile lds_f64*)(lds + L.tp());
-    const lds_f64* const ET = (const lds_f64*)(lds + L.et());
-    const int P = p.P, G = p.G, Kc = p.Kc;
-    const int tid = threadIdx.x;
-    const int W = (P + 31) / 32;
-    const int64_t ntiles = (a.M + NT - 1) / NT;
-    int64_t tile = blockIdx.x;
-    uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
-    if (tile < ntiles) {  // the first tile's words go out before the image is staged
-        const int64_t m0 = tile * NT + tid;
-        load_words(a.Xb, a.M, W, m0 < a.M ? m0 : a.M - 1, b0, b1, b2, b3);
-    }
-    {
-        const double2* src = reinterpret_cast<const double2*>(a.tab);
-        double2* dst = reinterpret_cast<double2*>(smem);
-        const int n2 = L.head() / 2;  // head() is even: every piece of the layout is
-        for (int i0 = tid; i0 < n2; i0 += NT * 8) {
-            double2 t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + u * NT;
-                t[u] = src[i < n2 ? i : n2 - 1];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = i0 + u * NT;
-                if (i < n2) dst[i] = t[u];
-            }
-        }
-    }
-    __syncthreads();
-    for (; tile < ntiles; tile += gridDim.x) {
-        const int64_t m = tile * NT + tid;
-        const bool valid = m < a.M;
-        const int64_t tnext = tile + gridDim.x;
-        uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
-        if (tnext < ntiles) {
-            const int64_t mn = tnext * NT + tid;
-            load_words(a.Xb, a.M, W, mn < a.M ? mn : a.M - 1, n0, n1, n2, n3);
-        }
-        double acc[KT];
-#pragma unroll
-        for (int k = 0; k < KT; ++k) acc[k] = 0.0;
-#pragma unroll 1
-        for (int h = 0; h < W; ++h) {
-            const uint32_t cur = word_of(h, b0, b1, b2, b3), nxt = word_of(h + 1, b0, b1, b2, b3);
-            const int g_lo = (32 * h + GW - 1) / GW;
-            int g_hi = (32 * (h + 1) + GW - 1) / GW;
-            g_hi = g_hi < G ? g_hi : G;
-#pragma unroll 1
-            for (int g = g_lo; g < g_hi; ++g) {
-                const unsigned nib = __builtin_amdgcn_alignbit(nxt, cur, (unsigned)(g * GW - 32 * h)) & (unsigned)(GM - 1);
-                const volatile lds_f64* row = Tp + ((size_t)g * KT * GM + nib);
-#pragma unroll
-                for (int c0 = 0; c0 < KT; c0 += CH) {
-                    double tv[CH];
-#pragma unroll
-                    for (int j = 0; j < CH; ++j) tv[j] = row[(c0 + j) * GM];
-#pragma unroll
-                    for (int j = 0; j < CH; ++j) acc[c0 + j] = acc[c0 + j] + tv[j];
-                    if (CH < KT) __builtin_amdgcn_sched_barrier(0);  // keep the chunks apart
-                }
-            }
-        }
-        double mx = neg_inf();
-#pragma unroll
-        for (int k = 0; k < KT; ++k) mx = __builtin_fmax(mx, acc[k]);
-        double tot = 0.0;
-#pragma unroll
-        for (int k = 0; k < KT; ++k) {
-            const double w = expw_tab(acc[k] - mx, ET);
-            tot = tot + w;
-            acc[k] = w;
-            if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);  // two at a time: bounds the temporaries
-        }
-        const double ld = mx + log_(tot);
-        if (valid) {
-            if (a.logdens) a.logdens[m] = ld;
-            if (a.run_max) predict_fold(a, m, ld, ET);
-            if (a.resp || a.resp_acc) {  // uniform
-#pragma unroll
-                for (int k = 0; k < KT; ++k) {
-                    if (k < Kc) {
-                        const double r = div_(acc[k], tot);
-                        if (a.resp) a.resp[(int64_t)k * a.M + m] = r;
-                        if (a.resp_acc) a.resp_acc[(int64_t)k * a.M + m] += r;
-                    }
-                }
-            }
-        }
-        b0 = n0; b1 = n1; b2 = n2; b3 = n3;
-    }
-}
-
-// Any shape (more than kMaxCats categories or P > kMaxP: the shapes k_resample_generic takes): tables gathered from
-// global memory, the scores in a per-thread scratch column scr[k * stride + thread], as there.  Same arithmetic and
-// the same order of sums as k_predict.
-__global__ __launch_bounds__(256) void k_predict_generic(ChainParams p, PredictArgs a, double* scr, int64_t stride) {
-    const TableLayout L = layout_of(p, false);
-    const int GM = L.M;
-    const double* const Tp = a.tab + L.tp();
-    const double* const ET = a.tab + L.et();
-    const int P = p.P, G = p.G, Kc = p.Kc, KT = p.KT;
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // < stride: the host sizes the grid
-    double* const my = scr + gid;
-    for (int64_t m = gid; m < a.M; m += (int64_t)gridDim.x * blockDim.x) {
-        double mx = neg_inf();
-        for (int k0 = 0; k0 < Kc; k0 += 16) {
-            double acc[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] = 0.0;
-            for (int g = 0; g < G; ++g) {
-                const double* row = Tp + ((size_t)g * KT + k0) * GM + field_from_x(nullptr, a.Xb, a.M, P, m, g, p.W);
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    if (k0 + j < Kc) acc[j] = acc[j] + row[j * GM];
-            }
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-                if (k0 + j < Kc) {
-                    my[(int64_t)(k0 + j) * stride] = acc[j];
-                    mx = __builtin_fmax(mx, acc[j]);
-                }
-        }
-        double tot = 0.0;
-        for (int k = 0; k < Kc; ++k) {
-            const double w = expw_tab(my[(int64_t)k * stride] - mx, ET);
-            tot = tot + w;
-            my[(int64_t)k * stride] = w;
-        }
-        const double ld = mx + log_(tot);
-        if (a.logdens) a.logdens[m] = ld;
-        if (a.run_max) predict_fold(a, m, ld, ET);
-        if (a.resp || a.resp_acc)
-            for (int k = 0; k < Kc; ++k) {
-                const double r = div_(my[(int64_t)k * stride], tot);
-                if (a.resp) a.resp[(int64_t)k * a.M + m] = r;
-                if (a.resp_acc) a.resp_acc[(int64_t)k * a.M + m] += r;
-            }
-    }
 }
 
 // empty accumulators: no state folded
@@ -2340,7 +2190,7 @@ __global__ __launch_bounds__(256) void k_predict_finish(int64_t M, int Kc, int n
 // z-step of row i with its own contribution removed, normalised as the predictive is: every label scored from the
 // plain tables (constants over N - 1 fitted rows), the row's own label from the minus-self tables (n_k - 1, S_k - x_i),
 // max-shift, expw, total, ell = max + log(total).  No uniform, no draw, no histogram, no statistics.  For the explicit
-// samplers the labels do not enter and the chain's own image (log pi in group 0) is scored as k_predict scores it.
+// samplers the labels do not enter and the chain's own image (log pi in group 0) is scored as a new row is.
 // A fitted row is owned by one lane, so the seven accumulators a row keeps across sweeps are updated without atomics
 // and in a fixed order.
 constexpr int kLooAcc = 7;
@@ -2350,91 +2200,12 @@ enum : int { LOO_MAX = 0, LOO_SUM, LOO_MIN, LOO_S1, LOO_S2, LOO_MEAN, LOO_M2 };
 //                      sum_s exp(-2 ell_s) = exp(-2 MIN) * S2
 //   LOO_MEAN, LOO_M2   Welford's mean and sum of squared deviations of ell
 constexpr int kLooOut = 5;  // per-row outputs of k_loo_finish: log_cpo, ess, lppd, mean, var
-struct LooArgs {
-    const int32_t* X;    // generic path on the int32 layout: the matrix as handed over (else null)
-    const uint32_t* Xb;  // bit planes of the fitted rows (null on the int32 layout)
-    int64_t N;           // fitted rows
-    const int32_t* z;    // the state's labels, 0-based (null for the explicit samplers)
-    const double* tab;   // counting samplers: the image k_loo_tables wrote; explicit samplers: the chain's own image
-    double* ell;         // or null: [N], this state's ell
-    double* acc;         // or null (nothing is folded): [kLooAcc][N]
-    int n;               // states folded before this one
-};
-
-// The two table sets of the counting samplers from the statistics as they stand (the pending deltas are added,
-// nothing is folded or cleared: this kernel changes no state of the chain), in the TableLayout with own-cluster
-// tables at the shape's group width.  One workgroup per category; roles by thread / 128: the term of feature d for
-// x = 1 and x = 0 of the plain set (0, 1) and of the minus-self set (2, 3).
-//   plain       label k: log(n_k + alpha/K) - log(N - 1 + alpha) (finite; an empty label included, with the prior
-//               Bernoulli terms), log(n_k) - log(N - 1 + alpha) (DP; -inf when unused); the DP's new cluster, category
-//               K: log(alpha) - log(N - 1 + alpha) with the prior Bernoulli terms as a per-feature table
-//   minus-self  label k with n_k >= 1, groups of kGroupWm: the same with n_k - 1 and S_kd - x_d.  n_k = 1 gives the
-//               prior term (finite) and -inf (DP: a row that sat alone has its own label unused).  An entry whose bit
-//               pattern no member of the label can have (x_d = 1 where S_kd = 0, x_d = 0 where S_kd = n_k) is never read.
-// Same functions as k_count_tables and k_predict_tables: log_, div_, term_x1 / term_x0, group_entry.
-__global__ __launch_bounds__(512) void k_loo_tables(ChainParams p, const int32_t* __restrict__ Nk,
-                                                    const int32_t* __restrict__ S, const int32_t* __restrict__ dNk,
-                                                    const int32_t* __restrict__ dS, const double* __restrict__ alpha_ptr,
-                                                    double* __restrict__ tab) {
-    __shared__ double e1[kMaxP], e0[kMaxP], m1[kMaxP], m0[kMaxP], cst[4];  // cst: Cp, log(bg + n), Cm, log(bg + n - 1)
-    const int k = blockIdx.x;
-    const TableLayout L = layout_of(p, true);
-    const int P = p.P, K = p.K;
-    const bool is_label = k < K;
-    const bool dp_new = p.mode == MODE_DP && k == K;
-    const size_t KP = (size_t)K * P;
-    const int64_t n = is_label ? (int64_t)Nk[k] + delta_take(const_cast<int32_t*>(dNk), k, K) : 0;
-    const int role = threadIdx.x >> 7, dl = threadIdx.x & 127;
-    if (threadIdx.x == 0) {
-        const double alpha = *alpha_ptr;
-        const double ldN = log_((double)(p.Ntot - 1) + alpha);
-        const double bg = p.beta + p.gamma;
-        double cp = neg_inf(), cm = neg_inf();
-        if (is_label && p.mode == MODE_COLLAPSED) {
-            const double ak = div_(alpha, (double)K);
-            cp = log_((double)n + ak) - ldN;
-            if (n >= 1) cm = log_((double)(n - 1) + ak) - ldN;
-        } else if (is_label) {
-            if (n > 0) cp = log_((double)n) - ldN;
-            if (n > 1) cm = log_((double)(n - 1)) - ldN;
-        } else if (dp_new) {
-            cp = log_(alpha) - ldN;
-        }
-        cst[0] = cp;
-        cst[1] = log_(bg + (double)n);
-        cst[2] = cm;
-        cst[3] = n >= 1 ? log_(bg + (double)(n - 1)) : 0.0;
-        tab[L.cp() + k] = cp;
-        tab[L.cm() + k] = cm;
-        reinterpret_cast<int32_t*>(tab + L.nk())[k] = (int32_t)n;
-    }
-    __syncthreads();
-    const bool scored = is_label || dp_new;  // accumulators past Kc keep all-zero tables under a -inf constant
-    for (int c0 = 0; c0 < P; c0 += kChunkP) {
-        const int pc = P - c0 < kChunkP ? P - c0 : kChunkP;
-        if (dl < pc) {
-            const int d = c0 + dl;
-            const int64_t s = is_label ? (int64_t)S[(size_t)k * P + d] + delta_take(const_cast<int32_t*>(dS), (size_t)k * P + d, KP) : 0;
-            double t = 0.0;
-            if (role == 0) { if (scored) t = term_x1(p.beta, s, cst[1]); }
-            else if (role == 1) { if (scored) t = term_x0(p.gamma, n, s, cst[1]); }
-            else if (role == 2) { if (is_label && n >= 1 && s >= 1) t = term_x1(p.beta, s - 1, cst[3]); }
-            else { if (is_label && n >= 1 && s <= n - 1) t = term_x0(p.gamma, n - 1, s, cst[3]); }
-            (role == 0 ? e1 : role == 1 ? e0 : role == 2 ? m1 : m0)[dl] = t;
-        }
-        __syncthreads();
-        write_group_tables(p.W, e1, e0, pc, c0, p.KT, k, cst[0], tab + L.tp());
-        write_group_tables(kGroupWm, m1, m0, pc, c0, p.KT, k, cst[2], tab + L.tm());
-        __syncthreads();
-    }
-    if (k == 0 && threadIdx.x < 256) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];
-}
 
 // one fitted row's share of the accumulators; ell = this state's value, ET the exp256 table
 template <class Tab>
-__device__ __forceinline__ void loo_fold(const LooArgs& a, int64_t i, double ell, Tab ET) {
+__device__ __forceinline__ void loo_fold(const ScoreArgs& a, int64_t i, double ell, Tab ET) {
     double* const A = a.acc + i;
-    const int64_t N = a.N;
+    const int64_t N = a.rows;
     {
         const double rm = A[LOO_MAX * N], rs = A[LOO_SUM * N];
         const bool up = ell > rm;
@@ -2460,15 +2231,18 @@ __device__ __forceinline__ void loo_fold(const LooArgs& a, int64_t i, double ell
     }
 }
 
-// One lane per fitted row, KT accumulators, NT threads.  MINUS: 0 the explicit samplers (no labels, no own pass),
-// 1 the minus-self tables in LDS behind the plain ones (the LDS image is Tp + Tm + the exponential's table: no
-// histogram, no chunk counter), 2 the minus-self tables gathered from global memory (the shapes whose resample
-// kernel does the same).  The own-label score is gathered before the accumulators are live, as k_resample's own
-// pass does; the others are read with the conflict-free per-group pattern of k_predict.  The next tile's words and
-// label are loaded before this tile is scored.
-constexpr int kLooThreads = 512;
-template <int KT, int NT, int GW, int MINUS>
-__global__ __launch_bounds__(NT) void k_loo(ChainParams p, LooArgs a) {
+// The scorer of stored states.  One lane per scored row, KT accumulators, NT threads; the LDS image is the head of the
+// table image and the exp256 table (no histogram, no chunk counter), read as k_resample reads it: one ds_read_b64
+// per category and group, conflict-free.  The next tile's words (and label) are loaded before this tile is scored.
+//   LOO = false  the predictive of new rows (MINUS = 0): logdens, responsibilities, predict_fold
+//   LOO = true   the leave-one-out predictive of the fitted rows: ell, loo_fold.  MINUS: 0 the explicit samplers (no
+//                labels, no own pass), 1 the minus-self tables in LDS behind the plain ones, 2 the minus-self tables
+//                gathered from global memory (the shapes whose resample kernel does the same).  The own-label score is
+//                gathered before the accumulators are live, as k_resample's own pass does.
+constexpr int kScoreThreads = 512;
+template <int KT, int NT, int GW, int MINUS, bool LOO>
+__global__ __launch_bounds__(NT) void k_score(ChainParams p, ScoreArgs a) {
+    static_assert(LOO || MINUS == 0, "a new row has no label of its own");
     constexpr int GM = 1 << GW;
     constexpr int CH = KT <= 24 ? KT : (KT <= 48 ? KT / 2 : KT / 4);  // lookups issued together
     static_assert(KT % CH == 0, "chunking");
@@ -2479,17 +2253,17 @@ __global__ __launch_bounds__(NT) void k_loo(ChainParams p, LooArgs a) {
     const volatile lds_f64* const TmL = (const volatile lds_f64*)(lds + L.tm());
     const double* const TmG = a.tab + L.tm();
     const lds_f64* const ET = (const lds_f64*)(lds + L.et());
-    const int P = p.P, G = p.G, Gm = p.Gm, K = p.K;
+    const int P = p.P, G = p.G, Gm = p.Gm, K = p.K, Kc = p.Kc;
     const int tid = threadIdx.x;
     const int W = (P + 31) / 32;
-    const int64_t ntiles = (a.N + NT - 1) / NT;
+    const int64_t ntiles = (a.rows + NT - 1) / NT;
     int64_t tile = blockIdx.x;
     uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
     int z = -1;
     if (tile < ntiles) {  // the first tile's words go out before the image is staged
         const int64_t i0 = tile * NT + tid;
-        const int64_t ic = i0 < a.N ? i0 : a.N - 1;
-        load_words(a.Xb, a.N, W, ic, b0, b1, b2, b3);
+        const int64_t ic = i0 < a.rows ? i0 : a.rows - 1;
+        load_words(a.Xb, a.rows, W, ic, b0, b1, b2, b3);
         if (MINUS) z = a.z[ic];
     }
     {
@@ -2513,14 +2287,14 @@ __global__ __launch_bounds__(NT) void k_loo(ChainParams p, LooArgs a) {
     __syncthreads();
     for (; tile < ntiles; tile += gridDim.x) {
         const int64_t i = tile * NT + tid;
-        const bool valid = i < a.N;
+        const bool valid = i < a.rows;
         const int64_t tnext = tile + gridDim.x;
         uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
         int zn = -1;
         if (tnext < ntiles) {
             const int64_t in = tnext * NT + tid;
-            const int64_t ic = in < a.N ? in : a.N - 1;
-            load_words(a.Xb, a.N, W, ic, n0, n1, n2, n3);
+            const int64_t ic = in < a.rows ? in : a.rows - 1;
+            load_words(a.Xb, a.rows, W, ic, n0, n1, n2, n3);
             if (MINUS) zn = a.z[ic];
         }
         const bool seated = !MINUS || (unsigned)z < (unsigned)K;
@@ -2576,24 +2350,42 @@ __global__ __launch_bounds__(NT) void k_loo(ChainParams p, LooArgs a) {
         double tot = 0.0;
 #pragma unroll
         for (int k = 0; k < KT; ++k) {
-            tot = tot + expw_tab(acc[k] - mx, ET);
+            const double w = expw_tab(acc[k] - mx, ET);
+            tot = tot + w;
+            if (!LOO) acc[k] = w;  // the responsibilities' numerators
             if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);  // two at a time: bounds the temporaries
         }
         if (MINUS) tot = tot + expw_tab(ownv - mx, ET);
-        const double ell = seated ? mx + log_(tot) : qnan();  // (the host refuses a state with an unseated row)
+        const double ld = seated ? mx + log_(tot) : qnan();  // (the host refuses a state with an unseated row)
         if (valid) {
-            if (a.ell) a.ell[i] = ell;
-            if (a.acc) loo_fold(a, i, ell, ET);
+            if (a.out) a.out[i] = ld;
+            if (LOO) {
+                if (a.acc) loo_fold(a, i, ld, ET);
+            } else {
+                if (a.run_max) predict_fold(a, i, ld, ET);
+                if (a.resp || a.resp_acc) {  // uniform
+#pragma unroll
+                    for (int k = 0; k < KT; ++k) {
+                        if (k < Kc) {
+                            const double r = div_(acc[k], tot);
+                            if (a.resp) a.resp[(int64_t)k * a.rows + i] = r;
+                            if (a.resp_acc) a.resp_acc[(int64_t)k * a.rows + i] += r;
+                        }
+                    }
+                }
+            }
         }
         b0 = n0; b1 = n1; b2 = n2; b3 = n3;
         z = zn;
     }
 }
 
-// Any shape (the shapes k_resample_generic takes): tables gathered from global memory, the scores in a per-thread
-// scratch column scr[k * stride + thread], as there.  Same arithmetic and the same order of sums as k_loo.
-__global__ __launch_bounds__(256) void k_loo_generic(ChainParams p, LooArgs a, double* scr, int64_t stride) {
-    const bool has_minus = !explicit_params(p.mode);
+// Any shape (more than kMaxCats categories or P > kMaxP: the shapes k_resample_generic takes; and a counting chain's
+// leave-one-out above kLooMaxOwnKT accumulators): tables gathered from global memory, the scores in a per-thread
+// scratch column scr[k * stride + thread], as there.  Same arithmetic and the same order of sums as k_score.
+template <bool LOO>
+__global__ __launch_bounds__(256) void k_score_generic(ChainParams p, ScoreArgs a, double* scr, int64_t stride) {
+    const bool has_minus = LOO && !explicit_params(p.mode);
     const TableLayout L = layout_of(p, has_minus);
     const int GM = L.M;
     const double* const Tp = a.tab + L.tp();
@@ -2602,22 +2394,22 @@ __global__ __launch_bounds__(256) void k_loo_generic(ChainParams p, LooArgs a, d
     const int P = p.P, G = p.G, K = p.K, Kc = p.Kc, KT = p.KT;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // < stride: the host sizes the grid
     double* const my = scr + gid;
-    for (int64_t i = gid; i < a.N; i += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t i = gid; i < a.rows; i += (int64_t)gridDim.x * blockDim.x) {
         const int z = has_minus ? a.z[i] : -1;
         const bool seated = !has_minus || (unsigned)z < (unsigned)K;
         const int zc = has_minus && seated ? z : 0;
         double own = 0.0;
         if (has_minus)
             for (int g = 0; g < p.Gm; ++g)
-                own = own + Tm[((size_t)g * KT + zc) * kGroupMm + field_from_x(a.X, a.Xb, a.N, P, i, g, kGroupWm)];
-        const double ownv = has_minus && seated ? own : neg_inf();  // one more category, summed last, as in k_loo
+                own = own + Tm[((size_t)g * KT + zc) * kGroupMm + field_from_x(a.X, a.Xb, a.rows, P, i, g, kGroupWm)];
+        const double ownv = has_minus && seated ? own : neg_inf();  // one more category, summed last, as in k_score
         double mx = ownv;
         for (int k0 = 0; k0 < Kc; k0 += 16) {
             double acc[16];
 #pragma unroll
             for (int j = 0; j < 16; ++j) acc[j] = has_minus && k0 + j == z ? neg_inf() : 0.0;
             for (int g = 0; g < G; ++g) {
-                const double* row = Tp + ((size_t)g * KT + k0) * GM + field_from_x(a.X, a.Xb, a.N, P, i, g, p.W);
+                const double* row = Tp + ((size_t)g * KT + k0) * GM + field_from_x(a.X, a.Xb, a.rows, P, i, g, p.W);
 #pragma unroll
                 for (int j = 0; j < 16; ++j)
                     if (k0 + j < Kc) acc[j] = acc[j] + row[j * GM];
@@ -2630,11 +2422,25 @@ __global__ __launch_bounds__(256) void k_loo_generic(ChainParams p, LooArgs a, d
                 }
         }
         double tot = 0.0;
-        for (int k = 0; k < Kc; ++k) tot = tot + expw_tab(my[(int64_t)k * stride] - mx, ET);
+        for (int k = 0; k < Kc; ++k) {
+            const double w = expw_tab(my[(int64_t)k * stride] - mx, ET);
+            tot = tot + w;
+            if (!LOO) my[(int64_t)k * stride] = w;
+        }
         if (has_minus) tot = tot + expw_tab(ownv - mx, ET);
-        const double ell = seated ? mx + log_(tot) : qnan();
-        if (a.ell) a.ell[i] = ell;
-        if (a.acc) loo_fold(a, i, ell, ET);
+        const double ld = seated ? mx + log_(tot) : qnan();
+        if (a.out) a.out[i] = ld;
+        if (LOO) {
+            if (a.acc) loo_fold(a, i, ld, ET);
+            continue;
+        }
+        if (a.run_max) predict_fold(a, i, ld, ET);
+        if (a.resp || a.resp_acc)
+            for (int k = 0; k < Kc; ++k) {
+                const double r = div_(my[(int64_t)k * stride], tot);
+                if (a.resp) a.resp[(int64_t)k * a.rows + i] = r;
+                if (a.resp_acc) a.resp_acc[(int64_t)k * a.rows + i] += r;
+            }
     }
 }
 

@@ -1,6 +1,6 @@
 """NumPy restatement of the leave-one-out predictive of the fitted rows (include/bmm_mcmc.h),
 written from the formulas with np.log, np.logaddexp and scipy's logsumexp only -- nothing of the library's arithmetic.
-The device kernels (csrc/kernels.hip.h, k_loo_tables / k_loo / k_loo_generic / k_loo_finish / k_loo_reduce) compute
+The device kernels (csrc/kernels.hip.h, k_state_tables / k_score / k_score_generic / k_loo_finish / k_loo_reduce) compute
 the same quantities; the tests hold them to each other.
 
 For a state (labels z, statistics Nk, S, concentration alpha) and a fitted row i with label z_i:

@@ -1,7 +1,7 @@
 """NumPy restatement of the per-state posterior predictive density of a new binary row (include/bmm_mcmc.h,
 DESIGN.md section 12), written from the three formulas with np.log and np.logaddexp only -- nothing of the
 library's arithmetic (no group tables, no max-shift by hand, no table exponential).  The device kernels
-(csrc/kernels.hip.h, k_predict_tables / k_predict / k_predict_generic / k_predict_finish) compute the same
+(csrc/kernels.hip.h, k_state_tables / k_score / k_score_generic / k_predict_finish) compute the same
 quantities; the tests hold them to each other.
 
 For a state s and a new row x of P binary features:

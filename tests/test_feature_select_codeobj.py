@@ -34,7 +34,8 @@ def kernels(tmp_path_factory):
     return out
 
 
-@pytest.mark.parametrize("pattern", ["k_fs_gamma", "k_count_tablesILb1E", "k_count_tablesILb0E"])
+# the sweep's table builds: masked, unmasked, and the allocation sampler's twin
+@pytest.mark.parametrize("pattern", ["k_fs_gamma", "k_count_tablesILb1E", "k_count_tablesILb0E", "k_alloc_tables"])
 def test_no_private_segment_and_no_spills(kernels, pattern):
     names = [n for n in kernels if pattern in n]
     assert len(names) == 1, names

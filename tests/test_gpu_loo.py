@@ -82,7 +82,7 @@ def test_every_number_of_fitted_rows(sampler, K, P, N):
 @pytest.mark.parametrize("sampler,K", [("collapsed", 5), ("dp", 9)])
 def test_pending_deltas_and_several_batches_per_sweep(sampler, K):
     """batch 700 of 3000: five launches per sweep; before the first sweep the finite sampler's statistics are all
-    pending deltas (k_count_labels), and k_loo_tables reads them without folding them"""
+    pending deltas (k_count_labels), and k_state_tables reads them without folding them"""
     X, _, _, _ = synth(3000, 20, 3, seed=12)
     beta, gamma = (0.7, 0.4) if sampler == "collapsed" else (0.5, 0.5)  # (the DP sampler takes beta == gamma only)
     with _chain(sampler, X, K, batch=700, beta=beta, gamma=gamma) as c:
