@@ -22,7 +22,7 @@ __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "
            "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
            "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
            "partition_distances", "posterior_similarity", "partition_plan", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
-           "ecr_relabel", "ecr_plan", "ECR_MAX_K"]
+           "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -418,6 +418,7 @@ def partition_plan(S, N, Kc, candidates=None, criterion="binder"):
 # ---------------------------------------------------------------- relabel="ecr": relabelling from the label trace alone
 ECR_MAX_K = 128  # include/bmm_mcmc.h BMM_ECR_MAX_K
 _ECR_GIVEN, _ECR_PARTITION, _ECR_ITERATIVE = 0, 1, 2
+_ECR_MAP = 3  # ecr_pivot="map": the best state of logpost=, relabelled to after the run (not a kind of the library's)
 
 
 class _EcrOut(_C.Structure):  # bmm_ecr_out
@@ -440,11 +441,13 @@ def _ecr_pivot(ecr_pivot, N, partition):
     if isinstance(ecr_pivot, str):
         if ecr_pivot == "iterative":
             return _ECR_ITERATIVE, None
+        if ecr_pivot == "map":
+            return _ECR_MAP, None
         if ecr_pivot == "partition":
             if partition is None:
                 raise ValueError('ecr_pivot="partition" needs partition="binder" or "vi"')
             return _ECR_PARTITION, None
-        raise ValueError('ecr_pivot must be "iterative", "partition" or N labels')
+        raise ValueError('ecr_pivot must be "iterative", "partition", "map" or N labels')
     pv = _np.ascontiguousarray(ecr_pivot, dtype=_np.int32).ravel()
     if pv.shape != (N,):
         raise ValueError("ecr_pivot must have one label per observation")
@@ -564,6 +567,203 @@ def _ecr_chains(chains_out, req, K, device):
     return chains_out
 
 
+# ---------------------------------------------------------------- logpost=: log joint trace, MAP allocation, ESS, R-hat
+_LP_KEYS = ("log_lik", "log_prior", "log_hyper", "log_joint")
+
+
+def ess(x):
+    """Effective sample size of a scalar trace (NumPy, on the host): n / tau with tau from Geyer's initial monotone
+    positive sequence over FFT autocovariances.  NaN for a constant series, a series with a non-finite value, or fewer
+    than 4 values per half (n < 8)."""
+    x = _np.asarray(x, dtype=_np.float64).ravel()
+    n = x.size
+    if n < 8 or not _np.all(_np.isfinite(x)):
+        return float("nan")
+    xc = x - x.mean()
+    if not _np.any(xc != 0.0):
+        return float("nan")
+    nfft = 1 << int(2 * n - 1).bit_length()
+    f = _np.fft.rfft(xc, nfft)
+    acov = _np.fft.irfft(f * _np.conj(f), nfft)[:n] / n
+    if not acov[0] > 0.0:
+        return float("nan")
+    rho = acov / acov[0]
+    m = n // 2
+    pairs = rho[0:2 * m:2] + rho[1:2 * m:2]  # Gamma_m = rho_2m + rho_2m+1
+    neg = _np.nonzero(pairs <= 0.0)[0]
+    if neg.size:
+        pairs = pairs[:neg[0]]
+    if pairs.size == 0:
+        return float(n)
+    pairs = _np.minimum.accumulate(pairs)  # monotone
+    tau = -1.0 + 2.0 * pairs.sum()
+    return float(n / tau) if tau > 0.0 else float("nan")
+
+
+def rhat(chains):
+    """Split-R-hat (Gelman et al., BDA3) of a scalar over several chains (NumPy, on the host): every chain is cut to
+    the length of the shortest (its tail is kept) and split in two halves.  NaN for a constant series, a non-finite
+    value, or fewer than 4 values per half."""
+    xs = [_np.asarray(c, dtype=_np.float64).ravel() for c in chains]
+    if not xs:
+        return float("nan")
+    n = min(x.size for x in xs) // 2
+    if n < 4:
+        return float("nan")
+    halves = []
+    for x in xs:
+        t = x[x.size - 2 * n:]
+        halves += [t[:n], t[n:]]
+    h = _np.stack(halves)
+    if not _np.all(_np.isfinite(h)):
+        return float("nan")
+    W = h.var(axis=1, ddof=1).mean()
+    if not W > 0.0:
+        return float("nan")
+    B = n * h.mean(axis=1).var(ddof=1)
+    return float(_np.sqrt(((n - 1.0) / n * W + B / n) / W))
+
+
+def _lp_summary(rows, z):
+    """out["logpost"] from the (S, 4) rows and the label trace as sampled: rows that were not folded are NaN"""
+    lj = rows[:, 3]
+    used = _np.nonzero(~_np.isnan(lj))[0]
+    out = {k: _np.ascontiguousarray(rows[:, q]) for q, k in enumerate(_LP_KEYS)}
+    best = int(used[_np.argmax(lj[used])]) if used.size else -1  # the first maximum
+    out.update(best=best, z_map=z[best].copy() if best >= 0 else _np.full(z.shape[1], NA_INTEGER, dtype=_np.int32),
+               ess=ess(lj[used]), n_used=int(used.size))
+    return out
+
+
+class _LogPostOut(_C.Structure):  # bmm_logpost_out
+    _fields_ = [("rows", _C.c_void_p), ("z_best", _C.c_void_p), ("best_total", _C.c_void_p), ("best_row", _C.c_void_p)]
+
+
+class _LogPost:
+    """Outputs of an armed bmm_set_logpost: the run fills them (include/bmm_mcmc.h "log joint trace", DESIGN.md
+    section 20).  With several chains nothing is armed: every chain is scored afterwards (_lp_chains)."""
+
+    def __init__(self, N, S):
+        self.rows = _np.full((S, 4), _np.nan, order="F")
+        self.z = _np.full(N, NA_INTEGER, dtype=_np.int32)
+        self.total = _C.c_double(float("nan"))
+        self.best = _C.c_int(-1)
+        self.s = _LogPostOut(self.rows.ctypes.data, self.z.ctypes.data, _C.addressof(self.total), _C.addressof(self.best))
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_logpost(_C.byref(self.s)))
+
+    def result(self):
+        lj = self.rows[:, 3]
+        used = _np.nonzero(~_np.isnan(lj))[0]
+        out = {k: _np.ascontiguousarray(self.rows[:, q]) for q, k in enumerate(_LP_KEYS)}
+        out.update(best=self.best.value, z_map=self.z, ess=ess(lj[used]), n_used=int(used.size))
+        return out
+
+
+def _make_logpost(logpost, ecr_req, N, S, chains):
+    """logpost= of a wrapper (ecr_pivot="map" implies it): the outputs to arm for a single chain, True for several
+    (they are scored afterwards), None when off"""
+    if not logpost and not (ecr_req is not None and ecr_req[0] == _ECR_MAP):
+        return None
+    return True if int(chains) > 1 else _LogPost(N, S)
+
+
+def log_joint(X, z, sampler, K, alpha=1.0, beta=0.5, gamma=0.5, a=1, b=1, sample_alpha=False, k_open=None, prior_k=None,
+              mask=None, rho=0.5, device=0):
+    """The log joint rows of any stack of label rows over the data X, on the device (bmm_device_log_joint; include/bmm_mcmc.h
+    "log joint trace").  z: (S, N) labels in 1..K, as a run returns them (or one row); sampler: "collapsed", "dp",
+    "stickbreaking", "full" or "allocation"; K: K or maxK; alpha: one value or S values, the concentration after each
+    sweep (a run's out["alpha"]; the allocation sampler: a); sample_alpha: whether the chain sampled alpha, so that its
+    Gamma(a, b) prior enters log_hyper; k_open (S values) and prior_k (see log_prior_k): the allocation sampler's K
+    trace and prior; mask: (P,) or (S, P) indicators in {0, 1} with rho (one mask per call: an (S, P) trace is scored
+    row by row).  Returns {"log_lik", "log_prior", "log_hyper", "log_joint"}, each (S,).  A run's own z and alpha give
+    the run's rows bit for bit."""
+    X = _capi.as_x(X)
+    N, P = X.shape
+    z = _np.asarray(z)
+    z = _as_trace(z.reshape(1, -1) if z.ndim == 1 else z)
+    S = z.shape[0]
+    if z.shape[1] != N:
+        raise ValueError("z must have one column per observation")
+    alloc = sampler == "allocation"
+    code = 0 if alloc else _capi.SAMPLER_CODE[sampler]
+    K = int(K)
+    al = _np.ascontiguousarray(_np.broadcast_to(_np.asarray(alpha, dtype=_np.float64).ravel(), (S,)))
+    lp = ko = None
+    if alloc:
+        if k_open is None:
+            raise ValueError('sampler="allocation" needs k_open, the K trace')
+        lp = log_prior_k("poisson" if prior_k is None else prior_k, K)
+        ko = _np.ascontiguousarray(_np.broadcast_to(_np.asarray(k_open, dtype=_np.int32).ravel(), (S,)))
+    if mask is not None:
+        m = _np.asarray(mask, dtype=_np.uint8)
+        if m.ndim == 2:
+            if m.shape != (S, P):
+                raise ValueError("a mask trace must be S x P")
+            parts = [log_joint(X, z[s:s + 1], sampler, K, al[s], beta, gamma, a, b, sample_alpha,
+                               None if ko is None else ko[s:s + 1], prior_k, m[s], rho, device) for s in range(S)]
+            return {k: _np.concatenate([p_[k] for p_ in parts]) for k in _LP_KEYS}
+        m = _np.ascontiguousarray(m.ravel())
+        if m.shape != (P,):
+            raise ValueError("mask must have one indicator per feature")
+    else:
+        m = None
+    out = _np.full((S, 4), _np.nan, order="F")
+    _capi.check(_capi.lib().bmm_device_log_joint(
+        _C.c_int(device), _capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(code), _C.c_int(K), _C.c_double(beta),
+        _C.c_double(gamma), _C.c_int(1 if sample_alpha else 0), _C.c_double(a), _C.c_double(b),
+        None if lp is None else _capi.vp(lp), _capi.vp(z), _C.c_int(S), _capi.vp(al), None if ko is None else _capi.vp(ko),
+        None if m is None else _capi.vp(m), _C.c_double(rho), _capi.vp(out)))
+    return {k: _np.ascontiguousarray(out[:, q]) for q, k in enumerate(_LP_KEYS)}
+
+
+def _lp_chains(chains_out, X, sampler, K, alpha, beta, gamma, a, b, device):
+    """chains > 1: every chain object is scored through the stand-alone call (rows that are no partition -- the
+    unassigned starting state of a run without burn-in -- stay NaN) and gains "logpost", with "rhat", the split-R-hat of
+    log_joint over the chains, and "chain", the chain that holds the overall best state."""
+    sample = alpha is None or float(alpha) == 0.0
+    for o in chains_out:
+        z = o["z"]
+        S = z.shape[0]
+        keep = [s for s in range(S) if z[s].min() >= 1]
+        rows = _np.full((S, 4), _np.nan)
+        if keep:
+            r = log_joint(X, z[keep], sampler, K, o["alpha"].ravel()[keep], beta, gamma, a, b, sample, device=device)
+            for q, k in enumerate(_LP_KEYS):
+                rows[keep, q] = r[k]
+        o["logpost"] = _lp_summary(rows, z)
+    lps = [o["logpost"] for o in chains_out]
+    r = rhat([lp["log_joint"][~_np.isnan(lp["log_joint"])] for lp in lps])
+    tops = [lp["log_joint"][lp["best"]] if lp["best"] >= 0 else -_np.inf for lp in lps]
+    top = int(_np.argmax(tops))
+    for lp in lps:
+        lp.update(rhat=r, chain=top)
+    return chains_out
+
+
+def _logpost_request(logpost, ecr_req, N, S, chains):
+    """(lp, ecr_req for the run, the "map" request or None)"""
+    lp = _make_logpost(logpost, ecr_req, N, S, chains)
+    if ecr_req is not None and ecr_req[0] == _ECR_MAP:
+        return lp, None, ecr_req
+    return lp, ecr_req, None
+
+
+def _with_logpost(out, lp, ecr_map, K, device):
+    """a single chain's object: the armed outputs attached, then the relabelling to the best state"""
+    if lp is not None:
+        out["logpost"] = lp.result()
+    return out if ecr_map is None else _ecr_map([out], ecr_map, K, device)[0]
+
+
+def _ecr_map(outs, req, K, device):
+    """ecr_pivot="map": the chains' traces relabelled to the best state among them all, after the run(s)"""
+    lps = [o["logpost"] for o in outs]
+    top = lps[0].get("chain", 0)
+    return _ecr_chains(outs, (_ECR_GIVEN, _np.ascontiguousarray(lps[top]["z_map"], dtype=_np.int32), req[2]), K, device)
+
+
 # ---------------------------------------------------------------- split_merge=: Jain & Neal's move for the DP chain
 SPLIT_MERGE_SCANS = 5  # the default of split_merge_scans (DESIGN.md section 15 says where it comes from)
 _SM_FIELDS = ("split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped")
@@ -637,7 +837,7 @@ def log_prior_k(prior_k, maxK):
 
 def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, moves=1, eject_a=1.0, beta=0.5, gamma=0.5,
                      burnin=None, *, seed=None, batch=None, device=0, initial_K=None, partition=None, partition_stride=1,
-                     similarity_of=None, relabel=False, ecr_pivot="iterative", ecr_max_iter=50):
+                     similarity_of=None, relabel=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False):
     """The allocation sampler of Nobile & Fearnside (2007): the finite collapsed Beta-Bernoulli mixture with the number of
     components K unknown, 1 <= K <= maxK <= 64 (include/bmm_mcmc.h "allocation sampler").  The
     weights are Dirichlet(a, ..., a) with `a` fixed per component; `prior_k`: see log_prior_k.  A sweep is the finite
@@ -646,7 +846,8 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
     (default min(maxK, 2)) and `initial_K` (1-based labels in 1..K0; default uniform).  Returns z (S, N), theta (maxK, P,
     S) with NaN where a label is empty, K (S,), k_posterior (maxK,): the kept-sweep frequencies of K = 1..maxK, k_used
     (S,): the non-empty labels per sweep, moves: the four counts, and with `partition=` the summary of gibbs_collapsed.
-    `relabel="ecr"` is refused by the library (BMM_E_UNSUPPORTED): the relabelling assumes a fixed number of components."""
+    `relabel="ecr"` is refused by the library (BMM_E_UNSUPPORTED): the relabelling assumes a fixed number of components.
+    `logpost=True`: as gibbs_collapsed, with log p(K) and the Dirichlet(a) prior over the open labels as log_prior."""
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, maxK = int(nsamples), int(maxK)
@@ -675,6 +876,9 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
         ec.arm()  # the library refuses the run
     if pt is not None:
         pt.arm()
+    lj = _LogPost(N, S) if logpost else None
+    if lj is not None:
+        lj.arm()
     _capi.check(_capi.lib().bmm_alloc_run(
         _capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(maxK), _C.c_double(a),
         _C.c_double(beta), _C.c_double(gamma), _capi.vp(lp), _C.c_int(K0), _C.c_int(int(moves)), _C.c_double(eject_a),
@@ -685,6 +889,8 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
            "moves": dict(zip(_EA_FIELDS, (int(v) for v in counts)))}
     if pt is not None:
         out["partition"] = pt.result()
+    if lj is not None:
+        out["logpost"] = lj.result()
     return out
 
 
@@ -779,7 +985,7 @@ class _Init:
         return info.as_dict()
 
 
-def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None):
+def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None, lp=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
@@ -793,6 +999,8 @@ def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=
         loo.arm()
     if ecr is not None:
         ecr.arm()
+    if lp is not None:
+        lp.arm()
     if init is not None:  # last, just ahead of the call: a run of another sampler refuses an armed start
         init.arm()
     if pr is None:
@@ -951,7 +1159,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                     initial_K=None, chains=1, devices=None, stephens=None, newdata=None, predictive_trace=False,
                     responsibilities=False, partition=None, partition_stride=1, similarity_of=None, loo=False,
                     select_features=False, rho=0.5, init="random", init_iters=INIT_ITERS, ecr_pivot="iterative",
-                    ecr_max_iter=50):
+                    ecr_max_iter=50, logpost=False):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -1002,6 +1210,14 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     a stephens="device" run (`permutations`, `z`, `theta` relabelled, `z_original`, `theta_original`) plus `ecr = {"agree",
     "pivot", "iterations", "converged", "n_used"}`.  With `chains > 1` the chains' traces are stacked and relabelled to one
     common pivot (for "partition" the pooled estimate), so their `theta` can be averaged across chains.
+    `logpost=True`: the result gains `logpost = {"log_lik", "log_prior", "log_hyper", "log_joint": (S,), "best", "z_map":
+    (N,), "ess", "n_used"}` -- the log joint of the state after every kept sweep, computed on the device from the folded
+    counts (include/bmm_mcmc.h "log joint trace"), the row of its first maximum and that row's
+    labels (the MAP allocation among the kept states; a row of `z_original` under a relabelling: the values are those
+    of the state as sampled), the effective sample size of log_joint (ess()) and the rows used (without burn-in row 0,
+    the starting state, is NaN and never best).  With `chains > 1` every chain is scored afterwards and every object
+    also gains "rhat", the split-R-hat of log_joint over the chains (rhat()), and "chain", the chain holding the overall
+    best state.  `ecr_pivot="map"` relabels to that state (over several chains the overall best) and implies logpost.
     """
     X = _capi.as_x(data)
     N, P = X.shape
@@ -1018,13 +1234,14 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, False, newdata, loo)
     lo = _make_loo(loo, N, nsamples - burnin, chains, False)
+    lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
 
     def done(out):
         if fs is not None:
             out["features"] = fs.result()
         if ini is not None:
             out["init"] = ini.result()
-        return out
+        return _with_logpost(out, lp, ecr_map, K, device)
     if chains > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
@@ -1039,8 +1256,12 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
         z0s = [_np.ascontiguousarray(_np.random.default_rng(seed + c).integers(1, K + 1, N), dtype=_np.int32)
                for c in range(chains)] if initial_K is None else [_np.ascontiguousarray(z, dtype=_np.int32) for z in initial_K]
         dev0 = device if devices is None else int(devices[0])
-        outs = _ecr_chains(_pooled(_multi("collapsed", X, chains, devices, z0s, None, None, nsamples, K, alpha, beta, gamma, a, b,
-                           burnin, batch, seed, False), partition, partition_stride, similarity_of, dev0), ecr_req, K, dev0)
+        outs = _multi("collapsed", X, chains, devices, z0s, None, None, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, False)
+        if lp is not None:
+            _lp_chains(outs, X, "collapsed", K, alpha, beta, gamma, a, b, dev0)
+        outs = _ecr_chains(_pooled(outs, partition, partition_stride, similarity_of, dev0), ecr_req, K, dev0)
+        if ecr_map is not None:
+            outs = _ecr_map(outs, ecr_map, K, dev0)
         if ini is not None:
             for o, info in zip(outs, infos):
                 o["init"] = info
@@ -1062,7 +1283,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
                 _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini)
+            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini, lp=lp)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
@@ -1074,7 +1295,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
             _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1086,7 +1307,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
              burnrelabel=50, maxK=30, debug=False, *, seed=None, batch=None, device=0, chains=1, devices=None,
              stephens=None, newdata=None, predictive_trace=False, responsibilities=False, partition=None,
              partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None,
-             select_features=False, rho=0.5, init="random", ecr_pivot="iterative", ecr_max_iter=50):
+             select_features=False, rho=0.5, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
@@ -1094,7 +1315,8 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     second, each with `split_merge_scans` intermediate restricted scans (default SPLIT_MERGE_SCANS); the result gains
     `split_merge = {"split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped"}`.  Per chain.
     `select_features`, `rho`: as gibbs_collapsed (needs beta == gamma; not with split_merge=).  `init`: "random" only (a
-    DP run seats its rows in its first sweep; Chain.init_labels re-seats a resident DP chain)."""
+    DP run seats its rows in its first sweep; Chain.init_labels re-seats a resident DP chain).  `logpost`,
+    `ecr_pivot="map"`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
     X = _capi.as_x(data)
     N, P = X.shape
@@ -1107,19 +1329,23 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     lo = _make_loo(loo, N, nsamples - burnin, chains, False)
     fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, True, newdata, loo, split_merge)
     sm = _make_split_merge(split_merge, split_merge_scans, chains)
+    lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
 
     def done(out):
         if sm is not None:
             out["split_merge"] = sm.result()
         if fs is not None:
             out["features"] = fs.result()
-        return out
+        return _with_logpost(out, lp, ecr_map, maxK, device)
     if int(chains) > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
         dev0 = device if devices is None else int(devices[0])
-        return _ecr_chains(_pooled(_multi("dp", X, int(chains), devices, None, None, None, nsamples, maxK, alpha, beta, gamma, a, b,
-                           burnin, batch, seed, False), partition, partition_stride, similarity_of, dev0), ecr_req, maxK, dev0)
+        outs = _multi("dp", X, int(chains), devices, None, None, None, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, False)
+        if lp is not None:
+            _lp_chains(outs, X, "dp", maxK, alpha, beta, gamma, a, b, dev0)
+        outs = _ecr_chains(_pooled(outs, partition, partition_stride, similarity_of, dev0), ecr_req, maxK, dev0)
+        return outs if ecr_map is None else _ecr_map(outs, ecr_map, maxK, dev0)
     S = nsamples - burnin
     W = _clamp_burnrelabel(burnrelabel, burnin)
     if _device_relabel(stephens, relabel, burnin, W):
@@ -1133,7 +1359,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                 _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
                 _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs)
+            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs, lp=lp)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, maxK, P, S)
@@ -1146,7 +1372,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec)
+        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1157,7 +1383,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
 def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, burnin, relabel, burnrelabel, seed,
               device, initial_pi, initial_theta, chains, devices, stephens, debug=False, newdata=None,
               predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None,
-              loo=False, ecr_pivot="iterative", ecr_max_iter=50):
+              loo=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False):
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, K = int(nsamples), int(K)
@@ -1168,7 +1394,11 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     lo = _make_loo(loo, N, nsamples - burnin, chains, True)
+    lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
     base = fn[len("bmm_"):-len("_run_probs")]
+
+    def done(out):
+        return _with_logpost(out, lp, ecr_map, K, device)
 
     def start(sd, pi, th):
         rng = _np.random.default_rng(sd)
@@ -1191,9 +1421,12 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
         st = [start(seed + c, initial_pi[c] if initial_pi is not None else None,
                     initial_theta[c] if initial_theta is not None else None) for c in range(chains)]
         dev0 = device if devices is None else int(devices[0])
-        return _ecr_chains(_pooled(_multi(sampler, X, chains, devices, None, [p for p, _ in st], [t for _, t in st], nsamples, K,
-                           alpha, beta, gamma, a, b, burnin, None, seed, True), partition, partition_stride, similarity_of, dev0),
-                           ecr_req, K, dev0)
+        outs = _multi(sampler, X, chains, devices, None, [p for p, _ in st], [t for _, t in st], nsamples, K, alpha, beta, gamma, a, b,
+                      burnin, None, seed, True)
+        if lp is not None:
+            _lp_chains(outs, X, sampler, K, alpha, beta, gamma, a, b, dev0)
+        outs = _ecr_chains(_pooled(outs, partition, partition_stride, similarity_of, dev0), ecr_req, K, dev0)
+        return outs if ecr_map is None else _ecr_map(outs, ecr_map, K, dev0)
     on_device = _device_relabel(stephens, relabel, burnin, W)
     pi0, th0 = start(seed, initial_pi, initial_theta)
     if on_device:
@@ -1207,8 +1440,8 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
                 _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
                 _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run(base, args, pr, rel=dr, part=pt, loo=lo)
-        return _with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo)
+            rc = _run(base, args, pr, rel=dr, part=pt, loo=lo, lp=lp)
+        return done(_with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
     z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
@@ -1220,43 +1453,44 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
             _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec)
+        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec, lp=lp)
     out = {"pi": pi, "alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
-        return _with_predictive(rl.finish(rc, out), pr, pt, lo)
+        return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
     _capi.check(rc)
-    return _with_predictive(out if ec is None else ec.finish(out), pr, pt, lo)
+    return done(_with_predictive(out if ec is None else ec.finish(out), pr, pt, lo))
 
 
 def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
                         relabel=False, burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None,
                         initial_theta=None, chains=1, devices=None, stephens=None, newdata=None,
                         predictive_trace=False, responsibilities=False, partition=None, partition_stride=1,
-                        similarity_of=None, loo=False, init="random", ecr_pivot="iterative", ecr_max_iter=50):
+                        similarity_of=None, loo=False, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
     src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
-    "random" only (the sampler starts from pi and theta)."""
+    "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`: as gibbs_collapsed; log_prior is
+    the stick-breaking prior with the sticks integrated out, which depends on the order of the labels."""
     _init_kind(init, 0, allowed=False)
     return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
                      burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter)
+                     ecr_max_iter, logpost)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
                burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None, initial_theta=None, chains=1,
                devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False,
                partition=None, partition_stride=1, similarity_of=None, loo=False, init="random", ecr_pivot="iterative",
-               ecr_max_iter=50):
+               ecr_max_iter=50, logpost=False):
     """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
-    "random" only (the sampler starts from pi and theta)."""
+    "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
     return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
                      relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter)
+                     ecr_max_iter, logpost)
 
 
 class Chain:
@@ -1497,6 +1731,34 @@ class Chain:
         _capi.check(_capi.lib().bmm_chain_loo_reset(self._h))
 
     # -- split-merge moves of a DP chain (include/bmm_mcmc.h)
+    def set_logpost(self, on=True):
+        """Arm (or disarm) the log joint trace and the keep-best state (include/bmm_mcmc.h "log joint trace", DESIGN.md
+        section 20).  Arming an armed chain empties the best state."""
+        _capi.check(_capi.lib().bmm_chain_set_logpost(self._h, _C.c_int(1 if on else 0)))
+
+    def logpost_state(self):
+        """{"log_lik", "log_prior", "log_hyper", "log_joint"} of the current state: no sweep, the best state untouched"""
+        out = (_C.c_double * 4)()
+        _capi.check(_capi.lib().bmm_chain_logpost_state(self._h, out))
+        return dict(zip(_LP_KEYS, (float(v) for v in out)))
+
+    def sweeps_logpost(self, n, trace=False):
+        """n more sweeps, each offered to the keep-best state; trace=True returns their (n, 4) rows (log_lik, log_prior,
+        log_hyper, log_joint) and waits"""
+        rows = _np.full((int(n), 4), _np.nan, order="F") if trace else None
+        _capi.check(_capi.lib().bmm_chain_sweeps_logpost(self._h, _C.c_int(int(n)), _capi.vp(rows) if trace else None))
+        return rows
+
+    def best(self):
+        """{"z_map": (N,) 1-based labels of the best folded state, "log_joint", "sweep"}"""
+        z = _np.empty(self.N, dtype=_np.int32)
+        total, sweep = _C.c_double(0.0), _C.c_int(-1)
+        _capi.check(_capi.lib().bmm_chain_get_best(self._h, _capi.vp(z), _C.byref(total), _C.byref(sweep)))
+        return {"z_map": z, "log_joint": total.value, "sweep": sweep.value}
+
+    def logpost_reset(self):
+        _capi.check(_capi.lib().bmm_chain_logpost_reset(self._h))
+
     def set_split_merge(self, moves_per_sweep, scans=SPLIT_MERGE_SCANS):
         """`moves_per_sweep` moves at the start of every sweep from the second (0: off), `scans` intermediate scans each."""
         _capi.check(_capi.lib().bmm_chain_set_split_merge(self._h, _C.c_int(int(moves_per_sweep)), _C.c_int(int(scans))))

@@ -42,6 +42,8 @@ SYMBOLS = [
     "bmm_chain_set_alloc", "bmm_chain_set_k", "bmm_chain_get_k", "bmm_chain_alloc", "bmm_chain_alloc_step",
     "bmm_chain_alloc_stats", "bmm_alloc_run",
     "bmm_device_ecr", "bmm_device_ecr_plan", "bmm_set_ecr_relabel",
+    "bmm_chain_set_logpost", "bmm_chain_logpost_state", "bmm_chain_sweeps_logpost", "bmm_chain_get_best",
+    "bmm_chain_logpost_reset", "bmm_set_logpost", "bmm_device_log_joint",
 ]
 
 

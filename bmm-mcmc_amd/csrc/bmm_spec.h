@@ -699,4 +699,117 @@ BMM_HD bool term_arg(const CountRule& r, int k, int role, int64_t n, int64_t s, 
 BMM_HD int term_den(int role) { return role < 2 ? 0 : 1; }
 BMM_HD double term_of(bool have, double raw, double den) { return have ? raw - den : 0.0; }
 
+// ---------------------------------------------------------------- log joint of a state
+// log p(x, z, alpha, mask) of the state after a sweep from its folded counts (include/bmm_mcmc.h "log joint trace";
+// DESIGN.md section 20): the pieces k_log_joint and k_log_joint_finish call, and log_joint_spec, the whole statement
+// in their order for the host.  THE ORDER, a pure function of (K, P, mask):
+//   a label's likelihood   kLjLanes partial sums, included feature d in partial d mod kLjLanes, ascending in d, each
+//                          from 0; the partials folded by a binary tree (partial t takes partial t + o, o = kLjLanes/2
+//                          .. 1); lgamma_(beta + gamma + n_k) once per label, subtracted per cell
+//   the pooled term        (a mask only) the excluded features the same way, feature d against (N, T_d)
+//   the totals             from 0, ascending in k: the likelihood of every label that holds a row, then the pooled term;
+//                          the labels' prior terms the same way, then the model's head added to that sum
+//   the row                {log_lik, log_prior, log_hyper, (log_lik + log_prior) + log_hyper}
+constexpr int kLjLanes = 256;
+enum : int { LJ_FINITE = 0, LJ_DP = 1, LJ_SB = 2, LJ_ALLOC = 3 };
+struct LjModel {
+    int kind;            // LJ_*: which prior on z (the collapsed and the full sampler share LJ_FINITE)
+    int K;               // labels (K or maxK)
+    int k_open;          // LJ_ALLOC: the open labels; else K
+    int P;
+    int64_t N;
+    double beta, gamma;
+    double alpha;        // the concentration after the sweep; LJ_ALLOC: a, the per-component parameter
+    int sample_alpha;    // the chain samples alpha: its Gamma(a, b) prior enters log_hyper
+    double a, b;
+    double log_pk;       // LJ_ALLOC: log p(K = k_open)
+    int masked;          // the chain has a feature mask: the pooled term and the mask's prior enter
+    double rho;
+    int p_in;            // included features (P without a mask)
+};
+BMM_HD bool lj_included(const uint32_t* mask, int d) { return !mask || ((mask[d >> 5] >> (d & 31)) & 1u); }
+BMM_HD double lj_lb0(double beta, double gamma) { return (lgamma_(beta) + lgamma_(gamma)) - lgamma_(beta + gamma); }
+// one cell: s ones among the n rows of a label (or T_d among all N); lgden = lgamma_(beta + gamma + n)
+BMM_HD double lj_cell(double beta, double gamma, int64_t n, int64_t s, double lgden, double lb0) {
+    return ((lgamma_(beta + (double)s) + lgamma_((gamma + (double)n) - (double)s)) - lgden) - lb0;
+}
+// whether label k of n rows enters the sums, and its prior term; n_after: the rows of the labels above k (LJ_SB)
+BMM_HD bool lj_label_lik(const LjModel& m, int k, int64_t n) { return k < m.k_open && n > 0; }
+BMM_HD bool lj_label_prior(const LjModel& m, int k, int64_t n) {
+    return m.kind == LJ_SB ? k < m.K - 1 : lj_label_lik(m, k, n);
+}
+BMM_HD double lj_prior_term(const LjModel& m, int64_t n, int64_t n_after) {
+    switch (m.kind) {
+        case LJ_FINITE: { const double ak = div_(m.alpha, (double)m.K); return lgamma_(ak + (double)n) - lgamma_(ak); }
+        case LJ_DP: return lgamma_((double)n);
+        case LJ_SB: return lbeta_(1.0 + (double)n, m.alpha + (double)n_after) - lbeta_(1.0, m.alpha);
+        default: return lgamma_(m.alpha + (double)n) - lgamma_(m.alpha);
+    }
+}
+// the row from the per-label values: lik[k], prior[k] (read only where the label enters), nk[k], pooled (a mask only)
+template <class NkOf>
+BMM_HD void lj_finish(const LjModel& m, const double* lik, const double* prior, NkOf nk, double pooled, double out[4]) {
+    double ll = 0.0, lp = 0.0;
+    int used = 0;
+    for (int k = 0; k < m.K; ++k) {
+        const int64_t n = nk(k);
+        if (lj_label_lik(m, k, n)) { ll = ll + lik[k]; ++used; }
+        if (lj_label_prior(m, k, n)) lp = lp + prior[k];
+    }
+    if (m.masked) ll = ll + pooled;
+    const double N = (double)m.N;
+    if (m.kind == LJ_FINITE) lp = (lgamma_(m.alpha) - lgamma_(m.alpha + N)) + lp;
+    else if (m.kind == LJ_DP) lp = ((double)used * log_(m.alpha) + lp) + (lgamma_(m.alpha) - lgamma_(m.alpha + N));
+    else if (m.kind == LJ_ALLOC) {
+        const double ka = (double)m.k_open * m.alpha;
+        lp = (m.log_pk + (lgamma_(ka) - lgamma_(ka + N))) + lp;
+    }
+    double lh = 0.0;
+    if (m.sample_alpha) lh = ((m.a * log_(m.b) - lgamma_(m.a)) + (m.a - 1.0) * log_(m.alpha)) - m.b * m.alpha;
+    if (m.masked) lh = lh + ((double)m.p_in * log_(m.rho) + (double)(m.P - m.p_in) * log_(1.0 - m.rho));
+    out[0] = ll; out[1] = lp; out[2] = lh; out[3] = (ll + lp) + lh;
+}
+// The whole statement for the host: Nk[K], S[K * P] (S[k * P + d]), mask words or null; scratch: 2 K doubles.
+inline void log_joint_spec(const LjModel& m, const int32_t* Nk, const int32_t* S, const uint32_t* mask, double* scratch,
+                           double out[4]) {
+    const double lb0 = lj_lb0(m.beta, m.gamma), bg = m.beta + m.gamma;
+    double* const lik = scratch;
+    double* const prior = scratch + m.K;
+    double part[kLjLanes];
+    auto tree = [&part]() {
+        for (int o = kLjLanes / 2; o > 0; o >>= 1)
+            for (int t = 0; t < o; ++t) part[t] = part[t] + part[t + o];
+        return part[0];
+    };
+    for (int k = 0; k < m.K; ++k) {
+        const int64_t n = Nk[k];
+        lik[k] = 0.0; prior[k] = 0.0;
+        if (lj_label_lik(m, k, n)) {
+            const double lgden = lgamma_(bg + (double)n);
+            for (int t = 0; t < kLjLanes; ++t) part[t] = 0.0;
+            for (int d = 0; d < m.P; ++d)
+                if (lj_included(mask, d)) part[d % kLjLanes] = part[d % kLjLanes] + lj_cell(m.beta, m.gamma, n, S[(size_t)k * m.P + d], lgden, lb0);
+            lik[k] = tree();
+        }
+        if (lj_label_prior(m, k, n)) {
+            int64_t after = 0;
+            for (int l = k + 1; l < m.K; ++l) after += Nk[l];
+            prior[k] = lj_prior_term(m, n, after);
+        }
+    }
+    double pooled = 0.0;
+    if (m.masked) {
+        const double lgden = lgamma_(bg + (double)m.N);
+        for (int t = 0; t < kLjLanes; ++t) part[t] = 0.0;
+        for (int d = 0; d < m.P; ++d) {
+            if (lj_included(mask, d)) continue;
+            int64_t T = 0;
+            for (int k = 0; k < m.K; ++k) T += S[(size_t)k * m.P + d];
+            part[d % kLjLanes] = part[d % kLjLanes] + lj_cell(m.beta, m.gamma, m.N, T, lgden, lb0);
+        }
+        pooled = tree();
+    }
+    lj_finish(m, lik, prior, [Nk](int k) { return (int64_t)Nk[k]; }, pooled, out);
+}
+
 }  // namespace bmm

@@ -25,6 +25,7 @@
 #include <condition_variable>
 #include <exception>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -617,6 +618,16 @@ struct bmm_chain {
     int ea_tag = -1;
     uint32_t ea_ctr = 0;
     SweepTrace k_rec;  // a run: one int32 per kept sweep, K after it
+    // log joint trace and keep-best allocation: one block holds the labels' values between the two
+    // launches, the row of the last state scored and the keep-best cell; dLjZ the N labels of the best folded state
+    // (0-based); lp_rec: the sweeps that are folded and the rows of four doubles they are recorded in
+    bool lp_on = false;
+    char* dLjBlock = nullptr;
+    double *dLjLik = nullptr, *dLjPrior = nullptr, *dLjOut = nullptr;
+    LjBest* dLjBest = nullptr;
+    int32_t* dLjZ = nullptr;
+    int lp_folded = 0;  // states folded so far
+    SweepTrace lp_rec;
     int prof = 0;             // > 0: HIP events around the resample launches of every prof-th sweep
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
@@ -686,7 +697,7 @@ int run_rows_out(const bmm_chain* c, const double* dtrace, int64_t width, double
 }
 
 // What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_loo_summary,
-// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel; bmm_alloc_run fills `alloc` for its own run), and what a
+// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost; bmm_alloc_run fills `alloc` for its own run), and what a
 // *_run_predict / *_run_relabel / *_run_probs entry point was handed.
 struct RunOptions {
     struct { bool on = false; bmm_partition_out o{}; } partition;
@@ -695,6 +706,7 @@ struct RunOptions {
     struct { bool on = false; bmm_feature_out o{}; } fs;
     struct { int kind = 0, iters = 0; } init;
     struct { bool on = false; bmm_ecr_out o{}; } ecr;
+    struct { bool on = false; bmm_logpost_out o{}; } logpost;
     struct { bool on = false; const double* log_prior_k = nullptr; int K0 = 0, moves = 0; double eject_a = 1.0; int32_t* k_out = nullptr; int64_t* moves_out = nullptr; } alloc;
     const bmm_relabel_hooks* hooks = nullptr;  // *_run_probs
     const bmm_relabel_out* rel = nullptr;      // *_run_relabel
@@ -1218,11 +1230,49 @@ int enqueue_loo(bmm_chain* c, int j, double* ell, bool fold) {
     if (fold) c->loo_folded++;
     return BMM_OK;
 }
-// the end of sweep j: what a predictive run, a leave-one-out run or the resident calls asked to fold
+// ---- log joint trace and keep-best allocation ----
+// Score the chain's state after sweep j from its statistics as they stand, stream-ordered behind whatever produced
+// them: the row goes to dLjOut and to `row` (device, may be null); fold also offers the state to the keep-best cell
+// and, when it won, copies its labels.
+LjArgs lj_args(bmm_chain* c) {
+    const ChainParams& p = c->p;
+    LjArgs a{};
+    a.Nk = c->dNk; a.S = c->dS; a.dNk = c->dDNk; a.dS = c->dDS;
+    a.mask = c->fs_mask ? c->dFsMask : nullptr;
+    a.alpha_ptr = c->dAlpha;
+    a.k_open = c->alloc_on ? c->dEaK : nullptr;
+    a.log_prior_k = c->alloc_on ? c->dEaLogPrior : nullptr;
+    a.lik = c->dLjLik; a.prior = c->dLjPrior; a.out = c->dLjOut; a.best = c->dLjBest;
+    a.rho = c->fs_rho;
+    a.kind = c->alloc_on ? LJ_ALLOC : (p.mode == MODE_DP ? LJ_DP : (p.mode == MODE_SB ? LJ_SB : LJ_FINITE));
+    return a;
+}
+int launch_log_joint(bmm_chain* c, const LjArgs& a) {
+    const ChainParams& p = c->p;
+    hipLaunchKernelGGL(k_log_joint, dim3((unsigned)(p.K + (a.mask ? 1 : 0))), dim3(kLjLanes), 0, c->stream, p, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_log_joint_finish, dim3(1), dim3(64), 0, c->stream, p, a);
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+int enqueue_log_joint(bmm_chain* c, int j, double* row, bool fold) {
+    LjArgs a = lj_args(c);
+    a.out_row = row; a.sweep = j; a.fold = fold ? 1 : 0;
+    const int rc = launch_log_joint(c, a);
+    if (rc || !fold) return rc;
+    const int64_t nb = (c->p.N + 255) / 256;
+    hipLaunchKernelGGL(k_log_joint_keep, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, c->stream,
+                       (const LjBest*)c->dLjBest, (const int32_t*)label_row(c, j), c->p.N, c->dLjZ);
+    HIP_TRY(hipGetLastError());
+    c->lp_folded++;
+    return BMM_OK;
+}
+// the end of sweep j: what a predictive run, a leave-one-out run, a log joint trace or the resident calls asked to fold
 int sweep_end_folds(bmm_chain* c, int j) {
-    const int rc = sweep_end_predict(c, j);
-    if (rc || !c->loo_rec.folds(j) || !c->loo_on) return rc;
-    return enqueue_loo(c, j, c->loo_rec.row<double>(j), true);
+    int rc = sweep_end_predict(c, j);
+    if (rc == BMM_OK && c->loo_rec.folds(j) && c->loo_on) rc = enqueue_loo(c, j, c->loo_rec.row<double>(j), true);
+    if (rc == BMM_OK && c->lp_rec.folds(j) && c->lp_on) rc = enqueue_log_joint(c, j, c->lp_rec.row<double>(j), true);
+    return rc;
 }
 
 // what the predictive, the leave-one-out summary and the split-merge moves answer a chain with a feature mask
@@ -1848,7 +1898,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     dev_pool().put(c->device, c->run_arena, c->run_arena_bytes);
     void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
                     c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch, c->dSmSide, c->dSmSideLaunch, c->dSmLq, c->dSmStat, c->dSmCell,
-                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide};
+                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dLjBlock, c->dLjZ};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     chain_stream_release(c->device, c->stream, c->stream_kind);  // synchronised above
@@ -2704,6 +2754,240 @@ static int loo_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, in
     if (!o.loo.on) return rc;
     rc = rec.end_run(rc);
     return rc == BMM_OK ? loo_run_out(c, o.loo.o, rec.rows.as<double>()) : rc;
+}
+
+// ---- log joint trace and keep-best allocation ----
+static int lp_refused(const bmm_chain* c) {
+    if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the log joint is not offered on a sharded chain: a shard holds a part of the counts");
+    return BMM_OK;
+}
+static int lp_armed(const bmm_chain* c) {
+    if (!c->lp_on) return set_err(BMM_E_STATE, "the log joint trace is not armed (bmm_chain_set_logpost)");
+    return BMM_OK;
+}
+// a state every row of which is seated, as the leave-one-out summary asks
+static int lp_seated(const bmm_chain* c) {
+    if (c->p.mode != MODE_COLLAPSED && c->sweep < 1)
+        return set_err(BMM_E_STATE, "no row has a label before the first sweep: this state has no log joint");
+    return BMM_OK;
+}
+static int lp_reset(bmm_chain* c) {
+    c->lp_folded = 0;
+    const LjBest empty{-std::numeric_limits<double>::infinity(), -1, 0};
+    HIP_TRY(hipMemcpyAsync(c->dLjBest, &empty, sizeof empty, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // `empty` goes out of scope
+    return BMM_OK;
+}
+// the block behind the scoring launches (any chain may be scored) and, for a chain that keeps its best state, the labels
+static int lp_setup(bmm_chain* c, bool keep) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->dLjBlock) {
+        const size_t K = (size_t)c->p.K;
+        auto carve = [&](Carver& v) {
+            c->dLjLik = v.take<double>(K + 1);
+            c->dLjPrior = v.take<double>(K);
+            c->dLjOut = v.take<double>(4);
+            c->dLjBest = v.take<LjBest>(1);
+        };
+        Carver measure{nullptr};
+        carve(measure);
+        HIP_TRY(hipMalloc(&c->dLjBlock, measure.used));
+        Carver real{c->dLjBlock};
+        carve(real);
+        HIP_TRY(hipMemsetAsync(c->dLjBlock, 0, measure.used, c->stream));
+        const int rc = lp_reset(c);
+        if (rc) return rc;
+    }
+    if (keep && !c->dLjZ) {
+        const int rc = pred_room((size_t)c->p.N * sizeof(int32_t), "the labels of the best state (N int32)");
+        if (rc) return rc;
+        HIP_TRY(hipMalloc(&c->dLjZ, (size_t)c->p.N * sizeof(int32_t)));
+        HIP_TRY(hipMemsetAsync(c->dLjZ, 0xff, (size_t)c->p.N * sizeof(int32_t), c->stream));  // -1: no state yet
+    }
+    return BMM_OK;
+}
+
+int bmm_chain_set_logpost(bmm_chain* c, int on) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        int rc = lp_refused(c);
+        if (rc) return rc;
+        if (!on) { c->lp_on = false; return BMM_OK; }  // the best state stays readable
+        rc = lp_setup(c, true);
+        if (rc) return rc;
+        if (c->lp_on) return lp_reset(c);
+        c->lp_on = true;
+        return lp_reset(c);
+    });
+}
+
+int bmm_chain_logpost_state(bmm_chain* c, double out[4]) {
+    return guarded([&]() -> int {
+        if (!c || !out) return set_err(BMM_E_ARG, "null argument");
+        int rc = lp_refused(c);
+        if (rc == BMM_OK) rc = lp_seated(c);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        if (!c->started) { rc = chain_start(c); if (rc) return rc; }
+        rc = lp_setup(c, false);
+        if (rc == BMM_OK) rc = enqueue_log_joint(c, c->sweep, nullptr, false);
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+        const hipError_t e = hipMemcpyAsync(out, c->dLjOut, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess || e2 != hipSuccess) return set_err(BMM_E_HIP, "copying the log joint failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_sweeps_logpost(bmm_chain* c, int n, double* trace) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (n < 0) return set_err(BMM_E_ARG, "n must be >= 0");
+        int rc = lp_refused(c);
+        if (rc == BMM_OK) rc = lp_armed(c);
+        if (rc) return rc;
+        return sweeps_folded(c, n, c->lp_rec, 4, trace, "the log joint trace (n x 4 doubles)");
+    });
+}
+
+int bmm_chain_get_best(bmm_chain* c, int32_t* z1, double* total, int* sweep) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (!c->dLjZ) return set_err(BMM_E_STATE, "the log joint trace was never armed on this chain (bmm_chain_set_logpost)");
+        if (c->lp_folded < 1) return set_err(BMM_E_STATE, "no state has been folded yet (bmm_chain_sweeps_logpost)");
+        HIP_TRY(hipSetDevice(c->device));
+        LjBest h{};
+        hipError_t e = hipMemcpyAsync(&h, c->dLjBest, sizeof h, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && z1) e = hipMemcpyAsync(z1, c->dLjZ, (size_t)c->p.N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess || e2 != hipSuccess) return set_err(BMM_E_HIP, "reading the best state failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        if (z1) for (int64_t i = 0; i < c->p.N; ++i) z1[i] = z1[i] < 0 ? BMM_NA_INTEGER : z1[i] + 1;
+        if (total) *total = h.sweep < 0 ? std::nan("") : h.total;
+        if (sweep) *sweep = h.sweep;
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_logpost_reset(bmm_chain* c) {
+    if (!c) return set_err(BMM_E_ARG, "null chain");
+    int rc = lp_armed(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return lp_reset(c);
+}
+
+// ... of a run: armed for it, every kept sweep folded as it is enqueued (sweep_end_folds)
+static int lp_run_attach(bmm_chain* c, const RunOptions& o, Recording& rec) {
+    if (!o.logpost.on) return BMM_OK;
+    int rc = bmm_chain_set_logpost(c, 1);
+    if (rc == BMM_OK && o.logpost.o.rows) rc = rec.alloc((size_t)c->S * 4 * sizeof(double), "the log joint trace (S x 4 doubles)");
+    if (rc) return rc;
+    rec.begin(c, c->lp_rec, 4 * sizeof(double), c->burnin, run_first_fold(c), true);
+    return BMM_OK;
+}
+static int lp_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, int rc) {
+    if (!o.logpost.on) return rc;
+    rc = rec.end_run(rc);
+    if (rc) return rc;
+    const bmm_logpost_out& out = o.logpost.o;
+    if (c->lp_folded < 1) {  // a run of one kept row without burn-in: the starting state alone
+        if (out.z_best) for (int64_t i = 0; i < c->p.N; ++i) out.z_best[i] = BMM_NA_INTEGER;
+        if (out.best_total) *out.best_total = std::nan("");
+        if (out.best_row) *out.best_row = -1;
+    } else {
+        int sweep = -1;
+        rc = bmm_chain_get_best(c, out.z_best, out.best_total, &sweep);
+        if (rc) return rc;
+        if (out.best_row) *out.best_row = sweep < 0 ? -1 : sweep - c->burnin;
+    }
+    return out.rows ? run_rows_out(c, rec.rows.as<double>(), 4, out.rows) : BMM_OK;
+}
+
+// The log joint of any stack of label rows over the same data, on a transient chain: X packed once, then per state the
+// labels uploaded, the statistics recounted (k_count_labels_generic) and the state scored by the launches of a chain.
+static int lj_check_labels(const int32_t* z, int S, int64_t N, int K, const int32_t* k_open) {
+    for (int s = 0; s < S; ++s) {
+        const int top = k_open ? k_open[s] : K;
+        if (top < 1 || top > K) return set_err(BMM_E_ARG, "k_open[%d] = %d lies outside 1..%d", s, top, K);
+        for (int64_t i = 0; i < N; ++i) {
+            const int32_t v = z[(size_t)s + (size_t)i * (size_t)S];
+            if (v < 1 || v > top)
+                return set_err(BMM_E_ARG, "z[%d, %lld] = %d is not a label in 1..%d (row %d, observation %lld, both 0-based)", s, (long long)i, (int)v, top, s, (long long)i);
+        }
+    }
+    return BMM_OK;
+}
+int bmm_device_log_joint(int device, const int32_t* X, int64_t N, int P, int sampler, int K, double beta, double gamma,
+                         int sample_alpha, double a, double b, const double* log_prior_k, const int32_t* z, int S,
+                         const double* alpha, const int32_t* k_open, const uint8_t* mask, double rho, double* out) {
+    return guarded([&]() -> int {
+        if (!X || !z || !alpha || !out) return set_err(BMM_E_ARG, "null argument");
+        if (S < 1) return set_err(BMM_E_ARG, "S must be >= 1");
+        if (sampler < 0 || sampler > 3) return set_err(BMM_E_ARG, "unknown sampler %d", sampler);
+        if ((log_prior_k != nullptr) != (k_open != nullptr)) return set_err(BMM_E_ARG, "log_prior_k and k_open go together (the allocation sampler)");
+        if (log_prior_k && sampler != BMM_SAMPLER_COLLAPSED) return set_err(BMM_E_ARG, "the allocation sampler is the finite collapsed sampler with K unknown");
+        if (mask && explicit_params(sampler)) return set_err(BMM_E_UNSUPPORTED, "a feature mask is offered for the collapsed and DP samplers only");
+        if (mask && !(rho > 0.0 && rho < 1.0)) return set_err(BMM_E_ARG, "rho must lie strictly inside (0, 1)");
+        int rc = check_common(N, P, K, beta, gamma);
+        if (rc) return rc;
+        for (int s = 0; s < S; ++s)
+            if (!(alpha[s] > 0.0) || !(alpha[s] < 1e300)) return set_err(BMM_E_ARG, "alpha[%d] must be > 0 and finite", s);
+        rc = lj_check_labels(z, S, N, K, k_open);
+        if (rc) return rc;
+        bmm_chain* c = nullptr;
+        rc = bmm_chain_create(&c, sampler, N, P, K, 1.0, beta, gamma, a, b, 0, 0, device);
+        if (rc) return rc;
+        struct Guard { bmm_chain* c; ~Guard() { bmm_chain_destroy(c); } } guard{c};
+        c->p.sample_alpha = sample_alpha != 0;
+        rc = bmm_chain_set_data_host(c, X);
+        if (rc == BMM_OK) rc = lp_setup(c, false);
+        if (rc) return rc;
+        const size_t Kz = (size_t)K, KP = Kz * (size_t)P, W = ((size_t)P + 31) / 32;
+        DevBuf dmask, dk, dlp;
+        LjArgs args = lj_args(c);
+        if (mask) {
+            std::vector<uint32_t> words(W, 0u);
+            for (int d = 0; d < P; ++d) {
+                if (mask[d] > 1) return set_err(BMM_E_ARG, "mask[%d] = %d is neither 0 nor 1", d, (int)mask[d]);
+                words[(size_t)d >> 5] |= (uint32_t)mask[d] << (d & 31);
+            }
+            HIP_TRY(dmask.alloc(W * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpy(dmask.p, words.data(), W * sizeof(uint32_t), hipMemcpyHostToDevice));
+            args.mask = dmask.as<uint32_t>();
+            args.rho = rho;
+        }
+        if (log_prior_k) {
+            HIP_TRY(dk.alloc(sizeof(int32_t)));
+            HIP_TRY(dlp.alloc(Kz * sizeof(double)));
+            HIP_TRY(hipMemcpy(dlp.p, log_prior_k, Kz * sizeof(double), hipMemcpyHostToDevice));
+            args.k_open = dk.as<int32_t>();
+            args.log_prior_k = dlp.as<double>();
+            args.kind = LJ_ALLOC;
+        }
+        HIP_TRY(hipMemsetAsync(c->dDNk, 0, Kz * kDeltaReps * sizeof(int32_t), c->stream));
+        HIP_TRY(hipMemsetAsync(c->dDS, 0, KP * kDeltaReps * sizeof(int32_t), c->stream));
+        std::vector<int32_t> row((size_t)N);
+        const int64_t nb = (N + 255) / 256;
+        for (int s = 0; s < S; ++s) {
+            for (int64_t i = 0; i < N; ++i) row[(size_t)i] = z[(size_t)s + (size_t)i * (size_t)S] - 1;
+            HIP_TRY(hipMemcpyAsync(c->dZ[0], row.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->dAlpha, alpha + s, sizeof(double), hipMemcpyHostToDevice, c->stream));
+            if (k_open) HIP_TRY(hipMemcpyAsync(dk.p, k_open + s, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipMemsetAsync(c->dNk, 0, Kz * sizeof(int32_t), c->stream));
+            HIP_TRY(hipMemsetAsync(c->dS, 0, KP * sizeof(int32_t), c->stream));
+            hipLaunchKernelGGL(k_count_labels_generic, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, c->stream, c->p, c->dX, c->dXb,
+                               (const int32_t*)c->dZ[0], c->dNk, c->dS);
+            HIP_TRY(hipGetLastError());
+            rc = launch_log_joint(c, args);
+            if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+            double h[4];
+            const hipError_t e = hipMemcpyAsync(h, c->dLjOut, sizeof h, hipMemcpyDeviceToHost, c->stream);
+            const hipError_t e2 = hipStreamSynchronize(c->stream);  // `row` is written again
+            if (e != hipSuccess || e2 != hipSuccess) return set_err(BMM_E_HIP, "scoring state %d failed: %s", s, hipGetErrorString(e != hipSuccess ? e : e2));
+            for (int q = 0; q < 4; ++q) out[(size_t)s + (size_t)q * (size_t)S] = h[q];
+        }
+        return BMM_OK;
+    });
 }
 
 // ---- split-merge moves ----
@@ -4431,14 +4715,16 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             if (rc) return rc;
             clock.lap(0);
             // what the options record per kept sweep: each ends, and waits for the stream before its rows go, on every way out
-            Recording pred_rec, loo_rec, fs_rec, k_rec;
+            Recording pred_rec, loo_rec, fs_rec, k_rec, lp_rec;
             rc = pred_run_attach(c, opts, pred_rec);
             if (rc == BMM_OK) rc = loo_run_attach(c, opts, loo_rec);
             if (rc == BMM_OK) rc = sm_run_attach(c, opts);
             if (rc == BMM_OK) rc = fs_run_attach(c, opts, fs_rec);
             if (rc == BMM_OK) rc = alloc_run_attach(c, opts, k_rec);
+            if (rc == BMM_OK) rc = lp_run_attach(c, opts, lp_rec);
             if (rc) return rc;
             rc = run_body(c, nsamples, io, opts);
+            rc = lp_run_collect(c, opts, lp_rec, rc);
             rc = sm_run_collect(c, opts, rc);
             rc = alloc_run_collect(c, opts, k_rec, rc);
             rc = fs_run_collect(c, opts, fs_rec, rc);
@@ -4800,6 +5086,12 @@ int bmm_set_feature_select(const bmm_feature_out* out) {
 int bmm_set_loo_summary(const bmm_loo_out* out) {
     g_armed.loo.on = out != nullptr;
     if (out) g_armed.loo.o = *out;
+    return BMM_OK;
+}
+
+int bmm_set_logpost(const bmm_logpost_out* out) {
+    g_armed.logpost.on = out != nullptr;
+    if (out) g_armed.logpost.o = *out;
     return BMM_OK;
 }
 

@@ -3826,4 +3826,122 @@ __global__ void k_test_lgamma(const double* in, double* out, int64_t n) {
     if (i < n) out[i] = lgamma_(in[i]);
 }
 
+// ---- log joint trace and keep-best allocation (include/bmm_mcmc.h "log joint trace") --------
+// The log joint of the chain's state from its integer statistics, in the order bmm_spec.h states (log_joint_spec is
+// the same statement for the host).  k_log_joint: one workgroup of kLjLanes threads per label and, with a mask, one
+// more for the pooled term of the excluded features; thread t adds the cells of features t, t + kLjLanes, ... in
+// ascending order, the partials are folded by a binary tree in LDS, thread 0 writes the label's total and its prior
+// term.  The statistics are read as they stand, pending deltas added and nothing cleared (as k_state_tables reads
+// them), so a finite chain before its first sweep is scored from its delta replicas.  No X is read: both layouts, any
+// P, up to kMaxCatsAny labels.  k_log_joint_finish: one lane adds the labels' values in ascending order, writes the
+// row and, when the state is folded, decides `improved` for the keep-best cell; k_log_joint_keep then copies the
+// label row only when `improved` is set -- stream-ordered behind the lane that wrote it, so no block reads a cell
+// another is writing.  Nothing is atomic in global memory: one state gives the same bits twice.
+struct LjBest {
+    double total;      // the largest log_joint folded so far (-inf: none)
+    int32_t sweep;     // the sweep it belongs to (-1: none)
+    int32_t improved;  // whether the last folded state replaced it
+};
+struct LjArgs {
+    const int32_t *Nk, *S, *dNk, *dS;  // the chain's statistics and their delta replicas
+    const uint32_t* mask;              // [ceil(P / 32)] words, or null: no feature mask
+    const double* alpha_ptr;
+    const int32_t* k_open;             // the allocation sampler's open label count, or null
+    const double* log_prior_k;         // ... and its log p(K), K = 1 .. maxK
+    double *lik, *prior;               // [K + 1], [K]: the labels' values between the two launches (lik[K]: the pooled term)
+    double* out;                       // [4]: the row
+    double* out_row;                   // or null: [4], this sweep's row of a trace
+    LjBest* best;                      // the keep-best cell
+    double rho;
+    int kind;                          // LJ_*
+    int sweep, fold;
+};
+__device__ __forceinline__ LjModel lj_model_of(const ChainParams& p, const LjArgs& a) {
+    LjModel m;
+    m.kind = a.kind; m.K = p.K; m.k_open = a.k_open ? *a.k_open : p.K; m.P = p.P; m.N = p.N;
+    m.beta = p.beta; m.gamma = p.gamma; m.alpha = *a.alpha_ptr; m.sample_alpha = p.sample_alpha; m.a = p.a; m.b = p.b;
+    m.log_pk = 0.0; m.masked = a.mask != nullptr; m.rho = a.rho; m.p_in = p.P;
+    return m;
+}
+__global__ __launch_bounds__(kLjLanes) void k_log_joint(ChainParams p, LjArgs a) {
+    __shared__ double part[kLjLanes];
+    __shared__ double sh_c[2];  // lgamma_(beta + gamma + n), lB(beta, gamma)
+    __shared__ unsigned long long sh_after;
+    const int K = p.K, P = p.P, tid = threadIdx.x, k = blockIdx.x;
+    const size_t KP = (size_t)K * P;
+    const LjModel m = lj_model_of(p, a);
+    const bool pooled = k == K;  // (launched with a mask only)
+    const int64_t n = pooled ? p.N : (int64_t)a.Nk[k] + delta_take(const_cast<int32_t*>(a.dNk), k, K);
+    const bool lik_on = pooled || lj_label_lik(m, k, n);  // uniform over the workgroup
+    if (tid == 0) {
+        sh_after = 0ull;
+        if (lik_on) { sh_c[0] = lgamma_((p.beta + p.gamma) + (double)n); sh_c[1] = lj_lb0(p.beta, p.gamma); }
+    }
+    __syncthreads();
+    double acc = 0.0;
+    if (lik_on) {
+        const double lgden = sh_c[0], lb0 = sh_c[1];
+        for (int d = tid; d < P; d += kLjLanes) {
+            if (lj_included(a.mask, d) == pooled) continue;
+            int64_t s = 0;
+            if (!pooled) {
+                s = (int64_t)a.S[(size_t)k * P + d] + delta_take(const_cast<int32_t*>(a.dS), (size_t)k * P + d, KP);
+            } else {
+                for (int l = 0; l < K; ++l)
+                    s += (int64_t)a.S[(size_t)l * P + d] + delta_take(const_cast<int32_t*>(a.dS), (size_t)l * P + d, KP);
+            }
+            acc = acc + lj_cell(p.beta, p.gamma, n, s, lgden, lb0);
+        }
+    }
+    part[tid] = acc;
+    // the rows of the labels above k (the stick-breaking prior): an integer, so the order of the adds is free
+    const bool prior_on = !pooled && lj_label_prior(m, k, n);
+    if (prior_on && m.kind == LJ_SB) {
+        unsigned long long after = 0ull;
+        for (int l = k + 1 + tid; l < K; l += kLjLanes)
+            after += (unsigned long long)((int64_t)a.Nk[l] + delta_take(const_cast<int32_t*>(a.dNk), l, K));
+        if (after) atomicAdd(&sh_after, after);  // LDS
+    }
+    __syncthreads();
+    for (int o = kLjLanes / 2; o > 0; o >>= 1) {
+        if (tid < o) part[tid] = part[tid] + part[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        a.lik[k] = part[0];
+        if (!pooled) a.prior[k] = prior_on ? lj_prior_term(m, n, (int64_t)sh_after) : 0.0;
+    }
+}
+struct LjNkOf {
+    const int32_t *Nk, *dNk;
+    int K;
+    __device__ int64_t operator()(int k) const { return (int64_t)Nk[k] + delta_take(const_cast<int32_t*>(dNk), k, K); }
+};
+__global__ __launch_bounds__(64) void k_log_joint_finish(ChainParams p, LjArgs a) {
+    if (threadIdx.x != 0) return;
+    LjModel m = lj_model_of(p, a);
+    if (a.log_prior_k) m.log_pk = a.log_prior_k[m.k_open - 1];
+    if (a.mask) {
+        int in = 0;
+        for (int w = 0; w < (p.P + 31) / 32; ++w) in += __popc(a.mask[w] & init_word_mask(p.P, w));
+        m.p_in = in;
+    }
+    double row[4];
+    lj_finish(m, a.lik, a.prior, LjNkOf{a.Nk, a.dNk, p.K}, a.mask ? a.lik[p.K] : 0.0, row);
+    for (int q = 0; q < 4; ++q) {
+        a.out[q] = row[q];
+        if (a.out_row) a.out_row[q] = row[q];
+    }
+    if (a.fold) {
+        const bool improved = row[3] > a.best->total;  // strict: the earliest sweep wins a tie, a NaN never wins
+        a.best->improved = improved ? 1 : 0;
+        if (improved) { a.best->total = row[3]; a.best->sweep = a.sweep; }
+    }
+}
+__global__ __launch_bounds__(256) void k_log_joint_keep(const LjBest* __restrict__ best, const int32_t* __restrict__ z,
+                                                        int64_t N, int32_t* __restrict__ z_best) {
+    if (!best->improved) return;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) z_best[i] = z[i];
+}
+
 }  // namespace bmm

@@ -956,6 +956,87 @@ typedef struct bmm_ecr_out {
 } bmm_ecr_out;
 int bmm_set_ecr_relabel(const bmm_ecr_out* out);
 
+/* ---- log joint trace and keep-best (MAP) allocation ------------------------------------------
+ * The number every MCMC user plots first: log p(x, z, alpha, mask) of the state after a kept sweep, from the integer
+ * statistics the sweep end has folded -- no pass over X.  n_k, s_kd: the folded counts of the state after kept sweep j;
+ * alpha_j: the concentration after that sweep's update (the value in the alpha trace row); lgamma, log: the spec's lgamma_
+ * and log_ (bmm_spec.h), the same bits on host and device; lB0 = lgamma(beta) + lgamma(gamma) - lgamma(beta + gamma).
+ *   log_lik    log p(x | z), theta integrated out -- for all five samplers, the explicit ones included, from the counts:
+ *              the sum over the labels k with n_k > 0 and the features d of
+ *                ((lgamma(beta + s_kd) + lgamma((gamma + n_k) - s_kd)) - lgamma(beta + gamma + n_k)) - lB0.
+ *              An empty label is skipped, not added as a zero (the per-cell term of the feature-selection step).  With a
+ *              feature mask an excluded feature contributes, once instead of per label, the pooled term of that section:
+ *              the same expression with (N, T_d), T_d = sum_k s_kd.
+ *   log_prior  log p(z | alpha_j):
+ *                collapsed, full  lgamma(alpha) - lgamma(alpha + N) + sum_{k: n_k > 0} [lgamma(alpha/K + n_k) - lgamma(alpha/K)]
+ *                                 -- the Dirichlet-multinomial MODEL, as the predictive and leave-one-out sections use it,
+ *                                 not the finite sampler's quirk that an emptied label stays empty for ever;
+ *                dp               K+ log(alpha) + sum_{n_k > 0} lgamma(n_k) + lgamma(alpha) - lgamma(alpha + N), K+ the labels in use;
+ *                                 the probability of the PARTITION (over the 877 partitions of 7 rows it sums to 1): every
+ *                                 numbering of its blocks within the maxK labels has this same value;
+ *                stick-breaking   sum_{k < K-1} [lbeta(1 + n_k, alpha + n_{>k}) - lbeta(1, alpha)], n_{>k} the rows of the labels
+ *                                 above k: the sticks integrated out.  It DEPENDS ON THE ORDER OF THE LABELS;
+ *                allocation       log p(K) + lgamma(K a) - lgamma(K a + N) + sum_{k < K, n_k > 0} [lgamma(a + n_k) - lgamma(a)],
+ *                                 K the open label count on the device, a the chain's per-component parameter.
+ *   log_hyper  a log(b) - lgamma(a) + (a - 1) log(alpha) - b alpha when the chain samples alpha (created with alpha = 0), else 0;
+ *              with a feature mask plus sum_d [gamma_d log rho + (1 - gamma_d) log(1 - rho)] = P_in log rho + (P - P_in) log(1 - rho),
+ *              rho as last given to bmm_chain_set_feature_select (1/2 for a mask that was only ever set by hand).
+ *   log_joint  (log_lik + log_prior) + log_hyper.
+ * A row of output is these four doubles, in this order.
+ * THE ORDER OF THE SUMS is a pure function of (K, P, mask); bmm_spec.h carries it once for host and device (the pieces
+ * lj_cell, lj_prior_term, lj_finish; log_joint_spec is the whole statement for the host).  One workgroup per label: lane t
+ * of 256 adds the cells of the included features t, t + 256, ... in ascending order from 0, and the 256 partial sums are
+ * folded by a binary tree in LDS (partial t takes partial t + o, o = 128 .. 1); lgamma(beta + gamma + n_k) is computed once
+ * per label and subtracted per cell; with a mask one more workgroup sums the pooled terms of the excluded features the
+ * same way.  One lane then adds, from 0 and ascending in k, the totals of the labels that hold a row and last the pooled
+ * term; the labels' prior terms the same way, and the model's head to that sum: (lgamma(alpha) - lgamma(alpha + N)) + sum;
+ * (K+ log(alpha) + sum) + (lgamma(alpha) - lgamma(alpha + N)); (log p(K) + (lgamma(K a) - lgamma(K a + N))) + sum.
+ * log_hyper is ((a log(b) - lgamma(a)) + (a - 1) log(alpha)) - b alpha, then plus the mask's term.  Nothing is atomic
+ * in global memory: one state gives the same bits twice.  The statistics are read as they stand, pending deltas added
+ * and nothing cleared, so a finite chain is scored before its first sweep too; no X is read, so both layouts, the
+ * generic path, any P and up to 1024 labels are served.
+ * KEEP-BEST: a cell on the device holds {best_total, best_sweep, improved}.  The lane that writes a folded row sets
+ * improved = total > best_total -- strict, so the earliest sweep wins a tie and a NaN never wins -- and a second launch
+ * copies the N labels of that sweep into the chain's best-state row only when improved is set.  Stream-ordered: a folded
+ * sweep adds no synchronisation and no host-device copy, an armed chain that is not folding enqueues what an unarmed
+ * one does.  The best state is the maximum a posteriori allocation among the folded states, the standard ECR pivot.
+ * Refused: a sharded chain with BMM_E_UNSUPPORTED; a DP, stick-breaking or full chain before its first sweep (rows
+ * without a label) with BMM_E_STATE, and the chain stays usable. */
+/* arm (allocates N int32 and a few doubles per label; arming an armed chain empties the best state) or disarm (the
+ * best state stays readable) */
+int bmm_chain_set_logpost(bmm_chain* c, int on);
+/* the row of the current state, once: no sweep, the best state untouched; needs no arming.  Waits. */
+int bmm_chain_logpost_state(bmm_chain* c, double out[4]);
+/* n more sweeps of an armed chain, each folded; trace n x 4 column-major (then the call waits) or NULL (then it returns
+ * without waiting, as bmm_chain_sweeps) */
+int bmm_chain_sweeps_logpost(bmm_chain* c, int n, double* trace);
+/* the best folded state: its labels (N int32, 1-based, or NULL), its log_joint and the sweep it followed.  Waits. */
+int bmm_chain_get_best(bmm_chain* c, int32_t* z1, double* total, int* sweep);
+int bmm_chain_logpost_reset(bmm_chain* c);
+/* For a run: armed per calling thread for the NEXT single-chain *_run* call of that thread, bmm_alloc_run included, and
+ * disarmed when that call returns, whatever it returns, as bmm_set_loo_summary; NULL disarms.  The struct is copied;
+ * its buffers must stay valid through that call; any field may be NULL.  Only kept sweeps (j >= burnin) are folded;
+ * without burn-in the first kept row is the starting state, not a sweep: row 0 of rows is NaN and cannot be best.  It
+ * combines with every other option; under a relabelling the values are those of the state as sampled and z_best is a
+ * row of z_original.  bmm_multi_run does not take it and disarms it. */
+typedef struct bmm_logpost_out {
+    double* rows;        /* S x 4 doubles column-major like logdens: log_lik, log_prior, log_hyper, log_joint */
+    int32_t* z_best;     /* N int32, 1-based: the labels of the best kept state, as sampled */
+    double* best_total;  /* its log_joint (NaN when no state was folded) */
+    int* best_row;       /* its row of the trace, 0-based: the first maximum of log_joint (-1 when no state was folded) */
+} bmm_logpost_out;
+int bmm_set_logpost(const bmm_logpost_out* out);
+/* The rows of any stack of label rows over the same data (traces of several chains can be stacked by the caller), on a
+ * transient chain: X is packed once, then per state the labels are uploaded, the statistics recounted and the state
+ * scored by the launches above, so a run's own z and alpha give the run's rows bit for bit.  z: S x N int32 column-major,
+ * 1-based; alpha: S values (> 0; the allocation sampler: a); sample_alpha: whether alpha's Gamma(a, b) prior enters
+ * log_hyper; log_prior_k (K = maxK values) and k_open (S values) go together and select the allocation model, NULL
+ * otherwise; mask: P bytes in {0, 1} with rho, or NULL; out: S x 4 column-major.  BMM_E_ARG, before a device is touched,
+ * for a label outside 1 .. K (1 .. k_open[s]), naming the first bad cell. */
+int bmm_device_log_joint(int device, const int32_t* X, int64_t N, int P, int sampler, int K, double beta, double gamma,
+                         int sample_alpha, double a, double b, const double* log_prior_k, const int32_t* z, int S,
+                         const double* alpha, const int32_t* k_open, const uint8_t* mask, double rho, double* out);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
