@@ -442,7 +442,8 @@ BMM_HD int draw_spec(const double (&sc)[KT], double m, double u) {
 
 // ---------------------------------------------------------------- the draw from scores summed in binary32
 // The packed tier (k_resample_pk): the scores themselves come from binary32 copies of the table entries, two categories
-// to a 64-bit lookup, summed in binary32 in group order; the own-cluster score is the binary64 sum narrowed once.
+// to a 64-bit lookup, summed in binary32 in group order; the own-cluster score the same way from a binary32 image of
+// its own (Tm32: the "observation removed" terms grouped at the shape's width, each binary64 entry narrowed once).
 // draw_pk takes those scores s~_k and their maximum m~ and is draw_tier1 from there on, with a band that also covers
 // what the scores lost.  As there, `true` means the count is PROVEN to be the definition's.
 //
@@ -452,8 +453,17 @@ BMM_HD int draw_spec(const double (&sc)[KT], double m, double u) {
 //     category that is not the observation's own has n_k <= N - 1), so the partial sums of a score only grow in
 //     magnitude and every one of them is <= |s_k|.  An entry narrowed to binary32 is within h of itself, each of the
 //     G - 1 binary32 additions within h of a partial sum: |s~_k - s_k| <= G h |s_k| (1 + G h).  (The host test pushes
-//     every narrowed entry a further ulp = 2 h: (G + 2) h |s_k|, which is why the band says G + 2.)  The own score is
-//     one narrowing of a binary64 sum: h |s_k|.
+//     every narrowed entry a further ulp = 2 h: (G + 2) h |s_k|, which is why the band says G + 2.)
+//   the own score is summed like every other, from narrowed entries in group order, and its entries are <= 0 too: the
+//     constant is log(n_k - 1 + alpha/K) - log(N - 1 + alpha) (or -inf for a cluster of one row), each term
+//     log(beta + s - 1) - log(beta + gamma + n - 1) or its x = 0 twin log(gamma + n - 1 - s) - log(beta + gamma + n - 1),
+//     with s - 1 <= n - 1 and s >= 0.  So |s~_k - s'_k| <= G h |s'_k| (1 + G h), s'_k the exact sum of the width-W
+//     entries.  The definition's own score s_k sums the same P terms and the constant grouped three at a time (Gm
+//     groups) where the tier's entries group them W at a time, each entry a binary64 sum of at most W terms: the two
+//     differ by the binary64 roundings of at most P + G + Gm additions of partial sums no larger than |s_k|,
+//     |s'_k - s_k| <= (P + G + Gm) 2^-53 |s_k| < 2^-45 |s_k| for P <= 128 -- 2^-21 of one h |s_k|, well inside the
+//     two h |s_k| that G + 2 carries beyond the summation's G.  A -inf entry (it sits in group 0 of both images, with
+//     the constant) narrows to -inf and makes both sums -inf: the category weighs exactly 0 on both sides.
 //   a shift common to all categories cancels in the sign of t - cdf_k, so m~ need not be m: tier and definition are
 //     compared on the weights e^(s_k - m~), which are the w_k times one common factor.  The argument of exp2 is
 //     (s~_k - m~) log2(e) (1 + delta), |delta| <= 3.01 h as in draw_tier1 (the subtraction's rounding in place of the

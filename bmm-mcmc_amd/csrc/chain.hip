@@ -818,11 +818,11 @@ size_t image_bytes(const ChainParams& q, bool own_tables) {
     return (size_t)(own_tables ? l.doubles() : l.head()) * sizeof(double) + ((size_t)q.K * q.P + q.K + 4) * sizeof(int32_t);
 }
 
-// LDS of a k_resample_pk workgroup: the packed image, the tail of the table image (Nk, E, Tm), the histogram with
-// its counters, the queue
+// LDS of a k_resample_pk workgroup: the packed image, the binary32 own-cluster image of as many bytes, Nk and E of
+// the table image, the histogram with its counters, the queue
 size_t pk_image_bytes(const ChainParams& q) {
     const TableLayout l = layout_of(q, true);
-    return (size_t)(pk_tq_doubles(l) + l.doubles() - l.nk()) * sizeof(double) + ((size_t)q.K * q.P + q.K + 4 + kPkQueue) * sizeof(int32_t);
+    return (size_t)(2 * pk_tq_doubles(l) + l.tm() - l.nk()) * sizeof(double) + ((size_t)q.K * q.P + q.K + 4 + kPkQueue) * sizeof(int32_t);
 }
 
 // The spec's rule for the group width of a shape (bmm_spec.h; the oracle restates it): groups of kGroupW
@@ -1007,8 +1007,8 @@ int chain_alloc(bmm_chain* c) {
     }
     const size_t nz = (size_t)p.N;
     const size_t ns = (size_t)p.K * p.P, nn = (size_t)p.K;
-    // (behind the image of a counting sampler: the packed image k_resample_pk reads)
-    const size_t ntab = (size_t)layout_of(c).doubles() + (explicit_params(p.mode) ? 0 : (size_t)pk_tq_doubles(layout_of(c)));
+    // (behind the image of a counting sampler: the two binary32 images k_resample_pk reads, Tq and Tm32)
+    const size_t ntab = (size_t)layout_of(c).doubles() + (explicit_params(p.mode) ? 0 : 2 * (size_t)pk_tq_doubles(layout_of(c)));
     auto carve = [&](Carver& a) {
         // the statistics, their delta replicas, the table image and the flags first: zeroed in one go
         c->dNk = a.take<int32_t>(nn);
@@ -1757,6 +1757,14 @@ extern "C" {
 const char* bmm_last_error(void) { return g_err; }
 int bmm_spec_group_width(void) { return kGroupW; }
 int bmm_spec_group_width_own(void) { return kGroupWm; }
+// LDS bytes of a k_resample_pk workgroup at (sampler, K, P) with groups of W features; -1 where the shape has no
+// resident kernel at all
+int64_t bmm_spec_pk_image_bytes(int sampler, int K, int P, int W) {
+    if (sampler < 0 || sampler > 3 || K < 1 || P < 1 || P > kMaxP || (W != kGroupW && W != kGroupWAlt)) return -1;
+    const int kt = pick_kt(sampler == BMM_SAMPLER_DP ? K + 1 : K);
+    if (kt < 0) return -1;
+    return (int64_t)pk_image_bytes(geometry(sampler, P, K, kt, W));
+}
 int bmm_spec_group_width_for(int sampler, int K, int P) {
     if (sampler < 0 || sampler > 3 || K < 1 || P < 1) return -1;
     return group_width_rule(sampler, K, P);

@@ -68,6 +68,9 @@ struct TableLayout {
     __host__ __device__ int doubles() const { return tm() + gm_pad() * KT * kGroupMm; }
 };
 
+// doubles of the packed image Tq behind the table image of a chain that runs k_resample_pk, and of Tm32 behind Tq
+__host__ __device__ inline int pk_tq_doubles(const TableLayout& L) { return L.G * (L.KT / 2) * L.M; }
+
 struct ChainParams {
     int mode;           // MODE_*
     int64_t N;          // observations held by this chain object (a shard, or all of them)
@@ -164,6 +167,29 @@ __device__ __forceinline__ void write_group_tables(int W, const double* e1, cons
     if (W == kGroupW) write_group_tables_w<kGroupW>(e1, e0, pc, g0, gc, KT, k, c, T, Tq);
     else if (W == kGroupWAlt) write_group_tables_w<kGroupWAlt>(e1, e0, pc, g0, gc, KT, k, c, T, Tq);
     else write_group_tables_w<kGroupWm>(e1, e0, pc, g0, gc, KT, k, c, T);
+}
+
+// The own-cluster image of the packed kernel, behind Tq: To[G][KT][M] binary32 -- the "observation removed" terms
+// o1/o0 of one chunk grouped at the SHAPE's width W (kGroupW or kGroupWAlt; uniform), the constant c folded into global
+// group 0 as Tm folds it, each binary64 sum narrowed once and stored nowhere else (k_resample_pk reads the entry with
+// the field that indexes Tq).  A loop of its own: carried through the loop of write_group_tables_w, its arguments
+// spilled SGPRs of k_count_tables<false>; so did what the compiler computed of it ahead of the chunk loop (the caller).
+template <int W>
+__device__ __forceinline__ void write_own32_w(const double* o1, const double* o0, int pc, int g0, int gc, int KT, int k,
+                                              double c, float* To) {
+    constexpr int M = 1 << W;
+    for (int idx = threadIdx.x; idx < gc * M; idx += blockDim.x) {
+        const int g = idx / M;
+        const unsigned m = idx % M;
+        const double t = group_entry(o1, o0, g, pc, m, W);
+        To[((size_t)(g0 + g) * KT + k) * M + m] = (float)(g0 + g == 0 ? c + t : t);
+    }
+}
+__device__ __forceinline__ void write_own32(int W, const double* o1, const double* o0, int pc, int c0, int KT, int k,
+                                            double c, float* To) {
+    const int g0 = c0 / W, gc = (pc + W - 1) / W;
+    if (W == kGroupW) write_own32_w<kGroupW>(o1, o0, pc, g0, gc, KT, k, c, To);
+    else write_own32_w<kGroupWAlt>(o1, o0, pc, g0, gc, KT, k, c, To);
 }
 
 constexpr int kCountTablesThreads = 576;
@@ -275,6 +301,11 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
         __syncthreads();
         write_group_tables(p.W, e1, e0, pc, c0, p.KT, k, cst[0], tab + L.tp(), Tq);
         write_group_tables(kGroupWm, m1, m0, pc, c0, p.KT, k, cst[1], tab + L.tm());
+        if (Tq) {  // Tm32, behind Tq
+            int w = p.W, kt = p.KT, g = p.G;
+            asm volatile("" : "+s"(w), "+s"(kt), "+s"(g));  // nothing of this block is computed ahead of the loop (SGPRs)
+            write_own32(w, m1, m0, pc, c0, kt, k, cst[1], Tq + ((size_t)g * kt << w));  // Tq is G * KT * 2^W floats
+        }
         __syncthreads();
     }
     if (is_label && threadIdx.x == 0) {  // every thread read the old pair before the barriers above
@@ -1286,21 +1317,27 @@ __global__ __launch_bounds__(NT) void k_resample(ChainParams p, ResampleArgs a) 
 }
 
 // ---------------------------------------------------------------------------------
-// k_resample_pk: the plain bit-plane kernel (one lane per observation, own-cluster tables in LDS) with the scores
-// of the other categories summed in binary32 from the packed image Tq -- one ds_read_b64 and one v_pk_add_f32 per
-// PAIR of categories and lookup group, half of k_resample's LDS and scoring VALU instructions.  The draw is
-// draw_pk (bmm_spec.h), which says per lane whether its count is proven to be the definition's.  A lane that is
-// not certain writes its observation's index into a queue in LDS and neither stores nor counts it; after the
-// tile loop the workgroup runs the binary64 definition on the queue (pk_exact_one: one wave per observation, one
-// lane per category, Tp read from the global image), so the labels are k_resample's bit for bit.  An
-// observation that finds the queue full is scored by its wave on the spot.
-// LDS, in doubles: Tq [G][KT/2][M] pairs | the image's tail as it lies in global memory (Nk, E, Tm) | histogram,
-// chunk counter, queue counter | queue.
+// k_resample_pk: the plain bit-plane kernel (one lane per observation) with every score summed in binary32.  The
+// other categories come from the packed image Tq -- one ds_read_b64 and one v_pk_add_f32 per PAIR of categories and
+// lookup group, half of k_resample's LDS and scoring VALU instructions -- and the observation's own cluster from
+// Tm32, the "observation removed" entries at the same group width: one ds_read_b32 and one v_add_f32 per group, at
+// the field the group step has already extracted for Tq.  The draw is draw_pk (bmm_spec.h), which says per lane
+// whether its count is proven to be the definition's.  A lane that is not certain writes its observation's index
+// into a queue in LDS and neither stores nor counts it; after the tile loop the workgroup runs the binary64
+// definition on the queue (pk_exact_one: one wave per observation, one lane per category, Tp and the width-3 Tm
+// read from the global image), so the labels are k_resample's bit for bit.  An observation that finds the queue
+// full is scored by its wave on the spot.
+// LDS, in doubles: Tq [G][KT/2][M] pairs | Tm32 [G][KT][M] binary32 (the two as they lie behind the table image in
+// global memory) | Nk, E (as they lie in the image) | histogram, chunk counter, queue counter | queue.  The binary64
+// Tm is not staged.
 // ---------------------------------------------------------------------------------
 constexpr int kPkQueue = 4096;  // queue entries (pk_image_bytes, chain.hip)
 typedef float pk_f2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) pk_f2 lds_pk_f2;
-__host__ __device__ inline int pk_tq_doubles(const TableLayout& L) { return L.G * (L.KT / 2) * L.M; }
+typedef __attribute__((address_space(3))) float lds_f32;
+// the own-cluster tables' groups at the largest P, padded: one lane each in pk_exact_one
+constexpr int kOwnPadMax = ((kMaxP + kGroupWm - 1) / kGroupWm + kOwnSub - 1) / kOwnSub * kOwnSub;
+static_assert(kOwnPadMax <= 64, "pk_exact_one loads the own-cluster entries one per lane");
 
 // the DP's bookkeeping for a draw of the new-cluster option (collapsed_gibbs_dp.cpp:212-231).  A second copy of the
 // block under `if (p.mode == MODE_DP && zn == K)` in k_resample, which stays inline there so that its 370
@@ -1326,12 +1363,13 @@ __device__ __forceinline__ unsigned pk_field(int bit, unsigned mask, uint32_t b0
 }
 
 // The definition for observation i (wave-uniform), by the whole wave: lane k scores category k -- the G entries of
-// Tp from the global image (L2), four loads in flight, added in group order; the own cluster from Tm in LDS, in
-// group order, padding groups included -- then the maximum, expw_ and the binary64 running sum walk the lanes in
-// label order.  Every operation and its order are k_resample's.
+// Tp from the global image (L2), four loads in flight, added in group order; the own cluster from Tm in the global
+// image too: lane l loads the entry of group l (gm_pad() <= kOwnPadMax lanes) in the same round trip as the first
+// four of Tp, and the entries are added in group order, padding groups included, lane by lane -- then the maximum,
+// expw_ and the binary64 running sum walk the lanes in label order.  Every operation and its order are k_resample's.
 template <int KT, int GW>
 __device__ __forceinline__ void pk_exact_one(const ChainParams& p, const ResampleArgs& a, const TableLayout& L, int64_t i,
-                                             const lds_f64* TmL, const lds_f64* ET, const int32_t* NkT, int32_t* hist,
+                                             const lds_f64* ET, const int32_t* NkT, int32_t* hist,
                                              int Kused, int new_label, int lane) {
     constexpr int GM = 1 << GW;
     const int P = p.P, G = p.G, K = p.K;
@@ -1341,6 +1379,9 @@ __device__ __forceinline__ void pk_exact_one(const ChainParams& p, const Resampl
     const int zoc = zo < 0 ? 0 : zo;
     const int k = lane < KT ? lane : KT - 1;
     const double* const tp = a.tab + L.tp();
+    const int gmp = L.gm_pad();
+    const int go = lane < gmp ? lane : gmp - 1;
+    const double oe = a.tab[L.tm() + ((size_t)go * KT + zoc) * kGroupMm + pk_field(go * kGroupWm, kGroupMm - 1, b0, b1, b2, b3)];
     double sc = 0.0;
 #pragma unroll 1
     for (int g0 = 0; g0 < G; g0 += 4) {
@@ -1355,10 +1396,16 @@ __device__ __forceinline__ void pk_exact_one(const ChainParams& p, const Resampl
             if (g0 + v < G) sc = sc + tv[v];
     }
     double own = 0.0;
-    const int gmp = L.gm_pad();
-#pragma unroll 1
-    for (int g = 0; g < gmp; ++g)
-        own = own + TmL[((size_t)g * KT + zoc) * kGroupMm + pk_field(g * kGroupWm, kGroupMm - 1, b0, b1, b2, b3)];
+    {
+        const int lo = (int)(uint32_t)__double_as_longlong(oe), hi = (int)(uint32_t)(__double_as_longlong(oe) >> 32);
+#pragma unroll
+        for (int g = 0; g < kOwnPadMax; ++g) {
+            if (g < gmp) {  // uniform
+                const uint64_t e = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(lo, g) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(hi, g) << 32);
+                own = own + __longlong_as_double((long long)e);
+            }
+        }
+    }
     if (k == zo) sc = own;
     double m = neg_inf();
 #pragma unroll
@@ -1391,12 +1438,12 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const TableLayout L{p.G, KT, p.Gm, GM};
     double* const lds = reinterpret_cast<double*>(smem);
-    const int nq_d = pk_tq_doubles(L), tail_d = L.doubles() - L.nk();
+    const int nq_d = pk_tq_doubles(L), tail_d = L.tm() - L.nk();  // Tq, and Tm32 of as many bytes; Nk and E
     const volatile lds_pk_f2* const Tq = (const volatile lds_pk_f2*)lds;
-    double* const tail = lds + nq_d;
+    const volatile lds_f32* const Tm32 = (const volatile lds_f32*)(lds + nq_d);
+    double* const tail = lds + 2 * nq_d;
     const int32_t* const NkT = reinterpret_cast<const int32_t*>(tail);
     const lds_f64* const ET = (const lds_f64*)(tail + (L.et() - L.nk()));
-    const lds_f64* const TmL = (const lds_f64*)(tail + (L.tm() - L.nk()));
     int32_t* const hist = reinterpret_cast<int32_t*>(tail + tail_d);  // [K*P] then [K]
     const int P = p.P, G = p.G, K = p.K;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1417,7 +1464,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
     uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
     if (has_tile) load_words(a.Xb, p.N, W, pos.ic, b0, b1, b2, b3);  // before the tables are staged
     {
-        // stage the packed image and the tail of the table image: eight 16-byte loads in flight per lane
+        // stage the two binary32 images and Nk, E of the table image: eight 16-byte loads in flight per lane
         auto stage = [&](const double* from, double* to, int n2) {
             const double2* src = reinterpret_cast<const double2*>(from);
             double2* dst = reinterpret_cast<double2*>(to);
@@ -1435,7 +1482,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
                 }
             }
         };
-        stage(a.tab + L.doubles(), lds, nq_d / 2);
+        stage(a.tab + L.doubles(), lds, nq_d);
         stage(a.tab + L.nk(), tail, tail_d / 2);
     }
     for (int i = tid; i < K * P + K; i += NT) hist[i] = 0;
@@ -1461,31 +1508,6 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
         int64_t i_prev = -1;  // < 0: nothing to store
         for (;;) {
             const int zoc = zo < 0 ? 0 : zo;
-            double acc_own = 0.0;
-            {
-                // the own cluster from the "minus self" tables in binary64, as in k_resample
-                uint32_t r0 = b0, r1 = b1, r2 = b2, r3 = b3;
-                constexpr int RB = kOwnSub * kGroupWm;
-                const int rounds = (p.Gm + kOwnSub - 1) / kOwnSub;
-                size_t at0 = (size_t)zoc * kGroupMm;
-#pragma unroll 1
-                for (int it = 0; it < rounds; ++it) {
-                    double ow[kOwnSub];
-#pragma unroll
-                    for (int v = 0; v < kOwnSub; ++v) {
-                        unsigned f;
-                        asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(f) : "v"(r0), "n"(v * kGroupWm), "n"(kGroupWm));
-                        ow[v] = TmL[at0 + (size_t)v * KT * kGroupMm + f];
-                    }
-                    r0 = __builtin_amdgcn_alignbit(r1, r0, RB);
-                    r1 = __builtin_amdgcn_alignbit(r2, r1, RB);
-                    r2 = __builtin_amdgcn_alignbit(r3, r2, RB);
-                    r3 >>= RB;
-                    at0 += (size_t)kOwnSub * KT * kGroupMm;
-#pragma unroll
-                    for (int v = 0; v < kOwnSub; ++v) acc_own = acc_own + ow[v];
-                }
-            }
             if (i_prev >= 0) a.z_out[i_prev] = zn_prev;
             int nc = 0;
             if (lane == 0) nc = atomicAdd(next_chunk, 1);
@@ -1496,10 +1518,13 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
             uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
             int zo_next = -1;
 
-            // ---- scoring: (K / 2) * G conflict-free 64-bit LDS lookups, one packed add each
+            // ---- scoring: (K / 2) * G conflict-free 64-bit LDS lookups, one packed add each; per group one 32-bit
+            // gather of the own cluster's "observation removed" entry at the same field, one add
             pk_f2 acc[KP];
 #pragma unroll
             for (int j = 0; j < KP; ++j) acc[j] = pk_f2{0.0f, 0.0f};
+            float own32 = 0.0f;
+            const volatile lds_f32* const orow0 = Tm32 + zoc * GM;
             __builtin_amdgcn_s_setprio(BMM_LOOKUP_PRIO);
 #pragma unroll 1
             for (int h = 0; h < W; ++h) {
@@ -1515,21 +1540,24 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
                 for (int g = g_lo; g < g_hi; ++g) {
                     const unsigned nib = __builtin_amdgcn_alignbit(nxt, cur, (unsigned)(g * GW - 32 * h)) & (unsigned)(GM - 1);
                     const volatile lds_pk_f2* row = Tq + ((size_t)g * KP * GM + nib);
+                    const volatile lds_f32* orow = orow0 + ((size_t)g * KT * GM + nib);
 #pragma unroll
                     for (int c0 = 0; c0 < KP; c0 += CH) {
                         pk_f2 tv[CH];
+                        float ov = 0.0f;
 #pragma unroll
                         for (int j = 0; j < CH; ++j) tv[j] = row[(c0 + j) * GM];
+                        if (c0 == 0) ov = *orow;  // with the first chunk of Tq reads
 #pragma unroll
                         for (int j = 0; j < CH; ++j) acc[c0 + j] = acc[c0 + j] + tv[j];
+                        if (c0 == 0) own32 = own32 + ov;
                         if (CH < KP) __builtin_amdgcn_sched_barrier(0);  // keep the chunks apart
                     }
                 }
             }
             __builtin_amdgcn_s_setprio(0);
-            // the binary32 scores, the observation's own cluster narrowed from its binary64 sum
+            // the binary32 scores, the observation's own cluster from its own image
             float sc[KT];
-            const float own32 = (float)acc_own;
             float m = -__builtin_inff();
 #pragma unroll
             for (int k = 0; k < KT; ++k) {
@@ -1559,7 +1587,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
                 while (o) {
                     const int src = __ffsll((long long)o) - 1;
                     o &= o - 1;
-                    pk_exact_one<KT, GW>(p, a, L, a.lo + __builtin_amdgcn_readlane(off, src), TmL, ET, NkT, hist, Kused,
+                    pk_exact_one<KT, GW>(p, a, L, a.lo + __builtin_amdgcn_readlane(off, src), ET, NkT, hist, Kused,
                                          new_label, lane);
                 }
             }
@@ -1578,7 +1606,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
     // ---- the exact pass: the queued observations, one wave each
     const int nqueued = *qcount < qcap ? *qcount : qcap;
     for (int q = wave; q < nqueued; q += NW)
-        pk_exact_one<KT, GW>(p, a, L, a.lo + queue[q], TmL, ET, NkT, hist, Kused, new_label, lane);
+        pk_exact_one<KT, GW>(p, a, L, a.lo + queue[q], ET, NkT, hist, Kused, new_label, lane);
     __syncthreads();
     flush_hist(hist, K, P, a.dS + (size_t)(blockIdx.x % kDeltaReps) * K * P, a.dNk + (blockIdx.x % kDeltaReps) * K, tid, NT);
 #ifdef BMM_DEBUG_HOOKS

@@ -90,6 +90,10 @@ const char* bmm_last_error(void);
 int bmm_spec_group_width(void);
 int bmm_spec_group_width_own(void);
 int bmm_spec_group_width_for(int sampler, int K, int P);
+/* LDS bytes a workgroup of the packed resample kernel needs at (sampler, K, P) with lookup groups of W features
+ * (W one of the two widths above): both binary32 images, Nk, E, the histogram and the queue; -1 where P or K is
+ * beyond the resident kernels or W is neither width */
+int64_t bmm_spec_pk_image_bytes(int sampler, int K, int P, int W);
 /* library default batch size for N observations (used when batch <= 0): below 2^16 observations floor(N/8)
  * for the finite sampler and floor(N/16) for the DP sampler (at least 1); from 2^16 on floor(N/4) for
  * both -- the bias of a batch shrinks with N and is not measurable there (TOLERANCE above; DESIGN.md
