@@ -22,7 +22,7 @@ __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "
            "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
            "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
            "partition_distances", "posterior_similarity", "partition_plan", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
-           "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat"]
+           "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat", "Ladder", "temper_ladder", "TEMPER_MAX_RUNGS"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -669,6 +669,63 @@ def _make_logpost(logpost, ecr_req, N, S, chains):
     return True if int(chains) > 1 else _LogPost(N, S)
 
 
+# ---------------------------------------------------------------- temper=: parallel tempering, a replica ladder
+TEMPER_MAX_RUNGS = 8
+
+
+def temper_ladder(R, hottest=0.1):
+    """R inverse temperatures from 1 down to `hottest`, geometrically spaced (R = 1: just 1)."""
+    R = int(R)
+    if not 1 <= R <= TEMPER_MAX_RUNGS:
+        raise ValueError("a ladder has 1 to %d rungs" % TEMPER_MAX_RUNGS)
+    if not 0.0 < hottest < 1.0:
+        raise ValueError("hottest must lie in (0, 1)")
+    b = _np.ones(R)
+    if R > 1:
+        b[1:] = float(hottest) ** (_np.arange(1, R) / (R - 1.0))
+    return b
+
+
+class _TemperOut(_C.Structure):  # bmm_temper_out
+    _fields_ = [("R", _C.c_int), ("inv_temp", _C.c_void_p), ("swap_every", _C.c_int), ("proposed", _C.c_void_p),
+                ("accepted", _C.c_void_p), ("walker_cold", _C.c_void_p), ("loglik", _C.c_void_p)]
+
+
+class _Temper:
+    """Outputs of an armed bmm_set_temper: the run fills them (include/bmm_mcmc.h "parallel tempering", DESIGN.md
+    section 21)."""
+
+    def __init__(self, inv_temp, swap_every, S):
+        self.b = _np.ascontiguousarray(inv_temp, dtype=_np.float64)
+        R = self.b.size
+        self.proposed = _np.zeros(max(R - 1, 1), dtype=_np.int64)[:max(R - 1, 0)]
+        self.accepted = _np.zeros(max(R - 1, 1), dtype=_np.int64)[:max(R - 1, 0)]
+        self.walker = _np.zeros(S, dtype=_np.int32)
+        self.loglik = _np.full((S, R), _np.nan, order="F")
+        self.s = _TemperOut(R, self.b.ctypes.data, int(swap_every), self.proposed.ctypes.data, self.accepted.ctypes.data,
+                            self.walker.ctypes.data, self.loglik.ctypes.data)
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_temper(_C.byref(self.s)))
+
+    def result(self):
+        with _np.errstate(invalid="ignore", divide="ignore"):
+            rate = self.accepted / self.proposed.astype(_np.float64)
+        return {"inv_temp": self.b, "proposed": self.proposed, "accepted": self.accepted, "rate": rate,
+                "walker_cold": self.walker, "loglik": self.loglik}
+
+
+def _make_temper(temper, swap_every, S, chains, hottest=0.1):
+    """temper= of a wrapper: a sequence of inverse temperatures starting at 1, or the number of rungs of
+    temper_ladder(); None when off"""
+    if temper is None:
+        return None
+    if int(chains) > 1:
+        raise _capi.BmmError(2, "temper= is offered per chain (chains=1): the rungs of a ladder are its chains")
+    b = temper_ladder(temper, hottest) if _np.ndim(temper) == 0 else _np.asarray(temper, dtype=_np.float64).ravel()
+    return _Temper(b, swap_every, S)
+
+
 def log_joint(X, z, sampler, K, alpha=1.0, beta=0.5, gamma=0.5, a=1, b=1, sample_alpha=False, k_open=None, prior_k=None,
               mask=None, rho=0.5, device=0):
     """The log joint rows of any stack of label rows over the data X, on the device (bmm_device_log_joint; include/bmm_mcmc.h
@@ -985,7 +1042,7 @@ class _Init:
         return info.as_dict()
 
 
-def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None, lp=None):
+def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None, lp=None, tp=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
@@ -1001,6 +1058,8 @@ def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=
         ecr.arm()
     if lp is not None:
         lp.arm()
+    if tp is not None:
+        tp.arm()
     if init is not None:  # last, just ahead of the call: a run of another sampler refuses an armed start
         init.arm()
     if pr is None:
@@ -1159,7 +1218,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                     initial_K=None, chains=1, devices=None, stephens=None, newdata=None, predictive_trace=False,
                     responsibilities=False, partition=None, partition_stride=1, similarity_of=None, loo=False,
                     select_features=False, rho=0.5, init="random", init_iters=INIT_ITERS, ecr_pivot="iterative",
-                    ecr_max_iter=50, logpost=False):
+                    ecr_max_iter=50, logpost=False, temper=None, swap_every=1, temper_hottest=0.1):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -1218,6 +1277,15 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     the starting state, is NaN and never best).  With `chains > 1` every chain is scored afterwards and every object
     also gains "rhat", the split-R-hat of log_joint over the chains (rhat()), and "chain", the chain holding the overall
     best state.  `ecr_pivot="map"` relabels to that state (over several chains the overall best) and implies logpost.
+    `temper=`: parallel tempering (include/bmm_mcmc.h "parallel tempering") -- a sequence of inverse
+    temperatures starting at 1 and strictly decreasing, or an integer R meaning temper_ladder(R, temper_hottest).  Helper
+    chains (seed + r, the same starting labels, the same planes) sample the posterior with the likelihood raised to
+    those powers on the same device, and after every `swap_every`-th sweep neighbouring rungs exchange their states by a
+    Metropolis test; everything returned is the chain at power 1, which samples the untouched posterior.  The result
+    gains `temper = {"inv_temp", "proposed", "accepted", "rate": (R - 1,), "walker_cold": (S,), "loglik": (S, R)}`:
+    the exchanges per neighbouring pair, which starting rung's state sat at power 1 after each kept sweep, and every
+    rung's log_lik after the exchange points of kept sweeps (NaN elsewhere).  temper=[1.0] is the run without it, byte
+    for byte.  Not with chains > 1, relabel=, select_features= (or split_merge= on gibbs_dp).
     """
     X = _capi.as_x(data)
     N, P = X.shape
@@ -1235,8 +1303,11 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, False, newdata, loo)
     lo = _make_loo(loo, N, nsamples - burnin, chains, False)
     lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
+    tp = _make_temper(temper, swap_every, nsamples - burnin, chains, temper_hottest)
 
     def done(out):
+        if tp is not None:
+            out["temper"] = tp.result()
         if fs is not None:
             out["features"] = fs.result()
         if ini is not None:
@@ -1283,7 +1354,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
                 _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini, lp=lp)
+            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini, lp=lp, tp=tp)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
@@ -1295,7 +1366,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
             _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1307,7 +1378,8 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
              burnrelabel=50, maxK=30, debug=False, *, seed=None, batch=None, device=0, chains=1, devices=None,
              stephens=None, newdata=None, predictive_trace=False, responsibilities=False, partition=None,
              partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None,
-             select_features=False, rho=0.5, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False):
+             select_features=False, rho=0.5, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
+             temper=None, swap_every=1, temper_hottest=0.1):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
@@ -1316,7 +1388,8 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     `split_merge = {"split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped"}`.  Per chain.
     `select_features`, `rho`: as gibbs_collapsed (needs beta == gamma; not with split_merge=).  `init`: "random" only (a
     DP run seats its rows in its first sweep; Chain.init_labels re-seats a resident DP chain).  `logpost`,
-    `ecr_pivot="map"`: as gibbs_collapsed."""
+    `ecr_pivot="map"`: as gibbs_collapsed.  `temper`, `swap_every`, `temper_hottest`: as gibbs_collapsed (the helper
+    chains seat their own rows in their first sweep; the new-cluster option carries the power on its likelihood part)."""
     _init_kind(init, 0, allowed=False)
     X = _capi.as_x(data)
     N, P = X.shape
@@ -1330,8 +1403,11 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, True, newdata, loo, split_merge)
     sm = _make_split_merge(split_merge, split_merge_scans, chains)
     lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
+    tp = _make_temper(temper, swap_every, nsamples - burnin, chains, temper_hottest)
 
     def done(out):
+        if tp is not None:
+            out["temper"] = tp.result()
         if sm is not None:
             out["split_merge"] = sm.result()
         if fs is not None:
@@ -1359,7 +1435,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                 _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
                 _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs, lp=lp)
+            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs, lp=lp, tp=tp)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, maxK, P, S)
@@ -1372,7 +1448,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp)
+        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1759,6 +1835,18 @@ class Chain:
     def logpost_reset(self):
         _capi.check(_capi.lib().bmm_chain_logpost_reset(self._h))
 
+    # -- parallel tempering (include/bmm_mcmc.h "parallel tempering")
+    def set_temper(self, inv_temp=1.0, on=True):
+        """The chain targets p(alpha) p(z | alpha) p(x | z)^inv_temp from its next table build on (0 < inv_temp <= 1;
+        1.0 runs the tempered table kernel and gives an unarmed chain's values); on=False: as it was."""
+        _capi.check(_capi.lib().bmm_chain_set_temper(self._h, _C.c_int(1 if on else 0), _C.c_double(float(inv_temp))))
+
+    def temper(self):
+        """(armed, inverse temperature)"""
+        on, b = _C.c_int(0), _C.c_double(1.0)
+        _capi.check(_capi.lib().bmm_chain_get_temper(self._h, _C.byref(on), _C.byref(b)))
+        return bool(on.value), b.value
+
     def set_split_merge(self, moves_per_sweep, scans=SPLIT_MERGE_SCANS):
         """`moves_per_sweep` moves at the start of every sweep from the second (0: off), `scans` intermediate scans each."""
         _capi.check(_capi.lib().bmm_chain_set_split_merge(self._h, _C.c_int(int(moves_per_sweep)), _C.c_int(int(scans))))
@@ -1926,6 +2014,61 @@ def sweep_chains(chains, n):
     one device overlap on their streams.  Returns without waiting; sync each chain afterwards."""
     tab = (_C.c_void_p * len(chains))(*[c._h.value for c in chains])
     _capi.check(_capi.lib().bmm_chains_sweeps(tab, _C.c_int(len(chains)), _C.c_int(int(n))))
+
+
+class _ExchangeStep(_C.Structure):  # bmm_exchange_step
+    _fields_ = [("d", _C.c_double), ("u", _C.c_double), ("proposed", _C.c_int32), ("accepted", _C.c_int32),
+                ("point", _C.c_int32), ("pad", _C.c_int32)]
+
+
+class Ladder:
+    """A replica ladder over resident chains (bmm_ladder_* in include/bmm_mcmc.h): chains[0] at
+    inverse temperature 1, the others armed with set_temper at strictly decreasing powers, all over one copy of the data
+    (share_data) on one device.  The chains stay the caller's and must outlive the ladder."""
+
+    def __init__(self, chains, seed=0):
+        self._h = _C.c_void_p()
+        self.chains = list(chains)
+        self.R = len(self.chains)
+        tab = (_C.c_void_p * self.R)(*[c._h.value for c in self.chains])
+        _capi.check(_capi.lib().bmm_ladder_create(_C.byref(self._h), tab, _C.c_int(self.R), _C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)))
+
+    def close(self):
+        if self._h:
+            _capi.lib().bmm_ladder_destroy(self._h)
+            self._h = _C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def sweeps(self, n, swap_every=1):
+        """n sweeps of every rung, an exchange point behind every sweep whose index is a multiple of swap_every.
+        Returns without waiting."""
+        _capi.check(_capi.lib().bmm_ladder_sweeps(self._h, _C.c_int(int(n)), _C.c_int(int(swap_every))))
+
+    def exchange_step(self):
+        """One exchange point now, waited for: a list of R - 1 records {"d", "u", "proposed", "accepted", "point"}."""
+        rec = (_ExchangeStep * max(self.R - 1, 1))()
+        _capi.check(_capi.lib().bmm_ladder_exchange_step(self._h, rec))
+        return [{"d": rec[r].d, "u": rec[r].u, "proposed": bool(rec[r].proposed), "accepted": bool(rec[r].accepted),
+                 "point": int(rec[r].point)} for r in range(self.R - 1)]
+
+    def stats(self):
+        """{"proposed", "accepted": (R - 1,), "walker": (R,)}: the exchanges per neighbouring pair and which starting
+        rung's state sits at each rung now."""
+        pr, ac = _np.zeros(max(self.R - 1, 1), dtype=_np.int64), _np.zeros(max(self.R - 1, 1), dtype=_np.int64)
+        w = _np.zeros(self.R, dtype=_np.int32)
+        _capi.check(_capi.lib().bmm_ladder_stats(self._h, _capi.vp(pr), _capi.vp(ac), _capi.vp(w)))
+        return {"proposed": pr[:self.R - 1], "accepted": ac[:self.R - 1], "walker": w}
 
 
 def broadcast_planes(chains):

@@ -44,6 +44,8 @@ SYMBOLS = [
     "bmm_device_ecr", "bmm_device_ecr_plan", "bmm_set_ecr_relabel",
     "bmm_chain_set_logpost", "bmm_chain_logpost_state", "bmm_chain_sweeps_logpost", "bmm_chain_get_best",
     "bmm_chain_logpost_reset", "bmm_set_logpost", "bmm_device_log_joint",
+    "bmm_chain_set_temper", "bmm_chain_get_temper", "bmm_ladder_create", "bmm_ladder_destroy", "bmm_ladder_sweeps",
+    "bmm_ladder_exchange_step", "bmm_ladder_stats", "bmm_set_temper",
 ]
 
 
@@ -75,6 +77,13 @@ def load(path):
     L.bmm_chain_destroy.restype = None
     L.bmm_chain_destroy.argtypes = [C.c_void_p]
     L.bmm_chain_share_data.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(L, "bmm_ladder_create"):  # (an older build loaded for a comparison has no ladder)
+        L.bmm_ladder_destroy.restype = None
+        L.bmm_ladder_destroy.argtypes = [C.c_void_p]
+        L.bmm_ladder_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64]
+        L.bmm_ladder_sweeps.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.bmm_ladder_exchange_step.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmm_ladder_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 

@@ -60,6 +60,7 @@ enum : uint32_t {
     kStreamAlloc = 11,     // an eject / absorb move: c0 = move index, c1 = block counter, c2 = sweep (ea_move_draws)
     kStreamAllocPeA = 12,  // its p_E ~ Beta(e, e): first gamma; c0 = move index, c2 = sweep
     kStreamAllocPeB = 13,  // ... second gamma
+    kStreamTemper = 14,    // the uniform of a replica exchange: c0 = pair index r, c1 = block counter, c2 = exchange point t (temper_uniform)
 };
 
 // ---------------------------------------------------------------- bit helpers
@@ -337,6 +338,17 @@ BMM_HD double expw_tab(double x, Tab T) {
     return ldexp_(fma_(t, q, t), k);
 }
 BMM_HD double expw_(double x) { return expw_tab(x, exp256_table()); }
+
+// The exchange of parallel tempering (include/bmm_mcmc.h "parallel tempering"): the uniform that decides pair r
+// (rungs r and r + 1) at exchange point t is the first block of a stream of its own under the ladder's seed; with
+// d = (b_r - b_{r+1}) * (L_{r+1} - L_r) the exchange is accepted iff d >= 0 or u < expw_(d); a NaN d rejects.
+BMM_HD double temper_uniform(uint64_t seed, uint32_t r, uint32_t t) {
+    Stream st = make_stream(seed, r, t, kStreamTemper);
+    const U4 x = st.next();
+    return u52(x.x, x.y);
+}
+BMM_HD double temper_log_ratio(double b_r, double b_r1, double L_r, double L_r1) { return (b_r - b_r1) * (L_r1 - L_r); }
+BMM_HD bool temper_accepts(double d, double u) { return d >= 0.0 || (d < 0.0 && u < expw_(d)); }
 
 // ---------------------------------------------------------------- lgamma
 // log Gamma(x) for x > 0 (the split-merge move's arguments: a prior plus an integer, up to about 1e7).  The

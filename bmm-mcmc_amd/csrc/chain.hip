@@ -628,6 +628,13 @@ struct bmm_chain {
     int32_t* dLjZ = nullptr;
     int lp_folded = 0;  // states folded so far
     SweepTrace lp_rec;
+    bool lp_defer = false;  // a ladder's exchange point follows this sweep: the ladder folds the row behind it
+    // parallel tempering: temper_on: the table builds are k_temper_tables at inverse temperature
+    // temper_b, and the kernel choice leaves out the forms that build their own tables and the packed one; ladder: the
+    // replica ladder a run drives this chain through as its rung 0 (not owned)
+    bool temper_on = false;
+    double temper_b = 1.0;
+    bmm_ladder* ladder = nullptr;
     int prof = 0;             // > 0: HIP events around the resample launches of every prof-th sweep
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
@@ -697,7 +704,7 @@ int run_rows_out(const bmm_chain* c, const double* dtrace, int64_t width, double
 }
 
 // What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_loo_summary,
-// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost; bmm_alloc_run fills `alloc` for its own run), and what a
+// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost, bmm_set_temper; bmm_alloc_run fills `alloc` for its own run), and what a
 // *_run_predict / *_run_relabel / *_run_probs entry point was handed.
 struct RunOptions {
     struct { bool on = false; bmm_partition_out o{}; } partition;
@@ -707,6 +714,7 @@ struct RunOptions {
     struct { int kind = 0, iters = 0; } init;
     struct { bool on = false; bmm_ecr_out o{}; } ecr;
     struct { bool on = false; bmm_logpost_out o{}; } logpost;
+    struct { bool on = false; bmm_temper_out o{}; } temper;
     struct { bool on = false; const double* log_prior_k = nullptr; int K0 = 0, moves = 0; double eject_a = 1.0; int32_t* k_out = nullptr; int64_t* moves_out = nullptr; } alloc;
     const bmm_relabel_hooks* hooks = nullptr;  // *_run_probs
     const bmm_relabel_out* rel = nullptr;      // *_run_relabel
@@ -1161,6 +1169,9 @@ int launch_count_tables(bmm_chain* c) {
     if (c->alloc_on)  // the allocation sampler: open empty labels keep their prior weight
         hipLaunchKernelGGL(k_alloc_tables, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
                            c->dDNk, c->dDS, (const int32_t*)c->dEaK, c->alloc_a, c->dTab);
+    else if (c->temper_on)  // a tempered chain: every per-feature term times its inverse temperature
+        hipLaunchKernelGGL(k_temper_tables, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
+                           c->dDNk, c->dDS, (const double*)c->dAlpha, c->temper_b, c->dTab);
     else if (c->fs_mask)  // feature selection: excluded features are written as zeros
         hipLaunchKernelGGL(k_count_tables<true>, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
                            c->dDNk, c->dDS, c->dAlpha, c->dTab, (const uint32_t*)c->dFsMask, 0);
@@ -1271,7 +1282,7 @@ int enqueue_log_joint(bmm_chain* c, int j, double* row, bool fold) {
 int sweep_end_folds(bmm_chain* c, int j) {
     int rc = sweep_end_predict(c, j);
     if (rc == BMM_OK && c->loo_rec.folds(j) && c->loo_on) rc = enqueue_loo(c, j, c->loo_rec.row<double>(j), true);
-    if (rc == BMM_OK && c->lp_rec.folds(j) && c->lp_on) rc = enqueue_log_joint(c, j, c->lp_rec.row<double>(j), true);
+    if (rc == BMM_OK && c->lp_rec.folds(j) && c->lp_on && !c->lp_defer) rc = enqueue_log_joint(c, j, c->lp_rec.row<double>(j), true);
     return rc;
 }
 
@@ -1283,8 +1294,13 @@ int fs_mask_refuses(const char* what) {
 }
 
 // ---- split-merge moves ----
+int temper_refuses(const char* what) {
+    return set_err(BMM_E_UNSUPPORTED, "%s is not offered on a tempered chain (parallel tempering): it is written for the "
+                   "likelihood at full power", what);
+}
 int sm_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_STATE, "split-merge moves are not offered on a sharded chain");
+    if (c->temper_on) return temper_refuses("the split-merge ratio");
     if (c->p.mode != MODE_DP)
         return set_err(BMM_E_UNSUPPORTED, "split-merge moves are offered for the DP sampler only (the finite sampler gives an "
                        "emptied label probability 0 for ever: a different model from the one the move's ratio targets)");
@@ -1684,7 +1700,7 @@ int tier_of(const bmm_chain* c) { return explicit_params(c->p.mode) ? 0 : (c->mi
 // The chain's resident kernel, set up for launching: the last form of the plan that the runtime takes.
 int pick_kernel(bmm_chain* c) {
     const KernelPlan plan = plan_kernel(c->p, c->bits, tier_of(c), c->batch, c->num_cus, c->shares_device, c->lds_bytes_base,
-                                        DebugSwitches{}, c->fs_mask || c->alloc_on);
+                                        DebugSwitches{}, c->fs_mask || c->alloc_on || c->temper_on);
     hipError_t e = hipSetDevice(c->device);
     for (int i = 0; i < plan.n; ++i) {
         const KernelForm& f = plan.form[i];
@@ -3142,6 +3158,7 @@ static int alloc_refused(const bmm_chain* c) {
     if (c->p.P > kEaMaxP) return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is offered up to %d features", kEaMaxP);
     if (!c->bits) return set_err(BMM_E_UNSUPPORTED, "the eject / absorb moves read the bit planes: not offered on the int32 layout");
     if (c->fs_mask) return fs_mask_refuses("the allocation sampler");
+    if (c->temper_on) return temper_refuses("the allocation sampler");
     if (c->predM > 0) return alloc_refuses("the predictive density");
     if (c->loo_on) return alloc_refuses("the leave-one-out predictive");
     if (c->p.K < 2) return set_err(BMM_E_ARG, "maxK must be >= 2");
@@ -3369,6 +3386,7 @@ static int fs_refused(const bmm_chain* c) {
     if (c->loo_on) return set_err(BMM_E_UNSUPPORTED, "feature selection is not offered together with the leave-one-out summary: its tables are written for the all-features model");
     if (c->sm_moves > 0) return set_err(BMM_E_UNSUPPORTED, "feature selection is not offered together with split-merge moves: their ratio is written for the all-features model");
     if (c->alloc_on) return alloc_refuses("feature selection");
+    if (c->temper_on) return temper_refuses("feature selection");
     if (!c->have_data) return set_err(BMM_E_STATE, "the chain has no rows to seat: set the data first");
     if (c->p.mode == MODE_COLLAPSED && !c->have_init) return set_err(BMM_E_STATE, "the chain's rows have no labels: set the initial labels first");
     return BMM_OK;
@@ -3569,6 +3587,282 @@ static int fs_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, int
         f.n_selected[t] = n;
     }
     return bmm_chain_get_feature_summary(c, f.inclusion, f.inclusion_rb, f.n_folded);
+}
+
+// ---- parallel tempering: a replica ladder (include/bmm_mcmc.h "parallel tempering") ----
+// who may be a rung
+static int temper_refused(const bmm_chain* c) {
+    if (!c) return set_err(BMM_E_ARG, "null chain");
+    if (explicit_params(c->p.mode))
+        return set_err(BMM_E_UNSUPPORTED, "parallel tempering is offered for the collapsed and DP samplers only: the stick-breaking "
+                       "and full samplers carry theta, and the power sits on the likelihood with theta integrated out");
+    if (c->alloc_on) return alloc_refuses("parallel tempering");
+    if (c->fs_mask) return fs_mask_refuses("parallel tempering");
+    if (c->sm_moves > 0) return set_err(BMM_E_UNSUPPORTED, "parallel tempering is not offered together with split-merge moves: their ratio would need the tempered likelihood");
+    if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "parallel tempering is not offered on a sharded chain");
+    return BMM_OK;
+}
+
+int bmm_chain_set_temper(bmm_chain* c, int on, double inv_temp) {
+    return guarded([&]() -> int {
+        int rc = temper_refused(c);
+        if (rc) return rc;
+        if (on && !(inv_temp > 0.0 && inv_temp <= 1.0)) return set_err(BMM_E_ARG, "inv_temp must lie in (0, 1]");
+        if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+        const bool was = c->temper_on;
+        c->temper_on = on != 0;
+        c->temper_b = on ? inv_temp : 1.0;
+        if (was == c->temper_on || c->generic) return BMM_OK;
+        return pick_kernel(c);  // again: without, or once more with, the forms a tempered chain leaves out
+    });
+}
+
+int bmm_chain_get_temper(const bmm_chain* c, int* on, double* inv_temp) {
+    if (!c) return set_err(BMM_E_ARG, "null chain");
+    if (on) *on = c->temper_on ? 1 : 0;
+    if (inv_temp) *inv_temp = c->temper_b;
+    return BMM_OK;
+}
+
+}  // extern "C"
+
+struct bmm_ladder {
+    int R = 0, device = 0;
+    bmm_chain* ch[kTemperMaxR] = {};
+    uint64_t seed = 0;
+    uint32_t t = 0;  // exchange points so far
+    char* dBlock = nullptr;
+    int32_t *dAccept = nullptr, *dWalker = nullptr;
+    long long* dCounters = nullptr;
+    TemperStep* dRec = nullptr;
+    hipEvent_t ready[kTemperMaxR] = {};  // rung r has scored its state
+    hipEvent_t done = nullptr;           // the exchange is over
+    // a run's recordings (device; owned by the run): [S][R] log_lik rows and [S] walkers at rung 0, row s = sweep - base
+    double* lik_rows = nullptr;
+    int32_t* walker_rows = nullptr;
+    int base = 0, swap_every = 1;
+};
+
+namespace {
+
+// One exchange point, enqueued: every rung scores its state on its own stream (the keep-best cell untouched), rung 0's
+// stream waits for them, decides and exchanges, the others wait for that.  Nothing blocks the host.
+int ladder_exchange(bmm_ladder* l, double* lik_row) {
+    const int R = l->R;
+    bmm_chain* const c0 = l->ch[0];
+    if (R < 2 && !lik_row) return BMM_OK;
+    TemperArgs a{};
+    for (int r = 0; r < R; ++r) {
+        bmm_chain* const c = l->ch[r];
+        int rc = lp_setup(c, false);
+        if (rc) return rc;
+        LjArgs lj = lj_args(c);
+        lj.out_row = nullptr; lj.sweep = c->sweep; lj.fold = 0;
+        rc = launch_log_joint(c, lj);
+        if (rc) return rc;
+        if (r > 0) HIP_TRY(hipEventRecord(l->ready[r], c->stream));
+        TemperRung& g = a.rung[r];
+        g.lj_out = c->dLjOut; g.z = label_row(c, c->sweep); g.Nk = c->dNk; g.S = c->dS; g.dNk = c->dDNk; g.dS = c->dDS;
+        g.alpha = c->dAlpha; g.b = c->temper_on ? c->temper_b : 1.0;
+    }
+    for (int r = 1; r < R; ++r) HIP_TRY(hipStreamWaitEvent(c0->stream, l->ready[r], 0));
+    a.R = R; a.t = l->t; a.seed = l->seed; a.accept = l->dAccept; a.walker = l->dWalker; a.counters = l->dCounters;
+    a.rec = l->dRec; a.lik_row = lik_row; a.N = c0->p.N; a.K = c0->p.K; a.P = c0->p.P;
+    hipLaunchKernelGGL(k_temper_decide, dim3(1), dim3(64), 0, c0->stream, a);
+    HIP_TRY(hipGetLastError());
+    const int pairs = (R - (int)(l->t & 1u)) / 2;  // r = t mod 2, then every other one, while r + 1 < R
+    if (pairs > 0) {
+        const int64_t nb = (c0->p.N + 4 * kTemperThreads - 1) / (4 * kTemperThreads);
+        hipLaunchKernelGGL(k_temper_exchange, dim3((unsigned)(nb < 256 ? nb : 256), (unsigned)pairs), dim3(kTemperThreads), 0,
+                           c0->stream, a);
+        HIP_TRY(hipGetLastError());
+        // rung 0's kept row of a run: theta-hat and alpha of the state it holds now (nothing is pending behind a
+        // sweep end, and the concentration is not drawn again)
+        if (c0->dTrace && c0->sweep >= c0->burnin && c0->sweep >= 1 && (l->t & 1u) == 0) {
+            ChainParams q = c0->p;
+            q.sample_alpha = 0;
+            const int s = c0->sweep - c0->burnin;
+            hipLaunchKernelGGL(k_count_sweep_end, dim3(1), dim3(1024), 0, c0->stream, q, c0->dNk, c0->dS, c0->dDNk, c0->dDS,
+                               c0->dAlpha, (uint32_t)c0->sweep, c0->dThetaTrace + (size_t)s * q.K * q.P, c0->dAlphaTrace + s,
+                               (int32_t*)nullptr);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(l->done, c0->stream));
+        for (int r = 1; r < R; ++r) HIP_TRY(hipStreamWaitEvent(l->ch[r]->stream, l->done, 0));
+    }
+    l->t++;
+    return BMM_OK;
+}
+
+int ladder_same_sweep(const bmm_ladder* l) {
+    for (int r = 1; r < l->R; ++r)
+        if (l->ch[r]->sweep != l->ch[0]->sweep)
+            return set_err(BMM_E_STATE, "rung %d is at sweep %d, rung 0 at sweep %d: the rungs of a ladder advance together", r, l->ch[r]->sweep, l->ch[0]->sweep);
+    return BMM_OK;
+}
+
+// n sweeps of every rung with an exchange point behind every sweep whose index is a multiple of swap_every
+int ladder_sweeps(bmm_ladder* l, int n, int swap_every) {
+    if (n < 0) return set_err(BMM_E_ARG, "n must be >= 0");
+    if (swap_every < 1) return set_err(BMM_E_ARG, "swap_every must be >= 1");
+    int rc = ladder_same_sweep(l);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(l->device));
+    bmm_chain* const c0 = l->ch[0];
+    for (int r = 0; r < l->R; ++r)
+        if (!l->ch[r]->started) { rc = chain_start(l->ch[r]); if (rc) return rc; }
+    for (int t = 0; t < n; ++t) {
+        const int j = c0->sweep + 1;
+        const bool point = j % swap_every == 0;
+        c0->lp_defer = point && l->R > 1;
+        for (int r = 0; r < l->R && rc == BMM_OK; ++r) {
+            rc = enqueue_sweep(l->ch[r], j);
+            if (rc == BMM_OK) l->ch[r]->sweep++;
+        }
+        const bool deferred = std::exchange(c0->lp_defer, false);
+        if (rc) return rc;
+        const bool kept = l->lik_rows && j >= l->base;
+        if (point) {
+            rc = ladder_exchange(l, kept ? l->lik_rows + (size_t)(j - l->base) * l->R : nullptr);
+            if (rc == BMM_OK && deferred && c0->lp_rec.folds(j) && c0->lp_on) rc = enqueue_log_joint(c0, j, c0->lp_rec.row<double>(j), true);
+            if (rc) return rc;
+        }
+        if (l->walker_rows && j >= l->base)
+            HIP_TRY(hipMemcpyAsync(l->walker_rows + (j - l->base), l->dWalker, sizeof(int32_t), hipMemcpyDeviceToDevice, c0->stream));
+    }
+    return BMM_OK;
+}
+
+int ladder_sync(bmm_ladder* l) {
+    HIP_TRY(hipSetDevice(l->device));
+    for (int r = 0; r < l->R; ++r) HIP_TRY(hipStreamSynchronize(l->ch[r]->stream));
+    return BMM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bmm_ladder_create(bmm_ladder** out, bmm_chain* const* chains, int R, uint64_t seed) {
+    return guarded([&]() -> int {
+        if (!out || !chains) return set_err(BMM_E_ARG, "null argument");
+        *out = nullptr;
+        if (R < 1 || R > kTemperMaxR) return set_err(BMM_E_ARG, "a ladder has 1 to %d rungs", kTemperMaxR);
+        for (int r = 0; r < R; ++r) {
+            const bmm_chain* c = chains[r];
+            if (!c) return set_err(BMM_E_ARG, "rung %d: null chain", r);
+            for (int q = 0; q < r; ++q)
+                if (chains[q] == c) return set_err(BMM_E_ARG, "rung %d: the chain is rung %d already", r, q);
+            if (temper_refused(c)) {
+                const std::string why = g_err;
+                return set_err(BMM_E_UNSUPPORTED, "rung %d: %s", r, why.c_str());
+            }
+            if (c->dTrace && r > 0) return set_err(BMM_E_STATE, "rung %d: the chain is inside a run", r);
+            if (c->ladder && r > 0) return set_err(BMM_E_STATE, "rung %d: the chain is rung 0 of a run's ladder", r);
+        }
+        const bmm_chain* c0 = chains[0];
+        if (c0->temper_on && c0->temper_b != 1.0) return set_err(BMM_E_ARG, "rung 0: the first chain runs at inverse temperature 1 (unarmed, or armed with 1.0)");
+        double prev = 1.0;
+        for (int r = 1; r < R; ++r) {
+            const bmm_chain* c = chains[r];
+            if (!c->temper_on) return set_err(BMM_E_STATE, "rung %d: the chain is not armed (bmm_chain_set_temper)", r);
+            if (!(c->temper_b < prev)) return set_err(BMM_E_ARG, "rung %d: the inverse temperatures must decrease strictly (%.17g after %.17g)", r, c->temper_b, prev);
+            prev = c->temper_b;
+            if (c->slot != c0->slot || c->device != c0->device) return set_err(BMM_E_UNSUPPORTED, "rung %d: the rungs of a ladder live on one device", r);
+            const ChainParams &p = c->p, &p0 = c0->p;
+            if (p.mode != p0.mode) return set_err(BMM_E_ARG, "rung %d: another sampler than rung 0's", r);
+            if (p.N != p0.N || p.P != p0.P || p.K != p0.K) return set_err(BMM_E_ARG, "rung %d: N, P or K differ from rung 0's", r);
+            if (p.beta != p0.beta || p.gamma != p0.gamma || p.a != p0.a || p.b != p0.b || p.sample_alpha != p0.sample_alpha)
+                return set_err(BMM_E_ARG, "rung %d: beta, gamma, a, b or the treatment of alpha differ from rung 0's", r);
+            if (c->batch != c0->batch) return set_err(BMM_E_ARG, "rung %d: batch %lld, rung 0 has %lld", r, (long long)c->batch, (long long)c0->batch);
+            if (c->sweep != c0->sweep) return set_err(BMM_E_STATE, "rung %d: at sweep %d, rung 0 at sweep %d", r, c->sweep, c0->sweep);
+            if (!c->have_data || !c0->have_data) return set_err(BMM_E_STATE, "rung %d: no data yet", r);
+            if (c->bits != c0->bits || (c->bits ? c->dXb != c0->dXb : c->dX != c0->dX))
+                return set_err(BMM_E_STATE, "rung %d: the rungs of a ladder share one copy of the data (bmm_chain_share_data)", r);
+        }
+        HIP_TRY(hipSetDevice(c0->device));
+        std::unique_ptr<bmm_ladder, void (*)(bmm_ladder*)> l(new bmm_ladder(), bmm_ladder_destroy);
+        l->R = R; l->device = c0->device; l->seed = seed;
+        for (int r = 0; r < R; ++r) l->ch[r] = chains[r];
+        auto carve = [&](Carver& v) {
+            l->dCounters = v.take<long long>(2 * (size_t)kTemperMaxR);
+            l->dRec = v.take<TemperStep>((size_t)kTemperMaxR);
+            l->dAccept = v.take<int32_t>((size_t)kTemperMaxR);
+            l->dWalker = v.take<int32_t>((size_t)kTemperMaxR);
+        };
+        Carver measure{nullptr};
+        carve(measure);
+        HIP_TRY(hipMalloc(&l->dBlock, measure.used));
+        Carver real{l->dBlock};
+        carve(real);
+        HIP_TRY(hipMemset(l->dBlock, 0, measure.used));
+        int32_t w[kTemperMaxR];
+        for (int r = 0; r < kTemperMaxR; ++r) w[r] = r;
+        HIP_TRY(hipMemcpy(l->dWalker, w, sizeof w, hipMemcpyHostToDevice));
+        for (int r = 1; r < R; ++r) HIP_TRY(hipEventCreateWithFlags(&l->ready[r], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&l->done, hipEventDisableTiming));
+        *out = l.release();
+        return BMM_OK;
+    });
+}
+
+void bmm_ladder_destroy(bmm_ladder* l) {
+    if (!l) return;
+    (void)hipSetDevice(l->device);
+    for (int r = 0; r < l->R; ++r)
+        if (l->ch[r] && l->ch[r]->stream) (void)hipStreamSynchronize(l->ch[r]->stream);
+    for (hipEvent_t e : l->ready) if (e) (void)hipEventDestroy(e);
+    if (l->done) (void)hipEventDestroy(l->done);
+    if (l->dBlock) (void)hipFree(l->dBlock);
+    delete l;
+}
+
+int bmm_ladder_sweeps(bmm_ladder* l, int n, int swap_every) {
+    return guarded([&]() -> int {
+        if (!l) return set_err(BMM_E_ARG, "null ladder");
+        return ladder_sweeps(l, n, swap_every);
+    });
+}
+
+int bmm_ladder_exchange_step(bmm_ladder* l, bmm_exchange_step* out) {
+    return guarded([&]() -> int {
+        if (!l) return set_err(BMM_E_ARG, "null ladder");
+        int rc = ladder_same_sweep(l);
+        if (rc == BMM_OK) rc = lp_seated(l->ch[0]);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(l->device));
+        for (int r = 0; r < l->R; ++r)
+            if (!l->ch[r]->started) { rc = chain_start(l->ch[r]); if (rc) return rc; }
+        const uint32_t t = l->t;
+        rc = ladder_exchange(l, nullptr);
+        const int rs = ladder_sync(l);
+        if (rc || rs) return rc ? rc : rs;
+        if (out && l->R > 1) {
+            TemperStep h[kTemperMaxR];
+            HIP_TRY(hipMemcpy(h, l->dRec, (size_t)(l->R - 1) * sizeof(TemperStep), hipMemcpyDeviceToHost));
+            for (int r = 0; r + 1 < l->R; ++r) {
+                out[r].d = h[r].d; out[r].u = h[r].u; out[r].proposed = h[r].proposed; out[r].accepted = h[r].accepted;
+                out[r].point = (int32_t)t; out[r].pad = 0;
+            }
+        }
+        return BMM_OK;
+    });
+}
+
+int bmm_ladder_stats(bmm_ladder* l, int64_t* proposed, int64_t* accepted, int32_t* walker) {
+    return guarded([&]() -> int {
+        if (!l) return set_err(BMM_E_ARG, "null ladder");
+        int rc = ladder_sync(l);
+        if (rc) return rc;
+        long long h[2 * kTemperMaxR];
+        HIP_TRY(hipMemcpy(h, l->dCounters, sizeof h, hipMemcpyDeviceToHost));
+        for (int r = 0; r + 1 < l->R; ++r) {
+            if (proposed) proposed[r] = h[r];
+            if (accepted) accepted[r] = h[l->R - 1 + r];
+        }
+        if (walker) HIP_TRY(hipMemcpy(walker, l->dWalker, (size_t)l->R * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return BMM_OK;
+    });
 }
 
 }  // extern "C"
@@ -4523,6 +4817,10 @@ int run_body(bmm_chain* c, int nsamples, const RunIO& io, const RunOptions& opts
         auto step = [&](int j) { return st_run_sweep(c, st, j); };
         if (g_progress.fn && g_progress.every > 0) rc = run_sweeps_reported(c, nsamples, step);
         else for (int j = 1; j < nsamples && rc == BMM_OK; ++j) rc = step(j);
+    } else if (c->ladder) {  // parallel tempering: the rungs advance together, this chain is rung 0
+        bmm_ladder* const l = c->ladder;
+        auto step = [&](int) { return ladder_sweeps(l, 1, l->swap_every); };
+        rc = g_progress.fn && g_progress.every > 0 ? run_sweeps_reported(c, nsamples, step) : ladder_sweeps(l, nsamples - 1, l->swap_every);
     } else {
         rc = opts.hooks ? run_sweeps_hooked(c, nsamples, opts.hooks)
                    : (g_progress.fn && g_progress.every > 0 ? run_sweeps_reported(c, nsamples) : bmm_chain_sweeps(c, nsamples - 1));
@@ -4674,6 +4972,105 @@ int check_run_args(const int32_t* X, int nsamples, int burnin, const RunIO& io, 
     return BMM_OK;
 }
 
+// ---- a run's replica ladder (bmm_set_temper) ----
+// refused before any device is touched
+int temper_run_check(const RunOptions& opts, int sampler) {
+    if (!opts.temper.on) return BMM_OK;
+    const bmm_temper_out& o = opts.temper.o;
+    if (sampler != BMM_SAMPLER_COLLAPSED && sampler != BMM_SAMPLER_DP)
+        return set_err(BMM_E_UNSUPPORTED, "parallel tempering is offered for the collapsed and DP samplers only");
+    if (opts.alloc.on) return set_err(BMM_E_UNSUPPORTED, "parallel tempering is not offered for the allocation sampler");
+    if (opts.rel || opts.hooks) return set_err(BMM_E_UNSUPPORTED, "parallel tempering is not offered together with a relabelling run or a probability hand-off");
+    if (opts.sm.moves > 0) return set_err(BMM_E_UNSUPPORTED, "parallel tempering is not offered together with split-merge moves: their ratio would need the tempered likelihood");
+    if (opts.fs.on) return set_err(BMM_E_UNSUPPORTED, "parallel tempering is not offered together with feature selection");
+    if (o.R < 1 || o.R > kTemperMaxR) return set_err(BMM_E_ARG, "temper: a ladder has 1 to %d rungs", kTemperMaxR);
+    if (!o.inv_temp) return set_err(BMM_E_ARG, "temper: inv_temp is null");
+    if (o.swap_every < 1) return set_err(BMM_E_ARG, "temper: swap_every must be >= 1");
+    if (o.inv_temp[0] != 1.0) return set_err(BMM_E_ARG, "temper: inv_temp[0] must be 1");
+    for (int r = 1; r < o.R; ++r)
+        if (!(o.inv_temp[r] > 0.0 && o.inv_temp[r] < o.inv_temp[r - 1]))
+            return set_err(BMM_E_ARG, "temper: inv_temp[%d] must lie in (0, inv_temp[%d])", r, r - 1);
+    return BMM_OK;
+}
+// The helpers and the ladder of a run, released in this order ahead of the run's own chain.
+struct TemperRun {
+    bmm_chain* c0 = nullptr;
+    bmm_ladder* l = nullptr;
+    std::vector<bmm_chain*> helpers;
+    DevBuf lik, walker;
+    ~TemperRun() {
+        if (c0) c0->ladder = nullptr;
+        bmm_ladder_destroy(l);
+        for (bmm_chain* h : helpers) bmm_chain_destroy(h);
+    }
+};
+// chain 0 has its data and its starting state and has not started
+int temper_run_attach(bmm_chain* c, const RunOptions& opts, double alpha, int64_t batch, uint64_t seed, TemperRun& tr) {
+    if (!opts.temper.on) return BMM_OK;
+    const bmm_temper_out& o = opts.temper.o;
+    const ChainParams& p = c->p;
+    const int R = o.R, S = c->S;
+    if (R > 1 && c->sm_moves > 0) return set_err(BMM_E_UNSUPPORTED, "parallel tempering is not offered together with split-merge moves");
+    std::vector<bmm_chain*> rungs{c};
+    for (int r = 1; r < R; ++r) {
+        bmm_chain* h = nullptr;
+        int rc = bmm_chain_create(&h, p.mode, p.N, p.P, p.K, alpha, p.beta, p.gamma, p.a, p.b, batch, seed + (uint64_t)r, c->slot);
+        if (rc) return rc;
+        tr.helpers.push_back(h);
+        rungs.push_back(h);
+        if (c->bits) {
+            rc = bmm_chain_share_data(h, c);
+        } else {  // the int32 layout: the run's device matrix, borrowed
+            rc = bmm_chain_set_x_layout(h, BMM_X_INT32);
+            h->dX = c->dX;
+            h->have_data = true;
+        }
+        if (rc) return rc;
+        if (p.mode == MODE_COLLAPSED) {  // the run's initial allocation, as chain 0 holds it (0-based)
+            HIP_TRY(hipMemcpyAsync(h->dZ[0], c->dZ[0], (size_t)p.N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            h->have_init = true;
+        }
+        rc = bmm_chain_set_temper(h, 1, o.inv_temp[r]);
+        if (rc) return rc;
+    }
+    int rc = bmm_ladder_create(&tr.l, rungs.data(), R, seed);
+    if (rc) return rc;
+    tr.l->swap_every = o.swap_every;
+    tr.l->base = c->burnin;
+    if (o.loglik) {
+        std::vector<double> nan((size_t)S * R, std::nan(""));
+        HIP_TRY(tr.lik.alloc(nan.size() * sizeof(double)));
+        HIP_TRY(hipMemcpy(tr.lik.p, nan.data(), nan.size() * sizeof(double), hipMemcpyHostToDevice));
+        tr.l->lik_rows = tr.lik.as<double>();
+    }
+    if (o.walker_cold) {
+        HIP_TRY(tr.walker.alloc((size_t)S * sizeof(int32_t)));
+        HIP_TRY(hipMemset(tr.walker.p, 0, (size_t)S * sizeof(int32_t)));
+        tr.l->walker_rows = tr.walker.as<int32_t>();
+    }
+    tr.c0 = c;
+    c->ladder = tr.l;
+    return BMM_OK;
+}
+int temper_run_collect(bmm_chain* c, const RunOptions& opts, TemperRun& tr, int rc) {
+    if (!opts.temper.on || !tr.l) return rc;
+    const bmm_temper_out& o = opts.temper.o;
+    const int R = o.R, S = c->S;
+    const int rs = ladder_sync(tr.l);
+    if (rc || rs) return rc ? rc : rs;
+    rc = bmm_ladder_stats(tr.l, o.proposed, o.accepted, nullptr);
+    if (rc) return rc;
+    if (o.walker_cold) HIP_TRY(hipMemcpy(o.walker_cold, tr.walker.p, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (o.loglik) {  // [S][R] on the device, S x R column-major for the caller
+        std::vector<double> rows((size_t)S * R);
+        HIP_TRY(hipMemcpy(rows.data(), tr.lik.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int s = 0; s < S; ++s)
+            for (int r = 0; r < R; ++r) o.loglik[(size_t)r * S + s] = rows[(size_t)s * R + r];
+    }
+    return BMM_OK;
+}
+
 int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int K, double alpha, double beta,
               double gamma, double a, double b, int burnin, int64_t batch, uint64_t seed, int device,
               const RunIO& io, const RunOptions& opts) {
@@ -4687,6 +5084,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
         if (rc == BMM_OK) rc = pred_run_check(opts);
         if (rc == BMM_OK) rc = fs_run_check(opts, sampler, beta, gamma);
         if (rc == BMM_OK) rc = alloc_run_check(opts);
+        if (rc == BMM_OK) rc = temper_run_check(opts, sampler);
         if (rc == BMM_OK) rc = st_run_check(opts, burnin, K);
         if (rc == BMM_OK) rc = ecr_run_check(opts, nsamples - burnin, N, K);
         if (rc) return rc;
@@ -4706,6 +5104,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
         c->crew = &crew;
         {
             struct Guard { bmm_chain* c; ~Guard() { bmm_chain_destroy(c); } } guard{c};
+            TemperRun temper;  // (released ahead of the chain)
             rc = run_prepare(c, nsamples, burnin);
             if (rc == BMM_OK) rc = run_start_state(c, io, opts.init.kind != 0);
             if (rc) return rc;
@@ -4730,8 +5129,10 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             if (rc == BMM_OK) rc = fs_run_attach(c, opts, fs_rec);
             if (rc == BMM_OK) rc = alloc_run_attach(c, opts, k_rec);
             if (rc == BMM_OK) rc = lp_run_attach(c, opts, lp_rec);
+            if (rc == BMM_OK) rc = temper_run_attach(c, opts, alpha, batch, seed, temper);
             if (rc) return rc;
             rc = run_body(c, nsamples, io, opts);
+            rc = temper_run_collect(c, opts, temper, rc);
             rc = lp_run_collect(c, opts, lp_rec, rc);
             rc = sm_run_collect(c, opts, rc);
             rc = alloc_run_collect(c, opts, k_rec, rc);
@@ -5100,6 +5501,12 @@ int bmm_set_loo_summary(const bmm_loo_out* out) {
 int bmm_set_logpost(const bmm_logpost_out* out) {
     g_armed.logpost.on = out != nullptr;
     if (out) g_armed.logpost.o = *out;
+    return BMM_OK;
+}
+
+int bmm_set_temper(const bmm_temper_out* out) {
+    g_armed.temper.on = out != nullptr;
+    if (out) g_armed.temper.o = *out;
     return BMM_OK;
 }
 

@@ -3567,6 +3567,213 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_alloc_tables(ChainParam
     if (k == 0 && threadIdx.x < 256) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];
 }
 
+// ---- parallel tempering (include/bmm_mcmc.h "parallel tempering") --------------------------
+// The table build of a chain that targets p(alpha) p(z | alpha) p(x | z)^b: k_count_tables<false> with every
+// per-feature term multiplied once by the inverse temperature b after its denominator is subtracted, in all four roles.
+// The category's constant (the allocation prior) is untouched; the DP's new-cluster constant carries b on its P prior
+// Bernoulli terms only.  It folds and clears the deltas as k_count_tables does and writes the same image, never a
+// packed one, so the resample kernels are the ones every chain runs.  Roles and order of operations are those of
+// k_count_tables: with b = 1 the two write the same bits (x * 1.0 is x).  The extra multiply sits behind the log_ of
+// a term thread, off wave 8's chain of constants.
+__global__ __launch_bounds__(kCountTablesThreads) void k_temper_tables(ChainParams p, int32_t* __restrict__ Nk,
+                                                                      int32_t* __restrict__ S,
+                                                                      int32_t* __restrict__ dNk,
+                                                                      int32_t* __restrict__ dS,
+                                                                      const double* __restrict__ alpha_ptr, double b,
+                                                                      double* __restrict__ tab) {
+    __shared__ double e1[kMaxP], e0[kMaxP], m1[kMaxP], m0[kMaxP], cst[4];  // cst: Cp, Cm, the two denominators
+    const int k = blockIdx.x;
+    const TableLayout L = layout_of(p, true);
+    const int P = p.P;
+    const bool is_label = k < p.K;
+    const int role = threadIdx.x >> 7;
+    const int dl = role < 4 ? (threadIdx.x & 127) : kMaxP;
+    int32_t n_old = 0, n_dl = 0, s_old = 0, s_dl = 0;
+    const size_t KP = (size_t)p.K * P;
+    if (is_label) { n_old = Nk[k]; n_dl = delta_take(dNk, k, p.K); }
+    if (is_label && dl < P) { s_old = S[(size_t)k * P + dl]; s_dl = delta_take(dS, (size_t)k * P + dl, KP); }
+    const double alpha = *alpha_ptr;
+    const int64_t n = (int64_t)n_old + n_dl;
+    const double bg = p.beta + p.gamma;
+    if (role == 4) {
+        const int lane = threadIdx.x & 63;
+        const bool dp_new = p.mode == MODE_DP && k == p.K;
+        const double ak = p.mode == MODE_COLLAPSED ? div_(alpha, (double)p.K) : 0.0;
+        double arg = 1.0;
+        bool need = false;
+        switch (lane) {
+            case 0: arg = bg + (double)n; need = is_label && n > 0; break;                 // log(beta+gamma+n)
+            case 1: arg = bg + (double)(n - 1); need = is_label && n > 1; break;           // ... with one removed
+            case 2: arg = (double)n + ak; need = is_label && n > 0; break;                 // log(n + alpha/K), log n
+            case 3: arg = (double)(n - 1) + ak; need = is_label && n > 1; break;
+            case 4: arg = (double)(p.Ntot - 1) + alpha; need = true; break;                // log(N - 1 + alpha)
+            case 5: arg = alpha; need = dp_new; break;
+            case 6: arg = p.beta; need = dp_new; break;
+            case 7: arg = bg; need = dp_new; break;
+            default: break;
+        }
+        const double v = need ? log_(arg) : 0.0;
+        const double den_p = __shfl(v, 0), den_m = __shfl(v, 1), ln = __shfl(v, 2), lm = __shfl(v, 3);
+        const double ldN = __shfl(v, 4), la = __shfl(v, 5), lb = __shfl(v, 6), lbg = __shfl(v, 7);
+        if (lane == 0) {
+            double cp = neg_inf(), cm = neg_inf();
+            if (is_label) {
+                if (n > 0) cp = ln - ldN;
+                if (n > 1) cm = lm - ldN;
+            } else if (dp_new) {
+                cp = (la - ldN) + b * ((double)P * (lb - lbg));  // the prior of opening a cluster, then its tempered likelihood
+            }
+            tab[L.cp() + k] = cp;
+            tab[L.cm() + k] = cm;
+            cst[0] = cp; cst[1] = cm; cst[2] = den_p; cst[3] = den_m;  // read after the first barrier below
+            reinterpret_cast<int32_t*>(tab + L.nk())[k] = (int32_t)n;
+        }
+    }
+    for (int c0 = 0; c0 < P; c0 += kChunkP) {  // kChunkP features (whole groups) at a time
+        const int pc = P - c0 < kChunkP ? P - c0 : kChunkP;
+        int32_t s = 0;
+        double raw = 0.0;
+        bool have = false;
+        if (dl < pc && is_label) {
+            const int d = c0 + dl;
+            s = c0 == 0 ? s_old + s_dl : S[(size_t)k * P + d] + delta_take(dS, (size_t)k * P + d, KP);
+            // term_x1 / term_x0 of bmm_spec.h, the denominator subtracted and the power applied below
+            if (role == 0) { have = n > 0; raw = have ? log_(p.beta + (double)s) : 0.0; }
+            else if (role == 1) { have = n > 0; raw = have ? log_((p.gamma + (double)n) - (double)s) : 0.0; }
+            else if (role == 2) { have = n > 1 && s >= 1; raw = have ? log_(p.beta + (double)((int64_t)s - 1)) : 0.0; }
+            else { have = n > 1 && s <= n - 1; raw = have ? log_((p.gamma + (double)(n - 1)) - (double)s) : 0.0; }
+        }
+        __syncthreads();  // the constants are in place; every role has read S + dS before either is rewritten
+        if (dl < pc) {
+            const double t = have ? b * (raw - cst[role < 2 ? 2 : 3]) : 0.0;
+            (role == 0 ? e1 : role == 1 ? e0 : role == 2 ? m1 : m0)[dl] = t;
+            if (role == 0 && is_label) {
+                const int d = c0 + dl;
+                S[(size_t)k * P + d] = s;
+                delta_clear(dS, (size_t)k * P + d, KP);
+            }
+        }
+        __syncthreads();
+        write_group_tables(p.W, e1, e0, pc, c0, p.KT, k, cst[0], tab + L.tp());
+        write_group_tables(kGroupWm, m1, m0, pc, c0, p.KT, k, cst[1], tab + L.tm());
+        __syncthreads();
+    }
+    if (is_label && threadIdx.x == 0) {  // every thread read the old pair before the barriers above
+        Nk[k] = (int32_t)n;
+        delta_clear(dNk, k, p.K);
+    }
+    if (k == 0 && threadIdx.x < 256) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];
+}
+
+// The exchange of a replica ladder: R <= kTemperMaxR chains ("rungs") over the same data at inverse temperatures
+// 1 = b_0 > b_1 > ...; rung r's row of k_log_joint_finish holds L_r = log p(x | z_r) of its current state.
+// k_temper_decide: one wave; lane j takes pair r = 2 j + (t mod 2), the pairs of exchange point t (they are disjoint,
+// so all are decided at once): d, u and the decision by the rules of bmm_spec.h, the record, the counters and the
+// walker ids, all plain stores by the deciding lane; the pairs that are not proposed at t get an empty record from
+// the lane that would own them at t + 1.  `lik_row` (or null) receives every rung's L as it stands after the
+// exchange.  k_temper_exchange: one y-slice of the grid per proposed pair, stream-ordered behind the lane that
+// wrote accept[r], so a slice whose pair was rejected returns at once and no block reads a cell another is writing;
+// an accepted pair swaps the two chains' current label rows, folded statistics, every replica of the pending deltas
+// as they stand (no fold) and the concentration.  States move, temperatures stay.  Nothing is atomic in global memory.
+constexpr int kTemperMaxR = 8;
+constexpr int kTemperThreads = 256;
+struct TemperStep {
+    double d, u;
+    int32_t proposed, accepted;
+};
+struct TemperRung {
+    const double* lj_out;  // the rung's log joint row: [0] = log_lik
+    int32_t* z;            // its current label row [N]
+    int32_t *Nk, *S;       // [K], [K * P]
+    int32_t *dNk, *dS;     // kDeltaReps replicas of each
+    double* alpha;
+    double* alpha_row;     // or null: the cell of the alpha trace that holds this state's concentration
+    double b;
+};
+struct TemperArgs {
+    TemperRung rung[kTemperMaxR];
+    int R;
+    uint32_t t;
+    unsigned long long seed;
+    int32_t* accept;       // [R - 1]
+    int32_t* walker;       // [R]
+    long long* counters;   // proposed [R - 1], then accepted [R - 1]
+    TemperStep* rec;       // [R - 1]
+    double* lik_row;       // or null: [R]
+    int64_t N;
+    int K, P;
+};
+__global__ __launch_bounds__(64) void k_temper_decide(TemperArgs a) {
+    const int lane = threadIdx.x, par = (int)(a.t & 1u);
+    const int r = 2 * lane + par, idle = 2 * lane + 1 - par;  // this lane's pair at t, and the one it leaves alone
+    if (idle + 1 < a.R) {
+        TemperStep e;
+        e.d = qnan(); e.u = qnan(); e.proposed = 0; e.accepted = 0;
+        a.rec[idle] = e;
+        a.accept[idle] = 0;
+    }
+    if (r + 1 < a.R) {
+        const double Lr = a.rung[r].lj_out[0], Lr1 = a.rung[r + 1].lj_out[0];
+        TemperStep e;
+        e.d = temper_log_ratio(a.rung[r].b, a.rung[r + 1].b, Lr, Lr1);
+        e.u = temper_uniform(a.seed, (uint32_t)r, a.t);
+        const bool acc = temper_accepts(e.d, e.u);
+        e.proposed = 1; e.accepted = acc ? 1 : 0;
+        a.rec[r] = e;
+        a.accept[r] = e.accepted;
+        a.counters[r] += 1;
+        if (acc) {
+            a.counters[a.R - 1 + r] += 1;
+            const int32_t w = a.walker[r];
+            a.walker[r] = a.walker[r + 1];
+            a.walker[r + 1] = w;
+        }
+        if (a.lik_row) { a.lik_row[r] = acc ? Lr1 : Lr; a.lik_row[r + 1] = acc ? Lr : Lr1; }
+    }
+    // a rung outside every pair of this point: the first at an odd point, the last when the pairs end before it
+    if (a.lik_row && lane < a.R) {
+        const int first = lane - ((lane - par) & 1);  // the pair that would hold rung `lane`
+        if (lane < par || first + 1 >= a.R) a.lik_row[lane] = a.rung[lane].lj_out[0];
+    }
+}
+// n int32 of x and y exchanged by the workgroups of one grid slice: 16 bytes per access where both are so aligned
+__device__ __forceinline__ void temper_swap(int32_t* __restrict__ x, int32_t* __restrict__ y, int64_t n) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    int64_t done = 0;
+    if ((((uintptr_t)x | (uintptr_t)y) & 15u) == 0) {
+        int4* const x4 = reinterpret_cast<int4*>(x);
+        int4* const y4 = reinterpret_cast<int4*>(y);
+        const int64_t n4 = n >> 2;
+        for (int64_t i = tid; i < n4; i += nth) {
+            const int4 u = x4[i], v = y4[i];
+            x4[i] = v; y4[i] = u;
+        }
+        done = n4 << 2;
+    }
+    for (int64_t i = done + tid; i < n; i += nth) {
+        const int32_t u = x[i], v = y[i];
+        x[i] = v; y[i] = u;
+    }
+}
+__global__ __launch_bounds__(kTemperThreads) void k_temper_exchange(TemperArgs a) {
+    const int r = 2 * (int)blockIdx.y + (int)(a.t & 1u);
+    if (r + 1 >= a.R || !a.accept[r]) return;
+    const TemperRung& x = a.rung[r];
+    const TemperRung& y = a.rung[r + 1];
+    const int64_t K = a.K, KP = (int64_t)a.K * a.P;
+    temper_swap(x.z, y.z, a.N);
+    temper_swap(x.Nk, y.Nk, K);
+    temper_swap(x.S, y.S, KP);
+    temper_swap(x.dNk, y.dNk, K * kDeltaReps);
+    temper_swap(x.dS, y.dS, KP * kDeltaReps);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const double ax = *x.alpha, ay = *y.alpha;
+        *x.alpha = ay; *y.alpha = ax;
+        if (x.alpha_row) *x.alpha_row = ay;
+        if (y.alpha_row) *y.alpha_row = ax;
+    }
+}
+
 // The eject / absorb move of Nobile & Fearnside (2007), p_E integrated out of the proposal density: k_ea_launch,
 // k_ea_decide, k_ea_commit, stream-ordered; the host never reads anything back.  One byte per row.  An eject of label
 // j1 into the appended label j2 = K: 0 a row of j1 that stays, 1 one that moves.  An absorb of j2 into j1: 0 a row of

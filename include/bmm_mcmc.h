@@ -1041,6 +1041,77 @@ int bmm_device_log_joint(int device, const int32_t* X, int64_t N, int P, int sam
                          int sample_alpha, double a, double b, const double* log_prior_k, const int32_t* z, int S,
                          const double* alpha, const int32_t* k_open, const uint8_t* mask, double rho, double* out);
 
+/* ---- parallel tempering: a replica ladder on the device ----------------------------------------
+ * Metropolis-coupled MCMC for the two counting samplers (collapsed, dp).  A ladder has R <= 8 rungs with inverse
+ * temperatures 1 = b_0 > b_1 > ... > b_{R-1} > 0; rung r holds a whole chain state (z, the counts, alpha) and targets
+ *     pi_r(z, alpha)  proportional to  p(alpha) p(z | alpha) p(x | z)^{b_r}.
+ * Only the marginal likelihood is tempered.  THE ONE-ROW CONDITIONAL of a tempered chain is the usual one with every
+ * per-feature log-predictive term multiplied once by b after its denominator is subtracted, t = b * (log(.) - log(beta +
+ * gamma + n)), in the table of the full statistics and in the one with the scored row removed alike; the category's
+ * constant, log(n_k + alpha/K) - log(N - 1 + alpha) (collapsed) or log n_k - log(N - 1 + alpha) (dp), is untouched, and
+ * the DP's new-cluster option is (log alpha - log(N - 1 + alpha)) + b * (P * (log beta - log(beta + gamma))).  With b = 1
+ * every table entry has the bits of an unarmed chain's (x * 1.0 is x).  A tempered chain runs the kernel forms of a
+ * chain with a feature mask: none that builds its own tables, no packed form; its draws are the same function of the
+ * tables as every chain's.
+ * THE EXCHANGE.  The priors are untempered, so they cancel: for neighbouring rungs r and r + 1, with L = log_lik of each
+ * rung's current state (column 0 of its log joint row, the section above: the same order of sums, the same bits),
+ *     d = (b_r - b_{r+1}) * (L_{r+1} - L_r),
+ * the exchange is accepted iff d >= 0 or u < expw(d) (the draw's weight exponential, bmm_spec.h); a NaN d rejects.
+ * u is the 52-bit uniform of the first two words of Philox4x32-10 at counter (r, 0, t, kStreamTemper = 14) under the
+ * LADDER's seed, t the exchange point, counted from 0 over the life of the ladder.  Point t proposes the pairs with
+ * r = t (mod 2); they are disjoint, so all are decided (one wave, one lane per pair, plain stores) and carried out
+ * (one grid slice per pair, stream-ordered behind the decision) at once.
+ * STATES MOVE, TEMPERATURES STAY: an accepted exchange swaps, in place on the device, the two chains' current label
+ * rows, Nk, S, every replica of the pending count deltas as they stand (no fold) and alpha.  Each chain keeps its rung,
+ * its seed, its streams and its kernels; rung 0 is always chains[0], an ordinary chain at b = 1 with every option and
+ * recorder it has otherwise.  walker[r] names the state at rung r: it starts as r and is swapped with the state.
+ * Refused with BMM_E_UNSUPPORTED, before anything is touched: stick-breaking, full and allocation chains, a chain with
+ * a feature mask, split-merge moves on any rung, a sharded chain, rungs on different devices.  Armed chains refuse
+ * those options in turn. */
+/* on: the chain's table builds run the tempered twin at inv_temp (0 < inv_temp <= 1; on with 1.0 runs the twin kernel
+ * and gives an unarmed chain's bits); off: the chain is as it was.  Between sweeps, any time. */
+int bmm_chain_set_temper(bmm_chain* c, int on, double inv_temp);
+int bmm_chain_get_temper(const bmm_chain* c, int* on, double* inv_temp);
+typedef struct bmm_ladder bmm_ladder;
+typedef struct bmm_exchange_step {
+    double d, u;        /* NaN for a pair that was not proposed at this point */
+    int32_t proposed;   /* 1 for the pairs with r = t (mod 2) */
+    int32_t accepted;
+    int32_t point;      /* t */
+    int32_t pad;
+} bmm_exchange_step;
+/* chains[0] unarmed or at 1.0, the others armed with strictly decreasing powers; one device, one sampler, equal N, P, K,
+ * beta, gamma, a, b, batch and sweep index; the data shared (bmm_chain_share_data; the int32 layout: one device matrix);
+ * nothing armed that the list above refuses.  BMM_E_ARG, or BMM_E_STATE where a chain's state is at fault, naming the
+ * rung.  The chains stay the caller's and must outlive the ladder. */
+int bmm_ladder_create(bmm_ladder** out, bmm_chain* const* chains, int R, uint64_t seed);
+void bmm_ladder_destroy(bmm_ladder* l);
+/* n sweeps of every rung, each on its own stream, an exchange point after every swap_every-th (>= 1) of them: every
+ * rung scores its state on its stream, chains[0]'s stream waits for them, decides and exchanges, the others wait for
+ * that.  One host thread; it never blocks, and the call returns without waiting.  A chains[0] armed for the log joint
+ * trace folds its rows after the exchange. */
+int bmm_ladder_sweeps(bmm_ladder* l, int n, int swap_every);
+/* one exchange point now; out: R - 1 records (or NULL).  Waits.  BMM_E_STATE for a DP ladder before its first sweep. */
+int bmm_ladder_exchange_step(bmm_ladder* l, bmm_exchange_step* out);
+/* proposed, accepted: R - 1 each; walker: R; any may be NULL.  Waits. */
+int bmm_ladder_stats(bmm_ladder* l, int64_t* proposed, int64_t* accepted, int32_t* walker);
+/* For a run: armed per calling thread for the NEXT bmm_collapsed_run / bmm_dp_run of that thread and disarmed when that
+ * call returns, as bmm_set_logpost; NULL disarms.  The run creates R - 1 helper chains with seed + r (mod 2^64) over the
+ * run's planes, gives them the run's initialK (collapsed), and drives the ladder under the run's seed; everything the
+ * call returns comes from chains[0], whose trace rows are the states after the exchange.  R = 1 is the run without it,
+ * byte for byte.  Refused with BMM_E_UNSUPPORTED together with a relabelling run, a probability hand-off, split-merge
+ * moves, feature selection, the allocation sampler or bmm_multi_run (which disarms it). */
+typedef struct bmm_temper_out {
+    int R;
+    const double* inv_temp;  /* R values, inv_temp[0] = 1 */
+    int swap_every;          /* >= 1 */
+    int64_t* proposed;       /* R - 1, or NULL */
+    int64_t* accepted;       /* R - 1, or NULL */
+    int32_t* walker_cold;    /* S, or NULL: the walker at rung 0 after each kept sweep (row 0 without burn-in: 0) */
+    double* loglik;          /* S x R column-major, or NULL: every rung's log_lik after the exchange point of a kept sweep, NaN elsewhere */
+} bmm_temper_out;
+int bmm_set_temper(const bmm_temper_out* out);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
