@@ -722,6 +722,8 @@ def _make_temper(temper, swap_every, S, chains, hottest=0.1):
         return None
     if int(chains) > 1:
         raise _capi.BmmError(2, "temper= is offered per chain (chains=1): the rungs of a ladder are its chains")
+    if _np.ndim(temper) == 0 and not 1 <= int(temper) <= TEMPER_MAX_RUNGS:  # (as the library refuses a sequence of that length)
+        raise _capi.BmmError(1, "temper: a ladder has 1 to %d rungs" % TEMPER_MAX_RUNGS)
     b = temper_ladder(temper, hottest) if _np.ndim(temper) == 0 else _np.asarray(temper, dtype=_np.float64).ravel()
     return _Temper(b, swap_every, S)
 

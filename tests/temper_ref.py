@@ -6,7 +6,10 @@ at `z` with the row's own contribution removed (what the device computes at batc
 conditional at batch = 1): every per-feature log-predictive term times b, the allocation prior untouched.  exchange_*
 restate the exchange rule and its uniform; restated_ladder is a whole ladder on a NumPy generator for small N;
 scan_matrix / exchange_matrix are the exact transition matrices of the tempered one-row scan over the partitions of a
-small data set and of one exchange point on the product space of two rungs."""
+small data set and of one exchange point on the product space of two rungs; product_scan / product_exchange apply the
+same two to a joint distribution over any number of rungs without forming the matrix.  The constants and the cases of
+the device tests (ladders, swap shapes, table edges, the replayed run) are chosen here and checked on the CPU in
+tests/test_temper_ref.py."""
 import os
 import sys
 
@@ -21,16 +24,72 @@ import split_merge_ref as smr  # noqa: E402
 
 STREAM = 14  # kStreamTemper
 
-# the exchange-decision test (tests/test_gpu_temper.py section 3): N, P, K, the data's seed and the powers of a ladder
-# of two and of five rungs, chosen so that in 60 exchange points with one sweep between them every pair both accepts
-# and rejects at least 10 of its proposals (tests/test_temper_ref.py holds the restated ladder to that)
+# the exchange-decision test (tests/test_gpu_temper.py section 3): N, P, K, the data's seed and the powers of ladders
+# of two, four, five and eight rungs, chosen so that in 60 exchange points with one sweep between them every pair both
+# accepts and rejects at least EXCHANGE_FLOOR of its proposals (tests/test_temper_ref.py holds the restated ladder to that)
 EXCHANGE_SHAPE = (300, 8, 4)
 EXCHANGE_THETAS = (0.5,)  # one component: the posterior over allocations is diffuse and log_lik moves smoothly with the power
 EXCHANGE_DATA_SEED = 3
 # (log_lik of this shape falls by about 300 per unit of power near 1 and spreads by about 15: steps of 0.03 to 0.04 at the top,
 # wider further down, put d near -1)
-EXCHANGE_POWERS = {2: (1.0, 0.97), 5: (1.0, 0.96, 0.915, 0.85, 0.765)}
+EXCHANGE_POWERS = {2: (1.0, 0.97), 4: (1.0, 0.96, 0.915, 0.85), 5: (1.0, 0.96, 0.915, 0.85, 0.765),
+                   8: (1.0, 0.96, 0.915, 0.85, 0.765, 0.66, 0.53, 0.38)}
 EXCHANGE_STEPS = 60
+# what every pair must both accept and reject at least, on the device and in the restatement: the ladders of four and
+# of eight (an even number of rungs above two: both end rungs idle at the odd points; the full ladder: four slices of
+# the exchange grid at the even points, three at the odd) are held to 3, which the restatement clears with room (its
+# worst count over three generator seeds is 7 of 30)
+EXCHANGE_FLOOR = {2: 10, 4: 3, 5: 10, 8: 3}
+
+# the run a hand-built ladder replays row by row (tests/test_gpu_temper_ladders.py): N = 301 puts three of four rows of
+# the label trace off a 16-byte boundary; powers in steps of 0.05, at which the restated ladder accepts 10 to 16 of
+# rung 0's 20 proposals in 39 sweeps and rejects the rest, either sampler (tests/test_temper_ref.py)
+REPLAY_SHAPE = (301, 33, 5)
+REPLAY_THETAS = (0.3, 0.5, 0.7)
+REPLAY_DATA_SEED = 4
+REPLAY_POWERS = {3: (1.0, 0.95, 0.9), 4: (1.0, 0.95, 0.9, 0.85), 8: (1.0, 0.95, 0.9, 0.85, 0.8, 0.75, 0.7, 0.65)}
+REPLAY_MAXK = 12    # of the DP runs
+REPLAY_SWEEPS = 40  # nsamples of the run: sweeps 1 .. 39
+REPLAY_BATCH = 64
+REPLAY_SEED = 21
+
+# the shapes at which temper_swap leaves its first trip and its 16-byte body: K = 37 and K * P = 1369 leave a scalar
+# tail of one, S and the eight delta replicas take several passes of a one-block grid; N = 300 001 takes a second pass
+# of the 256-block grid and leaves one label to the tail
+SWAP_SHAPES = ((64, 37, 37), (300_001, 8, 4))
+
+
+def swap_case(N, P, K):
+    """(X, z_a, z_b), labels 1-based: two allocations that differ in every row -- so in the last label, the scalar
+    tail of N = 300 001 -- and in the last cell of Nk and of S: z_a seats the first half of the rows, whose last
+    column is all ones, under label K and the rest under label 1; z_b uses labels 2 .. K - 1 only."""
+    rng = np.random.default_rng(N + 7 * P + K)
+    half = N // 2
+    X = (rng.random((N, P)) < np.where(np.arange(N) < half, 0.9, 0.1)[:, None]).astype(np.int32)
+    X[:half, P - 1] = 1
+    z_a = np.where(np.arange(N) < half, K, 1).astype(np.int32)
+    z_b = rng.integers(2, K, N).astype(np.int32)
+    return np.asfortranarray(X), z_a, z_b
+
+
+# the table edges of the tempered build on purpose (n = 0, n = 1, n = 2, s = 0, s = n): labels 0-based
+EDGE_SHAPE = (300, 37, 6)
+EDGE_EMPTY, EDGE_SINGLE, EDGE_PAIR = 1, 2, 3
+EDGE_ROWS = {"single": (5,), "pair": (10, 11)}
+
+
+def edge_case():
+    """(X, z): column 0 all zeros, column 1 all ones; label 1 empty, label 2 holds row 5 alone, label 3 rows 10 and 11,
+    labels 0, 4 and 5 share the rest"""
+    N, P, K = EDGE_SHAPE
+    X, _ = mixture(N, P, [0.2, 0.5, 0.8], 3)
+    X = np.array(X)
+    X[:, 0] = 0
+    X[:, 1] = 1
+    z = np.array([0, 4, 5])[np.random.default_rng(9).integers(0, 3, N)]
+    z[list(EDGE_ROWS["single"])] = EDGE_SINGLE
+    z[list(EDGE_ROWS["pair"])] = EDGE_PAIR
+    return np.asfortranarray(X.astype(np.int32)), z
 
 
 def mixture(N, P, thetas, seed):
@@ -190,6 +249,28 @@ def scan_matrix(X, parts, alpha, beta, gamma, b, K):
         for zt, pr in dist.items():
             T[si, index[zt]] += pr
     return T
+
+
+def product_scan(J, Ts):
+    """One scan of every rung of a ladder on the product space: J[s_0, ..., s_{R-1}] the joint distribution over the
+    rungs' partitions, Ts[r] the scan matrix of rung r.  The rungs move independently."""
+    for r, T in enumerate(Ts):
+        J = np.moveaxis(np.tensordot(J, T, axes=([r], [0])), -1, r)
+    return J
+
+
+def product_exchange(J, L, powers, pairs):
+    """One exchange point on the product space of R rungs: every pair (r, r + 1) in `pairs` (disjoint) is swapped with
+    probability min(1, exp((b_r - b_{r+1}) (L[s_{r+1}] - L[s_r]))).  exchange_matrix, without the matrix."""
+    L = np.asarray(L)
+    for r in pairs:
+        d = (powers[r] - powers[r + 1]) * (L[None, :] - L[:, None])  # d[s_r, s_{r+1}]
+        a = np.where(d >= 0, 1.0, np.exp(np.minimum(d, 0.0)))
+        M = np.moveaxis(J, (r, r + 1), (0, 1))
+        A = a.reshape(a.shape + (1,) * (J.ndim - 2))
+        M = (1.0 - A) * M + np.swapaxes(A * M, 0, 1)  # the mass at (s, s') that moves lands at (s', s)
+        J = np.moveaxis(M, (0, 1), (r, r + 1))
+    return J
 
 
 def exchange_matrix(L, b0, b1):

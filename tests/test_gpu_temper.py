@@ -89,6 +89,48 @@ def test_tempered_probabilities_equal_the_restatement(bmm, N, P, K, sampler, lay
         assert not c.kernel_shape()["builds_own_tables"]
 
 
+@pytest.mark.parametrize("layout", ["bits", "int32"])
+@pytest.mark.parametrize("sampler", ["collapsed", "dp"])
+def test_tempered_probabilities_at_the_table_edges(bmm, sampler, layout):
+    """The edges of k_temper_tables on purpose (tests/temper_ref.py edge_case): an empty label (n = 0: both constants
+    -inf, no term), a singleton (n = 1: nothing left with its row removed), a pair, a column of zeros (s = 0) and a
+    column of ones (s = n) in every label.  The finite chain holds the allocation as its starting labels (only a DP
+    chain takes labels between sweeps), so its first table build also folds the counts from the delta replicas.
+    What the edges can show: a singleton or an empty label given a constant (its row would get weight the reference
+    denies it).  The `have` guards at s = 0 and s = n - 1 of the own-cluster terms protect entries no draw reads (a row
+    of the label with x = 1 makes s >= 1): dropping them changes no probability, here or anywhere."""
+    N, P, K = tr.EDGE_SHAPE
+    X, z = tr.edge_case()
+    rows = np.unique(np.concatenate([tr.EDGE_ROWS["single"], tr.EDGE_ROWS["pair"], np.arange(0, 60), np.arange(N - 30, N)]))
+    at = {name: [int(np.flatnonzero(rows == i)[0]) for i in ids] for name, ids in tr.EDGE_ROWS.items()}
+    z1 = (z + 1).astype(np.int32)
+    for b in POWERS:
+        with _chain(bmm, sampler, X, K, N, 11, layout, initial=z1) as c:
+            if sampler == "dp":
+                c.sweeps(2)
+                c.set_labels(z1)
+            c.set_temper(b)
+            np.testing.assert_array_equal(c.labels(), z1)
+            probs = c.sweep_probs()
+        want = tr.z_conditional(X, z, K, ALPHA, BETA, GAMMA, b, sampler, rows=rows)
+        got = probs[rows]
+        # the edge is there, by the reference's own account
+        if sampler == "collapsed":
+            assert np.all(want[:, tr.EDGE_EMPTY] == 0.0) and want[at["single"][0], tr.EDGE_SINGLE] == 0.0
+        else:
+            assert np.all(want[:, tr.EDGE_EMPTY] > 0.0) and want[at["single"][0], tr.EDGE_SINGLE] == 0.0
+        assert np.all(want[at["pair"], tr.EDGE_PAIR] > 0.0)
+        big = want > 1e-300
+        rel = np.abs(got[big] - want[big]) / want[big]
+        for name, idx in at.items():
+            print("%s %s b=%g %s rows: worst relative %.2e" % (sampler, layout, b, name, (np.abs(got[idx] - want[idx])[big[idx]] / want[idx][big[idx]]).max()))
+        print("%s %s b=%g all %d rows: worst relative %.2e" % (sampler, layout, b, len(rows), rel.max()))
+        assert rel.max() <= 1e-12
+        assert np.all(got[~big] <= 1e-300)
+        if sampler == "dp":
+            assert np.all(got[:, tr.EDGE_EMPTY] > 0.0)
+
+
 # ---------------------------------------------------------------- 2. every form
 @pytest.mark.parametrize("env,sampler,N,P,K,batch", tfs.FORMS)
 def test_every_form_power_one_is_the_unarmed_chain_and_a_power_is_the_same_chain_on_every_form(bmm, dbg_lib, env, sampler, N, P, K, batch):
@@ -152,7 +194,10 @@ def test_sixty_exchange_points_replayed_from_the_rungs_own_rows(bmm, R):
             for c in chains:
                 c.sweeps(1)
             L = [c.logpost_state()["log_lik"] for c in chains]
-            rec = ladder.exchange_step()
+            before = [_state(c) for c in chains]
+            for st in before:                                                     # every sweep went on from a whole state
+                _counts_belong_to_the_labels(X, K, st)
+            rec, _ = _exchange_and_check(bmm, X, K, chains, ladder, before, go_on=False)
             pairs = tr.proposed_pairs(R, t)
             assert pairs == list(range(t % 2, R - 1, 2))                        # parity alternates
             for r in range(R - 1):
@@ -182,7 +227,13 @@ def test_sixty_exchange_points_replayed_from_the_rungs_own_rows(bmm, R):
         np.testing.assert_array_equal(st["accepted"], accepted)
         np.testing.assert_array_equal(st["walker"], walker)
         assert proposed.sum() == sum(len(tr.proposed_pairs(R, t)) for t in range(tr.EXCHANGE_STEPS))
-        assert np.all(accepted >= 10) and np.all(proposed - accepted >= 10)       # (it cannot pass empty)
+        floor = tr.EXCHANGE_FLOOR[R]
+        assert floor == (10 if R in (2, 5) else 3)
+        assert np.all(accepted >= floor) and np.all(proposed - accepted >= floor)  # (it cannot pass empty)
+        for c in chains:                                                          # and the chains go on from whole states
+            c.sweeps(2)
+        for c in chains:
+            _counts_belong_to_the_labels(X, K, _state(c))
     finally:
         _close(chains, ladder)
 
@@ -191,33 +242,46 @@ def test_sixty_exchange_points_replayed_from_the_rungs_own_rows(bmm, R):
 NEARLY_ONE = 1.0 - 2.0 ** -30  # d = 2^-30 (L' - L): acceptance all but certain
 
 
-def _exchange_and_check(bmm, X, K, chains, ladder, before, expect):
-    """one exchange point of a ladder of two: `before` the two states (labels, Nk, S, alpha bytes; None: unknown
-    counts, labels only) ahead of it"""
+def _counts_belong_to_the_labels(X, K, state):
+    Nk, S = _recount(X, np.frombuffer(state[0], dtype=np.int32), K)
+    np.testing.assert_array_equal(np.frombuffer(state[1], dtype=np.int32), Nk)
+    np.testing.assert_array_equal(np.frombuffer(state[2], dtype=np.int32).reshape(K, -1), S)
+
+
+def _exchange_and_check(bmm, X, K, chains, ladder, before, expect=None, go_on=True):
+    """One exchange point of a ladder of R rungs, the whole state of every rung held to it.  `before`: every rung's
+    state ahead of the point (labels, Nk, S, alpha bytes; Nk and S None: counts unknown, labels and alpha only).  The
+    recorded accepted pairs, applied as transpositions, say which state every rung must hold afterwards, byte for
+    byte; the walker ids must have moved the same way; the counts must be a recount of X under the labels; and with
+    `go_on` two more sweeps of every rung leave them so.  `expect`: the decisions, pair by pair, where the caller
+    knows them.  Returns (the records, every rung's state after the point)."""
+    R = len(chains)
     w0 = ladder.stats()["walker"]
-    rec = ladder.exchange_step()[0]
-    assert rec["proposed"] and rec["accepted"] == expect, rec
+    rec = ladder.exchange_step()
+    assert len(rec) == R - 1 and len(before) == R
+    if expect is not None:
+        assert [e["accepted"] for e in rec] == list(expect), rec
+    order = list(range(R))                                 # order[r]: the rung whose state sits at rung r now
+    for r, e in enumerate(rec):
+        assert e["proposed"] == (r in tr.proposed_pairs(R, e["point"])) and (e["proposed"] or not e["accepted"]), e
+        if e["accepted"]:
+            order[r], order[r + 1] = order[r + 1], order[r]
     after = [_state(c) for c in chains]
     w1 = ladder.stats()["walker"]
-    order = (1, 0) if expect else (0, 1)
-    for r in (0, 1):
+    for r in range(R):
         src = before[order[r]]
-        assert after[r][0] == src[0]                      # the labels
-        assert after[r][3] == src[3]                      # alpha
+        assert after[r][0] == src[0], (r, order)           # the labels
+        assert after[r][3] == src[3], (r, order)           # alpha
         if src[1] is not None:
-            assert after[r][1:3] == src[1:3]              # Nk, S
-        Nk, S = _recount(X, np.frombuffer(after[r][0], dtype=np.int32), K)
-        np.testing.assert_array_equal(np.frombuffer(after[r][1], dtype=np.int32), Nk)
-        np.testing.assert_array_equal(np.frombuffer(after[r][2], dtype=np.int32).reshape(K, -1), S)
-    np.testing.assert_array_equal(w1, w0[list(order)])
-    for c in chains:                                       # and the chains go on from whole states
-        c.sweeps(2)
-    for c in chains:
-        Nk, S = c.counts()
-        wNk, wS = _recount(X, c.labels(), K)
-        np.testing.assert_array_equal(Nk, wNk)
-        np.testing.assert_array_equal(S, wS)
-    return after
+            assert after[r][1:3] == src[1:3], (r, order)   # Nk, S
+        _counts_belong_to_the_labels(X, K, after[r])
+    np.testing.assert_array_equal(w1, w0[order])
+    if go_on:
+        for c in chains:                                   # and the chains go on from whole states
+            c.sweeps(2)
+        for c in chains:
+            _counts_belong_to_the_labels(X, K, _state(c))
+    return rec, after
 
 
 @pytest.mark.parametrize("N,P,K", [(300, 8, 4), (70_000, 130, 4)])
@@ -229,7 +293,8 @@ def test_an_accepted_exchange_before_the_first_sweep_swaps_the_pending_deltas(bm
     try:
         a = np.float64(ALPHA).tobytes()
         before = [(z.tobytes(), None, None, a) for z in zs]
-        _exchange_and_check(bmm, X, K, chains, ladder, before, True)
+        rec, _ = _exchange_and_check(bmm, X, K, chains, ladder, before, [True])
+        assert rec[0]["proposed"]
     finally:
         _close(chains, ladder)
 
@@ -245,7 +310,8 @@ def test_accepted_and_rejected_exchanges_between_sweeps(bmm):
         L = [c.logpost_state()["log_lik"] for c in chains]
         assert L[1] - L[0] < -100.0
         before = [_state(c) for c in chains]
-        _exchange_and_check(bmm, X, K, chains, ladder, before, False)
+        rec, _ = _exchange_and_check(bmm, X, K, chains, ladder, before, [False])
+        assert rec[0]["proposed"]
     finally:
         _close(chains, ladder)
     chains, ladder = _ladder(bmm, X, K, (1.0, NEARLY_ONE), initials=[good, poor])
@@ -254,7 +320,8 @@ def test_accepted_and_rejected_exchanges_between_sweeps(bmm):
             c.sweeps(3)
         before = [_state(c) for c in chains]
         assert before[0] != before[1]
-        after = _exchange_and_check(bmm, X, K, chains, ladder, before, True)
+        rec, after = _exchange_and_check(bmm, X, K, chains, ladder, before, [True])
+        assert rec[0]["proposed"]
         assert ladder.stats()["accepted"][0] == 1 and after[0] != after[1]
     finally:
         _close(chains, ladder)
@@ -272,7 +339,8 @@ def test_an_accepted_exchange_of_dp_chains_swaps_the_sampled_alpha(bmm):
             c.sweeps(4)
         before = [_state(c) for c in chains]
         assert before[0][3] != before[1][3]          # two concentrations
-        _exchange_and_check(bmm, X, K, chains, ladder, before, True)
+        rec, _ = _exchange_and_check(bmm, X, K, chains, ladder, before, [True])
+        assert rec[0]["proposed"]
     finally:
         _close(chains, ladder)
 
@@ -318,12 +386,31 @@ def test_the_cold_chain_of_a_ladder_samples_the_exact_posterior(bmm, exact_clust
     n_batches = 100
     out = bmm.gibbs_dp(np.asfortranarray(X), 20_001, alpha=ALPHA, beta=BETA, gamma=GAMMA, burnin=1, maxK=30, batch=1, seed=9,
                        temper=[1, 0.4], swap_every=swap_every)
-    k_used = np.array([len(set(row)) for row in out["z"]])
-    n = len(k_used) // n_batches * n_batches
     tp = out["temper"]
     print("swap_every %d: proposed %s accepted %s" % (swap_every, tp["proposed"], tp["accepted"]))
     assert tp["proposed"][0] == len(range(0, 20_000 // swap_every, 2)) and 0 < tp["accepted"][0] < tp["proposed"][0]
     assert set(np.unique(tp["walker_cold"])) == {0, 1}
+    _clusters_in_use_within_four_standard_errors(out, want, n_batches)
+
+
+def test_the_cold_chain_of_a_ladder_of_three_samples_the_exact_posterior(bmm, exact_clusters):
+    """Both parities act on the cold chain's neighbours: pair 0 at the even points, pair 1 at the odd ones (with two
+    rungs the odd points propose nothing).  tests/test_temper_ref.py holds the composition -- scan, even point, odd
+    point -- to the invariance of pi_1 x pi_0.6 x pi_0.3 by enumeration; here the device's cold chain is held to pi_1."""
+    X, want = exact_clusters
+    out = bmm.gibbs_dp(np.asfortranarray(X), 20_001, alpha=ALPHA, beta=BETA, gamma=GAMMA, burnin=1, maxK=30, batch=1, seed=9,
+                       temper=[1, 0.6, 0.3], swap_every=1)
+    tp = out["temper"]
+    print("three rungs: proposed %s accepted %s" % (tp["proposed"], tp["accepted"]))
+    np.testing.assert_array_equal(tp["proposed"], [10_000, 10_000])      # points 0 .. 19 999: the even ones, the odd ones
+    assert np.all(tp["accepted"] > 0) and np.all(tp["accepted"] < tp["proposed"])
+    assert set(np.unique(tp["walker_cold"])) == {0, 1, 2}
+    _clusters_in_use_within_four_standard_errors(out, want, 100)
+
+
+def _clusters_in_use_within_four_standard_errors(out, want, n_batches):
+    k_used = np.array([len(set(row)) for row in out["z"]])
+    n = len(k_used) // n_batches * n_batches
     worst = 0.0
     for k in range(1, 8):
         s, p = (k_used[:n] == k).astype(np.float64), float(want[k - 1])
