@@ -360,7 +360,7 @@ struct KernelForm {
     bool emit = false;  // the weight-emitting twin: what a sweep runs on while its probabilities go to the host
     int gw = kGroupW;   // the shape's group width (bmm_spec.h)
     bool self = false;  // workgroups that build their own table image (SELF)
-    bool pk = false;    // k_resample_pk: scores from the packed binary32 image, the definition for the queued few
+    bool pk = false;    // k_resample_pk: scores from the packed binary32 image, the definition for the uncertain few
 };
 constexpr int tile_of(const KernelForm& f) { return f.nt / f.lanes; }  // observations per tile
 constexpr KernelForm resized(KernelForm f, int nt, int lanes = 1) { f.nt = nt; f.lanes = lanes; return f; }
@@ -546,6 +546,7 @@ struct bmm_chain {
     int* dSelfDone = nullptr;     // SELF kernels: workgroups of the running launch that have read the statistics
     int32_t *dDNkAlt = nullptr, *dDSAlt = nullptr;  // ... and the second set of delta accumulators (self_fold_prev)
     unsigned long long* dPkStat = nullptr;  // -DBMM_DEBUG_HOOKS: k_resample_pk's draws and deferred observations
+    int pk_defer_every = 0;       // -DBMM_DEBUG_HOOKS: BMM_DEBUG_PK_DEFER_EVERY as read when the chain was made
     int* dDbgFlag = nullptr;      // -DBMM_DEBUG_HOOKS: raised by a kernel that meets a label out of range
     // posterior predictive of new rows: their bit planes [ceil(P/32)][predM], the predictive
     // table image of the counting samplers (the explicit samplers' own image dTab is the predictive image), the
@@ -802,6 +803,10 @@ struct DebugSwitches {
     bool noself = dbg_env("BMM_DEBUG_NOSELF");          // no table-building workgroups
     bool nopk = dbg_env("BMM_DEBUG_NOPK");              // k_resample where k_resample_pk would run (A/B in one library)
     bool pk = dbg_env("BMM_DEBUG_PK");                  // k_resample_pk whatever the length of a launch
+    // n >= 1: k_resample_pk treats a lane whose observation index is a multiple of n as uncertain, so that certain and
+    // settled lanes share a wave (tests/test_gpu_pk_inline.py).  BMM_DEBUG_PK_QUEUE is still accepted and does nothing:
+    // the queue it sized is gone
+    int pk_defer_every = dbg_env_int("BMM_DEBUG_PK_DEFER_EVERY", 0);
 };
 
 // What follows from (sampler, N, P, K, batch) alone -- no device state enters.
@@ -827,7 +832,9 @@ size_t image_bytes(const ChainParams& q, bool own_tables) {
 }
 
 // LDS of a k_resample_pk workgroup: the packed image, the binary32 own-cluster image of as many bytes, Nk and E of
-// the table image, the histogram with its counters, the queue
+// the table image, the histogram with its counters, and kPkQueue words the kernel no longer uses (they were its queue
+// of uncertain observations; tests/test_own32_cpu.py restates this sum, so the reservation stays until that test is
+// revised: DESIGN.md section 5)
 size_t pk_image_bytes(const ChainParams& q) {
     const TableLayout l = layout_of(q, true);
     return (size_t)(2 * pk_tq_doubles(l) + l.tm() - l.nk()) * sizeof(double) + ((size_t)q.K * q.P + q.K + 4 + kPkQueue) * sizeof(int32_t);
@@ -1033,7 +1040,7 @@ int chain_alloc(bmm_chain* c) {
         c->dDSAlt = a.take<int32_t>(ns * kDeltaReps);
 #ifdef BMM_DEBUG_HOOKS
         c->dDbgFlag = a.take<int>(1);
-        c->dPkStat = a.take<unsigned long long>(2);
+        c->dPkStat = a.take<unsigned long long>(3);
 #endif
         const size_t zeroed = a.used;
         c->dAlpha = a.take<double>(1);
@@ -1077,10 +1084,9 @@ int launch_resample(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t l
     a.dbg_flag = c->dDbgFlag; a.dbg_inject = (dbg_env("BMM_DEBUG_BADLABEL") ? 1 : 0) | (dbg_env("BMM_DEBUG_STRAGGLER") ? 2 : 0) |
                                              (dbg_env("BMM_DEBUG_DRAW_FALLBACK") ? 4 : 0) | (dbg_env("BMM_DEBUG_DRAW_NOEPS") ? 8 : 0);
     a.Nk = c->dNk; a.S = c->dS; a.alpha_ptr = c->dAlpha; a.self_done = c->dSelfDone;
-    a.pk_qcap = kPkQueue;
 #ifdef BMM_DEBUG_HOOKS
-    if (const int cap = dbg_env_int("BMM_DEBUG_PK_QUEUE", 0)) a.pk_qcap = cap < kPkQueue ? cap : kPkQueue;
     a.pk_stat = c->dPkStat;
+    a.pk_defer_every = c->pk_defer_every;
 #endif
     const bool emit = c->probs_dst != nullptr;
     const bool use_generic = c->generic || (emit && !c->fn_emit);  // the int32 layout has no emitting twin
@@ -1634,15 +1640,21 @@ KernelPlan plan_kernel(const ChainParams& p, bool bits, int minus, int64_t batch
     // The packed kernel takes the place of every form it exists for (not with a feature mask or the allocation
     // sampler's tables: the band of draw_pk rests on k_count_tables' entries, all of them <= 0); its LDS is its own
     // image.  The choice of the form itself -- size, lanes, step-down -- is made as before, from the binary64 image.
-    // Only for launches that give a wave at least four chunks: the exact pass is a tail of a few microseconds behind
-    // the workgroup's barrier (dependent L2 round trips for as little as one queued observation), the packed scoring
-    // saves about 2 us per chunk and wave.  Same-box: C5 (9.5 chunks per wave) +19 %; the north-star shape and c3
-    // (one chunk per wave) lost 11 % and 6 % with the packed kernel (profiles/r05/README.md).
+    // Only for launches that give a wave at least four chunks.  The rule dates from the kernel's exact pass, a tail of
+    // microseconds behind the workgroup's barrier for as little as one queued observation, while the packed scoring
+    // saves about 2 us per chunk and wave: same-box, C5 (9.5 chunks per wave) +19 %; the north-star shape and c3 (one
+    // chunk per wave) lost 11 % and 6 % with the packed kernel (profiles/r05/README.md).  The pass is gone -- uncertain
+    // lanes are settled inside the tile loop -- and the rule stays until a change of its own moves it: it decides
+    // which kernel other workloads run (profiles/r08/README.md has ns and c3 with the rule lifted).
     const size_t pk_lds = explicit_params(p.mode) ? 0 : pk_image_bytes(p);
     auto offer = [&](KernelForm g, size_t lds) {
         KernelForm h = g;
         h.pk = true;
+#ifdef BMM_EXP_PK_ALWAYS  // timing experiments only (tools/exp_lib.sh): the rule below lifted, as BMM_DEBUG_PK lifts it
+        const bool long_launch = true;
+#else
         const bool long_launch = batch >= (int64_t)4 * num_cus * g.nt;
+#endif
         if (!masked && !d.nopk && (long_launch || d.pk) && !g.self && !explicit_params(p.mode) && instantiated(h, false) &&
             pk_lds <= kLdsMax && batch < ((int64_t)1 << 31)) { g = h; lds = pk_lds; }
         plan.form[plan.n] = g; plan.lds[plan.n++] = lds;
@@ -1874,6 +1886,7 @@ int bmm_chain_create(bmm_chain** out, int sampler, int64_t N, int P, int K, doub
     const int cus = device_cus(device);
     if (cus <= 0) { delete c; return set_err(BMM_E_HIP, "hipGetDeviceProperties failed"); }
     c->bits = !dbg.int32_layout;
+    c->pk_defer_every = dbg.pk_defer_every;
     c->generic = shape.generic;
     c->minus_in_lds = shape.minus_in_lds;
     c->lds_bytes_base = c->lds_bytes = shape.lds_bytes_base;
@@ -1898,17 +1911,20 @@ void bmm_chain_destroy(bmm_chain* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
 #ifdef BMM_DIAG
     if (c->dDiag) {
-        unsigned long long d[16];
-        if (hipMemcpy(d, c->dDiag, sizeof d, hipMemcpyDeviceToHost) == hipSuccess && d[5]) {
+        unsigned long long d[16] = {};
+        const bool ok = hipMemcpy(d, c->dDiag, sizeof d, hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok && d[5] && d[0]) {  // (k_resample_pk stamps the launch phases only)
             const double tot = (double)(d[0] + d[1] + d[2] + d[3] + d[4]);
             fprintf(stderr, "[bmm diag] waves=%llu cycles/wave: score %.0f (%.1f%%) pack %.0f (%.1f%%) draw %.0f (%.1f%%) movers %.0f (%.1f%%) prologue %.0f (%.1f%%) movers/wave-launch %.2f\n",
                     d[5], d[0] / (double)d[5], 100 * d[0] / tot, d[1] / (double)d[5], 100 * d[1] / tot, d[2] / (double)d[5],
                     100 * d[2] / tot, d[3] / (double)d[5], 100 * d[3] / tot, d[4] / (double)d[5], 100 * d[4] / tot, d[6] / (double)d[5]);
         }
-        if (hipMemcpy(d, c->dDiag, sizeof d, hipMemcpyDeviceToHost) == hipSuccess && d[5])
+        if (ok && d[5])
             fprintf(stderr, "[bmm diag launch] ticks per wave and launch: table staging %.0f, tile loop %.0f, waiting for the workgroup %.0f, flush %.0f\n",
                     d[8] / (double)d[5], d[9] / (double)d[5], d[10] / (double)d[5], d[11] / (double)d[5]);
-        if (d[5] && d[12])
+        if (ok && d[7])  // k_resample_pk: wave 0 of each workgroup, slots of its own
+            fprintf(stderr, "[bmm diag launch pk] workgroup-launches %llu, ticks from entry to flushed %.0f\n", d[7], d[14] / (double)d[7]);
+        if (ok && d[5] && d[12])
             fprintf(stderr, "[bmm diag draw] draws of a wave (64 observations) %llu, of them by the binary64 definition %llu (%.4f%%)\n",
                     d[12], d[13], 100.0 * (double)d[13] / (double)d[12]);
     }
@@ -4921,6 +4937,17 @@ extern "C" int bmm_dbg_pk_counts(bmm_chain* c, unsigned long long* draws, unsign
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipMemcpy(v, c->dPkStat, sizeof v, hipMemcpyDeviceToHost));
         *draws = v[0]; *deferred = v[1];
+        return BMM_OK;
+    });
+}
+// ... and how many of the deferred the packed tier left uncertain by itself without BMM_DEBUG_PK_DEFER_EVERY selecting
+// them (tests/test_gpu_pk_inline.py: deferred == selected + this)
+extern "C" int bmm_dbg_pk_unselected(bmm_chain* c, unsigned long long* n) {
+    if (!c || !n) return set_err(BMM_E_ARG, "null argument");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(n, c->dPkStat + 2, sizeof *n, hipMemcpyDeviceToHost));
         return BMM_OK;
     });
 }

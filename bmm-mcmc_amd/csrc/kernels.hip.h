@@ -544,9 +544,13 @@ struct ResampleArgs {
     int32_t* dS_prev;
     const double* alpha_ptr;
     int* self_done;
-    // k_resample_pk: entries its LDS queue holds, and (test variant) its counters [draws, deferred]
-    int pk_qcap;
+    // k_resample_pk, test variant: its counters [draws, deferred, of the deferred those the packed tier left uncertain
+    // and BMM_DEBUG_PK_DEFER_EVERY did not select], and BMM_DEBUG_PK_DEFER_EVERY (n > 0: a lane whose observation index
+    // is a multiple of n counts as uncertain)
     unsigned long long* pk_stat;
+#ifdef BMM_DEBUG_HOOKS
+    int pk_defer_every;
+#endif
 };
 
 // The test variant of the library (-DBMM_DEBUG_HOOKS) checks every label a resample kernel is about to count
@@ -1322,22 +1326,26 @@ __global__ __launch_bounds__(NT) void k_resample(ChainParams p, ResampleArgs a) 
 // lookup group, half of k_resample's LDS and scoring VALU instructions -- and the observation's own cluster from
 // Tm32, the "observation removed" entries at the same group width: one ds_read_b32 and one v_add_f32 per group, at
 // the field the group step has already extracted for Tq.  The draw is draw_pk (bmm_spec.h), which says per lane
-// whether its count is proven to be the definition's.  A lane that is not certain writes its observation's index
-// into a queue in LDS and neither stores nor counts it; after the tile loop the workgroup runs the binary64
-// definition on the queue (pk_exact_one: one wave per observation, one lane per category, Tp and the width-3 Tm
-// read from the global image), so the labels are k_resample's bit for bit.  An observation that finds the queue
-// full is scored by its wave on the spot.
+// whether its count is proven to be the definition's.  The lanes that are not certain are settled where they arise:
+// right behind the draw the wave takes them one at a time and runs the binary64 definition on each (pk_exact_count:
+// one lane per category, Tp and the width-3 Tm read from the global image, every load in flight at once), and the
+// count goes into that lane, so the labels are k_resample's bit for bit.  From there on certain and settled lanes
+// are the same: one count_movers, one pipelined store.  No phase follows the tile loop but the flush of the histogram.
+// Settling is not free: measured at C5 (profiles/r08/README.md) a settled lane lengthens its wave's loop by about
+// 8 800 cycles -- the definition is a chain of dependent binary64 steps; the SIMD's other waves take the issue slots
+// meanwhile, but the workgroup's barrier waits for the wave that settled most -- and about half of the 12 us the pass
+// behind the loop took per launch came back.
 // LDS, in doubles: Tq [G][KT/2][M] pairs | Tm32 [G][KT][M] binary32 (the two as they lie behind the table image in
-// global memory) | Nk, E (as they lie in the image) | histogram, chunk counter, queue counter | queue.  The binary64
-// Tm is not staged.
+// global memory) | Nk, E (as they lie in the image) | histogram, chunk counter | kPkQueue words that nothing uses
+// (pk_image_bytes, chain.hip).  The binary64 Tm is not staged.
 // ---------------------------------------------------------------------------------
-constexpr int kPkQueue = 4096;  // queue entries (pk_image_bytes, chain.hip)
+constexpr int kPkQueue = 4096;  // words reserved behind the counters and unused (pk_image_bytes, chain.hip)
 typedef float pk_f2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) pk_f2 lds_pk_f2;
 typedef __attribute__((address_space(3))) float lds_f32;
-// the own-cluster tables' groups at the largest P, padded: one lane each in pk_exact_one
+// the own-cluster tables' groups at the largest P, padded: one lane each in pk_exact_count
 constexpr int kOwnPadMax = ((kMaxP + kGroupWm - 1) / kGroupWm + kOwnSub - 1) / kOwnSub * kOwnSub;
-static_assert(kOwnPadMax <= 64, "pk_exact_one loads the own-cluster entries one per lane");
+static_assert(kOwnPadMax <= 64, "pk_exact_count loads the own-cluster entries one per lane");
 
 // the DP's bookkeeping for a draw of the new-cluster option (collapsed_gibbs_dp.cpp:212-231).  A second copy of the
 // block under `if (p.mode == MODE_DP && zn == K)` in k_resample, which stays inline there so that its 370
@@ -1362,74 +1370,82 @@ __device__ __forceinline__ unsigned pk_field(int bit, unsigned mask, uint32_t b0
     return __builtin_amdgcn_alignbit(word_of(wd + 1, b0, b1, b2, b3), word_of(wd, b0, b1, b2, b3), (unsigned)(bit & 31)) & mask;
 }
 
-// The definition for observation i (wave-uniform), by the whole wave: lane k scores category k -- the G entries of
-// Tp from the global image (L2), four loads in flight, added in group order; the own cluster from Tm in the global
-// image too: lane l loads the entry of group l (gm_pad() <= kOwnPadMax lanes) in the same round trip as the first
-// four of Tp, and the entries are added in group order, padding groups included, lane by lane -- then the maximum,
-// expw_ and the binary64 running sum walk the lanes in label order.  Every operation and its order are k_resample's.
+// lane j's binary64 value in every lane (j uniform): two v_readlane_b32, no trip through the LDS crossbar
+__device__ __forceinline__ double pk_bcast(double x, int j) {
+    const long long b = __double_as_longlong(x);
+    const uint64_t e = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, j) |
+                       ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), j) << 32);
+    return __longlong_as_double((long long)e);
+}
+
+// The definition for one observation, by the whole wave; everything about the observation is wave-uniform and comes
+// from the lane that holds it: its words w0..w3, its label zo, its uniform u.  Lane k scores category k -- the G
+// entries of Tp from the global image (L2), added in group order; the own cluster from Tm in the global image too:
+// lane l loads the entry of group l (gm_pad() <= kOwnPadMax lanes), and the entries are added in group order, padding
+// groups included, lane by lane.  The loads of GR groups and the one of Tm are issued before the first is used: one
+// round trip up to GR groups (twenty from 12 accumulators on: P <= 100 at groups of five), ceil(G / GR) beyond (a
+// round's loads past G repeat the last group's and are not added).  Then the maximum, expw_ and the binary64 running sum walk the lanes in label order,
+// each lane's value broadcast by v_readlane (pk_bcast).
+// Every operation and its order are k_resample's.  Returns the count of the draw (the DP's new-cluster option is K:
+// the caller keeps the books), or the label to keep where every category is impossible.
 template <int KT, int GW>
-__device__ __forceinline__ void pk_exact_one(const ChainParams& p, const ResampleArgs& a, const TableLayout& L, int64_t i,
-                                             const lds_f64* ET, const int32_t* NkT, int32_t* hist,
-                                             int Kused, int new_label, int lane) {
+__device__ __forceinline__ int pk_exact_count(const ChainParams& p, const ResampleArgs& a, const TableLayout& L,
+                                              uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, int zo, double u,
+                                              const lds_f64* ET, int lane) {
     constexpr int GM = 1 << GW;
-    const int P = p.P, G = p.G, K = p.K;
-    uint32_t b0, b1, b2, b3;
-    load_words(a.Xb, p.N, (P + 31) / 32, i, b0, b1, b2, b3);
-    int zo = a.z_in ? a.z_in[i] : -1;
+    // loads in flight, two VGPRs each, sized so that no form holds fewer waves per SIMD by registers than it did with
+    // the pass behind the loop: the forms of up to 8 accumulators have few registers to spare (profiles/r08/README.md)
+    constexpr int GR = KT <= 4 ? 6 : KT <= 8 ? 10 : 20;
+    static_assert((kMaxP + GW - 1) / GW <= 64, "lane g holds the field of group g");
+    const int G = p.G;
     const int zoc = zo < 0 ? 0 : zo;
     const int k = lane < KT ? lane : KT - 1;
     const double* const tp = a.tab + L.tp();
     const int gmp = L.gm_pad();
     const int go = lane < gmp ? lane : gmp - 1;
-    const double oe = a.tab[L.tm() + ((size_t)go * KT + zoc) * kGroupMm + pk_field(go * kGroupWm, kGroupMm - 1, b0, b1, b2, b3)];
+    const double oe = a.tab[L.tm() + ((size_t)go * KT + zoc) * kGroupMm + pk_field(go * kGroupWm, kGroupMm - 1, w0, w1, w2, w3)];
+    // (the row of a group is uniform and the lane adds its category; lane g extracts the field of group g from the
+    // uniform words with selects, and the groups read theirs from it: no scalar code that branches on the word)
+    const unsigned koff = (unsigned)k * GM;
+    const int gl = lane < G ? lane : G - 1;
+    const int fld = (int)pk_field(gl * GW, GM - 1, w0, w1, w2, w3);
     double sc = 0.0;
 #pragma unroll 1
-    for (int g0 = 0; g0 < G; g0 += 4) {
-        double tv[4];
+    for (int g0 = 0; g0 < G; g0 += GR) {
+        double tv[GR];
 #pragma unroll
-        for (int v = 0; v < 4; ++v) {
+        for (int v = 0; v < GR; ++v) {
             const int g = g0 + v < G ? g0 + v : G - 1;
-            tv[v] = tp[((size_t)g * KT + k) * GM + pk_field(g * GW, GM - 1, b0, b1, b2, b3)];
+            const double* const row = tp + ((size_t)g * KT * GM + (unsigned)__builtin_amdgcn_readlane(fld, g));
+            tv[v] = row[koff];
         }
 #pragma unroll
-        for (int v = 0; v < 4; ++v)
+        for (int v = 0; v < GR; ++v)
             if (g0 + v < G) sc = sc + tv[v];
     }
     double own = 0.0;
-    {
-        const int lo = (int)(uint32_t)__double_as_longlong(oe), hi = (int)(uint32_t)(__double_as_longlong(oe) >> 32);
-#pragma unroll
-        for (int g = 0; g < kOwnPadMax; ++g) {
-            if (g < gmp) {  // uniform
-                const uint64_t e = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(lo, g) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(hi, g) << 32);
-                own = own + __longlong_as_double((long long)e);
-            }
-        }
-    }
+#pragma unroll 1
+    for (int g = 0; g < gmp; ++g) own = own + pk_bcast(oe, g);  // (a loop, not kOwnPadMax tests: the path is rare and cold)
     if (k == zo) sc = own;
     double m = neg_inf();
 #pragma unroll
-    for (int j = 0; j < KT; ++j) m = max_score(m, __shfl(sc, j));
-    const double u = z_uniform(p.seed, (uint64_t)(p.obs0 + i), a.sweep);
+    for (int j = 0; j < KT; ++j) m = max_score(m, pk_bcast(sc, j));
     const double w = expw_tab(sc - m, ET);
     double run = 0.0, cdf = 0.0;
 #pragma unroll
     for (int j = 0; j < KT; ++j) {
-        run = run + __shfl(w, j);
+        run = run + pk_bcast(w, j);
         cdf = lane == j ? run : cdf;
     }
     const double t = u * run;
     int zn = (int)__popcll(__ballot(lane < KT && t >= cdf));
     if (!(m > neg_inf())) zn = zoc;  // every category impossible: keep (or 0)
-    if (p.mode == MODE_DP && zn == K) zn = pk_dp_label(NkT, K, Kused, new_label, zo, zoc);
-    BMM_DBG_LABELS(a, true, i == a.lo, K, zn, zo);
-    count_movers(lane == 0 && zn >= 0 && zn != zo, zo, zn, b0, b1, b2, b3, hist, K, P, lane);
-    if (lane == 0) a.z_out[i] = zn;
+    return zn;
 }
 
 template <int KT, int NT, int GW>
 __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs a) {
-    static_assert(KT % 2 == 0 && KT <= 32, "pairs of categories, one lane per category in the exact pass");
+    static_assert(KT % 2 == 0 && KT <= 32, "pairs of categories, one lane per category in pk_exact_count");
     constexpr int GM = 1 << GW;
     constexpr int KP = KT / 2;                      // pairs = accumulators (two binary32 each)
     constexpr int CH = KP <= 12 ? KP : KP / 2;      // lookups issued together
@@ -1447,10 +1463,8 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
     int32_t* const hist = reinterpret_cast<int32_t*>(tail + tail_d);  // [K*P] then [K]
     const int P = p.P, G = p.G, K = p.K;
     const int tid = threadIdx.x, lane = tid & 63;
-    int* const next_chunk = hist + K * P + K;  // LDS counters behind the histogram
-    int* const qcount = next_chunk + 1;
-    int* const queue = next_chunk + 4;
-    const int qcap = a.pk_qcap;
+    int* const next_chunk = hist + K * P + K;  // LDS counter behind the histogram
+    DIAG(const unsigned long long d_entry = diag_stamp();)
     // work per wave in chunks of 64 observations, as in k_resample
     const int64_t nchunks = (a.hi - a.lo + 63) / 64;
     const int64_t cpw = (nchunks + gridDim.x - 1) / gridDim.x;
@@ -1486,8 +1500,9 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
         stage(a.tab + L.nk(), tail, tail_d / 2);
     }
     for (int i = tid; i < K * P + K; i += NT) hist[i] = 0;
-    if (tid == 0) { *next_chunk = NW; *qcount = 0; }
+    if (tid == 0) *next_chunk = NW;
     __syncthreads();
+    DIAG(const unsigned long long d_staged = diag_stamp();)
 
     int Kused = 0, new_label = -1;
     if (p.mode == MODE_DP) {
@@ -1499,6 +1514,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
     float unit = kPkEpsUnit;
 #ifdef BMM_DEBUG_HOOKS
     if (a.dbg_inject & 8) unit = 0.0f;
+    unsigned ndeferred = 0, nunselected = 0;  // valid lanes this wave has settled by the definition (bmm_dbg_pk_counts)
 #endif
 
     if (has_tile) {
@@ -1570,27 +1586,33 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
             int cnt = 0;
             bool certain = draw_pk<KT>(sc, m, u, G, unit, cnt);
             DBG_TIER1_FORCE(a, certain);
-            const bool defer = pos.valid && !certain;
+            bool defer = pos.valid && !certain;
+#ifdef BMM_DEBUG_HOOKS
+            const bool selected = a.pk_defer_every > 0 && pos.valid && pos.i % a.pk_defer_every == 0;
+            nunselected += (unsigned)__popcll(__ballot(defer && !selected));
+            defer = defer || selected;
+#endif
             int zn = cnt;
+            // ---- the lanes the packed tier cannot prove (uniform, rare): the definition, one lane at a time, its
+            // count into that lane.  (A certain lane has a finite maximum: the "every category impossible" case is
+            // always settled here.)
+            unsigned long long o = __ballot(defer);
+#ifdef BMM_DEBUG_HOOKS
+            ndeferred += (unsigned)__popcll(o);
+#endif
+            while (o) {
+                const int src = __ffsll((long long)o) - 1;
+                o &= o - 1;
+                const uint32_t w0 = __builtin_amdgcn_readlane(b0, src), w1 = __builtin_amdgcn_readlane(b1, src);
+                const uint32_t w2 = __builtin_amdgcn_readlane(b2, src), w3 = __builtin_amdgcn_readlane(b3, src);
+                const int e = pk_exact_count<KT, GW>(p, a, L, w0, w1, w2, w3, __builtin_amdgcn_readlane(zo, src),
+                                                     pk_bcast(u, src), ET, lane);
+                if (lane == src) zn = e;
+            }
             if (p.mode == MODE_DP && zn == K) zn = pk_dp_label(NkT, K, Kused, new_label, zo, zoc);
-            // (a certain lane has a finite maximum: the "every category impossible" case is always deferred)
-            const bool keep = pos.valid && certain;
+            const bool keep = pos.valid;
             BMM_DBG_LABELS(a, keep, pos.i == a.lo, K, zn, zo);
             count_movers(keep && zn >= 0 && zn != zo, zo, zn, b0, b1, b2, b3, hist, K, P, lane);
-            if (__ballot(defer)) {  // uniform, rare: into the queue, or by this wave here and now when it is full
-                const int off = (int)(pos.i - a.lo);
-                int slot = 0;
-                if (defer) slot = atomicAdd(qcount, 1);
-                const bool full = defer && slot >= qcap;
-                if (defer && !full) queue[slot] = off;
-                unsigned long long o = __ballot(full);
-                while (o) {
-                    const int src = __ffsll((long long)o) - 1;
-                    o &= o - 1;
-                    pk_exact_one<KT, GW>(p, a, L, a.lo + __builtin_amdgcn_readlane(off, src), ET, NkT, hist, Kused,
-                                         new_label, lane);
-                }
-            }
             zn_prev = zn;
             i_prev = keep ? pos.i : -1;
             if (!has_next) break;
@@ -1602,19 +1624,29 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
         if (i_prev >= 0) a.z_out[i_prev] = zn_prev;
     }
 
+    DIAG(const unsigned long long d_loop = diag_stamp();)
     __syncthreads();
-    // ---- the exact pass: the queued observations, one wave each
-    const int nqueued = *qcount < qcap ? *qcount : qcap;
-    for (int q = wave; q < nqueued; q += NW)
-        pk_exact_one<KT, GW>(p, a, L, a.lo + queue[q], ET, NkT, hist, Kused, new_label, lane);
-    __syncthreads();
+    DIAG(const unsigned long long d_sync = diag_stamp();)
     flush_hist(hist, K, P, a.dS + (size_t)(blockIdx.x % kDeltaReps) * K * P, a.dNk + (blockIdx.x % kDeltaReps) * K, tid, NT);
+    // diagnostic build: per-launch phases in the slots k_resample reports them in; workgroup-launches and entry to
+    // flushed in [7] and [14], which k_resample leaves alone; from wave 0 of the workgroup only (every wave's atomics
+    // on one line, as k_resample has them, take longer than this launch and hold up the global loads of workgroups
+    // still at work)
+    DIAG(asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); const unsigned long long d_flush = diag_stamp();)
+    DIAG(if (a.diag && tid == 0) {
+        atomicAdd(&a.diag[5], 1ull); atomicAdd(&a.diag[7], 1ull); atomicAdd(&a.diag[14], d_flush - d_entry);
+        atomicAdd(&a.diag[8], d_staged - d_entry); atomicAdd(&a.diag[9], d_loop - d_staged);
+        atomicAdd(&a.diag[10], d_sync - d_loop); atomicAdd(&a.diag[11], d_flush - d_sync);
+    })
 #ifdef BMM_DEBUG_HOOKS
-    if (tid == 0 && a.pk_stat) {  // test variant: draws made and observations deferred (bmm_dbg_pk_counts)
-        int64_t first = a.lo + wg_c0 * 64, last = a.lo + (wg_c0 + (wg_cn > 0 ? wg_cn : 0)) * 64;
-        last = last < a.hi ? last : a.hi;
-        if (last > first) atomicAdd(&a.pk_stat[0], (unsigned long long)(last - first));
-        atomicAdd(&a.pk_stat[1], (unsigned long long)*qcount);
+    if (a.pk_stat) {  // test variant: draws made and valid lanes settled by the definition (bmm_dbg_pk_counts)
+        if (tid == 0) {
+            int64_t first = a.lo + wg_c0 * 64, last = a.lo + (wg_c0 + (wg_cn > 0 ? wg_cn : 0)) * 64;
+            last = last < a.hi ? last : a.hi;
+            if (last > first) atomicAdd(&a.pk_stat[0], (unsigned long long)(last - first));
+        }
+        if (lane == 0 && ndeferred) atomicAdd(&a.pk_stat[1], (unsigned long long)ndeferred);
+        if (lane == 0 && nunselected) atomicAdd(&a.pk_stat[2], (unsigned long long)nunselected);
     }
 #endif
 }
