@@ -787,8 +787,9 @@ TableLayout layout_of(const bmm_chain* c) { return layout_of(c->p, !explicit_par
 // The test variant's switches (-DBMM_DEBUG_HOOKS: environment variables, read through dbg_env, so the product
 // library has none of them set).  These steer the shape and the kernel choice and are read when one of these is
 // made, once per choice; the others are read where they act: BMM_DEBUG_STREAM (chain_stream_create),
-// BMM_DEBUG_FAKE_DEVICES (fake_devices), BMM_DEBUG_BADLABEL, BMM_DEBUG_STRAGGLER, BMM_DEBUG_DRAW_FALLBACK and
-// BMM_DEBUG_DRAW_NOEPS (launch_resample).
+// BMM_DEBUG_FAKE_DEVICES (fake_devices), BMM_DEBUG_BADLABEL, BMM_DEBUG_STRAGGLER, BMM_DEBUG_DRAW_FALLBACK,
+// BMM_DEBUG_DRAW_NOEPS and BMM_DEBUG_PK_GENKEY (k_resample_pk draws under the general, per-lane form of the Philox
+// key whatever the launch) (launch_resample).
 int dbg_env_int(const char* name, int unset) { const char* v = dbg_env(name); return v ? (atoi(v) > 0 ? atoi(v) : 0) : unset; }
 struct DebugSwitches {
     bool generic = dbg_env("BMM_DEBUG_GENERIC");        // every shape on the generic path
@@ -1082,7 +1083,8 @@ int launch_resample(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t l
     a.X = c->dX; a.Xb = c->dXb; a.z_in = z_in; a.z_out = z_out; a.tab = c->dTab; a.dNk = c->dDNk; a.dS = c->dDS;
     a.lo = lo; a.hi = hi; a.sweep = sweep; a.minus_in_lds = c->minus_in_lds; a.diag = c->dDiag;
     a.dbg_flag = c->dDbgFlag; a.dbg_inject = (dbg_env("BMM_DEBUG_BADLABEL") ? 1 : 0) | (dbg_env("BMM_DEBUG_STRAGGLER") ? 2 : 0) |
-                                             (dbg_env("BMM_DEBUG_DRAW_FALLBACK") ? 4 : 0) | (dbg_env("BMM_DEBUG_DRAW_NOEPS") ? 8 : 0);
+                                             (dbg_env("BMM_DEBUG_DRAW_FALLBACK") ? 4 : 0) | (dbg_env("BMM_DEBUG_DRAW_NOEPS") ? 8 : 0) |
+                                             (dbg_env("BMM_DEBUG_PK_GENKEY") ? 16 : 0);
     a.Nk = c->dNk; a.S = c->dS; a.alpha_ptr = c->dAlpha; a.self_done = c->dSelfDone;
 #ifdef BMM_DEBUG_HOOKS
     a.pk_stat = c->dPkStat;
@@ -1104,6 +1106,14 @@ int launch_resample(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t l
         grid = (int)(nt256 < maxb ? nt256 : maxb);
     }
     if (emit) { a.wts = c->dWts; a.wtot = c->dWtot; }
+    // k_resample_pk addresses an observation by a 32-bit offset from the launch's first (plan_kernel offers it for
+    // launches of fewer than 2^31 observations): that first observation is folded into the bases here.  lo and hi stay
+    // what they are -- the draw's counter and the test variant's counters are in observation indices.
+    if (form.pk && !use_generic) {
+        a.Xb += lo;
+        if (a.z_in) a.z_in += lo;
+        a.z_out += lo;
+    }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->prof > 0 && sweep % (uint32_t)c->prof == 0) {
         if (c->ev_used + 2 > c->ev.size()) {
@@ -5907,6 +5917,35 @@ int bmm_device_math(int device, int op, const double* in, const double* in2, dou
     HIP_TRY(hipMemcpy(out, bo.p, n * sizeof(double), hipMemcpyDeviceToHost));
     return BMM_OK;
 }
+
+#ifdef BMM_DEBUG_HOOKS
+// Test variant only: k_resample_pk's draw (spec = 0) or bmm_spec.h's draw_pk (spec = 1) on n rows of kt scores each and
+// their uniforms, on the device (k_test_pk_draw); out[2 i ...] = count and verdict.
+int bmm_dbg_pk_draw(int device, int kt, int spec, const float* scores, const double* u, int G, int64_t n, int* out) {
+    if (!scores || !u || !out || n < 0) return set_err(BMM_E_ARG, "bad argument");
+    if (kt != 4 && kt != 12 && kt != 20 && kt != 32)
+        return set_err(BMM_E_ARG, "the draw is instantiated for 4, 12, 20 and 32 accumulators");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf bs, bu, bo;
+    HIP_TRY(bs.alloc((size_t)n * kt * sizeof(float)));
+    HIP_TRY(bu.alloc((size_t)n * sizeof(double)));
+    HIP_TRY(bo.alloc((size_t)n * 2 * sizeof(int)));
+    HIP_TRY(hipMemcpy(bs.p, scores, (size_t)n * kt * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(bu.p, u, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    const dim3 grid((unsigned)((n + 255) / 256));
+#define BMM_TEST_PK_DRAW(KT)                                                                                              \
+    if (spec) hipLaunchKernelGGL((k_test_pk_draw<KT, true>), grid, dim3(256), 0, 0, bs.as<float>(), bu.as<double>(), G, n, bo.as<int>()); \
+    else hipLaunchKernelGGL((k_test_pk_draw<KT, false>), grid, dim3(256), 0, 0, bs.as<float>(), bu.as<double>(), G, n, bo.as<int>())
+    if (kt == 4) { BMM_TEST_PK_DRAW(4); }
+    else if (kt == 12) { BMM_TEST_PK_DRAW(12); }
+    else if (kt == 20) { BMM_TEST_PK_DRAW(20); }
+    else { BMM_TEST_PK_DRAW(32); }
+#undef BMM_TEST_PK_DRAW
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, bo.p, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost));
+    return BMM_OK;
+}
+#endif
 
 int bmm_device_variates(int device, int kind, double p, double q, uint64_t seed, uint32_t sweep, double* out,
                         int64_t n) {

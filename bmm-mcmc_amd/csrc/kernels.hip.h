@@ -1335,6 +1335,13 @@ __global__ __launch_bounds__(NT) void k_resample(ChainParams p, ResampleArgs a) 
 // 8 800 cycles -- the definition is a chain of dependent binary64 steps; the SIMD's other waves take the issue slots
 // meanwhile, but the workgroup's barrier waits for the wave that settled most -- and about half of the 12 us the pass
 // behind the loop took per launch came back.
+// The loop's steady state -- a chunk without an uncertain lane and without a mover -- moves no spilled scalar: the
+// blocks beside it (pk_exact_count, pk_dp_label and its books, count_movers, the flush) take their arguments from the
+// kernel argument segment where they run (pk_args_view: scalar loads behind an opaque pointer) and rebuild layout and
+// LDS places from them, so none of that is held in scalar registers across the loop; their branches are marked
+// unlikely, which keeps the register allocator's spills inside them.  An observation is a 32-bit offset from the
+// launch's first (PkPos), the draw works on pairs (pk_draw2), and the Philox key is a scalar wherever the launch's
+// indices allow (pk_uniform).  Instruction counts before and after: profiles/r09/README.md.
 // LDS, in doubles: Tq [G][KT/2][M] pairs | Tm32 [G][KT][M] binary32 (the two as they lie behind the table image in
 // global memory) | Nk, E (as they lie in the image) | histogram, chunk counter | kPkQueue words that nothing uses
 // (pk_image_bytes, chain.hip).  The binary64 Tm is not staged.
@@ -1443,6 +1450,128 @@ __device__ __forceinline__ int pk_exact_count(const ChainParams& p, const Resamp
     return zn;
 }
 
+// The kernel's arguments as the blocks outside the loop's steady state read them: from the kernel argument segment,
+// through a pointer the compiler cannot see behind, where they run.  Everything those blocks need -- the definition's
+// table pointers and layout, the histogram's place and shape for the movers, the DP's books, the flush -- would
+// otherwise be computed ahead of the tile loop and held in scalar registers across it: more than the register file
+// has, so the loop's steady state moved them to and from VGPR lanes on every trip (profiles/r09/README.md).  Scalar
+// loads from the segment cost those rare blocks a round trip to the scalar cache and the loop nothing.
+struct PkArgsView {
+    const ChainParams* p;
+    const ResampleArgs* a;
+};
+static_assert(alignof(ChainParams) == 8 && alignof(ResampleArgs) == 8 && sizeof(ChainParams) % 8 == 0,
+              "k_resample_pk(ChainParams, ResampleArgs): the second argument lies right behind the first");
+__device__ __forceinline__ PkArgsView pk_args_view() {
+    const __attribute__((address_space(4))) char* ka =
+        (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));  // not the pointer the kernel's own argument loads come from, as far as the compiler knows
+    PkArgsView v;
+    v.p = (const ChainParams*)ka;
+    v.a = (const ResampleArgs*)(ka + sizeof(ChainParams));
+    return v;
+}
+// the LDS places behind the two binary32 images, from the layout (k_resample_pk's comment)
+struct PkLds {
+    const int32_t* NkT;
+    const lds_f64* ET;
+    int32_t* hist;
+};
+__device__ __forceinline__ PkLds pk_lds(char* smem, const TableLayout& L) {
+    double* const tail = reinterpret_cast<double*>(smem) + 2 * pk_tq_doubles(L);
+    PkLds r;
+    r.NkT = reinterpret_cast<const int32_t*>(tail);
+    r.ET = (const lds_f64*)(tail + (L.et() - L.nk()));
+    r.hist = reinterpret_cast<int32_t*>(tail + (L.tm() - L.nk()));
+    return r;
+}
+
+// Where a lane sits in a chunk of 64 consecutive observations of a launch of n < 2^31: the chunk's first observation
+// as an offset from the launch's first (uniform), and the lane's own offset from there, clamped to the last
+// observation of the launch (lanes past the end re-read it and never write back).  The launch's base pointers have the
+// batch's first observation folded in (launch_resample), so an observation's words and labels are at
+// base + s0 (scalar) + voff (a zero-extended 32-bit lane offset): no 64-bit lane arithmetic.
+struct PkPos {
+    uint32_t s0;    // uniform
+    uint32_t loff;  // lane offset in observations, clamped
+    bool valid;
+};
+__device__ __forceinline__ PkPos pk_pos(uint32_t n, int chunk, int lane) {
+    PkPos t;
+    t.s0 = (uint32_t)chunk << 6;
+    const uint32_t room = n - 1u - t.s0;
+    t.valid = (uint32_t)lane <= room;
+    t.loff = (uint32_t)lane < room ? (uint32_t)lane : room;
+    return t;
+}
+template <class T>
+__device__ __forceinline__ T* pk_at(T* sbase, uint32_t loff) {
+    static_assert(sizeof(T) == 4, "words and labels");
+    return (T*)((const char*)sbase + (loff * 4u));  // uniform base + zero-extended 32-bit lane offset (saddr form)
+}
+// load_words at a PkPos; W is tested where it is used (a flag computed ahead of the loop is a lane mask held across it)
+__device__ __forceinline__ void pk_load_words(const uint32_t* Xb, int64_t N, int W, const PkPos& t, uint32_t& w0,
+                                              uint32_t& w1, uint32_t& w2, uint32_t& w3) {
+    const uint32_t* const b = Xb + t.s0;
+    w0 = *pk_at(b, t.loff);
+    if (W > 1) w1 = *pk_at(b + N, t.loff);
+    if (W > 2) w2 = *pk_at(b + 2 * N, t.loff);
+    if (W > 3) w3 = *pk_at(b + 3 * N, t.loff);
+}
+
+// draw_pk (bmm_spec.h) on scores held in pairs: s - m, the scaling by log2(e) and t - c[k] as packed binary32
+// operations, each component rounded as the scalar instruction rounds it (same mode register), the running sum in the
+// same order: cnt and the verdict are draw_pk's bit for bit (tests/test_gpu_pk_lean.py runs the two side by side).
+// bmm_spec.h's function remains the statement of the draw.
+template <int KT>
+__device__ __forceinline__ bool pk_draw2(const pk_f2 (&s2)[KT / 2], float m, double u, int G, float unit, int& cnt) {
+    static_assert(KT % 2 == 0 && KT <= kTier1MaxCats, "the band is derived for at most kTier1MaxCats categories");
+    constexpr int KP = KT / 2;
+    const pk_f2 mm{m, m}, l2e{0x1.715476p+0f, 0x1.715476p+0f};
+    pk_f2 c[KP];
+    float run = 0.0f;
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        const pk_f2 x = (s2[j] - mm) * l2e;  // sub, then mul: no fma (-ffp-contract=off, and the band's derivation)
+        run = run + __builtin_amdgcn_exp2f(x.x);
+        c[j].x = run;
+        run = run + __builtin_amdgcn_exp2f(x.y);
+        c[j].y = run;
+    }
+    const float t = (float)u * run;
+    const pk_f2 tt{t, t};
+    float nearest = __builtin_inff();
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        const pk_f2 diff = tt - c[j];
+        n += diff.x >= 0.0f ? 1 : 0;
+        nearest = __builtin_fminf(nearest, __builtin_fabsf(diff.x));
+        n += diff.y >= 0.0f ? 1 : 0;
+        nearest = __builtin_fminf(nearest, __builtin_fabsf(diff.y));
+    }
+    cnt = n;
+    return nearest > pk_band(m, G, unit) * run && m > -__builtin_inff() && m < __builtin_inff();
+}
+// z_uniform (bmm_spec.h) of the observation whose global index is i0 + loff, i0 = obs0 + the launch's first.  While
+// obs0 + hi <= 2^32 the high word z_key folds in is zero for every lane of the launch (key_uniform, a scalar): key
+// and the ten round keys are scalars then, computed by the scalar unit.  The same bits by construction.  (gfx950 has
+// no three-operand xor: a round's hi ^ k ^ c1 stays two instructions in either form.)
+__device__ __forceinline__ double pk_uniform(uint64_t seed, uint64_t i0, uint32_t s0, uint32_t loff, uint32_t sweep,
+                                             bool key_uniform) {
+    uint32_t ra, rb;
+    if (key_uniform) {
+        uint32_t k = z_key(seed, 0);
+        asm volatile("" : "+s"(k));  // a scalar, and this form is not folded into the general one below
+        philox2x32_10((uint32_t)i0 + s0 + loff, sweep, k, ra, rb);
+        asm volatile("" : "+v"(ra), "+v"(rb));
+    } else {
+        const uint64_t i = i0 + s0 + loff;
+        philox2x32_10((uint32_t)i, sweep, z_key(seed, i), ra, rb);
+    }
+    return u52(ra, rb);
+}
+
 template <int KT, int NT, int GW>
 __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs a) {
     static_assert(KT % 2 == 0 && KT <= 32, "pairs of categories, one lane per category in pk_exact_count");
@@ -1458,25 +1587,25 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
     const volatile lds_pk_f2* const Tq = (const volatile lds_pk_f2*)lds;
     const volatile lds_f32* const Tm32 = (const volatile lds_f32*)(lds + nq_d);
     double* const tail = lds + 2 * nq_d;
-    const int32_t* const NkT = reinterpret_cast<const int32_t*>(tail);
-    const lds_f64* const ET = (const lds_f64*)(tail + (L.et() - L.nk()));
     int32_t* const hist = reinterpret_cast<int32_t*>(tail + tail_d);  // [K*P] then [K]
     const int P = p.P, G = p.G, K = p.K;
     const int tid = threadIdx.x, lane = tid & 63;
     int* const next_chunk = hist + K * P + K;  // LDS counter behind the histogram
     DIAG(const unsigned long long d_entry = diag_stamp();)
-    // work per wave in chunks of 64 observations, as in k_resample
-    const int64_t nchunks = (a.hi - a.lo + 63) / 64;
-    const int64_t cpw = (nchunks + gridDim.x - 1) / gridDim.x;
-    const int64_t wg_c0 = (int64_t)blockIdx.x * cpw;
-    const int64_t wg_cn = nchunks - wg_c0 < cpw ? nchunks - wg_c0 : cpw;  // chunks of this workgroup (may be <= 0)
+    // work per wave in chunks of 64 observations, as in k_resample; plan_kernel offers this kernel for launches of
+    // fewer than 2^31 observations only, and launch_resample has folded the launch's first observation into Xb, z_in
+    // and z_out: an observation is a 32-bit offset from there
+    const uint32_t n = (uint32_t)(a.hi - a.lo);
+    const int nchunks = (int)((n + 63u) >> 6);
+    const int cpw = (nchunks + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int wg_c0 = (int)blockIdx.x * cpw;
+    const int wg_cn = nchunks - wg_c0 < cpw ? nchunks - wg_c0 : cpw;  // chunks of this workgroup (may be <= 0)
     const int W = (P + 31) / 32;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int64_t tile = wg_c0 + wave;
     const bool has_tile = wave < wg_cn;
-    TilePos pos = tile_pos(a, has_tile ? tile : 0, 64, lane, lane);
+    PkPos pos = pk_pos(n, has_tile ? wg_c0 + wave : 0, lane);
     uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
-    if (has_tile) load_words(a.Xb, p.N, W, pos.ic, b0, b1, b2, b3);  // before the tables are staged
+    if (has_tile) pk_load_words(a.Xb, p.N, W, pos, b0, b1, b2, b3);  // before the tables are staged
     {
         // stage the two binary32 images and Nk, E of the table image: eight 16-byte loads in flight per lane
         auto stage = [&](const double* from, double* to, int n2) {
@@ -1504,35 +1633,51 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
     __syncthreads();
     DIAG(const unsigned long long d_staged = diag_stamp();)
 
-    int Kused = 0, new_label = -1;
-    if (p.mode == MODE_DP) {
-        for (int k = 0; k < K; ++k) {
-            if (NkT[k] > 0) ++Kused;
-            else if (new_label < 0) new_label = k;
-        }
-    }
     float unit = kPkEpsUnit;
 #ifdef BMM_DEBUG_HOOKS
     if (a.dbg_inject & 8) unit = 0.0f;
     unsigned ndeferred = 0, nunselected = 0;  // valid lanes this wave has settled by the definition (bmm_dbg_pk_counts)
 #endif
 
+    // What the loop's steady state -- a chunk without an uncertain lane and without a mover -- holds in scalar
+    // registers is named here: three base pointers, the plane stride, the launch's length and this workgroup's chunks,
+    // G, W, K, the draw's key and counter base, the two LDS places.  The blocks beside it (the definition for an
+    // uncertain lane, the DP's books, the movers, the flush) take their arguments from the kernel argument segment
+    // where they run (pk_args_view), and a uniform flag is tested on the value it comes from, behind an opaque copy,
+    // so that no lane mask of it is carried around the loop.
     if (has_tile) {
-        int zo = a.z_in ? a.z_in[pos.ic] : -1;
+        const uint32_t* const Xb = a.Xb;
+        const int32_t* const z_in = a.z_in;
+        int32_t* const z_out = a.z_out;
+        const int64_t N = p.N;
+        const uint64_t seed = p.seed, i0 = (uint64_t)(p.obs0 + a.lo);
+        const uint32_t sweep = a.sweep;
+        // every observation of the launch below 2^32: the key of z_uniform is one scalar (pk_uniform)
+        int key_general = (int)(uint32_t)(((uint64_t)(p.obs0 + a.hi) - 1u) >> 32);  // != 0: some index is >= 2^32
+#ifdef BMM_DEBUG_HOOKS
+        if (a.dbg_inject & 16) key_general = 1;  // BMM_DEBUG_PK_GENKEY: the general form whatever the launch
+#endif
+        key_general = __builtin_amdgcn_readfirstlane(key_general);
+        const int dp_K = p.mode == MODE_DP ? K : -1;  // the count that stands for the DP's new cluster, or none
+        const int has_zin = (int)((uint32_t)((uintptr_t)z_in >> 32) | (uint32_t)(uintptr_t)z_in);  // != 0: there are labels
+        int zo = -1;
+        if (z_in) zo = *pk_at(z_in + pos.s0, pos.loff);
         asm volatile("" : "+v"(zo));  // landed before the pipeline starts (k_resample)
         int zn_prev = 0;
-        int64_t i_prev = -1;  // < 0: nothing to store
+        uint32_t st_s0 = 0, st_loff = 0;  // the chunk whose labels are still to be stored
+        bool st_on = false;               //   ... and the lanes of it that store
         for (;;) {
             const int zoc = zo < 0 ? 0 : zo;
-            if (i_prev >= 0) a.z_out[i_prev] = zn_prev;
+            if (st_on) *pk_at(z_out + st_s0, st_loff) = zn_prev;
             int nc = 0;
             if (lane == 0) nc = atomicAdd(next_chunk, 1);
             nc = __builtin_amdgcn_readfirstlane(nc);
-            const int64_t next = wg_c0 + nc;
             const bool has_next = nc < wg_cn;  // uniform
-            const TilePos npos = tile_pos(a, has_next ? next : tile, 64, lane, lane);
+            const PkPos npos = pk_pos(n, has_next ? wg_c0 + nc : 0, lane);
             uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
             int zo_next = -1;
+            int Wl = W, zl = has_zin;
+            asm volatile("" : "+s"(Wl), "+s"(zl));  // (tested below, on the values)
 
             // ---- scoring: (K / 2) * G conflict-free 64-bit LDS lookups, one packed add each; per group one 32-bit
             // gather of the own cluster's "observation removed" entry at the same field, one add
@@ -1545,8 +1690,8 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
 #pragma unroll 1
             for (int h = 0; h < W; ++h) {
                 if (has_next && h == 0) {
-                    load_words(a.Xb, p.N, W, npos.ic, n0, n1, n2, n3);
-                    if (a.z_in) zo_next = a.z_in[npos.ic];
+                    pk_load_words(Xb, N, Wl, npos, n0, n1, n2, n3);
+                    if (zl) zo_next = *pk_at(z_in + npos.s0, npos.loff);
                 }
                 const uint32_t cur = word_of(h, b0, b1, b2, b3), nxt = word_of(h + 1, b0, b1, b2, b3);
                 const int g_lo = (32 * h + GW - 1) / GW;
@@ -1573,61 +1718,99 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
             }
             __builtin_amdgcn_s_setprio(0);
             // the binary32 scores, the observation's own cluster from its own image
-            float sc[KT];
+            pk_f2 s2[KP];
             float m = -__builtin_inff();
 #pragma unroll
-            for (int k = 0; k < KT; ++k) {
-                float v = (k & 1) ? acc[k >> 1].y : acc[k >> 1].x;
-                if (k == zo) v = own32;
-                sc[k] = v;
-                m = __builtin_fmaxf(m, v);
+            for (int j = 0; j < KP; ++j) {
+                float x = acc[j].x, y = acc[j].y;
+                if (2 * j == zo) x = own32;
+                if (2 * j + 1 == zo) y = own32;
+                s2[j] = pk_f2{x, y};
+                m = __builtin_fmaxf(m, x);
+                m = __builtin_fmaxf(m, y);
             }
-            const double u = z_uniform(p.seed, (uint64_t)(p.obs0 + pos.ic), a.sweep);
+            int kg = key_general;
+            asm volatile("" : "+s"(kg));
+            const double u = pk_uniform(seed, i0, pos.s0, pos.loff, sweep, kg == 0);
             int cnt = 0;
-            bool certain = draw_pk<KT>(sc, m, u, G, unit, cnt);
+            bool certain = pk_draw2<KT>(s2, m, u, G, unit, cnt);
             DBG_TIER1_FORCE(a, certain);
             bool defer = pos.valid && !certain;
 #ifdef BMM_DEBUG_HOOKS
-            const bool selected = a.pk_defer_every > 0 && pos.valid && pos.i % a.pk_defer_every == 0;
+            const bool selected = a.pk_defer_every > 0 && pos.valid &&
+                                  (a.lo + (int64_t)pos.s0 + lane) % a.pk_defer_every == 0;
             nunselected += (unsigned)__popcll(__ballot(defer && !selected));
             defer = defer || selected;
 #endif
             int zn = cnt;
             // ---- the lanes the packed tier cannot prove (uniform, rare): the definition, one lane at a time, its
             // count into that lane.  (A certain lane has a finite maximum: the "every category impossible" case is
-            // always settled here.)
+            // always settled here.)  Arguments, layout and the lane number are taken here, not ahead of the loop.
             unsigned long long o = __ballot(defer);
 #ifdef BMM_DEBUG_HOOKS
             ndeferred += (unsigned)__popcll(o);
 #endif
-            while (o) {
-                const int src = __ffsll((long long)o) - 1;
-                o &= o - 1;
-                const uint32_t w0 = __builtin_amdgcn_readlane(b0, src), w1 = __builtin_amdgcn_readlane(b1, src);
-                const uint32_t w2 = __builtin_amdgcn_readlane(b2, src), w3 = __builtin_amdgcn_readlane(b3, src);
-                const int e = pk_exact_count<KT, GW>(p, a, L, w0, w1, w2, w3, __builtin_amdgcn_readlane(zo, src),
-                                                     pk_bcast(u, src), ET, lane);
-                if (lane == src) zn = e;
+            if (__builtin_expect(o != 0, 0)) {
+                const PkArgsView v = pk_args_view();
+                const TableLayout Lc{v.p->G, KT, v.p->Gm, GM};
+                const PkLds lc = pk_lds(smem, Lc);
+                int ln = lane;
+                asm volatile("" : "+v"(ln));
+                do {
+                    const int src = __ffsll((long long)o) - 1;
+                    o &= o - 1;
+                    const uint32_t w0 = __builtin_amdgcn_readlane(b0, src), w1 = __builtin_amdgcn_readlane(b1, src);
+                    const uint32_t w2 = __builtin_amdgcn_readlane(b2, src), w3 = __builtin_amdgcn_readlane(b3, src);
+                    const int e = pk_exact_count<KT, GW>(*v.p, *v.a, Lc, w0, w1, w2, w3, __builtin_amdgcn_readlane(zo, src),
+                                                         pk_bcast(u, src), lc.ET, ln);
+                    if (ln == src) zn = e;
+                } while (o);
             }
-            if (p.mode == MODE_DP && zn == K) zn = pk_dp_label(NkT, K, Kused, new_label, zo, zoc);
+            if (__builtin_expect(__ballot(zn == dp_K) != 0, 0)) {  // the DP's new cluster was drawn (rare): its books, from the staged sizes
+                const PkArgsView v = pk_args_view();
+                const int Kc = v.p->K;
+                const TableLayout Lc{v.p->G, KT, v.p->Gm, GM};
+                const int32_t* const Nkc = pk_lds(smem, Lc).NkT;
+                int Kused = 0, new_label = -1;
+                for (int k = 0; k < Kc; ++k) {
+                    if (Nkc[k] > 0) ++Kused;
+                    else if (new_label < 0) new_label = k;
+                }
+                if (zn == Kc) zn = pk_dp_label(Nkc, Kc, Kused, new_label, zo, zoc);
+            }
             const bool keep = pos.valid;
-            BMM_DBG_LABELS(a, keep, pos.i == a.lo, K, zn, zo);
-            count_movers(keep && zn >= 0 && zn != zo, zo, zn, b0, b1, b2, b3, hist, K, P, lane);
+#ifdef BMM_DEBUG_HOOKS
+            BMM_DBG_LABELS(a, keep, pos.s0 + (uint32_t)lane == 0u, K, zn, zo);
+#endif
+            const bool moves = keep && zn >= 0 && zn != zo;
+            if (__builtin_expect(__ballot(moves) != 0, 0)) {
+                const PkArgsView v = pk_args_view();
+                const int Kc = v.p->K, Pc = v.p->P;
+                const TableLayout Lc{v.p->G, KT, v.p->Gm, GM};
+                int ln = lane;
+                asm volatile("" : "+v"(ln));
+                count_movers(moves, zo, zn, b0, b1, b2, b3, pk_lds(smem, Lc).hist, Kc, Pc, ln);
+            }
             zn_prev = zn;
-            i_prev = keep ? pos.i : -1;
+            st_s0 = pos.s0; st_loff = pos.loff; st_on = keep;
             if (!has_next) break;
             b0 = n0; b1 = n1; b2 = n2; b3 = n3;
             zo = zo_next;
             pos = npos;
-            tile = next;
         }
-        if (i_prev >= 0) a.z_out[i_prev] = zn_prev;
+        if (st_on) *pk_at(z_out + st_s0, st_loff) = zn_prev;
     }
 
     DIAG(const unsigned long long d_loop = diag_stamp();)
     __syncthreads();
     DIAG(const unsigned long long d_sync = diag_stamp();)
-    flush_hist(hist, K, P, a.dS + (size_t)(blockIdx.x % kDeltaReps) * K * P, a.dNk + (blockIdx.x % kDeltaReps) * K, tid, NT);
+    {
+        const PkArgsView v = pk_args_view();
+        const int Kc = v.p->K, Pc = v.p->P;
+        const TableLayout Lc{v.p->G, KT, v.p->Gm, GM};
+        const int rep = blockIdx.x % kDeltaReps;
+        flush_hist(pk_lds(smem, Lc).hist, Kc, Pc, v.a->dS + (size_t)rep * Kc * Pc, v.a->dNk + rep * Kc, tid, NT);
+    }
     // diagnostic build: per-launch phases in the slots k_resample reports them in; workgroup-launches and entry to
     // flushed in [7] and [14], which k_resample leaves alone; from wave 0 of the workgroup only (every wave's atomics
     // on one line, as k_resample has them, take longer than this launch and hold up the global loads of workgroups
@@ -1641,7 +1824,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
 #ifdef BMM_DEBUG_HOOKS
     if (a.pk_stat) {  // test variant: draws made and valid lanes settled by the definition (bmm_dbg_pk_counts)
         if (tid == 0) {
-            int64_t first = a.lo + wg_c0 * 64, last = a.lo + (wg_c0 + (wg_cn > 0 ? wg_cn : 0)) * 64;
+            int64_t first = a.lo + (int64_t)wg_c0 * 64, last = a.lo + ((int64_t)wg_c0 + (wg_cn > 0 ? wg_cn : 0)) * 64;
             last = last < a.hi ? last : a.hi;
             if (last > first) atomicAdd(&a.pk_stat[0], (unsigned long long)(last - first));
         }
@@ -2577,6 +2760,36 @@ __global__ void k_test_math(int op, const double* in, const double* in2, double*
     else y = expw_(x);
     out[i] = y;
 }
+#ifdef BMM_DEBUG_HOOKS
+// Test variant: k_resample_pk's draw (pk_draw2; SPEC = false) or the statement it is held to (draw_pk, bmm_spec.h;
+// SPEC = true) on rows of scores and their uniforms, one row per lane; the maximum is taken as the kernel takes it.
+// out[2 i ...]: count and verdict.  Two kernels, so that neither draw shares a subexpression with the other
+// (tests/test_gpu_pk_lean.py compares them).
+template <int KT, bool SPEC>
+__global__ __launch_bounds__(256) void k_test_pk_draw(const float* __restrict__ scores, const double* __restrict__ u,
+                                                      int G, int64_t n, int* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float sc[KT];
+    float m = -__builtin_inff();
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+        sc[k] = scores[i * KT + k];
+        m = __builtin_fmaxf(m, sc[k]);
+    }
+    int cnt = 0;
+    bool ok;
+    if constexpr (SPEC) {
+        ok = draw_pk<KT>(sc, m, u[i], G, kPkEpsUnit, cnt);
+    } else {
+        pk_f2 s2[KT / 2];
+#pragma unroll
+        for (int j = 0; j < KT / 2; ++j) s2[j] = pk_f2{sc[2 * j], sc[2 * j + 1]};
+        ok = pk_draw2<KT>(s2, m, u[i], G, kPkEpsUnit, cnt);
+    }
+    out[2 * i] = cnt; out[2 * i + 1] = ok ? 1 : 0;
+}
+#endif
 __global__ void k_test_variates(int kind, double pp, double qq, uint64_t seed, uint32_t sweep, double* out,
                                 int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
