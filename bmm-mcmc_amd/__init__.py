@@ -22,7 +22,7 @@ __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "
            "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
            "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
            "partition_distances", "posterior_similarity", "partition_plan", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
-           "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat", "Ladder", "temper_ladder", "TEMPER_MAX_RUNGS"]
+           "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat", "pair_check", "pair_check_plan", "pair_check_pairs", "PAIR_CHECK_MAX_M", "Ladder", "temper_ladder", "TEMPER_MAX_RUNGS"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -823,6 +823,134 @@ def _ecr_map(outs, req, K, device):
     return _ecr_chains(outs, (_ECR_GIVEN, _np.ascontiguousarray(lps[top]["z_map"], dtype=_np.int32), req[2]), K, device)
 
 
+# ---------------------------------------------------------------- pair_check=: pairwise local-dependence check
+PAIR_CHECK_MAX_M = 128  # include/bmm_mcmc.h BMM_PAIR_CHECK_MAX_M
+
+
+class _PairCheckOut(_C.Structure):  # bmm_pair_check_out
+    _fields_ = [("feat", _C.c_void_p), ("M", _C.c_int), ("stride", _C.c_int), ("z_rows", _C.c_void_p), ("x2_rows", _C.c_void_p),
+                ("sum_z", _C.c_void_p), ("sum_z2", _C.c_void_p), ("sum_x2", _C.c_void_p), ("sum_df", _C.c_void_p),
+                ("n_z", _C.c_void_p), ("n11", _C.c_void_p), ("n_folded", _C.c_void_p)]
+
+
+class _PairCheckPlanOut(_C.Structure):  # bmm_pair_check_plan_out
+    _fields_ = [("bytes_slices", _C.c_int64), ("bytes_counts", _C.c_int64), ("bytes_fold", _C.c_int64), ("chunks", _C.c_int64),
+                ("chunks_per_slice", _C.c_int64), ("chunks_per_round", _C.c_int), ("tiles", _C.c_int), ("row_slices", _C.c_int),
+                ("label_blocks", _C.c_int), ("ka", _C.c_int), ("pairs_per_lane", _C.c_int), ("threads", _C.c_int)]
+
+
+def _pc_features(features, P):
+    """the chosen features as int32: True / None means all P of them, which needs P <= PAIR_CHECK_MAX_M"""
+    if features is None or features is True:
+        if P > PAIR_CHECK_MAX_M:
+            raise ValueError("pair_check=True checks every pair of the %d features, more than %d: give a list of feature "
+                             "indices" % (P, PAIR_CHECK_MAX_M))
+        return _np.arange(P, dtype=_np.int32)
+    f = _np.ascontiguousarray(_np.asarray(features).ravel(), dtype=_np.int32)
+    if not 2 <= f.size <= PAIR_CHECK_MAX_M:
+        raise ValueError("pair_check takes 2 to %d features, not %d" % (PAIR_CHECK_MAX_M, f.size))
+    if f.min() < 0 or f.max() >= P:
+        raise ValueError("pair_check: a feature index lies outside 0..%d" % (P - 1))
+    if _np.unique(f).size != f.size:
+        raise ValueError("pair_check: the chosen features must be distinct")
+    return f
+
+
+def pair_check_pairs(M):
+    """the (npairs, 2) positions (i < j) in the feature list, in the library's pair order: numpy.triu_indices(M, 1)"""
+    i, j = _np.triu_indices(int(M), 1)
+    return _np.stack([i, j], axis=1).astype(_np.int32)
+
+
+class _PairFold:
+    """the host side of a fold: the buffers a bmm_pair_check_out points at, and the summary made of them"""
+
+    def __init__(self, feat, stride=1, S=0, trace=False):
+        self.feat = feat
+        M = feat.size
+        np_ = M * (M - 1) // 2
+        self.sum_z, self.sum_z2, self.sum_x2 = _np.zeros(np_), _np.zeros(np_), _np.zeros(np_)
+        self.sum_df = _np.zeros(np_, dtype=_np.int64)
+        self.n_z = _np.zeros(np_, dtype=_np.int32)
+        self.n11 = _np.zeros(np_, dtype=_np.uint32)
+        self.n_folded = _C.c_int(0)
+        self.z = _np.full((S, np_), _np.nan, order="F") if trace else None
+        self.x2 = _np.full((S, np_), _np.nan, order="F") if trace else None
+        self.s = _PairCheckOut(feat.ctypes.data, M, int(stride), None if self.z is None else self.z.ctypes.data,
+                               None if self.x2 is None else self.x2.ctypes.data, self.sum_z.ctypes.data, self.sum_z2.ctypes.data,
+                               self.sum_x2.ctypes.data, self.sum_df.ctypes.data, self.n_z.ctypes.data, self.n11.ctypes.data,
+                               _C.addressof(self.n_folded))
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_pair_check(_C.byref(self.s)))
+
+    def result(self):
+        n, nz = self.n_folded.value, self.n_z
+        with _np.errstate(invalid="ignore", divide="ignore"):
+            out = {"features": self.feat.copy(), "pairs": pair_check_pairs(self.feat.size), "n11": self.n11,
+                   "z_mean": _np.where(nz > 0, self.sum_z / nz, _np.nan), "z_rms": _np.where(nz > 0, _np.sqrt(self.sum_z2 / nz), _np.nan),
+                   "x2_mean": self.sum_x2 / n if n else _np.full(self.sum_x2.shape, _np.nan),
+                   "df_mean": self.sum_df / n if n else _np.full(self.sum_x2.shape, _np.nan), "n_folded": n,
+                   "sum_z": self.sum_z, "sum_z2": self.sum_z2, "sum_x2": self.sum_x2, "sum_df": self.sum_df, "n_z": nz}
+        if self.z is not None:
+            out["z"], out["x2"] = self.z, self.x2
+        return out
+
+
+def _make_pair_check(pair_check, stride, trace, P, S, chains):
+    """pair_check= of a wrapper: the outputs to arm, None when off; refused before a device is touched"""
+    if pair_check is None or pair_check is False:
+        return None
+    if int(chains) > 1:
+        raise ValueError("pair_check= is offered per chain (chains=1)")
+    if int(stride) < 1:
+        raise ValueError("pair_check_stride must be >= 1")
+    return _PairFold(_pc_features(pair_check, P), stride, S, bool(trace))
+
+
+def _with_pair_check(out, pc):
+    if pc is not None:
+        out["pair_check"] = pc.result()
+    return out
+
+
+def pair_check(X, z, Kc, features=None, counts=False, device=0):
+    """The pairwise local-dependence check of any stack of label rows over the data X, on the device
+    (bmm_device_pair_check; include/bmm_mcmc.h "pairwise local-dependence check").  z: (S, N)
+    labels in 1..Kc, as a run returns them (or one row); features: the chosen feature indices (default: all P, which
+    needs P <= 128).  Returns the summary of a run's out["pair_check"] folded over the S rows, with "z" and "x2" (S,
+    npairs), and with counts=True "counts" (S, Kc, npairs) uint32, the co-occurrence counts per label.  A run's own z
+    gives the run's rows bit for bit."""
+    X = _capi.as_x(X)
+    N, P = X.shape
+    z = _np.asarray(z)
+    z = _as_trace(z.reshape(1, -1) if z.ndim == 1 else z)
+    S = z.shape[0]
+    if z.shape[1] != N:
+        raise ValueError("z must have one column per observation")
+    fold = _PairFold(_pc_features(features, P))
+    np_ = fold.sum_z.size
+    rows = _np.full((S, 2 * np_), _np.nan, order="F")
+    cnt = _np.zeros((S, int(Kc), np_), dtype=_np.uint32) if counts else None
+    _capi.check(_capi.lib().bmm_device_pair_check(
+        _C.c_int(device), _capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(int(Kc)), _capi.vp(z), _C.c_int(S),
+        _capi.vp(fold.feat), _C.c_int(fold.feat.size), None if cnt is None else _capi.vp(cnt), _capi.vp(rows), _C.byref(fold.s)))
+    out = fold.result()
+    out["z"], out["x2"] = _np.ascontiguousarray(rows[:, :np_]), _np.ascontiguousarray(rows[:, np_:])
+    if counts:
+        out["counts"] = cnt
+    return out
+
+
+def pair_check_plan(N, Kc, M):
+    """What the check needs on the device and the grid of its counting kernel (bmm_pair_check_plan): a dict of
+    bytes_slices, bytes_counts, bytes_fold, chunks (of 64 rows), chunks_per_slice, chunks_per_round, tiles, row_slices,
+    label_blocks, ka, pairs_per_lane, threads"""
+    o = _PairCheckPlanOut()
+    _capi.check(_capi.lib().bmm_pair_check_plan(_C.c_int64(int(N)), _C.c_int(int(Kc)), _C.c_int(int(M)), _C.byref(o)))
+    return {k: int(getattr(o, k)) for k, _ in _PairCheckPlanOut._fields_}
+
+
 # ---------------------------------------------------------------- split_merge=: Jain & Neal's move for the DP chain
 SPLIT_MERGE_SCANS = 5  # the default of split_merge_scans (DESIGN.md section 15 says where it comes from)
 _SM_FIELDS = ("split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped")
@@ -1044,7 +1172,7 @@ class _Init:
         return info.as_dict()
 
 
-def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None, lp=None, tp=None):
+def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None, lp=None, tp=None, pc=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
@@ -1062,6 +1190,8 @@ def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=
         lp.arm()
     if tp is not None:
         tp.arm()
+    if pc is not None:
+        pc.arm()
     if init is not None:  # last, just ahead of the call: a run of another sampler refuses an armed start
         init.arm()
     if pr is None:
@@ -1220,7 +1350,8 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                     initial_K=None, chains=1, devices=None, stephens=None, newdata=None, predictive_trace=False,
                     responsibilities=False, partition=None, partition_stride=1, similarity_of=None, loo=False,
                     select_features=False, rho=0.5, init="random", init_iters=INIT_ITERS, ecr_pivot="iterative",
-                    ecr_max_iter=50, logpost=False, temper=None, swap_every=1, temper_hottest=0.1):
+                    ecr_max_iter=50, logpost=False, temper=None, swap_every=1, temper_hottest=0.1, pair_check=None,
+                    pair_check_stride=1, pair_check_trace=False):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -1288,6 +1419,17 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     the exchanges per neighbouring pair, which starting rung's state sat at power 1 after each kept sweep, and every
     rung's log_lik after the exchange points of kept sweeps (NaN elsewhere).  temper=[1.0] is the run without it, byte
     for byte.  Not with chains > 1, relabel=, select_features= (or split_merge= on gibbs_dp).
+    `pair_check=True` or a list of 2 to 128 feature indices: the model check of local independence (include/bmm_mcmc.h
+    "pairwise local-dependence check").  For every pair of the chosen features and every
+    `pair_check_stride`-th kept sweep the device counts the co-occurrences per cluster and scores them against their
+    hypergeometric reference given the labels and the margins: Z, the Cochran-Mantel-Haenszel score (about N(0, 1)
+    under the model, signed), and X2, the per-cluster chi-square sum with df degrees of freedom (it also sees
+    dependence whose sign differs between clusters).  The result gains `pair_check = {"features", "pairs" (npairs, 2:
+    positions in `features`, numpy.triu_indices order), "n11" (co-occurrences in the data), "z_mean", "z_rms", "x2_mean",
+    "df_mean" (npairs,), "n_folded"}` plus the raw sums, and with `pair_check_trace=True` "z" and "x2" (S, npairs), NaN
+    where a sweep was not evaluated.  |z_mean| well above 4, or x2_mean far above df_mean, names a pair of features
+    that stays associated inside the clusters.  It reads state only and changes no chain.  True needs P <= 128; per
+    chain (chains=1); not with select_features=.
     """
     X = _capi.as_x(data)
     N, P = X.shape
@@ -1305,6 +1447,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, False, newdata, loo)
     lo = _make_loo(loo, N, nsamples - burnin, chains, False)
     lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
+    pc = _make_pair_check(pair_check, pair_check_stride, pair_check_trace, P, nsamples - burnin, chains)
     tp = _make_temper(temper, swap_every, nsamples - burnin, chains, temper_hottest)
 
     def done(out):
@@ -1314,7 +1457,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             out["features"] = fs.result()
         if ini is not None:
             out["init"] = ini.result()
-        return _with_logpost(out, lp, ecr_map, K, device)
+        return _with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc)
     if chains > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
@@ -1356,7 +1499,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
                 _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini, lp=lp, tp=tp)
+            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini, lp=lp, tp=tp, pc=pc)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
@@ -1368,7 +1511,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
             _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp, pc=pc)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1381,7 +1524,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
              stephens=None, newdata=None, predictive_trace=False, responsibilities=False, partition=None,
              partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None,
              select_features=False, rho=0.5, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
-             temper=None, swap_every=1, temper_hottest=0.1):
+             temper=None, swap_every=1, temper_hottest=0.1, pair_check=None, pair_check_stride=1, pair_check_trace=False):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
@@ -1390,8 +1533,9 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     `split_merge = {"split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped"}`.  Per chain.
     `select_features`, `rho`: as gibbs_collapsed (needs beta == gamma; not with split_merge=).  `init`: "random" only (a
     DP run seats its rows in its first sweep; Chain.init_labels re-seats a resident DP chain).  `logpost`,
-    `ecr_pivot="map"`: as gibbs_collapsed.  `temper`, `swap_every`, `temper_hottest`: as gibbs_collapsed (the helper
-    chains seat their own rows in their first sweep; the new-cluster option carries the power on its likelihood part)."""
+    `ecr_pivot="map"`, `pair_check`, `pair_check_stride`, `pair_check_trace`: as gibbs_collapsed.  `temper`,
+    `swap_every`, `temper_hottest`: as gibbs_collapsed (the helper chains seat their own rows in their first sweep; the
+    new-cluster option carries the power on its likelihood part)."""
     _init_kind(init, 0, allowed=False)
     X = _capi.as_x(data)
     N, P = X.shape
@@ -1405,6 +1549,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, True, newdata, loo, split_merge)
     sm = _make_split_merge(split_merge, split_merge_scans, chains)
     lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
+    pc = _make_pair_check(pair_check, pair_check_stride, pair_check_trace, P, nsamples - burnin, chains)
     tp = _make_temper(temper, swap_every, nsamples - burnin, chains, temper_hottest)
 
     def done(out):
@@ -1414,7 +1559,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             out["split_merge"] = sm.result()
         if fs is not None:
             out["features"] = fs.result()
-        return _with_logpost(out, lp, ecr_map, maxK, device)
+        return _with_pair_check(_with_logpost(out, lp, ecr_map, maxK, device), pc)
     if int(chains) > 1:
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
@@ -1437,7 +1582,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                 _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
                 _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs, lp=lp, tp=tp)
+            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs, lp=lp, tp=tp, pc=pc)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, maxK, P, S)
@@ -1450,7 +1595,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp)
+        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp, pc=pc)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1461,7 +1606,8 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
 def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, burnin, relabel, burnrelabel, seed,
               device, initial_pi, initial_theta, chains, devices, stephens, debug=False, newdata=None,
               predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None,
-              loo=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False):
+              loo=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1,
+              pair_check_trace=False):
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, K = int(nsamples), int(K)
@@ -1473,10 +1619,11 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     lo = _make_loo(loo, N, nsamples - burnin, chains, True)
     lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
+    pc = _make_pair_check(pair_check, pair_check_stride, pair_check_trace, P, nsamples - burnin, chains)
     base = fn[len("bmm_"):-len("_run_probs")]
 
     def done(out):
-        return _with_logpost(out, lp, ecr_map, K, device)
+        return _with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc)
 
     def start(sd, pi, th):
         rng = _np.random.default_rng(sd)
@@ -1518,7 +1665,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
                 _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
                 _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run(base, args, pr, rel=dr, part=pt, loo=lo, lp=lp)
+            rc = _run(base, args, pr, rel=dr, part=pt, loo=lo, lp=lp, pc=pc)
         return done(_with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
@@ -1531,7 +1678,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
             _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec, lp=lp)
+        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec, lp=lp, pc=pc)
     out = {"pi": pi, "alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1543,32 +1690,35 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
                         relabel=False, burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None,
                         initial_theta=None, chains=1, devices=None, stephens=None, newdata=None,
                         predictive_trace=False, responsibilities=False, partition=None, partition_stride=1,
-                        similarity_of=None, loo=False, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False):
+                        similarity_of=None, loo=False, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
+                        pair_check=None, pair_check_stride=1, pair_check_trace=False):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
     src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
     "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`: as gibbs_collapsed; log_prior is
-    the stick-breaking prior with the sticks integrated out, which depends on the order of the labels."""
+    the stick-breaking prior with the sticks integrated out, which depends on the order of the labels.  `pair_check`,
+    `pair_check_stride`, `pair_check_trace`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
     return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
                      burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter, logpost)
+                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
                burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None, initial_theta=None, chains=1,
                devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False,
                partition=None, partition_stride=1, similarity_of=None, loo=False, init="random", ecr_pivot="iterative",
-               ecr_max_iter=50, logpost=False):
+               ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1, pair_check_trace=False):
     """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
-    "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`: as gibbs_collapsed."""
+    "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`, `pair_check`,
+    `pair_check_stride`, `pair_check_trace`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
     return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
                      relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter, logpost)
+                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace)
 
 
 class Chain:
@@ -1848,6 +1998,59 @@ class Chain:
         on, b = _C.c_int(0), _C.c_double(1.0)
         _capi.check(_capi.lib().bmm_chain_get_temper(self._h, _C.byref(on), _C.byref(b)))
         return bool(on.value), b.value
+
+    # -- pairwise local-dependence check (include/bmm_mcmc.h)
+    def set_pair_check(self, features=True, stride=1):
+        """Arm the pair check on `features` (True: all P, which needs P <= 128; a list of 2 to 128 distinct indices), every
+        `stride`-th folded sweep evaluated; None or False disarms and frees its memory.  Arming an armed chain empties
+        the fold and takes the new features."""
+        if features is None or features is False:
+            _capi.check(_capi.lib().bmm_chain_set_pair_check(self._h, None, _C.c_int(0), _C.c_int(1)))
+            self._pc_feat = None
+            return
+        f = _pc_features(features, self.P)
+        _capi.check(_capi.lib().bmm_chain_set_pair_check(self._h, _capi.vp(f), _C.c_int(f.size), _C.c_int(int(stride))))
+        self._pc_feat = f
+
+    def _pc_np(self):
+        f = getattr(self, "_pc_feat", None)
+        if f is None:
+            raise _capi.BmmError(5, "the pair check is not armed (Chain.set_pair_check)")
+        return f.size * (f.size - 1) // 2
+
+    def pair_check_state(self):
+        """{"z", "x2" (npairs,), "df" (npairs,) int32} of the current state: no sweep, the fold untouched"""
+        n = self._pc_np()
+        z, x2, df = _np.empty(n), _np.empty(n), _np.empty(n, dtype=_np.int32)
+        _capi.check(_capi.lib().bmm_chain_pair_check_state(self._h, _capi.vp(z), _capi.vp(x2), _capi.vp(df)))
+        return {"z": z, "x2": x2, "df": df}
+
+    def pair_counts(self, margins=False):
+        """the (Kc, npairs) uint32 co-occurrence counts of the current state; margins=True: also the (Kc, M) ones per
+        label and chosen feature and the (Kc,) rows per label, counted in the same pass"""
+        n, K, M = self._pc_np(), self.K, self._pc_feat.size
+        c = _np.empty((K, n), dtype=_np.uint32)
+        m, r = _np.empty((K, M), dtype=_np.uint32), _np.empty(K, dtype=_np.uint32)
+        _capi.check(_capi.lib().bmm_chain_pair_counts(self._h, _capi.vp(c), _capi.vp(m), _capi.vp(r)))
+        return (c, m, r) if margins else c
+
+    def sweeps_pair_check(self, n, trace=False):
+        """n more sweeps, sweeps 0, stride, 2 stride, ... of them evaluated and folded; trace=True returns {"z", "x2"}, each
+        (n, npairs) with NaN where a sweep was not evaluated, and waits"""
+        n, np_ = int(n), self._pc_np()
+        rows = _np.full((n, 2 * np_), _np.nan, order="F") if trace else None
+        _capi.check(_capi.lib().bmm_chain_sweeps_pair_check(self._h, _C.c_int(n), _capi.vp(rows) if trace else None))
+        return {"z": _np.ascontiguousarray(rows[:, :np_]), "x2": _np.ascontiguousarray(rows[:, np_:])} if trace else None
+
+    def pair_check(self):
+        """the fold so far: the summary of a run's out["pair_check"]"""
+        self._pc_np()
+        fold = _PairFold(self._pc_feat)
+        _capi.check(_capi.lib().bmm_chain_get_pair_check(self._h, _C.byref(fold.s)))
+        return fold.result()
+
+    def pair_check_reset(self):
+        _capi.check(_capi.lib().bmm_chain_pair_check_reset(self._h))
 
     def set_split_merge(self, moves_per_sweep, scans=SPLIT_MERGE_SCANS):
         """`moves_per_sweep` moves at the start of every sweep from the second (0: off), `scans` intermediate scans each."""

@@ -46,6 +46,8 @@ SYMBOLS = [
     "bmm_chain_logpost_reset", "bmm_set_logpost", "bmm_device_log_joint",
     "bmm_chain_set_temper", "bmm_chain_get_temper", "bmm_ladder_create", "bmm_ladder_destroy", "bmm_ladder_sweeps",
     "bmm_ladder_exchange_step", "bmm_ladder_stats", "bmm_set_temper",
+    "bmm_chain_set_pair_check", "bmm_chain_pair_check_state", "bmm_chain_sweeps_pair_check", "bmm_chain_get_pair_check",
+    "bmm_chain_pair_check_reset", "bmm_chain_pair_counts", "bmm_set_pair_check", "bmm_device_pair_check", "bmm_pair_check_plan",
 ]
 
 
@@ -77,6 +79,13 @@ def load(path):
     L.bmm_chain_destroy.restype = None
     L.bmm_chain_destroy.argtypes = [C.c_void_p]
     L.bmm_chain_share_data.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(L, "bmm_chain_set_pair_check"):  # (an older build loaded for a comparison has no pair check)
+        L.bmm_chain_set_pair_check.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.bmm_chain_pair_check_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bmm_chain_sweeps_pair_check.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.bmm_chain_get_pair_check.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmm_chain_pair_check_reset.argtypes = [C.c_void_p]
+        L.bmm_chain_pair_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "bmm_ladder_create"):  # (an older build loaded for a comparison has no ladder)
         L.bmm_ladder_destroy.restype = None
         L.bmm_ladder_destroy.argtypes = [C.c_void_p]

@@ -834,4 +834,49 @@ inline void log_joint_spec(const LjModel& m, const int32_t* Nk, const int32_t* S
     lj_finish(m, lik, prior, [Nk](int k) { return (int64_t)Nk[k]; }, pooled, out);
 }
 
+// ---------------------------------------------------------------- pairwise local-dependence check of a state
+// The bivariate residuals of a state (include/bmm_mcmc.h "pairwise local-dependence check").
+// Given the labels and each label's margins the co-occurrence count c_k(d, e) is Hypergeometric(n_k, s_kd, s_ke);
+// per pair the labels are taken in ascending order, labels of fewer than two rows skipped, and every integer below is
+// formed in int64 and converted to binary64 once.  pc_label adds one label to the running sums; pc_z closes the pair.
+// k_pc_stats and the host statement (pair_check_spec) call these and nothing else.
+constexpr int kPcMaxM = 128;
+struct PcSums {
+    double A, V, X2;  // sum of (c - E), of the variances, of the per-label chi-squares
+    int32_t df;       // labels with a positive variance
+};
+BMM_HD PcSums pc_zero() { PcSums s; s.A = 0.0; s.V = 0.0; s.X2 = 0.0; s.df = 0; return s; }
+BMM_HD void pc_label(PcSums& t, int64_t c, int64_t n, int64_t sd, int64_t se) {
+    if (n < 2) return;
+    const int64_t num = c * n - sd * se, pd = sd * (n - sd), pe = se * (n - se), nn = n * n;
+    const double a = div_((double)num, (double)n);
+    const double v = div_((double)pd * (double)pe, (double)nn * (double)(n - 1));
+    t.A = t.A + a;
+    t.V = t.V + v;
+    if (v > 0.0) { t.X2 = t.X2 + div_(a * a, v); t.df += 1; }
+}
+// Z of the pair, or NaN when no label has a positive variance
+BMM_HD double pc_z(const PcSums& t) { return t.V > 0.0 ? div_(t.A, sqrt_(t.V)) : qnan(); }
+// pairs (i < j) of positions in the feature list, numbered as numpy.triu_indices(M, 1) numbers them
+BMM_HD int64_t pc_pair_index(int i, int j, int M) { return (int64_t)i * M - (int64_t)i * (i + 1) / 2 + (j - i - 1); }
+BMM_HD int64_t pc_npairs(int M) { return (int64_t)M * (M - 1) / 2; }
+BMM_HD void pc_pair_ij(int64_t q, int M, int& i, int& j) {
+    int r = 0;
+    while (q >= M - 1 - r) { q -= M - 1 - r; ++r; }
+    i = r; j = r + 1 + (int)q;
+}
+// The whole statement for the host: cnt[Kc][npairs], nk[Kc], marg[Kc][M]; z, x2 [npairs] doubles, df [npairs] int32.
+inline void pair_check_spec(int Kc, int M, const uint32_t* cnt, const uint32_t* nk, const uint32_t* marg, double* z,
+                            double* x2, int32_t* df) {
+    const int64_t np = pc_npairs(M);
+    for (int64_t q = 0; q < np; ++q) {
+        int i = 0, j = 0;
+        pc_pair_ij(q, M, i, j);
+        PcSums t = pc_zero();
+        for (int k = 0; k < Kc; ++k)
+            pc_label(t, (int64_t)cnt[(size_t)k * np + q], (int64_t)nk[k], (int64_t)marg[(size_t)k * M + i], (int64_t)marg[(size_t)k * M + j]);
+        z[q] = pc_z(t); x2[q] = t.X2; df[q] = t.df;
+    }
+}
+
 }  // namespace bmm

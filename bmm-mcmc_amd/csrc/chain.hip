@@ -629,7 +629,25 @@ struct bmm_chain {
     int32_t* dLjZ = nullptr;
     int lp_folded = 0;  // states folded so far
     SweepTrace lp_rec;
-    bool lp_defer = false;  // a ladder's exchange point follows this sweep: the ladder folds the row behind it
+    // a ladder's exchange point follows this sweep: the recorders that score rung 0's state (the log joint row, the pair
+    // check) are enqueued by the ladder behind the exchange, not by the sweep end.  Set whether or not either is armed.
+    bool fold_defer = false;
+    // pairwise local-dependence check: the chosen features (host and device), their column
+    // slices [M][pc_C], one block with the counts of the last state scored, its values and the fold; pc_rec: the
+    // sweeps that are folded (every pc_stride-th from its base) and the rows of 2 npairs doubles they are recorded in
+    bool pc_on = false;
+    int pc_M = 0, pc_stride = 1;
+    int64_t pc_C = 0;
+    int32_t* dPcFeat = nullptr;
+    uint64_t* dPcXt = nullptr;
+    char* dPcBlock = nullptr;
+    size_t pc_count_bytes = 0, pc_fold_bytes = 0;
+    uint32_t *dPcCnt = nullptr, *dPcMarg = nullptr, *dPcNk = nullptr, *dPcN11 = nullptr;
+    double *dPcZ = nullptr, *dPcX2 = nullptr, *dPcSumZ = nullptr, *dPcSumZ2 = nullptr, *dPcSumX2 = nullptr;
+    long long* dPcSumDf = nullptr;
+    int32_t *dPcDf = nullptr, *dPcNz = nullptr;
+    int pc_folded = 0;  // states folded so far
+    SweepTrace pc_rec;
     // parallel tempering: temper_on: the table builds are k_temper_tables at inverse temperature
     // temper_b, and the kernel choice leaves out the forms that build their own tables and the packed one; ladder: the
     // replica ladder a run drives this chain through as its rung 0 (not owned)
@@ -705,7 +723,7 @@ int run_rows_out(const bmm_chain* c, const double* dtrace, int64_t width, double
 }
 
 // What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_loo_summary,
-// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost, bmm_set_temper; bmm_alloc_run fills `alloc` for its own run), and what a
+// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost, bmm_set_temper, bmm_set_pair_check; bmm_alloc_run fills `alloc` for its own run), and what a
 // *_run_predict / *_run_relabel / *_run_probs entry point was handed.
 struct RunOptions {
     struct { bool on = false; bmm_partition_out o{}; } partition;
@@ -716,6 +734,7 @@ struct RunOptions {
     struct { bool on = false; bmm_ecr_out o{}; } ecr;
     struct { bool on = false; bmm_logpost_out o{}; } logpost;
     struct { bool on = false; bmm_temper_out o{}; } temper;
+    struct { bool on = false; bmm_pair_check_out o{}; std::vector<int32_t> feat; } pc;
     struct { bool on = false; const double* log_prior_k = nullptr; int K0 = 0, moves = 0; double eject_a = 1.0; int32_t* k_out = nullptr; int64_t* moves_out = nullptr; } alloc;
     const bmm_relabel_hooks* hooks = nullptr;  // *_run_probs
     const bmm_relabel_out* rel = nullptr;      // *_run_relabel
@@ -1294,11 +1313,74 @@ int enqueue_log_joint(bmm_chain* c, int j, double* row, bool fold) {
     c->lp_folded++;
     return BMM_OK;
 }
-// the end of sweep j: what a predictive run, a leave-one-out run, a log joint trace or the resident calls asked to fold
+// ---- pairwise local-dependence check ----
+// The grid of k_pc_counts and the bytes behind it, a pure function of (N, Kc, M): a tile per kPcTile x kPcTile block of
+// the upper triangle, kPcKA labels per workgroup and further label blocks on grid.z, and as many row slices as bring
+// the grid to about eight workgroups per compute unit of a 256-unit device, none shorter than two rounds.
+struct PcPlan {
+    int64_t C, cps, npairs;
+    int tiles, slices, kblocks, ka;
+    size_t bytes_slices, bytes_counts, bytes_fold;
+};
+PcPlan pc_plan(int64_t N, int Kc, int M) {
+    PcPlan q{};
+    q.C = (N + 63) / 64;
+    q.npairs = pc_npairs(M);
+    const int T = (M + kPcTile - 1) / kPcTile;
+    q.tiles = T * (T + 1) / 2;
+    q.ka = kPcKA;
+    q.kblocks = (Kc + q.ka - 1) / q.ka;
+    int64_t most = 2048 / ((int64_t)q.tiles * q.kblocks);
+    if (most < 1) most = 1;
+    int64_t cps = ((q.C + most - 1) / most + kPcRound - 1) / kPcRound * kPcRound;
+    if (cps < 2 * kPcRound) cps = 2 * kPcRound;
+    q.cps = cps;
+    q.slices = (int)((q.C + cps - 1) / cps);
+    q.bytes_slices = (size_t)M * (size_t)q.C * sizeof(uint64_t);
+    q.bytes_counts = (size_t)Kc * ((size_t)q.npairs + (size_t)M + 1) * sizeof(uint32_t);
+    q.bytes_fold = (size_t)q.npairs * (5 * sizeof(double) + sizeof(long long) + 2 * sizeof(int32_t) + sizeof(uint32_t));
+    return q;
+}
+// Count and score the label row z (device, 0-based, every row seated), stream-ordered behind whatever wrote it: the
+// state's values go to dPcZ / dPcX2 / dPcDf and to `row` (device, may be null); fold adds them to the sums.
+int enqueue_pair_check(bmm_chain* c, const int32_t* z, double* row, bool fold) {
+    const PcPlan q = pc_plan(c->p.N, c->p.K, c->pc_M);
+    HIP_TRY(hipMemsetAsync(c->dPcCnt, 0, c->pc_count_bytes, c->stream));
+    PcArgs a{};
+    a.Xt = c->dPcXt; a.z = z; a.N = c->p.N; a.C = q.C; a.cps = q.cps; a.M = c->pc_M; a.Kc = c->p.K;
+    a.cnt = c->dPcCnt; a.marg = c->dPcMarg; a.nk = c->dPcNk;
+    const dim3 grid((unsigned)q.tiles, (unsigned)q.slices, (unsigned)q.kblocks);
+    hipLaunchKernelGGL((k_pc_counts<kPcKA, kPcR>), grid, dim3(kPcThreads), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    PcStatArgs s{};
+    s.cnt = c->dPcCnt; s.marg = c->dPcMarg; s.nk = c->dPcNk; s.M = c->pc_M; s.Kc = c->p.K;
+    s.z = c->dPcZ; s.x2 = c->dPcX2; s.df = c->dPcDf; s.out_row = row;
+    s.sum_z = c->dPcSumZ; s.sum_z2 = c->dPcSumZ2; s.sum_x2 = c->dPcSumX2; s.sum_df = c->dPcSumDf; s.n_z = c->dPcNz; s.n11 = c->dPcN11;
+    s.fold = fold ? 1 : 0;
+    hipLaunchKernelGGL(k_pc_stats, dim3((unsigned)((q.npairs + 255) / 256)), dim3(256), 0, c->stream, s);
+    HIP_TRY(hipGetLastError());
+    if (fold) c->pc_folded++;
+    return BMM_OK;
+}
+// X is cut into the check's column slices once, when it is armed: new data under an armed check would leave slices of
+// the old matrix behind, so the data entry points refuse until the check is disarmed
+int pc_data_locked(const bmm_chain* c) {
+    if (c->pc_on)
+        return set_err(BMM_E_STATE, "the pair check is armed on the data the chain holds: disarm it (bmm_chain_set_pair_check with "
+                       "no features) before new data is set, and arm it again afterwards");
+    return BMM_OK;
+}
+// whether sweep j is one the check evaluates: folded, and a multiple of the stride from the recording's first row
+bool pc_folds(const bmm_chain* c, int j) {
+    return c->pc_on && c->pc_rec.folds(j) && (j - c->pc_rec.base) % c->pc_stride == 0;
+}
+// the end of sweep j: what a predictive run, a leave-one-out run, a log joint trace, a pair check or the resident calls
+// asked to fold
 int sweep_end_folds(bmm_chain* c, int j) {
     int rc = sweep_end_predict(c, j);
     if (rc == BMM_OK && c->loo_rec.folds(j) && c->loo_on) rc = enqueue_loo(c, j, c->loo_rec.row<double>(j), true);
-    if (rc == BMM_OK && c->lp_rec.folds(j) && c->lp_on && !c->lp_defer) rc = enqueue_log_joint(c, j, c->lp_rec.row<double>(j), true);
+    if (rc == BMM_OK && c->lp_rec.folds(j) && c->lp_on && !c->fold_defer) rc = enqueue_log_joint(c, j, c->lp_rec.row<double>(j), true);
+    if (rc == BMM_OK && pc_folds(c, j) && !c->fold_defer) rc = enqueue_pair_check(c, label_row(c, j), c->pc_rec.row<double>(j), true);
     return rc;
 }
 
@@ -1948,7 +2030,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     dev_pool().put(c->device, c->run_arena, c->run_arena_bytes);
     void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
                     c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch, c->dSmSide, c->dSmSideLaunch, c->dSmLq, c->dSmStat, c->dSmCell,
-                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dLjBlock, c->dLjZ};
+                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     chain_stream_release(c->device, c->stream, c->stream_kind);  // synchronised above
@@ -1983,6 +2065,7 @@ int bmm_chain_get_x_layout(const bmm_chain* c, int* layout) {
 int bmm_chain_set_data_host(bmm_chain* c, const int32_t* X) {
     if (!c || !X) return set_err(BMM_E_ARG, "null argument");
     if (c->started) return set_err(BMM_E_STATE, "chain already started");
+    if (pc_data_locked(c)) return BMM_E_STATE;
     HIP_TRY(hipSetDevice(c->device));
     const int64_t N = c->p.N;
     const int P = c->p.P;
@@ -2048,6 +2131,7 @@ int bmm_chain_set_data_host(bmm_chain* c, const int32_t* X) {
 int bmm_chain_set_data_device(bmm_chain* c, const void* dX) {
     if (!c || !dX) return set_err(BMM_E_ARG, "null argument");
     if (c->started) return set_err(BMM_E_STATE, "chain already started");
+    if (pc_data_locked(c)) return BMM_E_STATE;
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, dX) != hipSuccess || at.type != hipMemoryTypeDevice) {
         (void)hipGetLastError();
@@ -2120,6 +2204,7 @@ int bmm_chain_planes_filled(bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (c->started) return set_err(BMM_E_STATE, "chain already started");
     if (!c->bits || !c->dXb) return set_err(BMM_E_STATE, "no planes to declare filled (bmm_chain_planes first)");
+    if (pc_data_locked(c)) return BMM_E_STATE;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());  // whatever filled them ran on a stream of the caller's
     c->dX = nullptr;
@@ -3040,6 +3125,300 @@ int bmm_device_log_joint(int device, const int32_t* X, int64_t N, int P, int sam
     });
 }
 
+// ---- pairwise local-dependence check ----
+static int pc_refused(const bmm_chain* c) {
+    if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the pair check is not offered on a sharded chain: a shard holds a part of the rows");
+    if (c->fs_mask)
+        return set_err(BMM_E_UNSUPPORTED, "the pair check is written for the model in which every feature clusters: not offered on a "
+                       "chain with a feature mask (the pooled model's reference distribution is another one)");
+    if (!c->bits) return set_err(BMM_E_UNSUPPORTED, "the pair check reads the bit planes of X: not offered on a chain on the int32 layout");
+    return BMM_OK;
+}
+static int pc_armed(const bmm_chain* c) {
+    if (!c->pc_on) return set_err(BMM_E_STATE, "the pair check is not armed (bmm_chain_set_pair_check)");
+    return BMM_OK;
+}
+static int pc_seated(const bmm_chain* c) {
+    if (c->p.mode != MODE_COLLAPSED && c->sweep < 1)
+        return set_err(BMM_E_STATE, "no row has a label before the first sweep: this state has unseated rows and no pair check");
+    return BMM_OK;
+}
+// M, the features and the stride, before a device is touched
+static int pc_check_args(const int32_t* feat, int M, int stride, int P, int Kc) {
+    if (M < 2 || M > kPcMaxM) return set_err(BMM_E_ARG, "the pair check takes 2 to %d features, not %d", kPcMaxM, M);
+    if (!feat) return set_err(BMM_E_ARG, "null feature list");
+    if (stride < 1) return set_err(BMM_E_ARG, "stride must be >= 1");
+    for (int m = 0; m < M; ++m) {
+        if (feat[m] < 0 || feat[m] >= P) return set_err(BMM_E_ARG, "feat[%d] = %d is not a feature in 0..%d", m, (int)feat[m], P - 1);
+        for (int l = 0; l < m; ++l)
+            if (feat[l] == feat[m]) return set_err(BMM_E_ARG, "feat[%d] and feat[%d] are both feature %d: the chosen features must be distinct", l, m, (int)feat[m]);
+    }
+    if (Kc > kPcKA * 65535)  // label blocks ride on grid.z
+        return set_err(BMM_E_ARG, "the pair check is offered up to %d labels, not %d", kPcKA * 65535, Kc);
+    const size_t bytes = (size_t)Kc * (size_t)pc_npairs(M) * sizeof(uint32_t);
+    if (bytes > (size_t)BMM_PAIR_CHECK_MAX_COUNT_BYTES)
+        return set_err(BMM_E_ARG, "the counts of %d labels and %d features take %zu bytes, above the cap of %u: choose fewer features", Kc, M,
+                       bytes, (unsigned)BMM_PAIR_CHECK_MAX_COUNT_BYTES);
+    return BMM_OK;
+}
+static void pc_free(bmm_chain* c) {
+    void* bufs[] = {c->dPcFeat, c->dPcXt, c->dPcBlock};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    c->dPcFeat = nullptr; c->dPcXt = nullptr; c->dPcBlock = nullptr;
+    c->pc_on = false; c->pc_M = 0; c->pc_folded = 0;
+}
+static int pc_reset(bmm_chain* c) {
+    c->pc_folded = 0;
+    HIP_TRY(hipMemsetAsync(c->dPcBlock + c->pc_count_bytes, 0, c->pc_fold_bytes, c->stream));
+    return BMM_OK;
+}
+
+int bmm_chain_set_pair_check(bmm_chain* c, const int32_t* feat, int M, int stride) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        HIP_TRY(hipSetDevice(c->device));
+        if (!feat || M == 0) {  // disarm: the memory goes
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            pc_free(c);
+            return BMM_OK;
+        }
+        int rc = pc_refused(c);
+        if (rc == BMM_OK) rc = pc_check_args(feat, M, stride, c->p.P, c->p.K);
+        if (rc) return rc;
+        if (!c->have_data || !c->dXb) return set_err(BMM_E_STATE, "data matrix not set");
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        pc_free(c);
+        const PcPlan q = pc_plan(c->p.N, c->p.K, M);
+        rc = pred_room(q.bytes_slices + q.bytes_counts + 2 * q.bytes_fold, "the pair check (the column slices, M N / 8 bytes, the counts and the fold)");
+        if (rc) return rc;
+        const size_t np = (size_t)q.npairs, Kz = (size_t)c->p.K;
+        auto carve = [&](Carver& v) {
+            c->dPcCnt = v.take<uint32_t>(Kz * np);
+            c->dPcMarg = v.take<uint32_t>(Kz * (size_t)M);
+            c->dPcNk = v.take<uint32_t>(Kz);
+            c->pc_count_bytes = v.used;  // what a state's launch zeroes: the three above
+            c->dPcSumZ = v.take<double>(np);
+            c->dPcSumZ2 = v.take<double>(np);
+            c->dPcSumX2 = v.take<double>(np);
+            c->dPcSumDf = v.take<long long>(np);
+            c->dPcNz = v.take<int32_t>(np);
+            c->dPcN11 = v.take<uint32_t>(np);
+            c->pc_fold_bytes = v.used - c->pc_count_bytes;  // what a reset zeroes
+            c->dPcZ = v.take<double>(np);
+            c->dPcX2 = v.take<double>(np);
+            c->dPcDf = v.take<int32_t>(np);
+        };
+        Carver measure{nullptr};
+        carve(measure);
+        HIP_TRY(hipMalloc(&c->dPcBlock, measure.used));
+        Carver real{c->dPcBlock};
+        carve(real);
+        HIP_TRY(hipMemsetAsync(c->dPcBlock, 0, measure.used, c->stream));
+        HIP_TRY(hipMalloc(&c->dPcFeat, (size_t)M * sizeof(int32_t)));
+        HIP_TRY(hipMalloc(&c->dPcXt, q.bytes_slices));
+        HIP_TRY(hipMemcpyAsync(c->dPcFeat, feat, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        const int64_t nb = (q.C + 3) / 4;
+        hipLaunchKernelGGL(k_pc_slices, dim3((unsigned)(nb < 1024 ? nb : 1024), (unsigned)M), dim3(256), 0, c->stream,
+                           (const uint32_t*)c->dXb, c->p.N, (const int32_t*)c->dPcFeat, q.C, c->dPcXt);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));  // `feat` is the caller's
+        c->pc_M = M; c->pc_stride = stride; c->pc_C = q.C; c->pc_folded = 0;
+        c->pc_on = true;
+        return BMM_OK;
+    });
+}
+
+// the three state vectors, or the counts, of the last state scored: to the host, then the call waits
+static int pc_copy_out(bmm_chain* c, void* dst, const void* src, size_t bytes) {
+    if (!dst) return BMM_OK;
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    return BMM_OK;
+}
+static int pc_score_now(bmm_chain* c) {
+    int rc = pc_refused(c);
+    if (rc == BMM_OK) rc = pc_armed(c);
+    if (rc == BMM_OK) rc = pc_seated(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->started) { rc = chain_start(c); if (rc) return rc; }
+    return enqueue_pair_check(c, label_row(c, c->sweep), nullptr, false);
+}
+
+int bmm_chain_pair_check_state(bmm_chain* c, double* z_out, double* x2_out, int32_t* df_out) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        int rc = pc_score_now(c);
+        const size_t np = (size_t)pc_npairs(c->pc_M);
+        if (rc == BMM_OK) rc = pc_copy_out(c, z_out, c->dPcZ, np * sizeof(double));
+        if (rc == BMM_OK) rc = pc_copy_out(c, x2_out, c->dPcX2, np * sizeof(double));
+        if (rc == BMM_OK) rc = pc_copy_out(c, df_out, c->dPcDf, np * sizeof(int32_t));
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == BMM_OK && e != hipSuccess) return set_err(BMM_E_HIP, "the pair check failed: %s", hipGetErrorString(e));
+        return rc;
+    });
+}
+
+int bmm_chain_pair_counts(bmm_chain* c, uint32_t* counts, uint32_t* margins, uint32_t* rows) {
+    return guarded([&]() -> int {
+        if (!c || !counts) return set_err(BMM_E_ARG, "null argument");
+        int rc = pc_score_now(c);
+        const size_t np = (size_t)pc_npairs(c->pc_M), Kz = (size_t)c->p.K;
+        if (rc == BMM_OK) rc = pc_copy_out(c, counts, c->dPcCnt, Kz * np * sizeof(uint32_t));
+        if (rc == BMM_OK) rc = pc_copy_out(c, margins, c->dPcMarg, Kz * (size_t)c->pc_M * sizeof(uint32_t));
+        if (rc == BMM_OK) rc = pc_copy_out(c, rows, c->dPcNk, Kz * sizeof(uint32_t));
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == BMM_OK && e != hipSuccess) return set_err(BMM_E_HIP, "the pair counts failed: %s", hipGetErrorString(e));
+        return rc;
+    });
+}
+
+// n more sweeps, every pc_stride-th evaluated; the rows that are not stay NaN (all bits set)
+int bmm_chain_sweeps_pair_check(bmm_chain* c, int n, double* trace) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (n < 0) return set_err(BMM_E_ARG, "n must be >= 0");
+        int rc = pc_refused(c);
+        if (rc == BMM_OK) rc = pc_armed(c);
+        if (rc || n == 0) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t width = 2 * (size_t)pc_npairs(c->pc_M);
+        Recording rec;
+        if (trace) {
+            rc = rec.alloc((size_t)n * width * sizeof(double), "the pair check trace (n x 2 npairs doubles)");
+            if (rc) return rc;
+            HIP_TRY(hipMemsetAsync(rec.rows.p, 0xff, (size_t)n * width * sizeof(double), c->stream));
+        }
+        rec.begin(c, c->pc_rec, width * sizeof(double), c->sweep + 1, c->sweep + 1, true);
+        rc = bmm_chain_sweeps(c, n);
+        const hipError_t e = rec.end();
+        if (rc || !trace) return rc;
+        if (e != hipSuccess) return set_err(BMM_E_HIP, "the sweeps failed: %s", hipGetErrorString(e));
+        std::vector<double> host((size_t)n * width);
+        HIP_TRY(hipMemcpy(host.data(), rec.rows.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (int s = 0; s < n; ++s)
+            for (size_t m = 0; m < width; ++m) {
+                const double v = host[(size_t)s * width + m];
+                trace[(size_t)s + m * (size_t)n] = v != v ? std::nan("") : v;
+            }
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_get_pair_check(bmm_chain* c, bmm_pair_check_out* out) {
+    return guarded([&]() -> int {
+        if (!c || !out) return set_err(BMM_E_ARG, "null argument");
+        int rc = pc_armed(c);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t np = (size_t)pc_npairs(c->pc_M);
+        rc = pc_copy_out(c, out->sum_z, c->dPcSumZ, np * sizeof(double));
+        if (rc == BMM_OK) rc = pc_copy_out(c, out->sum_z2, c->dPcSumZ2, np * sizeof(double));
+        if (rc == BMM_OK) rc = pc_copy_out(c, out->sum_x2, c->dPcSumX2, np * sizeof(double));
+        if (rc == BMM_OK) rc = pc_copy_out(c, out->sum_df, c->dPcSumDf, np * sizeof(long long));
+        if (rc == BMM_OK) rc = pc_copy_out(c, out->n_z, c->dPcNz, np * sizeof(int32_t));
+        if (rc == BMM_OK) rc = pc_copy_out(c, out->n11, c->dPcN11, np * sizeof(uint32_t));
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == BMM_OK && e != hipSuccess) return set_err(BMM_E_HIP, "reading the pair check failed: %s", hipGetErrorString(e));
+        if (out->n_folded) *out->n_folded = c->pc_folded;
+        return rc;
+    });
+}
+
+int bmm_chain_pair_check_reset(bmm_chain* c) {
+    if (!c) return set_err(BMM_E_ARG, "null chain");
+    int rc = pc_armed(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return pc_reset(c);
+}
+
+// ... of a run: refused before a device is touched, armed for it, every stride-th kept sweep folded (sweep_end_folds)
+static int pc_run_check(const RunOptions& o, int P, int K) {
+    if (!o.pc.on) return BMM_OK;
+    return pc_check_args(o.pc.feat.empty() ? nullptr : o.pc.feat.data(), o.pc.o.M, o.pc.o.stride, P, K);
+}
+static int pc_run_attach(bmm_chain* c, const RunOptions& o, Recording& rec) {
+    if (!o.pc.on) return BMM_OK;
+    int rc = bmm_chain_set_pair_check(c, o.pc.feat.data(), o.pc.o.M, o.pc.o.stride);
+    const size_t width = 2 * (size_t)pc_npairs(o.pc.o.M);
+    if (rc == BMM_OK && (o.pc.o.z_rows || o.pc.o.x2_rows)) {
+        rc = rec.alloc((size_t)c->S * width * sizeof(double), "the pair check trace (S x 2 npairs doubles)");
+        if (rc == BMM_OK) HIP_TRY(hipMemsetAsync(rec.rows.p, 0xff, (size_t)c->S * width * sizeof(double), c->stream));
+    }
+    if (rc) return rc;
+    rec.begin(c, c->pc_rec, width * sizeof(double), c->burnin, run_first_fold(c), true);
+    return BMM_OK;
+}
+static int pc_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, int rc) {
+    if (!o.pc.on) return rc;
+    rc = rec.end_run(rc);
+    if (rc) return rc;
+    bmm_pair_check_out out = o.pc.o;
+    rc = bmm_chain_get_pair_check(c, &out);
+    if (rc || !rec.rows.p) return rc;
+    const size_t np = (size_t)pc_npairs(o.pc.o.M), S = (size_t)c->S;
+    std::vector<double> host(S * 2 * np);
+    HIP_TRY(hipMemcpy(host.data(), rec.rows.p, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t s = 0; s < S; ++s)
+        for (size_t m = 0; m < 2 * np; ++m) {
+            const double v = host[s * 2 * np + m];
+            double* const dst = m < np ? out.z_rows : out.x2_rows;
+            if (dst) dst[s + (m < np ? m : m - np) * S] = v != v ? std::nan("") : v;
+        }
+    return BMM_OK;
+}
+
+int bmm_pair_check_plan(int64_t N, int Kc, int M, bmm_pair_check_plan_out* out) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    if (N < 1 || Kc < 1) return set_err(BMM_E_ARG, "N and Kc must be >= 1");
+    if (M < 2 || M > kPcMaxM) return set_err(BMM_E_ARG, "the pair check takes 2 to %d features, not %d", kPcMaxM, M);
+    const PcPlan q = pc_plan(N, Kc, M);
+    out->bytes_slices = (int64_t)q.bytes_slices; out->bytes_counts = (int64_t)q.bytes_counts; out->bytes_fold = (int64_t)q.bytes_fold;
+    out->chunks = q.C; out->chunks_per_slice = q.cps; out->chunks_per_round = kPcRound;
+    out->tiles = q.tiles; out->row_slices = q.slices; out->label_blocks = q.kblocks; out->ka = q.ka; out->pairs_per_lane = kPcR; out->threads = kPcThreads;
+    return BMM_OK;
+}
+
+// Any stack of label rows over the same data, on a transient chain: X packed once, the slices cut once, then per state
+// the labels uploaded and the state counted and scored by the launches of a chain.
+int bmm_device_pair_check(int device, const int32_t* X, int64_t N, int P, int Kc, const int32_t* z, int S,
+                          const int32_t* feat, int M, uint32_t* counts, double* rows, const bmm_pair_check_out* out) {
+    return guarded([&]() -> int {
+        if (!X || !z) return set_err(BMM_E_ARG, "null argument");
+        if (S < 1) return set_err(BMM_E_ARG, "S must be >= 1");
+        int rc = check_common(N, P, Kc, 0.5, 0.5);
+        if (rc == BMM_OK) rc = pc_check_args(feat, M, 1, P, Kc);
+        if (rc == BMM_OK) rc = lj_check_labels(z, S, N, Kc, nullptr);
+        if (rc) return rc;
+        bmm_chain* c = nullptr;
+        rc = bmm_chain_create(&c, BMM_SAMPLER_COLLAPSED, N, P, Kc, 1.0, 0.5, 0.5, 1.0, 1.0, 0, 0, device);
+        if (rc) return rc;
+        struct Guard { bmm_chain* c; ~Guard() { bmm_chain_destroy(c); } } guard{c};
+        rc = bmm_chain_set_data_host(c, X);
+        if (rc == BMM_OK) rc = bmm_chain_set_pair_check(c, feat, M, 1);
+        if (rc) return rc;
+        const size_t np = (size_t)pc_npairs(M), Kz = (size_t)Kc;
+        std::vector<int32_t> row((size_t)N);
+        std::vector<double> vals(2 * np);
+        for (int s = 0; s < S; ++s) {
+            for (int64_t i = 0; i < N; ++i) row[(size_t)i] = z[(size_t)s + (size_t)i * (size_t)S] - 1;
+            HIP_TRY(hipMemcpyAsync(c->dZ[0], row.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            rc = enqueue_pair_check(c, c->dZ[0], nullptr, true);
+            if (rc == BMM_OK && counts) rc = pc_copy_out(c, counts + (size_t)s * Kz * np, c->dPcCnt, Kz * np * sizeof(uint32_t));
+            if (rc == BMM_OK && rows) rc = pc_copy_out(c, vals.data(), c->dPcZ, np * sizeof(double));
+            if (rc == BMM_OK && rows) rc = pc_copy_out(c, vals.data() + np, c->dPcX2, np * sizeof(double));
+            const hipError_t e = hipStreamSynchronize(c->stream);  // `row` is written again
+            if (rc) return rc;
+            if (e != hipSuccess) return set_err(BMM_E_HIP, "scoring state %d failed: %s", s, hipGetErrorString(e));
+            if (rows) for (size_t m = 0; m < 2 * np; ++m) rows[(size_t)s + m * (size_t)S] = vals[m];
+        }
+        if (!out) return BMM_OK;
+        bmm_pair_check_out o = *out;
+        return bmm_chain_get_pair_check(c, &o);
+    });
+}
+
 // ---- split-merge moves ----
 int bmm_chain_set_split_merge(bmm_chain* c, int moves_per_sweep, int scans) {
     return guarded([&]() -> int {
@@ -3740,17 +4119,18 @@ int ladder_sweeps(bmm_ladder* l, int n, int swap_every) {
     for (int t = 0; t < n; ++t) {
         const int j = c0->sweep + 1;
         const bool point = j % swap_every == 0;
-        c0->lp_defer = point && l->R > 1;
+        c0->fold_defer = point && l->R > 1;
         for (int r = 0; r < l->R && rc == BMM_OK; ++r) {
             rc = enqueue_sweep(l->ch[r], j);
             if (rc == BMM_OK) l->ch[r]->sweep++;
         }
-        const bool deferred = std::exchange(c0->lp_defer, false);
+        const bool deferred = std::exchange(c0->fold_defer, false);
         if (rc) return rc;
         const bool kept = l->lik_rows && j >= l->base;
         if (point) {
             rc = ladder_exchange(l, kept ? l->lik_rows + (size_t)(j - l->base) * l->R : nullptr);
             if (rc == BMM_OK && deferred && c0->lp_rec.folds(j) && c0->lp_on) rc = enqueue_log_joint(c0, j, c0->lp_rec.row<double>(j), true);
+            if (rc == BMM_OK && deferred && pc_folds(c0, j)) rc = enqueue_pair_check(c0, label_row(c0, j), c0->pc_rec.row<double>(j), true);
             if (rc) return rc;
         }
         if (l->walker_rows && j >= l->base)
@@ -5124,6 +5504,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
         if (rc == BMM_OK) rc = temper_run_check(opts, sampler);
         if (rc == BMM_OK) rc = st_run_check(opts, burnin, K);
         if (rc == BMM_OK) rc = ecr_run_check(opts, nsamples - burnin, N, K);
+        if (rc == BMM_OK) rc = pc_run_check(opts, P, K);
         if (rc) return rc;
         for (double& v : g_phase_ms) v = 0.0;
         PhaseClock clock;
@@ -5159,17 +5540,19 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             if (rc) return rc;
             clock.lap(0);
             // what the options record per kept sweep: each ends, and waits for the stream before its rows go, on every way out
-            Recording pred_rec, loo_rec, fs_rec, k_rec, lp_rec;
+            Recording pred_rec, loo_rec, fs_rec, k_rec, lp_rec, pc_rec;
             rc = pred_run_attach(c, opts, pred_rec);
             if (rc == BMM_OK) rc = loo_run_attach(c, opts, loo_rec);
             if (rc == BMM_OK) rc = sm_run_attach(c, opts);
             if (rc == BMM_OK) rc = fs_run_attach(c, opts, fs_rec);
             if (rc == BMM_OK) rc = alloc_run_attach(c, opts, k_rec);
             if (rc == BMM_OK) rc = lp_run_attach(c, opts, lp_rec);
+            if (rc == BMM_OK) rc = pc_run_attach(c, opts, pc_rec);
             if (rc == BMM_OK) rc = temper_run_attach(c, opts, alpha, batch, seed, temper);
             if (rc) return rc;
             rc = run_body(c, nsamples, io, opts);
             rc = temper_run_collect(c, opts, temper, rc);
+            rc = pc_run_collect(c, opts, pc_rec, rc);
             rc = lp_run_collect(c, opts, lp_rec, rc);
             rc = sm_run_collect(c, opts, rc);
             rc = alloc_run_collect(c, opts, k_rec, rc);
@@ -5544,6 +5927,18 @@ int bmm_set_logpost(const bmm_logpost_out* out) {
 int bmm_set_temper(const bmm_temper_out* out) {
     g_armed.temper.on = out != nullptr;
     if (out) g_armed.temper.o = *out;
+    return BMM_OK;
+}
+
+int bmm_set_pair_check(const bmm_pair_check_out* out) {
+    g_armed.pc.on = out != nullptr;
+    g_armed.pc.feat.clear();
+    if (out) {
+        g_armed.pc.o = *out;
+        // the features are copied; a list the run will refuse (pc_run_check) is kept only as far as it can be read
+        if (out->feat && out->M > 0 && out->M <= kPcMaxM) g_armed.pc.feat.assign(out->feat, out->feat + out->M);
+        g_armed.pc.o.feat = nullptr;
+    }
     return BMM_OK;
 }
 

@@ -4424,4 +4424,151 @@ __global__ __launch_bounds__(256) void k_log_joint_keep(const LjBest* __restrict
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) z_best[i] = z[i];
 }
 
+// ---- pairwise local-dependence check (include/bmm_mcmc.h "pairwise local-dependence check") ----
+// k_pc_slices, once per arming: the chosen features out of the bit planes into column slices Xt[m][C], C = ceil(N/64)
+// words of 64 rows; bit r of word c is x of row 64 c + r, bits past N are zero.  One ballot per feature and chunk.
+// k_pc_counts, once per evaluated state: a workgroup of kPcThreads lanes owns a kPcTile x kPcTile block of the upper
+// triangle of the M x M pairs (blockIdx.x, diagonal blocks included), a slice of the chunks (blockIdx.y) and KA labels
+// (blockIdx.z).  Per round of kPcRound chunks it stages the 2 kPcTile slices of the tile and the labels of those rows
+// in LDS.  Lane (q, lj) owns the R pairs (R q .. R q + R - 1, lj) of the tile.  Per chunk a wave reads the 64 labels,
+// one per lane, and forms mask_k = ballot(z == k) itself: a compare whose result is a scalar register pair, used as
+// it is by the R pairs of every lane -- no mask goes through LDS (the first form staged them there, and one LDS read
+// per pair, label and chunk held the kernel at a third of its rate) -- and each pair adds
+// popcount(slice_a & slice_b & mask_k) into its KA accumulators.  The margins come from the same pass, so the result
+// is a function of (X, z) alone: a pair slot on the diagonal of a diagonal tile holds slice & slice = the feature's
+// own ones (s_kd), and the first wave of the first tile adds popcount(mask_k) (n_k) in scalar registers.  Slots below
+// the diagonal are computed and dropped.  At the end every non-zero accumulator is added with one integer atomic; the
+// buffers are zeroed stream-ordered ahead of the launch.  Labels below 0 never reach the kernel (the callers refuse
+// such states); they would match no mask.
+// k_pc_stats: one lane per pair walks the labels in ascending order with bmm_spec.h's pc_label, writes the state's
+// values, the trace row if one is recorded, and adds to the fold.  No floating-point atomic anywhere.
+constexpr int kPcTile = 32, kPcRound = 16, kPcKA = 8, kPcR = 4, kPcThreads = kPcTile * kPcTile / kPcR;
+struct PcArgs {
+    const uint64_t* Xt;  // [M][C]
+    const int32_t* z;    // [N], 0-based
+    int64_t N, C;        // rows, chunks of 64 rows
+    int64_t cps;         // chunks per row slice (a multiple of kPcRound)
+    int M, Kc;
+    uint32_t *cnt, *marg, *nk;  // [Kc][npairs], [Kc][M], [Kc]
+};
+__global__ __launch_bounds__(256) void k_pc_slices(const uint32_t* __restrict__ Xb, int64_t N, const int32_t* __restrict__ feat,
+                                                   int64_t C, uint64_t* __restrict__ Xt) {
+    const int m = blockIdx.y, f = feat[m], lane = threadIdx.x & 63;
+    const uint32_t* plane = Xb + (size_t)(f >> 5) * (size_t)N;
+    for (int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); c < C; c += (int64_t)gridDim.x * 4) {
+        const int64_t row = c * 64 + lane;
+        const bool bit = row < N && ((plane[row] >> (f & 31)) & 1u);
+        const unsigned long long b = __ballot(bit);
+        if (lane == 0) Xt[(size_t)m * (size_t)C + (size_t)c] = b;
+    }
+}
+template <int KA, int R>
+__global__ __launch_bounds__(kPcThreads) void k_pc_counts(PcArgs a) {
+    static_assert(kPcTile * kPcTile == kPcThreads * R && kPcTile % R == 0, "a tile is R pairs per lane");
+    __shared__ unsigned long long sX[kPcRound][2 * kPcTile];
+    __shared__ int32_t sZ[kPcRound][64];
+    const int tid = threadIdx.x, q = tid >> 5, lj = tid & 31, lane = tid & 63;
+    const int T = (a.M + kPcTile - 1) / kPcTile;
+    int ti = 0, tj = (int)blockIdx.x;
+    while (tj >= T - ti) { tj -= T - ti; ++ti; }
+    tj += ti;
+    const int j = tj * kPcTile + lj, kbase = (int)blockIdx.z * KA;
+    const bool rows = blockIdx.x == 0 && tid < 64;  // uniform over a wave
+    const int64_t c_lo = (int64_t)blockIdx.y * a.cps, c_hi = c_lo + a.cps < a.C ? c_lo + a.cps : a.C;
+    uint32_t acc[R][KA], nrows[KA];
+#pragma unroll
+    for (int k = 0; k < KA; ++k) {
+        nrows[k] = 0u;
+#pragma unroll
+        for (int p = 0; p < R; ++p) acc[p][k] = 0u;
+    }
+    for (int64_t c0 = c_lo; c0 < c_hi; c0 += kPcRound) {
+        // kPcRound x 2 kPcTile slice words and kPcRound x 64 labels, kPcThreads lanes
+        for (int t = tid; t < kPcRound * 2 * kPcTile; t += kPcThreads) {
+            const int sf = t / kPcRound, sr = t % kPcRound;
+            const int sm = sf < kPcTile ? ti * kPcTile + sf : tj * kPcTile + (sf - kPcTile);
+            const int64_t c = c0 + sr;
+            sX[sr][sf] = (sm < a.M && c < c_hi) ? a.Xt[(size_t)sm * (size_t)a.C + (size_t)c] : 0ull;
+        }
+        for (int t = tid; t < kPcRound * 64; t += kPcThreads) {
+            const int64_t c = c0 + (t >> 6), row = c * 64 + (t & 63);
+            sZ[t >> 6][t & 63] = (c < c_hi && row < a.N) ? a.z[row] : -1;
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int r = 0; r < kPcRound; ++r) {
+            const int32_t zz = sZ[r][lane];
+            const unsigned long long b = sX[r][kPcTile + lj];
+            uint32_t wlo[R], whi[R];
+#pragma unroll
+            for (int p = 0; p < R; ++p) {
+                const unsigned long long w = sX[r][q * R + p] & b;
+                wlo[p] = (uint32_t)w; whi[p] = (uint32_t)(w >> 32);
+            }
+#pragma unroll
+            for (int k = 0; k < KA; ++k) {
+                const unsigned long long m = __ballot(zz == kbase + k);
+                const uint32_t mlo = (uint32_t)m, mhi = (uint32_t)(m >> 32);
+                if (rows) nrows[k] += (uint32_t)__popcll(m);
+                // two population counts that add into the accumulator as they count
+#pragma unroll
+                for (int p = 0; p < R; ++p) acc[p][k] = (uint32_t)__popc(whi[p] & mhi) + ((uint32_t)__popc(wlo[p] & mlo) + acc[p][k]);
+            }
+        }
+        __syncthreads();
+    }
+    const int64_t np = pc_npairs(a.M);
+#pragma unroll
+    for (int p = 0; p < R; ++p) {
+        const int i = ti * kPcTile + q * R + p;
+        uint32_t* dst = nullptr;
+        size_t stride = 0;
+        if (i < j && j < a.M) { dst = a.cnt + pc_pair_index(i, j, a.M); stride = (size_t)np; }
+        else if (i == j && i < a.M) { dst = a.marg + i; stride = (size_t)a.M; }
+        if (!dst) continue;
+#pragma unroll
+        for (int k = 0; k < KA; ++k)
+            if (kbase + k < a.Kc && acc[p][k]) atomicAdd(dst + (size_t)(kbase + k) * stride, acc[p][k]);
+    }
+    if (rows && tid == 0) {
+#pragma unroll
+        for (int k = 0; k < KA; ++k)
+            if (kbase + k < a.Kc && nrows[k]) atomicAdd(a.nk + (kbase + k), nrows[k]);
+    }
+}
+struct PcStatArgs {
+    const uint32_t *cnt, *marg, *nk;
+    int M, Kc;
+    double *z, *x2;       // [npairs]: the state's values
+    int32_t* df;
+    double* out_row;      // or null: [2 npairs], Z then X2, this sweep's row of a trace
+    double *sum_z, *sum_z2, *sum_x2;  // the fold
+    long long* sum_df;
+    int32_t* n_z;
+    uint32_t* n11;
+    int fold;
+};
+__global__ __launch_bounds__(256) void k_pc_stats(PcStatArgs a) {
+    const int64_t np = pc_npairs(a.M), q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= np) return;
+    int i = 0, j = 0;
+    pc_pair_ij(q, a.M, i, j);
+    PcSums t = pc_zero();
+    uint32_t both = 0u;
+    for (int k = 0; k < a.Kc; ++k) {
+        const uint32_t c = a.cnt[(size_t)k * np + q];
+        both += c;
+        pc_label(t, (int64_t)c, (int64_t)a.nk[k], (int64_t)a.marg[(size_t)k * a.M + i], (int64_t)a.marg[(size_t)k * a.M + j]);
+    }
+    const double z = pc_z(t);
+    a.z[q] = z; a.x2[q] = t.X2; a.df[q] = t.df;
+    if (a.out_row) { a.out_row[q] = z; a.out_row[np + q] = t.X2; }
+    if (a.fold) {
+        if (t.V > 0.0) { a.sum_z[q] = a.sum_z[q] + z; a.sum_z2[q] = a.sum_z2[q] + z * z; a.n_z[q] += 1; }
+        a.sum_x2[q] = a.sum_x2[q] + t.X2;
+        a.sum_df[q] += t.df;
+        a.n11[q] = both;
+    }
+}
+
 }  // namespace bmm

@@ -1112,6 +1112,91 @@ typedef struct bmm_temper_out {
 } bmm_temper_out;
 int bmm_set_temper(const bmm_temper_out* out);
 
+/* ---- pairwise local-dependence check ---------------------------------------------------------
+ * The model check of a Bernoulli mixture: within a cluster the features are independent.  Condition on the labels and
+ * on each label's margins (n_k rows, s_kd ones of feature d, s_ke ones of feature e): under the model -- for the
+ * collapsed samplers too, theta integrates out of a statement conditional on sufficient statistics -- the co-occurrence
+ *   c_k(d, e) = #{i : z_i = k, x_id = 1, x_ie = 1}    is Hypergeometric(n_k, s_kd, s_ke), so
+ *   E_k = s_kd s_ke / n_k,    V_k = s_kd s_ke (n_k - s_kd)(n_k - s_ke) / (n_k^2 (n_k - 1)).
+ * Two realised discrepancies per pair and state, each with a reference distribution known under the model:
+ *   Z  = sum_k (c_k - E_k) / sqrt(sum_k V_k)            approximately N(0, 1), signed (Cochran-Mantel-Haenszel)
+ *   X2 = sum_{k: V_k > 0} (c_k - E_k)^2 / V_k           approximately chi-square with df = #{k : V_k > 0}
+ * Z is blind to dependence whose sign differs between clusters; X2 is not.
+ * CHOSEN FEATURES AND PAIRS: feat[0 .. M), 2 <= M <= 128, distinct, any order, any P.  The pairs (i < j) of positions
+ * in feat are numbered as numpy.triu_indices(M, 1) numbers them; npairs = M (M - 1) / 2.
+ * COUNTS: c[k][pair], uint32, over the labels k = 0 .. Kc - 1 (Kc = K, or the DP's maxK).  The margins are counted in
+ * the same pass over the same rows, so everything here is a function of (X, z) alone.
+ * FIXED ARITHMETIC per pair (bmm_spec.h pc_label, pc_z; no fused operation): the labels in ascending order, labels with
+ * n_k < 2 skipped; in int64 num = c n - s_d s_e, pd = s_d (n - s_d), pe = s_e (n - s_e), nn = n n, each converted to
+ * binary64 once; a_k = num / n; v_k = (pd pe) / (nn (n - 1)); A += a_k; V += v_k; if v_k > 0: X2 += (a_k a_k) / v_k and
+ * df += 1.  Z = A / sqrt(V) when V > 0, else the pair has no Z for that state (NaN in a row, not folded).
+ * THE FOLD over the evaluated states, one add per pair per state, in sweep order: doubles sum_z, sum_z2 (of Z Z),
+ * sum_x2; int64 sum_df; int32 n_z (the states with V > 0); n_folded; n11[pair] = sum_k c_k of the last evaluated state.
+ * No floating-point atomic is used anywhere (integer atomics build the counts): one state gives the same bits twice.
+ * Everything is enqueued on the chain's stream behind the sweep's last kernel: no host wait, no copy; an armed chain
+ * that is not folding enqueues exactly what an unarmed one does, and the check reads state only, so it changes no chain.
+ * Arming costs M N / 8 bytes (the chosen features as column slices of 64 rows per word, X being constant over a
+ * chain's life) plus Kc (npairs + M + 1) uint32 and 6 npairs values of fold; disarming frees them.
+ * REFUSED: BMM_E_UNSUPPORTED for a chain with a feature mask (the pooled model's reference distribution is another
+ * one), a sharded chain, a chain on the int32 layout (no bit planes); BMM_E_STATE for a state with unseated rows (a DP,
+ * stick-breaking or full chain before its first sweep); BMM_E_ARG for M outside 2 .. 128, a feature outside 0 .. P - 1
+ * or repeated, stride < 1, counts above BMM_PAIR_CHECK_MAX_COUNT_BYTES, or more than 8 * 65535 labels.  While the check is
+ * armed bmm_chain_set_data_host / _device and bmm_chain_planes_filled answer BMM_E_STATE: the slices were cut from the
+ * data the chain held at arming; disarm, set the data, arm again. */
+#define BMM_PAIR_CHECK_MAX_M 128
+#define BMM_PAIR_CHECK_MAX_COUNT_BYTES (16u << 20) /* Kc * npairs * 4 */
+typedef struct bmm_pair_check_out {
+    const int32_t* feat; /* bmm_set_pair_check: the M chosen features, 0-based (bmm_chain_get_pair_check ignores it) */
+    int M;
+    int stride;          /* bmm_set_pair_check: every stride-th kept sweep is evaluated, from the first kept row on */
+    double* z_rows;      /* a run: S x npairs column-major, or NULL; NaN where not evaluated or V = 0 */
+    double* x2_rows;     /* a run: S x npairs column-major, or NULL; NaN where not evaluated */
+    double* sum_z;       /* npairs each, any may be NULL */
+    double* sum_z2;
+    double* sum_x2;
+    int64_t* sum_df;
+    int32_t* n_z;
+    uint32_t* n11;
+    int* n_folded;
+} bmm_pair_check_out;
+/* arm (feat, M, stride as above; arming an armed chain empties the fold and takes the new features) or, with feat NULL
+ * or M = 0, disarm and free */
+int bmm_chain_set_pair_check(bmm_chain* c, const int32_t* feat, int M, int stride);
+/* the current state, once: no sweep, the fold untouched; npairs values each, any may be NULL.  Waits. */
+int bmm_chain_pair_check_state(bmm_chain* c, double* z_out, double* x2_out, int32_t* df_out);
+/* n more sweeps of an armed chain, sweeps 0, stride, 2 stride, ... of them evaluated and folded; trace n x (2 npairs)
+ * column-major, Z then X2, NaN where not evaluated (then the call waits) or NULL (then it does not wait) */
+int bmm_chain_sweeps_pair_check(bmm_chain* c, int n, double* trace);
+/* reads the fold (the sums, n_folded); z_rows, x2_rows, feat, M, stride are ignored.  Waits. */
+int bmm_chain_get_pair_check(bmm_chain* c, bmm_pair_check_out* out);
+int bmm_chain_pair_check_reset(bmm_chain* c);
+/* the Kc x npairs uint32 of the current state, counts[k * npairs + pair]; margins (Kc x M, or NULL) and rows (Kc, or
+ * NULL) are the s_kd and n_k counted in the same pass.  Waits. */
+int bmm_chain_pair_counts(bmm_chain* c, uint32_t* counts, uint32_t* margins, uint32_t* rows);
+/* For a run: armed per calling thread for the NEXT single-chain *_run* call of that thread and disarmed when that call
+ * returns, as bmm_set_logpost; NULL disarms.  The struct and feat are copied.  Only kept sweeps are folded, every
+ * stride-th of them counted from kept row 0 (without burn-in row 0 is the starting state and stays NaN).  Under
+ * bmm_set_temper the check sees rung 0 after the exchange point.  bmm_multi_run does not take it and disarms it. */
+int bmm_set_pair_check(const bmm_pair_check_out* out);
+/* Any stack of label rows over the same data on a transient chain, as bmm_device_log_joint: z S x N int32 column-major,
+ * 1-based in 1 .. Kc; counts: S x Kc x npairs uint32 (state s at counts + s Kc npairs) or NULL; rows: S x (2 npairs)
+ * column-major, Z then X2, or NULL; out: the fold over the S states in order (its z_rows, x2_rows, feat, M, stride
+ * are ignored), or NULL.  A run's own z gives the run's rows bit for bit. */
+int bmm_device_pair_check(int device, const int32_t* X, int64_t N, int P, int Kc, const int32_t* z, int S,
+                          const int32_t* feat, int M, uint32_t* counts, double* rows, const bmm_pair_check_out* out);
+/* pure bookkeeping: the bytes the check needs on the device and the grid of k_pc_counts */
+typedef struct bmm_pair_check_plan_out {
+    int64_t bytes_slices, bytes_counts, bytes_fold;
+    int64_t chunks;            /* ceil(N / 64) */
+    int64_t chunks_per_slice;  /* a multiple of chunks_per_round */
+    int chunks_per_round;      /* chunks a workgroup stages at a time, one per wave */
+    int tiles, row_slices, label_blocks;  /* the grid: x, y, z */
+    int ka;                    /* labels per workgroup: accumulators per pair */
+    int pairs_per_lane;        /* pairs of the tile a lane owns */
+    int threads;
+} bmm_pair_check_plan_out;
+int bmm_pair_check_plan(int64_t N, int Kc, int M, bmm_pair_check_plan_out* out);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
