@@ -1128,6 +1128,45 @@ def _make_features(select_features, rho, P, S, chains, beta, gamma, dp, newdata,
     return _Features(rho, P, S)
 
 
+# ---------------------------------------------------------------- missing=: NA cells imputed on the device
+class _MissingOut(_C.Structure):  # bmm_missing_out
+    _fields_ = [("mean_rb", _C.c_void_p), ("mean_draw", _C.c_void_p), ("last", _C.c_void_p), ("n_folded", _C.POINTER(_C.c_int64))]
+
+
+class _Missing:
+    """missing= of the four samplers: the sorted cell list, armed for exactly one run"""
+
+    def __init__(self, rows, cols, N, P):
+        self.rows, self.cols, self.size = rows, cols, N * P
+        n = rows.size
+        self.mean, self.mean_draw = _np.full(n, _np.nan), _np.full(n, _np.nan)
+        self.last = _np.zeros(n, dtype=_np.uint8)
+        self.n = _C.c_int64(0)
+        self.s = _MissingOut(_capi.vp(self.mean), _capi.vp(self.mean_draw), _capi.vp(self.last), _C.pointer(self.n))
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_missing(_capi.vp(self.rows), _capi.vp(self.cols), _C.c_int64(self.rows.size), _C.byref(self.s)))
+
+    def result(self):
+        return {"rows": self.rows, "cols": self.cols, "n_cells": int(self.rows.size),
+                "fraction": self.rows.size / self.size if self.size else 0.0, "mean": self.mean, "mean_draw": self.mean_draw,
+                "last": self.last, "n_folded": int(self.n.value)}
+
+
+def _take_missing(data, missing):
+    """(cleaned data, the cells or None): what the wrappers do with missing= before the matrix is looked at"""
+    if missing is None:
+        return data, None
+    rows, cols, data = _capi.missing_cells(data, missing)
+    return data, (rows, cols)
+
+
+def _with_missing(out, mi):
+    if mi is not None:
+        out["missing"] = mi.result()
+    return out
+
+
 # ---------------------------------------------------------------- init=: the k-modes++ start on the device
 INIT_KINDS = {"kmodes": 1}
 INIT_ITERS = 10  # a cap, not a tuned value: the refinement stops at the first round that changes no label
@@ -1172,7 +1211,8 @@ class _Init:
         return info.as_dict()
 
 
-def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None, lp=None, tp=None, pc=None):
+def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None, lp=None, tp=None, pc=None,
+         mi=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
@@ -1192,6 +1232,8 @@ def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=
         tp.arm()
     if pc is not None:
         pc.arm()
+    if mi is not None:
+        mi.arm()
     if init is not None:  # last, just ahead of the call: a run of another sampler refuses an armed start
         init.arm()
     if pr is None:
@@ -1351,7 +1393,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                     responsibilities=False, partition=None, partition_stride=1, similarity_of=None, loo=False,
                     select_features=False, rho=0.5, init="random", init_iters=INIT_ITERS, ecr_pivot="iterative",
                     ecr_max_iter=50, logpost=False, temper=None, swap_every=1, temper_hottest=0.1, pair_check=None,
-                    pair_check_stride=1, pair_check_trace=False):
+                    pair_check_stride=1, pair_check_trace=False, missing=None):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -1430,9 +1472,23 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     where a sweep was not evaluated.  |z_mean| well above 4, or x2_mean far above df_mean, names a pair of features
     that stays associated inside the clusters.  It reads state only and changes no chain.  True needs P <= 128; per
     chain (chains=1); not with select_features=.
+    `missing=`: None (an NA cell is an error), "na" (the NA_INTEGER cells of an integer matrix, the NaN cells of a
+    floating-point one) or a boolean N x P mask.  The named cells are taken as missing at random and imputed on the device
+    by data augmentation (include/bmm_mcmc.h "missing data"): they are redrawn exactly behind every
+    sweep, the sweep itself runs on the completed matrix, and the labels are draws from the posterior given the observed
+    cells alone.  The result gains `missing = {"rows", "cols", "n_cells", "fraction", "mean", "mean_draw", "last",
+    "n_folded"}`: the cells sorted by (row, column), the posterior probability that each is a 1 ("mean", the mean over
+    the kept sweeps of the rate it was drawn from; "mean_draw" is the share of ones drawn), the cells after the last
+    sweep and the sweeps folded.  The `theta` row of a sweep belongs to that sweep's labels and the cells as they stood
+    before its imputation step; `logpost=` gives the joint of the completed state.  With many cells missing the chain
+    mixes more slowly than one that integrates them out: run longer.  Works with partition=, relabel="ecr", newdata=
+    (complete rows) and logpost=; not with chains > 1, loo=, select_features=, temper=, pair_check=, init="kmodes",
+    relabel=True (or split_merge= on gibbs_dp).
     """
+    data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
     N, P = X.shape
+    mi = None if cells is None else _Missing(cells[0], cells[1], N, P)
     nsamples, K = int(nsamples), int(K)
     ik = _init_kind(init, init_iters)
     if ik is not None and initial_K is not None:
@@ -1457,8 +1513,10 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             out["features"] = fs.result()
         if ini is not None:
             out["init"] = ini.result()
-        return _with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc)
+        return _with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc), mi)
     if chains > 1:
+        if mi is not None:
+            mi.arm()  # (the run of several chains answers it)
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
         if ini is not None:
@@ -1499,7 +1557,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
                 _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini, lp=lp, tp=tp, pc=pc)
+            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini, lp=lp, tp=tp, pc=pc, mi=mi)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
@@ -1511,7 +1569,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
             _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp, pc=pc)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1524,7 +1582,8 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
              stephens=None, newdata=None, predictive_trace=False, responsibilities=False, partition=None,
              partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None,
              select_features=False, rho=0.5, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
-             temper=None, swap_every=1, temper_hottest=0.1, pair_check=None, pair_check_stride=1, pair_check_trace=False):
+             temper=None, swap_every=1, temper_hottest=0.1, pair_check=None, pair_check_stride=1, pair_check_trace=False,
+             missing=None):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
@@ -1535,10 +1594,12 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     DP run seats its rows in its first sweep; Chain.init_labels re-seats a resident DP chain).  `logpost`,
     `ecr_pivot="map"`, `pair_check`, `pair_check_stride`, `pair_check_trace`: as gibbs_collapsed.  `temper`,
     `swap_every`, `temper_hottest`: as gibbs_collapsed (the helper chains seat their own rows in their first sweep; the
-    new-cluster option carries the power on its likelihood part)."""
+    new-cluster option carries the power on its likelihood part).  `missing`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
+    data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
     N, P = X.shape
+    mi = None if cells is None else _Missing(cells[0], cells[1], N, P)
     nsamples, maxK = int(nsamples), int(maxK)
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
@@ -1559,8 +1620,10 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             out["split_merge"] = sm.result()
         if fs is not None:
             out["features"] = fs.result()
-        return _with_pair_check(_with_logpost(out, lp, ecr_map, maxK, device), pc)
+        return _with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, maxK, device), pc), mi)
     if int(chains) > 1:
+        if mi is not None:
+            mi.arm()  # (the run of several chains answers it)
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
         dev0 = device if devices is None else int(devices[0])
@@ -1582,7 +1645,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                 _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
                 _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs, lp=lp, tp=tp, pc=pc)
+            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs, lp=lp, tp=tp, pc=pc, mi=mi)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, maxK, P, S)
@@ -1595,7 +1658,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp, pc=pc)
+        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1607,9 +1670,11 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
               device, initial_pi, initial_theta, chains, devices, stephens, debug=False, newdata=None,
               predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None,
               loo=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1,
-              pair_check_trace=False):
+              pair_check_trace=False, missing=None):
+    data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
     N, P = X.shape
+    mi = None if cells is None else _Missing(cells[0], cells[1], N, P)
     nsamples, K = int(nsamples), int(K)
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
@@ -1623,7 +1688,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
     base = fn[len("bmm_"):-len("_run_probs")]
 
     def done(out):
-        return _with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc)
+        return _with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc), mi)
 
     def start(sd, pi, th):
         rng = _np.random.default_rng(sd)
@@ -1641,6 +1706,8 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
     S = nsamples - burnin
     W = _clamp_burnrelabel(burnrelabel, burnin) if clamp else int(burnrelabel)  # R/utils.R:97-101 has no clamp
     if chains > 1:
+        if mi is not None:
+            mi.arm()  # (the run of several chains answers it)
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
         st = [start(seed + c, initial_pi[c] if initial_pi is not None else None,
@@ -1665,7 +1732,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
                 _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
                 _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run(base, args, pr, rel=dr, part=pt, loo=lo, lp=lp, pc=pc)
+            rc = _run(base, args, pr, rel=dr, part=pt, loo=lo, lp=lp, pc=pc, mi=mi)
         return done(_with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
@@ -1678,7 +1745,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
             _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec, lp=lp, pc=pc)
+        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec, lp=lp, pc=pc, mi=mi)
     out = {"pi": pi, "alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1691,34 +1758,35 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
                         initial_theta=None, chains=1, devices=None, stephens=None, newdata=None,
                         predictive_trace=False, responsibilities=False, partition=None, partition_stride=1,
                         similarity_of=None, loo=False, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
-                        pair_check=None, pair_check_stride=1, pair_check_trace=False):
+                        pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
     src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
     "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`: as gibbs_collapsed; log_prior is
     the stick-breaking prior with the sticks integrated out, which depends on the order of the labels.  `pair_check`,
-    `pair_check_stride`, `pair_check_trace`: as gibbs_collapsed."""
+    `pair_check_stride`, `pair_check_trace`: as gibbs_collapsed.  `missing`: as gibbs_collapsed; the cells are drawn from
+    the theta the sweep has just drawn."""
     _init_kind(init, 0, allowed=False)
     return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
                      burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace)
+                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
                burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None, initial_theta=None, chains=1,
                devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False,
                partition=None, partition_stride=1, similarity_of=None, loo=False, init="random", ecr_pivot="iterative",
-               ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1, pair_check_trace=False):
+               ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None):
     """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
     "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`, `pair_check`,
-    `pair_check_stride`, `pair_check_trace`: as gibbs_collapsed."""
+    `pair_check_stride`, `pair_check_trace`, `missing`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
     return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
                      relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace)
+                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing)
 
 
 class Chain:
@@ -2195,6 +2263,40 @@ class Chain:
 
     def feature_reset(self):
         _capi.check(_capi.lib().bmm_chain_feature_reset(self._h))
+
+    def set_missing(self, rows=None, cols=None, mask=None):
+        """declare the missing cells (bmm_chain_set_missing): `mask`, a boolean N x P matrix, or `rows` / `cols`, 0-based
+        and strictly ascending in (row, column); nothing, or empty lists, withdraws the declaration.  Returns the
+        number of cells."""
+        if mask is not None:
+            rows, cols = _np.nonzero(_np.asarray(mask, dtype=bool))
+        rows = _np.ascontiguousarray(() if rows is None else rows, dtype=_np.int64)
+        cols = _np.ascontiguousarray(() if cols is None else cols, dtype=_np.int32)
+        if rows.shape != cols.shape or rows.ndim != 1:
+            raise ValueError("rows and cols must be two lists of one length")
+        _capi.check(_capi.lib().bmm_chain_set_missing(self._h, _capi.vp(rows), _capi.vp(cols), _C.c_int64(rows.size)))
+        self._na_cells = int(rows.size)
+        return self._na_cells
+
+    def impute_step(self):
+        """one imputation step now, under the index of the last sweep (bmm_chain_impute_step)"""
+        _capi.check(_capi.lib().bmm_chain_impute_step(self._h))
+
+    def missing_state(self):
+        """the declared cells' current values, uint8, in the order declared"""
+        bits = _np.zeros(getattr(self, "_na_cells", 0), dtype=_np.uint8)
+        _capi.check(_capi.lib().bmm_chain_get_missing_state(self._h, _capi.vp(bits)))
+        return bits
+
+    def missing_summary(self):
+        """{"mean", "mean_draw" (n_cells,), "n_folded"} over the steps folded so far"""
+        n = getattr(self, "_na_cells", 0)
+        rb, dr, nf = _np.zeros(n), _np.zeros(n), _C.c_int64(0)
+        _capi.check(_capi.lib().bmm_chain_get_missing_summary(self._h, _capi.vp(rb), _capi.vp(dr), _C.byref(nf)))
+        return {"mean": rb, "mean_draw": dr, "n_folded": int(nf.value)}
+
+    def missing_reset(self):
+        _capi.check(_capi.lib().bmm_chain_missing_reset(self._h))
 
     def profile(self, every=1):
         """Time the resample launches of every `every`-th sweep with HIP events (0/False: off)."""

@@ -48,6 +48,8 @@ SYMBOLS = [
     "bmm_ladder_exchange_step", "bmm_ladder_stats", "bmm_set_temper",
     "bmm_chain_set_pair_check", "bmm_chain_pair_check_state", "bmm_chain_sweeps_pair_check", "bmm_chain_get_pair_check",
     "bmm_chain_pair_check_reset", "bmm_chain_pair_counts", "bmm_set_pair_check", "bmm_device_pair_check", "bmm_pair_check_plan",
+    "bmm_chain_set_missing", "bmm_chain_impute_step", "bmm_chain_get_missing_state", "bmm_chain_get_missing_summary",
+    "bmm_chain_missing_reset", "bmm_set_missing",
 ]
 
 
@@ -86,6 +88,13 @@ def load(path):
         L.bmm_chain_get_pair_check.argtypes = [C.c_void_p, C.c_void_p]
         L.bmm_chain_pair_check_reset.argtypes = [C.c_void_p]
         L.bmm_chain_pair_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "bmm_chain_set_missing"):  # (an older build loaded for a comparison has no missing data)
+        L.bmm_chain_set_missing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        L.bmm_chain_impute_step.argtypes = [C.c_void_p]
+        L.bmm_chain_get_missing_state.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmm_chain_get_missing_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bmm_chain_missing_reset.argtypes = [C.c_void_p]
+        L.bmm_set_missing.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     if hasattr(L, "bmm_ladder_create"):  # (an older build loaded for a comparison has no ladder)
         L.bmm_ladder_destroy.restype = None
         L.bmm_ladder_destroy.argtypes = [C.c_void_p]
@@ -133,3 +142,30 @@ def as_x(data):
     if X.dtype != np.int32 and X.size and (X.min() < 0 or X.max() > 1):
         raise ValueError("data must be binary (0/1)")  # before a narrowing cast could hide it
     return np.asfortranarray(X, dtype=np.int32)
+
+
+def missing_cells(data, missing):
+    """The cells `missing=` names and the matrix without them: (rows int64, cols int32, cleaned data), the cells sorted
+    by (row, column).  "na": the NA_INTEGER cells of an integer matrix, the NaN cells of a floating-point one; or a
+    boolean N x P mask.  The named cells are zeroed so that the matrix passes as_x, which goes on refusing NA."""
+    X = np.asarray(data)
+    if X.ndim != 2:
+        raise ValueError("data must be a matrix with observations in rows")
+    if isinstance(missing, str):
+        if missing != "na":
+            raise ValueError('missing must be None, "na" or a boolean N x P mask')
+        if X.dtype.kind == "f":
+            mask = np.isnan(X)
+        elif X.dtype.kind == "i" and X.dtype.itemsize >= 4:
+            mask = X == NA_INTEGER
+        else:
+            mask = np.zeros(X.shape, dtype=bool)
+    else:
+        mask = np.asarray(missing)
+        if mask.dtype != np.bool_ or mask.shape != X.shape:
+            raise ValueError('missing must be None, "na" or a boolean N x P mask')
+    rows, cols = np.nonzero(mask)  # row-major order: sorted by (row, column)
+    if rows.size:
+        X = X.copy()
+        X[mask] = 0
+    return np.ascontiguousarray(rows, dtype=np.int64), np.ascontiguousarray(cols, dtype=np.int32), X

@@ -61,6 +61,9 @@ enum : uint32_t {
     kStreamAllocPeA = 12,  // its p_E ~ Beta(e, e): first gamma; c0 = move index, c2 = sweep
     kStreamAllocPeB = 13,  // ... second gamma
     kStreamTemper = 14,    // the uniform of a replica exchange: c0 = pair index r, c1 = block counter, c2 = exchange point t (temper_uniform)
+    kStreamMissing = 15,   // the uniform of missing cell (i, j) behind sweep t: c0, c1 = the low and high word of i * P + j, c2 = t (na_uniform; t = 0: the starting fill)
+    kStreamMissingA = 16,  // phi_kj ~ Beta of the imputation step of a counting chain: first gamma; c0 = k*P+j, c1 = block counter, c2 = sweep (na_phi)
+    kStreamMissingB = 17,  // ... second gamma
 };
 
 // ---------------------------------------------------------------- bit helpers
@@ -195,6 +198,15 @@ BMM_HD double fs_uniform(uint64_t seed, uint32_t d, uint32_t sweep) {
 BMM_HD double init_uniform(uint64_t seed, uint32_t j) {
     Stream st = make_stream(seed, j, 0, kStreamInit);
     const U4 r = st.next();
+    return u01(r.x, r.y);
+}
+
+// The uniform that decides missing cell `cell` = i * P + j behind sweep `sweep` (include/bmm_mcmc.h "missing data"; sweep
+// 0 is the starting fill): one Philox block under a stream id of its own, keyed by the cell's identity and the sweep and
+// by nothing else -- not the grid, not the order of the cell list.  Counter word 1 carries the high word of the cell
+// where the counted streams carry their block counter; the stream id is in no other use, so no (key, counter) pair is shared.
+BMM_HD double na_uniform(uint64_t seed, uint64_t cell, uint32_t sweep) {
+    const U4 r = philox4x32_10((uint32_t)cell, (uint32_t)(cell >> 32), sweep, kStreamMissing, (uint32_t)seed, (uint32_t)(seed >> 32));
     return u01(r.x, r.y);
 }
 // the valid bits of word w of a row of P features (every word but the last one is full)
@@ -563,6 +575,15 @@ BMM_HD double rgamma_(double shape, Stream& st) {
 BMM_HD double rbeta_(double p, double q, Stream& sa, Stream& sb) {
     const double x = rgamma_(p, sa), y = rgamma_(q, sb);
     return div_(x, x + y);
+}
+
+// The auxiliary rate of label k and feature j in the imputation step of a counting chain behind sweep `sweep`
+// (include/bmm_mcmc.h "missing data"): phi ~ Beta(beta + s, gamma + n - s) from the observed-only counts -- n of the
+// label's rows have the feature observed, s of them hold a 1; n = 0 is the prior.  kj = k * P + j.
+BMM_HD double na_phi(uint64_t seed, double beta, double gamma, uint32_t kj, uint32_t sweep, int64_t s, int64_t n) {
+    Stream sa = make_stream(seed, kj, sweep, kStreamMissingA);
+    Stream sb = make_stream(seed, kj, sweep, kStreamMissingB);
+    return rbeta_(beta + (double)s, (gamma + (double)n) - (double)s, sa, sb);
 }
 
 // The draws of eject / absorb move number `move` ahead of sweep `sweep` (include/bmm_mcmc.h "allocation sampler"), a

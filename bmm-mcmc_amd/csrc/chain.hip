@@ -648,6 +648,20 @@ struct bmm_chain {
     int32_t *dPcDf = nullptr, *dPcNz = nullptr;
     int pc_folded = 0;  // states folded so far
     SweepTrace pc_rec;
+    // missing data: na_on: the imputation step behind every sweep end.  One block holds the site
+    // list (row, word, mask, first cell), the census [2][K P], the rates [K P] of a counting chain and the cells' two
+    // folds; na_rec: the steps that are folded (every one of an armed chain, the kept ones of a run).
+    bool na_on = false, na_lds = false;
+    int64_t na_cells = 0, na_sites = 0, na_folded = 0;
+    int na_grid = 0;
+    char* dNaBlock = nullptr;
+    int64_t *dNaRow = nullptr, *dNaFirst = nullptr;
+    int32_t *dNaWord = nullptr, *dNaCnt = nullptr;
+    uint32_t *dNaMask = nullptr, *dNaOnes = nullptr;
+    double *dNaPhi = nullptr, *dNaSum = nullptr;
+    std::vector<int64_t> na_rows;  // the declared cells, as given
+    std::vector<int32_t> na_cols;
+    SweepTrace na_rec;
     // parallel tempering: temper_on: the table builds are k_temper_tables at inverse temperature
     // temper_b, and the kernel choice leaves out the forms that build their own tables and the packed one; ladder: the
     // replica ladder a run drives this chain through as its rung 0 (not owned)
@@ -723,7 +737,7 @@ int run_rows_out(const bmm_chain* c, const double* dtrace, int64_t width, double
 }
 
 // What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_loo_summary,
-// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost, bmm_set_temper, bmm_set_pair_check; bmm_alloc_run fills `alloc` for its own run), and what a
+// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost, bmm_set_temper, bmm_set_pair_check, bmm_set_missing; bmm_alloc_run fills `alloc` for its own run), and what a
 // *_run_predict / *_run_relabel / *_run_probs entry point was handed.
 struct RunOptions {
     struct { bool on = false; bmm_partition_out o{}; } partition;
@@ -735,6 +749,7 @@ struct RunOptions {
     struct { bool on = false; bmm_logpost_out o{}; } logpost;
     struct { bool on = false; bmm_temper_out o{}; } temper;
     struct { bool on = false; bmm_pair_check_out o{}; std::vector<int32_t> feat; } pc;
+    struct { bool on = false; const int64_t* rows = nullptr; const int32_t* cols = nullptr; int64_t n = 0; bmm_missing_out o{}; } na;
     struct { bool on = false; const double* log_prior_k = nullptr; int K0 = 0, moves = 0; double eject_a = 1.0; int32_t* k_out = nullptr; int64_t* moves_out = nullptr; } alloc;
     const bmm_relabel_hooks* hooks = nullptr;  // *_run_probs
     const bmm_relabel_out* rel = nullptr;      // *_run_relabel
@@ -1365,6 +1380,9 @@ int enqueue_pair_check(bmm_chain* c, const int32_t* z, double* row, bool fold) {
 // X is cut into the check's column slices once, when it is armed: new data under an armed check would leave slices of
 // the old matrix behind, so the data entry points refuse until the check is disarmed
 int pc_data_locked(const bmm_chain* c) {
+    if (c->na_on)
+        return set_err(BMM_E_STATE, "missing cells are declared on the data the chain holds: withdraw them (bmm_chain_set_missing with "
+                       "no cells) before new data is set, and declare them again afterwards");
     if (c->pc_on)
         return set_err(BMM_E_STATE, "the pair check is armed on the data the chain holds: disarm it (bmm_chain_set_pair_check with "
                        "no features) before new data is set, and arm it again afterwards");
@@ -1390,6 +1408,7 @@ int fs_mask_refuses(const char* what) {
     return set_err(BMM_E_UNSUPPORTED, "%s is written for the model in which every feature clusters: not offered on a chain "
                    "with a feature mask (feature selection)", what);
 }
+int na_refuses(const char* what);  // (... a chain with declared missing cells: DESIGN.md section 23)
 
 // ---- split-merge moves ----
 int temper_refuses(const char* what) {
@@ -1398,6 +1417,7 @@ int temper_refuses(const char* what) {
 }
 int sm_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_STATE, "split-merge moves are not offered on a sharded chain");
+    if (c->na_on) return na_refuses("a split-merge move");
     if (c->temper_on) return temper_refuses("the split-merge ratio");
     if (c->p.mode != MODE_DP)
         return set_err(BMM_E_UNSUPPORTED, "split-merge moves are offered for the DP sampler only (the finite sampler gives an "
@@ -1501,10 +1521,48 @@ int enqueue_fs_gamma(bmm_chain* c, int j) {
     return BMM_OK;
 }
 
+// ---- missing data: the imputation step ----
+NaArgs na_args(bmm_chain* c, const int32_t* z, uint32_t sweep, bool fold) {
+    NaArgs a{};
+    a.row = c->dNaRow; a.word = c->dNaWord; a.mask = c->dNaMask; a.first = c->dNaFirst; a.n_sites = c->na_sites;
+    a.Xb = c->dXb; a.z = z; a.S = c->dS; a.cnt = c->dNaCnt; a.Nk = c->dNk; a.dNk = c->dDNk; a.dS = c->dDS;
+    a.phi = explicit_params(c->p.mode) ? c->dTheta : c->dNaPhi;
+    a.sum_phi = c->dNaSum; a.ones = c->dNaOnes; a.sweep = sweep; a.fold = fold ? 1 : 0;
+    return a;
+}
+// The step behind sweep j, stream-ordered behind everything the sweep enqueued: the census and the auxiliary rates of
+// a counting chain (an explicit chain's rates are its theta), then the draw.  The deltas go into the folded S.
+int enqueue_na_step(bmm_chain* c, int j) {
+    const ChainParams& p = c->p;
+    const bool fold = c->na_rec.folds(j);
+    const NaArgs a = na_args(c, label_row(c, j), (uint32_t)j, fold);
+    const size_t KP = (size_t)p.K * p.P;
+    const dim3 grid((unsigned)c->na_grid), wg(kNaThreads);
+    if (!explicit_params(p.mode)) {
+        HIP_TRY(hipMemsetAsync(c->dNaCnt, 0, 2 * KP * sizeof(int32_t), c->stream));
+        if (c->na_lds) hipLaunchKernelGGL(k_na_census<true>, grid, wg, 2 * KP * sizeof(int32_t), c->stream, p, a);
+        else hipLaunchKernelGGL(k_na_census<false>, grid, wg, 0, c->stream, p, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_na_phi, dim3((unsigned)((KP + kNaThreads - 1) / kNaThreads)), wg, 0, c->stream, p, a);
+        HIP_TRY(hipGetLastError());
+    }
+    if (c->na_lds) hipLaunchKernelGGL(k_na_draw<true>, grid, wg, KP * (sizeof(double) + sizeof(int32_t)), c->stream, p, a);
+    else hipLaunchKernelGGL(k_na_draw<false>, grid, wg, 0, c->stream, p, a);
+    HIP_TRY(hipGetLastError());
+    if (fold) c->na_folded++;
+    return BMM_OK;
+}
+// what the options that read the data matrix as observed answer a chain with declared missing cells
+int na_refuses(const char* what) {
+    return set_err(BMM_E_UNSUPPORTED, "%s is not offered on a chain with missing cells (bmm_chain_set_missing): it would read "
+                   "the completed matrix as if it were observed", what);
+}
+
 // ---- k-modes++ initial allocation ----
 // who may be initialised on the device, whatever the moment
 int init_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_STATE, "the initialisation is not offered on a sharded chain");
+    if (c->na_on) return na_refuses("a data-driven start");
     if (explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "a data-driven start is offered for the collapsed and DP samplers only: the stick-breaking and "
                        "full samplers start from pi and theta");
@@ -1673,7 +1731,9 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
         hipLaunchKernelGGL(k_sb_theta_tables, dim3(p.KT + 1), dim3(256), 0, c->stream, p, c->dNk, c->dS,
                            c->dPi, c->dTheta, 1, (uint32_t)j, th_tr, c->dTab, c->dAlpha, al_tr, c->dViable);
         HIP_TRY(hipGetLastError());
-        return sweep_end_folds(c, j);
+        const int rc = sweep_end_folds(c, j);
+        // the missing cells, redrawn from the theta this sweep has just drawn: behind everything else of the sweep
+        return rc == BMM_OK && c->na_on ? enqueue_na_step(c, j) : rc;
     }
     // the armed moves, ahead of the sweep's first table build: split-merge (a DP chain) or eject / absorb (a finite one)
     const int n_sm = c->sm_moves, n_ea = c->alloc_on ? c->alloc_moves : 0;
@@ -1711,7 +1771,8 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
         const int rc = enqueue_fs_gamma(c, j);
         if (rc) return rc;
     }
-    return sweep_end_folds(c, j);
+    const int rc = sweep_end_folds(c, j);
+    return rc == BMM_OK && c->na_on ? enqueue_na_step(c, j) : rc;  // the missing cells: behind everything else of the sweep
 }
 
 // The resident kernel for a shape, batch and X layout: the forms to try, in order, each with its dynamic LDS.
@@ -2030,7 +2091,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     dev_pool().put(c->device, c->run_arena, c->run_arena_bytes);
     void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
                     c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch, c->dSmSide, c->dSmSideLaunch, c->dSmLq, c->dSmStat, c->dSmCell,
-                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock};
+                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock, c->dNaBlock};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     chain_stream_release(c->device, c->stream, c->stream_kind);  // synchronised above
@@ -2164,6 +2225,7 @@ int bmm_chain_share_data(bmm_chain* c, bmm_chain* from) {
     if (!c || !from) return set_err(BMM_E_ARG, "null argument");
     if (c->started || c->have_data) return set_err(BMM_E_STATE, "the chain already has its data");
     if (!from->have_data || !from->bits || !from->dXb) return set_err(BMM_E_STATE, "the source chain holds no bit planes");
+    if (from->na_on) return set_err(BMM_E_UNSUPPORTED, "the source chain redraws missing cells in its planes (bmm_chain_set_missing): they are its own");
     if (from->slot != c->slot) return set_err(BMM_E_ARG, "chains on different devices cannot share planes");
     if (from->p.N != c->p.N || from->p.P != c->p.P) return set_err(BMM_E_ARG, "the chains differ in N or P");
     if (!c->bits) return set_err(BMM_E_STATE, "the int32 layout streams the caller's matrix: hand it over instead");
@@ -2325,6 +2387,7 @@ int bmm_chain_sweep_probs(bmm_chain* c, double* probs_out) {
     if (!c || !probs_out) return set_err(BMM_E_ARG, "null argument");
     if (c->sharded) return set_err(BMM_E_STATE, "not available on a sharded chain");
     if (c->alloc_on) return alloc_refuses("the probability hand-off of the relabelling");
+    if (c->na_on) return na_refuses("the probability hand-off of the relabelling");
     HIP_TRY(hipSetDevice(c->device));
     int rc = probs_alloc(c, true);
     if (rc) return rc;
@@ -2689,6 +2752,7 @@ static int pred_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, i
 // ---- leave-one-out predictive of the fitted rows ----
 static int loo_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the leave-one-out predictive is not offered on a sharded chain");
+    if (c->na_on) return na_refuses("the leave-one-out predictive");
     if (c->fs_mask) return fs_mask_refuses("the leave-one-out predictive");
     if (c->alloc_on) return alloc_refuses("the leave-one-out predictive");
     return BMM_OK;
@@ -3128,6 +3192,7 @@ int bmm_device_log_joint(int device, const int32_t* X, int64_t N, int P, int sam
 // ---- pairwise local-dependence check ----
 static int pc_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the pair check is not offered on a sharded chain: a shard holds a part of the rows");
+    if (c->na_on) return na_refuses("the pair check (its column slices are cut once)");
     if (c->fs_mask)
         return set_err(BMM_E_UNSUPPORTED, "the pair check is written for the model in which every feature clusters: not offered on a "
                        "chain with a feature mask (the pooled model's reference distribution is another one)");
@@ -3553,6 +3618,7 @@ int bmm_chain_set_labels(bmm_chain* c, const int32_t* z1) {
 // who may run it: a whole finite collapsed chain on the bit planes, fixed concentration, rows with labels
 static int alloc_refused(const bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
+    if (c->na_on) return na_refuses("the allocation sampler");
     if (c->sharded) return set_err(BMM_E_STATE, "the allocation sampler is not offered on a sharded chain");
     if (c->p.mode != MODE_COLLAPSED)
         return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is the finite collapsed sampler with K unknown: create the chain with that sampler, K = maxK");
@@ -3782,6 +3848,7 @@ int bmm_chain_get_init_rows(bmm_chain* c, int64_t* rows, int32_t* Nk) {
 // who may carry a mask: the two counting samplers, whole (not sharded), with rows that have or will get seats
 static int fs_refused(const bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
+    if (c->na_on) return na_refuses("feature selection");
     if (c->sharded) return set_err(BMM_E_STATE, "feature selection is not offered on a sharded chain");
     if (explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "feature selection is offered for the collapsed and DP samplers only: the stick-breaking and "
@@ -3994,10 +4061,241 @@ static int fs_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, int
     return bmm_chain_get_feature_summary(c, f.inclusion, f.inclusion_rb, f.n_folded);
 }
 
+// ---- missing data: NA cells imputed behind every sweep (include/bmm_mcmc.h "missing data") ----
+// the cell list itself: in range and strictly ascending in (row, column).  Nothing of a device is touched.
+static int na_check_cells(const int64_t* rows, const int32_t* cols, int64_t n, int64_t N, int P) {
+    if (n < 0) return set_err(BMM_E_ARG, "n_cells must be >= 0");
+    if (n > 0 && (!rows || !cols)) return set_err(BMM_E_ARG, "null cell list");
+    for (int64_t q = 0; q < n; ++q) {
+        if (rows[q] < 0 || rows[q] >= N || cols[q] < 0 || cols[q] >= P)
+            return set_err(BMM_E_ARG, "missing cell %lld = (%lld, %d) lies outside the %lld x %d matrix", (long long)q, (long long)rows[q],
+                           (int)cols[q], (long long)N, P);
+        if (q > 0 && (rows[q] < rows[q - 1] || (rows[q] == rows[q - 1] && cols[q] <= cols[q - 1])))
+            return set_err(BMM_E_ARG, "the missing cells must be strictly ascending in (row, column): cell %lld is not", (long long)q);
+    }
+    return BMM_OK;
+}
+// who may carry missing cells: a whole chain on bit planes of its own, with none of the options that read the matrix
+// as observed or cut it once
+static int na_refused(const bmm_chain* c) {
+    if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered on a sharded chain");
+    if (!c->bits) return set_err(BMM_E_UNSUPPORTED, "the imputation step rewrites the bit planes: not offered on the int32 layout");
+    if (c->xb_borrowed || c->shares_device || (c->planes && c->planes->refs.load() > 1) || c->ladder)
+        return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered on planes that several chains read (bmm_chain_share_data, a "
+                       "ladder): every chain would need completed cells of its own");
+    if (c->loo_on) return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered together with the leave-one-out summary: it would score imputed cells as data");
+    if (c->temper_on) return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered on a tempered chain: the rungs share one matrix");
+    if (c->pc_on) return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered together with the pair check: its column slices are cut once");
+    if (c->fs_mask || c->sm_moves > 0 || c->alloc_on)
+        return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered together with feature selection, split-merge moves or the allocation sampler");
+    if (!c->have_data || !c->dXb) return set_err(BMM_E_STATE, "the chain has no data: set the data first");
+    if (c->shard_open) return set_err(BMM_E_STATE, "a sweep is open");
+    return BMM_OK;
+}
+static bool na_seated(const bmm_chain* c) { return c->started && (c->p.mode == MODE_COLLAPSED || c->sweep >= 1); }
+static void na_disarm(bmm_chain* c) {
+    c->na_on = false;
+    c->na_cells = c->na_sites = c->na_folded = 0;
+    c->na_rows.clear(); c->na_cols.clear();
+    c->na_rec = SweepTrace{};
+}
+static int na_reset(bmm_chain* c) {
+    c->na_folded = 0;
+    HIP_TRY(hipMemsetAsync(c->dNaSum, 0, (size_t)c->na_cells * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(c->dNaOnes, 0, (size_t)c->na_cells * sizeof(uint32_t), c->stream));
+    return BMM_OK;
+}
+
+int bmm_chain_set_missing(bmm_chain* c, const int64_t* rows, const int32_t* cols, int64_t n_cells) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        int rc = na_check_cells(rows, cols, n_cells, c->p.N, c->p.P);
+        if (rc) return rc;
+        if (n_cells == 0) {  // withdrawn: the planes keep the cells' last values
+            if (c->na_on) HIP_TRY(hipStreamSynchronize(c->stream));
+            na_disarm(c);
+            return BMM_OK;
+        }
+        if (c->na_on) return set_err(BMM_E_STATE, "missing cells are already declared: withdraw them first (n_cells = 0)");
+        rc = na_refused(c);
+        if (rc) return rc;
+        if (c->dTrace && c->sweep > 0) return set_err(BMM_E_STATE, "not offered inside a run");
+        HIP_TRY(hipSetDevice(c->device));
+        const ChainParams& p = c->p;
+        // the sites: one per (row, plane word) that has a hole
+        std::vector<int64_t> srow, sfirst;
+        std::vector<int32_t> sword;
+        std::vector<uint32_t> smask;
+        for (int64_t q = 0; q < n_cells; ++q) {
+            const int w = cols[q] >> 5;
+            if (srow.empty() || srow.back() != rows[q] || sword.back() != w) {
+                srow.push_back(rows[q]); sword.push_back(w); smask.push_back(0u); sfirst.push_back(q);
+            }
+            smask.back() |= 1u << (cols[q] & 31);
+        }
+        const size_t ns = srow.size(), nc = (size_t)n_cells, KP = (size_t)p.K * p.P;
+        Carver measure{nullptr};
+        auto carve = [&](Carver& v) {
+            c->dNaRow = v.take<int64_t>(ns);
+            c->dNaFirst = v.take<int64_t>(ns);
+            c->dNaSum = v.take<double>(nc);
+            c->dNaPhi = v.take<double>(KP);
+            c->dNaWord = v.take<int32_t>(ns);
+            c->dNaMask = v.take<uint32_t>(ns);
+            c->dNaCnt = v.take<int32_t>(2 * KP);
+            c->dNaOnes = v.take<uint32_t>(nc);
+        };
+        carve(measure);
+        rc = pred_room(measure.used, "the missing cells' site list and folds");
+        if (rc) return rc;
+        if (c->dNaBlock) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->dNaBlock); c->dNaBlock = nullptr; }
+        HIP_TRY(hipMalloc(&c->dNaBlock, measure.used));
+        Carver real{c->dNaBlock};
+        carve(real);
+        HIP_TRY(hipMemsetAsync(c->dNaBlock, 0, measure.used, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dNaRow, srow.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dNaFirst, sfirst.data(), ns * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dNaWord, sword.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dNaMask, smask.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        c->na_cells = n_cells; c->na_sites = (int64_t)ns; c->na_folded = 0;
+        c->na_lds = na_tables_in_lds(p.K, p.P);
+        // a workgroup per kNaThreads sites, up to two per compute unit, grid-stride beyond: every workgroup flushes a
+        // table of its own onto the same K P words, and those adds queue per word (north star, step alone: 0.041 ms at two
+        // per unit against 0.065 at eight with 1 % of the cells missing, 0.227 against 0.277 with 30 %; one per unit leaves
+        // the gathers too few waves: 0.342 at 30 %)
+        const int64_t nb = ((int64_t)ns + kNaThreads - 1) / kNaThreads, most = (int64_t)2 * (c->num_cus > 0 ? c->num_cus : 256);
+        const int dbg_grid = dbg_env_int("BMM_DEBUG_NA_GRID", 0);  // the test variant: that many workgroups at the most
+        c->na_grid = (int)(dbg_grid > 0 && nb > dbg_grid ? dbg_grid : (nb < most ? nb : most));
+        if (c->na_lds)  // the draw keeps the rates and the deltas: up to 72 KiB of dynamic LDS
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_na_draw<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)(KP * (sizeof(double) + sizeof(int32_t)))));
+        // the starting fill; where the rows have seats the counts follow the planes
+        const NaArgs a = na_args(c, na_seated(c) ? label_row(c, c->sweep) : nullptr, 0u, false);
+        hipLaunchKernelGGL(k_na_fill, dim3((unsigned)c->na_grid), dim3(kNaThreads), 0, c->stream, p, a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(c->stream));  // the host vectors go out of scope
+        c->na_rows.assign(rows, rows + n_cells);
+        c->na_cols.assign(cols, cols + n_cells);
+        c->na_rec = SweepTrace{};
+        c->na_rec.fold = true;  // every step from now on
+        c->na_rec.from = 0;
+        c->na_on = true;
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_impute_step(bmm_chain* c) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (!c->na_on) return set_err(BMM_E_STATE, "no missing cells are declared (bmm_chain_set_missing)");
+        HIP_TRY(hipSetDevice(c->device));
+        if (!c->started && c->p.mode == MODE_COLLAPSED) {
+            const int rc = chain_start(c);
+            if (rc) return rc;
+        }
+        if (!na_seated(c)) return set_err(BMM_E_STATE, "the chain has rows without a label: run a sweep first");
+        return enqueue_na_step(c, c->sweep);
+    });
+}
+
+int bmm_chain_get_missing_state(bmm_chain* c, uint8_t* bits) {
+    return guarded([&]() -> int {
+        if (!c || !bits) return set_err(BMM_E_ARG, "null argument");
+        if (!c->na_on) return set_err(BMM_E_STATE, "no missing cells are declared (bmm_chain_set_missing)");
+        int rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        // the sites' words, gathered on the device; a site's cells are consecutive in the list
+        const size_t ns = (size_t)c->na_sites;
+        DevBuf buf;
+        HIP_TRY(buf.alloc(ns * sizeof(uint32_t)));
+        const NaArgs a = na_args(c, nullptr, 0u, false);
+        hipLaunchKernelGGL(k_na_words, dim3((unsigned)c->na_grid), dim3(kNaThreads), 0, c->stream, c->p, a, buf.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        std::vector<uint32_t> word(ns);
+        HIP_TRY(hipMemcpyAsync(word.data(), buf.p, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        int64_t last_row = -1, t = -1; int last_w = -1;
+        for (int64_t q = 0; q < c->na_cells; ++q) {
+            const int64_t i = c->na_rows[(size_t)q];
+            const int w = c->na_cols[(size_t)q] >> 5;
+            if (i != last_row || w != last_w) { ++t; last_row = i; last_w = w; }
+            bits[q] = (uint8_t)((word[(size_t)t] >> (c->na_cols[(size_t)q] & 31)) & 1u);
+        }
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_get_missing_summary(bmm_chain* c, double* mean_rb, double* mean_draw, int64_t* n_folded) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (!c->na_on) return set_err(BMM_E_STATE, "no missing cells are declared (bmm_chain_set_missing)");
+        int rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        const size_t nc = (size_t)c->na_cells;
+        const double n = (double)c->na_folded;  // 0: NaN
+        if (mean_rb) {
+            HIP_TRY(hipMemcpy(mean_rb, c->dNaSum, nc * sizeof(double), hipMemcpyDeviceToHost));
+            for (size_t q = 0; q < nc; ++q) mean_rb[q] = mean_rb[q] / n;
+        }
+        if (mean_draw) {
+            std::vector<uint32_t> cnt(nc);
+            HIP_TRY(hipMemcpy(cnt.data(), c->dNaOnes, nc * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (size_t q = 0; q < nc; ++q) mean_draw[q] = (double)cnt[q] / n;
+        }
+        if (n_folded) *n_folded = c->na_folded;
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_missing_reset(bmm_chain* c) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (!c->na_on) return BMM_OK;
+        HIP_TRY(hipSetDevice(c->device));
+        return na_reset(c);
+    });
+}
+
+// ... of a run: armed for it (bmm_set_missing), the step behind every sweep, the kept sweeps folded
+static int na_run_check(const RunOptions& o, int64_t N, int P) {
+    if (!o.na.on) return BMM_OK;
+    int rc = na_check_cells(o.na.rows, o.na.cols, o.na.n, N, P);
+    if (rc) return rc;
+    if (!o.na.o.mean_rb || !o.na.o.mean_draw || !o.na.o.last || !o.na.o.n_folded) return set_err(BMM_E_ARG, "missing data: null buffer");
+    if (dbg_env("BMM_X_LAYOUT_INT32")) return set_err(BMM_E_UNSUPPORTED, "the imputation step rewrites the bit planes: not offered on the int32 layout");
+    if (o.loo.on) return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered together with the leave-one-out summary: it would score imputed cells as data");
+    if (o.temper.on) return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered together with parallel tempering: the rungs share one matrix");
+    if (o.pc.on) return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered together with the pair check: its column slices are cut once");
+    if (o.fs.on || o.sm.moves > 0 || o.init.kind != 0 || o.alloc.on)
+        return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered together with feature selection, split-merge moves, a device start or "
+                       "the allocation sampler");
+    if (o.hooks || o.rel)
+        return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered together with a probability hand-off (relabel = TRUE): relabel from the "
+                       "label trace instead (ECR)");
+    return BMM_OK;
+}
+static int na_run_attach(bmm_chain* c, const RunOptions& o) {
+    if (!o.na.on || o.na.n == 0) return BMM_OK;
+    const int rc = bmm_chain_set_missing(c, o.na.rows, o.na.cols, o.na.n);
+    if (rc) return rc;
+    c->na_rec.from = run_first_fold(c);
+    return BMM_OK;
+}
+static int na_run_collect(bmm_chain* c, const RunOptions& o, int rc) {
+    if (!o.na.on) return rc;
+    if (rc) return rc;
+    *o.na.o.n_folded = 0;
+    if (o.na.n == 0) return BMM_OK;
+    rc = bmm_chain_get_missing_summary(c, o.na.o.mean_rb, o.na.o.mean_draw, o.na.o.n_folded);
+    if (rc == BMM_OK) rc = bmm_chain_get_missing_state(c, o.na.o.last);
+    return rc;
+}
+
 // ---- parallel tempering: a replica ladder (include/bmm_mcmc.h "parallel tempering") ----
 // who may be a rung
 static int temper_refused(const bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
+    if (c->na_on) return na_refuses("parallel tempering");
     if (explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "parallel tempering is offered for the collapsed and DP samplers only: the stick-breaking "
                        "and full samplers carry theta, and the power sits on the likelihood with theta integrated out");
@@ -5505,6 +5803,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
         if (rc == BMM_OK) rc = st_run_check(opts, burnin, K);
         if (rc == BMM_OK) rc = ecr_run_check(opts, nsamples - burnin, N, K);
         if (rc == BMM_OK) rc = pc_run_check(opts, P, K);
+        if (rc == BMM_OK) rc = na_run_check(opts, N, P);
         if (rc) return rc;
         for (double& v : g_phase_ms) v = 0.0;
         PhaseClock clock;
@@ -5537,6 +5836,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
                 rc = bmm_chain_set_data_host(c, X);
             }
             if (rc == BMM_OK) rc = init_run_attach(c, opts);
+            if (rc == BMM_OK) rc = na_run_attach(c, opts);  // the cells are filled before anything counts them
             if (rc) return rc;
             clock.lap(0);
             // what the options record per kept sweep: each ends, and waits for the stream before its rows go, on every way out
@@ -5552,6 +5852,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             if (rc) return rc;
             rc = run_body(c, nsamples, io, opts);
             rc = temper_run_collect(c, opts, temper, rc);
+            rc = na_run_collect(c, opts, rc);
             rc = pc_run_collect(c, opts, pc_rec, rc);
             rc = lp_run_collect(c, opts, lp_rec, rc);
             rc = sm_run_collect(c, opts, rc);
@@ -5788,6 +6089,7 @@ int bmm_alloc_run(const int32_t* X, int64_t N, int P, const int32_t* initialK, i
                   int burnin, int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
                   int32_t* k_out, int64_t moves_out[4]) {
     RunOptions opts = take_run_options();
+    if (opts.na.on) return set_err(BMM_E_UNSUPPORTED, "missing cells (bmm_set_missing) are not offered by the allocation sampler's run");
     if (!log_prior_k || !k_out) return set_err(BMM_E_ARG, "null buffer");
     if (!(a > 0.0)) return set_err(BMM_E_ARG, "a must be > 0");
     if (maxK > kMaxCats) return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is offered up to maxK = %d", kMaxCats);
@@ -5930,6 +6232,12 @@ int bmm_set_temper(const bmm_temper_out* out) {
     return BMM_OK;
 }
 
+int bmm_set_missing(const int64_t* rows, const int32_t* cols, int64_t n_cells, const bmm_missing_out* out) {
+    g_armed.na.on = out != nullptr;
+    g_armed.na.rows = rows; g_armed.na.cols = cols; g_armed.na.n = n_cells;
+    g_armed.na.o = out ? *out : bmm_missing_out{};
+    return BMM_OK;
+}
 int bmm_set_pair_check(const bmm_pair_check_out* out) {
     g_armed.pc.on = out != nullptr;
     g_armed.pc.feat.clear();
@@ -6101,9 +6409,11 @@ int bmm_multi_run(int sampler, int n_chains, const int* devices, const int32_t* 
                   double gamma, double a, double b, int burnin, int64_t batch, uint64_t seed,
                   double* const* pi_out, int32_t* const* z_out, double* const* theta_out,
                   double* const* alpha_out) {
-    (void)take_run_options();  // a run of several chains disarms whatever was armed ...
+    const bool na_armed = take_run_options().na.on;  // a run of several chains disarms whatever was armed ...
     const RunOptions opts;     // ... and runs every chain without it
     return guarded([&]() -> int {
+        // (... but does not run over a matrix whose holes were zeroed as if nothing had been said)
+        if (na_armed) return set_err(BMM_E_UNSUPPORTED, "missing cells (bmm_set_missing) are not offered by a run of several chains: they share one matrix");
         if (sampler < 0 || sampler > 3) return set_err(BMM_E_ARG, "unknown sampler %d", sampler);
         if (n_chains < 1) return set_err(BMM_E_ARG, "n_chains must be >= 1");
         if (!z_out || !theta_out || !alpha_out) return set_err(BMM_E_ARG, "null output table");

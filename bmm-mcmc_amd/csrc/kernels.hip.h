@@ -4571,4 +4571,162 @@ __global__ __launch_bounds__(256) void k_pc_stats(PcStatArgs a) {
     }
 }
 
+// ---- missing data: NA cells imputed behind every sweep (include/bmm_mcmc.h "missing data") ----
+// The missing cells are a list of sites: one (row i, plane word w) with the mask of its missing bits and the index of its
+// first cell in the caller's (row, column) order, so a site's cells are consecutive there.  One thread owns a site: it
+// reads z_i and the word Xb[w * N + i], rewrites the masked bits and stores the word with a plain store -- no two
+// threads touch the same word, and a cell's sums have one owner too, so nothing floating-point is atomic and one seed
+// gives the same bits twice.  What is atomic is integer: the census and the S deltas, added in LDS per workgroup
+// (ds_add_u32; lanes that meet on a bank take turns, nothing more) and flushed with one device-scope atomicAdd per
+// non-empty cell, which is resolved in the memory side of the L2s and so holds across XCDs; integer adds in any order
+// give the same bits.  The site arrays are read a lane a site (coalesced), the words are gathers: a wave's 64 sites lie
+// in ascending (row, word) order, so its words of one plane fall into few cache lines when the holes are dense and into
+// one line each when they are sparse -- 64 B fetched for 4 B used, the price of a hole.
+// Above kNaLdsBytes the tables stay in global memory: the census and the deltas add there, phi / theta is read there.
+constexpr int kNaThreads = 256;
+constexpr size_t kNaLdsBytes = 49152;  // what the other histogram kernels allow themselves
+__host__ __device__ inline bool na_tables_in_lds(int K, int P) { return (size_t)K * (size_t)P * 8 <= kNaLdsBytes; }
+struct NaArgs {
+    const int64_t* row;     // [n_sites]
+    const int32_t* word;    // [n_sites] plane word w
+    const uint32_t* mask;   // [n_sites] the missing bits of the word
+    const int64_t* first;   // [n_sites] index of the site's first cell in the cell list
+    int64_t n_sites;
+    uint32_t* Xb;           // the planes [W][N]
+    const int32_t* z;       // [N] labels, 0-based (< 0: the row has no seat yet and is left alone); null: no row has one
+    int32_t* S;             // [K][P] the folded counts the deltas are added to
+    int32_t* cnt;           // [2][K*P]: M_kj, then O_kj (k_na_census, k_na_phi)
+    int32_t *Nk, *dNk, *dS; // the chain's sizes and pending deltas (k_na_phi reads the sums)
+    double* phi;            // [k + j*K]: the step's rates -- the auxiliary draws of a counting chain, theta of an explicit one
+    double* sum_phi;        // [n_cells] folds, or null
+    uint32_t* ones;         // [n_cells]
+    uint32_t sweep;
+    int fold;
+};
+
+// the starting fill: every cell Bernoulli(beta / (beta + gamma)) from the uniform of sweep 0; rows with a seat move S
+__global__ __launch_bounds__(kNaThreads) void k_na_fill(ChainParams p, NaArgs a) {
+    const double rate = div_(p.beta, p.beta + p.gamma);
+    for (int64_t t = (int64_t)blockIdx.x * kNaThreads + threadIdx.x; t < a.n_sites; t += (int64_t)gridDim.x * kNaThreads) {
+        const int64_t i = a.row[t];
+        const int w = a.word[t];
+        const int k = a.z ? a.z[i] : -1;
+        uint32_t m = a.mask[t];
+        const size_t at = (size_t)w * (size_t)p.N + (size_t)i;
+        uint32_t x = a.Xb[at];
+        while (m) {
+            const int b = __ffs(m) - 1;
+            m &= m - 1;
+            const int j = w * 32 + b;
+            const uint32_t nb = na_uniform(p.seed, (uint64_t)i * (uint64_t)p.P + (uint64_t)j, 0u) < rate ? 1u : 0u;
+            const int d = (int)nb - (int)((x >> b) & 1u);
+            x = (x & ~(1u << b)) | (nb << b);
+            if (d != 0 && k >= 0) atomicAdd(&a.S[(size_t)k * p.P + j], d);
+        }
+        a.Xb[at] = x;
+    }
+}
+
+// the sites' words as they stand, for the host (bmm_chain_get_missing_state)
+__global__ __launch_bounds__(kNaThreads) void k_na_words(ChainParams p, NaArgs a, uint32_t* __restrict__ out) {
+    for (int64_t t = (int64_t)blockIdx.x * kNaThreads + threadIdx.x; t < a.n_sites; t += (int64_t)gridDim.x * kNaThreads)
+        out[t] = a.Xb[(size_t)a.word[t] * (size_t)p.N + (size_t)a.row[t]];
+}
+
+// flush of an LDS table of n integers into global memory: one add per non-empty cell
+__device__ __forceinline__ void na_flush(const int32_t* hist, int n, int32_t* dst) {
+    for (int q = threadIdx.x; q < n; q += kNaThreads) {
+        const int32_t v = hist[q];
+        if (v != 0) atomicAdd(&dst[q], v);
+    }
+}
+
+// counting chains: M_kj, the missing cells among label k's rows, and O_kj, how many of them hold a 1
+template <bool LDS>
+__global__ __launch_bounds__(kNaThreads) void k_na_census(ChainParams p, NaArgs a) {
+    extern __shared__ int32_t na_hist[];
+    const int KP = p.K * p.P;
+    if (LDS) {
+        for (int q = threadIdx.x; q < 2 * KP; q += kNaThreads) na_hist[q] = 0;
+        __syncthreads();
+    }
+    int32_t* const dst = LDS ? na_hist : a.cnt;
+    for (int64_t t = (int64_t)blockIdx.x * kNaThreads + threadIdx.x; t < a.n_sites; t += (int64_t)gridDim.x * kNaThreads) {
+        const int64_t i = a.row[t];
+        const int k = a.z[i];
+        if (k < 0) continue;
+        const int w = a.word[t];
+        uint32_t m = a.mask[t];
+        const uint32_t x = a.Xb[(size_t)w * (size_t)p.N + (size_t)i];
+        while (m) {
+            const int b = __ffs(m) - 1;
+            m &= m - 1;
+            const int kj = k * p.P + w * 32 + b;
+            atomicAdd(&dst[kj], 1);
+            if ((x >> b) & 1u) atomicAdd(&dst[KP + kj], 1);
+        }
+    }
+    if (LDS) {
+        __syncthreads();
+        na_flush(na_hist, 2 * KP, a.cnt);
+    }
+}
+
+// counting chains: phi_kj ~ Beta(beta + s, gamma + n - s) from the observed-only counts, where a label has a hole in the feature
+__global__ __launch_bounds__(kNaThreads) void k_na_phi(ChainParams p, NaArgs a) {
+    const int KP = p.K * p.P;
+    const int kj = blockIdx.x * kNaThreads + threadIdx.x;
+    if (kj >= KP) return;
+    const int32_t M = a.cnt[kj];
+    if (M <= 0) return;
+    const int k = kj / p.P, j = kj % p.P;
+    const int64_t s = (int64_t)a.S[kj] + delta_take(a.dS, (size_t)kj, (size_t)KP) - a.cnt[KP + kj];
+    const int64_t n = (int64_t)a.Nk[k] + delta_take(a.dNk, (size_t)k, (size_t)p.K) - M;
+    a.phi[k + (size_t)j * p.K] = na_phi(p.seed, p.beta, p.gamma, (uint32_t)kj, a.sweep, s, n);
+}
+
+// the draw: bit = u_ij < phi_{z_i, j} for every missing cell, the word rewritten, S moved by the sum of (new - old)
+template <bool LDS>
+__global__ __launch_bounds__(kNaThreads) void k_na_draw(ChainParams p, NaArgs a) {
+    extern __shared__ double na_tab[];
+    const int KP = p.K * p.P;
+    int32_t* const hist = reinterpret_cast<int32_t*>(na_tab + KP);
+    if (LDS) {
+        for (int q = threadIdx.x; q < KP; q += kNaThreads) { na_tab[q] = a.phi[q]; hist[q] = 0; }
+        __syncthreads();
+    }
+    const double* const phi = LDS ? na_tab : a.phi;
+    int32_t* const dst = LDS ? hist : a.S;
+    for (int64_t t = (int64_t)blockIdx.x * kNaThreads + threadIdx.x; t < a.n_sites; t += (int64_t)gridDim.x * kNaThreads) {
+        const int64_t i = a.row[t];
+        const int k = a.z[i];
+        if (k < 0) continue;
+        const int w = a.word[t];
+        uint32_t m = a.mask[t];
+        int64_t cell = a.first[t];
+        const size_t at = (size_t)w * (size_t)p.N + (size_t)i;
+        uint32_t x = a.Xb[at];
+        while (m) {
+            const int b = __ffs(m) - 1;
+            m &= m - 1;
+            const int j = w * 32 + b;
+            const double ph = phi[k + (size_t)j * p.K];
+            const uint32_t nb = na_uniform(p.seed, (uint64_t)i * (uint64_t)p.P + (uint64_t)j, a.sweep) < ph ? 1u : 0u;
+            const int d = (int)nb - (int)((x >> b) & 1u);
+            x = (x & ~(1u << b)) | (nb << b);
+            if (d != 0) atomicAdd(&dst[k * p.P + j], d);
+            if (a.fold) {
+                a.sum_phi[cell] = a.sum_phi[cell] + ph;
+                a.ones[cell] += nb;
+            }
+            ++cell;
+        }
+        a.Xb[at] = x;
+    }
+    if (LDS) {
+        __syncthreads();
+        na_flush(hist, KP, a.S);
+    }
+}
+
 }  // namespace bmm

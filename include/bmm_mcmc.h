@@ -1197,6 +1197,61 @@ typedef struct bmm_pair_check_plan_out {
 } bmm_pair_check_plan_out;
 int bmm_pair_check_plan(int64_t N, int Kc, int M, bmm_pair_check_plan_out* out);
 
+/* ---- missing data: NA cells imputed on the device ------------------------------------------------
+ * Cells missing at random, handled by data augmentation.  The chain lives on (z, x_mis, ...): the sampler's own sweep
+ * runs on the completed matrix, unchanged, and behind every sweep end the missing cells are redrawn jointly and exactly
+ * given everything else.  Both steps leave p(z, x_mis, ... | x_obs) invariant, so the labels are draws from the posterior
+ * of the model with the missing cells integrated out.
+ *   Counting chains (collapsed, DP): for every label k and feature j with a missing cell among k's rows, with n the
+ * label's rows that have the feature observed and s of them holding a 1, phi_kj ~ Beta(beta + s, gamma + n - s) (n = 0:
+ * the prior; bmm_spec.h na_phi), thrown away after the step.  Explicit chains (stick-breaking, full): phi is the theta
+ * the sweep has just drawn.  Then every missing cell (i, j) becomes  u_ij < phi_{z_i, j},  u_ij = na_uniform(seed,
+ * i * P + j, sweep) (bmm_spec.h): keyed by the cell and the sweep alone.  phi first and the cells independently given it
+ * is the composition form of the Polya-urn joint of the cells of one (k, j); drawing them in parallel from the plug-in
+ * rate (beta + s) / (beta + gamma + n) would not be exact.
+ *   The step runs behind everything sweep t does today, so the theta row recorded for sweep t belongs to (z_t, X_{t-1}):
+ * the labels of sweep t with the cells as they stood before its step.  Whenever the chain is idle, bmm_chain_get_counts
+ * equals a recount of the completed matrix under the current labels.  The log joint (bmm_set_logpost) of an armed chain
+ * is the joint of the completed state.
+ *
+ * bmm_chain_set_missing: after the data is set, before or after the rows have labels.  rows / cols: the n_cells missing
+ * cells, 0-based, strictly ascending in (row, column); their values in the matrix that was handed over are ignored.
+ * Every cell is filled with  na_uniform(seed, cell, 0) < beta / (beta + gamma)  and, where the rows have labels, the
+ * counts follow.  n_cells = 0 withdraws the declaration (the planes keep the cells' last values).  From then on every
+ * sweep of bmm_chain_sweeps* is followed by the step, and every step is folded into the summary.
+ *   BMM_E_ARG: a cell out of range or out of order.  BMM_E_UNSUPPORTED: the int32 layout; a sharded chain; a chain
+ * whose planes other chains read (bmm_chain_share_data, a ladder); together, in either order, with the leave-one-out
+ * summary and parallel tempering (wrong on a completed or shared matrix), the pair check (its slices are cut once),
+ * feature selection, split-merge moves, the allocation sampler, bmm_chain_init_labels and bmm_chain_sweep_probs (not in
+ * this change).  BMM_E_STATE: no data yet, cells already declared, new data under declared cells.  All of these are
+ * answered before a device is touched. */
+int bmm_chain_set_missing(bmm_chain* c, const int64_t* rows, const int32_t* cols, int64_t n_cells);
+/* one imputation step now, under the index of the last sweep (the keys of that sweep's own step: meant for a chain
+ * inspected by hand, not for sampling).  Folded like any other step. */
+int bmm_chain_impute_step(bmm_chain* c);
+/* bits[n_cells]: the cells' current values, in the order they were declared */
+int bmm_chain_get_missing_state(bmm_chain* c, uint8_t* bits);
+/* over the folded steps, per cell (any may be NULL): mean_rb, the mean of phi_{z_i, j} (Rao-Blackwellised: the posterior
+ * probability that the cell is a 1), mean_draw, the share of ones drawn; NaN before the first fold.  Each cell's sums
+ * have one owner and the steps add in order: one seed gives the same bits twice. */
+int bmm_chain_get_missing_summary(bmm_chain* c, double* mean_rb, double* mean_draw, int64_t* n_folded);
+int bmm_chain_missing_reset(bmm_chain* c);
+/* For a run: armed per calling thread for the NEXT bmm_collapsed_run / bmm_dp_run / bmm_sb_run / bmm_full_run (and their
+ * _probs form without hooks, and _predict) of that thread and disarmed when that call returns; out = NULL disarms.
+ * rows, cols and the buffers of out must live until the run returns; the X of the run holds any 0 / 1 value in the
+ * missing cells.  Kept sweeps are folded; last[n_cells] receives the cells after the last sweep.  BMM_E_ARG and
+ * BMM_E_UNSUPPORTED as above, also for bmm_set_init and a *_run_relabel / hooked *_run_probs hand-off; bmm_multi_run
+ * and bmm_alloc_run answer an armed declaration with BMM_E_UNSUPPORTED.  n_cells = 0 is the run without it, byte for
+ * byte.  Allowed, and unchanged because they read labels or folded counts only: the partition summary, ECR, the
+ * predictive of complete new rows and the log joint trace. */
+typedef struct bmm_missing_out {
+    double* mean_rb;    /* [n_cells] */
+    double* mean_draw;  /* [n_cells] */
+    uint8_t* last;      /* [n_cells] */
+    int64_t* n_folded;
+} bmm_missing_out;
+int bmm_set_missing(const int64_t* rows, const int32_t* cols, int64_t n_cells, const bmm_missing_out* out);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
