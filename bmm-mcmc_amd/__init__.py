@@ -1003,6 +1003,18 @@ class _AllocStep(_C.Structure):  # bmm_alloc_step
                 ("log_r", _C.c_double), ("sweep", _C.c_uint32), ("move", _C.c_uint32), ("side", _C.c_void_p)]
 
 
+class _AllocSplitStep(_C.Structure):  # bmm_alloc_split_step
+    _fields_ = [("row_i", _C.c_int64), ("row_j", _C.c_int64), ("label_a", _C.c_int32), ("label_b", _C.c_int32),
+                ("kind", _C.c_int32), ("accepted", _C.c_int32), ("k_before", _C.c_int32), ("k_after", _C.c_int32),
+                ("moved", _C.c_int32), ("pad", _C.c_int32), ("members", _C.c_int64), ("n_before", _C.c_int64 * 2),
+                ("n_after", _C.c_int64 * 2), ("log_prior", _C.c_double), ("log_lik", _C.c_double),
+                ("log_q", _C.c_double), ("log_u", _C.c_double), ("log_r", _C.c_double), ("sweep", _C.c_uint32),
+                ("move", _C.c_uint32), ("launch_side", _C.c_void_p), ("proposal_side", _C.c_void_p)]
+
+
+_AS_FIELDS = ("proposed_splits", "accepted_splits", "proposed_merges", "accepted_merges", "skipped")
+
+
 def log_prior_k(prior_k, maxK):
     """log p(K), K = 1..maxK: "poisson" (Poisson(1) truncated to 1..maxK, the default of Nobile & Fearnside 2007),
     "uniform", or maxK positive weights (normalised here)"""
@@ -1024,7 +1036,8 @@ def log_prior_k(prior_k, maxK):
 
 def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, moves=1, eject_a=1.0, beta=0.5, gamma=0.5,
                      burnin=None, *, seed=None, batch=None, device=0, initial_K=None, partition=None, partition_stride=1,
-                     similarity_of=None, relabel=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False):
+                     similarity_of=None, relabel=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
+                     split_merge=0, split_merge_scans=SPLIT_MERGE_SCANS):
     """The allocation sampler of Nobile & Fearnside (2007): the finite collapsed Beta-Bernoulli mixture with the number of
     components K unknown, 1 <= K <= maxK <= 64 (include/bmm_mcmc.h "allocation sampler").  The
     weights are Dirichlet(a, ..., a) with `a` fixed per component; `prior_k`: see log_prior_k.  A sweep is the finite
@@ -1034,7 +1047,14 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
     S) with NaN where a label is empty, K (S,), k_posterior (maxK,): the kept-sweep frequencies of K = 1..maxK, k_used
     (S,): the non-empty labels per sweep, moves: the four counts, and with `partition=` the summary of gibbs_collapsed.
     `relabel="ecr"` is refused by the library (BMM_E_UNSUPPORTED): the relabelling assumes a fixed number of components.
-    `logpost=True`: as gibbs_collapsed, with log p(K) and the Dirichlet(a) prior over the open labels as log_prior."""
+    `logpost=True`: as gibbs_collapsed, with log p(K) and the Dirichlet(a) prior over the open labels as log_prior.
+    `split_merge=m`: m split-merge moves of the allocation sampler behind the eject / absorb moves
+    of every sweep from the second, each with `split_merge_scans` intermediate restricted scans: a split opens component
+    K + 1 along the data, a merge closes one.  The result gains `split_merge = {"proposed_splits", "accepted_splits",
+    "proposed_merges", "accepted_merges", "skipped"}`."""
+    split_merge, split_merge_scans = int(split_merge or 0), int(split_merge_scans)
+    if split_merge < 0 or split_merge_scans < 0:
+        raise ValueError("split_merge and split_merge_scans must be >= 0")
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, maxK = int(nsamples), int(maxK)
@@ -1066,6 +1086,8 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
     lj = _LogPost(N, S) if logpost else None
     if lj is not None:
         lj.arm()
+    if split_merge > 0:
+        _capi.check(_capi.lib().bmm_set_alloc_split_merge(_C.c_int(split_merge), _C.c_int(split_merge_scans)))
     _capi.check(_capi.lib().bmm_alloc_run(
         _capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(maxK), _C.c_double(a),
         _C.c_double(beta), _C.c_double(gamma), _capi.vp(lp), _C.c_int(K0), _C.c_int(int(moves)), _C.c_double(eject_a),
@@ -1074,6 +1096,10 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
     used = _np.array([len(_np.unique(row)) for row in z], dtype=_np.int32)
     out = {"z": z, "theta": theta, "K": Ks, "k_posterior": _np.bincount(Ks, minlength=maxK + 1)[1:] / float(S), "k_used": used,
            "moves": dict(zip(_EA_FIELDS, (int(v) for v in counts)))}
+    if split_merge > 0:
+        st = (_C.c_int64 * 5)()
+        _capi.check(_capi.lib().bmm_last_alloc_split_merge_stats(st))
+        out["split_merge"] = dict(zip(_AS_FIELDS, (int(v) for v in st)))
     if pt is not None:
         out["partition"] = pt.result()
     if lj is not None:
@@ -2192,6 +2218,40 @@ class Chain:
         out = (_C.c_int64 * 4)()
         _capi.check(_capi.lib().bmm_chain_alloc_stats(self._h, out))
         return dict(zip(_EA_FIELDS, (int(v) for v in out)))
+
+    # -- split-merge moves of the allocation sampler (include/bmm_mcmc.h)
+    def set_alloc_split_merge(self, moves_per_sweep, scans=SPLIT_MERGE_SCANS):
+        """`moves_per_sweep` moves at the start of every sweep from the second, behind its eject / absorb moves (0: off;
+        the scans of the manual moves are still set), `scans` intermediate scans each.  An armed allocation chain only."""
+        _capi.check(_capi.lib().bmm_chain_set_alloc_split_merge(self._h, _C.c_int(int(moves_per_sweep)), _C.c_int(int(scans))))
+
+    def alloc_split_merge(self, n):
+        """n moves now, enqueued behind whatever the chain is doing."""
+        _capi.check(_capi.lib().bmm_chain_alloc_split_merge(self._h, _C.c_int(int(n))))
+
+    def alloc_split_merge_step(self, sides=False):
+        """One move, waited for; its diagnostics as a dict (labels 1-based, rows 0-based; "moved": the label a committed
+        merge moved into the gap, or -1).  `sides=True` adds "launch_side" and "proposal_side" as split_merge_step."""
+        s = _AllocSplitStep()
+        la = pr = None
+        if sides:
+            la, pr = _np.zeros(self.N, dtype=_np.uint8), _np.zeros(self.N, dtype=_np.uint8)
+            s.launch_side, s.proposal_side = la.ctypes.data, pr.ctypes.data
+        _capi.check(_capi.lib().bmm_chain_alloc_split_merge_step(self._h, _C.byref(s)))
+        out = {"rows": (int(s.row_i), int(s.row_j)), "labels": (int(s.label_a), int(s.label_b)),
+               "kind": ("split", "merge", "skipped")[s.kind], "accepted": bool(s.accepted), "k_before": int(s.k_before),
+               "k_after": int(s.k_after), "moved": int(s.moved), "members": int(s.members),
+               "n_before": (int(s.n_before[0]), int(s.n_before[1])), "n_after": (int(s.n_after[0]), int(s.n_after[1])),
+               "log_prior": s.log_prior, "log_lik": s.log_lik, "log_q": s.log_q, "log_u": s.log_u, "log_r": s.log_r,
+               "sweep": int(s.sweep), "move": int(s.move)}
+        if sides:
+            out["launch_side"], out["proposal_side"] = la, pr
+        return out
+
+    def alloc_split_merge_stats(self):
+        out = (_C.c_int64 * 5)()
+        _capi.check(_capi.lib().bmm_chain_alloc_split_merge_stats(self._h, out))
+        return dict(zip(_AS_FIELDS, (int(v) for v in out)))
 
     def set_labels(self, z1):
         """Replace the allocation of a seated DP chain between sweeps (1-based labels); Nk and S are recounted."""

@@ -41,6 +41,8 @@ SYMBOLS = [
     "bmm_chain_init_labels", "bmm_chain_get_init_centres", "bmm_chain_get_init_rows", "bmm_set_init", "bmm_last_init_info",
     "bmm_chain_set_alloc", "bmm_chain_set_k", "bmm_chain_get_k", "bmm_chain_alloc", "bmm_chain_alloc_step",
     "bmm_chain_alloc_stats", "bmm_alloc_run",
+    "bmm_chain_set_alloc_split_merge", "bmm_chain_alloc_split_merge", "bmm_chain_alloc_split_merge_step",
+    "bmm_chain_alloc_split_merge_stats", "bmm_set_alloc_split_merge", "bmm_last_alloc_split_merge_stats",
     "bmm_device_ecr", "bmm_device_ecr_plan", "bmm_set_ecr_relabel",
     "bmm_chain_set_logpost", "bmm_chain_logpost_state", "bmm_chain_sweeps_logpost", "bmm_chain_get_best",
     "bmm_chain_logpost_reset", "bmm_set_logpost", "bmm_device_log_joint",

@@ -64,6 +64,7 @@ enum : uint32_t {
     kStreamMissing = 15,   // the uniform of missing cell (i, j) behind sweep t: c0, c1 = the low and high word of i * P + j, c2 = t (na_uniform; t = 0: the starting fill)
     kStreamMissingA = 16,  // phi_kj ~ Beta of the imputation step of a counting chain: first gamma; c0 = k*P+j, c1 = block counter, c2 = sweep (na_phi)
     kStreamMissingB = 17,  // ... second gamma
+    kStreamAllocSplit = 18,  // a split-merge move of the allocation chain: c0 = move index, c1 = block counter, c2 = sweep (as_move_draws)
 };
 
 // ---------------------------------------------------------------- bit helpers
@@ -621,6 +622,35 @@ BMM_HD EaDraws ea_move_draws(uint64_t seed, uint32_t sweep, uint32_t move, int K
 BMM_HD double lbeta_(double x, double y) { return (lgamma_(x) + lgamma_(y)) - lgamma_(x + y); }
 BMM_HD double ea_log_q(double e, int64_t n1, int64_t n2) {
     return lbeta_(e + (double)n1, e + (double)n2) - lbeta_(e, e);
+}
+
+// The draws of split-merge move number `move` of the allocation chain ahead of sweep `sweep` (include/bmm_mcmc.h
+// "split-merge moves of the allocation sampler"): sm_move_draws on a stream of its own, so an armed chain's eject /
+// absorb moves and these share no (key, counter) pair.  The members' uniforms are sm_member_uniform under the salt.
+BMM_HD SmDraws as_move_draws(uint64_t seed, uint32_t sweep, uint32_t move, int64_t N) {
+    Stream st = make_stream(seed, move, sweep, kStreamAllocSplit);
+    const U4 r0 = st.next(), r1 = st.next();
+    SmDraws d;
+    d.i = (int64_t)(u01(r0.x, r0.y) * (double)N);
+    d.i = d.i > N - 1 ? N - 1 : d.i;
+    int64_t j = (int64_t)(u01(r0.z, r0.w) * (double)(N - 1));
+    j = j > N - 2 ? N - 2 : j;
+    d.j = j >= d.i ? j + 1 : j;
+    d.u = u01_open0(r1.x, r1.y);
+    d.salt = r1.z;
+    return d;
+}
+// The prior part of that move's log ratio on the lumped state (K, partition), written once: host and device add in this
+// order.  K is the number of open labels before the move, N the rows of the whole chain, lpk[k] = log p(K = k + 1).  A
+// split takes a block of n rows into n0 and n1 at K -> K + 1; a merge of blocks n0 and n1 into n at K -> K - 1 is the
+// exact negative of the split from K - 1.  log(Kl + 1) is the lumping factor (Kl + 1)! / (Kl - t)! over Kl! / (Kl - t)!.
+BMM_HD double as_log_prior(int K, double N, double a, const double* lpk, int64_t n, int64_t n0, int64_t n1, bool split) {
+    const int Kl = split ? K : K - 1;  // the smaller K
+    const double ka = (double)Kl * a, kb = (double)(Kl + 1) * a;
+    const double prior = ((((lpk[Kl] - lpk[Kl - 1]) + log_((double)(Kl + 1))) +
+                           ((lgamma_(kb) - lgamma_(kb + N)) - (lgamma_(ka) - lgamma_(ka + N)))) +
+                          ((lgamma_(a + (double)n0) + lgamma_(a + (double)n1)) - lgamma_(a + (double)n))) - lgamma_(a);
+    return split ? prior : -prior;
 }
 
 // Escobar & West auxiliary-variable update of the concentration (utils.cpp:6-14).

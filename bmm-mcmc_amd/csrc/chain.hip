@@ -619,6 +619,16 @@ struct bmm_chain {
     int ea_tag = -1;
     uint32_t ea_ctr = 0;
     SweepTrace k_rec;  // a run: one int32 per kept sweep, K after it
+    // split-merge moves of the allocation chain: as_moves > 0: that many moves at the start of
+    // every sweep from the second, behind its eject / absorb moves.  The side bytes, the log probabilities and the
+    // statistic sets are the split-merge buffers above (a DP chain's moves are refused on an armed chain); one block
+    // holds the move's cell and the five counters.
+    int as_moves = 0, as_scans = 0;
+    char* dAsBlock = nullptr;
+    AsCell* dAsCell = nullptr;
+    long long* dAsCounters = nullptr;
+    int as_tag = -1;
+    uint32_t as_ctr = 0;
     // log joint trace and keep-best allocation: one block holds the labels' values between the two
     // launches, the row of the last state scored and the keep-best cell; dLjZ the N labels of the best folded state
     // (0-based); lp_rec: the sweeps that are folded and the rows of four doubles they are recorded in
@@ -751,6 +761,7 @@ struct RunOptions {
     struct { bool on = false; bmm_pair_check_out o{}; std::vector<int32_t> feat; } pc;
     struct { bool on = false; const int64_t* rows = nullptr; const int32_t* cols = nullptr; int64_t n = 0; bmm_missing_out o{}; } na;
     struct { bool on = false; const double* log_prior_k = nullptr; int K0 = 0, moves = 0; double eject_a = 1.0; int32_t* k_out = nullptr; int64_t* moves_out = nullptr; } alloc;
+    struct { int moves = 0, scans = 0; } as;  // bmm_set_alloc_split_merge: taken by bmm_alloc_run alone
     const bmm_relabel_hooks* hooks = nullptr;  // *_run_probs
     const bmm_relabel_out* rel = nullptr;      // *_run_relabel
     const int32_t* Xnew = nullptr; int64_t M = 0; const bmm_predict_out* pred = nullptr;  // *_run_predict
@@ -762,6 +773,7 @@ thread_local RunOptions g_armed;
 RunOptions take_run_options() { return std::exchange(g_armed, RunOptions{}); }
 // ... and what the bmm_last_* getters read of the thread's last run
 thread_local int64_t g_sm_stats[5] = {0, 0, 0, 0, 0};
+thread_local int64_t g_as_stats[5] = {0, 0, 0, 0, 0};
 thread_local bmm_init_info g_init_info{};
 
 int planes_alloc(bmm_chain* c, size_t words) {
@@ -1505,6 +1517,34 @@ int enqueue_ea(bmm_chain* c, int32_t* z, int tag) {
     return BMM_OK;
 }
 
+// one split-merge move of the allocation chain on label row `z`, ahead of sweep `tag`, enqueued on the stream
+int enqueue_as(bmm_chain* c, int32_t* z, int tag, bool keep_launch) {
+    const ChainParams& p = c->p;
+    if (c->as_tag != tag) { c->as_tag = tag; c->as_ctr = 0; }
+    AsArgs g{};
+    SmArgs& a = g.s;
+    a.Xb = c->dXb; a.z = z; a.Nk = c->dNk; a.S = c->dS; a.alpha_ptr = c->dAlpha;
+    a.side = c->dSmSide; a.side_launch = keep_launch ? c->dSmSideLaunch : nullptr; a.lq = c->dSmLq;
+    a.stat = c->dSmStat; a.cell = &c->dAsCell->m; a.counters = c->dAsCounters;
+    a.sweep = (uint32_t)tag; a.move = c->as_ctr++; a.scans = c->as_scans;
+    g.K = c->dEaK; g.log_prior_k = c->dEaLogPrior; g.cell = c->dAsCell; g.a = c->alloc_a;
+    const size_t set_bytes = (size_t)2 * (p.P + 1) * sizeof(int32_t);
+    HIP_TRY(hipMemsetAsync(c->dSmStat, 0, (size_t)(c->as_scans + 2) * set_bytes, c->stream));
+    const unsigned grid = (unsigned)((p.N + kSmThreads - 1) / kSmThreads);
+    hipLaunchKernelGGL(k_as_launch, dim3(grid), dim3(kSmThreads), set_bytes, c->stream, p, g);
+    HIP_TRY(hipGetLastError());
+    const size_t scan_lds = (size_t)4 * p.P * sizeof(double) + set_bytes;
+    for (int t = 1; t <= c->as_scans + 1; ++t) {
+        hipLaunchKernelGGL(k_as_scan, dim3(grid), dim3(kSmThreads), scan_lds, c->stream, p, g, t, t == c->as_scans + 1 ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_as_decide, dim3(1), dim3(1024), 0, c->stream, p, g);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_as_commit, dim3(grid), dim3(kSmThreads), 0, c->stream, p, g);
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+
 // ---- feature selection ----
 // the gamma-step behind the end of sweep j, stream-ordered: no host wait
 int enqueue_fs_gamma(bmm_chain* c, int j) {
@@ -1736,14 +1776,15 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
         return rc == BMM_OK && c->na_on ? enqueue_na_step(c, j) : rc;
     }
     // the armed moves, ahead of the sweep's first table build: split-merge (a DP chain) or eject / absorb (a finite one)
-    const int n_sm = c->sm_moves, n_ea = c->alloc_on ? c->alloc_moves : 0;
-    if ((n_sm > 0 || n_ea > 0) && j >= 2 && phase == 0) {
+    const int n_sm = c->sm_moves, n_ea = c->alloc_on ? c->alloc_moves : 0, n_as = c->alloc_on ? c->as_moves : 0;
+    if ((n_sm > 0 || n_ea > 0 || n_as > 0) && j >= 2 && phase == 0) {
         int32_t* row = nullptr;
         int rc = moves_row(c, j, &row);
         if (rc) return rc;
         zin = row;
         for (int m = 0; m < n_sm && rc == BMM_OK; ++m) rc = enqueue_move(c, row, j, false);
         for (int m = 0; m < n_ea && rc == BMM_OK; ++m) rc = enqueue_ea(c, row, j);
+        for (int m = 0; m < n_as && rc == BMM_OK; ++m) rc = enqueue_as(c, row, j, false);  // (the allocation chain's split-merge moves)
         if (rc) return rc;
     }
     int64_t lo = 0;
@@ -2091,7 +2132,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     dev_pool().put(c->device, c->run_arena, c->run_arena_bytes);
     void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
                     c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch, c->dSmSide, c->dSmSideLaunch, c->dSmLq, c->dSmStat, c->dSmCell,
-                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock, c->dNaBlock};
+                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dAsBlock, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock, c->dNaBlock};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     chain_stream_release(c->device, c->stream, c->stream_kind);  // synchronised above
@@ -3783,8 +3824,117 @@ int bmm_chain_alloc_stats(bmm_chain* c, int64_t out[4]) {
     });
 }
 
+// ---- split-merge moves of the allocation chain ----
+// who may take them: an armed allocation chain (so whatever bmm_chain_set_alloc refuses stays refused) of two rows or more
+static int as_refused(const bmm_chain* c) {
+    int rc = alloc_refused(c);
+    if (rc) return rc;
+    if (!c->alloc_on) return set_err(BMM_E_STATE, "the allocation sampler is not armed (bmm_chain_set_alloc)");
+    if (c->p.P > kSmMaxP) return set_err(BMM_E_UNSUPPORTED, "split-merge moves are offered up to %d features", kSmMaxP);
+    if (c->p.N < 2) return set_err(BMM_E_ARG, "a split-merge move needs two rows");
+    return BMM_OK;
+}
+// the buffers of the moves, for `scans` intermediate scans
+static int as_setup(bmm_chain* c, int scans) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->dAsBlock) {
+        auto carve = [&](Carver& v) {
+            c->dAsCell = v.take<AsCell>(1);
+            c->dAsCounters = v.take<long long>(5);
+        };
+        Carver measure{nullptr};
+        carve(measure);
+        HIP_TRY(hipMalloc(&c->dAsBlock, measure.used));
+        Carver real{c->dAsBlock};
+        carve(real);
+        HIP_TRY(hipMemsetAsync(c->dAsBlock, 0, measure.used, c->stream));
+    }
+    const int rc = sm_setup(c, scans);  // the side bytes, the log probabilities and the statistic sets
+    if (rc) return rc;
+    c->as_scans = scans;
+    return BMM_OK;
+}
+static int as_ready(bmm_chain* c) {
+    int rc = as_refused(c);
+    if (rc) return rc;
+    if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+    rc = alloc_prepare(c);
+    if (rc == BMM_OK && (!c->dAsBlock || c->sm_sets < c->as_scans + 2)) rc = as_setup(c, c->as_scans);
+    return rc;
+}
+
+int bmm_chain_set_alloc_split_merge(bmm_chain* c, int moves_per_sweep, int scans) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (moves_per_sweep < 0 || scans < 0 || scans > 4096) return set_err(BMM_E_ARG, "moves_per_sweep and scans must be >= 0 (scans at most 4096)");
+        int rc = as_refused(c);
+        if (rc == BMM_OK) rc = as_setup(c, scans);
+        if (rc) return rc;
+        c->as_moves = moves_per_sweep;
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_alloc_split_merge(bmm_chain* c, int n) {
+    return guarded([&]() -> int {
+        if (n < 0) return set_err(BMM_E_ARG, "n must be >= 0");
+        int rc = as_ready(c);
+        if (rc) return rc;
+        for (int t = 0; t < n; ++t) {
+            rc = enqueue_as(c, label_row(c, c->sweep), c->sweep + 1, false);
+            if (rc) return rc;
+        }
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_alloc_split_merge_step(bmm_chain* c, bmm_alloc_split_step* out) {
+    return guarded([&]() -> int {
+        if (!out) return set_err(BMM_E_ARG, "null argument");
+        int rc = as_ready(c);
+        if (rc) return rc;
+        rc = enqueue_as(c, label_row(c, c->sweep), c->sweep + 1, true);
+        if (rc) return rc;
+        rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        AsCell h;
+        HIP_TRY(hipMemcpy(&h, c->dAsCell, sizeof h, hipMemcpyDeviceToHost));
+        out->row_i = h.m.row_i; out->row_j = h.m.row_j; out->label_a = h.m.label_a + 1; out->label_b = h.m.label_b + 1;
+        out->kind = h.m.kind; out->accepted = h.m.accepted; out->k_before = h.k_before; out->k_after = h.k_after;
+        out->moved = h.moved < 0 ? -1 : h.moved + 1; out->pad = 0; out->members = h.m.members;
+        for (int q = 0; q < 2; ++q) { out->n_before[q] = h.m.n_before[q]; out->n_after[q] = h.m.n_after[q]; }
+        out->log_prior = h.m.log_prior; out->log_lik = h.m.log_lik; out->log_q = h.m.log_q; out->log_u = h.m.log_u; out->log_r = h.m.log_r;
+        out->sweep = (uint32_t)(c->sweep + 1); out->move = c->as_ctr - 1;
+        const size_t n = (size_t)c->p.N;
+        if (h.m.kind == SM_SKIPPED) {  // no launch state: every row outside
+            if (out->launch_side) std::memset(out->launch_side, 255, n);
+            if (out->proposal_side) std::memset(out->proposal_side, 255, n);
+            return BMM_OK;
+        }
+        if (out->launch_side) HIP_TRY(hipMemcpy(out->launch_side, c->dSmSideLaunch, n, hipMemcpyDeviceToHost));
+        if (out->proposal_side) HIP_TRY(hipMemcpy(out->proposal_side, c->dSmSide, n, hipMemcpyDeviceToHost));
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_alloc_split_merge_stats(bmm_chain* c, int64_t out[5]) {
+    return guarded([&]() -> int {
+        if (!c || !out) return set_err(BMM_E_ARG, "null argument");
+        for (int q = 0; q < 5; ++q) out[q] = 0;
+        if (!c->dAsCounters) return BMM_OK;
+        int rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        long long h[5];
+        HIP_TRY(hipMemcpy(h, c->dAsCounters, sizeof h, hipMemcpyDeviceToHost));
+        for (int q = 0; q < 5; ++q) out[q] = h[q];
+        return BMM_OK;
+    });
+}
+
 // ... of a run (bmm_alloc_run): armed, K set (the labels above it empty), K recorded behind every kept sweep
 static int alloc_run_check(const RunOptions& o) {
+    if (!o.alloc.on && o.as.moves > 0)
+        return set_err(BMM_E_UNSUPPORTED, "split-merge moves of the allocation sampler are armed (bmm_set_alloc_split_merge): taken by bmm_alloc_run only");
     if (o.alloc.on && (o.predict() || o.loo.on || o.sm.moves > 0 || o.fs.on || o.init.kind != 0 || o.rel || o.hooks))
         return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is not offered together with relabelling, feature selection, split-merge moves, "
                        "the leave-one-out summary, newdata or a device start: they assume a fixed number of components");
@@ -3794,6 +3944,8 @@ static int alloc_run_attach(bmm_chain* c, const RunOptions& o, Recording& rec) {
     if (!o.alloc.on) return BMM_OK;
     int rc = bmm_chain_set_alloc(c, o.alloc.log_prior_k, o.alloc.moves, o.alloc.eject_a);
     if (rc == BMM_OK) rc = alloc_set_k(c, o.alloc.K0);
+    for (int64_t& v : g_as_stats) v = 0;
+    if (rc == BMM_OK && o.as.moves > 0) rc = bmm_chain_set_alloc_split_merge(c, o.as.moves, o.as.scans);
     if (rc) return rc;
     HIP_TRY(rec.rows.alloc((size_t)c->S * sizeof(int32_t)));
     const int32_t k0 = o.alloc.K0;
@@ -3807,7 +3959,8 @@ static int alloc_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, 
     if (rc) return rc;
     const hipError_t ec = hipMemcpy(o.alloc.k_out, rec.rows.p, (size_t)c->S * sizeof(int32_t), hipMemcpyDeviceToHost);
     if (ec != hipSuccess) return set_err(BMM_E_HIP, "copying the K trace failed: %s", hipGetErrorString(ec));
-    return o.alloc.moves_out ? bmm_chain_alloc_stats(c, o.alloc.moves_out) : BMM_OK;
+    rc = o.alloc.moves_out ? bmm_chain_alloc_stats(c, o.alloc.moves_out) : BMM_OK;
+    return rc == BMM_OK && o.as.moves > 0 ? bmm_chain_alloc_split_merge_stats(c, g_as_stats) : rc;
 }
 
 // ---- k-modes++ initial allocation ----
@@ -6200,6 +6353,17 @@ int bmm_set_init(int kind, int iters) {
 int bmm_last_init_info(bmm_init_info* info) {
     if (!info) return set_err(BMM_E_ARG, "null argument");
     *info = g_init_info;
+    return BMM_OK;
+}
+int bmm_set_alloc_split_merge(int moves_per_sweep, int scans) {
+    if (moves_per_sweep < 0 || scans < 0 || scans > 4096) return set_err(BMM_E_ARG, "moves_per_sweep and scans must be >= 0 (scans at most 4096)");
+    g_armed.as.moves = moves_per_sweep;
+    g_armed.as.scans = scans;
+    return BMM_OK;
+}
+int bmm_last_alloc_split_merge_stats(int64_t out[5]) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    for (int q = 0; q < 5; ++q) out[q] = g_as_stats[q];
     return BMM_OK;
 }
 int bmm_last_split_merge_stats(int64_t out[5]) {

@@ -4180,6 +4180,239 @@ __global__ __launch_bounds__(kEaThreads) void k_ea_commit(ChainParams p, EaArgs 
     if (tid == 0) *a.K = c->k_after;
 }
 
+// ---- split-merge moves of the allocation chain (include/bmm_mcmc.h "split-merge moves of the allocation sampler";
+// DESIGN.md section 24) ---------------------------------------------------------------------------------------------
+// The restricted scans of the DP move under the allocation sampler's target: k_as_launch, `scans` + 1 launches of
+// k_as_scan, k_as_decide, k_as_commit, stream-ordered; the host never reads anything back.  Side bytes, `stat` sets
+// and the final scan's log probabilities are those of the DP move, and the record begins with the DP move's, so the
+// scan is the DP scan's twin with the `+ a` weights (k_sm_scan itself is not touched: a shared body, tried first,
+// changed its scalar register allocation).  A split opens label K, the first closed one; a merge closes
+// label K - 1 after moving it into the label the merge freed, as an absorb does.
+struct AsCell {
+    SmCell m;
+    int32_t k_before, k_after, moved, pad;  // moved: the label a committed merge moved into the gap, or -1
+};
+struct AsArgs {
+    SmArgs s;                   // (alpha_ptr is not read; cell points at AsCell::m)
+    int32_t* K;                 // the number of open labels
+    const double* log_prior_k;  // [maxK]: log p(K = k + 1)
+    AsCell* cell;
+    double a;                   // the Dirichlet parameter per component
+};
+
+// The pair, the kind and the two labels from the K cell (every workgroup derives them; workgroup 0 records them), then
+// the launch state and set 0, as k_sm_launch.  A split at K == maxK is skipped.
+__global__ __launch_bounds__(kSmThreads) void k_as_launch(ChainParams p, AsArgs g) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int32_t* const hist = reinterpret_cast<int32_t*>(smem);
+    const SmArgs& a = g.s;
+    __shared__ int sh_la, sh_lb, sh_kind;
+    __shared__ long long sh_i, sh_j;
+    __shared__ uint32_t sh_salt;
+    const int P = p.P, tid = threadIdx.x, lane = tid & 63;
+    const int64_t N = p.N;
+    for (int i = tid; i < 2 * (P + 1); i += kSmThreads) hist[i] = 0;
+    if (tid == 0) {
+        const int K = *g.K;
+        const SmDraws dr = as_move_draws(p.seed, a.sweep, a.move, N);
+        const int la = a.z[dr.i], zj = a.z[dr.j];
+        const int kind = la != zj ? SM_MERGE : (K < p.K ? SM_SPLIT : SM_SKIPPED);
+        const int lb = kind == SM_MERGE ? zj : (kind == SM_SPLIT ? K : la);
+        sh_i = dr.i; sh_j = dr.j; sh_la = la; sh_lb = lb; sh_kind = kind; sh_salt = dr.salt;
+        if (blockIdx.x == 0) {
+            AsCell* const c = g.cell;
+            c->m.row_i = dr.i; c->m.row_j = dr.j; c->m.label_a = la; c->m.label_b = lb; c->m.kind = kind; c->m.salt = dr.salt;
+            c->m.pad = 0; c->m.accepted = 0; c->m.members = 0;
+            c->m.n_before[0] = a.Nk[la]; c->m.n_before[1] = kind == SM_MERGE ? a.Nk[lb] : 0;
+            c->m.n_after[0] = c->m.n_after[1] = 0;
+            c->m.log_u = log_(dr.u);
+            c->m.log_prior = c->m.log_lik = c->m.log_q = c->m.log_r = 0.0;
+            c->k_before = K; c->k_after = K; c->moved = -1; c->pad = 0;
+        }
+    }
+    __syncthreads();
+    const int kind = sh_kind, la = sh_la, lb = sh_lb;
+    if (kind == SM_SKIPPED) return;
+    const int64_t r = (int64_t)blockIdx.x * kSmThreads + tid;
+    int sd = kSmOut;
+    if (r < N) {
+        const int zr = a.z[r];
+        if (zr == la || (kind == SM_MERGE && zr == lb)) {
+            if (r == sh_i) sd = 2;
+            else if (r == sh_j) sd = 3;
+            else sd = sm_member_uniform(sh_salt, (uint64_t)(p.obs0 + r), 0u) < 0.5 ? 0 : 1;
+        }
+        a.side[r] = (uint8_t)sd;
+        if (a.side_launch) a.side_launch[r] = (uint8_t)sd;
+    }
+    sm_count_wave(sd != kSmOut, sd & 1, a.Xb, N, P, r, hist, lane);
+    __syncthreads();
+    sm_flush(hist, P, a.stat, tid);
+}
+
+// k_sm_scan with the allocation prior between the two sides, w_c = (n_c - [own] + a) prod_d (...): its twin, statement
+// for statement but for base[].  Whoever changes one changes the other.
+__global__ __launch_bounds__(kSmThreads) void k_as_scan(ChainParams p, AsArgs g, int t, int final) {
+    const SmArgs& a = g.s;
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    const int P = p.P, tid = threadIdx.x, lane = tid & 63;
+    const int64_t N = p.N;
+    double* const D = reinterpret_cast<double*>(smem);                // [P][2][2]
+    int32_t* const hist = reinterpret_cast<int32_t*>(D + 4 * (size_t)P);
+    __shared__ double base[2];
+    const int kind = a.cell->kind;
+    if (kind == SM_SKIPPED) return;
+    const bool score_only = final && kind == SM_MERGE;
+    const int64_t r = (int64_t)blockIdx.x * kSmThreads + tid;
+    const int sd = r < N ? a.side[r] : kSmOut;
+    const bool member = sd < 2, counted = sd != kSmOut;
+    if (final && r < N && !member) a.lq[r] = 0.0;
+    if (!__syncthreads_or(counted)) return;
+    const int32_t* const in = a.stat + (size_t)(t - 1) * sm_set(P);
+    const int32_t n0 = in[0], n1 = in[P + 1];
+    const double bg = p.beta + p.gamma;
+    for (int idx = tid; idx < 4 * P; idx += kSmThreads) {
+        const int d = idx >> 2, own = (idx >> 1) & 1, x = idx & 1;
+        const int32_t s0 = in[1 + d], s1 = in[P + 2 + d];
+        const int64_t nm = (own ? n1 : n0) - 1, sm = own ? s1 : s0, np = own ? n0 : n1, sp = own ? s0 : s1;
+        const double denm = log_(bg + (double)nm), denp = log_(bg + (double)np);
+        // (a member with x = 1 is one of the sm rows, one with x = 0 one of the nm + 1 - sm: the other entries are never read)
+        double m = 0.0;
+        if (x) { if (sm >= 1) m = term_x1(p.beta, sm - 1, denm); }
+        else if (sm <= nm) m = term_x0(p.gamma, nm, sm, denm);
+        const double pl = x ? term_x1(p.beta, sp, denp) : term_x0(p.gamma, np, sp, denp);
+        D[idx] = own ? pl - m : m - pl;
+    }
+    for (int i = tid; i < 2 * (P + 1); i += kSmThreads) hist[i] = 0;
+    if (tid < 2) base[tid] = log_((double)(n0 - (tid == 0)) + g.a) - log_((double)(n1 - (tid == 1)) + g.a);
+    __syncthreads();
+    int ns = sd & 1;
+    if (member) {
+        const int own = sd;
+        double acc = base[own];
+        const int W = (P + 31) >> 5;
+        for (int w = 0; w < W; ++w) {
+            const uint32_t bits = a.Xb[(int64_t)w * N + r];
+            const int nd = P - w * 32 < 32 ? P - w * 32 : 32;
+            for (int q = 0; q < nd; ++q) {
+                const double4 e = *reinterpret_cast<const double4*>(D + 4 * (size_t)(w * 32 + q));  // one address for the wave
+                const bool x = (bits >> q) & 1u;
+                acc = acc + (own ? (x ? e.w : e.z) : (x ? e.y : e.x));
+            }
+        }
+        double lp0, lp1;
+        sm_side_logp(acc, lp0, lp1);
+        if (score_only) {
+            a.lq[r] = a.z[r] == a.cell->label_a ? lp0 : lp1;
+        } else {
+            const double u = sm_member_uniform(a.cell->salt, (uint64_t)(p.obs0 + r), (uint32_t)t);
+            ns = u < exp_(lp0) ? 0 : 1;
+            a.side[r] = (uint8_t)ns;
+            if (final) a.lq[r] = ns ? lp1 : lp0;
+        }
+    }
+    if (score_only) return;
+    sm_count_wave(counted, ns, a.Xb, N, P, r, hist, lane);
+    __syncthreads();
+    sm_flush(hist, P, a.stat + (size_t)t * sm_set(P), tid);
+}
+
+// One workgroup: k_sm_decide's sums for log q and the marginal-likelihood ratio, term for term and in its order; the
+// prior ratio is the spec's as_log_prior.
+__global__ __launch_bounds__(1024) void k_as_decide(ChainParams p, AsArgs g) {
+    __shared__ double sh[2][1024];
+    const SmArgs& a = g.s;
+    const int t = threadIdx.x, P = p.P;
+    AsCell* const cell = g.cell;
+    SmCell* const c = &cell->m;
+    const int kind = c->kind;
+    if (kind == SM_SKIPPED) {
+        if (t == 0) a.counters[4] += 1;
+        return;
+    }
+    const int la = c->label_a, lb = c->label_b;
+    const int32_t* const fin = a.stat + (size_t)(a.scans + 1) * sm_set(P);
+    const bool split = kind == SM_SPLIT;
+    const int64_t no0 = a.Nk[la], no1 = split ? 0 : a.Nk[lb];
+    const int64_t nn0 = split ? fin[0] : no0 + no1, nn1 = split ? fin[P + 1] : 0;
+    double lq = 0.0, ll = 0.0;
+    for (int64_t i = t; i < p.N; i += 1024) lq = lq + a.lq[i];
+    for (int d = t; d < P; d += 1024) {
+        const int64_t so0 = a.S[(size_t)la * P + d], so1 = split ? 0 : a.S[(size_t)lb * P + d];
+        const int64_t sn0 = split ? fin[1 + d] : so0 + so1, sn1 = split ? fin[P + 2 + d] : 0;
+        double term;
+        if (split) term = (sm_pair(p.beta, p.gamma, nn0, sn0) + sm_pair(p.beta, p.gamma, nn1, sn1)) - sm_pair(p.beta, p.gamma, no0, so0);
+        else term = sm_pair(p.beta, p.gamma, nn0, sn0) - (sm_pair(p.beta, p.gamma, no0, so0) + sm_pair(p.beta, p.gamma, no1, so1));
+        ll = ll + term;
+    }
+    sh[0][t] = lq; sh[1][t] = ll;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if (t < s) { sh[0][t] = sh[0][t] + sh[0][t + s]; sh[1][t] = sh[1][t] + sh[1][t + s]; }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    const double bg = p.beta + p.gamma;
+    const double c0 = (lgamma_(bg) - lgamma_(p.beta)) - lgamma_(p.gamma);
+    const double log_q = sh[0][0];
+    double cst;
+    if (split) cst = ((c0 - lgamma_(bg + (double)nn0)) - lgamma_(bg + (double)nn1)) + lgamma_(bg + (double)no0);
+    else cst = ((lgamma_(bg + (double)no0) + lgamma_(bg + (double)no1)) - lgamma_(bg + (double)nn0)) - c0;
+    const int K = cell->k_before;
+    const double log_prior = split ? as_log_prior(K, (double)p.Ntot, g.a, g.log_prior_k, no0, nn0, nn1, true)
+                                   : as_log_prior(K, (double)p.Ntot, g.a, g.log_prior_k, nn0, no0, no1, false);
+    const double log_lik = sh[1][0] + (double)P * cst;
+    const double log_r = split ? (log_prior + log_lik) - log_q : (log_prior + log_lik) + log_q;
+    const int acc = c->log_u < log_r ? 1 : 0;
+    c->log_prior = log_prior; c->log_lik = log_lik; c->log_q = log_q; c->log_r = log_r; c->accepted = acc;
+    c->n_after[0] = nn0; c->n_after[1] = nn1;
+    const int32_t* const first = a.stat;
+    c->members = (long long)first[0] + first[P + 1] - 2;
+    cell->k_after = acc ? (split ? K + 1 : K - 1) : K;
+    cell->moved = acc && !split && lb != K - 1 ? K - 1 : -1;
+    a.counters[split ? 0 : 2] += 1;
+    if (acc) a.counters[split ? 1 : 3] += 1;
+}
+
+// An accepted move.  Every workgroup relabels its own rows from the record alone: a split gives the rows of side 1
+// label K; a merge gives the rows of lb label la and then, as an absorb, the rows of label K - 1 the freed label lb
+// (with la == K - 1 the merged component ends up under lb).  Workgroup 0 writes the exact integer statistics of the
+// labels touched and the K cell, which no other workgroup reads.  A rejected or skipped move: nothing.
+__global__ __launch_bounds__(kSmThreads) void k_as_commit(ChainParams p, AsArgs g) {
+    const AsCell* const cell = g.cell;
+    const SmCell* const c = &cell->m;
+    if (!c->accepted) return;
+    const SmArgs& a = g.s;
+    const int P = p.P, tid = threadIdx.x, la = c->label_a, lb = c->label_b, last = cell->k_before - 1;
+    const bool split = c->kind == SM_SPLIT;
+    const int64_t r = (int64_t)blockIdx.x * kSmThreads + tid;
+    if (r < p.N) {
+        if (split) {
+            const int sd = a.side[r];
+            if (sd == 1 || sd == 3) a.z[r] = lb;
+        } else {
+            const int zr = a.z[r];
+            if (zr == lb) a.z[r] = (la == last && lb != last) ? lb : la;
+            else if (zr == last && lb != last) a.z[r] = lb;
+        }
+    }
+    if (blockIdx.x != 0) return;
+    const int32_t* const fin = a.stat + (size_t)(a.scans + 1) * sm_set(P);
+    for (int idx = tid; idx <= P; idx += kSmThreads) {
+        int32_t* const A = idx == 0 ? a.Nk + la : a.S + (size_t)la * P + (idx - 1);
+        int32_t* const B = idx == 0 ? a.Nk + lb : a.S + (size_t)lb * P + (idx - 1);
+        if (split) {
+            *A = fin[idx]; *B = fin[P + 1 + idx];
+        } else {  // in this order: la may be the last label
+            int32_t* const Z = idx == 0 ? a.Nk + last : a.S + (size_t)last * P + (idx - 1);
+            const int32_t s = *A + *B;
+            *A = s; *B = 0;
+            if (lb != last) { *B = *Z; *Z = 0; }
+        }
+    }
+    if (tid == 0) *g.K = cell->k_after;
+}
+
 // ---- ECR relabelling from the label trace alone (include/bmm_mcmc.h "ECR") -----------------
 // Label rows as the partition kernels hold them: 0-based, row t at lab + t * pitch, either the resident int32 trace
 // (pitch = N; -1 = unassigned, skipped everywhere) or the one-byte block k_pt_narrow makes of host input.  The pivot

@@ -885,6 +885,63 @@ int bmm_alloc_run(const int32_t* X, int64_t N, int P, const int32_t* initialK, i
                   int burnin, int64_t batch, uint64_t seed, int device, int32_t* z_out, double* theta_out,
                   int32_t* k_out, int64_t moves_out[4]);
 
+/* ---- split-merge moves of the allocation sampler ---------------------------------------------
+ * Eject / absorb cuts a component by a coin per row; at large N such a cut is never accepted (section 18).  These moves
+ * propose the cut along the data, by the restricted scans of the DP chain's split-merge move above, under the allocation
+ * sampler's target.  A split opens component K + 1, a merge closes one; the number of empty open components does not
+ * change.  The state is (K, z) as above; on the lumped state (K, partition rho with t non-empty blocks) the target is
+ *   pi(K, rho) = p(K) K! / (K - t)! Gamma(K a) / Gamma(K a + N) prod_c Gamma(a + n_c) / Gamma(a) prod_c m(x_c).
+ * THE MOVE, number m ahead of sweep j (tests/alloc_split_ref.py restates it in NumPy):
+ *   1. an ordered pair of distinct rows (i, j), the accept uniform and a salt as the DP move draws them, from stream 18.
+ *   2. z_i == z_j: a split of that block, la = z_i, lb = K, the first closed label; SKIPPED (and counted) when K == maxK.
+ *      z_i != z_j: a merge of la = z_i and lb = z_j.
+ *   3. launch state, `scans` intermediate restricted scans and the final scan as steps 4 to 7 of the DP move, with the
+ *      prior of the allocation model between the two sides: w_c = (n_c - [own] + a) prod_d (predictive of side c without
+ *      the row).  log q as there.
+ *   4. split of n into n0 (stays la, holds i) and n1 (takes label K, holds j), K -> K + 1:
+ *        log_prior = log p(K+1) - log p(K) + log(K + 1)
+ *                    + [lgamma((K+1)a) - lgamma((K+1)a + N)] - [lgamma(K a) - lgamma(K a + N)]
+ *                    + lgamma(a + n0) + lgamma(a + n1) - lgamma(a + n) - lgamma(a)      (as_log_prior of bmm_spec.h),
+ *        log_lik the DP move's, log r = log_prior + log_lik - log q.  log(K + 1) is the lumping factor
+ *        (K+1)! / (K-t)! over K! / (K-t)!: it is not in the labelled log pi(K, z).
+ *      merge at K -> K - 1: the exact negative of the split from K - 1 with the roles swapped,
+ *        log r = log_prior + log_lik + log q.
+ *   5. accept iff log u < log r.  A split gives the rows of side 1 label K and sets Nk, S of both labels to their exact
+ *      integer values; a merge gives the rows of lb label la, adds the statistics and then, as an absorb, moves label
+ *      K - 1 into lb (rows, Nk, S) unless lb == K - 1.  K is written on the device.
+ * The moves sit behind the sweep's eject / absorb moves and ahead of its first table build.  One seed gives the same bits
+ * twice; the sums run in the DP move's fixed orders.  Refused: whatever bmm_chain_set_alloc refuses, a chain that is not
+ * armed with BMM_E_STATE, N < 2 with BMM_E_ARG.  bmm_chain_set_split_merge stays refused on an armed chain, and
+ * bmm_set_split_merge ahead of bmm_alloc_run. */
+typedef struct bmm_alloc_split_step {
+    int64_t row_i, row_j;      /* 0-based */
+    int32_t label_a, label_b;  /* 1-based: la and lb (a split: lb = K + 1, the label opened) */
+    int32_t kind;              /* BMM_SM_* */
+    int32_t accepted;
+    int32_t k_before, k_after;
+    int32_t moved, pad;        /* 1-based: the label a committed merge moved into the gap, or -1 */
+    int64_t members;
+    int64_t n_before[2];       /* sizes of the two labels before the move (split: n, 0) */
+    int64_t n_after[2];        /* ... as proposed (split: n0, n1; merge: n_a + n_b, 0) */
+    double log_prior, log_lik, log_q, log_u, log_r;
+    uint32_t sweep, move;      /* what keyed the move's streams */
+    uint8_t* launch_side;      /* in: room for N side bytes (BMM_SM_OUTSIDE ...), or NULL; the launch state */
+    uint8_t* proposal_side;    /* in: the same; the state the final scan drew (split) or scored from (merge) */
+} bmm_alloc_split_step;
+/* moves_per_sweep moves at the start of every sweep from the second, behind its eject / absorb moves; 0 turns them off
+ * (and still sets the scans of the moves below).  A chain with none armed enqueues what it always did. */
+int bmm_chain_set_alloc_split_merge(bmm_chain* c, int moves_per_sweep, int scans);
+/* n moves now, with the scans last set (returns without waiting) */
+int bmm_chain_alloc_split_merge(bmm_chain* c, int n);
+/* one move, then waits; fills *out (set launch_side / proposal_side first) */
+int bmm_chain_alloc_split_merge_step(bmm_chain* c, bmm_alloc_split_step* out);
+/* proposed splits, accepted splits, proposed merges, accepted merges, skipped.  Waits. */
+int bmm_chain_alloc_split_merge_stats(bmm_chain* c, int64_t out[5]);
+/* For a run: armed per calling thread for the NEXT bmm_alloc_run of that thread and disarmed when it returns; any other
+ * run answers it with BMM_E_UNSUPPORTED.  The run's five counts are read with bmm_last_alloc_split_merge_stats. */
+int bmm_set_alloc_split_merge(int moves_per_sweep, int scans);
+int bmm_last_alloc_split_merge_stats(int64_t out[5]);
+
 /* ---- label-switching correction from the label trace alone: ECR ------------------------------
  * Equivalence Classes Representatives (Papastamoulis & Iliopoulos 2010) and its pivot-free iterative form
  * ECR-ITERATIVE-1 (Rodriguez & Walker 2014; Papastamoulis 2016): every kept sweep gets the permutation of its labels
