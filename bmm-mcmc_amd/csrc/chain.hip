@@ -361,6 +361,7 @@ struct KernelForm {
     int gw = kGroupW;   // the shape's group width (bmm_spec.h)
     bool self = false;  // workgroups that build their own table image (SELF)
     bool pk = false;    // k_resample_pk: scores from the packed binary32 image, the definition for the uncertain few
+    bool pipe = false;  // ... its pipelined body: a chunk is drawn while the next one is scored (pk_pipelined, kernels.hip.h)
 };
 constexpr int tile_of(const KernelForm& f) { return f.nt / f.lanes; }  // observations per tile
 constexpr KernelForm resized(KernelForm f, int nt, int lanes = 1) { f.nt = nt; f.lanes = lanes; return f; }
@@ -420,9 +421,14 @@ resample_fn instance() {
 resample_fn lookup(const KernelForm& f, bool named_size = false) {
     resample_fn fn = nullptr;
     if (f.pk) {
-        if (!instantiated(f, named_size)) return nullptr;
+        if (!instantiated(f, named_size) || (f.pipe && !pk_pipelined(f.kt, f.nt, f.gw))) return nullptr;
         lift([&](auto kt, auto nt, auto gw) {
-            if constexpr (instantiated(KernelForm{kt, nt, 1, true, 1, false, gw, false, true}, false)) fn = k_resample_pk<kt, nt, gw>;
+            if constexpr (instantiated(KernelForm{kt, nt, 1, true, 1, false, gw, false, true}, false)) {
+                // the present body of every form; the pipelined one of the forms that take it (BMM_DEBUG_PK_NOPIPE
+                // runs the present body where the pipelined one would run)
+                fn = k_resample_pk<kt, nt, gw, false>;
+                if constexpr (pk_pipelined(kt, nt, gw)) if (f.pipe) fn = k_resample_pk<kt, nt, gw, true>;
+            }
         }, kKT, f.kt, IntList<1024, 768, 512, 256>{}, f.nt, IntList<kGroupW, kGroupWAlt>{}, f.gw);
         return fn;
     }
@@ -850,6 +856,7 @@ struct DebugSwitches {
     bool noself = dbg_env("BMM_DEBUG_NOSELF");          // no table-building workgroups
     bool nopk = dbg_env("BMM_DEBUG_NOPK");              // k_resample where k_resample_pk would run (A/B in one library)
     bool pk = dbg_env("BMM_DEBUG_PK");                  // k_resample_pk whatever the length of a launch
+    bool nopipe = dbg_env("BMM_DEBUG_PK_NOPIPE");       // k_resample_pk's present body where the pipelined one would run
     // n >= 1: k_resample_pk treats a lane whose observation index is a multiple of n as uncertain, so that certain and
     // settled lanes share a wave (tests/test_gpu_pk_inline.py).  BMM_DEBUG_PK_QUEUE is still accepted and does nothing:
     // the queue it sized is gone
@@ -1079,7 +1086,7 @@ int chain_alloc(bmm_chain* c) {
         c->dDS = a.take<int32_t>(ns * kDeltaReps);
         c->dTab = a.take<double>(ntab);
 #ifdef BMM_DIAG
-        c->dDiag = a.take<unsigned long long>(16);
+        c->dDiag = a.take<unsigned long long>(18);
 #endif
         c->dSelfDone = a.take<int>(1);
         c->dViable = a.take<int>(1);
@@ -1844,6 +1851,7 @@ KernelPlan plan_kernel(const ChainParams& p, bool bits, int minus, int64_t batch
     auto offer = [&](KernelForm g, size_t lds) {
         KernelForm h = g;
         h.pk = true;
+        h.pipe = pk_pipelined(h.kt, h.nt, h.gw) && !d.nopipe;
 #ifdef BMM_EXP_PK_ALWAYS  // timing experiments only (tools/exp_lib.sh): the rule below lifted, as BMM_DEBUG_PK lifts it
         const bool long_launch = true;
 #else
@@ -2105,7 +2113,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
 #ifdef BMM_DIAG
     if (c->dDiag) {
-        unsigned long long d[16] = {};
+        unsigned long long d[18] = {};
         const bool ok = hipMemcpy(d, c->dDiag, sizeof d, hipMemcpyDeviceToHost) == hipSuccess;
         if (ok && d[5] && d[0]) {  // (k_resample_pk stamps the launch phases only)
             const double tot = (double)(d[0] + d[1] + d[2] + d[3] + d[4]);
@@ -2118,6 +2126,9 @@ void bmm_chain_destroy(bmm_chain* c) {
                     d[8] / (double)d[5], d[9] / (double)d[5], d[10] / (double)d[5], d[11] / (double)d[5]);
         if (ok && d[7])  // k_resample_pk: wave 0 of each workgroup, slots of its own
             fprintf(stderr, "[bmm diag launch pk] workgroup-launches %llu, ticks from entry to flushed %.0f\n", d[7], d[14] / (double)d[7]);
+        if (ok && d[7] && d[17])  // ... and wave 0's trips: between the first and the last lookup of a trip, and the rest of the loop
+            fprintf(stderr, "[bmm diag trip pk] trips of wave 0: %llu, ticks per trip: scoring %.0f, outside it %.0f\n", d[17],
+                    d[16] / (double)d[17], ((double)d[9] - (double)d[16]) / (double)d[17]);
         if (ok && d[5] && d[12])
             fprintf(stderr, "[bmm diag draw] draws of a wave (64 observations) %llu, of them by the binary64 definition %llu (%.4f%%)\n",
                     d[12], d[13], 100.0 * (double)d[13] / (double)d[12]);
@@ -5770,6 +5781,8 @@ static void kernel_key(const KernelForm& f, const KernelForm& twin, bool generic
 // ... whether that kernel is the packed one (k_resample_pk; the key's ten slots describe the form it stands in for),
 // and what its launches have counted so far: observations drawn, observations deferred to the binary64 definition
 extern "C" int bmm_dbg_kernel_packed(const bmm_chain* c) { return c && !c->generic && c->form.pk ? 1 : 0; }
+// ... and whether it runs the pipelined body (tests/test_gpu_pk_pipe.py)
+extern "C" int bmm_dbg_kernel_pk_pipelined(const bmm_chain* c) { return c && !c->generic && c->form.pk && c->form.pipe ? 1 : 0; }
 extern "C" int bmm_dbg_pk_counts(bmm_chain* c, unsigned long long* draws, unsigned long long* deferred) {
     if (!c || !draws || !deferred) return set_err(BMM_E_ARG, "null argument");
     return guarded([&]() -> int {

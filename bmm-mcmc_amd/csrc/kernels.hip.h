@@ -1342,6 +1342,9 @@ __global__ __launch_bounds__(NT) void k_resample(ChainParams p, ResampleArgs a) 
 // unlikely, which keeps the register allocator's spills inside them.  An observation is a 32-bit offset from the
 // launch's first (PkPos), the draw works on pairs (pk_draw2), and the Philox key is a scalar wherever the launch's
 // indices allow (pk_uniform).  Instruction counts before and after: profiles/r09/README.md.
+// PIPE: the second loop body, which the 1024-thread forms of up to 20 accumulators run (pk_pipelined): a trip scores
+// chunk i and draws chunk i - 1 in the same straight-line code (pk_rounds), everything behind the draw a trip late.
+// The present body is the other branch, unchanged, and every other form's.  profiles/r10/README.md.
 // LDS, in doubles: Tq [G][KT/2][M] pairs | Tm32 [G][KT][M] binary32 (the two as they lie behind the table image in
 // global memory) | Nk, E (as they lie in the image) | histogram, chunk counter | kPkQueue words that nothing uses
 // (pk_image_bytes, chain.hip).  The binary64 Tm is not staged.
@@ -1395,14 +1398,15 @@ __device__ __forceinline__ double pk_bcast(double x, int j) {
 // each lane's value broadcast by v_readlane (pk_bcast).
 // Every operation and its order are k_resample's.  Returns the count of the draw (the DP's new-cluster option is K:
 // the caller keeps the books), or the label to keep where every category is impossible.
-template <int KT, int GW>
+template <int KT, int GW, int GRMAX = 20>
 __device__ __forceinline__ int pk_exact_count(const ChainParams& p, const ResampleArgs& a, const TableLayout& L,
                                               uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, int zo, double u,
                                               const lds_f64* ET, int lane) {
     constexpr int GM = 1 << GW;
     // loads in flight, two VGPRs each, sized so that no form holds fewer waves per SIMD by registers than it did with
     // the pass behind the loop: the forms of up to 8 accumulators have few registers to spare (profiles/r08/README.md)
-    constexpr int GR = KT <= 4 ? 6 : KT <= 8 ? 10 : 20;
+    // (GRMAX: the pipelined body, which holds a second chunk's scores across the definition, asks for fewer)
+    constexpr int GR0 = KT <= 4 ? 6 : KT <= 8 ? 10 : 20, GR = GR0 < GRMAX ? GR0 : GRMAX;
     static_assert((kMaxP + GW - 1) / GW <= 64, "lane g holds the field of group g");
     const int G = p.G;
     const int zoc = zo < 0 ? 0 : zo;
@@ -1519,6 +1523,25 @@ __device__ __forceinline__ void pk_load_words(const uint32_t* Xb, int64_t N, int
     if (W > 3) w3 = *pk_at(b + 3 * N, t.loff);
 }
 
+// The draw's arithmetic, by pair of scores, written once: pk_draw2 runs the slices in order, the pipelined body places
+// them among its group steps.  Pair j of the first loop: the scores of the pair become its two running sums, in place
+__device__ __forceinline__ void pk_exp_slice(pk_f2& sc, float m, float& run) {
+    const pk_f2 mm{m, m}, l2e{0x1.715476p+0f, 0x1.715476p+0f};
+    const pk_f2 x = (sc - mm) * l2e;
+    run = run + __builtin_amdgcn_exp2f(x.x);
+    sc.x = run;
+    run = run + __builtin_amdgcn_exp2f(x.y);
+    sc.y = run;
+}
+// pair j of its second loop
+__device__ __forceinline__ void pk_cmp_slice(const pk_f2& c, float t, int& n, float& nearest) {
+    const pk_f2 tt{t, t};
+    const pk_f2 diff = tt - c;
+    n += diff.x >= 0.0f ? 1 : 0;
+    nearest = __builtin_fminf(nearest, __builtin_fabsf(diff.x));
+    n += diff.y >= 0.0f ? 1 : 0;
+    nearest = __builtin_fminf(nearest, __builtin_fabsf(diff.y));
+}
 // draw_pk (bmm_spec.h) on scores held in pairs: s - m, the scaling by log2(e) and t - c[k] as packed binary32
 // operations, each component rounded as the scalar instruction rounds it (same mode register), the running sum in the
 // same order: cnt and the verdict are draw_pk's bit for bit (tests/test_gpu_pk_lean.py runs the two side by side).
@@ -1527,29 +1550,18 @@ template <int KT>
 __device__ __forceinline__ bool pk_draw2(const pk_f2 (&s2)[KT / 2], float m, double u, int G, float unit, int& cnt) {
     static_assert(KT % 2 == 0 && KT <= kTier1MaxCats, "the band is derived for at most kTier1MaxCats categories");
     constexpr int KP = KT / 2;
-    const pk_f2 mm{m, m}, l2e{0x1.715476p+0f, 0x1.715476p+0f};
     pk_f2 c[KP];
     float run = 0.0f;
 #pragma unroll
     for (int j = 0; j < KP; ++j) {
-        const pk_f2 x = (s2[j] - mm) * l2e;  // sub, then mul: no fma (-ffp-contract=off, and the band's derivation)
-        run = run + __builtin_amdgcn_exp2f(x.x);
-        c[j].x = run;
-        run = run + __builtin_amdgcn_exp2f(x.y);
-        c[j].y = run;
+        c[j] = s2[j];
+        pk_exp_slice(c[j], m, run);  // sub, then mul: no fma (-ffp-contract=off, and the band's derivation)
     }
     const float t = (float)u * run;
-    const pk_f2 tt{t, t};
     float nearest = __builtin_inff();
     int n = 0;
 #pragma unroll
-    for (int j = 0; j < KP; ++j) {
-        const pk_f2 diff = tt - c[j];
-        n += diff.x >= 0.0f ? 1 : 0;
-        nearest = __builtin_fminf(nearest, __builtin_fabsf(diff.x));
-        n += diff.y >= 0.0f ? 1 : 0;
-        nearest = __builtin_fminf(nearest, __builtin_fabsf(diff.y));
-    }
+    for (int j = 0; j < KP; ++j) pk_cmp_slice(c[j], t, n, nearest);
     cnt = n;
     return nearest > pk_band(m, G, unit) * run && m > -__builtin_inff() && m < __builtin_inff();
 }
@@ -1572,7 +1584,235 @@ __device__ __forceinline__ double pk_uniform(uint64_t seed, uint64_t i0, uint32_
     return u52(ra, rb);
 }
 
-template <int KT, int NT, int GW>
+// ---- the pipelined body's pieces (k_resample_pk<.., PIPE = true>): pk_draw2 cut into slices by pair index, and one
+// group step at a compile-time group
+template <int I>
+struct PkIdx { static constexpr int value = I; };
+template <int I, int N, class F>
+__device__ __forceinline__ void pk_static_for(F&& f) {
+    if constexpr (I < N) {
+        f(PkIdx<I>{});
+        pk_static_for<I + 1, N>(f);
+    }
+}
+// The lookups of group g, g known at compile time: the field is one v_bfe_u32 (or one v_alignbit_b32 and a mask
+// where it crosses a word), the group's rows are instruction offsets.  `fill` runs behind the first reads and ahead
+// of the adds that need them: work that does not depend on the reads, placed in the shadow of their round trip.
+template <int KT, int GW, int g, class Fill>
+__device__ __forceinline__ void pk_step(const volatile lds_pk_f2* Tq, const volatile lds_f32* orow0, uint32_t b0,
+                                        uint32_t b1, uint32_t b2, uint32_t b3, pk_f2 (&acc)[KT / 2], float& own32,
+                                        Fill&& fill) {
+    constexpr int GM = 1 << GW, KP = KT / 2, CH = KP <= 12 ? KP : KP / 2;
+    constexpr int bit = g * GW, wd = bit >> 5, sh = bit & 31;
+    static_assert(bit < kMaxP, "a group of the pattern");
+    const uint32_t lo = wd == 0 ? b0 : (wd == 1 ? b1 : (wd == 2 ? b2 : b3));
+    const uint32_t hi = wd == 0 ? b1 : (wd == 1 ? b2 : (wd == 2 ? b3 : 0u));
+    const unsigned nib = (sh + GW <= 32 ? lo >> sh : __builtin_amdgcn_alignbit(hi, lo, (unsigned)sh)) & (unsigned)(GM - 1);
+    const volatile lds_pk_f2* row = Tq + ((size_t)g * KP * GM + nib);
+    const volatile lds_f32* orow = orow0 + ((size_t)g * KT * GM + nib);
+#pragma unroll
+    for (int c0 = 0; c0 < KP; c0 += CH) {
+        pk_f2 tv[CH];
+        float ov = 0.0f;
+#pragma unroll
+        for (int j = 0; j < CH; ++j) tv[j] = row[(c0 + j) * GM];
+        if (c0 == 0) ov = *orow;
+        if (c0 == 0) fill();
+#pragma unroll
+        for (int j = 0; j < CH; ++j) acc[c0 + j] = acc[c0 + j] + tv[j];
+        if (c0 == 0) own32 = own32 + ov;
+        if (CH < KP) __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// Behind an unrolled step: its sums exist here (the optimiser otherwise sinks the adds of several steps below the reads
+// of the steps behind them and holds every read value until then), and the next step's reads stay behind them.  One
+// statement for all the sums of a step (an inline asm takes up to 30 operands: 14 in-out pairs), so that the adds ahead
+// of it are placed freely among themselves and the step's slice.
+#define BMM_PK_PIN2(a, i) "+v"(a[i]), "+v"(a[(i) + 1])
+template <int KT>
+__device__ __forceinline__ void pk_step_end(pk_f2 (&acc)[KT / 2]) {
+    constexpr int KP = KT / 2;
+    static_assert(KP % 2 == 0 && KP <= 16, "pairs of sums");
+    if constexpr (KP == 2) asm volatile("" : BMM_PK_PIN2(acc, 0));
+    if constexpr (KP == 4) asm volatile("" : BMM_PK_PIN2(acc, 0), BMM_PK_PIN2(acc, 2));
+    if constexpr (KP == 6) asm volatile("" : BMM_PK_PIN2(acc, 0), BMM_PK_PIN2(acc, 2), BMM_PK_PIN2(acc, 4));
+    if constexpr (KP >= 8) asm volatile("" : BMM_PK_PIN2(acc, 0), BMM_PK_PIN2(acc, 2), BMM_PK_PIN2(acc, 4), BMM_PK_PIN2(acc, 6));
+    if constexpr (KP == 10) asm volatile("" : BMM_PK_PIN2(acc, 8));
+    if constexpr (KP == 12) asm volatile("" : BMM_PK_PIN2(acc, 8), BMM_PK_PIN2(acc, 10));
+    if constexpr (KP == 14) asm volatile("" : BMM_PK_PIN2(acc, 8), BMM_PK_PIN2(acc, 10), BMM_PK_PIN2(acc, 12));
+    if constexpr (KP == 16) asm volatile("" : BMM_PK_PIN2(acc, 8), BMM_PK_PIN2(acc, 10), BMM_PK_PIN2(acc, 12), BMM_PK_PIN2(acc, 14));
+    __builtin_amdgcn_sched_barrier(0);
+}
+#undef BMM_PK_PIN2
+// Groups [g_from, g_to) of a chunk in the rolled form of the present body: the word loop, the field by a runtime shift.
+// A second copy of the group loop in k_resample_pk's present body (the `for (int h = 0; h < W; ++h)` under "scoring"),
+// which stays inline there because calling this one cost that body four more spilled scalars at C5's form: a change to
+// either belongs in both.
+template <int KT, int GW>
+__device__ __forceinline__ void pk_groups(const volatile lds_pk_f2* Tq, const volatile lds_f32* orow0, int g_from, int g_to,
+                                          int W, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3, pk_f2 (&acc)[KT / 2],
+                                          float& own32) {
+    constexpr int GM = 1 << GW, KP = KT / 2, CH = KP <= 12 ? KP : KP / 2;
+#pragma unroll 1
+    for (int h = (g_from * GW) >> 5; h < W; ++h) {
+        const uint32_t cur = word_of(h, b0, b1, b2, b3), nxt = word_of(h + 1, b0, b1, b2, b3);
+        int g_lo = (32 * h + GW - 1) / GW;
+        g_lo = g_lo > g_from ? g_lo : g_from;
+        int g_hi = (32 * (h + 1) + GW - 1) / GW;
+        g_hi = g_hi < g_to ? g_hi : g_to;
+#pragma unroll 1
+        for (int g = g_lo; g < g_hi; ++g) {
+            const unsigned nib = __builtin_amdgcn_alignbit(nxt, cur, (unsigned)(g * GW - 32 * h)) & (unsigned)(GM - 1);
+            const volatile lds_pk_f2* row = Tq + ((size_t)g * KP * GM + nib);
+            const volatile lds_f32* orow = orow0 + ((size_t)g * KT * GM + nib);
+#pragma unroll
+            for (int c0 = 0; c0 < KP; c0 += CH) {
+                pk_f2 tv[CH];
+                float ov = 0.0f;
+#pragma unroll
+                for (int j = 0; j < CH; ++j) tv[j] = row[(c0 + j) * GM];
+                if (c0 == 0) ov = *orow;
+#pragma unroll
+                for (int j = 0; j < CH; ++j) acc[c0 + j] = acc[c0 + j] + tv[j];
+                if (c0 == 0) own32 = own32 + ov;
+                if (CH < KP) __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+}
+// The scoring of one chunk with the packed draw of the chunk before it cut into its group steps (DRAW).  The groups
+// are taken in rounds of KT/2.  A first round that is whole (G >= KT/2) is straight-line code, its groups known at
+// compile time, and step j carries pair j's exponents and running sums in the shadow of its reads; a second round that
+// is whole carries the compares the same way.  A round that is not whole runs the rolled loop and its slices follow
+// it; so do the groups from the third round on.  (A guard per step was tried first: the compiler either held a mask
+// per step in scalar registers across the tile loop or, with early exits, gave the accumulators new registers at every
+// step and spilled them -- profiles/r10/README.md.)  `head` runs in the shadow of group 0's reads.  c: the scores of
+// the previous chunk on entry (own-cluster substitution done, m their maximum), its running sums on return; run, cnt,
+// nearest as pk_draw2 leaves them.  G is tested on an opaque copy, where it is used.
+template <int KT, int GW, bool DRAW, class Head>
+__device__ __forceinline__ void pk_rounds(const volatile lds_pk_f2* Tq, const volatile lds_f32* orow0, int G, int W,
+                                          uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3, pk_f2 (&acc)[KT / 2],
+                                          float& own32, pk_f2 (&c)[KT / 2], float m, const double& u, float& run, int& cnt,
+                                          float& nearest, Head&& head) {
+    constexpr int KP = KT / 2;
+    constexpr bool kRound0 = (KP - 1) * GW < kMaxP, kRound1 = (2 * KP - 1) * GW < kMaxP;  // such a G exists
+    asm volatile("" : "+s"(G));
+    bool whole = false;
+    if constexpr (kRound0) whole = G >= KP;
+    if (whole) {
+        if constexpr (kRound0)
+            pk_static_for<0, KP>([&](auto J) {
+                constexpr int j = decltype(J)::value;
+                pk_step<KT, GW, j>(Tq, orow0, b0, b1, b2, b3, acc, own32, [&] {
+                    if constexpr (j == 0) head();
+                    if constexpr (DRAW) pk_exp_slice(c[j], m, run);
+                });
+                pk_step_end<KT>(acc);
+            });
+    } else {
+        head();
+        pk_groups<KT, GW>(Tq, orow0, 0, G < KP ? G : KP, W, b0, b1, b2, b3, acc, own32);
+        if constexpr (DRAW) pk_static_for<0, KP>([&](auto J) { pk_exp_slice(c[decltype(J)::value], m, run); });
+    }
+    float t = 0.0f;
+    if constexpr (DRAW) t = (float)u * run;
+    whole = false;
+    if constexpr (kRound1) whole = G >= 2 * KP;
+    if (whole) {
+        if constexpr (kRound1)
+            pk_static_for<0, KP>([&](auto J) {
+                constexpr int j = decltype(J)::value;
+                pk_step<KT, GW, KP + j>(Tq, orow0, b0, b1, b2, b3, acc, own32, [&] {
+                    if constexpr (DRAW) pk_cmp_slice(c[j], t, cnt, nearest);
+                });
+                pk_step_end<KT>(acc);
+            });
+        if (G > 2 * KP) pk_groups<KT, GW>(Tq, orow0, 2 * KP, G, W, b0, b1, b2, b3, acc, own32);
+    } else {
+        if (G > KP) pk_groups<KT, GW>(Tq, orow0, KP, G, W, b0, b1, b2, b3, acc, own32);
+        if constexpr (DRAW) pk_static_for<0, KP>([&](auto J) { pk_cmp_slice(c[decltype(J)::value], t, cnt, nearest); });
+    }
+}
+
+// Which forms run the pipelined body: the 1024-thread forms of up to 20 accumulators.  A workgroup of 1024 threads is
+// four waves per SIMD and may use 128 VGPRs; these forms compile within them without scratch (71, 87, 97, 109 and 128
+// VGPRs at 4, 8, 12, 16 and 20 accumulators) and hold the waves they held.  At 24 and 32 accumulators the body spills
+// there, and at the smaller workgroup sizes it would cost the forms waves (144 VGPRs at 20 accumulators: three waves
+// per SIMD where the present body holds five): those keep the present body.  Both bodies of every form:
+// profiles/r10/README.md.
+constexpr bool pk_pipelined(int kt, int nt, int /*gw*/) { return nt == 1024 && kt <= 20; }
+
+// What follows the packed draw of a chunk, the same in both bodies: the lanes the packed tier cannot prove, the DP's
+// books, the movers.  pos, zo, u and the words b0..b3 are those of the chunk that was drawn (in the pipelined body the
+// one before the chunk being scored).  Returns the label to store.
+template <int KT, int GW, int GRMAX = 20>
+__device__ __forceinline__ int pk_settle(const ResampleArgs& a, char* smem, const PkPos& pos, int lane, bool certain,
+                                         int cnt, double u, int zo, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3,
+                                         int dp_K, int K, unsigned& ndeferred, unsigned& nunselected) {
+    constexpr int GM = 1 << GW;
+    const int zoc = zo < 0 ? 0 : zo;
+    DBG_TIER1_FORCE(a, certain);
+    bool defer = pos.valid && !certain;
+#ifdef BMM_DEBUG_HOOKS
+    const bool selected = a.pk_defer_every > 0 && pos.valid &&
+                          (a.lo + (int64_t)pos.s0 + lane) % a.pk_defer_every == 0;
+    nunselected += (unsigned)__popcll(__ballot(defer && !selected));
+    defer = defer || selected;
+#endif
+    int zn = cnt;
+    // ---- the lanes the packed tier cannot prove (uniform, rare): the definition, one lane at a time, its
+    // count into that lane.  (A certain lane has a finite maximum: the "every category impossible" case is
+    // always settled here.)  Arguments, layout and the lane number are taken here, not ahead of the loop.
+    unsigned long long o = __ballot(defer);
+#ifdef BMM_DEBUG_HOOKS
+    ndeferred += (unsigned)__popcll(o);
+#endif
+    if (__builtin_expect(o != 0, 0)) {
+        const PkArgsView v = pk_args_view();
+        const TableLayout Lc{v.p->G, KT, v.p->Gm, GM};
+        const PkLds lc = pk_lds(smem, Lc);
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        do {
+            const int src = __ffsll((long long)o) - 1;
+            o &= o - 1;
+            const uint32_t w0 = __builtin_amdgcn_readlane(b0, src), w1 = __builtin_amdgcn_readlane(b1, src);
+            const uint32_t w2 = __builtin_amdgcn_readlane(b2, src), w3 = __builtin_amdgcn_readlane(b3, src);
+            const int e = pk_exact_count<KT, GW, GRMAX>(*v.p, *v.a, Lc, w0, w1, w2, w3, __builtin_amdgcn_readlane(zo, src),
+                                                        pk_bcast(u, src), lc.ET, ln);
+            if (ln == src) zn = e;
+        } while (o);
+    }
+    if (__builtin_expect(__ballot(zn == dp_K) != 0, 0)) {  // the DP's new cluster was drawn (rare): its books, from the staged sizes
+        const PkArgsView v = pk_args_view();
+        const int Kc = v.p->K;
+        const TableLayout Lc{v.p->G, KT, v.p->Gm, GM};
+        const int32_t* const Nkc = pk_lds(smem, Lc).NkT;
+        int Kused = 0, new_label = -1;
+        for (int k = 0; k < Kc; ++k) {
+            if (Nkc[k] > 0) ++Kused;
+            else if (new_label < 0) new_label = k;
+        }
+        if (zn == Kc) zn = pk_dp_label(Nkc, Kc, Kused, new_label, zo, zoc);
+    }
+    const bool keep = pos.valid;
+#ifdef BMM_DEBUG_HOOKS
+    BMM_DBG_LABELS(a, keep, pos.s0 + (uint32_t)lane == 0u, K, zn, zo);
+#endif
+    const bool moves = keep && zn >= 0 && zn != zo;
+    if (__builtin_expect(__ballot(moves) != 0, 0)) {
+        const PkArgsView v = pk_args_view();
+        const int Kc = v.p->K, Pc = v.p->P;
+        const TableLayout Lc{v.p->G, KT, v.p->Gm, GM};
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        count_movers(moves, zo, zn, b0, b1, b2, b3, pk_lds(smem, Lc).hist, Kc, Pc, ln);
+    }
+    return zn;
+}
+
+template <int KT, int NT, int GW, bool PIPE>
 __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs a) {
     static_assert(KT % 2 == 0 && KT <= 32, "pairs of categories, one lane per category in pk_exact_count");
     constexpr int GM = 1 << GW;
@@ -1632,12 +1872,15 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
     if (tid == 0) *next_chunk = NW;
     __syncthreads();
     DIAG(const unsigned long long d_staged = diag_stamp();)
+    DIAG(unsigned long long d_score = 0, d_trips = 0;)  // ticks of this wave's trips between the first and the last lookup, trips
 
     float unit = kPkEpsUnit;
 #ifdef BMM_DEBUG_HOOKS
     if (a.dbg_inject & 8) unit = 0.0f;
-    unsigned ndeferred = 0, nunselected = 0;  // valid lanes this wave has settled by the definition (bmm_dbg_pk_counts)
 #endif
+    // valid lanes this wave has settled by the definition: counted and reported by the test variant only
+    // (bmm_dbg_pk_counts); in the product nothing writes or reads them, nor the K that pk_settle hands to its label check
+    unsigned ndeferred = 0, nunselected = 0;
 
     // What the loop's steady state -- a chunk without an uncertain lane and without a mover -- holds in scalar
     // registers is named here: three base pointers, the plane stride, the launch's length and this workgroup's chunks,
@@ -1663,6 +1906,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
         int zo = -1;
         if (z_in) zo = *pk_at(z_in + pos.s0, pos.loff);
         asm volatile("" : "+v"(zo));  // landed before the pipeline starts (k_resample)
+        if constexpr (!PIPE) {
         int zn_prev = 0;
         uint32_t st_s0 = 0, st_loff = 0;  // the chunk whose labels are still to be stored
         bool st_on = false;               //   ... and the lanes of it that store
@@ -1680,12 +1924,14 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
             asm volatile("" : "+s"(Wl), "+s"(zl));  // (tested below, on the values)
 
             // ---- scoring: (K / 2) * G conflict-free 64-bit LDS lookups, one packed add each; per group one 32-bit
-            // gather of the own cluster's "observation removed" entry at the same field, one add
+            // gather of the own cluster's "observation removed" entry at the same field, one add.  (pk_groups is a
+            // second copy of this loop, for the pipelined body's rolled groups: a change to either belongs in both.)
             pk_f2 acc[KP];
 #pragma unroll
             for (int j = 0; j < KP; ++j) acc[j] = pk_f2{0.0f, 0.0f};
             float own32 = 0.0f;
             const volatile lds_f32* const orow0 = Tm32 + zoc * GM;
+            DIAG(const unsigned long long d_s0 = diag_stamp();)
             __builtin_amdgcn_s_setprio(BMM_LOOKUP_PRIO);
 #pragma unroll 1
             for (int h = 0; h < W; ++h) {
@@ -1717,6 +1963,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
                 }
             }
             __builtin_amdgcn_s_setprio(0);
+            DIAG(d_score += diag_stamp() - d_s0; ++d_trips;)
             // the binary32 scores, the observation's own cluster from its own image
             pk_f2 s2[KP];
             float m = -__builtin_inff();
@@ -1733,64 +1980,10 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
             asm volatile("" : "+s"(kg));
             const double u = pk_uniform(seed, i0, pos.s0, pos.loff, sweep, kg == 0);
             int cnt = 0;
-            bool certain = pk_draw2<KT>(s2, m, u, G, unit, cnt);
-            DBG_TIER1_FORCE(a, certain);
-            bool defer = pos.valid && !certain;
-#ifdef BMM_DEBUG_HOOKS
-            const bool selected = a.pk_defer_every > 0 && pos.valid &&
-                                  (a.lo + (int64_t)pos.s0 + lane) % a.pk_defer_every == 0;
-            nunselected += (unsigned)__popcll(__ballot(defer && !selected));
-            defer = defer || selected;
-#endif
-            int zn = cnt;
-            // ---- the lanes the packed tier cannot prove (uniform, rare): the definition, one lane at a time, its
-            // count into that lane.  (A certain lane has a finite maximum: the "every category impossible" case is
-            // always settled here.)  Arguments, layout and the lane number are taken here, not ahead of the loop.
-            unsigned long long o = __ballot(defer);
-#ifdef BMM_DEBUG_HOOKS
-            ndeferred += (unsigned)__popcll(o);
-#endif
-            if (__builtin_expect(o != 0, 0)) {
-                const PkArgsView v = pk_args_view();
-                const TableLayout Lc{v.p->G, KT, v.p->Gm, GM};
-                const PkLds lc = pk_lds(smem, Lc);
-                int ln = lane;
-                asm volatile("" : "+v"(ln));
-                do {
-                    const int src = __ffsll((long long)o) - 1;
-                    o &= o - 1;
-                    const uint32_t w0 = __builtin_amdgcn_readlane(b0, src), w1 = __builtin_amdgcn_readlane(b1, src);
-                    const uint32_t w2 = __builtin_amdgcn_readlane(b2, src), w3 = __builtin_amdgcn_readlane(b3, src);
-                    const int e = pk_exact_count<KT, GW>(*v.p, *v.a, Lc, w0, w1, w2, w3, __builtin_amdgcn_readlane(zo, src),
-                                                         pk_bcast(u, src), lc.ET, ln);
-                    if (ln == src) zn = e;
-                } while (o);
-            }
-            if (__builtin_expect(__ballot(zn == dp_K) != 0, 0)) {  // the DP's new cluster was drawn (rare): its books, from the staged sizes
-                const PkArgsView v = pk_args_view();
-                const int Kc = v.p->K;
-                const TableLayout Lc{v.p->G, KT, v.p->Gm, GM};
-                const int32_t* const Nkc = pk_lds(smem, Lc).NkT;
-                int Kused = 0, new_label = -1;
-                for (int k = 0; k < Kc; ++k) {
-                    if (Nkc[k] > 0) ++Kused;
-                    else if (new_label < 0) new_label = k;
-                }
-                if (zn == Kc) zn = pk_dp_label(Nkc, Kc, Kused, new_label, zo, zoc);
-            }
+            const bool certain = pk_draw2<KT>(s2, m, u, G, unit, cnt);
+            const int zn = pk_settle<KT, GW>(a, smem, pos, lane, certain, cnt, u, zo, b0, b1, b2, b3, dp_K, K, ndeferred,
+                                             nunselected);
             const bool keep = pos.valid;
-#ifdef BMM_DEBUG_HOOKS
-            BMM_DBG_LABELS(a, keep, pos.s0 + (uint32_t)lane == 0u, K, zn, zo);
-#endif
-            const bool moves = keep && zn >= 0 && zn != zo;
-            if (__builtin_expect(__ballot(moves) != 0, 0)) {
-                const PkArgsView v = pk_args_view();
-                const int Kc = v.p->K, Pc = v.p->P;
-                const TableLayout Lc{v.p->G, KT, v.p->Gm, GM};
-                int ln = lane;
-                asm volatile("" : "+v"(ln));
-                count_movers(moves, zo, zn, b0, b1, b2, b3, pk_lds(smem, Lc).hist, Kc, Pc, ln);
-            }
             zn_prev = zn;
             st_s0 = pos.s0; st_loff = pos.loff; st_on = keep;
             if (!has_next) break;
@@ -1799,6 +1992,121 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
             pos = npos;
         }
         if (st_on) *pk_at(z_out + st_s0, st_loff) = zn_prev;
+        } else {
+        // ---- the pipelined body: a trip scores chunk i and, in the same straight-line code, runs the packed draw of
+        // chunk i - 1 (pk_rounds), so that a wave has the draw's VALU work to issue while it waits for the lookups of
+        // the next chunk.  Carried across a trip: the scores of the chunk before (s2, their maximum pm), its place, its
+        // label and its words, which the settling path, the DP's books and the movers read a trip late.  The first trip
+        // of a wave scores only, the last one draws only; the next chunk's loads and Philox are issued in the shadow of
+        // group 0's reads, and the labels of chunk i - 1 are stored behind its draw, once the words of chunk i + 1 have
+        // landed: the wait that covers those loads covers no store, and the block that closes the trip has none.  The
+        // next wait on vector memory is the one the compiler puts behind the first load of the following trip's head,
+        // behind group 0's reads, and that one does cover the store.
+        pk_f2 s2[KP];
+#pragma unroll
+        for (int j = 0; j < KP; ++j) s2[j] = pk_f2{0.0f, 0.0f};
+        float pm = 0.0f;
+        PkPos ppos;  // (places are copied member by member: a whole-struct copy of a loop-carried PkPos goes through memory)
+        ppos.s0 = pos.s0; ppos.loff = pos.loff; ppos.valid = pos.valid;
+        int pzo = -1;
+        uint32_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;
+        bool have_prev = false, have_cur = true;  // uniform
+        for (;;) {
+            bool certain = false, has_next = false;
+            int cnt = 0;
+            double u = 0.0;
+            PkPos npos;
+            npos.s0 = pos.s0; npos.loff = pos.loff; npos.valid = pos.valid;
+            uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
+            int zo_next = -1;
+            pk_f2 acc[KP];
+#pragma unroll
+            for (int j = 0; j < KP; ++j) acc[j] = pk_f2{0.0f, 0.0f};
+            float own32 = 0.0f;
+            int kg = key_general;
+            asm volatile("" : "+s"(kg));
+            if (have_cur) {
+                const int zoc = zo < 0 ? 0 : zo;
+                // (the chunk counter's round trip stays at the head of the trip: the compiler turns this atomic into a
+                // wave reduction whose result it waits for and broadcasts on the spot, ahead of group 0's reads; only
+                // what follows from the index -- the next chunk's place and loads -- sits behind them, in grab())
+                int nc = 0;
+                if (lane == 0) nc = atomicAdd(next_chunk, 1);
+                int Wl = W, zl = has_zin;
+                asm volatile("" : "+s"(Wl), "+s"(zl));  // (tested below, on the values)
+                const volatile lds_f32* const orow0 = Tm32 + zoc * GM;
+                auto grab = [&] {
+                    __builtin_amdgcn_sched_barrier(0);  // group 0's reads are issued ahead of this, not behind it
+                    nc = __builtin_amdgcn_readfirstlane(nc);
+                    has_next = nc < wg_cn;  // uniform
+                    const PkPos t = pk_pos(n, has_next ? wg_c0 + nc : 0, lane);
+                    npos.s0 = t.s0; npos.loff = t.loff; npos.valid = t.valid;
+                    if (has_next) {
+                        pk_load_words(Xb, N, Wl, npos, n0, n1, n2, n3);
+                        if (zl) zo_next = *pk_at(z_in + npos.s0, npos.loff);
+                    }
+                };
+                DIAG(const unsigned long long d_s0 = diag_stamp();)
+                __builtin_amdgcn_s_setprio(BMM_LOOKUP_PRIO);
+#ifdef BMM_EXP_PK_NOOVERLAP  // timing experiments only (tools/exp_lib.sh): the unrolled steps and the trip head of this
+                             // body with the draw behind the lookups, not among them (profiles/r10/README.md)
+                if (have_prev) {
+                    float run = 0.0f, nearest = 0.0f;
+                    pk_rounds<KT, GW, false>(Tq, orow0, G, W, b0, b1, b2, b3, acc, own32, s2, pm, u, run, cnt, nearest, [&] {
+                        grab();
+                        u = pk_uniform(seed, i0, ppos.s0, ppos.loff, sweep, kg == 0);
+                    });
+                    certain = pk_draw2<KT>(s2, pm, u, G, unit, cnt);
+                } else
+#endif
+                if (have_prev) {
+                    float run = 0.0f, nearest = __builtin_inff();
+                    pk_rounds<KT, GW, true>(Tq, orow0, G, W, b0, b1, b2, b3, acc, own32, s2, pm, u, run, cnt, nearest, [&] {
+                        grab();
+                        u = pk_uniform(seed, i0, ppos.s0, ppos.loff, sweep, kg == 0);
+                    });
+                    certain = nearest > pk_band(pm, G, unit) * run && pm > -__builtin_inff() && pm < __builtin_inff();
+                } else {
+                    float run = 0.0f, nearest = 0.0f;
+                    pk_rounds<KT, GW, false>(Tq, orow0, G, W, b0, b1, b2, b3, acc, own32, s2, pm, u, run, cnt, nearest, grab);
+                }
+                __builtin_amdgcn_s_setprio(0);
+                DIAG(d_score += diag_stamp() - d_s0; ++d_trips;)
+            } else {
+                u = pk_uniform(seed, i0, ppos.s0, ppos.loff, sweep, kg == 0);
+                certain = pk_draw2<KT>(s2, pm, u, G, unit, cnt);
+            }
+            int zn = 0;
+            if (have_prev)
+                zn = pk_settle<KT, GW, 10>(a, smem, ppos, lane, certain, cnt, u, pzo, q0, q1, q2, q3, dp_K, K, ndeferred,
+                                           nunselected);
+            // the next chunk's words and label land here, on every trip (the first one, which stores nothing, included:
+            // otherwise the rotation below keeps a wait of its own, and that one covers the store), and only then the
+            // labels are stored: no wait on vector memory lies between this store and the next trip's first load
+            asm volatile("" : "+v"(n0), "+v"(n1), "+v"(n2), "+v"(n3), "+v"(zo_next));
+            if (have_prev && ppos.valid) *pk_at(z_out + ppos.s0, ppos.loff) = zn;
+            if (!have_cur) break;
+            // the binary32 scores of the chunk just scored, the observation's own cluster from its own image
+            pm = -__builtin_inff();
+#pragma unroll
+            for (int j = 0; j < KP; ++j) {
+                float x = acc[j].x, y = acc[j].y;
+                if (2 * j == zo) x = own32;
+                if (2 * j + 1 == zo) y = own32;
+                s2[j] = pk_f2{x, y};
+                pm = __builtin_fmaxf(pm, x);
+                pm = __builtin_fmaxf(pm, y);
+            }
+            ppos.s0 = pos.s0; ppos.loff = pos.loff; ppos.valid = pos.valid;
+            pzo = zo;
+            q0 = b0; q1 = b1; q2 = b2; q3 = b3;
+            have_prev = true;
+            have_cur = has_next;
+            b0 = n0; b1 = n1; b2 = n2; b3 = n3;
+            zo = zo_next;
+            pos.s0 = npos.s0; pos.loff = npos.loff; pos.valid = npos.valid;
+        }
+        }
     }
 
     DIAG(const unsigned long long d_loop = diag_stamp();)
@@ -1812,7 +2120,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
         flush_hist(pk_lds(smem, Lc).hist, Kc, Pc, v.a->dS + (size_t)rep * Kc * Pc, v.a->dNk + rep * Kc, tid, NT);
     }
     // diagnostic build: per-launch phases in the slots k_resample reports them in; workgroup-launches and entry to
-    // flushed in [7] and [14], which k_resample leaves alone; from wave 0 of the workgroup only (every wave's atomics
+    // flushed in [7] and [14], which k_resample leaves alone, the per-trip split in [16] and [17]; from wave 0 of the workgroup only (every wave's atomics
     // on one line, as k_resample has them, take longer than this launch and hold up the global loads of workgroups
     // still at work)
     DIAG(asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); const unsigned long long d_flush = diag_stamp();)
@@ -1820,6 +2128,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
         atomicAdd(&a.diag[5], 1ull); atomicAdd(&a.diag[7], 1ull); atomicAdd(&a.diag[14], d_flush - d_entry);
         atomicAdd(&a.diag[8], d_staged - d_entry); atomicAdd(&a.diag[9], d_loop - d_staged);
         atomicAdd(&a.diag[10], d_sync - d_loop); atomicAdd(&a.diag[11], d_flush - d_sync);
+        atomicAdd(&a.diag[16], d_score); atomicAdd(&a.diag[17], d_trips);  // wave 0's trips: the lookups, and how many
     })
 #ifdef BMM_DEBUG_HOOKS
     if (a.pk_stat) {  // test variant: draws made and valid lanes settled by the definition (bmm_dbg_pk_counts)
