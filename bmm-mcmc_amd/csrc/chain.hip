@@ -361,7 +361,7 @@ struct KernelForm {
     int gw = kGroupW;   // the shape's group width (bmm_spec.h)
     bool self = false;  // workgroups that build their own table image (SELF)
     bool pk = false;    // k_resample_pk: scores from the packed binary32 image, the definition for the uncertain few
-    bool pipe = false;  // ... its pipelined body: a chunk is drawn while the next one is scored (pk_pipelined, kernels.hip.h)
+    bool pipe = false;  // ... its second body: the plain trip with unrolled group steps (pk_pipelined, kernels.hip.h)
 };
 constexpr int tile_of(const KernelForm& f) { return f.nt / f.lanes; }  // observations per tile
 constexpr KernelForm resized(KernelForm f, int nt, int lanes = 1) { f.nt = nt; f.lanes = lanes; return f; }
@@ -424,8 +424,8 @@ resample_fn lookup(const KernelForm& f, bool named_size = false) {
         if (!instantiated(f, named_size) || (f.pipe && !pk_pipelined(f.kt, f.nt, f.gw))) return nullptr;
         lift([&](auto kt, auto nt, auto gw) {
             if constexpr (instantiated(KernelForm{kt, nt, 1, true, 1, false, gw, false, true}, false)) {
-                // the present body of every form; the pipelined one of the forms that take it (BMM_DEBUG_PK_NOPIPE
-                // runs the present body where the pipelined one would run)
+                // the present body of every form; the second one of the forms that take it (BMM_DEBUG_PK_NOPIPE
+                // runs the present body where the second one would run)
                 fn = k_resample_pk<kt, nt, gw, false>;
                 if constexpr (pk_pipelined(kt, nt, gw)) if (f.pipe) fn = k_resample_pk<kt, nt, gw, true>;
             }
@@ -856,7 +856,7 @@ struct DebugSwitches {
     bool noself = dbg_env("BMM_DEBUG_NOSELF");          // no table-building workgroups
     bool nopk = dbg_env("BMM_DEBUG_NOPK");              // k_resample where k_resample_pk would run (A/B in one library)
     bool pk = dbg_env("BMM_DEBUG_PK");                  // k_resample_pk whatever the length of a launch
-    bool nopipe = dbg_env("BMM_DEBUG_PK_NOPIPE");       // k_resample_pk's present body where the pipelined one would run
+    bool nopipe = dbg_env("BMM_DEBUG_PK_NOPIPE");       // k_resample_pk's present body where the second one would run
     // n >= 1: k_resample_pk treats a lane whose observation index is a multiple of n as uncertain, so that certain and
     // settled lanes share a wave (tests/test_gpu_pk_inline.py).  BMM_DEBUG_PK_QUEUE is still accepted and does nothing:
     // the queue it sized is gone
@@ -5781,7 +5781,7 @@ static void kernel_key(const KernelForm& f, const KernelForm& twin, bool generic
 // ... whether that kernel is the packed one (k_resample_pk; the key's ten slots describe the form it stands in for),
 // and what its launches have counted so far: observations drawn, observations deferred to the binary64 definition
 extern "C" int bmm_dbg_kernel_packed(const bmm_chain* c) { return c && !c->generic && c->form.pk ? 1 : 0; }
-// ... and whether it runs the pipelined body (tests/test_gpu_pk_pipe.py)
+// ... and whether it runs the second body (tests/test_gpu_pk_pipe.py, tests/test_gpu_pk_plain.py)
 extern "C" int bmm_dbg_kernel_pk_pipelined(const bmm_chain* c) { return c && !c->generic && c->form.pk && c->form.pipe ? 1 : 0; }
 extern "C" int bmm_dbg_pk_counts(bmm_chain* c, unsigned long long* draws, unsigned long long* deferred) {
     if (!c || !draws || !deferred) return set_err(BMM_E_ARG, "null argument");

@@ -1342,9 +1342,12 @@ __global__ __launch_bounds__(NT) void k_resample(ChainParams p, ResampleArgs a) 
 // unlikely, which keeps the register allocator's spills inside them.  An observation is a 32-bit offset from the
 // launch's first (PkPos), the draw works on pairs (pk_draw2), and the Philox key is a scalar wherever the launch's
 // indices allow (pk_uniform).  Instruction counts before and after: profiles/r09/README.md.
-// PIPE: the second loop body, which the 1024-thread forms of up to 20 accumulators run (pk_pipelined): a trip scores
-// chunk i and draws chunk i - 1 in the same straight-line code (pk_rounds), everything behind the draw a trip late.
-// The present body is the other branch, unchanged, and every other form's.  profiles/r10/README.md.
+// PIPE: the second loop body, which the 1024-thread forms of up to 20 accumulators run (pk_pipelined; the name is
+// round 10's, whose second body drew chunk i - 1 among the lookups of chunk i -- that measured as nothing and is
+// gone).  It is the present body's trip in the present body's order with the lookups in unrolled steps at
+// compile-time groups (pk_score: the field one v_bfe_u32, the rows instruction offsets) and the next chunk's place, its
+// loads and this chunk's Philox rounds behind group 0's reads.  The
+// present body is the other branch, unchanged, and every other form's.  profiles/r10/README.md, profiles/r11/README.md.
 // LDS, in doubles: Tq [G][KT/2][M] pairs | Tm32 [G][KT][M] binary32 (the two as they lie behind the table image in
 // global memory) | Nk, E (as they lie in the image) | histogram, chunk counter | kPkQueue words that nothing uses
 // (pk_image_bytes, chain.hip).  The binary64 Tm is not staged.
@@ -1398,15 +1401,14 @@ __device__ __forceinline__ double pk_bcast(double x, int j) {
 // each lane's value broadcast by v_readlane (pk_bcast).
 // Every operation and its order are k_resample's.  Returns the count of the draw (the DP's new-cluster option is K:
 // the caller keeps the books), or the label to keep where every category is impossible.
-template <int KT, int GW, int GRMAX = 20>
+template <int KT, int GW>
 __device__ __forceinline__ int pk_exact_count(const ChainParams& p, const ResampleArgs& a, const TableLayout& L,
                                               uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, int zo, double u,
                                               const lds_f64* ET, int lane) {
     constexpr int GM = 1 << GW;
     // loads in flight, two VGPRs each, sized so that no form holds fewer waves per SIMD by registers than it did with
     // the pass behind the loop: the forms of up to 8 accumulators have few registers to spare (profiles/r08/README.md)
-    // (GRMAX: the pipelined body, which holds a second chunk's scores across the definition, asks for fewer)
-    constexpr int GR0 = KT <= 4 ? 6 : KT <= 8 ? 10 : 20, GR = GR0 < GRMAX ? GR0 : GRMAX;
+    constexpr int GR = KT <= 4 ? 6 : KT <= 8 ? 10 : 20;
     static_assert((kMaxP + GW - 1) / GW <= 64, "lane g holds the field of group g");
     const int G = p.G;
     const int zoc = zo < 0 ? 0 : zo;
@@ -1523,25 +1525,6 @@ __device__ __forceinline__ void pk_load_words(const uint32_t* Xb, int64_t N, int
     if (W > 3) w3 = *pk_at(b + 3 * N, t.loff);
 }
 
-// The draw's arithmetic, by pair of scores, written once: pk_draw2 runs the slices in order, the pipelined body places
-// them among its group steps.  Pair j of the first loop: the scores of the pair become its two running sums, in place
-__device__ __forceinline__ void pk_exp_slice(pk_f2& sc, float m, float& run) {
-    const pk_f2 mm{m, m}, l2e{0x1.715476p+0f, 0x1.715476p+0f};
-    const pk_f2 x = (sc - mm) * l2e;
-    run = run + __builtin_amdgcn_exp2f(x.x);
-    sc.x = run;
-    run = run + __builtin_amdgcn_exp2f(x.y);
-    sc.y = run;
-}
-// pair j of its second loop
-__device__ __forceinline__ void pk_cmp_slice(const pk_f2& c, float t, int& n, float& nearest) {
-    const pk_f2 tt{t, t};
-    const pk_f2 diff = tt - c;
-    n += diff.x >= 0.0f ? 1 : 0;
-    nearest = __builtin_fminf(nearest, __builtin_fabsf(diff.x));
-    n += diff.y >= 0.0f ? 1 : 0;
-    nearest = __builtin_fminf(nearest, __builtin_fabsf(diff.y));
-}
 // draw_pk (bmm_spec.h) on scores held in pairs: s - m, the scaling by log2(e) and t - c[k] as packed binary32
 // operations, each component rounded as the scalar instruction rounds it (same mode register), the running sum in the
 // same order: cnt and the verdict are draw_pk's bit for bit (tests/test_gpu_pk_lean.py runs the two side by side).
@@ -1550,18 +1533,29 @@ template <int KT>
 __device__ __forceinline__ bool pk_draw2(const pk_f2 (&s2)[KT / 2], float m, double u, int G, float unit, int& cnt) {
     static_assert(KT % 2 == 0 && KT <= kTier1MaxCats, "the band is derived for at most kTier1MaxCats categories");
     constexpr int KP = KT / 2;
+    const pk_f2 mm{m, m}, l2e{0x1.715476p+0f, 0x1.715476p+0f};
     pk_f2 c[KP];
     float run = 0.0f;
 #pragma unroll
     for (int j = 0; j < KP; ++j) {
-        c[j] = s2[j];
-        pk_exp_slice(c[j], m, run);  // sub, then mul: no fma (-ffp-contract=off, and the band's derivation)
+        const pk_f2 x = (s2[j] - mm) * l2e;  // sub, then mul: no fma (-ffp-contract=off, and the band's derivation)
+        run = run + __builtin_amdgcn_exp2f(x.x);
+        c[j].x = run;
+        run = run + __builtin_amdgcn_exp2f(x.y);
+        c[j].y = run;
     }
     const float t = (float)u * run;
+    const pk_f2 tt{t, t};
     float nearest = __builtin_inff();
     int n = 0;
 #pragma unroll
-    for (int j = 0; j < KP; ++j) pk_cmp_slice(c[j], t, n, nearest);
+    for (int j = 0; j < KP; ++j) {
+        const pk_f2 diff = tt - c[j];
+        n += diff.x >= 0.0f ? 1 : 0;
+        nearest = __builtin_fminf(nearest, __builtin_fabsf(diff.x));
+        n += diff.y >= 0.0f ? 1 : 0;
+        nearest = __builtin_fminf(nearest, __builtin_fabsf(diff.y));
+    }
     cnt = n;
     return nearest > pk_band(m, G, unit) * run && m > -__builtin_inff() && m < __builtin_inff();
 }
@@ -1584,8 +1578,8 @@ __device__ __forceinline__ double pk_uniform(uint64_t seed, uint64_t i0, uint32_
     return u52(ra, rb);
 }
 
-// ---- the pipelined body's pieces (k_resample_pk<.., PIPE = true>): pk_draw2 cut into slices by pair index, and one
-// group step at a compile-time group
+// ---- the second body's pieces (k_resample_pk<.., PIPE = true>): one group step at a compile-time group, and the
+// scoring of a chunk written over it (pk_score)
 template <int I>
 struct PkIdx { static constexpr int value = I; };
 template <int I, int N, class F>
@@ -1681,72 +1675,60 @@ __device__ __forceinline__ void pk_groups(const volatile lds_pk_f2* Tq, const vo
         }
     }
 }
-// The scoring of one chunk with the packed draw of the chunk before it cut into its group steps (DRAW).  The groups
-// are taken in rounds of KT/2.  A first round that is whole (G >= KT/2) is straight-line code, its groups known at
-// compile time, and step j carries pair j's exponents and running sums in the shadow of its reads; a second round that
-// is whole carries the compares the same way.  A round that is not whole runs the rolled loop and its slices follow
-// it; so do the groups from the third round on.  (A guard per step was tried first: the compiler either held a mask
-// per step in scalar registers across the tile loop or, with early exits, gave the accumulators new registers at every
-// step and spilled them -- profiles/r10/README.md.)  `head` runs in the shadow of group 0's reads.  c: the scores of
-// the previous chunk on entry (own-cluster substitution done, m their maximum), its running sums on return; run, cnt,
-// nearest as pk_draw2 leaves them.  G is tested on an opaque copy, where it is used.
-template <int KT, int GW, bool DRAW, class Head>
-__device__ __forceinline__ void pk_rounds(const volatile lds_pk_f2* Tq, const volatile lds_f32* orow0, int G, int W,
-                                          uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3, pk_f2 (&acc)[KT / 2],
-                                          float& own32, pk_f2 (&c)[KT / 2], float m, const double& u, float& run, int& cnt,
-                                          float& nearest, Head&& head) {
+// The scoring of one chunk in the second body, from cleared sums.  Group 0 is a step of its own, whatever G, with
+// `head` in the shadow of its reads.  The groups behind it are taken in rounds of KT/2: a round that is whole (G >= KT/2, G >= KT)
+// is straight-line code, its groups known at compile time; a round that is not whole runs the rolled loop, and so do
+// the groups from the third round on.  (A guard per step was tried first: the compiler either held a mask per step in
+// scalar registers across the tile loop or, with early exits, gave the accumulators new registers at every step and
+// spilled them -- profiles/r10/README.md.)  G is tested on an opaque copy, where it is used.
+template <int KT, int GW, class Head>
+__device__ __forceinline__ void pk_score(const volatile lds_pk_f2* Tq, const volatile lds_f32* orow0, int G, int W,
+                                         uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3, pk_f2 (&acc)[KT / 2],
+                                         float& own32, Head&& head) {
     constexpr int KP = KT / 2;
     constexpr bool kRound0 = (KP - 1) * GW < kMaxP, kRound1 = (2 * KP - 1) * GW < kMaxP;  // such a G exists
     asm volatile("" : "+s"(G));
+#pragma unroll
+    for (int j = 0; j < KP; ++j) acc[j] = pk_f2{0.0f, 0.0f};
+    own32 = 0.0f;
+    pk_step<KT, GW, 0>(Tq, orow0, b0, b1, b2, b3, acc, own32, head);
+    pk_step_end<KT>(acc);
     bool whole = false;
     if constexpr (kRound0) whole = G >= KP;
     if (whole) {
         if constexpr (kRound0)
-            pk_static_for<0, KP>([&](auto J) {
-                constexpr int j = decltype(J)::value;
-                pk_step<KT, GW, j>(Tq, orow0, b0, b1, b2, b3, acc, own32, [&] {
-                    if constexpr (j == 0) head();
-                    if constexpr (DRAW) pk_exp_slice(c[j], m, run);
-                });
+            pk_static_for<1, KP>([&](auto J) {
+                pk_step<KT, GW, decltype(J)::value>(Tq, orow0, b0, b1, b2, b3, acc, own32, [] {});
                 pk_step_end<KT>(acc);
             });
-    } else {
-        head();
-        pk_groups<KT, GW>(Tq, orow0, 0, G < KP ? G : KP, W, b0, b1, b2, b3, acc, own32);
-        if constexpr (DRAW) pk_static_for<0, KP>([&](auto J) { pk_exp_slice(c[decltype(J)::value], m, run); });
+    } else if (G > 1) {
+        pk_groups<KT, GW>(Tq, orow0, 1, G, W, b0, b1, b2, b3, acc, own32);  // (G < KT/2 here)
     }
-    float t = 0.0f;
-    if constexpr (DRAW) t = (float)u * run;
     whole = false;
     if constexpr (kRound1) whole = G >= 2 * KP;
     if (whole) {
         if constexpr (kRound1)
             pk_static_for<0, KP>([&](auto J) {
-                constexpr int j = decltype(J)::value;
-                pk_step<KT, GW, KP + j>(Tq, orow0, b0, b1, b2, b3, acc, own32, [&] {
-                    if constexpr (DRAW) pk_cmp_slice(c[j], t, cnt, nearest);
-                });
+                pk_step<KT, GW, KP + decltype(J)::value>(Tq, orow0, b0, b1, b2, b3, acc, own32, [] {});
                 pk_step_end<KT>(acc);
             });
         if (G > 2 * KP) pk_groups<KT, GW>(Tq, orow0, 2 * KP, G, W, b0, b1, b2, b3, acc, own32);
-    } else {
-        if (G > KP) pk_groups<KT, GW>(Tq, orow0, KP, G, W, b0, b1, b2, b3, acc, own32);
-        if constexpr (DRAW) pk_static_for<0, KP>([&](auto J) { pk_cmp_slice(c[decltype(J)::value], t, cnt, nearest); });
+    } else if (G > KP) {
+        pk_groups<KT, GW>(Tq, orow0, KP, G, W, b0, b1, b2, b3, acc, own32);
     }
 }
 
-// Which forms run the pipelined body: the 1024-thread forms of up to 20 accumulators.  A workgroup of 1024 threads is
-// four waves per SIMD and may use 128 VGPRs; these forms compile within them without scratch (71, 87, 97, 109 and 128
-// VGPRs at 4, 8, 12, 16 and 20 accumulators) and hold the waves they held.  At 24 and 32 accumulators the body spills
-// there, and at the smaller workgroup sizes it would cost the forms waves (144 VGPRs at 20 accumulators: three waves
-// per SIMD where the present body holds five): those keep the present body.  Both bodies of every form:
-// profiles/r10/README.md.
+// Which forms run the second body: the 1024-thread forms of up to 20 accumulators, as round 10 chose them for its
+// pipelined body (the predicate and its name are kept: KernelForm::pipe and bmm_dbg_kernel_pk_pipelined mean "this
+// chain runs the second body").  They compile without scratch at 57, 65, 84, 86 and 98 VGPRs at 4, 8, 12, 16 and 20
+// accumulators, within one VGPR of the present body up to 16.  The plain trip would also fit the forms of up to 28
+// accumulators at every workgroup size (109 VGPRs at most, no scratch; 32 accumulators spill at 1024 threads); giving
+// it to them is a change of its own, with its own timings.  Both bodies of every form: profiles/r11/README.md.
 constexpr bool pk_pipelined(int kt, int nt, int /*gw*/) { return nt == 1024 && kt <= 20; }
 
 // What follows the packed draw of a chunk, the same in both bodies: the lanes the packed tier cannot prove, the DP's
-// books, the movers.  pos, zo, u and the words b0..b3 are those of the chunk that was drawn (in the pipelined body the
-// one before the chunk being scored).  Returns the label to store.
-template <int KT, int GW, int GRMAX = 20>
+// books, the movers.  pos, zo, u and the words b0..b3 are those of the chunk that was drawn.  Returns the label to store.
+template <int KT, int GW>
 __device__ __forceinline__ int pk_settle(const ResampleArgs& a, char* smem, const PkPos& pos, int lane, bool certain,
                                          int cnt, double u, int zo, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3,
                                          int dp_K, int K, unsigned& ndeferred, unsigned& nunselected) {
@@ -1779,7 +1761,7 @@ __device__ __forceinline__ int pk_settle(const ResampleArgs& a, char* smem, cons
             o &= o - 1;
             const uint32_t w0 = __builtin_amdgcn_readlane(b0, src), w1 = __builtin_amdgcn_readlane(b1, src);
             const uint32_t w2 = __builtin_amdgcn_readlane(b2, src), w3 = __builtin_amdgcn_readlane(b3, src);
-            const int e = pk_exact_count<KT, GW, GRMAX>(*v.p, *v.a, Lc, w0, w1, w2, w3, __builtin_amdgcn_readlane(zo, src),
+            const int e = pk_exact_count<KT, GW>(*v.p, *v.a, Lc, w0, w1, w2, w3, __builtin_amdgcn_readlane(zo, src),
                                                         pk_bcast(u, src), lc.ET, ln);
             if (ln == src) zn = e;
         } while (o);
@@ -1925,7 +1907,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
 
             // ---- scoring: (K / 2) * G conflict-free 64-bit LDS lookups, one packed add each; per group one 32-bit
             // gather of the own cluster's "observation removed" entry at the same field, one add.  (pk_groups is a
-            // second copy of this loop, for the pipelined body's rolled groups: a change to either belongs in both.)
+            // second copy of this loop, for the second body's rolled groups: a change to either belongs in both.)
             pk_f2 acc[KP];
 #pragma unroll
             for (int j = 0; j < KP; ++j) acc[j] = pk_f2{0.0f, 0.0f};
@@ -1993,119 +1975,70 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
         }
         if (st_on) *pk_at(z_out + st_s0, st_loff) = zn_prev;
         } else {
-        // ---- the pipelined body: a trip scores chunk i and, in the same straight-line code, runs the packed draw of
-        // chunk i - 1 (pk_rounds), so that a wave has the draw's VALU work to issue while it waits for the lookups of
-        // the next chunk.  Carried across a trip: the scores of the chunk before (s2, their maximum pm), its place, its
-        // label and its words, which the settling path, the DP's books and the movers read a trip late.  The first trip
-        // of a wave scores only, the last one draws only; the next chunk's loads and Philox are issued in the shadow of
-        // group 0's reads, and the labels of chunk i - 1 are stored behind its draw, once the words of chunk i + 1 have
-        // landed: the wait that covers those loads covers no store, and the block that closes the trip has none.  The
-        // next wait on vector memory is the one the compiler puts behind the first load of the following trip's head,
-        // behind group 0's reads, and that one does cover the store.
-        pk_f2 s2[KP];
-#pragma unroll
-        for (int j = 0; j < KP; ++j) s2[j] = pk_f2{0.0f, 0.0f};
-        float pm = 0.0f;
-        PkPos ppos;  // (places are copied member by member: a whole-struct copy of a loop-carried PkPos goes through memory)
-        ppos.s0 = pos.s0; ppos.loff = pos.loff; ppos.valid = pos.valid;
-        int pzo = -1;
-        uint32_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;
-        bool have_prev = false, have_cur = true;  // uniform
+        // ---- the second body: the present body's trip, in its order, with the lookups in unrolled steps at
+        // compile-time groups (pk_score).  The chunk counter's atomic stays at the head of the trip (the compiler turns
+        // it into a wave reduction whose result it waits for and broadcasts on the spot), and what follows from its
+        // index -- the next chunk's place and loads -- and the Philox rounds of this chunk's uniform are issued in the
+        // shadow of group 0's reads.  Nothing of a chunk is carried into the next trip but the labels to store.
+        int zn_prev = 0;
+        uint32_t st_s0 = 0, st_loff = 0;  // the chunk whose labels are still to be stored
+        bool st_on = false;               //   ... and the lanes of it that store
         for (;;) {
-            bool certain = false, has_next = false;
-            int cnt = 0;
-            double u = 0.0;
-            PkPos npos;
+            const int zoc = zo < 0 ? 0 : zo;
+            if (st_on) *pk_at(z_out + st_s0, st_loff) = zn_prev;
+            int nc = 0;
+            if (lane == 0) nc = atomicAdd(next_chunk, 1);
+            bool has_next = false;  // uniform
+            PkPos npos;  // (places are copied member by member: a whole-struct copy of a PkPos set in a lambda goes through memory)
             npos.s0 = pos.s0; npos.loff = pos.loff; npos.valid = pos.valid;
             uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
             int zo_next = -1;
+            double u = 0.0;
+            int Wl = W, zl = has_zin, kg = key_general;
+            asm volatile("" : "+s"(Wl), "+s"(zl), "+s"(kg));  // (tested below, on the values)
             pk_f2 acc[KP];
-#pragma unroll
-            for (int j = 0; j < KP; ++j) acc[j] = pk_f2{0.0f, 0.0f};
-            float own32 = 0.0f;
-            int kg = key_general;
-            asm volatile("" : "+s"(kg));
-            if (have_cur) {
-                const int zoc = zo < 0 ? 0 : zo;
-                // (the chunk counter's round trip stays at the head of the trip: the compiler turns this atomic into a
-                // wave reduction whose result it waits for and broadcasts on the spot, ahead of group 0's reads; only
-                // what follows from the index -- the next chunk's place and loads -- sits behind them, in grab())
-                int nc = 0;
-                if (lane == 0) nc = atomicAdd(next_chunk, 1);
-                int Wl = W, zl = has_zin;
-                asm volatile("" : "+s"(Wl), "+s"(zl));  // (tested below, on the values)
-                const volatile lds_f32* const orow0 = Tm32 + zoc * GM;
-                auto grab = [&] {
-                    __builtin_amdgcn_sched_barrier(0);  // group 0's reads are issued ahead of this, not behind it
-                    nc = __builtin_amdgcn_readfirstlane(nc);
-                    has_next = nc < wg_cn;  // uniform
-                    const PkPos t = pk_pos(n, has_next ? wg_c0 + nc : 0, lane);
-                    npos.s0 = t.s0; npos.loff = t.loff; npos.valid = t.valid;
-                    if (has_next) {
-                        pk_load_words(Xb, N, Wl, npos, n0, n1, n2, n3);
-                        if (zl) zo_next = *pk_at(z_in + npos.s0, npos.loff);
-                    }
-                };
-                DIAG(const unsigned long long d_s0 = diag_stamp();)
-                __builtin_amdgcn_s_setprio(BMM_LOOKUP_PRIO);
-#ifdef BMM_EXP_PK_NOOVERLAP  // timing experiments only (tools/exp_lib.sh): the unrolled steps and the trip head of this
-                             // body with the draw behind the lookups, not among them (profiles/r10/README.md)
-                if (have_prev) {
-                    float run = 0.0f, nearest = 0.0f;
-                    pk_rounds<KT, GW, false>(Tq, orow0, G, W, b0, b1, b2, b3, acc, own32, s2, pm, u, run, cnt, nearest, [&] {
-                        grab();
-                        u = pk_uniform(seed, i0, ppos.s0, ppos.loff, sweep, kg == 0);
-                    });
-                    certain = pk_draw2<KT>(s2, pm, u, G, unit, cnt);
-                } else
-#endif
-                if (have_prev) {
-                    float run = 0.0f, nearest = __builtin_inff();
-                    pk_rounds<KT, GW, true>(Tq, orow0, G, W, b0, b1, b2, b3, acc, own32, s2, pm, u, run, cnt, nearest, [&] {
-                        grab();
-                        u = pk_uniform(seed, i0, ppos.s0, ppos.loff, sweep, kg == 0);
-                    });
-                    certain = nearest > pk_band(pm, G, unit) * run && pm > -__builtin_inff() && pm < __builtin_inff();
-                } else {
-                    float run = 0.0f, nearest = 0.0f;
-                    pk_rounds<KT, GW, false>(Tq, orow0, G, W, b0, b1, b2, b3, acc, own32, s2, pm, u, run, cnt, nearest, grab);
+            float own32;
+            const volatile lds_f32* const orow0 = Tm32 + zoc * GM;
+            DIAG(const unsigned long long d_s0 = diag_stamp();)
+            __builtin_amdgcn_s_setprio(BMM_LOOKUP_PRIO);
+            pk_score<KT, GW>(Tq, orow0, G, W, b0, b1, b2, b3, acc, own32, [&] {
+                __builtin_amdgcn_sched_barrier(0);  // group 0's reads are issued ahead of this, not behind it
+                nc = __builtin_amdgcn_readfirstlane(nc);
+                has_next = nc < wg_cn;
+                const PkPos t = pk_pos(n, has_next ? wg_c0 + nc : 0, lane);
+                npos.s0 = t.s0; npos.loff = t.loff; npos.valid = t.valid;
+                if (has_next) {
+                    pk_load_words(Xb, N, Wl, npos, n0, n1, n2, n3);
+                    if (zl) zo_next = *pk_at(z_in + npos.s0, npos.loff);
                 }
-                __builtin_amdgcn_s_setprio(0);
-                DIAG(d_score += diag_stamp() - d_s0; ++d_trips;)
-            } else {
-                u = pk_uniform(seed, i0, ppos.s0, ppos.loff, sweep, kg == 0);
-                certain = pk_draw2<KT>(s2, pm, u, G, unit, cnt);
-            }
-            int zn = 0;
-            if (have_prev)
-                zn = pk_settle<KT, GW, 10>(a, smem, ppos, lane, certain, cnt, u, pzo, q0, q1, q2, q3, dp_K, K, ndeferred,
-                                           nunselected);
-            // the next chunk's words and label land here, on every trip (the first one, which stores nothing, included:
-            // otherwise the rotation below keeps a wait of its own, and that one covers the store), and only then the
-            // labels are stored: no wait on vector memory lies between this store and the next trip's first load
-            asm volatile("" : "+v"(n0), "+v"(n1), "+v"(n2), "+v"(n3), "+v"(zo_next));
-            if (have_prev && ppos.valid) *pk_at(z_out + ppos.s0, ppos.loff) = zn;
-            if (!have_cur) break;
-            // the binary32 scores of the chunk just scored, the observation's own cluster from its own image
-            pm = -__builtin_inff();
+                u = pk_uniform(seed, i0, pos.s0, pos.loff, sweep, kg == 0);
+            });
+            __builtin_amdgcn_s_setprio(0);
+            DIAG(d_score += diag_stamp() - d_s0; ++d_trips;)
+            // the binary32 scores, the observation's own cluster from its own image
+            pk_f2 s2[KP];
+            float m = -__builtin_inff();
 #pragma unroll
             for (int j = 0; j < KP; ++j) {
                 float x = acc[j].x, y = acc[j].y;
                 if (2 * j == zo) x = own32;
                 if (2 * j + 1 == zo) y = own32;
                 s2[j] = pk_f2{x, y};
-                pm = __builtin_fmaxf(pm, x);
-                pm = __builtin_fmaxf(pm, y);
+                m = __builtin_fmaxf(m, x);
+                m = __builtin_fmaxf(m, y);
             }
-            ppos.s0 = pos.s0; ppos.loff = pos.loff; ppos.valid = pos.valid;
-            pzo = zo;
-            q0 = b0; q1 = b1; q2 = b2; q3 = b3;
-            have_prev = true;
-            have_cur = has_next;
+            int cnt = 0;
+            const bool certain = pk_draw2<KT>(s2, m, u, G, unit, cnt);
+            const int zn = pk_settle<KT, GW>(a, smem, pos, lane, certain, cnt, u, zo, b0, b1, b2, b3, dp_K, K, ndeferred,
+                                             nunselected);
+            zn_prev = zn;
+            st_s0 = pos.s0; st_loff = pos.loff; st_on = pos.valid;
+            if (!has_next) break;
             b0 = n0; b1 = n1; b2 = n2; b3 = n3;
             zo = zo_next;
             pos.s0 = npos.s0; pos.loff = npos.loff; pos.valid = npos.valid;
         }
+        if (st_on) *pk_at(z_out + st_s0, st_loff) = zn_prev;
         }
     }
 

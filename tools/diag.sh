@@ -4,8 +4,8 @@
 # the GPU box) loads it for one bench run through BMM_LIB_PATH -- the product library is never
 # touched -- and prints the per-phase tick shares each chain reports on destroy.  Never timed, never shipped.
 # DIAG_DEFS adds defines to the build: DIAG_DEFS=-DBMM_DEBUG_HOOKS gives the stamped library the test variant's
-# switches, so that BMM_DEBUG_PK_NOPIPE=1 stamps k_resample_pk's present body and its absence the pipelined one
-# (profiles/r10/README.md section 0).
+# switches, so that BMM_DEBUG_PK_NOPIPE=1 stamps k_resample_pk's present body and its absence the second one
+# (profiles/r10/README.md section 0, profiles/r11/README.md).
 set -e
 cd "$(dirname "$0")/.."
 L=$(pwd)/bmm-mcmc_amd/lib

@@ -2,8 +2,8 @@
 # Register tables of k_resample_pk: every form of the library (8 accumulator counts x {1024, 768, 512, 256} threads at
 # groups of five, and the default size at groups of four) instantiated explicitly with one body, compiled alone for
 # gfx950 with the library's flags, the figures of -Rpass-analysis=kernel-resource-usage one line per form.
-# Usage: tools/pk_regs.sh true|false   (the pipelined body | the present body) -- needs no GPU; about two minutes.
-# The pipelined body is compiled here for every form, also for those that pk_pipelined leaves on the present body.
+# Usage: tools/pk_regs.sh true|false   (the second body | the present body) -- needs no GPU; about two minutes.
+# The second body is compiled here for every form, also for those that pk_pipelined leaves on the present body.
 set -e
 cd "$(dirname "$0")/.."
 BODY=${1:-true}
