@@ -1193,6 +1193,44 @@ def _with_missing(out, mi):
     return out
 
 
+# ---------------------------------------------------------------- known= / allowed=: constrained allocations
+class _Constraints:
+    """known= / allowed= of the four samplers: the sorted row list and the masks, armed for exactly one run"""
+
+    def __init__(self, rows, masks):
+        self.rows, self.masks = rows, masks
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_constraints(_C.c_int64(self.rows.size), _capi.vp(self.rows), _capi.vp(self.masks)))
+
+    def result(self):
+        pr, rv = _C.c_int64(0), _C.c_int64(0)
+        _capi.check(_capi.lib().bmm_last_constraint_stats(_C.byref(pr), _C.byref(rv)))
+        return _constraint_result(self.rows, self.masks, pr.value, rv.value)
+
+
+def _constraint_result(rows, masks, proposed, reverted):
+    return {"rows": rows, "n_rows": int(rows.size), "n_known": int(((masks & (masks - _np.uint64(1))) == 0).sum()),
+            "proposed": int(proposed), "reverted": int(reverted), "rate": reverted / proposed if proposed else float("nan")}
+
+
+def _take_constraints(known, allowed, N, K, sets=True):
+    """None, or the armed list of known= / allowed=; `sets`: whether the sampler takes allowed= (its labels are classes)"""
+    if known is None and allowed is None:
+        return None
+    if allowed is not None and not sets:
+        raise ValueError("allowed= is offered by gibbs_collapsed and gibbs_full only: a label of gibbs_dp and "
+                         "gibbs_stickbreaking is whatever cluster holds it, so only known= rows can pin one")
+    rows, masks, _ = _capi.constraint_list(N, K, known, allowed)
+    return _Constraints(rows, masks)
+
+
+def _with_constraints(out, cs):
+    if cs is not None:
+        out["constraints"] = cs.result()
+    return out
+
+
 # ---------------------------------------------------------------- init=: the k-modes++ start on the device
 INIT_KINDS = {"kmodes": 1}
 INIT_ITERS = 10  # a cap, not a tuned value: the refinement stops at the first round that changes no label
@@ -1238,7 +1276,7 @@ class _Init:
 
 
 def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None, lp=None, tp=None, pc=None,
-         mi=None):
+         mi=None, cs=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
@@ -1260,6 +1298,8 @@ def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=
         pc.arm()
     if mi is not None:
         mi.arm()
+    if cs is not None:
+        cs.arm()
     if init is not None:  # last, just ahead of the call: a run of another sampler refuses an armed start
         init.arm()
     if pr is None:
@@ -1419,7 +1459,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                     responsibilities=False, partition=None, partition_stride=1, similarity_of=None, loo=False,
                     select_features=False, rho=0.5, init="random", init_iters=INIT_ITERS, ecr_pivot="iterative",
                     ecr_max_iter=50, logpost=False, temper=None, swap_every=1, temper_hottest=0.1, pair_check=None,
-                    pair_check_stride=1, pair_check_trace=False, missing=None):
+                    pair_check_stride=1, pair_check_trace=False, missing=None, known=None, allowed=None):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -1510,12 +1550,23 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     mixes more slowly than one that integrates them out: run longer.  Works with partition=, relabel="ecr", newdata=
     (complete rows) and logpost=; not with chains > 1, loo=, select_features=, temper=, pair_check=, init="kmodes",
     relabel=True (or split_merge= on gibbs_dp).
+    `known=`: N integers, the rows' known classes -- 0, a negative value or NaN marks a free row, any other value is the
+    row's 1-based label, which it holds in every sweep.  `allowed=`: an N x K boolean array, the labels each row may take
+    (a row that is all True is free); where both name a row they must agree.  The constrained sweep is exact (include/
+    bmm_mcmc.h "constraints"): a listed row is drawn as ever and keeps its label when the draw
+    falls outside its set.  A few known rows per class pin the labelling, so `theta` needs no relabelling.  The starting
+    labels of listed rows are put inside their sets.  The result gains `constraints = {"rows", "n_rows", "n_known",
+    "proposed", "reverted", "rate"}`: the listed rows (0-based), how many hold a single label, the listed rows drawn,
+    those reverted and their share (how sticky partial sets are).  Works with newdata=, partition=, relabel="ecr",
+    logpost= (the joint of the whole state, held rows included), pair_check=, select_features= and missing=; not with
+    chains > 1, loo=, temper=, init="kmodes", relabel=True (or split_merge= on gibbs_dp, or gibbs_allocation).
     """
     data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
     N, P = X.shape
     mi = None if cells is None else _Missing(cells[0], cells[1], N, P)
     nsamples, K = int(nsamples), int(K)
+    cs = _take_constraints(known, allowed, N, K)
     ik = _init_kind(init, init_iters)
     if ik is not None and initial_K is not None:
         raise ValueError('init="kmodes" computes the starting labels: not together with initial_K')
@@ -1539,10 +1590,12 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             out["features"] = fs.result()
         if ini is not None:
             out["init"] = ini.result()
-        return _with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc), mi)
+        return _with_constraints(_with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc), mi), cs)
     if chains > 1:
         if mi is not None:
             mi.arm()  # (the run of several chains answers it)
+        if cs is not None:
+            cs.arm()
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
         if ini is not None:
@@ -1583,7 +1636,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
                 _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini, lp=lp, tp=tp, pc=pc, mi=mi)
+            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
@@ -1595,7 +1648,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
             _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1609,7 +1662,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
              partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None,
              select_features=False, rho=0.5, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
              temper=None, swap_every=1, temper_hottest=0.1, pair_check=None, pair_check_stride=1, pair_check_trace=False,
-             missing=None):
+             missing=None, known=None, allowed=None):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
@@ -1620,13 +1673,18 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     DP run seats its rows in its first sweep; Chain.init_labels re-seats a resident DP chain).  `logpost`,
     `ecr_pivot="map"`, `pair_check`, `pair_check_stride`, `pair_check_trace`: as gibbs_collapsed.  `temper`,
     `swap_every`, `temper_hottest`: as gibbs_collapsed (the helper chains seat their own rows in their first sweep; the
-    new-cluster option carries the power on its likelihood part).  `missing`: as gibbs_collapsed."""
+    new-cluster option carries the power on its likelihood part).  `missing`: as gibbs_collapsed.  `known`: as
+    gibbs_collapsed, but the values name the chain's labels 1..maxK: the rows known to share a class hold one label, which
+    pins that cluster there; a label that no held row occupies is an ordinary free label, and the free rows open new
+    clusters as ever (the semi-supervised, novelty-detection run).  Not with split_merge=.  `allowed=` is refused here
+    (ValueError): a label is whatever cluster holds it, so a set of labels says nothing about classes."""
     _init_kind(init, 0, allowed=False)
     data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
     N, P = X.shape
     mi = None if cells is None else _Missing(cells[0], cells[1], N, P)
     nsamples, maxK = int(nsamples), int(maxK)
+    cs = _take_constraints(known, allowed, N, maxK, sets=False)
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
     relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
@@ -1646,10 +1704,12 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             out["split_merge"] = sm.result()
         if fs is not None:
             out["features"] = fs.result()
-        return _with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, maxK, device), pc), mi)
+        return _with_constraints(_with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, maxK, device), pc), mi), cs)
     if int(chains) > 1:
         if mi is not None:
             mi.arm()  # (the run of several chains answers it)
+        if cs is not None:
+            cs.arm()
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
         dev0 = device if devices is None else int(devices[0])
@@ -1671,7 +1731,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                 _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
                 _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs, lp=lp, tp=tp, pc=pc, mi=mi)
+            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, maxK, P, S)
@@ -1684,7 +1744,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi)
+        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1696,12 +1756,13 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
               device, initial_pi, initial_theta, chains, devices, stephens, debug=False, newdata=None,
               predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None,
               loo=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1,
-              pair_check_trace=False, missing=None):
+              pair_check_trace=False, missing=None, known=None, allowed=None):
     data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
     N, P = X.shape
     mi = None if cells is None else _Missing(cells[0], cells[1], N, P)
     nsamples, K = int(nsamples), int(K)
+    cs = _take_constraints(known, allowed, N, K, sets=sampler == "full")
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
     chains = int(chains)
@@ -1714,7 +1775,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
     base = fn[len("bmm_"):-len("_run_probs")]
 
     def done(out):
-        return _with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc), mi)
+        return _with_constraints(_with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc), mi), cs)
 
     def start(sd, pi, th):
         rng = _np.random.default_rng(sd)
@@ -1734,6 +1795,8 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
     if chains > 1:
         if mi is not None:
             mi.arm()  # (the run of several chains answers it)
+        if cs is not None:
+            cs.arm()
         if relabel:
             raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
         st = [start(seed + c, initial_pi[c] if initial_pi is not None else None,
@@ -1758,7 +1821,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
                 _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
                 _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run(base, args, pr, rel=dr, part=pt, loo=lo, lp=lp, pc=pc, mi=mi)
+            rc = _run(base, args, pr, rel=dr, part=pt, loo=lo, lp=lp, pc=pc, mi=mi, cs=cs)
         return done(_with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
@@ -1771,7 +1834,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
             _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec, lp=lp, pc=pc, mi=mi)
+        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec, lp=lp, pc=pc, mi=mi, cs=cs)
     out = {"pi": pi, "alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1784,35 +1847,37 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
                         initial_theta=None, chains=1, devices=None, stephens=None, newdata=None,
                         predictive_trace=False, responsibilities=False, partition=None, partition_stride=1,
                         similarity_of=None, loo=False, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
-                        pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None):
+                        pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None, known=None,
+                        allowed=None):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
     src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
     "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`: as gibbs_collapsed; log_prior is
     the stick-breaking prior with the sticks integrated out, which depends on the order of the labels.  `pair_check`,
     `pair_check_stride`, `pair_check_trace`: as gibbs_collapsed.  `missing`: as gibbs_collapsed; the cells are drawn from
-    the theta the sweep has just drawn."""
+    the theta the sweep has just drawn.  `known`, `allowed`: as gibbs_dp (the values name the chain's labels 1..maxK; allowed= is refused)."""
     _init_kind(init, 0, allowed=False)
     return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
                      burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing)
+                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
                burnrelabel=50, debug=False, *, seed=None, device=0, initial_pi=None, initial_theta=None, chains=1,
                devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False,
                partition=None, partition_stride=1, similarity_of=None, loo=False, init="random", ecr_pivot="iterative",
-               ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None):
+               ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None,
+               known=None, allowed=None):
     """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
     "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`, `pair_check`,
-    `pair_check_stride`, `pair_check_trace`, `missing`: as gibbs_collapsed."""
+    `pair_check_stride`, `pair_check_trace`, `missing`, `known`, `allowed`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
     return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
                      relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing)
+                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed)
 
 
 class Chain:
@@ -2357,6 +2422,31 @@ class Chain:
 
     def missing_reset(self):
         _capi.check(_capi.lib().bmm_chain_missing_reset(self._h))
+
+    # -- constrained allocations (include/bmm_mcmc.h "constraints")
+    def set_constraints(self, rows=None, masks=None):
+        """the constrained rows (bmm_chain_set_constraints): `rows` 0-based and strictly ascending, `masks` their allowed
+        labels as 64-bit masks (bit k: label k + 1 of labels()); nothing, or empty lists, withdraws them.  Returns the
+        number of rows."""
+        rows = _np.ascontiguousarray(() if rows is None else rows, dtype=_np.int64)
+        masks = _np.ascontiguousarray(() if masks is None else masks, dtype=_np.uint64)
+        if rows.shape != masks.shape or rows.ndim != 1:
+            raise ValueError("rows and masks must be two lists of one length")
+        _capi.check(_capi.lib().bmm_chain_set_constraints(self._h, _C.c_int64(rows.size), _capi.vp(rows), _capi.vp(masks)))
+        self._cs = (rows, masks)
+        return int(rows.size)
+
+    def set_known(self, z):
+        """the rows' known labels: N integers, 0, a negative value or NaN for a free row, else the 1-based label"""
+        rows, masks, _ = _capi.constraint_list(self.N, self.K, known=z)
+        return self.set_constraints(rows, masks)
+
+    def constraint_stats(self):
+        """{"rows", "n_rows", "n_known", "proposed", "reverted", "rate"} since the constraints were set"""
+        pr, rv = _C.c_int64(0), _C.c_int64(0)
+        _capi.check(_capi.lib().bmm_chain_constraint_stats(self._h, _C.byref(pr), _C.byref(rv)))
+        rows, masks = getattr(self, "_cs", (_np.zeros(0, dtype=_np.int64), _np.zeros(0, dtype=_np.uint64)))
+        return _constraint_result(rows, masks, pr.value, rv.value)
 
     def profile(self, every=1):
         """Time the resample launches of every `every`-th sweep with HIP events (0/False: off)."""

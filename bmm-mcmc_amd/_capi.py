@@ -52,6 +52,7 @@ SYMBOLS = [
     "bmm_chain_pair_check_reset", "bmm_chain_pair_counts", "bmm_set_pair_check", "bmm_device_pair_check", "bmm_pair_check_plan",
     "bmm_chain_set_missing", "bmm_chain_impute_step", "bmm_chain_get_missing_state", "bmm_chain_get_missing_summary",
     "bmm_chain_missing_reset", "bmm_set_missing",
+    "bmm_chain_set_constraints", "bmm_chain_constraint_stats", "bmm_set_constraints", "bmm_last_constraint_stats",
 ]
 
 
@@ -97,6 +98,11 @@ def load(path):
         L.bmm_chain_get_missing_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bmm_chain_missing_reset.argtypes = [C.c_void_p]
         L.bmm_set_missing.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    if hasattr(L, "bmm_chain_set_constraints"):  # (an older build loaded for a comparison has no constraints)
+        L.bmm_chain_set_constraints.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.bmm_chain_constraint_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bmm_set_constraints.argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
+        L.bmm_last_constraint_stats.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(L, "bmm_ladder_create"):  # (an older build loaded for a comparison has no ladder)
         L.bmm_ladder_destroy.restype = None
         L.bmm_ladder_destroy.argtypes = [C.c_void_p]
@@ -171,3 +177,44 @@ def missing_cells(data, missing):
         X = X.copy()
         X[mask] = 0
     return np.ascontiguousarray(rows, dtype=np.int64), np.ascontiguousarray(cols, dtype=np.int32), X
+
+
+def constraint_list(N, K, known=None, allowed=None):
+    """The sorted list `known=` and `allowed=` name: (rows int64, masks uint64, n_known).  known: N integers, 0, a negative
+    value or NaN marks a free row, any other value is the row's 1-based label.  allowed: an N x K boolean array, a row
+    that is all True is free.  Where both constrain a row they must agree: the known label must be allowed, and the row is
+    held there.  Labels above 64 cannot be named (the masks are 64 bits wide)."""
+    mask = np.zeros(N, dtype=np.uint64)
+    listed = np.zeros(N, dtype=bool)
+    if allowed is not None:
+        A = np.asarray(allowed)
+        if A.dtype != np.bool_ or A.shape != (N, K):
+            raise ValueError("allowed must be a boolean N x K array")
+        if K > 64:
+            raise ValueError("allowed= names labels up to 64: K = %d" % K)
+        if not A.any(axis=1).all():
+            raise ValueError("allowed: row %d has no allowed label" % int(np.flatnonzero(~A.any(axis=1))[0]))
+        listed = ~A.all(axis=1)
+        mask = (A.astype(np.uint64) << np.arange(K, dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
+    held = np.zeros(N, dtype=bool)
+    if known is not None:
+        kn = np.asarray(known)
+        if kn.shape != (N,) or kn.dtype.kind not in "iuf":
+            raise ValueError("known must hold one number per observation")
+        if kn.dtype.kind == "f":
+            kn = np.where(np.isnan(kn), 0.0, kn)
+            if not np.all(kn == np.round(kn)):
+                raise ValueError("known must be integer valued")
+        kn = kn.astype(np.int64)
+        held = kn > 0
+        if held.any() and kn[held].max() > min(K, 64):
+            raise ValueError("known: label %d lies above %s" % (int(kn[held].max()), "K = %d" % K if K <= 64 else "64, the widest mask"))
+        bit = np.zeros(N, dtype=np.uint64)
+        bit[held] = np.uint64(1) << (kn[held] - 1).astype(np.uint64)
+        clash = held & listed & ((mask & bit) == 0)
+        if clash.any():
+            raise ValueError("known and allowed disagree on row %d" % int(np.flatnonzero(clash)[0]))
+        mask = np.where(held, bit, mask)
+        listed = listed | held
+    rows = np.flatnonzero(listed).astype(np.int64)
+    return np.ascontiguousarray(rows), np.ascontiguousarray(mask[rows], dtype=np.uint64), int(held.sum())

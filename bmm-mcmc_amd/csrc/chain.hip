@@ -14,6 +14,7 @@
 #include <sched.h>
 #include <sys/mman.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -678,6 +679,15 @@ struct bmm_chain {
     std::vector<int64_t> na_rows;  // the declared cells, as given
     std::vector<int32_t> na_cols;
     SweepTrace na_rec;
+    // constrained allocations: cs_on: k_constrain behind every resample launch whose range holds
+    // a listed row.  cs_rows: the listed rows, ascending (the host's binary search per launch); one block holds their
+    // device copy, the masks and the two counters.
+    bool cs_on = false;
+    std::vector<int64_t> cs_rows;
+    char* dCsBlock = nullptr;
+    int64_t* dCsRows = nullptr;
+    uint64_t* dCsMasks = nullptr;
+    unsigned long long* dCsStats = nullptr;
     // parallel tempering: temper_on: the table builds are k_temper_tables at inverse temperature
     // temper_b, and the kernel choice leaves out the forms that build their own tables and the packed one; ladder: the
     // replica ladder a run drives this chain through as its rung 0 (not owned)
@@ -753,7 +763,7 @@ int run_rows_out(const bmm_chain* c, const double* dtrace, int64_t width, double
 }
 
 // What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_loo_summary,
-// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost, bmm_set_temper, bmm_set_pair_check, bmm_set_missing; bmm_alloc_run fills `alloc` for its own run), and what a
+// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost, bmm_set_temper, bmm_set_pair_check, bmm_set_missing, bmm_set_constraints; bmm_alloc_run fills `alloc` for its own run), and what a
 // *_run_predict / *_run_relabel / *_run_probs entry point was handed.
 struct RunOptions {
     struct { bool on = false; bmm_partition_out o{}; } partition;
@@ -768,6 +778,7 @@ struct RunOptions {
     struct { bool on = false; const int64_t* rows = nullptr; const int32_t* cols = nullptr; int64_t n = 0; bmm_missing_out o{}; } na;
     struct { bool on = false; const double* log_prior_k = nullptr; int K0 = 0, moves = 0; double eject_a = 1.0; int32_t* k_out = nullptr; int64_t* moves_out = nullptr; } alloc;
     struct { int moves = 0, scans = 0; } as;  // bmm_set_alloc_split_merge: taken by bmm_alloc_run alone
+    struct { bool on = false; int64_t n = 0; const int64_t* rows = nullptr; const uint64_t* masks = nullptr; } cs;  // bmm_set_constraints
     const bmm_relabel_hooks* hooks = nullptr;  // *_run_probs
     const bmm_relabel_out* rel = nullptr;      // *_run_relabel
     const int32_t* Xnew = nullptr; int64_t M = 0; const bmm_predict_out* pred = nullptr;  // *_run_predict
@@ -1204,6 +1215,40 @@ int launch_resample(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t l
     return BMM_OK;
 }
 
+// ---- constrained allocations ----
+// what the options that move rows by themselves, or hand the rows' probabilities on, answer an armed chain
+int cs_refuses(const char* what) {
+    return set_err(BMM_E_UNSUPPORTED, "%s is not offered on a chain with constrained rows (bmm_chain_set_constraints): it knows "
+                   "nothing of the rows' allowed labels", what);
+}
+// k_constrain over the listed rows of [lo, hi), stream-ordered behind the launch that wrote z_out there, adding to the
+// pending delta set (the one launch_resample left in dDNk / dDS, whichever form it launched).  A range without a listed
+// row launches nothing.  project: the rows' labels put inside their sets instead (the starting labels' rule); counted:
+// whether something has counted the labels already, so that the deltas must follow.
+int launch_constrain(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t lo, int64_t hi, bool project = false,
+                     bool counted = true) {
+    const auto first = std::lower_bound(c->cs_rows.begin(), c->cs_rows.end(), lo);
+    const auto last = std::lower_bound(first, c->cs_rows.end(), hi);
+    if (first == last) return BMM_OK;
+    const int64_t q0 = first - c->cs_rows.begin();
+    ConstrainArgs a{};
+    a.rows = c->dCsRows + q0; a.masks = c->dCsMasks + q0; a.n = last - first;
+    a.z_in = z_in; a.z_out = z_out; a.X = c->dX; a.Xb = c->dXb;
+    if (counted) { a.dNk = c->dDNk; a.dS = c->dDS; }
+    a.stats = project ? nullptr : c->dCsStats;
+    a.project = project ? 1 : 0;
+    const int64_t nb = (a.n + 255) / 256;
+    const dim3 grid((unsigned)(nb < 1024 ? nb : 1024));
+    if (c->generic || !c->bits) {
+        hipLaunchKernelGGL(k_constrain_generic, grid, dim3(256), 0, c->stream, c->p, a);
+    } else {
+        const size_t hb = counted ? ((size_t)c->p.K * c->p.P + c->p.K) * sizeof(int32_t) : 0;
+        hipLaunchKernelGGL(k_constrain, grid, dim3(256), hb, c->stream, c->p, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+
 // buffers and kernel of the probability hand-off, set up on first use
 int probs_alloc(bmm_chain* c, bool with_matrix) {
     const size_t n = (size_t)c->p.N;
@@ -1437,6 +1482,7 @@ int temper_refuses(const char* what) {
 int sm_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_STATE, "split-merge moves are not offered on a sharded chain");
     if (c->na_on) return na_refuses("a split-merge move");
+    if (c->cs_on) return cs_refuses("a split-merge move");
     if (c->temper_on) return temper_refuses("the split-merge ratio");
     if (c->p.mode != MODE_DP)
         return set_err(BMM_E_UNSUPPORTED, "split-merge moves are offered for the DP sampler only (the finite sampler gives an "
@@ -1610,6 +1656,7 @@ int na_refuses(const char* what) {
 int init_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_STATE, "the initialisation is not offered on a sharded chain");
     if (c->na_on) return na_refuses("a data-driven start");
+    if (c->cs_on) return cs_refuses("a data-driven start");
     if (explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "a data-driven start is offered for the collapsed and DP samplers only: the stick-breaking and "
                        "full samplers start from pi and theta");
@@ -1767,6 +1814,7 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
     if (explicit_params(p.mode)) {
         if (phase != 2) {
             int rc = launch_resample(c, zin, zout, 0, p.N, (uint32_t)j);
+            if (rc == BMM_OK && c->cs_on) rc = launch_constrain(c, zin, zout, 0, p.N);
             if (rc) return rc;
         }
         if (phase == 1) return launch_reduce_deltas(c);  // sharded chain: the caller all-reduces replica 0 now
@@ -1807,6 +1855,7 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
         int rc = c->form.self && !c->probs_dst ? BMM_OK : launch_count_tables(c);
         if (rc) return rc;
         rc = launch_resample(c, zin, zout, lo, hi, (uint32_t)j);
+        if (rc == BMM_OK && c->cs_on) rc = launch_constrain(c, zin, zout, lo, hi);  // before the next table build
         if (rc) return rc;
         lo = hi;
     }
@@ -1950,6 +1999,10 @@ int chain_start(bmm_chain* c) {
     if (p.mode == MODE_COLLAPSED) {
         // statistics of the initial allocation (collapsed_gibbs.cpp:60-63)
         int32_t* row0 = label_row(c, 0);
+        if (c->cs_on) {  // the starting labels, put inside the rows' sets before anything counts them
+            const int rc = launch_constrain(c, nullptr, c->dZ[0], 0, p.N, true, false);
+            if (rc) return rc;
+        }
         if (row0 != c->dZ[0])
             HIP_TRY(hipMemcpyAsync(row0, c->dZ[0], (size_t)p.N * sizeof(int32_t), hipMemcpyDeviceToDevice,
                                    c->stream));
@@ -2143,7 +2196,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     dev_pool().put(c->device, c->run_arena, c->run_arena_bytes);
     void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
                     c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch, c->dSmSide, c->dSmSideLaunch, c->dSmLq, c->dSmStat, c->dSmCell,
-                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dAsBlock, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock, c->dNaBlock};
+                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dAsBlock, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock, c->dNaBlock, c->dCsBlock};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     chain_stream_release(c->device, c->stream, c->stream_kind);  // synchronised above
@@ -2384,6 +2437,7 @@ int bmm_chain_sweeps(bmm_chain* c, int n) {
 int bmm_chain_set_shard(bmm_chain* c, int64_t N_total, int64_t first_row) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (c->started) return set_err(BMM_E_STATE, "chain already started");
+    if (c->cs_on) return cs_refuses("a shard");
     if (!explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "only the stick-breaking and full samplers shard exactly over observations");
     if (first_row < 0 || N_total < first_row + c->p.N) return set_err(BMM_E_ARG, "shard [first_row, first_row + N) lies outside N_total");
@@ -2440,6 +2494,7 @@ int bmm_chain_sweep_probs(bmm_chain* c, double* probs_out) {
     if (c->sharded) return set_err(BMM_E_STATE, "not available on a sharded chain");
     if (c->alloc_on) return alloc_refuses("the probability hand-off of the relabelling");
     if (c->na_on) return na_refuses("the probability hand-off of the relabelling");
+    if (c->cs_on) return cs_refuses("the probability hand-off of the relabelling");
     HIP_TRY(hipSetDevice(c->device));
     int rc = probs_alloc(c, true);
     if (rc) return rc;
@@ -2805,6 +2860,7 @@ static int pred_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, i
 static int loo_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the leave-one-out predictive is not offered on a sharded chain");
     if (c->na_on) return na_refuses("the leave-one-out predictive");
+    if (c->cs_on) return cs_refuses("the leave-one-out predictive");
     if (c->fs_mask) return fs_mask_refuses("the leave-one-out predictive");
     if (c->alloc_on) return alloc_refuses("the leave-one-out predictive");
     return BMM_OK;
@@ -3627,6 +3683,7 @@ int bmm_chain_set_labels(bmm_chain* c, const int32_t* z1) {
     return guarded([&]() -> int {
         if (!c || !z1) return set_err(BMM_E_ARG, "null argument");
         if (c->p.mode != MODE_DP) return set_err(BMM_E_UNSUPPORTED, "only a DP chain takes labels between sweeps");
+        if (c->cs_on) return cs_refuses("labels set by hand");
         if (c->sharded) return set_err(BMM_E_STATE, "not offered on a sharded chain");
         int rc = sm_seated(c);
         if (rc) return rc;
@@ -3671,6 +3728,7 @@ int bmm_chain_set_labels(bmm_chain* c, const int32_t* z1) {
 static int alloc_refused(const bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (c->na_on) return na_refuses("the allocation sampler");
+    if (c->cs_on) return cs_refuses("the allocation sampler");
     if (c->sharded) return set_err(BMM_E_STATE, "the allocation sampler is not offered on a sharded chain");
     if (c->p.mode != MODE_COLLAPSED)
         return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is the finite collapsed sampler with K unknown: create the chain with that sampler, K = maxK");
@@ -4455,11 +4513,122 @@ static int na_run_collect(bmm_chain* c, const RunOptions& o, int rc) {
     return rc;
 }
 
+// ---- constrained allocations: known labels and allowed-label sets (include/bmm_mcmc.h "constraints") ----
+// the list itself: rows in range and strictly ascending, masks non-zero with no bit at or above K.  No device is touched.
+static int cs_check_list(int64_t n, const int64_t* rows, const uint64_t* masks, int64_t N, int K) {
+    if (n < 0) return set_err(BMM_E_ARG, "constraints: n must be >= 0");
+    if (n > 0 && (!rows || !masks)) return set_err(BMM_E_ARG, "constraints: null list");
+    for (int64_t q = 0; q < n; ++q) {
+        if (rows[q] < 0 || rows[q] >= N)
+            return set_err(BMM_E_ARG, "constraints: row %lld (entry %lld) lies outside the %lld rows", (long long)rows[q], (long long)q, (long long)N);
+        if (q > 0 && rows[q] <= rows[q - 1])
+            return set_err(BMM_E_ARG, "constraints: the rows must be strictly ascending: entry %lld is not", (long long)q);
+        if (masks[q] == 0) return set_err(BMM_E_ARG, "constraints: row %lld has an empty set of allowed labels", (long long)rows[q]);
+        if (K < 64 && (masks[q] >> K) != 0)
+            return set_err(BMM_E_ARG, "constraints: row %lld allows a label above K = %d", (long long)rows[q], K);
+    }
+    return BMM_OK;
+}
+// who may carry constrained rows: a whole chain whose rows only its own sweep moves
+static int cs_refused(const bmm_chain* c) {
+    if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "constrained rows are not offered on a sharded chain");
+    if (c->alloc_on) return set_err(BMM_E_UNSUPPORTED, "constrained rows are not offered by the allocation sampler: its moves change which labels exist");
+    if (c->sm_moves > 0) return set_err(BMM_E_UNSUPPORTED, "constrained rows are not offered together with split-merge moves: they move rows by themselves");
+    if (c->temper_on || c->ladder) return set_err(BMM_E_UNSUPPORTED, "constrained rows are not offered on a tempered chain: an exchange would hand the rows a state that knows nothing of them");
+    if (c->loo_on) return set_err(BMM_E_UNSUPPORTED, "constrained rows are not offered together with the leave-one-out summary: a held row is not predicted, it is given");
+    if (c->shard_open) return set_err(BMM_E_STATE, "a sweep is open");
+    return BMM_OK;
+}
+static bool cs_seated(const bmm_chain* c) { return c->started && (c->p.mode == MODE_COLLAPSED || c->sweep >= 1); }
+
+int bmm_chain_set_constraints(bmm_chain* c, int64_t n, const int64_t* rows, const uint64_t* masks) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        int rc = cs_check_list(n, rows, masks, c->p.N, c->p.K);
+        if (rc) return rc;
+        if (n == 0) {  // withdrawn: the rows are free from the next sweep on, the counters stay readable
+            if (c->cs_on) HIP_TRY(hipStreamSynchronize(c->stream));
+            c->cs_on = false;
+            c->cs_rows.clear();
+            return BMM_OK;
+        }
+        if (c->cs_on) return set_err(BMM_E_STATE, "constraints are already set: withdraw them first (n = 0)");
+        rc = cs_refused(c);
+        if (rc) return rc;
+        if (c->dTrace && c->sweep > 0) return set_err(BMM_E_STATE, "not offered inside a run");
+        HIP_TRY(hipSetDevice(c->device));
+        Carver measure{nullptr};
+        auto carve = [&](Carver& v) {
+            c->dCsRows = v.take<int64_t>((size_t)n);
+            c->dCsMasks = v.take<uint64_t>((size_t)n);
+            c->dCsStats = v.take<unsigned long long>(2);
+        };
+        carve(measure);
+        rc = pred_room(measure.used, "the constrained rows' list");
+        if (rc) return rc;
+        if (c->dCsBlock) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->dCsBlock); c->dCsBlock = nullptr; }
+        HIP_TRY(hipMalloc(&c->dCsBlock, measure.used));
+        Carver real{c->dCsBlock};
+        carve(real);
+        HIP_TRY(hipMemsetAsync(c->dCsBlock, 0, measure.used, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dCsRows, rows, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dCsMasks, masks, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        c->cs_rows.assign(rows, rows + n);
+        // rows that have labels are put inside their sets now and the counts follow; the finite chain's starting labels
+        // are projected when it starts (chain_start), a DP or explicit chain seats its rows in its first sweep
+        if (cs_seated(c)) {
+            rc = launch_constrain(c, nullptr, label_row(c, c->sweep), 0, c->p.N, true, true);
+            if (rc) { c->cs_rows.clear(); return rc; }
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));  // the caller's lists may go
+        c->cs_on = true;
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_constraint_stats(bmm_chain* c, int64_t* proposed, int64_t* reverted) {
+    return guarded([&]() -> int {
+        if (!c || !proposed || !reverted) return set_err(BMM_E_ARG, "null argument");
+        if (!c->dCsBlock) return set_err(BMM_E_STATE, "no constraints were set (bmm_chain_set_constraints)");
+        const int rc = bmm_chain_sync(c);
+        if (rc) return rc;
+        unsigned long long v[2] = {0, 0};
+        HIP_TRY(hipMemcpy(v, c->dCsStats, sizeof v, hipMemcpyDeviceToHost));
+        *proposed = (int64_t)v[0]; *reverted = (int64_t)v[1];
+        return BMM_OK;
+    });
+}
+
+// ... of a run: armed for it (bmm_set_constraints), refused before a device is touched
+static thread_local int64_t g_cs_stats[2] = {0, 0};
+static int cs_run_check(const RunOptions& o, int64_t N, int K) {
+    if (!o.cs.on) return BMM_OK;
+    const int rc = cs_check_list(o.cs.n, o.cs.rows, o.cs.masks, N, K);
+    if (rc) return rc;
+    if (o.sm.moves > 0) return set_err(BMM_E_UNSUPPORTED, "constrained rows are not offered together with split-merge moves: they move rows by themselves");
+    if (o.temper.on) return set_err(BMM_E_UNSUPPORTED, "constrained rows are not offered together with parallel tempering: an exchange would hand the rows a state that knows nothing of them");
+    if (o.loo.on) return set_err(BMM_E_UNSUPPORTED, "constrained rows are not offered together with the leave-one-out summary: a held row is not predicted, it is given");
+    if (o.init.kind != 0) return set_err(BMM_E_UNSUPPORTED, "constrained rows are not offered together with a device start: it knows nothing of the rows' allowed labels");
+    if (o.hooks || o.rel)
+        return set_err(BMM_E_UNSUPPORTED, "constrained rows are not offered together with a probability hand-off (relabel = TRUE): the "
+                       "handed-on rows would be those of draws that were reverted; anchored rows need no relabelling, and ECR reads the labels alone");
+    if (o.alloc.on) return set_err(BMM_E_UNSUPPORTED, "constrained rows are not offered by the allocation sampler");
+    return BMM_OK;
+}
+static int cs_run_attach(bmm_chain* c, const RunOptions& o) {
+    g_cs_stats[0] = g_cs_stats[1] = 0;
+    return o.cs.on ? bmm_chain_set_constraints(c, o.cs.n, o.cs.rows, o.cs.masks) : BMM_OK;
+}
+static int cs_run_collect(bmm_chain* c, const RunOptions& o, int rc) {
+    return rc == BMM_OK && o.cs.on ? bmm_chain_constraint_stats(c, &g_cs_stats[0], &g_cs_stats[1]) : rc;
+}
+
 // ---- parallel tempering: a replica ladder (include/bmm_mcmc.h "parallel tempering") ----
 // who may be a rung
 static int temper_refused(const bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (c->na_on) return na_refuses("parallel tempering");
+    if (c->cs_on) return cs_refuses("parallel tempering");
     if (explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "parallel tempering is offered for the collapsed and DP samplers only: the stick-breaking "
                        "and full samplers carry theta, and the power sits on the likelihood with theta integrated out");
@@ -5970,6 +6139,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
         if (rc == BMM_OK) rc = ecr_run_check(opts, nsamples - burnin, N, K);
         if (rc == BMM_OK) rc = pc_run_check(opts, P, K);
         if (rc == BMM_OK) rc = na_run_check(opts, N, P);
+        if (rc == BMM_OK) rc = cs_run_check(opts, N, K);
         if (rc) return rc;
         for (double& v : g_phase_ms) v = 0.0;
         PhaseClock clock;
@@ -6003,6 +6173,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             }
             if (rc == BMM_OK) rc = init_run_attach(c, opts);
             if (rc == BMM_OK) rc = na_run_attach(c, opts);  // the cells are filled before anything counts them
+            if (rc == BMM_OK) rc = cs_run_attach(c, opts);  // the starting labels are projected when the chain starts
             if (rc) return rc;
             clock.lap(0);
             // what the options record per kept sweep: each ends, and waits for the stream before its rows go, on every way out
@@ -6019,6 +6190,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             rc = run_body(c, nsamples, io, opts);
             rc = temper_run_collect(c, opts, temper, rc);
             rc = na_run_collect(c, opts, rc);
+            rc = cs_run_collect(c, opts, rc);
             rc = pc_run_collect(c, opts, pc_rec, rc);
             rc = lp_run_collect(c, opts, lp_rec, rc);
             rc = sm_run_collect(c, opts, rc);
@@ -6256,6 +6428,7 @@ int bmm_alloc_run(const int32_t* X, int64_t N, int P, const int32_t* initialK, i
                   int32_t* k_out, int64_t moves_out[4]) {
     RunOptions opts = take_run_options();
     if (opts.na.on) return set_err(BMM_E_UNSUPPORTED, "missing cells (bmm_set_missing) are not offered by the allocation sampler's run");
+    if (opts.cs.on) return set_err(BMM_E_UNSUPPORTED, "constrained rows (bmm_set_constraints) are not offered by the allocation sampler's run");
     if (!log_prior_k || !k_out) return set_err(BMM_E_ARG, "null buffer");
     if (!(a > 0.0)) return set_err(BMM_E_ARG, "a must be > 0");
     if (maxK > kMaxCats) return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is offered up to maxK = %d", kMaxCats);
@@ -6413,6 +6586,16 @@ int bmm_set_missing(const int64_t* rows, const int32_t* cols, int64_t n_cells, c
     g_armed.na.on = out != nullptr;
     g_armed.na.rows = rows; g_armed.na.cols = cols; g_armed.na.n = n_cells;
     g_armed.na.o = out ? *out : bmm_missing_out{};
+    return BMM_OK;
+}
+int bmm_set_constraints(int64_t n, const int64_t* rows, const uint64_t* masks) {
+    g_armed.cs.on = n != 0;
+    g_armed.cs.n = n; g_armed.cs.rows = rows; g_armed.cs.masks = masks;
+    return BMM_OK;
+}
+int bmm_last_constraint_stats(int64_t* proposed, int64_t* reverted) {
+    if (!proposed || !reverted) return set_err(BMM_E_ARG, "null argument");
+    *proposed = g_cs_stats[0]; *reverted = g_cs_stats[1];
     return BMM_OK;
 }
 int bmm_set_pair_check(const bmm_pair_check_out* out) {
@@ -6586,11 +6769,13 @@ int bmm_multi_run(int sampler, int n_chains, const int* devices, const int32_t* 
                   double gamma, double a, double b, int burnin, int64_t batch, uint64_t seed,
                   double* const* pi_out, int32_t* const* z_out, double* const* theta_out,
                   double* const* alpha_out) {
-    const bool na_armed = take_run_options().na.on;  // a run of several chains disarms whatever was armed ...
+    const RunOptions armed = take_run_options();  // a run of several chains disarms whatever was armed ...
+    const bool na_armed = armed.na.on, cs_armed = armed.cs.on;
     const RunOptions opts;     // ... and runs every chain without it
     return guarded([&]() -> int {
         // (... but does not run over a matrix whose holes were zeroed as if nothing had been said)
         if (na_armed) return set_err(BMM_E_UNSUPPORTED, "missing cells (bmm_set_missing) are not offered by a run of several chains: they share one matrix");
+        if (cs_armed) return set_err(BMM_E_UNSUPPORTED, "constrained rows (bmm_set_constraints) are not offered by a run of several chains");
         if (sampler < 0 || sampler > 3) return set_err(BMM_E_ARG, "unknown sampler %d", sampler);
         if (n_chains < 1) return set_err(BMM_E_ARG, "n_chains must be >= 1");
         if (!z_out || !theta_out || !alpha_out) return set_err(BMM_E_ARG, "null output table");

@@ -2205,6 +2205,115 @@ __global__ __launch_bounds__(256) void k_count_labels_generic(ChainParams p, con
     }
 }
 
+// ---- constrained allocations: known labels and allowed-label sets (include/bmm_mcmc.h "constraints"; DESIGN.md
+// section 25) ----
+// Behind a resample launch over [lo, hi): every listed row of that range whose drawn label lies outside its set goes
+// back to the label it had (z_in; the lowest allowed label where it had none), and the move the resample launch has
+// just flushed for it is undone in the same delta set: -1 at the drawn label, +1 at the restored one, for Nk and for
+// every set feature of the row.  The next consumer of the deltas (a table build, k_sb_params, k_count_sweep_end) sums
+// them, so the row never appears moved.  One lane per listed row; integer LDS and global atomics and plain stores only:
+// the result does not depend on any order.
+// project: the other use, outside a sweep -- a listed row whose label lies outside its set takes its
+// (label mod |set|)-th allowed label (the rule of the starting labels); dNk = null where nothing has counted the labels
+// yet, stats = null.
+struct ConstrainArgs {
+    const int64_t* rows;    // the listed rows of the range, ascending
+    const uint64_t* masks;  // bit k of masks[q]: rows[q] may take label k
+    int64_t n;
+    const int32_t* z_in;    // null: the rows had no labels (the first sweep of a DP or explicit chain)
+    int32_t* z_out;
+    const int32_t* X;       // the chain's matrix: int32 (the generic twin) ...
+    const uint32_t* Xb;     // ... or bit planes
+    int32_t *dNk, *dS;      // the pending delta set, kDeltaReps replicas of each
+    unsigned long long* stats;  // [0] listed rows drawn, [1] reverted
+    int project;
+};
+__device__ __forceinline__ int constrain_nth_allowed(uint64_t mask, int n) {
+    for (int t = 0; t < n; ++t) mask &= mask - 1;
+    return __ffsll((long long)mask) - 1;
+}
+// the label a listed row is to hold given the one it holds now (zd); `moves`: whether that is another one
+__device__ __forceinline__ int constrain_target(const ConstrainArgs& a, int64_t i, uint64_t mask, int zd, bool& moves) {
+    const bool inside = zd >= 0 && zd < 64 && ((mask >> zd) & 1ull);
+    moves = !inside && !(a.project && zd < 0);
+    if (!moves) return zd;
+    if (a.project) return constrain_nth_allowed(mask, zd % __popcll(mask));
+    const int zp = a.z_in ? a.z_in[i] : -1;
+    return zp >= 0 ? zp : __ffsll((long long)mask) - 1;
+}
+__device__ __forceinline__ void constrain_stats(const ConstrainArgs& a, unsigned long long reverted, int tid) {
+    if (!a.stats) return;
+    if ((tid & 63) == 0 && reverted) atomicAdd(&a.stats[1], reverted);
+    if (blockIdx.x == 0 && tid == 0) atomicAdd(&a.stats[0], (unsigned long long)a.n);
+}
+__global__ __launch_bounds__(256) void k_constrain(ChainParams p, ConstrainArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int32_t* const hist = reinterpret_cast<int32_t*>(smem);
+    const int P = p.P, K = p.K, tid = threadIdx.x, lane = tid & 63;
+    if (a.dNk) {
+        for (int i = tid; i < K * P + K; i += 256) hist[i] = 0;
+        __syncthreads();
+    }
+    unsigned long long reverted = 0;  // of this wave (uniform)
+    const int64_t ntiles = (a.n + 255) / 256;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t q = tile * 256 + tid;
+        const bool valid = q < a.n;
+        const int64_t qc = valid ? q : a.n - 1;
+        const int64_t i = a.rows[qc];
+        const uint64_t mask = a.masks[qc];
+        const int zd = a.z_out[i];
+        bool moves;
+        const int zr = constrain_target(a, i, mask, zd, moves);
+        moves = moves && valid;
+        uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+        if (moves) {
+            a.z_out[i] = zr;
+            if (a.dNk) load_words(a.Xb, p.N, (P + 31) / 32, i, b0, b1, b2, b3);
+        }
+        if (a.dNk) count_movers(moves, zd, zr, b0, b1, b2, b3, hist, K, P, lane);  // (uniform)
+        reverted += (unsigned long long)__popcll(__ballot(moves));
+    }
+    if (a.dNk) {
+        __syncthreads();
+        flush_hist(hist, K, P, a.dS + (size_t)(blockIdx.x % kDeltaReps) * K * P, a.dNk + (blockIdx.x % kDeltaReps) * K, tid, 256);
+    }
+    constrain_stats(a, reverted, tid);
+}
+// ... for a chain on the generic path or the int32 layout: the adds go straight to the replica, as k_resample_generic's do
+__global__ __launch_bounds__(256) void k_constrain_generic(ChainParams p, ConstrainArgs a) {
+    const int P = p.P, K = p.K, tid = threadIdx.x;
+    unsigned long long reverted = 0;
+    const int64_t ntiles = (a.n + 255) / 256;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t q = tile * 256 + tid;
+        const bool valid = q < a.n;
+        const int64_t qc = valid ? q : a.n - 1;
+        const int64_t i = a.rows[qc];
+        const uint64_t mask = a.masks[qc];
+        const int zd = a.z_out[i];
+        bool moves;
+        const int zr = constrain_target(a, i, mask, zd, moves);
+        moves = moves && valid;
+        if (moves) {
+            a.z_out[i] = zr;
+            if (a.dNk) {
+                int32_t* const rNk = a.dNk + (blockIdx.x % kDeltaReps) * K;
+                int32_t* const rS = a.dS + (size_t)(blockIdx.x % kDeltaReps) * K * P;
+                atomicAdd(&rNk[zr], 1);
+                if (zd >= 0) atomicAdd(&rNk[zd], -1);
+                for (int d = 0; d < P; ++d)
+                    if (a.Xb ? (a.Xb[(int64_t)(d >> 5) * p.N + i] >> (d & 31)) & 1u : (uint32_t)a.X[i + (int64_t)d * p.N] & 1u) {
+                        atomicAdd(&rS[(size_t)zr * P + d], 1);
+                        if (zd >= 0) atomicAdd(&rS[(size_t)zd * P + d], -1);
+                    }
+            }
+        }
+        reverted += (unsigned long long)__popcll(__ballot(moves));
+    }
+    constrain_stats(a, reverted, tid);
+}
+
 // The allocation probabilities of one batch, normalised and filed by label: the matrix the reference
 // stores for Stephens' relabelling (collapsed_gibbs.cpp:162-172, collapsed_gibbs_dp.cpp:190-200,
 // stickbreaking.cpp:129-139).  wts/wtot are what the resample kernel of this batch emitted;

@@ -1309,6 +1309,47 @@ typedef struct bmm_missing_out {
 } bmm_missing_out;
 int bmm_set_missing(const int64_t* rows, const int32_t* cols, int64_t n_cells, const bmm_missing_out* out);
 
+/* ---- constraints: known labels and allowed-label sets ---------------------------------------------
+ * Partial knowledge of the rows' classes.  A constrained row i has a non-empty set A_i of labels it may take, given as a
+ * 64-bit mask (bit k: label k, 0-based); a known label is the singleton set.  Rows that are not listed are free.
+ *   The move.  The sweep draws a listed row as it draws every row, a proposal k' from its full conditional.  If k' is in
+ * A_i the draw stands; if not, the row keeps the label it had.  The target is the conditional restricted to A_i, the
+ * proposal is the unrestricted conditional, so the Metropolis-Hastings ratio is 1 inside A_i and 0 outside: the move is
+ * exact and carries no weight; under a batch it is exact to the degree the unconstrained sweep is.  A row with a
+ * singleton set never moves.  The revert (k_constrain, behind every resample launch whose range holds a listed row)
+ * also undoes the row's move in the pending count deltas, so no table and no statistic ever sees the row moved.
+ *   Starting labels.  A listed row of the finite collapsed chain whose starting label z0 (0-based) lies outside A_i
+ * starts at its (z0 mod |A_i|)-th allowed label, counted from the lowest, projected on the device before the labels
+ * are counted.  The same rule puts the rows of a chain that is armed between sweeps inside their sets, and the counts
+ * follow.  A row of a DP, stick-breaking or full chain that is seated by the chain's first sweep and drawn outside A_i
+ * there takes its lowest allowed label.
+ *   Labels.  Masks name the chain's own labels.  On the finite and the full sampler label k is a class.  On the DP and
+ * the stick-breaking sampler (K = maxK) a label is whatever cluster holds it: singleton masks, which pin a cluster to a
+ * label by the rows held there, are the intended use; a DP label that no held row occupies is an ordinary free label,
+ * and free rows may open new clusters as they always do.
+ *
+ * bmm_chain_set_constraints: rows[n] 0-based and strictly ascending, masks[n] non-zero with no bit at or above K.  Before
+ * the chain has started or between sweeps.  n = 0 withdraws the constraints: the rows are free from the next sweep on.
+ * From then on every sweep of bmm_chain_sweeps* reverts; a sweep of a chain without constraints enqueues exactly what it
+ * always did.  The draws of held rows are still computed (the resample kernels are untouched).
+ *   BMM_E_ARG: a row out of range or out of order, an empty set, a label at or above K.  BMM_E_UNSUPPORTED: a sharded
+ * chain; together, in either order, with split-merge moves, parallel tempering (a ladder), the leave-one-out summary,
+ * the allocation sampler, bmm_chain_init_labels, bmm_chain_set_labels and bmm_chain_sweep_probs (the emitted rows would
+ * be those of reverted draws).  BMM_E_STATE: constraints already set, inside a run.  All of these are answered before a
+ * device is touched.  Unchanged beside it: the predictive of new rows, the partition summary, ECR, the log joint (of
+ * the whole state, held rows included), the pair check, feature selection and missing cells. */
+int bmm_chain_set_constraints(bmm_chain* c, int64_t n, const int64_t* rows, const uint64_t* masks);
+/* since the constraints were last set: proposed, the listed rows drawn (listed rows x sweeps); reverted, those drawn
+ * outside their set.  Integer counts: one seed gives the same values twice.  Readable after a withdrawal. */
+int bmm_chain_constraint_stats(bmm_chain* c, int64_t* proposed, int64_t* reverted);
+/* For a run: armed per calling thread for the NEXT bmm_collapsed_run / bmm_dp_run / bmm_sb_run / bmm_full_run (and their
+ * _probs form without hooks, and _predict) of that thread and disarmed when that call returns; n = 0 disarms and is the
+ * run without it, byte for byte.  rows and masks must live until the run returns.  BMM_E_ARG and BMM_E_UNSUPPORTED as
+ * above, also for bmm_set_init and a *_run_relabel / hooked *_run_probs hand-off; bmm_multi_run and bmm_alloc_run
+ * answer armed constraints with BMM_E_UNSUPPORTED.  bmm_last_constraint_stats: the counters of the thread's last run. */
+int bmm_set_constraints(int64_t n, const int64_t* rows, const uint64_t* masks);
+int bmm_last_constraint_stats(int64_t* proposed, int64_t* reverted);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
