@@ -22,7 +22,7 @@ __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "
            "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
            "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
            "partition_distances", "posterior_similarity", "partition_plan", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
-           "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat", "pair_check", "pair_check_plan", "pair_check_pairs", "PAIR_CHECK_MAX_M", "Ladder", "temper_ladder", "TEMPER_MAX_RUNGS"]
+           "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat", "pair_check", "pair_check_plan", "pair_check_pairs", "PAIR_CHECK_MAX_M", "run_bytes", "summary_plan", "Ladder", "temper_ladder", "TEMPER_MAX_RUNGS"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -956,6 +956,143 @@ SPLIT_MERGE_SCANS = 5  # the default of split_merge_scans (DESIGN.md section 15 
 _SM_FIELDS = ("split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped")
 
 
+# ---------------------------------------------------------------- summary=: online pivot relabelling, memberships
+_SUMMARY_PIVOT_NONE, _SUMMARY_PIVOT_FIRST, _SUMMARY_PIVOT_GIVEN = 0, 1, 2
+_SUMMARY_PLAN_FIELDS = ("threads", "fold_workgroups", "grid_cap", "pitch", "fold_lds_bytes", "profile_workgroups",
+                        "finish_workgroups", "finish_lds_bytes", "bytes_counts", "bytes_block", "launches_pivot",
+                        "launches_plain")
+
+
+class _SummaryOpts(_C.Structure):  # bmm_summary_opts
+    _fields_ = [("pivot_kind", _C.c_int), ("pivot", _C.c_void_p), ("stride", _C.c_int), ("keep_trace", _C.c_int)]
+
+
+class _SummaryOut(_C.Structure):  # bmm_summary_out
+    _fields_ = [("pivot", _C.c_void_p), ("z_hat", _C.c_void_p), ("n_max", _C.c_void_p), ("n_folded", _C.c_void_p),
+                ("size_sum", _C.c_void_p), ("theta_sum", _C.c_void_p), ("theta_sq", _C.c_void_p), ("theta_n", _C.c_void_p),
+                ("alpha_sum", _C.c_void_p), ("agree", _C.c_void_p), ("permutations", _C.c_void_p), ("counts", _C.c_void_p)]
+
+
+def _summary_pivot(pivot, N):
+    """summary_pivot= of a wrapper: (kind, labels or None); the labels' range is the library's to check"""
+    if pivot is None:
+        return _SUMMARY_PIVOT_NONE, None
+    if isinstance(pivot, str):
+        if pivot != "first":
+            raise ValueError('summary_pivot must be "first", None or N labels')
+        return _SUMMARY_PIVOT_FIRST, None
+    pv = _np.ascontiguousarray(pivot, dtype=_np.int32).ravel()
+    if pv.shape != (N,):
+        raise ValueError("summary_pivot must have one label per observation")
+    return _SUMMARY_PIVOT_GIVEN, pv
+
+
+class _SummaryFold:
+    """the host side of a summary: the buffers a bmm_summary_out points at, and the result derived from them"""
+
+    def __init__(self, N, K, P, pivot, stride, counts=False, S=0, keep_trace=True):
+        kind, self.given = _summary_pivot(pivot, N)
+        self.N, self.keep_trace = N, bool(keep_trace)
+        self.pivot = _np.zeros(N, dtype=_np.int32)
+        self.z_hat = _np.zeros(N, dtype=_np.int32)
+        self.n_max = _np.zeros(N, dtype=_np.uint32)
+        self.n_folded = _C.c_int(0)
+        self.size_sum = _np.zeros(K, dtype=_np.int64)
+        self.theta_sum = _np.zeros((K, P), order="F")
+        self.theta_sq = _np.zeros((K, P), order="F")
+        self.theta_n = _np.zeros(K, dtype=_np.int32)
+        self.alpha_sum = _np.zeros(2)
+        self.agree = _np.full(S, -1, dtype=_np.int64) if S else None
+        self.perms = _np.empty((S, K), dtype=_np.int32, order="F") if S else None
+        self.counts = _np.zeros((N, K), dtype=_np.uint32, order="F") if counts else None
+        self.opts = _SummaryOpts(kind, None if self.given is None else self.given.ctypes.data, int(stride), int(self.keep_trace))
+        self.s = _SummaryOut(self.pivot.ctypes.data, self.z_hat.ctypes.data, self.n_max.ctypes.data, _C.addressof(self.n_folded),
+                             self.size_sum.ctypes.data, self.theta_sum.ctypes.data, self.theta_sq.ctypes.data,
+                             self.theta_n.ctypes.data, self.alpha_sum.ctypes.data,
+                             None if self.agree is None else self.agree.ctypes.data,
+                             None if self.perms is None else self.perms.ctypes.data,
+                             None if self.counts is None else self.counts.ctypes.data)
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_summary(_C.byref(self.opts), _C.byref(self.s)))
+
+    def result(self):
+        n = self.n_folded.value
+        tn = self.theta_n.astype(_np.float64)[:, None]
+        with _np.errstate(divide="ignore", invalid="ignore"):
+            mean = self.theta_sum / tn
+            sd = _np.sqrt(_np.maximum(self.theta_sq / tn - mean * mean, 0.0))
+            total = self.size_sum.sum()
+            pi_mean = self.size_sum / float(total) if total else _np.full(self.size_sum.shape, _np.nan)
+        out = {"pivot": None if self.opts.pivot_kind == _SUMMARY_PIVOT_NONE else self.pivot, "z_hat": self.z_hat,
+               "n_max": self.n_max, "n_folded": n, "size_sum": self.size_sum, "pi_mean": pi_mean,
+               "theta_sum": self.theta_sum, "theta_sq": self.theta_sq, "theta_n": self.theta_n, "theta_mean": mean,
+               "theta_sd": sd, "alpha_mean": self.alpha_sum[0] / n if n else float("nan"), "alpha_sum": self.alpha_sum,
+               "agree": self.agree, "permutations": self.perms}
+        if self.counts is not None:
+            out["counts"] = self.counts
+        return out
+
+
+def _make_summary(summary, pivot, stride, keep_trace, N, K, P, S, chains, relabel=False, partition=None, similarity_of=None):
+    """summary= and keep_trace= of a wrapper: the outputs to arm, None when off.  What the wrapper itself cannot run is
+    refused here, before a device is touched; the library refuses the rest with its codes (include/bmm_mcmc.h)."""
+    on = not (summary is None or summary is False)
+    if not on:
+        if not keep_trace:
+            raise ValueError("keep_trace=False drops the label trace: it needs summary=, which folds the labels on the device")
+        return None
+    if not (summary is True or (isinstance(summary, str) and summary == "counts")):
+        raise ValueError('summary must be True, "counts" or None')
+    if int(chains) > 1:
+        raise ValueError("summary= is offered per chain (chains=1)")
+    if relabel:
+        raise ValueError("summary= relabels against its pivot as the chain runs: not together with relabel= (two relabellings)")
+    if not keep_trace and (partition is not None or similarity_of is not None):
+        raise ValueError("keep_trace=False drops the label trace, which partition= and similarity_of= read")
+    return _SummaryFold(N, K, P, pivot, stride, counts=summary == "counts", S=S, keep_trace=keep_trace)
+
+
+def _with_summary(out, su):
+    if su is not None:
+        out["summary"] = su.result()
+        if not su.keep_trace:
+            out["z"] = None
+    return out
+
+
+def _z_trace(S, N, su):
+    """the (S, N) label trace a run fills, or None for a run that keeps none (keep_trace=False)"""
+    if su is not None and not su.keep_trace:
+        return None
+    return _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
+
+
+def _vp0(a):
+    return None if a is None else _capi.vp(a)
+
+
+def run_bytes(sampler, N, P, K, S, keep_trace=True, summary=False):
+    """The bytes of device memory a run's own buffers take (bmm_run_bytes): the theta, alpha and pi traces, with
+    keep_trace the S x N label trace and the two staging blocks of its way out, and with summary the summary's block
+    (K planes of N counters, N-sized pivot and outputs, the sums) and its per-sweep rows.  The chain's resident state
+    (the bit planes of X, two label rows, the tables) is not part of it.  Pure: no device is touched."""
+    code = _capi.SAMPLER_CODE[sampler] if isinstance(sampler, str) else int(sampler)
+    v = _capi.lib().bmm_run_bytes(_C.c_int(code), _C.c_int64(int(N)), _C.c_int(int(P)), _C.c_int(int(K)), _C.c_int(int(S)),
+                        _C.c_int(int(bool(keep_trace))), _C.c_int(int(bool(summary))))
+    if v < 0:
+        raise ValueError("run_bytes: sampler, N, P, K and S must name a run")
+    return int(v)
+
+
+def summary_plan(N, P, K):
+    """The launch shapes of the summary's kernels and the bytes of its block (bmm_summary_plan), read from the function
+    the launches read without touching a device: a dict of the fields include/bmm_mcmc.h lists."""
+    out = (_C.c_int64 * 12)()
+    _capi.check(_capi.lib().bmm_summary_plan(_C.c_int64(int(N)), _C.c_int(int(P)), _C.c_int(int(K)), out))
+    return dict(zip(_SUMMARY_PLAN_FIELDS, (int(v) for v in out)))
+
+
 class _SplitMergeStep(_C.Structure):  # bmm_split_merge_step
     _fields_ = [("row_i", _C.c_int64), ("row_j", _C.c_int64), ("label_a", _C.c_int32), ("label_b", _C.c_int32),
                 ("kind", _C.c_int32), ("accepted", _C.c_int32), ("members", _C.c_int64), ("n_before", _C.c_int64 * 2),
@@ -1276,7 +1413,7 @@ class _Init:
 
 
 def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None, lp=None, tp=None, pc=None,
-         mi=None, cs=None):
+         mi=None, cs=None, su=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
@@ -1300,6 +1437,8 @@ def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=
         mi.arm()
     if cs is not None:
         cs.arm()
+    if su is not None:
+        su.arm()
     if init is not None:  # last, just ahead of the call: a run of another sampler refuses an armed start
         init.arm()
     if pr is None:
@@ -1459,7 +1598,8 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                     responsibilities=False, partition=None, partition_stride=1, similarity_of=None, loo=False,
                     select_features=False, rho=0.5, init="random", init_iters=INIT_ITERS, ecr_pivot="iterative",
                     ecr_max_iter=50, logpost=False, temper=None, swap_every=1, temper_hottest=0.1, pair_check=None,
-                    pair_check_stride=1, pair_check_trace=False, missing=None, known=None, allowed=None):
+                    pair_check_stride=1, pair_check_trace=False, missing=None, known=None, allowed=None, summary=None,
+                    summary_pivot="first", summary_stride=1, keep_trace=True):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -1560,6 +1700,22 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     those reverted and their share (how sticky partial sets are).  Works with newdata=, partition=, relabel="ecr",
     logpost= (the joint of the whole state, held rows included), pair_check=, select_features= and missing=; not with
     chains > 1, loo=, temper=, init="kmodes", relabel=True (or split_merge= on gibbs_dp, or gibbs_allocation).
+    `summary=True`: what a latent-class user takes out of a run, under one labelling, folded on the device behind the kept
+    sweeps (include/bmm_mcmc.h "posterior summary").  Every `summary_stride`-th kept sweep is
+    relabelled against a pivot allocation as relabel="ecr" would relabel it (`summary_pivot="first"`: the first kept
+    state that is assigned, copied device to device; an array of N labels in 1..K, e.g. the partition= estimate of a
+    short pilot run; None: no relabelling, the state is folded as sampled -- the choice with known=, where held rows pin
+    the labelling) and folded into per-row membership counters and per-class sums.  The result gains `summary = {"pivot",
+    "z_hat" (N,): each row's most frequent class, 1-based, the lowest on a tie; "n_max" (N,): in how many folded sweeps
+    it sat there, so n_max / n_folded is how sure the row is; "n_folded"; "size_sum" (K,) int64, "pi_mean" (K,): the
+    classes' sizes added over the folded sweeps and their shares; "theta_sum", "theta_sq" (K, P), "theta_n" (K,),
+    "theta_mean", "theta_sd": the classes' item profiles (a sweep in which a class was empty is left out of its row);
+    "alpha_mean"; "agree" (S,) int64 and "permutations" (S, K) int32, 0-based, per kept sweep: -1 and the identity where a
+    sweep was not folded}`.  `summary="counts"` adds "counts", the (N, K) uint32 memberships (4 N K bytes).  It reads
+    state only: z, theta and alpha are those of the run without it, byte for byte.  `keep_trace=False` (needs summary=):
+    the run carves no S x N label trace on the device and none on the host, `z` is None, theta and alpha stay; run_bytes()
+    tells what either run takes.  Per chain (chains=1); not with relabel=, temper= (two relabellings; a ladder), and
+    keep_trace=False not with partition=, similarity_of=.
     """
     data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
@@ -1582,8 +1738,11 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
     pc = _make_pair_check(pair_check, pair_check_stride, pair_check_trace, P, nsamples - burnin, chains)
     tp = _make_temper(temper, swap_every, nsamples - burnin, chains, temper_hottest)
+    su = _make_summary(summary, summary_pivot, summary_stride, keep_trace, N, K, P, nsamples - burnin, chains,
+                       bool(relabel) or ecr_req is not None, partition, similarity_of)
 
     def done(out):
+        out = _with_summary(out, su)
         if tp is not None:
             out["temper"] = tp.result()
         if fs is not None:
@@ -1640,15 +1799,15 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
-    z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
+    z = _z_trace(S, N, su)
     theta = _np.zeros((K, P, S), order="F")
     al = _np.zeros((S, 1), order="F")
     args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(K),
             _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
-            _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
+            _C.c_uint64(seed), _C.c_int(device), _vp0(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs, su=su)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1662,7 +1821,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
              partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None,
              select_features=False, rho=0.5, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
              temper=None, swap_every=1, temper_hottest=0.1, pair_check=None, pair_check_stride=1, pair_check_trace=False,
-             missing=None, known=None, allowed=None):
+             missing=None, known=None, allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
@@ -1677,7 +1836,8 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     gibbs_collapsed, but the values name the chain's labels 1..maxK: the rows known to share a class hold one label, which
     pins that cluster there; a label that no held row occupies is an ordinary free label, and the free rows open new
     clusters as ever (the semi-supervised, novelty-detection run).  Not with split_merge=.  `allowed=` is refused here
-    (ValueError): a label is whatever cluster holds it, so a set of labels says nothing about classes."""
+    (ValueError): a label is whatever cluster holds it, so a set of labels says nothing about classes.  `summary`,
+    `summary_pivot`, `summary_stride`, `keep_trace`: as gibbs_collapsed, over the maxK labels."""
     _init_kind(init, 0, allowed=False)
     data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
@@ -1696,8 +1856,11 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
     pc = _make_pair_check(pair_check, pair_check_stride, pair_check_trace, P, nsamples - burnin, chains)
     tp = _make_temper(temper, swap_every, nsamples - burnin, chains, temper_hottest)
+    su = _make_summary(summary, summary_pivot, summary_stride, keep_trace, N, maxK, P, nsamples - burnin, chains,
+                       bool(relabel) or ecr_req is not None, partition, similarity_of)
 
     def done(out):
+        out = _with_summary(out, su)
         if tp is not None:
             out["temper"] = tp.result()
         if sm is not None:
@@ -1735,16 +1898,16 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, maxK, P, S)
-    z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
+    z = _z_trace(S, N, su)
     theta = _np.zeros((maxK, P, S), order="F")
     al = _np.zeros((S, 1), order="F")
     args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(nsamples),
             _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int(maxK),
-            _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
+            _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _vp0(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
+        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs, su=su)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1756,7 +1919,8 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
               device, initial_pi, initial_theta, chains, devices, stephens, debug=False, newdata=None,
               predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None,
               loo=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1,
-              pair_check_trace=False, missing=None, known=None, allowed=None):
+              pair_check_trace=False, missing=None, known=None, allowed=None, summary=None, summary_pivot="first",
+              summary_stride=1, keep_trace=True):
     data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
     N, P = X.shape
@@ -1773,8 +1937,11 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
     lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
     pc = _make_pair_check(pair_check, pair_check_stride, pair_check_trace, P, nsamples - burnin, chains)
     base = fn[len("bmm_"):-len("_run_probs")]
+    su = _make_summary(summary, summary_pivot, summary_stride, keep_trace, N, K, P, nsamples - burnin, chains,
+                       bool(relabel) or ecr_req is not None, partition, similarity_of)
 
     def done(out):
+        out = _with_summary(out, su)
         return _with_constraints(_with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc), mi), cs)
 
     def start(sd, pi, th):
@@ -1825,16 +1992,16 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
         return done(_with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
-    z = _np.empty((S, N), dtype=_np.int32, order="F")  # every cell is written by the library
+    z = _z_trace(S, N, su)
     theta = _np.zeros((K, P, S), order="F")
     al = _np.zeros((S, 1), order="F")
     pi = _np.zeros((S, K), order="F")
     args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(pi0), _capi.vp(th0), _C.c_int(nsamples),
             _C.c_int(K), _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta),
             _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
-            _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
+            _C.c_int(device), _capi.vp(pi), _vp0(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec, lp=lp, pc=pc, mi=mi, cs=cs)
+        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec, lp=lp, pc=pc, mi=mi, cs=cs, su=su)
     out = {"pi": pi, "alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1848,7 +2015,7 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
                         predictive_trace=False, responsibilities=False, partition=None, partition_stride=1,
                         similarity_of=None, loo=False, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
                         pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None, known=None,
-                        allowed=None):
+                        allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
     src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
@@ -1860,7 +2027,8 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
     return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
                      burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed)
+                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed,
+                     summary, summary_pivot, summary_stride, keep_trace)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
@@ -1868,16 +2036,18 @@ def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, bur
                devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False,
                partition=None, partition_stride=1, similarity_of=None, loo=False, init="random", ecr_pivot="iterative",
                ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None,
-               known=None, allowed=None):
+               known=None, allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True):
     """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
     "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`, `pair_check`,
-    `pair_check_stride`, `pair_check_trace`, `missing`, `known`, `allowed`: as gibbs_collapsed."""
+    `pair_check_stride`, `pair_check_trace`, `missing`, `known`, `allowed`, `summary`, `summary_pivot`, `summary_stride`,
+    `keep_trace`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
     return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
                      relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed)
+                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed,
+                     summary, summary_pivot, summary_stride, keep_trace)
 
 
 class Chain:
@@ -2210,6 +2380,51 @@ class Chain:
 
     def pair_check_reset(self):
         _capi.check(_capi.lib().bmm_chain_pair_check_reset(self._h))
+
+    # -- posterior summary (include/bmm_mcmc.h "posterior summary")
+    def set_summary(self, pivot="first", stride=1, on=True):
+        """Arm the summary: `pivot` "first" (the state after the first sweep of sweeps_summary), N labels in 1..K, or None
+        (the state is folded as sampled); every `stride`-th sweep of sweeps_summary is folded.  on=False disarms and frees
+        its memory.  Arming an armed chain empties the fold."""
+        if not on:
+            _capi.check(_capi.lib().bmm_chain_set_summary(self._h, None))
+            self._sum = None
+            return
+        fold = _SummaryFold(self.N, self.K, self.P, pivot, stride)
+        _capi.check(_capi.lib().bmm_chain_set_summary(self._h, _C.byref(fold.opts)))
+        self._sum = (pivot, int(stride))
+
+    def _sum_armed(self):
+        if getattr(self, "_sum", None) is None:
+            raise _capi.BmmError(5, "the summary is not armed (Chain.set_summary)")
+        return self._sum
+
+    def summary_state(self):
+        """{"permutation" (K,) int32, 0-based, "agree"} of the current state against the pivot: no sweep, the fold untouched"""
+        self._sum_armed()
+        perm, agree = _np.zeros(self.K, dtype=_np.int32), _C.c_int64(0)
+        _capi.check(_capi.lib().bmm_chain_summary_state(self._h, _capi.vp(perm), _C.byref(agree)))
+        return {"permutation": perm, "agree": int(agree.value)}
+
+    def sweeps_summary(self, n, trace=False):
+        """n more sweeps, sweeps 0, stride, 2 stride, ... of them folded; trace=True returns {"agree" (n,), "permutations"
+        (n, K)}, -1 and the identity where a sweep was not folded, and waits"""
+        self._sum_armed()
+        n = int(n)
+        agree = _np.full(n, -1, dtype=_np.int64) if trace else None
+        perms = _np.empty((n, self.K), dtype=_np.int32, order="F") if trace else None
+        _capi.check(_capi.lib().bmm_chain_sweeps_summary(self._h, _C.c_int(n), _vp0(agree), _vp0(perms)))
+        return {"agree": agree, "permutations": perms} if trace else None
+
+    def summary(self, counts=False):
+        """the fold so far: the summary of a run's out["summary"] (without its per-sweep "agree" and "permutations")"""
+        pivot, stride = self._sum_armed()
+        fold = _SummaryFold(self.N, self.K, self.P, pivot, stride, counts=counts)
+        _capi.check(_capi.lib().bmm_chain_get_summary(self._h, _C.byref(fold.s)))
+        return fold.result()
+
+    def summary_reset(self):
+        _capi.check(_capi.lib().bmm_chain_summary_reset(self._h))
 
     def set_split_merge(self, moves_per_sweep, scans=SPLIT_MERGE_SCANS):
         """`moves_per_sweep` moves at the start of every sweep from the second (0: off), `scans` intermediate scans each."""

@@ -53,6 +53,8 @@ SYMBOLS = [
     "bmm_chain_set_missing", "bmm_chain_impute_step", "bmm_chain_get_missing_state", "bmm_chain_get_missing_summary",
     "bmm_chain_missing_reset", "bmm_set_missing",
     "bmm_chain_set_constraints", "bmm_chain_constraint_stats", "bmm_set_constraints", "bmm_last_constraint_stats",
+    "bmm_set_summary", "bmm_run_bytes", "bmm_summary_plan", "bmm_chain_set_summary", "bmm_chain_summary_state",
+    "bmm_chain_sweeps_summary", "bmm_chain_get_summary", "bmm_chain_summary_reset",
 ]
 
 
@@ -103,6 +105,16 @@ def load(path):
         L.bmm_chain_constraint_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.bmm_set_constraints.argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
         L.bmm_last_constraint_stats.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(L, "bmm_set_summary"):  # (an older build loaded for a comparison has no summary)
+        L.bmm_set_summary.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmm_run_bytes.restype = C.c_int64
+        L.bmm_run_bytes.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.bmm_summary_plan.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_void_p]
+        L.bmm_chain_set_summary.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmm_chain_summary_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bmm_chain_sweeps_summary.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.bmm_chain_get_summary.argtypes = [C.c_void_p, C.c_void_p]
+        L.bmm_chain_summary_reset.argtypes = [C.c_void_p]
     if hasattr(L, "bmm_ladder_create"):  # (an older build loaded for a comparison has no ladder)
         L.bmm_ladder_destroy.restype = None
         L.bmm_ladder_destroy.argtypes = [C.c_void_p]

@@ -487,6 +487,22 @@ struct SweepTrace {
     template <class T> T* row(int j) const { return p && j >= base ? reinterpret_cast<T*>(p + (size_t)(j - base) * row_bytes) : nullptr; }
 };
 
+// The posterior summary's device block, carved by sum_carve: the folds first (what a reset
+// zeroes), then the pivot, the outputs of k_sum_finish, an identity permutation, the live sweep's agreement and
+// permutation where no recording holds them, and the theta / alpha row of a sweep that no run trace records.
+struct SumBufs {
+    uint32_t* cnt = nullptr;  // [K][pitch]
+    double *theta_sum = nullptr, *theta_sq = nullptr, *alpha_acc = nullptr;
+    int32_t* theta_n = nullptr;
+    size_t fold_bytes = 0;
+    unsigned long long* size_sum = nullptr;
+    int32_t *pivot = nullptr, *z_hat = nullptr, *identity = nullptr, *perm_live = nullptr;
+    uint32_t* n_max = nullptr;
+    int64_t* agree_live = nullptr;
+    double *theta_row = nullptr, *alpha_row = nullptr;
+};
+struct EcrWork;
+
 }  // namespace
 
 struct bmm_chain {
@@ -688,6 +704,20 @@ struct bmm_chain {
     int64_t* dCsRows = nullptr;
     uint64_t* dCsMasks = nullptr;
     unsigned long long* dCsStats = nullptr;
+    // in_run: the chain belongs to a *_run call (run_prepare) -- its kept sweeps record theta, alpha and pi, and what
+    // is "not offered inside a run" is refused -- whether or not the run keeps a label trace (dTrace: keep_trace)
+    bool in_run = false;
+    // posterior summary: sum_on: a fold behind every stride-th sweep sum_rec names; one block
+    // of the device pool (sum) and the workspace of one row's ECR pass; sum_rec: the sweeps that are folded and the
+    // rows of (int64 agree, K int32 perm) they are recorded in
+    bool sum_on = false, sum_have_pivot = false;
+    int sum_pivot_kind = 0, sum_stride = 1, sum_folded = 0;
+    int64_t sum_pitch = 0;
+    char* dSumBlock = nullptr;
+    size_t sum_block_bytes = 0;  // as handed out by the device pool
+    SumBufs sum;
+    EcrWork* sum_ecr = nullptr;
+    SweepTrace sum_rec;
     // parallel tempering: temper_on: the table builds are k_temper_tables at inverse temperature
     // temper_b, and the kernel choice leaves out the forms that build their own tables and the packed one; ladder: the
     // replica ladder a run drives this chain through as its rung 0 (not owned)
@@ -779,6 +809,8 @@ struct RunOptions {
     struct { bool on = false; const double* log_prior_k = nullptr; int K0 = 0, moves = 0; double eject_a = 1.0; int32_t* k_out = nullptr; int64_t* moves_out = nullptr; } alloc;
     struct { int moves = 0, scans = 0; } as;  // bmm_set_alloc_split_merge: taken by bmm_alloc_run alone
     struct { bool on = false; int64_t n = 0; const int64_t* rows = nullptr; const uint64_t* masks = nullptr; } cs;  // bmm_set_constraints
+    struct { bool on = false; bmm_summary_opts opts{}; bmm_summary_out o{}; } summary;  // bmm_set_summary
+    bool keep_trace() const { return !summary.on || summary.opts.keep_trace != 0; }
     const bmm_relabel_hooks* hooks = nullptr;  // *_run_probs
     const bmm_relabel_out* rel = nullptr;      // *_run_relabel
     const int32_t* Xnew = nullptr; int64_t M = 0; const bmm_predict_out* pred = nullptr;  // *_run_predict
@@ -1453,9 +1485,12 @@ int pc_data_locked(const bmm_chain* c) {
     return BMM_OK;
 }
 // whether sweep j is one the check evaluates: folded, and a multiple of the stride from the recording's first row
-bool pc_folds(const bmm_chain* c, int j) {
-    return c->pc_on && c->pc_rec.folds(j) && (j - c->pc_rec.base) % c->pc_stride == 0;
-}
+bool stride_folds(const SweepTrace& rec, int stride, int j) { return rec.folds(j) && (j - rec.base) % stride == 0; }
+bool pc_folds(const bmm_chain* c, int j) { return c->pc_on && stride_folds(c->pc_rec, c->pc_stride, j); }
+// the posterior summary's share of a sweep end (defined with the ECR pass it enqueues)
+int sum_sweep_end(bmm_chain* c, int j);
+int sum_start_state(bmm_chain* c, const int32_t* row0);
+void sum_release(bmm_chain* c);
 // the end of sweep j: what a predictive run, a leave-one-out run, a log joint trace, a pair check or the resident calls
 // asked to fold
 int sweep_end_folds(bmm_chain* c, int j) {
@@ -1463,6 +1498,7 @@ int sweep_end_folds(bmm_chain* c, int j) {
     if (rc == BMM_OK && c->loo_rec.folds(j) && c->loo_on) rc = enqueue_loo(c, j, c->loo_rec.row<double>(j), true);
     if (rc == BMM_OK && c->lp_rec.folds(j) && c->lp_on && !c->fold_defer) rc = enqueue_log_joint(c, j, c->lp_rec.row<double>(j), true);
     if (rc == BMM_OK && pc_folds(c, j) && !c->fold_defer) rc = enqueue_pair_check(c, label_row(c, j), c->pc_rec.row<double>(j), true);
+    if (rc == BMM_OK && c->sum_on) rc = sum_sweep_end(c, j);
     return rc;
 }
 
@@ -1806,10 +1842,11 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
     const ChainParams& p = c->p;
     const int32_t* zin = (p.mode != MODE_COLLAPSED && j == 1) ? nullptr : label_row(c, j - 1);
     int32_t* zout = label_row(c, j);
-    const bool rec = c->dTrace && j >= c->burnin;
+    const bool rec = c->in_run && j >= c->burnin;
     const int s = j - c->burnin;
     double* th_tr = rec ? c->dThetaTrace + (size_t)s * p.K * p.P : nullptr;
     double* al_tr = rec ? c->dAlphaTrace + s : nullptr;
+    if (!rec && c->sum_on && c->sum_rec.folds(j)) { th_tr = c->sum.theta_row; al_tr = c->sum.alpha_row; }  // a resident chain's fold
     int32_t* nk_tr = c->dNkTrace ? c->dNkTrace + (size_t)(j - c->nk_trace_base) * p.K : nullptr;
     if (explicit_params(p.mode)) {
         if (phase != 2) {
@@ -2015,6 +2052,10 @@ int chain_start(bmm_chain* c) {
             hipLaunchKernelGGL(k_count_labels, dim3((unsigned)(nt < 2048 ? nt : 2048)), dim3(256), hb, c->stream,
                                p, c->dX, c->dXb, row0, c->dDNk, c->dDS);
         HIP_TRY(hipGetLastError());
+        if (c->sum_on) {  // (row 0 of a run without burn-in may be the summary's pivot)
+            const int rc = sum_start_state(c, row0);
+            if (rc) return rc;
+        }
     } else if (explicit_params(p.mode)) {
         hipLaunchKernelGGL(k_sb_theta_tables, dim3(p.KT), dim3(256), 0, c->stream, p, c->dNk, c->dS,
                            c->dPi, c->dTheta, 0, 0u, (double*)nullptr, c->dTab, (double*)nullptr, (double*)nullptr,
@@ -2194,6 +2235,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     }
     dev_pool().put(c->device, c->arena, c->arena_bytes);  // the stream is idle (synchronised above)
     dev_pool().put(c->device, c->run_arena, c->run_arena_bytes);
+    sum_release(c);
     void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
                     c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch, c->dSmSide, c->dSmSideLaunch, c->dSmLq, c->dSmStat, c->dSmCell,
                     c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dAsBlock, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock, c->dNaBlock, c->dCsBlock};
@@ -2440,6 +2482,7 @@ int bmm_chain_set_shard(bmm_chain* c, int64_t N_total, int64_t first_row) {
     if (c->cs_on) return cs_refuses("a shard");
     if (!explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "only the stick-breaking and full samplers shard exactly over observations");
+    if (c->sum_on) return set_err(BMM_E_UNSUPPORTED, "a chain with an armed summary does not shard: a shard holds a part of the rows");
     if (first_row < 0 || N_total < first_row + c->p.N) return set_err(BMM_E_ARG, "shard [first_row, first_row + N) lies outside N_total");
     c->p.Ntot = N_total;
     c->p.obs0 = first_row;
@@ -3610,7 +3653,7 @@ static int sm_ready(bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     int rc = sm_refused(c);
     if (rc == BMM_OK) rc = sm_seated(c);
-    if (rc == BMM_OK && c->dTrace) rc = set_err(BMM_E_STATE, "not offered inside a run");
+    if (rc == BMM_OK && c->in_run) rc = set_err(BMM_E_STATE, "not offered inside a run");
     if (rc == BMM_OK && !c->dSmStat) rc = sm_setup(c, c->sm_scans);
     return rc;
 }
@@ -3687,7 +3730,7 @@ int bmm_chain_set_labels(bmm_chain* c, const int32_t* z1) {
         if (c->sharded) return set_err(BMM_E_STATE, "not offered on a sharded chain");
         int rc = sm_seated(c);
         if (rc) return rc;
-        if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+        if (c->in_run) return set_err(BMM_E_STATE, "not offered inside a run");
         HIP_TRY(hipSetDevice(c->device));
         const int64_t N = c->p.N;
         const size_t K = (size_t)c->p.K, KP = K * c->p.P;
@@ -3729,6 +3772,7 @@ static int alloc_refused(const bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (c->na_on) return na_refuses("the allocation sampler");
     if (c->cs_on) return cs_refuses("the allocation sampler");
+    if (c->sum_on) return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is not offered on a chain with an armed summary");
     if (c->sharded) return set_err(BMM_E_STATE, "the allocation sampler is not offered on a sharded chain");
     if (c->p.mode != MODE_COLLAPSED)
         return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is the finite collapsed sampler with K unknown: create the chain with that sampler, K = maxK");
@@ -3760,7 +3804,7 @@ static int alloc_ready(bmm_chain* c) {
     int rc = alloc_refused(c);
     if (rc) return rc;
     if (!c->alloc_on) return set_err(BMM_E_STATE, "the allocation sampler is not armed (bmm_chain_set_alloc)");
-    if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+    if (c->in_run) return set_err(BMM_E_STATE, "not offered inside a run");
     return alloc_prepare(c);
 }
 static int alloc_set_k(bmm_chain* c, int K) {
@@ -3926,7 +3970,7 @@ static int as_setup(bmm_chain* c, int scans) {
 static int as_ready(bmm_chain* c) {
     int rc = as_refused(c);
     if (rc) return rc;
-    if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+    if (c->in_run) return set_err(BMM_E_STATE, "not offered inside a run");
     rc = alloc_prepare(c);
     if (rc == BMM_OK && (!c->dAsBlock || c->sm_sets < c->as_scans + 2)) rc = as_setup(c, c->as_scans);
     return rc;
@@ -4046,7 +4090,7 @@ static int init_run_attach(bmm_chain* c, const RunOptions& o) {
 int bmm_chain_init_labels(bmm_chain* c, int kind, int n_centres, int iters, bmm_init_info* info) {
     return guarded([&]() -> int {
         if (!c) return set_err(BMM_E_ARG, "null chain");
-        if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+        if (c->in_run) return set_err(BMM_E_STATE, "not offered inside a run");
         return init_labels(c, kind, n_centres, iters, info);
     });
 }
@@ -4144,7 +4188,7 @@ int bmm_chain_set_features(bmm_chain* c, const uint8_t* gamma) {
         if (!c || !gamma) return set_err(BMM_E_ARG, "null argument");
         int rc = fs_refused(c);
         if (rc) return rc;
-        if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+        if (c->in_run) return set_err(BMM_E_STATE, "not offered inside a run");
         const int P = c->p.P, W = (P + 31) / 32;
         std::vector<uint32_t> words((size_t)W, 0u);
         std::vector<uint8_t> bytes((size_t)P);
@@ -4341,7 +4385,7 @@ int bmm_chain_set_missing(bmm_chain* c, const int64_t* rows, const int32_t* cols
         if (c->na_on) return set_err(BMM_E_STATE, "missing cells are already declared: withdraw them first (n_cells = 0)");
         rc = na_refused(c);
         if (rc) return rc;
-        if (c->dTrace && c->sweep > 0) return set_err(BMM_E_STATE, "not offered inside a run");
+        if (c->in_run && c->sweep > 0) return set_err(BMM_E_STATE, "not offered inside a run");
         HIP_TRY(hipSetDevice(c->device));
         const ChainParams& p = c->p;
         // the sites: one per (row, plane word) that has a hole
@@ -4555,7 +4599,7 @@ int bmm_chain_set_constraints(bmm_chain* c, int64_t n, const int64_t* rows, cons
         if (c->cs_on) return set_err(BMM_E_STATE, "constraints are already set: withdraw them first (n = 0)");
         rc = cs_refused(c);
         if (rc) return rc;
-        if (c->dTrace && c->sweep > 0) return set_err(BMM_E_STATE, "not offered inside a run");
+        if (c->in_run && c->sweep > 0) return set_err(BMM_E_STATE, "not offered inside a run");
         HIP_TRY(hipSetDevice(c->device));
         Carver measure{nullptr};
         auto carve = [&](Carver& v) {
@@ -4629,6 +4673,7 @@ static int temper_refused(const bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (c->na_on) return na_refuses("parallel tempering");
     if (c->cs_on) return cs_refuses("parallel tempering");
+    if (c->sum_on) return set_err(BMM_E_UNSUPPORTED, "parallel tempering is not offered on a chain with an armed summary");
     if (explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "parallel tempering is offered for the collapsed and DP samplers only: the stick-breaking "
                        "and full samplers carry theta, and the power sits on the likelihood with theta integrated out");
@@ -4644,7 +4689,7 @@ int bmm_chain_set_temper(bmm_chain* c, int on, double inv_temp) {
         int rc = temper_refused(c);
         if (rc) return rc;
         if (on && !(inv_temp > 0.0 && inv_temp <= 1.0)) return set_err(BMM_E_ARG, "inv_temp must lie in (0, 1]");
-        if (c->dTrace) return set_err(BMM_E_STATE, "not offered inside a run");
+        if (c->in_run) return set_err(BMM_E_STATE, "not offered inside a run");
         const bool was = c->temper_on;
         c->temper_on = on != 0;
         c->temper_b = on ? inv_temp : 1.0;
@@ -4714,7 +4759,7 @@ int ladder_exchange(bmm_ladder* l, double* lik_row) {
         HIP_TRY(hipGetLastError());
         // rung 0's kept row of a run: theta-hat and alpha of the state it holds now (nothing is pending behind a
         // sweep end, and the concentration is not drawn again)
-        if (c0->dTrace && c0->sweep >= c0->burnin && c0->sweep >= 1 && (l->t & 1u) == 0) {
+        if (c0->in_run && c0->sweep >= c0->burnin && c0->sweep >= 1 && (l->t & 1u) == 0) {
             ChainParams q = c0->p;
             q.sample_alpha = 0;
             const int s = c0->sweep - c0->burnin;
@@ -4794,7 +4839,7 @@ int bmm_ladder_create(bmm_ladder** out, bmm_chain* const* chains, int R, uint64_
                 const std::string why = g_err;
                 return set_err(BMM_E_UNSUPPORTED, "rung %d: %s", r, why.c_str());
             }
-            if (c->dTrace && r > 0) return set_err(BMM_E_STATE, "rung %d: the chain is inside a run", r);
+            if (c->in_run && r > 0) return set_err(BMM_E_STATE, "rung %d: the chain is inside a run", r);
             if (c->ladder && r > 0) return set_err(BMM_E_STATE, "rung %d: the chain is rung 0 of a run's ladder", r);
         }
         const bmm_chain* c0 = chains[0];
@@ -4937,30 +4982,46 @@ size_t out_block_rows(int S, size_t el, int64_t N) {
     return (size_t)(B > N ? N : B);
 }
 
-// buffers of a *_run call: the traces and the two device blocks of the outgoing label trace, one allocation
-// (owned by the chain, released with it)
-int run_prepare(bmm_chain* c, int nsamples, int burnin) {
+// buffers of a *_run call: the traces and, for a run that keeps its label trace, that trace and the two device blocks
+// of its way out.  A pure function of (sampler, N, P, K, S, keep_trace): run_prepare carves with it and bmm_run_bytes
+// measures with it.
+struct RunBufs {
+    double *theta = nullptr, *alpha = nullptr, *pi = nullptr;
+    char* out_blk[2] = {nullptr, nullptr};
+    size_t out_blk_bytes = 0;
+    int32_t* trace = nullptr;
+};
+RunBufs run_carve(Carver& a, int sampler, int64_t N, int P, int K, int S, bool keep_trace) {
+    RunBufs b;
+    b.theta = a.take<double>((size_t)S * K * P);
+    b.alpha = a.take<double>((size_t)S);
+    b.pi = explicit_params(sampler) ? a.take<double>((size_t)S * K) : nullptr;
+    (void)a.take<char>(0);  // (the small traces end on a carving boundary: what the label trace adds is its own bytes)
+    if (!keep_trace) return b;
+    const size_t el = K <= 254 ? 1 : 4;
+    b.out_blk_bytes = out_block_rows(S, el, N) * (size_t)S * el;
+    b.out_blk[0] = a.take<char>(b.out_blk_bytes);
+    b.out_blk[1] = a.take<char>(b.out_blk_bytes);
+    b.trace = a.take<int32_t>((size_t)S * N);
+    return b;
+}
+// ... one allocation (owned by the chain, released with it)
+int run_prepare(bmm_chain* c, int nsamples, int burnin, bool keep_trace = true) {
     const int64_t N = c->p.N;
     const int K = c->p.K, P = c->p.P;
     const int S = nsamples - burnin;
     c->burnin = burnin; c->S = S;
+    c->in_run = true;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t el = K <= 254 ? 1 : 4;
-    c->out_blk_bytes = out_block_rows(S, el, N) * (size_t)S * el;
-    auto carve = [&](Carver& a) {
-        c->dThetaTrace = a.take<double>((size_t)S * K * P);
-        c->dAlphaTrace = a.take<double>((size_t)S);
-        c->dPiTrace = explicit_params(c->p.mode) ? a.take<double>((size_t)S * K) : nullptr;
-        c->dOutBlk[0] = a.take<char>(c->out_blk_bytes);
-        c->dOutBlk[1] = a.take<char>(c->out_blk_bytes);
-        c->dTrace = a.take<int32_t>((size_t)S * N);
-    };
     Carver measure{nullptr};
-    carve(measure);
+    (void)run_carve(measure, c->p.mode, N, P, K, S, keep_trace);
     c->run_arena = static_cast<char*>(dev_pool().get(c->device, measure.used, &c->run_arena_bytes));
     if (!c->run_arena) return set_err(BMM_E_HIP, "allocating the run's buffers failed: %s", hipGetErrorString(hipGetLastError()));
     Carver real{c->run_arena};
-    carve(real);
+    const RunBufs b = run_carve(real, c->p.mode, N, P, K, S, keep_trace);
+    c->dThetaTrace = b.theta; c->dAlphaTrace = b.alpha; c->dPiTrace = b.pi;
+    c->dOutBlk[0] = b.out_blk[0]; c->dOutBlk[1] = b.out_blk[1]; c->out_blk_bytes = b.out_blk_bytes;
+    c->dTrace = b.trace;
     return BMM_OK;
 }
 
@@ -5386,7 +5447,7 @@ int run_start_state(bmm_chain* c, const RunIO& io, bool device_init = false) {
         HIP_TRY(hipMemcpy(c->dAlphaTrace, &c->alpha0, sizeof(double), hipMemcpyHostToDevice));
         if (explicit_params(sampler))
             HIP_TRY(hipMemcpy2D(c->dPiTrace, (size_t)S * sizeof(double), io.pi0, sizeof(double), sizeof(double), K, hipMemcpyHostToDevice));
-        if (sampler != BMM_SAMPLER_COLLAPSED) HIP_TRY(hipMemset(c->dTrace, 0xff, (size_t)N * sizeof(int32_t)));
+        if (sampler != BMM_SAMPLER_COLLAPSED && c->dTrace) HIP_TRY(hipMemset(c->dTrace, 0xff, (size_t)N * sizeof(int32_t)));
     }
     return BMM_OK;
 }
@@ -5840,6 +5901,266 @@ int ecr_run(bmm_chain* c, const RunOptions& opts, DevBuf& perm) {
     return BMM_OK;
 }
 
+// ---- posterior summary: online pivot relabelling, memberships folded behind the sweeps (include/bmm_mcmc.h "posterior
+// summary") ----
+// The launch shapes and the block's bytes: a pure function of (N, P, K) -- the launches below, bmm_summary_plan and
+// bmm_run_bytes all read it from here.  k_sum_fold and k_sum_finish stride a grid of at most kSumGridCap workgroups
+// (eight of 256 threads per compute unit of a 256-unit device).
+constexpr int kSumGridCap = 2048;
+constexpr int kSumLaunchesPivot = 8;  // two memsets, k_ecr_tables, k_ecr_cost, k_st_assign, k_ecr_agree, k_sum_fold, k_sum_profiles
+constexpr int kSumLaunchesPlain = 2;  // k_sum_fold, k_sum_profiles
+void sum_carve(Carver& v, SumBufs& b, int64_t N, int P, int K, int64_t pitch) {
+    const size_t Kz = (size_t)K, KP = Kz * (size_t)P;
+    b.cnt = v.take<uint32_t>(Kz * (size_t)pitch);
+    b.theta_sum = v.take<double>(KP);
+    b.theta_sq = v.take<double>(KP);
+    b.alpha_acc = v.take<double>(2);
+    b.theta_n = v.take<int32_t>(Kz);
+    b.fold_bytes = v.used;  // what a reset zeroes: the five above
+    b.size_sum = v.take<unsigned long long>(Kz);
+    b.pivot = v.take<int32_t>((size_t)N);
+    b.z_hat = v.take<int32_t>((size_t)N);
+    b.n_max = v.take<uint32_t>((size_t)N);
+    b.identity = v.take<int32_t>(Kz);
+    b.perm_live = v.take<int32_t>(Kz);
+    b.agree_live = v.take<int64_t>(1);
+    b.theta_row = v.take<double>(KP);
+    b.alpha_row = v.take<double>(1);
+}
+struct SumPlan {
+    int fold_wgs = 1, prof_wgs = 1, finish_wgs = 1;
+    int64_t pitch = 0;
+    size_t fold_lds = 0, finish_lds = 0, bytes_counts = 0, bytes_block = 0;
+};
+SumPlan sum_plan(int64_t N, int P, int K) {
+    SumPlan q;
+    q.pitch = (N + 63) / 64 * 64;
+    const int64_t wg = (N + kSumThreads - 1) / kSumThreads;
+    q.fold_wgs = q.finish_wgs = (int)(wg < kSumGridCap ? wg : kSumGridCap);
+    q.prof_wgs = (int)(((int64_t)K * P + kSumThreads - 1) / kSumThreads);
+    q.fold_lds = (size_t)K * sizeof(int32_t);
+    q.finish_lds = (size_t)K * sizeof(unsigned long long);
+    q.bytes_counts = (size_t)K * (size_t)q.pitch * sizeof(uint32_t);
+    Carver measure{nullptr};
+    SumBufs b;
+    sum_carve(measure, b, N, P, K, q.pitch);
+    q.bytes_block = measure.used;
+    return q;
+}
+// the bytes of a recorded sweep: its agreement, then its permutation
+size_t sum_row_bytes(int K) { return (sizeof(int64_t) + (size_t)K * sizeof(int32_t) + 7) & ~(size_t)7; }
+
+// stride, N, K and the pivot, before a device is touched
+int sum_check_args(int64_t N, int K, const bmm_summary_opts& o) {
+    if (o.stride < 1) return set_err(BMM_E_ARG, "summary: stride must be >= 1 (got %d)", o.stride);
+    if (N >= ((int64_t)1 << 32)) return set_err(BMM_E_ARG, "summary: N must be below 2^32 (the counts are uint32)");
+    if (o.pivot_kind == BMM_SUMMARY_PIVOT_NONE) return BMM_OK;
+    if (o.pivot_kind != BMM_SUMMARY_PIVOT_FIRST && o.pivot_kind != BMM_SUMMARY_PIVOT_GIVEN)
+        return set_err(BMM_E_ARG, "summary: unknown kind of pivot %d", o.pivot_kind);
+    if (K > BMM_ECR_MAX_K)
+        return set_err(BMM_E_ARG, "summary: relabelling against a pivot is offered up to K = %d (got %d); without a pivot any K is folded as sampled", BMM_ECR_MAX_K, K);
+    if (o.pivot_kind == BMM_SUMMARY_PIVOT_FIRST) return BMM_OK;
+    if (!o.pivot) return set_err(BMM_E_ARG, "summary: the pivot is null");
+    for (int64_t i = 0; i < N; ++i)
+        if (o.pivot[i] < 1 || o.pivot[i] > K)
+            return set_err(BMM_E_ARG, "summary: pivot label %d at observation %lld (0-based) is outside 1 .. %d", o.pivot[i], (long long)i, K);
+    return BMM_OK;
+}
+int sum_refused(const bmm_chain* c) {
+    if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the summary is not offered on a sharded chain: a shard holds a part of the rows");
+    if (c->alloc_on) return set_err(BMM_E_UNSUPPORTED, "the summary is not offered for the allocation sampler: it assumes no fixed number of components");
+    if (c->temper_on || c->ladder) return temper_refuses("the summary");
+    return BMM_OK;
+}
+void sum_release(bmm_chain* c) {
+    delete c->sum_ecr;
+    c->sum_ecr = nullptr;
+    if (c->dSumBlock) dev_pool().put(c->device, c->dSumBlock, c->sum_block_bytes);
+    c->dSumBlock = nullptr; c->sum_block_bytes = 0;
+    c->sum = SumBufs{};
+    c->sum_on = false; c->sum_have_pivot = false; c->sum_folded = 0;
+}
+int sum_reset(bmm_chain* c) {
+    c->sum_folded = 0;
+    if (c->sum_pivot_kind == BMM_SUMMARY_PIVOT_FIRST) c->sum_have_pivot = false;
+    HIP_TRY(hipMemsetAsync(c->dSumBlock, 0, c->sum.fold_bytes, c->stream));
+    return BMM_OK;
+}
+// the block from the device pool, zeroed; the workspace of one row's ECR pass; a given pivot uploaded.  The stream is idle.
+int sum_arm(bmm_chain* c, const bmm_summary_opts& o) {
+    int rc = sum_refused(c);
+    if (rc == BMM_OK) rc = sum_check_args(c->p.N, c->p.K, o);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    sum_release(c);
+    const int64_t N = c->p.N;
+    const int K = c->p.K;
+    const SumPlan q = sum_plan(N, c->p.P, K);
+    c->dSumBlock = static_cast<char*>(dev_pool().get(c->device, q.bytes_block, &c->sum_block_bytes));
+    if (!c->dSumBlock) return set_err(BMM_E_HIP, "allocating the summary's buffers (%zu bytes) failed: %s", q.bytes_block, hipGetErrorString(hipGetLastError()));
+    Carver real{c->dSumBlock};
+    sum_carve(real, c->sum, N, c->p.P, K, q.pitch);
+    c->sum_pitch = q.pitch;
+    HIP_TRY(hipMemsetAsync(c->dSumBlock, 0, q.bytes_block, c->stream));
+    rc = ecr_perm_identity(c->stream, c->sum.identity, 1, K);
+    if (rc == BMM_OK) rc = ecr_perm_identity(c->stream, c->sum.perm_live, 1, K);
+    if (rc == BMM_OK && o.pivot_kind != BMM_SUMMARY_PIVOT_NONE) {
+        c->sum_ecr = new EcrWork();
+        rc = c->sum_ecr->alloc(1, N, K, false);
+    }
+    if (rc == BMM_OK && o.pivot_kind == BMM_SUMMARY_PIVOT_GIVEN) rc = ecr_upload_pivot(c->sum.pivot, o.pivot, N, c->stream);
+    if (rc) { (void)hipStreamSynchronize(c->stream); sum_release(c); return rc; }
+    c->sum_pivot_kind = o.pivot_kind; c->sum_stride = o.stride;
+    c->sum_have_pivot = o.pivot_kind == BMM_SUMMARY_PIVOT_GIVEN;
+    c->sum_folded = 0;
+    c->sum_on = true;
+    return BMM_OK;
+}
+// the _FIRST pivot: the labels of a kept state, device to device
+int sum_take_pivot(bmm_chain* c, const int32_t* z) {
+    HIP_TRY(hipMemcpyAsync(c->sum.pivot, z, (size_t)c->p.N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    c->sum_have_pivot = true;
+    return BMM_OK;
+}
+// one row's permutation against the pivot into perm (K entries, the identity on entry): the pass of "ECR" with S = 1
+int sum_relabel(bmm_chain* c, const int32_t* z, int32_t* perm) {
+    int iterations = 0, converged = 0;
+    return ecr_compute<int32_t>(c->stream, *c->sum_ecr, z, c->p.N, c->sum.pivot, perm, 1, false, 1, &iterations, &converged);
+}
+// the end of sweep j of an armed chain: the _FIRST pivot when j is the first kept sweep, then the fold when the
+// stride names j.  Everything is enqueued; nothing waits.
+int sum_sweep_end(bmm_chain* c, int j) {
+    const SweepTrace& r = c->sum_rec;
+    if (!r.fold || j < r.base) return BMM_OK;
+    if (c->sum_pivot_kind == BMM_SUMMARY_PIVOT_FIRST && !c->sum_have_pivot) {
+        const int rc = sum_take_pivot(c, label_row(c, j));
+        if (rc) return rc;
+    }
+    if (!stride_folds(r, c->sum_stride, j)) return BMM_OK;
+    const int64_t N = c->p.N;
+    const int K = c->p.K, P = c->p.P;
+    const SumPlan q = sum_plan(N, P, K);
+    const int32_t* const z = label_row(c, j);
+    char* const row = r.row<char>(j);
+    int64_t* const agree_out = row ? reinterpret_cast<int64_t*>(row) : c->sum.agree_live;
+    const int32_t* perm = c->sum.identity;
+    const int64_t* agree_in = nullptr;
+    if (c->sum_pivot_kind != BMM_SUMMARY_PIVOT_NONE) {
+        int32_t* const perm_row = row ? reinterpret_cast<int32_t*>(row + sizeof(int64_t)) : c->sum.perm_live;
+        const int rc = sum_relabel(c, z, perm_row);
+        if (rc) return rc;
+        perm = perm_row;
+        agree_in = c->sum_ecr->agree.as<int64_t>();
+    }
+    hipLaunchKernelGGL(k_sum_fold, dim3((unsigned)q.fold_wgs), dim3(kSumThreads), q.fold_lds, c->stream, z, perm, N, K, c->sum_pitch, c->sum.cnt);
+    HIP_TRY(hipGetLastError());
+    const bool rec = c->in_run && j >= c->burnin;  // the sweep's rows of the run's traces, or the rows enqueue_sweep had written for the fold
+    const double* const theta = rec ? c->dThetaTrace + (size_t)(j - c->burnin) * K * P : c->sum.theta_row;
+    const double* const alpha = rec ? c->dAlphaTrace + (j - c->burnin) : c->sum.alpha_row;
+    hipLaunchKernelGGL(k_sum_profiles, dim3((unsigned)q.prof_wgs), dim3(kSumThreads), 0, c->stream, theta, alpha, perm, K, P, c->sum.theta_sum,
+                       c->sum.theta_sq, c->sum.theta_n, c->sum.alpha_acc, agree_in, agree_out);
+    HIP_TRY(hipGetLastError());
+    c->sum_folded++;
+    return BMM_OK;
+}
+// the starting state of a finite collapsed run without burn-in is trace row 0: the _FIRST pivot (chain_start)
+int sum_start_state(bmm_chain* c, const int32_t* row0) {
+    if (c->sum_pivot_kind != BMM_SUMMARY_PIVOT_FIRST || c->sum_have_pivot || !c->sum_rec.fold || c->sum_rec.base != 0) return BMM_OK;
+    return sum_take_pivot(c, row0);
+}
+// k_sum_finish, then whatever `out` asks for to the host; waits
+int sum_get(bmm_chain* c, const bmm_summary_out& out) {
+    const int64_t N = c->p.N;
+    const int K = c->p.K, P = c->p.P;
+    const SumPlan q = sum_plan(N, P, K);
+    const size_t Kz = (size_t)K, KP = Kz * (size_t)P, Nz = (size_t)N;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemsetAsync(c->sum.size_sum, 0, Kz * sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(k_sum_finish, dim3((unsigned)q.finish_wgs), dim3(kSumThreads), q.finish_lds, c->stream, (const uint32_t*)c->sum.cnt, N, K,
+                       c->sum_pitch, c->sum.z_hat, c->sum.n_max, c->sum.size_sum);
+    HIP_TRY(hipGetLastError());
+    auto copy = [&](void* dst, const void* src, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIP_TRY(copy(out.z_hat, c->sum.z_hat, Nz * sizeof(int32_t)));
+    HIP_TRY(copy(out.n_max, c->sum.n_max, Nz * sizeof(uint32_t)));
+    HIP_TRY(copy(out.size_sum, c->sum.size_sum, Kz * sizeof(int64_t)));
+    HIP_TRY(copy(out.theta_sum, c->sum.theta_sum, KP * sizeof(double)));
+    HIP_TRY(copy(out.theta_sq, c->sum.theta_sq, KP * sizeof(double)));
+    HIP_TRY(copy(out.theta_n, c->sum.theta_n, Kz * sizeof(int32_t)));
+    HIP_TRY(copy(out.alpha_sum, c->sum.alpha_acc, 2 * sizeof(double)));
+    if (out.pivot && c->sum_have_pivot) HIP_TRY(copy(out.pivot, c->sum.pivot, Nz * sizeof(int32_t)));
+    if (out.counts)
+        HIP_TRY(hipMemcpy2DAsync(out.counts, Nz * sizeof(uint32_t), c->sum.cnt, (size_t)c->sum_pitch * sizeof(uint32_t), Nz * sizeof(uint32_t), Kz,
+                                 hipMemcpyDeviceToHost, c->stream));
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return set_err(BMM_E_HIP, "reading the summary failed: %s", hipGetErrorString(e));
+    if (out.pivot)
+        for (int64_t i = 0; i < N; ++i) out.pivot[i] = c->sum_have_pivot ? out.pivot[i] + 1 : 0;
+    if (out.n_folded) *out.n_folded = c->sum_folded;
+    return BMM_OK;
+}
+// rows of (agree, perm) for n sweeps: -1 and the identity until a fold writes them
+int sum_rows_alloc(bmm_chain* c, Recording& rec, int n) {
+    const int K = c->p.K;
+    const size_t width = sum_row_bytes(K);
+    int rc = rec.alloc((size_t)n * width, "the summary's per-sweep rows (agreement and permutation)");
+    if (rc) return rc;
+    std::vector<char> host((size_t)n * width, 0);
+    for (int s = 0; s < n; ++s) {
+        const int64_t none = -1;
+        std::memcpy(host.data() + (size_t)s * width, &none, sizeof none);
+        int32_t* const perm = reinterpret_cast<int32_t*>(host.data() + (size_t)s * width + sizeof(int64_t));
+        for (int k = 0; k < K; ++k) perm[k] = k;
+    }
+    HIP_TRY(hipMemcpyAsync(rec.rows.p, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // before the host copy goes
+    return BMM_OK;
+}
+// ... and out again: agree n int64, permutations n x K column-major
+int sum_rows_out(bmm_chain* c, const Recording& rec, int n, int64_t* agree, int32_t* permutations) {
+    const int K = c->p.K;
+    const size_t width = sum_row_bytes(K);
+    std::vector<char> host((size_t)n * width);
+    HIP_TRY(hipMemcpy(host.data(), rec.rows.p, host.size(), hipMemcpyDeviceToHost));
+    for (int s = 0; s < n; ++s) {
+        if (agree) std::memcpy(agree + s, host.data() + (size_t)s * width, sizeof(int64_t));
+        const int32_t* const perm = reinterpret_cast<const int32_t*>(host.data() + (size_t)s * width + sizeof(int64_t));
+        if (permutations) for (int k = 0; k < K; ++k) permutations[(size_t)s + (size_t)k * (size_t)n] = perm[k];
+    }
+    return BMM_OK;
+}
+
+// ... of a run: refused before a device is touched, armed for it, every stride-th kept sweep folded (sweep_end_folds)
+int sum_run_check(const RunOptions& opts, int64_t N, int K) {
+    if (!opts.summary.on) return BMM_OK;
+    if (opts.alloc.on)
+        return set_err(BMM_E_UNSUPPORTED, "summary: the allocation sampler is not offered together with the summary: it assumes no fixed number of components");
+    if (opts.temper.on) return set_err(BMM_E_UNSUPPORTED, "summary: not offered together with parallel tempering");
+    if (opts.ecr.on || opts.rel || opts.hooks)
+        return set_err(BMM_E_ARG, "summary: armed together with a relabelling of the run (ECR, a *_run_relabel call or *_run_probs hooks): two relabellings of one run");
+    if (!opts.keep_trace() && opts.partition.on)
+        return set_err(BMM_E_ARG, "summary: keep_trace = 0 together with the partition summary, which reads the label trace");
+    return sum_check_args(N, K, opts.summary.opts);
+}
+int sum_run_attach(bmm_chain* c, const RunOptions& opts, Recording& rec) {
+    if (!opts.summary.on) return BMM_OK;
+    int rc = sum_arm(c, opts.summary.opts);
+    if (rc == BMM_OK) rc = sum_rows_alloc(c, rec, c->S);
+    if (rc) return rc;
+    rec.begin(c, c->sum_rec, sum_row_bytes(c->p.K), c->burnin, run_first_fold(c), true);
+    return BMM_OK;
+}
+int sum_run_collect(bmm_chain* c, const RunOptions& opts, Recording& rec, int rc) {
+    if (!opts.summary.on) return rc;
+    rc = rec.end_run(rc);
+    if (rc) return rc;
+    rc = sum_get(c, opts.summary.o);
+    if (rc || !rec.rows.p) return rc;
+    return sum_rows_out(c, rec, c->S, opts.summary.o.agree, opts.summary.o.permutations);
+}
+
 // the sweeps, then the traces out (data and starting state are in place)
 int run_body(bmm_chain* c, int nsamples, const RunIO& io, const RunOptions& opts) {
     const bmm_relabel_out* const rel = opts.rel;
@@ -5889,9 +6210,12 @@ int run_body(bmm_chain* c, int nsamples, const RunIO& io, const RunOptions& opts
         if (rc) return rc;
         std::memcpy(theta_original, io.theta_out, (size_t)S * K * P * sizeof(double));
         permute_theta(theta_original, hperm, K, P, S, io.theta_out);
-    } else {
+    } else if (c->dTrace) {
         rc = trace_out(c, io.z_out, &clock);
         if (rc) return rc;
+    } else {  // a run without a label trace (bmm_set_summary, keep_trace = 0): the small traces queued above
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        clock.lap(3);
     }
     clock.lap(4);
     return dbg_labels_ok(c);
@@ -6013,8 +6337,8 @@ int st_run_check(const RunOptions& opts, int burnin, int K) {
     return st_check_k(K);
 }
 
-int check_run_args(const int32_t* X, int nsamples, int burnin, const RunIO& io, int sampler) {
-    if (!X || !io.z_out || !io.theta_out || !io.alpha_out) return set_err(BMM_E_ARG, "null buffer");
+int check_run_args(const int32_t* X, int nsamples, int burnin, const RunIO& io, int sampler, bool keep_trace = true) {
+    if (!X || (!io.z_out && keep_trace) || !io.theta_out || !io.alpha_out) return set_err(BMM_E_ARG, "null buffer");
     if (sampler == BMM_SAMPLER_COLLAPSED && !io.z0) return set_err(BMM_E_ARG, "initialK is null");
     if (explicit_params(sampler) && (!io.pi0 || !io.theta0 || !io.pi_out)) return set_err(BMM_E_ARG, "null buffer");
     if (nsamples < 1) return set_err(BMM_E_ARG, "nsamples must be >= 1");
@@ -6126,7 +6450,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
               const RunIO& io, const RunOptions& opts) {
     return guarded([&]() -> int {
         // refused before any device is touched
-        int rc = check_run_args(X, nsamples, burnin, io, sampler);
+        int rc = check_run_args(X, nsamples, burnin, io, sampler, opts.keep_trace());
         if (rc == BMM_OK) rc = pt_run_check(opts, nsamples - burnin, N, K);
         if (rc) return rc;
         g_init_info = bmm_init_info{};
@@ -6140,6 +6464,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
         if (rc == BMM_OK) rc = pc_run_check(opts, P, K);
         if (rc == BMM_OK) rc = na_run_check(opts, N, P);
         if (rc == BMM_OK) rc = cs_run_check(opts, N, K);
+        if (rc == BMM_OK) rc = sum_run_check(opts, N, K);
         if (rc) return rc;
         for (double& v : g_phase_ms) v = 0.0;
         PhaseClock clock;
@@ -6158,7 +6483,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
         {
             struct Guard { bmm_chain* c; ~Guard() { bmm_chain_destroy(c); } } guard{c};
             TemperRun temper;  // (released ahead of the chain)
-            rc = run_prepare(c, nsamples, burnin);
+            rc = run_prepare(c, nsamples, burnin, opts.keep_trace());
             if (rc == BMM_OK) rc = run_start_state(c, io, opts.init.kind != 0);
             if (rc) return rc;
             clock.lap(1);
@@ -6177,7 +6502,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             if (rc) return rc;
             clock.lap(0);
             // what the options record per kept sweep: each ends, and waits for the stream before its rows go, on every way out
-            Recording pred_rec, loo_rec, fs_rec, k_rec, lp_rec, pc_rec;
+            Recording pred_rec, loo_rec, fs_rec, k_rec, lp_rec, pc_rec, sum_rec;
             rc = pred_run_attach(c, opts, pred_rec);
             if (rc == BMM_OK) rc = loo_run_attach(c, opts, loo_rec);
             if (rc == BMM_OK) rc = sm_run_attach(c, opts);
@@ -6185,12 +6510,14 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             if (rc == BMM_OK) rc = alloc_run_attach(c, opts, k_rec);
             if (rc == BMM_OK) rc = lp_run_attach(c, opts, lp_rec);
             if (rc == BMM_OK) rc = pc_run_attach(c, opts, pc_rec);
+            if (rc == BMM_OK) rc = sum_run_attach(c, opts, sum_rec);
             if (rc == BMM_OK) rc = temper_run_attach(c, opts, alpha, batch, seed, temper);
             if (rc) return rc;
             rc = run_body(c, nsamples, io, opts);
             rc = temper_run_collect(c, opts, temper, rc);
             rc = na_run_collect(c, opts, rc);
             rc = cs_run_collect(c, opts, rc);
+            rc = sum_run_collect(c, opts, sum_rec, rc);
             rc = pc_run_collect(c, opts, pc_rec, rc);
             rc = lp_run_collect(c, opts, lp_rec, rc);
             rc = sm_run_collect(c, opts, rc);
@@ -6610,6 +6937,13 @@ int bmm_set_pair_check(const bmm_pair_check_out* out) {
     return BMM_OK;
 }
 
+int bmm_set_summary(const bmm_summary_opts* opts, const bmm_summary_out* out) {
+    g_armed.summary.on = opts != nullptr;
+    g_armed.summary.opts = opts ? *opts : bmm_summary_opts{};
+    g_armed.summary.o = out ? *out : bmm_summary_out{};
+    return BMM_OK;
+}
+
 int bmm_set_ecr_relabel(const bmm_ecr_out* out) {
     g_armed.ecr.on = out != nullptr;
     if (out) g_armed.ecr.o = *out;
@@ -6741,6 +7075,105 @@ int bmm_device_ecr_plan(int S, int64_t N, int K, int64_t out[12]) {
     out[6] = p.span; out[7] = (int64_t)p.tab_lds_bytes; out[8] = p.votes_lds; out[9] = p.votes_wgs;
     out[10] = (int64_t)p.votes_bytes; out[11] = p.pitch;
     return BMM_OK;
+}
+
+// ---- posterior summary: the pure functions and the resident entry points ----
+int64_t bmm_run_bytes(int sampler, int64_t N, int P, int K, int S, int keep_trace, int summary) {
+    if (sampler < 0 || sampler > 3 || N < 1 || P < 1 || K < 1 || S < 1) return -1;
+    Carver measure{nullptr};
+    (void)run_carve(measure, sampler, N, P, K, S, keep_trace != 0);
+    size_t bytes = measure.used;
+    if (summary) bytes += sum_plan(N, P, K).bytes_block + (size_t)S * sum_row_bytes(K);
+    return (int64_t)bytes;
+}
+int bmm_summary_plan(int64_t N, int P, int K, int64_t out[12]) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    if (N < 1 || P < 1 || K < 1) return set_err(BMM_E_ARG, "summary: N, P and K must be >= 1");
+    if (N >= ((int64_t)1 << 32)) return set_err(BMM_E_ARG, "summary: N must be below 2^32 (the counts are uint32)");
+    const SumPlan q = sum_plan(N, P, K);
+    out[0] = kSumThreads; out[1] = q.fold_wgs; out[2] = kSumGridCap; out[3] = q.pitch; out[4] = (int64_t)q.fold_lds;
+    out[5] = q.prof_wgs; out[6] = q.finish_wgs; out[7] = (int64_t)q.finish_lds; out[8] = (int64_t)q.bytes_counts;
+    out[9] = (int64_t)q.bytes_block; out[10] = kSumLaunchesPivot; out[11] = kSumLaunchesPlain;
+    return BMM_OK;
+}
+static int sum_armed(const bmm_chain* c) {
+    if (!c->sum_on) return set_err(BMM_E_STATE, "the summary is not armed (bmm_chain_set_summary)");
+    return BMM_OK;
+}
+int bmm_chain_set_summary(bmm_chain* c, const bmm_summary_opts* opts) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (c->in_run) return set_err(BMM_E_STATE, "not offered inside a run");
+        HIP_TRY(hipSetDevice(c->device));
+        if (!opts) {  // disarm: the memory goes
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            sum_release(c);
+            return BMM_OK;
+        }
+        return sum_arm(c, *opts);
+    });
+}
+int bmm_chain_summary_state(bmm_chain* c, int32_t* perm_out, int64_t* agree_out) {
+    return guarded([&]() -> int {
+        if (!c || !perm_out || !agree_out) return set_err(BMM_E_ARG, "null argument");
+        int rc = sum_armed(c);
+        if (rc) return rc;
+        if (c->p.mode != MODE_COLLAPSED && c->sweep < 1)
+            return set_err(BMM_E_STATE, "no row has a label before the first sweep: this state has nothing to relabel");
+        const int K = c->p.K;
+        HIP_TRY(hipSetDevice(c->device));
+        if (c->sum_pivot_kind == BMM_SUMMARY_PIVOT_NONE) {
+            for (int k = 0; k < K; ++k) perm_out[k] = k;
+            *agree_out = 0;
+            return BMM_OK;
+        }
+        if (!c->sum_have_pivot) return set_err(BMM_E_STATE, "the summary has no pivot yet: it is the state after the first sweep of bmm_chain_sweeps_summary");
+        if (!c->started) { rc = chain_start(c); if (rc) return rc; }
+        rc = ecr_perm_identity(c->stream, c->sum.perm_live, 1, K);
+        if (rc == BMM_OK) rc = sum_relabel(c, label_row(c, c->sweep), c->sum.perm_live);
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+        HIP_TRY(hipMemcpyAsync(perm_out, c->sum.perm_live, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(agree_out, c->sum_ecr->agree.p, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return BMM_OK;
+    });
+}
+// n more sweeps, every sum_stride-th folded from the first on
+int bmm_chain_sweeps_summary(bmm_chain* c, int n, int64_t* agree, int32_t* permutations) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (n < 0) return set_err(BMM_E_ARG, "n must be >= 0");
+        int rc = sum_refused(c);
+        if (rc == BMM_OK) rc = sum_armed(c);
+        if (rc || n == 0) return rc;
+        if (c->in_run) return set_err(BMM_E_STATE, "not offered inside a run");
+        HIP_TRY(hipSetDevice(c->device));
+        Recording rec;
+        if (agree || permutations) {
+            rc = sum_rows_alloc(c, rec, n);
+            if (rc) return rc;
+        }
+        rec.begin(c, c->sum_rec, sum_row_bytes(c->p.K), c->sweep + 1, c->sweep + 1, true);
+        rc = bmm_chain_sweeps(c, n);
+        const hipError_t e = rec.end();
+        if (rc || !rec.rows.p) return rc;
+        if (e != hipSuccess) return set_err(BMM_E_HIP, "the sweeps failed: %s", hipGetErrorString(e));
+        return sum_rows_out(c, rec, n, agree, permutations);
+    });
+}
+int bmm_chain_get_summary(bmm_chain* c, bmm_summary_out* out) {
+    return guarded([&]() -> int {
+        if (!c || !out) return set_err(BMM_E_ARG, "null argument");
+        const int rc = sum_armed(c);
+        return rc ? rc : sum_get(c, *out);
+    });
+}
+int bmm_chain_summary_reset(bmm_chain* c) {
+    if (!c) return set_err(BMM_E_ARG, "null chain");
+    const int rc = sum_armed(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return sum_reset(c);
 }
 
 // ---- several independent chains in one call (SURVEY.md section 8 rows b, e) ----------------

@@ -5313,4 +5313,88 @@ __global__ __launch_bounds__(kNaThreads) void k_na_draw(ChainParams p, NaArgs a)
     }
 }
 
+// ---- posterior summary folded behind the sweeps (include/bmm_mcmc.h "posterior summary") ------
+// The membership counts are K planes of `pitch` uint32 words, plane k word i = the folded sweeps in which observation
+// i carried (relabelled) label k: the lanes of a wave own neighbouring observations, so whatever labels they carry
+// they touch neighbouring words of at most K planes.  perm: the sweep's K-entry permutation (perm[l] = the label draw
+// label l leaves as), entry l at perm[l]; an entry out of range is clamped, as k_ecr_agree clamps it.
+constexpr int kSumThreads = 256;
+
+// One lane per observation, grid-stride; the permutation is staged once per workgroup (dynamic LDS: K int32).  A word
+// is owned by the lane of its observation: plain read-modify-write.  An unassigned label (-1) is skipped.
+__global__ __launch_bounds__(kSumThreads) void k_sum_fold(const int32_t* __restrict__ z, const int32_t* __restrict__ perm,
+                                                          int64_t N, int K, int64_t pitch, uint32_t* __restrict__ cnt) {
+    extern __shared__ int32_t sum_perm[];
+    for (int l = threadIdx.x; l < K; l += kSumThreads) sum_perm[l] = min(max(perm[l], 0), K - 1);
+    __syncthreads();
+    const int64_t nth = (int64_t)gridDim.x * kSumThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kSumThreads + threadIdx.x; i < N; i += nth) {
+        const int a = z[i];
+        if ((uint32_t)a >= (uint32_t)K) continue;  // unassigned
+        uint32_t* const w = cnt + (size_t)sum_perm[a] * (size_t)pitch + (size_t)i;
+        *w = *w + 1u;
+    }
+}
+
+// K P lanes: cell (l, j) of the sweep's theta row (theta[l + j K], exactly as it goes into the theta trace) is added
+// to cell (perm[l], j) of the sums, its square (rounded before the add) to the sums of squares; a NaN cell (the finite
+// sampler's empty label) is left out, and theta_n[perm[l]] counts the sweeps whose cell (l, 0) was not NaN.  perm is a
+// permutation, so every cell of the sums has one lane: one add per sweep, in sweep order.  Lane 0 also folds the
+// sweep's alpha (acc[0] += alpha, acc[1] += alpha * alpha) and records the sweep's agreement (agree_in null: 0).
+__global__ __launch_bounds__(kSumThreads) void k_sum_profiles(const double* __restrict__ theta, const double* __restrict__ alpha,
+                                                              const int32_t* __restrict__ perm, int K, int P,
+                                                              double* __restrict__ theta_sum, double* __restrict__ theta_sq,
+                                                              int32_t* __restrict__ theta_n, double* __restrict__ alpha_acc,
+                                                              const int64_t* __restrict__ agree_in, int64_t* __restrict__ agree_out) {
+    const int e = blockIdx.x * kSumThreads + threadIdx.x;
+    if (e < K * P) {
+        const int j = e / K, l = e - j * K;
+        const double t = theta[e];
+        if (t == t) {
+            const int to = min(max(perm[l], 0), K - 1);
+            const size_t o = (size_t)to + (size_t)j * K;
+            const double sq = __dmul_rn(t, t);
+            theta_sum[o] = __dadd_rn(theta_sum[o], t);
+            theta_sq[o] = __dadd_rn(theta_sq[o], sq);
+            if (j == 0) theta_n[to] += 1;
+        }
+    }
+    if (e == 0) {
+        const double a = *alpha;
+        const double sq = __dmul_rn(a, a);
+        alpha_acc[0] = __dadd_rn(alpha_acc[0], a);
+        alpha_acc[1] = __dadd_rn(alpha_acc[1], sq);
+        if (agree_out) *agree_out = agree_in ? *agree_in : 0;
+    }
+}
+
+// After the last fold: one lane per observation down the K planes (coalesced across the lanes) writes z_hat, the label
+// with the largest count, the lowest on a tie, 1-based, and n_max, that count; size_sum[k] receives the sum of plane k,
+// the cluster sizes under the permutations added over the folded sweeps (wave sums, then one integer add per
+// workgroup and label: exact in any order).  size_sum is zero on entry.  Dynamic LDS: K uint64.
+__global__ __launch_bounds__(kSumThreads) void k_sum_finish(const uint32_t* __restrict__ cnt, int64_t N, int K, int64_t pitch,
+                                                            int32_t* __restrict__ z_hat, uint32_t* __restrict__ n_max,
+                                                            unsigned long long* __restrict__ size_sum) {
+    extern __shared__ unsigned long long sum_size[];
+    for (int k = threadIdx.x; k < K; k += kSumThreads) sum_size[k] = 0;
+    __syncthreads();
+    const int64_t nth = (int64_t)gridDim.x * kSumThreads;
+    for (int64_t base = (int64_t)blockIdx.x * kSumThreads; base < N; base += nth) {  // (a trip is uniform over the workgroup)
+        const int64_t i = base + threadIdx.x;
+        uint32_t best = 0;
+        int bk = 0;
+        for (int k = 0; k < K; ++k) {
+            const uint32_t n = i < N ? cnt[(size_t)k * (size_t)pitch + (size_t)i] : 0u;
+            if (n > best) { best = n; bk = k; }
+            unsigned long long s = n;
+            for (int h = 32; h > 0; h >>= 1) s += __shfl_down(s, h, 64);
+            if ((threadIdx.x & 63) == 0 && s) atomicAdd(&sum_size[k], s);
+        }
+        if (i < N) { z_hat[i] = bk + 1; n_max[i] = best; }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < K; k += kSumThreads)
+        if (sum_size[k]) atomicAdd(&size_sum[k], sum_size[k]);
+}
+
 }  // namespace bmm

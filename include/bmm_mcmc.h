@@ -1350,6 +1350,98 @@ int bmm_chain_constraint_stats(bmm_chain* c, int64_t* proposed, int64_t* reverte
 int bmm_set_constraints(int64_t n, const int64_t* rows, const uint64_t* masks);
 int bmm_last_constraint_stats(int64_t* proposed, int64_t* reverted);
 
+/* ---- posterior summary: online pivot relabelling, memberships folded on the device ----------
+ * What a latent-class user takes out of a chain -- each row's class and how sure it is, each class's size and item
+ * profile, under one labelling -- folded behind the kept sweeps on the live label row, so that the S x N label trace
+ * need not exist.  Labels are 0-based in these definitions (1-based at the interfaces); z_s is the state after kept
+ * sweep s, theta_s and alpha_s its rows of the theta and alpha traces, c the pivot.
+ *   folded sweeps  kept sweep j is folded when it is a sweep (trace row 0 of a run without burn-in is the starting
+ *                state and never folded) and (j - first kept sweep index) is a multiple of `stride`: the rule of the
+ *                pair check's stride.  n_folded counts them.
+ *   permutation  BMM_SUMMARY_PIVOT_FIRST / _GIVEN: perm_s and agree_s of z_s against c exactly as "ECR" above defines
+ *                them with a pivot given (table, min-cost assignment, its tie rule, agree): one pass per folded sweep,
+ *                enqueued behind it, no host wait.  BMM_SUMMARY_PIVOT_NONE: the identity and agree_s = 0, no launch.
+ *                perm_s[l] keeps its meaning: draw label l leaves as pivot label perm_s[l].
+ *   pivot        _FIRST: the first kept state that is assigned -- trace row 0, or row 1 for the DP, stick-breaking and
+ *                full samplers in a run without burn-in -- copied device to device behind that sweep, whether or not the
+ *                stride folds it.  _GIVEN: N labels in 1 .. K.  _NONE: none; the state is folded as sampled (the choice
+ *                with constraints, where a few held rows per class pin the labelling).
+ *   counts       cnt[k][i] = #{folded s : perm_s[z_s[i]] = k}, uint32; an unassigned label is skipped.
+ *   z_hat, n_max z_hat[i] = the k with the largest cnt[k][i], the lowest on a tie (1-based on the way out); n_max[i]
+ *                that count.  A row never assigned has z_hat 1 and n_max 0.
+ *   size_sum     size_sum[k] = sum_i cnt[k][i], int64: the cluster sizes under perm_s added over the folded sweeps.
+ *   profiles     theta_sum[perm_s[l], d] += theta_s[l, d]; theta_sq[perm_s[l], d] += theta_s[l, d] * theta_s[l, d],
+ *                the product rounded before the add, no contraction; one add per folded sweep in sweep order, so two
+ *                runs give the same bits.  A NaN cell (the finite sampler's empty label) is left out; theta_n[perm_s[l]]
+ *                counts the folded sweeps whose theta_s[l, 0] is not NaN.  alpha_sum[0] += alpha_s and alpha_sum[1] +=
+ *                alpha_s * alpha_s likewise.
+ *   per sweep    agree[s] (int64) and permutations (S x K int32 column-major, 0-based) for every kept sweep; -1 and the
+ *                identity where the sweep was not folded.
+ * Nothing per row is floating point; probabilities, entropies, means and deviations are the caller's to derive from
+ * the integers and the sums.  The summary reads state only: an armed chain's labels, theta and alpha are those of an
+ * unarmed one, byte for byte. */
+#define BMM_SUMMARY_PIVOT_NONE 0
+#define BMM_SUMMARY_PIVOT_FIRST 1
+#define BMM_SUMMARY_PIVOT_GIVEN 2
+typedef struct bmm_summary_opts {
+    int pivot_kind;       /* BMM_SUMMARY_PIVOT_NONE, _FIRST or _GIVEN */
+    const int32_t* pivot; /* _GIVEN: N labels, 1-based, in 1 .. K; else ignored */
+    int stride;           /* >= 1 */
+    int keep_trace;       /* bmm_set_summary: 0 drops the label trace of the run (below); else 1 */
+} bmm_summary_opts;
+typedef struct bmm_summary_out { /* any pointer may be NULL */
+    int32_t* pivot;        /* N int32, 1-based: the pivot used (0 for _NONE, or when no kept state was assigned) */
+    int32_t* z_hat;        /* N int32, 1-based */
+    uint32_t* n_max;       /* N */
+    int* n_folded;
+    int64_t* size_sum;     /* K */
+    double* theta_sum;     /* K x P column-major */
+    double* theta_sq;      /* K x P column-major */
+    int32_t* theta_n;      /* K */
+    double* alpha_sum;     /* 2: the sum and the sum of squares */
+    int64_t* agree;        /* a run: S */
+    int32_t* permutations; /* a run: S x K int32 column-major, 0-based */
+    uint32_t* counts;      /* N x K uint32 column-major (cnt[k][i] at [i + k N]): 4 N K bytes, so only on request */
+} bmm_summary_out;
+/* For a run: armed per calling thread for the NEXT single-chain bmm_collapsed_run / bmm_dp_run / bmm_sb_run /
+ * bmm_full_run (and their _probs form without hooks, and _predict) of that thread and disarmed when that call returns,
+ * whatever it returns; opts NULL disarms.  Both structs are copied; their buffers must stay valid through that call.
+ * keep_trace = 0: the run carves no label trace on the device, writes no z_out (z_out may then be NULL, and only then)
+ * and skips the trace's way out; the theta, alpha and pi traces stay.  Refused before a device is touched: BMM_E_ARG for
+ * stride < 1, N >= 2^32, K > BMM_ECR_MAX_K unless the pivot is _NONE, a pivot label outside 1 .. K, together with a
+ * relabelling of the same run (bmm_set_ecr_relabel, a *_run_relabel call, *_run_probs hooks), and for keep_trace = 0
+ * together with anything that reads the trace (the partition summary, ECR, Stephens' relabelling);
+ * BMM_E_UNSUPPORTED for bmm_alloc_run and together with parallel tempering; bmm_multi_run disarms it like any other
+ * option.  Composes with what only reads state or acts between sweeps (constraints, a device start, the log joint
+ * trace, the pair check, the predictive summaries, split-merge moves, feature selection, missing cells). */
+int bmm_set_summary(const bmm_summary_opts* opts, const bmm_summary_out* out);
+/* The bytes a run's device buffers take -- the traces, and with keep_trace the label trace and the two staging blocks
+ * of its way out -- plus, with summary != 0, the summary's own block.  A pure function, read by the run itself; no
+ * device is touched.  With keep_trace = 0 no term grows with S N.  -1 for an argument out of range. */
+int64_t bmm_run_bytes(int sampler, int64_t N, int P, int K, int S, int keep_trace, int summary);
+/* The launch shapes of the summary's kernels, from the function the launches read (no device is touched).  out:
+ *   [0] threads per workgroup                     [1] workgroups of k_sum_fold (its grid cap: [2])
+ *   [2] the cap                                   [3] words per plane of the counts (N rounded up to 64)
+ *   [4] bytes of dynamic LDS of k_sum_fold        [5] workgroups of k_sum_profiles
+ *   [6] workgroups of k_sum_finish                [7] its bytes of dynamic LDS
+ *   [8] bytes of the counts                       [9] bytes of the summary's whole block
+ *   [10] launches per folded sweep with a pivot (memsets included)   [11] ... and without one.
+ * BMM_E_ARG unless N, P, K >= 1 and N < 2^32. */
+int bmm_summary_plan(int64_t N, int P, int K, int64_t out[12]);
+/* Resident chains.  bmm_chain_set_summary arms (opts->keep_trace is ignored) or, with opts NULL, disarms and frees;
+ * BMM_E_UNSUPPORTED on a sharded chain, a chain of the allocation sampler and a tempered chain, BMM_E_STATE inside a
+ * run, BMM_E_ARG as above.  Armed, bmm_chain_sweeps_summary(c, n) runs n sweeps and folds every stride-th of them from
+ * its first on (agree n int64 and permutations n x K column-major, or NULL); plain bmm_chain_sweeps folds nothing.  The
+ * _FIRST pivot is the state after the first sweep a bmm_chain_sweeps_summary call runs.  bmm_chain_summary_state folds
+ * nothing: it relabels the present state against the pivot and returns its permutation (K) and agreement; BMM_E_STATE
+ * before a pivot exists.  bmm_chain_get_summary finishes (z_hat, n_max, size_sum) and copies out; it waits, and may
+ * be called again after more sweeps.  bmm_chain_summary_reset zeroes the folds and forgets a _FIRST pivot. */
+int bmm_chain_set_summary(bmm_chain* c, const bmm_summary_opts* opts);
+int bmm_chain_summary_state(bmm_chain* c, int32_t* perm_out, int64_t* agree_out);
+int bmm_chain_sweeps_summary(bmm_chain* c, int n, int64_t* agree, int32_t* permutations);
+int bmm_chain_get_summary(bmm_chain* c, bmm_summary_out* out);
+int bmm_chain_summary_reset(bmm_chain* c);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
