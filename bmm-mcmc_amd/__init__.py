@@ -21,7 +21,7 @@ from .rdata import read_rdata_matrix  # the package's bundled data sets (data/*.
 __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "Chain", "BmmError", "NA_INTEGER", "set_progress",
            "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
            "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
-           "partition_distances", "posterior_similarity", "partition_plan", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
+           "partition_distances", "posterior_similarity", "partition_plan", "partition_search", "partition_search_plan", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
            "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat", "pair_check", "pair_check_plan", "pair_check_pairs", "PAIR_CHECK_MAX_M", "run_bytes", "summary_plan", "Ladder", "temper_ladder", "TEMPER_MAX_RUNGS"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
@@ -413,6 +413,157 @@ def partition_plan(S, N, Kc, candidates=None, criterion="binder"):
     _capi.check(_capi.lib().bmm_device_partition_plan(_C.c_int(int(S)), _C.c_int64(int(N)), _C.c_int(int(Kc)),
                                                       _C.c_int(C), _C.c_int(_criterion(criterion)), out))
     return dict(zip(_PT_PLAN_FIELDS, (int(v) for v in out)))
+
+
+# ---------------------------------------------------------------- partition_search=: greedy search for the estimate
+PARTITION_SEARCH_MAX_K = 64  # include/bmm_mcmc.h BMM_PARTITION_SEARCH_MAX_K
+_PS_KEYS = ("batch", "min_batch", "max_passes", "max_clusters")
+
+
+class _SearchOpts(_C.Structure):  # bmm_partition_search_opts
+    _fields_ = [("batch", _C.c_int64), ("min_batch", _C.c_int64), ("max_passes", _C.c_int), ("max_clusters", _C.c_int)]
+
+
+class _SearchOut(_C.Structure):  # bmm_partition_search_out
+    _fields_ = [(k, _C.c_void_p) for k in ("z_hat", "binder2", "loss", "start_loss", "start_binder2", "passes", "pass_batch",
+                                           "pass_moved", "pass_binder2", "pass_total", "converged", "n_clusters")]
+
+
+def _search_opts(N, Kc, batch=None, min_batch=None, max_passes=50, max_clusters=None):
+    """the options of a search with the defaults filled in: batch ceil(N / 8), min_batch ceil(N / 256), Ka = Kc"""
+    batch = -(-N // 8) if batch is None else int(batch)
+    min_batch = -(-N // 256) if min_batch is None else int(min_batch)
+    max_passes = int(max_passes)
+    Ka = int(Kc) if max_clusters is None else int(max_clusters)
+    if batch < 1 or min_batch < 1:
+        raise ValueError("partition_search: batch and min_batch must be >= 1")
+    if max_passes < 1:
+        raise ValueError("partition_search: max_passes must be >= 1")
+    if Ka < 1 or Ka > PARTITION_SEARCH_MAX_K:
+        raise ValueError("partition_search: max_clusters must be in 1 .. %d" % PARTITION_SEARCH_MAX_K)
+    return _SearchOpts(batch, min_batch, max_passes, Ka)
+
+
+class _Search:
+    """Outputs of a greedy search (bmm_device_partition_search, or armed with bmm_set_partition_search for a run)."""
+
+    def __init__(self, criterion, N, opts):
+        self.criterion, self.opts = criterion, opts
+        P = opts.max_passes
+        self.z = _np.zeros(N, dtype=_np.int32)
+        self.u64 = _np.zeros(2, dtype=_np.uint64)   # binder2, start_binder2
+        self.f64 = _np.full(2, _np.nan)             # loss, start_loss
+        self.i32 = _np.full(3, -1, dtype=_np.int32)  # passes, converged, n_clusters
+        self.pb = _np.zeros(P, dtype=_np.int64)
+        self.pm = _np.zeros(P, dtype=_np.int64)
+        self.p2 = _np.zeros(P, dtype=_np.uint64)
+        self.ptot = _np.full(P, _np.nan)
+        self.s = _SearchOut(self.z.ctypes.data, self.u64.ctypes.data, self.f64.ctypes.data, self.f64.ctypes.data + 8,
+                            self.u64.ctypes.data + 8, self.i32.ctypes.data, self.pb.ctypes.data, self.pm.ctypes.data,
+                            self.p2.ctypes.data, self.ptot.ctypes.data, self.i32.ctypes.data + 4, self.i32.ctypes.data + 8)
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_partition_search(_C.byref(self.opts), _C.byref(self.s)))
+
+    def result(self):
+        n = int(self.i32[0])
+        if n < 0:  # the run had no usable row: nothing was searched
+            return None
+        total = [int(v) for v in self.p2[:n]] if self.criterion == "binder" else [float(v) for v in self.ptot[:n]]
+        return {"z": self.z, "loss": float(self.f64[0]), "binder2": int(self.u64[0]), "start_loss": float(self.f64[1]),
+                "start_binder2": int(self.u64[1]), "passes": n, "batch": [int(v) for v in self.pb[:n]],
+                "moved": [int(v) for v in self.pm[:n]], "total": total, "converged": bool(self.i32[1]),
+                "n_clusters": int(self.i32[2])}
+
+
+def partition_search(z, criterion="binder", start=None, batch=None, min_batch=None, max_passes=50, max_clusters=None,
+                     device=0, Kc=None):
+    """Greedy search for the clustering point estimate, on the device (include/bmm_mcmc.h "greedy search", DESIGN.md
+    section 27).  z: S x N labels, 1-based, as partition_distances takes them.  From `start` (N labels in
+    1 .. max_clusters; default: the row of z that partition_distances would choose) single rows are moved to whichever
+    cluster lowers the posterior expected Binder or VI loss most, in passes of batches of `batch` rows scored against
+    one state of the tables (default ceil(N / 8), halved down to `min_batch`, default ceil(N / 256), whenever a pass
+    does not improve), until no row wants to move or `max_passes` passes have run.  `max_clusters`: the slots a row may
+    move to, empty ones included (default Kc, at most 64).  Returns {"z" (N,) the searched partition, "loss" its expected
+    loss, "binder2" its exact total sum_t 2 B(z, z_t), "start_loss", "start_binder2", "passes", and per pass "batch",
+    "moved", "total" (binder2 as Python integers, or the VI total S N x expected VI), "converged" (no single-row move
+    lowers the loss), "n_clusters"}.  The result is never worse than the start.  Kc: number of categories of z (default:
+    the largest label), at most 64."""
+    z = _as_trace(z)
+    S, N = z.shape
+    code = _criterion(criterion)
+    Kc = max(1, int(z.max())) if Kc is None else int(Kc)
+    opts = _search_opts(N, Kc, batch, min_batch, max_passes, max_clusters)
+    st = None
+    if start is not None:
+        st = _np.ascontiguousarray(start, dtype=_np.int32)
+        if st.shape != (N,):
+            raise ValueError("start must have one label per observation")
+    so = _Search(criterion, N, opts)
+    _capi.check(_capi.lib().bmm_device_partition_search(
+        _C.c_int(device), _capi.vp(z), _C.c_int(S), _C.c_int64(N), _C.c_int(Kc), _C.c_int(code),
+        _capi.vp(st) if st is not None else None, _C.byref(opts), _C.byref(so.s)))
+    return so.result()
+
+
+_PS_PLAN_FIELDS = ("label_bytes", "slot_stride", "threads_per_row", "rows_per_workgroup", "draws_per_block", "draw_blocks",
+                   "block_bound", "lds_bytes", "workgroups", "batches", "vi", "table_bytes")
+
+
+def partition_search_plan(S, N, Kc, max_clusters=None, criterion="binder", batch=None):
+    """Which form of the search kernels a shape runs, read from the library's launch arithmetic without touching a
+    device (bmm_partition_search_plan): a dict of the fields include/bmm_mcmc.h lists; "block_bound" is 0 when a block
+    of draws holds all S, 1 when the LDS budget bounds it, 2 when the 32-bit sums of a block do."""
+    out = (_C.c_int64 * 12)()
+    N = int(N)
+    Ka = int(Kc) if max_clusters is None else int(max_clusters)
+    batch = -(-N // 8) if batch is None else int(batch)
+    L = _capi.lib()
+    L.bmm_partition_search_plan.argtypes = [_C.c_int, _C.c_int64, _C.c_int, _C.c_int, _C.c_int, _C.c_int64, _C.c_void_p]
+    _capi.check(L.bmm_partition_search_plan(int(S), N, int(Kc), Ka, _criterion(criterion), batch, out))
+    return dict(zip(_PS_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def _make_search(partition_search, partition, N, K, chains):
+    """partition_search= of a wrapper, checked before any device is touched: True or a dict of batch, min_batch,
+    max_passes, max_clusters.  One chain: the outputs to arm; several: the options (searched after pooling)."""
+    if partition_search is None or partition_search is False:
+        return None
+    if partition is None:
+        raise ValueError('partition_search= needs partition="binder" or "vi"')
+    kw = {} if partition_search is True else dict(partition_search)
+    bad = sorted(set(kw) - set(_PS_KEYS))
+    if bad:
+        raise ValueError("partition_search: unknown option %s (known: %s)" % (bad[0], ", ".join(_PS_KEYS)))
+    if K > PARTITION_SEARCH_MAX_K:
+        raise ValueError("partition_search= takes at most %d categories (got %d)" % (PARTITION_SEARCH_MAX_K, K))
+    opts = _search_opts(N, K, **kw)
+    if opts.max_clusters < K:
+        raise ValueError("partition_search: max_clusters must be at least the %d labels of the run" % K)
+    return kw if int(chains) > 1 else _Search(partition, N, opts)
+
+
+def _with_search(out, ps):
+    """the search of a single-chain run beside the summary it started from"""
+    if ps is not None and "partition" in out:
+        res = ps.result()
+        if res is not None:
+            out["partition"]["search"] = res
+    return out
+
+
+def _pooled_search(chains_out, kw, partition, K, device):
+    """chains > 1: the search over the stacked traces _pooled used, from the pooled estimate, through the stand-alone call"""
+    if kw is None:
+        return chains_out
+    rows = []
+    for o in chains_out:
+        z = o["z"]
+        rows.append(z[[s for s in range(z.shape[0]) if z[s].min() >= 1]])
+    zz = _np.asfortranarray(_np.concatenate(rows, axis=0))
+    res = partition_search(zz, partition, start=chains_out[0]["partition"]["z"], device=device, Kc=K, **kw)
+    chains_out[0]["partition"]["search"] = res  # (one dict shared by every chain object)
+    return chains_out
 
 
 # ---------------------------------------------------------------- relabel="ecr": relabelling from the label trace alone
@@ -1413,7 +1564,7 @@ class _Init:
 
 
 def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None, lp=None, tp=None, pc=None,
-         mi=None, cs=None, su=None):
+         mi=None, cs=None, su=None, ps=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
     them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
     L = _capi.lib()
@@ -1423,6 +1574,8 @@ def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=
         fs.arm()
     if part is not None:
         part.arm()
+    if ps is not None:
+        ps.arm()
     if loo is not None:
         loo.arm()
     if ecr is not None:
@@ -1599,7 +1752,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                     select_features=False, rho=0.5, init="random", init_iters=INIT_ITERS, ecr_pivot="iterative",
                     ecr_max_iter=50, logpost=False, temper=None, swap_every=1, temper_hottest=0.1, pair_check=None,
                     pair_check_stride=1, pair_check_trace=False, missing=None, known=None, allowed=None, summary=None,
-                    summary_pivot="first", summary_stride=1, keep_trace=True):
+                    summary_pivot="first", summary_stride=1, keep_trace=True, partition_search=None):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -1716,6 +1869,13 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     the run carves no S x N label trace on the device and none on the host, `z` is None, theta and alpha stay; run_bytes()
     tells what either run takes.  Per chain (chains=1); not with relabel=, temper= (two relabellings; a ladder), and
     keep_trace=False not with partition=, similarity_of=.
+    `partition_search=True` (needs partition=), or a dict of `batch`, `min_batch`, `max_passes`, `max_clusters`: after the
+    summary the device searches from the chosen sweep for a better estimate, moving single rows to whichever cluster
+    lowers the expected loss most until none wants to move (partition_search(); include/bmm_mcmc.h "greedy search",
+    DESIGN.md section 27).  `partition` gains `search = {"z", "loss", "binder2", "start_loss", "start_binder2", "passes",
+    "batch", "moved", "total", "converged", "n_clusters"}`; its other keys, z, theta and alpha are those of the run without
+    it, and `ecr_pivot="partition"` goes on using the visited sweep.  At most 64 categories.  With `chains > 1` the search
+    runs once over the pooled traces from the pooled estimate.
     """
     data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
@@ -1733,6 +1893,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
+    ps = _make_search(partition_search, partition, N, K, chains)
     fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, False, newdata, loo)
     lo = _make_loo(loo, N, nsamples - burnin, chains, False)
     lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
@@ -1742,7 +1903,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                        bool(relabel) or ecr_req is not None, partition, similarity_of)
 
     def done(out):
-        out = _with_summary(out, su)
+        out = _with_search(_with_summary(out, su), ps)
         if tp is not None:
             out["temper"] = tp.result()
         if fs is not None:
@@ -1771,7 +1932,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
         outs = _multi("collapsed", X, chains, devices, z0s, None, None, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, False)
         if lp is not None:
             _lp_chains(outs, X, "collapsed", K, alpha, beta, gamma, a, b, dev0)
-        outs = _ecr_chains(_pooled(outs, partition, partition_stride, similarity_of, dev0), ecr_req, K, dev0)
+        outs = _ecr_chains(_pooled_search(_pooled(outs, partition, partition_stride, similarity_of, dev0), ps, partition, K, dev0), ecr_req, K, dev0)
         if ecr_map is not None:
             outs = _ecr_map(outs, ecr_map, K, dev0)
         if ini is not None:
@@ -1795,7 +1956,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                 _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
                 _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("collapsed", args, pr, rel=dr, part=pt, loo=lo, fs=fs, init=ini, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
+            rc = _run("collapsed", args, pr, rel=dr, part=pt, ps=ps, loo=lo, fs=fs, init=ini, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
@@ -1807,7 +1968,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
             _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
             _C.c_uint64(seed), _C.c_int(device), _vp0(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs, su=su)
+        rc = _run("collapsed", args, pr, hooks=rl, part=pt, ps=ps, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs, su=su)
     out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1821,7 +1982,8 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
              partition_stride=1, similarity_of=None, loo=False, split_merge=0, split_merge_scans=None,
              select_features=False, rho=0.5, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
              temper=None, swap_every=1, temper_hottest=0.1, pair_check=None, pair_check_stride=1, pair_check_trace=False,
-             missing=None, known=None, allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True):
+             missing=None, known=None, allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True,
+             partition_search=None):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
     gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
@@ -1837,7 +1999,8 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     pins that cluster there; a label that no held row occupies is an ordinary free label, and the free rows open new
     clusters as ever (the semi-supervised, novelty-detection run).  Not with split_merge=.  `allowed=` is refused here
     (ValueError): a label is whatever cluster holds it, so a set of labels says nothing about classes.  `summary`,
-    `summary_pivot`, `summary_stride`, `keep_trace`: as gibbs_collapsed, over the maxK labels."""
+    `summary_pivot`, `summary_stride`, `keep_trace`: as gibbs_collapsed, over the maxK labels.  `partition_search`: as
+    gibbs_collapsed (maxK <= 64)."""
     _init_kind(init, 0, allowed=False)
     data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
@@ -1850,6 +2013,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, maxK + 1, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
+    ps = _make_search(partition_search, partition, N, maxK, chains)
     lo = _make_loo(loo, N, nsamples - burnin, chains, False)
     fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, True, newdata, loo, split_merge)
     sm = _make_split_merge(split_merge, split_merge_scans, chains)
@@ -1860,7 +2024,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                        bool(relabel) or ecr_req is not None, partition, similarity_of)
 
     def done(out):
-        out = _with_summary(out, su)
+        out = _with_search(_with_summary(out, su), ps)
         if tp is not None:
             out["temper"] = tp.result()
         if sm is not None:
@@ -1879,7 +2043,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
         outs = _multi("dp", X, int(chains), devices, None, None, None, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, False)
         if lp is not None:
             _lp_chains(outs, X, "dp", maxK, alpha, beta, gamma, a, b, dev0)
-        outs = _ecr_chains(_pooled(outs, partition, partition_stride, similarity_of, dev0), ecr_req, maxK, dev0)
+        outs = _ecr_chains(_pooled_search(_pooled(outs, partition, partition_stride, similarity_of, dev0), ps, partition, maxK, dev0), ecr_req, maxK, dev0)
         return outs if ecr_map is None else _ecr_map(outs, ecr_map, maxK, dev0)
     S = nsamples - burnin
     W = _clamp_burnrelabel(burnrelabel, burnin)
@@ -1894,7 +2058,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                 _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
                 _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run("dp", args, pr, rel=dr, part=pt, loo=lo, sm=sm, fs=fs, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
+            rc = _run("dp", args, pr, rel=dr, part=pt, ps=ps, loo=lo, sm=sm, fs=fs, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
         return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, maxK, P, S)
@@ -1907,7 +2071,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
             _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _vp0(z),
             _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs, su=su)
+        rc = _run("dp", args, pr, hooks=rl, part=pt, ps=ps, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs, su=su)
     out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -1920,7 +2084,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
               predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None,
               loo=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1,
               pair_check_trace=False, missing=None, known=None, allowed=None, summary=None, summary_pivot="first",
-              summary_stride=1, keep_trace=True):
+              summary_stride=1, keep_trace=True, partition_search=None):
     data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
     N, P = X.shape
@@ -1933,6 +2097,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
     relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
     pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
+    ps = _make_search(partition_search, partition, N, K, chains)
     lo = _make_loo(loo, N, nsamples - burnin, chains, True)
     lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
     pc = _make_pair_check(pair_check, pair_check_stride, pair_check_trace, P, nsamples - burnin, chains)
@@ -1941,7 +2106,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
                        bool(relabel) or ecr_req is not None, partition, similarity_of)
 
     def done(out):
-        out = _with_summary(out, su)
+        out = _with_search(_with_summary(out, su), ps)
         return _with_constraints(_with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc), mi), cs)
 
     def start(sd, pi, th):
@@ -1973,7 +2138,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
                       burnin, None, seed, True)
         if lp is not None:
             _lp_chains(outs, X, sampler, K, alpha, beta, gamma, a, b, dev0)
-        outs = _ecr_chains(_pooled(outs, partition, partition_stride, similarity_of, dev0), ecr_req, K, dev0)
+        outs = _ecr_chains(_pooled_search(_pooled(outs, partition, partition_stride, similarity_of, dev0), ps, partition, K, dev0), ecr_req, K, dev0)
         return outs if ecr_map is None else _ecr_map(outs, ecr_map, K, dev0)
     on_device = _device_relabel(stephens, relabel, burnin, W)
     pi0, th0 = start(seed, initial_pi, initial_theta)
@@ -1988,7 +2153,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
                 _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
                 _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
         with _progress(debug):
-            rc = _run(base, args, pr, rel=dr, part=pt, loo=lo, lp=lp, pc=pc, mi=mi, cs=cs)
+            rc = _run(base, args, pr, rel=dr, part=pt, ps=ps, loo=lo, lp=lp, pc=pc, mi=mi, cs=cs)
         return done(_with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
     rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
     ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
@@ -2001,7 +2166,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
             _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
             _C.c_int(device), _capi.vp(pi), _vp0(z), _capi.vp(theta), _capi.vp(al))
     with _progress(debug):
-        rc = _run(base, args, pr, hooks=rl, part=pt, loo=lo, ecr=ec, lp=lp, pc=pc, mi=mi, cs=cs, su=su)
+        rc = _run(base, args, pr, hooks=rl, part=pt, ps=ps, loo=lo, ecr=ec, lp=lp, pc=pc, mi=mi, cs=cs, su=su)
     out = {"pi": pi, "alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
     if rl:
         return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
@@ -2015,20 +2180,22 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
                         predictive_trace=False, responsibilities=False, partition=None, partition_stride=1,
                         similarity_of=None, loo=False, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
                         pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None, known=None,
-                        allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True):
+                        allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True,
+                        partition_search=None):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
     src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
     "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`: as gibbs_collapsed; log_prior is
     the stick-breaking prior with the sticks integrated out, which depends on the order of the labels.  `pair_check`,
     `pair_check_stride`, `pair_check_trace`: as gibbs_collapsed.  `missing`: as gibbs_collapsed; the cells are drawn from
-    the theta the sweep has just drawn.  `known`, `allowed`: as gibbs_dp (the values name the chain's labels 1..maxK; allowed= is refused)."""
+    the theta the sweep has just drawn.  `known`, `allowed`: as gibbs_dp (the values name the chain's labels 1..maxK; allowed= is refused).
+    `partition_search`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
     return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
                      burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
                      ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed,
-                     summary, summary_pivot, summary_stride, keep_trace)
+                     summary, summary_pivot, summary_stride, keep_trace, partition_search)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
@@ -2036,18 +2203,19 @@ def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, bur
                devices=None, stephens=None, newdata=None, predictive_trace=False, responsibilities=False,
                partition=None, partition_stride=1, similarity_of=None, loo=False, init="random", ecr_pivot="iterative",
                ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None,
-               known=None, allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True):
+               known=None, allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True,
+               partition_search=None):
     """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
     `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
     "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`, `pair_check`,
     `pair_check_stride`, `pair_check_trace`, `missing`, `known`, `allowed`, `summary`, `summary_pivot`, `summary_stride`,
-    `keep_trace`: as gibbs_collapsed."""
+    `keep_trace`, `partition_search`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
     return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
                      relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
                      ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed,
-                     summary, summary_pivot, summary_stride, keep_trace)
+                     summary, summary_pivot, summary_stride, keep_trace, partition_search)
 
 
 class Chain:

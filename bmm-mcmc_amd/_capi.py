@@ -32,6 +32,7 @@ SYMBOLS = [
     "bmm_chain_sweeps_predict", "bmm_chain_get_predictive", "bmm_chain_predict_reset",
     "bmm_collapsed_run_predict", "bmm_dp_run_predict", "bmm_sb_run_predict", "bmm_full_run_predict",
     "bmm_device_partition_distances", "bmm_device_psm", "bmm_device_partition_plan", "bmm_set_partition_summary",
+    "bmm_device_partition_search", "bmm_partition_search_plan", "bmm_set_partition_search",
     "bmm_chain_set_loo", "bmm_chain_loo_state", "bmm_chain_sweeps_loo", "bmm_chain_get_loo", "bmm_chain_loo_reset",
     "bmm_set_loo_summary",
     "bmm_chain_set_split_merge", "bmm_chain_split_merge", "bmm_chain_split_merge_step", "bmm_chain_split_merge_stats",

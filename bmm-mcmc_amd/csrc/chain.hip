@@ -792,11 +792,12 @@ int run_rows_out(const bmm_chain* c, const double* dtrace, int64_t width, double
     return S > first ? rows_out(dtrace + (size_t)first * (size_t)width, S - first, width, out, S, first) : BMM_OK;
 }
 
-// What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_loo_summary,
+// What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_partition_search, bmm_set_loo_summary,
 // bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost, bmm_set_temper, bmm_set_pair_check, bmm_set_missing, bmm_set_constraints; bmm_alloc_run fills `alloc` for its own run), and what a
 // *_run_predict / *_run_relabel / *_run_probs entry point was handed.
 struct RunOptions {
     struct { bool on = false; bmm_partition_out o{}; } partition;
+    struct { bool on = false, has_opts = false; bmm_partition_search_opts opts{}; bmm_partition_search_out o{}; } psearch;  // bmm_set_partition_search
     struct { bool on = false; bmm_loo_out o{}; } loo;
     struct { int moves = 0, scans = 0; } sm;
     struct { bool on = false; bmm_feature_out o{}; } fs;
@@ -5675,8 +5676,211 @@ int pt_check_idx(const int64_t* idx, int64_t M, int64_t N) {
     return BMM_OK;
 }
 
+// ---- greedy search for the point estimate (include/bmm_mcmc.h "greedy search") ----
+// Which form of the k_ps_* kernels a shape runs: a pure function of (S, N, Kc, Ka, criterion, batch) -- the launches
+// below and bmm_partition_search_plan both read it from here.
+constexpr size_t kPsLdsBudget = (size_t)48 << 10;                                  // bytes of tables per workgroup
+constexpr size_t kPsScoreBytes = (size_t)kPtThreads * kPsChunk * sizeof(int64_t);  // the scores of a workgroup's rows
+struct PsPlan {
+    int el = 1, KaP = 12, nch = 1, rows = kPtThreads, D = 1, blocks = 1, bound = 0, vi = 0, apply_y = 1, apply_len = 1;
+    int64_t wgs = 1, batches = 1, pitch = 0, span = 0;
+    size_t lds_bytes = 0, table_bytes = 0;
+};
+PsPlan ps_plan(int S, int64_t N, int Kc, int Ka, int criterion, int64_t batch) {
+    PsPlan p;
+    p.vi = criterion == BMM_PARTITION_VI ? 1 : 0;
+    p.nch = (Ka + kPsChunk - 1) / kPsChunk;
+    p.KaP = p.nch * kPsChunk + 4;  // runs of 8 slots stay 16-byte aligned, neighbouring labels 4 banks apart
+    p.rows = kPtThreads / p.nch;
+    p.pitch = (N + 15) / 16 * 16;
+    const size_t cell = p.vi ? sizeof(double) : sizeof(uint32_t);
+    const size_t tb = (size_t)Kc * p.KaP * cell;
+    int64_t D = S;
+    if ((int64_t)(kPsLdsBudget / tb) < D) { D = (int64_t)(kPsLdsBudget / tb); p.bound = 1; }
+    if (!p.vi && D * N >= ((int64_t)1 << 32)) { D = (((int64_t)1 << 32) - 1) / N; p.bound = 2; }
+    p.D = (int)(D < 1 ? 1 : D);
+    p.blocks = (S + p.D - 1) / p.D;
+    p.lds_bytes = (size_t)p.D * tb > kPsScoreBytes ? (size_t)p.D * tb : kPsScoreBytes;
+    if (batch > N) batch = N;
+    p.wgs = (batch + p.rows - 1) / p.rows;
+    p.batches = (N + batch - 1) / batch;
+    p.table_bytes = (size_t)S * Kc * p.KaP * (sizeof(uint32_t) + (p.vi ? 2 * sizeof(double) : 0));
+    p.span = 8192;  // rows of a draw per workgroup of k_ps_tables
+    p.apply_y = S < 8 ? S : 8;  // k_ps_apply: the draws of a moved row over this many workgroups
+    p.apply_len = (S + p.apply_y - 1) / p.apply_y;
+    return p;
+}
+struct PsOpts { int64_t batch = 0, min_batch = 0; int max_passes = 50, Ka = 0; };
+// the options resolved against a shape, and everything refused before any device is touched
+int ps_check(int S, int64_t N, int Kc, int criterion, const bmm_partition_search_opts* o, bool own_start, PsOpts& r) {
+    int rc = pt_check_shape(S, N, Kc, criterion, 1);
+    if (rc) return rc;
+    if (Kc > BMM_PARTITION_SEARCH_MAX_K)
+        return set_err(BMM_E_ARG, "partition search: Kc = %d is above the %d whose tables fit in LDS", Kc, BMM_PARTITION_SEARCH_MAX_K);
+    r.batch = o ? o->batch : (N + 7) / 8;
+    r.min_batch = o ? o->min_batch : (N + 255) / 256;
+    r.max_passes = o ? o->max_passes : 50;
+    r.Ka = o ? o->max_clusters : Kc;
+    if (r.batch < 1 || r.min_batch < 1) return set_err(BMM_E_ARG, "partition search: batch and min_batch must be >= 1 (got %lld, %lld)", (long long)r.batch, (long long)r.min_batch);
+    if (r.max_passes < 1) return set_err(BMM_E_ARG, "partition search: max_passes must be >= 1 (got %d)", r.max_passes);
+    if (r.Ka < 1 || r.Ka > BMM_PARTITION_SEARCH_MAX_K)
+        return set_err(BMM_E_ARG, "partition search: max_clusters must be in 1 .. %d (got %d)", BMM_PARTITION_SEARCH_MAX_K, r.Ka);
+    if (own_start && r.Ka < Kc)
+        return set_err(BMM_E_ARG, "partition search: starting from a draw needs max_clusters >= Kc (got %d < %d)", r.Ka, Kc);
+    if (r.batch > N) r.batch = N;
+    if (r.min_batch > r.batch) r.min_batch = r.batch;
+    return BMM_OK;
+}
+int ps_check_out(const bmm_partition_search_out* o) {
+    if (!o || !o->z_hat || !o->binder2 || !o->loss || !o->start_loss || !o->start_binder2 || !o->passes || !o->pass_batch ||
+        !o->pass_moved || !o->pass_binder2 || !o->pass_total || !o->converged || !o->n_clusters)
+        return set_err(BMM_E_ARG, "partition search: null output buffer");
+    return BMM_OK;
+}
+
+struct PsWork {
+    int S = 0, Kc = 0, Ka = 0;
+    int64_t N = 0;
+    PsPlan plan;
+    DevBuf T, n, phi, phim, sphi, c, best, newc, d2, w, moved, res;
+    size_t cells() const { return (size_t)S * Kc * plan.KaP; }
+    int alloc(int S_, int64_t N_, int Kc_, int Ka_, int criterion, int64_t batch) {
+        S = S_; N = N_; Kc = Kc_; Ka = Ka_;
+        plan = ps_plan(S, N, Kc, Ka, criterion, batch);
+        HIP_TRY(T.alloc(cells() * sizeof(uint32_t)));
+        HIP_TRY(n.alloc((size_t)plan.KaP * sizeof(uint32_t)));
+        if (plan.vi) {
+            HIP_TRY(phi.alloc(cells() * sizeof(double)));
+            HIP_TRY(phim.alloc(cells() * sizeof(double)));
+            HIP_TRY(sphi.alloc((size_t)2 * plan.KaP * sizeof(double)));
+        }
+        HIP_TRY(c.alloc((size_t)N * sizeof(int32_t)));
+        HIP_TRY(best.alloc((size_t)N * sizeof(int32_t)));
+        HIP_TRY(newc.alloc((size_t)N * sizeof(int32_t)));
+        HIP_TRY(d2.alloc((size_t)S * sizeof(uint64_t)));
+        HIP_TRY(w.alloc((size_t)S * sizeof(double)));
+        HIP_TRY(moved.alloc(sizeof(unsigned long long)));
+        HIP_TRY(res.alloc(3 * sizeof(unsigned long long)));
+        return BMM_OK;
+    }
+};
+// VI: the phi tables follow the counts
+int ps_phi(hipStream_t st, PsWork& w) {
+    if (!w.plan.vi) return BMM_OK;
+    const int64_t cells = (int64_t)w.cells();
+    int64_t g = (cells + kPtThreads - 1) / kPtThreads;
+    if (g > 1024) g = 1024;
+    hipLaunchKernelGGL(k_ps_phi, dim3((unsigned)g), dim3(256), 0, st, w.T.as<uint32_t>(), w.n.as<uint32_t>(), cells, w.plan.KaP,
+                       w.phi.as<double>(), w.phim.as<double>(), w.sphi.as<double>());
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+// tables and sizes of the candidate as it stands in w.c
+int ps_rebuild(hipStream_t st, PsWork& w, const uint8_t* lab) {
+    const PsPlan& p = w.plan;
+    HIP_TRY(hipMemsetAsync(w.T.p, 0, w.cells() * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(w.n.p, 0, (size_t)p.KaP * sizeof(uint32_t), st));
+    const dim3 grid((unsigned)((w.N + p.span - 1) / p.span), (unsigned)w.S);
+    const size_t lds = ((size_t)w.Kc * p.KaP + p.KaP) * sizeof(uint32_t);
+    hipLaunchKernelGGL(k_ps_tables, grid, dim3(256), lds, st, lab, p.pitch, w.N, w.Kc, p.KaP, p.span, w.c.as<int32_t>(), w.T.as<uint32_t>(), w.n.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    return ps_phi(st, w);
+}
+// the totals of the state and the moved count, read back: the one wait of a pass
+int ps_total(hipStream_t st, PsWork& w, uint64_t* binder2, double* vi_tot, int64_t* moved) {
+    const PsPlan& p = w.plan;
+    if (p.vi) hipLaunchKernelGGL(k_ps_total<true>, dim3(w.S), dim3(256), 0, st, w.T.as<uint32_t>(), w.n.as<uint32_t>(), w.Kc, w.Ka, p.KaP, w.d2.as<uint64_t>(), w.w.as<double>());
+    else hipLaunchKernelGGL(k_ps_total<false>, dim3(w.S), dim3(256), 0, st, w.T.as<uint32_t>(), w.n.as<uint32_t>(), w.Kc, w.Ka, p.KaP, w.d2.as<uint64_t>(), w.w.as<double>());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_ps_reduce, dim3(1), dim3(256), 0, st, w.d2.as<uint64_t>(), w.w.as<double>(), w.S, w.moved.as<unsigned long long>(), w.res.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    unsigned long long h[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, w.res.p, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *binder2 = h[0];
+    std::memcpy(vi_tot, &h[1], sizeof(double));
+    *moved = (int64_t)h[2];
+    return BMM_OK;
+}
+// one pass with batch B: score, apply (and, for VI, the phi tables) per batch, everything enqueued
+int ps_pass(hipStream_t st, PsWork& w, const uint8_t* lab, int64_t B) {
+    const PsPlan& p = w.plan;
+    HIP_TRY(hipMemsetAsync(w.moved.p, 0, sizeof(unsigned long long), st));
+    for (int64_t i0 = 0; i0 < w.N; i0 += B) {
+        const int64_t i1 = i0 + B < w.N ? i0 + B : w.N;
+        const dim3 gs((unsigned)((i1 - i0 + p.rows - 1) / p.rows)), ga((unsigned)((i1 - i0 + kPtThreads - 1) / kPtThreads), (unsigned)p.apply_y);
+        if (p.vi) hipLaunchKernelGGL(k_ps_score<true>, gs, dim3(256), p.lds_bytes, st, lab, p.pitch, w.S, w.Kc, w.Ka, p.KaP, p.nch, p.rows, p.D, w.T.as<uint32_t>(), w.phi.as<double>(), w.phim.as<double>(), w.sphi.as<double>(), w.n.as<uint32_t>(), w.c.as<int32_t>(), i0, i1, w.newc.as<int32_t>());
+        else hipLaunchKernelGGL(k_ps_score<false>, gs, dim3(256), p.lds_bytes, st, lab, p.pitch, w.S, w.Kc, w.Ka, p.KaP, p.nch, p.rows, p.D, w.T.as<uint32_t>(), nullptr, nullptr, nullptr, w.n.as<uint32_t>(), w.c.as<int32_t>(), i0, i1, w.newc.as<int32_t>());
+        hipLaunchKernelGGL(k_ps_apply, ga, dim3(256), 0, st, lab, p.pitch, w.S, w.Kc, p.KaP, p.apply_len, w.T.as<uint32_t>(), w.n.as<uint32_t>(), w.c.as<int32_t>(), w.newc.as<int32_t>(), i0, i1, w.moved.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(w.c.as<int32_t>() + i0, w.newc.as<int32_t>() + i0, (size_t)(i1 - i0) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        const int rc = ps_phi(st, w);
+        if (rc) return rc;
+    }
+    return BMM_OK;
+}
+// The search (the header's pseudo-code) from the candidate in w.c (0-based slots), over the label block `lab`
+int ps_search(hipStream_t st, PsWork& w, const uint8_t* lab, const PsOpts& o, const bmm_partition_search_out& out) {
+    const size_t nb = (size_t)w.N * sizeof(int32_t);
+    const bool vi = w.plan.vi != 0;
+    const double SN = (double)w.S * (double)w.N;
+    auto loss_of = [&](uint64_t b2, double vt) { return vi ? vt / SN : (double)b2 / (2.0 * (double)w.S); };
+    int rc = ps_rebuild(st, w, lab);
+    if (rc) return rc;
+    uint64_t b2 = 0, best_b2 = 0;
+    double vt = 0.0, best_vt = 0.0;
+    int64_t moved = 0;
+    rc = ps_total(st, w, &best_b2, &best_vt, &moved);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(w.best.p, w.c.p, nb, hipMemcpyDeviceToDevice, st));
+    *out.start_binder2 = best_b2;
+    *out.start_loss = loss_of(best_b2, best_vt);
+    int passes = 0, converged = 0;
+    int64_t B = o.batch;
+    while (passes < o.max_passes) {
+        rc = ps_pass(st, w, lab, B);
+        if (rc == BMM_OK) rc = ps_total(st, w, &b2, &vt, &moved);
+        if (rc) return rc;
+        out.pass_batch[passes] = B;
+        out.pass_moved[passes] = moved;
+        out.pass_binder2[passes] = b2;
+        out.pass_total[passes] = vi ? vt : (double)b2;
+        ++passes;
+        if (moved == 0) { converged = 1; break; }
+        if (vi ? vt < best_vt : b2 < best_b2) {
+            best_b2 = b2; best_vt = vt;
+            HIP_TRY(hipMemcpyAsync(w.best.p, w.c.p, nb, hipMemcpyDeviceToDevice, st));
+        } else {
+            HIP_TRY(hipMemcpyAsync(w.c.p, w.best.p, nb, hipMemcpyDeviceToDevice, st));
+            rc = ps_rebuild(st, w, lab);
+            if (rc) return rc;
+            if (B == o.min_batch) break;
+            B = B / 2 > o.min_batch ? B / 2 : o.min_batch;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(out.z_hat, w.best.p, nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<char> used((size_t)w.Ka, 0);
+    for (int64_t i = 0; i < w.N; ++i) { used[(size_t)out.z_hat[i]] = 1; out.z_hat[i] += 1; }
+    int nc = 0;
+    for (char u : used) nc += u;
+    *out.binder2 = best_b2;
+    *out.loss = loss_of(best_b2, best_vt);
+    *out.passes = passes;
+    *out.converged = converged;
+    *out.n_clusters = nc;
+    return BMM_OK;
+}
+
 // The summary of a run (bmm_set_partition_summary): what the run checks of it before any device is touched
 int pt_run_check(const RunOptions& opts, int S, int64_t N, int K) {
+    if (opts.psearch.on) {
+        if (!opts.partition.on) return set_err(BMM_E_ARG, "partition search: needs an armed partition summary (bmm_set_partition_summary)");
+        PsOpts r;
+        int rc = ps_check(S, N, K, opts.partition.o.criterion, opts.psearch.has_opts ? &opts.psearch.opts : nullptr, true, r);
+        if (rc == BMM_OK) rc = ps_check_out(&opts.psearch.o);
+        if (rc) return rc;
+    }
     if (!opts.partition.on) return BMM_OK;
     const bmm_partition_out& o = opts.partition.o;
     if (!o.loss || !o.best || !o.n_used) return set_err(BMM_E_ARG, "partition: null buffer (loss, best, n_used)");
@@ -5686,7 +5890,7 @@ int pt_run_check(const RunOptions& opts, int S, int64_t N, int K) {
     return pt_check_idx(o.psm_idx, o.psm_M, N);
 }
 // after the last sweep, before the trace leaves: everything on the chain's stream, then one wait
-int pt_run_summary(bmm_chain* c, const bmm_partition_out& o) {
+int pt_run_summary(bmm_chain* c, const bmm_partition_out& o, const RunOptions& opts) {
     const int64_t N = c->p.N;
     const int first = (c->burnin == 0 && c->p.mode != MODE_COLLAPSED) ? 1 : 0;  // row 0: the unassigned starting state
     const int Su = c->S - first;
@@ -5710,6 +5914,16 @@ int pt_run_summary(bmm_chain* c, const bmm_partition_out& o) {
         for (int64_t i = 0; i < N; ++i) o.z_best[i] += 1;
     }
     if (o.psm_M > 0) rc = pt_psm(c->stream, w, o.psm_idx, o.psm_M, o.psm_cnt);
+    if (rc == BMM_OK && opts.psearch.on) {  // the greedy search from the chosen row, over the rows the summary used
+        PsOpts r;
+        rc = ps_check(Su, N, c->p.K, o.criterion, opts.psearch.has_opts ? &opts.psearch.opts : nullptr, true, r);
+        if (rc) return rc;
+        PsWork sw;
+        rc = sw.alloc(Su, N, c->p.K, r.Ka, o.criterion, r.batch);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(sw.c.p, c->dTrace + (size_t)(first + best) * N, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+        rc = ps_search(c->stream, sw, w.lab.as<uint8_t>(), r, opts.psearch.o);
+    }
     return rc;
 }
 
@@ -6191,7 +6405,7 @@ int run_body(bmm_chain* c, int nsamples, const RunIO& io, const RunOptions& opts
     if (explicit_params(sampler))
         HIP_TRY(hipMemcpyAsync(io.pi_out, c->dPiTrace, (size_t)S * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (opts.partition.on) {  // the clustering summary, from the resident trace (labels as sampled)
-        rc = pt_run_summary(c, opts.partition.o);
+        rc = pt_run_summary(c, opts.partition.o, opts);
         if (rc) return rc;
     }
     DevBuf ecr_perm;
@@ -6953,6 +7167,74 @@ int bmm_set_ecr_relabel(const bmm_ecr_out* out) {
 int bmm_set_partition_summary(const bmm_partition_out* out) {
     g_armed.partition.on = out != nullptr;
     if (out) g_armed.partition.o = *out;
+    return BMM_OK;
+}
+
+int bmm_set_partition_search(const bmm_partition_search_opts* opts, const bmm_partition_search_out* out) {
+    g_armed.psearch.on = out != nullptr;
+    g_armed.psearch.has_opts = out != nullptr && opts != nullptr;
+    if (out) g_armed.psearch.o = *out;
+    if (out && opts) g_armed.psearch.opts = *opts;
+    return BMM_OK;
+}
+
+int bmm_device_partition_search(int device, const int32_t* z, int S, int64_t N, int Kc, int criterion,
+                                const int32_t* start, const bmm_partition_search_opts* opts,
+                                const bmm_partition_search_out* out) {
+    return guarded([&]() -> int {
+        if (!z) return set_err(BMM_E_ARG, "null argument");
+        PsOpts r;
+        int rc = ps_check(S, N, Kc, criterion, opts, start == nullptr, r);
+        if (rc == BMM_OK) rc = ps_check_out(out);
+        if (rc == BMM_OK) rc = pt_check_labels(z, S, N, 1, Kc, nullptr, "partition search");
+        if (rc) return rc;
+        if (start)
+            for (int64_t i = 0; i < N; ++i)
+                if (start[i] < 1 || start[i] > r.Ka)
+                    return set_err(BMM_E_ARG, "partition search: start label %d at observation %lld (0-based) is outside 1 .. %d", start[i], (long long)i, r.Ka);
+        HIP_TRY(hipSetDevice(device));
+        PtWork w;
+        w.shape(S, N, Kc, criterion, 1);
+        rc = w.alloc_labels();
+        if (rc == BMM_OK) rc = pt_upload(w, z);
+        if (rc) return rc;
+        std::vector<int32_t> c0((size_t)N);
+        if (start) {
+            for (int64_t i = 0; i < N; ++i) c0[(size_t)i] = start[i] - 1;
+        } else {  // the draws' minimiser at stride 1, as bmm_device_partition_distances finds it
+            rc = w.alloc_pairs(false);
+            if (rc == BMM_OK) rc = pt_compute(nullptr, w);
+            if (rc) { (void)hipDeviceSynchronize(); return rc; }
+            HIP_TRY(hipDeviceSynchronize());
+            std::vector<double> loss((size_t)S);
+            int best = -1;
+            rc = pt_fetch(w, loss.data(), nullptr, &best, nullptr);
+            if (rc) return rc;
+            for (int64_t i = 0; i < N; ++i) c0[(size_t)i] = z[(size_t)best + (size_t)i * S] - 1;
+        }
+        int flag = 0;
+        HIP_TRY(hipMemcpy(&flag, w.flag.p, sizeof flag, hipMemcpyDeviceToHost));
+        if (flag) return set_err(BMM_E_STATE, "partition search: a label outside 0 .. %d reached the device", Kc - 1);
+        PsWork sw;
+        rc = sw.alloc(S, N, Kc, r.Ka, criterion, r.batch);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(sw.c.p, c0.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
+        rc = ps_search(nullptr, sw, w.lab.as<uint8_t>(), r, *out);
+        if (rc) (void)hipDeviceSynchronize();
+        return rc;
+    });
+}
+
+// Which form of every k_ps_* kernel a shape runs, from the function the launches call (no device is touched)
+int bmm_partition_search_plan(int S, int64_t N, int Kc, int Ka, int criterion, int64_t batch, int64_t out[12]) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    const bmm_partition_search_opts o{batch, 1, 1, Ka};
+    PsOpts r;
+    const int rc = ps_check(S, N, Kc, criterion, &o, false, r);
+    if (rc) return rc;
+    const PsPlan p = ps_plan(S, N, Kc, r.Ka, criterion, r.batch);
+    out[0] = p.el; out[1] = p.KaP; out[2] = p.nch; out[3] = p.rows; out[4] = p.D; out[5] = p.blocks; out[6] = p.bound;
+    out[7] = (int64_t)p.lds_bytes; out[8] = p.wgs; out[9] = p.batches; out[10] = p.vi; out[11] = (int64_t)p.table_bytes;
     return BMM_OK;
 }
 

@@ -3444,6 +3444,264 @@ __global__ __launch_bounds__(256) void k_pt_psm(const L* __restrict__ g, int S, 
             }
 }
 
+// ---- greedy search for the point estimate (include/bmm_mcmc.h "greedy search") ----------
+// The candidate c is N int32 slots in 0 .. Ka-1, the draws are the byte label block of k_pt_narrow.  One table per
+// draw, T[t][b][a] = #{i : c_i = a, z_t,i = b}, uint32, laid out [b][a] with the b stride KaP = 8 * ceil(Ka / 8) + 4
+// (the cells past Ka stay 0), in global memory between the launches and in LDS inside k_ps_score -- the two layouts
+// are the same, so staging a block of draws is one flat copy.  A row reads runs of kPsChunk slots, 16-byte aligned.
+// Every count is an integer; every floating-point sum runs in an order fixed by the shape.  No float atomics.
+constexpr int kPsChunk = 8;  // slots per thread of k_ps_score
+
+// Tables and sizes from c and the label block (both zeroed by the caller): workgroup (x, t) adds the rows
+// [x * span, x * span + span) of draw t into a table in LDS and flushes its non-zero cells with integer adds; the
+// workgroups of draw 0 also count the sizes n_a.  Dynamic LDS: Kc * KaP + KaP uint32.
+__global__ __launch_bounds__(256) void k_ps_tables(const uint8_t* __restrict__ lab, int64_t pitch, int64_t N, int Kc,
+                                                   int KaP, int64_t span, const int32_t* __restrict__ c,
+                                                   uint32_t* __restrict__ T, uint32_t* __restrict__ n) {
+    extern __shared__ uint32_t pt_lds[];
+    const int tid = threadIdx.x, t = blockIdx.y, cells = Kc * KaP;
+    for (int k = tid; k < cells + KaP; k += kPtThreads) pt_lds[k] = 0;
+    __syncthreads();
+    const int64_t i0 = (int64_t)blockIdx.x * span, i1 = i0 + span < N ? i0 + span : N;
+    const uint8_t* __restrict__ row = lab + (size_t)t * pitch;
+    for (int64_t i = i0 + tid; i < i1; i += kPtThreads) {
+        const int a = c[i];
+        atomicAdd(&pt_lds[(uint32_t)row[i] * KaP + a], 1u);
+        if (t == 0) atomicAdd(&pt_lds[cells + a], 1u);
+    }
+    __syncthreads();
+    uint32_t* const Tt = T + (size_t)t * cells;
+    for (int k = tid; k < cells; k += kPtThreads)
+        if (pt_lds[k]) atomicAdd(&Tt[k], pt_lds[k]);
+    if (t == 0)
+        for (int k = tid; k < KaP; k += kPtThreads)
+            if (pt_lds[cells + k]) atomicAdd(&n[k], pt_lds[cells + k]);
+}
+
+// phi(n) = f(n + 1) - f(n), phi(0) = 0: what a cell of n gains in f when a row joins it
+__device__ inline double ps_phi(uint32_t n) { return pt_f(n + 1u) - pt_f(n); }
+
+// VI only, after every change of the tables: phi[k] = phi(T[k]) and phim[k] = phi(T[k] - 1) (0 where T[k] = 0: never
+// read, a row's own cell holds the row) for every cell, and the same of the sizes into sphi[0 .. KaP), sphi[KaP .. 2 KaP).
+__global__ __launch_bounds__(256) void k_ps_phi(const uint32_t* __restrict__ T, const uint32_t* __restrict__ n,
+                                                int64_t cells, int KaP, double* __restrict__ phi,
+                                                double* __restrict__ phim, double* __restrict__ sphi) {
+    const int64_t stride = (int64_t)gridDim.x * kPtThreads;
+    for (int64_t k = (int64_t)blockIdx.x * kPtThreads + threadIdx.x; k < cells; k += stride) {
+        const uint32_t v = T[k];
+        phi[k] = ps_phi(v);
+        phim[k] = v ? ps_phi(v - 1u) : 0.0;
+    }
+    if (blockIdx.x == 0)
+        for (int k = threadIdx.x; k < KaP; k += kPtThreads) {
+            const uint32_t v = n[k];
+            sphi[k] = ps_phi(v);
+            sphi[KaP + k] = v ? ps_phi(v - 1u) : 0.0;
+        }
+}
+
+// The hot path: the rows [i0, i1) scored against the tables as they stand.  Thread (r, ch) of a workgroup holds row
+// i0 + blockIdx.x * rows + r and the slots [8 ch, 8 ch + 8); the nch threads of a row are neighbours.  The draws come
+// through LDS in blocks of D tables (uint32 for Binder, the binary64 phi tables for VI): per draw a thread reads its
+// row's label b and one run of 8 cells at [b][8 ch ..], lanes with the same label reading the same address.
+//   Binder  sum_t T_t[a][z_t,i] in uint32 within a block (D * N < 2^32, the plan's promise), in uint64 across blocks;
+//           g_a = S m_a - 2 (sum - S own), int64
+//   VI      sum_t phi(U_t,a) in binary64, ascending t; the own slot's cell is T - 1, read from phim in global memory;
+//           g_a = S phi(m_a) - 2 sum
+// with own = [a = c_i], m_a = n_a - own.  Then the g of a row meet in LDS and its first thread takes the smallest,
+// the current slot on a tie, then the lowest: newc[i].  Dynamic LDS: max(D tables, 256 * 8 * 8 bytes).
+template <bool VI>
+__global__ __launch_bounds__(256) void k_ps_score(const uint8_t* __restrict__ lab, int64_t pitch, int S, int Kc, int Ka,
+                                                  int KaP, int nch, int rows, int D, const uint32_t* __restrict__ T,
+                                                  const double* __restrict__ phi, const double* __restrict__ phim,
+                                                  const double* __restrict__ sphi, const uint32_t* __restrict__ n,
+                                                  const int32_t* __restrict__ c, int64_t i0, int64_t i1,
+                                                  int32_t* __restrict__ newc) {
+    extern __shared__ uint4 ps_lds4[];
+    const int tid = threadIdx.x, r = tid / nch, ch = tid - r * nch;
+    const int64_t i = i0 + (int64_t)blockIdx.x * rows + r;
+    const bool live = r < rows && i < i1;
+    const int cells = Kc * KaP;
+    const int a0 = live ? c[i] : 0;
+    const int j0 = a0 - ch * kPsChunk;  // the own slot's place in this thread's run, if it is in it
+    const bool owner = live && j0 >= 0 && j0 < kPsChunk;
+    uint64_t acc[kPsChunk];
+    double accd[kPsChunk];
+#pragma unroll
+    for (int j = 0; j < kPsChunk; ++j) { acc[j] = 0; accd[j] = 0.0; }
+    for (int t0 = 0; t0 < S; t0 += D) {
+        const int nD = S - t0 < D ? S - t0 : D;
+        __syncthreads();  // the block before has been read
+        if (VI) {
+            const double2* __restrict__ src = reinterpret_cast<const double2*>(phi + (size_t)t0 * cells);
+            double2* const dst = reinterpret_cast<double2*>(ps_lds4);
+            for (int k = tid; k < nD * cells / 2; k += kPtThreads) dst[k] = src[k];
+        } else {
+            const uint4* __restrict__ src = reinterpret_cast<const uint4*>(T + (size_t)t0 * cells);
+            for (int k = tid; k < nD * cells / 4; k += kPtThreads) ps_lds4[k] = src[k];
+        }
+        __syncthreads();
+        if (!live) continue;
+        if (VI) {
+            const double* const tab = reinterpret_cast<const double*>(ps_lds4);
+#pragma unroll 2
+            for (int tt = 0; tt < nD; ++tt) {
+                const uint32_t b = lab[(size_t)(t0 + tt) * pitch + i];
+                const int at = (tt * Kc + (int)b) * KaP + ch * kPsChunk;
+                const double2* const p = reinterpret_cast<const double2*>(tab + at);
+                double v[kPsChunk];
+#pragma unroll
+                for (int q = 0; q < kPsChunk / 2; ++q) { const double2 x = p[q]; v[2 * q] = x.x; v[2 * q + 1] = x.y; }
+                if (owner) {
+                    const double pm = phim[(size_t)(t0 + tt) * cells + ((int)b * KaP + a0)];
+#pragma unroll
+                    for (int j = 0; j < kPsChunk; ++j) v[j] = j == j0 ? pm : v[j];
+                }
+#pragma unroll
+                for (int j = 0; j < kPsChunk; ++j) accd[j] += v[j];
+            }
+        } else {
+            const uint32_t* const tab = reinterpret_cast<const uint32_t*>(ps_lds4);
+            uint32_t a32[kPsChunk];
+#pragma unroll
+            for (int j = 0; j < kPsChunk; ++j) a32[j] = 0;
+#pragma unroll 4
+            for (int tt = 0; tt < nD; ++tt) {
+                const uint32_t b = lab[(size_t)(t0 + tt) * pitch + i];
+                const uint4* const p = reinterpret_cast<const uint4*>(tab + (tt * Kc + (int)b) * KaP + ch * kPsChunk);
+                const uint4 x = p[0], y = p[1];
+                a32[0] += x.x; a32[1] += x.y; a32[2] += x.z; a32[3] += x.w;
+                a32[4] += y.x; a32[5] += y.y; a32[6] += y.z; a32[7] += y.w;
+            }
+#pragma unroll
+            for (int j = 0; j < kPsChunk; ++j) acc[j] += a32[j];
+        }
+    }
+    __syncthreads();  // the last block has been read: the LDS now carries the scores
+    if (VI) {
+        double* const g = reinterpret_cast<double*>(ps_lds4);
+        if (live) {
+#pragma unroll
+            for (int j = 0; j < kPsChunk; ++j) {
+                const int a = ch * kPsChunk + j;
+                const double pm = sphi[(a == a0 ? KaP : 0) + a];  // phi(m_a)
+                g[tid * kPsChunk + j] = (double)S * pm - 2.0 * accd[j];
+            }
+        }
+    } else {
+        int64_t* const g = reinterpret_cast<int64_t*>(ps_lds4);
+        if (live) {
+#pragma unroll
+            for (int j = 0; j < kPsChunk; ++j) {
+                const int a = ch * kPsChunk + j;
+                const int64_t own = a == a0 ? 1 : 0;
+                g[tid * kPsChunk + j] = (int64_t)S * ((int64_t)n[a] - own) - 2 * ((int64_t)acc[j] - (int64_t)S * own);
+            }
+        }
+    }
+    __syncthreads();
+    if (live && ch == 0) {
+        int best = a0;
+        if (VI) {
+            const double* const g = reinterpret_cast<const double*>(ps_lds4) + (size_t)tid * kPsChunk;
+            for (int a = 0; a < Ka; ++a) if (g[a] < g[best]) best = a;
+        } else {
+            const int64_t* const g = reinterpret_cast<const int64_t*>(ps_lds4) + (size_t)tid * kPsChunk;
+            for (int a = 0; a < Ka; ++a) if (g[a] < g[best]) best = a;
+        }
+        newc[i] = best;
+    }
+}
+
+// The moves of the rows [i0, i1): thread x of workgroup (x, y) holds a row and the draws [y len, y len + len); a moved
+// row takes itself out of its old cell of each of those draws' tables and into the new one (integer adds: exact in
+// any order), and in the workgroups of y = 0 it moves between the two sizes and is counted.  c is only read: the
+// caller copies newc over it behind this launch.
+__global__ __launch_bounds__(256) void k_ps_apply(const uint8_t* __restrict__ lab, int64_t pitch, int S, int Kc, int KaP,
+                                                  int len, uint32_t* __restrict__ T, uint32_t* __restrict__ n,
+                                                  const int32_t* __restrict__ c, const int32_t* __restrict__ newc,
+                                                  int64_t i0, int64_t i1, unsigned long long* __restrict__ moved) {
+    const int64_t i = i0 + (int64_t)blockIdx.x * kPtThreads + threadIdx.x;
+    if (i >= i1) return;
+    const int a0 = c[i], a1 = newc[i];
+    if (a0 == a1) return;
+    const size_t cells = (size_t)Kc * KaP;
+    const int t0 = blockIdx.y * len, t1 = t0 + len < S ? t0 + len : S;
+    for (int t = t0; t < t1; ++t) {
+        uint32_t* const rowb = T + (size_t)t * cells + (size_t)lab[(size_t)t * pitch + i] * KaP;
+        atomicSub(rowb + a0, 1u);
+        atomicAdd(rowb + a1, 1u);
+    }
+    if (blockIdx.y == 0) {
+        atomicSub(n + a0, 1u);
+        atomicAdd(n + a1, 1u);
+        atomicAdd(moved, 1ull);
+    }
+}
+
+// The totals of the state, draw t per workgroup: A = sum_a n_a^2 and F = sum_a f(n_a) of the candidate, the same of the
+// draw's own sizes n_t,b = sum_a T[b][a], Q = sum_ab T^2 and G = sum_ab f(T) -- cell k = a * Kc + b in partial
+// k mod 256, ascending, then the tree, as k_pt_pairs adds them.  d2[t] = 2 B(c, z_t), exact; w[t] = F_c + F_t - 2 G,
+// N times the VI distance, and exactly 0 where d2 is 0, as k_pt_loss has it.
+template <bool VI>
+__global__ __launch_bounds__(256) void k_ps_total(const uint32_t* __restrict__ T, const uint32_t* __restrict__ n, int Kc,
+                                                  int Ka, int KaP, uint64_t* __restrict__ d2, double* __restrict__ w) {
+    __shared__ uint64_t su[kPtThreads];
+    __shared__ double sd[kPtThreads];
+    const int tid = threadIdx.x, t = blockIdx.x;
+    const uint32_t* __restrict__ Tt = T + (size_t)t * Kc * KaP;
+    uint64_t ac = 0, at = 0, q = 0;
+    double fc = 0.0, ft = 0.0, g = 0.0;
+    for (int a = tid; a < Ka; a += kPtThreads) {
+        const uint32_t v = n[a];
+        ac += (uint64_t)v * v;
+        if (VI) fc += pt_f(v);
+    }
+    for (int b = tid; b < Kc; b += kPtThreads) {
+        uint32_t v = 0;
+        for (int a = 0; a < Ka; ++a) v += Tt[b * KaP + a];
+        at += (uint64_t)v * v;
+        if (VI) ft += pt_f(v);
+    }
+    for (int k = tid; k < Ka * Kc; k += kPtThreads) {
+        const int a = k / Kc, b = k - a * Kc;
+        const uint32_t v = Tt[b * KaP + a];
+        q += (uint64_t)v * v;
+        if (VI) g += pt_f(v);
+    }
+    ac = pt_block_sum(ac, su);
+    at = pt_block_sum(at, su);
+    q = pt_block_sum(q, su);
+    if (VI) {
+        fc = pt_block_sum(fc, sd);
+        ft = pt_block_sum(ft, sd);
+        g = pt_block_sum(g, sd);
+    }
+    if (tid == 0) {
+        const uint64_t d = ac + at - 2 * q;
+        d2[t] = d;
+        w[t] = (VI && d != 0) ? fc + ft - 2.0 * g : 0.0;
+    }
+}
+// binder2 = sum_t d2[t] and vi_tot = sum_t w[t] (draw t in partial t mod 256, ascending, then the tree), and the count
+// of moved rows beside them: the 24 bytes a pass reads back.  One workgroup.
+__global__ __launch_bounds__(256) void k_ps_reduce(const uint64_t* __restrict__ d2, const double* __restrict__ w, int S,
+                                                   const unsigned long long* __restrict__ moved,
+                                                   unsigned long long* __restrict__ res) {
+    __shared__ uint64_t su[kPtThreads];
+    __shared__ double sd[kPtThreads];
+    uint64_t b = 0;
+    double v = 0.0;
+    for (int t = threadIdx.x; t < S; t += kPtThreads) { b += d2[t]; v += w[t]; }
+    b = pt_block_sum(b, su);
+    v = pt_block_sum(v, sd);
+    if (threadIdx.x == 0) {
+        res[0] = b;
+        res[1] = (unsigned long long)__double_as_longlong(v);
+        res[2] = *moved;
+    }
+}
+
 // ---- split-merge moves of the DP chain (include/bmm_mcmc.h "split-merge moves") ----------
 // One move = k_sm_launch, `scans` + 1 launches of k_sm_scan, k_sm_decide, k_sm_commit, stream-ordered; the host
 // never reads anything back.  The two labels of the move are its sides 0 and 1.  One byte per row: its side (0 / 1)

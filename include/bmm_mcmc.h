@@ -531,6 +531,88 @@ typedef struct bmm_partition_out {
 } bmm_partition_out;
 int bmm_set_partition_summary(const bmm_partition_out* out);
 
+/* ---- greedy search for the clustering point estimate ----------------------------------
+ * The summary above answers with a visited state.  The search moves single rows of a candidate partition to whichever
+ * cluster lowers the posterior expected loss most, until no row wants to move (the greedy searches of Wade &
+ * Ghahramani 2018, Rastelli & Friel 2018, the sweeps of SALSO, Dahl, Johnson & Mueller 2022), on the device.
+ *   z_t (t < S)    the draws, labels in 0 .. Kc-1;
+ *   c              the candidate, labels in 0 .. Ka-1: Ka slots, of which any may be empty;
+ *   n_a            the size of slot a;  T_t[a][b] = #{i : c_i = a, z_t,i = b};  n_t,b the size of label b of draw t;
+ *   binder2(c)     = S sum_a n_a^2 + sum_t sum_b n_t,b^2 - 2 sum_t sum_ab T_t[a][b]^2 = sum_t 2 B(c, z_t), uint64, exact;
+ *   vi_tot(c)      = S sum_a f(n_a) + sum_t sum_b f(n_t,b) - 2 sum_t sum_ab f(T_t[a][b]), f(n) = n log_(n), f(0) = 0: the
+ *                  device adds it draw by draw, w_t = F_c + F_t - 2 G_t in the fixed order of the section above and
+ *                  exactly 0 where B(c, z_t) = 0, then over t (draw t in partial t mod 256, ascending, then a binary
+ *                  tree).  The expected VI is vi_tot / (S N);
+ *   score          of row i for slot a, the row taken out of the state: with a0 = c_i, own = [a = a0], m_a = n_a - own
+ *                  and U_t,a = T_t[a][z_t,i] - own,
+ *                    Binder  g_a = S m_a - 2 sum_t U_t,a                                  (int64)
+ *                    VI      g_a = S phi(m_a) - 2 sum_t phi(U_t,a),  phi(n) = f(n + 1) - f(n), phi(0) = 0, the sum over
+ *                            t ascending in binary64.
+ *                  g_a - g_a0 is the change of the total when the row moves from a0 to a.  An empty slot scores 0 by
+ *                  this very formula, and so does the row's own cluster when the row is alone in it: opening a new
+ *                  cluster is no case of its own;
+ *   move           the row goes to the slot with the smallest g; on exact ties its current slot wins, then the lowest;
+ *   pass           the rows are cut into contiguous batches [k B, (k + 1) B); every row of a batch is scored against
+ *                  the tables as they stood at the start of the batch, then the batch's moves are applied (n, T brought
+ *                  up to date with integer adds, -1 / +1 per draw and moved row).  B = 1 is the sequential greedy;
+ *   search         best = start; best_tot = total(start); B = batch
+ *                  repeat up to max_passes times:
+ *                      moved = one pass over c with batch B;  tot = total(c)
+ *                      if moved == 0: converged; stop                            (c == best here)
+ *                      if tot < best_tot: best, best_tot = c, tot               (strict)
+ *                      else: c = best; if B == min_batch: stop; B = max(min_batch, B / 2)
+ *                  total is binder2 under Binder and vi_tot under VI.  The result is never worse than the start;
+ *                  converged means that no single-row move to any of the Ka slots lowers the loss.
+ * Limits: 1 <= Kc <= BMM_PARTITION_SEARCH_MAX_K and the same for Ka (the tables of a draw live in LDS), S and N as
+ * bmm_device_partition_distances (S N^2 < 2^63). */
+#define BMM_PARTITION_SEARCH_MAX_K 64
+typedef struct bmm_partition_search_opts {
+    int64_t batch;     /* B of the first pass, >= 1 (above N: N) */
+    int64_t min_batch; /* >= 1 (above batch: batch) */
+    int max_passes;    /* >= 1 */
+    int max_clusters;  /* Ka, 1 .. BMM_PARTITION_SEARCH_MAX_K */
+} bmm_partition_search_opts;
+/* NULL options mean batch = ceil(N / 8), min_batch = ceil(N / 256), max_passes = 50, Ka = Kc. */
+typedef struct bmm_partition_search_out {
+    int32_t* z_hat;          /* N int32, 1-based: the searched partition, in the slots' numbering */
+    uint64_t* binder2;       /* its exact total sum_t 2 B(z_hat, z_t), under either criterion */
+    double* loss;            /* its expected loss: binder2 / (2 S), or vi_tot / (S N) */
+    double* start_loss;      /* the same two of the start */
+    uint64_t* start_binder2;
+    int* passes;             /* passes run, at most max_passes */
+    int64_t* pass_batch;     /* per pass, room for max_passes each: its B, */
+    int64_t* pass_moved;     /*   the rows it moved, */
+    uint64_t* pass_binder2;  /*   binder2 of the state it left (before a restore), */
+    double* pass_total;      /*   and that state's total as a double: binder2 converted, or vi_tot */
+    int* converged;          /* 1: the last pass moved no row */
+    int* n_clusters;         /* non-empty slots of z_hat */
+} bmm_partition_search_out;
+/* z as bmm_device_partition_distances takes it.  start: N int32 in 1 .. Ka, or NULL: the draws' minimiser of the
+ * criterion at stride 1 (then Ka >= Kc).  BMM_E_ARG before a device is touched: the limits above, a start label outside
+ * 1 .. Ka (the observation is named), batch, min_batch or max_passes below 1, a null z or out or a null buffer in out. */
+int bmm_device_partition_search(int device, const int32_t* z, int S, int64_t N, int Kc, int criterion,
+                                const int32_t* start, const bmm_partition_search_opts* opts,
+                                const bmm_partition_search_out* out);
+/* Which form of the k_ps_* kernels a shape runs, as pure bookkeeping -- no device is touched, and the values come from
+ * the function the launches themselves call.  out:
+ *   [0] bytes per label of the draws (1)          [1] cells from one label's run of slots to the next, KaP
+ *   [2] threads per row, ceil(Ka / 8)             [3] rows per workgroup of k_ps_score
+ *   [4] draws per LDS block, D                    [5] blocks of draws, ceil(S / D)
+ *   [6] what bounds D: 0 S, 1 the LDS budget, 2 the 32-bit sums of a block (D N < 2^32)
+ *   [7] bytes of dynamic LDS of k_ps_score        [8] workgroups of one k_ps_score launch, ceil(batch / [3])
+ *   [9] batches of a pass, ceil(N / batch)        [10] 1: VI (binary64 tables and sums), 0: Binder (uint32, 32-bit sums
+ *   within a block, 64-bit across)                [11] bytes of tables in global memory.
+ * BMM_E_ARG as bmm_device_partition_search. */
+int bmm_partition_search_plan(int S, int64_t N, int Kc, int Ka, int criterion, int64_t batch, int64_t out[12]);
+/* For a run: armed per calling thread for the NEXT single-chain *_run* call, as bmm_set_partition_summary, and
+ * disarmed when that call returns; out = NULL disarms, opts = NULL means the defaults.  Needs the partition summary
+ * armed (its z_best may be NULL): the search takes the summary's criterion and starts from the row it chose, device to
+ * device, after the summary and before the trace leaves, over the rows the summary used (n_used; with none usable
+ * nothing is searched and out is left as it was).  BMM_E_ARG, before a device is touched, when no partition summary is
+ * armed, the run's K is above BMM_PARTITION_SEARCH_MAX_K or max_clusters is below it.  Not armed: no allocation, no
+ * launch.  The structs are copied; the buffers must stay valid through the call.  bmm_partition_out is not touched. */
+int bmm_set_partition_search(const bmm_partition_search_opts* opts, const bmm_partition_search_out* out);
+
 /* ---- leave-one-out predictive of the fitted rows: LPML, WAIC ---------------------------
  * For the state s after a kept sweep and a fitted row i with label z_i, ell[s, i] is the log density of x_i given
  * everything else in the state:
