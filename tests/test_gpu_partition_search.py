@@ -5,7 +5,9 @@ converged -- equal the NumPy restatement tests/partition_search_ref.py with ==, 
 total equals what the existing distance kernels give for the result.  VI: near-ties may be decided differently from a
 NumPy sum, so it is held by what must be true -- the reported loss is the expected VI of the result by the existing
 device distances, it is no worse than the start, a converged result passes the brute-force check, and two calls give
-the same bits.  Through a run: the armed search equals the stand-alone call and leaves everything else as it was."""
+the same bits; decision by decision it is held to a restatement in tests/test_gpu_partition_search_vi.py, on cases
+whose gaps exclude every near-tie.  Through a run: the armed search equals the stand-alone call and leaves everything
+else as it was."""
 import functools
 
 import numpy as np

@@ -3,6 +3,8 @@ be checked without a GPU.  The restatement tests/partition_search_ref.py against
 scores against differences of full totals, passes that never raise the total, converged results against a brute
 force), and the library's plan and refusals, which touch no device."""
 import ctypes as C
+import functools
+import hashlib
 import math
 
 import numpy as np
@@ -255,3 +257,176 @@ def test_arming_needs_a_partition_summary():
                                    C.c_int(1), C.c_int64(0), C.c_uint64(1), C.c_int(0), _capi.vp(z), _capi.vp(th),
                                    _capi.vp(al), None)
     assert rc == 1 and "needs an armed partition summary" in L.bmm_last_error().decode()
+
+
+# ---- the VI search held to a restatement, decision by decision: the reference side (no device) --------------------
+# make_trace(Kc, N, S, EPS, 100 + Kc) of CASES before the decay= keyword: sha256 of z (column-major) + truth
+TRACE_DIGESTS = [
+    "64ed86b909d6d0502b64b28db0ea1272ffb358e20e9b1d88b63ccb07fa900cf5",
+    "0626b0fd2a02d8b8669a58368385f587a54a13b0156682565ad15664004ab752",
+    "115e2bf210c04ee3a742984ee23430ffc4b35e55b8d21445a3cc1a8438f700b2",
+    "076d66b2637cd2d191477b303011c77c69665853bfc90f0c104a5a79c83132b4",
+    "bdf1fbed6b8553869eb7b72ba72e642b9a13acca376125a58d1807cb892bc5a7",
+    "5a0029f025f516c1d5032b051be0ee111adc4050e12cf6cc83e63a6c24514f9f",
+    "bda6c303cf50549e3f7773357092684e200c040034fdca4bd31f714f4d894663",
+    "5a0387d469555b0ecfc3c017de5716b39c288ac2eaaa0bd312e5a212f19f026b",
+    "ed870f8b0201c53d0f2f74b3cb2ad42d401a4c0fb6410d811e119ff441dec1a6",
+    "3028173d2a63b7edc52dbd0ca0e8a6aa43c216c0a46751e7732ac56c552aebf6",
+    "f4ba450299573c7e3df50cc6a7821a3776047dbc042d97cea83872db6801e23c",
+]
+
+
+def test_the_default_decay_leaves_every_trace_byte_equal():
+    assert len(TRACE_DIGESTS) == len(ref.CASES)
+    for case, want in zip(ref.CASES, TRACE_DIGESTS):
+        z, truth = ref.make_trace(case[0], case[1], case[2], ref.EPS, 100 + case[0])
+        assert z.dtype == np.int32 and truth.dtype == np.int32 and z.flags.f_contiguous
+        assert hashlib.sha256(z.tobytes(order="F") + truth.tobytes()).hexdigest() == want, ref.case_id(case)
+    a = ref.make_trace(5, 100, 3, ref.EPS, 7)
+    b = ref.make_trace(5, 100, 3, ref.EPS, 7, decay=0.7)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    flat = ref.make_trace(5, 4000, 1, 0.0, 7, decay=1.0)[1]
+    assert np.bincount(flat)[1:].min() > 700  # decay = 1: a flat truth
+
+
+@functools.lru_cache(maxsize=None)
+def _vi_ref(case):
+    return ref.vi_reference(case)
+
+
+@functools.lru_cache(maxsize=None)
+def _vi_first_pass(case):
+    return ref.vi_reference(case, batch=case[1], min_batch=case[1], max_passes=1)
+
+
+def test_vi_case_list_is_well_formed():
+    assert len(set(ref.VI_CASES)) == len(ref.VI_CASES) <= 16 and max(c[1] for c in ref.VI_CASES) <= 4100
+    assert len({ref.vi_case_id(c) for c in ref.VI_CASES}) == len(ref.VI_CASES)
+    assert set(ref.VI_MAX_PASSES) <= set(ref.VI_CASES) and set(ref.VI_FIRST_PASS) <= set(ref.VI_CASES)
+    for case in ref.VI_CASES:
+        Kc, N, S, batch, min_batch, start, Ka, decay, seed = case
+        z = ref.vi_trace(case)
+        st = ref.vi_start(case, z)
+        assert z.shape == (S, N) and z.min() >= 1 and z.max() <= Kc
+        assert st.shape == (N,) and st.dtype == np.int32 and st.min() >= 1 and st.max() <= Ka
+        if start == "rand":
+            assert np.array_equal(st, np.random.default_rng(seed + 50).integers(1, Ka + 1, N))
+
+
+@pytest.mark.parametrize("case", [c for c in ref.VI_CASES if c[1] <= 600], ids=ref.vi_case_id)
+def test_the_margin_restatement_follows_the_search(case):
+    """the vectorised np.longdouble search against the row-by-row binary64 one: the same course, the totals within
+    the project's bound for a VI total"""
+    Kc, N, S, batch, min_batch, _, Ka, _, _ = case
+    z, start, got = _vi_ref(case)
+    want = ref.search(z, Kc, "vi", start, batch, min_batch, ref.VI_MAX_PASSES.get(case, 50), Ka)
+    for k in ("passes", "batch", "moved", "converged", "n_clusters", "binder2", "start_binder2"):
+        assert got[k] == want[k], k
+    assert np.array_equal(got["z"], want["z"]) and got["z"].dtype == np.int32
+    bound = pr.vi_bound(max(Kc, Ka), N) * S * N
+    assert len(got["pass_total"]) == len(want["pass_total"])
+    for a, b in zip(got["pass_total"] + [got["total"], got["start_total"]], want["pass_total"] + [want["total"], want["start_total"]]):
+        assert abs(a - b) <= bound
+    assert got["loss"] == got["total"] / (S * N) and got["start_loss"] == got["start_total"] / (S * N)
+
+
+def test_structural_ties_are_left_out_and_nothing_else():
+    """Ka = 6 slots, three of them empty, and row 0, which no draw puts with any other row, alone in slot 3: it stays,
+    the three empty slots score 0 from the same cells as its own and are no margin.  An exact tie between two slots
+    whose cells differ in their order is none of them"""
+    z = np.asfortranarray(np.array([[2, 1, 1, 1, 1, 1, 1]] * 3, dtype=np.int32))
+    c = np.array([3, 1, 1, 2, 2, 1, 2], dtype=np.int32)
+    res = ref.search_vi_margins(z, 2, c, 7, 7, max_passes=1, Ka=6, keep_scores=True)
+    G = res["first_scores"]
+    assert G.dtype == np.longdouble and G.shape == (7, 6)
+    assert np.all(G[:, 3:] == 0) and G[0, 2] == 0
+    assert res["first_choice"][0] == 3 and G[0, :2].min() > 0
+    assert res["structural_ties"] == 3 and res["score_margin"] > 0 and np.isfinite(res["score_margin"])
+    st = ref.State(z, c, 2, 6)
+    for i in range(7):
+        g = st.scores(i, "vi")
+        assert np.allclose(np.asarray(G[i], dtype=float), g, rtol=0, atol=1e-12)
+        assert res["first_choice"][i] == ref.State.choose(g, st.c[i]) + 1
+    # rows 0, 1 in slot 0, rows 2, 3 in slot 1, row 4 alone: the draws put 2 then 1 rows of slot 0 beside row 4 and 1
+    # then 2 of slot 1 -- the same cells in another order, equal to the last bit in a sum of two yet no structural
+    # tie, so the margin is 0 and such a case is refused
+    z = np.asfortranarray(np.array([[1, 1, 1, 2, 1], [1, 2, 1, 1, 1]], dtype=np.int32))
+    res = ref.search_vi_margins(z, 2, np.array([1, 1, 2, 2, 3], dtype=np.int32), 5, 5, max_passes=1, Ka=3, keep_scores=True)
+    assert res["first_scores"][4, 0] == res["first_scores"][4, 1] < 0 and res["first_choice"][4] == 1
+    assert res["score_margin"] == 0
+    assert not ref.margins_hold(res, 2, 3, 5, 2)
+
+
+@pytest.mark.parametrize("case", ref.VI_CASES, ids=ref.vi_case_id)
+def test_vi_cases_meet_the_margin_condition(case):
+    """No decision of the reference's course is within 2^10 x 2 error bounds of another: E_g for two scores,
+    vi_bound S N for two totals -- so the device must follow it with ==.  A case that fails is replaced."""
+    Kc, N, S, _, _, _, Ka, _, _ = case
+    runs = [("search", _vi_ref(case)[2])]
+    if case in ref.VI_FIRST_PASS:
+        runs.append(("first pass", _vi_first_pass(case)[2]))
+    for name, res in runs:
+        print("%s %s: score_margin %.3g (E_g %.3g), total_margin %.3g (bound %.3g), %d structural ties; passes %d, batches %s, moved %s, %s"
+              % (ref.vi_case_id(case), name, res["score_margin"], ref.score_error_bound(N, S), res["total_margin"],
+                 pr.vi_bound(max(Kc, Ka), N) * S * N, res["structural_ties"], res["passes"], res["batch"], res["moved"], res["stopped"]))
+        assert res["score_margin"] >= 2 ** 10 * 2 * ref.score_error_bound(N, S)
+        assert res["total_margin"] >= 2 ** 10 * 2 * pr.vi_bound(max(Kc, Ka), N) * S * N
+        assert ref.margins_hold(res, Kc, Ka, N, S)
+    if case in ref.VI_FIRST_PASS:
+        fp = _vi_first_pass(case)[2]
+        assert fp["moved"][0] > 0 and fp["pass_total"][0] < fp["start_total"]  # the first pass improves: z is its choices
+        assert np.array_equal(fp["z"], ref.vi_reference(case, batch=case[1], min_batch=case[1], max_passes=1, keep_scores=True)[2]["first_choice"])
+
+
+def test_vi_cases_reach_every_path_of_the_vi_kernels():
+    """from the library's plan and the reference's log: what k_ps_phi, k_ps_score<VI> and the host's keep-best can do
+    differently, each reached by a case"""
+    tpr, bound, last, stopped = set(), set(), [], set()
+    seen = dict.fromkeys(("one_draw_blocks", "out_of_high", "into_high", "opened", "fewer_slots", "batches", "ragged",
+                          "halved", "ties"), False)
+    for case in ref.VI_CASES:
+        Kc, N, S, batch, min_batch, start, Ka, _, _ = case
+        res = _vi_ref(case)[2]
+        p = bm.partition_search_plan(S, N, Kc, max_clusters=Ka, criterion="vi", batch=batch)
+        assert p["vi"] == 1 and p["draws_per_block"] * 8 * Kc * p["slot_stride"] <= 48 << 10
+        D = p["draws_per_block"]
+        tpr.add(p["threads_per_row"])
+        bound.add(p["block_bound"])
+        last.append((D, S - (p["draw_blocks"] - 1) * D, res["score_margin"]))
+        stopped.add(res["stopped"])
+        seen["one_draw_blocks"] |= D == 1 and S > 1
+        seen["out_of_high"] |= res["from_high"] > 0 and p["threads_per_row"] > 1
+        seen["into_high"] |= res["into_high"] > 0 and p["threads_per_row"] > 1
+        seen["opened"] |= Ka > Kc and res["opened_empty"] > 0
+        seen["fewer_slots"] |= Ka < Kc and sum(res["moved"]) > 0
+        seen["batches"] |= p["batches"] > 1 and res["moved"][0] > 0  # the phi tables refreshed inside a pass
+        seen["ragged"] |= p["workgroups"] > 1 and min(batch, N) % p["rows_per_workgroup"] != 0
+        seen["halved"] |= any(b < a for a, b in zip(res["batch"], res["batch"][1:]))  # no improvement, restore, halve
+        seen["ties"] |= res["structural_ties"] > 0
+    assert tpr == {1, 2, 3, 5, 8}
+    assert bound == {0, 1}
+    # the draw loop is unrolled by two: a last block with an odd number of draws, in one that is shorter than the
+    # others (S % D != 0) and in a single block; the 48 KiB budget leaves one draw a block at Kc = Ka = 64
+    # ... each in a case that decides some row by less than 2 phi(1), the least that one cell of one draw adds to a
+    # score: where every gap is far above that, a draw left out changes nothing
+    small = 2 * ref.phi(1)
+    assert any(D >= 2 and n < D and n % 2 == 1 and g < small for D, n, g in last)
+    assert any(D >= 2 and n < D and n % 2 == 0 for D, n, g in last)
+    assert any(D >= 2 and n == D and n % 2 == 1 and g < small for D, n, g in last)
+    assert stopped == {"converged", "min_batch", "max_passes"}
+    assert all(seen.values()), seen
+    assert bm.partition_search_plan(11, 2053, 64, criterion="vi")["draws_per_block"] == 1
+
+
+@pytest.mark.parametrize("case", [c for c in ref.VI_CASES if c[1] <= 300], ids=ref.vi_case_id)
+def test_converged_vi_cases_pass_the_brute_force(case):
+    """what the device test asks of a converged result, asked of the reference's own"""
+    Kc, N, S, _, _, _, Ka, _, _ = case
+    z, _, res = _vi_ref(case)
+    if case not in ref.VI_MAX_PASSES:
+        assert res["converged"]
+    if res["converged"]:
+        st = ref.State(z, res["z"], Kc, Ka)
+        for i in range(N):
+            for a in range(Ka):
+                assert st.move_delta_vi(i, a) / (S * N) >= -pr.vi_bound(max(Kc, Ka), N), (i, a)
