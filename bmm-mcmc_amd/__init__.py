@@ -176,9 +176,19 @@ class _Predict:
     """Inputs and outputs of a bmm_*_run_predict call: the new rows, lppd (M,), optionally the (S, M) trace of
     log p(x_m | state s) and the (M, Kc) mean responsibilities (include/bmm_mcmc.h)."""
 
-    def __init__(self, newdata, P, S, Kc, trace, responsibilities, chains):
+    def __init__(self, newdata, P, S, Kc, trace, responsibilities, chains, newdata_missing=None, burnin=0):
         if int(chains) > 1:
             raise NotImplementedError("newdata= is offered per chain (chains=1)")
+        self.cells = None
+        self.n_folded = S if int(burnin) > 0 else max(S - 1, 0)  # (row 0 of a run without burn-in is the start, not a sweep)
+        if newdata_missing is not None:  # incomplete new rows (DESIGN.md section 28): the cells, and the matrix without them
+            try:
+                rows, cols, newdata = _capi.missing_cells(newdata, newdata_missing)
+            except ValueError as e:
+                raise ValueError(str(e).replace("missing must", "newdata_missing must").replace("N x P", "M x P")) from None
+            if rows.size:  # (a set without missing cells takes the complete-row kernels: byte-equal results)
+                self.cells = (rows, cols)
+                self.cell_mean = _np.full(rows.size, _np.nan)
         self.X = _capi.as_x(newdata)
         if self.X.shape[1] != P:
             raise ValueError("newdata must have the %d columns of data" % P)
@@ -189,13 +199,35 @@ class _Predict:
         self.s = _PredictOut(self.lppd.ctypes.data, self.logdens.ctypes.data if trace else None,
                              self.resp.ctypes.data if responsibilities else None, None, None)
 
+    def arm(self):
+        if self.cells is not None:
+            rows, cols = self.cells
+            _capi.check(_capi.lib().bmm_set_newdata_missing(_capi.vp(rows), _capi.vp(cols), _C.c_int64(rows.size), _capi.vp(self.cell_mean)))
+
     def result(self):
         out = {"lppd": self.lppd}
         if self.logdens is not None:
             out["logdens"] = self.logdens
         if self.resp is not None:
             out["resp"] = self.resp
+        if self.cells is not None:
+            rows, cols = self.cells
+            out["cells"] = {"rows": rows, "cols": cols, "n_cells": int(rows.size), "mean": self.cell_mean, "n_folded": self.n_folded}
         return out
+
+
+class _PredictNaPlanOut(_C.Structure):  # bmm_predict_na_plan_out
+    _fields_ = [("form", _C.c_int), ("threads", _C.c_int), ("lds_bytes", _C.c_int64), ("table_bytes", _C.c_int64)]
+
+
+def predict_na_plan(sampler, K, P):
+    """Which form of the masked scorer of incomplete new rows a shape takes, without a device (bmm_predict_na_plan,
+    DESIGN.md section 28): {"form": "lds" | "global", "lds_bytes", "threads", "table_bytes"}.  K: the labels (maxK for
+    gibbs_dp and gibbs_stickbreaking)."""
+    o = _PredictNaPlanOut()
+    _capi.check(_capi.lib().bmm_predict_na_plan(_C.c_int(_capi.SAMPLER_CODE[sampler]), _C.c_int(int(K)), _C.c_int(int(P)), _C.byref(o)))
+    return {"form": "lds" if o.form == 0 else "global", "lds_bytes": int(o.lds_bytes), "threads": int(o.threads),
+            "table_bytes": int(o.table_bytes)}
 
 
 def _with_predictive(out, pr, pt=None, lo=None):
@@ -1598,6 +1630,7 @@ def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=
         if rel is not None:
             return getattr(L, "bmm_%s_run_relabel" % base)(*args, rel.ref())
         return getattr(L, "bmm_%s_run_probs" % base)(*args, hooks.ref() if hooks else None)
+    pr.arm()
     pr.s.relabel = _C.addressof(rel.s) if rel is not None else None
     pr.s.hooks = _C.addressof(hooks.hooks) if hooks is not None else None
     return getattr(L, "bmm_%s_run_predict" % base)(*args, _capi.vp(pr.X), _C.c_int64(pr.M), _C.byref(pr.s))
@@ -1752,7 +1785,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                     select_features=False, rho=0.5, init="random", init_iters=INIT_ITERS, ecr_pivot="iterative",
                     ecr_max_iter=50, logpost=False, temper=None, swap_every=1, temper_hottest=0.1, pair_check=None,
                     pair_check_stride=1, pair_check_trace=False, missing=None, known=None, allowed=None, summary=None,
-                    summary_pivot="first", summary_stride=1, keep_trace=True, partition_search=None):
+                    summary_pivot="first", summary_stride=1, keep_trace=True, partition_search=None, newdata_missing=None):
     """Collapsed Gibbs sampler, finite K (R/utils.R:37-47 -> src/collapsed_gibbs.cpp:24).
 
     Extra keyword-only arguments: `seed` (Philox key; default drawn from the global NumPy
@@ -1767,7 +1800,15 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     burn-in its first row, the starting state, is NaN), `responsibilities=True` adds "resp", the (M, K) mean
     normalised category weights -- in the sampler's label order of each sweep, so they mean something only for a
     chain that does not switch labels (relabel=True does not reorder them).  The predictive itself does not
-    depend on the labels.  `partition="binder"` or `"vi"`: the result gains `partition = {"criterion", "loss", "binder2",
+    depend on the labels.  `newdata_missing=`: None (an NA cell in newdata is an error), "na" (the NA_INTEGER / NaN cells
+    of newdata) or a boolean M x P mask: incomplete new rows (include/bmm_mcmc.h "incomplete new rows", DESIGN.md section
+    28).  A new row is not in the fit, so its missing cells marginalise out exactly: "lppd" and "logdens" are the density
+    of the row's observed cells, and "resp" comes from the observed cells alone.  `predictive` gains `cells = {"rows",
+    "cols", "n_cells", "mean", "n_folded"}` (cells sorted by (row, column), 0-based): "mean" is P(x_d = 1 | the row's
+    observed cells, the fitted data), the ratio sum_s p(x_O, x_d = 1 | s) / sum_s p(x_O | s) over the kept sweeps -- the
+    states weighted by the density of the row's observed cells, NOT the plain mean over the sweeps of the per-state
+    probability (the chain samples its states given the fitted data, not given the new row).  A set without a missing
+    cell gives exactly what it gives without the keyword.  `partition="binder"` or `"vi"`: the result gains `partition = {"criterion", "loss", "binder2",
     "best", "z", "n_used"}` -- the kept sweep that minimises the posterior expected Binder or variation-of-information
     loss over the kept sweeps (candidates every `partition_stride`-th), computed on the device from the resident trace;
     `best` is its row of `z` (of `z_original` under stephens="device": the summary is on the labels as sampled and does
@@ -1841,7 +1882,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     sweep and the sweeps folded.  The `theta` row of a sweep belongs to that sweep's labels and the cells as they stood
     before its imputation step; `logpost=` gives the joint of the completed state.  With many cells missing the chain
     mixes more slowly than one that integrates them out: run longer.  Works with partition=, relabel="ecr", newdata=
-    (complete rows) and logpost=; not with chains > 1, loo=, select_features=, temper=, pair_check=, init="kmodes",
+    (complete rows, or incomplete ones with newdata_missing=: those cells are integrated out, not imputed) and logpost=; not with chains > 1, loo=, select_features=, temper=, pair_check=, init="kmodes",
     relabel=True (or split_merge= on gibbs_dp).
     `known=`: N integers, the rows' known classes -- 0, a negative value or NaN marks a free row, any other value is the
     row's 1-based label, which it holds in every sweep.  `allowed=`: an N x K boolean array, the labels each row may take
@@ -1891,7 +1932,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     seed = _seed(seed)
     chains = int(chains)
     relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
-    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
+    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains, newdata_missing, burnin)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     ps = _make_search(partition_search, partition, N, K, chains)
     fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, False, newdata, loo)
@@ -1983,10 +2024,12 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
              select_features=False, rho=0.5, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
              temper=None, swap_every=1, temper_hottest=0.1, pair_check=None, pair_check_stride=1, pair_check_trace=False,
              missing=None, known=None, allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True,
-             partition_search=None):
+             partition_search=None, newdata_missing=None):
     """Collapsed Gibbs sampler with a Dirichlet-process prior, truncated at maxK
     (R/utils.R:23-30 -> src/collapsed_gibbs_dp.cpp:27).  `newdata`, `predictive_trace`, `responsibilities`, `loo`: as
-    gibbs_collapsed; "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
+    gibbs_collapsed; `newdata_missing`: as gibbs_collapsed ("mean" is the importance-weighted ratio over the kept sweeps,
+    the states weighted by the density of the row's observed cells; "resp" comes from the observed cells, the new-cluster
+    column included); "resp" is (M, maxK + 1), the maxK labels and then the new-cluster column.  `split_merge=m`: m
     split-merge Metropolis-Hastings moves (Jain & Neal 2004, include/bmm_mcmc.h) at the start of every sweep from the
     second, each with `split_merge_scans` intermediate restricted scans (default SPLIT_MERGE_SCANS); the result gains
     `split_merge = {"split_proposed", "split_accepted", "merge_proposed", "merge_accepted", "skipped"}`.  Per chain.
@@ -2011,7 +2054,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
     relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
-    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, maxK + 1, predictive_trace, responsibilities, chains)
+    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, maxK + 1, predictive_trace, responsibilities, chains, newdata_missing, burnin)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     ps = _make_search(partition_search, partition, N, maxK, chains)
     lo = _make_loo(loo, N, nsamples - burnin, chains, False)
@@ -2084,7 +2127,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
               predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None,
               loo=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1,
               pair_check_trace=False, missing=None, known=None, allowed=None, summary=None, summary_pivot="first",
-              summary_stride=1, keep_trace=True, partition_search=None):
+              summary_stride=1, keep_trace=True, partition_search=None, newdata_missing=None):
     data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
     N, P = X.shape
@@ -2095,7 +2138,7 @@ def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, b
     seed = _seed(seed)
     chains = int(chains)
     relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
-    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains)
+    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains, newdata_missing, burnin)
     pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
     ps = _make_search(partition_search, partition, N, K, chains)
     lo = _make_loo(loo, N, nsamples - burnin, chains, True)
@@ -2181,10 +2224,13 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
                         similarity_of=None, loo=False, init="random", ecr_pivot="iterative", ecr_max_iter=50, logpost=False,
                         pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None, known=None,
                         allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True,
-                        partition_search=None):
+                        partition_search=None, newdata_missing=None):
     """Blocked Gibbs sampler, truncated stick-breaking prior (R/utils.R:95-107 ->
     src/stickbreaking.cpp:10).  The z-step is exactly parallel, so there is no batch.  `newdata`,
-    `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
+    `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `newdata_missing`: as gibbs_collapsed, from the
+    pi and theta of each kept sweep ("mean" is the importance-weighted ratio over the kept sweeps, the states weighted
+    by the density of the row's observed cells; "resp" comes from the observed cells; a row with every cell missing has
+    density sum(pi)); `loo` adds "p_waic" and "elpd_waic".  `init`:
     "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`: as gibbs_collapsed; log_prior is
     the stick-breaking prior with the sticks integrated out, which depends on the order of the labels.  `pair_check`,
     `pair_check_stride`, `pair_check_trace`: as gibbs_collapsed.  `missing`: as gibbs_collapsed; the cells are drawn from
@@ -2195,7 +2241,7 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
                      burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
                      ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed,
-                     summary, summary_pivot, summary_stride, keep_trace, partition_search)
+                     summary, summary_pivot, summary_stride, keep_trace, partition_search, newdata_missing)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
@@ -2204,9 +2250,11 @@ def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, bur
                partition=None, partition_stride=1, similarity_of=None, loo=False, init="random", ecr_pivot="iterative",
                ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1, pair_check_trace=False, missing=None,
                known=None, allowed=None, summary=None, summary_pivot="first", summary_stride=1, keep_trace=True,
-               partition_search=None):
+               partition_search=None, newdata_missing=None):
     """Full (uncollapsed) Gibbs sampler, finite K (R/utils.R:64-78 -> src/full_gibbs.cpp:32).  `newdata`,
-    `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `loo` adds "p_waic" and "elpd_waic".  `init`:
+    `predictive_trace`, `responsibilities`, `loo`: as gibbs_collapsed; `newdata_missing`: as gibbs_stickbreaking ("mean" is
+    the importance-weighted ratio over the kept sweeps, the states weighted by the density of the row's observed cells;
+    "resp" comes from the observed cells); `loo` adds "p_waic" and "elpd_waic".  `init`:
     "random" only (the sampler starts from pi and theta).  `logpost`, `ecr_pivot="map"`, `pair_check`,
     `pair_check_stride`, `pair_check_trace`, `missing`, `known`, `allowed`, `summary`, `summary_pivot`, `summary_stride`,
     `keep_trace`, `partition_search`: as gibbs_collapsed."""
@@ -2215,7 +2263,7 @@ def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, bur
                      relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
                      newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
                      ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed,
-                     summary, summary_pivot, summary_stride, keep_trace, partition_search)
+                     summary, summary_pivot, summary_stride, keep_trace, partition_search, newdata_missing)
 
 
 class Chain:
@@ -2375,28 +2423,47 @@ class Chain:
         return pi, theta
 
     # -- posterior predictive density of new rows (include/bmm_mcmc.h)
-    def set_newdata(self, Xnew, responsibilities=False):
+    def set_newdata(self, Xnew, responsibilities=False, missing=None):
         """M x P binary rows the chain has not seen, validated and packed on the device; replaces any earlier set and
         empties the accumulators (None or zero rows: drops it).  `responsibilities`: sweeps_predict also accumulates
-        the mean normalised category weights (Kc more doubles per row and sweep)."""
+        the mean normalised category weights (Kc more doubles per row and sweep).  `missing`: None, "na" or a boolean
+        M x P mask, as newdata_missing= of the gibbs_* wrappers: the rows are incomplete, their observed cells are
+        scored and their missing cells predicted."""
         if Xnew is None:
             Xnew = _np.zeros((0, self.P), dtype=_np.int32)
+        cells = None
+        if missing is not None:
+            rows, cols, Xnew = _capi.missing_cells(Xnew, missing)
+            cells = (rows, cols) if rows.size else None
         Xn = _capi.as_x(Xnew)
         if Xn.shape[1] != self.P:
             raise ValueError("newdata must have the %d columns of data" % self.P)
         _capi.check(_capi.lib().bmm_chain_predict_responsibilities(self._h, _C.c_int(1 if responsibilities else 0)))
         _capi.check(_capi.lib().bmm_chain_set_newdata_host(self._h, _capi.vp(Xn), _C.c_int64(Xn.shape[0])))
         self._M = Xn.shape[0]
+        self._cells = None
+        if cells is not None:
+            _capi.check(_capi.lib().bmm_chain_set_newdata_missing(self._h, _capi.vp(cells[0]), _capi.vp(cells[1]), _C.c_int64(cells[0].size)))
+            self._cells = cells
 
     def _kc(self):
         return self.K + 1 if self.sampler == "dp" else self.K
 
-    def predict_state(self, responsibilities=False):
+    def predict_state(self, responsibilities=False, cells=False):
         """log p(x_m | current state) for every new row, (M,); no sweep is run and the accumulators are untouched.
         With responsibilities=True returns (logdens, resp): resp (M, Kc) are the normalised category weights (DP:
-        the maxK labels, then the new-cluster column), in the sampler's label order."""
+        the maxK labels, then the new-cluster column), in the sampler's label order.  Incomplete new rows
+        (set_newdata(missing=)): the density and the weights of the observed cells; cells=True appends the per-state
+        P(x_d = 1 | the row's observed cells, this state) of every missing cell, in the order of the sorted cell list."""
         ld = _np.zeros(self._M)
         rp = _np.zeros((self._M, self._kc()), order="F") if responsibilities else None
+        if cells:
+            if getattr(self, "_cells", None) is None:
+                raise ValueError("cells=True needs new rows with missing cells (set_newdata(missing=))")
+            cl = _np.zeros(self._cells[0].size)
+            _capi.check(_capi.lib().bmm_chain_predict_state_cells(self._h, _capi.vp(ld), _capi.vp(rp) if responsibilities else None,
+                                                                  _capi.vp(cl)))
+            return (ld, rp, cl) if responsibilities else (ld, cl)
         _capi.check(_capi.lib().bmm_chain_predict_state(self._h, _capi.vp(ld), _capi.vp(rp) if responsibilities else None))
         return (ld, rp) if responsibilities else ld
 
@@ -2419,7 +2486,23 @@ class Chain:
         out = {"lppd": lp, "n": n.value}
         if responsibilities:
             out["resp"] = rp
+        if getattr(self, "_cells", None) is not None:
+            rows, cols = self._cells
+            mean = _np.zeros(rows.size)
+            nf = _C.c_int(0)
+            _capi.check(_capi.lib().bmm_chain_get_predictive_cells(self._h, _capi.vp(mean), _C.byref(nf)))
+            out["cells"] = {"rows": rows, "cols": cols, "n_cells": int(rows.size), "mean": mean, "n_folded": nf.value}
         return out
+
+    def set_newdata_missing(self, rows, cols):
+        """the missing cells of the new rows as a sorted 0-based (row, column) list (bmm_chain_set_newdata_missing); an
+        empty list drops the mask.  set_newdata(missing=) calls this."""
+        rows = _np.ascontiguousarray(rows, dtype=_np.int64)
+        cols = _np.ascontiguousarray(cols, dtype=_np.int32)
+        if rows.shape != cols.shape or rows.ndim != 1:
+            raise ValueError("rows and cols must be vectors of one length")
+        _capi.check(_capi.lib().bmm_chain_set_newdata_missing(self._h, _capi.vp(rows), _capi.vp(cols), _C.c_int64(rows.size)))
+        self._cells = (rows, cols) if rows.size else None
 
     def predict_reset(self):
         _capi.check(_capi.lib().bmm_chain_predict_reset(self._h))

@@ -31,6 +31,8 @@ SYMBOLS = [
     "bmm_chain_set_newdata_host", "bmm_chain_predict_responsibilities", "bmm_chain_predict_state",
     "bmm_chain_sweeps_predict", "bmm_chain_get_predictive", "bmm_chain_predict_reset",
     "bmm_collapsed_run_predict", "bmm_dp_run_predict", "bmm_sb_run_predict", "bmm_full_run_predict",
+    "bmm_chain_set_newdata_missing", "bmm_chain_predict_state_cells", "bmm_chain_get_predictive_cells",
+    "bmm_set_newdata_missing", "bmm_predict_na_plan",
     "bmm_device_partition_distances", "bmm_device_psm", "bmm_device_partition_plan", "bmm_set_partition_summary",
     "bmm_device_partition_search", "bmm_partition_search_plan", "bmm_set_partition_search",
     "bmm_chain_set_loo", "bmm_chain_loo_state", "bmm_chain_sweeps_loo", "bmm_chain_get_loo", "bmm_chain_loo_reset",
@@ -101,6 +103,12 @@ def load(path):
         L.bmm_chain_get_missing_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bmm_chain_missing_reset.argtypes = [C.c_void_p]
         L.bmm_set_missing.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    if hasattr(L, "bmm_chain_set_newdata_missing"):  # (an older build loaded for a comparison has no incomplete new rows)
+        L.bmm_chain_set_newdata_missing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        L.bmm_chain_predict_state_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bmm_chain_get_predictive_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bmm_set_newdata_missing.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.bmm_predict_na_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
     if hasattr(L, "bmm_chain_set_constraints"):  # (an older build loaded for a comparison has no constraints)
         L.bmm_chain_set_constraints.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.bmm_chain_constraint_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

@@ -465,6 +465,23 @@ score_fn lookup_score(int kt, int gw, int minus, bool loo) {
 }
 
 constexpr size_t kLdsMax = 163840;  // gfx950: 160 KiB per workgroup
+
+// The masked scorer of incomplete new rows.  Which form runs is a pure function of the shape:
+// the LDS form (k_score_na: kScoreThreads lanes, the whole split image staged) when the shape has a resident kernel and
+// the doubled head with the constants and the exp256 table fits in LDS; the global form (k_score_na_generic: 256
+// threads, tables from L2, scores in scratch columns) otherwise.  bmm_predict_na_plan reports it, the launches read it.
+typedef void (*na_score_fn)(ChainParams, NaScoreArgs);
+struct NaForm { bool lds; size_t lds_bytes; int threads; size_t table_bytes; };
+NaForm na_form_of(const ChainParams& p, bool generic) {
+    const size_t bytes = (size_t)split_layout_of(p).doubles() * sizeof(double);
+    const bool lds = !generic && bytes <= kLdsMax;
+    return NaForm{lds, lds ? bytes : 0, lds ? kScoreThreads : 256, bytes};
+}
+na_score_fn lookup_score_na(int kt, int gw) {
+    na_score_fn fn = nullptr;
+    lift([&](auto KT, auto GW) { fn = k_score_na<KT, kScoreThreads, GW>; }, kKT, kt, IntList<kGroupW, kGroupWAlt>{}, gw);
+    return fn;
+}
 // The one place a kernel is set up for launching with `lds` bytes of dynamic LDS: the attribute that allows
 // them, and how many of its workgroups of nt threads the runtime then fits on a CU.
 template <class Fn>
@@ -583,6 +600,19 @@ struct bmm_chain {
     int pred_grid_max = 0;
     size_t pred_lds = 0;
     SweepTrace pred_rec;
+    // ... of incomplete new rows: the mask planes (laid out as dXnb), the sorted cell list as
+    // rows / CSR offsets / columns, the cell pairs that live across sweeps, the split image, and the launch of the
+    // shape's form (na_form_of): pn_fn with pn_lds bytes, or k_score_na_generic on score columns (the chain's own on a
+    // generic shape, dPnScratch otherwise).  pred_cells = 0: the new rows are complete and take k_score.
+    int64_t pred_cells = 0;
+    uint32_t* dPnMb = nullptr;
+    int64_t *dPnRow = nullptr, *dPnOff = nullptr;
+    int32_t* dPnCol = nullptr;
+    double *dCellMax = nullptr, *dCellSum = nullptr, *dSplitTab = nullptr, *dPnScratch = nullptr;
+    int64_t pn_scratch_stride = 0;
+    na_score_fn pn_fn = nullptr;
+    int pn_grid_max = 0;
+    size_t pn_lds = 0;
     // leave-one-out predictive of the fitted rows: the two table sets of the counting samplers
     // (the explicit samplers score their own image dTab), the accumulators [kLooAcc][N] that live across sweeps, the
     // outputs of k_loo_finish ([kLooOut][N], then the scalars), and what a sweep folds and records (loo_rec: rows of N doubles)
@@ -815,6 +845,7 @@ struct RunOptions {
     const bmm_relabel_hooks* hooks = nullptr;  // *_run_probs
     const bmm_relabel_out* rel = nullptr;      // *_run_relabel
     const int32_t* Xnew = nullptr; int64_t M = 0; const bmm_predict_out* pred = nullptr;  // *_run_predict
+    struct { bool on = false; const int64_t* rows = nullptr; const int32_t* cols = nullptr; int64_t n = 0; double* mean = nullptr; } pna;  // bmm_set_newdata_missing
     bool predict() const { return pred && M > 0; }
 };
 thread_local RunOptions g_armed;
@@ -1360,8 +1391,41 @@ int launch_score(bmm_chain* c, ScoreArgs a, bool loo) {
     HIP_TRY(hipGetLastError());
     return BMM_OK;
 }
-int enqueue_predict(bmm_chain* c, double* logdens, double* resp, bool fold) {
+// ... of incomplete new rows: the split image of the current state, then the masked scorer in
+// the shape's form; cell (device, may be null) receives this state's P(x_d = 1 | x_O, state) per missing cell
+int launch_score_na(bmm_chain* c, double* logdens, double* resp, double* cell, bool fold) {
+    const ChainParams& p = c->p;
+    hipLaunchKernelGGL(k_split_tables, dim3(p.KT), dim3(256), 0, c->stream, p, c->dNk, c->dS, c->dDNk, c->dDS, c->dAlpha,
+                       c->dPi, c->dTheta, c->dSplitTab);
+    HIP_TRY(hipGetLastError());
+    NaScoreArgs a{};
+    a.Xb = c->dXnb; a.Mb = c->dPnMb; a.rows = c->predM; a.tab = c->dSplitTab; a.off = c->dPnOff; a.col = c->dPnCol;
+    a.out = logdens; a.resp = resp; a.cell = cell;
+    if (fold) {
+        a.run_max = c->dPredMax; a.run_sum = c->dPredSum; a.resp_acc = c->pred_resp ? c->dRespAcc : nullptr;
+        a.cell_max = c->dCellMax; a.cell_sum = c->dCellSum;
+    }
+    if (na_form_of(p, c->generic).lds) {
+        const int64_t ntiles = (a.rows + kScoreThreads - 1) / kScoreThreads;
+        hipLaunchKernelGGL(c->pn_fn, dim3((int)(ntiles < c->pn_grid_max ? ntiles : c->pn_grid_max)), dim3(kScoreThreads),
+                           c->pn_lds, c->stream, p, a);
+    } else {
+        double* const scr = c->generic ? c->dScratch : c->dPnScratch;
+        const int64_t stride = c->generic ? c->scratch_stride : c->pn_scratch_stride;
+        const int64_t nb = (a.rows + 255) / 256, maxb = stride / 256;
+        hipLaunchKernelGGL(k_score_na_generic, dim3((unsigned)(nb < maxb ? nb : maxb)), dim3(256), 0, c->stream, p, a, scr, stride);
+    }
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+int enqueue_predict(bmm_chain* c, double* logdens, double* resp, bool fold, double* cell = nullptr) {
     if (c->predM <= 0) return BMM_OK;
+    if (c->pred_cells > 0) {
+        const int rc = launch_score_na(c, logdens, resp, cell, fold);
+        if (rc) return rc;
+        if (fold) c->pred_folded++;
+        return BMM_OK;
+    }
     ScoreArgs a{};
     a.Xb = c->dXnb; a.rows = c->predM; a.out = logdens; a.resp = resp;
     if (fold) { a.run_max = c->dPredMax; a.run_sum = c->dPredSum; a.resp_acc = c->pred_resp ? c->dRespAcc : nullptr; }
@@ -2239,7 +2303,8 @@ void bmm_chain_destroy(bmm_chain* c) {
     sum_release(c);
     void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
                     c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch, c->dSmSide, c->dSmSideLaunch, c->dSmLq, c->dSmStat, c->dSmCell,
-                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dAsBlock, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock, c->dNaBlock, c->dCsBlock};
+                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dAsBlock, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock, c->dNaBlock, c->dCsBlock,
+                    c->dPnMb, c->dPnRow, c->dPnOff, c->dPnCol, c->dCellMax, c->dCellSum, c->dSplitTab, c->dPnScratch};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     chain_stream_release(c->device, c->stream, c->stream_kind);  // synchronised above
@@ -2687,7 +2752,22 @@ static int pred_reset(bmm_chain* c) {
                        c->dPredMax, c->dPredSum);
     HIP_TRY(hipGetLastError());
     if (c->dRespAcc) HIP_TRY(hipMemsetAsync(c->dRespAcc, 0, (size_t)c->predM * c->p.Kc * sizeof(double), c->stream));
+    if (c->pred_cells > 0) {  // the cell pairs of incomplete new rows
+        const int64_t cb = (c->pred_cells + 255) / 256;
+        hipLaunchKernelGGL(k_predict_reset, dim3((unsigned)(cb < 4096 ? cb : 4096)), dim3(256), 0, c->stream, c->pred_cells,
+                           c->dCellMax, c->dCellSum);
+        HIP_TRY(hipGetLastError());
+    }
     return BMM_OK;
+}
+// the mask of incomplete new rows and everything sized by it (the stream is idle)
+static void pred_na_drop(bmm_chain* c) {
+    void** bufs[] = {reinterpret_cast<void**>(&c->dPnMb), reinterpret_cast<void**>(&c->dPnRow), reinterpret_cast<void**>(&c->dPnOff),
+                     reinterpret_cast<void**>(&c->dPnCol), reinterpret_cast<void**>(&c->dCellMax), reinterpret_cast<void**>(&c->dCellSum),
+                     reinterpret_cast<void**>(&c->dPnScratch)};
+    for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    c->pred_cells = 0;
+    c->pn_scratch_stride = 0;
 }
 // n more sweeps folded through `slot` and, with `trace` (n x width, the caller's), recorded; without: enqueued, not waited for
 static int sweeps_folded(bmm_chain* c, int n, SweepTrace& slot, int64_t width, double* trace, const char* what) {
@@ -2749,6 +2829,7 @@ int bmm_chain_set_newdata_host(bmm_chain* c, const int32_t* Xnew, int64_t M) {
             void** bufs[] = {reinterpret_cast<void**>(&c->dXnb), reinterpret_cast<void**>(&c->dPredMax),
                              reinterpret_cast<void**>(&c->dPredSum), reinterpret_cast<void**>(&c->dRespAcc)};
             for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+            pred_na_drop(c);  // the mask belongs to the set that goes
             c->predM = 0;
             c->pred_folded = 0;
         };
@@ -2869,18 +2950,164 @@ int bmm_chain_predict_reset(bmm_chain* c) {
     return pred_reset(c);
 }
 
+// ---- ... of incomplete new rows ----
+static int na_check_cells(const int64_t* rows, const int32_t* cols, int64_t n, int64_t N, int P);
+// the masked scorer of the chain's shape, set up on first use
+static int pred_na_setup(bmm_chain* c) {
+    const NaForm f = na_form_of(c->p, c->generic);
+    if (!f.lds || c->pn_fn) return BMM_OK;
+    na_score_fn fn = lookup_score_na(c->p.KT, c->p.W);
+    if (!fn) return set_err(BMM_E_STATE, "no masked predictive kernel for %d accumulators", c->p.KT);
+    int per_cu = 0;
+    const hipError_t e = kernel_fits(fn, kScoreThreads, f.lds_bytes, &per_cu);
+    if (e != hipSuccess) return set_err(BMM_E_HIP, "kernel set-up failed: %s", hipGetErrorString(e));
+    c->pn_fn = fn;
+    c->pn_lds = f.lds_bytes;
+    c->pn_grid_max = (per_cu < 1 ? 1 : per_cu) * c->num_cus;
+    return BMM_OK;
+}
+
+int bmm_chain_set_newdata_missing(bmm_chain* c, const int64_t* rows, const int32_t* cols, int64_t n) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        int rc = pred_refused(c);
+        if (rc) return rc;
+        if (c->predM <= 0) return set_err(BMM_E_STATE, "no new data set (bmm_chain_set_newdata_host)");
+        rc = na_check_cells(rows, cols, n, c->predM, c->p.P);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // nothing still reads the mask that goes
+        if (n == 0) { pred_na_drop(c); return pred_reset(c); }
+        rc = pred_na_setup(c);
+        if (rc) return rc;
+        const NaForm f = na_form_of(c->p, c->generic);
+        const int64_t M = c->predM;
+        const int W = (c->p.P + 31) / 32;
+        int64_t stride = 0;
+        if (!f.lds && !c->generic) {  // a resident shape in the global form: score columns of its own
+            stride = (M + 255) / 256 * 256;
+            if (stride > generic_threads(c->p.Kc)) stride = generic_threads(c->p.Kc);
+        }
+        const size_t plane_bytes = (size_t)W * M * sizeof(uint32_t), cell_bytes = (size_t)n * sizeof(double);
+        const size_t scr_bytes = (size_t)stride * c->p.Kc * sizeof(double);
+        rc = pred_room(plane_bytes + (size_t)(M + 1 + n) * 8 + (size_t)n * 4 + 2 * cell_bytes + scr_bytes + (c->dSplitTab ? 0 : f.table_bytes),
+                       "the mask of the new rows, the cell list and the cell accumulators");
+        if (rc) return rc;
+        // the mask planes (bit d % 32 of word d / 32, as k_pack_bits lays the data out) and the CSR offsets, on the host
+        std::vector<uint32_t> mb((size_t)W * M, 0u);
+        std::vector<int64_t> off((size_t)M + 1, 0);
+        for (int64_t q = 0; q < n; ++q) {
+            mb[(size_t)(cols[q] >> 5) * M + rows[q]] |= 1u << (cols[q] & 31);
+            off[(size_t)rows[q] + 1]++;
+        }
+        for (int64_t m = 0; m < M; ++m) off[(size_t)m + 1] += off[(size_t)m];
+        DevBuf dmb, drw, dof, dcl, dmx, dsm, dsc;
+        HIP_TRY(dmb.alloc(plane_bytes));
+        HIP_TRY(drw.alloc((size_t)n * sizeof(int64_t)));
+        HIP_TRY(dof.alloc((size_t)(M + 1) * sizeof(int64_t)));
+        HIP_TRY(dcl.alloc((size_t)n * sizeof(int32_t)));
+        HIP_TRY(dmx.alloc(cell_bytes));
+        HIP_TRY(dsm.alloc(cell_bytes));
+        if (scr_bytes) HIP_TRY(dsc.alloc(scr_bytes));
+        if (!c->dSplitTab) HIP_TRY(hipMalloc(&c->dSplitTab, f.table_bytes));
+        HIP_TRY(hipMemcpy(dmb.p, mb.data(), plane_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(drw.p, rows, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dof.p, off.data(), (size_t)(M + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dcl.p, cols, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+        pred_na_drop(c);
+        c->dPnMb = dmb.as<uint32_t>(); dmb.p = nullptr;
+        c->dPnRow = drw.as<int64_t>(); drw.p = nullptr;
+        c->dPnOff = dof.as<int64_t>(); dof.p = nullptr;
+        c->dPnCol = dcl.as<int32_t>(); dcl.p = nullptr;
+        c->dCellMax = dmx.as<double>(); dmx.p = nullptr;
+        c->dCellSum = dsm.as<double>(); dsm.p = nullptr;
+        c->dPnScratch = dsc.as<double>(); dsc.p = nullptr;
+        c->pn_scratch_stride = stride;
+        c->pred_cells = n;
+        return pred_reset(c);
+    });
+}
+
+int bmm_chain_predict_state_cells(bmm_chain* c, double* logdens_out, double* resp_out, double* cell_out) {
+    return guarded([&]() -> int {
+        if (!c || !logdens_out) return set_err(BMM_E_ARG, "null argument");
+        int rc = pred_refused(c);
+        if (rc) return rc;
+        if (c->predM <= 0) return set_err(BMM_E_STATE, "no new data set (bmm_chain_set_newdata_host)");
+        if (cell_out && c->pred_cells <= 0) return set_err(BMM_E_STATE, "the new rows have no missing cell (bmm_chain_set_newdata_missing)");
+        HIP_TRY(hipSetDevice(c->device));
+        if (!c->started) { rc = chain_start(c); if (rc) return rc; }
+        const size_t M = (size_t)c->predM, Kc = (size_t)c->p.Kc, n = (size_t)c->pred_cells;
+        DevBuf ld, rp, cl;
+        HIP_TRY(ld.alloc(M * sizeof(double)));
+        if (resp_out) {
+            rc = pred_room(M * Kc * sizeof(double), "the responsibilities (M x Kc doubles)");
+            if (rc) return rc;
+            HIP_TRY(rp.alloc(M * Kc * sizeof(double)));
+        }
+        if (cell_out) HIP_TRY(cl.alloc(n * sizeof(double)));
+        rc = enqueue_predict(c, ld.as<double>(), resp_out ? rp.as<double>() : nullptr, false, cell_out ? cl.as<double>() : nullptr);
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+        hipError_t e = hipMemcpyAsync(logdens_out, ld.p, M * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && resp_out) e = hipMemcpyAsync(resp_out, rp.p, M * Kc * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && cell_out) e = hipMemcpyAsync(cell_out, cl.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);  // the scratch goes out of scope
+        if (e != hipSuccess || e2 != hipSuccess) return set_err(BMM_E_HIP, "copying the predictive failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        return BMM_OK;
+    });
+}
+
+int bmm_chain_get_predictive_cells(bmm_chain* c, double* cell_mean, int* n_folded) {
+    return guarded([&]() -> int {
+        if (!c || !cell_mean) return set_err(BMM_E_ARG, "null argument");
+        int rc = pred_refused(c);
+        if (rc) return rc;
+        if (c->predM <= 0) return set_err(BMM_E_STATE, "no new data set (bmm_chain_set_newdata_host)");
+        if (c->pred_cells <= 0) return set_err(BMM_E_STATE, "the new rows have no missing cell (bmm_chain_set_newdata_missing)");
+        if (n_folded) *n_folded = c->pred_folded;
+        if (c->pred_folded < 1) return set_err(BMM_E_STATE, "no state has been folded yet (bmm_chain_sweeps_predict)");
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t n = (size_t)c->pred_cells;
+        DevBuf cm;
+        HIP_TRY(cm.alloc(n * sizeof(double)));
+        const int64_t nb = ((int64_t)n + 255) / 256;
+        hipLaunchKernelGGL(k_predict_cells_finish, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, c->stream, c->pred_cells,
+                           c->dPnRow, c->dPredMax, c->dPredSum, c->dCellMax, c->dCellSum, cm.as<double>());
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(cell_mean, cm.p, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess || e2 != hipSuccess) return set_err(BMM_E_HIP, "reading the predictive failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        return BMM_OK;
+    });
+}
+
+int bmm_predict_na_plan(int sampler, int K, int P, bmm_predict_na_plan_out* out) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    if (sampler < 0 || sampler > 3 || K < 1 || P < 1) return set_err(BMM_E_ARG, "bmm_predict_na_plan: sampler in 0 .. 3, K >= 1, P >= 1");
+    const DebugSwitches dbg;
+    const ChainShape s = chain_shape(sampler, 1, P, K, 1, dbg);
+    const NaForm f = na_form_of(s.p, s.generic);
+    out->form = f.lds ? BMM_PREDICT_NA_LDS : BMM_PREDICT_NA_GLOBAL;
+    out->threads = f.threads;
+    out->lds_bytes = (int64_t)f.lds_bytes;
+    out->table_bytes = (int64_t)f.table_bytes;
+    return BMM_OK;
+}
+
 // ... of a run: every kept sweep is folded as it is enqueued (sweep_end_predict)
-static int pred_run_check(const RunOptions& o) {
+static int pred_run_check(const RunOptions& o, int P) {
     if (!o.pred) return BMM_OK;
     if (o.M < 0) return set_err(BMM_E_ARG, "M must be >= 0");
     if (o.M > 0 && !o.Xnew) return set_err(BMM_E_ARG, "Xnew is null");
     if (o.M > 0 && !o.pred->lppd) return set_err(BMM_E_ARG, "null buffer: lppd");
+    if (o.pna.on && o.M > 0) return na_check_cells(o.pna.rows, o.pna.cols, o.pna.n, o.M, P);  // before a device is touched
     return BMM_OK;
 }
 static int pred_run_attach(bmm_chain* c, const RunOptions& o, Recording& rec) {
     if (!o.predict()) return BMM_OK;
     c->pred_resp = o.pred->resp != nullptr;
     int rc = bmm_chain_set_newdata_host(c, o.Xnew, o.M);
+    if (rc == BMM_OK && o.pna.on && o.pna.n > 0) rc = bmm_chain_set_newdata_missing(c, o.pna.rows, o.pna.cols, o.pna.n);
     if (rc == BMM_OK && o.pred->logdens) rc = rec.alloc((size_t)c->S * (size_t)o.M * sizeof(double), "the log-density trace (S x M doubles)");
     if (rc) return rc;
     rec.begin(c, c->pred_rec, (size_t)o.M * sizeof(double), c->burnin, run_first_fold(c), true);
@@ -2895,6 +3122,10 @@ static int pred_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, i
         if (o.pred->resp) for (int64_t q = 0; q < o.M * c->p.Kc; ++q) o.pred->resp[q] = std::nan("");
     } else {
         rc = bmm_chain_get_predictive(c, o.pred->lppd, o.pred->resp, nullptr);
+    }
+    if (rc == BMM_OK && o.pna.on && o.pna.n > 0) {
+        if (c->pred_folded < 1) for (int64_t q = 0; q < o.pna.n; ++q) o.pna.mean[q] = std::nan("");
+        else rc = bmm_chain_get_predictive_cells(c, o.pna.mean, nullptr);
     }
     if (rc == BMM_OK && o.pred->logdens) rc = run_rows_out(c, rec.rows.as<double>(), o.M, o.pred->logdens);
     return rc;
@@ -6669,7 +6900,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
         if (rc) return rc;
         g_init_info = bmm_init_info{};
         rc = init_run_check(opts, sampler);
-        if (rc == BMM_OK) rc = pred_run_check(opts);
+        if (rc == BMM_OK) rc = pred_run_check(opts, P);
         if (rc == BMM_OK) rc = fs_run_check(opts, sampler, beta, gamma);
         if (rc == BMM_OK) rc = alloc_run_check(opts);
         if (rc == BMM_OK) rc = temper_run_check(opts, sampler);
@@ -7127,6 +7358,11 @@ int bmm_set_missing(const int64_t* rows, const int32_t* cols, int64_t n_cells, c
     g_armed.na.on = out != nullptr;
     g_armed.na.rows = rows; g_armed.na.cols = cols; g_armed.na.n = n_cells;
     g_armed.na.o = out ? *out : bmm_missing_out{};
+    return BMM_OK;
+}
+int bmm_set_newdata_missing(const int64_t* rows, const int32_t* cols, int64_t n_cells, double* cell_mean_out) {
+    g_armed.pna.on = cell_mean_out != nullptr;
+    g_armed.pna.rows = rows; g_armed.pna.cols = cols; g_armed.pna.n = n_cells; g_armed.pna.mean = cell_mean_out;
     return BMM_OK;
 }
 int bmm_set_constraints(int64_t n, const int64_t* rows, const uint64_t* masks) {

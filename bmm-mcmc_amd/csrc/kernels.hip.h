@@ -3038,6 +3038,366 @@ __global__ __launch_bounds__(256) void k_score_generic(ChainParams p, ScoreArgs 
     }
 }
 
+// ---- incomplete new rows: the observed cells scored, the missing cells predicted -----------
+// A new row with missing cells is not in the fit, so a missing cell marginalises out exactly: its Bernoulli term sums
+// to 1 and simply leaves the product.  The group tables of k_score cannot score a group with a hole in it, and taking
+// the masked terms back out of an entry cancels (and is -inf - -inf where an explicit theta is 0 or 1), so the image
+// is split by bit value instead, in doubles:
+//   T1  [G][KT][M]   T1[g][k][m] = sum over the bits j set in m of e1[g*W + j]   (the x = 1 terms)
+//   T0  [G][KT][M]   T0[g][k][m] = sum over the bits j set in m of e0[g*W + j]   (the x = 0 terms; features past P: 0)
+//   Cp  [KT]         the category's constant, log w_k: it STARTS the accumulator -- group 0 may be wholly missing
+//   E   [256]        the exp256 table
+// With nib the data bits and mn the mask bits (1 = missing) of group g, the group adds T1[g][k][nib & ~mn] and
+// T0[g][k][~nib & ~mn]: two reads per category and group, terms of observed cells only, and a complete group costs
+// the same two reads.  The single-bit entry T1[g][k][1 << j] is t_kd(1) itself, so the joint of a missing cell,
+//   log q_md = log sum_k exp(acc_k + T1[g_d][k][1 << j_d]),
+// needs no further table.  The mask is a second set of bit planes laid out as the data planes are, and the missing
+// cells of a row a CSR list (off[m] .. off[m+1] into the sorted (row, column) list).  A row, and so each of its cells,
+// is owned by one lane: the streaming pairs (run_max, run_sum) of the row and (cell_max, cell_sum) of the cell are
+// folded without atomics and in a fixed order.
+struct SplitLayout {
+    int G, KT, M;
+    __host__ __device__ int t1() const { return 0; }
+    __host__ __device__ int t0() const { return G * KT * M; }
+    __host__ __device__ int cp() const { return 2 * G * KT * M; }
+    __host__ __device__ int et() const { return cp() + KT + (KT & 1); }
+    __host__ __device__ int doubles() const { return et() + 256; }
+};
+__host__ __device__ inline SplitLayout split_layout_of(const ChainParams& p) { return SplitLayout{p.G, p.KT, 1 << p.W}; }
+
+struct NaScoreArgs {
+    const uint32_t* Xb;   // data planes of the new rows (k_pack_bits)
+    const uint32_t* Mb;   // mask planes, the same layout: bit set = the cell is missing
+    int64_t rows;
+    const double* tab;    // the split image (k_split_tables)
+    const int64_t* off;   // [rows + 1] offsets of a row's missing cells in the sorted cell list
+    const int32_t* col;   // [cells] their columns
+    double* out;          // or null: [rows], this state's log p(x_O | state)
+    double* resp;         // or null: [Kc][rows], this state's normalised category weights, from the observed cells
+    double* cell;         // or null: [cells], this state's q / p = P(x_d = 1 | x_O, state)
+    double* run_max;      // or null (nothing is folded): the row pairs, as ScoreArgs
+    double* run_sum;
+    double* resp_acc;     // or null
+    double* cell_max;     // [cells] the cell pairs: sum_s q_md(s) = exp(cell_max) * cell_sum
+    double* cell_sum;
+};
+
+// one entry of a split table: the terms e[] of the features of group g whose bit is set in m (chunk-local, as group_entry)
+__device__ __forceinline__ double split_entry(const double* e, int g, int pc, unsigned m, int W) {
+    double t = 0.0;
+    for (int j = 0; j < W; ++j) {
+        const int d = g * W + j;
+        if (d < pc && ((m >> j) & 1u)) t = t + e[d];
+    }
+    return t;
+}
+
+// The split image of the chain's current state, one workgroup per category, 256 threads: roles 0 (x = 1), 1 (x = 0).
+//   counting samplers   the count-table rules, BUILD_PREDICT, from the statistics as they stand (pending deltas added,
+//                       nothing folded or cleared), exactly the terms and constants k_state_tables<false> writes
+//   explicit samplers   from the sweep's pi / theta with the log_ arguments of k_sb_theta_tables: log_(pi_k),
+//                       log_(theta_kd), log_(1.0 - theta_kd); an accumulator past K: -inf over all-zero tables
+__global__ __launch_bounds__(256) void k_split_tables(ChainParams p, const int32_t* __restrict__ Nk,
+                                                      const int32_t* __restrict__ S, const int32_t* __restrict__ dNk,
+                                                      const int32_t* __restrict__ dS,
+                                                      const double* __restrict__ alpha_ptr,
+                                                      const double* __restrict__ pi, const double* __restrict__ theta,
+                                                      double* __restrict__ tab) {
+    __shared__ double e1[kMaxP], e0[kMaxP], cst[2];  // cst: Cp, the terms' denominator
+    const int k = blockIdx.x;
+    const SplitLayout L = split_layout_of(p);
+    const int P = p.P, K = p.K, W = p.W, M = L.M;
+    const bool is_label = k < K;
+    const bool expl = explicit_params(p.mode);
+    const size_t KP = (size_t)K * P;
+    const int64_t n = !expl && is_label ? (int64_t)Nk[k] + delta_take(const_cast<int32_t*>(dNk), k, K) : 0;
+    const CountRule r{BUILD_PREDICT, p.mode == MODE_DP, K, p.Ntot, p.beta, p.gamma, expl ? 1.0 : *alpha_ptr};
+    const int role = threadIdx.x >> 7, dl = threadIdx.x & 127;
+    if (threadIdx.x == 0) {
+        if (expl) {
+            cst[0] = is_label ? log_(pi[k]) : neg_inf();
+            cst[1] = 0.0;
+        } else {
+            const double ak = rule_ak(r);
+            double v[kRuleLogs];
+#pragma unroll
+            for (int j = 0; j < kRuleLogs; ++j) {
+                double arg;
+                v[j] = const_arg(r, ak, k, n, j, arg) ? log_(arg) : 0.0;
+            }
+            const CatConsts c = cat_consts(r, k, n, v);
+            cst[0] = c.cp;
+            cst[1] = c.den_p;
+        }
+        tab[L.cp() + k] = cst[0];
+        if ((L.KT & 1) && k == 0) tab[L.cp() + L.KT] = 0.0;  // the pad
+    }
+    __syncthreads();
+    for (int c0 = 0; c0 < P; c0 += kChunkP) {
+        const int pc = P - c0 < kChunkP ? P - c0 : kChunkP;
+        if (dl < pc) {
+            const int d = c0 + dl;
+            double t = 0.0;
+            if (expl) {
+                if (is_label) {
+                    const double th = theta[k + (size_t)d * K];
+                    t = role == 0 ? log_(th) : log_(1.0 - th);
+                }
+            } else {
+                const int64_t s = is_label ? (int64_t)S[(size_t)k * P + d] + delta_take(const_cast<int32_t*>(dS), (size_t)k * P + d, KP) : 0;
+                double arg;
+                const bool have = term_arg(r, k, role, n, s, arg);
+                t = term_of(have, have ? log_(arg) : 0.0, cst[1]);
+            }
+            (role == 0 ? e1 : e0)[dl] = t;
+        }
+        __syncthreads();
+        const int g0 = c0 / W, gc = (pc + W - 1) / W;
+        for (int idx = threadIdx.x; idx < gc * M; idx += blockDim.x) {
+            const int g = idx / M;
+            const unsigned m = idx % M;
+            const size_t at = ((size_t)(g0 + g) * L.KT + k) * M + m;
+            tab[L.t1() + at] = split_entry(e1, g, pc, m, W);
+            tab[L.t0() + at] = split_entry(e0, g, pc, m, W);
+        }
+        __syncthreads();
+    }
+    if (k == 0) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];  // 256 threads
+}
+
+// one value's share of a streaming log-sum-exp pair (the arithmetic of predict_fold); ET the exp256 table
+template <class Tab>
+__device__ __forceinline__ void lse_fold(double* __restrict__ vmax, double* __restrict__ vsum, int64_t at, double v, Tab ET) {
+    const double rm = vmax[at], rs = vsum[at];
+    const bool up = v > rm;
+    const double e = expw_tab(up ? rm - v : v - rm, ET);  // (-inf and NaN arguments give exactly 0)
+    vmax[at] = up ? v : rm;
+    vsum[at] = up ? rs * e + 1.0 : rs + e;
+}
+
+// The masked scorer, LDS form: the whole split image staged as k_score stages its head, one lane per new row, KT
+// accumulators, NT threads; the next tile's words and mask words are loaded before this tile is scored.  After the
+// max-shift and the total the lane walks its own missing cells while the accumulators are still live.
+template <int KT, int NT, int GW>
+__global__ __launch_bounds__(NT) void k_score_na(ChainParams p, NaScoreArgs a) {
+    constexpr int GM = 1 << GW;
+    constexpr int CH = KT <= 24 ? KT : (KT <= 48 ? KT / 2 : KT / 4);  // lookups issued together
+    static_assert(KT % CH == 0, "chunking");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const SplitLayout L{p.G, KT, GM};
+    double* const lds = reinterpret_cast<double*>(smem);
+    const volatile lds_f64* const T1 = (const volatile lds_f64*)(lds + L.t1());
+    const volatile lds_f64* const T0 = (const volatile lds_f64*)(lds + L.t0());
+    const volatile lds_f64* const CP = (const volatile lds_f64*)(lds + L.cp());
+    const lds_f64* const ET = (const lds_f64*)(lds + L.et());
+    const int P = p.P, G = p.G, Kc = p.Kc;
+    const int tid = threadIdx.x;
+    const int W = (P + 31) / 32;
+    const int64_t ntiles = (a.rows + NT - 1) / NT;
+    int64_t tile = blockIdx.x;
+    uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0, m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+    if (tile < ntiles) {  // the first tile's words go out before the image is staged
+        const int64_t i0 = tile * NT + tid;
+        const int64_t ic = i0 < a.rows ? i0 : a.rows - 1;
+        load_words(a.Xb, a.rows, W, ic, b0, b1, b2, b3);
+        load_words(a.Mb, a.rows, W, ic, m0, m1, m2, m3);
+    }
+    {
+        const double2* src = reinterpret_cast<const double2*>(a.tab);
+        double2* dst = reinterpret_cast<double2*>(smem);
+        const int n2 = L.doubles() / 2;  // even: every piece of the layout is
+        for (int i0 = tid; i0 < n2; i0 += NT * 8) {
+            double2 t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + u * NT;
+                t[u] = src[i < n2 ? i : n2 - 1];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int i = i0 + u * NT;
+                if (i < n2) dst[i] = t[u];
+            }
+        }
+    }
+    __syncthreads();
+    for (; tile < ntiles; tile += gridDim.x) {
+        const int64_t i = tile * NT + tid;
+        const bool valid = i < a.rows;
+        const int64_t tnext = tile + gridDim.x;
+        uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0, q0 = 0, q1 = 0, q2 = 0, q3 = 0;
+        if (tnext < ntiles) {
+            const int64_t in = tnext * NT + tid;
+            const int64_t ic = in < a.rows ? in : a.rows - 1;
+            load_words(a.Xb, a.rows, W, ic, n0, n1, n2, n3);
+            load_words(a.Mb, a.rows, W, ic, q0, q1, q2, q3);
+        }
+        double acc[KT];
+#pragma unroll
+        for (int k = 0; k < KT; ++k) acc[k] = CP[k];
+#pragma unroll 1
+        for (int h = 0; h < W; ++h) {
+            const uint32_t cur = word_of(h, b0, b1, b2, b3), nxt = word_of(h + 1, b0, b1, b2, b3);
+            const uint32_t mcur = word_of(h, m0, m1, m2, m3), mnxt = word_of(h + 1, m0, m1, m2, m3);
+            const int g_lo = (32 * h + GW - 1) / GW;
+            int g_hi = (32 * (h + 1) + GW - 1) / GW;
+            g_hi = g_hi < G ? g_hi : G;
+#pragma unroll 1
+            for (int g = g_lo; g < g_hi; ++g) {
+                const unsigned sh = (unsigned)(g * GW - 32 * h);
+                const unsigned nib = __builtin_amdgcn_alignbit(nxt, cur, sh), mn = __builtin_amdgcn_alignbit(mnxt, mcur, sh);
+                const unsigned o1 = nib & ~mn & (unsigned)(GM - 1), o0 = ~nib & ~mn & (unsigned)(GM - 1);
+                const volatile lds_f64* row1 = T1 + ((size_t)g * KT * GM + o1);
+                const volatile lds_f64* row0 = T0 + ((size_t)g * KT * GM + o0);
+#pragma unroll
+                for (int c0 = 0; c0 < KT; c0 += CH) {
+                    double tv[CH];
+#pragma unroll
+                    for (int j = 0; j < CH; ++j) tv[j] = row1[(c0 + j) * GM];
+#pragma unroll
+                    for (int j = 0; j < CH; ++j) acc[c0 + j] = acc[c0 + j] + tv[j];
+                    __builtin_amdgcn_sched_barrier(0);  // keep the chunks apart
+#pragma unroll
+                    for (int j = 0; j < CH; ++j) tv[j] = row0[(c0 + j) * GM];
+#pragma unroll
+                    for (int j = 0; j < CH; ++j) acc[c0 + j] = acc[c0 + j] + tv[j];
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        double mx = neg_inf();
+#pragma unroll
+        for (int k = 0; k < KT; ++k) mx = __builtin_fmax(mx, acc[k]);
+        double tot = 0.0;
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            tot = tot + expw_tab(acc[k] - mx, ET);
+            if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);  // two at a time: bounds the temporaries
+        }
+        const double ld = mx + log_(tot);
+        if (valid) {
+            if (a.out) a.out[i] = ld;
+            if (a.run_max) lse_fold(a.run_max, a.run_sum, i, ld, ET);
+            // the row's missing cells: the joint with x_d = 1 from the live accumulators and the single-bit entry
+            const int64_t q_end = a.off[i + 1];
+#pragma unroll 1
+            for (int64_t q = a.off[i]; q < q_end; ++q) {
+                const int d = a.col[q];
+                const int g = d / GW, j = d - g * GW;
+                const volatile lds_f64* r1 = T1 + ((size_t)g * KT * GM + (1u << j));
+                // t_kd(1) <= 1: the row's own shift mx bounds every term of the joint, so one pass does (a second
+                // maximum would keep KT more sums live: scratch from 32 accumulators on)
+                double cs = 0.0;
+#pragma unroll
+                for (int k = 0; k < KT; ++k) {
+                    cs = cs + expw_tab((acc[k] + r1[k * GM]) - mx, ET);
+                    if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);
+                }
+                const double lj = mx + log_(cs);
+                if (a.cell) a.cell[q] = expw_tab(lj - ld, ET);
+                if (a.cell_max) lse_fold(a.cell_max, a.cell_sum, q, lj, ET);
+            }
+            if (a.resp || a.resp_acc) {  // uniform
+                // the column stride in a VGPR: as a scalar the compiler keeps all KT column offsets of both matrices
+                // live across the tile loop (over a hundred spilled SGPRs at 28 accumulators)
+                int64_t ld_resp = a.rows;
+                asm volatile("" : "+v"(ld_resp));
+                int64_t at = i;
+                double mx_r = mx;  // the weights are computed again here, not kept live through the cell pass
+                asm volatile("" : "+v"(mx_r));
+#pragma unroll
+                for (int k = 0; k < KT; ++k) {
+                    if (k < Kc) {  // (a break here turns acc into an indexed array: a private segment)
+                        const double r = div_(expw_tab(acc[k] - mx_r, ET), tot);
+                        if (a.resp) a.resp[at] = r;
+                        if (a.resp_acc) a.resp_acc[at] += r;
+                    }
+                    at += ld_resp;
+                }
+            }
+        }
+        b0 = n0; b1 = n1; b2 = n2; b3 = n3;
+        m0 = q0; m1 = q1; m2 = q2; m3 = q3;
+    }
+}
+
+// The masked scorer, global form: the doubled head does not fit in LDS, or the shape is k_resample_generic's.  Tables
+// gathered from global memory (L2), the scores in a per-thread scratch column scr[k * stride + thread] as
+// k_score_generic keeps them.  Same arithmetic and the same order of sums as k_score_na.
+__global__ __launch_bounds__(256) void k_score_na_generic(ChainParams p, NaScoreArgs a, double* scr, int64_t stride) {
+    const SplitLayout L = split_layout_of(p);
+    const int GM = L.M;
+    const double* const T1 = a.tab + L.t1();
+    const double* const T0 = a.tab + L.t0();
+    const double* const CP = a.tab + L.cp();
+    const double* const ET = a.tab + L.et();
+    const int P = p.P, G = p.G, Kc = p.Kc, KT = p.KT, GW = p.W;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // < stride: the host sizes the grid
+    double* const my = scr + gid;
+    for (int64_t i = gid; i < a.rows; i += (int64_t)gridDim.x * blockDim.x) {
+        double mx = neg_inf();
+        for (int k0 = 0; k0 < Kc; k0 += 16) {
+            double acc[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc[j] = k0 + j < Kc ? CP[k0 + j] : 0.0;
+            for (int g = 0; g < G; ++g) {
+                const unsigned nib = field_from_x(nullptr, a.Xb, a.rows, P, i, g, GW);
+                const unsigned mn = field_from_x(nullptr, a.Mb, a.rows, P, i, g, GW);
+                const unsigned o1 = nib & ~mn & (unsigned)(GM - 1), o0 = ~nib & ~mn & (unsigned)(GM - 1);
+                const double* row1 = T1 + ((size_t)g * KT + k0) * GM + o1;
+                const double* row0 = T0 + ((size_t)g * KT + k0) * GM + o0;
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if (k0 + j < Kc) acc[j] = (acc[j] + row1[j * GM]) + row0[j * GM];
+            }
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (k0 + j < Kc) {
+                    my[(int64_t)(k0 + j) * stride] = acc[j];
+                    mx = __builtin_fmax(mx, acc[j]);
+                }
+        }
+        double tot = 0.0;
+        for (int k = 0; k < Kc; ++k) tot = tot + expw_tab(my[(int64_t)k * stride] - mx, ET);
+        const double ld = mx + log_(tot);
+        if (a.out) a.out[i] = ld;
+        if (a.run_max) lse_fold(a.run_max, a.run_sum, i, ld, ET);
+        const int64_t q_end = a.off[i + 1];
+        for (int64_t q = a.off[i]; q < q_end; ++q) {
+            const int d = a.col[q];
+            const int g = d / GW, j = d - g * GW;
+            const double* r1 = T1 + (size_t)g * KT * GM + (1u << j);
+            double cs = 0.0;  // (the row's own shift, as k_score_na)
+            for (int k = 0; k < Kc; ++k) cs = cs + expw_tab((my[(int64_t)k * stride] + r1[(size_t)k * GM]) - mx, ET);
+            const double lj = mx + log_(cs);
+            if (a.cell) a.cell[q] = expw_tab(lj - ld, ET);
+            if (a.cell_max) lse_fold(a.cell_max, a.cell_sum, q, lj, ET);
+        }
+        if (a.resp || a.resp_acc)
+            for (int k = 0; k < Kc; ++k) {
+                const double r = div_(expw_tab(my[(int64_t)k * stride] - mx, ET), tot);
+                if (a.resp) a.resp[(int64_t)k * a.rows + i] = r;
+                if (a.resp_acc) a.resp_acc[(int64_t)k * a.rows + i] += r;
+            }
+    }
+}
+
+// The cell pairs after the folded states: cell_mean = sum_s q_md(s) / sum_s p(x_O | s), the states weighted by the
+// density of the row's observed cells (the chain samples s | X, not s | X, x_O).  The number of states cancels.  The
+// accumulators are left as they are, so more sweeps may be folded afterwards.
+__global__ __launch_bounds__(256) void k_predict_cells_finish(int64_t cells, const int64_t* __restrict__ row,
+                                                              const double* __restrict__ run_max,
+                                                              const double* __restrict__ run_sum,
+                                                              const double* __restrict__ cell_max,
+                                                              const double* __restrict__ cell_sum,
+                                                              double* __restrict__ cell_mean) {
+    const double* const ET = exp256_table();
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < cells; q += (int64_t)gridDim.x * 256) {
+        const int64_t m = row[q];
+        cell_mean[q] = expw_tab((cell_max[q] + log_(cell_sum[q])) - (run_max[m] + log_(run_sum[m])), ET);
+    }
+}
+
 // empty accumulators: no state folded
 __global__ __launch_bounds__(256) void k_loo_reset(int64_t N, double* __restrict__ acc) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {

@@ -457,6 +457,56 @@ int bmm_full_run_predict(const int32_t* X, int64_t N, int P, const double* initi
                          double* theta_out, double* alpha_out, const int32_t* Xnew, int64_t M,
                          const bmm_predict_out* pred);
 
+/* ---- incomplete new rows: density of the observed cells, missing cells predicted ------
+ * A new row x may have missing cells: observed cells O, missing cells U.  The row is not in the fit, so nothing is
+ * imputed or approximated: a missing cell marginalises out exactly (its Bernoulli term sums to 1), and the category
+ * terms are those of the section above with the product running over d in O only,
+ *   p(x_O | s) = sum_k w_k(s) prod_{d in O} t_kd(x_d),
+ * w_k the category weights and t_kd the Bernoulli terms of the three formulas above (for the DP the new-cluster column
+ * included, an unused label at weight 0).  A row with O empty has p = sum_k w_k: 1 for the finite and the DP sampler,
+ * sum_k pi_k for the explicit ones.  For a missing cell (m, d) the per-state joint with a 1 in it is
+ *   q_md(s) = p(x_O, x_d = 1 | s) = sum_k w_k prod_{O} t_k.(x.) * t_kd(1).
+ * Over the S folded states:
+ *   lppd[m]          log((1/S) sum_s p(x_O | s)), on the observed cells;
+ *   resp[m, k]       the mean of the normalised category weights from the observed cells;
+ *   cell_mean[m, d]  sum_s q_md(s) / sum_s p(x_O | s) = P(x_d = 1 | x_O, X), the posterior predictive probability of a 1
+ *                    in the missing cell given the row's observed cells and the fitted data;
+ *   cell_state[m, d] q_md(s) / p(x_O | s) = P(x_d = 1 | x_O, s), the per-state value;
+ *   logdens[s, m]    log p(x_O | s).
+ * cell_mean is NOT the plain mean over the states of cell_state: the chain samples s | X, not s | X, x_O, so the states
+ * are weighted by p(x_O | s) (self-normalised importance weights).  Both sums are kept as streaming log-sum-exp pairs,
+ * one lane per row and per cell: no atomics, a fixed order, the same bits twice.
+ * The cells are given as bmm_set_missing takes them: strictly ascending in (row, column), rows int64 in 0 .. M-1,
+ * columns int32 in 0 .. P-1; Xnew holds 0 in them (any 0/1 value is ignored).  Per-cell outputs are in the order of the
+ * list.  A set without missing cells takes the kernels of the section above and gives their results byte for byte.
+ * Refused, leaving the chain as it was: unsorted or repeated cells, a cell outside M x P (BMM_E_ARG), and whatever
+ * the predictive itself refuses. */
+/* resident chains: after bmm_chain_set_newdata_host; replaces any earlier mask and empties the accumulators;
+ * n = 0 drops the mask.  A later bmm_chain_set_newdata_host drops it with the set it belonged to. */
+int bmm_chain_set_newdata_missing(bmm_chain* c, const int64_t* rows, const int32_t* cols, int64_t n);
+/* bmm_chain_predict_state with the per-state P(x_d = 1 | x_O, s) of every missing cell: cell_out n doubles or NULL
+ * (non-NULL needs a mask); resp_out M x Kc or NULL.  Waits. */
+int bmm_chain_predict_state_cells(bmm_chain* c, double* logdens_out, double* resp_out, double* cell_out);
+/* cell_mean (n doubles) over the states folded so far, and their number; the accumulators stay */
+int bmm_chain_get_predictive_cells(bmm_chain* c, double* cell_mean, int* n_folded);
+/* One call: armed for the next *_run_predict call of the calling thread and disarmed when that call returns, whatever
+ * it returns, exactly as bmm_set_missing; the cells index the Xnew of that call, cell_mean_out receives n_cells doubles
+ * (NaN when no sweep was folded).  cell_mean_out = NULL disarms.  The list must stay valid until the run returns. */
+int bmm_set_newdata_missing(const int64_t* rows, const int32_t* cols, int64_t n_cells, double* cell_mean_out);
+/* Which form of the masked scorer a shape takes -- a pure function of (sampler, K, P), no device is touched; the
+ * launches read the same function.  LDS: the split table image (two tables per group, by bit value, the constants and
+ * the exp table) staged in LDS, lds_bytes of it, `threads` lanes per workgroup; GLOBAL: the image does not fit or the
+ * shape has no resident kernel: tables read from global memory, scores in scratch columns, lds_bytes = 0.  table_bytes:
+ * the image in device memory.  K: the labels (maxK for the DP and stick-breaking samplers). */
+enum { BMM_PREDICT_NA_LDS = 0, BMM_PREDICT_NA_GLOBAL = 1 };
+typedef struct bmm_predict_na_plan_out {
+    int form;             /* BMM_PREDICT_NA_* */
+    int threads;
+    int64_t lds_bytes;
+    int64_t table_bytes;
+} bmm_predict_na_plan_out;
+int bmm_predict_na_plan(int sampler, int K, int P, bmm_predict_na_plan_out* out);
+
 /* ---- clustering point estimate and posterior similarity ------------------------------
  * Label-invariant summaries of a label trace, computed where the trace is.  A row z of N labels in 0 .. Kc-1 is a
  * partition.  For two rows c, z let n_ab = #{i : c_i = a, z_i = b}, n_a. = sum_b n_ab, n_.b = sum_a n_ab.
@@ -1382,7 +1432,7 @@ int bmm_chain_missing_reset(bmm_chain* c);
  * BMM_E_UNSUPPORTED as above, also for bmm_set_init and a *_run_relabel / hooked *_run_probs hand-off; bmm_multi_run
  * and bmm_alloc_run answer an armed declaration with BMM_E_UNSUPPORTED.  n_cells = 0 is the run without it, byte for
  * byte.  Allowed, and unchanged because they read labels or folded counts only: the partition summary, ECR, the
- * predictive of complete new rows and the log joint trace. */
+ * predictive of new rows (complete, or incomplete: the section "incomplete new rows") and the log joint trace. */
 typedef struct bmm_missing_out {
     double* mean_rb;    /* [n_cells] */
     double* mean_draw;  /* [n_cells] */
