@@ -11,6 +11,7 @@ There is no CPU fallback: without the built HIP library and a gfx950 device ever
 sampler call raises.
 """
 import ctypes as _C
+from collections import namedtuple as _namedtuple
 
 import numpy as _np
 
@@ -166,15 +167,40 @@ class _DeviceRelabelRun:
         return out
 
 
+# ---------------------------------------------------------------- what every option of a run is
+class _Option:
+    """What a run carries for one of its options: arm() hands it to the library just ahead of the call, into(out)
+    adds what the run left in it to the result -- under `key`, unless the option says otherwise."""
+    key = None
+
+    def into(self, out):
+        out[self.key] = self.result()
+        return out
+
+
+def _arm(options):
+    for o in options:
+        if o is not None:
+            o.arm()
+
+
+def _collect(out, options):
+    for o in options:
+        if o is not None:
+            out = o.into(out)
+    return out
+
+
 # ---------------------------------------------------------------- newdata=: the posterior predictive
 class _PredictOut(_C.Structure):  # bmm_predict_out
     _fields_ = [("lppd", _C.c_void_p), ("logdens", _C.c_void_p), ("resp", _C.c_void_p), ("relabel", _C.c_void_p),
                 ("hooks", _C.c_void_p)]
 
 
-class _Predict:
+class _Predict(_Option):
     """Inputs and outputs of a bmm_*_run_predict call: the new rows, lppd (M,), optionally the (S, M) trace of
     log p(x_m | state s) and the (M, Kc) mean responsibilities (include/bmm_mcmc.h)."""
+    key = "predictive"
 
     def __init__(self, newdata, P, S, Kc, trace, responsibilities, chains, newdata_missing=None, burnin=0):
         if int(chains) > 1:
@@ -230,16 +256,6 @@ def predict_na_plan(sampler, K, P):
             "table_bytes": int(o.table_bytes)}
 
 
-def _with_predictive(out, pr, pt=None, lo=None):
-    if pr is not None:
-        out["predictive"] = pr.result()
-    if pt is not None:
-        out["partition"] = pt.result()
-    if lo is not None:
-        out["loo"] = lo.result()
-    return out
-
-
 # ---------------------------------------------------------------- loo=: leave-one-out predictive, LPML, WAIC
 class _LooOut(_C.Structure):  # bmm_loo_out
     _fields_ = [("log_cpo", _C.c_void_p), ("ess", _C.c_void_p), ("lppd", _C.c_void_p), ("mean", _C.c_void_p),
@@ -247,10 +263,11 @@ class _LooOut(_C.Structure):  # bmm_loo_out
                 ("elpd_waic", _C.c_void_p), ("n_folded", _C.c_void_p), ("ell", _C.c_void_p)]
 
 
-class _Loo:
+class _Loo(_Option):
     """Outputs of the leave-one-out summary (include/bmm_mcmc.h): per fitted row log_cpo, ess,
     lppd, mean and var of ell over the folded states; lpml, min_ess, n_folded; p_waic and elpd_waic for the samplers
     that carry explicit parameters; optionally the (S, N) trace ell."""
+    key = "loo"
 
     def __init__(self, N, S=0, trace=False, waic=False):
         self.waic = waic
@@ -317,9 +334,10 @@ def _indices(idx, N):
     return idx
 
 
-class _Partition:
+class _Partition(_Option):
     """Outputs of an armed bmm_set_partition_summary: the run fills them after its last sweep (include/bmm_mcmc.h,
     DESIGN.md section 13).  With several chains nothing is armed: the traces are pooled afterwards."""
+    key = "partition"
 
     def __init__(self, criterion, stride, similarity_of, N, S):
         self.criterion, self.stride = criterion, _stride(stride)
@@ -476,7 +494,7 @@ def _search_opts(N, Kc, batch=None, min_batch=None, max_passes=50, max_clusters=
     return _SearchOpts(batch, min_batch, max_passes, Ka)
 
 
-class _Search:
+class _Search(_Option):
     """Outputs of a greedy search (bmm_device_partition_search, or armed with bmm_set_partition_search for a run)."""
 
     def __init__(self, criterion, N, opts):
@@ -506,6 +524,13 @@ class _Search:
                 "start_binder2": int(self.u64[1]), "passes": n, "batch": [int(v) for v in self.pb[:n]],
                 "moved": [int(v) for v in self.pm[:n]], "total": total, "converged": bool(self.i32[1]),
                 "n_clusters": int(self.i32[2])}
+
+    def into(self, out):
+        """the search of a single-chain run beside the summary it started from"""
+        res = self.result() if "partition" in out else None
+        if res is not None:
+            out["partition"]["search"] = res
+        return out
 
 
 def partition_search(z, criterion="binder", start=None, batch=None, min_batch=None, max_passes=50, max_clusters=None,
@@ -575,15 +600,6 @@ def _make_search(partition_search, partition, N, K, chains):
     return kw if int(chains) > 1 else _Search(partition, N, opts)
 
 
-def _with_search(out, ps):
-    """the search of a single-chain run beside the summary it started from"""
-    if ps is not None and "partition" in out:
-        res = ps.result()
-        if res is not None:
-            out["partition"]["search"] = res
-    return out
-
-
 def _pooled_search(chains_out, kw, partition, K, device):
     """chains > 1: the search over the stacked traces _pooled used, from the pooled estimate, through the stand-alone call"""
     if kw is None:
@@ -647,7 +663,7 @@ def _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition):
     return False, (kind, pv, int(ecr_max_iter))
 
 
-class _Ecr:
+class _Ecr(_Option):
     """Outputs of an armed bmm_set_ecr_relabel: the run fills them after its last sweep (include/bmm_mcmc.h "ECR",
     DESIGN.md section 19).  With several chains nothing is armed: the traces are stacked afterwards (_ecr_chains)."""
 
@@ -667,7 +683,7 @@ class _Ecr:
     def arm(self):
         _capi.check(_capi.lib().bmm_set_ecr_relabel(_C.byref(self.s)))
 
-    def finish(self, out):
+    def into(self, out):
         out.update(permutations=self.perms, z_original=self.z_orig, theta_original=self.th_orig,
                    ecr={"agree": self.agree, "pivot": self.pivot, "iterations": self.iterations.value,
                         "converged": bool(self.converged.value), "n_used": self.n_used.value})
@@ -822,11 +838,14 @@ class _LogPostOut(_C.Structure):  # bmm_logpost_out
     _fields_ = [("rows", _C.c_void_p), ("z_best", _C.c_void_p), ("best_total", _C.c_void_p), ("best_row", _C.c_void_p)]
 
 
-class _LogPost:
+class _LogPost(_Option):
     """Outputs of an armed bmm_set_logpost: the run fills them (include/bmm_mcmc.h "log joint trace", DESIGN.md
-    section 20).  With several chains nothing is armed: every chain is scored afterwards (_lp_chains)."""
+    section 20).  With several chains nothing is armed: every chain is scored afterwards (_lp_chains).  relabel_to:
+    (the ecr_pivot="map" request, K, device) of a run that is then relabelled to its best state."""
+    key = "logpost"
 
-    def __init__(self, N, S):
+    def __init__(self, N, S, relabel_to=None):
+        self.relabel_to = relabel_to
         self.rows = _np.full((S, 4), _np.nan, order="F")
         self.z = _np.full(N, NA_INTEGER, dtype=_np.int32)
         self.total = _C.c_double(float("nan"))
@@ -843,13 +862,10 @@ class _LogPost:
         out.update(best=self.best.value, z_map=self.z, ess=ess(lj[used]), n_used=int(used.size))
         return out
 
-
-def _make_logpost(logpost, ecr_req, N, S, chains):
-    """logpost= of a wrapper (ecr_pivot="map" implies it): the outputs to arm for a single chain, True for several
-    (they are scored afterwards), None when off"""
-    if not logpost and not (ecr_req is not None and ecr_req[0] == _ECR_MAP):
-        return None
-    return True if int(chains) > 1 else _LogPost(N, S)
+    def into(self, out):
+        """a single chain's object: the armed outputs attached, then the relabelling to the best state"""
+        out["logpost"] = self.result()
+        return out if self.relabel_to is None else _ecr_map([out], *self.relabel_to)[0]
 
 
 # ---------------------------------------------------------------- temper=: parallel tempering, a replica ladder
@@ -874,9 +890,10 @@ class _TemperOut(_C.Structure):  # bmm_temper_out
                 ("accepted", _C.c_void_p), ("walker_cold", _C.c_void_p), ("loglik", _C.c_void_p)]
 
 
-class _Temper:
+class _Temper(_Option):
     """Outputs of an armed bmm_set_temper: the run fills them (include/bmm_mcmc.h "parallel tempering", DESIGN.md
     section 21)."""
+    key = "temper"
 
     def __init__(self, inv_temp, swap_every, S):
         self.b = _np.ascontiguousarray(inv_temp, dtype=_np.float64)
@@ -984,19 +1001,14 @@ def _lp_chains(chains_out, X, sampler, K, alpha, beta, gamma, a, b, device):
     return chains_out
 
 
-def _logpost_request(logpost, ecr_req, N, S, chains):
-    """(lp, ecr_req for the run, the "map" request or None)"""
-    lp = _make_logpost(logpost, ecr_req, N, S, chains)
-    if ecr_req is not None and ecr_req[0] == _ECR_MAP:
-        return lp, None, ecr_req
-    return lp, ecr_req, None
-
-
-def _with_logpost(out, lp, ecr_map, K, device):
-    """a single chain's object: the armed outputs attached, then the relabelling to the best state"""
-    if lp is not None:
-        out["logpost"] = lp.result()
-    return out if ecr_map is None else _ecr_map([out], ecr_map, K, device)[0]
+def _logpost_request(logpost, ecr_req, N, S, chains, K, device):
+    """logpost= of a wrapper (ecr_pivot="map" implies it): (lp, ecr_req for the run, the "map" request or None); lp:
+    the outputs to arm for a single chain, True for several (they are scored afterwards), None when off"""
+    ecr_map = ecr_req if ecr_req is not None and ecr_req[0] == _ECR_MAP else None
+    if not logpost and ecr_map is None:
+        return None, ecr_req, None
+    lp = True if chains > 1 else _LogPost(N, S, None if ecr_map is None else (ecr_map, K, device))
+    return lp, None if ecr_map is not None else ecr_req, ecr_map
 
 
 def _ecr_map(outs, req, K, device):
@@ -1045,8 +1057,9 @@ def pair_check_pairs(M):
     return _np.stack([i, j], axis=1).astype(_np.int32)
 
 
-class _PairFold:
+class _PairFold(_Option):
     """the host side of a fold: the buffers a bmm_pair_check_out points at, and the summary made of them"""
+    key = "pair_check"
 
     def __init__(self, feat, stride=1, S=0, trace=False):
         self.feat = feat
@@ -1089,12 +1102,6 @@ def _make_pair_check(pair_check, stride, trace, P, S, chains):
     if int(stride) < 1:
         raise ValueError("pair_check_stride must be >= 1")
     return _PairFold(_pc_features(pair_check, P), stride, S, bool(trace))
-
-
-def _with_pair_check(out, pc):
-    if pc is not None:
-        out["pair_check"] = pc.result()
-    return out
 
 
 def pair_check(X, z, Kc, features=None, counts=False, device=0):
@@ -1170,8 +1177,9 @@ def _summary_pivot(pivot, N):
     return _SUMMARY_PIVOT_GIVEN, pv
 
 
-class _SummaryFold:
+class _SummaryFold(_Option):
     """the host side of a summary: the buffers a bmm_summary_out points at, and the result derived from them"""
+    key = "summary"
 
     def __init__(self, N, K, P, pivot, stride, counts=False, S=0, keep_trace=True):
         kind, self.given = _summary_pivot(pivot, N)
@@ -1216,6 +1224,12 @@ class _SummaryFold:
             out["counts"] = self.counts
         return out
 
+    def into(self, out):
+        out["summary"] = self.result()
+        if not self.keep_trace:
+            out["z"] = None
+        return out
+
 
 def _make_summary(summary, pivot, stride, keep_trace, N, K, P, S, chains, relabel=False, partition=None, similarity_of=None):
     """summary= and keep_trace= of a wrapper: the outputs to arm, None when off.  What the wrapper itself cannot run is
@@ -1234,14 +1248,6 @@ def _make_summary(summary, pivot, stride, keep_trace, N, K, P, S, chains, relabe
     if not keep_trace and (partition is not None or similarity_of is not None):
         raise ValueError("keep_trace=False drops the label trace, which partition= and similarity_of= read")
     return _SummaryFold(N, K, P, pivot, stride, counts=summary == "counts", S=S, keep_trace=keep_trace)
-
-
-def _with_summary(out, su):
-    if su is not None:
-        out["summary"] = su.result()
-        if not su.keep_trace:
-            out["z"] = None
-    return out
 
 
 def _z_trace(S, N, su):
@@ -1284,22 +1290,25 @@ class _SplitMergeStep(_C.Structure):  # bmm_split_merge_step
                 ("move", _C.c_uint32), ("launch_side", _C.c_void_p), ("proposal_side", _C.c_void_p)]
 
 
-class _SplitMerge:
-    """split_merge= of gibbs_dp, checked before any device is touched and armed for exactly one run"""
+class _SplitMerge(_Option):
+    """split_merge= of gibbs_dp and (alloc) of gibbs_allocation, checked before any device is touched and armed for
+    exactly one run"""
+    key = "split_merge"
 
-    def __init__(self, moves, scans):
+    def __init__(self, moves, scans, alloc=False):
         self.moves, self.scans = int(moves), int(scans)
+        self.infix, self.fields = ("alloc_", _AS_FIELDS) if alloc else ("", _SM_FIELDS)
 
     def arm(self):
-        _capi.check(_capi.lib().bmm_set_split_merge(_C.c_int(self.moves), _C.c_int(self.scans)))
+        _capi.check(getattr(_capi.lib(), "bmm_set_%ssplit_merge" % self.infix)(_C.c_int(self.moves), _C.c_int(self.scans)))
 
     def result(self):
         out = (_C.c_int64 * 5)()
-        _capi.check(_capi.lib().bmm_last_split_merge_stats(out))
-        return dict(zip(_SM_FIELDS, (int(v) for v in out)))
+        _capi.check(getattr(_capi.lib(), "bmm_last_%ssplit_merge_stats" % self.infix)(out))
+        return dict(zip(self.fields, (int(v) for v in out)))
 
 
-def _make_split_merge(split_merge, scans, chains):
+def _make_split_merge(split_merge, scans, chains, alloc=False):
     moves = int(split_merge or 0)
     scans = SPLIT_MERGE_SCANS if scans is None else int(scans)
     if moves < 0 or scans < 0:
@@ -1308,7 +1317,7 @@ def _make_split_merge(split_merge, scans, chains):
         return None
     if int(chains) > 1:
         raise ValueError("split_merge= is offered per chain (chains=1)")
-    return _SplitMerge(moves, scans)
+    return _SplitMerge(moves, scans, alloc)
 
 
 # ---------------------------------------------------------------- gibbs_allocation: unknown K for the finite chain
@@ -1372,9 +1381,7 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
     of every sweep from the second, each with `split_merge_scans` intermediate restricted scans: a split opens component
     K + 1 along the data, a merge closes one.  The result gains `split_merge = {"proposed_splits", "accepted_splits",
     "proposed_merges", "accepted_merges", "skipped"}`."""
-    split_merge, split_merge_scans = int(split_merge or 0), int(split_merge_scans)
-    if split_merge < 0 or split_merge_scans < 0:
-        raise ValueError("split_merge and split_merge_scans must be >= 0")
+    sm = _make_split_merge(split_merge, split_merge_scans, 1, alloc=True)
     X = _capi.as_x(data)
     N, P = X.shape
     nsamples, maxK = int(nsamples), int(maxK)
@@ -1395,19 +1402,14 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
     theta = _np.zeros((maxK, P, S), order="F")
     Ks = _np.zeros(S, dtype=_np.int32)
     counts = (_C.c_int64 * 4)()
+    ec = None
     if relabel:
         ecr_req = _ecr_request(relabel, None, ecr_pivot, ecr_max_iter, N, partition)[1]
         if ecr_req is None:
             raise ValueError('gibbs_allocation offers no relabelling (relabel must be False)')
-        ec = _Ecr(ecr_req, N, maxK, P, S)  # alive through the call
-        ec.arm()  # the library refuses the run
-    if pt is not None:
-        pt.arm()
+        ec = _Ecr(ecr_req, N, maxK, P, S)  # armed below: the library refuses the run
     lj = _LogPost(N, S) if logpost else None
-    if lj is not None:
-        lj.arm()
-    if split_merge > 0:
-        _capi.check(_capi.lib().bmm_set_alloc_split_merge(_C.c_int(split_merge), _C.c_int(split_merge_scans)))
+    _arm((ec, pt, lj, sm))
     _capi.check(_capi.lib().bmm_alloc_run(
         _capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(maxK), _C.c_double(a),
         _C.c_double(beta), _C.c_double(gamma), _capi.vp(lp), _C.c_int(K0), _C.c_int(int(moves)), _C.c_double(eject_a),
@@ -1416,15 +1418,7 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
     used = _np.array([len(_np.unique(row)) for row in z], dtype=_np.int32)
     out = {"z": z, "theta": theta, "K": Ks, "k_posterior": _np.bincount(Ks, minlength=maxK + 1)[1:] / float(S), "k_used": used,
            "moves": dict(zip(_EA_FIELDS, (int(v) for v in counts)))}
-    if split_merge > 0:
-        st = (_C.c_int64 * 5)()
-        _capi.check(_capi.lib().bmm_last_alloc_split_merge_stats(st))
-        out["split_merge"] = dict(zip(_AS_FIELDS, (int(v) for v in st)))
-    if pt is not None:
-        out["partition"] = pt.result()
-    if lj is not None:
-        out["logpost"] = lj.result()
-    return out
+    return _collect(out, (sm, pt, lj))
 
 
 # ---------------------------------------------------------------- select_features=: noise features (White, Wyse & Murphy 2016)
@@ -1438,8 +1432,9 @@ class _FeatureOut(_C.Structure):  # bmm_feature_out
                 ("n_selected", _C.c_void_p), ("n_folded", _C.POINTER(_C.c_int))]
 
 
-class _Features:
+class _Features(_Option):
     """select_features= of gibbs_collapsed / gibbs_dp, checked before any device is touched and armed for one run"""
+    key = "features"
 
     def __init__(self, rho, P, S):
         self.rho = float(rho)
@@ -1479,8 +1474,9 @@ class _MissingOut(_C.Structure):  # bmm_missing_out
     _fields_ = [("mean_rb", _C.c_void_p), ("mean_draw", _C.c_void_p), ("last", _C.c_void_p), ("n_folded", _C.POINTER(_C.c_int64))]
 
 
-class _Missing:
+class _Missing(_Option):
     """missing= of the four samplers: the sorted cell list, armed for exactly one run"""
+    key = "missing"
 
     def __init__(self, rows, cols, N, P):
         self.rows, self.cols, self.size = rows, cols, N * P
@@ -1507,15 +1503,10 @@ def _take_missing(data, missing):
     return data, (rows, cols)
 
 
-def _with_missing(out, mi):
-    if mi is not None:
-        out["missing"] = mi.result()
-    return out
-
-
 # ---------------------------------------------------------------- known= / allowed=: constrained allocations
-class _Constraints:
+class _Constraints(_Option):
     """known= / allowed= of the four samplers: the sorted row list and the masks, armed for exactly one run"""
+    key = "constraints"
 
     def __init__(self, rows, masks):
         self.rows, self.masks = rows, masks
@@ -1543,12 +1534,6 @@ def _take_constraints(known, allowed, N, K, sets=True):
                          "gibbs_stickbreaking is whatever cluster holds it, so only known= rows can pin one")
     rows, masks, _ = _capi.constraint_list(N, K, known, allowed)
     return _Constraints(rows, masks)
-
-
-def _with_constraints(out, cs):
-    if cs is not None:
-        out["constraints"] = cs.result()
-    return out
 
 
 # ---------------------------------------------------------------- init=: the k-modes++ start on the device
@@ -1580,8 +1565,9 @@ def _init_kind(init, init_iters, allowed=True):
     return INIT_KINDS[init], iters
 
 
-class _Init:
+class _Init(_Option):
     """init= of gibbs_collapsed, armed for exactly one run"""
+    key = "init"
 
     def __init__(self, kind, iters):
         self.kind, self.iters = kind, iters
@@ -1595,37 +1581,13 @@ class _Init:
         return info.as_dict()
 
 
-def _run(base, args, pr, hooks=None, rel=None, part=None, loo=None, sm=None, fs=None, init=None, ecr=None, lp=None, tp=None, pc=None,
-         mi=None, cs=None, su=None, ps=None):
+def _run(base, args, options, pr=None, hooks=None, rel=None):
     """One *_run call: plain / hooked (bmm_<base>_run_probs), relabelled on the device (_run_relabel), or either of
-    them with the predictive of new rows (_run_predict); part: the partition summary armed for exactly this call."""
+    them with the predictive of new rows (_run_predict).  options: what is armed for exactly this call, in the order
+    of arming -- _gibbs lists it with the start of init= last, just ahead of the call: a run of another sampler
+    refuses an armed start."""
     L = _capi.lib()
-    if sm is not None:
-        sm.arm()
-    if fs is not None:
-        fs.arm()
-    if part is not None:
-        part.arm()
-    if ps is not None:
-        ps.arm()
-    if loo is not None:
-        loo.arm()
-    if ecr is not None:
-        ecr.arm()
-    if lp is not None:
-        lp.arm()
-    if tp is not None:
-        tp.arm()
-    if pc is not None:
-        pc.arm()
-    if mi is not None:
-        mi.arm()
-    if cs is not None:
-        cs.arm()
-    if su is not None:
-        su.arm()
-    if init is not None:  # last, just ahead of the call: a run of another sampler refuses an armed start
-        init.arm()
+    _arm(options)
     if pr is None:
         if rel is not None:
             return getattr(L, "bmm_%s_run_relabel" % base)(*args, rel.ref())
@@ -1778,6 +1740,154 @@ def _multi(sampler, X, chains, devices, z0s, pi0s, th0s, nsamples, K, alpha, bet
     return out
 
 
+_Sampler = _namedtuple("_Sampler", "name base start new_column waic sets clamp")
+# What differs between the four samplers, beside the layout of their arguments (_run_args).  name, base: what the
+# library calls the sampler and its entry points; start: the state a run starts from -- labels (initial_K), the
+# parameters (initial_pi, initial_theta: such a run also returns "pi") or nothing; new_column: the new-cluster column of
+# the predictive beside the K labels; waic: loo= reports WAIC; sets: allowed= is offered; clamp: burnrelabel is cut to
+# the burn-in (R/utils.R:26,41,72; :97-101 has no clamp).
+_COLLAPSED = _Sampler(name="collapsed", base="collapsed", start="labels", new_column=0, waic=False, sets=True, clamp=True)
+_DP = _Sampler(name="dp", base="dp", start=None, new_column=1, waic=False, sets=False, clamp=True)
+_STICKBREAKING = _Sampler(name="stickbreaking", base="sb", start="params", new_column=0, waic=True, sets=False, clamp=False)
+_FULL = _Sampler(name="full", base="full", start="params", new_column=0, waic=True, sets=True, clamp=True)
+
+
+def _start_params(seed, pi, th, K, P):
+    rng = _np.random.default_rng(seed)
+    if pi is None:  # R/utils.R:68-70, 98-100
+        pi = _np.exp(rng.random(K))
+        pi = pi / pi.sum()
+    if th is None:  # R/utils.R:74, 103
+        th = rng.random(K * P).reshape((K, P), order="F")
+    pi = _np.ascontiguousarray(pi, dtype=_np.float64)
+    th = _np.asfortranarray(th, dtype=_np.float64)
+    if pi.shape != (K,) or th.shape != (K, P):
+        raise ValueError("initial_pi must have K entries and initial_theta be K x P")
+    return pi, th
+
+
+def _run_args(spec, X, start, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, device, pi, z, theta, al):
+    """the arguments the three entry points of a sampler share, as include/bmm_mcmc.h orders them; z: None for a run
+    that keeps no label trace"""
+    data = (_capi.vp(X), _C.c_int64(X.shape[0]), _C.c_int(X.shape[1]))
+    n, k, burn, bt = _C.c_int(nsamples), _C.c_int(K), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch)
+    hyper = (_C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma), _C.c_double(a), _C.c_double(b))
+    where = (_C.c_uint64(seed), _C.c_int(device))
+    out = (_vp0(z), _capi.vp(theta), _capi.vp(al))
+    if spec.base == "collapsed":
+        return data + (_capi.vp(start), n, k) + hyper + (burn, bt) + where + out
+    if spec.base == "dp":
+        return data + (n,) + hyper + (burn, k, bt) + where + out
+    return data + (_capi.vp(start[0]), _capi.vp(start[1]), n, k) + hyper + (burn,) + where + (_capi.vp(pi),) + out
+
+
+def _gibbs(spec, data, nsamples, K, *, alpha, beta, gamma, a, b, burnin, relabel, burnrelabel, debug, seed, device, chains,
+           devices, stephens, newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo,
+           ecr_pivot, ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed,
+           summary, summary_pivot, summary_stride, keep_trace, partition_search, newdata_missing, batch=None, initial_K=None,
+           initial_pi=None, initial_theta=None, init="random", init_iters=INIT_ITERS, select_features=False, rho=0.5,
+           split_merge=0, split_merge_scans=None, temper=None, swap_every=1, temper_hottest=0.1):
+    """The run behind gibbs_collapsed, gibbs_dp, gibbs_stickbreaking and gibbs_full (K: K or maxK): the keywords parsed
+    into the run's options and refused where they do not go together, several chains handed to the multi-chain call and
+    pooled, or one run with its options armed (_run) and what they hold collected into the result.  An option a sampler
+    does not offer is one its wrapper does not pass: the defaults here mean off."""
+    data, cells = _take_missing(data, missing)
+    X = _capi.as_x(data)
+    N, P = X.shape
+    mi = None if cells is None else _Missing(cells[0], cells[1], N, P)
+    nsamples, K = int(nsamples), int(K)
+    cs = _take_constraints(known, allowed, N, K, sets=spec.sets)
+    ik = _init_kind(init, init_iters)
+    if ik is not None and initial_K is not None:
+        raise ValueError('init="kmodes" computes the starting labels: not together with initial_K')
+    ini = None if ik is None else _Init(*ik)
+    burnin = _burnin(burnin, nsamples)
+    seed = _seed(seed)
+    chains = int(chains)
+    S = nsamples - burnin
+    with_pi = spec.start == "params"
+    relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
+    pr = None if newdata is None else _Predict(newdata, P, S, K + spec.new_column, predictive_trace, responsibilities, chains,
+                                               newdata_missing, burnin)
+    pt = _make_partition(partition, partition_stride, similarity_of, N, S, chains)
+    ps = _make_search(partition_search, partition, N, K, chains)
+    features = (select_features, rho, P, S, chains, beta, gamma, spec is _DP, newdata, loo, split_merge)
+    if spec is _COLLAPSED:  # (whose refusals of select_features= have always come ahead of those of loo=; gibbs_dp: behind them)
+        fs = _make_features(*features)
+    lo = _make_loo(loo, N, S, chains, spec.waic)
+    if spec is not _COLLAPSED:
+        fs = _make_features(*features)
+    sm = _make_split_merge(split_merge, split_merge_scans, chains)
+    lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, S, chains, K, device)
+    pc = _make_pair_check(pair_check, pair_check_stride, pair_check_trace, P, S, chains)
+    tp = _make_temper(temper, swap_every, S, chains, temper_hottest)
+    su = _make_summary(summary, summary_pivot, summary_stride, keep_trace, N, K, P, S, chains,
+                       bool(relabel) or ecr_req is not None, partition, similarity_of)
+    if chains > 1:
+        _arm((mi, cs))  # (the run of several chains answers them)
+        if relabel:
+            raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
+        z0s = pi0s = th0s = None
+        infos = []
+        if ini is not None:
+            initial_K = []
+            for c in range(chains):
+                with Chain("collapsed", N, P, K, alpha=alpha, beta=beta, gamma=gamma, a=a, b=b, seed=seed + c, device=0) as ch:
+                    ch.set_data(X)
+                    info = ch.init_labels("kmodes", iters=ik[1])
+                    infos.append({k: info[k] for k in ("k_eff", "rounds_run", "changed_last", "cost", "device_ms")})
+                    initial_K.append(ch.labels())
+        if spec.start == "labels":
+            z0s = [_np.ascontiguousarray(_np.random.default_rng(seed + c).integers(1, K + 1, N), dtype=_np.int32)
+                   for c in range(chains)] if initial_K is None else [_np.ascontiguousarray(z, dtype=_np.int32) for z in initial_K]
+        elif with_pi:
+            st = [_start_params(seed + c, initial_pi[c] if initial_pi is not None else None,
+                                initial_theta[c] if initial_theta is not None else None, K, P) for c in range(chains)]
+            pi0s, th0s = [p for p, _ in st], [t for _, t in st]
+        dev0 = device if devices is None else int(devices[0])
+        outs = _multi(spec.name, X, chains, devices, z0s, pi0s, th0s, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, with_pi)
+        if lp is not None:
+            _lp_chains(outs, X, spec.name, K, alpha, beta, gamma, a, b, dev0)
+        outs = _ecr_chains(_pooled_search(_pooled(outs, partition, partition_stride, similarity_of, dev0), ps, partition, K, dev0), ecr_req, K, dev0)
+        if ecr_map is not None:
+            outs = _ecr_map(outs, ecr_map, K, dev0)
+        for o, info in zip(outs, infos):
+            o["init"] = info
+        return outs
+    start = None
+    if spec.start == "labels":
+        if initial_K is None:
+            initial_K = _np.random.default_rng(seed).integers(1, K + 1, N)
+        start = _np.ascontiguousarray(initial_K, dtype=_np.int32)
+        if start.shape != (N,):
+            raise ValueError("initial_K must have one label per observation")
+    W = _clamp_burnrelabel(burnrelabel, burnin) if spec.clamp else int(burnrelabel)
+    on_device = _device_relabel(stephens, relabel, burnin, W)
+    if with_pi:
+        start = _start_params(seed, initial_pi, initial_theta, K, P)
+    if on_device:
+        rel = _DeviceRelabelRun(N, K, P, S, W)
+    else:
+        rel = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
+    ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
+    z = _z_trace(S, N, su)
+    theta = _np.zeros((K, P, S), order="F")
+    al = _np.zeros((S, 1), order="F")
+    pi = _np.zeros((S, K), order="F") if with_pi else None
+    args = _run_args(spec, X, start, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, device, pi, z, theta, al)
+    with _progress(debug):
+        rc = _run(spec.base, args, (sm, fs, pt, ps, lo, ec, lp, tp, pc, mi, cs, su, ini), pr,
+                  hooks=None if on_device else rel, rel=rel if on_device else None)
+    out = {"alpha": al, "permutations": None if on_device else _na_perm(S, K), "z": z, "theta": theta}
+    if with_pi:
+        out = {"pi": pi, **out}
+    if rel is not None:
+        out = rel.finish(rc, out)
+    else:
+        _capi.check(rc)
+    return _collect(out, (ec, pr, pt, lo, su, ps, tp, sm, fs, ini, lp, pc, mi, cs))
+
+
 def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
                     relabel=False, burnrelabel=50, debug=False, *, seed=None, batch=None, device=0,
                     initial_K=None, chains=1, devices=None, stephens=None, newdata=None, predictive_trace=False,
@@ -1918,103 +2028,16 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
     it, and `ecr_pivot="partition"` goes on using the visited sweep.  At most 64 categories.  With `chains > 1` the search
     runs once over the pooled traces from the pooled estimate.
     """
-    data, cells = _take_missing(data, missing)
-    X = _capi.as_x(data)
-    N, P = X.shape
-    mi = None if cells is None else _Missing(cells[0], cells[1], N, P)
-    nsamples, K = int(nsamples), int(K)
-    cs = _take_constraints(known, allowed, N, K)
-    ik = _init_kind(init, init_iters)
-    if ik is not None and initial_K is not None:
-        raise ValueError('init="kmodes" computes the starting labels: not together with initial_K')
-    ini = None if ik is None else _Init(*ik)
-    burnin = _burnin(burnin, nsamples)
-    seed = _seed(seed)
-    chains = int(chains)
-    relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
-    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains, newdata_missing, burnin)
-    pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
-    ps = _make_search(partition_search, partition, N, K, chains)
-    fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, False, newdata, loo)
-    lo = _make_loo(loo, N, nsamples - burnin, chains, False)
-    lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
-    pc = _make_pair_check(pair_check, pair_check_stride, pair_check_trace, P, nsamples - burnin, chains)
-    tp = _make_temper(temper, swap_every, nsamples - burnin, chains, temper_hottest)
-    su = _make_summary(summary, summary_pivot, summary_stride, keep_trace, N, K, P, nsamples - burnin, chains,
-                       bool(relabel) or ecr_req is not None, partition, similarity_of)
-
-    def done(out):
-        out = _with_search(_with_summary(out, su), ps)
-        if tp is not None:
-            out["temper"] = tp.result()
-        if fs is not None:
-            out["features"] = fs.result()
-        if ini is not None:
-            out["init"] = ini.result()
-        return _with_constraints(_with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc), mi), cs)
-    if chains > 1:
-        if mi is not None:
-            mi.arm()  # (the run of several chains answers it)
-        if cs is not None:
-            cs.arm()
-        if relabel:
-            raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
-        if ini is not None:
-            initial_K, infos = [], []
-            for c in range(chains):
-                with Chain("collapsed", N, P, K, alpha=alpha, beta=beta, gamma=gamma, a=a, b=b, seed=seed + c, device=0) as ch:
-                    ch.set_data(X)
-                    info = ch.init_labels("kmodes", iters=ik[1])
-                    infos.append({k: info[k] for k in ("k_eff", "rounds_run", "changed_last", "cost", "device_ms")})
-                    initial_K.append(ch.labels())
-        z0s = [_np.ascontiguousarray(_np.random.default_rng(seed + c).integers(1, K + 1, N), dtype=_np.int32)
-               for c in range(chains)] if initial_K is None else [_np.ascontiguousarray(z, dtype=_np.int32) for z in initial_K]
-        dev0 = device if devices is None else int(devices[0])
-        outs = _multi("collapsed", X, chains, devices, z0s, None, None, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, False)
-        if lp is not None:
-            _lp_chains(outs, X, "collapsed", K, alpha, beta, gamma, a, b, dev0)
-        outs = _ecr_chains(_pooled_search(_pooled(outs, partition, partition_stride, similarity_of, dev0), ps, partition, K, dev0), ecr_req, K, dev0)
-        if ecr_map is not None:
-            outs = _ecr_map(outs, ecr_map, K, dev0)
-        if ini is not None:
-            for o, info in zip(outs, infos):
-                o["init"] = info
-        return outs
-    if initial_K is None:
-        initial_K = _np.random.default_rng(seed).integers(1, K + 1, N)
-    z0 = _np.ascontiguousarray(initial_K, dtype=_np.int32)
-    if z0.shape != (N,):
-        raise ValueError("initial_K must have one label per observation")
-    S = nsamples - burnin
-    W = _clamp_burnrelabel(burnrelabel, burnin)
-    if _device_relabel(stephens, relabel, burnin, W):
-        dr = _DeviceRelabelRun(N, K, P, S, W)
-        z = _np.empty((S, N), dtype=_np.int32, order="F")
-        theta = _np.zeros((K, P, S), order="F")
-        al = _np.zeros((S, 1), order="F")
-        args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(K),
-                _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
-                _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
-                _C.c_uint64(seed), _C.c_int(device), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
-        with _progress(debug):
-            rc = _run("collapsed", args, pr, rel=dr, part=pt, ps=ps, loo=lo, fs=fs, init=ini, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
-        return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
-    rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
-    ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
-    z = _z_trace(S, N, su)
-    theta = _np.zeros((K, P, S), order="F")
-    al = _np.zeros((S, 1), order="F")
-    args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(K),
-            _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
-            _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int64(0 if batch is None else batch),
-            _C.c_uint64(seed), _C.c_int(device), _vp0(z), _capi.vp(theta), _capi.vp(al))
-    with _progress(debug):
-        rc = _run("collapsed", args, pr, hooks=rl, part=pt, ps=ps, loo=lo, fs=fs, init=ini, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs, su=su)
-    out = {"alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
-    if rl:
-        return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
-    _capi.check(rc)
-    return done(_with_predictive(out if ec is None else ec.finish(out), pr, pt, lo))
+    return _gibbs(_COLLAPSED, data, nsamples, K, alpha=alpha, beta=beta, gamma=gamma, a=a, b=b, burnin=burnin, relabel=relabel,
+                  burnrelabel=burnrelabel, debug=debug, seed=seed, batch=batch, device=device, initial_K=initial_K, chains=chains,
+                  devices=devices, stephens=stephens, newdata=newdata, predictive_trace=predictive_trace,
+                  responsibilities=responsibilities, partition=partition, partition_stride=partition_stride,
+                  similarity_of=similarity_of, loo=loo, select_features=select_features, rho=rho, init=init, init_iters=init_iters,
+                  ecr_pivot=ecr_pivot, ecr_max_iter=ecr_max_iter, logpost=logpost, temper=temper, swap_every=swap_every,
+                  temper_hottest=temper_hottest, pair_check=pair_check, pair_check_stride=pair_check_stride,
+                  pair_check_trace=pair_check_trace, missing=missing, known=known, allowed=allowed, summary=summary,
+                  summary_pivot=summary_pivot, summary_stride=summary_stride, keep_trace=keep_trace,
+                  partition_search=partition_search, newdata_missing=newdata_missing)
 
 
 def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=None, relabel=False,
@@ -2045,176 +2068,16 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
     `summary_pivot`, `summary_stride`, `keep_trace`: as gibbs_collapsed, over the maxK labels.  `partition_search`: as
     gibbs_collapsed (maxK <= 64)."""
     _init_kind(init, 0, allowed=False)
-    data, cells = _take_missing(data, missing)
-    X = _capi.as_x(data)
-    N, P = X.shape
-    mi = None if cells is None else _Missing(cells[0], cells[1], N, P)
-    nsamples, maxK = int(nsamples), int(maxK)
-    cs = _take_constraints(known, allowed, N, maxK, sets=False)
-    burnin = _burnin(burnin, nsamples)
-    seed = _seed(seed)
-    relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
-    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, maxK + 1, predictive_trace, responsibilities, chains, newdata_missing, burnin)
-    pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
-    ps = _make_search(partition_search, partition, N, maxK, chains)
-    lo = _make_loo(loo, N, nsamples - burnin, chains, False)
-    fs = _make_features(select_features, rho, P, nsamples - burnin, chains, beta, gamma, True, newdata, loo, split_merge)
-    sm = _make_split_merge(split_merge, split_merge_scans, chains)
-    lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
-    pc = _make_pair_check(pair_check, pair_check_stride, pair_check_trace, P, nsamples - burnin, chains)
-    tp = _make_temper(temper, swap_every, nsamples - burnin, chains, temper_hottest)
-    su = _make_summary(summary, summary_pivot, summary_stride, keep_trace, N, maxK, P, nsamples - burnin, chains,
-                       bool(relabel) or ecr_req is not None, partition, similarity_of)
-
-    def done(out):
-        out = _with_search(_with_summary(out, su), ps)
-        if tp is not None:
-            out["temper"] = tp.result()
-        if sm is not None:
-            out["split_merge"] = sm.result()
-        if fs is not None:
-            out["features"] = fs.result()
-        return _with_constraints(_with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, maxK, device), pc), mi), cs)
-    if int(chains) > 1:
-        if mi is not None:
-            mi.arm()  # (the run of several chains answers it)
-        if cs is not None:
-            cs.arm()
-        if relabel:
-            raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
-        dev0 = device if devices is None else int(devices[0])
-        outs = _multi("dp", X, int(chains), devices, None, None, None, nsamples, maxK, alpha, beta, gamma, a, b, burnin, batch, seed, False)
-        if lp is not None:
-            _lp_chains(outs, X, "dp", maxK, alpha, beta, gamma, a, b, dev0)
-        outs = _ecr_chains(_pooled_search(_pooled(outs, partition, partition_stride, similarity_of, dev0), ps, partition, maxK, dev0), ecr_req, maxK, dev0)
-        return outs if ecr_map is None else _ecr_map(outs, ecr_map, maxK, dev0)
-    S = nsamples - burnin
-    W = _clamp_burnrelabel(burnrelabel, burnin)
-    if _device_relabel(stephens, relabel, burnin, W):
-        dr = _DeviceRelabelRun(N, maxK, P, S, W)
-        z = _np.empty((S, N), dtype=_np.int32, order="F")
-        theta = _np.zeros((maxK, P, S), order="F")
-        al = _np.zeros((S, 1), order="F")
-        args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(nsamples),
-                _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
-                _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int(maxK),
-                _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _capi.vp(z),
-                _capi.vp(theta), _capi.vp(al))
-        with _progress(debug):
-            rc = _run("dp", args, pr, rel=dr, part=pt, ps=ps, loo=lo, sm=sm, fs=fs, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs)
-        return done(_with_predictive(dr.finish(rc, {"alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
-    rl = _Relabel(stephens, N, maxK, nsamples, burnin, W) if relabel else None
-    ec = None if ecr_req is None else _Ecr(ecr_req, N, maxK, P, S)
-    z = _z_trace(S, N, su)
-    theta = _np.zeros((maxK, P, S), order="F")
-    al = _np.zeros((S, 1), order="F")
-    args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(nsamples),
-            _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma),
-            _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_int(maxK),
-            _C.c_int64(0 if batch is None else batch), _C.c_uint64(seed), _C.c_int(device), _vp0(z),
-            _capi.vp(theta), _capi.vp(al))
-    with _progress(debug):
-        rc = _run("dp", args, pr, hooks=rl, part=pt, ps=ps, loo=lo, sm=sm, fs=fs, ecr=ec, lp=lp, tp=tp, pc=pc, mi=mi, cs=cs, su=su)
-    out = {"alpha": al, "permutations": _na_perm(S, maxK), "z": z, "theta": theta}
-    if rl:
-        return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
-    _capi.check(rc)
-    return done(_with_predictive(out if ec is None else ec.finish(out), pr, pt, lo))
-
-
-def _explicit(sampler, fn, clamp, data, nsamples, K, alpha, beta, gamma, a, b, burnin, relabel, burnrelabel, seed,
-              device, initial_pi, initial_theta, chains, devices, stephens, debug=False, newdata=None,
-              predictive_trace=False, responsibilities=False, partition=None, partition_stride=1, similarity_of=None,
-              loo=False, ecr_pivot="iterative", ecr_max_iter=50, logpost=False, pair_check=None, pair_check_stride=1,
-              pair_check_trace=False, missing=None, known=None, allowed=None, summary=None, summary_pivot="first",
-              summary_stride=1, keep_trace=True, partition_search=None, newdata_missing=None):
-    data, cells = _take_missing(data, missing)
-    X = _capi.as_x(data)
-    N, P = X.shape
-    mi = None if cells is None else _Missing(cells[0], cells[1], N, P)
-    nsamples, K = int(nsamples), int(K)
-    cs = _take_constraints(known, allowed, N, K, sets=sampler == "full")
-    burnin = _burnin(burnin, nsamples)
-    seed = _seed(seed)
-    chains = int(chains)
-    relabel, ecr_req = _ecr_request(relabel, stephens, ecr_pivot, ecr_max_iter, N, partition)
-    pr = None if newdata is None else _Predict(newdata, P, nsamples - burnin, K, predictive_trace, responsibilities, chains, newdata_missing, burnin)
-    pt = _make_partition(partition, partition_stride, similarity_of, N, nsamples - burnin, chains)
-    ps = _make_search(partition_search, partition, N, K, chains)
-    lo = _make_loo(loo, N, nsamples - burnin, chains, True)
-    lp, ecr_req, ecr_map = _logpost_request(logpost, ecr_req, N, nsamples - burnin, chains)
-    pc = _make_pair_check(pair_check, pair_check_stride, pair_check_trace, P, nsamples - burnin, chains)
-    base = fn[len("bmm_"):-len("_run_probs")]
-    su = _make_summary(summary, summary_pivot, summary_stride, keep_trace, N, K, P, nsamples - burnin, chains,
-                       bool(relabel) or ecr_req is not None, partition, similarity_of)
-
-    def done(out):
-        out = _with_search(_with_summary(out, su), ps)
-        return _with_constraints(_with_missing(_with_pair_check(_with_logpost(out, lp, ecr_map, K, device), pc), mi), cs)
-
-    def start(sd, pi, th):
-        rng = _np.random.default_rng(sd)
-        if pi is None:  # R/utils.R:68-70, 98-100
-            pi = _np.exp(rng.random(K))
-            pi = pi / pi.sum()
-        if th is None:  # R/utils.R:74, 103
-            th = rng.random(K * P).reshape((K, P), order="F")
-        pi = _np.ascontiguousarray(pi, dtype=_np.float64)
-        th = _np.asfortranarray(th, dtype=_np.float64)
-        if pi.shape != (K,) or th.shape != (K, P):
-            raise ValueError("initial_pi must have K entries and initial_theta be K x P")
-        return pi, th
-
-    S = nsamples - burnin
-    W = _clamp_burnrelabel(burnrelabel, burnin) if clamp else int(burnrelabel)  # R/utils.R:97-101 has no clamp
-    if chains > 1:
-        if mi is not None:
-            mi.arm()  # (the run of several chains answers it)
-        if cs is not None:
-            cs.arm()
-        if relabel:
-            raise NotImplementedError("relabel=TRUE is offered per chain (chains=1)")
-        st = [start(seed + c, initial_pi[c] if initial_pi is not None else None,
-                    initial_theta[c] if initial_theta is not None else None) for c in range(chains)]
-        dev0 = device if devices is None else int(devices[0])
-        outs = _multi(sampler, X, chains, devices, None, [p for p, _ in st], [t for _, t in st], nsamples, K, alpha, beta, gamma, a, b,
-                      burnin, None, seed, True)
-        if lp is not None:
-            _lp_chains(outs, X, sampler, K, alpha, beta, gamma, a, b, dev0)
-        outs = _ecr_chains(_pooled_search(_pooled(outs, partition, partition_stride, similarity_of, dev0), ps, partition, K, dev0), ecr_req, K, dev0)
-        return outs if ecr_map is None else _ecr_map(outs, ecr_map, K, dev0)
-    on_device = _device_relabel(stephens, relabel, burnin, W)
-    pi0, th0 = start(seed, initial_pi, initial_theta)
-    if on_device:
-        dr = _DeviceRelabelRun(N, K, P, S, W)
-        z = _np.empty((S, N), dtype=_np.int32, order="F")
-        theta = _np.zeros((K, P, S), order="F")
-        al = _np.zeros((S, 1), order="F")
-        pi = _np.zeros((S, K), order="F")
-        args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(pi0), _capi.vp(th0), _C.c_int(nsamples),
-                _C.c_int(K), _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta),
-                _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
-                _C.c_int(device), _capi.vp(pi), _capi.vp(z), _capi.vp(theta), _capi.vp(al))
-        with _progress(debug):
-            rc = _run(base, args, pr, rel=dr, part=pt, ps=ps, loo=lo, lp=lp, pc=pc, mi=mi, cs=cs)
-        return done(_with_predictive(dr.finish(rc, {"pi": pi, "alpha": al, "permutations": None, "z": z, "theta": theta}), pr, pt, lo))
-    rl = _Relabel(stephens, N, K, nsamples, burnin, W) if relabel else None
-    ec = None if ecr_req is None else _Ecr(ecr_req, N, K, P, S)
-    z = _z_trace(S, N, su)
-    theta = _np.zeros((K, P, S), order="F")
-    al = _np.zeros((S, 1), order="F")
-    pi = _np.zeros((S, K), order="F")
-    args = (_capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(pi0), _capi.vp(th0), _C.c_int(nsamples),
-            _C.c_int(K), _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta),
-            _C.c_double(gamma), _C.c_double(a), _C.c_double(b), _C.c_int(burnin), _C.c_uint64(seed),
-            _C.c_int(device), _capi.vp(pi), _vp0(z), _capi.vp(theta), _capi.vp(al))
-    with _progress(debug):
-        rc = _run(base, args, pr, hooks=rl, part=pt, ps=ps, loo=lo, ecr=ec, lp=lp, pc=pc, mi=mi, cs=cs, su=su)
-    out = {"pi": pi, "alpha": al, "permutations": _na_perm(S, K), "z": z, "theta": theta}
-    if rl:
-        return done(_with_predictive(rl.finish(rc, out), pr, pt, lo))
-    _capi.check(rc)
-    return done(_with_predictive(out if ec is None else ec.finish(out), pr, pt, lo))
+    return _gibbs(_DP, data, nsamples, maxK, alpha=alpha, beta=beta, gamma=gamma, a=a, b=b, burnin=burnin, relabel=relabel,
+                  burnrelabel=burnrelabel, debug=debug, seed=seed, batch=batch, device=device, chains=chains, devices=devices,
+                  stephens=stephens, newdata=newdata, predictive_trace=predictive_trace, responsibilities=responsibilities,
+                  partition=partition, partition_stride=partition_stride, similarity_of=similarity_of, loo=loo,
+                  split_merge=split_merge, split_merge_scans=split_merge_scans, select_features=select_features, rho=rho,
+                  ecr_pivot=ecr_pivot, ecr_max_iter=ecr_max_iter, logpost=logpost, temper=temper, swap_every=swap_every,
+                  temper_hottest=temper_hottest, pair_check=pair_check, pair_check_stride=pair_check_stride,
+                  pair_check_trace=pair_check_trace, missing=missing, known=known, allowed=allowed, summary=summary,
+                  summary_pivot=summary_pivot, summary_stride=summary_stride, keep_trace=keep_trace,
+                  partition_search=partition_search, newdata_missing=newdata_missing)
 
 
 def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
@@ -2237,11 +2100,15 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
     the theta the sweep has just drawn.  `known`, `allowed`: as gibbs_dp (the values name the chain's labels 1..maxK; allowed= is refused).
     `partition_search`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
-    return _explicit("stickbreaking", "bmm_sb_run_probs", False, data, nsamples, maxK, alpha, beta, gamma, a, b,
-                     burnin, relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
-                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed,
-                     summary, summary_pivot, summary_stride, keep_trace, partition_search, newdata_missing)
+    return _gibbs(_STICKBREAKING, data, nsamples, maxK, alpha=alpha, beta=beta, gamma=gamma, a=a, b=b, burnin=burnin, relabel=relabel,
+                  burnrelabel=burnrelabel, debug=debug, seed=seed, device=device, initial_pi=initial_pi,
+                  initial_theta=initial_theta, chains=chains, devices=devices, stephens=stephens, newdata=newdata,
+                  predictive_trace=predictive_trace, responsibilities=responsibilities, partition=partition,
+                  partition_stride=partition_stride, similarity_of=similarity_of, loo=loo, ecr_pivot=ecr_pivot,
+                  ecr_max_iter=ecr_max_iter, logpost=logpost, pair_check=pair_check, pair_check_stride=pair_check_stride,
+                  pair_check_trace=pair_check_trace, missing=missing, known=known, allowed=allowed, summary=summary,
+                  summary_pivot=summary_pivot, summary_stride=summary_stride, keep_trace=keep_trace,
+                  partition_search=partition_search, newdata_missing=newdata_missing)
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
@@ -2259,11 +2126,15 @@ def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, bur
     `pair_check_stride`, `pair_check_trace`, `missing`, `known`, `allowed`, `summary`, `summary_pivot`, `summary_stride`,
     `keep_trace`, `partition_search`: as gibbs_collapsed."""
     _init_kind(init, 0, allowed=False)
-    return _explicit("full", "bmm_full_run_probs", True, data, nsamples, K, alpha, beta, gamma, a, b, burnin,
-                     relabel, burnrelabel, seed, device, initial_pi, initial_theta, chains, devices, stephens, debug,
-                     newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo, ecr_pivot,
-                     ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed,
-                     summary, summary_pivot, summary_stride, keep_trace, partition_search, newdata_missing)
+    return _gibbs(_FULL, data, nsamples, K, alpha=alpha, beta=beta, gamma=gamma, a=a, b=b, burnin=burnin, relabel=relabel,
+                  burnrelabel=burnrelabel, debug=debug, seed=seed, device=device, initial_pi=initial_pi,
+                  initial_theta=initial_theta, chains=chains, devices=devices, stephens=stephens, newdata=newdata,
+                  predictive_trace=predictive_trace, responsibilities=responsibilities, partition=partition,
+                  partition_stride=partition_stride, similarity_of=similarity_of, loo=loo, ecr_pivot=ecr_pivot,
+                  ecr_max_iter=ecr_max_iter, logpost=logpost, pair_check=pair_check, pair_check_stride=pair_check_stride,
+                  pair_check_trace=pair_check_trace, missing=missing, known=known, allowed=allowed, summary=summary,
+                  summary_pivot=summary_pivot, summary_stride=summary_stride, keep_trace=keep_trace,
+                  partition_search=partition_search, newdata_missing=newdata_missing)
 
 
 class Chain:
