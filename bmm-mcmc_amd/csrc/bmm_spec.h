@@ -695,9 +695,9 @@ BMM_HD double group_entry(const double* e1, const double* e0, int g, int P, unsi
 // The log terms of a counting chain's table image -- which category scores, the argument of each log_ and when it is
 // needed -- for the three builds that call these functions: build_tables_self (BUILD_SELF) and
 // k_state_tables (BUILD_PREDICT, BUILD_LOO).  A builder takes the raw log_ of every argument that is needed and
-// subtracts the denominators afterwards (term_of, cat_consts).  The sweep's own launches, k_count_tables and
-// k_alloc_tables, are NOT among the callers: they keep bodies of their own (kernels.hip.h says why), and whoever
-// changes a rule of the finite sweep changes it there and here.
+// subtracts the denominators afterwards (term_of, cat_consts).  The sweep's own launch, k_count_tables in its four
+// flavours, is NOT among the callers: it keeps a body of its own (kernels.hip.h says why), and whoever changes a rule
+// of the finite sweep changes it there and here.
 //   BUILD_SELF     the finite sampler's z-step image as k_count_tables writes it: a label scores when it holds a row,
 //                  the scored row's own label from the minus-self set when it holds another; denominator log(N - 1 + alpha)
 //   BUILD_PREDICT  a new row against a stored state: no minus-self set, denominator log(N + alpha); the finite sampler's

@@ -656,7 +656,7 @@ struct bmm_chain {
     std::vector<uint32_t> init_centres;
     std::vector<long long> init_rows;
     std::vector<int32_t> init_nk;
-    // the allocation sampler: alloc_on: the table builds are k_alloc_tables, reading the open
+    // the allocation sampler: alloc_on: the table builds are k_count_tables<TAB_ALLOC>, reading the open
     // label count dEaK, and (for good) the kernel choice leaves out the forms that build their own tables; alloc_moves
     // > 0: that many eject / absorb moves at the start of every sweep from the second.  One block holds K, log p(K),
     // the moved rows' statistics, the move's cell and the four counters; the side bytes are a block of their own.
@@ -748,7 +748,7 @@ struct bmm_chain {
     SumBufs sum;
     EcrWork* sum_ecr = nullptr;
     SweepTrace sum_rec;
-    // parallel tempering: temper_on: the table builds are k_temper_tables at inverse temperature
+    // parallel tempering: temper_on: the table builds are k_count_tables<TAB_TEMPER> at inverse temperature
     // temper_b, and the kernel choice leaves out the forms that build their own tables and the packed one; ladder: the
     // replica ladder a run drives this chain through as its rung 0 (not owned)
     bool temper_on = false;
@@ -1344,18 +1344,18 @@ int launch_reduce_deltas(bmm_chain* c) {
 }
 
 int launch_count_tables(bmm_chain* c) {
+    auto launch = [c](auto kernel, const uint32_t* mask, int packed, auto... extra) {
+        hipLaunchKernelGGL(kernel, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS, c->dDNk, c->dDS,
+                           (const double*)c->dAlpha, c->dTab, mask, packed, extra...);
+    };
     if (c->alloc_on)  // the allocation sampler: open empty labels keep their prior weight
-        hipLaunchKernelGGL(k_alloc_tables, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
-                           c->dDNk, c->dDS, (const int32_t*)c->dEaK, c->alloc_a, c->dTab);
+        launch(k_count_tables<TAB_ALLOC, const int32_t*, double>, nullptr, 0, (const int32_t*)c->dEaK, c->alloc_a);
     else if (c->temper_on)  // a tempered chain: every per-feature term times its inverse temperature
-        hipLaunchKernelGGL(k_temper_tables, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
-                           c->dDNk, c->dDS, (const double*)c->dAlpha, c->temper_b, c->dTab);
+        launch(k_count_tables<TAB_TEMPER, double>, nullptr, 0, c->temper_b);
     else if (c->fs_mask)  // feature selection: excluded features are written as zeros
-        hipLaunchKernelGGL(k_count_tables<true>, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
-                           c->dDNk, c->dDS, c->dAlpha, c->dTab, (const uint32_t*)c->dFsMask, 0);
+        launch(k_count_tables<TAB_MASK>, (const uint32_t*)c->dFsMask, 0);
     else
-        hipLaunchKernelGGL(k_count_tables<false>, dim3(c->p.KT), dim3(kCountTablesThreads), 0, c->stream, c->p, c->dNk, c->dS,
-                           c->dDNk, c->dDS, c->dAlpha, c->dTab, (const uint32_t*)nullptr, c->form.pk && !c->generic ? 1 : 0);
+        launch(k_count_tables<TAB_PLAIN>, nullptr, c->form.pk && !c->generic ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return BMM_OK;
 }
@@ -1621,29 +1621,71 @@ int sm_setup(bmm_chain* c, int scans) {
     c->sm_scans = scans;
     return BMM_OK;
 }
-// one move on label row `z`, ahead of sweep `tag`, enqueued on the stream
+// one move on label row `z`, ahead of sweep `tag`, enqueued on the stream: the DP chain's, or (ALLOC) the allocation
+// chain's, which has its own numbering, scans, cell and counters and shares the side bytes and the statistic sets
+template <bool ALLOC>
 int enqueue_move(bmm_chain* c, int32_t* z, int tag, bool keep_launch) {
     const ChainParams& p = c->p;
-    if (c->sm_tag != tag) { c->sm_tag = tag; c->sm_ctr = 0; }
-    SmArgs a{};
+    int& last_tag = ALLOC ? c->as_tag : c->sm_tag;
+    uint32_t& ctr = ALLOC ? c->as_ctr : c->sm_ctr;
+    const int scans = ALLOC ? c->as_scans : c->sm_scans;
+    if (last_tag != tag) { last_tag = tag; ctr = 0; }
+    SmArgsOf<ALLOC> g{};
+    SmArgs& a = g;
     a.Xb = c->dXb; a.z = z; a.Nk = c->dNk; a.S = c->dS; a.alpha_ptr = c->dAlpha;
     a.side = c->dSmSide; a.side_launch = keep_launch ? c->dSmSideLaunch : nullptr; a.lq = c->dSmLq;
-    a.stat = c->dSmStat; a.cell = c->dSmCell; a.counters = c->dSmCounters;
-    a.sweep = (uint32_t)tag; a.move = c->sm_ctr++; a.scans = c->sm_scans;
+    a.stat = c->dSmStat; a.sweep = (uint32_t)tag; a.move = ctr++; a.scans = scans;
+    if constexpr (ALLOC) {
+        a.cell = &c->dAsCell->m; a.counters = c->dAsCounters;
+        g.K = c->dEaK; g.log_prior_k = c->dEaLogPrior; g.as_cell = c->dAsCell; g.a = c->alloc_a;
+    } else {
+        a.cell = c->dSmCell; a.counters = c->dSmCounters;
+    }
     const size_t set_bytes = (size_t)2 * (p.P + 1) * sizeof(int32_t);
-    HIP_TRY(hipMemsetAsync(c->dSmStat, 0, (size_t)(c->sm_scans + 2) * set_bytes, c->stream));
+    HIP_TRY(hipMemsetAsync(c->dSmStat, 0, (size_t)(scans + 2) * set_bytes, c->stream));
     const unsigned grid = (unsigned)((p.N + kSmThreads - 1) / kSmThreads);
-    hipLaunchKernelGGL(k_sm_launch, dim3(grid), dim3(kSmThreads), set_bytes, c->stream, p, a);
+    hipLaunchKernelGGL(k_sm_launch<ALLOC>, dim3(grid), dim3(kSmThreads), set_bytes, c->stream, p, g);
     HIP_TRY(hipGetLastError());
     const size_t scan_lds = (size_t)4 * p.P * sizeof(double) + set_bytes;
-    for (int t = 1; t <= c->sm_scans + 1; ++t) {
-        hipLaunchKernelGGL(k_sm_scan, dim3(grid), dim3(kSmThreads), scan_lds, c->stream, p, a, t, t == c->sm_scans + 1 ? 1 : 0);
+    for (int t = 1; t <= scans + 1; ++t) {
+        hipLaunchKernelGGL(k_sm_scan<ALLOC>, dim3(grid), dim3(kSmThreads), scan_lds, c->stream, p, g, t, t == scans + 1 ? 1 : 0);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_sm_decide, dim3(1), dim3(1024), 0, c->stream, p, a);
+    hipLaunchKernelGGL(k_sm_decide<ALLOC>, dim3(1), dim3(1024), 0, c->stream, p, g);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sm_commit, dim3(grid), dim3(kSmThreads), 0, c->stream, p, a);
+    hipLaunchKernelGGL(k_sm_commit<ALLOC>, dim3(grid), dim3(kSmThreads), 0, c->stream, p, g);
     HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+// what a step entry point returns of a move just synchronised: the DP move's part of the record (labels 1-based) and
+// the two side-byte arrays; `out` is bmm_split_merge_step or bmm_alloc_split_step
+template <class Step>
+int sm_step_out(bmm_chain* c, const SmCell& h, uint32_t move, Step* out) {
+    out->row_i = h.row_i; out->row_j = h.row_j; out->label_a = h.label_a + 1; out->label_b = h.label_b + 1;
+    out->kind = h.kind; out->accepted = h.accepted; out->members = h.members;
+    for (int q = 0; q < 2; ++q) { out->n_before[q] = h.n_before[q]; out->n_after[q] = h.n_after[q]; }
+    out->log_prior = h.log_prior; out->log_lik = h.log_lik; out->log_q = h.log_q; out->log_u = h.log_u; out->log_r = h.log_r;
+    out->sweep = (uint32_t)(c->sweep + 1); out->move = move;
+    const size_t n = (size_t)c->p.N;
+    if (h.kind == SM_SKIPPED) {  // no launch state: every row outside
+        if (out->launch_side) std::memset(out->launch_side, 255, n);
+        if (out->proposal_side) std::memset(out->proposal_side, 255, n);
+        return BMM_OK;
+    }
+    if (out->launch_side) HIP_TRY(hipMemcpy(out->launch_side, c->dSmSideLaunch, n, hipMemcpyDeviceToHost));
+    if (out->proposal_side) HIP_TRY(hipMemcpy(out->proposal_side, c->dSmSide, n, hipMemcpyDeviceToHost));
+    return BMM_OK;
+}
+// the five counters of either kind of move, zeros before the first one
+int sm_counters_out(bmm_chain* c, const long long* counters, int64_t out[5]) {
+    if (!c || !out) return set_err(BMM_E_ARG, "null argument");
+    for (int q = 0; q < 5; ++q) out[q] = 0;
+    if (!counters) return BMM_OK;
+    int rc = bmm_chain_sync(c);
+    if (rc) return rc;
+    long long h[5];
+    HIP_TRY(hipMemcpy(h, counters, sizeof h, hipMemcpyDeviceToHost));
+    for (int q = 0; q < 5; ++q) out[q] = h[q];
     return BMM_OK;
 }
 
@@ -1667,34 +1709,6 @@ int enqueue_ea(bmm_chain* c, int32_t* z, int tag) {
     hipLaunchKernelGGL(k_ea_decide, dim3(1), dim3(1024), 0, c->stream, p, a);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_ea_commit, dim3(grid), dim3(kEaThreads), 0, c->stream, p, a);
-    HIP_TRY(hipGetLastError());
-    return BMM_OK;
-}
-
-// one split-merge move of the allocation chain on label row `z`, ahead of sweep `tag`, enqueued on the stream
-int enqueue_as(bmm_chain* c, int32_t* z, int tag, bool keep_launch) {
-    const ChainParams& p = c->p;
-    if (c->as_tag != tag) { c->as_tag = tag; c->as_ctr = 0; }
-    AsArgs g{};
-    SmArgs& a = g.s;
-    a.Xb = c->dXb; a.z = z; a.Nk = c->dNk; a.S = c->dS; a.alpha_ptr = c->dAlpha;
-    a.side = c->dSmSide; a.side_launch = keep_launch ? c->dSmSideLaunch : nullptr; a.lq = c->dSmLq;
-    a.stat = c->dSmStat; a.cell = &c->dAsCell->m; a.counters = c->dAsCounters;
-    a.sweep = (uint32_t)tag; a.move = c->as_ctr++; a.scans = c->as_scans;
-    g.K = c->dEaK; g.log_prior_k = c->dEaLogPrior; g.cell = c->dAsCell; g.a = c->alloc_a;
-    const size_t set_bytes = (size_t)2 * (p.P + 1) * sizeof(int32_t);
-    HIP_TRY(hipMemsetAsync(c->dSmStat, 0, (size_t)(c->as_scans + 2) * set_bytes, c->stream));
-    const unsigned grid = (unsigned)((p.N + kSmThreads - 1) / kSmThreads);
-    hipLaunchKernelGGL(k_as_launch, dim3(grid), dim3(kSmThreads), set_bytes, c->stream, p, g);
-    HIP_TRY(hipGetLastError());
-    const size_t scan_lds = (size_t)4 * p.P * sizeof(double) + set_bytes;
-    for (int t = 1; t <= c->as_scans + 1; ++t) {
-        hipLaunchKernelGGL(k_as_scan, dim3(grid), dim3(kSmThreads), scan_lds, c->stream, p, g, t, t == c->as_scans + 1 ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_as_decide, dim3(1), dim3(1024), 0, c->stream, p, g);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_as_commit, dim3(grid), dim3(kSmThreads), 0, c->stream, p, g);
     HIP_TRY(hipGetLastError());
     return BMM_OK;
 }
@@ -1939,9 +1953,9 @@ int enqueue_sweep(bmm_chain* c, int j, int phase = 0) {
         int rc = moves_row(c, j, &row);
         if (rc) return rc;
         zin = row;
-        for (int m = 0; m < n_sm && rc == BMM_OK; ++m) rc = enqueue_move(c, row, j, false);
+        for (int m = 0; m < n_sm && rc == BMM_OK; ++m) rc = enqueue_move<false>(c, row, j, false);
         for (int m = 0; m < n_ea && rc == BMM_OK; ++m) rc = enqueue_ea(c, row, j);
-        for (int m = 0; m < n_as && rc == BMM_OK; ++m) rc = enqueue_as(c, row, j, false);  // (the allocation chain's split-merge moves)
+        for (int m = 0; m < n_as && rc == BMM_OK; ++m) rc = enqueue_move<true>(c, row, j, false);  // (the allocation chain's split-merge moves)
         if (rc) return rc;
     }
     int64_t lo = 0;
@@ -2053,7 +2067,7 @@ KernelPlan plan_kernel(const ChainParams& p, bool bits, int minus, int64_t batch
     // shape is bound by launches then, and this drops k_count_tables from every batch (BASELINE config 2)
     f.self = true;
     const size_t lds = (lds_bytes_base + 7) / 8 * 8 + self_scratch_doubles(p.K, p.KT, p.P) * sizeof(double);  // scratch behind the image
-    // (not for a chain with a feature mask: build_tables_self knows no mask, k_count_tables<true> does)
+    // (not for a chain with a feature mask: build_tables_self knows no mask, k_count_tables<TAB_MASK> does)
     if (BMM_SELF_TABLES && bits && minus == 1 && !shares_device && self_tables_fit(p.mode, p.K, p.P, 256) && !d.noself &&
         !masked && instantiated(f, false) && lds <= kLdsMax)
         offer(f, lds);
@@ -3897,7 +3911,7 @@ int bmm_chain_split_merge(bmm_chain* c, int n) {
         if (rc) return rc;
         HIP_TRY(hipSetDevice(c->device));
         for (int t = 0; t < n; ++t) {
-            rc = enqueue_move(c, label_row(c, c->sweep), c->sweep + 1, false);
+            rc = enqueue_move<false>(c, label_row(c, c->sweep), c->sweep + 1, false);
             if (rc) return rc;
         }
         return BMM_OK;
@@ -3910,39 +3924,18 @@ int bmm_chain_split_merge_step(bmm_chain* c, bmm_split_merge_step* out) {
         int rc = sm_ready(c);
         if (rc) return rc;
         HIP_TRY(hipSetDevice(c->device));
-        rc = enqueue_move(c, label_row(c, c->sweep), c->sweep + 1, true);
+        rc = enqueue_move<false>(c, label_row(c, c->sweep), c->sweep + 1, true);
         if (rc) return rc;
         rc = bmm_chain_sync(c);
         if (rc) return rc;
         SmCell h;
         HIP_TRY(hipMemcpy(&h, c->dSmCell, sizeof h, hipMemcpyDeviceToHost));
-        out->row_i = h.row_i; out->row_j = h.row_j; out->label_a = h.label_a + 1; out->label_b = h.label_b + 1;
-        out->kind = h.kind; out->accepted = h.accepted; out->members = h.members;
-        for (int q = 0; q < 2; ++q) { out->n_before[q] = h.n_before[q]; out->n_after[q] = h.n_after[q]; }
-        out->log_prior = h.log_prior; out->log_lik = h.log_lik; out->log_q = h.log_q; out->log_u = h.log_u; out->log_r = h.log_r;
-        out->sweep = (uint32_t)(c->sweep + 1); out->move = c->sm_ctr - 1;
-        const size_t n = (size_t)c->p.N;
-        if (h.kind == SM_SKIPPED) {  // no launch state: every row outside
-            if (out->launch_side) std::memset(out->launch_side, 255, n);
-            if (out->proposal_side) std::memset(out->proposal_side, 255, n);
-            return BMM_OK;
-        }
-        if (out->launch_side) HIP_TRY(hipMemcpy(out->launch_side, c->dSmSideLaunch, n, hipMemcpyDeviceToHost));
-        if (out->proposal_side) HIP_TRY(hipMemcpy(out->proposal_side, c->dSmSide, n, hipMemcpyDeviceToHost));
-        return BMM_OK;
+        return sm_step_out(c, h, c->sm_ctr - 1, out);
     });
 }
 
 int bmm_chain_split_merge_stats(bmm_chain* c, int64_t out[5]) {
-    if (!c || !out) return set_err(BMM_E_ARG, "null argument");
-    for (int q = 0; q < 5; ++q) out[q] = 0;
-    if (!c->dSmCounters) return BMM_OK;
-    int rc = bmm_chain_sync(c);
-    if (rc) return rc;
-    long long h[5];
-    HIP_TRY(hipMemcpy(h, c->dSmCounters, sizeof h, hipMemcpyDeviceToHost));
-    for (int q = 0; q < 5; ++q) out[q] = h[q];
-    return BMM_OK;
+    return sm_counters_out(c, c ? c->dSmCounters : nullptr, out);
 }
 
 // ... of a run: the moves armed for it (bmm_set_split_merge), and their counters for bmm_last_split_merge_stats
@@ -4226,7 +4219,7 @@ int bmm_chain_alloc_split_merge(bmm_chain* c, int n) {
         int rc = as_ready(c);
         if (rc) return rc;
         for (int t = 0; t < n; ++t) {
-            rc = enqueue_as(c, label_row(c, c->sweep), c->sweep + 1, false);
+            rc = enqueue_move<true>(c, label_row(c, c->sweep), c->sweep + 1, false);
             if (rc) return rc;
         }
         return BMM_OK;
@@ -4238,42 +4231,20 @@ int bmm_chain_alloc_split_merge_step(bmm_chain* c, bmm_alloc_split_step* out) {
         if (!out) return set_err(BMM_E_ARG, "null argument");
         int rc = as_ready(c);
         if (rc) return rc;
-        rc = enqueue_as(c, label_row(c, c->sweep), c->sweep + 1, true);
+        rc = enqueue_move<true>(c, label_row(c, c->sweep), c->sweep + 1, true);
         if (rc) return rc;
         rc = bmm_chain_sync(c);
         if (rc) return rc;
         AsCell h;
         HIP_TRY(hipMemcpy(&h, c->dAsCell, sizeof h, hipMemcpyDeviceToHost));
-        out->row_i = h.m.row_i; out->row_j = h.m.row_j; out->label_a = h.m.label_a + 1; out->label_b = h.m.label_b + 1;
-        out->kind = h.m.kind; out->accepted = h.m.accepted; out->k_before = h.k_before; out->k_after = h.k_after;
-        out->moved = h.moved < 0 ? -1 : h.moved + 1; out->pad = 0; out->members = h.m.members;
-        for (int q = 0; q < 2; ++q) { out->n_before[q] = h.m.n_before[q]; out->n_after[q] = h.m.n_after[q]; }
-        out->log_prior = h.m.log_prior; out->log_lik = h.m.log_lik; out->log_q = h.m.log_q; out->log_u = h.m.log_u; out->log_r = h.m.log_r;
-        out->sweep = (uint32_t)(c->sweep + 1); out->move = c->as_ctr - 1;
-        const size_t n = (size_t)c->p.N;
-        if (h.m.kind == SM_SKIPPED) {  // no launch state: every row outside
-            if (out->launch_side) std::memset(out->launch_side, 255, n);
-            if (out->proposal_side) std::memset(out->proposal_side, 255, n);
-            return BMM_OK;
-        }
-        if (out->launch_side) HIP_TRY(hipMemcpy(out->launch_side, c->dSmSideLaunch, n, hipMemcpyDeviceToHost));
-        if (out->proposal_side) HIP_TRY(hipMemcpy(out->proposal_side, c->dSmSide, n, hipMemcpyDeviceToHost));
-        return BMM_OK;
+        out->k_before = h.k_before; out->k_after = h.k_after;
+        out->moved = h.moved < 0 ? -1 : h.moved + 1; out->pad = 0;
+        return sm_step_out(c, h.m, c->as_ctr - 1, out);
     });
 }
 
 int bmm_chain_alloc_split_merge_stats(bmm_chain* c, int64_t out[5]) {
-    return guarded([&]() -> int {
-        if (!c || !out) return set_err(BMM_E_ARG, "null argument");
-        for (int q = 0; q < 5; ++q) out[q] = 0;
-        if (!c->dAsCounters) return BMM_OK;
-        int rc = bmm_chain_sync(c);
-        if (rc) return rc;
-        long long h[5];
-        HIP_TRY(hipMemcpy(h, c->dAsCounters, sizeof h, hipMemcpyDeviceToHost));
-        for (int q = 0; q < 5; ++q) out[q] = h[q];
-        return BMM_OK;
-    });
+    return guarded([&]() -> int { return sm_counters_out(c, c ? c->dAsCounters : nullptr, out); });
 }
 
 // ... of a run (bmm_alloc_run): armed, K set (the labels above it empty), K recorded behind every kept sweep

@@ -25,6 +25,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "bmm_spec.h"
 
 namespace bmm {
@@ -173,7 +175,7 @@ __device__ __forceinline__ void write_group_tables(int W, const double* e1, cons
 // o1/o0 of one chunk grouped at the SHAPE's width W (kGroupW or kGroupWAlt; uniform), the constant c folded into global
 // group 0 as Tm folds it, each binary64 sum narrowed once and stored nowhere else (k_resample_pk reads the entry with
 // the field that indexes Tq).  A loop of its own: carried through the loop of write_group_tables_w, its arguments
-// spilled SGPRs of k_count_tables<false>; so did what the compiler computed of it ahead of the chunk loop (the caller).
+// spilled SGPRs of k_count_tables<TAB_PLAIN>; so did what the compiler computed of it ahead of the chunk loop (the caller).
 template <int W>
 __device__ __forceinline__ void write_own32_w(const double* o1, const double* o0, int pc, int g0, int gc, int KT, int k,
                                               double c, float* To) {
@@ -193,15 +195,41 @@ __device__ __forceinline__ void write_own32(int W, const double* o1, const doubl
 }
 
 constexpr int kCountTablesThreads = 576;
-// This kernel and its twin k_alloc_tables write their log terms out themselves; they do not call the count-table
-// rules of bmm_spec.h that build_tables_self and k_state_tables share.  One kernel template over those functions
-// wrote the same bits but averaged 0.2 us (4 %) more per launch (profiles/r06/README.md), and this launch sits on every
-// batch of every counting chain, so the two bodies are left as they were: separate copies of the sweep's rules.
-// MASK (feature selection): `mask` holds one inclusion bit per feature (word d / 32, bit d % 32,
-// the bits from P on zero).  An excluded feature's terms are written as 0 in all four roles -- it scores the same for
-// every category, so it drops out of the conditional -- and the DP's new-cluster term counts the included features
-// only.  The statistics are folded for every feature alike.  MASK = false is the code as it always was.
-template <bool MASK>
+// The table build of every counting chain, one body in four flavours.  A flavour changes expressions only where they
+// stand below, behind `if constexpr` or a `?:` on a constant, so that each instantiation is the kernel that was once
+// written out for it; the values a flavour alone needs are trailing kernel arguments that exist for it only.
+//   TAB_PLAIN   the collapsed and the DP chain.  `packed`: the chain runs k_resample_pk and the packed image goes
+//               behind this one.
+//   TAB_MASK    feature selection: `mask` holds one inclusion bit per feature (word d / 32, bit
+//               d % 32, the bits from P on zero).  An excluded feature's terms are written as 0 in all four roles -- it
+//               scores the same for every category, so it drops out of the conditional -- and the DP's new-cluster
+//               term counts the included features only.  The statistics are folded for every feature alike.  Never a
+//               packed image (plan_kernel).
+//   TAB_ALLOC   the allocation sampler (extra: Kact, a): the number of components is part of
+//               the state, p.K is maxK and the first *Kact labels are open.  An open label scores with its prior
+//               weight a and the prior Bernoulli terms when it is empty (the Dirichlet-multinomial model; the plain
+//               build gives an empty label -inf for ever), and a row that sits alone keeps its own label at that
+//               weight; a label from *Kact on is closed: -inf, tables zero.  `a` is the Dirichlet parameter per
+//               component, the denominator log(N - 1 + K a).  alpha_ptr is not read.
+//   TAB_TEMPER  a rung of a replica ladder (extra: b), target p(alpha) p(z | alpha) p(x | z)^b:
+//               every per-feature term is multiplied once by the inverse temperature b after its denominator is
+//               subtracted, in all four roles.  The category's constant (the allocation prior) is untouched; the DP's
+//               new-cluster constant carries b on its P prior Bernoulli terms only.  The multiply sits behind the log_
+//               of a term thread, off wave 8's chain of constants.
+// Every flavour folds and clears the deltas and writes the same image with the same roles and order of operations, so
+// the resample kernels are the ones every chain runs, and these bit-equalities hold against TAB_PLAIN: TAB_MASK with a
+// mask of all ones; TAB_TEMPER with b = 1 (x * 1.0 is x); TAB_ALLOC with no label empty or single and K a = alpha.
+// The log terms are written out here; the kernel does not call the count-table rules of bmm_spec.h that
+// build_tables_self and k_state_tables share.  One kernel template over those functions wrote the same bits but
+// averaged 0.2 us (4 %) more per launch (profiles/r06/README.md), and this launch sits on every batch of every counting
+// chain.
+enum : int { TAB_PLAIN = 0, TAB_MASK = 1, TAB_ALLOC = 2, TAB_TEMPER = 3 };
+template <int I, class T, class... R>
+__device__ __forceinline__ auto tab_extra(T t, R... r) {  // trailing kernel argument I
+    if constexpr (I == 0) return t;
+    else return tab_extra<I - 1>(r...);
+}
+template <int F, class... Extra>
 __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParams p, int32_t* __restrict__ Nk,
                                                                      int32_t* __restrict__ S,
                                                                      int32_t* __restrict__ dNk,
@@ -209,14 +237,20 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
                                                                      const double* __restrict__ alpha_ptr,
                                                                      double* __restrict__ tab,
                                                                      const uint32_t* __restrict__ mask,
-                                                                     int packed) {
+                                                                     int packed, Extra... extra) {
+    constexpr bool MASK = F == TAB_MASK, ALLOC = F == TAB_ALLOC, TEMPER = F == TAB_TEMPER;
     __shared__ double e1[kMaxP], e0[kMaxP], m1[kMaxP], m0[kMaxP], cst[4];  // cst: Cp, Cm, the two denominators
     const int k = blockIdx.x;
     const TableLayout L = layout_of(p, true);
-    // the chain runs k_resample_pk: the packed image goes behind this one (uniform; never with a mask, plan_kernel)
-    float* const Tq = !MASK && packed ? reinterpret_cast<float*>(tab + L.doubles()) : nullptr;
+    // the chain runs k_resample_pk: the packed image goes behind this one (uniform)
+    float* const Tq = F == TAB_PLAIN && packed ? reinterpret_cast<float*>(tab + L.doubles()) : nullptr;
     const int P = p.P;
     const bool is_label = k < p.K;
+    int Ka = 0;            // ALLOC: the number of open labels, and the Dirichlet parameter
+    double a = 0.0, b = 1.0;  // TEMPER: the inverse temperature
+    if constexpr (ALLOC) { Ka = *tab_extra<0>(extra...); a = tab_extra<1>(extra...); }
+    if constexpr (TEMPER) b = tab_extra<0>(extra...);
+    const bool open = k < Ka;
     // 576 threads, ONE log_ each on the critical path (a log_ is about 150 dependent instructions).  Waves
     // 0-7: role r = thread / 128 -- the term of feature d for x = 1 and for x = 0 against the full
     // statistics (r = 0, 1) and with the scored observation removed (r = 2, 3).  Wave 8: the cluster's
@@ -230,21 +264,21 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
     const size_t KP = (size_t)p.K * P;
     if (is_label) { n_old = Nk[k]; n_dl = delta_take(dNk, k, p.K); }
     if (is_label && dl < P) { s_old = S[(size_t)k * P + dl]; s_dl = delta_take(dS, (size_t)k * P + dl, KP); }
-    const double alpha = *alpha_ptr;
+    const double alpha = ALLOC ? 0.0 : *alpha_ptr;
     const int64_t n = (int64_t)n_old + n_dl;
     const double bg = p.beta + p.gamma;
     if (role == 4) {
         const int lane = threadIdx.x & 63;
-        const bool dp_new = p.mode == MODE_DP && k == p.K;
-        const double ak = p.mode == MODE_COLLAPSED ? div_(alpha, (double)p.K) : 0.0;
+        const bool dp_new = !ALLOC && p.mode == MODE_DP && k == p.K;
+        const double ak = ALLOC ? a : p.mode == MODE_COLLAPSED ? div_(alpha, (double)p.K) : 0.0;
         double arg = 1.0;
         bool need = false;
-        switch (lane) {
-            case 0: arg = bg + (double)n; need = is_label && n > 0; break;                 // log(beta+gamma+n)
-            case 1: arg = bg + (double)(n - 1); need = is_label && n > 1; break;           // ... with one removed
-            case 2: arg = (double)n + ak; need = is_label && n > 0; break;                 // log(n + alpha/K), log n
-            case 3: arg = (double)(n - 1) + ak; need = is_label && n > 1; break;
-            case 4: arg = (double)(p.Ntot - 1) + alpha; need = true; break;                // log(N - 1 + alpha)
+        switch (lane) {  // (an open label of ALLOC takes its terms down to n = 0 and n - 1 = 0)
+            case 0: arg = bg + (double)n; need = ALLOC ? open : is_label && n > 0; break;  // log(beta+gamma+n)
+            case 1: arg = bg + (double)(n - 1); need = ALLOC ? open && n > 0 : is_label && n > 1; break;  // ... with one removed
+            case 2: arg = (double)n + ak; need = ALLOC ? open : is_label && n > 0; break;  // log(n + alpha/K), log n, log(n + a)
+            case 3: arg = (double)(n - 1) + ak; need = ALLOC ? open && n > 0 : is_label && n > 1; break;
+            case 4: arg = (double)(p.Ntot - 1) + (ALLOC ? (double)Ka * a : alpha); need = true; break;  // log(N - 1 + alpha), ... + K a)
             case 5: arg = alpha; need = dp_new; break;
             case 6: arg = p.beta; need = dp_new; break;
             case 7: arg = bg; need = dp_new; break;
@@ -261,11 +295,12 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
         const double ldN = __shfl(v, 4), la = __shfl(v, 5), lb = __shfl(v, 6), lbg = __shfl(v, 7);
         if (lane == 0) {
             double cp = neg_inf(), cm = neg_inf();
-            if (is_label) {
-                if (n > 0) cp = ln - ldN;
-                if (n > 1) cm = lm - ldN;
-            } else if (dp_new) {
-                cp = (la - ldN) + (double)p_in * (lb - lbg);
+            if (ALLOC ? open : is_label) {
+                if (ALLOC || n > 0) cp = ln - ldN;
+                if (n > (ALLOC ? 0 : 1)) cm = lm - ldN;
+            } else if (dp_new) {  // the prior of opening a cluster, then its (tempered) likelihood
+                if constexpr (TEMPER) cp = (la - ldN) + b * ((double)P * (lb - lbg));
+                else cp = (la - ldN) + (double)p_in * (lb - lbg);
             }
             tab[L.cp() + k] = cp;
             tab[L.cm() + k] = cm;
@@ -281,15 +316,15 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
         if (dl < pc && is_label) {
             const int d = c0 + dl;
             s = c0 == 0 ? s_old + s_dl : S[(size_t)k * P + d] + delta_take(dS, (size_t)k * P + d, KP);
-            // term_x1 / term_x0 of bmm_spec.h, the denominator subtracted below
-            if (role == 0) { have = n > 0; raw = have ? log_(p.beta + (double)s) : 0.0; }
-            else if (role == 1) { have = n > 0; raw = have ? log_((p.gamma + (double)n) - (double)s) : 0.0; }
-            else if (role == 2) { have = n > 1 && s >= 1; raw = have ? log_(p.beta + (double)((int64_t)s - 1)) : 0.0; }
-            else { have = n > 1 && s <= n - 1; raw = have ? log_((p.gamma + (double)(n - 1)) - (double)s) : 0.0; }
+            // term_x1 / term_x0 of bmm_spec.h, the denominator subtracted (and the power applied) below
+            if (role == 0) { have = ALLOC ? open : n > 0; raw = have ? log_(p.beta + (double)s) : 0.0; }
+            else if (role == 1) { have = ALLOC ? open : n > 0; raw = have ? log_((p.gamma + (double)n) - (double)s) : 0.0; }
+            else if (role == 2) { have = (ALLOC ? open && n > 0 : n > 1) && s >= 1; raw = have ? log_(p.beta + (double)((int64_t)s - 1)) : 0.0; }
+            else { have = (ALLOC ? open && n > 0 : n > 1) && s <= n - 1; raw = have ? log_((p.gamma + (double)(n - 1)) - (double)s) : 0.0; }
         }
         __syncthreads();  // the constants are in place; every role has read S + dS before either is rewritten
         if (dl < pc) {
-            double t = have ? raw - cst[role < 2 ? 2 : 3] : 0.0;
+            double t = have ? (TEMPER ? b * (raw - cst[role < 2 ? 2 : 3]) : raw - cst[role < 2 ? 2 : 3]) : 0.0;
             if (MASK && !((mask[(c0 + dl) >> 5] >> ((c0 + dl) & 31)) & 1u)) t = 0.0;
             (role == 0 ? e1 : role == 1 ? e0 : role == 2 ? m1 : m0)[dl] = t;
             if (role == 0 && is_label) {
@@ -4062,13 +4097,21 @@ __global__ __launch_bounds__(256) void k_ps_reduce(const uint64_t* __restrict__ 
     }
 }
 
-// ---- split-merge moves of the DP chain (include/bmm_mcmc.h "split-merge moves") ----------
+// ---- split-merge moves (include/bmm_mcmc.h "split-merge moves", "split-merge moves of the allocation sampler";
+// DESIGN.md sections 15 and 24) ----------------------------------------------------------------------------------------
 // One move = k_sm_launch, `scans` + 1 launches of k_sm_scan, k_sm_decide, k_sm_commit, stream-ordered; the host
 // never reads anything back.  The two labels of the move are its sides 0 and 1.  One byte per row: its side (0 / 1)
 // for a member, 2 + side for the two anchors, kSmOut for every other row.  The statistics of the two sides after
 // the launch state (set 0) and after scan t (set t) live in `stat`, a set being {n_0, S_0[P], n_1, S_1[P]} int32:
 // scan t reads set t - 1, frozen, and adds into set t, which the host zeroed when it enqueued the move.  The last
 // set (scans + 1) is the proposal of a split.  A workgroup holds 256 consecutive rows, one per lane.
+// The four kernels are templates over the target, and a flavour's own statements stand behind `if constexpr`:
+//   ALLOC = false  the DP chain: a split takes the first empty label, the prior ratio is the CRP's.
+//   ALLOC = true   the allocation chain (AsArgs, AsCell: the DP move's with the K cell, p(K) and the Dirichlet
+//                  parameter a behind them): the same restricted scans under the allocation sampler's target, the
+//                  weights w_c carrying `+ a`.  A split opens label K, the first closed one, and is skipped at
+//                  K == maxK; a merge closes label K - 1 after moving it into the label the merge freed, as an
+//                  absorb does.  Its draws come from a stream of their own (as_move_draws).
 constexpr int kSmThreads = 256;
 constexpr int kSmMaxP = 1024;  // the per-feature terms (32 bytes a feature) and the histogram stay below 64 KiB of LDS
 constexpr uint8_t kSmOut = 255;
@@ -4092,6 +4135,20 @@ struct SmArgs {
     uint32_t sweep, move;
     int scans;
 };
+struct AsCell {
+    SmCell m;
+    int32_t k_before, k_after, moved, pad;  // moved: the label a committed merge moved into the gap, or -1
+};
+struct AsArgs : SmArgs {        // (alpha_ptr is not read; SmArgs::cell points at AsCell::m)
+    int32_t* K;                 // the number of open labels
+    const double* log_prior_k;  // [maxK]: log p(K = k + 1)
+    AsCell* as_cell;
+    double a;                   // the Dirichlet parameter per component
+};
+// A kernel binds `a`, the DP move's arguments, to its parameter itself (const SmArgs& a = g): handed through a function,
+// however inlined, the parameter is copied first and its loads lose what the compiler knows of kernel arguments.
+template <bool ALLOC>
+using SmArgsOf = std::conditional_t<ALLOC, AsArgs, SmArgs>;
 __device__ __forceinline__ size_t sm_set(int P) { return (size_t)2 * (P + 1); }
 
 // The rows of one wave into the histogram {n_0, S_0[P], n_1, S_1[P]} of a workgroup: a ballot per feature, one
@@ -4128,35 +4185,45 @@ __device__ __forceinline__ void sm_flush(const int32_t* hist, int P, int32_t* se
 
 // The pair, the two labels and the kind of the move (every workgroup derives them; workgroup 0 records them), then
 // the launch state: anchor i on side 0, anchor j on side 1, every other row of the two labels on either side with
-// probability 1/2 from its own uniform, whatever its current label.
-__global__ __launch_bounds__(kSmThreads) void k_sm_launch(ChainParams p, SmArgs a) {
+// probability 1/2 from its own uniform, whatever its current label.  The label a split opens: the first empty one
+// (DP; none: skipped), the K cell's (ALLOC; K == maxK: skipped).
+template <bool ALLOC>
+__global__ __launch_bounds__(kSmThreads) void k_sm_launch(ChainParams p, SmArgsOf<ALLOC> g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int32_t* const hist = reinterpret_cast<int32_t*>(smem);
+    const SmArgs& a = g;
     __shared__ int sh_free, sh_la, sh_lb, sh_kind;
     __shared__ long long sh_i, sh_j;
     __shared__ uint32_t sh_salt;
     const int P = p.P, K = p.K, tid = threadIdx.x, lane = tid & 63;
     const int64_t N = p.N;
     for (int i = tid; i < 2 * (P + 1); i += kSmThreads) hist[i] = 0;
-    if (tid == 0) sh_free = K;
-    __syncthreads();
-    for (int k = tid; k < K; k += kSmThreads)
-        if (a.Nk[k] == 0) atomicMin(&sh_free, k);
-    __syncthreads();
+    if constexpr (!ALLOC) {
+        if (tid == 0) sh_free = K;
+        __syncthreads();
+        for (int k = tid; k < K; k += kSmThreads)
+            if (a.Nk[k] == 0) atomicMin(&sh_free, k);
+        __syncthreads();
+    }
     if (tid == 0) {
-        const SmDraws dr = sm_move_draws(p.seed, a.sweep, a.move, N);
+        int Ka = 0;  // ALLOC: the number of open labels
+        if constexpr (ALLOC) Ka = *g.K;
+        const SmDraws dr = ALLOC ? as_move_draws(p.seed, a.sweep, a.move, N) : sm_move_draws(p.seed, a.sweep, a.move, N);
         const int la = a.z[dr.i], zj = a.z[dr.j];
-        const int kind = la != zj ? SM_MERGE : (sh_free < K ? SM_SPLIT : SM_SKIPPED);
-        const int lb = kind == SM_MERGE ? zj : sh_free;
+        const int kind = la != zj ? SM_MERGE : ((ALLOC ? Ka : sh_free) < K ? SM_SPLIT : SM_SKIPPED);
+        const int lb = kind == SM_MERGE ? zj : ALLOC ? (kind == SM_SPLIT ? Ka : la) : sh_free;
         sh_i = dr.i; sh_j = dr.j; sh_la = la; sh_lb = lb; sh_kind = kind; sh_salt = dr.salt;
         if (blockIdx.x == 0) {
             SmCell* c = a.cell;
+            if constexpr (ALLOC) c = &g.as_cell->m;  // (the same cell, through the one pointer the flavour follows)
             c->row_i = dr.i; c->row_j = dr.j; c->label_a = la; c->label_b = lb; c->kind = kind; c->salt = dr.salt;
+            if constexpr (ALLOC) c->pad = 0;
             c->accepted = 0; c->members = 0;
             c->n_before[0] = a.Nk[la]; c->n_before[1] = kind == SM_MERGE ? a.Nk[lb] : 0;
             c->n_after[0] = c->n_after[1] = 0;
             c->log_u = log_(dr.u);
             c->log_prior = c->log_lik = c->log_q = c->log_r = 0.0;
+            if constexpr (ALLOC) { g.as_cell->k_before = Ka; g.as_cell->k_after = Ka; g.as_cell->moved = -1; g.as_cell->pad = 0; }
         }
     }
     __syncthreads();
@@ -4194,7 +4261,9 @@ __device__ __forceinline__ void sm_side_logp(double diff, double& lp0, double& l
 // feature order onto base[own] = log(n_0 - [own = 0]) - log(n_1 - [own = 1]).  The final scan of a split is drawn
 // like the others and records the log probability of the side drawn; the final scan of a merge draws nothing and
 // records the log probability of the side that is the row's current label.
-__global__ __launch_bounds__(kSmThreads) void k_sm_scan(ChainParams p, SmArgs a, int t, int final) {
+template <bool ALLOC>
+__global__ __launch_bounds__(kSmThreads) void k_sm_scan(ChainParams p, SmArgsOf<ALLOC> g, int t, int final) {
+    const SmArgs& a = g;
     extern __shared__ __attribute__((aligned(32))) char smem[];
     const int P = p.P, tid = threadIdx.x, lane = tid & 63;
     const int64_t N = p.N;
@@ -4225,7 +4294,11 @@ __global__ __launch_bounds__(kSmThreads) void k_sm_scan(ChainParams p, SmArgs a,
         D[idx] = own ? pl - m : m - pl;
     }
     for (int i = tid; i < 2 * (P + 1); i += kSmThreads) hist[i] = 0;
-    if (tid < 2) base[tid] = log_((double)(n0 - (tid == 0))) - log_((double)(n1 - (tid == 1)));
+    if constexpr (ALLOC) {
+        if (tid < 2) base[tid] = log_((double)(n0 - (tid == 0)) + g.a) - log_((double)(n1 - (tid == 1)) + g.a);
+    } else {
+        if (tid < 2) base[tid] = log_((double)(n0 - (tid == 0))) - log_((double)(n1 - (tid == 1)));
+    }
     __syncthreads();
     int ns = sd & 1;
     if (member) {
@@ -4259,15 +4332,18 @@ __global__ __launch_bounds__(kSmThreads) void k_sm_scan(ChainParams p, SmArgs a,
 }
 
 // One workgroup: log q in an order fixed by N (1024 partial sums, row i in partial i mod 1024, ascending, then a
-// binary tree, as k_loo_reduce), the marginal-likelihood ratio the same way over the features, the prior ratio, the
-// decision and the counters.
+// binary tree, as k_loo_reduce), the marginal-likelihood ratio the same way over the features, the prior ratio (the
+// CRP's; ALLOC: the spec's as_log_prior, and with it what the move does to K), the decision and the counters.
 __device__ __forceinline__ double sm_pair(double beta, double gamma, int64_t n, int64_t s) {
     return lgamma_(beta + (double)s) + lgamma_((gamma + (double)n) - (double)s);
 }
-__global__ __launch_bounds__(1024) void k_sm_decide(ChainParams p, SmArgs a) {
+template <bool ALLOC>
+__global__ __launch_bounds__(1024) void k_sm_decide(ChainParams p, SmArgsOf<ALLOC> g) {
     __shared__ double sh[2][1024];
+    const SmArgs& a = g;
     const int t = threadIdx.x, P = p.P;
-    SmCell* const c = a.cell;
+    SmCell* c = a.cell;
+    if constexpr (ALLOC) c = &g.as_cell->m;
     const int kind = c->kind;
     if (kind == SM_SKIPPED) {
         if (t == 0) a.counters[4] += 1;
@@ -4295,16 +4371,24 @@ __global__ __launch_bounds__(1024) void k_sm_decide(ChainParams p, SmArgs a) {
         __syncthreads();
     }
     if (t != 0) return;
-    const double bg = p.beta + p.gamma, la_ = log_(*a.alpha_ptr);
+    const double bg = p.beta + p.gamma;
+    double la_ = 0.0;  // DP: log alpha
+    if constexpr (!ALLOC) la_ = log_(*a.alpha_ptr);
     const double c0 = (lgamma_(bg) - lgamma_(p.beta)) - lgamma_(p.gamma);
     const double log_q = sh[0][0];
     double cst, log_prior;
     if (split) {
         cst = ((c0 - lgamma_(bg + (double)nn0)) - lgamma_(bg + (double)nn1)) + lgamma_(bg + (double)no0);
-        log_prior = ((la_ + lgamma_((double)nn0)) + lgamma_((double)nn1)) - lgamma_((double)no0);
+        if constexpr (!ALLOC) log_prior = ((la_ + lgamma_((double)nn0)) + lgamma_((double)nn1)) - lgamma_((double)no0);
     } else {
         cst = ((lgamma_(bg + (double)no0) + lgamma_(bg + (double)no1)) - lgamma_(bg + (double)nn0)) - c0;
-        log_prior = ((lgamma_((double)nn0) - lgamma_((double)no0)) - lgamma_((double)no1)) - la_;
+        if constexpr (!ALLOC) log_prior = ((lgamma_((double)nn0) - lgamma_((double)no0)) - lgamma_((double)no1)) - la_;
+    }
+    int K = 0;  // ALLOC: the number of open labels before the move
+    if constexpr (ALLOC) {
+        K = g.as_cell->k_before;
+        log_prior = split ? as_log_prior(K, (double)p.Ntot, g.a, g.log_prior_k, no0, nn0, nn1, true)
+                          : as_log_prior(K, (double)p.Ntot, g.a, g.log_prior_k, nn0, no0, no1, false);
     }
     const double log_lik = sh[1][0] + (double)P * cst;
     const double log_r = split ? (log_prior + log_lik) - log_q : (log_prior + log_lik) + log_q;
@@ -4313,16 +4397,29 @@ __global__ __launch_bounds__(1024) void k_sm_decide(ChainParams p, SmArgs a) {
     c->n_after[0] = nn0; c->n_after[1] = nn1;
     const int32_t* const first = a.stat;
     c->members = (long long)first[0] + first[P + 1] - 2;
+    if constexpr (ALLOC) {
+        g.as_cell->k_after = acc ? (split ? K + 1 : K - 1) : K;
+        g.as_cell->moved = acc && !split && lb != K - 1 ? K - 1 : -1;
+    }
     a.counters[split ? 0 : 2] += 1;
     if (acc) a.counters[split ? 1 : 3] += 1;
 }
 
-// An accepted move: the labels and the exact integer statistics of the two labels.  A rejected or skipped one:
-// nothing, so the host never waits inside a move.
-__global__ __launch_bounds__(kSmThreads) void k_sm_commit(ChainParams p, SmArgs a) {
-    const SmCell* const c = a.cell;
+// An accepted move: the labels and the exact integer statistics of the labels touched.  A rejected or skipped one:
+// nothing, so the host never waits inside a move.  Every workgroup relabels its own rows from the record alone: a
+// split gives the rows of side 1 label lb; a DP merge gives the rows of the higher label the lower one; an ALLOC merge
+// gives the rows of lb label la and then, as an absorb, the rows of label K - 1 the freed label lb (with la == K - 1
+// the merged component ends up under lb).  Workgroup 0 writes the statistics and, ALLOC, the K cell, which no other
+// workgroup reads.
+template <bool ALLOC>
+__global__ __launch_bounds__(kSmThreads) void k_sm_commit(ChainParams p, SmArgsOf<ALLOC> g) {
+    const SmArgs& a = g;
+    const SmCell* c = a.cell;
+    if constexpr (ALLOC) c = &g.as_cell->m;
     if (!c->accepted) return;
     const int P = p.P, tid = threadIdx.x, la = c->label_a, lb = c->label_b;
+    int last = 0;  // ALLOC: label K - 1, which a merge moves into the gap
+    if constexpr (ALLOC) last = g.as_cell->k_before - 1;
     const bool split = c->kind == SM_SPLIT;
     const int lo = la < lb ? la : lb, hi = la < lb ? lb : la;
     const int64_t r = (int64_t)blockIdx.x * kSmThreads + tid;
@@ -4330,6 +4427,10 @@ __global__ __launch_bounds__(kSmThreads) void k_sm_commit(ChainParams p, SmArgs 
         if (split) {
             const int sd = a.side[r];
             if (sd == 1 || sd == 3) a.z[r] = lb;
+        } else if constexpr (ALLOC) {
+            const int zr = a.z[r];
+            if (zr == lb) a.z[r] = (la == last && lb != last) ? lb : la;
+            else if (zr == last && lb != last) a.z[r] = lb;
         } else if (a.z[r] == hi) {
             a.z[r] = lo;
         }
@@ -4341,11 +4442,19 @@ __global__ __launch_bounds__(kSmThreads) void k_sm_commit(ChainParams p, SmArgs 
         int32_t* const B = idx == 0 ? a.Nk + lb : a.S + (size_t)lb * P + (idx - 1);
         if (split) {
             *A = fin[idx]; *B = fin[P + 1 + idx];
+        } else if constexpr (ALLOC) {  // in this order: la may be the last label
+            int32_t* const Z = idx == 0 ? a.Nk + last : a.S + (size_t)last * P + (idx - 1);
+            const int32_t s = *A + *B;
+            *A = s; *B = 0;
+            if (lb != last) { *B = *Z; *Z = 0; }
         } else {
             const int32_t s = *A + *B;
             *(la < lb ? A : B) = s;
             *(la < lb ? B : A) = 0;
         }
+    }
+    if constexpr (ALLOC) {
+        if (tid == 0) *g.K = g.as_cell->k_after;
     }
 }
 
@@ -4690,195 +4799,10 @@ __global__ __launch_bounds__(kInitThreads) void k_init_modes(ChainParams p, Init
 }
 
 // ---- the allocation sampler: unknown K for the finite chain (include/bmm_mcmc.h "allocation sampler")
-// The table build of a chain whose number of components K is part of the state: k_count_tables for maxK = p.K
-// labels of which the first *Kact are open.  It folds and clears the deltas as k_count_tables does and writes the same
-// image, so the resample kernels are the ones every chain runs.  A label below *Kact scores with its prior weight and
-// the prior Bernoulli terms when it is empty (the Dirichlet-multinomial model; k_count_tables gives it -inf for ever),
-// and a row that sits alone keeps its own label at that weight; a label from *Kact on is closed: -inf, tables zero.
-// `a` is the Dirichlet parameter per component, the denominator log(N - 1 + K a).  Roles and order of operations are
-// those of k_count_tables; with no label empty or single and K a = alpha the two write the same bits.
-__global__ __launch_bounds__(kCountTablesThreads) void k_alloc_tables(ChainParams p, int32_t* __restrict__ Nk,
-                                                                     int32_t* __restrict__ S,
-                                                                     int32_t* __restrict__ dNk,
-                                                                     int32_t* __restrict__ dS,
-                                                                     const int32_t* __restrict__ Kact, double a,
-                                                                     double* __restrict__ tab) {
-    __shared__ double e1[kMaxP], e0[kMaxP], m1[kMaxP], m0[kMaxP], cst[4];  // cst: Cp, Cm, the two denominators
-    const int k = blockIdx.x;
-    const TableLayout L = layout_of(p, true);
-    const int P = p.P;
-    const bool is_label = k < p.K;
-    const int Ka = *Kact;
-    const bool open = k < Ka;
-    const int role = threadIdx.x >> 7;
-    const int dl = role < 4 ? (threadIdx.x & 127) : kMaxP;
-    int32_t n_old = 0, n_dl = 0, s_old = 0, s_dl = 0;
-    const size_t KP = (size_t)p.K * P;
-    if (is_label) { n_old = Nk[k]; n_dl = delta_take(dNk, k, p.K); }
-    if (is_label && dl < P) { s_old = S[(size_t)k * P + dl]; s_dl = delta_take(dS, (size_t)k * P + dl, KP); }
-    const int64_t n = (int64_t)n_old + n_dl;
-    const double bg = p.beta + p.gamma;
-    if (role == 4) {
-        const int lane = threadIdx.x & 63;
-        double arg = 1.0;
-        bool need = false;
-        switch (lane) {
-            case 0: arg = bg + (double)n; need = open; break;                       // log(beta+gamma+n)
-            case 1: arg = bg + (double)(n - 1); need = open && n > 0; break;         // ... with one removed
-            case 2: arg = (double)n + a; need = open; break;                        // log(n + a)
-            case 3: arg = (double)(n - 1) + a; need = open && n > 0; break;
-            case 4: arg = (double)(p.Ntot - 1) + (double)Ka * a; need = true; break;  // log(N - 1 + K a)
-            default: break;
-        }
-        const double v = need ? log_(arg) : 0.0;
-        const double den_p = __shfl(v, 0), den_m = __shfl(v, 1), ln = __shfl(v, 2), lm = __shfl(v, 3);
-        const double ldN = __shfl(v, 4);
-        if (lane == 0) {
-            double cp = neg_inf(), cm = neg_inf();
-            if (open) {
-                cp = ln - ldN;
-                if (n > 0) cm = lm - ldN;
-            }
-            tab[L.cp() + k] = cp;
-            tab[L.cm() + k] = cm;
-            cst[0] = cp; cst[1] = cm; cst[2] = den_p; cst[3] = den_m;  // read after the first barrier below
-            reinterpret_cast<int32_t*>(tab + L.nk())[k] = (int32_t)n;
-        }
-    }
-    for (int c0 = 0; c0 < P; c0 += kChunkP) {  // kChunkP features (whole groups) at a time
-        const int pc = P - c0 < kChunkP ? P - c0 : kChunkP;
-        int32_t s = 0;
-        double raw = 0.0;
-        bool have = false;
-        if (dl < pc && is_label) {
-            const int d = c0 + dl;
-            s = c0 == 0 ? s_old + s_dl : S[(size_t)k * P + d] + delta_take(dS, (size_t)k * P + d, KP);
-            // term_x1 / term_x0 of bmm_spec.h, the denominator subtracted below
-            if (role == 0) { have = open; raw = have ? log_(p.beta + (double)s) : 0.0; }
-            else if (role == 1) { have = open; raw = have ? log_((p.gamma + (double)n) - (double)s) : 0.0; }
-            else if (role == 2) { have = open && n > 0 && s >= 1; raw = have ? log_(p.beta + (double)((int64_t)s - 1)) : 0.0; }
-            else { have = open && n > 0 && s <= n - 1; raw = have ? log_((p.gamma + (double)(n - 1)) - (double)s) : 0.0; }
-        }
-        __syncthreads();  // the constants are in place; every role has read S + dS before either is rewritten
-        if (dl < pc) {
-            const double t = have ? raw - cst[role < 2 ? 2 : 3] : 0.0;
-            (role == 0 ? e1 : role == 1 ? e0 : role == 2 ? m1 : m0)[dl] = t;
-            if (role == 0 && is_label) {
-                const int d = c0 + dl;
-                S[(size_t)k * P + d] = s;
-                delta_clear(dS, (size_t)k * P + d, KP);
-            }
-        }
-        __syncthreads();
-        write_group_tables(p.W, e1, e0, pc, c0, p.KT, k, cst[0], tab + L.tp());
-        write_group_tables(kGroupWm, m1, m0, pc, c0, p.KT, k, cst[1], tab + L.tm());
-        __syncthreads();
-    }
-    if (is_label && threadIdx.x == 0) {  // every thread read the old pair before the barriers above
-        Nk[k] = (int32_t)n;
-        delta_clear(dNk, k, p.K);
-    }
-    if (k == 0 && threadIdx.x < 256) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];
-}
+// (its table build is k_count_tables<TAB_ALLOC>)
 
 // ---- parallel tempering (include/bmm_mcmc.h "parallel tempering") --------------------------
-// The table build of a chain that targets p(alpha) p(z | alpha) p(x | z)^b: k_count_tables<false> with every
-// per-feature term multiplied once by the inverse temperature b after its denominator is subtracted, in all four roles.
-// The category's constant (the allocation prior) is untouched; the DP's new-cluster constant carries b on its P prior
-// Bernoulli terms only.  It folds and clears the deltas as k_count_tables does and writes the same image, never a
-// packed one, so the resample kernels are the ones every chain runs.  Roles and order of operations are those of
-// k_count_tables: with b = 1 the two write the same bits (x * 1.0 is x).  The extra multiply sits behind the log_ of
-// a term thread, off wave 8's chain of constants.
-__global__ __launch_bounds__(kCountTablesThreads) void k_temper_tables(ChainParams p, int32_t* __restrict__ Nk,
-                                                                      int32_t* __restrict__ S,
-                                                                      int32_t* __restrict__ dNk,
-                                                                      int32_t* __restrict__ dS,
-                                                                      const double* __restrict__ alpha_ptr, double b,
-                                                                      double* __restrict__ tab) {
-    __shared__ double e1[kMaxP], e0[kMaxP], m1[kMaxP], m0[kMaxP], cst[4];  // cst: Cp, Cm, the two denominators
-    const int k = blockIdx.x;
-    const TableLayout L = layout_of(p, true);
-    const int P = p.P;
-    const bool is_label = k < p.K;
-    const int role = threadIdx.x >> 7;
-    const int dl = role < 4 ? (threadIdx.x & 127) : kMaxP;
-    int32_t n_old = 0, n_dl = 0, s_old = 0, s_dl = 0;
-    const size_t KP = (size_t)p.K * P;
-    if (is_label) { n_old = Nk[k]; n_dl = delta_take(dNk, k, p.K); }
-    if (is_label && dl < P) { s_old = S[(size_t)k * P + dl]; s_dl = delta_take(dS, (size_t)k * P + dl, KP); }
-    const double alpha = *alpha_ptr;
-    const int64_t n = (int64_t)n_old + n_dl;
-    const double bg = p.beta + p.gamma;
-    if (role == 4) {
-        const int lane = threadIdx.x & 63;
-        const bool dp_new = p.mode == MODE_DP && k == p.K;
-        const double ak = p.mode == MODE_COLLAPSED ? div_(alpha, (double)p.K) : 0.0;
-        double arg = 1.0;
-        bool need = false;
-        switch (lane) {
-            case 0: arg = bg + (double)n; need = is_label && n > 0; break;                 // log(beta+gamma+n)
-            case 1: arg = bg + (double)(n - 1); need = is_label && n > 1; break;           // ... with one removed
-            case 2: arg = (double)n + ak; need = is_label && n > 0; break;                 // log(n + alpha/K), log n
-            case 3: arg = (double)(n - 1) + ak; need = is_label && n > 1; break;
-            case 4: arg = (double)(p.Ntot - 1) + alpha; need = true; break;                // log(N - 1 + alpha)
-            case 5: arg = alpha; need = dp_new; break;
-            case 6: arg = p.beta; need = dp_new; break;
-            case 7: arg = bg; need = dp_new; break;
-            default: break;
-        }
-        const double v = need ? log_(arg) : 0.0;
-        const double den_p = __shfl(v, 0), den_m = __shfl(v, 1), ln = __shfl(v, 2), lm = __shfl(v, 3);
-        const double ldN = __shfl(v, 4), la = __shfl(v, 5), lb = __shfl(v, 6), lbg = __shfl(v, 7);
-        if (lane == 0) {
-            double cp = neg_inf(), cm = neg_inf();
-            if (is_label) {
-                if (n > 0) cp = ln - ldN;
-                if (n > 1) cm = lm - ldN;
-            } else if (dp_new) {
-                cp = (la - ldN) + b * ((double)P * (lb - lbg));  // the prior of opening a cluster, then its tempered likelihood
-            }
-            tab[L.cp() + k] = cp;
-            tab[L.cm() + k] = cm;
-            cst[0] = cp; cst[1] = cm; cst[2] = den_p; cst[3] = den_m;  // read after the first barrier below
-            reinterpret_cast<int32_t*>(tab + L.nk())[k] = (int32_t)n;
-        }
-    }
-    for (int c0 = 0; c0 < P; c0 += kChunkP) {  // kChunkP features (whole groups) at a time
-        const int pc = P - c0 < kChunkP ? P - c0 : kChunkP;
-        int32_t s = 0;
-        double raw = 0.0;
-        bool have = false;
-        if (dl < pc && is_label) {
-            const int d = c0 + dl;
-            s = c0 == 0 ? s_old + s_dl : S[(size_t)k * P + d] + delta_take(dS, (size_t)k * P + d, KP);
-            // term_x1 / term_x0 of bmm_spec.h, the denominator subtracted and the power applied below
-            if (role == 0) { have = n > 0; raw = have ? log_(p.beta + (double)s) : 0.0; }
-            else if (role == 1) { have = n > 0; raw = have ? log_((p.gamma + (double)n) - (double)s) : 0.0; }
-            else if (role == 2) { have = n > 1 && s >= 1; raw = have ? log_(p.beta + (double)((int64_t)s - 1)) : 0.0; }
-            else { have = n > 1 && s <= n - 1; raw = have ? log_((p.gamma + (double)(n - 1)) - (double)s) : 0.0; }
-        }
-        __syncthreads();  // the constants are in place; every role has read S + dS before either is rewritten
-        if (dl < pc) {
-            const double t = have ? b * (raw - cst[role < 2 ? 2 : 3]) : 0.0;
-            (role == 0 ? e1 : role == 1 ? e0 : role == 2 ? m1 : m0)[dl] = t;
-            if (role == 0 && is_label) {
-                const int d = c0 + dl;
-                S[(size_t)k * P + d] = s;
-                delta_clear(dS, (size_t)k * P + d, KP);
-            }
-        }
-        __syncthreads();
-        write_group_tables(p.W, e1, e0, pc, c0, p.KT, k, cst[0], tab + L.tp());
-        write_group_tables(kGroupWm, m1, m0, pc, c0, p.KT, k, cst[1], tab + L.tm());
-        __syncthreads();
-    }
-    if (is_label && threadIdx.x == 0) {  // every thread read the old pair before the barriers above
-        Nk[k] = (int32_t)n;
-        delta_clear(dNk, k, p.K);
-    }
-    if (k == 0 && threadIdx.x < 256) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];
-}
-
+// (a rung's table build is k_count_tables<TAB_TEMPER>)
 // The exchange of a replica ladder: R <= kTemperMaxR chains ("rungs") over the same data at inverse temperatures
 // 1 = b_0 > b_1 > ...; rung r's row of k_log_joint_finish holds L_r = log p(x | z_r) of its current state.
 // k_temper_decide: one wave; lane j takes pair r = 2 j + (t mod 2), the pairs of exchange point t (they are disjoint,
@@ -5150,237 +5074,7 @@ __global__ __launch_bounds__(kEaThreads) void k_ea_commit(ChainParams p, EaArgs 
 }
 
 // ---- split-merge moves of the allocation chain (include/bmm_mcmc.h "split-merge moves of the allocation sampler";
-// DESIGN.md section 24) ---------------------------------------------------------------------------------------------
-// The restricted scans of the DP move under the allocation sampler's target: k_as_launch, `scans` + 1 launches of
-// k_as_scan, k_as_decide, k_as_commit, stream-ordered; the host never reads anything back.  Side bytes, `stat` sets
-// and the final scan's log probabilities are those of the DP move, and the record begins with the DP move's, so the
-// scan is the DP scan's twin with the `+ a` weights (k_sm_scan itself is not touched: a shared body, tried first,
-// changed its scalar register allocation).  A split opens label K, the first closed one; a merge closes
-// label K - 1 after moving it into the label the merge freed, as an absorb does.
-struct AsCell {
-    SmCell m;
-    int32_t k_before, k_after, moved, pad;  // moved: the label a committed merge moved into the gap, or -1
-};
-struct AsArgs {
-    SmArgs s;                   // (alpha_ptr is not read; cell points at AsCell::m)
-    int32_t* K;                 // the number of open labels
-    const double* log_prior_k;  // [maxK]: log p(K = k + 1)
-    AsCell* cell;
-    double a;                   // the Dirichlet parameter per component
-};
-
-// The pair, the kind and the two labels from the K cell (every workgroup derives them; workgroup 0 records them), then
-// the launch state and set 0, as k_sm_launch.  A split at K == maxK is skipped.
-__global__ __launch_bounds__(kSmThreads) void k_as_launch(ChainParams p, AsArgs g) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int32_t* const hist = reinterpret_cast<int32_t*>(smem);
-    const SmArgs& a = g.s;
-    __shared__ int sh_la, sh_lb, sh_kind;
-    __shared__ long long sh_i, sh_j;
-    __shared__ uint32_t sh_salt;
-    const int P = p.P, tid = threadIdx.x, lane = tid & 63;
-    const int64_t N = p.N;
-    for (int i = tid; i < 2 * (P + 1); i += kSmThreads) hist[i] = 0;
-    if (tid == 0) {
-        const int K = *g.K;
-        const SmDraws dr = as_move_draws(p.seed, a.sweep, a.move, N);
-        const int la = a.z[dr.i], zj = a.z[dr.j];
-        const int kind = la != zj ? SM_MERGE : (K < p.K ? SM_SPLIT : SM_SKIPPED);
-        const int lb = kind == SM_MERGE ? zj : (kind == SM_SPLIT ? K : la);
-        sh_i = dr.i; sh_j = dr.j; sh_la = la; sh_lb = lb; sh_kind = kind; sh_salt = dr.salt;
-        if (blockIdx.x == 0) {
-            AsCell* const c = g.cell;
-            c->m.row_i = dr.i; c->m.row_j = dr.j; c->m.label_a = la; c->m.label_b = lb; c->m.kind = kind; c->m.salt = dr.salt;
-            c->m.pad = 0; c->m.accepted = 0; c->m.members = 0;
-            c->m.n_before[0] = a.Nk[la]; c->m.n_before[1] = kind == SM_MERGE ? a.Nk[lb] : 0;
-            c->m.n_after[0] = c->m.n_after[1] = 0;
-            c->m.log_u = log_(dr.u);
-            c->m.log_prior = c->m.log_lik = c->m.log_q = c->m.log_r = 0.0;
-            c->k_before = K; c->k_after = K; c->moved = -1; c->pad = 0;
-        }
-    }
-    __syncthreads();
-    const int kind = sh_kind, la = sh_la, lb = sh_lb;
-    if (kind == SM_SKIPPED) return;
-    const int64_t r = (int64_t)blockIdx.x * kSmThreads + tid;
-    int sd = kSmOut;
-    if (r < N) {
-        const int zr = a.z[r];
-        if (zr == la || (kind == SM_MERGE && zr == lb)) {
-            if (r == sh_i) sd = 2;
-            else if (r == sh_j) sd = 3;
-            else sd = sm_member_uniform(sh_salt, (uint64_t)(p.obs0 + r), 0u) < 0.5 ? 0 : 1;
-        }
-        a.side[r] = (uint8_t)sd;
-        if (a.side_launch) a.side_launch[r] = (uint8_t)sd;
-    }
-    sm_count_wave(sd != kSmOut, sd & 1, a.Xb, N, P, r, hist, lane);
-    __syncthreads();
-    sm_flush(hist, P, a.stat, tid);
-}
-
-// k_sm_scan with the allocation prior between the two sides, w_c = (n_c - [own] + a) prod_d (...): its twin, statement
-// for statement but for base[].  Whoever changes one changes the other.
-__global__ __launch_bounds__(kSmThreads) void k_as_scan(ChainParams p, AsArgs g, int t, int final) {
-    const SmArgs& a = g.s;
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    const int P = p.P, tid = threadIdx.x, lane = tid & 63;
-    const int64_t N = p.N;
-    double* const D = reinterpret_cast<double*>(smem);                // [P][2][2]
-    int32_t* const hist = reinterpret_cast<int32_t*>(D + 4 * (size_t)P);
-    __shared__ double base[2];
-    const int kind = a.cell->kind;
-    if (kind == SM_SKIPPED) return;
-    const bool score_only = final && kind == SM_MERGE;
-    const int64_t r = (int64_t)blockIdx.x * kSmThreads + tid;
-    const int sd = r < N ? a.side[r] : kSmOut;
-    const bool member = sd < 2, counted = sd != kSmOut;
-    if (final && r < N && !member) a.lq[r] = 0.0;
-    if (!__syncthreads_or(counted)) return;
-    const int32_t* const in = a.stat + (size_t)(t - 1) * sm_set(P);
-    const int32_t n0 = in[0], n1 = in[P + 1];
-    const double bg = p.beta + p.gamma;
-    for (int idx = tid; idx < 4 * P; idx += kSmThreads) {
-        const int d = idx >> 2, own = (idx >> 1) & 1, x = idx & 1;
-        const int32_t s0 = in[1 + d], s1 = in[P + 2 + d];
-        const int64_t nm = (own ? n1 : n0) - 1, sm = own ? s1 : s0, np = own ? n0 : n1, sp = own ? s0 : s1;
-        const double denm = log_(bg + (double)nm), denp = log_(bg + (double)np);
-        // (a member with x = 1 is one of the sm rows, one with x = 0 one of the nm + 1 - sm: the other entries are never read)
-        double m = 0.0;
-        if (x) { if (sm >= 1) m = term_x1(p.beta, sm - 1, denm); }
-        else if (sm <= nm) m = term_x0(p.gamma, nm, sm, denm);
-        const double pl = x ? term_x1(p.beta, sp, denp) : term_x0(p.gamma, np, sp, denp);
-        D[idx] = own ? pl - m : m - pl;
-    }
-    for (int i = tid; i < 2 * (P + 1); i += kSmThreads) hist[i] = 0;
-    if (tid < 2) base[tid] = log_((double)(n0 - (tid == 0)) + g.a) - log_((double)(n1 - (tid == 1)) + g.a);
-    __syncthreads();
-    int ns = sd & 1;
-    if (member) {
-        const int own = sd;
-        double acc = base[own];
-        const int W = (P + 31) >> 5;
-        for (int w = 0; w < W; ++w) {
-            const uint32_t bits = a.Xb[(int64_t)w * N + r];
-            const int nd = P - w * 32 < 32 ? P - w * 32 : 32;
-            for (int q = 0; q < nd; ++q) {
-                const double4 e = *reinterpret_cast<const double4*>(D + 4 * (size_t)(w * 32 + q));  // one address for the wave
-                const bool x = (bits >> q) & 1u;
-                acc = acc + (own ? (x ? e.w : e.z) : (x ? e.y : e.x));
-            }
-        }
-        double lp0, lp1;
-        sm_side_logp(acc, lp0, lp1);
-        if (score_only) {
-            a.lq[r] = a.z[r] == a.cell->label_a ? lp0 : lp1;
-        } else {
-            const double u = sm_member_uniform(a.cell->salt, (uint64_t)(p.obs0 + r), (uint32_t)t);
-            ns = u < exp_(lp0) ? 0 : 1;
-            a.side[r] = (uint8_t)ns;
-            if (final) a.lq[r] = ns ? lp1 : lp0;
-        }
-    }
-    if (score_only) return;
-    sm_count_wave(counted, ns, a.Xb, N, P, r, hist, lane);
-    __syncthreads();
-    sm_flush(hist, P, a.stat + (size_t)t * sm_set(P), tid);
-}
-
-// One workgroup: k_sm_decide's sums for log q and the marginal-likelihood ratio, term for term and in its order; the
-// prior ratio is the spec's as_log_prior.
-__global__ __launch_bounds__(1024) void k_as_decide(ChainParams p, AsArgs g) {
-    __shared__ double sh[2][1024];
-    const SmArgs& a = g.s;
-    const int t = threadIdx.x, P = p.P;
-    AsCell* const cell = g.cell;
-    SmCell* const c = &cell->m;
-    const int kind = c->kind;
-    if (kind == SM_SKIPPED) {
-        if (t == 0) a.counters[4] += 1;
-        return;
-    }
-    const int la = c->label_a, lb = c->label_b;
-    const int32_t* const fin = a.stat + (size_t)(a.scans + 1) * sm_set(P);
-    const bool split = kind == SM_SPLIT;
-    const int64_t no0 = a.Nk[la], no1 = split ? 0 : a.Nk[lb];
-    const int64_t nn0 = split ? fin[0] : no0 + no1, nn1 = split ? fin[P + 1] : 0;
-    double lq = 0.0, ll = 0.0;
-    for (int64_t i = t; i < p.N; i += 1024) lq = lq + a.lq[i];
-    for (int d = t; d < P; d += 1024) {
-        const int64_t so0 = a.S[(size_t)la * P + d], so1 = split ? 0 : a.S[(size_t)lb * P + d];
-        const int64_t sn0 = split ? fin[1 + d] : so0 + so1, sn1 = split ? fin[P + 2 + d] : 0;
-        double term;
-        if (split) term = (sm_pair(p.beta, p.gamma, nn0, sn0) + sm_pair(p.beta, p.gamma, nn1, sn1)) - sm_pair(p.beta, p.gamma, no0, so0);
-        else term = sm_pair(p.beta, p.gamma, nn0, sn0) - (sm_pair(p.beta, p.gamma, no0, so0) + sm_pair(p.beta, p.gamma, no1, so1));
-        ll = ll + term;
-    }
-    sh[0][t] = lq; sh[1][t] = ll;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if (t < s) { sh[0][t] = sh[0][t] + sh[0][t + s]; sh[1][t] = sh[1][t] + sh[1][t + s]; }
-        __syncthreads();
-    }
-    if (t != 0) return;
-    const double bg = p.beta + p.gamma;
-    const double c0 = (lgamma_(bg) - lgamma_(p.beta)) - lgamma_(p.gamma);
-    const double log_q = sh[0][0];
-    double cst;
-    if (split) cst = ((c0 - lgamma_(bg + (double)nn0)) - lgamma_(bg + (double)nn1)) + lgamma_(bg + (double)no0);
-    else cst = ((lgamma_(bg + (double)no0) + lgamma_(bg + (double)no1)) - lgamma_(bg + (double)nn0)) - c0;
-    const int K = cell->k_before;
-    const double log_prior = split ? as_log_prior(K, (double)p.Ntot, g.a, g.log_prior_k, no0, nn0, nn1, true)
-                                   : as_log_prior(K, (double)p.Ntot, g.a, g.log_prior_k, nn0, no0, no1, false);
-    const double log_lik = sh[1][0] + (double)P * cst;
-    const double log_r = split ? (log_prior + log_lik) - log_q : (log_prior + log_lik) + log_q;
-    const int acc = c->log_u < log_r ? 1 : 0;
-    c->log_prior = log_prior; c->log_lik = log_lik; c->log_q = log_q; c->log_r = log_r; c->accepted = acc;
-    c->n_after[0] = nn0; c->n_after[1] = nn1;
-    const int32_t* const first = a.stat;
-    c->members = (long long)first[0] + first[P + 1] - 2;
-    cell->k_after = acc ? (split ? K + 1 : K - 1) : K;
-    cell->moved = acc && !split && lb != K - 1 ? K - 1 : -1;
-    a.counters[split ? 0 : 2] += 1;
-    if (acc) a.counters[split ? 1 : 3] += 1;
-}
-
-// An accepted move.  Every workgroup relabels its own rows from the record alone: a split gives the rows of side 1
-// label K; a merge gives the rows of lb label la and then, as an absorb, the rows of label K - 1 the freed label lb
-// (with la == K - 1 the merged component ends up under lb).  Workgroup 0 writes the exact integer statistics of the
-// labels touched and the K cell, which no other workgroup reads.  A rejected or skipped move: nothing.
-__global__ __launch_bounds__(kSmThreads) void k_as_commit(ChainParams p, AsArgs g) {
-    const AsCell* const cell = g.cell;
-    const SmCell* const c = &cell->m;
-    if (!c->accepted) return;
-    const SmArgs& a = g.s;
-    const int P = p.P, tid = threadIdx.x, la = c->label_a, lb = c->label_b, last = cell->k_before - 1;
-    const bool split = c->kind == SM_SPLIT;
-    const int64_t r = (int64_t)blockIdx.x * kSmThreads + tid;
-    if (r < p.N) {
-        if (split) {
-            const int sd = a.side[r];
-            if (sd == 1 || sd == 3) a.z[r] = lb;
-        } else {
-            const int zr = a.z[r];
-            if (zr == lb) a.z[r] = (la == last && lb != last) ? lb : la;
-            else if (zr == last && lb != last) a.z[r] = lb;
-        }
-    }
-    if (blockIdx.x != 0) return;
-    const int32_t* const fin = a.stat + (size_t)(a.scans + 1) * sm_set(P);
-    for (int idx = tid; idx <= P; idx += kSmThreads) {
-        int32_t* const A = idx == 0 ? a.Nk + la : a.S + (size_t)la * P + (idx - 1);
-        int32_t* const B = idx == 0 ? a.Nk + lb : a.S + (size_t)lb * P + (idx - 1);
-        if (split) {
-            *A = fin[idx]; *B = fin[P + 1 + idx];
-        } else {  // in this order: la may be the last label
-            int32_t* const Z = idx == 0 ? a.Nk + last : a.S + (size_t)last * P + (idx - 1);
-            const int32_t s = *A + *B;
-            *A = s; *B = 0;
-            if (lb != last) { *B = *Z; *Z = 0; }
-        }
-    }
-    if (tid == 0) *g.K = cell->k_after;
-}
+// DESIGN.md section 24): the ALLOC flavour of k_sm_launch / k_sm_scan / k_sm_decide / k_sm_commit above.
 
 // ---- ECR relabelling from the label trace alone (include/bmm_mcmc.h "ECR") -----------------
 // Label rows as the partition kernels hold them: 0-based, row t at lab + t * pitch, either the resident int32 trace

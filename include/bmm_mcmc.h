@@ -836,7 +836,7 @@ int bmm_last_split_merge_stats(int64_t out[5]);
  * inclusion[d] is the mean of the draws over the folded steps, inclusion_rb[d] the mean of p_d (the Rao-Blackwellised
  * estimate of the same probability; one binary64 add per step, so one seed gives the same bits twice).
  * A chain that was never given a mask enqueues exactly what it always did.  A chain with a mask builds its tables with
- * the masked twin of the table kernel and never takes the form whose workgroups build their own tables
+ * the masked flavour of the table kernel and never takes the form whose workgroups build their own tables
  * (bmm_chain_kernel_form reports what runs); its values with the all-ones mask are those of a chain without one.
  * Refused: the stick-breaking and full samplers (they carry theta) and a run of the DP sampler with beta != gamma (its
  * new-cluster term is the model's only when they are equal; a resident DP chain is created with beta == gamma only)
@@ -945,7 +945,7 @@ int bmm_last_init_info(bmm_init_info* info);
  * COMPONENT (not alpha / K); theta_kd ~ Beta(beta, gamma).  With the weights and theta integrated out,
  *   log pi(K, z) = log p(K) + lgamma(K a) - lgamma(K a + N) + sum_k [lgamma(a + n_k) - lgamma(a)] + sum_k L(k),
  * L the L(c) of the split-merge section, 0 for an empty label.
- *   sweep   the finite sampler's sweep with the table build k_alloc_tables: label k < K scores log(n + a) - log(N - 1
+ *   sweep   the finite sampler's sweep with the table build k_count_tables<TAB_ALLOC>: label k < K scores log(n + a) - log(N - 1
  *           + K a) plus the Beta-Bernoulli terms of its statistics -- the prior terms when it is empty, so an emptied
  *           label can be taken again; the row's own label with the row removed, log(n - 1 + a) - ..., so a row that
  *           sits alone keeps its label at prior weight; labels from K on are closed.  K is read from the device: no
@@ -1257,7 +1257,7 @@ int bmm_device_log_joint(int device, const int32_t* X, int64_t N, int P, int sam
  * Refused with BMM_E_UNSUPPORTED, before anything is touched: stick-breaking, full and allocation chains, a chain with
  * a feature mask, split-merge moves on any rung, a sharded chain, rungs on different devices.  Armed chains refuse
  * those options in turn. */
-/* on: the chain's table builds run the tempered twin at inv_temp (0 < inv_temp <= 1; on with 1.0 runs the twin kernel
+/* on: the chain's table builds run the tempered flavour at inv_temp (0 < inv_temp <= 1; on with 1.0 runs that kernel
  * and gives an unarmed chain's bits); off: the chain is as it was.  Between sweeps, any time. */
 int bmm_chain_set_temper(bmm_chain* c, int on, double inv_temp);
 int bmm_chain_get_temper(const bmm_chain* c, int* on, double* inv_temp);

@@ -1,4 +1,4 @@
-"""The shapes at which tests/test_gpu_alloc_sweep.py holds the allocation sampler's sweep (k_alloc_tables and the
+"""The shapes at which tests/test_gpu_alloc_sweep.py holds the allocation sampler's sweep (k_count_tables<TAB_ALLOC> and the
 resample kernels behind it) to the oracle chain oracle.alloc bit for bit, and what each of them is there to reach.
 
 A label's weight shows in the drawn labels only when it is not negligible, so the data make empty labels and rows that

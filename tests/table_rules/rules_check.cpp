@@ -8,7 +8,7 @@
 // kGroupWm -- and compares them with score[] of oracle_collapsed_cond_spec (oracle/bmm_oracle.c).  The oracle's scores
 // are that table arithmetic, so equality is exact (-inf equals -inf).  The stored-state rules share every function
 // with this one; their values are held on the device (tests/test_gpu_predict.py, tests/test_gpu_loo.py, the pins).
-// k_count_tables and k_alloc_tables do not call these functions; the oracle chains hold them on the device
+// k_count_tables (any flavour) does not call these functions; the oracle chains hold it on the device
 // (tests/test_gpu_parity.py, tests/test_gpu_alloc_sweep.py).
 //
 // The labels leave one label empty and one with a single row, one label has a feature nobody shows and a feature

@@ -1,6 +1,6 @@
-"""Code-object metadata of the kernels of the allocation sampler's split-merge move in the built gfx950 library
-(DESIGN.md section 24): no private segment, no dynamic stack, no register spills of either kind; and the DP chain's scan,
-whose body they share, keeps none either."""
+"""Code-object metadata of the split-merge kernels in the built gfx950 library (DESIGN.md sections 15 and 24), both
+flavours of each -- the DP chain's (ILb0E) and the allocation chain's (ILb1E): no private segment, no dynamic stack, no
+register spills of either kind."""
 import re
 
 import pytest
@@ -8,7 +8,7 @@ import pytest
 from test_feature_select_codeobj import kernels  # noqa: F401  (the fixture)
 
 
-@pytest.mark.parametrize("pattern", ["k_as_launch", "k_as_scan", "k_as_decide", "k_as_commit", "k_sm_scan"])
+@pytest.mark.parametrize("pattern", ["k_sm_%sILb%dE" % (k, f) for f in (1, 0) for k in ("launch", "scan", "decide", "commit")])
 def test_no_private_segment_and_no_spills(kernels, pattern):  # noqa: F811
     names = [n for n in kernels if pattern in n]
     assert len(names) == 1, names

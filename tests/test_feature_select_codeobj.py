@@ -34,8 +34,9 @@ def kernels(tmp_path_factory):
     return out
 
 
-# the sweep's table builds: masked, unmasked, and the allocation sampler's twin
-@pytest.mark.parametrize("pattern", ["k_fs_gamma", "k_count_tablesILb1E", "k_count_tablesILb0E", "k_alloc_tables"])
+# the gamma-step, and every flavour of the sweep's table build (TAB_PLAIN, TAB_MASK, TAB_ALLOC, TAB_TEMPER)
+@pytest.mark.parametrize("pattern", ["k_fs_gamma", "k_count_tablesILi0E", "k_count_tablesILi1E", "k_count_tablesILi2E",
+                                     "k_count_tablesILi3E"])
 def test_no_private_segment_and_no_spills(kernels, pattern):
     names = [n for n in kernels if pattern in n]
     assert len(names) == 1, names

@@ -1,4 +1,4 @@
-"""The allocation sampler's sweep on the device (k_alloc_tables and the resample kernels that draw from its image;
+"""The allocation sampler's sweep on the device (k_count_tables<TAB_ALLOC> and the resample kernels that draw from its image;
 include/bmm_mcmc.h "allocation sampler": sweep) against the oracle chain oracle.alloc, bit for
 bit: equal labels after every sweep, at the shapes of tests/alloc_sweep_cases.py, on every kernel form an armed chain
 can take, with K changed between the sweeps by set_k and by the moves.  Everything compared is an integer or a ratio

@@ -92,7 +92,7 @@ def test_tempered_probabilities_equal_the_restatement(bmm, N, P, K, sampler, lay
 @pytest.mark.parametrize("layout", ["bits", "int32"])
 @pytest.mark.parametrize("sampler", ["collapsed", "dp"])
 def test_tempered_probabilities_at_the_table_edges(bmm, sampler, layout):
-    """The edges of k_temper_tables on purpose (tests/temper_ref.py edge_case): an empty label (n = 0: both constants
+    """The edges of k_count_tables<TAB_TEMPER> on purpose (tests/temper_ref.py edge_case): an empty label (n = 0: both constants
     -inf, no term), a singleton (n = 1: nothing left with its row removed), a pair, a column of zeros (s = 0) and a
     column of ones (s = n) in every label.  The finite chain holds the allocation as its starting labels (only a DP
     chain takes labels between sweeps), so its first table build also folds the counts from the delta replicas.

@@ -5,7 +5,7 @@ oracle_collapsed_cond_spec -- exactly, -inf equal to -inf: the oracle's scores a
 
 Reached, and counted by the program (a guard that never fired fails it): an empty label; a single-row label scored by
 its own row and by another; features with s = 0 and s = n under the minus-self guards; P = 125; both group widths.
-(k_count_tables and k_alloc_tables write their terms out themselves and are held to the oracle chains on the device.)"""
+(k_count_tables writes its terms out itself in all four flavours and is held to the oracle chains on the device.)"""
 import os
 import subprocess
 import sys
