@@ -11,6 +11,7 @@ There is no CPU fallback: without the built HIP library and a gfx950 device ever
 sampler call raises.
 """
 import ctypes as _C
+import threading as _threading
 from collections import namedtuple as _namedtuple
 
 import numpy as _np
@@ -22,7 +23,7 @@ from .rdata import read_rdata_matrix  # the package's bundled data sets (data/*.
 __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "Chain", "BmmError", "NA_INTEGER", "set_progress",
            "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
            "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
-           "partition_distances", "posterior_similarity", "partition_plan", "partition_search", "partition_search_plan", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
+           "partition_distances", "posterior_similarity", "partition_plan", "partition_search", "partition_search_plan", "credible_ball", "credible_ball_plan", "run_options", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
            "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat", "pair_check", "pair_check_plan", "pair_check_pairs", "PAIR_CHECK_MAX_M", "run_bytes", "summary_plan", "Ladder", "temper_ladder", "TEMPER_MAX_RUNGS"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
@@ -176,6 +177,50 @@ class _Option:
     def into(self, out):
         out[self.key] = self.result()
         return out
+
+
+_RUN_OPTIONS = ("credible_ball",)
+_run_options = _threading.local()
+
+
+class run_options:
+    """Options of the gibbs_* calls made inside the block by this thread, beside their own keywords:
+
+        with bm.run_options(credible_ball={"level": 0.9, "membership_of": rows}):
+            out = bm.gibbs_dp(X, 1000, partition="vi", partition_search=True)
+        out["partition"]["credible_ball"]
+
+    `credible_ball=True` (level 0.95; needs partition= on the call), a level in (0, 1], or a dict of `level`,
+    `membership`, `membership_of`: how sure the clustering estimate is (credible_ball(); include/bmm_mcmc.h "credible
+    ball").  After the summary and the search the device measures every kept sweep's distance to
+    the estimate -- the searched partition with partition_search=, else the visited sweep -- and `partition` gains
+    `credible_ball = {"level", "criterion", "centre" ("search" or "visited"), "radius", "n_in", "n_used", "distance",
+    "binder2", "n_clusters", and "horizontal", "upper", "lower": {"sweep" (row of z), "ties", "n_clusters", "distance",
+    "z"}}`; with `membership=True` (all rows) or `membership_of=` (rows 0 .. N-1) also "sim", "membership", "sizes",
+    "rows": the similarity of rows to the clusters of the estimate, a soft membership that needs no relabelling.
+    Everything else is that of the run without it.  Taken by every wrapper that takes partition= (the four gibbs_*
+    samplers and gibbs_allocation); at most 64 categories; not with keep_trace=False.  With `chains > 1` it is computed
+    once over the pooled traces.  An unknown option is refused by name.  Blocks nest: the inner one wins, and the outer
+    options are back when it ends."""
+
+    def __init__(self, **options):
+        bad = sorted(set(options) - set(_RUN_OPTIONS))
+        if bad:
+            raise ValueError("run_options: unknown option %s (known: %s)" % (bad[0], ", ".join(_RUN_OPTIONS)))
+        self.options = options
+
+    def __enter__(self):
+        self.saved = getattr(_run_options, "now", {})
+        _run_options.now = {**self.saved, **self.options}
+        return self
+
+    def __exit__(self, *exc):
+        _run_options.now = self.saved
+        return False
+
+
+def _run_option(name):
+    return getattr(_run_options, "now", {}).get(name)
 
 
 def _arm(options):
@@ -611,6 +656,214 @@ def _pooled_search(chains_out, kw, partition, K, device):
     zz = _np.asfortranarray(_np.concatenate(rows, axis=0))
     res = partition_search(zz, partition, start=chains_out[0]["partition"]["z"], device=device, Kc=K, **kw)
     chains_out[0]["partition"]["search"] = res  # (one dict shared by every chain object)
+    return chains_out
+
+
+# ---------------------------------------------------------------- credible_ball=: how sure the point estimate is
+_CB_KEYS = ("level", "membership", "membership_of")
+_CB_BOUNDS = ("horizontal", "upper", "lower")
+
+
+class _BallBound(_C.Structure):  # bmm_credible_bound
+    _fields_ = [(k, _C.c_void_p) for k in ("sweep", "ties", "n_clusters", "dist", "d2", "z")]
+
+
+class _BallOut(_C.Structure):  # bmm_credible_ball_out
+    _fields_ = [("d2", _C.c_void_p), ("dist", _C.c_void_p), ("n_clusters", _C.c_void_p), ("radius", _C.c_void_p),
+                ("radius2", _C.c_void_p), ("n_in", _C.c_void_p), ("horizontal", _BallBound), ("upper", _BallBound),
+                ("lower", _BallBound), ("sim", _C.c_void_p), ("member_idx", _C.c_void_p), ("member_M", _C.c_int64),
+                ("sizes", _C.c_void_p)]
+
+
+def _ball_opts(credible_ball, N):
+    """credible_ball= as (level, membership, membership_of): True, a level, or a dict of the three"""
+    if credible_ball is True:
+        kw = {}
+    elif isinstance(credible_ball, dict):
+        kw = dict(credible_ball)
+    else:
+        kw = {"level": credible_ball}
+    bad = sorted(set(kw) - set(_CB_KEYS))
+    if bad:
+        raise ValueError("credible_ball: unknown option %s (known: %s)" % (bad[0], ", ".join(_CB_KEYS)))
+    return _ball_level(kw.get("level", 0.95)), bool(kw.get("membership", False)), _ball_rows(kw.get("membership_of"), N)
+
+
+def _ball_level(level):
+    level = float(level)
+    if not 0.0 < level <= 1.0:
+        raise ValueError("credible_ball: level must be in (0, 1]")
+    return level
+
+
+def _ball_rows(membership_of, N):
+    if membership_of is None:
+        return None
+    idx = _np.ascontiguousarray(membership_of, dtype=_np.int64).ravel()
+    if idx.size < 1 or idx.min() < 0 or idx.max() >= N:
+        raise ValueError("credible_ball: membership_of must be observations 0 .. N-1, at least one")
+    return idx
+
+
+class _Ball(_Option):
+    """Outputs of a credible ball (bmm_device_credible_ball, or armed with bmm_set_credible_ball for a run): S draws
+    at most, N observations, Ka slots of the centre."""
+
+    def __init__(self, criterion, level, S, N, Ka, membership=False, rows=None, centre="visited"):
+        self.criterion, self.level, self.centre, self.S = criterion, level, centre, S
+        self.d2 = _np.zeros(S, dtype=_np.uint64)
+        self.dist = _np.full(S, _np.nan)
+        self.k = _np.zeros(S, dtype=_np.int32)
+        self.f64 = _np.full(4, _np.nan)               # radius, and the distance of the three bounds
+        self.u64 = _np.zeros(4, dtype=_np.uint64)     # radius2, and d2 of the three bounds
+        self.i32 = _np.full(10, -1, dtype=_np.int32)  # n_in, then sweep, ties, n_clusters of each bound
+        self.zb = _np.zeros((3, N), dtype=_np.int32)
+        self.sizes = _np.zeros(Ka, dtype=_np.int64)
+        self.rows = rows
+        self.sim = None
+        if membership or rows is not None:
+            self.sim = _np.zeros((N if rows is None else rows.size, Ka), dtype=_np.uint64)
+        bounds = [_BallBound(self.i32.ctypes.data + 4 * (1 + 3 * q), self.i32.ctypes.data + 4 * (2 + 3 * q),
+                             self.i32.ctypes.data + 4 * (3 + 3 * q), self.f64.ctypes.data + 8 * (1 + q),
+                             self.u64.ctypes.data + 8 * (1 + q), self.zb[q].ctypes.data) for q in range(3)]
+        self.s = _BallOut(self.d2.ctypes.data, self.dist.ctypes.data, self.k.ctypes.data, self.f64.ctypes.data,
+                          self.u64.ctypes.data, self.i32.ctypes.data, bounds[0], bounds[1], bounds[2],
+                          None if self.sim is None else self.sim.ctypes.data,
+                          None if rows is None else rows.ctypes.data, 0 if rows is None else rows.size,
+                          self.sizes.ctypes.data)
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_credible_ball(_C.c_double(self.level), _C.byref(self.s)))
+
+    def result(self, n_used=None):
+        if int(self.i32[0]) < 0:  # the run had no usable row: there is no ball
+            return None
+        nu = self.S if n_used is None else int(n_used)
+        out = {"level": self.level, "criterion": self.criterion, "centre": self.centre, "radius": float(self.f64[0]),
+               "n_in": int(self.i32[0]), "n_used": nu, "distance": self.dist[:nu],
+               "binder2": _np.array([int(v) for v in self.d2[:nu]], dtype=object), "n_clusters": self.k[:nu]}
+        for q, name in enumerate(_CB_BOUNDS):
+            out[name] = {"sweep": int(self.i32[1 + 3 * q]), "ties": int(self.i32[2 + 3 * q]),
+                         "n_clusters": int(self.i32[3 + 3 * q]), "distance": float(self.f64[1 + q]), "z": self.zb[q]}
+        if self.sim is not None:
+            out.update(_membership(self.sim, self.sizes, self.rows, nu, self._centre_labels))
+        return out
+
+    _centre_labels = None
+
+    def into(self, out):
+        """the ball of a single-chain run beside the summary, around the searched partition where there is one"""
+        pt = out.get("partition")
+        if pt is None:
+            return out
+        self._centre_labels = pt["search"]["z"] if "search" in pt else pt["z"]
+        res = self.result(pt["n_used"])
+        if res is not None:
+            pt["credible_ball"] = res
+        return out
+
+
+def _membership(sim, sizes, rows, S, centre):
+    """membership[u, a] = (sim[u, a] - S own) / (S (n_a - own)), own = [a = c_u]: NaN for an empty slot and for a row
+    alone in its cluster"""
+    rows = _np.arange(sim.shape[0], dtype=_np.int64) if rows is None else rows
+    own = _np.zeros(sim.shape, dtype=_np.int64)
+    own[_np.arange(rows.size), _np.asarray(centre, dtype=_np.int64)[rows] - 1] = 1
+    den = (float(S) * (sizes[None, :] - own)).astype(_np.float64)
+    num = sim.astype(_np.int64) - S * own
+    with _np.errstate(divide="ignore", invalid="ignore"):
+        mem = _np.where(den > 0, num / _np.where(den > 0, den, 1.0), _np.nan)
+    return {"sim": sim, "membership": mem, "sizes": sizes, "rows": rows}
+
+
+def credible_ball(z, centre, criterion="vi", level=0.95, membership=False, membership_of=None, device=0, Kc=None,
+                  max_clusters=None):
+    """Credible ball of Wade & Ghahramani (2018) around the partition `centre`, and the similarity of rows to its
+    clusters, on the device (include/bmm_mcmc.h "credible ball").  z: S x N labels, 1-based, as
+    partition_distances takes them; centre: N labels in 1 .. max_clusters (default: the larger of Kc and the largest
+    label of centre, at most 64), e.g. partition["z"] or partition["search"]["z"].  The draws are ordered by their Binder
+    or VI distance to the centre; the radius is the distance of draw ceil(level S) in that order, ties at the radius are
+    all inside.  Returns {"level", "criterion", "centre" ("given"), "radius", "n_in", "n_used" (S), "distance" (S,): B
+    or VI in nats per draw, "binder2" (S,): 2 B as Python integers under either criterion, "n_clusters" (S,): non-empty
+    clusters per draw, "horizontal", "upper", "lower": {"sweep", "ties", "n_clusters", "distance", "z"}} -- the draw
+    of the ball farthest from the centre, and the farthest among those with the fewest and with the most clusters, the
+    lowest row on ties and how many tie.  `membership=True` (all rows) or `membership_of=` (rows 0 .. N-1, any order,
+    repeats allowed) adds "sim" (M, Ka) uint64: how often the row sat with each member of each cluster of the centre,
+    summed over draws and members (the row itself included S times in its own cluster), "membership" (M, Ka): the mean
+    posterior similarity of the row to the other members of each cluster (NaN for an empty cluster and for a row alone
+    in its own) -- a soft membership that needs no relabelling and works for gibbs_dp --, "sizes" (Ka,) and "rows".
+    Kc: number of categories of z (default: the largest label), at most 64."""
+    z = _as_trace(z)
+    S, N = z.shape
+    code = _criterion(criterion)
+    level = _ball_level(level)
+    rows = _ball_rows(membership_of, N)
+    c = _np.ascontiguousarray(centre, dtype=_np.int32)
+    if c.shape != (N,):
+        raise ValueError("centre must have one label per observation")
+    Kc = max(1, int(z.max())) if Kc is None else int(Kc)
+    Ka = max(Kc, int(c.max())) if max_clusters is None else int(max_clusters)
+    if Ka < 1 or Ka > PARTITION_SEARCH_MAX_K:
+        raise ValueError("credible_ball: max_clusters must be in 1 .. %d" % PARTITION_SEARCH_MAX_K)
+    b = _Ball(criterion, level, S, N, Ka, membership, rows, centre="given")
+    _capi.check(_capi.lib().bmm_device_credible_ball(
+        _C.c_int(device), _capi.vp(z), _C.c_int(S), _C.c_int64(N), _C.c_int(Kc), _C.c_int(code), _capi.vp(c),
+        _C.c_int(Ka), _C.c_double(level), _C.byref(b.s)))
+    b._centre_labels = c
+    return b.result()
+
+
+_CB_PLAN_FIELDS = ("label_bytes", "slot_stride", "threads_per_row", "rows_per_workgroup", "draws_per_block", "draw_blocks",
+                   "block_bound", "lds_bytes", "workgroups", "gathered", "vi", "table_bytes")
+
+
+def credible_ball_plan(S, N, Kc, max_clusters=None, criterion="vi", rows=None):
+    """Which form of the credible-ball kernels a shape runs, read from the library's launch arithmetic without touching
+    a device (bmm_credible_ball_plan): a dict of the fields include/bmm_mcmc.h lists.  `rows`: how many rows the
+    similarity is asked for (default all N, read from the label block; fewer are gathered first); "block_bound" as
+    partition_search_plan."""
+    out = (_C.c_int64 * 12)()
+    N = int(N)
+    Ka = int(Kc) if max_clusters is None else int(max_clusters)
+    M = N if rows is None else int(rows)
+    _capi.check(_capi.lib().bmm_credible_ball_plan(_C.c_int(int(S)), _C.c_int64(N), _C.c_int(int(Kc)), _C.c_int(Ka),
+                                                   _C.c_int(_criterion(criterion)), _C.c_int64(M), out))
+    return dict(zip(_CB_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def _make_ball(credible_ball, partition, search, keep_trace, N, S, K, chains):
+    """credible_ball= of run_options for a wrapper, checked before any device is touched: True (level 0.95), a level, or a dict of
+    level, membership, membership_of.  One chain: the outputs to arm; several: the options (pooled afterwards)."""
+    if credible_ball is None or credible_ball is False:
+        return None
+    if partition is None:
+        raise ValueError('credible_ball= needs partition="binder" or "vi"')
+    if not keep_trace:
+        raise ValueError("keep_trace=False drops the label trace, which credible_ball= reads")
+    level, membership, rows = _ball_opts(credible_ball, N)
+    if K > PARTITION_SEARCH_MAX_K:
+        raise ValueError("credible_ball= takes at most %d categories (got %d)" % (PARTITION_SEARCH_MAX_K, K))
+    if int(chains) > 1:
+        return {"level": level, "membership": membership, "membership_of": rows}
+    Ka = K if search is None else search.opts.max_clusters
+    return _Ball(partition, level, S, N, Ka, membership, rows, centre="visited" if search is None else "search")
+
+
+def _pooled_ball(chains_out, kw, ps_kw, partition, K, device):
+    """chains > 1: the ball over the stacked traces _pooled used, around the pooled centre, through the stand-alone call"""
+    if kw is None:
+        return chains_out
+    rows = []
+    for o in chains_out:
+        z = o["z"]
+        rows.append(z[[s for s in range(z.shape[0]) if z[s].min() >= 1]])
+    zz = _np.asfortranarray(_np.concatenate(rows, axis=0))
+    pt = chains_out[0]["partition"]
+    searched = "search" in pt
+    Ka = _search_opts(zz.shape[1], K, **ps_kw).max_clusters if searched else K
+    res = credible_ball(zz, pt["search"]["z"] if searched else pt["z"], partition, device=device, Kc=K, max_clusters=Ka, **kw)
+    res["centre"] = "search" if searched else "visited"
+    pt["credible_ball"] = res  # (one dict shared by every chain object)
     return chains_out
 
 
@@ -1398,6 +1651,7 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
         raise ValueError("initial_K must have one label per observation")
     S = nsamples - burnin
     pt = _make_partition(partition, partition_stride, similarity_of, N, S, 1)
+    cb = _make_ball(_run_option("credible_ball"), partition, None, True, N, S, maxK, 1)
     z = _np.empty((S, N), dtype=_np.int32, order="F")
     theta = _np.zeros((maxK, P, S), order="F")
     Ks = _np.zeros(S, dtype=_np.int32)
@@ -1409,7 +1663,7 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
             raise ValueError('gibbs_allocation offers no relabelling (relabel must be False)')
         ec = _Ecr(ecr_req, N, maxK, P, S)  # armed below: the library refuses the run
     lj = _LogPost(N, S) if logpost else None
-    _arm((ec, pt, lj, sm))
+    _arm((ec, pt, cb, lj, sm))
     _capi.check(_capi.lib().bmm_alloc_run(
         _capi.vp(X), _C.c_int64(N), _C.c_int(P), _capi.vp(z0), _C.c_int(nsamples), _C.c_int(maxK), _C.c_double(a),
         _C.c_double(beta), _C.c_double(gamma), _capi.vp(lp), _C.c_int(K0), _C.c_int(int(moves)), _C.c_double(eject_a),
@@ -1418,7 +1672,7 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
     used = _np.array([len(_np.unique(row)) for row in z], dtype=_np.int32)
     out = {"z": z, "theta": theta, "K": Ks, "k_posterior": _np.bincount(Ks, minlength=maxK + 1)[1:] / float(S), "k_used": used,
            "moves": dict(zip(_EA_FIELDS, (int(v) for v in counts)))}
-    return _collect(out, (sm, pt, lj))
+    return _collect(out, (sm, pt, cb, lj))
 
 
 # ---------------------------------------------------------------- select_features=: noise features (White, Wyse & Murphy 2016)
@@ -1784,8 +2038,8 @@ def _run_args(spec, X, start, nsamples, K, alpha, beta, gamma, a, b, burnin, bat
 def _gibbs(spec, data, nsamples, K, *, alpha, beta, gamma, a, b, burnin, relabel, burnrelabel, debug, seed, device, chains,
            devices, stephens, newdata, predictive_trace, responsibilities, partition, partition_stride, similarity_of, loo,
            ecr_pivot, ecr_max_iter, logpost, pair_check, pair_check_stride, pair_check_trace, missing, known, allowed,
-           summary, summary_pivot, summary_stride, keep_trace, partition_search, newdata_missing, batch=None, initial_K=None,
-           initial_pi=None, initial_theta=None, init="random", init_iters=INIT_ITERS, select_features=False, rho=0.5,
+           summary, summary_pivot, summary_stride, keep_trace, partition_search, newdata_missing, credible_ball=None, batch=None,
+           initial_K=None, initial_pi=None, initial_theta=None, init="random", init_iters=INIT_ITERS, select_features=False, rho=0.5,
            split_merge=0, split_merge_scans=None, temper=None, swap_every=1, temper_hottest=0.1):
     """The run behind gibbs_collapsed, gibbs_dp, gibbs_stickbreaking and gibbs_full (K: K or maxK): the keywords parsed
     into the run's options and refused where they do not go together, several chains handed to the multi-chain call and
@@ -1811,6 +2065,7 @@ def _gibbs(spec, data, nsamples, K, *, alpha, beta, gamma, a, b, burnin, relabel
                                                newdata_missing, burnin)
     pt = _make_partition(partition, partition_stride, similarity_of, N, S, chains)
     ps = _make_search(partition_search, partition, N, K, chains)
+    cb = _make_ball(credible_ball, partition, ps, keep_trace, N, S, K, chains)
     features = (select_features, rho, P, S, chains, beta, gamma, spec is _DP, newdata, loo, split_merge)
     if spec is _COLLAPSED:  # (whose refusals of select_features= have always come ahead of those of loo=; gibbs_dp: behind them)
         fs = _make_features(*features)
@@ -1848,7 +2103,8 @@ def _gibbs(spec, data, nsamples, K, *, alpha, beta, gamma, a, b, burnin, relabel
         outs = _multi(spec.name, X, chains, devices, z0s, pi0s, th0s, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, with_pi)
         if lp is not None:
             _lp_chains(outs, X, spec.name, K, alpha, beta, gamma, a, b, dev0)
-        outs = _ecr_chains(_pooled_search(_pooled(outs, partition, partition_stride, similarity_of, dev0), ps, partition, K, dev0), ecr_req, K, dev0)
+        outs = _pooled_search(_pooled(outs, partition, partition_stride, similarity_of, dev0), ps, partition, K, dev0)
+        outs = _ecr_chains(_pooled_ball(outs, cb, ps, partition, K, dev0), ecr_req, K, dev0)
         if ecr_map is not None:
             outs = _ecr_map(outs, ecr_map, K, dev0)
         for o, info in zip(outs, infos):
@@ -1876,7 +2132,7 @@ def _gibbs(spec, data, nsamples, K, *, alpha, beta, gamma, a, b, burnin, relabel
     pi = _np.zeros((S, K), order="F") if with_pi else None
     args = _run_args(spec, X, start, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, device, pi, z, theta, al)
     with _progress(debug):
-        rc = _run(spec.base, args, (sm, fs, pt, ps, lo, ec, lp, tp, pc, mi, cs, su, ini), pr,
+        rc = _run(spec.base, args, (sm, fs, pt, ps, cb, lo, ec, lp, tp, pc, mi, cs, su, ini), pr,
                   hooks=None if on_device else rel, rel=rel if on_device else None)
     out = {"alpha": al, "permutations": None if on_device else _na_perm(S, K), "z": z, "theta": theta}
     if with_pi:
@@ -1885,7 +2141,7 @@ def _gibbs(spec, data, nsamples, K, *, alpha, beta, gamma, a, b, burnin, relabel
         out = rel.finish(rc, out)
     else:
         _capi.check(rc)
-    return _collect(out, (ec, pr, pt, lo, su, ps, tp, sm, fs, ini, lp, pc, mi, cs))
+    return _collect(out, (ec, pr, pt, lo, su, ps, cb, tp, sm, fs, ini, lp, pc, mi, cs))
 
 
 def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
@@ -2037,7 +2293,7 @@ def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1
                   temper_hottest=temper_hottest, pair_check=pair_check, pair_check_stride=pair_check_stride,
                   pair_check_trace=pair_check_trace, missing=missing, known=known, allowed=allowed, summary=summary,
                   summary_pivot=summary_pivot, summary_stride=summary_stride, keep_trace=keep_trace,
-                  partition_search=partition_search, newdata_missing=newdata_missing)
+                  partition_search=partition_search, newdata_missing=newdata_missing, credible_ball=_run_option("credible_ball"))
 
 
 def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=None, relabel=False,
@@ -2077,7 +2333,7 @@ def gibbs_dp(data, nsamples, alpha=None, a=1, b=1, beta=0.5, gamma=0.5, burnin=N
                   temper_hottest=temper_hottest, pair_check=pair_check, pair_check_stride=pair_check_stride,
                   pair_check_trace=pair_check_trace, missing=missing, known=known, allowed=allowed, summary=summary,
                   summary_pivot=summary_pivot, summary_stride=summary_stride, keep_trace=keep_trace,
-                  partition_search=partition_search, newdata_missing=newdata_missing)
+                  partition_search=partition_search, newdata_missing=newdata_missing, credible_ball=_run_option("credible_ball"))
 
 
 def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
@@ -2108,7 +2364,7 @@ def gibbs_stickbreaking(data, nsamples, maxK, alpha=None, beta=0.5, gamma=0.5, a
                   ecr_max_iter=ecr_max_iter, logpost=logpost, pair_check=pair_check, pair_check_stride=pair_check_stride,
                   pair_check_trace=pair_check_trace, missing=missing, known=known, allowed=allowed, summary=summary,
                   summary_pivot=summary_pivot, summary_stride=summary_stride, keep_trace=keep_trace,
-                  partition_search=partition_search, newdata_missing=newdata_missing)
+                  partition_search=partition_search, newdata_missing=newdata_missing, credible_ball=_run_option("credible_ball"))
 
 
 def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None, relabel=False,
@@ -2134,7 +2390,7 @@ def gibbs_full(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, bur
                   ecr_max_iter=ecr_max_iter, logpost=logpost, pair_check=pair_check, pair_check_stride=pair_check_stride,
                   pair_check_trace=pair_check_trace, missing=missing, known=known, allowed=allowed, summary=summary,
                   summary_pivot=summary_pivot, summary_stride=summary_stride, keep_trace=keep_trace,
-                  partition_search=partition_search, newdata_missing=newdata_missing)
+                  partition_search=partition_search, newdata_missing=newdata_missing, credible_ball=_run_option("credible_ball"))
 
 
 class Chain:

@@ -35,6 +35,7 @@ SYMBOLS = [
     "bmm_set_newdata_missing", "bmm_predict_na_plan",
     "bmm_device_partition_distances", "bmm_device_psm", "bmm_device_partition_plan", "bmm_set_partition_summary",
     "bmm_device_partition_search", "bmm_partition_search_plan", "bmm_set_partition_search",
+    "bmm_device_credible_ball", "bmm_credible_ball_plan", "bmm_set_credible_ball",
     "bmm_chain_set_loo", "bmm_chain_loo_state", "bmm_chain_sweeps_loo", "bmm_chain_get_loo", "bmm_chain_loo_reset",
     "bmm_set_loo_summary",
     "bmm_chain_set_split_merge", "bmm_chain_split_merge", "bmm_chain_split_merge_step", "bmm_chain_split_merge_stats",

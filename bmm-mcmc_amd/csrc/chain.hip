@@ -822,12 +822,13 @@ int run_rows_out(const bmm_chain* c, const double* dtrace, int64_t width, double
     return S > first ? rows_out(dtrace + (size_t)first * (size_t)width, S - first, width, out, S, first) : BMM_OK;
 }
 
-// What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_partition_search, bmm_set_loo_summary,
+// What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_partition_search, bmm_set_credible_ball, bmm_set_loo_summary,
 // bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost, bmm_set_temper, bmm_set_pair_check, bmm_set_missing, bmm_set_constraints; bmm_alloc_run fills `alloc` for its own run), and what a
 // *_run_predict / *_run_relabel / *_run_probs entry point was handed.
 struct RunOptions {
     struct { bool on = false; bmm_partition_out o{}; } partition;
     struct { bool on = false, has_opts = false; bmm_partition_search_opts opts{}; bmm_partition_search_out o{}; } psearch;  // bmm_set_partition_search
+    struct { bool on = false; double level = 0.0; bmm_credible_ball_out o{}; } cball;  // bmm_set_credible_ball
     struct { bool on = false; bmm_loo_out o{}; } loo;
     struct { int moves = 0, scans = 0; } sm;
     struct { bool on = false; bmm_feature_out o{}; } fs;
@@ -6074,6 +6075,180 @@ int ps_search(hipStream_t st, PsWork& w, const uint8_t* lab, const PsOpts& o, co
     return BMM_OK;
 }
 
+// ---- credible ball and row-to-cluster similarity (include/bmm_mcmc.h "credible ball") ----
+// Which form of the k_cb_* kernels a shape runs: a pure function of (S, N, Kc, Ka, criterion, M, gathered) -- the
+// launches below and bmm_credible_ball_plan both read it from here.  The tables are the search's uint32 tables under
+// either criterion, so KaP, the threads of a row, the rows of a workgroup and D are those of its Binder form.
+struct CbPlan {
+    int el = 1, KaP = 12, nch = 1, rows = kPtThreads, D = 1, blocks = 1, bound = 0, vi = 0, gathered = 0;
+    int64_t wgs = 1, pitch = 0, span = 0;
+    size_t lds_bytes = 0, table_bytes = 0;
+};
+CbPlan cb_plan(int S, int64_t N, int Kc, int Ka, int criterion, int64_t M, bool gathered) {
+    const PsPlan q = ps_plan(S, N, Kc, Ka, BMM_PARTITION_BINDER, N);
+    CbPlan p;
+    p.el = q.el; p.KaP = q.KaP; p.nch = q.nch; p.rows = q.rows; p.D = q.D; p.blocks = q.blocks; p.bound = q.bound;
+    p.pitch = q.pitch; p.span = q.span;
+    p.vi = criterion == BMM_PARTITION_VI ? 1 : 0;
+    p.gathered = gathered ? 1 : 0;
+    p.wgs = (M + p.rows - 1) / p.rows;
+    p.lds_bytes = (size_t)p.D * Kc * p.KaP * sizeof(uint32_t);
+    p.table_bytes = (size_t)S * Kc * p.KaP * sizeof(uint32_t);
+    return p;
+}
+// refused before any device is touched
+int cb_check(int S, int64_t N, int Kc, int criterion, int Ka, double level) {
+    const int rc = pt_check_shape(S, N, Kc, criterion, 1);
+    if (rc) return rc;
+    if (Kc > BMM_PARTITION_SEARCH_MAX_K)
+        return set_err(BMM_E_ARG, "credible ball: Kc = %d is above the %d whose tables fit in LDS", Kc, BMM_PARTITION_SEARCH_MAX_K);
+    if (Ka < 1 || Ka > BMM_PARTITION_SEARCH_MAX_K)
+        return set_err(BMM_E_ARG, "credible ball: Ka must be in 1 .. %d (got %d)", BMM_PARTITION_SEARCH_MAX_K, Ka);
+    if (!(level > 0.0 && level <= 1.0)) return set_err(BMM_E_ARG, "credible ball: level must be in (0, 1] (got %g)", level);
+    return BMM_OK;
+}
+int cb_check_members(const bmm_credible_ball_out& o, int64_t N) {
+    if (!o.sim || !o.member_idx) return BMM_OK;
+    if (o.member_M < 1) return set_err(BMM_E_ARG, "credible ball: member_M must be >= 1 with member_idx (got %lld)", (long long)o.member_M);
+    for (int64_t u = 0; u < o.member_M; ++u)
+        if (o.member_idx[u] < 0 || o.member_idx[u] >= N)
+            return set_err(BMM_E_ARG, "credible ball: member_idx[%lld] = %lld is outside 0 .. %lld", (long long)u, (long long)o.member_idx[u], (long long)(N - 1));
+    return BMM_OK;
+}
+
+struct CbWork {
+    int S = 0, Kc = 0, Ka = 0;
+    int64_t N = 0, M = 0;
+    CbPlan plan;
+    DevBuf T, n, c, d2, w, k;
+    int alloc(int S_, int64_t N_, int Kc_, int Ka_, int criterion, const bmm_credible_ball_out& o) {
+        S = S_; N = N_; Kc = Kc_; Ka = Ka_;
+        M = o.sim ? (o.member_idx ? o.member_M : N) : 0;
+        plan = cb_plan(S, N, Kc, Ka, criterion, M > 0 ? M : N, o.sim && o.member_idx);
+        HIP_TRY(T.alloc(plan.table_bytes));
+        HIP_TRY(n.alloc((size_t)plan.KaP * sizeof(uint32_t)));
+        HIP_TRY(c.alloc((size_t)N * sizeof(int32_t)));
+        HIP_TRY(d2.alloc((size_t)S * sizeof(uint64_t)));
+        HIP_TRY(w.alloc((size_t)S * sizeof(double)));
+        HIP_TRY(k.alloc((size_t)S * sizeof(int32_t)));
+        return BMM_OK;
+    }
+};
+// tables, sizes, d2, w and k of the centre in w.c (0-based slots) over the label block: everything enqueued on st
+int cb_distances(hipStream_t st, CbWork& w, const uint8_t* lab) {
+    const CbPlan& p = w.plan;
+    HIP_TRY(hipMemsetAsync(w.T.p, 0, p.table_bytes, st));
+    HIP_TRY(hipMemsetAsync(w.n.p, 0, (size_t)p.KaP * sizeof(uint32_t), st));
+    const dim3 grid((unsigned)((w.N + p.span - 1) / p.span), (unsigned)w.S);
+    const size_t lds = ((size_t)w.Kc * p.KaP + p.KaP) * sizeof(uint32_t);
+    hipLaunchKernelGGL(k_ps_tables, grid, dim3(256), lds, st, lab, p.pitch, w.N, w.Kc, p.KaP, p.span, w.c.as<int32_t>(), w.T.as<uint32_t>(), w.n.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    if (p.vi) hipLaunchKernelGGL(k_ps_total<true>, dim3(w.S), dim3(256), 0, st, w.T.as<uint32_t>(), w.n.as<uint32_t>(), w.Kc, w.Ka, p.KaP, w.d2.as<uint64_t>(), w.w.as<double>());
+    else hipLaunchKernelGGL(k_ps_total<false>, dim3(w.S), dim3(256), 0, st, w.T.as<uint32_t>(), w.n.as<uint32_t>(), w.Kc, w.Ka, p.KaP, w.d2.as<uint64_t>(), w.w.as<double>());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cb_sizes, dim3(w.S), dim3(256), 0, st, w.T.as<uint32_t>(), w.Kc, w.Ka, p.KaP, w.k.as<int32_t>());
+    HIP_TRY(hipGetLastError());
+    return BMM_OK;
+}
+// sim of the chosen rows from the tables cb_distances left, out to the caller; waits for st
+int cb_member(hipStream_t st, CbWork& w, const uint8_t* lab, const bmm_credible_ball_out& o) {
+    const CbPlan& p = w.plan;
+    const int64_t M = w.M;
+    const size_t sim_bytes = (size_t)M * w.Ka * sizeof(uint64_t);
+    DevBuf didx, g, sim;
+    HIP_TRY(sim.alloc(sim_bytes));
+    const uint8_t* rows = lab;
+    int64_t pitch = p.pitch;
+    if (p.gathered) {  // the labels of the subset once, [S][M]
+        HIP_TRY(didx.alloc((size_t)M * sizeof(int64_t)));
+        HIP_TRY(g.alloc((size_t)w.S * M));
+        HIP_TRY(hipMemcpyAsync(didx.p, o.member_idx, (size_t)M * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        const dim3 gg((unsigned)((M + 255) / 256), (unsigned)w.S);
+        hipLaunchKernelGGL(k_pt_gather<uint8_t>, gg, dim3(256), 0, st, lab, p.pitch, didx.as<int64_t>(), M, g.as<uint8_t>());
+        HIP_TRY(hipGetLastError());
+        rows = g.as<uint8_t>();
+        pitch = M;
+    }
+    hipLaunchKernelGGL(k_cb_member, dim3((unsigned)p.wgs), dim3(256), p.lds_bytes, st, rows, pitch, w.S, w.Kc, w.Ka, p.KaP, p.nch, p.rows, p.D,
+                       w.T.as<uint32_t>(), M, sim.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(o.sim, sim.p, sim_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return BMM_OK;
+}
+// The ball and its three bounds from D_t and k_t as the device produced them (the header's definitions), on the host
+struct CbBound { int sweep = -1, ties = 0, k = 0; };
+struct CbBall { int m = 0, at = -1, n_in = 0; CbBound hor, up, lo; };  // at: the m-th draw in the order (D_t, t)
+template <class V>
+CbBall cb_ball(const V* D, const int32_t* k, int S, double level) {
+    CbBall r;
+    std::vector<int> order((size_t)S);
+    for (int t = 0; t < S; ++t) order[(size_t)t] = t;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return D[a] < D[b] || (D[a] == D[b] && a < b); });
+    double mm = std::ceil(level * (double)S);
+    if (mm < 1.0) mm = 1.0;
+    r.m = mm > (double)S ? S : (int)mm;
+    r.at = order[(size_t)r.m - 1];
+    const V radius = D[r.at];
+    int kmin = INT32_MAX, kmax = INT32_MIN;
+    for (int t = 0; t < S; ++t)
+        if (D[t] <= radius) { ++r.n_in; kmin = k[t] < kmin ? k[t] : kmin; kmax = k[t] > kmax ? k[t] : kmax; }
+    // the lowest draw of the ball with the largest D among those with k_t = kk (kk < 0: any k_t)
+    auto bound = [&](int kk) {
+        CbBound b;
+        for (int t = 0; t < S; ++t) {
+            if (!(D[t] <= radius) || (kk >= 0 && k[t] != kk)) continue;
+            if (b.sweep < 0 || D[t] > D[b.sweep]) { b.sweep = t; b.ties = 1; }
+            else if (D[t] == D[b.sweep]) ++b.ties;
+        }
+        b.k = k[b.sweep];
+        return b;
+    };
+    r.hor = bound(-1);
+    r.up = bound(kmin);
+    r.lo = bound(kmax);
+    return r;
+}
+// After the stream has been waited for: d2, w, k and the sizes read back, the ball chosen, the outputs filled.
+// row(t, dst) copies draw t, 1-based, into dst; `first` is added to every reported draw (the rows a run left out).
+template <class RowFn>
+int cb_finish(CbWork& w, double level, const bmm_credible_ball_out& o, int first, RowFn row) {
+    const int S = w.S;
+    std::vector<uint64_t> d2((size_t)S);
+    std::vector<double> wv((size_t)S);
+    std::vector<int32_t> k((size_t)S);
+    std::vector<uint32_t> n((size_t)w.plan.KaP);
+    HIP_TRY(hipMemcpy(d2.data(), w.d2.p, (size_t)S * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(wv.data(), w.w.p, (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(k.data(), w.k.p, (size_t)S * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n.data(), w.n.p, n.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const bool vi = w.plan.vi != 0;
+    auto dist_of = [&](int t) { return vi ? wv[(size_t)t] / (double)w.N : (double)d2[(size_t)t] / 2.0; };
+    const CbBall b = vi ? cb_ball(wv.data(), k.data(), S, level) : cb_ball(d2.data(), k.data(), S, level);
+    for (int t = 0; t < S; ++t) {
+        if (o.d2) o.d2[t] = d2[(size_t)t];
+        if (o.dist) o.dist[t] = dist_of(t);
+        if (o.n_clusters) o.n_clusters[t] = k[(size_t)t];
+    }
+    if (o.radius) *o.radius = dist_of(b.at);
+    if (o.radius2) *o.radius2 = d2[(size_t)b.at];
+    if (o.n_in) *o.n_in = b.n_in;
+    if (o.sizes) for (int a = 0; a < w.Ka; ++a) o.sizes[a] = (int64_t)n[(size_t)a];
+    const bmm_credible_bound* const dst[3] = {&o.horizontal, &o.upper, &o.lower};
+    const CbBound* const src[3] = {&b.hor, &b.up, &b.lo};
+    for (int q = 0; q < 3; ++q) {
+        const bmm_credible_bound& h = *dst[q];
+        const CbBound& s = *src[q];
+        if (h.sweep) *h.sweep = first + s.sweep;
+        if (h.ties) *h.ties = s.ties;
+        if (h.n_clusters) *h.n_clusters = s.k;
+        if (h.dist) *h.dist = dist_of(s.sweep);
+        if (h.d2) *h.d2 = d2[(size_t)s.sweep];
+        if (h.z) { const int rc = row(s.sweep, h.z); if (rc) return rc; }
+    }
+    return BMM_OK;
+}
+
 // The summary of a run (bmm_set_partition_summary): what the run checks of it before any device is touched
 int pt_run_check(const RunOptions& opts, int S, int64_t N, int K) {
     if (opts.psearch.on) {
@@ -6081,6 +6256,13 @@ int pt_run_check(const RunOptions& opts, int S, int64_t N, int K) {
         PsOpts r;
         int rc = ps_check(S, N, K, opts.partition.o.criterion, opts.psearch.has_opts ? &opts.psearch.opts : nullptr, true, r);
         if (rc == BMM_OK) rc = ps_check_out(&opts.psearch.o);
+        if (rc) return rc;
+    }
+    if (opts.cball.on) {
+        if (!opts.partition.on) return set_err(BMM_E_ARG, "credible ball: needs an armed partition summary (bmm_set_partition_summary)");
+        const int Ka = opts.psearch.on && opts.psearch.has_opts ? opts.psearch.opts.max_clusters : K;
+        int rc = cb_check(S, N, K, opts.partition.o.criterion, Ka, opts.cball.level);
+        if (rc == BMM_OK) rc = cb_check_members(opts.cball.o, N);
         if (rc) return rc;
     }
     if (!opts.partition.on) return BMM_OK;
@@ -6116,15 +6298,34 @@ int pt_run_summary(bmm_chain* c, const bmm_partition_out& o, const RunOptions& o
         for (int64_t i = 0; i < N; ++i) o.z_best[i] += 1;
     }
     if (o.psm_M > 0) rc = pt_psm(c->stream, w, o.psm_idx, o.psm_M, o.psm_cnt);
+    PsWork sw;
+    int Ka = c->p.K;
     if (rc == BMM_OK && opts.psearch.on) {  // the greedy search from the chosen row, over the rows the summary used
         PsOpts r;
         rc = ps_check(Su, N, c->p.K, o.criterion, opts.psearch.has_opts ? &opts.psearch.opts : nullptr, true, r);
         if (rc) return rc;
-        PsWork sw;
         rc = sw.alloc(Su, N, c->p.K, r.Ka, o.criterion, r.batch);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(sw.c.p, c->dTrace + (size_t)(first + best) * N, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
         rc = ps_search(c->stream, sw, w.lab.as<uint8_t>(), r, opts.psearch.o);
+        Ka = r.Ka;
+    }
+    if (rc == BMM_OK && opts.cball.on) {  // the credible ball around the searched partition, else around the chosen row
+        const bmm_credible_ball_out& bo = opts.cball.o;
+        CbWork bw;
+        rc = bw.alloc(Su, N, c->p.K, Ka, o.criterion, bo);
+        if (rc) return rc;
+        const int32_t* const centre = opts.psearch.on ? sw.best.as<int32_t>() : c->dTrace + (size_t)(first + best) * N;
+        HIP_TRY(hipMemcpyAsync(bw.c.p, centre, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+        rc = cb_distances(c->stream, bw, w.lab.as<uint8_t>());
+        if (rc == BMM_OK && bw.M > 0) rc = cb_member(c->stream, bw, w.lab.as<uint8_t>(), bo);
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        rc = cb_finish(bw, opts.cball.level, bo, first, [&](int t, int32_t* dst) -> int {
+            HIP_TRY(hipMemcpy(dst, c->dTrace + (size_t)(first + t) * N, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < N; ++i) dst[i] += 1;
+            return BMM_OK;
+        });
     }
     return rc;
 }
@@ -7382,6 +7583,63 @@ int bmm_set_partition_search(const bmm_partition_search_opts* opts, const bmm_pa
     g_armed.psearch.has_opts = out != nullptr && opts != nullptr;
     if (out) g_armed.psearch.o = *out;
     if (out && opts) g_armed.psearch.opts = *opts;
+    return BMM_OK;
+}
+
+int bmm_set_credible_ball(double level, const bmm_credible_ball_out* out) {
+    g_armed.cball.on = out != nullptr;
+    g_armed.cball.level = level;
+    if (out) g_armed.cball.o = *out;
+    return BMM_OK;
+}
+
+int bmm_device_credible_ball(int device, const int32_t* z, int S, int64_t N, int Kc, int criterion,
+                             const int32_t* centre, int Ka, double level, const bmm_credible_ball_out* out) {
+    return guarded([&]() -> int {
+        if (!z || !centre || !out) return set_err(BMM_E_ARG, "credible ball: null argument");
+        int rc = cb_check(S, N, Kc, criterion, Ka, level);
+        if (rc == BMM_OK) rc = cb_check_members(*out, N);
+        if (rc == BMM_OK) rc = pt_check_labels(z, S, N, 1, Kc, nullptr, "credible ball");
+        if (rc) return rc;
+        std::vector<int32_t> c0((size_t)N);
+        for (int64_t i = 0; i < N; ++i) {
+            if (centre[i] < 1 || centre[i] > Ka)
+                return set_err(BMM_E_ARG, "credible ball: centre label %d at observation %lld (0-based) is outside 1 .. %d", centre[i], (long long)i, Ka);
+            c0[(size_t)i] = centre[i] - 1;
+        }
+        HIP_TRY(hipSetDevice(device));
+        PtWork w;
+        w.shape(S, N, Kc, criterion, 1);
+        rc = w.alloc_labels();
+        if (rc == BMM_OK) rc = pt_upload(w, z);
+        if (rc) return rc;
+        int flag = 0;
+        HIP_TRY(hipMemcpy(&flag, w.flag.p, sizeof flag, hipMemcpyDeviceToHost));
+        if (flag) return set_err(BMM_E_STATE, "credible ball: a label outside 0 .. %d reached the device", Kc - 1);
+        CbWork bw;
+        rc = bw.alloc(S, N, Kc, Ka, criterion, *out);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(bw.c.p, c0.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
+        rc = cb_distances(nullptr, bw, w.lab.as<uint8_t>());
+        if (rc == BMM_OK && bw.M > 0) rc = cb_member(nullptr, bw, w.lab.as<uint8_t>(), *out);
+        if (rc) { (void)hipDeviceSynchronize(); return rc; }
+        HIP_TRY(hipDeviceSynchronize());
+        return cb_finish(bw, level, *out, 0, [&](int t, int32_t* dst) -> int {
+            for (int64_t i = 0; i < N; ++i) dst[i] = z[(size_t)t + (size_t)i * S];
+            return BMM_OK;
+        });
+    });
+}
+
+// Which form of every k_cb_* kernel a shape runs, from the function the launches call (no device is touched)
+int bmm_credible_ball_plan(int S, int64_t N, int Kc, int Ka, int criterion, int64_t M, int64_t out[12]) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    const int rc = cb_check(S, N, Kc, criterion, Ka, 1.0);
+    if (rc) return rc;
+    if (M < 1) return set_err(BMM_E_ARG, "credible ball: M must be >= 1 (got %lld)", (long long)M);
+    const CbPlan p = cb_plan(S, N, Kc, Ka, criterion, M, M != N);
+    out[0] = p.el; out[1] = p.KaP; out[2] = p.nch; out[3] = p.rows; out[4] = p.D; out[5] = p.blocks; out[6] = p.bound;
+    out[7] = (int64_t)p.lds_bytes; out[8] = p.wgs; out[9] = p.gathered; out[10] = p.vi; out[11] = (int64_t)p.table_bytes;
     return BMM_OK;
 }
 

@@ -4097,6 +4097,82 @@ __global__ __launch_bounds__(256) void k_ps_reduce(const uint64_t* __restrict__ 
     }
 }
 
+// ---- credible ball and row-to-cluster similarity (include/bmm_mcmc.h "credible ball") -----
+// Around one centre c: the tables T_t of k_ps_tables and d2[t], w[t] of k_ps_total as the search has them, unchanged.
+// k_t, the non-empty labels of draw t, from the row sums of T_t (n_t,b = sum_a T_t[b][a]): one workgroup per draw.
+__global__ __launch_bounds__(256) void k_cb_sizes(const uint32_t* __restrict__ T, int Kc, int Ka, int KaP,
+                                                  int32_t* __restrict__ k) {
+    __shared__ uint32_t su[kPtThreads];
+    const int tid = threadIdx.x, t = blockIdx.x;
+    const uint32_t* __restrict__ Tt = T + (size_t)t * Kc * KaP;
+    uint32_t used = 0;
+    for (int b = tid; b < Kc; b += kPtThreads) {
+        uint32_t v = 0;
+        for (int a = 0; a < Ka; ++a) v += Tt[b * KaP + a];
+        used += v ? 1u : 0u;
+    }
+    used = pt_block_sum(used, su);
+    if (tid == 0) k[t] = (int32_t)used;
+}
+
+// The hot path: sim[u][a] = sum_t T_t[a][z_t,u] for the M chosen rows.  `lab` is the label block itself (all rows:
+// pitch as k_pt_narrow left it, row u is observation u) or the [S][M] block k_pt_gather made of a subset (pitch M).
+// Thread (r, ch) of a workgroup holds row blockIdx.x * rows + r and the slots [8 ch, 8 ch + 8); the nch threads of a
+// row are neighbours.  The draws come through LDS in blocks of D tables, one flat copy each (the layout is that of
+// global memory); per draw a thread reads its row's label b and the run of 8 cells at [b][8 ch ..], 16-byte aligned,
+// lanes with the same label reading the same address.  The kernel waits on its label loads more than on the LDS
+// (section 29), so a thread issues the loads of kCbAhead draws together.  uint32 sums within a block (D * N < 2^32, the plan's promise),
+// uint64 across blocks; the cells past Ka of a run are zero and are not stored.  Integers only, no atomics, nothing
+// decided here.  Dynamic LDS: D tables.
+constexpr int kCbAhead = 8;  // label loads of a row issued together
+__global__ __launch_bounds__(256) void k_cb_member(const uint8_t* __restrict__ lab, int64_t pitch, int S, int Kc, int Ka,
+                                                   int KaP, int nch, int rows, int D, const uint32_t* __restrict__ T,
+                                                   int64_t M, uint64_t* __restrict__ sim) {
+    extern __shared__ uint4 cb_lds4[];
+    const int tid = threadIdx.x, r = tid / nch, ch = tid - r * nch;
+    const int64_t u = (int64_t)blockIdx.x * rows + r;
+    const bool live = r < rows && u < M;
+    const int cells = Kc * KaP;
+    uint64_t acc[kPsChunk];
+#pragma unroll
+    for (int j = 0; j < kPsChunk; ++j) acc[j] = 0;
+    for (int t0 = 0; t0 < S; t0 += D) {
+        const int nD = S - t0 < D ? S - t0 : D;
+        __syncthreads();  // the block before has been read
+        const uint4* __restrict__ src = reinterpret_cast<const uint4*>(T + (size_t)t0 * cells);
+        for (int k = tid; k < nD * cells / 4; k += kPtThreads) cb_lds4[k] = src[k];
+        __syncthreads();
+        if (!live) continue;
+        const uint32_t* const tab = reinterpret_cast<const uint32_t*>(cb_lds4);
+        uint32_t a32[kPsChunk];
+#pragma unroll
+        for (int j = 0; j < kPsChunk; ++j) a32[j] = 0;
+        const uint8_t* __restrict__ col = lab + (size_t)t0 * pitch + u;
+        auto add = [&](int tt, uint32_t b) {
+            const uint4* const p = reinterpret_cast<const uint4*>(tab + (tt * Kc + (int)b) * KaP + ch * kPsChunk);
+            const uint4 x = p[0], y = p[1];
+            a32[0] += x.x; a32[1] += x.y; a32[2] += x.z; a32[3] += x.w;
+            a32[4] += y.x; a32[5] += y.y; a32[6] += y.z; a32[7] += y.w;
+        };
+        int tt = 0;
+        for (; tt + kCbAhead <= nD; tt += kCbAhead) {  // the labels of kCbAhead draws in flight before the first is used
+            uint32_t b[kCbAhead];
+#pragma unroll
+            for (int q = 0; q < kCbAhead; ++q) b[q] = col[(size_t)(tt + q) * pitch];
+#pragma unroll
+            for (int q = 0; q < kCbAhead; ++q) add(tt + q, b[q]);
+        }
+        for (; tt < nD; ++tt) add(tt, col[(size_t)tt * pitch]);
+#pragma unroll
+        for (int j = 0; j < kPsChunk; ++j) acc[j] += a32[j];
+    }
+    if (!live) return;
+    uint64_t* const out = sim + (size_t)u * Ka + ch * kPsChunk;
+#pragma unroll
+    for (int j = 0; j < kPsChunk; ++j)
+        if (ch * kPsChunk + j < Ka) out[j] = acc[j];
+}
+
 // ---- split-merge moves (include/bmm_mcmc.h "split-merge moves", "split-merge moves of the allocation sampler";
 // DESIGN.md sections 15 and 24) ----------------------------------------------------------------------------------------
 // One move = k_sm_launch, `scans` + 1 launches of k_sm_scan, k_sm_decide, k_sm_commit, stream-ordered; the host

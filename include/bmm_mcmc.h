@@ -663,6 +663,83 @@ int bmm_partition_search_plan(int S, int64_t N, int Kc, int Ka, int criterion, i
  * launch.  The structs are copied; the buffers must stay valid through the call.  bmm_partition_out is not touched. */
 int bmm_set_partition_search(const bmm_partition_search_opts* opts, const bmm_partition_search_out* out);
 
+/* ---- credible ball and row-to-cluster similarity of the point estimate -----------------
+ * How sure the estimate is: the credible ball of Wade & Ghahramani (2018) around one centre partition c under the
+ * criterion, and how often every row sat with the members of every cluster of c.  In the notation of the block above:
+ *   z_t (t < S)    the draws, labels in 0 .. Kc-1;
+ *   c              the centre, labels in 0 .. Ka-1: Ka slots, of which any may be empty;
+ *   n_a            the size of slot a;  T_t[a][b] = #{i : c_i = a, z_t,i = b};  n_t,b the size of label b of draw t;
+ *   d2_t           = 2 B(c, z_t), uint64, exact;
+ *   w_t            = N VI(c, z_t), binary64, F_c + F_t - 2 G_t in the order the search's totals fix, and exactly 0
+ *                  where d2_t = 0;
+ *   D_t            d2_t under Binder, w_t under VI.  Every comparison below is made on these values as the device
+ *                  produced them: integer compares under Binder, binary64 compares under VI;
+ *   k_t            the non-empty labels of draw t, #{b : n_t,b > 0};
+ *   ball           the draws ordered by (D_t, t), m = min(S, max(1, ceil(level S))): the radius is the D of the m-th
+ *                  draw in that order, the ball is {t : D_t <= radius}.  Ties at the radius are all inside: n_in >= m;
+ *   horizontal     bound: the draws of the ball with the largest D_t (the radius, by construction): the lowest such t
+ *                  and how many there are;
+ *   upper          vertical upper bound: among the ball's draws with the smallest k_t those with the largest D_t: the
+ *                  lowest such t, how many, k_t and D_t;
+ *   lower          vertical lower bound: the same with the largest k_t;
+ *   similarity     of a chosen row i to slot a: sim[i][a] = sum_t T_t[a][z_t,i], uint64, exact, a < Ka.  It equals
+ *                  sum_{j : c_j = a} cnt[i, j] with cnt the similarity counts of bmm_device_psm; for a = c_i it
+ *                  includes the row itself S times.
+ * Derived by the caller: with own = [a = c_i], membership[i][a] = (sim[i][a] - S own) / (S (n_a - own)), the posterior
+ * mean similarity of the row to the other members of the slot -- a soft membership that does not depend on how the
+ * draws number their clusters (undefined for an empty slot and for a row alone in its cluster).
+ * The radius and the three bounds are chosen on the host from the 24 S bytes of d2, w and k read back, O(S log S); the
+ * three bounding rows leave the device as three rows.  The similarity is the device's one large pass, N Ka S table
+ * reads for all rows.  Limits as the search: 1 <= Kc, Ka <= BMM_PARTITION_SEARCH_MAX_K, S N^2 < 2^63. */
+typedef struct bmm_credible_bound {
+    int* sweep;           /* the lowest draw (row of z, 0-based) attaining the bound */
+    int* ties;            /* the draws attaining it */
+    int* n_clusters;      /* k_t of those draws */
+    double* dist;         /* their distance in the criterion's natural unit: B = d2 / 2, or VI = w / N */
+    uint64_t* d2;         /* d2 of draw `sweep` */
+    int32_t* z;           /* N int32, 1-based: draw `sweep` */
+} bmm_credible_bound;     /* any pointer may be NULL */
+typedef struct bmm_credible_ball_out {
+    uint64_t* d2;              /* S: d2_t, under either criterion */
+    double* dist;              /* S: d2_t / 2 under Binder, w_t / N under VI */
+    int32_t* n_clusters;       /* S: k_t */
+    double* radius;            /* the radius in the unit of dist */
+    uint64_t* radius2;         /* d2 of the m-th draw in the order (D_t, t) */
+    int* n_in;                 /* draws in the ball */
+    bmm_credible_bound horizontal, upper, lower;
+    uint64_t* sim;             /* member_M x Ka uint64, row-major ([u][a]); NULL: the similarity pass is not launched */
+    const int64_t* member_idx; /* member_M observations, 0-based, any order, repeats allowed; NULL: all N rows in order
+                                  (member_M is then taken as N) */
+    int64_t member_M;
+    int64_t* sizes;            /* Ka: n_a */
+} bmm_credible_ball_out;       /* any output pointer may be NULL */
+/* z as bmm_device_partition_distances takes it; centre: N int32 in 1 .. Ka.  BMM_E_ARG before a device is touched: Kc
+ * or Ka outside 1 .. BMM_PARTITION_SEARCH_MAX_K, a centre label outside 1 .. Ka (the observation is named), level
+ * outside (0, 1] or NaN, a member index outside 0 .. N-1, S N^2 >= 2^63, a null z, centre or out. */
+int bmm_device_credible_ball(int device, const int32_t* z, int S, int64_t N, int Kc, int criterion,
+                             const int32_t* centre, int Ka, double level, const bmm_credible_ball_out* out);
+/* Which form of the k_cb_* kernels a shape runs, as pure bookkeeping -- no device is touched, and the values come from
+ * the function the launches themselves call.  M: the chosen rows (N: all rows, read from the label block; fewer: a
+ * gathered subset).  out:
+ *   [0] bytes per label of the draws (1)          [1] cells from one label's run of slots to the next, KaP
+ *   [2] threads per row, ceil(Ka / 8)             [3] rows per workgroup of k_cb_member
+ *   [4] draws per LDS block, D                    [5] blocks of draws, ceil(S / D)
+ *   [6] what bounds D: 0 S, 1 the LDS budget, 2 the 32-bit sums of a block (D N < 2^32)
+ *   [7] bytes of dynamic LDS of k_cb_member       [8] workgroups of k_cb_member, ceil(M / [3])
+ *   [9] 1: the labels of a subset are gathered first, 0: all rows, the label block is read directly
+ *   [10] 1: VI (w_t computed), 0: Binder          [11] bytes of tables in global memory.
+ * BMM_E_ARG as bmm_device_credible_ball, and unless 1 <= M. */
+int bmm_credible_ball_plan(int S, int64_t N, int Kc, int Ka, int criterion, int64_t M, int64_t out[12]);
+/* For a run: armed per calling thread for the NEXT single-chain *_run* call, as bmm_set_partition_search, and disarmed
+ * when that call returns; out = NULL disarms.  Needs the partition summary armed: the ball takes the summary's
+ * criterion, and its centre is the searched partition when a search is armed too, else the row the summary chose,
+ * device to device; it runs over the rows the summary used (n_used; with none usable out is left as it was), after the
+ * search and before the trace leaves.  The bounds' `sweep` are rows of the run's trace.  BMM_E_ARG, before a device is
+ * touched, when no partition summary is armed, the run's K is above BMM_PARTITION_SEARCH_MAX_K, level is outside
+ * (0, 1] or a member index is outside 0 .. N-1.  Not armed: no allocation, no launch.  The struct is copied; its
+ * buffers must stay valid through the call (sizes and a row of sim hold Ka = the search's max_clusters, or K). */
+int bmm_set_credible_ball(double level, const bmm_credible_ball_out* out);
+
 /* ---- leave-one-out predictive of the fitted rows: LPML, WAIC ---------------------------
  * For the state s after a kept sweep and a fitted row i with label z_i, ell[s, i] is the log density of x_i given
  * everything else in the state:
