@@ -24,7 +24,8 @@ __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "
            "default_batch", "sweep_chains", "broadcast_planes", "read_rdata_matrix", "chain_summary", "TOL_PROPORTIONS", "TOL_THETA",
            "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
            "partition_distances", "posterior_similarity", "partition_plan", "partition_search", "partition_search_plan", "credible_ball", "credible_ball_plan", "run_options", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
-           "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat", "pair_check", "pair_check_plan", "pair_check_pairs", "PAIR_CHECK_MAX_M", "run_bytes", "summary_plan", "Ladder", "temper_ladder", "TEMPER_MAX_RUNGS"]
+           "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat", "pair_check", "pair_check_plan", "pair_check_pairs", "PAIR_CHECK_MAX_M", "run_bytes", "summary_plan", "Ladder", "temper_ladder", "TEMPER_MAX_RUNGS",
+           "categorical", "Categorical", "categorical_plan"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -1191,6 +1192,7 @@ def log_joint(X, z, sampler, K, alpha=1.0, beta=0.5, gamma=0.5, a=1, b=1, sample
     trace and prior; mask: (P,) or (S, P) indicators in {0, 1} with rho (one mask per call: an (S, P) trace is scored
     row by row).  Returns {"log_lik", "log_prior", "log_hyper", "log_joint"}, each (S,).  A run's own z and alpha give
     the run's rows bit for bit."""
+    _refuse_categorical(X, "log_joint")
     X = _capi.as_x(X)
     N, P = X.shape
     z = _np.asarray(z)
@@ -1364,6 +1366,7 @@ def pair_check(X, z, Kc, features=None, counts=False, device=0):
     needs P <= 128).  Returns the summary of a run's out["pair_check"] folded over the S rows, with "z" and "x2" (S,
     npairs), and with counts=True "counts" (S, Kc, npairs) uint32, the co-occurrence counts per label.  A run's own z
     gives the run's rows bit for bit."""
+    _refuse_categorical(X, "pair_check")
     X = _capi.as_x(X)
     N, P = X.shape
     z = _np.asarray(z)
@@ -1634,6 +1637,7 @@ def gibbs_allocation(data, nsamples, maxK, a=1.0, prior_k="poisson", K0=None, mo
     of every sweep from the second, each with `split_merge_scans` intermediate restricted scans: a split opens component
     K + 1 along the data, a merge closes one.  The result gains `split_merge = {"proposed_splits", "accepted_splits",
     "proposed_merges", "accepted_merges", "skipped"}`."""
+    _refuse_categorical(data, "gibbs_allocation")
     sm = _make_split_merge(split_merge, split_merge_scans, 1, alloc=True)
     X = _capi.as_x(data)
     N, P = X.shape
@@ -1833,6 +1837,130 @@ class _Init(_Option):
         info = _InitInfo()
         _capi.check(_capi.lib().bmm_last_init_info(_C.byref(info)))
         return info.as_dict()
+
+
+# ---------------------------------------------------------------- categorical features: the data says what it is
+class Categorical(_np.ndarray):
+    """What categorical() returns: the expanded N x P 0/1 matrix (int32, column-major), carrying `levels` (F,: the levels
+    of every feature), `chain_levels` (F,: what the library is told -- 1 for a two-level feature, which is one Bernoulli
+    column, else L), `columns` (feature -> slice of its columns) and decode().  Only the object itself carries them: a
+    slice, a copy or numpy.asarray of it is a plain 0/1 matrix, and is modelled as one."""
+
+    def __array_finalize__(self, obj):
+        self.levels = self.chain_levels = self.columns = None
+
+    def decode(self, theta):
+        """theta (K, P), or (K, P, S), as the chain reports it (S / Nk per column) -> a list of F arrays (K, L_j[, S]): the
+        level proportions of every feature; a two-level feature's are (1 - theta, theta)."""
+        theta = _np.asarray(theta)
+        if self.columns is None or theta.ndim < 2 or theta.shape[1] != self.shape[1]:
+            raise ValueError("decode takes the K x P theta of a chain over these columns")
+        out = []
+        for L, sl in zip(self.levels, self.columns):
+            t = theta[:, sl]
+            out.append(_np.concatenate((1.0 - t, t), axis=1) if L == 2 else t)
+        return out
+
+
+def categorical(X, levels=None):
+    """An N x F integer matrix of categorical features -- feature j takes the values 0 .. L_j - 1 -- as data for
+    gibbs_collapsed and gibbs_dp (include/bmm_mcmc.h "categorical features").  `levels`: L_j per
+    feature, each >= 2; None: the column's maximum + 1 (at least 2).  Returns the expanded 0/1 matrix (Categorical): a
+    feature of L >= 3 levels is a block of L neighbouring one-hot columns, modelled with a symmetric Dirichlet(beta, ...,
+    beta) prior on its level probabilities (beta: the run's); a feature of 2 levels is ONE Bernoulli column (its value)
+    under the run's Beta(beta, gamma) -- with gamma != beta its two levels are not exchangeable, as in the Bernoulli
+    model.  Handing the object to gibbs_collapsed or gibbs_dp arms the levels: the result gains `categorical = {"levels",
+    "columns"}`, `theta` holds the level proportions column by column (decode() splits it per feature), and a partition
+    is scored under the categorical likelihood, not under L independent Bernoulli columns.  Not offered (ValueError,
+    before the library is asked): the other samplers, chains > 1, temper=, select_features=, split_merge=, missing=,
+    newdata=, loo=, logpost= (and ecr_pivot="map"), pair_check=, init="kmodes", relabel=True.  partition= with its search
+    and credible ball, relabel="ecr", known= / allowed=, summary= and keep_trace= work as ever.  A resident chain takes
+    the raw vector instead: Chain.set_categorical."""
+    X = _np.asarray(X)
+    if X.ndim != 2 or X.dtype.kind not in "iub" or X.shape[1] < 1:
+        raise ValueError("categorical takes an N x F integer matrix")
+    N, F = X.shape
+    X = X.astype(_np.int64)
+    if levels is None:
+        lv = _np.maximum(X.max(axis=0) + 1, 2) if N else _np.full(F, 2, dtype=_np.int64)
+    else:
+        lv = _np.asarray(levels)
+        if lv.shape != (F,) or lv.dtype.kind not in "iu":
+            raise ValueError("levels must hold one integer per feature")
+        lv = lv.astype(_np.int64)
+    if (lv < 2).any():
+        raise ValueError("feature %d has %d levels: a feature has at least 2" % (int(_np.flatnonzero(lv < 2)[0]), int(lv[lv < 2][0])))
+    if (lv > 255).any():
+        raise ValueError("feature %d has %d levels: at most 255 are offered" % (int(_np.flatnonzero(lv > 255)[0]), int(lv[lv > 255][0])))
+    bad = (X < 0) | (X >= lv[None, :])
+    if bad.any():
+        i, j = (int(v[0]) for v in _np.nonzero(bad))
+        raise ValueError("row %d, feature %d: the value %d lies outside 0 .. %d" % (i, j, int(X[i, j]), int(lv[j]) - 1))
+    width = _np.where(lv == 2, 1, lv)
+    first = _np.concatenate(([0], _np.cumsum(width)))
+    out = _np.zeros((N, int(first[-1])), dtype=_np.int32, order="F").view(Categorical)
+    rows = _np.arange(N)
+    for j in range(F):
+        if lv[j] == 2:
+            out[:, first[j]] = X[:, j]
+        else:
+            _np.asarray(out)[rows, first[j] + X[:, j]] = 1
+    out.levels = lv.astype(_np.int32)
+    out.chain_levels = _np.ascontiguousarray(width, dtype=_np.int32)
+    out.columns = [slice(int(first[j]), int(first[j + 1])) for j in range(F)]
+    return out
+
+
+def _categorical_of(data):
+    return data if isinstance(data, Categorical) and data.levels is not None else None
+
+
+def _refuse_categorical(data, who, **options):
+    """categorical data handed to something that models a Bernoulli cell per column: refused before the library is asked"""
+    if _categorical_of(data) is None:
+        return
+    if who is not None:
+        raise ValueError("%s models every column as a Bernoulli cell: categorical data go to gibbs_collapsed and gibbs_dp" % who)
+    armed = [k for k, v in options.items() if v]
+    if armed:
+        raise ValueError("%s= is not offered with categorical data: it knows the Bernoulli cell only" % armed[0])
+
+
+class _Categorical(_Option):
+    """the levels of categorical data, armed for exactly one run"""
+    key = "categorical"
+
+    def __init__(self, data):
+        self.levels, self.columns, self.raw = data.levels.copy(), list(data.columns), data.chain_levels
+
+    def arm(self):
+        _capi.check(_capi.lib().bmm_set_categorical(_capi.vp(self.raw), _C.c_int(self.raw.size)))
+
+    def result(self):
+        return {"levels": self.levels, "columns": self.columns}
+
+
+class _CategoricalPlanOut(_C.Structure):  # bmm_categorical_plan_out
+    _fields_ = [("n_columns", _C.c_int32), ("n_blocks", _C.c_int32), ("generic", _C.c_int32), ("threads", _C.c_int32),
+                ("lanes", _C.c_int32), ("packed", _C.c_int32), ("builds_own_tables", _C.c_int32), ("batch", _C.c_int64)]
+
+
+def categorical_plan(sampler, N, K, levels, batch=None, num_cus=256):
+    """What bmm_categorical_plan reports of a raw levels vector (1: a Bernoulli column, L >= 2: a block of L one-hot
+    columns) without touching a device: {"P", "n_blocks", "first_column" (F,), "lev" (P,) uint8: 0 or the L of the column's
+    block, "generic", "threads", "lanes_per_observation", "packed", "builds_own_tables", "batch"}."""
+    lv = _np.ascontiguousarray(levels, dtype=_np.int32)
+    if lv.ndim != 1:
+        raise ValueError("levels is a vector")
+    first = _np.zeros(max(lv.size, 1), dtype=_np.int32)
+    lev = _np.zeros(max(int(_np.maximum(lv, 1).sum()), 1), dtype=_np.uint8)
+    o = _CategoricalPlanOut()
+    _capi.check(_capi.lib().bmm_categorical_plan(_C.c_int(_capi.SAMPLER_CODE[sampler]), _C.c_int64(N), _C.c_int(K),
+                                                 _C.c_int64(0 if batch is None else batch), _C.c_int(num_cus), _capi.vp(lv),
+                                                 _C.c_int(lv.size), _capi.vp(first), _capi.vp(lev), _C.byref(o)))
+    return {"P": int(o.n_columns), "n_blocks": int(o.n_blocks), "first_column": first[:lv.size], "lev": lev[:o.n_columns],
+            "generic": bool(o.generic), "threads": int(o.threads), "lanes_per_observation": int(o.lanes),
+            "packed": bool(o.packed), "builds_own_tables": bool(o.builds_own_tables), "batch": int(o.batch)}
 
 
 def _run(base, args, options, pr=None, hooks=None, rel=None):
@@ -2045,6 +2173,15 @@ def _gibbs(spec, data, nsamples, K, *, alpha, beta, gamma, a, b, burnin, relabel
     into the run's options and refused where they do not go together, several chains handed to the multi-chain call and
     pooled, or one run with its options armed (_run) and what they hold collected into the result.  An option a sampler
     does not offer is one its wrapper does not pass: the defaults here mean off."""
+    ct = None
+    if _categorical_of(data) is not None:  # (plain data: nothing new is looked at, nothing new is called)
+        _refuse_categorical(data, None if spec in (_COLLAPSED, _DP) else "gibbs_" + spec.name)
+        _refuse_categorical(data, None, chains=int(chains) > 1, temper=temper is not None, select_features=select_features,
+                            split_merge=int(split_merge or 0) > 0, missing=missing is not None, newdata=newdata is not None,
+                            loo=loo is not None and loo is not False, logpost=bool(logpost) or ecr_pivot == "map",
+                            pair_check=pair_check is not None and pair_check is not False,
+                            init=init is not None and init != "random", relabel=bool(relabel) and relabel != "ecr")
+        ct = _Categorical(data)
     data, cells = _take_missing(data, missing)
     X = _capi.as_x(data)
     N, P = X.shape
@@ -2132,7 +2269,7 @@ def _gibbs(spec, data, nsamples, K, *, alpha, beta, gamma, a, b, burnin, relabel
     pi = _np.zeros((S, K), order="F") if with_pi else None
     args = _run_args(spec, X, start, nsamples, K, alpha, beta, gamma, a, b, burnin, batch, seed, device, pi, z, theta, al)
     with _progress(debug):
-        rc = _run(spec.base, args, (sm, fs, pt, ps, cb, lo, ec, lp, tp, pc, mi, cs, su, ini), pr,
+        rc = _run(spec.base, args, (sm, fs, pt, ps, cb, lo, ec, lp, tp, pc, mi, cs, su, ct, ini), pr,
                   hooks=None if on_device else rel, rel=rel if on_device else None)
     out = {"alpha": al, "permutations": None if on_device else _na_perm(S, K), "z": z, "theta": theta}
     if with_pi:
@@ -2141,7 +2278,7 @@ def _gibbs(spec, data, nsamples, K, *, alpha, beta, gamma, a, b, burnin, relabel
         out = rel.finish(rc, out)
     else:
         _capi.check(rc)
-    return _collect(out, (ec, pr, pt, lo, su, ps, cb, tp, sm, fs, ini, lp, pc, mi, cs))
+    return _collect(out, (ec, pr, pt, lo, su, ps, cb, tp, sm, fs, ini, lp, pc, mi, cs, ct))
 
 
 def gibbs_collapsed(data, nsamples, K, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
@@ -2944,6 +3081,28 @@ class Chain:
     def set_feature_select(self, on=True, rho=0.5):
         """a gamma-step behind every sweep from now on (on=False: no more steps, the mask stays)"""
         _capi.check(_capi.lib().bmm_chain_set_feature_select(self._h, _C.c_int(1 if on else 0), _C.c_double(float(rho))))
+
+    def set_categorical(self, levels=None):
+        """the levels of the chain's features (bmm_chain_set_categorical): the raw vector, one entry per feature -- 1: a
+        binary feature in one column under Beta(beta, gamma); L >= 2: a block of L neighbouring one-hot columns under a
+        symmetric Dirichlet(beta, ..., beta), blocks of 2 included -- whose columns add up to P.  Before or after the
+        data, before the first sweep or between sweeps; when levels and data meet the device checks that every row has
+        exactly one 1 in every block (BmmError names the first bad row and its feature).  None or an empty vector
+        withdraws the levels.  Returns the number of features."""
+        lv = _np.ascontiguousarray(() if levels is None else levels, dtype=_np.int32)
+        if lv.ndim != 1:
+            raise ValueError("levels is a vector with one entry per feature")
+        _capi.check(_capi.lib().bmm_chain_set_categorical(self._h, _capi.vp(lv), _C.c_int(lv.size)))
+        return int(lv.size)
+
+    def categorical(self):
+        """the levels the chain carries (an empty vector: none)"""
+        F = _C.c_int(0)
+        _capi.check(_capi.lib().bmm_chain_get_categorical(self._h, None, _C.byref(F)))
+        lv = _np.zeros(F.value, dtype=_np.int32)
+        if F.value:
+            _capi.check(_capi.lib().bmm_chain_get_categorical(self._h, _capi.vp(lv), _C.byref(F)))
+        return lv
 
     def set_features(self, gamma):
         """the inclusion mask, between sweeps: P values in {0, 1}"""

@@ -59,6 +59,7 @@ SYMBOLS = [
     "bmm_chain_set_constraints", "bmm_chain_constraint_stats", "bmm_set_constraints", "bmm_last_constraint_stats",
     "bmm_set_summary", "bmm_run_bytes", "bmm_summary_plan", "bmm_chain_set_summary", "bmm_chain_summary_state",
     "bmm_chain_sweeps_summary", "bmm_chain_get_summary", "bmm_chain_summary_reset",
+    "bmm_chain_set_categorical", "bmm_chain_get_categorical", "bmm_set_categorical", "bmm_categorical_plan",
 ]
 
 
@@ -125,6 +126,12 @@ def load(path):
         L.bmm_chain_sweeps_summary.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.bmm_chain_get_summary.argtypes = [C.c_void_p, C.c_void_p]
         L.bmm_chain_summary_reset.argtypes = [C.c_void_p]
+    if hasattr(L, "bmm_chain_set_categorical"):  # (an older build loaded for a comparison has no categorical features)
+        L.bmm_chain_set_categorical.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.bmm_chain_get_categorical.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bmm_set_categorical.argtypes = [C.c_void_p, C.c_int]
+        L.bmm_categorical_plan.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
     if hasattr(L, "bmm_ladder_create"):  # (an older build loaded for a comparison has no ladder)
         L.bmm_ladder_destroy.restype = None
         L.bmm_ladder_destroy.argtypes = [C.c_void_p]

@@ -695,7 +695,7 @@ BMM_HD double group_entry(const double* e1, const double* e0, int g, int P, unsi
 // The log terms of a counting chain's table image -- which category scores, the argument of each log_ and when it is
 // needed -- for the three builds that call these functions: build_tables_self (BUILD_SELF) and
 // k_state_tables (BUILD_PREDICT, BUILD_LOO).  A builder takes the raw log_ of every argument that is needed and
-// subtracts the denominators afterwards (term_of, cat_consts).  The sweep's own launch, k_count_tables in its four
+// subtracts the denominators afterwards (term_of, cat_consts).  The sweep's own launch, k_count_tables in its five
 // flavours, is NOT among the callers: it keeps a body of its own (kernels.hip.h says why), and whoever changes a rule
 // of the finite sweep changes it there and here.
 //   BUILD_SELF     the finite sampler's z-step image as k_count_tables writes it: a label scores when it holds a row,
@@ -771,6 +771,30 @@ BMM_HD bool term_arg(const CountRule& r, int k, int role, int64_t n, int64_t s, 
 }
 BMM_HD int term_den(int role) { return role < 2 ? 0 : 1; }
 BMM_HD double term_of(bool have, double raw, double den) { return have ? raw - den : 0.0; }
+
+// Categorical features of the finite sweep (BUILD_SELF's conditions; k_count_tables<TAB_CAT>).
+// A feature of L >= 2 levels is a block of L neighbouring one-hot columns under a symmetric Dirichlet(beta, ..., beta):
+// a row has exactly one 1 in the block, so the predictive (beta + c_l) / (L beta + n) of its level is the block's
+// whole factor, and it rides on the x = 1 term of that level's column.  For a column of such a block with s ones among
+// the label's n rows:
+//   roles 0, 2   log(beta + s) - log(L beta + n), log(beta + (s - 1)) - log(L beta + (n - 1)): the numerator's log is
+//                that of a Bernoulli column (term_arg), the denominator the block's own (cat_den_arg) -- L beta is formed
+//                as (double)L * beta and the count added to it
+//   roles 1, 3   0: a level the row does not have says nothing more
+// A term exists when the Bernoulli term of its role exists, role 2 when n > 1 && s >= 1.  The DP's new cluster takes the
+// plain constant over the Bernoulli columns alone and then, block by block in ascending column order, cat_new_block
+// (1 / L, the prior predictive of any level).  No block: the plain build, bit for bit.  The stored-state builds
+// (BUILD_PREDICT, BUILD_LOO) and build_tables_self know the Bernoulli cell only: a categorical chain is offered neither.
+BMM_HD bool cat_term_arg(const CountRule& r, int k, int role, int64_t n, int64_t s, double& arg) {
+    if (role == 1 || role == 3) { arg = 1.0; return false; }
+    return term_arg(r, k, role, n, s, arg);
+}
+BMM_HD bool cat_den_arg(const CountRule& r, int k, int L, int role, int64_t n, double& arg) {
+    const double lbeta = (double)L * r.beta;
+    arg = role < 2 ? lbeta + (double)n : lbeta + (double)(n - 1);
+    return role < 2 ? rule_scores(r, k, n) : rule_minus(r, k, n);
+}
+BMM_HD double cat_new_block(double lb, double beta, int L) { return lb - log_((double)L * beta); }
 
 // ---------------------------------------------------------------- log joint of a state
 // log p(x, z, alpha, mask) of the state after a sweep from its folded counts (include/bmm_mcmc.h "log joint trace";

@@ -650,6 +650,17 @@ struct bmm_chain {
     double *dFsRec = nullptr, *dFsProb = nullptr;
     int fs_folded = 0, fs_last = -1;  // fs_last: the sweep of the last step, -1 none yet
     SweepTrace fs_rec;
+    // categorical features: cat_on: the table builds are k_count_tables<TAB_CAT>, reading dCatLev (P
+    // bytes: 0 a Bernoulli column, else the L of the column's block), and the kernel choice leaves out the forms that
+    // build their own tables; cat_checked: k_cat_check has passed these levels over these data.  One block holds the
+    // bytes, the block list and the check's key.
+    bool cat_on = false, cat_checked = false;
+    std::vector<int32_t> cat_levels;
+    std::vector<CatBlock> cat_blocks;
+    char* dCatBlock = nullptr;
+    uint8_t* dCatLev = nullptr;
+    CatBlock* dCatBlocks = nullptr;
+    unsigned long long* dCatBad = nullptr;
     // the last k-modes++ initialisation, kept on the host: the k_eff centres [k_eff][W], the
     // picked rows and the final cluster sizes
     int init_keff = 0;
@@ -823,7 +834,7 @@ int run_rows_out(const bmm_chain* c, const double* dtrace, int64_t width, double
 }
 
 // What is armed for the next whole-run call of the calling thread (bmm_set_partition_summary, bmm_set_partition_search, bmm_set_credible_ball, bmm_set_loo_summary,
-// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost, bmm_set_temper, bmm_set_pair_check, bmm_set_missing, bmm_set_constraints; bmm_alloc_run fills `alloc` for its own run), and what a
+// bmm_set_split_merge, bmm_set_feature_select, bmm_set_init, bmm_set_ecr_relabel, bmm_set_logpost, bmm_set_temper, bmm_set_pair_check, bmm_set_missing, bmm_set_constraints, bmm_set_categorical; bmm_alloc_run fills `alloc` for its own run), and what a
 // *_run_predict / *_run_relabel / *_run_probs entry point was handed.
 struct RunOptions {
     struct { bool on = false; bmm_partition_out o{}; } partition;
@@ -842,6 +853,7 @@ struct RunOptions {
     struct { int moves = 0, scans = 0; } as;  // bmm_set_alloc_split_merge: taken by bmm_alloc_run alone
     struct { bool on = false; int64_t n = 0; const int64_t* rows = nullptr; const uint64_t* masks = nullptr; } cs;  // bmm_set_constraints
     struct { bool on = false; bmm_summary_opts opts{}; bmm_summary_out o{}; } summary;  // bmm_set_summary
+    struct { bool on = false; std::vector<int32_t> levels; } cat;  // bmm_set_categorical (a copy: the caller's vector may go)
     bool keep_trace() const { return !summary.on || summary.opts.keep_trace != 0; }
     const bmm_relabel_hooks* hooks = nullptr;  // *_run_probs
     const bmm_relabel_out* rel = nullptr;      // *_run_relabel
@@ -1280,6 +1292,75 @@ int launch_resample(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t l
     return BMM_OK;
 }
 
+// ---- categorical features ----
+// what everything that scores a Bernoulli cell by itself answers a chain with levels set
+int cat_refuses(const char* what) {
+    return set_err(BMM_E_UNSUPPORTED, "%s knows the Bernoulli cell only: not offered on a chain with categorical features "
+                   "(bmm_chain_set_categorical)", what);
+}
+// The column map of a levels vector over P columns: feature f of levels[f] = 1 is a Bernoulli column, of L >= 2 a block
+// of L neighbouring one-hot columns.  lev (or null): the P bytes k_count_tables<TAB_CAT> reads; blocks (or null): the
+// list k_cat_check walks; first_column (or null): F entries.  No device is touched.
+int cat_map(const int32_t* levels, int F, int P, std::vector<uint8_t>* lev, std::vector<CatBlock>* blocks, int32_t* first_column) {
+    if (!levels || F < 1) return set_err(BMM_E_ARG, "categorical: null or empty levels");
+    if (F >= (1 << kCatKeyBits)) return set_err(BMM_E_ARG, "categorical: at most %d features", (1 << kCatKeyBits) - 1);
+    int64_t cols = 0;
+    for (int f = 0; f < F; ++f) {
+        if (levels[f] < 1)
+            return set_err(BMM_E_ARG, "categorical: feature %d has %d levels: a feature has at least 1 (1 is a binary feature in one column)", f, levels[f]);
+        if (levels[f] > 255) return set_err(BMM_E_ARG, "categorical: feature %d has %d levels: at most 255 are offered", f, levels[f]);
+        cols += levels[f];
+    }
+    if (cols != P) return set_err(BMM_E_ARG, "categorical: the levels take %lld columns, the chain has P = %d", (long long)cols, P);
+    if (lev) lev->assign((size_t)P, 0);
+    if (blocks) blocks->clear();
+    int col = 0;
+    for (int f = 0; f < F; ++f) {
+        const int L = levels[f];
+        if (first_column) first_column[f] = col;
+        if (L >= 2) {
+            if (lev) std::fill(lev->begin() + col, lev->begin() + col + L, (uint8_t)L);
+            if (blocks) blocks->push_back(CatBlock{col, L, f});
+        }
+        col += L;
+    }
+    return BMM_OK;
+}
+// k_cat_check over the resident planes, once per pairing of levels and data: every row has exactly one bit in every block
+int cat_check(bmm_chain* c) {
+    if (!c->cat_on || !c->have_data || c->cat_checked) return BMM_OK;
+    if (!c->bits || !c->dXb) return set_err(BMM_E_UNSUPPORTED, "categorical features read the bit planes: not offered on the int32 layout");
+    if (!c->cat_blocks.empty()) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipMemsetAsync(c->dCatBad, 0xff, sizeof(unsigned long long), c->stream));
+        const int64_t nb = (c->p.N + 255) / 256;
+        hipLaunchKernelGGL(k_cat_check, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, c->stream, (const uint32_t*)c->dXb,
+                           c->p.N, (const CatBlock*)c->dCatBlocks, (int)c->cat_blocks.size(), c->dCatBad);
+        HIP_TRY(hipGetLastError());
+        unsigned long long bad = 0;
+        HIP_TRY(hipMemcpyAsync(&bad, c->dCatBad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (bad != ~0ull) {
+            const int f = (int)(bad & ((1ull << kCatKeyBits) - 1));
+            int col = 0;
+            for (int g = 0; g < f; ++g) col += c->cat_levels[(size_t)g];
+            return set_err(BMM_E_ARG, "categorical: row %lld does not have exactly one level of feature %d (columns %d..%d): "
+                           "a block of one-hot columns holds a single 1 per row", (long long)(bad >> kCatKeyBits), f, col,
+                           col + c->cat_levels[(size_t)f] - 1);
+        }
+    }
+    c->cat_checked = true;
+    return BMM_OK;
+}
+// ... behind every hand-over of data to a chain whose levels are set: data that fail are not the chain's data
+int cat_data_changed(bmm_chain* c) {
+    if (!c->cat_on) return BMM_OK;
+    c->cat_checked = false;
+    const int rc = cat_check(c);
+    if (rc) c->have_data = false;
+    return rc;
+}
+
 // ---- constrained allocations ----
 // what the options that move rows by themselves, or hand the rows' probabilities on, answer an armed chain
 int cs_refuses(const char* what) {
@@ -1355,6 +1436,8 @@ int launch_count_tables(bmm_chain* c) {
         launch(k_count_tables<TAB_TEMPER, double>, nullptr, 0, c->temper_b);
     else if (c->fs_mask)  // feature selection: excluded features are written as zeros
         launch(k_count_tables<TAB_MASK>, (const uint32_t*)c->dFsMask, 0);
+    else if (c->cat_on)  // categorical features: a block's denominator rides on its x = 1 terms
+        launch(k_count_tables<TAB_CAT, const uint8_t*>, nullptr, c->form.pk && !c->generic ? 1 : 0, (const uint8_t*)c->dCatLev);
     else
         launch(k_count_tables<TAB_PLAIN>, nullptr, c->form.pk && !c->generic ? 1 : 0);
     HIP_TRY(hipGetLastError());
@@ -1585,6 +1668,7 @@ int sm_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_STATE, "split-merge moves are not offered on a sharded chain");
     if (c->na_on) return na_refuses("a split-merge move");
     if (c->cs_on) return cs_refuses("a split-merge move");
+    if (c->cat_on) return cat_refuses("the split-merge ratio");
     if (c->temper_on) return temper_refuses("the split-merge ratio");
     if (c->p.mode != MODE_DP)
         return set_err(BMM_E_UNSUPPORTED, "split-merge moves are offered for the DP sampler only (the finite sampler gives an "
@@ -1773,6 +1857,7 @@ int init_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_STATE, "the initialisation is not offered on a sharded chain");
     if (c->na_on) return na_refuses("a data-driven start");
     if (c->cs_on) return cs_refuses("a data-driven start");
+    if (c->cat_on) return cat_refuses("a data-driven start (its distance)");
     if (explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "a data-driven start is offered for the collapsed and DP samplers only: the stick-breaking and "
                        "full samplers start from pi and theta");
@@ -2000,7 +2085,7 @@ struct KernelPlan {
     bool named_size = false;  // form[0] has its workgroup size from BMM_DEBUG_THREADS (stage_width)
 };
 KernelPlan plan_kernel(const ChainParams& p, bool bits, int minus, int64_t batch, int num_cus, bool shares_device,
-                       size_t lds_bytes_base, const DebugSwitches& d, bool masked = false) {
+                       size_t lds_bytes_base, const DebugSwitches& d, bool masked = false, bool categorical = false) {
     const bool alt = p.W != kGroupW;  // the narrower groups: default-sized kernels only
     KernelForm f{p.KT, threads_for(p.KT, bits), minus, bits, 1, false, p.W, false};
     KernelPlan plan;
@@ -2068,9 +2153,10 @@ KernelPlan plan_kernel(const ChainParams& p, bool bits, int minus, int64_t batch
     // shape is bound by launches then, and this drops k_count_tables from every batch (BASELINE config 2)
     f.self = true;
     const size_t lds = (lds_bytes_base + 7) / 8 * 8 + self_scratch_doubles(p.K, p.KT, p.P) * sizeof(double);  // scratch behind the image
-    // (not for a chain with a feature mask: build_tables_self knows no mask, k_count_tables<TAB_MASK> does)
+    // (not for a chain with a feature mask: build_tables_self knows no mask, k_count_tables<TAB_MASK> does; nor for
+    // categorical features, which keep the packed form: k_count_tables<TAB_CAT> writes its image)
     if (BMM_SELF_TABLES && bits && minus == 1 && !shares_device && self_tables_fit(p.mode, p.K, p.P, 256) && !d.noself &&
-        !masked && instantiated(f, false) && lds <= kLdsMax)
+        !masked && !categorical && instantiated(f, false) && lds <= kLdsMax)
         offer(f, lds);
     return plan;
 }
@@ -2080,7 +2166,7 @@ int tier_of(const bmm_chain* c) { return explicit_params(c->p.mode) ? 0 : (c->mi
 // The chain's resident kernel, set up for launching: the last form of the plan that the runtime takes.
 int pick_kernel(bmm_chain* c) {
     const KernelPlan plan = plan_kernel(c->p, c->bits, tier_of(c), c->batch, c->num_cus, c->shares_device, c->lds_bytes_base,
-                                        DebugSwitches{}, c->fs_mask || c->alloc_on || c->temper_on);
+                                        DebugSwitches{}, c->fs_mask || c->alloc_on || c->temper_on, c->cat_on);
     hipError_t e = hipSetDevice(c->device);
     for (int i = 0; i < plan.n; ++i) {
         const KernelForm& f = plan.form[i];
@@ -2109,6 +2195,7 @@ int pick_kernel(bmm_chain* c) {
 int chain_start(bmm_chain* c) {
     const ChainParams& p = c->p;
     if (!c->have_data) return set_err(BMM_E_STATE, "data matrix not set");
+    if (c->cat_on && !c->cat_checked) { const int rcc = cat_check(c); if (rcc) return rcc; }
     if (p.mode != MODE_DP && !c->have_init)
         return set_err(BMM_E_STATE, p.mode == MODE_COLLAPSED ? "initial labels not set"
                                                              : "initial pi/theta not set");
@@ -2318,7 +2405,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     sum_release(c);
     void* bufs[] = {c->dX_owned, c->dScratch, c->dProbs, c->dWts, c->dWtot, c->dXnb, c->dPredTab, c->dPredMax, c->dPredSum, c->dRespAcc,
                     c->dLooTab, c->dLooAcc, c->dLooOut, c->dLooScratch, c->dSmSide, c->dSmSideLaunch, c->dSmLq, c->dSmStat, c->dSmCell,
-                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dAsBlock, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock, c->dNaBlock, c->dCsBlock,
+                    c->dSmCounters, c->dFsBlock, c->dEaBlock, c->dEaSide, c->dAsBlock, c->dLjBlock, c->dLjZ, c->dPcFeat, c->dPcXt, c->dPcBlock, c->dNaBlock, c->dCsBlock, c->dCatBlock,
                     c->dPnMb, c->dPnRow, c->dPnOff, c->dPnCol, c->dCellMax, c->dCellSum, c->dSplitTab, c->dPnScratch};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -2340,6 +2427,7 @@ int bmm_chain_set_x_layout(bmm_chain* c, int layout) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (layout != BMM_X_BITPLANES && layout != BMM_X_INT32) return set_err(BMM_E_ARG, "unknown X layout %d", layout);
     if (c->have_data || c->started) return set_err(BMM_E_STATE, "the X layout is chosen before the data are set");
+    if (c->cat_on && layout == BMM_X_INT32) return set_err(BMM_E_UNSUPPORTED, "categorical features read the bit planes: not offered on the int32 layout");
     c->bits = c->form.bits = layout == BMM_X_BITPLANES;
     if (c->generic) return BMM_OK;  // one kernel for both layouts there
     return pick_kernel(c);
@@ -2367,7 +2455,7 @@ int bmm_chain_set_data_host(bmm_chain* c, const int32_t* X) {
         int rc = validate_binary(c, c->dX, N * P);
         if (rc) return rc;
         c->have_data = true;
-        return BMM_OK;
+        return cat_data_changed(c);
     }
     // Bit planes from a host matrix: the host's own cores validate and pack it, slab by slab, into pinned
     // staging, and only the planes cross PCIe -- 4 * ceil(P/32) bytes per observation instead of 4 * P (8 MB
@@ -2413,7 +2501,7 @@ int bmm_chain_set_data_host(bmm_chain* c, const int32_t* X) {
         if (c->dX_owned) { (void)hipFree(c->dX_owned); c->dX_owned = nullptr; }
         c->dX = nullptr;
         c->have_data = true;
-        return BMM_OK;
+        return cat_data_changed(c);
     });
 }
 
@@ -2445,7 +2533,7 @@ int bmm_chain_set_data_device(bmm_chain* c, const void* dX) {
         c->dX = x;  // borrowed for the life of the chain
     }
     c->have_data = true;
-    return BMM_OK;
+    return cat_data_changed(c);
 }
 
 // ---- bit planes shared between chains, or filled by the caller (a broadcast) ----------------
@@ -2472,7 +2560,7 @@ int bmm_chain_share_data(bmm_chain* c, bmm_chain* from) {
     c->xb_borrowed = true;
     c->dX = nullptr;
     c->have_data = true;
-    return BMM_OK;
+    return cat_data_changed(c);
 }
 
 int bmm_chain_planes(bmm_chain* c, void** dXb, int64_t* n_words) {
@@ -2499,7 +2587,7 @@ int bmm_chain_planes_filled(bmm_chain* c) {
     HIP_TRY(hipDeviceSynchronize());  // whatever filled them ran on a stream of the caller's
     c->dX = nullptr;
     c->have_data = true;
-    return BMM_OK;
+    return cat_data_changed(c);
 }
 
 int bmm_chain_set_initial_labels(bmm_chain* c, const int32_t* z1) {
@@ -2561,6 +2649,7 @@ int bmm_chain_set_shard(bmm_chain* c, int64_t N_total, int64_t first_row) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (c->started) return set_err(BMM_E_STATE, "chain already started");
     if (c->cs_on) return cs_refuses("a shard");
+    if (c->cat_on) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered on a sharded chain");
     if (!explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "only the stick-breaking and full samplers shard exactly over observations");
     if (c->sum_on) return set_err(BMM_E_UNSUPPORTED, "a chain with an armed summary does not shard: a shard holds a part of the rows");
@@ -2757,6 +2846,7 @@ static int pred_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the predictive density is not offered on a sharded chain");
     if (c->fs_mask) return fs_mask_refuses("the predictive density");
     if (c->alloc_on) return alloc_refuses("the predictive density");
+    if (c->cat_on) return cat_refuses("the predictive density");
     return BMM_OK;
 }
 static int pred_reset(bmm_chain* c) {
@@ -3151,6 +3241,7 @@ static int loo_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the leave-one-out predictive is not offered on a sharded chain");
     if (c->na_on) return na_refuses("the leave-one-out predictive");
     if (c->cs_on) return cs_refuses("the leave-one-out predictive");
+    if (c->cat_on) return cat_refuses("the leave-one-out predictive");
     if (c->fs_mask) return fs_mask_refuses("the leave-one-out predictive");
     if (c->alloc_on) return alloc_refuses("the leave-one-out predictive");
     return BMM_OK;
@@ -3356,6 +3447,7 @@ static int loo_run_collect(bmm_chain* c, const RunOptions& o, Recording& rec, in
 // ---- log joint trace and keep-best allocation ----
 static int lp_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the log joint is not offered on a sharded chain: a shard holds a part of the counts");
+    if (c->cat_on) return cat_refuses("the log joint");
     return BMM_OK;
 }
 static int lp_armed(const bmm_chain* c) {
@@ -3591,6 +3683,7 @@ int bmm_device_log_joint(int device, const int32_t* X, int64_t N, int P, int sam
 static int pc_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "the pair check is not offered on a sharded chain: a shard holds a part of the rows");
     if (c->na_on) return na_refuses("the pair check (its column slices are cut once)");
+    if (c->cat_on) return cat_refuses("the pair check");
     if (c->fs_mask)
         return set_err(BMM_E_UNSUPPORTED, "the pair check is written for the model in which every feature clusters: not offered on a "
                        "chain with a feature mask (the pooled model's reference distribution is another one)");
@@ -3998,6 +4091,7 @@ static int alloc_refused(const bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (c->na_on) return na_refuses("the allocation sampler");
     if (c->cs_on) return cs_refuses("the allocation sampler");
+    if (c->cat_on) return cat_refuses("the allocation sampler");
     if (c->sum_on) return set_err(BMM_E_UNSUPPORTED, "the allocation sampler is not offered on a chain with an armed summary");
     if (c->sharded) return set_err(BMM_E_STATE, "the allocation sampler is not offered on a sharded chain");
     if (c->p.mode != MODE_COLLAPSED)
@@ -4319,6 +4413,7 @@ int bmm_chain_get_init_rows(bmm_chain* c, int64_t* rows, int32_t* Nk) {
 static int fs_refused(const bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (c->na_on) return na_refuses("feature selection");
+    if (c->cat_on) return cat_refuses("feature selection");
     if (c->sharded) return set_err(BMM_E_STATE, "feature selection is not offered on a sharded chain");
     if (explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "feature selection is offered for the collapsed and DP samplers only: the stick-breaking and "
@@ -4550,6 +4645,7 @@ static int na_check_cells(const int64_t* rows, const int32_t* cols, int64_t n, i
 static int na_refused(const bmm_chain* c) {
     if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered on a sharded chain");
     if (!c->bits) return set_err(BMM_E_UNSUPPORTED, "the imputation step rewrites the bit planes: not offered on the int32 layout");
+    if (c->cat_on) return cat_refuses("the imputation step");
     if (c->xb_borrowed || c->shares_device || (c->planes && c->planes->refs.load() > 1) || c->ladder)
         return set_err(BMM_E_UNSUPPORTED, "missing cells are not offered on planes that several chains read (bmm_chain_share_data, a "
                        "ladder): every chain would need completed cells of its own");
@@ -4871,12 +4967,158 @@ static int cs_run_collect(bmm_chain* c, const RunOptions& o, int rc) {
     return rc == BMM_OK && o.cs.on ? bmm_chain_constraint_stats(c, &g_cs_stats[0], &g_cs_stats[1]) : rc;
 }
 
+// ---- categorical features (include/bmm_mcmc.h "categorical features") ----
+// who may carry levels: a whole counting chain on bit planes whose every armed option reads labels and counts only
+static int cat_refused(const bmm_chain* c) {
+    if (!c->bits) return set_err(BMM_E_UNSUPPORTED, "categorical features read the bit planes: not offered on the int32 layout");
+    if (c->sharded) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered on a sharded chain");
+    if (explicit_params(c->p.mode))
+        return set_err(BMM_E_UNSUPPORTED, "categorical features are offered for the collapsed and DP samplers only: the stick-breaking "
+                       "and full samplers carry a Bernoulli theta per column");
+    if (c->alloc_on) return alloc_refuses("a categorical feature");
+    if (c->temper_on || c->ladder) return temper_refuses("a categorical feature");
+    if (c->fs_mask) return fs_mask_refuses("a categorical feature");
+    if (c->sm_moves > 0) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with split-merge moves: their ratio knows the Bernoulli cell only");
+    if (c->na_on) return na_refuses("a categorical feature");
+    if (c->predM > 0) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with newdata: the predictive tables know the Bernoulli cell only");
+    if (c->loo_on) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with the leave-one-out summary: its tables know the Bernoulli cell only");
+    if (c->lp_on) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with the log joint trace: its cells are Bernoulli cells");
+    if (c->pc_on) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with the pair check: the columns of a block depend on each other by construction");
+    if (c->shard_open) return set_err(BMM_E_STATE, "a sweep is open");
+    return BMM_OK;
+}
+static void cat_withdraw(bmm_chain* c) {
+    c->cat_on = c->cat_checked = false;
+    c->cat_levels.clear();
+    c->cat_blocks.clear();
+}
+
+int bmm_chain_set_categorical(bmm_chain* c, const int32_t* levels, int F) {
+    return guarded([&]() -> int {
+        if (!c) return set_err(BMM_E_ARG, "null chain");
+        if (F < 0) return set_err(BMM_E_ARG, "categorical: F must be >= 0");
+        if (c->in_run && c->sweep > 0) return set_err(BMM_E_STATE, "not offered inside a run");
+        if (F == 0) {  // withdrawn: every column is a Bernoulli column from the next table build on
+            if (!c->cat_on) return BMM_OK;
+            HIP_TRY(hipSetDevice(c->device));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            cat_withdraw(c);
+            return c->generic ? BMM_OK : pick_kernel(c);
+        }
+        std::vector<uint8_t> lev;
+        std::vector<CatBlock> blocks;
+        int rc = cat_map(levels, F, c->p.P, &lev, &blocks, nullptr);
+        if (rc == BMM_OK) rc = cat_refused(c);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t nb = blocks.size() ? blocks.size() : 1;
+        Carver measure{nullptr};
+        auto carve = [&](Carver& v) {
+            c->dCatBad = v.take<unsigned long long>(1);
+            c->dCatBlocks = v.take<CatBlock>(nb);
+            c->dCatLev = v.take<uint8_t>((size_t)c->p.P);
+        };
+        carve(measure);
+        HIP_TRY(hipStreamSynchronize(c->stream));  // a table build in flight reads the bytes that go
+        if (c->dCatBlock) { (void)hipFree(c->dCatBlock); c->dCatBlock = nullptr; }
+        const bool was = c->cat_on;
+        cat_withdraw(c);
+        HIP_TRY(hipMalloc(&c->dCatBlock, measure.used));
+        Carver real{c->dCatBlock};
+        carve(real);
+        HIP_TRY(hipMemsetAsync(c->dCatBlock, 0, measure.used, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->dCatLev, lev.data(), lev.size(), hipMemcpyHostToDevice, c->stream));
+        if (!blocks.empty())
+            HIP_TRY(hipMemcpyAsync(c->dCatBlocks, blocks.data(), blocks.size() * sizeof(CatBlock), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // the host vectors go
+        c->cat_levels.assign(levels, levels + F);
+        c->cat_blocks = blocks;
+        c->cat_on = true;
+        rc = cat_check(c);  // (a chain without data: checked when they arrive)
+        if (rc) {
+            cat_withdraw(c);
+            if (was && !c->generic) (void)pick_kernel(c);
+            return rc;
+        }
+        return c->generic ? BMM_OK : pick_kernel(c);  // again, without the forms that build their own tables
+    });
+}
+
+int bmm_chain_get_categorical(const bmm_chain* c, int32_t* levels, int* F) {
+    if (!c || !F) return set_err(BMM_E_ARG, "null argument");
+    *F = c->cat_on ? (int)c->cat_levels.size() : 0;
+    if (levels && c->cat_on) std::memcpy(levels, c->cat_levels.data(), c->cat_levels.size() * sizeof(int32_t));
+    return BMM_OK;
+}
+
+// The column map and the kernel form of a shape, without a device: first_column (or null) F entries, lev (or null) P
+// bytes as k_count_tables<TAB_CAT> reads them.  The form is the last one plan_kernel offers on num_cus compute units.
+int bmm_categorical_plan(int sampler, int64_t N, int K, int64_t batch, int num_cus, const int32_t* levels, int F,
+                         int32_t* first_column, uint8_t* lev_out, bmm_categorical_plan_out* out) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    if (sampler != BMM_SAMPLER_COLLAPSED && sampler != BMM_SAMPLER_DP)
+        return set_err(BMM_E_UNSUPPORTED, "categorical features are offered for the collapsed and DP samplers only");
+    if (N < 1 || K < 1 || num_cus < 1 || F < 1 || !levels) return set_err(BMM_E_ARG, "bmm_categorical_plan: N, K, num_cus, F >= 1");
+    int64_t P64 = 0;
+    for (int f = 0; f < F; ++f) P64 += levels[f] < 1 ? 1 : levels[f];
+    if (P64 > (1 << 24)) return set_err(BMM_E_ARG, "categorical: too many columns");
+    const int P = (int)P64;
+    std::vector<uint8_t> lev;
+    std::vector<CatBlock> blocks;
+    int rc = cat_map(levels, F, P, &lev, &blocks, first_column);
+    if (rc) return rc;
+    if (lev_out) std::memcpy(lev_out, lev.data(), lev.size());
+    const DebugSwitches dbg;
+    const ChainShape s = chain_shape(sampler, N, P, K, batch, dbg);
+    *out = bmm_categorical_plan_out{};
+    out->n_columns = P;
+    out->n_blocks = (int32_t)blocks.size();
+    out->generic = s.generic ? 1 : 0;
+    out->batch = s.batch;
+    if (s.generic) {
+        out->threads = 256; out->lanes = 1;
+        return BMM_OK;
+    }
+    const KernelPlan plan = plan_kernel(s.p, true, s.minus_in_lds ? 1 : 2, s.batch, num_cus, false, s.lds_bytes_base, dbg, false, true);
+    const KernelForm& f = plan.form[plan.n - 1];
+    out->threads = f.nt; out->lanes = f.lanes; out->packed = f.pk ? 1 : 0; out->builds_own_tables = f.self ? 1 : 0;
+    return BMM_OK;
+}
+
+// ... of a run: armed for it (bmm_set_categorical), refused before a device is touched
+static int cat_run_check(const RunOptions& o, int sampler, int P) {
+    if (!o.cat.on) return BMM_OK;
+    const int rc = cat_map(o.cat.levels.data(), (int)o.cat.levels.size(), P, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (dbg_env("BMM_X_LAYOUT_INT32") != nullptr) return set_err(BMM_E_UNSUPPORTED, "categorical features read the bit planes: not offered on the int32 layout");
+    if (explicit_params(sampler))
+        return set_err(BMM_E_UNSUPPORTED, "categorical features are offered for the collapsed and DP samplers only: the stick-breaking "
+                       "and full samplers carry a Bernoulli theta per column");
+    if (o.alloc.on) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered by the allocation sampler");
+    if (o.temper.on) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with parallel tempering");
+    if (o.fs.on) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with feature selection");
+    if (o.sm.moves > 0) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with split-merge moves: their ratio knows the Bernoulli cell only");
+    if (o.na.on) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with missing cells: the imputation step knows the Bernoulli cell only");
+    if (o.pred) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with newdata: the predictive tables know the Bernoulli cell only");
+    if (o.loo.on) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with the leave-one-out summary: its tables know the Bernoulli cell only");
+    if (o.logpost.on) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with the log joint trace: its cells are Bernoulli cells");
+    if (o.pc.on) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with the pair check: the columns of a block depend on each other by construction");
+    if (o.init.kind != 0) return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with a device start (init_labels): its distance counts a block's columns one by one");
+    if (o.hooks || o.rel)
+        return set_err(BMM_E_UNSUPPORTED, "categorical features are not offered together with a probability hand-off (relabel = TRUE); ECR reads the labels alone");
+    return BMM_OK;
+}
+static int cat_run_attach(bmm_chain* c, const RunOptions& o) {
+    return o.cat.on ? bmm_chain_set_categorical(c, o.cat.levels.data(), (int)o.cat.levels.size()) : BMM_OK;
+}
+
 // ---- parallel tempering: a replica ladder (include/bmm_mcmc.h "parallel tempering") ----
 // who may be a rung
 static int temper_refused(const bmm_chain* c) {
     if (!c) return set_err(BMM_E_ARG, "null chain");
     if (c->na_on) return na_refuses("parallel tempering");
     if (c->cs_on) return cs_refuses("parallel tempering");
+    if (c->cat_on) return cat_refuses("parallel tempering");
     if (c->sum_on) return set_err(BMM_E_UNSUPPORTED, "parallel tempering is not offered on a chain with an armed summary");
     if (explicit_params(c->p.mode))
         return set_err(BMM_E_UNSUPPORTED, "parallel tempering is offered for the collapsed and DP samplers only: the stick-breaking "
@@ -7068,6 +7310,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
     return guarded([&]() -> int {
         // refused before any device is touched
         int rc = check_run_args(X, nsamples, burnin, io, sampler, opts.keep_trace());
+        if (rc == BMM_OK) rc = cat_run_check(opts, sampler, P);  // (ahead of the options' own checks: it names the pairing)
         if (rc == BMM_OK) rc = pt_run_check(opts, nsamples - burnin, N, K);
         if (rc) return rc;
         g_init_info = bmm_init_info{};
@@ -7116,6 +7359,7 @@ int run_chain(int sampler, const int32_t* X, int64_t N, int P, int nsamples, int
             if (rc == BMM_OK) rc = init_run_attach(c, opts);
             if (rc == BMM_OK) rc = na_run_attach(c, opts);  // the cells are filled before anything counts them
             if (rc == BMM_OK) rc = cs_run_attach(c, opts);  // the starting labels are projected when the chain starts
+            if (rc == BMM_OK) rc = cat_run_attach(c, opts);  // the levels meet the data: k_cat_check
             if (rc) return rc;
             clock.lap(0);
             // what the options record per kept sweep: each ends, and waits for the stream before its rows go, on every way out
@@ -7542,6 +7786,15 @@ int bmm_set_constraints(int64_t n, const int64_t* rows, const uint64_t* masks) {
     g_armed.cs.n = n; g_armed.cs.rows = rows; g_armed.cs.masks = masks;
     return BMM_OK;
 }
+int bmm_set_categorical(const int32_t* levels, int F) {
+    g_armed.cat.on = false;
+    g_armed.cat.levels.clear();
+    if (F == 0) return BMM_OK;
+    if (F < 0 || !levels) return set_err(BMM_E_ARG, "categorical: null levels or F < 0");
+    g_armed.cat.levels.assign(levels, levels + F);
+    g_armed.cat.on = true;
+    return BMM_OK;
+}
 int bmm_last_constraint_stats(int64_t* proposed, int64_t* reverted) {
     if (!proposed || !reverted) return set_err(BMM_E_ARG, "null argument");
     *proposed = g_cs_stats[0]; *reverted = g_cs_stats[1];
@@ -7950,12 +8203,13 @@ int bmm_multi_run(int sampler, int n_chains, const int* devices, const int32_t* 
                   double* const* pi_out, int32_t* const* z_out, double* const* theta_out,
                   double* const* alpha_out) {
     const RunOptions armed = take_run_options();  // a run of several chains disarms whatever was armed ...
-    const bool na_armed = armed.na.on, cs_armed = armed.cs.on;
+    const bool na_armed = armed.na.on, cs_armed = armed.cs.on, cat_armed = armed.cat.on;
     const RunOptions opts;     // ... and runs every chain without it
     return guarded([&]() -> int {
         // (... but does not run over a matrix whose holes were zeroed as if nothing had been said)
         if (na_armed) return set_err(BMM_E_UNSUPPORTED, "missing cells (bmm_set_missing) are not offered by a run of several chains: they share one matrix");
         if (cs_armed) return set_err(BMM_E_UNSUPPORTED, "constrained rows (bmm_set_constraints) are not offered by a run of several chains");
+        if (cat_armed) return set_err(BMM_E_UNSUPPORTED, "categorical features (bmm_set_categorical) are not offered by a run of several chains (bmm_multi_run)");
         if (sampler < 0 || sampler > 3) return set_err(BMM_E_ARG, "unknown sampler %d", sampler);
         if (n_chains < 1) return set_err(BMM_E_ARG, "n_chains must be >= 1");
         if (!z_out || !theta_out || !alpha_out) return set_err(BMM_E_ARG, "null output table");

@@ -195,7 +195,7 @@ __device__ __forceinline__ void write_own32(int W, const double* o1, const doubl
 }
 
 constexpr int kCountTablesThreads = 576;
-// The table build of every counting chain, one body in four flavours.  A flavour changes expressions only where they
+// The table build of every counting chain, one body in five flavours.  A flavour changes expressions only where they
 // stand below, behind `if constexpr` or a `?:` on a constant, so that each instantiation is the kernel that was once
 // written out for it; the values a flavour alone needs are trailing kernel arguments that exist for it only.
 //   TAB_PLAIN   the collapsed and the DP chain.  `packed`: the chain runs k_resample_pk and the packed image goes
@@ -216,18 +216,40 @@ constexpr int kCountTablesThreads = 576;
 //               subtracted, in all four roles.  The category's constant (the allocation prior) is untouched; the DP's
 //               new-cluster constant carries b on its P prior Bernoulli terms only.  The multiply sits behind the log_
 //               of a term thread, off wave 8's chain of constants.
+//   TAB_CAT     categorical features (extra: lev, P bytes): lev[d] = 0 marks a Bernoulli column,
+//               computed as TAB_PLAIN computes it, operation for operation; lev[d] = L > 0 a column of a block of L
+//               neighbouring one-hot columns, one feature of L levels under a symmetric Dirichlet(beta, ..., beta).  A row
+//               has exactly one 1 in a block (k_cat_check), so the block's denominator rides on the x = 1 terms:
+//               role 0 is log(beta + s) - log(L beta + n), role 2 log(beta + (s - 1)) - log(L beta + (n - 1)), and the
+//               x = 0 terms, roles 1 and 3, are 0.  Their threads are idle and take the column's two denominators, so a
+//               thread still has one log_ on its path.  The DP's new cluster counts the Bernoulli columns in the plain
+//               expression and adds lb - log(L beta) per block, blocks in ascending column order (1 / L per feature).
+//               Every entry stays <= 0, so a packed chain keeps its image (`packed`) and k_resample_pk.  One barrier more
+//               than the other flavours, ahead of the chunk loop: behind it the cluster size is folded (Nk and dNk are
+//               not carried through the loop) and wave 8 of the new cluster's workgroup adds the blocks.
 // Every flavour folds and clears the deltas and writes the same image with the same roles and order of operations, so
 // the resample kernels are the ones every chain runs, and these bit-equalities hold against TAB_PLAIN: TAB_MASK with a
-// mask of all ones; TAB_TEMPER with b = 1 (x * 1.0 is x); TAB_ALLOC with no label empty or single and K a = alpha.
+// mask of all ones; TAB_TEMPER with b = 1 (x * 1.0 is x); TAB_ALLOC with no label empty or single and K a = alpha;
+// TAB_CAT with lev all zero.
 // The log terms are written out here; the kernel does not call the count-table rules of bmm_spec.h that
 // build_tables_self and k_state_tables share.  One kernel template over those functions wrote the same bits but
 // averaged 0.2 us (4 %) more per launch (profiles/r06/README.md), and this launch sits on every batch of every counting
 // chain.
-enum : int { TAB_PLAIN = 0, TAB_MASK = 1, TAB_ALLOC = 2, TAB_TEMPER = 3 };
+enum : int { TAB_PLAIN = 0, TAB_MASK = 1, TAB_ALLOC = 2, TAB_TEMPER = 3, TAB_CAT = 4 };
 template <int I, class T, class... R>
 __device__ __forceinline__ auto tab_extra(T t, R... r) {  // trailing kernel argument I
     if constexpr (I == 0) return t;
     else return tab_extra<I - 1>(r...);
+}
+// the LDS that TAB_CAT alone has (the other flavours' kernels hold none of it)
+template <bool ON>
+__device__ __forceinline__ double* tab_cat_lds() {
+    if constexpr (ON) {
+        __shared__ double a[256 + 2 * kMaxP];
+        return a;
+    } else {
+        return nullptr;
+    }
 }
 template <int F, class... Extra>
 __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParams p, int32_t* __restrict__ Nk,
@@ -238,18 +260,20 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
                                                                      double* __restrict__ tab,
                                                                      const uint32_t* __restrict__ mask,
                                                                      int packed, Extra... extra) {
-    constexpr bool MASK = F == TAB_MASK, ALLOC = F == TAB_ALLOC, TEMPER = F == TAB_TEMPER;
+    constexpr bool MASK = F == TAB_MASK, ALLOC = F == TAB_ALLOC, TEMPER = F == TAB_TEMPER, CAT = F == TAB_CAT;
     __shared__ double e1[kMaxP], e0[kMaxP], m1[kMaxP], m0[kMaxP], cst[4];  // cst: Cp, Cm, the two denominators
     const int k = blockIdx.x;
     const TableLayout L = layout_of(p, true);
     // the chain runs k_resample_pk: the packed image goes behind this one (uniform)
-    float* const Tq = F == TAB_PLAIN && packed ? reinterpret_cast<float*>(tab + L.doubles()) : nullptr;
+    float* const Tq = (F == TAB_PLAIN || CAT) && packed ? reinterpret_cast<float*>(tab + L.doubles()) : nullptr;
     const int P = p.P;
     const bool is_label = k < p.K;
     int Ka = 0;            // ALLOC: the number of open labels, and the Dirichlet parameter
     double a = 0.0, b = 1.0;  // TEMPER: the inverse temperature
     if constexpr (ALLOC) { Ka = *tab_extra<0>(extra...); a = tab_extra<1>(extra...); }
     if constexpr (TEMPER) b = tab_extra<0>(extra...);
+    const uint8_t* lev = nullptr;  // CAT: the block length of every column
+    if constexpr (CAT) lev = tab_extra<0>(extra...);
     const bool open = k < Ka;
     // 576 threads, ONE log_ each on the critical path (a log_ is about 150 dependent instructions).  Waves
     // 0-7: role r = thread / 128 -- the term of feature d for x = 1 and for x = 0 against the full
@@ -264,9 +288,18 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
     const size_t KP = (size_t)p.K * P;
     if (is_label) { n_old = Nk[k]; n_dl = delta_take(dNk, k, p.K); }
     if (is_label && dl < P) { s_old = S[(size_t)k * P + dl]; s_dl = delta_take(dS, (size_t)k * P + dl, KP); }
+    int lv = 0;  // CAT: lev of this thread's column in the first chunk
+    if constexpr (CAT) { if (is_label && dl < P) lv = lev[dl]; }
     const double alpha = ALLOC ? 0.0 : *alpha_ptr;
     const int64_t n = (int64_t)n_old + n_dl;
     const double bg = p.beta + p.gamma;
+    // CAT, the DP's new cluster (its term threads have no term): log(L beta) for every L a block can have, one per thread
+    const bool cat_new = CAT && p.mode == MODE_DP && k == p.K;
+    double* const lgl = tab_cat_lds<CAT>();       // CAT: [256], then the columns' denominators dn[2][kMaxP]
+    double* const dn = CAT ? lgl + 256 : nullptr;
+    if constexpr (CAT) {
+        if (cat_new && threadIdx.x >= 2 && threadIdx.x < 256) lgl[threadIdx.x] = log_((double)threadIdx.x * p.beta);
+    }
     if (role == 4) {
         const int lane = threadIdx.x & 63;
         const bool dp_new = !ALLOC && p.mode == MODE_DP && k == p.K;
@@ -300,12 +333,46 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
                 if (n > (ALLOC ? 0 : 1)) cm = lm - ldN;
             } else if (dp_new) {  // the prior of opening a cluster, then its (tempered) likelihood
                 if constexpr (TEMPER) cp = (la - ldN) + b * ((double)P * (lb - lbg));
+                else if constexpr (CAT) cp = la - ldN;  // the prior alone: the likelihood joins it behind the first barrier below
                 else cp = (la - ldN) + (double)p_in * (lb - lbg);
             }
             tab[L.cp() + k] = cp;
             tab[L.cm() + k] = cm;
             cst[0] = cp; cst[1] = cm; cst[2] = den_p; cst[3] = den_m;  // read after the first barrier below
             reinterpret_cast<int32_t*>(tab + L.nk())[k] = (int32_t)n;
+            if constexpr (CAT) { lgl[0] = lb; lgl[1] = lbg; }  // (threads 0 and 1 put no log there)
+        }
+    }
+    if constexpr (CAT) {
+        __syncthreads();  // lgl and cst are in place; every thread has read the old Nk and dNk
+        if (is_label && threadIdx.x == 0) {  // (here, not behind the loop: the two pointers are not carried through it,
+            Nk[k] = (int32_t)n;              // and the kernel has no scalar register to spare)
+            delta_clear(dNk, k, p.K);
+        }
+        // the DP's new cluster, the likelihood of its constant: the plain expression over the Bernoulli columns, then
+        // lb - log(L beta) per block, blocks in ascending column order.  Wave 8 walks the columns, 64 bytes of lev per
+        // load; cst[0] is read behind the chunk loop's barriers.  (vz: a zero the compiler takes for a lane's own, so
+        // that the walk's values live in vector registers.)
+        if (cat_new && role == 4) {
+            const int lane = threadIdx.x & 63;
+            const int vz = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) - lane;
+            const double lb = lgl[vz], lbg = lgl[vz + 1];
+            int p_in = 0;
+            for (int d = lane; d < P; d += 64) p_in += lev[d] == 0 ? 1 : 0;
+            for (int o = 32; o > 0; o >>= 1) p_in += __shfl_xor(p_in, o);
+            double cp = cst[vz] + (double)p_in * (lb - lbg);
+            int skip = vz;
+            for (int base = 0; base < P; base += 64) {
+                const int mine = base + lane < P ? (int)lev[base + lane] : 0;
+#pragma unroll 1
+                for (int j = 0; j < 64; ++j) {  // (the columns from P on: 0, a step that adds nothing)
+                    const int lj = __shfl(mine, j + vz);
+                    const bool starts = skip == 0 && lj > 0;
+                    cp = cp + (starts ? lb - lgl[lj] : 0.0);
+                    skip = starts ? lj - 1 : (skip > 0 ? skip - 1 : 0);
+                }
+            }
+            if (lane == 0) { tab[L.cp() + k] = cp; cst[0] = cp; }
         }
     }
     for (int c0 = 0; c0 < P; c0 += kChunkP) {  // kChunkP features (whole groups) at a time
@@ -317,6 +384,22 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
             const int d = c0 + dl;
             s = c0 == 0 ? s_old + s_dl : S[(size_t)k * P + d] + delta_take(dS, (size_t)k * P + d, KP);
             // term_x1 / term_x0 of bmm_spec.h, the denominator subtracted (and the power applied) below
+            if constexpr (CAT) {
+                // one log_ per thread, its argument picked by role and by the column's kind (no branch inside a branch: the
+                // kernel has no scalar register to spare).  A one-hot column (cat_den_arg of bmm_spec.h): roles 1 and 3
+                // have no term and take the column's two denominators.
+                if (c0 != 0) lv = lev[d];
+                const bool oh = lv > 0;
+                const double lbeta = (double)lv * p.beta;
+                double arg;
+                if (role == 0) { have = n > 0; arg = p.beta + (double)s; }
+                else if (role == 1) { have = n > 0; arg = oh ? lbeta + (double)n : (p.gamma + (double)n) - (double)s; }
+                else if (role == 2) { have = n > 1 && s >= 1; arg = p.beta + (double)((int64_t)s - 1); }
+                else { have = n > 1 && (oh || s <= n - 1); arg = oh ? lbeta + (double)(n - 1) : (p.gamma + (double)(n - 1)) - (double)s; }
+                const double lg = log_(have ? arg : 1.0);
+                raw = have ? lg : 0.0;
+                if (oh && (role & 1)) { dn[(role >> 1) * kMaxP + dl] = raw; have = false; }
+            } else
             if (role == 0) { have = ALLOC ? open : n > 0; raw = have ? log_(p.beta + (double)s) : 0.0; }
             else if (role == 1) { have = ALLOC ? open : n > 0; raw = have ? log_((p.gamma + (double)n) - (double)s) : 0.0; }
             else if (role == 2) { have = (ALLOC ? open && n > 0 : n > 1) && s >= 1; raw = have ? log_(p.beta + (double)((int64_t)s - 1)) : 0.0; }
@@ -325,6 +408,7 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
         __syncthreads();  // the constants are in place; every role has read S + dS before either is rewritten
         if (dl < pc) {
             double t = have ? (TEMPER ? b * (raw - cst[role < 2 ? 2 : 3]) : raw - cst[role < 2 ? 2 : 3]) : 0.0;
+            if constexpr (CAT) t = have ? raw - (lv > 0 ? dn[(role >> 1) * kMaxP + dl] : cst[role < 2 ? 2 : 3]) : 0.0;
             if (MASK && !((mask[(c0 + dl) >> 5] >> ((c0 + dl) & 31)) & 1u)) t = 0.0;
             (role == 0 ? e1 : role == 1 ? e0 : role == 2 ? m1 : m0)[dl] = t;
             if (role == 0 && is_label) {
@@ -343,11 +427,39 @@ __global__ __launch_bounds__(kCountTablesThreads) void k_count_tables(ChainParam
         }
         __syncthreads();
     }
-    if (is_label && threadIdx.x == 0) {  // every thread read the old pair before the barriers above
+    if (!CAT && is_label && threadIdx.x == 0) {  // every thread read the old pair before the barriers above
         Nk[k] = (int32_t)n;
         delta_clear(dNk, k, p.K);
     }
     if (k == 0 && threadIdx.x < 256) tab[L.et() + threadIdx.x] = exp256_table()[threadIdx.x];
+}
+
+// Categorical features: every row of the resident bit planes has exactly one bit set in every
+// block -- k_count_tables<TAB_CAT> scores a row on that footing, and a row with two bits, or none, would be scored
+// without a word.  A thread per row (grid-stride); a block may straddle plane words; the blocks ascend, so a row's first
+// bad block is the first one met.  The smallest (row, feature) key over all rows lands in *first_bad (all ones: clean).
+struct CatBlock { int32_t col, len, feature; };
+constexpr int kCatKeyBits = 20;  // features per key
+__global__ __launch_bounds__(256) void k_cat_check(const uint32_t* __restrict__ Xb, int64_t N,
+                                                   const CatBlock* __restrict__ blocks, int nb,
+                                                   unsigned long long* __restrict__ first_bad) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
+        for (int q = 0; q < nb; ++q) {
+            const CatBlock b = blocks[q];
+            const int end = b.col + b.len;  // one past the block's last column
+            int ones = 0;
+            for (int w = b.col >> 5; w <= (end - 1) >> 5; ++w) {
+                const int lo = b.col > 32 * w ? b.col - 32 * w : 0;
+                const int hi = end - 32 * w < 32 ? end - 32 * w : 32;  // bits [lo, hi) of word w
+                const uint32_t m = (hi - lo == 32 ? ~0u : (1u << (hi - lo)) - 1u) << lo;
+                ones += __popc(Xb[(int64_t)w * N + i] & m);
+            }
+            if (ones != 1) {
+                atomicMin(first_bad, ((unsigned long long)i << kCatKeyBits) | (unsigned long long)b.feature);
+                break;
+            }
+        }
+    }
 }
 
 // Stick-breaking: theta_kd ~ Beta(beta + V_kd, gamma + c_k - V_kd) (stickbreaking.cpp:217-229),

@@ -1651,6 +1651,52 @@ int bmm_chain_sweeps_summary(bmm_chain* c, int n, int64_t* agree, int32_t* permu
 int bmm_chain_get_summary(bmm_chain* c, bmm_summary_out* out);
 int bmm_chain_summary_reset(bmm_chain* c);
 
+/* ---- categorical features: polytomous items for the collapsed and the DP sampler ------------
+ * A feature j has L_j levels, levels[j].  L_j = 1 is a binary feature in one column under the chain's Beta(beta, gamma)
+ * prior, exactly the cell every chain has.  L_j >= 2 is a block of L_j neighbouring one-hot columns -- column l of the
+ * block is 1 in the rows at level l -- under a symmetric Dirichlet(beta, ..., beta) prior on the level probabilities,
+ * beta being the chain's beta.  The columns of the features, in order, are the chain's P columns.  For a cluster of n
+ * rows with c_l at level l the predictive of level l is (beta + c_l) / (L beta + n), with the scored row removed
+ * (beta + c_l - 1) / (L beta + n - 1); the DP's new cluster gives every level 1 / L.  (One-hot columns run through the
+ * Bernoulli model are a different model: it scores a row's L - 1 zeros, divides by beta + gamma + n per column and gives
+ * the new cluster (beta / (beta + gamma))^L per item.)  A block of 2 levels is Dirichlet(beta, beta): the Bernoulli
+ * column with gamma = beta.  The counts of ones per cluster are the level counts, so Nk, S, theta = S / Nk (the level
+ * proportions), the resample kernels and everything that reads labels and counts are unchanged; the sweep's table
+ * build alone (k_count_tables<TAB_CAT>) reads which columns form a block.
+ *
+ * bmm_chain_set_categorical: before or after the data, before the chain has started or between sweeps.  F = 0 withdraws
+ * the levels.  When levels and data first meet, and whenever either changes, the device checks that every row has
+ * exactly one bit set in every block (k_cat_check): BMM_E_ARG otherwise, and bmm_last_error names the first bad row and
+ * its feature; data that fail are not taken.  Levels of all 1 are the plain chain, byte for byte.
+ *   BMM_E_ARG: a level below 1 (or above 255); the levels' columns do not add up to P.  BMM_E_UNSUPPORTED, in either
+ * order of arming: the int32 layout; a sharded chain; the stick-breaking and the full sampler; the allocation sampler;
+ * parallel tempering (a ladder); feature selection; split-merge moves; missing cells; newdata, the leave-one-out
+ * summary, the log joint trace and the pair check (their scorers know the Bernoulli cell only); bmm_chain_init_labels.
+ * BMM_E_STATE: inside a run.  Unchanged beside it: the partition summary with its search and credible ball, ECR,
+ * constraints, the posterior summary, bmm_chain_sweep_probs, bmm_chain_get_counts / _get_params.  A categorical chain
+ * runs every resample form but those that build their own tables, the packed one (k_resample_pk) included. */
+int bmm_chain_set_categorical(bmm_chain* c, const int32_t* levels, int F);
+/* the levels a chain carries: *F (0: none), and levels[*F] when levels is not NULL */
+int bmm_chain_get_categorical(const bmm_chain* c, int32_t* levels, int* F);
+/* For a run: armed per calling thread for the NEXT bmm_collapsed_run / bmm_dp_run (and their _probs form without hooks)
+ * of that thread and disarmed when that call returns; F = 0 disarms.  The vector is copied.  BMM_E_ARG and
+ * BMM_E_UNSUPPORTED as above, before a device is touched, also for bmm_set_init, a *_run_relabel / hooked *_run_probs
+ * hand-off (relabel = TRUE), bmm_sb_run / bmm_full_run, bmm_alloc_run and bmm_multi_run. */
+int bmm_set_categorical(const int32_t* levels, int F);
+/* Pure bookkeeping, no device: the column map of a levels vector -- first_column[F] (or NULL), lev[P] (or NULL): 0 for a
+ * Bernoulli column, else the L of the column's block, the bytes the table build reads -- and the kernel form a chain of
+ * that shape gets on num_cus compute units (batch <= 0: the default batch).  P is the levels' sum. */
+typedef struct bmm_categorical_plan_out {
+    int32_t n_columns, n_blocks;
+    int32_t generic;            /* the shape runs the generic kernels */
+    int32_t threads, lanes;     /* of a resample workgroup; lanes per observation */
+    int32_t packed;             /* k_resample_pk: k_count_tables<TAB_CAT> writes the packed image */
+    int32_t builds_own_tables;  /* always 0: not offered to a categorical chain */
+    int64_t batch;
+} bmm_categorical_plan_out;
+int bmm_categorical_plan(int sampler, int64_t N, int K, int64_t batch, int num_cus, const int32_t* levels, int F,
+                         int32_t* first_column, uint8_t* lev, bmm_categorical_plan_out* out);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
