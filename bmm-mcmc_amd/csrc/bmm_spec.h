@@ -538,6 +538,73 @@ BMM_HD bool draw_pk(const float (&sc)[KT], float m, double u, int G, float unit,
     return nearest > pk_band(m, G, unit) * run && m > -__builtin_inff() && m < __builtin_inff();  // false when `run` is NaN
 }
 
+// ---------------------------------------------------------------- the draw from the binary32 entries, summed in binary64
+// The middle tier (k_resample_pk, for the lanes draw_pk leaves uncertain): the same binary32 entries the packed loop
+// reads -- Tq for every category, Tm32 for the observation's own label, padding groups included -- each widened to
+// binary64 and added in binary64, then the definition's own steps on those scores: the maximum m^, d_k = s^_k - m^,
+// expw_, a binary64 running sum in label order, t = u c^_K and the count.  What is left of the packed tier's error is
+// what the entries themselves lost when they were narrowed; the summation, the exponential and the running sum no
+// longer add to it.  As for draw_pk, `true` means the count is PROVEN to be the definition's.
+//
+// The band, per observation: kMidEpsUnit * (kMidC0 + 2 (|m^| + ln 64 + 1)) * c^_K.  With h = 2^-24 and s_k, m,
+// d_k = s_k - m <= 0, w_k = e^(d_k), T = sum w_k >= 1 the definition's quantities, as in draw_pk's derivation:
+//   an entry narrowed to binary32 is within half an ulp of itself, at most h relative; the host test pushes every
+//     narrowed entry a further whole ulp, at most 2 h relative (an ulp of binary32 is between h and 2 h of the value).
+//     Entries are <= 0, so sum |entry| = |s_k|: the exact sum of the entries is within h |s_k| of s_k as the kernel
+//     has them and within 3 h |s_k| as the test pushes them.  The band is sized for the pushed ones.
+//   the binary64 sum of G widened entries, in any order: each addition within 2^-53 of a partial sum no larger than
+//     |s_k|, at most G 2^-53 |s_k|.  The own score: the entries group the terms W at a time where the definition
+//     groups them three at a time, a further (P + G + Gm) 2^-53 |s_k| < 2^-45 |s_k| (draw_pk).  Together
+//     |s^_k - s_k| <= (3 h + 2^-44) |s_k| < 3.0001 h |s_k|.
+//   a shift common to all categories cancels in the sign of t - cdf_k, so m^ need not be m.  The weight of category k
+//     is off by the factor e^x, |x| <= 3.0001 h |s_k| + 2^-52 |d_k| (the subtraction's rounding) < 4e-4 down to scores
+//     of -2000, so e^x - 1 <= 1.0002 |x|.  With |s_k| = |m| + |d_k| and sum_k w_k |d_k| <= T ln K the weights together
+//     are off by at most 3.001 h (|m| + ln 64) T.
+//   expw_ (< 2^-52 of each weight), the running sum (K - 1 binary64 additions, or ceil(log2 K) levels of a log-step
+//     scan where the kernel takes one: at most 63 * 2^-53 either way), the product u c^_K (2^-53) and the definition's
+//     own rounding (2^-45): together < 2^-44 = 2^-20 h.
+// In all E <= h (3.001 (|m| + ln 64) + 2^-20) in units of T, |m^| >= |m| (1 - 3.0001 h) and c^_K >= T (1 - E).  With
+// kMidEpsUnit = 4.8 h and kMidC0 = 1 the band is 4.8 h (1 + 2 (|m^| + ln 64 + 1)) c^_K > 3.19 E T: the packed band's
+// factor of more than three, against entries an ulp further off than the kernel ever has them (against the kernel's
+// own h per entry the factor is above nine).  Next to the packed band at C5 (G = 20, |m| about 60):
+// 4.8 (1 + 2 * 65.2) / (3.2 (80 + 22 * 65.2)) = 0.13.
+// Ties and categories of weight zero are never "further than"; a NaN among the scores, a maximum that is not finite
+// (+inf, or every category impossible) and a NaN total are never certain: draw_tier1's rules.
+constexpr double kMidEpsUnit = 4.8 * 0x1p-24;
+constexpr double kMidC0 = 1.0;
+constexpr double kMidLnCats = 4.1588830833596715;  // ln kTier1MaxCats
+BMM_HD double mid_band(double m, double unit) {
+    return unit * (kMidC0 + 2.0 * (__builtin_fabs(m) + kMidLnCats + 1.0));
+}
+// e[g][k]: the binary32 entry of group g < G for category k (the own label's column from Tm32), u the draw's uniform,
+// unit = kMidEpsUnit (0: no band, for the tests that show what the band is for).
+template <int KT, int GMAX>
+BMM_HD bool draw_mid(const float (&e)[GMAX][KT], int G, double u, double unit, int& cnt) {
+    static_assert(KT <= kTier1MaxCats, "the band is derived for at most kTier1MaxCats categories");
+    double sc[KT], c[KT];
+    double m = neg_inf();
+    bool nan = false;
+    for (int k = 0; k < KT; ++k) {
+        double a = 0.0;
+        for (int g = 0; g < G; ++g) a = a + (double)e[g][k];
+        sc[k] = a;
+        nan = nan || a != a;
+        m = __builtin_fmax(m, a);
+    }
+    double run = 0.0;
+    for (int k = 0; k < KT; ++k) { run = run + expw_(sc[k] - m); c[k] = run; }
+    const double t = u * run;
+    const double band = mid_band(m, unit) * run;
+    bool clear = true;
+    int n = 0;
+    for (int k = 0; k < KT; ++k) {
+        n += t >= c[k] ? 1 : 0;
+        clear = clear && __builtin_fabs(t - c[k]) > band;  // false for a NaN
+    }
+    cnt = n;
+    return clear && !nan && m > neg_inf() && m < pos_inf();
+}
+
 // ---------------------------------------------------------------- variates
 // Standard normal by the Marsaglia polar method (log and sqrt only).
 BMM_HD double rnorm_(Stream& st) {

@@ -587,6 +587,7 @@ struct bmm_chain {
     int32_t *dDNkAlt = nullptr, *dDSAlt = nullptr;  // ... and the second set of delta accumulators (self_fold_prev)
     unsigned long long* dPkStat = nullptr;  // -DBMM_DEBUG_HOOKS: k_resample_pk's draws and deferred observations
     int pk_defer_every = 0;       // -DBMM_DEBUG_HOOKS: BMM_DEBUG_PK_DEFER_EVERY as read when the chain was made
+    int pk_mid_fail_every = 0;    //   ... and BMM_DEBUG_PK_MID_FAIL_EVERY
     int* dDbgFlag = nullptr;      // -DBMM_DEBUG_HOOKS: raised by a kernel that meets a label out of range
     // posterior predictive of new rows: their bit planes [ceil(P/32)][predM], the predictive
     // table image of the counting samplers (the explicit samplers' own image dTab is the predictive image), the
@@ -949,6 +950,10 @@ struct DebugSwitches {
     // settled lanes share a wave (tests/test_gpu_pk_inline.py).  BMM_DEBUG_PK_QUEUE is still accepted and does nothing:
     // the queue it sized is gone
     int pk_defer_every = dbg_env_int("BMM_DEBUG_PK_DEFER_EVERY", 0);
+    // n >= 1: k_resample_pk's middle settle tier reports "uncertain" for observation indices that are multiples of n, so
+    // that lanes settled by it and by the definition share a wave (tests/test_gpu_pk_mid.py).  BMM_DEBUG_PK_NOMID
+    // (launch_resample) skips the middle tier: the definition settles every uncertain lane, as before there was one
+    int pk_mid_fail_every = dbg_env_int("BMM_DEBUG_PK_MID_FAIL_EVERY", 0);
 };
 
 // What follows from (sampler, N, P, K, batch) alone -- no device state enters.
@@ -1174,7 +1179,7 @@ int chain_alloc(bmm_chain* c) {
         c->dDS = a.take<int32_t>(ns * kDeltaReps);
         c->dTab = a.take<double>(ntab);
 #ifdef BMM_DIAG
-        c->dDiag = a.take<unsigned long long>(18);
+        c->dDiag = a.take<unsigned long long>(22);
 #endif
         c->dSelfDone = a.take<int>(1);
         c->dViable = a.take<int>(1);
@@ -1182,7 +1187,7 @@ int chain_alloc(bmm_chain* c) {
         c->dDSAlt = a.take<int32_t>(ns * kDeltaReps);
 #ifdef BMM_DEBUG_HOOKS
         c->dDbgFlag = a.take<int>(1);
-        c->dPkStat = a.take<unsigned long long>(3);
+        c->dPkStat = a.take<unsigned long long>(6);
 #endif
         const size_t zeroed = a.used;
         c->dAlpha = a.take<double>(1);
@@ -1225,11 +1230,12 @@ int launch_resample(bmm_chain* c, const int32_t* z_in, int32_t* z_out, int64_t l
     a.lo = lo; a.hi = hi; a.sweep = sweep; a.minus_in_lds = c->minus_in_lds; a.diag = c->dDiag;
     a.dbg_flag = c->dDbgFlag; a.dbg_inject = (dbg_env("BMM_DEBUG_BADLABEL") ? 1 : 0) | (dbg_env("BMM_DEBUG_STRAGGLER") ? 2 : 0) |
                                              (dbg_env("BMM_DEBUG_DRAW_FALLBACK") ? 4 : 0) | (dbg_env("BMM_DEBUG_DRAW_NOEPS") ? 8 : 0) |
-                                             (dbg_env("BMM_DEBUG_PK_GENKEY") ? 16 : 0);
+                                             (dbg_env("BMM_DEBUG_PK_GENKEY") ? 16 : 0) | (dbg_env("BMM_DEBUG_PK_NOMID") ? 32 : 0);
     a.Nk = c->dNk; a.S = c->dS; a.alpha_ptr = c->dAlpha; a.self_done = c->dSelfDone;
 #ifdef BMM_DEBUG_HOOKS
     a.pk_stat = c->dPkStat;
     a.pk_defer_every = c->pk_defer_every;
+    a.pk_mid_fail_every = c->pk_mid_fail_every;
 #endif
     const bool emit = c->probs_dst != nullptr;
     const bool use_generic = c->generic || (emit && !c->fn_emit);  // the int32 layout has no emitting twin
@@ -2350,6 +2356,7 @@ int bmm_chain_create(bmm_chain** out, int sampler, int64_t N, int P, int K, doub
     if (cus <= 0) { delete c; return set_err(BMM_E_HIP, "hipGetDeviceProperties failed"); }
     c->bits = !dbg.int32_layout;
     c->pk_defer_every = dbg.pk_defer_every;
+    c->pk_mid_fail_every = dbg.pk_mid_fail_every;
     c->generic = shape.generic;
     c->minus_in_lds = shape.minus_in_lds;
     c->lds_bytes_base = c->lds_bytes = shape.lds_bytes_base;
@@ -2374,7 +2381,7 @@ void bmm_chain_destroy(bmm_chain* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
 #ifdef BMM_DIAG
     if (c->dDiag) {
-        unsigned long long d[18] = {};
+        unsigned long long d[22] = {};
         const bool ok = hipMemcpy(d, c->dDiag, sizeof d, hipMemcpyDeviceToHost) == hipSuccess;
         if (ok && d[5] && d[0]) {  // (k_resample_pk stamps the launch phases only)
             const double tot = (double)(d[0] + d[1] + d[2] + d[3] + d[4]);
@@ -2390,6 +2397,19 @@ void bmm_chain_destroy(bmm_chain* c) {
         if (ok && d[7] && d[17])  // ... and wave 0's trips: between the first and the last lookup of a trip, and the rest of the loop
             fprintf(stderr, "[bmm diag trip pk] trips of wave 0: %llu, ticks per trip: scoring %.0f, outside it %.0f\n", d[17],
                     d[16] / (double)d[17], ((double)d[9] - (double)d[16]) / (double)d[17]);
+        if (ok && d[7] && (d[19] || d[21]))  // ... and the lanes wave 0 settled: inside the middle tier, inside the definition
+            fprintf(stderr, "[bmm diag settle pk] wave 0 per workgroup-launch: middle tier runs %.4f at %.0f ticks each, definition runs %.4f at %.0f ticks each, "
+                    "together %.0f ticks of the tile loop's %.0f (%.2f%%)\n",
+                    d[19] / (double)d[7], d[19] ? d[18] / (double)d[19] : 0.0, d[21] / (double)d[7], d[21] ? d[20] / (double)d[21] : 0.0,
+                    (double)(d[18] + d[20]) / (double)d[7], d[9] / (double)d[5], 100.0 * (double)(d[18] + d[20]) / (double)d[9]);
+#ifdef BMM_DEBUG_HOOKS
+        if (ok && d[7] && c->dPkStat) {  // the test variant's counters of every wave, over the chain's life
+            unsigned long long v[6] = {};
+            if (hipMemcpy(v, c->dPkStat, sizeof v, hipMemcpyDeviceToHost) == hipSuccess && v[0])
+                fprintf(stderr, "[bmm diag tiers pk] draws %llu deferred %llu (%.4f%%) middle tier tried %llu settled %llu definition runs %llu\n", v[0],
+                        v[1], 100.0 * (double)v[1] / (double)v[0], v[3], v[4], v[5]);
+        }
+#endif
         if (ok && d[5] && d[12])
             fprintf(stderr, "[bmm diag draw] draws of a wave (64 observations) %llu, of them by the binary64 definition %llu (%.4f%%)\n",
                     d[12], d[13], 100.0 * (double)d[13] / (double)d[12]);
@@ -7154,6 +7174,20 @@ extern "C" int bmm_dbg_pk_unselected(bmm_chain* c, unsigned long long* n) {
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipMemcpy(n, c->dPkStat + 2, sizeof *n, hipMemcpyDeviceToHost));
+        return BMM_OK;
+    });
+}
+// ... and how the deferred were settled: runs of the middle tier (pk_mid_count), of them certain, runs of the
+// definition (pk_exact_count) (tests/test_gpu_pk_mid.py: tried == deferred, definition == tried - settled)
+extern "C" int bmm_dbg_pk_tier_counts(bmm_chain* c, unsigned long long* mid_tried, unsigned long long* mid_settled,
+                                      unsigned long long* exact_runs) {
+    if (!c || !mid_tried || !mid_settled || !exact_runs) return set_err(BMM_E_ARG, "null argument");
+    return guarded([&]() -> int {
+        unsigned long long v[3] = {0, 0, 0};
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipMemcpy(v, c->dPkStat + 3, sizeof v, hipMemcpyDeviceToHost));
+        *mid_tried = v[0]; *mid_settled = v[1]; *exact_runs = v[2];
         return BMM_OK;
     });
 }

@@ -694,9 +694,12 @@ struct ResampleArgs {
     // k_resample_pk, test variant: its counters [draws, deferred, of the deferred those the packed tier left uncertain
     // and BMM_DEBUG_PK_DEFER_EVERY did not select], and BMM_DEBUG_PK_DEFER_EVERY (n > 0: a lane whose observation index
     // is a multiple of n counts as uncertain)
+    // then the settle tiers' [runs of the middle tier, of them certain, runs of the definition], and
+    // BMM_DEBUG_PK_MID_FAIL_EVERY (n > 0: the middle tier's verdict is dropped for observation indices that are multiples of n)
     unsigned long long* pk_stat;
 #ifdef BMM_DEBUG_HOOKS
     int pk_defer_every;
+    int pk_mid_fail_every;
 #endif
 };
 
@@ -1478,6 +1481,9 @@ __global__ __launch_bounds__(NT) void k_resample(ChainParams p, ResampleArgs a) 
 // one lane per category, Tp and the width-3 Tm read from the global image, every load in flight at once), and the
 // count goes into that lane, so the labels are k_resample's bit for bit.  From there on certain and settled lanes
 // are the same: one count_movers, one pipelined store.  No phase follows the tile loop but the flush of the histogram.
+// Since round 12 a middle tier stands ahead of the definition: pk_mid_count sums the lane's binary32 entries, which are
+// in LDS, in binary64 (draw_mid, bmm_spec.h) and settles about six uncertain lanes in seven at C5 for 1 600 ticks
+// instead of 8 900, at priority 3; the definition runs, unchanged, for the rest (profiles/r12/README.md).
 // Settling is not free: measured at C5 (profiles/r08/README.md) a settled lane lengthens its wave's loop by about
 // 8 800 cycles -- the definition is a chain of dependent binary64 steps; the SIMD's other waves take the issue slots
 // meanwhile, but the workgroup's barrier waits for the wave that settled most -- and about half of the 12 us the pass
@@ -1601,6 +1607,123 @@ __device__ __forceinline__ int pk_exact_count(const ChainParams& p, const Resamp
     int zn = (int)__popcll(__ballot(lane < KT && t >= cdf));
     if (!(m > neg_inf())) zn = zoc;  // every category impossible: keep (or 0)
     return zn;
+}
+
+// One step of a walk over the lanes of a wave in DPP moves (two v_mov_b32 with a DPP control, no LDS crossbar and no
+// s_waitcnt): x as the lanes CTRL names hold it, `old` where CTRL names no lane or ROWS leaves the row out.
+// CTRL: 0x110 + n is row_shr:n (lane i - n of the same row of 16), 0x142 row_bcast:15 (lane 15 of the row below).
+template <int CTRL, int ROWS>
+__device__ __forceinline__ double pk_dpp(double old, double x) {
+    const long long o = __double_as_longlong(old), b = __double_as_longlong(x);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)o, (int)(uint32_t)b, CTRL, ROWS, 0xf, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(o >> 32), (int)(uint32_t)(b >> 32), CTRL, ROWS, 0xf, false);
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+// bits [g GW, g GW + GW) of a pattern whose words are uniform, g known at compile time: scalar shifts, no lane involved
+template <int GW, int g>
+__device__ __forceinline__ unsigned pk_field_at(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
+    constexpr int bit = g * GW, wd = bit >> 5, sh = bit & 31;
+    static_assert(bit + GW <= kMaxP, "a group of the pattern");
+    const uint32_t lo = wd == 0 ? w0 : (wd == 1 ? w1 : (wd == 2 ? w2 : w3));
+    const uint32_t hi = wd == 0 ? w1 : (wd == 1 ? w2 : (wd == 2 ? w3 : 0u));
+    const uint32_t f = sh + GW <= 32 ? lo >> sh : (lo >> sh) | (hi << ((32 - sh) & 31));
+    return f & (unsigned)((1 << GW) - 1);
+}
+
+// The middle tier for one observation, by the whole wave, ahead of the definition: draw_mid (bmm_spec.h) on the
+// binary32 entries the packed loop read for it, which are all in LDS.  As in pk_exact_count everything about the
+// observation is wave-uniform and lane k takes category k: the G entries of its column (a whole first round at
+// compile-time groups, the field a scalar extract; behind it the field of group g from lane g by v_readlane), up to
+// MR reads issued before the first is used, each widened and added in binary64 (four partial
+// sums: any order is within draw_mid's band).  The lane of the observation's own label reads its column of Tm32 where
+// the others read theirs of Tq -- the two images have the same stride from group to group, so that is another base
+// and the field taken once, not twice -- and nothing is added across lanes.  The maximum and the running sum are
+// log-step walks in DPP moves over the 32 lanes that can hold a category (four steps inside a row of 16, one from row
+// to row), the total and the maximum come from lane 31 by v_readlane, expw_tab reads E in LDS, the count and the
+// verdict are ballots.  No global load, and two waits for LDS in all.  `certain` is uniform; where it comes back false
+// the caller runs pk_exact_count as before.
+// A first form walked the lanes with ds_bpermute_b32 (17 round trips through the LDS pipeline, which the scoring waves
+// keep busy) and added the own entries across lanes: 6 200 ticks per observation where the definition takes 8 900;
+// a second took every field by v_readlane and ran at priority 0: 3 300 (profiles/r12/README.md).
+template <int KT, int GW>
+__device__ __forceinline__ int pk_mid_count(const TableLayout& L, int G, const char* smem, uint32_t w0, uint32_t w1,
+                                            uint32_t w2, uint32_t w3, int zo, double u, const lds_f64* ET, int lane,
+                                            bool& certain) {
+    constexpr int GM = 1 << GW;
+    // reads in flight, one VGPR each: as many as pk_exact_count has loads in flight at two VGPRs each, so that this
+    // block, not that one, never decides a form's registers (C5's twenty groups are one round)
+    constexpr int MR = KT <= 4 ? 6 : KT <= 8 ? 10 : 20;
+    static_assert(KT <= 32, "the walks cover two rows of 16 lanes");
+    static_assert((kMaxP + GW - 1) / GW <= 64, "lane g holds the field of group g");
+    const lds_f32* const img = (const lds_f32*)smem;  // Tq as single entries (pair j of a row at 2 j and 2 j + 1), Tm32 behind it
+    const int k = lane < KT ? lane : KT - 1;
+    const bool is_own = lane == zo;  // (zo < KT; -1: no lane)
+    // entry of group g at field f: Tq[g * KT * GM + (k / 2) * 2 GM + 2 f + (k & 1)], Tm32[g * KT * GM + zo * GM + f]
+    const unsigned base = is_own ? 2u * (unsigned)pk_tq_doubles(L) + (unsigned)k * GM : (unsigned)(k >> 1) * (2 * GM) + (unsigned)(k & 1);
+    const unsigned fsh = is_own ? 0u : 1u;
+    double part[4] = {0.0, 0.0, 0.0, 0.0};
+    int g_from = 0;
+    if (G >= MR) {
+        // a whole first round (C5's twenty groups): groups known at compile time, so a field is a scalar extract of the
+        // uniform words and a row an instruction offset -- one VALU instruction and the read per group
+        static_assert(MR * GW <= kMaxP, "the first round's groups exist");
+        float tv[MR];
+        pk_static_for<0, MR>([&](auto J) {
+            constexpr int g = decltype(J)::value;
+            tv[g] = img[(unsigned)g * (KT * GM) + (base + (pk_field_at<GW, g>(w0, w1, w2, w3) << fsh))];
+        });
+        pk_static_for<0, MR>([&](auto J) {
+            constexpr int g = decltype(J)::value;
+            part[g & 3] = part[g & 3] + (double)tv[g];
+        });
+        g_from = MR;
+    }
+    // the groups behind it, and every group of a shape with fewer than MR: lane g extracts the field of group g with
+    // selects and the groups read theirs from it by v_readlane, as pk_exact_count does
+    int fld = 0;
+    if (g_from < G) {
+        const int gl = lane < G ? lane : G - 1;
+        fld = (int)pk_field(gl * GW, GM - 1, w0, w1, w2, w3);
+    }
+#pragma unroll 1
+    for (int g0 = g_from; g0 < G; g0 += MR) {
+        float tv[MR];
+#pragma unroll
+        for (int v = 0; v < MR; ++v) {
+            const int g = g0 + v < G ? g0 + v : G - 1;
+            tv[v] = img[(unsigned)g * (KT * GM) + base + ((unsigned)__builtin_amdgcn_readlane(fld, g) << fsh)];
+        }
+#pragma unroll
+        for (int v = 0; v < MR; ++v)
+            if (g0 + v < G) part[v & 3] = part[v & 3] + (double)tv[v];
+    }
+    double sc = (part[0] + part[1]) + (part[2] + part[3]);
+    if (lane >= KT) sc = neg_inf();
+    const bool nan = __ballot(sc != sc) != 0;
+    // the maximum of lanes 0 .. 31 in lane 31: row_shr 1, 2, 4, 8 leave a row's maximum in its lane 15, row_bcast:15
+    // brings row 0's to row 1 (a lane without a source keeps its own value)
+    double m = sc;
+    m = __builtin_fmax(m, pk_dpp<0x111, 0xf>(m, m));
+    m = __builtin_fmax(m, pk_dpp<0x112, 0xf>(m, m));
+    m = __builtin_fmax(m, pk_dpp<0x114, 0xf>(m, m));
+    m = __builtin_fmax(m, pk_dpp<0x118, 0xf>(m, m));
+    m = __builtin_fmax(m, pk_dpp<0x142, 0xa>(m, m));
+    m = pk_bcast(m, 31);
+    // the running sum in label order, the same walk with 0 where there is no source (lanes from KT on weigh 0)
+    double cdf = lane < KT ? expw_tab(sc - m, ET) : 0.0;
+    cdf = cdf + pk_dpp<0x111, 0xf>(0.0, cdf);
+    cdf = cdf + pk_dpp<0x112, 0xf>(0.0, cdf);
+    cdf = cdf + pk_dpp<0x114, 0xf>(0.0, cdf);
+    cdf = cdf + pk_dpp<0x118, 0xf>(0.0, cdf);
+    cdf = cdf + pk_dpp<0x142, 0xa>(0.0, cdf);
+    const double tot = pk_bcast(cdf, 31);
+    const double t = u * tot;
+    const double band = mid_band(m, kMidEpsUnit) * tot;
+    const int cnt = (int)__popcll(__ballot(lane < KT && t >= cdf));
+    const bool close = __ballot(lane < KT && !(__builtin_fabs(t - cdf) > band)) != 0;  // a NaN is close
+    certain = !close && !nan && m > neg_inf() && m < pos_inf();
+    return cnt;
 }
 
 // The kernel's arguments as the blocks outside the loop's steady state read them: from the kernel argument segment,
@@ -1873,12 +1996,22 @@ __device__ __forceinline__ void pk_score(const volatile lds_pk_f2* Tq, const vol
 // it to them is a change of its own, with its own timings.  Both bodies of every form: profiles/r11/README.md.
 constexpr bool pk_pipelined(int kt, int nt, int /*gw*/) { return nt == 1024 && kt <= 20; }
 
+// What a wave counts about its uncertain lanes: the test variant's counters (bmm_dbg_pk_counts, bmm_dbg_pk_unselected,
+// bmm_dbg_pk_tier_counts) and the stamped build's ticks inside the two settle tiers.  In the product nothing writes or
+// reads any of it.
+struct PkTally {
+    unsigned deferred = 0, unselected = 0;                // valid lanes handed to pk_settle's rare block; of them not selected
+    unsigned mid_tried = 0, mid_settled = 0, exact = 0;   // runs of pk_mid_count, of them certain; runs of pk_exact_count
+    DIAG(unsigned long long t_mid = 0, t_exact = 0;)      // ticks inside the runs of either
+    DIAG(unsigned n_mid = 0, n_exact = 0;)
+};
+
 // What follows the packed draw of a chunk, the same in both bodies: the lanes the packed tier cannot prove, the DP's
 // books, the movers.  pos, zo, u and the words b0..b3 are those of the chunk that was drawn.  Returns the label to store.
 template <int KT, int GW>
 __device__ __forceinline__ int pk_settle(const ResampleArgs& a, char* smem, const PkPos& pos, int lane, bool certain,
                                          int cnt, double u, int zo, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3,
-                                         int dp_K, int K, unsigned& ndeferred, unsigned& nunselected) {
+                                         int dp_K, int K, PkTally& tally) {
     constexpr int GM = 1 << GW;
     const int zoc = zo < 0 ? 0 : zo;
     DBG_TIER1_FORCE(a, certain);
@@ -1886,16 +2019,17 @@ __device__ __forceinline__ int pk_settle(const ResampleArgs& a, char* smem, cons
 #ifdef BMM_DEBUG_HOOKS
     const bool selected = a.pk_defer_every > 0 && pos.valid &&
                           (a.lo + (int64_t)pos.s0 + lane) % a.pk_defer_every == 0;
-    nunselected += (unsigned)__popcll(__ballot(defer && !selected));
+    tally.unselected += (unsigned)__popcll(__ballot(defer && !selected));
     defer = defer || selected;
 #endif
     int zn = cnt;
-    // ---- the lanes the packed tier cannot prove (uniform, rare): the definition, one lane at a time, its
-    // count into that lane.  (A certain lane has a finite maximum: the "every category impossible" case is
-    // always settled here.)  Arguments, layout and the lane number are taken here, not ahead of the loop.
+    // ---- the lanes the packed tier cannot prove (uniform, rare), one lane at a time: the middle tier on the LDS
+    // image first (pk_mid_count), the definition where that is not certain either, the count into that lane.  (A
+    // certain lane of either tier has a finite maximum: the "every category impossible" case is always settled by the
+    // definition.)  Arguments, layout and the lane number are taken here, not ahead of the loop.
     unsigned long long o = __ballot(defer);
 #ifdef BMM_DEBUG_HOOKS
-    ndeferred += (unsigned)__popcll(o);
+    tally.deferred += (unsigned)__popcll(o);
 #endif
     if (__builtin_expect(o != 0, 0)) {
         const PkArgsView v = pk_args_view();
@@ -1903,15 +2037,43 @@ __device__ __forceinline__ int pk_settle(const ResampleArgs& a, char* smem, cons
         const PkLds lc = pk_lds(smem, Lc);
         int ln = lane;
         asm volatile("" : "+v"(ln));
+        // above the scoring waves' priority while it settles: this wave is the one its workgroup's barrier waits for
+        __builtin_amdgcn_s_setprio(3);
         do {
             const int src = __ffsll((long long)o) - 1;
             o &= o - 1;
             const uint32_t w0 = __builtin_amdgcn_readlane(b0, src), w1 = __builtin_amdgcn_readlane(b1, src);
             const uint32_t w2 = __builtin_amdgcn_readlane(b2, src), w3 = __builtin_amdgcn_readlane(b3, src);
-            const int e = pk_exact_count<KT, GW>(*v.p, *v.a, Lc, w0, w1, w2, w3, __builtin_amdgcn_readlane(zo, src),
-                                                        pk_bcast(u, src), lc.ET, ln);
+            const int zs = __builtin_amdgcn_readlane(zo, src);
+            const double us = pk_bcast(u, src);
+            bool settled = false;
+            int e = 0;
+            bool try_mid = true;
+#ifdef BMM_DEBUG_HOOKS
+            if (v.a->dbg_inject & 32) try_mid = false;  // BMM_DEBUG_PK_NOMID
+#endif
+            if (try_mid) {
+                DIAG(const unsigned long long d_m0 = diag_stamp();)
+                e = pk_mid_count<KT, GW>(Lc, v.p->G, smem, w0, w1, w2, w3, zs, us, lc.ET, ln, settled);
+                DIAG(tally.t_mid += diag_stamp() - d_m0; ++tally.n_mid;)
+#ifdef BMM_DEBUG_HOOKS
+                // BMM_DEBUG_PK_MID_FAIL_EVERY: the middle tier's verdict dropped for every n-th observation
+                if (v.a->pk_mid_fail_every > 0 && (v.a->lo + (int64_t)pos.s0 + src) % v.a->pk_mid_fail_every == 0) settled = false;
+                ++tally.mid_tried;
+                tally.mid_settled += settled ? 1u : 0u;
+#endif
+            }
+            if (!settled) {
+                DIAG(const unsigned long long d_e0 = diag_stamp();)
+                e = pk_exact_count<KT, GW>(*v.p, *v.a, Lc, w0, w1, w2, w3, zs, us, lc.ET, ln);
+                DIAG(tally.t_exact += diag_stamp() - d_e0; ++tally.n_exact;)
+#ifdef BMM_DEBUG_HOOKS
+                ++tally.exact;
+#endif
+            }
             if (ln == src) zn = e;
         } while (o);
+        __builtin_amdgcn_s_setprio(0);
     }
     if (__builtin_expect(__ballot(zn == dp_K) != 0, 0)) {  // the DP's new cluster was drawn (rare): its books, from the staged sizes
         const PkArgsView v = pk_args_view();
@@ -2009,7 +2171,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
 #endif
     // valid lanes this wave has settled by the definition: counted and reported by the test variant only
     // (bmm_dbg_pk_counts); in the product nothing writes or reads them, nor the K that pk_settle hands to its label check
-    unsigned ndeferred = 0, nunselected = 0;
+    PkTally tally;
 
     // What the loop's steady state -- a chunk without an uncertain lane and without a mover -- holds in scalar
     // registers is named here: three base pointers, the plane stride, the launch's length and this workgroup's chunks,
@@ -2110,8 +2272,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
             const double u = pk_uniform(seed, i0, pos.s0, pos.loff, sweep, kg == 0);
             int cnt = 0;
             const bool certain = pk_draw2<KT>(s2, m, u, G, unit, cnt);
-            const int zn = pk_settle<KT, GW>(a, smem, pos, lane, certain, cnt, u, zo, b0, b1, b2, b3, dp_K, K, ndeferred,
-                                             nunselected);
+            const int zn = pk_settle<KT, GW>(a, smem, pos, lane, certain, cnt, u, zo, b0, b1, b2, b3, dp_K, K, tally);
             const bool keep = pos.valid;
             zn_prev = zn;
             st_s0 = pos.s0; st_loff = pos.loff; st_on = keep;
@@ -2176,8 +2337,7 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
             }
             int cnt = 0;
             const bool certain = pk_draw2<KT>(s2, m, u, G, unit, cnt);
-            const int zn = pk_settle<KT, GW>(a, smem, pos, lane, certain, cnt, u, zo, b0, b1, b2, b3, dp_K, K, ndeferred,
-                                             nunselected);
+            const int zn = pk_settle<KT, GW>(a, smem, pos, lane, certain, cnt, u, zo, b0, b1, b2, b3, dp_K, K, tally);
             zn_prev = zn;
             st_s0 = pos.s0; st_loff = pos.loff; st_on = pos.valid;
             if (!has_next) break;
@@ -2209,6 +2369,9 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
         atomicAdd(&a.diag[8], d_staged - d_entry); atomicAdd(&a.diag[9], d_loop - d_staged);
         atomicAdd(&a.diag[10], d_sync - d_loop); atomicAdd(&a.diag[11], d_flush - d_sync);
         atomicAdd(&a.diag[16], d_score); atomicAdd(&a.diag[17], d_trips);  // wave 0's trips: the lookups, and how many
+        // wave 0's settled lanes: ticks inside the middle tier and inside the definition, and the runs of either
+        if (tally.n_mid) { atomicAdd(&a.diag[18], tally.t_mid); atomicAdd(&a.diag[19], (unsigned long long)tally.n_mid); }
+        if (tally.n_exact) { atomicAdd(&a.diag[20], tally.t_exact); atomicAdd(&a.diag[21], (unsigned long long)tally.n_exact); }
     })
 #ifdef BMM_DEBUG_HOOKS
     if (a.pk_stat) {  // test variant: draws made and valid lanes settled by the definition (bmm_dbg_pk_counts)
@@ -2217,8 +2380,12 @@ __global__ __launch_bounds__(NT) void k_resample_pk(ChainParams p, ResampleArgs 
             last = last < a.hi ? last : a.hi;
             if (last > first) atomicAdd(&a.pk_stat[0], (unsigned long long)(last - first));
         }
-        if (lane == 0 && ndeferred) atomicAdd(&a.pk_stat[1], (unsigned long long)ndeferred);
-        if (lane == 0 && nunselected) atomicAdd(&a.pk_stat[2], (unsigned long long)nunselected);
+        if (lane == 0 && tally.deferred) atomicAdd(&a.pk_stat[1], (unsigned long long)tally.deferred);
+        if (lane == 0 && tally.unselected) atomicAdd(&a.pk_stat[2], (unsigned long long)tally.unselected);
+        // the settle tiers (bmm_dbg_pk_tier_counts): runs of the middle tier, of them certain, runs of the definition
+        if (lane == 0 && tally.mid_tried) atomicAdd(&a.pk_stat[3], (unsigned long long)tally.mid_tried);
+        if (lane == 0 && tally.mid_settled) atomicAdd(&a.pk_stat[4], (unsigned long long)tally.mid_settled);
+        if (lane == 0 && tally.exact) atomicAdd(&a.pk_stat[5], (unsigned long long)tally.exact);
     }
 #endif
 }
