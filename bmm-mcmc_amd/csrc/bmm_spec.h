@@ -616,13 +616,20 @@ BMM_HD double rnorm_(Stream& st) {
     }
 }
 
-// Gamma(shape, scale 1), Marsaglia & Tsang (2000); shape < 1 by the u^(1/shape) boost.
-BMM_HD double rgamma_(double shape, Stream& st) {
-    if (!(shape > 0.0)) return 0.0;  // R::rgamma(0, .) is 0
-    double boost = 1.0;
+// Gamma(shape, scale 1), Marsaglia & Tsang (2000); shape < 1 by the u^(1/shape) boost.  The boost flushes to 0 once
+// log(u) / shape < -708 (exp_), so a small shape returns exactly 0 where the variate is below the binary64 range, as
+// R's rgamma does (about half the draws at shape 1e-3, one in 2000 at 1e-2).  LOGGED = true is the same draw from the
+// same Philox blocks that returns, in place of such a 0, the variate's logarithm log(d v) + log(u) / shape: below
+// -690 wherever the product flushed, -inf for a shape that is not positive, so any value <= 0 is a logarithm and any
+// value > 0 the variate itself, with the bits rgamma_ gives it (rbeta_join_ below reads the two apart).
+template <bool LOGGED>
+BMM_HD double rgamma_draw_(double shape, Stream& st) {
+    if (!(shape > 0.0)) return LOGGED ? neg_inf() : 0.0;  // R::rgamma(0, .) is 0
+    double boost = 1.0, lboost = 0.0;
     if (shape < 1.0) {
         const U4 r = st.next();
-        boost = exp_(div_(log_(u01_open0(r.x, r.y)), shape));
+        lboost = div_(log_(u01_open0(r.x, r.y)), shape);
+        boost = exp_(lboost);
         shape = shape + 1.0;
     }
     const double d = shape - 0.33333333333333331483;
@@ -635,14 +642,34 @@ BMM_HD double rgamma_(double shape, Stream& st) {
         const U4 r = st.next();
         const double u = u01_open0(r.x, r.y);
         const double x2 = x * x;
-        if (log_(u) < 0.5 * x2 + d - d * v + d * log_(v)) return d * v * boost;
+        if (log_(u) < 0.5 * x2 + d - d * v + d * log_(v)) {
+            const double g = d * v * boost;
+            if (LOGGED && !(g > 0.0)) return log_(d * v) + lboost;
+            return g;
+        }
     }
 }
+BMM_HD double rgamma_(double shape, Stream& st) { return rgamma_draw_<false>(shape, st); }
 
-// Beta(p, q) = X / (X + Y), X ~ Gamma(p), Y ~ Gamma(q), two separate streams.
+// Beta(p, q) = X / (X + Y) from two logged gamma draws (rgamma_draw_<true>; the halves may come from different
+// threads).  Where neither gamma flushed to 0 this is the plain quotient.  Where one did -- p or q below 0.052 -- the
+// quotient would be 0/0 (both), or exactly 0 or 1 although the flushed variate may be the larger part of the sum (one:
+// a boost just below e^-708 against one just above it); the same two variates are then compared through their
+// logarithms lx, ly (log_ of a variate that did not flush): X / (X + Y) = 1 / (1 + exp(ly - lx)), the same random
+// variable continued below the binary64 range, so the law stays Beta(p, q).  Nearly all of its mass is then beyond
+// e^-37 of 0 or 1 and the result rounds to what the quotient gave.  Two logarithms of -inf (p and q below 2.5e-307,
+// where log(u) / p overflows) leave nothing to compare: 1/2.  Never NaN, always in [0, 1], for every p, q > 0.
+BMM_HD double rbeta_join_(double xs, double ys) {
+    if (xs > 0.0 && ys > 0.0) return div_(xs, xs + ys);
+    const double lx = xs > 0.0 ? log_(xs) : xs, ly = ys > 0.0 ? log_(ys) : ys;
+    const double t = ly - lx;
+    if (t != t) return 0.5;
+    return div_(1.0, 1.0 + exp_(t));
+}
+// X ~ Gamma(p), Y ~ Gamma(q) on two separate streams.
 BMM_HD double rbeta_(double p, double q, Stream& sa, Stream& sb) {
-    const double x = rgamma_(p, sa), y = rgamma_(q, sb);
-    return div_(x, x + y);
+    const double xs = rgamma_draw_<true>(p, sa), ys = rgamma_draw_<true>(q, sb);
+    return rbeta_join_(xs, ys);
 }
 
 // The auxiliary rate of label k and feature j in the imputation step of a counting chain behind sweep `sweep`

@@ -8495,4 +8495,32 @@ int bmm_device_variates(int device, int kind, double p, double q, uint64_t seed,
     return BMM_OK;
 }
 
+int bmm_device_variates_ex(int device, int kind, const double* p, const double* q, double a, double b, double N,
+                           uint64_t seed, uint32_t sweep, double* out, int64_t n) {
+    if (!out || !p || n < 0 || n > (int64_t)1 << 30 || kind < 0 || kind > 4 || (kind != 0 && !q))
+        return set_err(BMM_E_ARG, "bad argument");
+    if (n == 0) return BMM_OK;
+    HIP_TRY(hipSetDevice(device));
+    DevBuf bp, bq, bo;
+    HIP_TRY(bp.alloc(n * sizeof(double)));
+    HIP_TRY(bo.alloc(n * sizeof(double)));
+    HIP_TRY(hipMemcpy(bp.p, p, n * sizeof(double), hipMemcpyHostToDevice));
+    if (q) {
+        HIP_TRY(bq.alloc(n * sizeof(double)));
+        HIP_TRY(hipMemcpy(bq.p, q, n * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (kind <= 2)
+        hipLaunchKernelGGL(k_test_variates_ex, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, kind, bp.as<double>(),
+                           bq.as<double>(), a, b, N, seed, sweep, bo.as<double>(), n);
+    else if (kind == 3)
+        hipLaunchKernelGGL(k_test_alpha_wave, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, 0, bp.as<double>(),
+                           bq.as<double>(), a, b, N, seed, sweep, bo.as<double>(), n);
+    else
+        hipLaunchKernelGGL(k_test_split_beta, dim3((unsigned)((n + 127) / 128)), dim3(256), 0, 0, bp.as<double>(),
+                           bq.as<double>(), seed, sweep, bo.as<double>(), n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, bo.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    return BMM_OK;
+}
+
 }  // extern "C"

@@ -129,7 +129,9 @@ __device__ __forceinline__ double update_alpha_wave(double alpha_old, double a, 
         g = rgamma_(shape, st);
     }
     const double x = __shfl(g, 0), y = __shfl(g, 1), g1 = __shfl(g, 2), g2 = __shfl(g, 3);
-    const double eta = div_(x, x + y);  // rbeta_
+    // rbeta_'s quotient.  Its fallback for two gammas that both flushed to 0 cannot be reached here: the shapes are
+    // alpha_old + 1 >= 1 and N >= 1, and a gamma of shape >= 1 has no boost to underflow.
+    const double eta = div_(x, x + y);
     const double b_eps = b - log_(eta);
     const double pi1 = a + (double)K - 1.0;
     const double pi2 = N * b_eps;
@@ -462,6 +464,14 @@ __global__ __launch_bounds__(256) void k_cat_check(const uint32_t* __restrict__ 
     }
 }
 
+// One half of a Beta draw split over two threads, as k_sb_theta_tables draws theta: half 0 draws X ~ Gamma(shape) on
+// stream kStreamThetaA of counter word c0, half 1 draws Y on kStreamThetaB.  The draws are logged (rgamma_draw_<true>,
+// bmm_spec.h), so that rbeta_join_ of the two halves is rbeta_ bit for bit, its underflow fallback included.
+__device__ __forceinline__ double sb_theta_half(uint64_t seed, uint32_t c0, uint32_t sweep, int half, double shape) {
+    Stream st = make_stream(seed, c0, sweep, half ? kStreamThetaB : kStreamThetaA);
+    return rgamma_draw_<true>(shape, st);
+}
+
 // Stick-breaking: theta_kd ~ Beta(beta + V_kd, gamma + c_k - V_kd) (stickbreaking.cpp:217-229),
 // unless draw == 0 (initial theta is used as given), then the tables of cluster k.
 __global__ __launch_bounds__(256) void k_sb_theta_tables(ChainParams p, const int32_t* __restrict__ Nk,
@@ -509,15 +519,14 @@ __global__ __launch_bounds__(256) void k_sb_theta_tables(ChainParams p, const in
         if (draw && is_label && dl < pc) {
             const int32_t ck = Nk[k], V = S[(size_t)k * P + d];
             const uint32_t c0s = (uint32_t)((size_t)k * P + d);
-            Stream st = make_stream(p.seed, c0s, sweep, half ? kStreamThetaB : kStreamThetaA);
-            gam[half][dl] = rgamma_(half ? (p.gamma + (double)ck) - (double)V : p.beta + (double)V, st);
+            gam[half][dl] = sb_theta_half(p.seed, c0s, sweep, half,
+                                          half ? (p.gamma + (double)ck) - (double)V : p.beta + (double)V);
         }
         __syncthreads();
         if (dl < pc) {
             double t = 0.0;
             if (is_label) {
-                const double x = gam[0][dl];
-                const double th = draw ? div_(x, x + gam[1][dl]) : theta[k + (size_t)d * K];  // rbeta_
+                const double th = draw ? rbeta_join_(gam[0][dl], gam[1][dl]) : theta[k + (size_t)d * K];  // rbeta_
                 if (half == 0) {
                     if (draw) theta[k + (size_t)d * K] = th;
                     if (theta_trace) theta_trace[k + (size_t)d * K] = th;
@@ -3831,6 +3840,48 @@ __global__ void k_test_variates(int kind, double pp, double qq, uint64_t seed, u
         y = update_alpha_(pp, 1.0, 1.0, 1000.0, (int)qq, seed + (uint64_t)i, sweep);
     }
     out[i] = y;
+}
+// The same with parameters per element (bmm_device_variates_ex): kind 0 gamma(p[i]), 1 beta(p[i], q[i]), 2
+// update_alpha_ from alpha_old = p[i] with K = (int)q[i] under (a, b, N); stream index and seed offset i as above.
+__global__ void k_test_variates_ex(int kind, const double* __restrict__ p, const double* __restrict__ q, double a,
+                                   double b, double N, uint64_t seed, uint32_t sweep, double* __restrict__ out,
+                                   int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double y;
+    if (kind == 0) {
+        Stream s = make_stream(seed, (uint32_t)i, sweep, kStreamThetaA);
+        y = rgamma_(p[i], s);
+    } else if (kind == 1) {
+        Stream sa = make_stream(seed, (uint32_t)i, sweep, kStreamThetaA);
+        Stream sb = make_stream(seed, (uint32_t)i, sweep, kStreamThetaB);
+        y = rbeta_(p[i], q[i], sa, sb);
+    } else {
+        y = update_alpha_(p[i], a, b, N, (int)q[i], seed + (uint64_t)i, sweep);
+    }
+    out[i] = y;
+}
+// Kind 3: update_alpha_wave as the kernels call it, one whole wave per element, lane 0's value.  256 threads.
+__global__ __launch_bounds__(256) void k_test_alpha_wave(const double* __restrict__ p, const double* __restrict__ q,
+                                                         double a, double b, double N, uint64_t seed, uint32_t sweep,
+                                                         double* __restrict__ out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // uniform over the wave
+    if (i >= n) return;
+    const int lane = threadIdx.x & 63;
+    const double y = update_alpha_wave(p[i], a, b, N, (int)q[i], seed + (uint64_t)i, sweep, lane);
+    if (lane == 0) out[i] = y;
+}
+// Kind 4: Beta(p[i], q[i]) split over two threads exactly as k_sb_theta_tables draws theta: thread dl of the first
+// 128 draws X, thread 128 + dl draws Y (sb_theta_half), LDS and a barrier between them and the quotient.  256 threads.
+__global__ __launch_bounds__(256) void k_test_split_beta(const double* __restrict__ p, const double* __restrict__ q,
+                                                         uint64_t seed, uint32_t sweep, double* __restrict__ out,
+                                                         int64_t n) {
+    __shared__ double gam[2][128];
+    const int half = threadIdx.x >> 7, dl = threadIdx.x & 127;
+    const int64_t i = (int64_t)blockIdx.x * 128 + dl;
+    if (i < n) gam[half][dl] = sb_theta_half(seed, (uint32_t)i, sweep, half, half ? q[i] : p[i]);
+    __syncthreads();
+    if (i < n && half == 0) out[i] = rbeta_join_(gam[0][dl], gam[1][dl]);
 }
 
 // ---- partition summaries over a label trace (include/bmm_mcmc.h "clustering point estimate")

@@ -126,7 +126,18 @@ int bmm_host_threads(void);
  * come back with the next call. */
 int bmm_release_pools(void);
 
-/* ---- drop-in entry points --------------------------------------------------------
+/* ---- beta, gamma: the Beta(beta, gamma) prior of every theta_kd ------------------------------
+ * Any beta, gamma > 0 is accepted.  Every Beta variate the samplers draw (theta, the sticks, the imputation step's
+ * phi, the eject move's p_E, the eta of the concentration's update) is X / (X + Y) of two gamma variates and is a
+ * number in [0, 1] for every pair of positive shapes, never NaN.  A gamma variate of shape below 0.052 can lie below
+ * the binary64 range and is then exactly 0, as R's rgamma returns it; a Beta draw one of whose gammas did so is
+ * decided from the logarithms of the same two variates, 1 / (1 + exp(log Y - log X)), which continues the same
+ * random variable and keeps the law Beta(p, q) (csrc/bmm_spec.h, rbeta_join_; DESIGN.md "Variates").  With small
+ * beta and gamma most of a Beta(beta + s, gamma + n - s) draw's mass of an empty or one-sided cell rounds to
+ * exactly 0 or 1: such theta cells appear in the trace from beta = gamma of about 0.05 down, and their table entries
+ * are -inf (a category whose weight is exactly 0 for a row that contradicts the cell).
+ *
+ * ---- drop-in entry points --------------------------------------------------------
  * Replaces collapsed_gibbs_cpp (src/collapsed_gibbs.cpp:24-36; .Call symbol
  * _bmmmcmc_collapsed_gibbs_cpp, src/RcppExports.cpp:11-31) with relabel = FALSE. */
 int bmm_collapsed_run(const int32_t* X, int64_t N, int P, const int32_t* initialK, int nsamples,
@@ -1705,6 +1716,17 @@ int bmm_device_math(int device, int op, const double* in, const double* in2, dou
  * with alpha_old p, K = (int)q, N = 1000, a = b = 1) for stream index i, on the GPU */
 int bmm_device_variates(int device, int kind, double p, double q, uint64_t seed, uint32_t sweep,
                         double* out, int64_t n);
+/* The same with parameters per element: out[i] from p[i], q[i] and the scalars a, b, N, for stream index i
+ * (kinds 0 and 1: streams 3 and 4 of counter word i; kinds 2 and 3: seed + i).
+ *   0  gamma(shape p[i])                                   (q may be NULL)
+ *   1  beta(p[i], q[i]), the spec's rbeta_
+ *   2  update_alpha_ from alpha_old = p[i] with K = (int)q[i], under (a, b, N)
+ *   3  the same through update_alpha_wave, the form the kernels run: one wave per element, lane 0's value
+ *   4  beta(p[i], q[i]) with X and Y drawn by two threads 128 apart and joined through LDS, by the device functions
+ *      k_sb_theta_tables draws theta with
+ * Kinds 3 and 4 equal kinds 2 and 1 bit for bit. */
+int bmm_device_variates_ex(int device, int kind, const double* p, const double* q, double a, double b, double N,
+                           uint64_t seed, uint32_t sweep, double* out, int64_t n);
 int bmm_device_count(int* n);
 
 #ifdef __cplusplus

@@ -211,14 +211,20 @@ static double o_rnorm(ostream* s) {
         if (q < 1.0 && q > 0.0) return v1 * sqrt((-2.0 * oracle_log(q)) / q);
     }
 }
-/* Marsaglia-Tsang gamma, scale 1 */
-static double o_rgamma(double shape, ostream* s) {
-    if (!(shape > 0.0)) return 0.0;
-    double boost = 1.0;
+/* Marsaglia-Tsang gamma, scale 1.  For a shape below 1 the boost u^(1/shape) flushes to 0 once log(u)/shape < -708,
+ * so the variate is exactly 0 where it lies below the binary64 range, as R's rgamma is.  *lg (when asked for)
+ * receives the variate's logarithm, log(d v) + log(u)/shape, which such a 0 still has; -inf for shape <= 0. */
+static double o_rgamma_lg(double shape, ostream* s, double* lg) {
+    if (!(shape > 0.0)) {
+        if (lg) *lg = -O_POS_INF;
+        return 0.0;
+    }
+    double boost = 1.0, lboost = 0.0;
     if (shape < 1.0) {
         uint32_t o[4];
         st_next(s, o);
-        boost = oracle_exp(oracle_log(1.0 - oracle_u01(o[0], o[1])) / shape);
+        lboost = oracle_log(1.0 - oracle_u01(o[0], o[1])) / shape;
+        boost = oracle_exp(lboost);
         shape = shape + 1.0;
     }
     double d = shape - 0.33333333333333331483, c = 1.0 / sqrt(9.0 * d);
@@ -230,18 +236,32 @@ static double o_rgamma(double shape, ostream* s) {
         st_next(s, o);
         double u = 1.0 - oracle_u01(o[0], o[1]);
         double x2 = x * x;
-        if (oracle_log(u) < 0.5 * x2 + d - d * v + d * oracle_log(v)) return d * v * boost;
+        if (oracle_log(u) < 0.5 * x2 + d - d * v + d * oracle_log(v)) {
+            if (lg) *lg = oracle_log(d * v) + lboost;
+            return d * v * boost;
+        }
     }
 }
+static double o_rgamma(double shape, ostream* s) { return o_rgamma_lg(shape, s, 0); }
 double oracle_rgamma(double shape, uint64_t seed, uint32_t c0, uint32_t sweep, uint32_t stream) {
     ostream s = mk_stream(seed, c0, sweep, stream);
     return o_rgamma(shape, &s);
 }
+/* X / (X + Y).  When a gamma flushed to 0 the quotient would be 0/0 (both), or 0 or 1 whatever the flushed one's
+ * share of the sum (one): the same two variates are then compared through their logarithms (oracle_log of one that
+ * did not flush), 1 / (1 + exp(ly - lx)) -- the same random variable, so the law is still Beta(p, q); two
+ * logarithms of -inf (p, q below 2.5e-307) give 1/2.  In [0, 1] and never NaN for p, q > 0. */
 double oracle_rbeta(double p, double q, uint64_t seed, uint32_t c0a, uint32_t c0b, uint32_t sweep,
                     uint32_t stream_a, uint32_t stream_b) {
     ostream sa = mk_stream(seed, c0a, sweep, stream_a), sb = mk_stream(seed, c0b, sweep, stream_b);
-    double x = o_rgamma(p, &sa), y = o_rgamma(q, &sb);
-    return x / (x + y);
+    double lx, ly;
+    double x = o_rgamma_lg(p, &sa, &lx), y = o_rgamma_lg(q, &sb, &ly);
+    if (x > 0.0 && y > 0.0) return x / (x + y);
+    if (x > 0.0) lx = oracle_log(x);
+    if (y > 0.0) ly = oracle_log(y);
+    double t = ly - lx;
+    if (t != t) return 0.5;
+    return 1.0 / (1.0 + oracle_exp(t));
 }
 /* utils.cpp:6-14 (Escobar & West), with the build's variate generators */
 double oracle_update_alpha(double alpha_old, double a, double b, double N, int K, uint64_t seed,
@@ -254,6 +274,21 @@ double oracle_update_alpha(double alpha_old, double a, double b, double N, int K
     double ga = oracle_rgamma(a + (double)K, seed, 0, sweep, 6) * scale;
     double gb = oracle_rgamma(a + (double)K - 1.0, seed, 0, sweep, 7) * scale;
     return pi * ga + (1.0 - pi) * gb;
+}
+
+/* array forms for the tests: element i is the scalar call at stream index / seed offset i */
+void oracle_rgamma_array(const double* shape, uint64_t seed, uint32_t sweep, uint32_t stream, double* out, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) out[i] = oracle_rgamma(shape[i], seed, (uint32_t)i, sweep, stream);
+}
+void oracle_rbeta_array(const double* p, const double* q, uint64_t seed, uint32_t sweep, uint32_t stream_a,
+                        uint32_t stream_b, double* out, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        out[i] = oracle_rbeta(p[i], q[i], seed, (uint32_t)i, (uint32_t)i, sweep, stream_a, stream_b);
+}
+void oracle_update_alpha_array(const double* alpha_old, const double* K, double a, double b, double N, uint64_t seed,
+                               uint32_t sweep, double* out, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        out[i] = oracle_update_alpha(alpha_old[i], a, b, N, (int)K[i], seed + (uint64_t)i, sweep);
 }
 
 /* Inverse-CDF draw shared by every sampler: weights w[0..n), one uniform u <= 1 - 2^-52.
@@ -829,6 +864,7 @@ thetas:
         for (int d = 0; d < P; ++d) { /* stickbreaking.cpp:217-229, full_gibbs.cpp:213-226 */
             int32_t V = Vkd[(size_t)k * P + d];
             uint32_t c0 = (uint32_t)((size_t)k * P + d);
+            /* oracle_rbeta: in [0, 1] and never NaN, also where both gammas flush to 0 (small beta, gamma) */
             theta[k + (size_t)d * maxK] =
                 oracle_rbeta(beta + (double)V, (gamma + (double)ck[k]) - (double)V, seed, c0, c0, j, 3, 4);
         }

@@ -55,6 +55,13 @@ double oracle_rbeta(double p, double q, uint64_t seed, uint32_t c0a, uint32_t c0
                     uint32_t stream_a, uint32_t stream_b);
 double oracle_update_alpha(double alpha_old, double a, double b, double N, int K, uint64_t seed,
                            uint32_t sweep);
+/* array forms: element i is the scalar call at stream index c0 = i (gamma, beta) or seed + i (update_alpha, K[i]
+ * truncated to int) */
+void oracle_rgamma_array(const double* shape, uint64_t seed, uint32_t sweep, uint32_t stream, double* out, int64_t n);
+void oracle_rbeta_array(const double* p, const double* q, uint64_t seed, uint32_t sweep, uint32_t stream_a,
+                        uint32_t stream_b, double* out, int64_t n);
+void oracle_update_alpha_array(const double* alpha_old, const double* K, double a, double b, double N, uint64_t seed,
+                               uint32_t sweep, double* out, int64_t n);
 void oracle_log_array(const double* x, double* y, int64_t n);
 void oracle_exp_array(const double* x, double* y, int64_t n);
 int oracle_group_width(void);

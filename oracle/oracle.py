@@ -133,6 +133,42 @@ def update_alpha(alpha_old, a, b, N, K, seed, sweep):
     return lib().oracle_update_alpha(alpha_old, a, b, float(N), K, seed, sweep)
 
 
+def _f64(x, n=None):
+    x = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (n,) if n is not None else np.shape(x)))
+    return x.reshape(-1)
+
+
+def rgamma_array(shape, seed, sweep, stream=3):
+    """out[i] = rgamma(shape[i], seed, i, sweep, stream)"""
+    s = _f64(shape)
+    out = np.empty_like(s)
+    lib().oracle_rgamma_array(s.ctypes.data_as(C.c_void_p), C.c_uint64(seed), C.c_uint32(sweep), C.c_uint32(stream),
+                              out.ctypes.data_as(C.c_void_p), C.c_int64(s.size))
+    return out
+
+
+def rbeta_array(p, q, seed, sweep, stream_a=3, stream_b=4):
+    """out[i] = rbeta(p[i], q[i], seed, i, i, sweep, stream_a, stream_b)"""
+    p = _f64(p)
+    q = _f64(q, p.size)
+    out = np.empty_like(p)
+    lib().oracle_rbeta_array(p.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p), C.c_uint64(seed),
+                             C.c_uint32(sweep), C.c_uint32(stream_a), C.c_uint32(stream_b),
+                             out.ctypes.data_as(C.c_void_p), C.c_int64(p.size))
+    return out
+
+
+def update_alpha_array(alpha_old, K, a, b, N, seed, sweep):
+    """out[i] = update_alpha(alpha_old[i], a, b, N, int(K[i]), seed + i, sweep)"""
+    al = _f64(alpha_old)
+    K = _f64(K, al.size)
+    out = np.empty_like(al)
+    lib().oracle_update_alpha_array(al.ctypes.data_as(C.c_void_p), K.ctypes.data_as(C.c_void_p), C.c_double(a),
+                                    C.c_double(b), C.c_double(float(N)), C.c_uint64(seed), C.c_uint32(sweep),
+                                    out.ctypes.data_as(C.c_void_p), C.c_int64(al.size))
+    return out
+
+
 # ---------------------------------------------------------------- conditionals
 def _cond(fn, X, z, i, K, alpha, beta, gamma, ncat):
     X = _x(X)

@@ -153,18 +153,30 @@ def test_full_chain_samples_the_dirichlet_multinomial_posterior(oracle, data):
 
 def test_update_alpha_leaves_the_escobar_west_posterior_invariant(oracle):
     """utils.cpp:6-14 with this build's variate generators: 1e5 successive draws of alpha for fixed K and N against
-    p(alpha | K, N) by quadrature"""
-    a, b, Nn, K = 1.0, 1.0, 500.0, 6
-    grid = np.linspace(1e-4, 30.0, 300_001)
-    logp = (a - 1) * np.log(grid) - b * grid + K * np.log(grid) + gammaln(grid) - gammaln(grid + Nn)
-    p = np.exp(logp - logp.max())
-    p /= p.sum()
-    mean, var = float((p * grid).sum()), float((p * grid ** 2).sum() - (p * grid).sum() ** 2)
-    alpha, draws = 1.0, []
-    for j in range(1, 100_001):
-        alpha = oracle.update_alpha(alpha, a, b, Nn, K, 77, j)
-        draws.append(alpha)
-    draws = np.array(draws[1000:])
-    assert abs(draws.mean() - mean) < 0.02 * mean and abs(draws.var() - var) < 0.06 * var, (draws.mean(), mean, draws.var(), var)
-    q_exact = np.interp([0.1, 0.5, 0.9], np.cumsum(p), grid)
-    assert np.abs(np.quantile(draws, [0.1, 0.5, 0.9]) - q_exact).max() < 0.03 * q_exact[2]
+    p(alpha | K, N) by quadrature.  Three (a, b, N, K): the reference's defaults; a + K - 1 < 1, where the mixture's
+    second gamma has a shape below 1 (the boosted draw) and the density is unbounded at 0; an informative prior with
+    more clusters.  The quadrature runs over log alpha (the density times alpha, trapezoid rule), so that the pole at 0
+    is an integrable power of the variable.
+
+    Every point has N (b - log eta) far above a + K - 1, and has to: utils.cpp:12 returns pi G1 + (1 - pi) G2, the
+    weighted sum of the two gamma variates, where Escobar & West's update takes G1 with probability pi and G2
+    otherwise.  The sum has the mixture's mean and less than its variance, so the posterior is invariant only as pi
+    goes to 0 (at a = 2, b = 0.5, N = 50, K = 12, where pi is about 0.1, the chain's variance is 2.00 against the
+    posterior's 2.32).  The product reproduces the reference's update as it stands."""
+    for a, b, Nn, K in ((1.0, 1.0, 500.0, 6), (0.3, 1.0, 200.0, 1), (2.0, 0.5, 5000.0, 12)):
+        t = np.linspace(np.log(1e-40), np.log(200.0), 400_001)
+        grid = np.exp(t)
+        logp = (a - 1) * t - b * grid + K * t + gammaln(grid) - gammaln(grid + Nn) + t
+        p = np.exp(logp - logp.max())
+        p /= p.sum()
+        mean, var = float((p * grid).sum()), float((p * grid ** 2).sum() - (p * grid).sum() ** 2)
+        alpha, draws = 1.0, []
+        for j in range(1, 100_001):
+            alpha = oracle.update_alpha(alpha, a, b, Nn, K, 77, j)
+            draws.append(alpha)
+        draws = np.array(draws[1000:])
+        assert np.isfinite(draws).all() and (draws > 0).all()
+        assert abs(draws.mean() - mean) < 0.02 * mean and abs(draws.var() - var) < 0.06 * var, \
+            (a, b, Nn, K, draws.mean(), mean, draws.var(), var)
+        q_exact = np.interp([0.1, 0.5, 0.9], np.cumsum(p), grid)
+        assert np.abs(np.quantile(draws, [0.1, 0.5, 0.9]) - q_exact).max() < 0.03 * q_exact[2], (a, b, Nn, K)
