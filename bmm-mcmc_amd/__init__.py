@@ -25,7 +25,7 @@ __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "
            "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
            "partition_distances", "posterior_similarity", "partition_plan", "partition_search", "partition_search_plan", "credible_ball", "credible_ball_plan", "run_options", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
            "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat", "pair_check", "pair_check_plan", "pair_check_pairs", "PAIR_CHECK_MAX_M", "run_bytes", "summary_plan", "Ladder", "temper_ladder", "TEMPER_MAX_RUNGS",
-           "categorical", "Categorical", "categorical_plan"]
+           "categorical", "Categorical", "categorical_plan", "gibbs_ensemble", "ensemble_plan"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -3313,3 +3313,82 @@ def chain_summary(obj, cluster_threshold=0.1):
     for k in clusters:
         shown[k - 1] = th[k - 1]
     return {"proportions": props, "clusters": clusters, "theta": shown}
+
+
+# ---------------------------------------------------------------- an ensemble of exact chains
+_ENSEMBLE_SAMPLERS = ("collapsed", "dp")
+
+
+def ensemble_plan(sampler, N, P, K, chains=64):
+    """What bmm_ensemble_plan reports of an ensemble of `chains` exact chains of that shape (K: K, or maxK for "dp"),
+    without touching a device: {"group_width", "lds_bytes_per_chain", "chains_per_workgroup", "workgroups",
+    "launches_per_sweep", "state_bytes", "bytes_per_kept_sweep", "label_bytes_per_kept_sweep"}.  A shape that does not
+    fit -- more than 64 categories, P > 128, N >= 65536, terms beyond the LDS of a workgroup -- raises BmmError
+    (BMM_E_UNSUPPORTED)."""
+    if sampler not in _capi.SAMPLER_CODE:
+        raise ValueError("unknown sampler %r" % (sampler,))
+    out = _np.zeros(8, dtype=_np.int64)
+    _capi.check(_capi.lib().bmm_ensemble_plan(_C.c_int(_capi.SAMPLER_CODE[sampler]), _C.c_int64(N), _C.c_int(P), _C.c_int(K),
+                                              _C.c_int(chains), _capi.vp(out)))
+    keys = ("group_width", "lds_bytes_per_chain", "chains_per_workgroup", "workgroups", "launches_per_sweep", "state_bytes",
+            "bytes_per_kept_sweep", "label_bytes_per_kept_sweep")
+    return {k: int(v) for k, v in zip(keys, out)}
+
+
+def _ensemble_run(*args):
+    return _capi.lib().bmm_ensemble_run(*args)
+
+
+def gibbs_ensemble(data, nsamples, K, sampler="collapsed", chains=64, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
+                   seed=None, initial_K=None, keep_trace=True, device=0):
+    """`chains` independent exact chains -- batch = 1, the reference's sequential scan -- of gibbs_collapsed
+    (sampler="collapsed") or gibbs_dp (sampler="dp"; K is maxK) over one data set, one wavefront per chain, all of them
+    advanced by one kernel launch per sweep.  For small data (N < 65536, P <= 128, at most 64 categories: ensemble_plan),
+    where a single batch = 1 chain costs two launches per observation.  Chain c draws under seed + c and starts as
+    chains= starts it: from numpy.random.default_rng(seed + c).integers(1, K + 1, N) unless `initial_K` lists one start
+    per chain ("collapsed" only), so it is, bit for bit, the chain gibbs_collapsed(..., batch=1, seed=seed + c) runs.
+    Returns a list of dicts {"alpha" (S, 1), "permutations", "z" (S, N) or None with keep_trace=False, "theta" (K, P, S),
+    "sizes" (S, K), "z_last" (N,)}.  No run option is offered; the traces go to the stand-alone tools (rhat, ess,
+    partition_distances, ecr_relabel)."""
+    if sampler not in _ENSEMBLE_SAMPLERS:
+        raise ValueError('gibbs_ensemble: sampler must be "collapsed" or "dp"')
+    if _categorical_of(data) is not None:
+        raise ValueError("gibbs_ensemble: categorical features are not offered")
+    X = _capi.as_x(data)
+    N, P = X.shape
+    nsamples, K, chains = int(nsamples), int(K), int(chains)
+    if chains < 1:
+        raise ValueError("gibbs_ensemble: chains must be >= 1")
+    dp = sampler == "dp"
+    if dp and beta != gamma:
+        raise ValueError("gibbs_ensemble: the DP sampler needs beta == gamma")
+    if dp and initial_K is not None:
+        raise ValueError("gibbs_ensemble: a DP chain seats its rows in its first sweep: no initial_K")
+    burnin = _burnin(burnin, nsamples)
+    seed = _seed(seed)
+    ensemble_plan(sampler, N, P, K, chains)  # the limits, by name
+    z0s = None
+    if not dp:
+        if initial_K is None:
+            z0s = [_np.ascontiguousarray(_np.random.default_rng(seed + c).integers(1, K + 1, N), dtype=_np.int32) for c in range(chains)]
+        else:
+            z0s = [_np.ascontiguousarray(z, dtype=_np.int32) for z in initial_K]
+            if len(z0s) != chains:
+                raise ValueError("gibbs_ensemble: initial_K must list one start per chain (%d given, %d chains)" % (len(z0s), chains))
+            if any(z.shape != (N,) for z in z0s):
+                raise ValueError("gibbs_ensemble: every start in initial_K must have one label per observation")
+    S = nsamples - burnin
+    zs = [_np.empty((S, N), dtype=_np.int32, order="F") for _ in range(chains)] if keep_trace else None
+    nks = [_np.zeros((S, K), dtype=_np.int32) for _ in range(chains)]
+    ths = [_np.zeros((K, P, S), order="F") for _ in range(chains)]
+    als = [_np.zeros((S, 1), order="F") for _ in range(chains)]
+    zl = [_np.zeros(N, dtype=_np.int32) for _ in range(chains)]
+    rc = _ensemble_run(
+        _C.c_int(_capi.SAMPLER_CODE[sampler]), _capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(chains),
+        _ptr_table(z0s) if z0s is not None else None, _C.c_int(nsamples), _C.c_int(K),
+        _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma), _C.c_double(a), _C.c_double(b),
+        _C.c_int(burnin), _C.c_uint64(seed), _C.c_int(device), _ptr_table(zs) if keep_trace else None, _ptr_table(nks),
+        _ptr_table(ths), _ptr_table(als), _ptr_table(zl))
+    _capi.check(rc)
+    return [{"alpha": als[c], "permutations": _na_perm(S, K), "z": zs[c] if keep_trace else None, "theta": ths[c],
+             "sizes": nks[c], "z_last": zl[c]} for c in range(chains)]

@@ -60,6 +60,7 @@ SYMBOLS = [
     "bmm_set_summary", "bmm_run_bytes", "bmm_summary_plan", "bmm_chain_set_summary", "bmm_chain_summary_state",
     "bmm_chain_sweeps_summary", "bmm_chain_get_summary", "bmm_chain_summary_reset",
     "bmm_chain_set_categorical", "bmm_chain_get_categorical", "bmm_set_categorical", "bmm_categorical_plan",
+    "bmm_ensemble_plan", "bmm_ensemble_run",
 ]
 
 
@@ -132,6 +133,11 @@ def load(path):
         L.bmm_set_categorical.argtypes = [C.c_void_p, C.c_int]
         L.bmm_categorical_plan.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
+    if hasattr(L, "bmm_ensemble_run"):  # (an older build loaded for a comparison has no ensemble)
+        L.bmm_ensemble_plan.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.bmm_ensemble_run.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "bmm_ladder_create"):  # (an older build loaded for a comparison has no ladder)
         L.bmm_ladder_destroy.restype = None
         L.bmm_ladder_destroy.argtypes = [C.c_void_p]

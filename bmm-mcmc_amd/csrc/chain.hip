@@ -42,6 +42,7 @@
 
 #include "../../include/bmm_mcmc.h"
 #include "kernels.hip.h"
+#include "ensemble.hip.h"
 #include "host_crew.h"
 
 using namespace bmm;
@@ -8521,6 +8522,183 @@ int bmm_device_variates_ex(int device, int kind, const double* p, const double* 
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, bo.p, n * sizeof(double), hipMemcpyDeviceToHost));
     return BMM_OK;
+}
+
+}  // extern "C"
+
+// ---- an ensemble of exact chains (include/bmm_mcmc.h "ensemble of exact chains") ----
+namespace {
+
+// What follows from (sampler, N, P, K, chains) alone: the shape of the launches and the bytes, or the refusal.
+struct EnsPlan {
+    int W = 0, Kc = 0, cpw = 0, groups = 0, launches = 0;
+    int64_t slice = 0, state_bytes = 0, row_bytes = 0, label_row_bytes = 0;
+};
+int ens_plan(int sampler, int64_t N, int P, int K, int chains, EnsPlan& o) {
+    if (sampler != BMM_SAMPLER_COLLAPSED && sampler != BMM_SAMPLER_DP)
+        return set_err(BMM_E_UNSUPPORTED, "an ensemble runs the collapsed and DP samplers only: the explicit samplers' z-step is exact already");
+    if (chains < 1) return set_err(BMM_E_ARG, "chains must be >= 1");
+    if (N < 1) return set_err(BMM_E_ARG, "N must be >= 1");
+    if (P < 1) return set_err(BMM_E_ARG, "P must be >= 1");
+    if (K < 1) return set_err(BMM_E_ARG, "K must be >= 1");
+    const bool dp = sampler == BMM_SAMPLER_DP;
+    if (dp && K < 2) return set_err(BMM_E_ARG, "maxK must be >= 2");
+    o.Kc = dp ? K + 1 : K;
+    if (o.Kc > kEnsMaxCats)
+        return set_err(BMM_E_UNSUPPORTED, "an ensemble chain scores its categories on the lanes of one wave: %d categories exceed %d", o.Kc, kEnsMaxCats);
+    if (P > kEnsMaxP) return set_err(BMM_E_UNSUPPORTED, "an ensemble chain takes at most %d features: P = %d", kEnsMaxP, P);
+    if (N >= kEnsMaxN)
+        return set_err(BMM_E_UNSUPPORTED, "an ensemble chain takes fewer than %d observations: N = %lld", kEnsMaxN, (long long)N);
+    o.slice = ens_slice_bytes(P, K, o.Kc);
+    if ((size_t)o.slice > kLdsMax)
+        return set_err(BMM_E_UNSUPPORTED, "the terms of one ensemble chain (%lld bytes at K = %d, P = %d) do not fit in the %zu bytes of LDS of a workgroup",
+                       (long long)o.slice, K, P, kLdsMax);
+    o.W = group_width_rule(sampler, K, P);
+    const int fit = (int)(kLdsMax / (size_t)o.slice);
+    o.cpw = fit < kEnsWaves ? fit : kEnsWaves;
+    o.groups = (chains + o.cpw - 1) / o.cpw;
+    o.launches = (int)((N + ens_rows(P) - 1) / ens_rows(P));
+    o.state_bytes = (int64_t)chains * (N * 4 + (int64_t)K * 4 + (int64_t)K * P * 4 + 8);
+    o.row_bytes = (int64_t)chains * ((int64_t)K * 4 + (int64_t)K * P * 8 + 8);
+    o.label_row_bytes = (int64_t)chains * N * 4;
+    return BMM_OK;
+}
+bool ens_options_armed(const RunOptions& o) {
+    return o.partition.on || o.psearch.on || o.cball.on || o.loo.on || o.sm.moves > 0 || o.fs.on || o.init.kind != 0 || o.ecr.on ||
+           o.logpost.on || o.temper.on || o.pc.on || o.na.on || o.alloc.on || o.as.moves > 0 || o.cs.on || o.summary.on || o.cat.on ||
+           o.hooks || o.rel || o.pred || o.pna.on;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bmm_ensemble_plan(int sampler, int64_t N, int P, int K, int chains, int64_t out[8]) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    EnsPlan pl;
+    const int rc = ens_plan(sampler, N, P, K, chains, pl);
+    if (rc) return rc;
+    out[0] = pl.W; out[1] = pl.slice; out[2] = pl.cpw; out[3] = pl.groups; out[4] = pl.launches;
+    out[5] = pl.state_bytes; out[6] = pl.row_bytes; out[7] = pl.label_row_bytes;
+    return BMM_OK;
+}
+
+int bmm_ensemble_run(int sampler, const int32_t* X, int64_t N, int P, int chains, const int32_t* const* z0, int nsamples, int K,
+                     double alpha, double beta, double gamma, double a, double b, int burnin, uint64_t seed, int device,
+                     int32_t* const* z_out, int32_t* const* nk_out, double* const* theta_out, double* const* alpha_out,
+                     int32_t* const* z_last) {
+    const RunOptions opts = take_run_options();
+    return guarded([&]() -> int {
+        // refused before any device is touched
+        if (ens_options_armed(opts)) return set_err(BMM_E_UNSUPPORTED, "an ensemble runs plain chains: no run option is offered (the traces feed the stand-alone tools)");
+        EnsPlan pl;
+        int rc = ens_plan(sampler, N, P, K, chains, pl);
+        if (rc) return rc;
+        const bool dp = sampler == BMM_SAMPLER_DP;
+        if (!(beta > 0.0) || !(gamma > 0.0)) return set_err(BMM_E_ARG, "beta and gamma must be > 0");
+        if (dp && beta != gamma)  // collapsed_gibbs_dp.cpp:48-50
+            return set_err(BMM_E_ARG, "Error: sampler currently not implemented for non-symmetric priors on beta and gamma");
+        if (alpha < 0.0) return set_err(BMM_E_ARG, "alpha must be >= 0 (0 = sample it)");
+        if (nsamples < 1) return set_err(BMM_E_ARG, "nsamples must be >= 1");
+        if (burnin < 0 || burnin >= nsamples) return set_err(BMM_E_ARG, "burnin must be in [0, nsamples)");
+        if (!X || !nk_out || !theta_out || !alpha_out || !z_last || (!dp && !z0)) return set_err(BMM_E_ARG, "null buffer");
+        for (int c = 0; c < chains; ++c)
+            if (!nk_out[c] || !theta_out[c] || !alpha_out[c] || !z_last[c] || (z_out && !z_out[c]) || (!dp && !z0[c]))
+                return set_err(BMM_E_ARG, "null buffer (chain %d)", c);
+        if (dbg_env("BMM_X_LAYOUT_INT32") != nullptr)
+            return set_err(BMM_E_UNSUPPORTED, "an ensemble reads the bit planes: not offered on the int32 layout");
+        const int S = nsamples - burnin;
+        const size_t KP = (size_t)K * P, n = (size_t)N;
+        // the starting state of every chain, on the host: labels (0-based, -1 unassigned) and their counts
+        std::vector<int32_t> hz((size_t)chains * n, -1), hnk((size_t)chains * K, 0), hs((size_t)chains * KP, 0);
+        if (!dp) {
+            for (int c = 0; c < chains; ++c) {
+                int32_t* const nk = hnk.data() + (size_t)c * K;
+                int32_t* const s = hs.data() + (size_t)c * KP;
+                for (size_t i = 0; i < n; ++i) {
+                    const int32_t k = z0[c][i] - 1;
+                    if (k < 0 || k >= K) return set_err(BMM_E_ARG, "initialK out of range: chain %d, observation %zu", c, i);
+                    hz[(size_t)c * n + i] = k;
+                    nk[k]++;
+                    for (int d = 0; d < P; ++d) s[(size_t)k * P + d] += X[i + (size_t)d * n] & 1;
+                }
+            }
+        }
+        const double alpha0 = alpha == 0.0 ? 1.0 : alpha;
+        // the data: validated and packed once, by the chain object every run uses, and shared by all chains
+        bmm_chain* h = nullptr;
+        rc = bmm_chain_create(&h, sampler, N, P, K, alpha, beta, gamma, a, b, 1, seed, device);
+        if (rc) return rc;
+        struct Guard { bmm_chain* c; ~Guard() { bmm_chain_destroy(c); } } guard{h};
+        if (!h->bits) return set_err(BMM_E_UNSUPPORTED, "an ensemble reads the bit planes: not offered on the int32 layout");
+        rc = bmm_chain_set_data_host(h, X);
+        if (rc) return rc;
+        const bool keep = z_out != nullptr;
+        const size_t zt = keep ? (size_t)chains * n * S : 0;
+        const size_t need = (size_t)pl.state_bytes + (size_t)pl.row_bytes * S + zt * 4;
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        if (need > free_b)
+            return set_err(BMM_E_ARG, "ensemble: the state and the traces of %d chains need %zu bytes of device memory, %zu are free%s", chains,
+                           need, free_b, keep ? " (the label trace is optional)" : "");
+        DevBuf dz, dnk, ds, dal, dzt, dnkt, dtht, dalt;
+        HIP_TRY(dz.alloc(hz.size() * 4));
+        HIP_TRY(dnk.alloc(hnk.size() * 4));
+        HIP_TRY(ds.alloc(hs.size() * 4));
+        HIP_TRY(dal.alloc((size_t)chains * 8));
+        if (keep) HIP_TRY(dzt.alloc(zt * 4));
+        HIP_TRY(dnkt.alloc((size_t)chains * S * K * 4));
+        HIP_TRY(dtht.alloc((size_t)chains * S * KP * 8));
+        HIP_TRY(dalt.alloc((size_t)chains * S * 8));
+        const std::vector<double> hal((size_t)chains, alpha0);
+        hipStream_t st = h->stream;
+        HIP_TRY(hipMemcpyAsync(dz.p, hz.data(), hz.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dnk.p, hnk.data(), hnk.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ds.p, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(dal.p, hal.data(), hal.size() * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));  // the host vectors are pageable
+        EnsArgs g{};
+        g.Xb = h->dXb; g.N = (int)N; g.P = P; g.K = K; g.Kc = pl.Kc; g.W = pl.W;
+        g.chains = chains; g.cpw = pl.cpw; g.slice_bytes = (int)pl.slice;
+        g.beta = beta; g.gamma = gamma; g.a = a; g.b = b; g.sample_alpha = alpha == 0.0; g.seed = seed;
+        g.z = dz.as<int32_t>(); g.Nk = dnk.as<int32_t>(); g.S = ds.as<int32_t>(); g.alpha = dal.as<double>();
+        g.rows = S; g.z_tr = keep ? dzt.as<int32_t>() : nullptr; g.nk_tr = dnkt.as<int32_t>();
+        g.th_tr = dtht.as<double>(); g.al_tr = dalt.as<double>();
+        void (*fn)(EnsArgs) = dp ? k_ens_sweep<true> : k_ens_sweep<false>;
+        const size_t lds = (size_t)pl.slice * pl.cpw;
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        for (int j = 1; j < nsamples; ++j) {
+            g.sweep = (uint32_t)j;
+            g.row = j >= burnin ? j - burnin : -1;
+            for (int lo = 0; lo < (int)N; lo += ens_rows(P)) {
+                g.lo = lo;
+                g.hi = lo + ens_rows(P) < (int)N ? lo + ens_rows(P) : (int)N;
+                hipLaunchKernelGGL(fn, dim3((unsigned)pl.groups), dim3((unsigned)pl.cpw * 64), lds, st, g);
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+        // the traces: each chain's block is laid out as its caller's matrix is
+        for (int c = 0; c < chains; ++c) {
+            if (keep) HIP_TRY(hipMemcpy(z_out[c], dzt.as<int32_t>() + (size_t)c * n * S, n * S * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(nk_out[c], dnkt.as<int32_t>() + (size_t)c * S * K, (size_t)S * K * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(theta_out[c], dtht.as<double>() + (size_t)c * S * KP, (size_t)S * KP * 8, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(alpha_out[c], dalt.as<double>() + (size_t)c * S, (size_t)S * 8, hipMemcpyDeviceToHost));
+            if (burnin == 0) {  // row 0 is the start, as in run_counts_chain: z0 or NA, theta NaN or 0, the first alpha
+                if (keep) for (size_t i = 0; i < n; ++i) z_out[c][i * S] = dp ? (int32_t)0x80000000 : z0[c][i];
+                for (size_t q = 0; q < KP; ++q) theta_out[c][q] = dp ? 0.0 : std::nan("");
+                alpha_out[c][0] = alpha0;
+                std::memcpy(nk_out[c], hnk.data() + (size_t)c * K, (size_t)K * 4);
+            }
+        }
+        HIP_TRY(hipMemcpy(hz.data(), dz.p, hz.size() * 4, hipMemcpyDeviceToHost));
+        for (int c = 0; c < chains; ++c)
+            for (size_t i = 0; i < n; ++i) {
+                const int32_t v = hz[(size_t)c * n + i];
+                z_last[c][i] = v < 0 ? (int32_t)0x80000000 : v + 1;
+            }
+        return BMM_OK;
+    });
 }
 
 }  // extern "C"

@@ -1708,6 +1708,31 @@ typedef struct bmm_categorical_plan_out {
 int bmm_categorical_plan(int sampler, int64_t N, int K, int64_t batch, int num_cus, const int32_t* levels, int F,
                          int32_t* first_column, uint8_t* lev, bmm_categorical_plan_out* out);
 
+/* ---- ensemble of exact chains.  `chains` independent batch = 1 chains of the collapsed
+ * (BMM_SAMPLER_COLLAPSED) or the DP sampler (BMM_SAMPLER_DP; K is maxK) over one data set, one wavefront per chain, every
+ * chain advanced by one launch per sweep (k_ens_sweep; a sweep over more than 2048 / ceil(P / 8) rows, rounded down to a multiple of 64, is several launches).  Chain c
+ * draws under seed + c and is, bit for bit, the chain bmm_collapsed_run / bmm_dp_run run at batch = 1 under that seed: the
+ * arithmetic is bmm_spec.h's in the same order.  alpha = 0: sampled (a, b), as everywhere.
+ *   z0         collapsed: one start per chain, N labels in 1..K each; dp: NULL (the rows are seated in sweep 1)
+ *   z_out      per chain an S x N column-major label trace, S = nsamples - burnin; or NULL: no label trace at all
+ *   nk_out     per chain S x K cluster sizes, row s at nk_out[c] + s * K
+ *   theta_out  per chain K x P x S;  alpha_out per chain S;  z_last per chain the N labels after the last sweep
+ * Row 0 of a run without burn-in is the start, as in the single-chain runs: z0 (dp: NA_integer_), theta NaN (dp: 0), the
+ * first alpha, the sizes of the start.
+ * Limits, refused with BMM_E_UNSUPPORTED before a device is touched: at most 64 categories (K, or maxK + 1), P <= 128,
+ * N < 65536, the terms of one chain within the 160 KiB of LDS of a workgroup ((4 P Kc + 256) * 8 + 4 K P bytes), a sampler
+ * other than the two, any armed run option (bmm_set_*: an ensemble runs plain chains), the int32 layout of the test
+ * variant.  BMM_E_ARG: chains < 1, beta != gamma for the DP, a start label outside 1..K, a null buffer.
+ * bmm_ensemble_plan is pure bookkeeping, no device: out = {group width of the scores (bmm_spec_group_width_for), LDS
+ * bytes per chain, chains per workgroup, workgroups per launch, launches per sweep, device bytes of the chains' state,
+ * device bytes per kept sweep without the label trace, device bytes per kept sweep of the label trace}; the same
+ * refusals of a shape. */
+int bmm_ensemble_plan(int sampler, int64_t N, int P, int K, int chains, int64_t out[8]);
+int bmm_ensemble_run(int sampler, const int32_t* X, int64_t N, int P, int chains, const int32_t* const* z0, int nsamples, int K,
+                     double alpha, double beta, double gamma, double a, double b, int burnin, uint64_t seed, int device,
+                     int32_t* const* z_out, int32_t* const* nk_out, double* const* theta_out, double* const* alpha_out,
+                     int32_t* const* z_last);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
