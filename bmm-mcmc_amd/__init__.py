@@ -25,7 +25,7 @@ __all__ = ["gibbs_collapsed", "gibbs_dp", "gibbs_stickbreaking", "gibbs_full", "
            "stephens_batch", "stephens_online", "stephens_plan", "DeviceStephens", "STEPHENS_MAX_K",
            "partition_distances", "posterior_similarity", "partition_plan", "partition_search", "partition_search_plan", "credible_ball", "credible_ball_plan", "run_options", "PARTITION_MAX_K", "gibbs_allocation", "log_prior_k",
            "ecr_relabel", "ecr_plan", "ECR_MAX_K", "log_joint", "ess", "rhat", "pair_check", "pair_check_plan", "pair_check_pairs", "PAIR_CHECK_MAX_M", "run_bytes", "summary_plan", "Ladder", "temper_ladder", "TEMPER_MAX_RUNGS",
-           "categorical", "Categorical", "categorical_plan", "gibbs_ensemble", "ensemble_plan"]
+           "categorical", "Categorical", "categorical_plan", "gibbs_ensemble", "ensemble_plan", "ensemble_fold_plan", "ensemble_pool"]
 
 # include/bmm_mcmc.h: the stated tolerance of a batch > 1 against the reference's sequential scan
 TOL_PROPORTIONS = 0.015
@@ -3339,8 +3339,84 @@ def _ensemble_run(*args):
     return _capi.lib().bmm_ensemble_run(*args)
 
 
+class _EnsembleFolds(_C.Structure):  # bmm_ensemble_folds
+    _fields_ = [("newdata", _C.c_void_p), ("M", _C.c_int64), ("loo", _C.c_int32), ("loo_trace", _C.c_int32),
+                ("predictive_trace", _C.c_int32), ("pred_lppd", _C.c_void_p), ("pred_logdens", _C.c_void_p),
+                ("loo_log_cpo", _C.c_void_p), ("loo_ess", _C.c_void_p), ("loo_lppd", _C.c_void_p), ("loo_mean", _C.c_void_p),
+                ("loo_var", _C.c_void_p), ("loo_ell", _C.c_void_p), ("loo_lpml", _C.c_void_p), ("loo_min_ess", _C.c_void_p),
+                ("n_folded", _C.c_void_p)]
+
+
+def ensemble_fold_plan(sampler, N, P, K, chains=64, M=0, loo=False):
+    """What bmm_ensemble_fold_plan reports of the folds of an ensemble, without touching a device:
+    {"lds_bytes_per_chain", "chains_per_workgroup", "accumulator_bytes", "ell_bytes_per_kept_sweep",
+    "logdens_bytes_per_kept_sweep", "launches_per_kept_sweep"}; M: the new rows (0: no newdata=).  The shapes ensemble_plan
+    refuses are refused here."""
+    if sampler not in _capi.SAMPLER_CODE:
+        raise ValueError("unknown sampler %r" % (sampler,))
+    out = _np.zeros(6, dtype=_np.int64)
+    _capi.check(_capi.lib().bmm_ensemble_fold_plan(_C.c_int(_capi.SAMPLER_CODE[sampler]), _C.c_int64(N), _C.c_int(P), _C.c_int(K),
+                                                   _C.c_int(chains), _C.c_int64(M), _C.c_int(1 if loo else 0), _capi.vp(out)))
+    keys = ("lds_bytes_per_chain", "chains_per_workgroup", "accumulator_bytes", "ell_bytes_per_kept_sweep",
+            "logdens_bytes_per_kept_sweep", "launches_per_kept_sweep")
+    return {k: int(v) for k, v in zip(keys, out)}
+
+
+def _ensemble_run_ex(*args):
+    return _capi.lib().bmm_ensemble_run_ex(*args)
+
+
+def _logsumexp(v):
+    v = _np.asarray(v, dtype=_np.float64)
+    m = _np.max(v, axis=0)
+    m = _np.where(_np.isfinite(m), m, 0.0)
+    with _np.errstate(divide="ignore"):
+        return m + _np.log(_np.sum(_np.exp(v - m), axis=0))
+
+
+def ensemble_pool(outs):
+    """The leave-one-out and predictive summaries of the chains of gibbs_ensemble(..., loo=..., newdata=...) pooled over
+    chains, on the host, from the per-chain results alone.  With n_c = chain c's n_folded:
+      loo         A_c = log n_c - log_cpo_c; log_cpo = log(sum n_c) - logsumexp_c A_c; B_c = 2 A_c - log ess_c;
+                  ess = exp(2 logsumexp_c A_c - logsumexp_c B_c); lppd = logsumexp_c(log n_c + lppd_c) - log(sum n_c):
+                  what one summary over the concatenated states would give.  {"log_cpo", "ess", "lppd", "lpml" (sum of
+                  log_cpo), "min_ess", "n_folded", "lpml_chains" (per chain), "lpml_sd" (their standard deviation, ddof = 1)}
+      predictive  {"lppd" (pooled as above), "n_folded", "lppd_chains" (chain c's lppd summed over the new rows)}
+    Returns a dict with the key of every summary all chains carry."""
+    outs = list(outs)
+    if not outs:
+        raise ValueError("ensemble_pool: no chain")
+    res = {}
+    if all("loo" in o for o in outs):
+        n = _np.array([float(o["loo"]["n_folded"]) for o in outs])
+        if _np.any(n < 1):
+            raise ValueError("ensemble_pool: a chain has folded no state")
+        ln = _np.log(n)[:, None]
+        lt = _np.log(n.sum())
+        A = ln - _np.stack([_np.asarray(o["loo"]["log_cpo"], dtype=_np.float64) for o in outs])
+        lA = _logsumexp(A)
+        B = 2.0 * A - _np.log(_np.stack([_np.asarray(o["loo"]["ess"], dtype=_np.float64) for o in outs]))
+        lp = _logsumexp(ln + _np.stack([_np.asarray(o["loo"]["lppd"], dtype=_np.float64) for o in outs])) - lt
+        log_cpo = lt - lA
+        ess = _np.exp(2.0 * lA - _logsumexp(B))
+        lc = _np.array([float(o["loo"]["lpml"]) for o in outs])
+        res["loo"] = {"log_cpo": log_cpo, "ess": ess, "lppd": lp, "lpml": float(log_cpo.sum()), "min_ess": float(ess.min()),
+                      "n_folded": int(n.sum()), "lpml_chains": lc,
+                      "lpml_sd": float(_np.std(lc, ddof=1)) if lc.size > 1 else float("nan")}
+    if all("predictive" in o for o in outs):
+        n = _np.array([float(o["predictive"]["n_folded"]) for o in outs])
+        if _np.any(n < 1):
+            raise ValueError("ensemble_pool: a chain has folded no state")
+        L = _np.stack([_np.asarray(o["predictive"]["lppd"], dtype=_np.float64) for o in outs])
+        res["predictive"] = {"lppd": _logsumexp(_np.log(n)[:, None] + L) - _np.log(n.sum()), "n_folded": int(n.sum()),
+                             "lppd_chains": L.sum(axis=1)}
+    if not res:
+        raise ValueError("ensemble_pool: the chains carry neither \"loo\" nor \"predictive\"")
+    return res
+
+
 def gibbs_ensemble(data, nsamples, K, sampler="collapsed", chains=64, alpha=None, beta=0.5, gamma=0.5, a=1, b=1, burnin=None,
-                   seed=None, initial_K=None, keep_trace=True, device=0):
+                   seed=None, initial_K=None, keep_trace=True, device=0, newdata=None, predictive_trace=False, loo=False):
     """`chains` independent exact chains -- batch = 1, the reference's sequential scan -- of gibbs_collapsed
     (sampler="collapsed") or gibbs_dp (sampler="dp"; K is maxK) over one data set, one wavefront per chain, all of them
     advanced by one kernel launch per sweep.  For small data (N < 65536, P <= 128, at most 64 categories: ensemble_plan),
@@ -3348,8 +3424,13 @@ def gibbs_ensemble(data, nsamples, K, sampler="collapsed", chains=64, alpha=None
     chains= starts it: from numpy.random.default_rng(seed + c).integers(1, K + 1, N) unless `initial_K` lists one start
     per chain ("collapsed" only), so it is, bit for bit, the chain gibbs_collapsed(..., batch=1, seed=seed + c) runs.
     Returns a list of dicts {"alpha" (S, 1), "permutations", "z" (S, N) or None with keep_trace=False, "theta" (K, P, S),
-    "sizes" (S, K), "z_last" (N,)}.  No run option is offered; the traces go to the stand-alone tools (rhat, ess,
-    partition_distances, ecr_relabel)."""
+    "sizes" (S, K), "z_last" (N,)}.  The traces go to the stand-alone tools (rhat, ess, partition_distances, ecr_relabel).
+    Two of the run options are offered, scored on every chain by its own wavefront after each kept sweep (DESIGN.md section
+    32): `newdata` (M >= 1 complete rows; `predictive_trace=True` adds the (S, M) trace) gives chain c
+    "predictive" = {"lppd", ["logdens"], "n_folded"}, and `loo` (True or "trace") gives it "loo" = {"log_cpo", "ess", "lppd",
+    "mean", "var", "lpml", "min_ess", "n_folded", ["ell"]}: the keys, meanings and bits of gibbs_collapsed / gibbs_dp(...,
+    batch=1, seed=seed + c, newdata=..., loo=...).  Mean responsibilities are not offered (labels switch between chains);
+    ensemble_pool pools the summaries over chains."""
     if sampler not in _ENSEMBLE_SAMPLERS:
         raise ValueError('gibbs_ensemble: sampler must be "collapsed" or "dp"')
     if _categorical_of(data) is not None:
@@ -3366,6 +3447,18 @@ def gibbs_ensemble(data, nsamples, K, sampler="collapsed", chains=64, alpha=None
         raise ValueError("gibbs_ensemble: a DP chain seats its rows in its first sweep: no initial_K")
     burnin = _burnin(burnin, nsamples)
     seed = _seed(seed)
+    if loo is not True and loo is not False and loo is not None and not (isinstance(loo, str) and loo == "trace"):
+        raise ValueError('gibbs_ensemble: loo must be True, "trace" or False')
+    Xn = None
+    if newdata is not None:
+        Xn = _capi.as_x(newdata)
+        if Xn.ndim != 2 or Xn.shape[1] != P:
+            raise ValueError("gibbs_ensemble: newdata must have the %d columns of data" % P)
+        if Xn.shape[0] < 1:
+            raise ValueError("gibbs_ensemble: newdata has no rows")
+    elif predictive_trace:
+        raise ValueError("gibbs_ensemble: predictive_trace needs newdata")
+    folds = bool(loo) or Xn is not None
     ensemble_plan(sampler, N, P, K, chains)  # the limits, by name
     z0s = None
     if not dp:
@@ -3383,12 +3476,47 @@ def gibbs_ensemble(data, nsamples, K, sampler="collapsed", chains=64, alpha=None
     ths = [_np.zeros((K, P, S), order="F") for _ in range(chains)]
     als = [_np.zeros((S, 1), order="F") for _ in range(chains)]
     zl = [_np.zeros(N, dtype=_np.int32) for _ in range(chains)]
-    rc = _ensemble_run(
+    args = (
         _C.c_int(_capi.SAMPLER_CODE[sampler]), _capi.vp(X), _C.c_int64(N), _C.c_int(P), _C.c_int(chains),
         _ptr_table(z0s) if z0s is not None else None, _C.c_int(nsamples), _C.c_int(K),
         _C.c_double(0.0 if alpha is None else alpha), _C.c_double(beta), _C.c_double(gamma), _C.c_double(a), _C.c_double(b),
         _C.c_int(burnin), _C.c_uint64(seed), _C.c_int(device), _ptr_table(zs) if keep_trace else None, _ptr_table(nks),
         _ptr_table(ths), _ptr_table(als), _ptr_table(zl))
-    _capi.check(rc)
-    return [{"alpha": als[c], "permutations": _na_perm(S, K), "z": zs[c] if keep_trace else None, "theta": ths[c],
+    if not folds:
+        _capi.check(_ensemble_run(*args))
+    else:
+        each = lambda shape, order="C": [_np.full(shape, _np.nan, order=order) for _ in range(chains)]  # noqa: E731
+        M = 0 if Xn is None else Xn.shape[0]
+        pl = each(M) if M else None
+        pt = each((S, M), "F") if M and predictive_trace else None
+        lrows = {k: each(N) for k in ("log_cpo", "ess", "lppd", "mean", "var")} if loo else None
+        lt = each((S, N), "F") if loo == "trace" else None
+        lpml, mess = _np.full(chains, _np.nan), _np.full(chains, _np.nan)
+        nf = _C.c_int32(0)
+        tables = {}
+
+        def tab(key, arrays):
+            if arrays is None:
+                return None
+            tables[key] = _ptr_table(arrays)
+            return _C.cast(tables[key], _C.c_void_p)
+
+        fs = _EnsembleFolds(
+            Xn.ctypes.data if M else None, M, 1 if loo else 0, 1 if lt is not None else 0, 1 if pt is not None else 0,
+            tab("pl", pl), tab("pt", pt), *[tab(k, lrows[k] if loo else None) for k in ("log_cpo", "ess", "lppd", "mean", "var")],
+            tab("lt", lt), lpml.ctypes.data if loo else None, mess.ctypes.data if loo else None, _C.addressof(nf))
+        _capi.check(_ensemble_run_ex(*args, _C.byref(fs)))
+    outs = [{"alpha": als[c], "permutations": _na_perm(S, K), "z": zs[c] if keep_trace else None, "theta": ths[c],
              "sizes": nks[c], "z_last": zl[c]} for c in range(chains)]
+    if folds:
+        for c, o in enumerate(outs):
+            if M:
+                o["predictive"] = {"lppd": pl[c], "n_folded": int(nf.value)}
+                if pt is not None:
+                    o["predictive"]["logdens"] = pt[c]
+            if loo:
+                o["loo"] = {k: lrows[k][c] for k in ("log_cpo", "ess", "lppd", "mean", "var")}
+                o["loo"].update(lpml=float(lpml[c]), min_ess=float(mess[c]), n_folded=int(nf.value))
+                if lt is not None:
+                    o["loo"]["ell"] = lt[c]
+    return outs

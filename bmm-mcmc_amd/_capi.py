@@ -60,7 +60,7 @@ SYMBOLS = [
     "bmm_set_summary", "bmm_run_bytes", "bmm_summary_plan", "bmm_chain_set_summary", "bmm_chain_summary_state",
     "bmm_chain_sweeps_summary", "bmm_chain_get_summary", "bmm_chain_summary_reset",
     "bmm_chain_set_categorical", "bmm_chain_get_categorical", "bmm_set_categorical", "bmm_categorical_plan",
-    "bmm_ensemble_plan", "bmm_ensemble_run",
+    "bmm_ensemble_plan", "bmm_ensemble_run", "bmm_ensemble_fold_plan", "bmm_ensemble_run_ex",
 ]
 
 
@@ -138,6 +138,9 @@ def load(path):
         L.bmm_ensemble_run.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "bmm_ensemble_run_ex"):  # (an older build loaded for a comparison has no folds on ensemble chains)
+        L.bmm_ensemble_fold_plan.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p]
+        L.bmm_ensemble_run_ex.argtypes = L.bmm_ensemble_run.argtypes + [C.c_void_p]
     if hasattr(L, "bmm_ladder_create"):  # (an older build loaded for a comparison has no ladder)
         L.bmm_ladder_destroy.restype = None
         L.bmm_ladder_destroy.argtypes = [C.c_void_p]

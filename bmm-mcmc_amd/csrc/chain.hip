@@ -8569,6 +8569,102 @@ bool ens_options_armed(const RunOptions& o) {
            o.hooks || o.rel || o.pred || o.pna.on;
 }
 
+// The folds of an ensemble: what follows from the plan and (M, loo) alone
+struct EnsFoldPlan {
+    int64_t acc_bytes = 0, loo_row_bytes = 0, pred_row_bytes = 0;
+    int launches = 0;
+};
+EnsFoldPlan ens_fold_plan(int64_t N, int P, int chains, int64_t M, bool loo) {
+    EnsFoldPlan o;
+    if (loo) {
+        o.acc_bytes += (int64_t)chains * ((kLooAcc + kLooOut) * N + 8) * 8;
+        o.loo_row_bytes = (int64_t)chains * N * 8;
+        o.launches++;
+    }
+    if (M > 0) {
+        o.acc_bytes += (int64_t)chains * 3 * M * 8 + (int64_t)((P + 31) / 32) * M * 4;
+        o.pred_row_bytes = (int64_t)chains * M * 8;
+        o.launches++;
+    }
+    return o;
+}
+// the struct as handed over: the new rows binary, every table that is asked for in place; no device
+int ens_folds_check(const bmm_ensemble_folds& f, int chains, int P) {
+    if (f.M < 0) return set_err(BMM_E_ARG, "M must be >= 0");
+    auto table = [&](const void* const* t, const char* name) -> int {
+        if (!t) return set_err(BMM_E_ARG, "null buffer: %s", name);
+        for (int c = 0; c < chains; ++c)
+            if (!t[c]) return set_err(BMM_E_ARG, "null buffer: %s (chain %d)", name, c);
+        return BMM_OK;
+    };
+    int rc = BMM_OK;
+    if (f.M > 0) {
+        if (!f.newdata) return set_err(BMM_E_ARG, "Xnew is null");
+        const int64_t cells = f.M * (int64_t)P;
+        for (int64_t q = 0; q < cells; ++q)
+            if ((uint32_t)f.newdata[q] > 1u) return set_err(BMM_E_ARG, "newdata must be binary: Xnew holds a value other than 0 and 1");
+        rc = table(reinterpret_cast<const void* const*>(f.pred_lppd), "pred_lppd");
+        if (rc == BMM_OK && f.predictive_trace) rc = table(reinterpret_cast<const void* const*>(f.pred_logdens), "pred_logdens");
+        if (rc) return rc;
+    }
+    if (f.loo) {
+        const void* const* t[] = {reinterpret_cast<const void* const*>(f.loo_log_cpo), reinterpret_cast<const void* const*>(f.loo_ess),
+                                  reinterpret_cast<const void* const*>(f.loo_lppd), reinterpret_cast<const void* const*>(f.loo_mean),
+                                  reinterpret_cast<const void* const*>(f.loo_var)};
+        const char* const names[] = {"loo_log_cpo", "loo_ess", "loo_lppd", "loo_mean", "loo_var"};
+        for (int q = 0; q < 5 && rc == BMM_OK; ++q) rc = table(t[q], names[q]);
+        if (rc == BMM_OK && f.loo_trace) rc = table(reinterpret_cast<const void* const*>(f.loo_ell), "loo_ell");
+        if (rc == BMM_OK && (!f.loo_lpml || !f.loo_min_ess)) rc = set_err(BMM_E_ARG, "null buffer: loo_lpml, loo_min_ess");
+    }
+    return rc;
+}
+// a device trace [chains][S][width] into each chain's S x width column-major matrix; the rows before the first fold NaN
+int ens_trace_out(const double* dtrace, int chains, int64_t width, int S, int first, double* const* out) {
+    std::vector<double> hrow((size_t)S * (size_t)width);
+    for (int c = 0; c < chains; ++c) {
+        HIP_TRY(hipMemcpy(hrow.data(), dtrace + (size_t)c * hrow.size(), hrow.size() * 8, hipMemcpyDeviceToHost));
+        for (int s = 0; s < S; ++s)
+            for (int64_t m = 0; m < width; ++m)
+                out[c][(size_t)s + (size_t)m * (size_t)S] = s < first ? std::nan("") : hrow[(size_t)s * (size_t)width + (size_t)m];
+    }
+    return BMM_OK;
+}
+// the outputs of the folds after the run (the stream is idle): as loo_run_out and pred_run_collect fill them
+int ens_folds_out(const bmm_ensemble_folds& f, int chains, int64_t N, int64_t M, int S, int burnin, int folded, const double* dlout,
+                  const double* dltr, const double* dpout, const double* dptr) {
+    const double nan = std::nan("");
+    const int first = burnin > 0 ? 0 : 1;
+    const size_t n = (size_t)N, m = (size_t)M;
+    if (f.n_folded) *f.n_folded = folded;
+    if (f.loo) {
+        double* const* const rows[kLooOut] = {f.loo_log_cpo, f.loo_ess, f.loo_lppd, f.loo_mean, f.loo_var};
+        const size_t lout = n * kLooOut + 8;
+        std::vector<double> ho(folded > 0 ? lout : 0);
+        for (int c = 0; c < chains; ++c) {
+            if (folded > 0) HIP_TRY(hipMemcpy(ho.data(), dlout + (size_t)c * lout, lout * 8, hipMemcpyDeviceToHost));
+            for (int q = 0; q < kLooOut; ++q)
+                for (size_t i = 0; i < n; ++i) rows[q][c][i] = folded > 0 ? ho[(size_t)q * n + i] : nan;
+            f.loo_lpml[c] = folded > 0 ? ho[n * kLooOut] : nan;
+            f.loo_min_ess[c] = folded > 0 ? ho[n * kLooOut + 1] : nan;
+        }
+        if (f.loo_trace) {
+            const int rc = ens_trace_out(dltr, chains, N, S, folded > 0 ? first : S, f.loo_ell);
+            if (rc) return rc;
+        }
+    }
+    if (M > 0) {
+        for (int c = 0; c < chains; ++c) {
+            if (folded > 0) HIP_TRY(hipMemcpy(f.pred_lppd[c], dpout + (size_t)c * m, m * 8, hipMemcpyDeviceToHost));
+            else for (size_t q = 0; q < m; ++q) f.pred_lppd[c][q] = nan;
+        }
+        if (f.predictive_trace) {
+            const int rc = ens_trace_out(dptr, chains, M, S, folded > 0 ? first : S, f.pred_logdens);
+            if (rc) return rc;
+        }
+    }
+    return BMM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -8583,11 +8679,11 @@ int bmm_ensemble_plan(int sampler, int64_t N, int P, int K, int chains, int64_t 
     return BMM_OK;
 }
 
-int bmm_ensemble_run(int sampler, const int32_t* X, int64_t N, int P, int chains, const int32_t* const* z0, int nsamples, int K,
-                     double alpha, double beta, double gamma, double a, double b, int burnin, uint64_t seed, int device,
-                     int32_t* const* z_out, int32_t* const* nk_out, double* const* theta_out, double* const* alpha_out,
-                     int32_t* const* z_last) {
-    const RunOptions opts = take_run_options();
+// The run behind both entries; f: the folds asked for, or null (bmm_ensemble_run)
+static int ens_run(const RunOptions& opts, int sampler, const int32_t* X, int64_t N, int P, int chains, const int32_t* const* z0,
+                   int nsamples, int K, double alpha, double beta, double gamma, double a, double b, int burnin, uint64_t seed,
+                   int device, int32_t* const* z_out, int32_t* const* nk_out, double* const* theta_out, double* const* alpha_out,
+                   int32_t* const* z_last, const bmm_ensemble_folds* f) {
     return guarded([&]() -> int {
         // refused before any device is touched
         if (ens_options_armed(opts)) return set_err(BMM_E_UNSUPPORTED, "an ensemble runs plain chains: no run option is offered (the traces feed the stand-alone tools)");
@@ -8609,6 +8705,13 @@ int bmm_ensemble_run(int sampler, const int32_t* X, int64_t N, int P, int chains
             return set_err(BMM_E_UNSUPPORTED, "an ensemble reads the bit planes: not offered on the int32 layout");
         const int S = nsamples - burnin;
         const size_t KP = (size_t)K * P, n = (size_t)N;
+        // the folds: what is asked for, and its buffers, before a device is touched
+        const bool f_loo = f && f->loo != 0, f_pred = f && f->M > 0;
+        const int64_t M = f_pred ? f->M : 0;
+        if (f) {
+            rc = ens_folds_check(*f, chains, P);
+            if (rc) return rc;
+        }
         // the starting state of every chain, on the host: labels (0-based, -1 unassigned) and their counts
         std::vector<int32_t> hz((size_t)chains * n, -1), hnk((size_t)chains * K, 0), hs((size_t)chains * KP, 0);
         if (!dp) {
@@ -8633,9 +8736,15 @@ int bmm_ensemble_run(int sampler, const int32_t* X, int64_t N, int P, int chains
         if (!h->bits) return set_err(BMM_E_UNSUPPORTED, "an ensemble reads the bit planes: not offered on the int32 layout");
         rc = bmm_chain_set_data_host(h, X);
         if (rc) return rc;
+        if (f_pred) {  // the new rows: validated and packed as newdata= packs them (k_validate_binary, k_pack_bits)
+            rc = bmm_chain_set_newdata_host(h, f->newdata, M);
+            if (rc) return rc;
+        }
+        const EnsFoldPlan fp = ens_fold_plan(N, P, chains, M, f_loo);
         const bool keep = z_out != nullptr;
         const size_t zt = keep ? (size_t)chains * n * S : 0;
-        const size_t need = (size_t)pl.state_bytes + (size_t)pl.row_bytes * S + zt * 4;
+        const size_t need = (size_t)pl.state_bytes + (size_t)pl.row_bytes * S + zt * 4 + (size_t)fp.acc_bytes +
+                            (f_loo && f->loo_trace ? (size_t)fp.loo_row_bytes * S : 0) + (f_pred && f->predictive_trace ? (size_t)fp.pred_row_bytes * S : 0);
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         if (need > free_b)
@@ -8667,6 +8776,46 @@ int bmm_ensemble_run(int sampler, const int32_t* X, int64_t N, int P, int chains
         void (*fn)(EnsArgs) = dp ? k_ens_sweep<true> : k_ens_sweep<false>;
         const size_t lds = (size_t)pl.slice * pl.cpw;
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        // the folds: per chain the accumulators ([kLooAcc][N]; [2][M]), the outputs of the finish kernels, the traces
+        DevBuf dlacc, dlout, dltr, dpacc, dpout, dptr;
+        EnsFoldArgs gl{}, gp{};
+        void (*lfn)(EnsFoldArgs) = dp ? k_ens_score<true, true> : k_ens_score<false, true>;
+        void (*pfn)(EnsFoldArgs) = dp ? k_ens_score<true, false> : k_ens_score<false, false>;
+        const size_t lout = n * kLooOut + 8;  // doubles per chain: k_loo_finish's rows, then k_loo_reduce's scalars
+        if (f_loo || f_pred) {
+            EnsFoldArgs base{};
+            base.N = (int)N; base.P = P; base.K = K; base.Kc = pl.Kc; base.W = pl.W;
+            base.chains = chains; base.cpw = pl.cpw; base.slice_bytes = (int)pl.slice;
+            base.beta = beta; base.gamma = gamma;
+            base.z = dz.as<int32_t>(); base.Nk = dnk.as<int32_t>(); base.S = ds.as<int32_t>(); base.alpha = dal.as<double>();
+            base.rows = S;
+            gl = base; gp = base;
+        }
+        if (f_loo) {
+            HIP_TRY(dlacc.alloc((size_t)chains * kLooAcc * n * 8));
+            HIP_TRY(dlout.alloc((size_t)chains * lout * 8));
+            if (f->loo_trace) HIP_TRY(dltr.alloc((size_t)chains * S * n * 8));
+            const int64_t nb = (N + 255) / 256;
+            for (int c = 0; c < chains; ++c)
+                hipLaunchKernelGGL(k_loo_reset, dim3((unsigned)nb), dim3(256), 0, st, N, dlacc.as<double>() + (size_t)c * kLooAcc * n);
+            HIP_TRY(hipGetLastError());
+            gl.Xb = h->dXb; gl.R = (int)N; gl.acc = dlacc.as<double>(); gl.trace = f->loo_trace ? dltr.as<double>() : nullptr;
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
+        if (f_pred) {
+            const size_t m = (size_t)M;
+            HIP_TRY(dpacc.alloc((size_t)chains * 2 * m * 8));
+            HIP_TRY(dpout.alloc((size_t)chains * m * 8));
+            if (f->predictive_trace) HIP_TRY(dptr.alloc((size_t)chains * S * m * 8));
+            const int64_t nb = (M + 255) / 256;
+            for (int c = 0; c < chains; ++c)
+                hipLaunchKernelGGL(k_predict_reset, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, st, M,
+                                   dpacc.as<double>() + (size_t)c * 2 * m, dpacc.as<double>() + (size_t)c * 2 * m + m);
+            HIP_TRY(hipGetLastError());
+            gp.Xb = h->dXnb; gp.R = (int)M; gp.acc = dpacc.as<double>(); gp.trace = f->predictive_trace ? dptr.as<double>() : nullptr;
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(pfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
+        int folded = 0;
         for (int j = 1; j < nsamples; ++j) {
             g.sweep = (uint32_t)j;
             g.row = j >= burnin ? j - burnin : -1;
@@ -8675,9 +8824,41 @@ int bmm_ensemble_run(int sampler, const int32_t* X, int64_t N, int P, int chains
                 g.hi = lo + ens_rows(P) < (int)N ? lo + ens_rows(P) : (int)N;
                 hipLaunchKernelGGL(fn, dim3((unsigned)pl.groups), dim3((unsigned)pl.cpw * 64), lds, st, g);
             }
+            if (g.row >= 0 && (f_loo || f_pred)) {  // a kept sweep: its state is scored behind the launch that ended it
+                if (f_loo) {
+                    gl.row = g.row; gl.n = folded;
+                    hipLaunchKernelGGL(lfn, dim3((unsigned)pl.groups), dim3((unsigned)pl.cpw * 64), lds, st, gl);
+                }
+                if (f_pred) {
+                    gp.row = g.row; gp.n = folded;
+                    hipLaunchKernelGGL(pfn, dim3((unsigned)pl.groups), dim3((unsigned)pl.cpw * 64), lds, st, gp);
+                }
+                ++folded;
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        if (folded > 0) {  // the outputs, chain by chain, by the kernels of the single-chain summaries
+            const int64_t nbl = (N + 255) / 256, nbp = (M + 255) / 256;
+            for (int c = 0; c < chains; ++c) {
+                if (f_loo) {
+                    double* const out = dlout.as<double>() + (size_t)c * lout;
+                    hipLaunchKernelGGL(k_loo_finish, dim3((unsigned)(nbl < 4096 ? nbl : 4096)), dim3(256), 0, st, N, folded,
+                                       dlacc.as<double>() + (size_t)c * kLooAcc * n, out);
+                    hipLaunchKernelGGL(k_loo_reduce, dim3(1), dim3(1024), 0, st, N, out, out + n * kLooOut);
+                }
+                if (f_pred) {
+                    const double* const ac = dpacc.as<double>() + (size_t)c * 2 * (size_t)M;
+                    hipLaunchKernelGGL(k_predict_finish, dim3((unsigned)(nbp < 4096 ? nbp : 4096)), dim3(256), 0, st, M, pl.Kc, folded, ac,
+                                       ac + (size_t)M, (const double*)nullptr, dpout.as<double>() + (size_t)c * (size_t)M, (double*)nullptr);
+                }
+            }
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipStreamSynchronize(st));
+        if (f) {
+            rc = ens_folds_out(*f, chains, N, M, S, burnin, folded, dlout.as<double>(), dltr.as<double>(), dpout.as<double>(), dptr.as<double>());
+            if (rc) return rc;
+        }
         // the traces: each chain's block is laid out as its caller's matrix is
         for (int c = 0; c < chains; ++c) {
             if (keep) HIP_TRY(hipMemcpy(z_out[c], dzt.as<int32_t>() + (size_t)c * n * S, n * S * 4, hipMemcpyDeviceToHost));
@@ -8699,6 +8880,36 @@ int bmm_ensemble_run(int sampler, const int32_t* X, int64_t N, int P, int chains
             }
         return BMM_OK;
     });
+}
+
+int bmm_ensemble_run(int sampler, const int32_t* X, int64_t N, int P, int chains, const int32_t* const* z0, int nsamples, int K,
+                     double alpha, double beta, double gamma, double a, double b, int burnin, uint64_t seed, int device,
+                     int32_t* const* z_out, int32_t* const* nk_out, double* const* theta_out, double* const* alpha_out,
+                     int32_t* const* z_last) {
+    const RunOptions opts = take_run_options();
+    return ens_run(opts, sampler, X, N, P, chains, z0, nsamples, K, alpha, beta, gamma, a, b, burnin, seed, device, z_out, nk_out,
+                   theta_out, alpha_out, z_last, nullptr);
+}
+
+int bmm_ensemble_run_ex(int sampler, const int32_t* X, int64_t N, int P, int chains, const int32_t* const* z0, int nsamples, int K,
+                        double alpha, double beta, double gamma, double a, double b, int burnin, uint64_t seed, int device,
+                        int32_t* const* z_out, int32_t* const* nk_out, double* const* theta_out, double* const* alpha_out,
+                        int32_t* const* z_last, const bmm_ensemble_folds* folds) {
+    const RunOptions opts = take_run_options();
+    return ens_run(opts, sampler, X, N, P, chains, z0, nsamples, K, alpha, beta, gamma, a, b, burnin, seed, device, z_out, nk_out,
+                   theta_out, alpha_out, z_last, folds);
+}
+
+int bmm_ensemble_fold_plan(int sampler, int64_t N, int P, int K, int chains, int64_t M, int loo, int64_t out[6]) {
+    if (!out) return set_err(BMM_E_ARG, "null argument");
+    EnsPlan pl;
+    const int rc = ens_plan(sampler, N, P, K, chains, pl);
+    if (rc) return rc;
+    if (M < 0) return set_err(BMM_E_ARG, "M must be >= 0");
+    const EnsFoldPlan fp = ens_fold_plan(N, P, chains, M, loo != 0);
+    out[0] = pl.slice; out[1] = pl.cpw; out[2] = fp.acc_bytes; out[3] = fp.loo_row_bytes; out[4] = fp.pred_row_bytes;
+    out[5] = fp.launches;
+    return BMM_OK;
 }
 
 }  // extern "C"

@@ -314,4 +314,180 @@ __global__ __launch_bounds__(kEnsWaves * 64) void k_ens_sweep(EnsArgs a) {
     }
 }
 
+// ---- k_ens_score: the stored state of every chain scored after a kept sweep ----
+// The posterior predictive of new rows (LOO = false, BUILD_PREDICT) or the leave-one-out predictive of the fitted rows
+// (LOO = true, BUILD_LOO) of the state the sweep left, folded into the chain's own accumulators: what k_state_tables and
+// k_score do for one chain, for every chain of the ensemble in one launch.  Placement is k_ens_sweep's -- a wave per
+// chain, cpw chains a workgroup, the same slice of LDS (ens_slice_bytes), no barrier between waves -- but the work is
+// turned round:
+//   the build              every category's constants on its own lane (the kRuleLogs logs of const_arg, one log_ per lane
+//                          and pass; cat_consts), then the (column, role, category) terms round the lanes, one log_ each
+//                          per pass, into T[(d * 4 + role) * Kc + k]: term_arg, term_of against the category's
+//                          denominator, fetched from its lane.  Roles 2, 3 are built for LOO only
+//   rows on lanes          lane l owns row base + l: its plane words, its label.  Nothing here is sequential.  The lane
+//                          walks the categories and the columns; a category's constant is a v_readlane of a uniform
+//                          index, a column's term is read from one of two addresses chosen by the row's bit, so a read
+//                          is a broadcast of at most two words
+//   the order of a score   k_score's: a group's terms added from 0.0 in ascending column order (group_entry), the constant
+//                          added to group 0's sum as write_group_tables folds it in, the groups added from 0.0 in group
+//                          order.  The own label's plain score counts -inf, exactly 0 after expw; its minus-self score,
+//                          in groups of kGroupWm, is one more category, summed last
+//   two passes             the maximum first, then expw_tab(score - max) summed in category order: a score is computed
+//                          twice, the same additions in the same order, and no lane keeps Kc scores (an array indexed by a
+//                          run-time category would be a private segment)
+//   the fold               predict_fold / loo_fold on the chain's accumulators in global memory, a lane per row, no atomics
+struct EnsFoldArgs {
+    const uint32_t* Xb;  // bit planes of the scored rows: word w of row i at Xb[w * R + i]
+    int R;               // scored rows: N (LOO) or the M new rows
+    int N, P, K, Kc, W;  // the chains' shape, as EnsArgs
+    int chains, cpw;
+    int slice_bytes;
+    double beta, gamma;
+    const int32_t* z;     // [chains][N] (LOO)
+    const int32_t* Nk;    // [chains][K]
+    const int32_t* S;     // [chains][K * P]
+    const double* alpha;  // [chains]: after the sweep's update
+    double* acc;          // [chains][kLooAcc][N] (LOO) or [chains][2][M]: run_max, run_sum
+    int n;                // states folded before this one
+    double* trace;        // or null: [chains][rows][R]
+    int row, rows;        // the kept row this state is recorded as, of `rows`
+};
+
+template <bool DP, bool LOO>
+__global__ __launch_bounds__(kEnsWaves * 64) void k_ens_score(EnsFoldArgs a) {
+    extern __shared__ double ens_lds[];
+    const int lane = threadIdx.x & 63;
+    const int wv = ens_uniform((int)(threadIdx.x >> 6));
+    const int c = blockIdx.x * a.cpw + wv;
+    if (wv >= a.cpw || c >= a.chains) return;  // (a whole wave: nothing below waits for another wave)
+    const int N = a.N, P = a.P, K = a.K, Kc = a.Kc, R = a.R;
+    double* const T = reinterpret_cast<double*>(reinterpret_cast<char*>(ens_lds) + wv * a.slice_bytes);
+    double* const E = T + 4 * P * Kc;
+    int32_t* const Sl = reinterpret_cast<int32_t*>(E + 256);
+    const int32_t* const Sg = a.S + (size_t)c * K * P;
+    const int nw = (P + 31) >> 5;
+
+    // stage: the exponential table, the counts, the sizes
+    for (int j = lane; j < 256; j += 64) E[j] = exp256_table()[j];
+    for (int j = lane; j < K * P; j += 64) Sl[j] = Sg[j];
+    const int nk = lane < K ? a.Nk[(size_t)c * K + lane] : 0;
+    const CountRule r{LOO ? BUILD_LOO : BUILD_PREDICT, DP, K, (int64_t)N, a.beta, a.gamma, a.alpha[c]};
+    // the constants of category `lane`
+    double cp, cm, den_p, den_m;
+    {
+        const double ak = rule_ak(r);
+        double v[kRuleLogs];
+#pragma unroll
+        for (int j = 0; j < kRuleLogs; ++j) {
+            double arg;
+            const bool need = const_arg(r, ak, lane, nk, j, arg) && (j == 4 || lane < Kc);
+            const double raw = log_(need ? arg : 1.0);
+            v[j] = need ? raw : 0.0;
+        }
+        const CatConsts cc = cat_consts(r, lane, nk, v);
+        cp = cc.cp; cm = cc.cm; den_p = cc.den_p; den_m = cc.den_m;
+    }
+    __builtin_amdgcn_wave_barrier();
+    // the terms: (column, role) by category, a category's neighbours on neighbouring lanes
+    {
+        constexpr int kRoles = LOO ? 4 : 2;
+        const int total = P * kRoles * Kc;
+        for (int base = 0; base < total; base += 64) {  // (the whole wave takes every trip: __shfl below)
+            const int idx = base + lane;
+            const bool in = idx < total;
+            const int q = in ? idx / Kc : 0;
+            const int k = in ? idx - q * Kc : 0;
+            const int d = q / kRoles, role = q % kRoles;
+            const int64_t n = __shfl(nk, k);
+            const double dp_ = __shfl(den_p, k), dm_ = __shfl(den_m, k);
+            const int64_t s = k < K ? Sl[k * P + d] : 0;
+            double arg;
+            const bool have = term_arg(r, k, role, n, s, arg);
+            const double raw = log_(have ? arg : 1.0);
+            if (in) T[(d * 4 + role) * Kc + k] = term_of(have, raw, term_den(role) ? dm_ : dp_);
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+
+    const int32_t* const zc = a.z + (size_t)c * N;
+    double* const accc = a.acc + (size_t)c * (LOO ? kLooAcc : 2) * R;
+    double* const tr = a.trace ? a.trace + ((size_t)c * a.rows + a.row) * R : nullptr;
+    const int W = a.W;
+    for (int base = 0; base < R; base += 64) {
+        const int i = base + lane;
+        const bool valid = i < R;
+        const int ic = valid ? i : R - 1;
+        uint32_t xw[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) xw[w] = a.Xb[(size_t)(w < nw ? w : nw - 1) * R + ic];  // (a word past the last: the last again, not read)
+        const int z = LOO ? zc[ic] : -1;
+        const bool seated = !LOO || (unsigned)z < (unsigned)K;
+        // the row's own label from the minus-self terms, in groups of kGroupWm
+        double ownv = neg_inf();
+        if (LOO) {
+            const int zs = seated ? z : 0;
+            const double cmz = __shfl(cm, zs);
+            const double* const tb = T + 2 * Kc + zs;
+            double own = 0.0, t = 0.0;
+            int cnt = 0;
+            bool first = true;
+            for (int w = 0; w < nw; ++w) {
+                const uint32_t word = xw[w];
+                const int nb = P - 32 * w < 32 ? P - 32 * w : 32;
+                for (int j = 0; j < nb; ++j) {
+                    const int d = 32 * w + j;
+                    const int bit = (int)((word >> j) & 1u);
+                    t = t + tb[(d * 4 + 1 - bit) * Kc];
+                    ++cnt;
+                    if (cnt == kGroupWm || d == P - 1) { own = own + (first ? cmz + t : t); t = 0.0; cnt = 0; first = false; }
+                }
+            }
+            ownv = seated ? own : neg_inf();
+        }
+        // category k's plain score of this lane's row; k uniform
+        auto score = [&](int k) -> double {
+            const double ck = ens_rl(cp, k);
+            const double* const tb = T + k;
+            double acc = 0.0, t = 0.0;
+            int cnt = 0;
+            bool first = true;
+            for (int w = 0; w < nw; ++w) {
+                const uint32_t word = xw[w];
+                const int nb = P - 32 * w < 32 ? P - 32 * w : 32;
+                for (int j = 0; j < nb; ++j) {
+                    const int d = 32 * w + j;
+                    const int bit = (int)((word >> j) & 1u);
+                    t = t + tb[(d * 4 + 1 - bit) * Kc];
+                    ++cnt;
+                    if (cnt == W || d == P - 1) { acc = acc + (first ? ck + t : t); t = 0.0; cnt = 0; first = false; }
+                }
+            }
+            return LOO && k == z ? neg_inf() : acc;
+        };
+        double mx = ownv;
+        for (int k = 0; k < Kc; ++k) mx = __builtin_fmax(mx, score(k));
+        double tot = 0.0;
+        for (int k = 0; k < Kc; ++k) tot = tot + expw_tab(score(k) - mx, E);
+        if (LOO) tot = tot + expw_tab(ownv - mx, E);
+        const double ld = seated ? mx + log_(tot) : qnan();
+        if (valid) {
+            if (tr) tr[i] = ld;
+            ScoreArgs sa{};
+            sa.rows = R;
+            sa.n = a.n;
+            if (LOO) {
+                // A vector copy of the pointer.  With the scalar pair, AMD clang 22.0.0git (ROCm 7.2.0) dies compiling the LOO
+                // instantiations: a segmentation fault in the greedy register allocator (VirtRegAuxInfo::isRematerializable,
+                // from calculateSpillWeightsAndHints).  A toolchain that compiles `sa.acc = accc` no longer needs this
+                sa.acc = ens_v(accc);
+                loo_fold(sa, i, ld, E);
+            } else {
+                sa.run_max = accc;
+                sa.run_sum = accc + R;
+                predict_fold(sa, i, ld, E);
+            }
+        }
+    }
+}
+
 }  // namespace bmm

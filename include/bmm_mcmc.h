@@ -1733,6 +1733,51 @@ int bmm_ensemble_run(int sampler, const int32_t* X, int64_t N, int P, int chains
                      int32_t* const* z_out, int32_t* const* nk_out, double* const* theta_out, double* const* alpha_out,
                      int32_t* const* z_last);
 
+/* ---- leave-one-out and held-out predictive on every chain of an ensemble.  bmm_ensemble_run_ex
+ * is bmm_ensemble_run with a last argument, the folds asked for; NULL: bmm_ensemble_run itself.  After every kept sweep
+ * (every sweep from `burnin` on; row 0 of a run without burn-in is the start and is not folded) the state of each chain
+ * is scored by its own wavefront (k_ens_score, one launch per fold asked for, all chains) and folded into accumulators
+ * of the chain's own:
+ *   newdata, M   M new rows x P, column-major, every cell 0 or 1 (BMM_E_ARG otherwise; incomplete new rows are not
+ *                offered here): the posterior predictive of "posterior predictive density" above, per chain.
+ *                M = 0: none
+ *   loo          nonzero: the leave-one-out predictive of the fitted rows ("leave-one-out predictive"), per chain
+ * The quantities, their arithmetic and its order are those of bmm_collapsed_run / bmm_dp_run at batch = 1 with the same
+ * option, so chain c's outputs equal, bit for bit, those of the single run under seed + c.  alpha is the chain's value
+ * after the sweep's update.  Outputs, a table of `chains` pointers each (a table that is not asked for may be NULL):
+ *   pred_lppd     [M]                       pred_logdens  S x M column-major, when predictive_trace is nonzero
+ *   loo_log_cpo, loo_ess, loo_lppd, loo_mean, loo_var   [N] each
+ *   loo_ell       S x N column-major, when loo_trace is nonzero
+ *   loo_lpml, loo_min_ess   [chains] doubles;  n_folded: one int, the states folded (the same for every chain and fold)
+ * A trace row that was not folded is NaN; with no state folded every output is NaN and n_folded 0.  The mean
+ * responsibilities are not offered: labels switch between chains.  An armed bmm_set_* option is refused by both entries.
+ * bmm_ensemble_fold_plan is pure bookkeeping, no device: out = {LDS bytes per chain of the scorer (the sweep's slice),
+ * chains per workgroup, device bytes of the accumulators and the finish kernels' outputs (loo: chains * (12 N + 8)
+ * doubles; newdata: chains * 3 M doubles and ceil(P / 32) * M plane words), device bytes per kept sweep of the ell trace
+ * (chains * N doubles) and of the logdens trace (chains * M doubles), launches added per kept sweep}; bmm_ensemble_plan's
+ * refusals of a shape, and BMM_E_ARG for M < 0. */
+typedef struct {
+    const int32_t* newdata;
+    int64_t M;
+    int32_t loo, loo_trace, predictive_trace;
+    double* const* pred_lppd;
+    double* const* pred_logdens;
+    double* const* loo_log_cpo;
+    double* const* loo_ess;
+    double* const* loo_lppd;
+    double* const* loo_mean;
+    double* const* loo_var;
+    double* const* loo_ell;
+    double* loo_lpml;
+    double* loo_min_ess;
+    int32_t* n_folded;
+} bmm_ensemble_folds;
+int bmm_ensemble_fold_plan(int sampler, int64_t N, int P, int K, int chains, int64_t M, int loo, int64_t out[6]);
+int bmm_ensemble_run_ex(int sampler, const int32_t* X, int64_t N, int P, int chains, const int32_t* const* z0, int nsamples, int K,
+                        double alpha, double beta, double gamma, double a, double b, int burnin, uint64_t seed, int device,
+                        int32_t* const* z_out, int32_t* const* nk_out, double* const* theta_out, double* const* alpha_out,
+                        int32_t* const* z_last, const bmm_ensemble_folds* folds);
+
 /* ---- device self-checks used by the parity tests (op: 0 log, 1 exp, 2 div by in2, 3 sqrt,
  * 4 the draw's weight exponential expw, 5 lgamma_; elementwise over n doubles, evaluated on the GPU with the
  * spec arithmetic) */
